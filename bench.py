@@ -7,7 +7,7 @@ batch of synthetic per-step inputs already resident in HBM.  Workload at N=1: BA
 fp64).  Multi-GPU: every rank owns the same number of plants (weak scaling), no collective in the
 data path; one RCCL all-gather of the observation block after the timed region (episode end).
 
-Launch:  python bench.py --gpus 1 --steps K --warmup W
+Launch:  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 Rank 0 prints ONE JSON line.
 """
@@ -167,6 +167,26 @@ def step_kernel_name(n, storage="f64", forced=None, mode="full", maintenance=Fal
     return "npb_step%s_kernel" % m
 
 
+DUMP_BYTES = 64_000_000   # --dump-outputs writes at most this much in all
+
+
+def last_step_outputs(obs, reward, done, info, lo, seed=0):
+    """{name: float64 array} of what one step handed its caller -- obs, reward, done and every info column (info_<key>) -- as
+    host copies.  Rows are plants; when all of them would not fit in DUMP_BYTES, a sample drawn with a fixed seed (the same
+    rows for the same plant count).  "plant_index" holds the global ids of the rows."""
+    import torch
+    cols = [("obs", obs), ("reward", reward), ("done", done)] + [("info_" + k, v) for k, v in info.items()]
+    n = obs.shape[0]
+    width = 1 + sum(1 if v.dim() == 1 else v.shape[1] for _, v in cols)      # float64 values per plant, plant_index included
+    keep = (DUMP_BYTES - 128 * (len(cols) + 1)) // (8 * width)                # 128 B: an .npy header
+    rows = np.arange(n) if n <= keep else np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+    idx = torch.from_numpy(rows).to(obs.device)
+    out = {"plant_index": (lo + rows).astype(np.float64)}
+    for name, v in cols:
+        out[name] = v.index_select(0, idx).double().cpu().numpy()
+    return out
+
+
 def past_the_knee(n, device, storage, bytes_per_plant, K=40):
     import ctypes
     import torch
@@ -210,7 +230,13 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="no stepping, no GPU: the ranks rendezvous (NPB_BENCH_BACKEND, e.g. gloo), all-reduce one number and rank 0 prints "
                          "{n_gpus, launch_check: true} -- a test of the launcher path on a box without GPUs, not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned to its caller (obs, reward, done, every info "
+                         "column) as DIR/<name>.npy in float64: rank 0's plants, a fixed seeded sample of them if all would exceed "
+                         "64 MB, with their global ids in DIR/plant_index.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Run plainly as `python bench.py --gpus N`: nobody has set up the ranks.  Start them here -- N fresh worker processes
@@ -335,6 +361,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    # the last timed step's outputs are the env's own buffers, which the replays below overwrite: copy them now
+    dumped = last_step_outputs(obs, rew, done, info, lo) if (args.dump_outputs and rank == 0) else None
 
     # roofline leg: the step kernel's own duration, HIP events on the stream it is launched on (torch's current
     # stream), one pair per launch, over a replay of the same steps (outside the timed region so that event
@@ -435,6 +463,11 @@ def main():
             # the same kernel with the working set well past the 256 MB Infinity Cache (twice the plants): what the fraction is
             # when nothing of the state survives in the memory-side cache between two steps
             out["roofline"]["past_the_cache_knee"] = past_the_knee(2 * n, local_rank, args.storage, bytes_per_plant)
+        if dumped is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+            out["dump_outputs"] = {"dir": args.dump_outputs, "plants": len(dumped["plant_index"]), "after_steps": W + K, "files": sorted(dumped)}
         print(json.dumps(out), flush=True)
     if distributed:
         dist.barrier()
