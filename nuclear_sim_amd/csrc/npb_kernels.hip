@@ -51,6 +51,7 @@ extern "C" __attribute__((visibility("default"))) int npb_debug_set_stamp_buffer
 #include "npd_maintenance.h"
 #include "npd_init.h"
 #include "npd_reset.h"
+#include "npd_step.h"
 #include "npb_kernels.h"
 
 #ifndef NPD_OUT_STORE
@@ -319,22 +320,6 @@ __device__ __forceinline__ void npd_store_rows(const double *row, double *__rest
 
 __device__ __forceinline__ double npd_sel3(int i, double a0, double a1, double a2) { return (i == 0) ? a0 : ((i == 1) ? a1 : a2); }
 
-/* get_observation  sim.py:290-333 (primary part) */
-__device__ __forceinline__ void npd_obs_primary(const npb_prim_t &s, double *obs) {
-  obs[0] = s.neutron_flux / 1e12;
-  obs[1] = s.fuel_temperature / 1000;
-  obs[2] = s.coolant_temperature / 300;
-  obs[3] = s.coolant_pressure / 20;
-  obs[4] = s.coolant_flow_rate / 50000;
-  obs[5] = s.steam_temperature / 300;
-  obs[6] = s.steam_pressure / 10;
-  obs[7] = s.steam_flow_rate / 3000;
-  obs[8] = s.control_rod_position / 100;
-  obs[9] = s.steam_valve_position / 100;
-  obs[10] = s.power_level / 100;
-  obs[11] = (double)(s.scram_status != 0);
-}
-
 /* info["reactivity_components"] (sim.py:205): the second block of the info buffer, only for a caller that asked
  * (params.info_reactivity_components) under the reactor heat source -- include/npb.h NPB_RHO_* */
 __device__ __forceinline__ void npd_store_reactivity_components(const npb_params_t &P, const double *rho, double *__restrict__ info_out,
@@ -360,12 +345,7 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_step_primary_kernel(
   NPD_SEGMENT(f64, N, block_base);
   const size_t p = block_base + threadIdx.x;
   const bool live = p < (size_t)n_plants;
-  npd_inputs_t in;
-  in.action = (live && action) ? action[p] : 8;
-  in.magnitude = (live && magnitude) ? magnitude[p] : 1.0;
-  in.power_setpoint = (live && setpoint) ? setpoint[p] : NAN;
-  in.noise_z = (live && noise_z) ? noise_z[p] : 0.0;
-  in.cooling_water_temp = NAN;
+  const npd_inputs_t in = npd_step_inputs(live, p, action, magnitude, setpoint, noise_z, nullptr);
   npb_prim_t s;
   NPD_LOAD(PRIM, npb_prim_t, s, 0);
   if (P.heat_source != NPB_HEAT_EXTERNAL && !isnan(in.power_setpoint)) s.hs_setpoint_percent = npd_clip(in.power_setpoint, 0.0, 150.0);
@@ -379,14 +359,8 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_step_primary_kernel(
   npd_obs_primary(s, obs);
 #pragma unroll
   for (int k = 12; k < NPB_OBS_DIM; k++) obs[k] = 0.0;
-  /* calculate_reward(None)  sim.py:503-519 */
-  double power_reward = -fabs(s.power_level - 100) / 100;
-  double temp_penalty = 0, pressure_penalty = 0;
-  if (s.fuel_temperature > 800) temp_penalty = -(s.fuel_temperature - 800) / 100;
-  if (s.coolant_pressure > 16) pressure_penalty = -(s.coolant_pressure - 16);
-  double scram_penalty = s.scram_status ? -100 : 0;
   if (live) {
-    if (reward_out) reward_out[p] = power_reward + temp_penalty + pressure_penalty + scram_penalty;
+    if (reward_out) reward_out[p] = npd_base_reward(s);
     if (done_out) done_out[p] = (uint8_t)scram_fired;
     if (trip_out) trip_out[p] = (s.scram_status ? NPB_TRIP_SCRAM : 0u) | (scram_fired ? NPB_TRIP_SCRAM_FIRED : 0u) | (nan_reset ? NPB_TRIP_NAN_RESET : 0u);
   }
@@ -394,9 +368,7 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_step_primary_kernel(
   if (info_out) {
 #pragma unroll
     for (int k = 0; k < NPB_INFO_DIM; k++) info[k] = NAN;
-    info[NPB_INFO_THERMAL_POWER] = s.thermal_power_mw;
-    info[NPB_INFO_REACTIVITY_PCM] = s.total_reactivity_pcm;
-    info[NPB_INFO_TIME] = s.sim_time;
+    npd_info_primary(info, s.thermal_power_mw, s.total_reactivity_pcm, s.sim_time);
     npd_store_rows<NPB_INFO_DIM>(info, info_out, lds, block_base, (size_t)n_plants);
   }
 }
@@ -619,12 +591,6 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_observe_kernel(int mode, int n_p
     npd_store_rows<NPB_OBS_DIM>(obs, obs_out, lds, block_base, (size_t)n_plants);
     return;
   }
-  obs[12] = NPD_F64_COL(SEC, npb_sec_t, electrical_power_output, 0) / 1100;
-  obs[13] = NPD_F64_COL(SEC, npb_sec_t, thermal_efficiency, 0) / 0.35;
-  obs[14] = NPD_F64_COL(SEC, npb_sec_t, total_steam_flow, 0) / 1665;
-  obs[15] = NPD_F64_COL(SEC, npb_sec_t, load_demand, 0) / 100;
-  obs[16] = 227.0 / 250;
-  obs[17] = NPD_F64_COL(SEC, npb_sec_t, cooling_water_temperature, 0) / 35;
   double fwf, fwp; int fwa;
   if (mode == NPB_MODE_PRIMARY_SG) { fwf = NPD_F64_COL(SEC, npb_sec_t, total_feedwater_flow, 0); fwp = 0.0; fwa = 1; }
   else {
@@ -632,10 +598,9 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_observe_kernel(int mode, int n_p
     fwp = NPD_F64_COL(FW, npb_fw_t, total_power_consumption, 0);
     fwa = NPD_I32_COL(FW, npb_fw_t, system_availability, 0) != 0;
   }
-  obs[18] = fwf / 1665;
-  obs[19] = fwp / 40;
-  obs[20] = (double)fwa;
-  obs[21] = fwf / 1665;
+  npd_obs_secondary(obs, s.steam_flow_rate, NPD_F64_COL(SEC, npb_sec_t, electrical_power_output, 0), NPD_F64_COL(SEC, npb_sec_t, thermal_efficiency, 0),
+                    NPD_F64_COL(SEC, npb_sec_t, total_steam_flow, 0), NPD_F64_COL(SEC, npb_sec_t, load_demand, 0),
+                    NPD_F64_COL(SEC, npb_sec_t, cooling_water_temperature, 0), fwf, fwp, (double)fwa);
   npd_store_rows<NPB_OBS_DIM>(obs, obs_out, lds, block_base, (size_t)n_plants);
 }
 

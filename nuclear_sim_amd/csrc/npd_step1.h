@@ -29,12 +29,7 @@ __global__ __launch_bounds__(NPB_WAVE) void NPD_STEP1_KERNEL(
 #endif
 
   /* per-step inputs first (plain loads), then the first staged group: primary + secondary-level scalars */
-  npd_inputs_t in;
-  in.action = (live && action) ? action[p] : 8;
-  in.magnitude = (live && magnitude) ? magnitude[p] : 1.0;
-  in.power_setpoint = (live && setpoint) ? setpoint[p] : NAN;
-  in.noise_z = (live && noise_z) ? noise_z[p] : 0.0;
-  in.cooling_water_temp = (live && cw_temp) ? cw_temp[p] : NAN;
+  const npd_inputs_t in = npd_step_inputs(live, p, action, magnitude, setpoint, noise_z, cw_temp);
   /* automatic maintenance on (npd_maintenance.h, "the threshold screen inside the step kernels"): lane l fetches entry l of the
    * folded threshold table from the kernel-argument segment; it goes to the last 512 B of the staging region -- no staged
    * section reaches that far -- once the first staged group has landed, and the pump phase reads it from there */
@@ -118,35 +113,18 @@ __global__ __launch_bounds__(NPB_WAVE) void NPD_STEP1_KERNEL(
     }
     scram_status = s.scram_status;
     npd_obs_primary(s, obs); /* obs[7] is patched after the secondary side has produced the steam flow */
-    /* base reward, sim.py:503-519 */
-    double power_reward = -fabs(s.power_level - 100) / 100;
-    double temp_penalty = 0, pressure_penalty = 0;
-    if (s.fuel_temperature > 800) temp_penalty = -(s.fuel_temperature - 800) / 100;
-    if (s.coolant_pressure > 16) pressure_penalty = -(s.coolant_pressure - 16);
-    double scram_penalty = s.scram_status ? -100 : 0;
-    base_reward = power_reward + temp_penalty + pressure_penalty + scram_penalty;
-    info[NPB_INFO_THERMAL_POWER] = s.thermal_power_mw;
-    info[NPB_INFO_REACTIVITY_PCM] = s.total_reactivity_pcm;
-    info[NPB_INFO_TIME] = s.sim_time;
+    base_reward = npd_base_reward(s);
+    npd_info_primary(info, s.thermal_power_mw, s.total_reactivity_pcm, s.sim_time);
   }
 
   /* ================= secondary prelude (secondary/__init__.py:371-453) ================= */
   if (!isnan(in.cooling_water_temp)) cooling_water_temperature = in.cooling_water_temp; /* sim.py:138-139 */
-  double actual_feedwater_temp;
-  {
-    double estimated_feedwater_temp = 40.0 + 187.0;
-    double alpha = 0.1;
-    actual_feedwater_temp = (alpha * estimated_feedwater_temp + (1 - alpha) * prev_feedwater_temp);
-  }
+  const double actual_feedwater_temp = npd_feedwater_temp(prev_feedwater_temp);
   double primary_thermal_power = 0.0;
 #pragma unroll
   for (int i = 0; i < NPB_NUM_SG; i++) primary_thermal_power += c.thermal_power[i];
-  double load_demand_fraction = npd_pymin(1.0, primary_thermal_power / 3000.0);
-  load_demand_fraction = npd_pymax(load_demand_fraction, 0.2);
-  if (!has_prev) { /* :447-453 hard-coded first-step values, not the SG initial conditions */
-#pragma unroll
-    for (int i = 0; i < NPB_NUM_SG; i++) { prev_levels[i] = 12.5; prev_flows[i] = 555.0 * load_demand_fraction; prev_quals[i] = 0.99; }
-  }
+  const double load_demand_fraction = npd_load_demand_fraction(primary_thermal_power);
+  if (!has_prev) npd_first_step_sg_conditions(load_demand_fraction, prev_levels, prev_flows, prev_quals);
 
 #ifdef NPD_STEP1_DIAG
   NPD_DIAG(st, NPB_DIAG_FW_AVG_SG_LEVEL, (0.0 + prev_levels[0] + prev_levels[1] + prev_levels[2]) / 3);
@@ -363,15 +341,7 @@ __global__ __launch_bounds__(NPB_WAVE) void NPD_STEP1_KERNEL(
                        load_demand, 0.007, dt / 60.0, &tr);
     NPD_STAMP(18);
     /* ================= phase 4: condenser (:591-621) ================= */
-    double lp_exhaust_quality = 0.90;
-    {
-      double h_f = npd_cond_hf(tr.condenser_pressure), h_g = npd_cond_hg(tr.condenser_pressure);
-      double h_fg = h_g - h_f;
-      if (h_fg > 0) {
-        lp_exhaust_quality = (tr.lp6_outlet_enthalpy - h_f) / h_fg;
-        lp_exhaust_quality = npd_pymax(0.0, npd_pymin(1.0, lp_exhaust_quality));
-      }
-    }
+    const double lp_exhaust_quality = npd_lp_exhaust_quality(tr.condenser_pressure, tr.lp6_outlet_enthalpy);
     npd_condenser_result_t cr;
     {
       NPD_ST_STORE_ELIDE(TURB, npb_turb_t, t, t_old, 0);
@@ -411,20 +381,11 @@ __global__ __launch_bounds__(NPB_WAVE) void NPD_STEP1_KERNEL(
     NPD_ST_STORE_ELIDE(CHEM, npb_chem_t, ch0, ch0_old, 0);
     NPD_ST_STORE_ELIDE(PH, npb_ph_t, ph, ph_old, 0);
     NPD_STAMP(20);
-    /* ================= electrical-power gates (:750-932) ================= */
-    double turbine_electrical_power = tr.electrical_power_net;
+    /* ================= electrical-power gates ================= */
     turbine_gross_power = tr.electrical_power_gross;
     turbine_efficiency = tr.overall_efficiency; turbine_hp_power = tr.hp_power; turbine_lp_power = tr.lp_power;
-    total_system_heat_rejection = (primary_thermal_power - turbine_electrical_power) * 1e6;
-    double power_reduction_factor = 1.0;
-    if (fw_total_flow < 300.0) power_reduction_factor = 0.0;
-    if (power_reduction_factor > 0.0) {
-      if (sg_total_steam < (300.0 * 0.5)) power_reduction_factor *= 0.1;
-      if (sg_avg_pressure < (1.0 * 0.5)) power_reduction_factor *= 0.1;
-      if (primary_thermal_power > (primary_thermal_power * 1.1)) power_reduction_factor = 0.0;
-    }
-    electrical_power = turbine_electrical_power * power_reduction_factor;
-    thermal_efficiency = (primary_thermal_power > 0) ? electrical_power / primary_thermal_power : 0.0;
+    const npd_power_t pw = npd_power_gates(tr.electrical_power_net, primary_thermal_power, fw_total_flow, sg_total_steam, sg_avg_pressure);
+    electrical_power = pw.electrical_power; thermal_efficiency = pw.thermal_efficiency; total_system_heat_rejection = pw.heat_rejection;
     if (tr.trip_active) trip_flags |= NPB_TRIP_TURBINE;
   } else {
     fw_total_flow = sg_total_steam; /* config-2 mode: feedwater == steam demand */
@@ -435,44 +396,19 @@ __global__ __launch_bounds__(NPB_WAVE) void NPD_STEP1_KERNEL(
   NPD_ST_F64_ELIDE(SEC, npb_sec_t, cooling_water_temperature, 0, 0, cooling_water_temperature, cw_old);
   NPD_ST_F64(SEC, npb_sec_t, operating_hours, 0, 0) = operating_hours + dt / 3600.0;
   { /* the section's outputs and flags: narrow members, stored as whole columns */
-    npb_sec_t so;
-    so.electrical_power_output = electrical_power; so.thermal_efficiency = thermal_efficiency;
-    so.total_steam_flow = sg_total_steam; so.total_heat_transfer = sg_total_thermal; so.total_feedwater_flow = fw_total_flow;
-    so.load_demand = load_demand; so.sg_avg_pressure = sg_avg_pressure; so.sg_avg_temperature = sg_avg_temperature;
-    so.sg_avg_quality = sg_avg_quality; so.has_previous_sg_conditions = 1; so.sg_system_availability = sg_system_availability;
+    const npb_sec_t so = npd_sec_outputs(electrical_power, thermal_efficiency, sg_total_steam, sg_total_thermal, fw_total_flow, load_demand,
+                                         sg_avg_pressure, sg_avg_temperature, sg_avg_quality, sg_system_availability);
     NPD_ST_STORE_NARROW(SEC, npb_sec_t, so, 0);
   }
 
-  /* ================= _apply_secondary_to_primary_feedback  sim.py:429-498 ================= */
-  double heat_removal_factor = sg_total_steam / 1665.0;
-  if (!fw_available) heat_removal_factor *= 0.5;
+  /* ================= feedback into the primary state ================= */
   NPD_ST_F64(PRIM, npb_prim_t, steam_flow_rate, 0, 0) = sg_total_steam;
-  NPD_ST_F64(PRIM, npb_prim_t, last_heat_removal_factor, 0, 0) = heat_removal_factor;
+  NPD_ST_F64(PRIM, npb_prim_t, last_heat_removal_factor, 0, 0) = npd_heat_removal_factor(sg_total_steam, fw_available);
 
   /* ================= observation / reward / done / flags / info ================= */
-  obs[7] = sg_total_steam / 3000;
-  obs[12] = electrical_power / 1100;
-  obs[13] = thermal_efficiency / 0.35;
-  obs[14] = sg_total_steam / 1665;
-  obs[15] = load_demand / 100;
-  obs[16] = 227.0 / 250;
-  obs[17] = cooling_water_temperature / 35;
-  obs[18] = fw_total_flow / 1665;
-  obs[19] = fw_total_power / 40;
-  obs[20] = (double)fw_available;
-  obs[21] = fw_total_flow / 1665;
-
-  /* calculate_reward  sim.py:521-542 */
-  double efficiency_reward = (thermal_efficiency - 0.30) * 10;
-  double target_electrical_power = load_demand / 100.0 * 1100.0;
-  double electrical_reward = -fabs(electrical_power - target_electrical_power) / 100;
-  double steam_pressure_penalty = 0;
-  if (sg_avg_pressure < 5.0 || sg_avg_pressure > 8.0) steam_pressure_penalty = -fabs(sg_avg_pressure - 6.895) * 5;
-  double condenser_penalty = 0;
-  if (condenser_pressure > 0.01) condenser_penalty = -(condenser_pressure - 0.007) * 100;
-  double secondary_reward = efficiency_reward + electrical_reward + steam_pressure_penalty + condenser_penalty;
-  double reward = base_reward + secondary_reward * 0.5;
-
+  npd_obs_secondary(obs, sg_total_steam, electrical_power, thermal_efficiency, sg_total_steam, load_demand, cooling_water_temperature,
+                    fw_total_flow, fw_total_power, (double)fw_available);
+  const double reward = npd_reward(base_reward, thermal_efficiency, load_demand, electrical_power, sg_avg_pressure, condenser_pressure);
   if (scram_status) trip_flags |= NPB_TRIP_SCRAM;
   if (scram_fired) trip_flags |= NPB_TRIP_SCRAM_FIRED;
   if (nan_reset) trip_flags |= NPB_TRIP_NAN_RESET;
@@ -488,18 +424,9 @@ __global__ __launch_bounds__(NPB_WAVE) void NPD_STEP1_KERNEL(
   NPD_STAMP(21);
   if (obs_out) npd_store_rows<NPB_OBS_DIM>(obs, obs_out, lds, block_base, (size_t)n_plants);
   if (info_out) {
-    /* info  sim.py:199-250 with the non-finite substitutions of :231-240 */
-    info[NPB_INFO_ELECTRICAL_POWER] = isfinite(electrical_power) ? electrical_power : 0.0;
-    info[NPB_INFO_THERMAL_EFFICIENCY] = npd_pymax(0.0, npd_pymin(isfinite(thermal_efficiency) ? thermal_efficiency : 0.0, 0.35));
-    info[NPB_INFO_STEAM_FLOW] = isfinite(sg_total_steam) ? sg_total_steam : 1665.0;
-    info[NPB_INFO_STEAM_PRESSURE] = isfinite(sg_avg_pressure) ? sg_avg_pressure : 6.895;
-    info[NPB_INFO_CONDENSER_PRESSURE] = isfinite(condenser_pressure) ? condenser_pressure : 0.007;
-    info[NPB_INFO_CONDENSER_HEAT_REJECTION] = isfinite(total_system_heat_rejection) ? total_system_heat_rejection : 0.0;
-    info[NPB_INFO_FEEDWATER_FLOW] = fw_total_flow;
-    info[NPB_INFO_SG_HEAT_TRANSFER] = sg_total_thermal; info[NPB_INFO_TURBINE_POWER] = turbine_gross_power;
-    info[NPB_INFO_FEEDWATER_POWER] = fw_total_power; info[NPB_INFO_PRIMARY_THERMAL_POWER] = primary_thermal_power;
-    info[NPB_INFO_TURBINE_EFFICIENCY] = turbine_efficiency;
-    info[NPB_INFO_TURBINE_HP_POWER] = turbine_hp_power; info[NPB_INFO_TURBINE_LP_POWER] = turbine_lp_power;
+    npd_info_secondary(info, electrical_power, thermal_efficiency, sg_total_steam, sg_avg_pressure, condenser_pressure, total_system_heat_rejection,
+                       fw_total_flow, sg_total_thermal, turbine_gross_power, fw_total_power, primary_thermal_power, turbine_efficiency,
+                       turbine_hp_power, turbine_lp_power);
     npd_store_rows<NPB_INFO_DIM>(info, info_out, lds, block_base, (size_t)n_plants);
   }
   NPD_STAMP(22);

@@ -353,12 +353,7 @@ __device__ __forceinline__ void npd_step2_body(
     npd_maint_due_t maint_due = {};
     npd_u32x4 maint_cache01 = {0, 0, 0, 0};       /* {mask, until} of this wave's pumps 0, 1 (npd_maintenance.h) */
     if (maint) { npd_maint_due_load(&maint_due, f64, N, p); maint_cache01 = npd_maint_cache_fetch(MC, p, 0); }
-    npd_inputs_t in;
-    in.action = (live && action) ? action[p] : 8;
-    in.magnitude = (live && magnitude) ? magnitude[p] : 1.0;
-    in.power_setpoint = (live && setpoint) ? setpoint[p] : NAN;
-    in.noise_z = (live && noise_z) ? noise_z[p] : 0.0;
-    in.cooling_water_temp = (live && cw_temp) ? cw_temp[p] : NAN;
+    const npd_inputs_t in = npd_step_inputs(live, p, action, magnitude, setpoint, noise_z, cw_temp);
     double base_reward, load_demand, cooling_water_temperature, primary_thermal_power = 0.0;
     int scram_fired, nan_reset, scram_status;
     double thermal_power_info, reactivity_info, time_info;
@@ -396,12 +391,7 @@ __device__ __forceinline__ void npd_step2_body(
       s.sim_time += dt;
       load_demand = s.power_level;
       scram_status = s.scram_status;
-      double power_reward = -fabs(s.power_level - 100) / 100;
-      double temp_penalty = 0, pressure_penalty = 0;
-      if (s.fuel_temperature > 800) temp_penalty = -(s.fuel_temperature - 800) / 100;
-      if (s.coolant_pressure > 16) pressure_penalty = -(s.coolant_pressure - 16);
-      double scram_penalty = s.scram_status ? -100 : 0;
-      base_reward = power_reward + temp_penalty + pressure_penalty + scram_penalty;
+      base_reward = npd_base_reward(s);
       thermal_power_info = s.thermal_power_mw; reactivity_info = s.total_reactivity_pcm; time_info = s.sim_time;
       s.has_heat_removal_factor = 1;
       NPD_ST_STORE_ELIDE_PRIM(s, s_old);
@@ -426,13 +416,9 @@ __device__ __forceinline__ void npd_step2_body(
       prev_quals[i] = (double)NPD_ST_F64(SEC, npb_sec_t, prev_sg_qualities, 0, i);
     }
     if (!isnan(in.cooling_water_temp)) cooling_water_temperature = in.cooling_water_temp;
-    const double actual_feedwater_temp = (0.1 * (40.0 + 187.0) + (1 - 0.1) * prev_feedwater_temp);
-    double load_demand_fraction = npd_pymin(1.0, primary_thermal_power / 3000.0);
-    load_demand_fraction = npd_pymax(load_demand_fraction, 0.2);
-    if (!has_prev) {
-#pragma unroll
-      for (int i = 0; i < NPB_NUM_SG; i++) { prev_levels[i] = 12.5; prev_flows[i] = 555.0 * load_demand_fraction; prev_quals[i] = 0.99; }
-    }
+    const double actual_feedwater_temp = npd_feedwater_temp(prev_feedwater_temp);
+    const double load_demand_fraction = npd_load_demand_fraction(primary_thermal_power);
+    if (!has_prev) npd_first_step_sg_conditions(load_demand_fraction, prev_levels, prev_flows, prev_quals);
     /* ---- feedwater control, and what wave B needs to start its pumps and its steam generator */
     npb_fw_t fw;
     NPD_ST_LOAD(FW, npb_fw_t, fw, 0);
@@ -639,22 +625,13 @@ __device__ __forceinline__ void npd_step2_body(
       *NPD_NP(int32_t, NPD_SEC_COL(TURB, 0) + NC + 4 / NPD_NPC, 4 % NPD_NPC) = t.trip_active;
       *NPD_NP(int32_t, NPD_SEC_COL(TURB, 0) + NC + 5 / NPD_NPC, 5 % NPD_NPC) = t.trip_latched_mask;
     }
-    /* ---- electrical-power gates (secondary/__init__.py:750-932) */
-    const double turbine_electrical_power = t.total_power_output * 0.98;
-    const double total_system_heat_rejection = (primary_thermal_power - turbine_electrical_power) * 1e6;
-    double power_reduction_factor = 1.0;
-    if (fw_total_flow < 300.0) power_reduction_factor = 0.0;
-    if (power_reduction_factor > 0.0) {
-      if (sg_total_steam < (300.0 * 0.5)) power_reduction_factor *= 0.1;
-      if (sg_avg_pressure < (1.0 * 0.5)) power_reduction_factor *= 0.1;
-      if (primary_thermal_power > (primary_thermal_power * 1.1)) power_reduction_factor = 0.0;
-    }
-    const double electrical_power = turbine_electrical_power * power_reduction_factor;
-    const double thermal_efficiency = (primary_thermal_power > 0) ? electrical_power / primary_thermal_power : 0.0;
+    /* ---- electrical-power gates */
+    const npd_power_t pw = npd_power_gates(t.total_power_output * 0.98, primary_thermal_power, fw_total_flow, sg_total_steam, sg_avg_pressure);
+    const double electrical_power = pw.electrical_power, thermal_efficiency = pw.thermal_efficiency;
     if (t.trip_active) trip_flags |= NPB_TRIP_TURBINE;
     /* what wave B needs for reward and info */
     XW(X_TAIL + 0, base_reward); XW(X_TAIL + 1, electrical_power); XW(X_TAIL + 2, thermal_efficiency); XW(X_TAIL + 3, load_demand);
-    XW(X_TAIL + 4, sg_avg_pressure); XW(X_TAIL + 5, sg_total_steam); XW(X_TAIL + 6, fw_total_flow); XW(X_TAIL + 7, total_system_heat_rejection);
+    XW(X_TAIL + 4, sg_avg_pressure); XW(X_TAIL + 5, sg_total_steam); XW(X_TAIL + 6, fw_total_flow); XW(X_TAIL + 7, pw.heat_rejection);
     XW(X_TAIL + 8, thermal_power_info); XW(X_TAIL + 9, reactivity_info); XW(X_TAIL + 10, time_info);
     XW(X_TAIL + 11, sg_total_thermal); XW(X_TAIL + 12, sg_avg_temperature); XW(X_TAIL + 13, sg_avg_quality);
     XW(X_TAIL + 14, (double)(sg_system_availability | (fw_available << 1))); XW(X_TAIL + 15, prev_feedwater_temp); XW(X_TAIL + 16, cw_old);
@@ -675,13 +652,11 @@ __device__ __forceinline__ void npd_step2_body(
     obs[9] = (double)NPD_ST_F64(PRIM, npb_prim_t, steam_valve_position, 0, 0) / 100;
     obs[10] = load_demand / 100;                 /* load_demand IS state.power_level (sim.py:161) */
     obs[11] = (double)(scram_status != 0);
-    obs[7] = sg_total_steam / 3000;
-    obs[12] = electrical_power / 1100; obs[13] = thermal_efficiency / 0.35; obs[14] = sg_total_steam / 1665;
-    obs[15] = load_demand / 100; obs[16] = 227.0 / 250; obs[17] = cooling_water_temperature / 35;
-    obs[18] = fw_total_flow / 1665; obs[19] = fw_total_power / 40; obs[20] = (double)fw_available; obs[21] = fw_total_flow / 1665;
+    npd_obs_secondary(obs, sg_total_steam, electrical_power, thermal_efficiency, sg_total_steam, load_demand, cooling_water_temperature,
+                      fw_total_flow, fw_total_power, (double)fw_available);
     if (scram_status) trip_flags |= NPB_TRIP_SCRAM;
-    if (scram_fired) trip_flags |= NPB_TRIP_SCRAM_FIRED;
-    if (nan_reset) trip_flags |= NPB_TRIP_NAN_RESET;
+  if (scram_fired) trip_flags |= NPB_TRIP_SCRAM_FIRED;
+  if (nan_reset) trip_flags |= NPB_TRIP_NAN_RESET;
     if (live) {
       if (done_out) __builtin_nontemporal_store((uint8_t)scram_fired, &done_out[p]);
       if (trip_out) __builtin_nontemporal_store(trip_flags, &trip_out[p]);
@@ -846,64 +821,36 @@ __device__ __forceinline__ void npd_step2_body(
     NPD2_SYNCJ(9);                                                                                     /* #7 */
     const double effective_steam_flow = XR(X_EFFLOW), lp6_outlet_enthalpy = XR(X_LP6H), cooling_water_temperature = XR(X_CWT);
     /* ---- condenser (secondary/__init__.py:591-621) */
-    double lp_exhaust_quality = 0.90;
-    {
-      double h_f = npd_cond_hf(0.007), h_g = npd_cond_hg(0.007);
-      double h_fg = h_g - h_f;
-      if (h_fg > 0) {
-        lp_exhaust_quality = (lp6_outlet_enthalpy - h_f) / h_fg;
-        lp_exhaust_quality = npd_pymax(0.0, npd_pymin(1.0, lp_exhaust_quality));
-      }
-    }
+    const double lp_exhaust_quality = npd_lp_exhaust_quality(0.007, lp6_outlet_enthalpy);
     npd_condenser_result_t cr;
     npd_condenser_update(&cd, &chc, 0.007, effective_steam_flow, lp_exhaust_quality, 45000.0, cooling_water_temperature, 1.2, 185.0, tdt, &cr);
     NPD_ST_STORE_ELIDE(COND, npb_cond_t, cd, cd_old, 0);
     NPD_ST_STORE_ELIDE(CHEM, npb_chem_t, chc, chc_old, 1);
     const double condenser_pressure = cr.condenser_pressure;
     NPD2_SYNCJ(11);                                                                                     /* #9 */
-    /* ---- reward (sim.py:521-542) and info (sim.py:199-250) */
+    /* ---- reward and info */
     const double base_reward = XR(X_TAIL + 0), electrical_power = XR(X_TAIL + 1), thermal_efficiency = XR(X_TAIL + 2), load_demand = XR(X_TAIL + 3);
     const double sg_avg_pressure = XR(X_TAIL + 4), sg_total_steam = XR(X_TAIL + 5), fw_total_flow_t = XR(X_TAIL + 6), heat_rejection = XR(X_TAIL + 7);
-    double efficiency_reward = (thermal_efficiency - 0.30) * 10;
-    double target_electrical_power = load_demand / 100.0 * 1100.0;
-    double electrical_reward = -fabs(electrical_power - target_electrical_power) / 100;
-    double steam_pressure_penalty = 0;
-    if (sg_avg_pressure < 5.0 || sg_avg_pressure > 8.0) steam_pressure_penalty = -fabs(sg_avg_pressure - 6.895) * 5;
-    double condenser_penalty = 0;
-    if (condenser_pressure > 0.01) condenser_penalty = -(condenser_pressure - 0.007) * 100;
-    double secondary_reward = efficiency_reward + electrical_reward + steam_pressure_penalty + condenser_penalty;
-    double reward = base_reward + secondary_reward * 0.5;
+    const double reward = npd_reward(base_reward, thermal_efficiency, load_demand, electrical_power, sg_avg_pressure, condenser_pressure);
     if (live && reward_out) __builtin_nontemporal_store(reward, &reward_out[p]);
-    /* ---- secondary-level state write-back, feedback into the primary state (sim.py:429-498) */
+    /* ---- secondary-level state write-back, feedback into the primary state */
     {
       const int avail = (int)XR(X_TAIL + 14);
       NPD_ST_F64_ELIDE(SEC, npb_sec_t, previous_feedwater_temp, 0, 0, actual_feedwater_temp, XR(X_TAIL + 15));
       NPD_ST_F64_ELIDE(SEC, npb_sec_t, cooling_water_temperature, 0, 0, cooling_water_temperature, XR(X_TAIL + 16));
       NPD_ST_F64(SEC, npb_sec_t, operating_hours, 0, 0) = (npd_real_t)(XR(X_TAIL + 17) + dt / 3600.0);
-      npb_sec_t so;
-      so.electrical_power_output = electrical_power; so.thermal_efficiency = thermal_efficiency;
-      so.total_steam_flow = sg_total_steam; so.total_heat_transfer = XR(X_TAIL + 11); so.total_feedwater_flow = fw_total_flow_t;
-      so.load_demand = load_demand; so.sg_avg_pressure = sg_avg_pressure; so.sg_avg_temperature = XR(X_TAIL + 12);
-      so.sg_avg_quality = XR(X_TAIL + 13); so.has_previous_sg_conditions = 1; so.sg_system_availability = avail & 1;
+      const npb_sec_t so = npd_sec_outputs(electrical_power, thermal_efficiency, sg_total_steam, XR(X_TAIL + 11), fw_total_flow_t, load_demand,
+                                           sg_avg_pressure, XR(X_TAIL + 12), XR(X_TAIL + 13), avail & 1);
       NPD_ST_STORE_NARROW(SEC, npb_sec_t, so, 0);
-      double heat_removal_factor = sg_total_steam / 1665.0;
-      if (!(avail & 2)) heat_removal_factor *= 0.5;
       NPD_ST_F64(PRIM, npb_prim_t, steam_flow_rate, 0, 0) = (npd_real_t)sg_total_steam;
-      NPD_ST_F64(PRIM, npb_prim_t, last_heat_removal_factor, 0, 0) = (npd_real_t)heat_removal_factor;
+      NPD_ST_F64(PRIM, npb_prim_t, last_heat_removal_factor, 0, 0) = (npd_real_t)npd_heat_removal_factor(sg_total_steam, avail & 2);
     }
     if (info_out) {
       double info[NPB_INFO_DIM];
-      info[NPB_INFO_THERMAL_POWER] = XR(X_TAIL + 8); info[NPB_INFO_REACTIVITY_PCM] = XR(X_TAIL + 9); info[NPB_INFO_TIME] = XR(X_TAIL + 10);
-      info[NPB_INFO_ELECTRICAL_POWER] = isfinite(electrical_power) ? electrical_power : 0.0;
-      info[NPB_INFO_THERMAL_EFFICIENCY] = npd_pymax(0.0, npd_pymin(isfinite(thermal_efficiency) ? thermal_efficiency : 0.0, 0.35));
-      info[NPB_INFO_STEAM_FLOW] = isfinite(sg_total_steam) ? sg_total_steam : 1665.0;
-      info[NPB_INFO_STEAM_PRESSURE] = isfinite(sg_avg_pressure) ? sg_avg_pressure : 6.895;
-      info[NPB_INFO_CONDENSER_PRESSURE] = isfinite(condenser_pressure) ? condenser_pressure : 0.007;
-      info[NPB_INFO_CONDENSER_HEAT_REJECTION] = isfinite(heat_rejection) ? heat_rejection : 0.0;
-      info[NPB_INFO_FEEDWATER_FLOW] = fw_total_flow_t;
-      info[NPB_INFO_SG_HEAT_TRANSFER] = XR(X_TAIL + 11); info[NPB_INFO_TURBINE_POWER] = XR(X_TAIL + 18);
-      info[NPB_INFO_FEEDWATER_POWER] = XR(X_TAIL + 19); info[NPB_INFO_PRIMARY_THERMAL_POWER] = XR(X_TAIL + 20);
-      info[NPB_INFO_TURBINE_EFFICIENCY] = XR(X_TAIL2 + 0); info[NPB_INFO_TURBINE_HP_POWER] = XR(X_TAIL2 + 1); info[NPB_INFO_TURBINE_LP_POWER] = XR(X_TAIL2 + 2);
+      npd_info_primary(info, XR(X_TAIL + 8), XR(X_TAIL + 9), XR(X_TAIL + 10));
+      npd_info_secondary(info, electrical_power, thermal_efficiency, sg_total_steam, sg_avg_pressure, condenser_pressure, heat_rejection,
+                         fw_total_flow_t, XR(X_TAIL + 11), XR(X_TAIL + 18), XR(X_TAIL + 19), XR(X_TAIL + 20), XR(X_TAIL2 + 0),
+                         XR(X_TAIL2 + 1), XR(X_TAIL2 + 2));
       npd2_store_rows<NPB_INFO_DIM>(info, info_out, xch + X_INFO * NPB_WAVE, lane, block_base, (size_t)n_plants);
     }
   }

@@ -300,16 +300,13 @@ __device__ __forceinline__ void npd_step4_body(
     }
     const double cw_in = (live && cw_temp) ? cw_temp[p] : NAN;
     if (!isnan(cw_in)) cooling_water_temperature = cw_in;
-    actual_feedwater_temp = (0.1 * (40.0 + 187.0) + (1 - 0.1) * prev_feedwater_temp);
+    actual_feedwater_temp = npd_feedwater_temp(prev_feedwater_temp);
     NPD_ST_LOAD(FW, npb_fw_t, fw, 0);
     fw_old = fw;
     if (__builtin_amdgcn_ballot_w64(!has_prev) != 0) {   /* a plant's first step: its previous conditions come from the primary side's load */
       NPD4_FLAG_WAIT(FL_PRIM, 1);
       const double load_demand_fraction = XR(Y_LDF);
-      if (!has_prev) {
-#pragma unroll
-        for (int i = 0; i < NPB_NUM_SG; i++) { prev_levels[i] = 12.5; prev_flows[i] = 555.0 * load_demand_fraction; prev_quals[i] = 0.99; }
-      }
+      if (!has_prev) npd_first_step_sg_conditions(load_demand_fraction, prev_levels, prev_flows, prev_quals);
     }
     const double total_flow_demand = npd_fw_level_control(&fw, prev_levels, prev_flows, prev_quals, dt);
     int n_prev_running = 0;
@@ -436,22 +433,11 @@ __device__ __forceinline__ void npd_step4_body(
 #pragma unroll
     for (int k = 0; k < 8; k++) max_stress = (k == 0) ? XR(Y_STRESS) : npd_pymax(max_stress, XR(Y_STRESS + k));
     npd_turbine_protect(&t, stage_power_mw, max_stress, max_bearing_metal, total_displacement, sg_system_availability, 0.007, tdt);
-    /* ---- electrical-power gates (secondary/__init__.py:750-932) */
-    const double primary_thermal_power = XR(Y_PRIM + 4);
-    const double turbine_electrical_power = t.total_power_output * 0.98;
-    const double total_system_heat_rejection = (primary_thermal_power - turbine_electrical_power) * 1e6;
-    double power_reduction_factor = 1.0;
-    if (fw_total_flow < 300.0) power_reduction_factor = 0.0;
-    if (power_reduction_factor > 0.0) {
-      if (sg_total_steam < (300.0 * 0.5)) power_reduction_factor *= 0.1;
-      if (sg_avg_pressure < (1.0 * 0.5)) power_reduction_factor *= 0.1;
-      if (primary_thermal_power > (primary_thermal_power * 1.1)) power_reduction_factor = 0.0;
-    }
-    const double electrical_power = turbine_electrical_power * power_reduction_factor;
-    const double thermal_efficiency = (primary_thermal_power > 0) ? electrical_power / primary_thermal_power : 0.0;
+    /* ---- electrical-power gates */
+    const npd_power_t pw = npd_power_gates(t.total_power_output * 0.98, XR(Y_PRIM + 4), fw_total_flow, sg_total_steam, sg_avg_pressure);
     if (t.trip_active) trip_flags |= NPB_TRIP_TURBINE;
-    XW(Y_TAIL + 0, electrical_power); XW(Y_TAIL + 1, thermal_efficiency); XW(Y_TAIL + 2, sg_avg_pressure); XW(Y_TAIL + 3, sg_total_steam);
-    XW(Y_TAIL + 4, fw_total_flow); XW(Y_TAIL + 5, total_system_heat_rejection); XW(Y_TAIL + 6, sg_total_thermal); XW(Y_TAIL + 7, sg_avg_temperature);
+    XW(Y_TAIL + 0, pw.electrical_power); XW(Y_TAIL + 1, pw.thermal_efficiency); XW(Y_TAIL + 2, sg_avg_pressure); XW(Y_TAIL + 3, sg_total_steam);
+    XW(Y_TAIL + 4, fw_total_flow); XW(Y_TAIL + 5, pw.heat_rejection); XW(Y_TAIL + 6, sg_total_thermal); XW(Y_TAIL + 7, sg_avg_temperature);
     XW(Y_TAIL + 8, sg_avg_quality); XW(Y_TAIL + 9, (double)(sg_system_availability | (fw_available << 1))); XW(Y_TAIL + 10, prev_feedwater_temp);
     XW(Y_TAIL + 11, cw_old); XW(Y_TAIL + 12, operating_hours); XW(Y_TAIL + 13, t.total_power_output); XW(Y_TAIL + 14, fw_total_power);
     XW(Y_TAIL + 15, turbine_efficiency); XW(Y_TAIL + 16, hp_power); XW(Y_TAIL + 17, lp_power); XW(Y_TAIL + 18, (double)trip_flags);
@@ -475,21 +461,14 @@ __device__ __forceinline__ void npd_step4_body(
     }
     NPD4_FLAG_WAIT(FL_CONDP, 1);                   /* wave 2's condenser */
     NPD4_STAMP(12);
-    if (info_out) {   /* info (sim.py:199-250) */
+    if (info_out) {
       const double condenser_pressure = XR(Y_CONDP), electrical_power = XR(Y_TAIL + 0), thermal_efficiency = XR(Y_TAIL + 1);
       const double sg_avg_pressure_t = XR(Y_TAIL + 2), sg_total_steam_t = XR(Y_TAIL + 3), heat_rejection = XR(Y_TAIL + 5);
       double info[NPB_INFO_DIM];
-      info[NPB_INFO_THERMAL_POWER] = XR(Y_PRIM + 2); info[NPB_INFO_REACTIVITY_PCM] = XR(Y_PRIM + 3); info[NPB_INFO_TIME] = XR(Y_TIME);
-      info[NPB_INFO_ELECTRICAL_POWER] = isfinite(electrical_power) ? electrical_power : 0.0;
-      info[NPB_INFO_THERMAL_EFFICIENCY] = npd_pymax(0.0, npd_pymin(isfinite(thermal_efficiency) ? thermal_efficiency : 0.0, 0.35));
-      info[NPB_INFO_STEAM_FLOW] = isfinite(sg_total_steam_t) ? sg_total_steam_t : 1665.0;
-      info[NPB_INFO_STEAM_PRESSURE] = isfinite(sg_avg_pressure_t) ? sg_avg_pressure_t : 6.895;
-      info[NPB_INFO_CONDENSER_PRESSURE] = isfinite(condenser_pressure) ? condenser_pressure : 0.007;
-      info[NPB_INFO_CONDENSER_HEAT_REJECTION] = isfinite(heat_rejection) ? heat_rejection : 0.0;
-      info[NPB_INFO_FEEDWATER_FLOW] = XR(Y_TAIL + 4);
-      info[NPB_INFO_SG_HEAT_TRANSFER] = XR(Y_TAIL + 6); info[NPB_INFO_TURBINE_POWER] = XR(Y_TAIL + 13);
-      info[NPB_INFO_FEEDWATER_POWER] = XR(Y_TAIL + 14); info[NPB_INFO_PRIMARY_THERMAL_POWER] = XR(Y_PRIM + 4);
-      info[NPB_INFO_TURBINE_EFFICIENCY] = XR(Y_TAIL + 15); info[NPB_INFO_TURBINE_HP_POWER] = XR(Y_TAIL + 16); info[NPB_INFO_TURBINE_LP_POWER] = XR(Y_TAIL + 17);
+      npd_info_primary(info, XR(Y_PRIM + 2), XR(Y_PRIM + 3), XR(Y_TIME));
+      npd_info_secondary(info, electrical_power, thermal_efficiency, sg_total_steam_t, sg_avg_pressure_t, condenser_pressure, heat_rejection,
+                         XR(Y_TAIL + 4), XR(Y_TAIL + 6), XR(Y_TAIL + 13), XR(Y_TAIL + 14), XR(Y_PRIM + 4), XR(Y_TAIL + 15),
+                         XR(Y_TAIL + 16), XR(Y_TAIL + 17));
       npd2_store_rows<NPB_INFO_DIM>(info, info_out, xch + Y_INFO * NPB_WAVE, lane, block_base, (size_t)n_plants);
     }
     NPD4_STAMP(13);
@@ -509,12 +488,7 @@ __device__ __forceinline__ void npd_step4_body(
     if (wave == 0) {
       npd_maint_due_t maint_due = {};
       if (maint) npd_maint_due_load(&maint_due, f64, N, p);
-      npd_inputs_t in;
-      in.action = (live && action) ? action[p] : 8;
-      in.magnitude = (live && magnitude) ? magnitude[p] : 1.0;
-      in.power_setpoint = (live && setpoint) ? setpoint[p] : NAN;
-      in.noise_z = (live && noise_z) ? noise_z[p] : 0.0;
-      in.cooling_water_temp = NAN;      /* (wave 3 reads the cooling-water input) */
+      const npd_inputs_t in = npd_step_inputs(live, p, action, magnitude, setpoint, noise_z, nullptr);   /* (wave 3 reads the cooling-water input) */
       npb_prim_t s;
       if (kinetics) {
         NPD_ST_LOAD(PRIM, npb_prim_t, s, 0);
@@ -544,17 +518,10 @@ __device__ __forceinline__ void npd_step4_body(
         XW(Y_CFLOW + i, c.flow[i]); XW(Y_CIN + i, c.inlet_temp[i]); XW(Y_COUT + i, c.outlet_temp[i]);
         primary_thermal_power += c.thermal_power[i];
       }
-      double load_demand_fraction = npd_pymin(1.0, primary_thermal_power / 3000.0);
-      load_demand_fraction = npd_pymax(load_demand_fraction, 0.2);
-      XW(Y_LDF, load_demand_fraction);
+      XW(Y_LDF, npd_load_demand_fraction(primary_thermal_power));
       s.sim_time += dt;
-      const double power_reward = -fabs(s.power_level - 100) / 100;
-      double temp_penalty = 0, pressure_penalty = 0;
-      if (s.fuel_temperature > 800) temp_penalty = -(s.fuel_temperature - 800) / 100;
-      if (s.coolant_pressure > 16) pressure_penalty = -(s.coolant_pressure - 16);
-      const double scram_penalty = s.scram_status ? -100 : 0;
       scram_bits = (s.scram_status != 0) | (scram_fired ? 2 : 0) | (nan_reset ? 4 : 0);
-      XW(Y_PRIM + 0, power_reward + temp_penalty + pressure_penalty + scram_penalty); XW(Y_PRIM + 1, s.power_level);
+      XW(Y_PRIM + 0, npd_base_reward(s)); XW(Y_PRIM + 1, s.power_level);
       XW(Y_PRIM + 2, s.thermal_power_mw); XW(Y_PRIM + 3, s.total_reactivity_pcm); XW(Y_PRIM + 4, primary_thermal_power);
       XW(Y_PRIM + 5, (double)scram_bits); XW(Y_TIME, s.sim_time);
       NPD4_FLAG_SET(FL_PRIM, 1);
@@ -717,10 +684,7 @@ __device__ __forceinline__ void npd_step4_body(
       NPD4_STAMP(10);
       const double ld = XR(Y_PRIM + 1), sg_total_steam_t = XR(Y_TAIL + 3), fw_flow_t = XR(Y_TAIL + 4);
       obs[10] = ld / 100;                          /* load_demand IS state.power_level (sim.py:161) */
-      obs[7] = sg_total_steam_t / 3000;
-      obs[12] = XR(Y_TAIL + 0) / 1100; obs[13] = XR(Y_TAIL + 1) / 0.35; obs[14] = sg_total_steam_t / 1665;
-      obs[15] = ld / 100; obs[16] = 227.0 / 250; obs[17] = XR(Y_CWT) / 35;
-      obs[18] = fw_flow_t / 1665; obs[19] = XR(Y_TAIL + 14) / 40; obs[20] = XR(Y_TAIL + 20); obs[21] = fw_flow_t / 1665;
+      npd_obs_secondary(obs, sg_total_steam_t, XR(Y_TAIL + 0), XR(Y_TAIL + 1), sg_total_steam_t, ld, XR(Y_CWT), fw_flow_t, XR(Y_TAIL + 14), XR(Y_TAIL + 20));
       uint32_t flags = (uint32_t)XR(Y_TAIL + 18);
       if (scram_bits & 1) flags |= NPB_TRIP_SCRAM;
       if (scram_bits & 2) flags |= NPB_TRIP_SCRAM_FIRED;
@@ -750,49 +714,28 @@ __device__ __forceinline__ void npd_step4_body(
       NPD4_STAMP(11);
       NPD4_FLAG_WAIT(FL_TAIL, 1); NPD4_FLAG_WAIT(FL_CONDP, 1);
       NPD4_STAMP(12);
-      /* ---- reward (sim.py:521-542), secondary-level state write-back, feedback into the primary state (sim.py:429-498) */
+      /* ---- reward, secondary-level state write-back, feedback into the primary state */
       const double condenser_pressure = XR(Y_CONDP);
       const double base_reward = XR(Y_PRIM + 0), ld = XR(Y_PRIM + 1);
       const double electrical_power = XR(Y_TAIL + 0), thermal_efficiency = XR(Y_TAIL + 1), sg_avg_pressure_t = XR(Y_TAIL + 2), sg_total_steam_t = XR(Y_TAIL + 3);
-      double efficiency_reward = (thermal_efficiency - 0.30) * 10;
-      double target_electrical_power = ld / 100.0 * 1100.0;
-      double electrical_reward = -fabs(electrical_power - target_electrical_power) / 100;
-      double steam_pressure_penalty = 0;
-      if (sg_avg_pressure_t < 5.0 || sg_avg_pressure_t > 8.0) steam_pressure_penalty = -fabs(sg_avg_pressure_t - 6.895) * 5;
-      double condenser_penalty = 0;
-      if (condenser_pressure > 0.01) condenser_penalty = -(condenser_pressure - 0.007) * 100;
-      double secondary_reward = efficiency_reward + electrical_reward + steam_pressure_penalty + condenser_penalty;
-      double reward = base_reward + secondary_reward * 0.5;
+      const double reward = npd_reward(base_reward, thermal_efficiency, ld, electrical_power, sg_avg_pressure_t, condenser_pressure);
       if (live && reward_out) __builtin_nontemporal_store(reward, &reward_out[p]);
       const int avail = (int)XR(Y_TAIL + 9);
       NPD_ST_F64_ELIDE(SEC, npb_sec_t, previous_feedwater_temp, 0, 0, XR(Y_TAIL + 19), XR(Y_TAIL + 10));
       NPD_ST_F64_ELIDE(SEC, npb_sec_t, cooling_water_temperature, 0, 0, XR(Y_CWT), XR(Y_TAIL + 11));
       NPD_ST_F64(SEC, npb_sec_t, operating_hours, 0, 0) = (npd_real_t)(XR(Y_TAIL + 12) + dt / 3600.0);
-      npb_sec_t so;
-      so.electrical_power_output = electrical_power; so.thermal_efficiency = thermal_efficiency;
-      so.total_steam_flow = sg_total_steam_t; so.total_heat_transfer = XR(Y_TAIL + 6); so.total_feedwater_flow = XR(Y_TAIL + 4);
-      so.load_demand = ld; so.sg_avg_pressure = sg_avg_pressure_t; so.sg_avg_temperature = XR(Y_TAIL + 7);
-      so.sg_avg_quality = XR(Y_TAIL + 8); so.has_previous_sg_conditions = 1; so.sg_system_availability = avail & 1;
+      const npb_sec_t so = npd_sec_outputs(electrical_power, thermal_efficiency, sg_total_steam_t, XR(Y_TAIL + 6), XR(Y_TAIL + 4), ld,
+                                           sg_avg_pressure_t, XR(Y_TAIL + 7), XR(Y_TAIL + 8), avail & 1);
       NPD_ST_STORE_NARROW(SEC, npb_sec_t, so, 0);
-      double heat_removal_factor = sg_total_steam_t / 1665.0;
-      if (!(avail & 2)) heat_removal_factor *= 0.5;
       NPD_ST_F64(PRIM, npb_prim_t, steam_flow_rate, 0, 0) = (npd_real_t)sg_total_steam_t;
-      NPD_ST_F64(PRIM, npb_prim_t, last_heat_removal_factor, 0, 0) = (npd_real_t)heat_removal_factor;
+      NPD_ST_F64(PRIM, npb_prim_t, last_heat_removal_factor, 0, 0) = (npd_real_t)npd_heat_removal_factor(sg_total_steam_t, avail & 2);
       NPD4_STAMP(13);
     } else {
       NPD4_FLAG_WAIT(FL_CHAINDONE, 1);
       __builtin_amdgcn_s_setprio(2);               /* condenser -> info is what ends the step */
       /* ---- condenser (secondary/__init__.py:591-621) */
       const double effective_steam_flow = XR(Y_CHRES + 6), lp6_outlet_enthalpy = XR(Y_CHRES + 2), cwt = XR(Y_CWT);
-      double lp_exhaust_quality = 0.90;
-      {
-        double h_f = npd_cond_hf(0.007), h_g = npd_cond_hg(0.007);
-        double h_fg = h_g - h_f;
-        if (h_fg > 0) {
-          lp_exhaust_quality = (lp6_outlet_enthalpy - h_f) / h_fg;
-          lp_exhaust_quality = npd_pymax(0.0, npd_pymin(1.0, lp_exhaust_quality));
-        }
-      }
+      const double lp_exhaust_quality = npd_lp_exhaust_quality(0.007, lp6_outlet_enthalpy);
       npd_condenser_result_t cr;
       npd_condenser_update(&cd, &chc, 0.007, effective_steam_flow, lp_exhaust_quality, 45000.0, cwt, 1.2, 185.0, tdt, &cr);
       XW(Y_CONDP, cr.condenser_pressure);
