@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define NPB_VERSION 142 /* 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
+#define NPB_VERSION 143 /* 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
 #ifndef NPB_API
 #define NPB_API __attribute__((visibility("default")))
 #endif
@@ -293,6 +293,30 @@ NPB_API const char *npb_step_kernel_name(int kernel_id);
 
 /* NuclearPlantSimulator.get_observation (sim.py:290-333) */
 NPB_API int npb_observe(NpbHandle *h, double *obs, void *stream);
+
+/* Episodes (no reference counterpart: the reference steps one simulator until the caller builds a new one).  The semantics are
+ * gymnasium's vector-env "same-step" autoreset with truncation.
+ * npb_snapshot: copy the whole arena into a snapshot arena the handle owns -- the same layout (segments, pitch, storage type), one
+ * device-to-device copy on `stream` -- allocated on first use (NPB_EHIP if that fails), freed by npb_destroy.  Take it after the
+ * initial conditions have been put in (npb_set_field ...): it is each plant's episode-start state.  Episode counters are not touched. */
+NPB_API int npb_snapshot(NpbHandle *h, void *stream);
+/* the plants of mask (device, uint8[n], NULL = all) back to the snapshot, their episode counters (if any) to zero; with
+ * params.maint_enabled their maintenance cooldown cache and their entries in the event-count column follow.  NPB_EINVAL without a
+ * snapshot.  Follow with npb_observe for the restored observation. */
+NPB_API int npb_restore(NpbHandle *h, const uint8_t *mask, void *stream);
+/* enabled != 0: every npb_step is followed, on the same stream, by the episode kernel (no host synchronisation, nothing read back):
+ * per plant len += 1, ret += reward; truncated = max_episode_steps > 0 && len >= max_episode_steps && !done (termination wins);
+ * a plant with done | truncated goes back to the snapshot as npb_restore would, its obs row is first copied to final_obs and
+ * then replaced by the restored state's observation; reward, info and trip_flags keep describing the terminal transition.  The
+ * episode buffers (npb_set_episode_buffers) receive len / ret as of this step (a reset plant's: its finished episode's) and the
+ * truncation flag.  Needs a snapshot; allocates the handle's carried counters (int32 length[pitch], double return[pitch]) and
+ * zeroes them; npb_step then needs a non-NULL done column.  Refused (NPB_EINVAL) while npb_set_diagnostics is set, as that is
+ * refused while autoreset is on: the diagnostics buffer carries plant state outside the arena.  enabled = 0 turns it off.
+ * npb_reset, npb_reset_reference and npb_restore zero the counters of the plants they reset. */
+NPB_API int npb_set_autoreset(NpbHandle *h, int enabled, int max_episode_steps /* 0 = no limit */);
+/* the caller's output columns of the episode kernel (device; each may be NULL): length int32[n], ret double[n], truncated
+ * uint8[n], final_obs double[n][NPB_OBS_DIM] (rows of plants reset on the step; other rows are left as they were) */
+NPB_API int npb_set_episode_buffers(NpbHandle *h, int32_t *length, double *ret, uint8_t *truncated, double *final_obs /* [n,22] */);
 
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the

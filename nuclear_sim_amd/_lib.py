@@ -198,6 +198,11 @@ def load():
     L.npb_step.argtypes = [vp] + [vp] * 11
     L.npb_observe.argtypes = [vp, vp, vp]
     L.npb_debug_touch.argtypes = [vp, vp]
+    if hasattr(L, "npb_snapshot"):     # ABI 143: episodes
+        L.npb_snapshot.argtypes = [vp, vp]
+        L.npb_restore.argtypes = [vp, vp, vp]
+        L.npb_set_autoreset.argtypes = [vp, ci, ci]
+        L.npb_set_episode_buffers.argtypes = [vp, vp, vp, vp, vp]
     if L.npb_num_f64() != SCHEMA.total_f64 or L.npb_num_i32() != SCHEMA.total_i32:
         raise NpbError("libnpb.so was built against a different include/npb_fields.h (%d/%d vs %d/%d): rebuild"
                        % (L.npb_num_f64(), L.npb_num_i32(), SCHEMA.total_f64, SCHEMA.total_i32))

@@ -30,6 +30,10 @@ struct NpbHandle {
   int step_kernel;                 /* 0 = chosen by batch size, 1 = one-wave kernel, 2 = two-wave kernel, 3 = its two-waves-per-SIMD build, 4 = one-wave with streaming stores, 5 = four-wave kernel (npb_set_step_kernel) */
   npb_maint_table_t maint_table;   /* thresholds of the automatic maintenance (include/npb_maint.h) */
   bool maint_table_custom;         /* set through npb_set_maintenance_table: the table is then taken as it is */
+  void *snap;          /* npb_snapshot: the episode-start arena, the arena's layout, or NULL */
+  int32_t *ep_len; double *ep_ret; /* npb_set_autoreset: carried steps / summed reward of each plant's running episode ([pitch] each), or NULL */
+  bool autoreset; int max_episode_steps;
+  int32_t *ep_out_len; double *ep_out_ret; uint8_t *ep_out_truncated; double *ep_final_obs;   /* npb_set_episode_buffers: the caller's columns, or NULL */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
   std::vector<int> plan_key;
   std::string error;
@@ -258,6 +262,8 @@ int npb_destroy(NpbHandle *h) {
   (void)hipFree(h->f64);
   if (h->convert) (void)hipFree(h->convert);
   if (h->plan_dev) (void)hipFree(h->plan_dev);
+  if (h->snap) (void)hipFree(h->snap);
+  if (h->ep_len) (void)hipFree(h->ep_len);
   delete h;
   return NPB_OK;
 }
@@ -287,6 +293,8 @@ int npb_set_diagnostics(NpbHandle *h, double *buf, size_t pitch) {
   if (!h) return NPB_EINVAL;
   if (buf && h->params.mode != NPB_MODE_FULL) return fail(h, NPB_EINVAL, "npb_set_diagnostics: full mode only");
   if (buf && pitch < h->pitch) return fail(h, NPB_EINVAL, "npb_set_diagnostics: pitch must be at least n_plants rounded up to 64");
+  if (buf && h->autoreset)      /* the buffer carries plant state outside the arena, which a restore from the snapshot would not put back */
+    return fail(h, NPB_EINVAL, "npb_set_diagnostics: autoreset is on (npb_set_autoreset); the diagnostics buffer carries plant state the snapshot does not hold");
   h->diag = buf; h->diag_pitch = buf ? pitch : 0;
   return NPB_OK;
 }
@@ -317,6 +325,7 @@ int npb_reset(NpbHandle *h, const uint8_t *mask, void *stream) {
   NPB_USE_DEVICE(h);
   h->maint_cache_stale = true;
   (h->storage == NPB_STORAGE_F32 ? npb32_launch_init : npb_launch_init)(&h->params, h->n_plants, NPB_N(h), h->f64, mask, (hipStream_t)stream);
+  if (h->ep_len) npb_launch_episode_clear(mask, h->ep_len, h->ep_ret, h->n_plants, h->pitch, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -326,6 +335,7 @@ int npb_reset_reference(NpbHandle *h, const uint8_t *mask, int start_at_steady_s
   NPB_USE_DEVICE(h);
   h->maint_cache_stale = true;
   (h->storage == NPB_STORAGE_F32 ? npb32_launch_reset : npb_launch_reset)(&h->params, h->n_plants, NPB_N(h), h->f64, mask, start_at_steady_state != 0, (hipStream_t)stream);
+  if (h->ep_len) npb_launch_episode_clear(mask, h->ep_len, h->ep_ret, h->n_plants, h->pitch, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -431,6 +441,8 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
              const double *noise_z, const double *cooling_water_temp, double *obs, double *reward, uint8_t *done,
              uint32_t *trip_flags, double *info, void *stream) {
   if (!h) return NPB_EINVAL;
+  if (h->autoreset && !done)      /* the episode kernel reads the step's terminations from the done column */
+    return fail(h, NPB_EINVAL, "npb_step: autoreset is on (npb_set_autoreset) and needs the done column: it must not be NULL");
   if (h->params.heat_source == NPB_HEAT_EXTERNAL && !noise_z)      /* a NULL column would read as 0 MW thermal, silently */
     return fail(h, NPB_EINVAL, "npb_step: params.heat_source is NPB_HEAT_EXTERNAL, whose thermal power arrives in the noise_z column (include/npb_params.h): it must not be NULL");
   NPB_USE_DEVICE(h);
@@ -465,8 +477,61 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
                                                  maint ? &table : nullptr, maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
   if (maint && h->params.mode != NPB_MODE_FULL)   /* a full-mode step kernel has run the rule itself, for the waves whose pump phase found something */
     (narrow ? npb32_launch_maint : npb_launch_maint)(NPB_N(h), h->f64, h->maint_side, h->maint_counts, h->n_plants, (hipStream_t)stream);
+  if (h->autoreset)   /* same stream, nothing read back, the maintenance cache kept per plant by the kernel itself */
+    (narrow ? npb32_launch_episode : npb_launch_episode)(h->params.mode, h->n_plants, NPB_N(h), h->f64, h->snap, done, reward, obs, h->ep_len, h->ep_ret,
+                                                         h->ep_out_len, h->ep_out_ret, h->ep_out_truncated, h->ep_final_obs, h->max_episode_steps,
+                                                         maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, NPB_EHIP, "npb_step: kernel launch failed", e);
+  return NPB_OK;
+}
+
+int npb_snapshot(NpbHandle *h, void *stream) {
+  if (!h) return NPB_EINVAL;
+  NPB_USE_DEVICE(h);
+  const size_t bytes = arena_columns(h->storage) * arena_plants(h) * h->real_bytes;
+  if (!h->snap) {
+    hipError_t e = hipMalloc(&h->snap, bytes);
+    if (e != hipSuccess) { h->snap = nullptr; return fail(h, NPB_EHIP, "npb_snapshot: hipMalloc of the snapshot arena failed", e); }
+  }
+  NPB_HIP(h, hipMemcpyAsync(h->snap, h->f64, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return NPB_OK;
+}
+
+int npb_restore(NpbHandle *h, const uint8_t *mask, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->snap) return fail(h, NPB_EINVAL, "npb_restore: no snapshot (npb_snapshot) to restore from");
+  NPB_USE_DEVICE(h);
+  const bool maint = h->params.maint_enabled != 0;
+  (h->storage == NPB_STORAGE_F32 ? npb32_launch_restore : npb_launch_restore)(h->n_plants, NPB_N(h), h->f64, h->snap, mask, h->ep_len, h->ep_ret,
+                                                                              maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+
+int npb_set_autoreset(NpbHandle *h, int enabled, int max_episode_steps) {
+  if (!h) return NPB_EINVAL;
+  if (!enabled) { h->autoreset = false; return NPB_OK; }
+  if (max_episode_steps < 0) return fail(h, NPB_EINVAL, "npb_set_autoreset: max_episode_steps must be >= 0 (0 = no limit)");
+  if (!h->snap) return fail(h, NPB_EINVAL, "npb_set_autoreset: no snapshot (npb_snapshot) to reset to");
+  if (h->diag) return fail(h, NPB_EINVAL, "npb_set_autoreset: diagnostics are on (npb_set_diagnostics); their buffer carries plant state the snapshot does not hold");
+  NPB_USE_DEVICE(h);
+  if (!h->ep_len) {     /* one allocation: [pitch] int32 lengths, then [pitch] double returns */
+    const size_t len_bytes = (h->pitch * sizeof(int32_t) + 255) / 256 * 256;
+    hipError_t e = hipMalloc((void **)&h->ep_len, len_bytes + h->pitch * sizeof(double));
+    if (e != hipSuccess) { h->ep_len = nullptr; return fail(h, NPB_EHIP, "npb_set_autoreset: hipMalloc of the episode counters failed", e); }
+    h->ep_ret = (double *)((char *)h->ep_len + len_bytes);
+  }
+  const size_t len_bytes = (size_t)((char *)h->ep_ret - (char *)h->ep_len);
+  NPB_HIP(h, hipMemset(h->ep_len, 0, len_bytes + h->pitch * sizeof(double)));
+  h->autoreset = true;
+  h->max_episode_steps = max_episode_steps;
+  return NPB_OK;
+}
+
+int npb_set_episode_buffers(NpbHandle *h, int32_t *length, double *ret, uint8_t *truncated, double *final_obs) {
+  if (!h) return NPB_EINVAL;
+  h->ep_out_len = length; h->ep_out_ret = ret; h->ep_out_truncated = truncated; h->ep_final_obs = final_obs;
   return NPB_OK;
 }
 

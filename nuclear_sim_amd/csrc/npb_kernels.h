@@ -27,11 +27,18 @@ extern "C" {
   /* kind: 0 carried real, 1 output real (float), 2 int32; buffers: double for reals, int32 for ints */ \
   void prefix##field_get(const void *arena, size_t npad, int col, int sub, int kind, void *out, int n, hipStream_t stream); \
   void prefix##field_set(void *arena, size_t npad, int col, int sub, int kind, const void *in, int n, hipStream_t stream); \
-  void prefix##gather(const void *arena, size_t npad, const int *plan_dev, int n_fields, double *out, int n, hipStream_t stream);
+  void prefix##gather(const void *arena, size_t npad, const int *plan_dev, int n_fields, double *out, int n, hipStream_t stream); \
+  /* episodes: snap = the snapshot arena (the arena's layout); maint_side / maint_counts NULL unless params.maint_enabled */ \
+  void prefix##restore(int n_plants, size_t npad, void *arena, const void *snap, const uint8_t *mask, int32_t *len, double *ret, \
+                       void *maint_side, int32_t *maint_counts, hipStream_t stream); \
+  void prefix##episode(int mode, int n_plants, size_t npad, void *arena, const void *snap, const uint8_t *done, const double *reward, \
+                       double *obs, int32_t *len, double *ret, int32_t *out_len, double *out_ret, uint8_t *out_truncated, \
+                       double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, hipStream_t stream);
 NPB__DECL(npb_launch_)
 NPB__DECL(npb32_launch_)
 #undef NPB__DECL
 void npb_launch_touch(size_t npad, double *arena, hipStream_t stream);
+void npb_launch_episode_clear(const uint8_t *mask, int32_t *len, double *ret, int n_plants, size_t npad, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

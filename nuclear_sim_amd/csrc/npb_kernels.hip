@@ -573,22 +573,15 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_maint_kernel(const npd_maint_rul
 #include "npd_step2.h"
 #include "npd_step4.h"
 
-/* get_observation() without stepping (after reset / set_field): sim.py:290-333 */
-__global__ __launch_bounds__(NPB_WAVE) void npb_observe_kernel(int mode, int n_plants, size_t N, const npd_real_t *__restrict__ f64c,
-                                                               double *__restrict__ obs_out) {
-  __shared__ double lds[NPB_WAVE * NPB_OBS_PAD];
-  npd_real_t *f64 = const_cast<npd_real_t *>(f64c);
-  const size_t block_base = (size_t)blockIdx.x * NPB_WAVE;
-  NPD_SEGMENT(f64, N, block_base);
-  const size_t p = block_base + threadIdx.x;
-  double obs[NPB_OBS_DIM];
+/* get_observation() of one plant from the arena as it stands (sim.py:290-333), in each of the three modes; f64 / N already moved to
+ * the plant's segment */
+__device__ __forceinline__ void npd_observe_row(int mode, npd_real_t *f64, size_t N, size_t p, double *obs) {
   npb_prim_t s;
   NPD_LOAD(PRIM, npb_prim_t, s, 0);
   npd_obs_primary(s, obs);
   if (mode == NPB_MODE_PRIMARY) {   /* sim.py:333: twelve values */
 #pragma unroll
     for (int k = 12; k < NPB_OBS_DIM; k++) obs[k] = 0.0;
-    npd_store_rows<NPB_OBS_DIM>(obs, obs_out, lds, block_base, (size_t)n_plants);
     return;
   }
   double fwf, fwp; int fwa;
@@ -601,7 +594,132 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_observe_kernel(int mode, int n_p
   npd_obs_secondary(obs, s.steam_flow_rate, NPD_F64_COL(SEC, npb_sec_t, electrical_power_output, 0), NPD_F64_COL(SEC, npb_sec_t, thermal_efficiency, 0),
                     NPD_F64_COL(SEC, npb_sec_t, total_steam_flow, 0), NPD_F64_COL(SEC, npb_sec_t, load_demand, 0),
                     NPD_F64_COL(SEC, npb_sec_t, cooling_water_temperature, 0), fwf, fwp, (double)fwa);
+}
+
+/* get_observation() without stepping (after reset / set_field): sim.py:290-333 */
+__global__ __launch_bounds__(NPB_WAVE) void npb_observe_kernel(int mode, int n_plants, size_t N, const npd_real_t *__restrict__ f64c,
+                                                               double *__restrict__ obs_out) {
+  __shared__ double lds[NPB_WAVE * NPB_OBS_PAD];
+  npd_real_t *f64 = const_cast<npd_real_t *>(f64c);
+  const size_t block_base = (size_t)blockIdx.x * NPB_WAVE;
+  NPD_SEGMENT(f64, N, block_base);
+  double obs[NPB_OBS_DIM];
+  npd_observe_row(mode, f64, N, block_base + threadIdx.x, obs);
   npd_store_rows<NPB_OBS_DIM>(obs, obs_out, lds, block_base, (size_t)n_plants);
+}
+
+/* ---- episodes: restore from the handle's snapshot arena (npb_snapshot / npb_restore) and same-step autoreset after npb_step
+ * (npb_set_autoreset).  The snapshot has the arena's own layout (segments, pitch, storage type), so a plant's element of column c
+ * sits at the same offset in both: restoring a plant is a copy of its lane of every column, nothing is decoded. */
+#ifdef NPB_BUILD_F32
+typedef uint32_t npd_word_t;
+#else
+typedef uint64_t npd_word_t;
+#endif
+/* where the restore writes besides the arena: the maintenance screen's cooldown cache (zeroed = "look", npd_maintenance.h) and the
+ * caller's event-count column (npb_set_maintenance_count_buffer), both NULL unless params.maint_enabled */
+struct npd_restore_side_t { npd_u32x4 *maint_entry; int32_t *maint_counts; int n_plants; };
+/* the wave's plants with `reset` set go back to the snapshot; f64 / snap / N already moved to the wave's segment.  Only reset lanes
+ * load and store (a wave whose 64 plants all reset moves 512 B per column and direction, coalesced; one with a single reset plant
+ * touches one line per column instead of the wave's 512 B): the copy is latency-bound, so the loads of U columns are issued
+ * before their stores */
+__device__ __forceinline__ void npd_restore_lanes(npd_real_t *__restrict__ f64, const npd_real_t *__restrict__ snap, size_t N, size_t p, bool reset,
+                                                  const npd_restore_side_t &R) {
+  npd_word_t *dst = reinterpret_cast<npd_word_t *>(f64);
+  const npd_word_t *src = reinterpret_cast<const npd_word_t *>(snap);
+  constexpr int U = 32;
+  if (reset) {
+#pragma unroll 1
+    for (int c0 = 0; c0 < NPD_ARENA_COLS; c0 += U) {
+      npd_word_t v[U];
+#pragma unroll
+      for (int u = 0; u < U; u++)
+        if (c0 + u < NPD_ARENA_COLS) v[u] = __builtin_nontemporal_load(&src[(size_t)(c0 + u) * N + p]);
+#pragma unroll
+      for (int u = 0; u < U; u++)
+        if (c0 + u < NPD_ARENA_COLS) dst[(size_t)(c0 + u) * N + p] = v[u];
+    }
+  }
+  if (reset && R.maint_entry) {       /* the cooldowns of the restored stamps are unknown to the cache: look */
+    const npd_u32x4 zero = {0u, 0u, 0u, 0u};
+    R.maint_entry[p * 2] = zero; R.maint_entry[p * 2 + 1] = zero;
+  }
+  if (reset && R.maint_counts && p < (size_t)R.n_plants) {
+    const npd_real_t *f64 = snap;     /* (the member macro reads `f64`) */
+    R.maint_counts[p] = NPD_I32_COL(MAINT, npb_maint_t, maintenance_actions_performed, 0);
+  }
+}
+/* [64][W] rows held one per lane -> row-major global memory, only the rows whose bit is set in `rows` (npd_store_rows otherwise) */
+template <int W>
+__device__ __forceinline__ void npd_store_rows_masked(const double *row, double *__restrict__ out, double *lds, size_t block_base, uint64_t rows) {
+  const int lane = threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < W; j++) lds[lane * NPB_OBS_PAD + j] = row[j];
+  NPD_LDS_DRAIN();
+#pragma unroll
+  for (int k = 0; k < W; k++) {
+    const int idx = k * NPB_WAVE + lane, r = idx / W, c = idx % W;
+    if ((rows >> r) & 1u) out[block_base * W + idx] = lds[r * NPB_OBS_PAD + c];
+  }
+  NPD_LDS_DRAIN();
+}
+/* the episode bookkeeping of one step, after the step kernel (and the maintenance kernel) on the same stream */
+struct npd_episode_t {
+  int32_t *len; double *ret;                                  /* carried: steps and summed reward of the running episode */
+  int32_t *out_len; double *out_ret; uint8_t *out_truncated; double *final_obs;   /* the caller's columns, each may be NULL */
+  int max_steps;                                              /* 0 = no limit */
+};
+__global__ __launch_bounds__(NPB_WAVE) void npb_episode_kernel(int mode, int n_plants, size_t N, npd_real_t *__restrict__ f64, const npd_real_t *__restrict__ snap,
+                                                               const uint8_t *__restrict__ done, const double *__restrict__ reward, double *__restrict__ obs_out,
+                                                               npd_episode_t E, npd_restore_side_t R) {
+  __shared__ double lds[NPB_WAVE * NPB_OBS_PAD];
+  const size_t block_base = (size_t)blockIdx.x * NPB_WAVE;
+  size_t Ns = N;
+  NPD_SEGMENT(snap, Ns, block_base);
+  NPD_SEGMENT(f64, N, block_base);
+  const size_t p = block_base + threadIdx.x;
+  bool reset = false;
+  if (p < (size_t)n_plants) {
+    const bool terminated = done[p] != 0;
+    const int32_t len = E.len[p] + 1;
+    const double ret = reward ? E.ret[p] + reward[p] : E.ret[p];
+    const bool truncated = E.max_steps > 0 && len >= E.max_steps && !terminated;     /* termination wins */
+    reset = terminated || truncated;
+    if (E.out_len) E.out_len[p] = len;
+    if (E.out_ret) E.out_ret[p] = ret;
+    if (E.out_truncated) E.out_truncated[p] = (uint8_t)truncated;
+    E.len[p] = reset ? 0 : len;
+    E.ret[p] = reset ? 0.0 : ret;
+  }
+  if (!__any(reset)) return;
+  const uint64_t rows = __ballot(reset);
+  if (obs_out && E.final_obs) {     /* the terminal observation: this step's row, before it is replaced */
+#pragma unroll
+    for (int k = 0; k < NPB_OBS_DIM; k++) {
+      const int idx = k * NPB_WAVE + threadIdx.x;
+      if ((rows >> (idx / NPB_OBS_DIM)) & 1u) E.final_obs[block_base * NPB_OBS_DIM + idx] = obs_out[block_base * NPB_OBS_DIM + idx];
+    }
+  }
+  npd_restore_lanes(f64, snap, N, p, reset, R);
+  if (obs_out) {
+    double obs[NPB_OBS_DIM];
+    npd_observe_row(mode, f64, N, p, obs);
+    npd_store_rows_masked<NPB_OBS_DIM>(obs, obs_out, lds, block_base, rows);
+  }
+}
+/* npb_restore: the plants of mask (NULL = all) back to the snapshot, their episode counters (if any) to zero */
+__global__ __launch_bounds__(NPB_WAVE) void npb_restore_kernel(int n_plants, size_t N, npd_real_t *__restrict__ f64, const npd_real_t *__restrict__ snap,
+                                                               const uint8_t *__restrict__ mask, int32_t *__restrict__ len, double *__restrict__ ret,
+                                                               npd_restore_side_t R) {
+  const size_t block_base = (size_t)blockIdx.x * NPB_WAVE;
+  size_t Ns = N;
+  NPD_SEGMENT(snap, Ns, block_base);
+  NPD_SEGMENT(f64, N, block_base);
+  const size_t p = block_base + threadIdx.x;
+  const bool reset = mask ? (p < (size_t)n_plants && mask[p] != 0) : true;
+  if (reset && len) { len[p] = 0; ret[p] = 0.0; }
+  if (!__any(reset)) return;
+  npd_restore_lanes(f64, snap, N, p, reset, R);
 }
 
 /* construction-time state for every plant selected by mask (NULL = all): the state the reference's
@@ -876,3 +994,34 @@ extern "C" void NPB_LAUNCHER(init)(const npb_params_t *P, int n_plants, size_t n
   dim3 grid((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), block(NPB_WAVE);
   hipLaunchKernelGGL(npb_init_kernel, grid, block, 0, stream, *P, npad, (npd_real_t *)arena, mask, n_plants);
 }
+/* episodes (npb_snapshot / npb_restore / npb_set_autoreset): maint_side / maint_counts NULL unless params.maint_enabled */
+static npd_restore_side_t npd_restore_side_of(void *maint_side, int32_t *maint_counts, int n_plants) {
+  npd_restore_side_t R;
+  R.maint_entry = npd_maint_cache_of(maint_side, maint_counts, n_plants).entry; R.maint_counts = maint_counts; R.n_plants = n_plants;
+  return R;
+}
+extern "C" void NPB_LAUNCHER(restore)(int n_plants, size_t npad, void *arena, const void *snap, const uint8_t *mask, int32_t *len, double *ret,
+                                      void *maint_side, int32_t *maint_counts, hipStream_t stream) {
+  hipLaunchKernelGGL(npb_restore_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, n_plants, npad, (npd_real_t *)arena,
+                     (const npd_real_t *)snap, mask, len, ret, npd_restore_side_of(maint_side, maint_counts, n_plants));
+}
+extern "C" void NPB_LAUNCHER(episode)(int mode, int n_plants, size_t npad, void *arena, const void *snap, const uint8_t *done, const double *reward,
+                                      double *obs, int32_t *len, double *ret, int32_t *out_len, double *out_ret, uint8_t *out_truncated,
+                                      double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, hipStream_t stream) {
+  npd_episode_t E;
+  E.len = len; E.ret = ret; E.out_len = out_len; E.out_ret = out_ret; E.out_truncated = out_truncated; E.final_obs = final_obs; E.max_steps = max_steps;
+  hipLaunchKernelGGL(npb_episode_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, mode, n_plants, npad, (npd_real_t *)arena,
+                     (const npd_real_t *)snap, done, reward, obs, E, npd_restore_side_of(maint_side, maint_counts, n_plants));
+}
+#ifndef NPB_BUILD_F32
+/* npb_reset / npb_reset_reference: the episode counters of the plants they reset (mask NULL = all) back to zero */
+__global__ void npb_episode_clear_kernel(const uint8_t *__restrict__ mask, int32_t *__restrict__ len, double *__restrict__ ret, int n_plants, int npad) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npad || (mask && (p >= n_plants || !mask[p]))) return;
+  len[p] = 0; ret[p] = 0.0;
+}
+extern "C" void npb_launch_episode_clear(const uint8_t *mask, int32_t *len, double *ret, int n_plants, size_t npad, hipStream_t stream) {
+  const int n = (int)NPD_NPAD(npad);
+  hipLaunchKernelGGL(npb_episode_clear_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, mask, len, ret, n_plants, n);
+}
+#endif

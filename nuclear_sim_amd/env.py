@@ -131,6 +131,17 @@ class BatchedPlantEnv:
     Every tensor step() hands out -- obs, reward, done and each column of info, ``info["maintenance_event_count"]`` included (the
     column the step kernels keep current, npb_set_maintenance_count_buffer) -- is one of the env's own device buffers, written again
     by the next step: ``clone()`` what is to be kept (a list that appends them step after step holds N aliases of the latest values).
+
+    Episodes (no reference counterpart; gymnasium's vector-env "same-step" autoreset): ``snapshot()`` records every plant's
+    episode-start state on the device -- call it AFTER ``set_fields`` has put the initial conditions in -- and ``restore(mask)``
+    puts the masked plants back to it.  ``autoreset=True`` snapshots the construction state and has every step() put plants whose
+    episode ended (``done``, or ``max_episode_steps`` steps: truncation, which termination wins over) back to the snapshot in the
+    same step, on the device: ``obs`` then holds the restored observation for them, while reward, done and the rest of ``info``
+    describe the terminal transition; ``info`` gains ``truncated``, ``final_observation`` (this step's obs of the reset plants;
+    other rows are stale), ``episode_length`` and ``episode_return`` (as of this step: a reset plant's finished episode).  Only the
+    plant state in the arena is restored: the pre-drawn heat-source noise stream (``HeatSourceNoise``) continues across an
+    autoreset (its filter state, in the arena, is restored), and a StateLog's history-window columns do not restart.  Autoreset
+    and ``enable_diagnostics`` exclude each other (the diagnostics buffer carries plant state the snapshot does not hold).
     """
 
     action_space_size = 15       # NuclearPlantEnv sim.py:916
@@ -140,7 +151,9 @@ class BatchedPlantEnv:
                  noise_std_percent: float = 0.1, noise_seeds: Optional[Sequence[int]] = None,
                  mode: str = "full", device: int = 0, params: Optional[dict] = None, maintenance: bool = False,
                  storage: str = "f64", maintenance_thresholds: Optional[dict] = None, reactivity_components: bool = False,
-                 integrator: str = "reference"):
+                 integrator: str = "reference", autoreset: bool = False, max_episode_steps: Optional[int] = None):
+        if max_episode_steps is not None and not autoreset:
+            raise ValueError("max_episode_steps needs autoreset=True")
         if not torch.cuda.is_available():
             raise _lib.NpbError("BatchedPlantEnv needs a HIP device (torch.cuda.is_available() is False); "
                                 "there is no CPU fallback")
@@ -205,14 +218,21 @@ class BatchedPlantEnv:
         if noise_enabled and noise_seeds is not None:
             self._noise = HeatSourceNoise(noise_seeds, device=self.device)
         self._keep = []
+        self._episode = None
+        if autoreset:
+            self.snapshot()
+            self._enable_autoreset(max_episode_steps)
 
     @classmethod
     def action_test(cls, action: str, seeds: Sequence[int], dt: float = 5.0, device: int = 0, randomize: bool = True,
-                    params: Optional[dict] = None) -> "BatchedPlantEnv":
+                    params: Optional[dict] = None, autoreset: bool = False, max_episode_steps: Optional[int] = None) -> "BatchedPlantEnv":
         """One plant per seed, as data_gen's MaintenanceScenarioRunner builds them for
         ``compose_action_test_scenario(action, randomize=True, randomization_seed=seed)``
         (maintenance_scenario_runner.py:210-244): dt in minutes, ConstantHeatSource with 0.1 % noise seeded 42,
-        automatic maintenance on, initial conditions from nuclear_sim_amd.scenarios (BASELINE config 4)."""
+        automatic maintenance on, initial conditions from nuclear_sim_amd.scenarios (BASELINE config 4).  With ``autoreset`` the
+        snapshot is taken after the initial conditions are in: each plant restarts from its own."""
+        if max_episode_steps is not None and not autoreset:
+            raise ValueError("max_episode_steps needs autoreset=True")
         from . import scenarios
         env = cls(len(seeds), dt=dt, heat_source="constant", noise_enabled=True, noise_std_percent=0.1,
                   noise_seeds=[42] * len(seeds), device=device, maintenance=True, params=params)
@@ -222,6 +242,9 @@ class BatchedPlantEnv:
         # fixed from the initial conditions (nuclear_sim_amd/statelog.py)
         env.log_naming = "composed"
         env.log_side_columns = scenarios.log_side_columns(action, seeds, randomize=randomize)
+        if autoreset:
+            env.snapshot()
+            env._enable_autoreset(max_episode_steps)
         return env
 
     # ------------------------------------------------------------------ helpers
@@ -264,6 +287,31 @@ class BatchedPlantEnv:
                 buf[row].fill_(value)
             else:
                 buf[row, : self.n].masked_fill_(mask.to(torch.bool), value)
+
+    def snapshot(self) -> None:
+        """Record every plant's current state as its episode start (npb_snapshot: one device-to-device copy of the arena).  Call it
+        after ``set_fields`` has put the initial conditions in; ``restore`` and the autoreset go back to it."""
+        _lib.check(self.L.npb_snapshot(self._h, self._stream()), self._h)
+
+    def restore(self, mask=None) -> torch.Tensor:
+        """The plants of ``mask`` (None = all) back to the state ``snapshot()`` recorded -- unlike ``reset()``, with their own initial
+        conditions -- and their episode counters to zero.  Returns the observation, as ``reset()`` does."""
+        m = self._col(mask, torch.uint8)
+        self._reset_carried_diagnostics(m)
+        _lib.check(self.L.npb_restore(self._h, self._p(m), self._stream()), self._h)
+        return self.get_observation()
+
+    def _enable_autoreset(self, max_episode_steps: Optional[int]) -> None:
+        """npb_set_autoreset on the snapshot taken, and the four info columns the episode kernel writes"""
+        with torch.cuda.device(self.device):
+            self._episode = {"truncated": torch.zeros(self.n, dtype=torch.uint8, device=self.device),
+                             "final_observation": torch.zeros((self.n, 22), dtype=torch.float64, device=self.device),
+                             "episode_length": torch.zeros(self.n, dtype=torch.int32, device=self.device),
+                             "episode_return": torch.zeros(self.n, dtype=torch.float64, device=self.device)}
+        _lib.check(self.L.npb_set_autoreset(self._h, 1, int(max_episode_steps or 0)), self._h)
+        e = self._episode
+        _lib.check(self.L.npb_set_episode_buffers(self._h, self._p(e["episode_length"]), self._p(e["episode_return"]), self._p(e["truncated"]),
+                                                  self._p(e["final_observation"])), self._h)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -429,6 +477,8 @@ class BatchedPlantEnv:
         if self.params.maint_enabled:  # bit-exact counterpart of AutoMaintenanceSystem.maintenance_actions_performed
             # a column the step keeps current (npb_set_maintenance_count_buffer): no gather launch per step
             info["maintenance_event_count"] = self._event_counts if self._event_counts is not None else self.get_field("maint.maintenance_actions_performed")
+        if self._episode is not None:     # autoreset: written by the episode kernel behind the step (npb_set_autoreset)
+            info.update(self._episode)
         return self._obs, self._reward, self._done, info
 
 
