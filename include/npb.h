@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define NPB_VERSION 143 /* 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
+#define NPB_VERSION 144 /* 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
 #ifndef NPB_API
 #define NPB_API __attribute__((visibility("default")))
 #endif
@@ -309,7 +309,8 @@ NPB_API int npb_restore(NpbHandle *h, const uint8_t *mask, void *stream);
  * a plant with done | truncated goes back to the snapshot as npb_restore would, its obs row is first copied to final_obs and
  * then replaced by the restored state's observation; reward, info and trip_flags keep describing the terminal transition.  The
  * episode buffers (npb_set_episode_buffers) receive len / ret as of this step (a reset plant's: its finished episode's) and the
- * truncation flag.  Needs a snapshot; allocates the handle's carried counters (int32 length[pitch], double return[pitch]) and
+ * truncation flag.  With a start bank and slots (npb_set_start_bank, npb_set_start_slots) the reset plants are restored from their
+ * bank entries instead.  Needs a snapshot, or a bank and slots; allocates the handle's carried counters (int32 length[pitch], double return[pitch]) and
  * zeroes them; npb_step then needs a non-NULL done column.  Refused (NPB_EINVAL) while npb_set_diagnostics is set, as that is
  * refused while autoreset is on: the diagnostics buffer carries plant state outside the arena.  enabled = 0 turns it off.
  * npb_reset, npb_reset_reference and npb_restore zero the counters of the plants they reset. */
@@ -317,6 +318,28 @@ NPB_API int npb_set_autoreset(NpbHandle *h, int enabled, int max_episode_steps /
 /* the caller's output columns of the episode kernel (device; each may be NULL): length int32[n], ret double[n], truncated
  * uint8[n], final_obs double[n][NPB_OBS_DIM] (rows of plants reset on the step; other rows are left as they were) */
 NPB_API int npb_set_episode_buffers(NpbHandle *h, int32_t *length, double *ret, uint8_t *truncated, double *final_obs /* [n,22] */);
+/* Start bank: restarts from a bank of M start states instead of each plant's own snapshot lane (M independent of n).
+ * npb_set_start_bank: copy src's whole arena into a bank arena h owns -- one device-to-device copy on `stream`; M =
+ * npb_num_plants(src); the bank keeps src's layout (pitch, segment size), src may be h itself.  NPB_EINVAL if the storage type or
+ * the device differs.  Called again it replaces the bank (reallocating only if the new one needs more room).  src = NULL frees the
+ * bank, refused while autoreset is on and the handle has no snapshot to fall back on.  npb_destroy frees it.  Setting a bank
+ * (first, or after freeing it) puts every plant's carried start entry (npb_set_episode_start_buffer) to -1. */
+NPB_API int npb_set_start_bank(NpbHandle *h, const NpbHandle *src, void *stream);
+/* which bank entry each restore takes (device int32[n] columns the caller owns; episode_start may be NULL): plant p restored from the
+ * bank takes entry s = ((next_slot[p] % M) + M) % M, defined for any value the caller wrote, and the library then stores
+ * next_slot[p] = (s + advance) % M and episode_start[p] = s.  advance = 0 leaves every restart to the caller (e.g. random slots written
+ * on the same stream).  NPB_EINVAL for next_slot = NULL or advance < 0.  With a bank and slots, npb_step's autoreset restores from
+ * the bank (npb_episode_bank_kernel) instead of the snapshot. */
+NPB_API int npb_set_start_slots(NpbHandle *h, int32_t *next_slot, int32_t *episode_start, int advance);
+/* npb_restore's counterpart: the plants of mask (device, uint8[n], NULL = all) from their bank entries, episode counters (if any) to
+ * zero; with params.maint_enabled their cooldown cache and event counts follow, as npb_restore's do.  NPB_EINVAL without a bank and
+ * slots.  Follow with npb_observe for the restored observation. */
+NPB_API int npb_restore_bank(NpbHandle *h, const uint8_t *mask, void *stream);
+/* a caller column (device int32[n], NULL = none) the bank episode kernel fills on every step with the bank entry of the episode this
+ * step's transition belonged to (a plant reset on the step: its finished episode's, as length / ret of npb_set_episode_buffers).
+ * -1 for an episode that did not start from the bank: construction, npb_reset, npb_reset_reference and npb_restore put the carried
+ * entry to -1. */
+NPB_API int npb_set_episode_start_buffer(NpbHandle *h, int32_t *out_start);
 
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the

@@ -203,6 +203,11 @@ def load():
         L.npb_restore.argtypes = [vp, vp, vp]
         L.npb_set_autoreset.argtypes = [vp, ci, ci]
         L.npb_set_episode_buffers.argtypes = [vp, vp, vp, vp, vp]
+    if hasattr(L, "npb_set_start_bank"):     # ABI 144: restarts from a bank of start states
+        L.npb_set_start_bank.argtypes = [vp, vp, vp]
+        L.npb_set_start_slots.argtypes = [vp, vp, vp, ci]
+        L.npb_restore_bank.argtypes = [vp, vp, vp]
+        L.npb_set_episode_start_buffer.argtypes = [vp, vp]
     if L.npb_num_f64() != SCHEMA.total_f64 or L.npb_num_i32() != SCHEMA.total_i32:
         raise NpbError("libnpb.so was built against a different include/npb_fields.h (%d/%d vs %d/%d): rebuild"
                        % (L.npb_num_f64(), L.npb_num_i32(), SCHEMA.total_f64, SCHEMA.total_i32))

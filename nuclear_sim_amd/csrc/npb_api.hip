@@ -34,6 +34,10 @@ struct NpbHandle {
   int32_t *ep_len; double *ep_ret; /* npb_set_autoreset: carried steps / summed reward of each plant's running episode ([pitch] each), or NULL */
   bool autoreset; int max_episode_steps;
   int32_t *ep_out_len; double *ep_out_ret; uint8_t *ep_out_truncated; double *ep_final_obs;   /* npb_set_episode_buffers: the caller's columns, or NULL */
+  void *bank; size_t bank_bytes; size_t bank_N; int bank_M;   /* npb_set_start_bank: the bank arena (src's layout), its allocation, its packed pitch (NPB_N of src), its entries */
+  int32_t *ep_start;   /* with a bank: carried bank entry of each plant's running episode, -1 = not from the bank ([pitch]), or NULL */
+  int32_t *next_slot; int32_t *slot_start; int slot_advance;  /* npb_set_start_slots: the caller's columns (next_slot NULL = no slots) */
+  int32_t *ep_out_start;                                       /* npb_set_episode_start_buffer: the caller's column, or NULL */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
   std::vector<int> plan_key;
   std::string error;
@@ -92,6 +96,13 @@ static size_t arena_columns(int storage) { return storage == NPB_STORAGE_F32 ? (
 static size_t arena_plants(const NpbHandle *h) { return h->seg ? (h->pitch + h->seg - 1) / h->seg * h->seg : h->pitch; }
 /* what the launchers take as the column pitch: the pitch with the segment size in the upper half (npb_kernels.hip, NPD_SEGMENT) */
 #define NPB_N(h) ((size_t)(h)->pitch | ((size_t)(h)->seg << 32))
+/* the bank as the bank launchers take it */
+static npb_bank_t bank_of(const NpbHandle *h) {
+  npb_bank_t B;
+  B.arena = h->bank; B.N = h->bank_N; B.M = h->bank_M;
+  B.next_slot = h->next_slot; B.episode_start = h->slot_start; B.advance = h->slot_advance; B.start = h->ep_start; B.out_start = h->ep_out_start;
+  return B;
+}
 
 /* Where an arena lands in physical memory changes the step kernel's time when the bytes a step touches are about the
  * size of the 256 MB Infinity Cache (65 536 fp64 plants: 276 MB): handles created one after another in one process run
@@ -264,6 +275,8 @@ int npb_destroy(NpbHandle *h) {
   if (h->plan_dev) (void)hipFree(h->plan_dev);
   if (h->snap) (void)hipFree(h->snap);
   if (h->ep_len) (void)hipFree(h->ep_len);
+  if (h->bank) (void)hipFree(h->bank);
+  if (h->ep_start) (void)hipFree(h->ep_start);
   delete h;
   return NPB_OK;
 }
@@ -326,6 +339,7 @@ int npb_reset(NpbHandle *h, const uint8_t *mask, void *stream) {
   h->maint_cache_stale = true;
   (h->storage == NPB_STORAGE_F32 ? npb32_launch_init : npb_launch_init)(&h->params, h->n_plants, NPB_N(h), h->f64, mask, (hipStream_t)stream);
   if (h->ep_len) npb_launch_episode_clear(mask, h->ep_len, h->ep_ret, h->n_plants, h->pitch, (hipStream_t)stream);
+  if (h->ep_start) npb_launch_start_clear(mask, h->ep_start, h->n_plants, h->pitch, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -336,6 +350,7 @@ int npb_reset_reference(NpbHandle *h, const uint8_t *mask, int start_at_steady_s
   h->maint_cache_stale = true;
   (h->storage == NPB_STORAGE_F32 ? npb32_launch_reset : npb_launch_reset)(&h->params, h->n_plants, NPB_N(h), h->f64, mask, start_at_steady_state != 0, (hipStream_t)stream);
   if (h->ep_len) npb_launch_episode_clear(mask, h->ep_len, h->ep_ret, h->n_plants, h->pitch, (hipStream_t)stream);
+  if (h->ep_start) npb_launch_start_clear(mask, h->ep_start, h->n_plants, h->pitch, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -477,7 +492,11 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
                                                  maint ? &table : nullptr, maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
   if (maint && h->params.mode != NPB_MODE_FULL)   /* a full-mode step kernel has run the rule itself, for the waves whose pump phase found something */
     (narrow ? npb32_launch_maint : npb_launch_maint)(NPB_N(h), h->f64, h->maint_side, h->maint_counts, h->n_plants, (hipStream_t)stream);
-  if (h->autoreset)   /* same stream, nothing read back, the maintenance cache kept per plant by the kernel itself */
+  if (h->autoreset && h->bank && h->next_slot)   /* the same, restoring from the bank */
+    (narrow ? npb32_launch_episode_bank : npb_launch_episode_bank)(h->params.mode, h->n_plants, NPB_N(h), h->f64, bank_of(h), done, reward, obs, h->ep_len, h->ep_ret,
+                                                                   h->ep_out_len, h->ep_out_ret, h->ep_out_truncated, h->ep_final_obs, h->max_episode_steps,
+                                                                   maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
+  else if (h->autoreset)   /* same stream, nothing read back, the maintenance cache kept per plant by the kernel itself */
     (narrow ? npb32_launch_episode : npb_launch_episode)(h->params.mode, h->n_plants, NPB_N(h), h->f64, h->snap, done, reward, obs, h->ep_len, h->ep_ret,
                                                          h->ep_out_len, h->ep_out_ret, h->ep_out_truncated, h->ep_final_obs, h->max_episode_steps,
                                                          maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
@@ -505,6 +524,7 @@ int npb_restore(NpbHandle *h, const uint8_t *mask, void *stream) {
   const bool maint = h->params.maint_enabled != 0;
   (h->storage == NPB_STORAGE_F32 ? npb32_launch_restore : npb_launch_restore)(h->n_plants, NPB_N(h), h->f64, h->snap, mask, h->ep_len, h->ep_ret,
                                                                               maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
+  if (h->ep_start) npb_launch_start_clear(mask, h->ep_start, h->n_plants, h->pitch, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -513,7 +533,8 @@ int npb_set_autoreset(NpbHandle *h, int enabled, int max_episode_steps) {
   if (!h) return NPB_EINVAL;
   if (!enabled) { h->autoreset = false; return NPB_OK; }
   if (max_episode_steps < 0) return fail(h, NPB_EINVAL, "npb_set_autoreset: max_episode_steps must be >= 0 (0 = no limit)");
-  if (!h->snap) return fail(h, NPB_EINVAL, "npb_set_autoreset: no snapshot (npb_snapshot) to reset to");
+  if (!h->snap && !(h->bank && h->next_slot))
+    return fail(h, NPB_EINVAL, "npb_set_autoreset: no snapshot (npb_snapshot), nor a start bank with slots (npb_set_start_bank, npb_set_start_slots), to reset to");
   if (h->diag) return fail(h, NPB_EINVAL, "npb_set_autoreset: diagnostics are on (npb_set_diagnostics); their buffer carries plant state the snapshot does not hold");
   NPB_USE_DEVICE(h);
   if (!h->ep_len) {     /* one allocation: [pitch] int32 lengths, then [pitch] double returns */
@@ -532,6 +553,64 @@ int npb_set_autoreset(NpbHandle *h, int enabled, int max_episode_steps) {
 int npb_set_episode_buffers(NpbHandle *h, int32_t *length, double *ret, uint8_t *truncated, double *final_obs) {
   if (!h) return NPB_EINVAL;
   h->ep_out_len = length; h->ep_out_ret = ret; h->ep_out_truncated = truncated; h->ep_final_obs = final_obs;
+  return NPB_OK;
+}
+
+int npb_set_start_bank(NpbHandle *h, const NpbHandle *src, void *stream) {
+  if (!h) return NPB_EINVAL;
+  NPB_USE_DEVICE(h);
+  if (!src) {
+    if (h->autoreset && !h->snap)
+      return fail(h, NPB_EINVAL, "npb_set_start_bank: autoreset is on and restores from the bank; without it there is no snapshot (npb_snapshot) to fall back on");
+    if (h->bank) (void)hipFree(h->bank);
+    if (h->ep_start) (void)hipFree(h->ep_start);
+    h->bank = nullptr; h->bank_bytes = 0; h->bank_N = 0; h->bank_M = 0; h->ep_start = nullptr;
+    return NPB_OK;
+  }
+  if (src->storage != h->storage)
+    return fail(h, NPB_EINVAL, "npb_set_start_bank: the bank handle's storage type differs from this handle's (npb_create_storage)");
+  if (src->device != h->device)
+    return fail(h, NPB_EINVAL, "npb_set_start_bank: the bank handle lives on another device");
+  const size_t bytes = arena_columns(src->storage) * arena_plants(src) * src->real_bytes;
+  if (!h->ep_start) {       /* a bank after none: no running episode started from it */
+    hipError_t e = hipMalloc((void **)&h->ep_start, h->pitch * sizeof(int32_t));
+    if (e != hipSuccess) { h->ep_start = nullptr; return fail(h, NPB_EHIP, "npb_set_start_bank: hipMalloc of the start entries failed", e); }
+    NPB_HIP(h, hipMemsetAsync(h->ep_start, 0xff, h->pitch * sizeof(int32_t), (hipStream_t)stream));
+  }
+  if (bytes > h->bank_bytes) {
+    if (h->bank) (void)hipFree(h->bank);
+    h->bank = nullptr; h->bank_bytes = 0; h->bank_M = 0;
+    hipError_t e = hipMalloc(&h->bank, bytes);
+    if (e != hipSuccess) { h->bank = nullptr; return fail(h, NPB_EHIP, "npb_set_start_bank: hipMalloc of the bank arena failed", e); }
+    h->bank_bytes = bytes;
+  }
+  NPB_HIP(h, hipMemcpyAsync(h->bank, src->f64, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  h->bank_N = NPB_N(src); h->bank_M = src->n_plants;
+  return NPB_OK;
+}
+
+int npb_set_start_slots(NpbHandle *h, int32_t *next_slot, int32_t *episode_start, int advance) {
+  if (!h) return NPB_EINVAL;
+  if (!next_slot) return fail(h, NPB_EINVAL, "npb_set_start_slots: next_slot must not be NULL");
+  if (advance < 0) return fail(h, NPB_EINVAL, "npb_set_start_slots: advance must be >= 0");
+  h->next_slot = next_slot; h->slot_start = episode_start; h->slot_advance = advance;
+  return NPB_OK;
+}
+
+int npb_restore_bank(NpbHandle *h, const uint8_t *mask, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->bank || !h->next_slot) return fail(h, NPB_EINVAL, "npb_restore_bank: no start bank (npb_set_start_bank) with slots (npb_set_start_slots) to restore from");
+  NPB_USE_DEVICE(h);
+  const bool maint = h->params.maint_enabled != 0;
+  (h->storage == NPB_STORAGE_F32 ? npb32_launch_restore_bank : npb_launch_restore_bank)(h->n_plants, NPB_N(h), h->f64, bank_of(h), mask, h->ep_len, h->ep_ret,
+                                                                                        maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+
+int npb_set_episode_start_buffer(NpbHandle *h, int32_t *out_start) {
+  if (!h) return NPB_EINVAL;
+  h->ep_out_start = out_start;
   return NPB_OK;
 }
 

@@ -11,6 +11,17 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+/* a start bank (npb_set_start_bank) and its slot columns (npb_set_start_slots) as the bank kernels take them */
+typedef struct {
+  const void *arena;        /* the bank arena: M plants in the layout of the handle it was copied from */
+  size_t N;                 /* its packed pitch: pitch | segment size << 32 (NPD_SEGMENT) */
+  int M;                    /* its entries */
+  int32_t *next_slot;       /* the caller's [n]: a restored plant takes entry ((next_slot % M) + M) % M, then next_slot = (s + advance) % M */
+  int32_t *episode_start;   /* the caller's [n], or NULL: the entry a restored plant took */
+  int advance;
+  int32_t *start;           /* carried [pitch]: the entry of each plant's running episode, -1 = not from the bank */
+  int32_t *out_start;       /* the caller's [n], or NULL: the episode kernel's copy of `start` as of each step */
+} npb_bank_t;
 #define NPB__DECL(prefix) \
   int prefix##step(const npb_params_t *P, int n_plants, size_t npad, void *arena, const int32_t *action, \
                     const double *magnitude, const double *setpoint, const double *noise_z, const double *cw_temp, \
@@ -33,12 +44,19 @@ extern "C" {
                        void *maint_side, int32_t *maint_counts, hipStream_t stream); \
   void prefix##episode(int mode, int n_plants, size_t npad, void *arena, const void *snap, const uint8_t *done, const double *reward, \
                        double *obs, int32_t *len, double *ret, int32_t *out_len, double *out_ret, uint8_t *out_truncated, \
-                       double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, hipStream_t stream);
+                       double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, hipStream_t stream); \
+  /* the same from a start bank */ \
+  void prefix##restore_bank(int n_plants, size_t npad, void *arena, npb_bank_t bank, const uint8_t *mask, int32_t *len, double *ret, \
+                            void *maint_side, int32_t *maint_counts, hipStream_t stream); \
+  void prefix##episode_bank(int mode, int n_plants, size_t npad, void *arena, npb_bank_t bank, const uint8_t *done, const double *reward, \
+                            double *obs, int32_t *len, double *ret, int32_t *out_len, double *out_ret, uint8_t *out_truncated, \
+                            double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, hipStream_t stream);
 NPB__DECL(npb_launch_)
 NPB__DECL(npb32_launch_)
 #undef NPB__DECL
 void npb_launch_touch(size_t npad, double *arena, hipStream_t stream);
 void npb_launch_episode_clear(const uint8_t *mask, int32_t *len, double *ret, int n_plants, size_t npad, hipStream_t stream);
+void npb_launch_start_clear(const uint8_t *mask, int32_t *start, int n_plants, size_t npad, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

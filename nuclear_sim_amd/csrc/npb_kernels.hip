@@ -649,8 +649,10 @@ __device__ __forceinline__ void npd_restore_lanes(npd_real_t *__restrict__ f64, 
     R.maint_counts[p] = NPD_I32_COL(MAINT, npb_maint_t, maintenance_actions_performed, 0);
   }
 }
-/* [64][W] rows held one per lane -> row-major global memory, only the rows whose bit is set in `rows` (npd_store_rows otherwise) */
-template <int W>
+/* [64][W] rows held one per lane -> row-major global memory, only the rows whose bit is set in `rows` (npd_store_rows otherwise).
+ * TAG only separates instantiations: the bank episode kernel calls its own, because sharing one with npb_episode_kernel changed
+ * that kernel's address arithmetic (same registers, other instructions) */
+template <int W, int TAG = 0>
 __device__ __forceinline__ void npd_store_rows_masked(const double *row, double *__restrict__ out, double *lds, size_t block_base, uint64_t rows) {
   const int lane = threadIdx.x;
 #pragma unroll
@@ -720,6 +722,103 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_restore_kernel(int n_plants, siz
   if (reset && len) { len[p] = 0; ret[p] = 0.0; }
   if (!__any(reset)) return;
   npd_restore_lanes(f64, snap, N, p, reset, R);
+}
+
+/* ---- start bank (npb_set_start_bank / npb_restore_bank, and the autoreset with a bank): the source of a restore is entry s of the
+ * bank, chosen per plant (npd_bank_take), addressed through the bank's own pitch and segment.  The bank kernels are separate
+ * kernels, so that the snapshot path above keeps its code. */
+/* the bank entry a restored plant takes from its slot, and the slot and start columns it leaves behind (include/npb.h) */
+__device__ __forceinline__ int32_t npd_bank_take(const npb_bank_t &B, size_t p) {
+  int32_t s = B.next_slot[p] % B.M;
+  if (s < 0) s += B.M;                  /* ((next % M) + M) % M, for any value the caller wrote */
+  B.next_slot[p] = (int32_t)(((uint32_t)s + (uint32_t)B.advance) % (uint32_t)B.M);    /* s, advance < 2^31: no wrap */
+  if (B.episode_start) B.episode_start[p] = s;
+  B.start[p] = s;
+  return s;
+}
+/* npd_restore_lanes with a per-lane source: the wave's plants with `reset` set from bank entry s of their lane; f64 / N already moved
+ * to the wave's segment, the bank (bank, Nb packed) is moved per lane.  Neighbouring lanes generally read different entries, so the
+ * loads are not coalesced (one line per lane and column); the copy stays latency-bound and the loads of U columns are issued before
+ * their stores */
+__device__ __forceinline__ void npd_restore_lanes_bank(npd_real_t *__restrict__ f64, size_t N, size_t p, bool reset, const npd_real_t *__restrict__ bank,
+                                                       size_t Nb, int32_t s, const npd_restore_side_t &R) {
+  if (!reset) return;
+  NPD_SEGMENT(bank, Nb, (size_t)s);
+  npd_word_t *dst = reinterpret_cast<npd_word_t *>(f64) + p;
+  const npd_word_t *src = reinterpret_cast<const npd_word_t *>(bank) + s;
+  constexpr int U = 32;
+#pragma unroll 1
+  for (int c0 = 0; c0 < NPD_ARENA_COLS; c0 += U) {
+    npd_word_t v[U];
+#pragma unroll
+    for (int u = 0; u < U; u++)
+      if (c0 + u < NPD_ARENA_COLS) v[u] = __builtin_nontemporal_load(&src[(size_t)(c0 + u) * Nb]);
+#pragma unroll
+    for (int u = 0; u < U; u++)
+      if (c0 + u < NPD_ARENA_COLS) dst[(size_t)(c0 + u) * N] = v[u];
+  }
+  if (R.maint_entry) {                /* the cooldowns of the restored stamps are unknown to the cache: look */
+    const npd_u32x4 zero = {0u, 0u, 0u, 0u};
+    R.maint_entry[p * 2] = zero; R.maint_entry[p * 2 + 1] = zero;
+  }
+  if (R.maint_counts && p < (size_t)R.n_plants) {
+    int32_t *counts = R.maint_counts + p;
+    const npd_real_t *f64 = bank;     /* (the member macro reads `f64`, `N` and `p`: the bank entry's) */
+    const size_t N = Nb, p = (size_t)s;
+    *counts = NPD_I32_COL(MAINT, npb_maint_t, maintenance_actions_performed, 0);
+  }
+}
+/* npb_episode_kernel restoring from the bank; also hands out the bank entry of each plant's episode as of this step */
+__global__ __launch_bounds__(NPB_WAVE) void npb_episode_bank_kernel(int mode, int n_plants, size_t N, npd_real_t *__restrict__ f64, npb_bank_t B,
+                                                                    const uint8_t *__restrict__ done, const double *__restrict__ reward, double *__restrict__ obs_out,
+                                                                    npd_episode_t E, npd_restore_side_t R) {
+  __shared__ double lds[NPB_WAVE * NPB_OBS_PAD];
+  const size_t block_base = (size_t)blockIdx.x * NPB_WAVE;
+  NPD_SEGMENT(f64, N, block_base);
+  const size_t p = block_base + threadIdx.x;
+  bool reset = false;
+  if (p < (size_t)n_plants) {
+    const bool terminated = done[p] != 0;
+    const int32_t len = E.len[p] + 1;
+    const double ret = reward ? E.ret[p] + reward[p] : E.ret[p];
+    const bool truncated = E.max_steps > 0 && len >= E.max_steps && !terminated;     /* termination wins */
+    reset = terminated || truncated;
+    if (E.out_len) E.out_len[p] = len;
+    if (E.out_ret) E.out_ret[p] = ret;
+    if (E.out_truncated) E.out_truncated[p] = (uint8_t)truncated;
+    if (B.out_start) B.out_start[p] = B.start[p];      /* the episode this step's transition belonged to */
+    E.len[p] = reset ? 0 : len;
+    E.ret[p] = reset ? 0.0 : ret;
+  }
+  if (!__any(reset)) return;
+  const uint64_t rows = __ballot(reset);
+  if (obs_out && E.final_obs) {     /* the terminal observation: this step's row, before it is replaced */
+#pragma unroll
+    for (int k = 0; k < NPB_OBS_DIM; k++) {
+      const int idx = k * NPB_WAVE + threadIdx.x;
+      if ((rows >> (idx / NPB_OBS_DIM)) & 1u) E.final_obs[block_base * NPB_OBS_DIM + idx] = obs_out[block_base * NPB_OBS_DIM + idx];
+    }
+  }
+  const int32_t s = reset ? npd_bank_take(B, p) : 0;
+  npd_restore_lanes_bank(f64, N, p, reset, (const npd_real_t *)B.arena, B.N, s, R);
+  if (obs_out) {
+    double obs[NPB_OBS_DIM];
+    npd_observe_row(mode, f64, N, p, obs);
+    npd_store_rows_masked<NPB_OBS_DIM, 1>(obs, obs_out, lds, block_base, rows);
+  }
+}
+/* npb_restore_bank: the plants of mask (NULL = all) from their bank entries, their episode counters (if any) to zero */
+__global__ __launch_bounds__(NPB_WAVE) void npb_restore_bank_kernel(int n_plants, size_t N, npd_real_t *__restrict__ f64, npb_bank_t B,
+                                                                    const uint8_t *__restrict__ mask, int32_t *__restrict__ len, double *__restrict__ ret,
+                                                                    npd_restore_side_t R) {
+  const size_t block_base = (size_t)blockIdx.x * NPB_WAVE;
+  NPD_SEGMENT(f64, N, block_base);
+  const size_t p = block_base + threadIdx.x;
+  const bool reset = p < (size_t)n_plants && (!mask || mask[p] != 0);     /* the slot columns have n entries: no padding lane */
+  if (reset && len) { len[p] = 0; ret[p] = 0.0; }
+  if (!__any(reset)) return;
+  const int32_t s = reset ? npd_bank_take(B, p) : 0;
+  npd_restore_lanes_bank(f64, N, p, reset, (const npd_real_t *)B.arena, B.N, s, R);
 }
 
 /* construction-time state for every plant selected by mask (NULL = all): the state the reference's
@@ -1013,6 +1112,19 @@ extern "C" void NPB_LAUNCHER(episode)(int mode, int n_plants, size_t npad, void 
   hipLaunchKernelGGL(npb_episode_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, mode, n_plants, npad, (npd_real_t *)arena,
                      (const npd_real_t *)snap, done, reward, obs, E, npd_restore_side_of(maint_side, maint_counts, n_plants));
 }
+extern "C" void NPB_LAUNCHER(restore_bank)(int n_plants, size_t npad, void *arena, npb_bank_t bank, const uint8_t *mask, int32_t *len, double *ret,
+                                           void *maint_side, int32_t *maint_counts, hipStream_t stream) {
+  hipLaunchKernelGGL(npb_restore_bank_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, n_plants, npad, (npd_real_t *)arena,
+                     bank, mask, len, ret, npd_restore_side_of(maint_side, maint_counts, n_plants));
+}
+extern "C" void NPB_LAUNCHER(episode_bank)(int mode, int n_plants, size_t npad, void *arena, npb_bank_t bank, const uint8_t *done, const double *reward,
+                                           double *obs, int32_t *len, double *ret, int32_t *out_len, double *out_ret, uint8_t *out_truncated,
+                                           double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, hipStream_t stream) {
+  npd_episode_t E;
+  E.len = len; E.ret = ret; E.out_len = out_len; E.out_ret = out_ret; E.out_truncated = out_truncated; E.final_obs = final_obs; E.max_steps = max_steps;
+  hipLaunchKernelGGL(npb_episode_bank_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, mode, n_plants, npad, (npd_real_t *)arena,
+                     bank, done, reward, obs, E, npd_restore_side_of(maint_side, maint_counts, n_plants));
+}
 #ifndef NPB_BUILD_F32
 /* npb_reset / npb_reset_reference: the episode counters of the plants they reset (mask NULL = all) back to zero */
 __global__ void npb_episode_clear_kernel(const uint8_t *__restrict__ mask, int32_t *__restrict__ len, double *__restrict__ ret, int n_plants, int npad) {
@@ -1023,5 +1135,15 @@ __global__ void npb_episode_clear_kernel(const uint8_t *__restrict__ mask, int32
 extern "C" void npb_launch_episode_clear(const uint8_t *mask, int32_t *len, double *ret, int n_plants, size_t npad, hipStream_t stream) {
   const int n = (int)NPD_NPAD(npad);
   hipLaunchKernelGGL(npb_episode_clear_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, mask, len, ret, n_plants, n);
+}
+/* npb_reset / npb_reset_reference / npb_restore with a start bank: the carried start entries of the plants they reset to -1 (not from the bank) */
+__global__ void npb_start_clear_kernel(const uint8_t *__restrict__ mask, int32_t *__restrict__ start, int n_plants, int npad) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npad || (mask && (p >= n_plants || !mask[p]))) return;
+  start[p] = -1;
+}
+extern "C" void npb_launch_start_clear(const uint8_t *mask, int32_t *start, int n_plants, size_t npad, hipStream_t stream) {
+  const int n = (int)NPD_NPAD(npad);
+  hipLaunchKernelGGL(npb_start_clear_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, mask, start, n_plants, n);
 }
 #endif

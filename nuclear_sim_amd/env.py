@@ -142,6 +142,12 @@ class BatchedPlantEnv:
     plant state in the arena is restored: the pre-drawn heat-source noise stream (``HeatSourceNoise``) continues across an
     autoreset (its filter state, in the arena, is restored), and a StateLog's history-window columns do not restart.  Autoreset
     and ``enable_diagnostics`` exclude each other (the diagnostics buffer carries plant state the snapshot does not hold).
+
+    Start bank: ``set_start_bank(bank_env)`` copies another batch's states (M plants, any M) into a bank the handle owns; from then
+    on the autoreset, and ``restore_from_bank(mask)``, restore a plant from bank entry ``next_start_slots[p] mod M`` instead of its
+    own snapshot lane, and advance its slot, all on the device.  ``info["episode_start"]`` is the bank entry of the episode each
+    step's transition belonged to (-1: not from the bank), ``episode_start`` the entry of each plant's last bank restore.  A
+    restored plant takes the entry's clock and maintenance stamps; the heat-source noise stream stays with the plant position.
     """
 
     action_space_size = 15       # NuclearPlantEnv sim.py:916
@@ -219,18 +225,22 @@ class BatchedPlantEnv:
             self._noise = HeatSourceNoise(noise_seeds, device=self.device)
         self._keep = []
         self._episode = None
+        self._bank = None
         if autoreset:
             self.snapshot()
             self._enable_autoreset(max_episode_steps)
 
     @classmethod
     def action_test(cls, action: str, seeds: Sequence[int], dt: float = 5.0, device: int = 0, randomize: bool = True,
-                    params: Optional[dict] = None, autoreset: bool = False, max_episode_steps: Optional[int] = None) -> "BatchedPlantEnv":
+                    params: Optional[dict] = None, autoreset: bool = False, max_episode_steps: Optional[int] = None,
+                    bank_seeds: Optional[Sequence[int]] = None) -> "BatchedPlantEnv":
         """One plant per seed, as data_gen's MaintenanceScenarioRunner builds them for
         ``compose_action_test_scenario(action, randomize=True, randomization_seed=seed)``
         (maintenance_scenario_runner.py:210-244): dt in minutes, ConstantHeatSource with 0.1 % noise seeded 42,
         automatic maintenance on, initial conditions from nuclear_sim_amd.scenarios (BASELINE config 4).  With ``autoreset`` the
-        snapshot is taken after the initial conditions are in: each plant restarts from its own."""
+        snapshot is taken after the initial conditions are in: each plant restarts from its own.  With ``bank_seeds`` later
+        episodes start from a bank built as ``action_test(action, bank_seeds)`` with the same ``randomize``, ``dt`` and ``params``
+        (``set_start_bank`` with its default slots): each restart draws a fresh scenario, as the data-gen runner's episodes do."""
         if max_episode_steps is not None and not autoreset:
             raise ValueError("max_episode_steps needs autoreset=True")
         from . import scenarios
@@ -245,6 +255,11 @@ class BatchedPlantEnv:
         if autoreset:
             env.snapshot()
             env._enable_autoreset(max_episode_steps)
+        if bank_seeds is not None:
+            bank = cls.action_test(action, bank_seeds, dt=dt, device=device, randomize=randomize, params=params)
+            env.set_start_bank(bank)
+            torch.cuda.current_stream(env.device).synchronize()     # the copy has read the bank batch's arena
+            bank.close()
         return env
 
     # ------------------------------------------------------------------ helpers
@@ -299,6 +314,42 @@ class BatchedPlantEnv:
         m = self._col(mask, torch.uint8)
         self._reset_carried_diagnostics(m)
         _lib.check(self.L.npb_restore(self._h, self._p(m), self._stream()), self._h)
+        return self.get_observation()
+
+    def set_start_bank(self, bank_env: Optional["BatchedPlantEnv"], slots=None, advance: Optional[int] = None) -> None:
+        """Copy the states of ``bank_env``'s M plants (same storage type and device; ``self`` allowed) into a start bank
+        (npb_set_start_bank: one device-to-device copy); the autoreset and ``restore_from_bank`` then restore plant p from entry
+        ``next_start_slots[p] mod M`` and advance that slot by ``advance``.  ``slots`` defaults to ``arange(n) % M`` and
+        ``advance`` to n, so plant p walks through entries p, p + n, p + 2n, ... mod M; with ``advance = 0`` the caller picks
+        every restart by writing ``next_start_slots``.  ``bank_env = None`` frees the bank."""
+        if bank_env is None:
+            _lib.check(self.L.npb_set_start_bank(self._h, None, self._stream()), self._h)
+            self._bank = None
+            return
+        adv = self.n if advance is None else int(advance)
+        if adv < 0:
+            raise ValueError("advance must be >= 0")
+        _lib.check(self.L.npb_set_start_bank(self._h, bank_env._h, self._stream()), self._h)
+        M = bank_env.n
+        with torch.cuda.device(self.device):
+            if self._bank is None:
+                self.next_start_slots = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+                self.episode_start = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
+                self._episode_start_out = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
+            if slots is None:
+                self.next_start_slots.copy_(torch.arange(self.n, device=self.device) % M)
+            else:
+                self.next_start_slots.copy_(self._col(slots, torch.int32))
+        _lib.check(self.L.npb_set_start_slots(self._h, self._p(self.next_start_slots), self._p(self.episode_start), adv), self._h)
+        _lib.check(self.L.npb_set_episode_start_buffer(self._h, self._p(self._episode_start_out)), self._h)
+        self._bank = {"entries": M, "advance": adv}
+
+    def restore_from_bank(self, mask=None) -> torch.Tensor:
+        """The plants of ``mask`` (None = all) from their bank entries (``set_start_bank``; npb_restore_bank), their slots
+        advanced and their episode counters to zero.  Returns the observation, as ``restore()`` does."""
+        m = self._col(mask, torch.uint8)
+        self._reset_carried_diagnostics(m)
+        _lib.check(self.L.npb_restore_bank(self._h, self._p(m), self._stream()), self._h)
         return self.get_observation()
 
     def _enable_autoreset(self, max_episode_steps: Optional[int]) -> None:
@@ -479,6 +530,8 @@ class BatchedPlantEnv:
             info["maintenance_event_count"] = self._event_counts if self._event_counts is not None else self.get_field("maint.maintenance_actions_performed")
         if self._episode is not None:     # autoreset: written by the episode kernel behind the step (npb_set_autoreset)
             info.update(self._episode)
+            if self._bank is not None:    # the bank episode kernel's: the bank entry this transition's episode started from
+                info["episode_start"] = self._episode_start_out
         return self._obs, self._reward, self._done, info
 
 
