@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define NPB_VERSION 144 /* 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
+#define NPB_VERSION 145 /* 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
 #ifndef NPB_API
 #define NPB_API __attribute__((visibility("default")))
 #endif
@@ -340,6 +340,25 @@ NPB_API int npb_restore_bank(NpbHandle *h, const uint8_t *mask, void *stream);
  * -1 for an episode that did not start from the bank: construction, npb_reset, npb_reset_reference and npb_restore put the carried
  * entry to -1. */
 NPB_API int npb_set_episode_start_buffer(NpbHandle *h, int32_t *out_start);
+
+/* Heat-source noise streams on the device (constant_heat_source.py:58-62,178: each ConstantHeatSource owns a
+ * np.random.RandomState(seed) and draws rng.normal(0, sigma) per step, i.e. sigma * standard_normal()).  One MT19937 per plant,
+ * owned by the handle (about 2.5 KB a plant), that follows numpy.random.RandomState(seed).standard_normal() -- legacy_gauss: the polar
+ * method with its one-value cache: the integer state (key, pos, has_gauss) is numpy's exactly and every draw is within a few ulp of
+ * numpy's (only the fp64 log is the device library's).  The step kernels do not change: npb_noise_fill writes a [k][n] block whose
+ * row t npb_step takes as its noise_z column.
+ * npb_noise_seed: plant p's generator becomes RandomState(seeds[p]) (seeds: host int64[n]); allocated on first use, freed by
+ * npb_destroy, or by seeds = NULL.  NPB_EINVAL for a seed outside [0, 2^32), as numpy refuses it.  Returns once the seeding is done. */
+NPB_API int npb_noise_seed(NpbHandle *h, const int64_t *seeds, void *stream);
+/* the next k standard_normal() draws of every plant into out (device, double[k][n]: out[t * n + p]), enqueued on `stream`.
+ * Allocates nothing.  NPB_EINVAL if the handle has no generators or k < 1. */
+NPB_API int npb_noise_fill(NpbHandle *h, int k, double *out, void *stream);
+/* the generators' state in numpy's RandomState.get_state() layout (host buffers): key uint32[n][624], pos int32[n] (0-624),
+ * has_gauss int32[n] (0 | 1), cached double[n] (0.0 when has_gauss is 0).  Synchronous on `stream`.  NPB_EINVAL without generators.
+ * npb_noise_set_state loads such a state (allocating the generators if there are none): checkpoints, and a host stream continued on
+ * the device.  It refuses pos outside [0, 624] and has_gauss outside {0, 1}. */
+NPB_API int npb_noise_get_state(NpbHandle *h, uint32_t *key, int32_t *pos, int32_t *has_gauss, double *cached, void *stream);
+NPB_API int npb_noise_set_state(NpbHandle *h, const uint32_t *key, const int32_t *pos, const int32_t *has_gauss, const double *cached, void *stream);
 
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the

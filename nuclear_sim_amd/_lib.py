@@ -208,6 +208,11 @@ def load():
         L.npb_set_start_slots.argtypes = [vp, vp, vp, ci]
         L.npb_restore_bank.argtypes = [vp, vp, vp]
         L.npb_set_episode_start_buffer.argtypes = [vp, vp]
+    if hasattr(L, "npb_noise_seed"):     # ABI 145: heat-source noise streams on the device
+        L.npb_noise_seed.argtypes = [vp, vp, vp]
+        L.npb_noise_fill.argtypes = [vp, ci, vp, vp]
+        L.npb_noise_get_state.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.npb_noise_set_state.argtypes = [vp, vp, vp, vp, vp, vp]
     if L.npb_num_f64() != SCHEMA.total_f64 or L.npb_num_i32() != SCHEMA.total_i32:
         raise NpbError("libnpb.so was built against a different include/npb_fields.h (%d/%d vs %d/%d): rebuild"
                        % (L.npb_num_f64(), L.npb_num_i32(), SCHEMA.total_f64, SCHEMA.total_i32))

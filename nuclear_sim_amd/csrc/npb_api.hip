@@ -10,6 +10,7 @@
 #include <vector>
 #include "../../include/npb.h"
 #include "npb_kernels.h"
+#include "npb_noise.h"
 
 struct NpbHandle {
   npb_params_t params;
@@ -38,6 +39,7 @@ struct NpbHandle {
   int32_t *ep_start;   /* with a bank: carried bank entry of each plant's running episode, -1 = not from the bank ([pitch]), or NULL */
   int32_t *next_slot; int32_t *slot_start; int slot_advance;  /* npb_set_start_slots: the caller's columns (next_slot NULL = no slots) */
   int32_t *ep_out_start;                                       /* npb_set_episode_start_buffer: the caller's column, or NULL */
+  void *noise; npb_noise_t noise_g;  /* npb_noise_seed / npb_noise_set_state: the heat-source noise generators (npb_noise.hip), or NULL */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
   std::vector<int> plan_key;
   std::string error;
@@ -277,6 +279,7 @@ int npb_destroy(NpbHandle *h) {
   if (h->ep_len) (void)hipFree(h->ep_len);
   if (h->bank) (void)hipFree(h->bank);
   if (h->ep_start) (void)hipFree(h->ep_start);
+  if (h->noise) (void)hipFree(h->noise);
   delete h;
   return NPB_OK;
 }
@@ -611,6 +614,89 @@ int npb_restore_bank(NpbHandle *h, const uint8_t *mask, void *stream) {
 int npb_set_episode_start_buffer(NpbHandle *h, int32_t *out_start) {
   if (!h) return NPB_EINVAL;
   h->ep_out_start = out_start;
+  return NPB_OK;
+}
+
+static int noise_alloc(NpbHandle *h, const char *who) {
+  if (h->noise) return NPB_OK;
+  hipError_t e = hipMalloc(&h->noise, npb_noise_bytes(h->pitch));
+  if (e != hipSuccess) { h->noise = nullptr; std::string m = who; m += ": hipMalloc of the noise generators failed"; return fail(h, NPB_EHIP, m.c_str(), e); }
+  h->noise_g = npb_noise_layout(h->noise, h->pitch);
+  return NPB_OK;
+}
+
+int npb_noise_seed(NpbHandle *h, const int64_t *seeds, void *stream) {
+  if (!h) return NPB_EINVAL;
+  NPB_USE_DEVICE(h);
+  if (!seeds) {
+    if (h->noise) { NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream)); (void)hipFree(h->noise); }
+    h->noise = nullptr;
+    return NPB_OK;
+  }
+  const int n = h->n_plants;
+  std::vector<uint32_t> s32((size_t)n);
+  for (int p = 0; p < n; p++) {
+    if (seeds[p] < 0 || seeds[p] > (int64_t)0xffffffffLL)
+      return fail(h, NPB_EINVAL, "npb_noise_seed: a seed is outside [0, 2^32), which numpy.random.RandomState refuses");
+    s32[p] = (uint32_t)seeds[p];
+  }
+  if (int rc = noise_alloc(h, "npb_noise_seed")) return rc;
+  /* the seeds travel in the pos column, which the seed kernel then overwrites */
+  NPB_HIP(h, hipMemcpyAsync(h->noise_g.pos, s32.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, (hipStream_t)stream));
+  npb_launch_noise_seed(h->noise_g, n, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));    /* s32 is read until the copy is done */
+  return NPB_OK;
+}
+
+int npb_noise_fill(NpbHandle *h, int k, double *out, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->noise) return fail(h, NPB_EINVAL, "npb_noise_fill: no noise generators (npb_noise_seed or npb_noise_set_state first)");
+  if (k < 1 || !out) return fail(h, NPB_EINVAL, "npb_noise_fill: k must be >= 1 and out non-NULL");
+  NPB_USE_DEVICE(h);
+  npb_launch_noise_fill(h->noise_g, h->n_plants, k, out, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, NPB_EHIP, "npb_noise_fill: kernel launch failed", e);
+  return NPB_OK;
+}
+
+int npb_noise_get_state(NpbHandle *h, uint32_t *key, int32_t *pos, int32_t *has_gauss, double *cached, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->noise) return fail(h, NPB_EINVAL, "npb_noise_get_state: no noise generators (npb_noise_seed or npb_noise_set_state first)");
+  if (!key || !pos || !has_gauss || !cached) return fail(h, NPB_EINVAL, "npb_noise_get_state: NULL output");
+  NPB_USE_DEVICE(h);
+  const size_t n = (size_t)h->n_plants, pitch = h->pitch;
+  std::vector<uint32_t> rows((size_t)NPB_MT_N * n);     /* [624][n], then transposed to numpy's [n][624] */
+  hipStream_t st = (hipStream_t)stream;
+  NPB_HIP(h, hipMemcpy2DAsync(rows.data(), n * sizeof(uint32_t), h->noise_g.key, pitch * sizeof(uint32_t), n * sizeof(uint32_t), NPB_MT_N, hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpyAsync(pos, h->noise_g.pos, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpyAsync(has_gauss, h->noise_g.has_gauss, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpyAsync(cached, h->noise_g.gauss, n * sizeof(double), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipStreamSynchronize(st));
+  for (size_t i = 0; i < (size_t)NPB_MT_N; i++)
+    for (size_t p = 0; p < n; p++) key[p * NPB_MT_N + i] = rows[i * n + p];
+  return NPB_OK;
+}
+
+int npb_noise_set_state(NpbHandle *h, const uint32_t *key, const int32_t *pos, const int32_t *has_gauss, const double *cached, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!key || !pos || !has_gauss || !cached) return fail(h, NPB_EINVAL, "npb_noise_set_state: NULL input");
+  const size_t n = (size_t)h->n_plants, pitch = h->pitch;
+  for (size_t p = 0; p < n; p++) {
+    if (pos[p] < 0 || pos[p] > NPB_MT_N) return fail(h, NPB_EINVAL, "npb_noise_set_state: pos outside [0, 624]");
+    if (has_gauss[p] != 0 && has_gauss[p] != 1) return fail(h, NPB_EINVAL, "npb_noise_set_state: has_gauss outside {0, 1}");
+  }
+  NPB_USE_DEVICE(h);
+  if (int rc = noise_alloc(h, "npb_noise_set_state")) return rc;
+  std::vector<uint32_t> rows((size_t)NPB_MT_N * n);
+  for (size_t i = 0; i < (size_t)NPB_MT_N; i++)
+    for (size_t p = 0; p < n; p++) rows[i * n + p] = key[p * NPB_MT_N + i];
+  hipStream_t st = (hipStream_t)stream;
+  NPB_HIP(h, hipMemcpy2DAsync(h->noise_g.key, pitch * sizeof(uint32_t), rows.data(), n * sizeof(uint32_t), n * sizeof(uint32_t), NPB_MT_N, hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(h->noise_g.pos, pos, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(h->noise_g.has_gauss, has_gauss, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(h->noise_g.gauss, cached, n * sizeof(double), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipStreamSynchronize(st));    /* rows and the caller's buffers are read until the copies are done */
   return NPB_OK;
 }
 

@@ -1,0 +1,175 @@
+/*
+ * npb_noise.hip -- the heat-source noise streams on the device: one Mersenne Twister per plant that follows
+ * numpy.random.RandomState(seed).standard_normal() (the reference's ConstantHeatSource draws rng.normal(0, sigma) per step,
+ * constant_heat_source.py:58-62,178; numpy's legacy normal is loc + scale * gauss).
+ *
+ * What is restated is numpy 2.2's published legacy path, as nuclear_sim_amd/csrc/npb_seeds.cpp does for the host: MT19937
+ * (Matsumoto & Nishimura 1998) seeded by init_genrand, a word per call with the twist made when pos reaches 624, doubles from two
+ * words ((a >> 5) * 2^26 + (b >> 6)) / 2^53, and legacy_gauss: the polar method with a one-value cache that is zeroed when consumed.
+ *
+ * Built on its own (Makefile): -ffp-contract=off keeps r2 = x1 * x1 + x2 * x2 two rounded products and one rounded sum, so every
+ * accept / reject decision -- and with it the word stream -- is numpy's bit for bit; without -freciprocal-math / -fapprox-func the
+ * division and the square root are IEEE, and only the device library's fp64 log can differ from the host's libm.
+ *
+ * One lane per plant.  Lanes reject independently and so run out of words at different draws; a lane that does waits, and the
+ * wave twists every waiting lane in one pass, so the 624-word loop is run once per generation for the wave, not once per lane.
+ */
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include "npb_noise.h"
+
+namespace {
+
+constexpr int MT_N = NPB_MT_N, MT_M = 397;
+constexpr uint32_t UPPER = 0x80000000u, LOWER = 0x7fffffffu, MATRIX_A = 0x9908b0dfu;
+
+__device__ __forceinline__ uint32_t temper(uint32_t y) {
+  y ^= (y >> 11);
+  y ^= (y << 7) & 0x9d2c5680u;
+  y ^= (y << 15) & 0xefc60000u;
+  y ^= (y >> 18);
+  return y;
+}
+
+__device__ __forceinline__ uint32_t twist_word(uint32_t cur, uint32_t next, uint32_t far) {
+  const uint32_t y = (cur & UPPER) | (next & LOWER);
+  return far ^ (y >> 1) ^ ((y & 1u) ? MATRIX_A : 0u);
+}
+
+__device__ __forceinline__ double to_double(uint32_t a, uint32_t b) {
+  return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) / 9007199254740992.0;
+}
+
+/* words [i, hi) of the twist, B at a time, word j from words j, j + 1 and j + off: each batch issues all its loads before its
+ * stores.  No batch reads a word it writes: for j < 227 the far word j + 397 is not written in this pass, for 227 <= j < 623 it is
+ * j - 227 < j, written by an earlier batch (B <= 227), and word j + 1 is not yet written.  Returns where it stopped. */
+template <int B>
+__device__ __forceinline__ int twist_batches(uint32_t *col, size_t pitch, int i, int hi, int off) {
+  for (; i + B <= hi; i += B) {
+    uint32_t cur[B + 1], far[B];
+#pragma unroll
+    for (int j = 0; j <= B; j++) cur[j] = col[(size_t)(i + j) * pitch];
+#pragma unroll
+    for (int j = 0; j < B; j++) far[j] = col[(size_t)(i + j + off) * pitch];
+#pragma unroll
+    for (int j = 0; j < B; j++) col[(size_t)(i + j) * pitch] = twist_word(cur[j], cur[j + 1], far[j]);
+  }
+  return i;
+}
+
+/* mt19937_gen: one generation in place, in numpy's three ranges.  A lane waits for its loads once per batch: batches of 16, then
+ * 4, then 1 make it 45 waits per generation (batches of 32: 26 waits, twice the registers, no faster at 65 536 plants). */
+__device__ void twist(uint32_t *col, size_t pitch) {
+  int i = twist_batches<16>(col, pitch, 0, MT_N - MT_M, MT_M);
+  i = twist_batches<4>(col, pitch, i, MT_N - MT_M, MT_M);
+  twist_batches<1>(col, pitch, i, MT_N - MT_M, MT_M);
+  i = twist_batches<16>(col, pitch, MT_N - MT_M, MT_N - 1, MT_M - MT_N);
+  i = twist_batches<4>(col, pitch, i, MT_N - 1, MT_M - MT_N);
+  twist_batches<1>(col, pitch, i, MT_N - 1, MT_M - MT_N);
+  col[(size_t)(MT_N - 1) * pitch] = twist_word(col[(size_t)(MT_N - 1) * pitch], col[0], col[(size_t)(MT_M - 1) * pitch]);
+}
+
+__global__ __launch_bounds__(256) void npb_noise_seed_kernel(npb_noise_t g, int n_plants) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_plants) return;
+  uint32_t s = ((const uint32_t *)g.pos)[p];
+  uint32_t *col = g.key + p;
+  col[0] = s;
+  for (int i = 1; i < MT_N; i++) {
+    s = 1812433253u * (s ^ (s >> 30)) + (uint32_t)i;
+    col[(size_t)i * g.pitch] = s;
+  }
+  g.pos[p] = MT_N;
+  g.has_gauss[p] = 0;
+  g.gauss[p] = 0.0;
+}
+
+/* k draws per lane into out[t * n + p]: a lane draws until it has k or its generation is spent; then the wave twists every lane
+ * that is out of words, and they go on.  Within a generation a lane loads GROUP words at once and makes up to GROUP / 4 polar
+ * attempts from them, consuming (pos += 4) only the attempts it makes: one wait for memory per GROUP words instead of per four.
+ * Near the end of a generation the words of one attempt are kept in w0..w3 (w0 the oldest), so an attempt whose words straddle a
+ * twist resumes after it. */
+constexpr int GROUP = 16;
+
+__global__ __launch_bounds__(64) void npb_noise_fill_kernel(npb_noise_t g, int n_plants, int k, double *__restrict__ out) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_plants) return;
+  const size_t pitch = g.pitch, n = (size_t)n_plants;
+  uint32_t *col = g.key + p;
+  double *o = out + p;
+  int pos = g.pos[p];
+  int t = 0;
+  if (g.has_gauss[p]) o[(size_t)t++ * n] = g.gauss[p];   /* k >= 1 */
+  int has = 0;
+  double cached = 0.0;
+  /* legacy_gauss's loop body on four words: on acceptance f * x2 is drawn and f * x1 cached -- here drawn too if k allows */
+  auto attempt = [&](uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+    const double x1 = 2.0 * to_double(a, b) - 1.0;
+    const double x2 = 2.0 * to_double(c, d) - 1.0;
+    const double r2 = x1 * x1 + x2 * x2;
+    if (r2 >= 1.0 || r2 == 0.0) return;
+    const double f = sqrt(-2.0 * log(r2) / r2);
+    o[(size_t)t++ * n] = f * x2;
+    if (t < k) o[(size_t)t++ * n] = f * x1;
+    else { has = 1; cached = f * x1; }
+  };
+  uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
+  int cnt = 0;
+  for (;;) {
+    while (t < k) {
+      if (cnt == 0 && pos <= MT_N - GROUP) {
+        uint32_t w[GROUP];
+#pragma unroll
+        for (int j = 0; j < GROUP; j++) w[j] = temper(col[(size_t)(pos + j) * pitch]);
+#pragma unroll
+        for (int j = 0; j < GROUP; j += 4)
+          if (t < k) { pos += 4; attempt(w[j], w[j + 1], w[j + 2], w[j + 3]); }
+        continue;
+      }
+      while (cnt < 4 && pos < MT_N) {
+        w0 = w1; w1 = w2; w2 = w3;
+        w3 = temper(col[(size_t)pos++ * pitch]);
+        cnt++;
+      }
+      if (cnt < 4) break;         /* out of words: twisted below */
+      cnt = 0;
+      attempt(w0, w1, w2, w3);
+    }
+    const bool need = t < k;
+    if (!__any(need)) break;
+    if (need) {
+      twist(col, pitch);
+      pos = 0;
+    }
+  }
+  g.pos[p] = pos;
+  g.has_gauss[p] = has;
+  g.gauss[p] = cached;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t npb_noise_bytes(size_t pitch) { return pitch * ((size_t)MT_N * sizeof(uint32_t) + 2 * sizeof(int32_t) + sizeof(double)); }
+
+npb_noise_t npb_noise_layout(void *base, size_t pitch) {
+  npb_noise_t g;
+  char *b = (char *)base;
+  g.pitch = pitch;
+  g.key = (uint32_t *)b;               b += pitch * MT_N * sizeof(uint32_t);
+  g.gauss = (double *)b;               b += pitch * sizeof(double);
+  g.pos = (int32_t *)b;                b += pitch * sizeof(int32_t);
+  g.has_gauss = (int32_t *)b;
+  return g;
+}
+
+void npb_launch_noise_seed(npb_noise_t g, int n_plants, hipStream_t stream) {
+  hipLaunchKernelGGL(npb_noise_seed_kernel, dim3((n_plants + 255) / 256), dim3(256), 0, stream, g, n_plants);
+}
+
+void npb_launch_noise_fill(npb_noise_t g, int n_plants, int k, double *out, hipStream_t stream) {
+  hipLaunchKernelGGL(npb_noise_fill_kernel, dim3((n_plants + 63) / 64), dim3(64), 0, stream, g, n_plants, k, out);
+}
+
+}  /* extern "C" */

@@ -79,6 +79,65 @@ class HeatSourceNoise:
         return out
 
 
+class DeviceHeatSourceNoise:
+    """``HeatSourceNoise`` generated on the device: one Mersenne Twister per plant, owned by ``env``'s handle (npb_noise_seed),
+    that follows ``np.random.RandomState(seed).standard_normal()`` -- the integer state exactly, every draw within a few ulp (only
+    the fp64 log is the device library's).  ``next()`` hands out one [n] float64 device row per call and refills a
+    [block, n] block with npb_noise_fill when it runs out.  Each refill is a fresh tensor from torch's stream-ordered allocator, so
+    rows handed out earlier stay valid, as they do with the host class.
+
+    ``get_state()`` / ``set_state()`` use numpy's ``get_state()`` layout (key [n, 624] uint32, pos, has_gauss, cached).  The state is
+    the generators' -- after the current block, not after the last row handed out; ``set_state`` drops the rest of the block.
+    The generators belong to the handle: a second instance on the same env re-seeds them."""
+
+    def __init__(self, env: "BatchedPlantEnv", seeds: Sequence[int], block: int = 256):
+        if int(block) < 1:
+            raise ValueError("block must be >= 1")
+        s = np.ascontiguousarray(np.asarray(seeds, dtype=np.int64).reshape(-1))
+        if s.size != env.n:
+            raise ValueError("one seed per plant: %d seeds for %d plants" % (s.size, env.n))
+        self._env = env
+        self._block = int(block)
+        _lib.check(env.L.npb_noise_seed(env._h, s.ctypes.data_as(ctypes.c_void_p), env._stream()), env._h)
+        self._buf = None
+        self._pos = self._block
+
+    def next(self) -> torch.Tensor:
+        env = self._env
+        if self._pos >= self._block:
+            with torch.cuda.device(env.device):
+                self._buf = torch.empty((self._block, env.n), dtype=torch.float64, device=env.device)
+            _lib.check(env.L.npb_noise_fill(env._h, self._block, ctypes.c_void_p(self._buf.data_ptr()), env._stream()), env._h)
+            self._pos = 0
+        out = self._buf[self._pos]
+        self._pos += 1
+        return out
+
+    def get_state(self):
+        """(key [n, 624] uint32, pos [n] int32, has_gauss [n] int32, cached [n] float64) of every plant's generator"""
+        env, n = self._env, self._env.n
+        key = np.empty((n, 624), dtype=np.uint32)
+        pos, has_gauss = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        cached = np.empty(n, dtype=np.float64)
+        _lib.check(env.L.npb_noise_get_state(env._h, *(a.ctypes.data_as(ctypes.c_void_p) for a in (key, pos, has_gauss, cached)),
+                                             env._stream()), env._h)
+        return key, pos, has_gauss, cached
+
+    def set_state(self, key, pos, has_gauss, cached) -> None:
+        """load every plant's generator state (numpy's layout, as ``get_state`` returns it); the rest of the block is dropped"""
+        env, n = self._env, self._env.n
+        arrays = (np.ascontiguousarray(np.broadcast_to(np.asarray(key, dtype=np.uint32), (n, 624))),
+                  np.ascontiguousarray(np.broadcast_to(np.asarray(pos, dtype=np.int32), (n,))),
+                  np.ascontiguousarray(np.broadcast_to(np.asarray(has_gauss, dtype=np.int32), (n,))),
+                  np.ascontiguousarray(np.broadcast_to(np.asarray(cached, dtype=np.float64), (n,))))
+        _lib.check(env.L.npb_noise_set_state(env._h, *(a.ctypes.data_as(ctypes.c_void_p) for a in arrays), env._stream()), env._h)
+        self._buf = None
+        self._pos = self._block
+
+
+NOISE_GENERATORS = ("host", "device")
+
+
 def equilibrium_state(power_level=100.0, control_rod_position=95.0) -> Dict[str, object]:
     """create_equilibrium_state(power_level, control_rod_position, auto_balance=True)  reactivity_model.py:443-529, as a field
     dict for ``BatchedPlantEnv.set_fields``.  Scalars, or arrays [n] for one state per plant (BASELINE config 2: power ~ U[60, 100] %,
@@ -148,6 +207,11 @@ class BatchedPlantEnv:
     own snapshot lane, and advance its slot, all on the device.  ``info["episode_start"]`` is the bank entry of the episode each
     step's transition belonged to (-1: not from the bank), ``episode_start`` the entry of each plant's last bank restore.  A
     restored plant takes the entry's clock and maintenance stamps; the heat-source noise stream stays with the plant position.
+
+    Heat-source noise (``noise_enabled``): ``noise_generator="host"`` (the default) draws each plant's
+    ``RandomState(seed).standard_normal()`` stream on the host (``HeatSourceNoise``); ``"device"`` generates the same streams on the
+    device (``DeviceHeatSourceNoise``: integer state exactly numpy's, every draw within a few ulp), with no host work per step.
+    Either way ``reset()`` of the whole batch re-seeds seeded streams; a masked reset, ``restore`` and the autoreset keep them going.
     """
 
     action_space_size = 15       # NuclearPlantEnv sim.py:916
@@ -157,9 +221,12 @@ class BatchedPlantEnv:
                  noise_std_percent: float = 0.1, noise_seeds: Optional[Sequence[int]] = None,
                  mode: str = "full", device: int = 0, params: Optional[dict] = None, maintenance: bool = False,
                  storage: str = "f64", maintenance_thresholds: Optional[dict] = None, reactivity_components: bool = False,
-                 integrator: str = "reference", autoreset: bool = False, max_episode_steps: Optional[int] = None):
+                 integrator: str = "reference", autoreset: bool = False, max_episode_steps: Optional[int] = None,
+                 noise_generator: str = "host"):
         if max_episode_steps is not None and not autoreset:
             raise ValueError("max_episode_steps needs autoreset=True")
+        if noise_generator not in NOISE_GENERATORS:
+            raise ValueError("noise_generator must be one of %r" % (NOISE_GENERATORS,))
         if not torch.cuda.is_available():
             raise _lib.NpbError("BatchedPlantEnv needs a HIP device (torch.cuda.is_available() is False); "
                                 "there is no CPU fallback")
@@ -220,9 +287,10 @@ class BatchedPlantEnv:
                 self._event_counts = torch.zeros(self.n, dtype=torch.int32, device=self.device)
             _lib.check(self.L.npb_set_maintenance_count_buffer(self._h, ctypes.c_void_p(self._event_counts.data_ptr())), self._h)
         self._noise = None
+        self.noise_generator = noise_generator
         self._noise_seeds = None if noise_seeds is None else np.asarray(noise_seeds, dtype=np.int64).copy()
         if noise_enabled and noise_seeds is not None:
-            self._noise = HeatSourceNoise(noise_seeds, device=self.device)
+            self._noise = self._make_noise(noise_seeds)
         self._keep = []
         self._episode = None
         self._bank = None
@@ -233,19 +301,20 @@ class BatchedPlantEnv:
     @classmethod
     def action_test(cls, action: str, seeds: Sequence[int], dt: float = 5.0, device: int = 0, randomize: bool = True,
                     params: Optional[dict] = None, autoreset: bool = False, max_episode_steps: Optional[int] = None,
-                    bank_seeds: Optional[Sequence[int]] = None) -> "BatchedPlantEnv":
+                    bank_seeds: Optional[Sequence[int]] = None, noise_generator: str = "host") -> "BatchedPlantEnv":
         """One plant per seed, as data_gen's MaintenanceScenarioRunner builds them for
         ``compose_action_test_scenario(action, randomize=True, randomization_seed=seed)``
         (maintenance_scenario_runner.py:210-244): dt in minutes, ConstantHeatSource with 0.1 % noise seeded 42,
         automatic maintenance on, initial conditions from nuclear_sim_amd.scenarios (BASELINE config 4).  With ``autoreset`` the
         snapshot is taken after the initial conditions are in: each plant restarts from its own.  With ``bank_seeds`` later
         episodes start from a bank built as ``action_test(action, bank_seeds)`` with the same ``randomize``, ``dt`` and ``params``
-        (``set_start_bank`` with its default slots): each restart draws a fresh scenario, as the data-gen runner's episodes do."""
+        (``set_start_bank`` with its default slots): each restart draws a fresh scenario, as the data-gen runner's episodes do.
+        ``noise_generator`` as for the constructor."""
         if max_episode_steps is not None and not autoreset:
             raise ValueError("max_episode_steps needs autoreset=True")
         from . import scenarios
         env = cls(len(seeds), dt=dt, heat_source="constant", noise_enabled=True, noise_std_percent=0.1,
-                  noise_seeds=[42] * len(seeds), device=device, maintenance=True, params=params)
+                  noise_seeds=[42] * len(seeds), device=device, maintenance=True, params=params, noise_generator=noise_generator)
         eff = float(env.get_field("pump.lubrication_effectiveness")[0].item())
         env.set_fields(scenarios.action_test_fields(action, seeds, eff, randomize=randomize))
         # what a state log of these plants needs beside their state: the composer's provider names and the values the constructor
@@ -263,6 +332,12 @@ class BatchedPlantEnv:
         return env
 
     # ------------------------------------------------------------------ helpers
+    def _make_noise(self, seeds):
+        """the heat-source noise stream of ``noise_generator``: drawn on the host, or on the device by the handle's generators"""
+        if self.noise_generator == "device":
+            return DeviceHeatSourceNoise(self, seeds)
+        return HeatSourceNoise(seeds, device=self.device)
+
     def set_step_kernel(self, variant: int) -> None:
         """0 = by batch size (default), 1 = one-wave kernel, 2 = two-wave kernel, 3 = its 256-register build at any size, 4 = the
         one-wave kernel with streaming state stores (what 0 takes above 114 688 plants), 5 = four-wave kernel (what 0 takes up
@@ -474,7 +549,7 @@ class BatchedPlantEnv:
             # drawing from the old one: constant_heat_source.py:185-194 does not touch the RNG).  Plants that share a seed
             # share one pre-drawn stream here, so only a reset of the whole batch can restart it.
             if mask is None and self._noise is not None and self._noise_seeds is not None:
-                self._noise = HeatSourceNoise(self._noise_seeds, device=self.device)
+                self._noise = self._make_noise(self._noise_seeds)
         return self.get_observation()
 
     def get_observation(self) -> torch.Tensor:
@@ -513,7 +588,7 @@ class BatchedPlantEnv:
         if noise_z is None and self._noise is None and self.params.hs_noise_enabled:
             # ConstantHeatSource(noise_enabled=True, noise_seed=None) draws from an unseeded generator
             # (constant_heat_source.py:58-62): one fresh, unseeded stream per plant
-            self._noise = HeatSourceNoise(np.random.SeedSequence().generate_state(self.n, dtype=np.uint32), device=self.device)
+            self._noise = self._make_noise(np.random.SeedSequence().generate_state(self.n, dtype=np.uint32))
         if noise_z is None and self._noise is not None:
             noise_z = self._noise.next()
         z = self._col(noise_z, torch.float64)
