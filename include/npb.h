@@ -329,13 +329,13 @@ NPB_API int npb_set_start_bank(NpbHandle *h, const NpbHandle *src, void *stream)
  * bank takes entry s = ((next_slot[p] % M) + M) % M, defined for any value the caller wrote, and the library then stores
  * next_slot[p] = (s + advance) % M and episode_start[p] = s.  advance = 0 leaves every restart to the caller (e.g. random slots written
  * on the same stream).  NPB_EINVAL for next_slot = NULL or advance < 0.  With a bank and slots, npb_step's autoreset restores from
- * the bank (npb_episode_bank_kernel) instead of the snapshot. */
+ * the bank instead of the snapshot. */
 NPB_API int npb_set_start_slots(NpbHandle *h, int32_t *next_slot, int32_t *episode_start, int advance);
 /* npb_restore's counterpart: the plants of mask (device, uint8[n], NULL = all) from their bank entries, episode counters (if any) to
  * zero; with params.maint_enabled their cooldown cache and event counts follow, as npb_restore's do.  NPB_EINVAL without a bank and
  * slots.  Follow with npb_observe for the restored observation. */
 NPB_API int npb_restore_bank(NpbHandle *h, const uint8_t *mask, void *stream);
-/* a caller column (device int32[n], NULL = none) the bank episode kernel fills on every step with the bank entry of the episode this
+/* a caller column (device int32[n], NULL = none) the autoreset from the bank fills on every step with the bank entry of the episode this
  * step's transition belonged to (a plant reset on the step: its finished episode's, as length / ret of npb_set_episode_buffers).
  * -1 for an episode that did not start from the bank: construction, npb_reset, npb_reset_reference and npb_restore put the carried
  * entry to -1. */

@@ -19,6 +19,7 @@ struct NpbHandle {
   size_t pitch;        /* n_plants rounded up to a multiple of the wave size */
   size_t seg;          /* plants per arena segment (npb_kernels.hip, "segmented arena"), 0 = the arena is one [column][pitch] block */
   int storage;         /* NPB_STORAGE_F64 | NPB_STORAGE_F32: element type of the real-valued columns */
+  const npb_launchers_t *K;   /* the launchers of that storage type's build of npb_kernels.hip */
   size_t real_bytes;   /* 8 | 4 */
   void *f64;           /* the arena: [NPB_TOTAL_COL64][pitch] 8-byte columns, or [NPB_TOTAL_COL32][pitch] 4-byte ones */
   double *convert;     /* one staging column (pitch doubles) used by get/set_field with host buffers */
@@ -98,12 +99,19 @@ static size_t arena_columns(int storage) { return storage == NPB_STORAGE_F32 ? (
 static size_t arena_plants(const NpbHandle *h) { return h->seg ? (h->pitch + h->seg - 1) / h->seg * h->seg : h->pitch; }
 /* what the launchers take as the column pitch: the pitch with the segment size in the upper half (npb_kernels.hip, NPD_SEGMENT) */
 #define NPB_N(h) ((size_t)(h)->pitch | ((size_t)(h)->seg << 32))
-/* the bank as the bank launchers take it */
-static npb_bank_t bank_of(const NpbHandle *h) {
-  npb_bank_t B;
-  B.arena = h->bank; B.N = h->bank_N; B.M = h->bank_M;
-  B.next_slot = h->next_slot; B.episode_start = h->slot_start; B.advance = h->slot_advance; B.start = h->ep_start; B.out_start = h->ep_out_start;
-  return B;
+/* where a restore copies from: the start bank with its slots (bank), or else the snapshot, which has no slot or start columns */
+static npb_source_t source_of(const NpbHandle *h, bool bank) {
+  npb_source_t S = {};
+  if (!bank) { S.arena = h->snap; S.N = NPB_N(h); return S; }
+  S.arena = h->bank; S.N = h->bank_N; S.M = h->bank_M;
+  S.next_slot = h->next_slot; S.episode_start = h->slot_start; S.advance = h->slot_advance; S.start = h->ep_start; S.out_start = h->ep_out_start;
+  return S;
+}
+/* npb_reset / npb_reset_reference (counters) and npb_restore: the episode counters (with counters) and the carried start entries of the
+ * plants of mask (NULL = every lane of the pitch) to 0 and -1 */
+static void clear_episodes(NpbHandle *h, const uint8_t *mask, bool counters, hipStream_t stream) {
+  int32_t *len = counters ? h->ep_len : nullptr;
+  if (len || h->ep_start) npb_launch_episode_clear(mask, len, counters ? h->ep_ret : nullptr, h->ep_start, h->n_plants, h->pitch, stream);
 }
 
 /* Where an arena lands in physical memory changes the step kernel's time when the bytes a step touches are about the
@@ -118,7 +126,6 @@ static void probe_placement(NpbHandle *h, size_t step_columns) {
   if (env && atoi(env) == 0) return;
   const double touched_mb = (double)step_columns * h->real_bytes * h->pitch / 1.0e6;
   if (touched_mb < 200.0 || touched_mb > 340.0 || h->params.mode == NPB_MODE_PRIMARY) return;
-  const bool narrow = h->storage == NPB_STORAGE_F32;
   const size_t bytes = arena_columns(h->storage) * arena_plants(h) * h->real_bytes;
   const int max_candidates = 4, launches = 12;
   void *cand[max_candidates] = {h->f64, nullptr, nullptr, nullptr};
@@ -129,20 +136,20 @@ static void probe_placement(NpbHandle *h, size_t step_columns) {
   /* the clocks first: after an idle period the step kernel needs ~170 launches to reach its steady time (bench.py,
    * "preconditioning"), and the first candidate would otherwise be timed on the ramp -- a 5-7 % bias against it, half of
    * the effect being selected on.  Untimed launches on candidate 0 until ~20 ms have passed. */
-  (narrow ? npb32_launch_init : npb_launch_init)(&h->params, h->n_plants, NPB_N(h), cand[0], nullptr, nullptr);
+  h->K->init(&h->params, h->n_plants, NPB_N(h), cand[0], nullptr, nullptr);
   for (int k = 0; k < 200; k++)
-    (void)(narrow ? npb32_launch_step : npb_launch_step)(&h->params, h->n_plants, NPB_N(h), cand[0], nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                         nullptr, nullptr, nullptr, nullptr, nullptr, h->step_kernel, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
+    (void)h->K->step(&h->params, h->n_plants, NPB_N(h), cand[0], nullptr, nullptr, nullptr, nullptr, nullptr,
+                     nullptr, nullptr, nullptr, nullptr, nullptr, h->step_kernel, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
   if (hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); (void)hipEventDestroy(a); (void)hipEventDestroy(b); return; }
   int n = 0;
   for (; n < max_candidates; n++) {
     if (n > 0 && hipMalloc(&cand[n], bytes) != hipSuccess) { cand[n] = nullptr; (void)hipGetLastError(); break; }
-    (narrow ? npb32_launch_init : npb_launch_init)(&h->params, h->n_plants, NPB_N(h), cand[n], nullptr, nullptr);
+    h->K->init(&h->params, h->n_plants, NPB_N(h), cand[n], nullptr, nullptr);
     float best = 1e30f;
     for (int k = 0; k < launches; k++) {
       (void)hipEventRecord(a, nullptr);
-      (void)(narrow ? npb32_launch_step : npb_launch_step)(&h->params, h->n_plants, NPB_N(h), cand[n], nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                           nullptr, nullptr, nullptr, nullptr, nullptr, h->step_kernel, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
+      (void)h->K->step(&h->params, h->n_plants, NPB_N(h), cand[n], nullptr, nullptr, nullptr, nullptr, nullptr,
+                       nullptr, nullptr, nullptr, nullptr, nullptr, h->step_kernel, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
       (void)hipEventRecord(b, nullptr);
       if (hipEventSynchronize(b) != hipSuccess) { best = 1e30f; break; }
       float t = 0;
@@ -238,6 +245,7 @@ int npb_create_storage(const npb_params_t *params, int n_plants, int device, int
   h->n_plants = n_plants; h->device = device;
   h->pitch = ((size_t)n_plants + 63) / 64 * 64;
   h->storage = storage; h->real_bytes = real_bytes;
+  h->K = storage == NPB_STORAGE_F32 ? &npb32_launch_table : &npb_launch_table;
   h->f64 = nullptr; h->convert = nullptr; h->plan_dev = nullptr;
   /* batches past the two-wave kernel's range keep their arena in segments of 16 384 plants (npb_kernels.hip, "segmented arena") */
   {   /* NPB_ARENA_SEGMENT=0 turns it off, =<plants> (a multiple of 64) forces that segment size at any batch size: A/B aids */
@@ -256,7 +264,7 @@ int npb_create_storage(const npb_params_t *params, int n_plants, int device, int
   }
   h->maint_side = (void *)(h->convert + h->pitch);
   h->maint_cache_stale = true;
-  (storage == NPB_STORAGE_F32 ? npb32_launch_init : npb_launch_init)(&h->params, n_plants, NPB_N(h), h->f64, nullptr, nullptr);
+  h->K->init(&h->params, n_plants, NPB_N(h), h->f64, nullptr, nullptr);
   e = hipDeviceSynchronize();
   if (caller_device >= 0 && caller_device != device) (void)hipSetDevice(caller_device); /* the caller's current device is left as it was */
   if (e != hipSuccess) {
@@ -340,9 +348,8 @@ int npb_reset(NpbHandle *h, const uint8_t *mask, void *stream) {
   if (!h) return NPB_EINVAL;
   NPB_USE_DEVICE(h);
   h->maint_cache_stale = true;
-  (h->storage == NPB_STORAGE_F32 ? npb32_launch_init : npb_launch_init)(&h->params, h->n_plants, NPB_N(h), h->f64, mask, (hipStream_t)stream);
-  if (h->ep_len) npb_launch_episode_clear(mask, h->ep_len, h->ep_ret, h->n_plants, h->pitch, (hipStream_t)stream);
-  if (h->ep_start) npb_launch_start_clear(mask, h->ep_start, h->n_plants, h->pitch, (hipStream_t)stream);
+  h->K->init(&h->params, h->n_plants, NPB_N(h), h->f64, mask, (hipStream_t)stream);
+  clear_episodes(h, mask, true, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -351,9 +358,8 @@ int npb_reset_reference(NpbHandle *h, const uint8_t *mask, int start_at_steady_s
   if (!h) return NPB_EINVAL;
   NPB_USE_DEVICE(h);
   h->maint_cache_stale = true;
-  (h->storage == NPB_STORAGE_F32 ? npb32_launch_reset : npb_launch_reset)(&h->params, h->n_plants, NPB_N(h), h->f64, mask, start_at_steady_state != 0, (hipStream_t)stream);
-  if (h->ep_len) npb_launch_episode_clear(mask, h->ep_len, h->ep_ret, h->n_plants, h->pitch, (hipStream_t)stream);
-  if (h->ep_start) npb_launch_start_clear(mask, h->ep_start, h->n_plants, h->pitch, (hipStream_t)stream);
+  h->K->reset(&h->params, h->n_plants, NPB_N(h), h->f64, mask, start_at_steady_state != 0, (hipStream_t)stream);
+  clear_episodes(h, mask, true, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -374,7 +380,7 @@ int npb_get_field(NpbHandle *h, int kind, int slot, void *buf, int buf_is_device
   if (rc) return rc;
   NPB_USE_DEVICE(h);
   void *dst = buf_is_device ? buf : (void *)h->convert;
-  (h->storage == NPB_STORAGE_F32 ? npb32_launch_field_get : npb_launch_field_get)(h->f64, NPB_N(h), col, sub, akind, dst, h->n_plants, (hipStream_t)stream);
+  h->K->field_get(h->f64, NPB_N(h), col, sub, akind, dst, h->n_plants, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   if (!buf_is_device) {
     NPB_HIP(h, hipMemcpyAsync(buf, dst, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
@@ -395,7 +401,7 @@ int npb_set_field(NpbHandle *h, int kind, int slot, const void *buf, int buf_is_
     NPB_HIP(h, hipMemcpyAsync(h->convert, buf, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
     src = h->convert;
   }
-  (h->storage == NPB_STORAGE_F32 ? npb32_launch_field_set : npb_launch_field_set)(h->f64, NPB_N(h), col, sub, akind, src, h->n_plants, (hipStream_t)stream);
+  h->K->field_set(h->f64, NPB_N(h), col, sub, akind, src, h->n_plants, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   if (!buf_is_device) NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
   return NPB_OK;
@@ -416,7 +422,7 @@ int npb_gather_fields(NpbHandle *h, int n_fields, const int *kinds, const int *s
     NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
     h->plan_key = key;
   }
-  (h->storage == NPB_STORAGE_F32 ? npb32_launch_gather : npb_launch_gather)(h->f64, NPB_N(h), h->plan_dev, n_fields, out, h->n_plants, (hipStream_t)stream);
+  h->K->gather(h->f64, NPB_N(h), h->plan_dev, n_fields, out, h->n_plants, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -464,7 +470,6 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
   if (h->params.heat_source == NPB_HEAT_EXTERNAL && !noise_z)      /* a NULL column would read as 0 MW thermal, silently */
     return fail(h, NPB_EINVAL, "npb_step: params.heat_source is NPB_HEAT_EXTERNAL, whose thermal power arrives in the noise_z column (include/npb_params.h): it must not be NULL");
   NPB_USE_DEVICE(h);
-  const bool narrow = h->storage == NPB_STORAGE_F32;
   npb_maint_table_t table;
   const bool maint = h->params.maint_enabled != 0;
   if (maint) {
@@ -485,24 +490,20 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
       if (h->maint_counts) {       /* the caller's event-count column: whole once, then kept by the rule for the plants whose count it moves */
         int col, sub, akind;
         if (locate(h->storage, NPB_KIND_I32, NPB_MAINT_I32_BASE + NPB_I32_SLOT(npb_maint_t, MAINT, maintenance_actions_performed), &col, &sub, &akind))
-          (narrow ? npb32_launch_field_get : npb_launch_field_get)(h->f64, NPB_N(h), col, sub, akind, h->maint_counts, h->n_plants, (hipStream_t)stream);
+          h->K->field_get(h->f64, NPB_N(h), col, sub, akind, h->maint_counts, h->n_plants, (hipStream_t)stream);
       }
       h->maint_cache_stale = false;
     }
   }
-  h->last_kernel = (narrow ? npb32_launch_step : npb_launch_step)(&h->params, h->n_plants, NPB_N(h), h->f64, action, magnitude, power_setpoint,
-                                                 noise_z, cooling_water_temp, obs, reward, done, trip_flags, info, h->step_kernel, h->diag, h->diag_pitch,
-                                                 maint ? &table : nullptr, maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
+  h->last_kernel = h->K->step(&h->params, h->n_plants, NPB_N(h), h->f64, action, magnitude, power_setpoint,
+                              noise_z, cooling_water_temp, obs, reward, done, trip_flags, info, h->step_kernel, h->diag, h->diag_pitch,
+                              maint ? &table : nullptr, maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
   if (maint && h->params.mode != NPB_MODE_FULL)   /* a full-mode step kernel has run the rule itself, for the waves whose pump phase found something */
-    (narrow ? npb32_launch_maint : npb_launch_maint)(NPB_N(h), h->f64, h->maint_side, h->maint_counts, h->n_plants, (hipStream_t)stream);
-  if (h->autoreset && h->bank && h->next_slot)   /* the same, restoring from the bank */
-    (narrow ? npb32_launch_episode_bank : npb_launch_episode_bank)(h->params.mode, h->n_plants, NPB_N(h), h->f64, bank_of(h), done, reward, obs, h->ep_len, h->ep_ret,
-                                                                   h->ep_out_len, h->ep_out_ret, h->ep_out_truncated, h->ep_final_obs, h->max_episode_steps,
-                                                                   maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
-  else if (h->autoreset)   /* same stream, nothing read back, the maintenance cache kept per plant by the kernel itself */
-    (narrow ? npb32_launch_episode : npb_launch_episode)(h->params.mode, h->n_plants, NPB_N(h), h->f64, h->snap, done, reward, obs, h->ep_len, h->ep_ret,
-                                                         h->ep_out_len, h->ep_out_ret, h->ep_out_truncated, h->ep_final_obs, h->max_episode_steps,
-                                                         maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
+    h->K->maint(NPB_N(h), h->f64, h->maint_side, h->maint_counts, h->n_plants, (hipStream_t)stream);
+  if (h->autoreset)   /* from the bank while it has slots, else from the snapshot; same stream, nothing read back, the maintenance cache kept per plant by the kernel itself */
+    h->K->episode(h->params.mode, h->n_plants, NPB_N(h), h->f64, source_of(h, h->bank && h->next_slot), done, reward, obs, h->ep_len, h->ep_ret,
+                  h->ep_out_len, h->ep_out_ret, h->ep_out_truncated, h->ep_final_obs, h->max_episode_steps,
+                  maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, NPB_EHIP, "npb_step: kernel launch failed", e);
   return NPB_OK;
@@ -525,9 +526,9 @@ int npb_restore(NpbHandle *h, const uint8_t *mask, void *stream) {
   if (!h->snap) return fail(h, NPB_EINVAL, "npb_restore: no snapshot (npb_snapshot) to restore from");
   NPB_USE_DEVICE(h);
   const bool maint = h->params.maint_enabled != 0;
-  (h->storage == NPB_STORAGE_F32 ? npb32_launch_restore : npb_launch_restore)(h->n_plants, NPB_N(h), h->f64, h->snap, mask, h->ep_len, h->ep_ret,
-                                                                              maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
-  if (h->ep_start) npb_launch_start_clear(mask, h->ep_start, h->n_plants, h->pitch, (hipStream_t)stream);
+  h->K->restore(h->n_plants, NPB_N(h), h->f64, source_of(h, false), mask, h->ep_len, h->ep_ret,
+                maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
+  clear_episodes(h, mask, false, (hipStream_t)stream);     /* the restored episodes are not from the bank */
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -605,8 +606,8 @@ int npb_restore_bank(NpbHandle *h, const uint8_t *mask, void *stream) {
   if (!h->bank || !h->next_slot) return fail(h, NPB_EINVAL, "npb_restore_bank: no start bank (npb_set_start_bank) with slots (npb_set_start_slots) to restore from");
   NPB_USE_DEVICE(h);
   const bool maint = h->params.maint_enabled != 0;
-  (h->storage == NPB_STORAGE_F32 ? npb32_launch_restore_bank : npb_launch_restore_bank)(h->n_plants, NPB_N(h), h->f64, bank_of(h), mask, h->ep_len, h->ep_ret,
-                                                                                        maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
+  h->K->restore(h->n_plants, NPB_N(h), h->f64, source_of(h, true), mask, h->ep_len, h->ep_ret,
+                maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -713,7 +714,7 @@ int npb_debug_touch(NpbHandle *h, void *stream) {
 int npb_observe(NpbHandle *h, double *obs, void *stream) {
   if (!h || !obs) return NPB_EINVAL;
   NPB_USE_DEVICE(h);
-  (h->storage == NPB_STORAGE_F32 ? npb32_launch_observe : npb_launch_observe)(h->params.mode, h->n_plants, NPB_N(h), h->f64, obs, (hipStream_t)stream);
+  h->K->observe(h->params.mode, h->n_plants, NPB_N(h), h->f64, obs, (hipStream_t)stream);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, NPB_EHIP, "npb_observe: kernel launch failed", e);
   return NPB_OK;

@@ -1,6 +1,7 @@
 /* npb_kernels.h -- host-callable launchers of the device kernels (internal to libnpb.so).
- * npb_kernels.hip is compiled twice: 8-byte arena columns (npb_launch_*) and 4-byte columns for fp32 storage
- * (npb32_launch_*, -DNPB_BUILD_F32); the arena pointer is void* here and typed inside each translation unit. */
+ * npb_kernels.hip is compiled twice: 8-byte arena columns (npb_launch_table) and 4-byte columns for fp32 storage
+ * (npb32_launch_table, -DNPB_BUILD_F32); the arena pointer is void* here and typed inside each translation unit.  A handle
+ * picks its table once, by its storage type. */
 #ifndef NPB_KERNELS_H
 #define NPB_KERNELS_H
 #include <hip/hip_runtime.h>
@@ -11,52 +12,46 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-/* a start bank (npb_set_start_bank) and its slot columns (npb_set_start_slots) as the bank kernels take them */
+/* where a restore copies from: the snapshot (npb_snapshot), or a start bank (npb_set_start_bank) with its slot columns
+ * (npb_set_start_slots).  Entry s of the source is lane s of an arena in a handle's own layout; a snapshot has the bank fields NULL */
 typedef struct {
-  const void *arena;        /* the bank arena: M plants in the layout of the handle it was copied from */
+  const void *arena;        /* the snapshot arena, or the bank arena: M plants in the layout of the handle it was copied from */
   size_t N;                 /* its packed pitch: pitch | segment size << 32 (NPD_SEGMENT) */
-  int M;                    /* its entries */
-  int32_t *next_slot;       /* the caller's [n]: a restored plant takes entry ((next_slot % M) + M) % M, then next_slot = (s + advance) % M */
+  int M;                    /* a bank's entries */
+  int32_t *next_slot;       /* the caller's [n], NULL for the snapshot: a restored plant takes entry ((next_slot % M) + M) % M, then next_slot = (s + advance) % M */
   int32_t *episode_start;   /* the caller's [n], or NULL: the entry a restored plant took */
   int advance;
   int32_t *start;           /* carried [pitch]: the entry of each plant's running episode, -1 = not from the bank */
   int32_t *out_start;       /* the caller's [n], or NULL: the episode kernel's copy of `start` as of each step */
-} npb_bank_t;
-#define NPB__DECL(prefix) \
-  int prefix##step(const npb_params_t *P, int n_plants, size_t npad, void *arena, const int32_t *action, \
-                    const double *magnitude, const double *setpoint, const double *noise_z, const double *cw_temp, \
-                    double *obs, double *reward, uint8_t *done, uint32_t *trip_flags, double *info, int variant, double *diag, size_t diag_pitch, \
-                    const npb_maint_table_t *maint_table, void *maint_side, int32_t *maint_counts, hipStream_t stream); \
-  void prefix##maint(size_t npad, void *arena, void *maint_side, int32_t *counts, int n_plants, hipStream_t stream); \
-  void prefix##maint_consts(const npb_params_t *P, const npb_maint_table_t *T, void *host_out); \
-  size_t prefix##maint_consts_bytes(void); \
-  size_t prefix##maint_side_bytes(size_t npad); \
-  size_t prefix##maint_cache_offset(void); \
-  void prefix##observe(int mode, int n_plants, size_t npad, const void *arena, double *obs, hipStream_t stream); \
-  void prefix##init(const npb_params_t *P, int n_plants, size_t npad, void *arena, const uint8_t *mask, hipStream_t stream); \
-  void prefix##reset(const npb_params_t *P, int n_plants, size_t npad, void *arena, const uint8_t *mask, int steady, hipStream_t stream); \
-  /* kind: 0 carried real, 1 output real (float), 2 int32; buffers: double for reals, int32 for ints */ \
-  void prefix##field_get(const void *arena, size_t npad, int col, int sub, int kind, void *out, int n, hipStream_t stream); \
-  void prefix##field_set(void *arena, size_t npad, int col, int sub, int kind, const void *in, int n, hipStream_t stream); \
-  void prefix##gather(const void *arena, size_t npad, const int *plan_dev, int n_fields, double *out, int n, hipStream_t stream); \
-  /* episodes: snap = the snapshot arena (the arena's layout); maint_side / maint_counts NULL unless params.maint_enabled */ \
-  void prefix##restore(int n_plants, size_t npad, void *arena, const void *snap, const uint8_t *mask, int32_t *len, double *ret, \
-                       void *maint_side, int32_t *maint_counts, hipStream_t stream); \
-  void prefix##episode(int mode, int n_plants, size_t npad, void *arena, const void *snap, const uint8_t *done, const double *reward, \
-                       double *obs, int32_t *len, double *ret, int32_t *out_len, double *out_ret, uint8_t *out_truncated, \
-                       double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, hipStream_t stream); \
-  /* the same from a start bank */ \
-  void prefix##restore_bank(int n_plants, size_t npad, void *arena, npb_bank_t bank, const uint8_t *mask, int32_t *len, double *ret, \
-                            void *maint_side, int32_t *maint_counts, hipStream_t stream); \
-  void prefix##episode_bank(int mode, int n_plants, size_t npad, void *arena, npb_bank_t bank, const uint8_t *done, const double *reward, \
-                            double *obs, int32_t *len, double *ret, int32_t *out_len, double *out_ret, uint8_t *out_truncated, \
-                            double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, hipStream_t stream);
-NPB__DECL(npb_launch_)
-NPB__DECL(npb32_launch_)
-#undef NPB__DECL
+} npb_source_t;
+typedef struct {
+  int (*step)(const npb_params_t *P, int n_plants, size_t npad, void *arena, const int32_t *action,
+              const double *magnitude, const double *setpoint, const double *noise_z, const double *cw_temp,
+              double *obs, double *reward, uint8_t *done, uint32_t *trip_flags, double *info, int variant, double *diag, size_t diag_pitch,
+              const npb_maint_table_t *maint_table, void *maint_side, int32_t *maint_counts, hipStream_t stream);
+  void (*maint)(size_t npad, void *arena, void *maint_side, int32_t *counts, int n_plants, hipStream_t stream);
+  void (*observe)(int mode, int n_plants, size_t npad, const void *arena, double *obs, hipStream_t stream);
+  void (*init)(const npb_params_t *P, int n_plants, size_t npad, void *arena, const uint8_t *mask, hipStream_t stream);
+  void (*reset)(const npb_params_t *P, int n_plants, size_t npad, void *arena, const uint8_t *mask, int steady, hipStream_t stream);
+  /* kind: 0 carried real, 1 output real (float), 2 int32; buffers: double for reals, int32 for ints */
+  void (*field_get)(const void *arena, size_t npad, int col, int sub, int kind, void *out, int n, hipStream_t stream);
+  void (*field_set)(void *arena, size_t npad, int col, int sub, int kind, const void *in, int n, hipStream_t stream);
+  void (*gather)(const void *arena, size_t npad, const int *plan_dev, int n_fields, double *out, int n, hipStream_t stream);
+  /* episodes: src = the snapshot or a bank with slots (npb_source_t); maint_side / maint_counts NULL unless params.maint_enabled */
+  void (*restore)(int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *mask, int32_t *len, double *ret,
+                  void *maint_side, int32_t *maint_counts, hipStream_t stream);
+  void (*episode)(int mode, int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *done, const double *reward,
+                  double *obs, int32_t *len, double *ret, int32_t *out_len, double *out_ret, uint8_t *out_truncated,
+                  double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, hipStream_t stream);
+} npb_launchers_t;
+extern npb_launchers_t npb_launch_table, npb32_launch_table;
+/* the same for either storage type */
+void npb_launch_maint_consts(const npb_params_t *P, const npb_maint_table_t *T, void *host_out);
+size_t npb_launch_maint_consts_bytes(void);
+size_t npb_launch_maint_side_bytes(size_t npad);
+size_t npb_launch_maint_cache_offset(void);
 void npb_launch_touch(size_t npad, double *arena, hipStream_t stream);
-void npb_launch_episode_clear(const uint8_t *mask, int32_t *len, double *ret, int n_plants, size_t npad, hipStream_t stream);
-void npb_launch_start_clear(const uint8_t *mask, int32_t *start, int n_plants, size_t npad, hipStream_t stream);
+void npb_launch_episode_clear(const uint8_t *mask, int32_t *len, double *ret, int32_t *start, int n_plants, size_t npad, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -608,9 +608,9 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_observe_kernel(int mode, int n_p
   npd_store_rows<NPB_OBS_DIM>(obs, obs_out, lds, block_base, (size_t)n_plants);
 }
 
-/* ---- episodes: restore from the handle's snapshot arena (npb_snapshot / npb_restore) and same-step autoreset after npb_step
- * (npb_set_autoreset).  The snapshot has the arena's own layout (segments, pitch, storage type), so a plant's element of column c
- * sits at the same offset in both: restoring a plant is a copy of its lane of every column, nothing is decoded. */
+/* ---- episodes: restore from the handle's snapshot arena (npb_snapshot / npb_restore) or from a start bank (npb_set_start_bank /
+ * npb_restore_bank), and same-step autoreset after npb_step (npb_set_autoreset).  Either source is an arena in a handle's own layout
+ * (segments, pitch, storage type; npb_source_t): restoring a plant is a copy of one lane of every column, nothing is decoded. */
 #ifdef NPB_BUILD_F32
 typedef uint32_t npd_word_t;
 #else
@@ -619,40 +619,52 @@ typedef uint64_t npd_word_t;
 /* where the restore writes besides the arena: the maintenance screen's cooldown cache (zeroed = "look", npd_maintenance.h) and the
  * caller's event-count column (npb_set_maintenance_count_buffer), both NULL unless params.maint_enabled */
 struct npd_restore_side_t { npd_u32x4 *maint_entry; int32_t *maint_counts; int n_plants; };
-/* the wave's plants with `reset` set go back to the snapshot; f64 / snap / N already moved to the wave's segment.  Only reset lanes
- * load and store (a wave whose 64 plants all reset moves 512 B per column and direction, coalesced; one with a single reset plant
- * touches one line per column instead of the wave's 512 B): the copy is latency-bound, so the loads of U columns are issued
- * before their stores */
-__device__ __forceinline__ void npd_restore_lanes(npd_real_t *__restrict__ f64, const npd_real_t *__restrict__ snap, size_t N, size_t p, bool reset,
+/* the bank entry a restored plant takes from its slot, and the slot and start columns it leaves behind (include/npb.h) */
+__device__ __forceinline__ int32_t npd_bank_take(const npb_source_t &B, size_t p) {
+  int32_t s = B.next_slot[p] % B.M;
+  if (s < 0) s += B.M;                  /* ((next % M) + M) % M, for any value the caller wrote */
+  B.next_slot[p] = (int32_t)(((uint32_t)s + (uint32_t)B.advance) % (uint32_t)B.M);    /* s, advance < 2^31: no wrap */
+  if (B.episode_start) B.episode_start[p] = s;
+  B.start[p] = s;
+  return s;
+}
+/* the wave's plants with `reset` set from entry s of the source (the snapshot: s = p; a bank: the entry the plant took); f64 / N
+ * already moved to the wave's segment, the source is moved per lane through its own pitch and segment.  Only reset lanes load and
+ * store: a wave whose 64 plants all reset from the snapshot moves 512 B per column and direction, coalesced; one with a single reset
+ * plant touches one line per column, and so does every lane of a bank restore, whose neighbouring lanes generally read different
+ * entries.  The copy is latency-bound, so the loads of U columns are issued before their stores */
+__device__ __forceinline__ void npd_restore_lanes(npd_real_t *__restrict__ f64, size_t N, size_t p, bool reset, const npb_source_t &src, size_t s,
                                                   const npd_restore_side_t &R) {
-  npd_word_t *dst = reinterpret_cast<npd_word_t *>(f64);
-  const npd_word_t *src = reinterpret_cast<const npd_word_t *>(snap);
+  if (!reset) return;
+  const npd_real_t *from = (const npd_real_t *)src.arena;
+  size_t Ns = src.N;
+  NPD_SEGMENT(from, Ns, s);
+  npd_word_t *dst = reinterpret_cast<npd_word_t *>(f64) + p;
+  const npd_word_t *in = reinterpret_cast<const npd_word_t *>(from) + s;
   constexpr int U = 32;
-  if (reset) {
 #pragma unroll 1
-    for (int c0 = 0; c0 < NPD_ARENA_COLS; c0 += U) {
-      npd_word_t v[U];
+  for (int c0 = 0; c0 < NPD_ARENA_COLS; c0 += U) {
+    npd_word_t v[U];
 #pragma unroll
-      for (int u = 0; u < U; u++)
-        if (c0 + u < NPD_ARENA_COLS) v[u] = __builtin_nontemporal_load(&src[(size_t)(c0 + u) * N + p]);
+    for (int u = 0; u < U; u++)
+      if (c0 + u < NPD_ARENA_COLS) v[u] = __builtin_nontemporal_load(&in[(size_t)(c0 + u) * Ns]);
 #pragma unroll
-      for (int u = 0; u < U; u++)
-        if (c0 + u < NPD_ARENA_COLS) dst[(size_t)(c0 + u) * N + p] = v[u];
-    }
+    for (int u = 0; u < U; u++)
+      if (c0 + u < NPD_ARENA_COLS) dst[(size_t)(c0 + u) * N] = v[u];
   }
-  if (reset && R.maint_entry) {       /* the cooldowns of the restored stamps are unknown to the cache: look */
+  if (R.maint_entry) {                /* the cooldowns of the restored stamps are unknown to the cache: look */
     const npd_u32x4 zero = {0u, 0u, 0u, 0u};
     R.maint_entry[p * 2] = zero; R.maint_entry[p * 2 + 1] = zero;
   }
-  if (reset && R.maint_counts && p < (size_t)R.n_plants) {
-    const npd_real_t *f64 = snap;     /* (the member macro reads `f64`) */
-    R.maint_counts[p] = NPD_I32_COL(MAINT, npb_maint_t, maintenance_actions_performed, 0);
+  if (R.maint_counts && p < (size_t)R.n_plants) {
+    int32_t *counts = R.maint_counts + p;
+    const npd_real_t *f64 = from;     /* (the member macro reads `f64`, `N` and `p`: the source entry's) */
+    const size_t N = Ns, p = s;
+    *counts = NPD_I32_COL(MAINT, npb_maint_t, maintenance_actions_performed, 0);
   }
 }
-/* [64][W] rows held one per lane -> row-major global memory, only the rows whose bit is set in `rows` (npd_store_rows otherwise).
- * TAG only separates instantiations: the bank episode kernel calls its own, because sharing one with npb_episode_kernel changed
- * that kernel's address arithmetic (same registers, other instructions) */
-template <int W, int TAG = 0>
+/* [64][W] rows held one per lane -> row-major global memory, only the rows whose bit is set in `rows` (npd_store_rows otherwise) */
+template <int W>
 __device__ __forceinline__ void npd_store_rows_masked(const double *row, double *__restrict__ out, double *lds, size_t block_base, uint64_t rows) {
   const int lane = threadIdx.x;
 #pragma unroll
@@ -671,13 +683,12 @@ struct npd_episode_t {
   int32_t *out_len; double *out_ret; uint8_t *out_truncated; double *final_obs;   /* the caller's columns, each may be NULL */
   int max_steps;                                              /* 0 = no limit */
 };
-__global__ __launch_bounds__(NPB_WAVE) void npb_episode_kernel(int mode, int n_plants, size_t N, npd_real_t *__restrict__ f64, const npd_real_t *__restrict__ snap,
+/* src: the snapshot, or a bank with its slots (then it also hands out the bank entry of each plant's episode as of this step) */
+__global__ __launch_bounds__(NPB_WAVE) void npb_episode_kernel(int mode, int n_plants, size_t N, npd_real_t *__restrict__ f64, npb_source_t src,
                                                                const uint8_t *__restrict__ done, const double *__restrict__ reward, double *__restrict__ obs_out,
                                                                npd_episode_t E, npd_restore_side_t R) {
   __shared__ double lds[NPB_WAVE * NPB_OBS_PAD];
   const size_t block_base = (size_t)blockIdx.x * NPB_WAVE;
-  size_t Ns = N;
-  NPD_SEGMENT(snap, Ns, block_base);
   NPD_SEGMENT(f64, N, block_base);
   const size_t p = block_base + threadIdx.x;
   bool reset = false;
@@ -690,6 +701,7 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_episode_kernel(int mode, int n_p
     if (E.out_len) E.out_len[p] = len;
     if (E.out_ret) E.out_ret[p] = ret;
     if (E.out_truncated) E.out_truncated[p] = (uint8_t)truncated;
+    if (src.out_start) src.out_start[p] = src.start[p];      /* the episode this step's transition belonged to */
     E.len[p] = reset ? 0 : len;
     E.ret[p] = reset ? 0.0 : ret;
   }
@@ -702,123 +714,27 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_episode_kernel(int mode, int n_p
       if ((rows >> (idx / NPB_OBS_DIM)) & 1u) E.final_obs[block_base * NPB_OBS_DIM + idx] = obs_out[block_base * NPB_OBS_DIM + idx];
     }
   }
-  npd_restore_lanes(f64, snap, N, p, reset, R);
+  const size_t s = reset && src.next_slot ? (size_t)npd_bank_take(src, p) : p;
+  npd_restore_lanes(f64, N, p, reset, src, s, R);
   if (obs_out) {
     double obs[NPB_OBS_DIM];
     npd_observe_row(mode, f64, N, p, obs);
     npd_store_rows_masked<NPB_OBS_DIM>(obs, obs_out, lds, block_base, rows);
   }
 }
-/* npb_restore: the plants of mask (NULL = all) back to the snapshot, their episode counters (if any) to zero */
-__global__ __launch_bounds__(NPB_WAVE) void npb_restore_kernel(int n_plants, size_t N, npd_real_t *__restrict__ f64, const npd_real_t *__restrict__ snap,
+/* npb_restore / npb_restore_bank: the lanes below `lanes` of mask (NULL = all of them) from the source, their episode counters (if
+ * any) to zero */
+__global__ __launch_bounds__(NPB_WAVE) void npb_restore_kernel(int lanes, size_t N, npd_real_t *__restrict__ f64, npb_source_t src,
                                                                const uint8_t *__restrict__ mask, int32_t *__restrict__ len, double *__restrict__ ret,
                                                                npd_restore_side_t R) {
   const size_t block_base = (size_t)blockIdx.x * NPB_WAVE;
-  size_t Ns = N;
-  NPD_SEGMENT(snap, Ns, block_base);
   NPD_SEGMENT(f64, N, block_base);
   const size_t p = block_base + threadIdx.x;
-  const bool reset = mask ? (p < (size_t)n_plants && mask[p] != 0) : true;
+  const bool reset = p < (size_t)lanes && (!mask || mask[p] != 0);
   if (reset && len) { len[p] = 0; ret[p] = 0.0; }
   if (!__any(reset)) return;
-  npd_restore_lanes(f64, snap, N, p, reset, R);
-}
-
-/* ---- start bank (npb_set_start_bank / npb_restore_bank, and the autoreset with a bank): the source of a restore is entry s of the
- * bank, chosen per plant (npd_bank_take), addressed through the bank's own pitch and segment.  The bank kernels are separate
- * kernels, so that the snapshot path above keeps its code. */
-/* the bank entry a restored plant takes from its slot, and the slot and start columns it leaves behind (include/npb.h) */
-__device__ __forceinline__ int32_t npd_bank_take(const npb_bank_t &B, size_t p) {
-  int32_t s = B.next_slot[p] % B.M;
-  if (s < 0) s += B.M;                  /* ((next % M) + M) % M, for any value the caller wrote */
-  B.next_slot[p] = (int32_t)(((uint32_t)s + (uint32_t)B.advance) % (uint32_t)B.M);    /* s, advance < 2^31: no wrap */
-  if (B.episode_start) B.episode_start[p] = s;
-  B.start[p] = s;
-  return s;
-}
-/* npd_restore_lanes with a per-lane source: the wave's plants with `reset` set from bank entry s of their lane; f64 / N already moved
- * to the wave's segment, the bank (bank, Nb packed) is moved per lane.  Neighbouring lanes generally read different entries, so the
- * loads are not coalesced (one line per lane and column); the copy stays latency-bound and the loads of U columns are issued before
- * their stores */
-__device__ __forceinline__ void npd_restore_lanes_bank(npd_real_t *__restrict__ f64, size_t N, size_t p, bool reset, const npd_real_t *__restrict__ bank,
-                                                       size_t Nb, int32_t s, const npd_restore_side_t &R) {
-  if (!reset) return;
-  NPD_SEGMENT(bank, Nb, (size_t)s);
-  npd_word_t *dst = reinterpret_cast<npd_word_t *>(f64) + p;
-  const npd_word_t *src = reinterpret_cast<const npd_word_t *>(bank) + s;
-  constexpr int U = 32;
-#pragma unroll 1
-  for (int c0 = 0; c0 < NPD_ARENA_COLS; c0 += U) {
-    npd_word_t v[U];
-#pragma unroll
-    for (int u = 0; u < U; u++)
-      if (c0 + u < NPD_ARENA_COLS) v[u] = __builtin_nontemporal_load(&src[(size_t)(c0 + u) * Nb]);
-#pragma unroll
-    for (int u = 0; u < U; u++)
-      if (c0 + u < NPD_ARENA_COLS) dst[(size_t)(c0 + u) * N] = v[u];
-  }
-  if (R.maint_entry) {                /* the cooldowns of the restored stamps are unknown to the cache: look */
-    const npd_u32x4 zero = {0u, 0u, 0u, 0u};
-    R.maint_entry[p * 2] = zero; R.maint_entry[p * 2 + 1] = zero;
-  }
-  if (R.maint_counts && p < (size_t)R.n_plants) {
-    int32_t *counts = R.maint_counts + p;
-    const npd_real_t *f64 = bank;     /* (the member macro reads `f64`, `N` and `p`: the bank entry's) */
-    const size_t N = Nb, p = (size_t)s;
-    *counts = NPD_I32_COL(MAINT, npb_maint_t, maintenance_actions_performed, 0);
-  }
-}
-/* npb_episode_kernel restoring from the bank; also hands out the bank entry of each plant's episode as of this step */
-__global__ __launch_bounds__(NPB_WAVE) void npb_episode_bank_kernel(int mode, int n_plants, size_t N, npd_real_t *__restrict__ f64, npb_bank_t B,
-                                                                    const uint8_t *__restrict__ done, const double *__restrict__ reward, double *__restrict__ obs_out,
-                                                                    npd_episode_t E, npd_restore_side_t R) {
-  __shared__ double lds[NPB_WAVE * NPB_OBS_PAD];
-  const size_t block_base = (size_t)blockIdx.x * NPB_WAVE;
-  NPD_SEGMENT(f64, N, block_base);
-  const size_t p = block_base + threadIdx.x;
-  bool reset = false;
-  if (p < (size_t)n_plants) {
-    const bool terminated = done[p] != 0;
-    const int32_t len = E.len[p] + 1;
-    const double ret = reward ? E.ret[p] + reward[p] : E.ret[p];
-    const bool truncated = E.max_steps > 0 && len >= E.max_steps && !terminated;     /* termination wins */
-    reset = terminated || truncated;
-    if (E.out_len) E.out_len[p] = len;
-    if (E.out_ret) E.out_ret[p] = ret;
-    if (E.out_truncated) E.out_truncated[p] = (uint8_t)truncated;
-    if (B.out_start) B.out_start[p] = B.start[p];      /* the episode this step's transition belonged to */
-    E.len[p] = reset ? 0 : len;
-    E.ret[p] = reset ? 0.0 : ret;
-  }
-  if (!__any(reset)) return;
-  const uint64_t rows = __ballot(reset);
-  if (obs_out && E.final_obs) {     /* the terminal observation: this step's row, before it is replaced */
-#pragma unroll
-    for (int k = 0; k < NPB_OBS_DIM; k++) {
-      const int idx = k * NPB_WAVE + threadIdx.x;
-      if ((rows >> (idx / NPB_OBS_DIM)) & 1u) E.final_obs[block_base * NPB_OBS_DIM + idx] = obs_out[block_base * NPB_OBS_DIM + idx];
-    }
-  }
-  const int32_t s = reset ? npd_bank_take(B, p) : 0;
-  npd_restore_lanes_bank(f64, N, p, reset, (const npd_real_t *)B.arena, B.N, s, R);
-  if (obs_out) {
-    double obs[NPB_OBS_DIM];
-    npd_observe_row(mode, f64, N, p, obs);
-    npd_store_rows_masked<NPB_OBS_DIM, 1>(obs, obs_out, lds, block_base, rows);
-  }
-}
-/* npb_restore_bank: the plants of mask (NULL = all) from their bank entries, their episode counters (if any) to zero */
-__global__ __launch_bounds__(NPB_WAVE) void npb_restore_bank_kernel(int n_plants, size_t N, npd_real_t *__restrict__ f64, npb_bank_t B,
-                                                                    const uint8_t *__restrict__ mask, int32_t *__restrict__ len, double *__restrict__ ret,
-                                                                    npd_restore_side_t R) {
-  const size_t block_base = (size_t)blockIdx.x * NPB_WAVE;
-  NPD_SEGMENT(f64, N, block_base);
-  const size_t p = block_base + threadIdx.x;
-  const bool reset = p < (size_t)n_plants && (!mask || mask[p] != 0);     /* the slot columns have n entries: no padding lane */
-  if (reset && len) { len[p] = 0; ret[p] = 0.0; }
-  if (!__any(reset)) return;
-  const int32_t s = reset ? npd_bank_take(B, p) : 0;
-  npd_restore_lanes_bank(f64, N, p, reset, (const npd_real_t *)B.arena, B.N, s, R);
+  const size_t s = reset && src.next_slot ? (size_t)npd_bank_take(src, p) : p;
+  npd_restore_lanes(f64, N, p, reset, src, s, R);
 }
 
 /* construction-time state for every plant selected by mask (NULL = all): the state the reference's
@@ -909,7 +825,7 @@ extern "C" void npb_launch_touch(size_t npad_seg, double *f64, hipStream_t strea
 }
 #endif
 
-/* ---- host-side launchers (called from npb_api.hip); one set per storage type */
+/* ---- host-side launchers: one table per storage type (npb_launchers_t), which npb_api.hip calls through */
 #ifdef NPB_BUILD_F32
 #define NPB_LAUNCHER(name) npb32_launch_##name
 #else
@@ -951,13 +867,13 @@ __global__ void npb_gather_kernel(const npd_real_t *__restrict__ arena, size_t N
   else v = (double)*(const int32_t *)(e + sub * 4);
   out[(size_t)f * n + i] = v;
 }
-extern "C" void NPB_LAUNCHER(gather)(const void *arena, size_t npad, const int *plan_dev, int n_fields, double *out, int n, hipStream_t stream) {
+static void NPB_LAUNCHER(gather)(const void *arena, size_t npad, const int *plan_dev, int n_fields, double *out, int n, hipStream_t stream) {
   hipLaunchKernelGGL(npb_gather_kernel, dim3((n + 255) / 256, n_fields), dim3(256), 0, stream, (const npd_real_t *)arena, npad, plan_dev, out, n);
 }
-extern "C" void NPB_LAUNCHER(field_get)(const void *arena, size_t npad, int col, int sub, int kind, void *out, int n, hipStream_t stream) {
+static void NPB_LAUNCHER(field_get)(const void *arena, size_t npad, int col, int sub, int kind, void *out, int n, hipStream_t stream) {
   hipLaunchKernelGGL(npb_field_get_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const npd_real_t *)arena, npad, col, sub, kind, out, n);
 }
-extern "C" void NPB_LAUNCHER(field_set)(void *arena, size_t npad, int col, int sub, int kind, const void *in, int n, hipStream_t stream) {
+static void NPB_LAUNCHER(field_set)(void *arena, size_t npad, int col, int sub, int kind, const void *in, int n, hipStream_t stream) {
   hipLaunchKernelGGL(npb_field_set_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (npd_real_t *)arena, npad, col, sub, kind, in, n);
 }
 /* fp64-storage plants above which the sweep of a step (4 221 B per plant) is so far past the 256 MB Infinity Cache that streaming
@@ -995,11 +911,11 @@ static npd_maint_cache_t npd_maint_cache_of(void *maint_side, int32_t *counts, i
   return C;
 }
 /* maint_table / maint_side (the handle's maintenance side buffer, rule constants uploaded): NULL unless the automatic maintenance is on (npb_step) */
-extern "C" int NPB_LAUNCHER(step)(const npb_params_t *P, int n_plants, size_t npad_seg, void *arena,
-                                const int32_t *action, const double *magnitude, const double *setpoint,
-                                const double *noise_z, const double *cw_temp, double *obs, double *reward, uint8_t *done,
-                                uint32_t *trip_flags, double *info, int variant, double *diag, size_t diag_pitch,
-                                const npb_maint_table_t *maint_table, void *maint_side, int32_t *maint_counts, hipStream_t stream) {
+static int NPB_LAUNCHER(step)(const npb_params_t *P, int n_plants, size_t npad_seg, void *arena,
+                              const int32_t *action, const double *magnitude, const double *setpoint,
+                              const double *noise_z, const double *cw_temp, double *obs, double *reward, uint8_t *done,
+                              uint32_t *trip_flags, double *info, int variant, double *diag, size_t diag_pitch,
+                              const npb_maint_table_t *maint_table, void *maint_side, int32_t *maint_counts, hipStream_t stream) {
   const size_t npad = NPD_NPAD(npad_seg), seg = NPD_SEG_OF(npad_seg);   /* column pitch in plants / plants per arena segment (0: one segment) */
   npd_maint_hot_t MH;
   npd_maint_fold_table(P, maint_side ? maint_table : nullptr, &MH);
@@ -1054,12 +970,14 @@ extern "C" int NPB_LAUNCHER(step)(const npb_params_t *P, int n_plants, size_t np
   return with_maint ? NPB_KERNEL_STEP_MAINT : NPB_KERNEL_STEP;
 }
 /* the rule as a launch of its own (modes that do not step the pumps) */
-extern "C" void NPB_LAUNCHER(maint)(size_t npad, void *arena, void *maint_side, int32_t *counts, int n_plants, hipStream_t stream) {
+static void NPB_LAUNCHER(maint)(size_t npad, void *arena, void *maint_side, int32_t *counts, int n_plants, hipStream_t stream) {
   hipLaunchKernelGGL(npb_maint_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, (const npd_maint_rule_consts_t *)maint_side,
                      npd_maint_cache_of(maint_side, counts, n_plants), npad, (npd_real_t *)arena);
 }
-/* the rule's constants as the device reads them: host_out = NPB_LAUNCHER(maint_consts_bytes)() bytes */
-extern "C" void NPB_LAUNCHER(maint_consts)(const npb_params_t *P, const npb_maint_table_t *T, void *host_out) {
+#ifndef NPB_BUILD_F32
+/* the maintenance side buffer does not depend on the storage type (npd_maint_rule_consts_t holds no npd_real_t): one copy of
+ * these.  The rule's constants as the device reads them: host_out = npb_launch_maint_consts_bytes() bytes */
+extern "C" void npb_launch_maint_consts(const npb_params_t *P, const npb_maint_table_t *T, void *host_out) {
   npd_maint_rule_consts_t *RC = (npd_maint_rule_consts_t *)host_out;
   memset(RC, 0, sizeof(*RC));
   RC->P = *P; RC->T = *T;
@@ -1077,19 +995,20 @@ extern "C" void NPB_LAUNCHER(maint_consts)(const npb_params_t *P, const npb_main
     if (c != NPB_CMP_GREATER_THAN && c != NPB_CMP_GREATER_EQUAL && c != NPB_CMP_LESS_THAN && c != NPB_CMP_LESS_EQUAL && c != NPB_CMP_EQUALS) S.want_far |= bit;
   }
 }
-extern "C" size_t NPB_LAUNCHER(maint_consts_bytes)(void) { return sizeof(npd_maint_rule_consts_t); }
+extern "C" size_t npb_launch_maint_consts_bytes(void) { return sizeof(npd_maint_rule_consts_t); }
 /* rule constants + cooldown cache (npd_maint_cache_of); a zeroed cache = "nothing known: look" */
-extern "C" size_t NPB_LAUNCHER(maint_side_bytes)(size_t npad) { return NPD_MAINT_CONSTS_BYTES + (size_t)NPB_NUM_PUMPS * NPD_NPAD(npad) * (sizeof(float) + sizeof(uint32_t)); }
-extern "C" size_t NPB_LAUNCHER(maint_cache_offset)(void) { return NPD_MAINT_CONSTS_BYTES; }
-extern "C" void NPB_LAUNCHER(observe)(int mode, int n_plants, size_t npad, const void *arena, double *obs, hipStream_t stream) {
+extern "C" size_t npb_launch_maint_side_bytes(size_t npad) { return NPD_MAINT_CONSTS_BYTES + (size_t)NPB_NUM_PUMPS * NPD_NPAD(npad) * (sizeof(float) + sizeof(uint32_t)); }
+extern "C" size_t npb_launch_maint_cache_offset(void) { return NPD_MAINT_CONSTS_BYTES; }
+#endif
+static void NPB_LAUNCHER(observe)(int mode, int n_plants, size_t npad, const void *arena, double *obs, hipStream_t stream) {
   dim3 grid((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), block(NPB_WAVE);
   hipLaunchKernelGGL(npb_observe_kernel, grid, block, 0, stream, mode, n_plants, npad, (const npd_real_t *)arena, obs);
 }
-extern "C" void NPB_LAUNCHER(reset)(const npb_params_t *P, int n_plants, size_t npad, void *arena, const uint8_t *mask, int steady, hipStream_t stream) {
+static void NPB_LAUNCHER(reset)(const npb_params_t *P, int n_plants, size_t npad, void *arena, const uint8_t *mask, int steady, hipStream_t stream) {
   dim3 grid((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), block(NPB_WAVE);
   hipLaunchKernelGGL(npb_reset_kernel, grid, block, 0, stream, *P, npad, (npd_real_t *)arena, mask, n_plants, steady);
 }
-extern "C" void NPB_LAUNCHER(init)(const npb_params_t *P, int n_plants, size_t npad, void *arena, const uint8_t *mask, hipStream_t stream) {
+static void NPB_LAUNCHER(init)(const npb_params_t *P, int n_plants, size_t npad, void *arena, const uint8_t *mask, hipStream_t stream) {
   dim3 grid((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), block(NPB_WAVE);
   hipLaunchKernelGGL(npb_init_kernel, grid, block, 0, stream, *P, npad, (npd_real_t *)arena, mask, n_plants);
 }
@@ -1099,51 +1018,40 @@ static npd_restore_side_t npd_restore_side_of(void *maint_side, int32_t *maint_c
   R.maint_entry = npd_maint_cache_of(maint_side, maint_counts, n_plants).entry; R.maint_counts = maint_counts; R.n_plants = n_plants;
   return R;
 }
-extern "C" void NPB_LAUNCHER(restore)(int n_plants, size_t npad, void *arena, const void *snap, const uint8_t *mask, int32_t *len, double *ret,
-                                      void *maint_side, int32_t *maint_counts, hipStream_t stream) {
-  hipLaunchKernelGGL(npb_restore_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, n_plants, npad, (npd_real_t *)arena,
-                     (const npd_real_t *)snap, mask, len, ret, npd_restore_side_of(maint_side, maint_counts, n_plants));
+/* src: the snapshot (npb_restore, the snapshot autoreset) or a bank with its slots (npb_restore_bank, the bank autoreset).  mask NULL
+ * restores every lane of the pitch from the snapshot, the plants only from a bank (its slot columns have n entries) */
+static void NPB_LAUNCHER(restore)(int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *mask, int32_t *len, double *ret,
+                                  void *maint_side, int32_t *maint_counts, hipStream_t stream) {
+  const int lanes = mask || src.next_slot ? n_plants : (int)NPD_NPAD(npad);
+  hipLaunchKernelGGL(npb_restore_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, lanes, npad, (npd_real_t *)arena,
+                     src, mask, len, ret, npd_restore_side_of(maint_side, maint_counts, n_plants));
 }
-extern "C" void NPB_LAUNCHER(episode)(int mode, int n_plants, size_t npad, void *arena, const void *snap, const uint8_t *done, const double *reward,
-                                      double *obs, int32_t *len, double *ret, int32_t *out_len, double *out_ret, uint8_t *out_truncated,
-                                      double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, hipStream_t stream) {
+static void NPB_LAUNCHER(episode)(int mode, int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *done, const double *reward,
+                                  double *obs, int32_t *len, double *ret, int32_t *out_len, double *out_ret, uint8_t *out_truncated,
+                                  double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, hipStream_t stream) {
   npd_episode_t E;
   E.len = len; E.ret = ret; E.out_len = out_len; E.out_ret = out_ret; E.out_truncated = out_truncated; E.final_obs = final_obs; E.max_steps = max_steps;
   hipLaunchKernelGGL(npb_episode_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, mode, n_plants, npad, (npd_real_t *)arena,
-                     (const npd_real_t *)snap, done, reward, obs, E, npd_restore_side_of(maint_side, maint_counts, n_plants));
+                     src, done, reward, obs, E, npd_restore_side_of(maint_side, maint_counts, n_plants));
 }
-extern "C" void NPB_LAUNCHER(restore_bank)(int n_plants, size_t npad, void *arena, npb_bank_t bank, const uint8_t *mask, int32_t *len, double *ret,
-                                           void *maint_side, int32_t *maint_counts, hipStream_t stream) {
-  hipLaunchKernelGGL(npb_restore_bank_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, n_plants, npad, (npd_real_t *)arena,
-                     bank, mask, len, ret, npd_restore_side_of(maint_side, maint_counts, n_plants));
-}
-extern "C" void NPB_LAUNCHER(episode_bank)(int mode, int n_plants, size_t npad, void *arena, npb_bank_t bank, const uint8_t *done, const double *reward,
-                                           double *obs, int32_t *len, double *ret, int32_t *out_len, double *out_ret, uint8_t *out_truncated,
-                                           double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, hipStream_t stream) {
-  npd_episode_t E;
-  E.len = len; E.ret = ret; E.out_len = out_len; E.out_ret = out_ret; E.out_truncated = out_truncated; E.final_obs = final_obs; E.max_steps = max_steps;
-  hipLaunchKernelGGL(npb_episode_bank_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, mode, n_plants, npad, (npd_real_t *)arena,
-                     bank, done, reward, obs, E, npd_restore_side_of(maint_side, maint_counts, n_plants));
-}
+/* not const: clang emits a namespace-scope const into the device code too, where these host functions do not exist */
+extern "C" npb_launchers_t NPB_LAUNCHER(table) = {
+  NPB_LAUNCHER(step), NPB_LAUNCHER(maint), NPB_LAUNCHER(observe), NPB_LAUNCHER(init), NPB_LAUNCHER(reset),
+  NPB_LAUNCHER(field_get), NPB_LAUNCHER(field_set), NPB_LAUNCHER(gather), NPB_LAUNCHER(restore), NPB_LAUNCHER(episode),
+};
 #ifndef NPB_BUILD_F32
-/* npb_reset / npb_reset_reference: the episode counters of the plants they reset (mask NULL = all) back to zero */
-__global__ void npb_episode_clear_kernel(const uint8_t *__restrict__ mask, int32_t *__restrict__ len, double *__restrict__ ret, int n_plants, int npad) {
+/* npb_reset / npb_reset_reference / npb_restore: the episode counters (len, ret) and the carried start entries (start: -1, not from
+ * the bank) of the plants of mask (NULL = every lane of the pitch); each column may be NULL */
+__global__ void npb_episode_clear_kernel(const uint8_t *__restrict__ mask, int32_t *__restrict__ len, double *__restrict__ ret, int32_t *__restrict__ start,
+                                         int n_plants, int npad) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= npad || (mask && (p >= n_plants || !mask[p]))) return;
-  len[p] = 0; ret[p] = 0.0;
+  if (len) len[p] = 0;
+  if (ret) ret[p] = 0.0;
+  if (start) start[p] = -1;
 }
-extern "C" void npb_launch_episode_clear(const uint8_t *mask, int32_t *len, double *ret, int n_plants, size_t npad, hipStream_t stream) {
+extern "C" void npb_launch_episode_clear(const uint8_t *mask, int32_t *len, double *ret, int32_t *start, int n_plants, size_t npad, hipStream_t stream) {
   const int n = (int)NPD_NPAD(npad);
-  hipLaunchKernelGGL(npb_episode_clear_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, mask, len, ret, n_plants, n);
-}
-/* npb_reset / npb_reset_reference / npb_restore with a start bank: the carried start entries of the plants they reset to -1 (not from the bank) */
-__global__ void npb_start_clear_kernel(const uint8_t *__restrict__ mask, int32_t *__restrict__ start, int n_plants, int npad) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= npad || (mask && (p >= n_plants || !mask[p]))) return;
-  start[p] = -1;
-}
-extern "C" void npb_launch_start_clear(const uint8_t *mask, int32_t *start, int n_plants, size_t npad, hipStream_t stream) {
-  const int n = (int)NPD_NPAD(npad);
-  hipLaunchKernelGGL(npb_start_clear_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, mask, start, n_plants, n);
+  hipLaunchKernelGGL(npb_episode_clear_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, mask, len, ret, start, n_plants, n);
 }
 #endif

@@ -605,7 +605,7 @@ class BatchedPlantEnv:
             info["maintenance_event_count"] = self._event_counts if self._event_counts is not None else self.get_field("maint.maintenance_actions_performed")
         if self._episode is not None:     # autoreset: written by the episode kernel behind the step (npb_set_autoreset)
             info.update(self._episode)
-            if self._bank is not None:    # the bank episode kernel's: the bank entry this transition's episode started from
+            if self._bank is not None:    # the episode kernel's, restoring from the bank: the bank entry this transition's episode started from
                 info["episode_start"] = self._episode_start_out
         return self._obs, self._reward, self._done, info
 

@@ -1,5 +1,5 @@
-"""What the autoreset costs when it restarts plants from a start bank (npb_set_start_bank: the bank episode kernel behind every
-npb_step) against the snapshot autoreset, at 65 536 plants.
+"""What the autoreset costs when it restarts plants from a start bank (npb_set_start_bank: the episode kernel behind every
+npb_step, restoring from the bank) against the snapshot autoreset, at 65 536 plants.
 
 One handle throughout, as in tools/autoreset_overhead.py -- where an arena lands in physical memory moves the step time from one
 handle to the next (npb_api.hip, probe_placement).  The bank is a second batch of --bank plants, copied in before each bank block.  After >= 200
