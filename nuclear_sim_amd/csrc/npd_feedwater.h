@@ -409,12 +409,95 @@ NPD_FN double npd_fw_level_control(npb_fw_t *fw, const double *sg_levels, const 
   return total_flow_demand;
 }
 
-/* one pump of FeedwaterPumpSystem.update_system  pump_system.py:1235-1329, followed by this pump's pass
- * through PerformanceDiagnostics.update_diagnostics  performance_monitoring.py:423-542 (shared
- * CavitationModel :113-202) and the per-pump loops of FeedwaterProtectionSystem.check_protection_systems
- * protection_system.py:378-481.  Protection setpoints resolve through getattr fallbacks against
- * FeedwaterProtectionConfig: NPSH low-low / critical and suction-pressure trips all fall back to
- * low_suction_pressure_trip = 0.1; discharge 10.0; vibration 10, bearing 120, motor 130; delays 5/10/30/60 s. */
+/* one pump of FeedwaterPumpSystem.update_system  pump_system.py:1262-1283: the demand hand-out gate (open while fewer pumps
+ * are RUNNING than ran in the previous step), then the pump itself */
+NPD_FN void npd_fw_pump_update(npb_pump_t *p, int gate_open, int n_prev_running, double flow_per_pump,
+                               const npd_pump_sysconds_t *sc, double dt) {
+  if (p->status == NPD_PUMP_RUNNING && n_prev_running > 0 && gate_open) {
+    if (!(flow_per_pump < NPD_PUMP_RATED_FLOW * 0.2)) npd_pump_set_flow_demand(p, flow_per_pump);
+  }
+  npd_pump_update(p, sc, dt);
+}
+
+/* the 13 values of an updated pump that its tail (below) reads; the multi-wave kernels publish them to LDS */
+enum { NPD_PUMP_VALS_N = 13 };
+typedef struct npd_pump_vals_t {
+  int code;   /* bit 0: RUNNING, bit 1: trip_active */
+  double flow_rate, power, npsh_required, npsh_available, speed_percent, max_bearing, seal_wear, vibration_level,
+         suction_pressure, discharge_pressure, oil_temperature, motor_temperature;
+} npd_pump_vals_t;
+/* ... read back from NPD_PUMP_VALS_N exchange slots of 64 doubles (slot j at x + j * NPB_WAVE), one lane per plant (npd2_publish_pump
+ * writes them) */
+NPD_FN npd_pump_vals_t npd_pump_vals_read(const double *x, int lane) {
+  npd_pump_vals_t v;
+  v.code = (int)x[0 * NPB_WAVE + lane];
+  v.flow_rate = x[1 * NPB_WAVE + lane]; v.power = x[2 * NPB_WAVE + lane]; v.npsh_required = x[3 * NPB_WAVE + lane];
+  v.npsh_available = x[4 * NPB_WAVE + lane]; v.speed_percent = x[5 * NPB_WAVE + lane]; v.max_bearing = x[6 * NPB_WAVE + lane];
+  v.seal_wear = x[7 * NPB_WAVE + lane]; v.vibration_level = x[8 * NPB_WAVE + lane]; v.suction_pressure = x[9 * NPB_WAVE + lane];
+  v.discharge_pressure = x[10 * NPB_WAVE + lane]; v.oil_temperature = x[11 * NPB_WAVE + lane]; v.motor_temperature = x[12 * NPB_WAVE + lane];
+  return v;
+}
+
+/* pump i's tail, after its update: the system sums of FeedwaterPumpSystem.update_system (pump_system.py:1285-1329), this pump's
+ * pass through PerformanceDiagnostics.update_diagnostics  performance_monitoring.py:423-542 (shared CavitationModel :113-202) and
+ * the per-pump loops of FeedwaterProtectionSystem.check_protection_systems  protection_system.py:378-481.  Protection setpoints
+ * resolve through getattr fallbacks against FeedwaterProtectionConfig: NPSH low-low / critical and suction-pressure trips all fall
+ * back to low_suction_pressure_trip = 0.1; discharge 10.0; vibration 10, bearing 120, motor 130; delays 5/10/30/60 s.
+ * The multi-wave kernels' text; npd_fw_pump_step below keeps its own, which also collects acc->trip_kinds for the diagnostics */
+NPD_FN void npd_fw_pump_tail(const npd_pump_vals_t &v, int i, npb_fw_t *fw, npd_fw_acc_t *acc, double dt) {
+  if (v.code & 1) { acc->total_flow += v.flow_rate; acc->total_power += v.power; acc->running_count++; acc->running_mask |= 1 << i; }
+  if (v.code & 2) acc->trip_mask |= 1u << i;
+  acc->flow_sum += v.flow_rate;
+  /* diagnostics: shared cavitation monitor, dt "hours" = simulator dt */
+  {
+    double cavitation_threshold = v.npsh_required + 2.0;
+    double current_intensity;
+    if (v.npsh_available < cavitation_threshold) {
+      double npsh_deficit = cavitation_threshold - v.npsh_available;
+      double severity = npd_pymin(1.0, npsh_deficit / cavitation_threshold);
+      double flow_factor = npd_sq(v.flow_rate / 555.0);
+      double speed_factor = npd_powc(v.speed_percent / 100.0, 1.5);
+      current_intensity = severity * flow_factor * speed_factor;
+      fw->cav_time_in_cavitation += dt;
+      if (current_intensity > 0.1) { fw->cav_events_count += 1; if (fw->cav_events_count > 100) fw->cav_events_count = 100; }
+    } else {
+      current_intensity = 0.0;
+    }
+    if (current_intensity > 0.1) fw->cav_accumulated_damage += (npd_sq(current_intensity) * 0.01) * dt;
+    double intensity_risk = npd_pymin(1.0, current_intensity / 0.5);
+    double damage_risk = npd_pymin(1.0, fw->cav_accumulated_damage / 10.0);
+    double frequency_risk = npd_pymin(1.0, fw->cav_events_count / 50.0);
+    acc->total_cavitation_risk += (intensity_risk * 0.4 + damage_risk * 0.4 + frequency_risk * 0.2);
+    acc->total_wear_level += (v.max_bearing + v.seal_wear);
+    acc->total_vibration += v.vibration_level;
+  }
+  /* protection, per-pump loops */
+  double dt_seconds = dt * 60.0;
+  {
+    int critical_active = 0;
+    if (v.npsh_available < 0.1) {
+      fw->npsh_low_low_timer += dt_seconds;
+      if (fw->npsh_low_low_timer >= 5.0) fw->npsh_low_low_trip_active = 1;
+    } else {
+      fw->npsh_low_low_timer = 0.0;
+      fw->npsh_low_low_trip_active = 0;
+    }
+    if (v.npsh_available < 0.1) critical_active = 1;
+    if (critical_active || fw->npsh_low_low_trip_active) acc->trips++;
+  }
+  if (v.suction_pressure < 0.1) acc->trips++;
+  if (v.discharge_pressure > 10.0) acc->trips++;
+  if (v.vibration_level > 10.0) { fw->timer_vibration += dt_seconds; if (fw->timer_vibration >= 10.0) acc->trips++; }
+  else fw->timer_vibration = 0.0;
+  double bearing_temp = v.oil_temperature + 5.0; /* pump_system.py:477 */
+  if (bearing_temp > 120.0) { fw->timer_bearing_temp += dt_seconds; if (fw->timer_bearing_temp >= 30.0) acc->trips++; }
+  else fw->timer_bearing_temp = 0.0;
+  if (v.motor_temperature > 130.0) { fw->timer_motor_temp += dt_seconds; if (fw->timer_motor_temp >= 60.0) acc->trips++; }
+  else fw->timer_motor_temp = 0.0;
+}
+
+/* one pump of the one-wave kernel: its update behind the demand gate, then its tail.  Written out (not npd_fw_pump_update /
+ * npd_fw_pump_tail): as calls they move the one-wave kernels' register allocation */
 NPD_FN void npd_fw_pump_step(npb_pump_t *p, npb_fw_t *fw, npd_fw_acc_t *acc, int i, int n_prev_running,
                              double flow_per_pump, const npd_pump_sysconds_t *sc, double dt) {
   if (p->status == NPD_PUMP_RUNNING && n_prev_running > 0) {

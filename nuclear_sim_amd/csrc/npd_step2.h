@@ -62,7 +62,7 @@ enum {
   /* primary / feedwater control -> wave B */
   X_CFLOW0 = 0, X_CFLOW1, X_CFLOW2, X_CIN2, X_COUT2, X_LDF, X_FWTEMP, X_NPREV, X_FPP, X_MAXLVL,
   /* per-pump values for the diagnostics / protection passes: 13 per pump, pumps 0..3 */
-  X_PUMP = 10, X_PUMP_N = 13,
+  X_PUMP = 10, X_PUMP_N = NPD_PUMP_VALS_N,
   /* steam generators 1, 2 between their two parts: heat transfer, and the fp64 values of the two output members
    * (stored as float) that are still needed: TSP pressure-drop ratio, secondary temperature */
   X_SGCARRY = 62, X_FLAG2 = 68, X_MAINT_TAB = 69,
@@ -98,7 +98,8 @@ __device__ __forceinline__ void npd2_store_rows(const double *row, double *__res
   NPD_LDS_DRAIN();
 }
 
-/* the values of one updated pump that the diagnostics / protection passes and the system sums read */
+/* publish one updated pump's npd_pump_vals_t (npd_feedwater.h) to exchange slots X_PUMP + i * X_PUMP_N ... of xch (the four-wave
+ * kernel passes its own region's base shifted by X_PUMP) */
 __device__ __forceinline__ void npd2_publish_pump(double *xch, int lane, int i, const npb_pump_t &p) {
   const int b = X_PUMP + i * X_PUMP_N;
   XW(b + 0, (double)((p.status == NPD_PUMP_RUNNING) | (p.trip_active ? 2 : 0)));
@@ -108,209 +109,8 @@ __device__ __forceinline__ void npd2_publish_pump(double *xch, int lane, int i, 
   XW(b + 11, p.oil_temperature); XW(b + 12, p.motor_temperature);
 }
 
-/* npd_fw_pump_step's tail for one pump, from the published values: the system sums of FeedwaterPumpSystem.update_system
- * (pump_system.py:1285-1329), this pump's pass through PerformanceDiagnostics.update_diagnostics and through the per-pump
- * loops of FeedwaterProtectionSystem.check_protection_systems (npd_feedwater.h, npd_fw_pump_step) */
-__device__ __forceinline__ void npd2_pump_tail(const double *xch, int lane, int i, npb_fw_t *fw, npd_fw_acc_t *acc, double dt) {
-  const int b = X_PUMP + i * X_PUMP_N;
-  const int code = (int)XR(b + 0);
-  const double flow_rate = XR(b + 1), power = XR(b + 2), npsh_required = XR(b + 3), npsh_available = XR(b + 4), speed_percent = XR(b + 5);
-  const double max_bearing = XR(b + 6), seal_wear = XR(b + 7), vibration_level = XR(b + 8), suction_pressure = XR(b + 9);
-  const double discharge_pressure = XR(b + 10), oil_temperature = XR(b + 11), motor_temperature = XR(b + 12);
-  if (code & 1) { acc->total_flow += flow_rate; acc->total_power += power; acc->running_count++; acc->running_mask |= 1 << i; }
-  if (code & 2) acc->trip_mask |= 1u << i;
-  acc->flow_sum += flow_rate;
-  {
-    double cavitation_threshold = npsh_required + 2.0;
-    double current_intensity;
-    if (npsh_available < cavitation_threshold) {
-      double npsh_deficit = cavitation_threshold - npsh_available;
-      double severity = npd_pymin(1.0, npsh_deficit / cavitation_threshold);
-      double flow_factor = npd_sq(flow_rate / 555.0);
-      double speed_factor = npd_powc(speed_percent / 100.0, 1.5);
-      current_intensity = severity * flow_factor * speed_factor;
-      fw->cav_time_in_cavitation += dt;
-      if (current_intensity > 0.1) { fw->cav_events_count += 1; if (fw->cav_events_count > 100) fw->cav_events_count = 100; }
-    } else {
-      current_intensity = 0.0;
-    }
-    if (current_intensity > 0.1) fw->cav_accumulated_damage += (npd_sq(current_intensity) * 0.01) * dt;
-    double intensity_risk = npd_pymin(1.0, current_intensity / 0.5);
-    double damage_risk = npd_pymin(1.0, fw->cav_accumulated_damage / 10.0);
-    double frequency_risk = npd_pymin(1.0, fw->cav_events_count / 50.0);
-    acc->total_cavitation_risk += (intensity_risk * 0.4 + damage_risk * 0.4 + frequency_risk * 0.2);
-    acc->total_wear_level += (max_bearing + seal_wear);
-    acc->total_vibration += vibration_level;
-  }
-  double dt_seconds = dt * 60.0;
-  {
-    int critical_active = 0;
-    if (npsh_available < 0.1) {
-      fw->npsh_low_low_timer += dt_seconds;
-      if (fw->npsh_low_low_timer >= 5.0) fw->npsh_low_low_trip_active = 1;
-    } else {
-      fw->npsh_low_low_timer = 0.0;
-      fw->npsh_low_low_trip_active = 0;
-    }
-    if (npsh_available < 0.1) critical_active = 1;
-    if (critical_active || fw->npsh_low_low_trip_active) acc->trips++;
-  }
-  if (suction_pressure < 0.1) acc->trips++;
-  if (discharge_pressure > 10.0) acc->trips++;
-  if (vibration_level > 10.0) { fw->timer_vibration += dt_seconds; if (fw->timer_vibration >= 10.0) acc->trips++; }
-  else fw->timer_vibration = 0.0;
-  double bearing_temp = oil_temperature + 5.0;
-  if (bearing_temp > 120.0) { fw->timer_bearing_temp += dt_seconds; if (fw->timer_bearing_temp >= 30.0) acc->trips++; }
-  else fw->timer_bearing_temp = 0.0;
-  if (motor_temperature > 130.0) { fw->timer_motor_temp += dt_seconds; if (fw->timer_motor_temp >= 60.0) acc->trips++; }
-  else fw->timer_motor_temp = 0.0;
-}
-
-/* one pump of FeedwaterPumpSystem.update_system: the demand hand-out gate, then the pump itself */
-__device__ __forceinline__ void npd2_pump(npb_pump_t *p, int gate_open, int n_prev_running, double flow_per_pump,
-                                          const npd_pump_sysconds_t *sc, double dt) {
-  if (p->status == NPD_PUMP_RUNNING && n_prev_running > 0 && gate_open) {
-    if (!(flow_per_pump < NPD_PUMP_RATED_FLOW * 0.2)) npd_pump_set_flow_demand(p, flow_per_pump);
-  }
-  npd_pump_update(p, sc, dt);
-}
-
-/* stage pass A for all 14 stages (pressures, flows; no transcendentals): npd_stage_system_update's first block */
-__device__ __forceinline__ bool npd2_stage_pass_a(double inlet_pressure, double inlet_flow, double load_demand,
-                                                  double *p_self, double *flow_out, double *p_ext, double *ext_flow) {
-#define NPD_EXT_IDX(k) ((k) == 2 ? 0 : (k) == 3 ? 1 : (k) == 4 ? 2 : (k) == 8 ? 3 : 4)
-#define NPD_IS_EXT(k) ((k) == 2 || (k) == 3 || (k) == 4 || (k) == 8 || (k) == 9)
-  bool rare = !(inlet_pressure >= 0.001 && inlet_pressure <= 22.0);
-  double cur_p = inlet_pressure, cur_flow = inlet_flow;
-#pragma unroll
-  for (int k = 0; k < 14; k++) {
-    double d_in, d_out, design_flow; int has_extraction, is_lp;
-    npd_stage_design(k, &d_in, &d_out, &design_flow, &has_extraction, &is_lp);
-    double design_pressure_ratio = d_out / d_in;
-    double extraction_demand = (k == 2) ? 25.0 * load_demand : (k == 3) ? 30.0 * load_demand : (k == 4) ? 20.0 * load_demand
-                             : (k == 8) ? 15.0 * load_demand : (k == 9) ? 10.0 * load_demand : 0.0;
-    double outlet_pressure = npd_stage_requested_outlet(k, cur_p, inlet_flow);
-    rare = rare || (outlet_pressure >= cur_p);
-    double min_allowed, max_allowed;
-    if (k == 13) { min_allowed = 0.002; max_allowed = 0.009; }
-    else { min_allowed = cur_p * (design_pressure_ratio * 0.7); max_allowed = cur_p * (design_pressure_ratio * 1.3); }
-    double self_out = (outlet_pressure < min_allowed) ? min_allowed : ((outlet_pressure > max_allowed) ? max_allowed : outlet_pressure);
-    rare = rare || (self_out != outlet_pressure);
-    double ef = 0.0, pe = cur_p;
-    if (has_extraction && extraction_demand > 0) {
-      ef = npd_clip(extraction_demand, 5.0, npd_pymin(50.0, cur_flow * 0.3));
-      pe = cur_p * 0.7 + outlet_pressure * (1 - 0.7);
-    }
-    if (NPD_IS_EXT(k)) { ext_flow[NPD_EXT_IDX(k)] = ef; p_ext[NPD_EXT_IDX(k)] = pe; }
-    p_self[k] = self_out;
-    flow_out[k] = cur_flow - ef;
-    rare = rare || !(self_out >= 0.001 && self_out <= 22.0) || !(pe >= 0.001 && pe <= 22.0) || !(outlet_pressure >= 0.001);
-    cur_p = self_out; cur_flow = flow_out[k];
-  }
-  return rare;
-}
-
-/* one stage of the temperature / enthalpy chain (npd_stage_system_update, pass C) without its degradation / metal part */
-struct npd2_chain_t { double T_in, sat_in, hg_in, total_power, total_extraction, lp6_outlet_enthalpy, hp_power, lp_power, h_in0; };
-__device__ __forceinline__ void npd2_chain_stage(int k, npd2_chain_t &c, double p_in, double p_self_k, double sat_k, double hg_k, double tratio_k,
-                                                 double flow_out_k, double ef, double hg_ext_k, double total_efficiency,
-                                                 double *T_out_o, double *loading_o) {
-  double cp_in = (p_in > 10.0) ? 2.5 : ((p_in > 1.0) ? 2.2 : 2.0);
-  double T_c = npd_pymax(0.0, npd_pymin(c.T_in, 800.0));
-  double inlet_enthalpy = (T_c <= c.sat_in) ? c.hg_in : c.hg_in + cp_in * (T_c - c.sat_in);
-  double T_isen = (c.T_in + 273.15) * tratio_k - 273.15;
-  double T_isen_c = npd_pymax(0.0, npd_pymin(T_isen, 800.0));
-  double cp_out = (p_self_k > 10.0) ? 2.5 : ((p_self_k > 1.0) ? 2.2 : 2.0);
-  double h_isen = (T_isen_c <= sat_k) ? hg_k : hg_k + cp_out * (T_isen_c - sat_k);
-  double isentropic_enthalpy_drop = inlet_enthalpy - h_isen;
-  if (isentropic_enthalpy_drop <= 0) {
-    double min_enthalpy_drop = 50.0 * (1.0 - p_self_k / p_in);
-    isentropic_enthalpy_drop = npd_pymax(min_enthalpy_drop, 10.0);
-  }
-  double actual_enthalpy_drop = total_efficiency * isentropic_enthalpy_drop;
-  if (actual_enthalpy_drop <= 0) actual_enthalpy_drop = npd_pymax(1.0, isentropic_enthalpy_drop * 0.5);
-  double outlet_enthalpy = inlet_enthalpy - actual_enthalpy_drop;
-  double T_out = (outlet_enthalpy <= hg_k) ? sat_k : sat_k + (outlet_enthalpy - hg_k) / 2.1;
-  double main_power = flow_out_k * actual_enthalpy_drop / 1000.0;
-  if (main_power < 0) main_power = 0.0;
-  double extraction_power = 0.0;
-  if (ef > 0) extraction_power = ef * (inlet_enthalpy - hg_ext_k) / 1000.0;
-  *loading_o = actual_enthalpy_drop / npd_pymax(1.0, 0.88 * isentropic_enthalpy_drop);
-  c.total_power += main_power + extraction_power; c.total_extraction += ef;
-  if (k < 8) c.hp_power += main_power + extraction_power; else c.lp_power += main_power + extraction_power;
-  if (k == 0) c.h_in0 = inlet_enthalpy;
-  if (k == 13) c.lp6_outlet_enthalpy = outlet_enthalpy;
-  *T_out_o = T_out;
-  c.T_in = T_out; c.sat_in = sat_k; c.hg_in = hg_k;
-}
-
-/* the sequential stage chain of npd_stage_system_update_seq for one stage, without the degradation / metal part */
-__device__ __forceinline__ void npd2_seq_stage(int k, double &cur_p, double &cur_T, double &cur_flow, double inlet_flow, double load_demand,
-                                               double total_efficiency, npd2_chain_t &c, double *T_out_o, double *loading_o) {
-  double extraction_demand = (k == 2) ? 25.0 * load_demand : (k == 3) ? 30.0 * load_demand : (k == 4) ? 20.0 * load_demand
-                           : (k == 8) ? 15.0 * load_demand : (k == 9) ? 10.0 * load_demand : 0.0;
-  double outlet_pressure = npd_stage_requested_outlet(k, cur_p, inlet_flow);
-  npd_stage_out_t so;   /* the four efficiency factors enter the expansion only as their product (stage_system.py:209-212) */
-  npd_stage_expansion(k, total_efficiency, 1.0, 1.0, 1.0, cur_p, cur_T, cur_flow, outlet_pressure, extraction_demand, &so);
-  c.total_power += so.power_output; c.total_extraction += so.extraction_flow;
-  if (k < 8) c.hp_power += so.power_output; else c.lp_power += so.power_output;
-  if (k == 13) c.lp6_outlet_enthalpy = so.outlet_enthalpy;
-  *T_out_o = so.outlet_temperature; *loading_o = so.loading_factor;
-  cur_p = so.outlet_pressure; cur_T = so.outlet_temperature; cur_flow = so.outlet_flow;
-}
-
-/* npd_stage_post (npd_turbine.h) with the stage's old values already in registers; new values go straight to the arena */
-#define NPD2_TSTG(member, k) (*NPD_RP(NPD_SEC_COL(TSTG, 0) + NPB_F64_SLOT(npb_tstg_t, member) + (k)))
-struct npd2_tstg_old_t { double eff_deg[14], deposit[14], blade_wear[14], rotor_t[8], casing_t[6], blade_t[14]; };
-/* stage k's old values as scalars (rotor_t / casing_t are read only where the stage has such a point); stress_out: rotor point
- * k's thermal stress (k < 8) */
-/* DEG: this caller also advances the stage's efficiency degradation and deposit thickness (the four-wave kernel's chain wave does
- * that itself, from the copies it has to load anyway: npd_step4.h) */
-template <bool DEG = true>
-__device__ __forceinline__ void npd2_stage_post_vals(const npd_stage_t &st, int k, double eff_deg, double deposit, double blade_wear_old, double rotor_t,
-                                                     double casing_t, double blade_t, double loading_factor, double outlet_temperature, double dt,
-                                                     double *stress_out) {
-  if constexpr (DEG) {
-    NPD2_TSTG(stage_efficiency_degradation, k) = (npd_real_t)(eff_deg + 1e-05 * dt);
-    NPD2_TSTG(stage_deposit_thickness, k) = (npd_real_t)(deposit + 5e-05 * dt);
-  }
-  double blade_wear = (1e-06 * dt) * npd_sq(loading_factor);
-  NPD2_TSTG(stage_blade_wear_factor, k) = (npd_real_t)npd_pymax(0.7, blade_wear_old - blade_wear);
-  const double time_constant = 3600.0 / 3600.0, ambient = 25.0;
-  if (k < 8) {
-    double rt = rotor_t;
-    double tc = ((outlet_temperature - 50.0) - rt) / time_constant * dt;
-    double max_rate = 5.0 * dt;
-    tc = npd_clip(tc, -max_rate, max_rate);
-    rt += tc;
-    NPD2_TSTG(rotor_temperatures, k < 8 ? k : 0) = (npd_real_t)rt;
-    *stress_out = (1.2e-05 * (rt - ambient)) * 200000000000.0 * 0.1;
-  }
-  if (k < 6) {
-    double ct = casing_t;
-    double tc = ((outlet_temperature - 80.0) - ct) / time_constant * dt;
-    tc = npd_clip(tc, -3.0 * dt, 3.0 * dt);
-    NPD2_TSTG(casing_temperatures, k < 6 ? k : 0) = (npd_real_t)(ct + tc);
-  }
-  {
-    double bt = blade_t;
-    double tc = ((outlet_temperature - 20.0) - bt) / (time_constant * 0.5) * dt;
-    tc = npd_clip(tc, -10.0 * dt, 10.0 * dt);
-    NPD2_TSTG(blade_temperatures, k) = (npd_real_t)(bt + tc);
-  }
-}
-__device__ __forceinline__ void npd2_stage_post_one(const npd_stage_t &st, const npd2_tstg_old_t &o, int k, double loading_factor,
-                                                    double outlet_temperature, double dt, double *stress_out) {
-  npd2_stage_post_vals(st, k, o.eff_deg[k], o.deposit[k], o.blade_wear[k], o.rotor_t[k < 8 ? k : 0], o.casing_t[k < 6 ? k : 0], o.blade_t[k],
-                       loading_factor, outlet_temperature, dt, stress_out);
-}
-/* the same, folding MetalTemperatureTracker's max over the rotor points in stage order */
-__device__ __forceinline__ void npd2_stage_post(const npd_stage_t &st, const npd2_tstg_old_t &o, int k, double loading_factor,
-                                                double outlet_temperature, double dt, double *max_thermal_stress) {
-  double stress = 0.0;
-  npd2_stage_post_one(st, o, k, loading_factor, outlet_temperature, dt, &stress);
-  if (k < 8) *max_thermal_stress = (k == 0) ? stress : npd_pymax(*max_thermal_stress, stress);
-}
+/* this kernel's stage array reads (the stage efficiencies, the post-pass's old values) */
+#define NPD2_TSTG(member, k) (*NPD_RP(NPD_TSTG_COL(member, k)))
 
 /* the body of both two-wave kernels (below): same code, compiled once per register budget */
 /* MAINT: with the automatic maintenance compiled in (see npd_step1.h, NPD_STEP1_MAINT) */
@@ -454,7 +254,7 @@ __device__ __forceinline__ void npd_step2_body(
       const npb_pump_t pm_old = pm;
       const uint32_t cooling_mask = i == 0 ? maint_cache01.x : maint_cache01.z;     /* this (plant, pump)'s entry of the cooldown cache */
       const float cooling_until = __uint_as_float(i == 0 ? maint_cache01.y : maint_cache01.w);
-      npd2_pump(&pm, running_count < n_prev_running, n_prev_running, flow_per_pump, &sc, dt);
+      npd_fw_pump_update(&pm, running_count < n_prev_running, n_prev_running, flow_per_pump, &sc, dt);
       running_count += pm.status == NPD_PUMP_RUNNING;
       npd2_publish_pump(xch, lane, i, pm);
       if (maint) {   /* anything new at this pump, for any plant of the group?  (npd_maintenance.h) */
@@ -470,7 +270,7 @@ __device__ __forceinline__ void npd_step2_body(
     acc.total_cavitation_risk = acc.total_wear_level = acc.total_vibration = 0.0;
     acc.running_count = acc.running_mask = acc.trips = 0; acc.trip_mask = 0; acc.trip_kinds = 0;
 #pragma unroll
-    for (int i = 0; i < NPB_NUM_PUMPS; i++) npd2_pump_tail(xch, lane, i, &fw, &acc, dt);
+    for (int i = 0; i < NPB_NUM_PUMPS; i++) npd_fw_pump_tail(npd_pump_vals_read(xch + (X_PUMP + i * X_PUMP_N) * NPB_WAVE, lane), i, &fw, &acc, dt);
     npd_fw_result_t fwr;
     npd_fw_finish(&fw, &acc, prev_levels, dt, &fwr);
     const double fw_total_flow = fwr.total_flow_rate, fw_total_power = fwr.total_power_consumption;
@@ -514,13 +314,9 @@ __device__ __forceinline__ void npd_step2_body(
     const npb_turb_t t_old = t;
     double stage_eff[14];
 #pragma unroll
-    for (int k = 0; k < 14; k++) {
-      double fouling_factor = 1.0 / (1.0 + (double)NPD2_TSTG(stage_deposit_thickness, k) / 0.5);
-      double blade_wear_factor = (double)NPD2_TSTG(stage_blade_wear_factor, k);
-      double blade_condition_factor = npd_pymin(fouling_factor, blade_wear_factor);
-      double actual_efficiency = npd_pymax(0.7, 0.88 - (double)NPD2_TSTG(stage_efficiency_degradation, k));
-      stage_eff[k] = (actual_efficiency * blade_condition_factor * fouling_factor * blade_wear_factor * 1.0);
-    }
+    for (int k = 0; k < 14; k++)
+      stage_eff[k] = npd_stage_total_efficiency((double)NPD2_TSTG(stage_deposit_thickness, k), (double)NPD2_TSTG(stage_blade_wear_factor, k),
+                                                (double)NPD2_TSTG(stage_efficiency_degradation, k));
     NPD2_SYNCJ(5);                                                                                     /* #4 */
 #pragma unroll
     for (int i = 1; i < NPB_NUM_SG; i++) {
@@ -536,7 +332,7 @@ __device__ __forceinline__ void npd_step2_body(
     t.load_demand = load_demand;
     const double pressure_stability_factor = npd_pressure_stability_factor(sg_pressures);
     double p_self[14], flow_out[14], p_ext[5], ext_flow[5];
-    const bool rare = npd2_stage_pass_a(sg_avg_pressure, sg_total_steam, load_demand, p_self, flow_out, p_ext, ext_flow);
+    const bool rare = npd_stage_pass_a(sg_avg_pressure, sg_total_steam, load_demand, p_self, flow_out, p_ext, ext_flow);
     const bool seq = __builtin_amdgcn_ballot_w64(rare) != 0;
 #pragma unroll
     for (int k = 0; k < 14; k++) XW(X_PSELF + k, p_self[k]);
@@ -545,7 +341,7 @@ __device__ __forceinline__ void npd_step2_body(
     XW(X_PIN, seq ? NAN : sg_avg_pressure);         /* NaN tells wave B that the group takes the sequential chain */
     XW(X_CWT, cooling_water_temperature);
     NPD2_SYNCJ(7);                                                                                     /* #5 */
-    npd2_chain_t ch;
+    npd_chain_t ch;
     ch.T_in = sg_avg_temperature; ch.total_power = 0.0; ch.total_extraction = 0.0; ch.lp6_outlet_enthalpy = 0.0;
     ch.hp_power = 0.0; ch.lp_power = 0.0; ch.h_in0 = 0.0;
     double turbine_efficiency = 0.0;   /* stage_system.py:983-993 (info only) */
@@ -570,30 +366,22 @@ __device__ __forceinline__ void npd_step2_body(
         const double ef = NPD_IS_EXT(k) ? ext_flow[NPD_EXT_IDX(k)] : 0.0;
         const double hgx = NPD_IS_EXT(k) ? XR(X_HGEXT + NPD_EXT_IDX(k)) : 0.0;
         double T_out, loading;
-        npd2_chain_stage(k, ch, p_in, p_self[k], sat_k, hg_k, tr_k, flow_out[k], ef, hgx, stage_eff[k], &T_out, &loading);
+        npd_stage_chain(k, ch, p_in, p_self[k], sat_k, hg_k, tr_k, flow_out[k], ef, hgx, stage_eff[k], &T_out, &loading);
         XW(X_TOUT + k, T_out); XW(X_LOADING + k, loading);
         NPD2_FLAG_SET(k + 1);
       }
-      {   /* _steam_enthalpy at the last stage's outlet, whose saturation state pass B has */
-        const double T_c = npd_pymax(0.0, npd_pymin(ch.T_in, 800.0));
-        const double cp = (p_self[13] > 10.0) ? 2.5 : ((p_self[13] > 1.0) ? 2.2 : 2.0);
-        const double h_out = (T_c <= ch.sat_in) ? ch.hg_in : ch.hg_in + cp * (T_c - ch.sat_in);
-        if (sg_total_steam > 0) turbine_efficiency = (ch.h_in0 - h_out) / ch.h_in0;
-      }
+      turbine_efficiency = npd_stage_overall_efficiency(ch, p_self[13], sg_total_steam);
     } else {
       NPD2_SYNCJ(8);                                                                                   /* #6 */
       double cur_p = sg_avg_pressure, cur_T = sg_avg_temperature, cur_flow = sg_total_steam;
 #pragma unroll
       for (int k = 0; k < 14; k++) {
         double T_out, loading;
-        npd2_seq_stage(k, cur_p, cur_T, cur_flow, sg_total_steam, load_demand, stage_eff[k], ch, &T_out, &loading);
+        npd_stage_seq(k, cur_p, cur_T, cur_flow, sg_total_steam, load_demand, stage_eff[k], ch, &T_out, &loading);
         XW(X_TOUT + k, T_out); XW(X_LOADING + k, loading);
         NPD2_FLAG_SET(k + 1);
       }
-      if (sg_total_steam > 0) {
-        const double h_in = npd_stage_steam_enthalpy(sg_avg_temperature, sg_avg_pressure);
-        turbine_efficiency = (h_in - npd_stage_steam_enthalpy(cur_T, cur_p)) / h_in;
-      }
+      turbine_efficiency = npd_stage_overall_efficiency_seq(sg_avg_temperature, sg_avg_pressure, cur_T, cur_p, sg_total_steam);
     }
     const double stage_power_mw = ch.total_power * pressure_stability_factor;
     XW(X_EFFLOW, sg_total_steam - ch.total_extraction); XW(X_LP6H, ch.lp6_outlet_enthalpy);
@@ -725,7 +513,7 @@ __device__ __forceinline__ void npd_step2_body(
       const uint32_t cooling_mask = i == 2 ? maint_cache23.x : maint_cache23.z;
       const float cooling_until = __uint_as_float(i == 2 ? maint_cache23.y : maint_cache23.w);
       /* parallel mode: the gate cannot close (serial_pumps is false for every lane), so its outcome needs no count */
-      npd2_pump(&pm, serial_pumps ? (running_count < n_prev_running) : 1, n_prev_running, flow_per_pump, &sc, dt);
+      npd_fw_pump_update(&pm, serial_pumps ? (running_count < n_prev_running) : 1, n_prev_running, flow_per_pump, &sc, dt);
       running_count += pm.status == NPD_PUMP_RUNNING;
       npd2_publish_pump(xch, lane, i, pm);
       if (maint) {
@@ -780,16 +568,18 @@ __device__ __forceinline__ void npd_step2_body(
     NPD2_SYNCJ(5);                                                                                     /* #4 */
     /* the 70 stage-array columns go to registers while wave A runs stage pass A (they are updated stage by stage
      * behind wave A's chain, below) */
-    npd2_tstg_old_t old;
+    npd_tstg_old_t old;
+#define NPD2_OLD(member, k) (old.v[NPD_TSTG_SLOT(member, k)] = (double)NPD2_TSTG(member, k))
 #pragma unroll
     for (int k = 0; k < 14; k++) {
-      old.eff_deg[k] = (double)NPD2_TSTG(stage_efficiency_degradation, k); old.deposit[k] = (double)NPD2_TSTG(stage_deposit_thickness, k);
-      old.blade_wear[k] = (double)NPD2_TSTG(stage_blade_wear_factor, k); old.blade_t[k] = (double)NPD2_TSTG(blade_temperatures, k);
+      NPD2_OLD(stage_efficiency_degradation, k); NPD2_OLD(stage_deposit_thickness, k);
+      NPD2_OLD(stage_blade_wear_factor, k); NPD2_OLD(blade_temperatures, k);
     }
 #pragma unroll
-    for (int k = 0; k < 8; k++) old.rotor_t[k] = (double)NPD2_TSTG(rotor_temperatures, k);
+    for (int k = 0; k < 8; k++) NPD2_OLD(rotor_temperatures, k);
 #pragma unroll
-    for (int k = 0; k < 6; k++) old.casing_t[k] = (double)NPD2_TSTG(casing_temperatures, k);
+    for (int k = 0; k < 6; k++) NPD2_OLD(casing_temperatures, k);
+#undef NPD2_OLD
     NPD2_SYNCJ(7);                                                                                     /* #5 */
     const double p_in0 = XR(X_PIN);
     const bool seq = __builtin_amdgcn_ballot_w64(isnan(p_in0)) != 0;
@@ -811,7 +601,8 @@ __device__ __forceinline__ void npd_step2_body(
 #pragma unroll
     for (int k = 0; k < 14; k++) {
       NPD2_FLAG_WAIT(k + 1);
-      npd2_stage_post(st, old, k, XR(X_LOADING + k), XR(X_TOUT + k), tdt, &max_stress);
+      const double stress = npd_stage_post<NPD_SM>(st, k, old, XR(X_LOADING + k), XR(X_TOUT + k), tdt).stress;
+      if (k < 8) max_stress = (k == 0) ? stress : npd_pymax(max_stress, stress);
     }
     XW(X_MAXSTRESS, max_stress);
     npb_cond_t cd; npb_chem_t chc;
@@ -867,8 +658,6 @@ __device__ __forceinline__ void npd_step2_body(
       if (bits | maint_due_with_orders) npd_maint_rule_for_wave<WHO>(maint_rc, MC, f64, N, p, bits, maint_due_with_orders);
     }
   }
-#undef NPD_EXT_IDX
-#undef NPD_IS_EXT
 }
 
 #define NPD2_KERNEL_ARGS \

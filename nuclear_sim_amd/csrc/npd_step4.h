@@ -100,37 +100,27 @@ __device__ __forceinline__ void npd4_store_turb_range(const npd_stage_t &st, con
 /* the stage arrays of the stages k = R, R + 3, R + 6 ... (at most five) into registers / their post-pass behind the chain's flag.
  * The arrays are indexed by the stage's position j in the wave's list, so that the three waves that share this code path keep them
  * in the same registers */
-/* NPD4_CHAIN_STORES_DEG = 1 (round 4, measured and NOT kept): the chain's wave, which has to load every stage's efficiency degradation and
- * deposit thickness for the stage efficiencies anyway, also stores their advanced values (old + rate x dt), so that the post-pass waves do not
- * read those 28 columns a second time.  65 536 plants 0.0850 -> 0.0887 ms, 32 768 plants 0.0426 -> 0.0450: 28 stores and 28 adds more on the
- * wave whose chain is the group's critical path cost 4-6 %, and the second reads were hitting the L2 anyway (FETCH_SIZE 255.5 -> 253.1 MB per
- * launch for 14.7 MB fewer bytes requested): profiles/r4_ab_chain_stores_deg_rejected.txt */
-#ifndef NPD4_CHAIN_STORES_DEG
-#define NPD4_CHAIN_STORES_DEG 0
-#endif
 #ifndef NPD4_UNITS_FIRST
 #define NPD4_UNITS_FIRST 1   /* wave 0: its pass B units before the preload of its stage arrays, which only its post-pass needs -- wave 0's steam generator is
                               * the last to finish, so its first unit is what the chain's first stage waits for (round 4: 32 768 plants 0.04277 -> 0.04245 ms,
                               * three alternating runs each, profiles/r4_ab_units_first.txt) */
 #endif
-struct npd4_old_t { double eff_deg[5], deposit[5], blade_wear[5], blade_t[5], rotor_t[5], casing_t[5]; };
 template <int R>
-__device__ __forceinline__ void npd4_stage_preload(const npd_stage_t &st, npd4_old_t &old) {
+__device__ __forceinline__ void npd4_stage_preload(const npd_stage_t &st, npd_tstg_old_t &old) {
+#define NPD4_OLD(member, k) (old.v[NPD_TSTG_SLOT(member, k)] = (double)NPD2_TSTG(member, k))
 #pragma unroll
   for (int j = 0; j < 5; j++) {
     const int k = R + 3 * j;
-    if (k >= 14) { old.eff_deg[j] = old.deposit[j] = old.blade_wear[j] = old.blade_t[j] = 0.0; }
-    else {
-      if (NPD4_CHAIN_STORES_DEG) { old.eff_deg[j] = old.deposit[j] = 0.0; }
-      else { old.eff_deg[j] = (double)NPD2_TSTG(stage_efficiency_degradation, k < 14 ? k : 0); old.deposit[j] = (double)NPD2_TSTG(stage_deposit_thickness, k < 14 ? k : 0); }
-      old.blade_wear[j] = (double)NPD2_TSTG(stage_blade_wear_factor, k < 14 ? k : 0); old.blade_t[j] = (double)NPD2_TSTG(blade_temperatures, k < 14 ? k : 0);
-    }
-    old.rotor_t[j] = (k < 8) ? (double)NPD2_TSTG(rotor_temperatures, k < 8 ? k : 0) : 0.0;
-    old.casing_t[j] = (k < 6) ? (double)NPD2_TSTG(casing_temperatures, k < 6 ? k : 0) : 0.0;
+    if (k >= 14) continue;
+    NPD4_OLD(stage_efficiency_degradation, k); NPD4_OLD(stage_deposit_thickness, k);
+    NPD4_OLD(stage_blade_wear_factor, k); NPD4_OLD(blade_temperatures, k);
+    if (k < 8) NPD4_OLD(rotor_temperatures, k);
+    if (k < 6) NPD4_OLD(casing_temperatures, k);
   }
+#undef NPD4_OLD
 }
 template <int R>
-__device__ __forceinline__ void npd4_stage_post(const npd_stage_t &st, const npd4_old_t &old, double *xch, int lane, double tdt) {
+__device__ __forceinline__ void npd4_stage_post(const npd_stage_t &st, const npd_tstg_old_t &old, double *xch, int lane, double tdt) {
   /* the chain runs ahead of pass A's verdict on the fast path; the arena is only written once the verdict is in (a group that
    * takes the sequential chain gets its stages a second time, counted from 100) */
   NPD4_FLAG_WAIT(FL_VERDICT, 1);
@@ -140,9 +130,7 @@ __device__ __forceinline__ void npd4_stage_post(const npd_stage_t &st, const npd
     const int k = R + 3 * j;
     if (k >= 14) continue;
     NPD4_FLAG_WAIT(FL_CHAIN, base + k + 1);
-    double stress = 0.0;
-    npd2_stage_post_vals<!NPD4_CHAIN_STORES_DEG>(st, k, old.eff_deg[j], old.deposit[j], old.blade_wear[j], old.rotor_t[j], old.casing_t[j], old.blade_t[j],
-                                                 XR(Y_LOADING + (k < 14 ? k : 0)), XR(Y_TOUT + (k < 14 ? k : 0)), tdt, &stress);
+    const double stress = npd_stage_post<NPD_SM>(st, k, old, XR(Y_LOADING + k), XR(Y_TOUT + k), tdt).stress;
     if (k < 8) XW(Y_STRESS + (k < 8 ? k : 0), stress);
   }
   NPD4_FLAG_SET(FL_POST + R, 1);
@@ -152,8 +140,6 @@ __device__ __forceinline__ void npd4_stage_post(const npd_stage_t &st, const npd
  * has one, its extraction pressure) */
 template <int U0, int STEP, int COUNT, int WHOSE>
 __device__ __forceinline__ void npd4_pass_b_units(double *xch, int lane) {
-#define NPD_EXT_IDX(k) ((k) == 2 ? 0 : (k) == 3 ? 1 : (k) == 4 ? 2 : (k) == 8 ? 3 : 4)
-#define NPD_IS_EXT(k) ((k) == 2 || (k) == 3 || (k) == 4 || (k) == 8 || (k) == 9)
 #pragma unroll
   for (int j = 0; j < COUNT; j++) {
     const int u = U0 + STEP * j;
@@ -171,8 +157,6 @@ __device__ __forceinline__ void npd4_pass_b_units(double *xch, int lane) {
     }
     NPD4_FLAG_SET(FL_UNIT + WHOSE, j + 1);
   }
-#undef NPD_EXT_IDX
-#undef NPD_IS_EXT
 }
 
 /* pump i of FeedwaterPumpSystem.update_system, by whichever wave has it: waits for the level control's hand-out (and, with the
@@ -194,21 +178,14 @@ __device__ __forceinline__ void npd4_pass_b_units(double *xch, int lane) {
     const float cooling_until = __uint_as_float((i & 1) ? maint_cache.w : maint_cache.y); \
     const npb_pump_t pm_old = pm; \
     if (!serial_pumps) { \
-      npd2_pump(&pm, 1, n_prev_running, flow_per_pump, &sc, dt);        /* the gate cannot close: its outcome needs no count */ \
+      npd_fw_pump_update(&pm, 1, n_prev_running, flow_per_pump, &sc, dt);        /* the gate cannot close: its outcome needs no count */ \
     } else { \
       int running_count = 0; \
       if (i > 0) { NPD4_FLAG_WAIT(FL_PUMP + (i > 0 ? i - 1 : 0), 1); running_count = (int)XR(Y_RUNCOUNT); } \
-      npd2_pump(&pm, running_count < n_prev_running, n_prev_running, flow_per_pump, &sc, dt); \
+      npd_fw_pump_update(&pm, running_count < n_prev_running, n_prev_running, flow_per_pump, &sc, dt); \
       XW(Y_RUNCOUNT, (double)(running_count + (pm.status == NPD_PUMP_RUNNING))); \
     } \
-    {   /* npd2_publish_pump, into this kernel's region */ \
-      const int b = Y_PUMP + i * X_PUMP_N; \
-      XW(b + 0, (double)((pm.status == NPD_PUMP_RUNNING) | (pm.trip_active ? 2 : 0))); \
-      XW(b + 1, pm.flow_rate); XW(b + 2, pm.power_consumption); XW(b + 3, npd_pump_npsh_required(&pm)); XW(b + 4, pm.npsh_available); \
-      XW(b + 5, pm.speed_percent); XW(b + 6, npd_pymax3(pm.wear_motor_bearings, pm.wear_pump_bearings, pm.wear_thrust_bearing)); \
-      XW(b + 7, pm.wear_mechanical_seals); XW(b + 8, pm.vibration_level); XW(b + 9, pm.suction_pressure); XW(b + 10, pm.discharge_pressure); \
-      XW(b + 11, pm.oil_temperature); XW(b + 12, pm.motor_temperature); \
-    } \
+    npd2_publish_pump(xch + (Y_PUMP - X_PUMP) * NPB_WAVE, lane, i, pm); \
     NPD4_FLAG_SET(FL_PUMP + i, 1); \
     if (maint) {   /* anything new at this pump, for any plant of the group?  (npd_maintenance.h) */ \
       if (__builtin_amdgcn_ballot_w64(npd_maint_pump_hit(&pm, maint_tab, cooling_mask, cooling_until, maint_time)) != 0) maint_hit_bits |= 1u << i; \
@@ -333,7 +310,7 @@ __device__ __forceinline__ void npd_step4_body(
     acc.total_cavitation_risk = acc.total_wear_level = acc.total_vibration = 0.0;
     acc.running_count = acc.running_mask = acc.trips = 0; acc.trip_mask = 0; acc.trip_kinds = 0;
 #pragma unroll
-    for (int i = 0; i < NPB_NUM_PUMPS; i++) npd2_pump_tail(xch + (Y_PUMP - X_PUMP) * NPB_WAVE, lane, i, &fw, &acc, dt);
+    for (int i = 0; i < NPB_NUM_PUMPS; i++) npd_fw_pump_tail(npd_pump_vals_read(xch + (Y_PUMP + i * X_PUMP_N) * NPB_WAVE, lane), i, &fw, &acc, dt);
     npd_fw_result_t fwr;
     npd_fw_finish(&fw, &acc, prev_levels, dt, &fwr);
     fw_total_flow = fwr.total_flow_rate; fw_total_power = fwr.total_power_consumption;
@@ -348,7 +325,7 @@ __device__ __forceinline__ void npd_step4_body(
     NPD_ST_LOAD(TURB, npb_turb_t, t, 0);          /* wave 1 owns the lub_* members; they are neither used nor stored here */
     NPD4_ST_STORE(FW, npb_fw_t, fw, fw_old, 0);
     t_old = t;
-    npd4_old_t old;
+    npd_tstg_old_t old;
     npd4_stage_preload<2>(st, old);               /* this wave's share of the stage post-pass: stages 2, 5, 8, 11 */
     NPD4_STAMP(5);
     NPD4_FLAG_WAIT(FL_SG + 0, 1); NPD4_FLAG_WAIT(FL_SG + 1, 1); NPD4_FLAG_WAIT(FL_SG + 2, 1);
@@ -377,10 +354,9 @@ __device__ __forceinline__ void npd_step4_body(
     XW(Y_CWT, cooling_water_temperature);
     XW(Y_PIN, sg_avg_pressure); XW(Y_TIN, sg_avg_temperature); XW(Y_STEAM, sg_total_steam);
     NPD4_FLAG_SET(FL_PASSA, 1);
-    {   /* stage pass A (npd2_stage_pass_a, npd_step2.h: pressures and flows, no transcendentals), each stage's outlet pressure
-         * published as it is known so that the other waves' pass B runs behind this loop instead of behind its end */
-#define NPD_EXT_IDX(k) ((k) == 2 ? 0 : (k) == 3 ? 1 : (k) == 4 ? 2 : (k) == 8 ? 3 : 4)
-#define NPD_IS_EXT(k) ((k) == 2 || (k) == 3 || (k) == 4 || (k) == 8 || (k) == 9)
+    {   /* stage pass A (npd_stage_pass_a, npd_turbine.h: pressures and flows, no transcendentals), each stage's outlet pressure
+         * published as it is known so that the other waves' pass B runs behind this loop instead of behind its end.  Written out:
+         * as a per-stage function it moves this kernel's register allocation */
       const double inlet_pressure = sg_avg_pressure, inlet_flow = sg_total_steam;
       bool rare = !(inlet_pressure >= 0.001 && inlet_pressure <= 22.0);
       double cur_p = inlet_pressure, cur_flow = inlet_flow;
@@ -412,8 +388,6 @@ __device__ __forceinline__ void npd_step4_body(
       }
       seq = __builtin_amdgcn_ballot_w64(rare) != 0;   /* any lane off the fast path: the group takes the sequential chain (pass B and wave 1's chain so far are then not used) */
       NPD4_FLAG_SET(FL_VERDICT, seq ? 2 : 1);
-#undef NPD_EXT_IDX
-#undef NPD_IS_EXT
     }
     __builtin_amdgcn_s_setprio(0);
     NPD4_STAMP(7);
@@ -567,7 +541,7 @@ __device__ __forceinline__ void npd_step4_body(
       NPD4_FLAG_SET(FL_SG + i, 1);
     }
     NPD4_STAMP(6);
-    npd4_old_t old;
+    npd_tstg_old_t old;
     npb_cond_t cd, cd_old; npb_chem_t chc, chc_old;   /* wave 2: the condenser's sections, loaded ahead of its stage post-pass */
     if (wave == 1) {
       /* ---- the stage chain (npd_stage_system_update's pass C, npd_turbine.h), behind the other waves' pass B units, i.e. while
@@ -577,26 +551,16 @@ __device__ __forceinline__ void npd_step4_body(
 #pragma unroll
       for (int k = 0; k < 14; k++) {
         const double deposit = (double)NPD2_TSTG(stage_deposit_thickness, k), eff_deg = (double)NPD2_TSTG(stage_efficiency_degradation, k);
-        double fouling_factor = 1.0 / (1.0 + deposit / 0.5);
-        double blade_wear_factor = (double)NPD2_TSTG(stage_blade_wear_factor, k);
-        double blade_condition_factor = npd_pymin(fouling_factor, blade_wear_factor);
-        double actual_efficiency = npd_pymax(0.7, 0.88 - eff_deg);
-        stage_eff[k] = (actual_efficiency * blade_condition_factor * fouling_factor * blade_wear_factor * 1.0);
-        if (NPD4_CHAIN_STORES_DEG) {   /* the stage post-pass's two rate updates (npd2_stage_post_vals), here where the old values are in registers */
-          NPD2_TSTG(stage_efficiency_degradation, k) = (npd_real_t)(eff_deg + 1e-05 * tdt);
-          NPD2_TSTG(stage_deposit_thickness, k) = (npd_real_t)(deposit + 5e-05 * tdt);
-        }
+        stage_eff[k] = npd_stage_total_efficiency(deposit, (double)NPD2_TSTG(stage_blade_wear_factor, k), eff_deg);
       }
       NPD4_STAMP(7);
       __builtin_amdgcn_s_setprio(3);               /* the chain is the group's critical path from here to its last stage */
       NPD4_FLAG_WAIT(FL_PASSA, 1);
       const double sg_avg_pressure = XR(Y_PIN), sg_avg_temperature = XR(Y_TIN), sg_total_steam = XR(Y_STEAM), load_demand = XR(Y_PRIM + 1);
-      npd2_chain_t ch;
+      npd_chain_t ch;
       ch.T_in = sg_avg_temperature; ch.total_power = 0.0; ch.total_extraction = 0.0; ch.lp6_outlet_enthalpy = 0.0;
       ch.hp_power = 0.0; ch.lp_power = 0.0; ch.h_in0 = 0.0;
       double turbine_efficiency = 0.0;   /* stage_system.py:983-993 (info only) */
-#define NPD_EXT_IDX(k) ((k) == 2 ? 0 : (k) == 3 ? 1 : (k) == 4 ? 2 : (k) == 8 ? 3 : 4)
-#define NPD_IS_EXT(k) ((k) == 2 || (k) == 3 || (k) == 4 || (k) == 8 || (k) == 9)
       {   /* the fast path, ahead of pass A's verdict (a group that turns out to need the sequential chain runs it below) */
         NPD4_UNIT_WAIT(0);                           /* the inlet's saturation state */
         ch.sat_in = XR(Y_SAT + 0); ch.hg_in = XR(Y_HG + 0);
@@ -608,20 +572,14 @@ __device__ __forceinline__ void npd_step4_body(
           const double sat_k = XR(Y_SAT + k + 1), hg_k = XR(Y_HG + k + 1), tr_k = XR(Y_TRATIO + k);
           const double ef = NPD_IS_EXT(k) ? XR(Y_EXTF + NPD_EXT_IDX(k)) : 0.0;
           const double hgx = NPD_IS_EXT(k) ? XR(Y_HGEXT + NPD_EXT_IDX(k)) : 0.0;
-          const double flow_out_k = cur_flow - ef;   /* pass A's own recurrence (npd2_stage_pass_a) */
+          const double flow_out_k = cur_flow - ef;   /* pass A's own recurrence (npd_stage_pass_a) */
           cur_flow = flow_out_k;
           double T_out, loading;
-          npd2_chain_stage(k, ch, p_in, p_self_k, sat_k, hg_k, tr_k, flow_out_k, ef, hgx, stage_eff[k], &T_out, &loading);
+          npd_stage_chain(k, ch, p_in, p_self_k, sat_k, hg_k, tr_k, flow_out_k, ef, hgx, stage_eff[k], &T_out, &loading);
           XW(Y_TOUT + k, T_out); XW(Y_LOADING + k, loading);
           NPD4_FLAG_SET(FL_CHAIN, k + 1);
         }
-        {   /* _steam_enthalpy at the last stage's outlet, whose saturation state pass B has */
-          const double p13 = XR(Y_PSELF + 13);
-          const double T_c = npd_pymax(0.0, npd_pymin(ch.T_in, 800.0));
-          const double cp = (p13 > 10.0) ? 2.5 : ((p13 > 1.0) ? 2.2 : 2.0);
-          const double h_out = (T_c <= ch.sat_in) ? ch.hg_in : ch.hg_in + cp * (T_c - ch.sat_in);
-          if (sg_total_steam > 0) turbine_efficiency = (ch.h_in0 - h_out) / ch.h_in0;
-        }
+        turbine_efficiency = npd_stage_overall_efficiency(ch, XR(Y_PSELF + 13), sg_total_steam);
       }
       NPD4_FLAG_WAIT(FL_VERDICT, 1);
       if (__builtin_amdgcn_readfirstlane(*NPD4_FLAGP(FL_VERDICT)) == 2) {   /* some lane left the fast path's assumptions: the reference's own order, stage by stage */
@@ -632,17 +590,12 @@ __device__ __forceinline__ void npd_step4_body(
 #pragma unroll
         for (int k = 0; k < 14; k++) {
           double T_out, loading;
-          npd2_seq_stage(k, cur_p, cur_T, cur_flow, sg_total_steam, load_demand, stage_eff[k], ch, &T_out, &loading);
+          npd_stage_seq(k, cur_p, cur_T, cur_flow, sg_total_steam, load_demand, stage_eff[k], ch, &T_out, &loading);
           XW(Y_TOUT + k, T_out); XW(Y_LOADING + k, loading);
           NPD4_FLAG_SET(FL_CHAIN, 100 + k + 1);
         }
-        if (sg_total_steam > 0) {
-          const double h_in = npd_stage_steam_enthalpy(sg_avg_temperature, sg_avg_pressure);
-          turbine_efficiency = (h_in - npd_stage_steam_enthalpy(cur_T, cur_p)) / h_in;
-        }
+        turbine_efficiency = npd_stage_overall_efficiency_seq(sg_avg_temperature, sg_avg_pressure, cur_T, cur_p, sg_total_steam);
       }
-#undef NPD_EXT_IDX
-#undef NPD_IS_EXT
       XW(Y_CHRES + 0, ch.total_power); XW(Y_CHRES + 1, ch.total_extraction); XW(Y_CHRES + 2, ch.lp6_outlet_enthalpy);
       XW(Y_CHRES + 3, ch.hp_power); XW(Y_CHRES + 4, ch.lp_power); XW(Y_CHRES + 5, turbine_efficiency);
       XW(Y_CHRES + 6, sg_total_steam - ch.total_extraction);     /* the effective steam flow the condenser sees */

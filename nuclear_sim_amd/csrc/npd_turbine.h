@@ -170,24 +170,91 @@ typedef struct npd_stagesys_out_t {
   double prev_rotor, prev_casing, max_gradient;   /* diagnostics build only: the tracker's largest rotor / casing gradient, enhanced_physics.py:128-135 */
 } npd_stagesys_out_t;
 
-/* per-stage column access: the stage / tracker arrays are read from the LDS staging region (the whole
- * tstg section is LDS-DMA'd there while the lubrication step and passes A/B run, npd_stage.h) and each
- * updated value is written straight to its SoA column; every column is read before it is written and
- * never re-read within a step, so the staged copy does not need the update */
-#define NPD_TSTG_RD(member, k) NPD_LDS_REAL(0, NPB_F64_SLOT(npb_tstg_t, member) + (k))
-#define NPD_TSTG_WR(member, k, v) npd_store_real<SM>(st, NPD_SEC_COL(TSTG, 0) + NPB_F64_SLOT(npb_tstg_t, member) + (k), (v))
+/* slot of stage k's entry of a stage / tracker array in the tstg section, and its arena column */
+#define NPD_TSTG_SLOT(member, k) (NPB_F64_SLOT(npb_tstg_t, member) + (k))
+#define NPD_TSTG_COL(member, k) (NPD_SEC_COL(TSTG, 0) + NPD_TSTG_SLOT(member, k))
+/* the one-wave kernel reads the stage / tracker arrays from the LDS staging region (the whole tstg section is LDS-DMA'd there
+ * while the lubrication step and passes A/B run, npd_stage.h) and writes each updated value straight to its SoA column; every
+ * column is read before it is written and never re-read within a step, so the staged copy does not need the update */
+#define NPD_TSTG_RD(member, k) NPD_LDS_REAL(0, NPD_TSTG_SLOT(member, k))
 
+/* the extraction stages 2, 3, 4, 8, 9 and their compact index 0 .. 4 */
+#define NPD_EXT_IDX(k) ((k) == 2 ? 0 : (k) == 3 ? 1 : (k) == 4 ? 2 : (k) == 8 ? 3 : 4)
+#define NPD_IS_EXT(k) ((k) == 2 || (k) == 3 || (k) == 4 || (k) == 8 || (k) == 9)
+
+/* extraction demand of stage k  enhanced_physics.py:729-735 */
+NPD_FN double npd_stage_extraction_demand(int k, double load_demand) {
+  return (k == 2) ? 25.0 * load_demand : (k == 3) ? 30.0 * load_demand : (k == 4) ? 20.0 * load_demand
+       : (k == 8) ? 15.0 * load_demand : (k == 9) ? 10.0 * load_demand : 0.0;
+}
+
+/* a stage's efficiency product from its state as the previous step left it  stage_system.py:128-133, 206-212 */
+NPD_FN double npd_stage_total_efficiency(double deposit, double blade_wear_factor, double eff_deg) {
+  double fouling_factor = 1.0 / (1.0 + deposit / 0.5);
+  double blade_condition_factor = npd_pymin(fouling_factor, blade_wear_factor);
+  double actual_efficiency = npd_pymax(0.7, 0.88 - eff_deg);
+  return (actual_efficiency * blade_condition_factor * fouling_factor * blade_wear_factor * 1.0);
+}
+
+/* the multi-wave kernels' register copy of the stage arrays as the previous step left it, by tstg slot (each kernel loads the
+ * stages it post-processes) */
+struct npd_tstg_old_t {
+  double v[NPB_TSTG_NF64];
+  NPD_FN double operator()(int slot) const { return v[slot]; }
+};
+/* what a stage's post-pass leaves behind: rotor point k's thermal stress and temperature rate (k < 8), and the new rotor /
+ * casing temperatures (the one-wave diagnostics' gradients) */
+struct npd_stage_post_t { double stress, rate, rotor_t, casing_t; };
 /* one stage's share of TurbineStage.update_degradation (stage_system.py:294-339) and of
- * MetalTemperatureTracker.update_temperatures (enhanced_physics.py:73-166, time constant 1 h, ambient 25 C);
- * both only touch stage k's own state, so running them right after stage k's expansion is the
- * reference's result */
-template <int SM = 0>
-NPD_FN void npd_stage_post(const npd_stage_t &st, const double *stg, int k, double loading_factor,
-                           double outlet_temperature, double dt, npd_stagesys_out_t *out) {
-  NPD_TSTG_WR(stage_efficiency_degradation, k, NPD_TSTG_RD(stage_efficiency_degradation, k) + 1e-05 * dt);
-  NPD_TSTG_WR(stage_deposit_thickness, k, NPD_TSTG_RD(stage_deposit_thickness, k) + 5e-05 * dt);
+ * MetalTemperatureTracker.update_temperatures (enhanced_physics.py:73-166, time constant 1 h, ambient 25 C); both only touch
+ * stage k's own state, so running them right after stage k's expansion is the reference's result.  old(slot) is the stage
+ * arrays' old value at a tstg slot, read where the update needs it (the one-wave kernel's reads of its staged copy stay behind
+ * the stores before them); rotor / casing temperatures are read only where the stage has such a point */
+template <int SM, typename OLD>
+NPD_FN npd_stage_post_t npd_stage_post(const npd_stage_t &st, int k, const OLD &old, double loading_factor, double outlet_temperature, double dt) {
+  npd_stage_post_t r = {0.0, 0.0, 0.0, 0.0};
+  npd_store_real<SM>(st, NPD_TSTG_COL(stage_efficiency_degradation, k), old(NPD_TSTG_SLOT(stage_efficiency_degradation, k)) + 1e-05 * dt);
+  npd_store_real<SM>(st, NPD_TSTG_COL(stage_deposit_thickness, k), old(NPD_TSTG_SLOT(stage_deposit_thickness, k)) + 5e-05 * dt);
   double blade_wear = (1e-06 * dt) * npd_sq(loading_factor);
-  NPD_TSTG_WR(stage_blade_wear_factor, k, npd_pymax(0.7, NPD_TSTG_RD(stage_blade_wear_factor, k) - blade_wear));
+  npd_store_real<SM>(st, NPD_TSTG_COL(stage_blade_wear_factor, k), npd_pymax(0.7, old(NPD_TSTG_SLOT(stage_blade_wear_factor, k)) - blade_wear));
+  const double time_constant = 3600.0 / 3600.0, ambient = 25.0;
+  if (k < 8) {
+    double rt = old(NPD_TSTG_SLOT(rotor_temperatures, k));
+    double tc = ((outlet_temperature - 50.0) - rt) / time_constant * dt;
+    double max_rate = 5.0 * dt;
+    tc = npd_clip(tc, -max_rate, max_rate);
+    rt += tc;
+    npd_store_real<SM>(st, NPD_TSTG_COL(rotor_temperatures, k), rt);
+    r.rotor_t = rt;
+    r.rate = fabs(tc / dt * 60.0);
+    r.stress = (1.2e-05 * (rt - ambient)) * 200000000000.0 * 0.1;
+  }
+  if (k < 6) {
+    double ct = old(NPD_TSTG_SLOT(casing_temperatures, k));
+    double tc = ((outlet_temperature - 80.0) - ct) / time_constant * dt;
+    tc = npd_clip(tc, -3.0 * dt, 3.0 * dt);
+    npd_store_real<SM>(st, NPD_TSTG_COL(casing_temperatures, k), ct + tc);
+    r.casing_t = ct + tc;
+  }
+  {
+    double bt = old(NPD_TSTG_SLOT(blade_temperatures, k));
+    double tc = ((outlet_temperature - 20.0) - bt) / (time_constant * 0.5) * dt;
+    tc = npd_clip(tc, -10.0 * dt, 10.0 * dt);
+    npd_store_real<SM>(st, NPD_TSTG_COL(blade_temperatures, k), bt + tc);
+  }
+  return r;
+}
+
+/* the one-wave kernel's stage post-pass, from its staged copy, with MetalTemperatureTracker's reductions in stage order (the
+ * largest temperature rate and, diagnostics build only, the largest rotor / casing gradient are read by this kernel alone).
+ * Written out: as a call of npd_stage_post it moves the register allocation of the one-wave diagnostics kernels */
+template <int SM>
+NPD_FN void npd_stage_post_staged(const npd_stage_t &st, int k, double loading_factor, double outlet_temperature, double dt,
+                                  npd_stagesys_out_t *out) {
+  npd_store_real<SM>(st, NPD_TSTG_COL(stage_efficiency_degradation, k), NPD_TSTG_RD(stage_efficiency_degradation, k) + 1e-05 * dt);
+  npd_store_real<SM>(st, NPD_TSTG_COL(stage_deposit_thickness, k), NPD_TSTG_RD(stage_deposit_thickness, k) + 5e-05 * dt);
+  double blade_wear = (1e-06 * dt) * npd_sq(loading_factor);
+  npd_store_real<SM>(st, NPD_TSTG_COL(stage_blade_wear_factor, k), npd_pymax(0.7, NPD_TSTG_RD(stage_blade_wear_factor, k) - blade_wear));
   const double time_constant = 3600.0 / 3600.0, ambient = 25.0;
   if (k < 8) {
     double rt = NPD_TSTG_RD(rotor_temperatures, k);
@@ -195,7 +262,7 @@ NPD_FN void npd_stage_post(const npd_stage_t &st, const double *stg, int k, doub
     double max_rate = 5.0 * dt;
     tc = npd_clip(tc, -max_rate, max_rate);
     rt += tc;
-    NPD_TSTG_WR(rotor_temperatures, k, rt);
+    npd_store_real<SM>(st, NPD_TSTG_COL(rotor_temperatures, k), rt);
     double rate = fabs(tc / dt * 60.0);
     out->max_temp_rate = (k == 0) ? rate : npd_pymax(out->max_temp_rate, rate);
     double stress = (1.2e-05 * (rt - ambient)) * 200000000000.0 * 0.1;
@@ -209,7 +276,7 @@ NPD_FN void npd_stage_post(const npd_stage_t &st, const double *stg, int k, doub
     double ct = NPD_TSTG_RD(casing_temperatures, k);
     double tc = ((outlet_temperature - 80.0) - ct) / time_constant * dt;
     tc = npd_clip(tc, -3.0 * dt, 3.0 * dt);
-    NPD_TSTG_WR(casing_temperatures, k, ct + tc);
+    npd_store_real<SM>(st, NPD_TSTG_COL(casing_temperatures, k), ct + tc);
     if (st.diag) {   /* casing points 1.5 m apart; max(max(rotor), max(casing)) taken at the end (stage 5 comes after every rotor pair but the last two) */
       if (k > 0) out->max_gradient = npd_pymax(out->max_gradient, fabs((ct + tc) - out->prev_casing) / (1.5 * 100));
       out->prev_casing = ct + tc;
@@ -219,7 +286,7 @@ NPD_FN void npd_stage_post(const npd_stage_t &st, const double *stg, int k, doub
     double bt = NPD_TSTG_RD(blade_temperatures, k);
     double tc = ((outlet_temperature - 20.0) - bt) / (time_constant * 0.5) * dt;
     tc = npd_clip(tc, -10.0 * dt, 10.0 * dt);
-    NPD_TSTG_WR(blade_temperatures, k, bt + tc);
+    npd_store_real<SM>(st, NPD_TSTG_COL(blade_temperatures, k), bt + tc);
   }
 }
 
@@ -239,10 +306,42 @@ NPD_FN double npd_stage_requested_outlet(int k, double current_pressure, double 
   return outlet_pressure;
 }
 
+/* the turbine's running sums over the stage chain, and the chain's state at the current stage's inlet */
+struct npd_chain_t { double T_in, sat_in, hg_in, total_power, total_extraction, lp6_outlet_enthalpy, hp_power, lp_power, h_in0; };
+
+/* one stage of the sequential chain (npd_stage_system_update_seq) without its degradation / metal part: cur_p / cur_T / cur_flow
+ * advance to the stage's outlet.  power_o / extraction_o: the stage's power and extraction flow, for the one-wave diagnostics */
+NPD_FN void npd_stage_seq(int k, double &cur_p, double &cur_T, double &cur_flow, double inlet_flow, double load_demand,
+                          double total_efficiency, npd_chain_t &c, double *T_out_o, double *loading_o,
+                          double *power_o = nullptr, double *extraction_o = nullptr) {
+  double extraction_demand = npd_stage_extraction_demand(k, load_demand);
+  double outlet_pressure = npd_stage_requested_outlet(k, cur_p, inlet_flow);
+  npd_stage_out_t so;   /* the four efficiency factors enter the expansion only as their product (stage_system.py:209-212) */
+  npd_stage_expansion(k, total_efficiency, 1.0, 1.0, 1.0, cur_p, cur_T, cur_flow, outlet_pressure, extraction_demand, &so);
+  c.total_power += so.power_output; c.total_extraction += so.extraction_flow;
+  if (k < 8) c.hp_power += so.power_output; else c.lp_power += so.power_output;
+  if (k == 13) c.lp6_outlet_enthalpy = so.outlet_enthalpy;
+  *T_out_o = so.outlet_temperature; *loading_o = so.loading_factor;
+  if (power_o) *power_o = so.power_output;
+  if (extraction_o) *extraction_o = so.extraction_flow;
+  cur_p = so.outlet_pressure; cur_T = so.outlet_temperature; cur_flow = so.outlet_flow;
+}
+
+/* overall efficiency after the sequential chain: _steam_enthalpy at the turbine inlet and the last stage's outlet  stage_system.py:983-993 */
+NPD_FN double npd_stage_overall_efficiency_seq(double inlet_temperature, double inlet_pressure, double out_T, double out_p, double inlet_flow) {
+  double eff = 0.0;
+  if (inlet_flow > 0) {
+    const double h_in = npd_stage_steam_enthalpy(inlet_temperature, inlet_pressure);
+    eff = (h_in - npd_stage_steam_enthalpy(out_T, out_p)) / h_in;
+  }
+  return eff;
+}
+
 /* TurbineStageSystem.update_state  stage_system.py:928-1016, reference order, one stage at a time.
+ * Written out (not npd_stage_seq): as calls the stage moves the one-wave kernels' register allocation.
  * Exact for every input; used when a lane of the wave leaves the fast path's assumptions. */
 template <int SM = 0>
-NPD_FN void npd_stage_system_update_seq(const npd_stage_t &st, const double *stg, double inlet_pressure,
+NPD_FN void npd_stage_system_update_seq(const npd_stage_t &st, double inlet_pressure,
                                         double inlet_temperature, double inlet_flow, double load_demand,
                                         double pressure_stability_factor, double dt, npd_stagesys_out_t *out) {
   double current_pressure = inlet_pressure, current_temperature = inlet_temperature, current_flow = inlet_flow;
@@ -267,7 +366,7 @@ NPD_FN void npd_stage_system_update_seq(const npd_stage_t &st, const double *stg
     NPD_DIAG(st, NPB_DIAG_STAGE_OUTLET_PRESSURE + k, so.outlet_pressure); NPD_DIAG(st, NPB_DIAG_STAGE_OUTLET_TEMPERATURE + k, so.outlet_temperature);
     NPD_DIAG(st, NPB_DIAG_STAGE_POWER_OUTPUT + k, so.power_output); NPD_DIAG(st, NPB_DIAG_STAGE_LOADING_FACTOR + k, so.loading_factor);
     NPD_DIAG(st, NPB_DIAG_STAGE_EXTRACTION_FLOW + k, so.extraction_flow);
-    npd_stage_post<SM>(st, stg, k, so.loading_factor, so.outlet_temperature, dt, out);
+    npd_stage_post_staged<SM>(st, k, so.loading_factor, so.outlet_temperature, dt, out);
     current_pressure = so.outlet_pressure; current_temperature = so.outlet_temperature; current_flow = so.outlet_flow;
   }
   out->total_power = total_power * pressure_stability_factor;
@@ -280,6 +379,85 @@ NPD_FN void npd_stage_system_update_seq(const npd_stage_t &st, const double *stg
   }
 }
 
+/* pass A for all 14 stages (pressures, flows; no transcendentals); returns whether a lane leaves the fast path */
+NPD_FN bool npd_stage_pass_a(double inlet_pressure, double inlet_flow, double load_demand,
+                             double *p_self, double *flow_out, double *p_ext, double *ext_flow) {
+  bool rare = !(inlet_pressure >= 0.001 && inlet_pressure <= 22.0);
+  double cur_p = inlet_pressure, cur_flow = inlet_flow;
+#pragma unroll
+  for (int k = 0; k < 14; k++) {
+    double d_in, d_out, design_flow; int has_extraction, is_lp;
+    npd_stage_design(k, &d_in, &d_out, &design_flow, &has_extraction, &is_lp);
+    double design_pressure_ratio = d_out / d_in;
+    double extraction_demand = (k == 2) ? 25.0 * load_demand : (k == 3) ? 30.0 * load_demand : (k == 4) ? 20.0 * load_demand
+                             : (k == 8) ? 15.0 * load_demand : (k == 9) ? 10.0 * load_demand : 0.0;
+    double outlet_pressure = npd_stage_requested_outlet(k, cur_p, inlet_flow);
+    rare = rare || (outlet_pressure >= cur_p);
+    double min_allowed, max_allowed;
+    if (k == 13) { min_allowed = 0.002; max_allowed = 0.009; }
+    else { min_allowed = cur_p * (design_pressure_ratio * 0.7); max_allowed = cur_p * (design_pressure_ratio * 1.3); }
+    double self_out = (outlet_pressure < min_allowed) ? min_allowed : ((outlet_pressure > max_allowed) ? max_allowed : outlet_pressure);
+    rare = rare || (self_out != outlet_pressure);
+    double ef = 0.0, pe = cur_p;
+    if (has_extraction && extraction_demand > 0) {
+      ef = npd_clip(extraction_demand, 5.0, npd_pymin(50.0, cur_flow * 0.3));
+      pe = cur_p * 0.7 + outlet_pressure * (1 - 0.7);
+    }
+    if (NPD_IS_EXT(k)) { ext_flow[NPD_EXT_IDX(k)] = ef; p_ext[NPD_EXT_IDX(k)] = pe; }
+    p_self[k] = self_out;
+    flow_out[k] = cur_flow - ef;
+    rare = rare || !(self_out >= 0.001 && self_out <= 22.0) || !(pe >= 0.001 && pe <= 22.0) || !(outlet_pressure >= 0.001);
+    cur_p = self_out; cur_flow = flow_out[k];
+  }
+  return rare;
+}
+
+/* one stage of the temperature / enthalpy chain (pass C, below) without its degradation / metal part, from the stage's pass B
+ * values (p_in: its inlet pressure; ef / hg_ext_k: its extraction flow and the extraction's vapour enthalpy, 0 where it has none).
+ * power_o: the stage's power, for the one-wave diagnostics */
+NPD_FN void npd_stage_chain(int k, npd_chain_t &c, double p_in, double p_self_k, double sat_k, double hg_k, double tratio_k,
+                            double flow_out_k, double ef, double hg_ext_k, double total_efficiency,
+                            double *T_out_o, double *loading_o, double *power_o = nullptr) {
+  double cp_in = (p_in > 10.0) ? 2.5 : ((p_in > 1.0) ? 2.2 : 2.0);
+  double T_c = npd_pymax(0.0, npd_pymin(c.T_in, 800.0));
+  double inlet_enthalpy = (T_c <= c.sat_in) ? c.hg_in : c.hg_in + cp_in * (T_c - c.sat_in);
+  double T_isen = (c.T_in + 273.15) * tratio_k - 273.15;
+  double T_isen_c = npd_pymax(0.0, npd_pymin(T_isen, 800.0));
+  double cp_out = (p_self_k > 10.0) ? 2.5 : ((p_self_k > 1.0) ? 2.2 : 2.0);
+  double h_isen = (T_isen_c <= sat_k) ? hg_k : hg_k + cp_out * (T_isen_c - sat_k);
+  double isentropic_enthalpy_drop = inlet_enthalpy - h_isen;
+  if (isentropic_enthalpy_drop <= 0) {
+    double min_enthalpy_drop = 50.0 * (1.0 - p_self_k / p_in);
+    isentropic_enthalpy_drop = npd_pymax(min_enthalpy_drop, 10.0);
+  }
+  double actual_enthalpy_drop = total_efficiency * isentropic_enthalpy_drop;
+  if (actual_enthalpy_drop <= 0) actual_enthalpy_drop = npd_pymax(1.0, isentropic_enthalpy_drop * 0.5);
+  double outlet_enthalpy = inlet_enthalpy - actual_enthalpy_drop;
+  /* requested outlet pressure == the stage's own outlet pressure on this path */
+  double T_out = (outlet_enthalpy <= hg_k) ? sat_k : sat_k + (outlet_enthalpy - hg_k) / 2.1;
+  double main_power = flow_out_k * actual_enthalpy_drop / 1000.0;
+  if (main_power < 0) main_power = 0.0;
+  double extraction_power = 0.0;
+  if (ef > 0) extraction_power = ef * (inlet_enthalpy - hg_ext_k) / 1000.0;
+  *loading_o = actual_enthalpy_drop / npd_pymax(1.0, 0.88 * isentropic_enthalpy_drop);
+  c.total_power += main_power + extraction_power; c.total_extraction += ef;
+  if (k < 8) c.hp_power += main_power + extraction_power; else c.lp_power += main_power + extraction_power;
+  if (k == 0) c.h_in0 = inlet_enthalpy;   /* = _steam_enthalpy(inlet_temperature, inlet_pressure) of stage_system.py:985 */
+  if (k == 13) c.lp6_outlet_enthalpy = outlet_enthalpy;
+  *T_out_o = T_out;
+  if (power_o) *power_o = main_power + extraction_power;
+  c.T_in = T_out; c.sat_in = sat_k; c.hg_in = hg_k;
+}
+
+/* overall efficiency after the chain  stage_system.py:983-993: _steam_enthalpy at the last stage's outlet (pressure p_out), whose
+ * saturation state pass B already has */
+NPD_FN double npd_stage_overall_efficiency(const npd_chain_t &c, double p_out, double inlet_flow) {
+  const double T_c = npd_pymax(0.0, npd_pymin(c.T_in, 800.0));
+  const double cp = (p_out > 10.0) ? 2.5 : ((p_out > 1.0) ? 2.2 : 2.0);
+  const double h_out = (T_c <= c.sat_in) ? c.hg_in : c.hg_in + cp * (T_c - c.sat_in);
+  return (inlet_flow > 0) ? (c.h_in0 - h_out) / c.h_in0 : 0.0;
+}
+
 /* Same result, restructured for instruction-level parallelism (one wave per SIMD has nothing else to
  * hide latency with): the pressure / flow chain does not depend on the temperature chain unless a stage
  * takes the "invalid pressure ratio" branch (stage_system.py:146-155), so
@@ -290,13 +468,11 @@ NPD_FN void npd_stage_system_update_seq(const npd_stage_t &st, const double *stg
  *           degradation and metal-temperature state.
  * Lanes that would take a rare branch make the whole wave use npd_stage_system_update_seq. */
 template <int SM = 0>
-NPD_FN void npd_stage_system_update(const npd_stage_t &st, const double *stg, double inlet_pressure,
+NPD_FN void npd_stage_system_update(const npd_stage_t &st, double inlet_pressure,
                                     double inlet_temperature, double inlet_flow, double load_demand,
                                     double pressure_stability_factor, double dt, npd_stagesys_out_t *out) {
-  /* extraction stages 2, 3, 4, 8, 9 -> compact index 0..4 */
-#define NPD_EXT_IDX(k) ((k) == 2 ? 0 : (k) == 3 ? 1 : (k) == 4 ? 2 : (k) == 8 ? 3 : 4)
-#define NPD_IS_EXT(k) ((k) == 2 || (k) == 3 || (k) == 4 || (k) == 8 || (k) == 9)
   double p_self[14], flow_out[14], p_ext[5], ext_flow[5];
+  /* passes A and C written out (not npd_stage_pass_a / npd_stage_chain): as calls they move this kernel's register allocation */
   bool rare = !(inlet_pressure >= 0.001 && inlet_pressure <= 22.0);
   {
     double cur_p = inlet_pressure, cur_flow = inlet_flow;
@@ -329,8 +505,8 @@ NPD_FN void npd_stage_system_update(const npd_stage_t &st, const double *stg, do
     }
   }
   if (__builtin_amdgcn_ballot_w64(rare) != 0) { /* wave-uniform: any lane off the fast path */
-    npd_stage_system_update_seq<SM>(st, stg, inlet_pressure, inlet_temperature, inlet_flow, load_demand,
-                                pressure_stability_factor, dt, out);
+    npd_stage_system_update_seq<SM>(st, inlet_pressure, inlet_temperature, inlet_flow, load_demand,
+                                    pressure_stability_factor, dt, out);
     return;
   }
   NPD_STAMP(13);
@@ -394,7 +570,7 @@ NPD_FN void npd_stage_system_update(const npd_stage_t &st, const double *stg, do
     NPD_DIAG(st, NPB_DIAG_STAGE_OUTLET_PRESSURE + k, p_self[k]); NPD_DIAG(st, NPB_DIAG_STAGE_OUTLET_TEMPERATURE + k, T_out);
     NPD_DIAG(st, NPB_DIAG_STAGE_POWER_OUTPUT + k, main_power + extraction_power); NPD_DIAG(st, NPB_DIAG_STAGE_LOADING_FACTOR + k, loading_factor);
     NPD_DIAG(st, NPB_DIAG_STAGE_EXTRACTION_FLOW + k, ef);
-    npd_stage_post<SM>(st, stg, k, loading_factor, T_out, dt, out);
+    npd_stage_post_staged<SM>(st, k, loading_factor, T_out, dt, out);
     T_in = T_out; sat_in = sat_self[k]; hg_in = hg_self[k];
   }
   NPD_STAMP(28);
@@ -407,8 +583,6 @@ NPD_FN void npd_stage_system_update(const npd_stage_t &st, const double *stg, do
     const double h_out = (T_c <= sat_in) ? hg_in : hg_in + cp * (T_c - sat_in);
     out->overall_efficiency = (inlet_flow > 0) ? (h_in0 - h_out) / h_in0 : 0.0;
   }
-#undef NPD_EXT_IDX
-#undef NPD_IS_EXT
 }
 
 /* _calculate_pressure_variation_effects  enhanced_physics.py:1312-1350 */
@@ -654,7 +828,7 @@ NPD_FN void npd_turbine_update(npb_turb_t *t, const npd_stage_t &st, double stea
   t->load_demand = load_demand;
   double pressure_stability_factor = npd_pressure_stability_factor(sg_pressures);
   npd_stagesys_out_t ss;
-  npd_stage_system_update<SM>(st, (const double *)0, steam_pressure, steam_temperature, steam_flow, load_demand,
+  npd_stage_system_update<SM>(st, steam_pressure, steam_temperature, steam_flow, load_demand,
                           pressure_stability_factor, dt, &ss);
   NPD_STAMP(15);
   double stage_power_mw = ss.total_power;
@@ -680,7 +854,7 @@ NPD_FN void npd_turbine_update(npb_turb_t *t, const npd_stage_t &st, double stea
     const double applied_torque = stage_power_mw * 1e6 / (2 * NPD_PI * 3600 / 60);
     NPD_DIAG(st, NPB_DIAG_TURBINE_PERFORMANCE_FACTOR, se * (1.0 - torques[0] / npd_pymax(1.0, applied_torque) * 0.1) * (1.0 - thermal_shock_risk * 0.1));
   }
-  /* MetalTemperatureTracker.update_temperatures ran per stage inside the stage pass (npd_stage_post) */
+  /* MetalTemperatureTracker.update_temperatures ran per stage inside the stage pass (npd_stage_post_staged) */
   npd_turbine_protect(t, stage_power_mw, ss.max_thermal_stress, max_bearing_metal, total_displacement, sg_system_availability, condenser_pressure, dt);
   res->electrical_power_gross = t->total_power_output;
   res->mechanical_power = t->total_power_output / 0.985;
