@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define NPB_VERSION 145 /* 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
+#define NPB_VERSION 146 /* 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
 #ifndef NPB_API
 #define NPB_API __attribute__((visibility("default")))
 #endif
@@ -194,6 +194,18 @@ NPB_API void npb_default_maintenance_table(npb_maint_table_t *table);
  * then kept by the maintenance rule kernel for the plants whose count it moves -- so a loop that wants the event counts after
  * each step (the data-gen runner does, maintenance_scenario_runner.py:392-411) needs no npb_get_field launch per step. */
 NPB_API int npb_set_maintenance_count_buffer(NpbHandle *h, int32_t *counts);
+/* The maintenance event log: every work order the automatic maintenance creates or completes, as an npb_maint_event_t record
+ * (include/npb_maint.h: time, creation time, planned start, plant, order number n = the reference's WO-%06d, pump, action,
+ * kind, priority, bearing, trigger mask) -- what the reference keeps in WorkOrderManager.work_orders / completed_work_orders and
+ * the data-gen runner exports as *_work_orders.csv / *_maintenance_actions.csv.  records (device, capacity records, 8-byte aligned:
+ * each record is stored whole and holds doubles) and cursor (device, one uint32, 4-byte aligned) are the caller's; records = NULL (capacity 0) turns the log off.  Every step with params.maint_enabled
+ * appends: each event adds 1 to *cursor (atomically, so the records of one step arrive in no particular order) and is written to
+ * records[slot] only while slot < capacity; a cursor past the capacity counts the events that were dropped.  The caller drains
+ * the log on its stream: read the cursor, copy min(cursor, capacity) records, zero the cursor.  The log is output only: not plant
+ * state, and npb_snapshot / npb_restore / the autoreset / the start bank neither read nor reset it.  NPB_EINVAL for a negative
+ * capacity, records without a cursor, a capacity without records, or misaligned buffers. */
+NPB_API int npb_set_maintenance_log(NpbHandle *h, void *records, int capacity, uint32_t *cursor);
+NPB_API size_t npb_maint_event_bytes(void);   /* sizeof(npb_maint_event_t) */
 
 /* re-initialise plants to the construction-time state; mask (device, uint8[n], NULL = all) selects plants.
  * Stands in for constructing a fresh simulator (the data-gen runner's episode start,

@@ -22,6 +22,7 @@
  */
 #ifndef NPB_MAINT_H
 #define NPB_MAINT_H
+#include <stdint.h>
 
 #define NPB_MAINT_NPARAM 16
 #define NPB_MAINT_NACT 18
@@ -121,5 +122,32 @@ static inline void npb_maint_table_default(npb_maint_table_t *t) {
   NPB__T(15, SUM_WEAR_LEVEL,          75.0, GREATER_THAN, COMPONENT_OVERHAUL,       4380.0, HIGH,     ALL)
 #undef NPB__T
 }
+
+/* one record of the maintenance event log (npb_set_maintenance_log): a work order created or completed on a feedwater pump.
+ * The reference keeps these in WorkOrderManager.work_orders / completed_work_orders (work_orders.py) and the data-gen runner
+ * writes them out as *_work_orders.csv / *_maintenance_actions.csv (maintenance_scenario_runner.py:1071-1231). */
+enum { NPB_MAINT_EVENT_CREATED = 0, NPB_MAINT_EVENT_COMPLETED = 1 };
+typedef struct npb_maint_event_t {
+  double time;            /* the rule's clock: prim.sim_time of the step [min], fp64 under either storage type */
+  double created;         /* the order's creation time [min]; for a completion mpump.last_trigger_time[action], which is the open
+                           * order's creation time because a second open order for the same (pump, action) is never created */
+  double planned_start;   /* mpump.wo_planned_start[action] as the arena holds it [min] */
+  int32_t plant;          /* the plant's index within the handle */
+  int32_t order;          /* the per-plant creation number n (mpump.wo_order): the reference's work-order id WO-%06d */
+  uint16_t trigger;       /* creation: bit q = catalog parameter q whose last_violation_time this scan stamped; 0 for a completion */
+  uint8_t pump;           /* 0..3 = FWP-1..4 */
+  uint8_t action;         /* action catalog index (NPB_MA_*) */
+  uint8_t kind;           /* NPB_MAINT_EVENT_CREATED | NPB_MAINT_EVENT_COMPLETED */
+  uint8_t priority;       /* creation: NPB_PRIO_* of the order; 0 for a completion (the state does not keep an order's priority) */
+  uint8_t bearing;        /* bearing_replacement: NPB_BEARING_* of the order (mpump.wo_bearing); else 0 */
+  uint8_t reserved;
+} npb_maint_event_t;
+#define NPB_MAINT_EVENT_BYTES 40
+#ifdef __cplusplus
+static_assert(sizeof(npb_maint_event_t) == NPB_MAINT_EVENT_BYTES, "npb_maint_event_t layout");
+static_assert(NPB_MAINT_NPARAM <= 16 && NPB_MAINT_NACT <= 255, "npb_maint_event_t field widths");
+#else
+_Static_assert(sizeof(npb_maint_event_t) == NPB_MAINT_EVENT_BYTES, "npb_maint_event_t layout");
+#endif
 
 #endif /* NPB_MAINT_H */

@@ -208,6 +208,10 @@ def load():
         L.npb_set_start_slots.argtypes = [vp, vp, vp, ci]
         L.npb_restore_bank.argtypes = [vp, vp, vp]
         L.npb_set_episode_start_buffer.argtypes = [vp, vp]
+    if hasattr(L, "npb_set_maintenance_log"):     # ABI 146: the maintenance event log
+        L.npb_set_maintenance_log.argtypes = [vp, vp, ci, vp]
+        L.npb_maint_event_bytes.restype = ctypes.c_size_t
+        L.npb_maint_action_has_handler.argtypes = [ci]
     if hasattr(L, "npb_noise_seed"):     # ABI 145: heat-source noise streams on the device
         L.npb_noise_seed.argtypes = [vp, vp, vp]
         L.npb_noise_fill.argtypes = [vp, ci, vp, vp]

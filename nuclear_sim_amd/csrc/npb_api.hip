@@ -27,6 +27,7 @@ struct NpbHandle {
   std::vector<char> maint_consts_host;
   double *diag; size_t diag_pitch; /* npb_set_diagnostics: the caller's [NPB_DIAG_DIM][diag_pitch] buffer, or NULL */
   int32_t *maint_counts;           /* npb_set_maintenance_count_buffer: the caller's [n_plants] int32 column, or NULL */
+  npb_maint_event_t *maint_log; uint32_t *maint_log_cursor; int maint_log_capacity;   /* npb_set_maintenance_log: the caller's records and cursor, or NULL */
   bool maint_cache_stale;          /* the cooldown cache of the step kernels' maintenance screen must be zeroed before the next step */
   int last_kernel;                 /* NPB_KERNEL_*: what the last npb_step launched */
   int step_kernel;                 /* 0 = chosen by batch size, 1 = one-wave kernel, 2 = two-wave kernel, 3 = its two-waves-per-SIMD build, 4 = one-wave with streaming stores, 5 = four-wave kernel (npb_set_step_kernel) */
@@ -342,6 +343,19 @@ int npb_set_maintenance_count_buffer(NpbHandle *h, int32_t *counts) {
   h->maint_cache_stale = true;     /* filled whole before the next step */
   return NPB_OK;
 }
+int npb_set_maintenance_log(NpbHandle *h, void *records, int capacity, uint32_t *cursor) {
+  if (!h) return NPB_EINVAL;
+  if (capacity < 0) return fail(h, NPB_EINVAL, "npb_set_maintenance_log: capacity must be >= 0");
+  if (records && !cursor) return fail(h, NPB_EINVAL, "npb_set_maintenance_log: records without a cursor");
+  if (!records && capacity > 0) return fail(h, NPB_EINVAL, "npb_set_maintenance_log: a capacity without records");
+  if (((uintptr_t)records & 7u) || ((uintptr_t)cursor & 3u)) return fail(h, NPB_EINVAL, "npb_set_maintenance_log: records must be 8-byte and the cursor 4-byte aligned");
+  h->maint_log = (npb_maint_event_t *)records;
+  h->maint_log_cursor = records ? cursor : nullptr;
+  h->maint_log_capacity = records ? capacity : 0;
+  h->maint_cache_stale = true;     /* the log's descriptor travels with the rule's constants: uploaded before the next step */
+  return NPB_OK;
+}
+size_t npb_maint_event_bytes(void) { return sizeof(npb_maint_event_t); }
 void npb_default_maintenance_table(npb_maint_table_t *table) { if (table) npb_maint_table_default(table); }
 
 int npb_reset(NpbHandle *h, const uint8_t *mask, void *stream) {
@@ -482,7 +496,7 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
       /* parameters, table, state or clock may have changed since the last step: the rule's constants go to the device anew and
        * the screen's cooldown cache is zeroed (= nothing known: every wave is looked at once and its entries rebuilt) */
       h->maint_consts_host.resize(npb_launch_maint_consts_bytes());
-      npb_launch_maint_consts(&h->params, &table, h->maint_consts_host.data());
+      npb_launch_maint_consts(&h->params, &table, h->maint_log, h->maint_log_cursor, h->maint_log_capacity, h->maint_consts_host.data());
       NPB_HIP(h, hipMemcpyAsync(h->maint_side, h->maint_consts_host.data(), h->maint_consts_host.size(), hipMemcpyHostToDevice, (hipStream_t)stream));
       NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));      /* the host copy may change again before an asynchronous copy would read it */
       NPB_HIP(h, hipMemsetAsync((char *)h->maint_side + npb_launch_maint_cache_offset(), 0, npb_launch_maint_side_bytes(h->pitch) - npb_launch_maint_cache_offset(),

@@ -46,7 +46,8 @@ typedef struct {
 } npb_launchers_t;
 extern npb_launchers_t npb_launch_table, npb32_launch_table;
 /* the same for either storage type */
-void npb_launch_maint_consts(const npb_params_t *P, const npb_maint_table_t *T, void *host_out);
+void npb_launch_maint_consts(const npb_params_t *P, const npb_maint_table_t *T, npb_maint_event_t *log_records, uint32_t *log_cursor,
+                             int log_capacity, void *host_out);
 size_t npb_launch_maint_consts_bytes(void);
 size_t npb_launch_maint_side_bytes(size_t npad);
 size_t npb_launch_maint_cache_offset(void);

@@ -398,7 +398,24 @@ struct npd_maint_screen_t {
   double cooldown_minutes[NPB_MAINT_NPARAM];
   uint32_t want_gt, want_lt, want_eq, want_near, want_far;    /* bit q: row q fires on value > / < / == threshold, |value - threshold| < / >= 0.001 */
 };
-struct npd_maint_rule_consts_t { npb_params_t P; npb_maint_table_t T; npd_maint_screen_t S; };
+/* the maintenance event log (npb_set_maintenance_log): the caller's records and cursor; cursor NULL = off */
+struct npd_maint_log_t { npb_maint_event_t *records; uint32_t *cursor; int capacity; };
+struct npd_maint_rule_consts_t { npb_params_t P; npb_maint_table_t T; npd_maint_screen_t S; npd_maint_log_t L; };
+/* one event site of a wave: the lanes with `want` take consecutive slots of the log through one device-scope atomic of the
+ * wave's first active lane (ballot, mbcnt, readfirstlane).  The cursor counts every event; a slot at or past the capacity is
+ * not written. */
+__device__ __forceinline__ void npd_maint_log(const npd_maint_log_t &L, bool want, const npb_maint_event_t &e) {
+  const uint64_t lanes = __ballot(want);
+  if (lanes == 0) return;
+  const uint64_t active = __ballot(1);
+  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(lanes >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lanes, 0u));
+  const bool first = __builtin_amdgcn_mbcnt_hi((uint32_t)(active >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)active, 0u)) == 0;
+  uint32_t base = 0;
+  if (first) base = __hip_atomic_fetch_add(L.cursor, (uint32_t)__popcll(lanes), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+  const uint32_t slot = base + rank;
+  if (want && slot < (uint32_t)L.capacity) L.records[slot] = e;
+}
 /* does pump k of this lane's plant have a crossed threshold outside its cooldown?  (StateManager._check_maintenance_thresholds up
  * to the point where a violation is recorded, state_manager.py:1307-1369) */
 __device__ __forceinline__ bool npd_maint_second_look(const npd_maint_screen_t &S, const npd_real_t *f64c, size_t N, size_t p, int k, double t) {
@@ -470,6 +487,9 @@ __device__ __attribute__((noinline)) void npd_maint_rule_for_wave(const npd_main
   npb_maint_t m;
   NPD_LOAD(MAINT, npb_maint_t, m, 0);
   int dirty = 0, executed = -1;      /* executed: the pump this lane's plant has just maintained (its readings have moved: scanned in any case) */
+  const bool log_on = RC->L.cursor != nullptr, live = p < (size_t)MC.n_plants;    /* padding lanes never log */
+  npb_maint_event_t ev = {};         /* the event log's record of this lane (npb_set_maintenance_log) */
+  ev.time = t; ev.plant = (int32_t)p;
   /* ---- AutoMaintenanceSystem.update: one due order, the earliest created, is carried out */
   if (npd_maint_check_due(&m, &P, t)) {
     dirty = 1;
@@ -486,6 +506,12 @@ __device__ __attribute__((noinline)) void npd_maint_rule_for_wave(const npd_main
         npb_mpump_t mp;
         NPD_MP_LOAD(pick, wo_order, NPB_MAINT_NACT); NPD_MP_LOAD(pick, wo_planned_start, NPB_MAINT_NACT);
         mp.wo_bearing = (double)*(const npd_real_t *)npd_gaddr(f64, N, p, NPD_MP_COL(pick, wo_bearing, 0));
+        if (log_on) {      /* the order as the arena holds it, before it is closed */
+          ev.created = (double)*(const npd_real_t *)npd_gaddr(f64, N, p, NPD_MP_COL(pick, last_trigger_time, pick_action));
+          ev.planned_start = (double)*(const npd_real_t *)npd_gaddr(f64, N, p, NPD_MP_COL(pick, wo_planned_start, pick_action));
+          ev.order = (int32_t)best; ev.action = (uint8_t)pick_action;
+          ev.bearing = pick_action == NPB_MA_BEARING_REPLACEMENT ? (uint8_t)mp.wo_bearing : 0;
+        }
         const int bearing = npd_maint_close_order(&mp, &m, pick_action);
         NPD_MP_STORE(pick, wo_order, NPB_MAINT_NACT); NPD_MP_STORE(pick, wo_planned_start, NPB_MAINT_NACT);
         *(npd_real_t *)npd_gaddr(f64, N, p, NPD_MP_COL(pick, wo_bearing, 0)) = (npd_real_t)mp.wo_bearing;
@@ -502,6 +528,10 @@ __device__ __attribute__((noinline)) void npd_maint_rule_for_wave(const npd_main
       }
     }
   }
+  if (log_on) {      /* at most one completion per plant and step */
+    ev.kind = NPB_MAINT_EVENT_COMPLETED; ev.pump = (uint8_t)(executed < 0 ? 0 : executed);
+    npd_maint_log(RC->L, live && executed >= 0, ev);
+  }
   /* ---- StateManager.collect_states: threshold scan, one orchestrated event per pump (after the work above, as the
    * reference orders it) */
 #pragma unroll 1
@@ -511,9 +541,30 @@ __device__ __attribute__((noinline)) void npd_maint_rule_for_wave(const npd_main
     NPD_LOAD(PUMP, npb_pump_t, pm, k);
     npb_mpump_t mp;
     NPD_LOAD(MPUMP, npb_mpump_t, mp, k);
+    const int created_before = m.work_orders_created;
     if (npd_maint_scan_pump(&mp, &m, &P, &T, &pm, t)) {
       dirty = 1;
+      if (log_on && m.work_orders_created != created_before) {    /* a work order was created: the action whose wo_order is the new count */
+        const double n = (double)m.work_orders_created;
+        ev.action = 0; ev.planned_start = 0.0;
+#pragma unroll
+        for (int a = 0; a < NPB_MAINT_NACT; a++)
+          if (mp.wo_order[a] == n) { ev.action = (uint8_t)a; ev.planned_start = (double)(npd_real_t)mp.wo_planned_start[a]; }
+        /* the rows this scan stamped (the arena still holds the stamps from before it) and the batched event's priority, their highest */
+        uint32_t trigger = 0; int priority = 0;
+#pragma unroll
+        for (int q = 0; q < NPB_MAINT_NPARAM; q++)
+          if (mp.last_violation_time[q] != (double)*(const npd_real_t *)npd_gaddr(f64, N, p, NPD_MP_COL(k, last_violation_time, q))) {
+            trigger |= 1u << q; priority = T.priority[q] > priority ? T.priority[q] : priority;
+          }
+        ev.created = t; ev.order = m.work_orders_created; ev.trigger = (uint16_t)trigger; ev.priority = (uint8_t)priority;
+        ev.bearing = ev.action == NPB_MA_BEARING_REPLACEMENT ? (uint8_t)mp.wo_bearing : 0;
+      }
       NPD_STORE(MPUMP, npb_mpump_t, mp, k);
+    }
+    if (log_on) {    /* at most one creation per pump, plant and step */
+      ev.kind = NPB_MAINT_EVENT_CREATED; ev.pump = (uint8_t)k;
+      npd_maint_log(RC->L, live && m.work_orders_created != created_before, ev);
     }
   }
   if (dirty) {
@@ -977,10 +1028,12 @@ static void NPB_LAUNCHER(maint)(size_t npad, void *arena, void *maint_side, int3
 #ifndef NPB_BUILD_F32
 /* the maintenance side buffer does not depend on the storage type (npd_maint_rule_consts_t holds no npd_real_t): one copy of
  * these.  The rule's constants as the device reads them: host_out = npb_launch_maint_consts_bytes() bytes */
-extern "C" void npb_launch_maint_consts(const npb_params_t *P, const npb_maint_table_t *T, void *host_out) {
+extern "C" void npb_launch_maint_consts(const npb_params_t *P, const npb_maint_table_t *T, npb_maint_event_t *log_records, uint32_t *log_cursor,
+                                        int log_capacity, void *host_out) {
   npd_maint_rule_consts_t *RC = (npd_maint_rule_consts_t *)host_out;
   memset(RC, 0, sizeof(*RC));
   RC->P = *P; RC->T = *T;
+  RC->L.records = log_records; RC->L.cursor = log_records ? log_cursor : nullptr; RC->L.capacity = log_records ? log_capacity : 0;
   npd_maint_screen_t &S = RC->S;
   for (int q = 0; q < NPB_MAINT_NPARAM; q++) {
     S.threshold[q] = T->threshold[q];

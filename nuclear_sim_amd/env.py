@@ -301,7 +301,8 @@ class BatchedPlantEnv:
     @classmethod
     def action_test(cls, action: str, seeds: Sequence[int], dt: float = 5.0, device: int = 0, randomize: bool = True,
                     params: Optional[dict] = None, autoreset: bool = False, max_episode_steps: Optional[int] = None,
-                    bank_seeds: Optional[Sequence[int]] = None, noise_generator: str = "host") -> "BatchedPlantEnv":
+                    bank_seeds: Optional[Sequence[int]] = None, noise_generator: str = "host",
+                    maintenance_log: Optional[int] = None) -> "BatchedPlantEnv":
         """One plant per seed, as data_gen's MaintenanceScenarioRunner builds them for
         ``compose_action_test_scenario(action, randomize=True, randomization_seed=seed)``
         (maintenance_scenario_runner.py:210-244): dt in minutes, ConstantHeatSource with 0.1 % noise seeded 42,
@@ -309,7 +310,7 @@ class BatchedPlantEnv:
         snapshot is taken after the initial conditions are in: each plant restarts from its own.  With ``bank_seeds`` later
         episodes start from a bank built as ``action_test(action, bank_seeds)`` with the same ``randomize``, ``dt`` and ``params``
         (``set_start_bank`` with its default slots): each restart draws a fresh scenario, as the data-gen runner's episodes do.
-        ``noise_generator`` as for the constructor."""
+        ``noise_generator`` as for the constructor; ``maintenance_log`` = a capacity: ``enable_maintenance_log(capacity)``."""
         if max_episode_steps is not None and not autoreset:
             raise ValueError("max_episode_steps needs autoreset=True")
         from . import scenarios
@@ -329,6 +330,8 @@ class BatchedPlantEnv:
             env.set_start_bank(bank)
             torch.cuda.current_stream(env.device).synchronize()     # the copy has read the bank batch's arena
             bank.close()
+        if maintenance_log is not None:
+            env.enable_maintenance_log(maintenance_log)
         return env
 
     # ------------------------------------------------------------------ helpers
@@ -377,6 +380,73 @@ class BatchedPlantEnv:
                 buf[row].fill_(value)
             else:
                 buf[row, : self.n].masked_fill_(mask.to(torch.bool), value)
+
+    def enable_maintenance_log(self, capacity: Optional[int] = 65536) -> None:
+        """Have every step append the work orders the automatic maintenance creates and completes to a log on the device
+        (npb_set_maintenance_log: one record per event, include/npb_maint.h npb_maint_event_t) that ``maintenance_log()`` drains:
+        what the reference keeps in WorkOrderManager.work_orders / completed_work_orders and the data-gen runner exports as
+        ``*_work_orders.csv`` / ``*_maintenance_actions.csv``.  ``capacity`` records are allocated; events past them are counted,
+        not written, until the next drain.  ``None`` turns the log off.  The log is output only: ``snapshot``, ``restore``, the
+        autoreset and the start bank neither read nor reset it, so a plant's episodes are told apart by time alone, and after a
+        restore its work-order numbers restart from the restored counters, as a fresh reference simulator's would."""
+        if capacity is None:
+            _lib.check(self.L.npb_set_maintenance_log(self._h, None, 0, None), self._h)
+            self._mlog = None
+            return
+        if not self.params.maint_enabled:
+            raise ValueError("the maintenance log needs the automatic maintenance (maintenance=True)")
+        cap = int(capacity)
+        if cap < 0:
+            raise ValueError("capacity must be >= 0")
+        from . import maintlog
+        nbytes = int(self.L.npb_maint_event_bytes())
+        assert nbytes == maintlog.EVENT_DTYPE.itemsize, (nbytes, maintlog.EVENT_DTYPE.itemsize)
+        with torch.cuda.device(self.device):
+            records = torch.zeros(max(cap, 1) * nbytes, dtype=torch.uint8, device=self.device)
+            cursor = torch.zeros(1, dtype=torch.int32, device=self.device)     # a uint32 on the device
+        _lib.check(self.L.npb_set_maintenance_log(self._h, self._p(records), cap, self._p(cursor)), self._h)
+        # the drain's landing place: pinned host memory, so that a drain is a DMA copy rather than a staged one
+        self._mlog = {"records": records, "cursor": cursor, "capacity": cap, "host": torch.empty(records.numel(), dtype=torch.uint8, pin_memory=True),
+                      "host_cursor": torch.empty(1, dtype=torch.int32, pin_memory=True)}
+
+    def maintenance_log_records(self, clear: bool = True, allow_overflow: bool = False) -> np.ndarray:
+        """Drain the log on the env's stream: the records (numpy, ``maintlog.EVENT_DTYPE``) in the device's order.  An overflowed
+        log raises, naming how many events were dropped, and is left as it is, unless ``allow_overflow``."""
+        from . import maintlog
+        ml = getattr(self, "_mlog", None)
+        if ml is None:
+            raise _lib.NpbError("no maintenance log: enable_maintenance_log() first")
+        stream = torch.cuda.current_stream(self.device)
+        ml["host_cursor"].copy_(ml["cursor"], non_blocking=True)
+        stream.synchronize()
+        count = int(ml["host_cursor"][0]) & 0xFFFFFFFF
+        cap = ml["capacity"]
+        if count > cap and not allow_overflow:
+            raise _lib.NpbError("maintenance log overflowed: %d events, capacity %d, %d dropped (enable_maintenance_log with a larger "
+                                "capacity, drain more often, or pass allow_overflow=True)" % (count, cap, count - cap))
+        nb = min(count, cap) * maintlog.EVENT_DTYPE.itemsize
+        if nb:
+            ml["host"][:nb].copy_(ml["records"][:nb], non_blocking=True)
+            stream.synchronize()
+        rec = ml["host"][:nb].numpy().view(maintlog.EVENT_DTYPE).copy()
+        if clear:
+            ml["cursor"].zero_()
+        return rec
+
+    def maintenance_log(self, clear: bool = True, allow_overflow: bool = False) -> Dict[str, np.ndarray]:
+        """``maintenance_log_records`` as columns sorted by (plant, time, completion before creation, pump), named as the
+        reference's export (nuclear_sim_amd/maintlog.py): plant, pump, action_type, event_type, timestamp_minutes / _hours,
+        work_order_id, component_id, priority, work_order_type, title, created_date, planned_start_date, actual_completion_date,
+        bearing, trigger_parameters, has_handler."""
+        from . import maintlog
+        rec = self.maintenance_log_records(clear=clear, allow_overflow=allow_overflow)
+        handlers = [int(self.L.npb_maint_action_has_handler(a)) for a in range(len(_lib.MAINT_ACTIONS))]
+        return maintlog.columns(rec, _lib.MAINT_ACTIONS, _lib.MAINT_PARAMS, handlers)
+
+    def write_maintenance_log(self, path: str, clear: bool = True, allow_overflow: bool = False) -> None:
+        """Drain the log into a CSV (``.csv``) or Parquet file"""
+        from . import maintlog
+        maintlog.write(self.maintenance_log(clear=clear, allow_overflow=allow_overflow), path)
 
     def snapshot(self) -> None:
         """Record every plant's current state as its episode start (npb_snapshot: one device-to-device copy of the arena).  Call it
