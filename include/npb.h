@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define NPB_VERSION 146 /* 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
+#define NPB_VERSION 147 /* 0.1.4.7: npb_perform_maintenance, NPB_MAINT_EVENT_OPERATOR (maintenance a caller orders, carried out on the device between two steps); 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
 #ifndef NPB_API
 #define NPB_API __attribute__((visibility("default")))
 #endif
@@ -206,6 +206,27 @@ NPB_API int npb_set_maintenance_count_buffer(NpbHandle *h, int32_t *counts);
  * capacity, records without a cursor, a capacity without records, or misaligned buffers. */
 NPB_API int npb_set_maintenance_log(NpbHandle *h, void *records, int capacity, uint32_t *cursor);
 NPB_API size_t npb_maint_event_bytes(void);   /* sizeof(npb_maint_event_t) */
+/* Operator-ordered maintenance: FeedwaterPump.perform_maintenance(maintenance_type, **kwargs) (feedwater/pump_system.py:750), i.e. the
+ * lubrication system's dispatcher (feedwater/pump_lubrication.py:625-674), called by the USER between two steps: for every plant p
+ * with action[p] >= 0, what that call does to pump pump[p] (0..3 = FWP-1..4) of the plant, at once -- no work order, no delay.  All
+ * pointers are device pointers to n_plants elements; asynchronous on `stream`.
+ *   action        NPB_MA_* index (npb_maint_action_name), -1 = nothing for this plant
+ *   bearing       NULL = NPB_BEARING_ALL: the component_id kwarg of _perform_bearing_replacement (:755-808), NPB_BEARING_*
+ *   target_level  NULL = 95.0, the default ARGUMENT of _perform_oil_top_off (:710) -- not params.maint_top_off_target, which is what the
+ *                 automatic maintenance passes; the other handlers ignore both columns, as the reference's **kwargs do
+ *   success       may be NULL; 1 where the reference's result dict has 'success': True -- the dispatcher has a handler for the action
+ *                 (npb_maint_action_has_handler) and a bearing replacement names a valid bearing -- else 0, plants with action -1 included.
+ *                 An action outside the catalog, a pump outside 0..3, a bearing_replacement with a bearing outside 0..3 are the reference's
+ *                 "Unknown maintenance type" / "Invalid bearing component": success 0, state untouched, no error code (the columns are on
+ *                 the device and the call does not synchronise).
+ * Only the pump section of the ordered pump changes, and a plant without a successful order keeps its exact bits.  The work-order queue,
+ * the maint.* / mpump.* columns, the count buffer (npb_set_maintenance_count_buffer) and the diagnostics rows do not move: a direct call
+ * bypasses AutoMaintenanceSystem in the reference too.  Works with params.maint_enabled 0 or 1, in every mode and storage type.  With a
+ * maintenance log set (npb_set_maintenance_log) every successful order appends one NPB_MAINT_EVENT_OPERATOR record.  Not offered: work
+ * orders created by the operator (queued, delayed, counted), and maintenance of steam generators, turbine, condenser.
+ * NPB_EINVAL for action = NULL or pump = NULL. */
+NPB_API int npb_perform_maintenance(NpbHandle *h, const int32_t *action, const int32_t *pump, const int32_t *bearing,
+                                    const double *target_level, uint8_t *success, void *stream);
 
 /* re-initialise plants to the construction-time state; mask (device, uint8[n], NULL = all) selects plants.
  * Stands in for constructing a fresh simulator (the data-gen runner's episode start,

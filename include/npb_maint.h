@@ -126,7 +126,9 @@ static inline void npb_maint_table_default(npb_maint_table_t *t) {
 /* one record of the maintenance event log (npb_set_maintenance_log): a work order created or completed on a feedwater pump.
  * The reference keeps these in WorkOrderManager.work_orders / completed_work_orders (work_orders.py) and the data-gen runner
  * writes them out as *_work_orders.csv / *_maintenance_actions.csv (maintenance_scenario_runner.py:1071-1231). */
-enum { NPB_MAINT_EVENT_CREATED = 0, NPB_MAINT_EVENT_COMPLETED = 1 };
+/* NPB_MAINT_EVENT_OPERATOR: an action a caller ordered through npb_perform_maintenance and the dispatcher carried out at once (no work
+ * order behind it): order = 0, created = planned_start = time = the plant's clock at the call, trigger = priority = 0 */
+enum { NPB_MAINT_EVENT_CREATED = 0, NPB_MAINT_EVENT_COMPLETED = 1, NPB_MAINT_EVENT_OPERATOR = 2 };
 typedef struct npb_maint_event_t {
   double time;            /* the rule's clock: prim.sim_time of the step [min], fp64 under either storage type */
   double created;         /* the order's creation time [min]; for a completion mpump.last_trigger_time[action], which is the open
@@ -137,7 +139,7 @@ typedef struct npb_maint_event_t {
   uint16_t trigger;       /* creation: bit q = catalog parameter q whose last_violation_time this scan stamped; 0 for a completion */
   uint8_t pump;           /* 0..3 = FWP-1..4 */
   uint8_t action;         /* action catalog index (NPB_MA_*) */
-  uint8_t kind;           /* NPB_MAINT_EVENT_CREATED | NPB_MAINT_EVENT_COMPLETED */
+  uint8_t kind;           /* NPB_MAINT_EVENT_CREATED | NPB_MAINT_EVENT_COMPLETED | NPB_MAINT_EVENT_OPERATOR */
   uint8_t priority;       /* creation: NPB_PRIO_* of the order; 0 for a completion (the state does not keep an order's priority) */
   uint8_t bearing;        /* bearing_replacement: NPB_BEARING_* of the order (mpump.wo_bearing); else 0 */
   uint8_t reserved;

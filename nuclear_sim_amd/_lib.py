@@ -97,6 +97,8 @@ def __getattr__(name):
         if len(params) != MAINT_NPARAM or len(actions) != MAINT_NACT:
             raise NpbError("libnpb.so's maintenance catalogs (%d parameters, %d actions) are not the %d / %d this binding's "
                            "NpbMaintTable is laid out for: rebuild" % (len(params), len(actions), MAINT_NPARAM, MAINT_NACT))
+        if tuple(actions) != MAINT_ACTION_NAMES:
+            raise NpbError("libnpb.so's action catalog is not this binding's MAINT_ACTION_NAMES: rebuild")
         globals()["MAINT_PARAMS"], globals()["MAINT_ACTIONS"] = params, actions
         return globals()[name]
     raise AttributeError(name)
@@ -105,6 +107,23 @@ def __getattr__(name):
 MAINT_COMPARISONS = ("greater_than", "less_than", "greater_equal", "less_equal", "equals", "not_equals")
 MAINT_PRIORITIES = {"LOW": 1, "MEDIUM": 2, "HIGH": 3, "CRITICAL": 4, "EMERGENCY": 5}
 MAINT_BEARINGS = {None: 0, "all": 0, "motor_bearings": 1, "pump_bearings": 2, "thrust_bearing": 3}
+MAINT_ACTION_NONE = -1     # npb_perform_maintenance: nothing ordered for this plant
+# include/npb_maint.h NPB_MAINT_ACTIONS, for the checks that must not need the library (an unknown name is refused before any device
+# is looked for); load() holds it against the library's own catalog
+MAINT_ACTION_NAMES = ("oil_change", "oil_top_off", "lubrication_system_check", "impeller_inspection", "impeller_replacement",
+                      "cavitation_analysis", "npsh_analysis", "bearing_replacement", "seal_replacement", "vibration_analysis",
+                      "lubrication_inspection", "motor_inspection", "component_overhaul", "comprehensive_system_inspection",
+                      "bearing_inspection", "oil_analysis", "system_cleaning", "routine_maintenance")
+PUMP_IDS = ("FWP-1", "FWP-2", "FWP-3", "FWP-4")
+
+
+def maint_action_index(action) -> int:
+    """an action name of the catalog, or an index, -> index; ValueError for an unknown name (host only, no library needed)"""
+    if isinstance(action, str):
+        if action not in MAINT_ACTION_NAMES:
+            raise ValueError("unknown maintenance action %r: not in the action catalog (include/npb_maint.h)" % (action,))
+        return MAINT_ACTION_NAMES.index(action)
+    return int(action)
 
 
 def maint_table_from_thresholds(thresholds: dict) -> "NpbMaintTable":
@@ -212,6 +231,8 @@ def load():
         L.npb_set_maintenance_log.argtypes = [vp, vp, ci, vp]
         L.npb_maint_event_bytes.restype = ctypes.c_size_t
         L.npb_maint_action_has_handler.argtypes = [ci]
+    if hasattr(L, "npb_perform_maintenance"):     # ABI 147: maintenance the caller orders
+        L.npb_perform_maintenance.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "npb_noise_seed"):     # ABI 145: heat-source noise streams on the device
         L.npb_noise_seed.argtypes = [vp, vp, vp]
         L.npb_noise_fill.argtypes = [vp, ci, vp, vp]

@@ -356,6 +356,23 @@ int npb_set_maintenance_log(NpbHandle *h, void *records, int capacity, uint32_t 
   return NPB_OK;
 }
 size_t npb_maint_event_bytes(void) { return sizeof(npb_maint_event_t); }
+
+int npb_perform_maintenance(NpbHandle *h, const int32_t *action, const int32_t *pump, const int32_t *bearing, const double *target_level,
+                            uint8_t *success, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!action || !pump) return fail(h, NPB_EINVAL, "npb_perform_maintenance: the action and pump columns must not be NULL");
+  NPB_USE_DEVICE(h);
+  /* maint_cache_stale is left alone.  The cooldown cache of the step kernels' threshold screen holds, per (plant, pump), which table rows
+   * are inside their cooldown and until when: a function of the mpump.last_violation_time stamps, the table and the clock
+   * (npd_maint_cache_entry), none of which a handler writes -- it changes members of the pump section only, and those the screen reads
+   * fresh from the pump phase's registers at every step (npd_maint_pump_hit).  Nor does the caller's count column move: an operator
+   * action is not counted in maintenance_actions_performed.  The log's descriptor travels as a kernel argument, so the call does not
+   * depend on the rule's constants having been uploaded (they are only with params.maint_enabled). */
+  h->K->operator_maint(h->n_plants, NPB_N(h), h->f64, action, pump, bearing, target_level, success, h->maint_log, h->maint_log_cursor,
+                       h->maint_log_capacity, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
 void npb_default_maintenance_table(npb_maint_table_t *table) { if (table) npb_maint_table_default(table); }
 
 int npb_reset(NpbHandle *h, const uint8_t *mask, void *stream) {

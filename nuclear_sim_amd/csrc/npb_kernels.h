@@ -43,6 +43,11 @@ typedef struct {
   void (*episode)(int mode, int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *done, const double *reward,
                   double *obs, int32_t *len, double *ret, int32_t *out_len, double *out_ret, uint8_t *out_truncated,
                   double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, hipStream_t stream);
+  /* npb_perform_maintenance: the caller's [n_plants] order columns (bearing / target_level / success may be NULL) and the maintenance
+   * event log's descriptor (log_records NULL = off) */
+  void (*operator_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *pump, const int32_t *bearing,
+                         const double *target_level, uint8_t *success, npb_maint_event_t *log_records, uint32_t *log_cursor, int log_capacity,
+                         hipStream_t stream);
 } npb_launchers_t;
 extern npb_launchers_t npb_launch_table, npb32_launch_table;
 /* the same for either storage type */

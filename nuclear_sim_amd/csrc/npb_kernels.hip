@@ -859,6 +859,61 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_reset_kernel(npb_params_t P, siz
   /* the pH controller and its pending doses are not reset (secondary/__init__.py:1041-1072 never touches them) */
 }
 
+/* operator-ordered maintenance (npb_perform_maintenance): FeedwaterPump.perform_maintenance(type, **kwargs) called by the user between
+ * two steps (feedwater/pump_system.py:750 -> the lubrication system's dispatcher, pump_lubrication.py:625-674), for every plant whose
+ * lane of the caller's columns orders one.  One wave per 64 plants.  The expected use is sparse -- a policy orders service for a
+ * small share of the plants per step -- so a wave first reads its 64 orders (8 B per plant) and leaves when none can succeed; a wave
+ * that stays visits the pumps somebody ordered, and only the ordering lanes load, change and store their pump section: a plant
+ * without a successful order keeps its exact bits under either storage type because nothing is stored to it.  The work-order queue,
+ * the maint.* / mpump.* sections and the counters are not touched (a direct call bypasses AutoMaintenanceSystem in the reference too). */
+struct npd_operator_orders_t {
+  const int32_t *action, *pump, *bearing;     /* the caller's [n_plants] columns; bearing NULL = NPB_BEARING_ALL */
+  const double *target_level;                 /* [n_plants], NULL = 95.0: _perform_oil_top_off's default argument (pump_lubrication.py:710) */
+  uint8_t *success;                           /* [n_plants] or NULL */
+  int n_plants;
+};
+__global__ __launch_bounds__(NPB_WAVE) void npb_operator_maint_kernel(npd_operator_orders_t O, npd_maint_log_t L, size_t N, npd_real_t *__restrict__ f64) {
+  const size_t p = (size_t)blockIdx.x * NPB_WAVE + threadIdx.x;
+  const bool live = p < (size_t)O.n_plants;      /* the columns have n_plants elements, not the pitch */
+  int action = -1, pump = 0;
+  if (live) { action = O.action[p]; pump = O.pump[p]; }
+  /* "Unknown maintenance type" (pump_lubrication.py:661-668): an action outside the catalog or without a handler; a pump that is none */
+  bool ok = action >= 0 && action < NPB_MAINT_NACT && ((NPD_MA_HANDLER_MASK >> (action & 31)) & 1u) && pump >= 0 && pump < NPB_NUM_PUMPS;
+  if (!__any(ok)) {
+    if (live && O.success) O.success[p] = 0;
+    return;
+  }
+  int bearing = NPB_BEARING_ALL;
+  double target_level = 95.0;
+  if (ok && O.bearing) bearing = O.bearing[p];
+  if (ok && O.target_level) target_level = O.target_level[p];
+  /* "Invalid bearing component" (:789-797); the other handlers take no component_id and ignore it */
+  if (action == NPB_MA_BEARING_REPLACEMENT && (bearing < NPB_BEARING_ALL || bearing > NPB_BEARING_THRUST)) ok = false;
+  if (live && O.success) O.success[p] = ok ? 1 : 0;
+  NPD_SEGMENT(f64, N, (size_t)blockIdx.x * NPB_WAVE);
+#pragma unroll 1
+  for (int k = 0; k < NPB_NUM_PUMPS; k++) {
+    const bool mine = ok && pump == k;
+    if (!__any(mine)) continue;
+    if (mine) {
+      npb_pump_t pm;
+      NPD_LOAD(PUMP, npb_pump_t, pm, k);
+      npb_params_t P = {};      /* the handlers read one parameter: the top-off target, which here is the caller's argument */
+      P.maint_top_off_target = target_level;
+      npd_maint_execute(&pm, &P, action, bearing);
+      NPD_STORE(PUMP, npb_pump_t, pm, k);
+    }
+  }
+  if (L.cursor) {      /* the event log (npb_set_maintenance_log): one record per successful order, one atomic per wave */
+    const double t = NPD_F64_COL(PRIM, npb_prim_t, sim_time, 0);
+    npb_maint_event_t ev = {};
+    ev.time = t; ev.created = t; ev.planned_start = t; ev.plant = (int32_t)p;
+    ev.pump = (uint8_t)pump; ev.action = (uint8_t)action; ev.kind = NPB_MAINT_EVENT_OPERATOR;
+    ev.bearing = action == NPB_MA_BEARING_REPLACEMENT ? (uint8_t)bearing : 0;
+    npd_maint_log(L, ok, ev);
+  }
+}
+
 #ifndef NPB_BUILD_F32
 /* calibration aid for the HBM traffic counters: reads every arena column and writes it back unchanged,
  * with exactly the access shape of the step kernel (8 B per lane, one 512-B line per wave and column),
@@ -1087,10 +1142,21 @@ static void NPB_LAUNCHER(episode)(int mode, int n_plants, size_t npad, void *are
   hipLaunchKernelGGL(npb_episode_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, mode, n_plants, npad, (npd_real_t *)arena,
                      src, done, reward, obs, E, npd_restore_side_of(maint_side, maint_counts, n_plants));
 }
+/* npb_perform_maintenance: the caller's order columns; log_* = the maintenance event log (npb_set_maintenance_log), records NULL = off */
+static void NPB_LAUNCHER(operator_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *pump, const int32_t *bearing,
+                                         const double *target_level, uint8_t *success, npb_maint_event_t *log_records, uint32_t *log_cursor,
+                                         int log_capacity, hipStream_t stream) {
+  npd_operator_orders_t O;
+  O.action = action; O.pump = pump; O.bearing = bearing; O.target_level = target_level; O.success = success; O.n_plants = n_plants;
+  npd_maint_log_t L;
+  L.records = log_records; L.cursor = log_records ? log_cursor : nullptr; L.capacity = log_records ? log_capacity : 0;
+  hipLaunchKernelGGL(npb_operator_maint_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, O, L, npad, (npd_real_t *)arena);
+}
 /* not const: clang emits a namespace-scope const into the device code too, where these host functions do not exist */
 extern "C" npb_launchers_t NPB_LAUNCHER(table) = {
   NPB_LAUNCHER(step), NPB_LAUNCHER(maint), NPB_LAUNCHER(observe), NPB_LAUNCHER(init), NPB_LAUNCHER(reset),
   NPB_LAUNCHER(field_get), NPB_LAUNCHER(field_set), NPB_LAUNCHER(gather), NPB_LAUNCHER(restore), NPB_LAUNCHER(episode),
+  NPB_LAUNCHER(operator_maint),
 };
 #ifndef NPB_BUILD_F32
 /* npb_reset / npb_reset_reference / npb_restore: the episode counters (len, ret) and the carried start entries (start: -1, not from

@@ -13,6 +13,7 @@ from __future__ import annotations
 import ctypes
 import os
 import enum
+import re
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -207,6 +208,10 @@ class BatchedPlantEnv:
     own snapshot lane, and advance its slot, all on the device.  ``info["episode_start"]`` is the bank entry of the episode each
     step's transition belonged to (-1: not from the bank), ``episode_start`` the entry of each plant's last bank restore.  A
     restored plant takes the entry's clock and maintenance stamps; the heat-source noise stream stays with the plant position.
+
+    Operator-ordered maintenance: ``perform_maintenance(action, pump, mask=...)`` is the reference's
+    ``pump.perform_maintenance(type, **kwargs)`` for the whole batch, between two steps, on the device (npb_perform_maintenance): the
+    caller decides when a feedwater pump is serviced, with the automatic maintenance off or beside it.
 
     Heat-source noise (``noise_enabled``): ``noise_generator="host"`` (the default) draws each plant's
     ``RandomState(seed).standard_normal()`` stream on the host (``HeatSourceNoise``); ``"device"`` generates the same streams on the
@@ -447,6 +452,80 @@ class BatchedPlantEnv:
         """Drain the log into a CSV (``.csv``) or Parquet file"""
         from . import maintlog
         maintlog.write(self.maintenance_log(clear=clear, allow_overflow=allow_overflow), path)
+
+    def _order_column(self, key, value, dtype, to_number):
+        """one column of perform_maintenance's order: a device tensor of the right type is passed as it is, anything else lands in a
+        buffer the env keeps (a scalar by fill_, an array by one copy); ``to_number`` maps a name to its index"""
+        if isinstance(value, torch.Tensor) and value.device == self.device and value.dtype == dtype and value.shape == (self.n,) and value.is_contiguous():
+            return value
+        buf = self._orders.get(key)
+        if buf is None:
+            with torch.cuda.device(self.device):
+                buf = self._orders[key] = torch.empty(self.n, dtype=dtype, device=self.device)
+        if isinstance(value, torch.Tensor):
+            buf.copy_(value.expand(self.n), non_blocking=True)
+        else:
+            a = np.asarray(to_number(value) if isinstance(value, str) or value is None else value)
+            if a.size == 1:
+                buf.fill_(a.reshape(()).item())
+            else:
+                buf.copy_(torch.as_tensor(np.array(np.broadcast_to(a, (self.n,)))))
+        return buf
+
+    def perform_maintenance(self, action, pump, mask=None, bearing=None, target_level=None) -> torch.Tensor:
+        """Operator-ordered maintenance between two steps (npb_perform_maintenance): what the reference's
+        ``pump.perform_maintenance(action, **kwargs)`` (feedwater/pump_system.py:750, the lubrication system's dispatcher
+        pump_lubrication.py:625-674) does to the ordered pump of every ordered plant, at once, on the device.
+
+        ``action``: a name of ``_lib.MAINT_ACTIONS``, its index, or an int32 column (``-1`` = nothing for that plant); an unknown name
+        raises ValueError before any device work.  ``pump``: 0..3, ``"FWP-1"``..``"FWP-4"``, or an int32 column.  ``mask`` (column,
+        nonzero = ordered) turns the order into ``-1`` where it is 0.  ``bearing``: the ``component_id`` of a bearing replacement --
+        None / ``"all"`` / ``"motor_bearings"`` / ``"pump_bearings"`` / ``"thrust_bearing"`` / NPB_BEARING_* / a column.
+        ``target_level``: the oil top-off's target, default 95.0 as the reference's argument (not ``params.maint_top_off_target``,
+        which the automatic maintenance uses).  Returns the ``success`` column (uint8; one of the env's own buffers, like step()'s
+        outputs): 1 where the reference's result dict has ``'success': True``.  An action without a handler, a pump or bearing that does
+        not exist: success 0, state untouched.  No host synchronisation, and with scalars or device columns no allocation after the first call
+        (a host array is copied to the device, as step()'s inputs are).
+
+        Only the ordered pump's state changes: no work order is created, ``info["maintenance_event_count"]`` and the ``maint.*`` /
+        ``mpump.*`` columns do not move (the reference's direct call bypasses AutoMaintenanceSystem too); with the maintenance log
+        on, each successful order is one ``operator_maintenance`` record.  Not covered: operator-created work orders, maintenance of
+        steam generators / turbine / condenser, and -- with ``enable_diagnostics`` -- the per-pump ``maintenance_occurred`` /
+        ``oil_top_off_occurred`` / ``maintenance_action`` diagnostics rows, which an operator action leaves alone."""
+        if isinstance(action, str):
+            action = _lib.maint_action_index(action)       # ValueError for an unknown name, before anything else
+        if isinstance(pump, str):
+            if pump not in _lib.PUMP_IDS:
+                raise ValueError("unknown feedwater pump %r: one of %r" % (pump, _lib.PUMP_IDS))
+            pump = _lib.PUMP_IDS.index(pump)
+        if isinstance(bearing, str) and bearing not in _lib.MAINT_BEARINGS:
+            raise ValueError("unknown bearing %r: one of %r" % (bearing, [k for k in _lib.MAINT_BEARINGS if k]))
+        if not hasattr(self.L, "npb_perform_maintenance"):
+            raise _lib.NpbError("libnpb.so has no npb_perform_maintenance (older than ABI 147): rebuild")
+        if getattr(self, "_orders", None) is None:
+            self._orders = {}
+            with torch.cuda.device(self.device):
+                self._orders["success"] = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+        a = self._order_column("action", action, torch.int32, _lib.maint_action_index)
+        if mask is not None:
+            m = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(np.array(np.broadcast_to(np.asarray(mask), (self.n,))))
+            none = self._orders.get("none")
+            if none is None:
+                with torch.cuda.device(self.device):
+                    none = self._orders["none"] = torch.empty(self.n, dtype=torch.bool, device=self.device)
+                    self._orders["masked"] = torch.empty(self.n, dtype=torch.int32, device=self.device)
+            if m.device != self.device:
+                m = m.to(self.device, non_blocking=True)
+            torch.eq(m.expand(self.n), 0, out=none)
+            masked = self._orders["masked"]
+            masked.copy_(a)         # the caller's own column is left as it is
+            a = masked.masked_fill_(none, _lib.MAINT_ACTION_NONE)
+        k = self._order_column("pump", pump, torch.int32, _lib.PUMP_IDS.index)
+        b = None if bearing is None else self._order_column("bearing", bearing, torch.int32, _lib.MAINT_BEARINGS.__getitem__)
+        lvl = None if target_level is None else self._order_column("target_level", target_level, torch.float64, float)
+        ok = self._orders["success"]
+        _lib.check(self.L.npb_perform_maintenance(self._h, self._p(a), self._p(k), self._p(b), self._p(lvl), self._p(ok), self._stream()), self._h)
+        return ok
 
     def snapshot(self) -> None:
         """Record every plant's current state as its episode start (npb_snapshot: one device-to-device copy of the arena).  Call it
@@ -856,10 +935,35 @@ class _PathProxy:
             return _PathProxy(self._env, path)
         raise AttributeError("%s is not a state member of the plant" % path)
 
+    # the two objects of the reference whose perform_maintenance is on the device: a feedwater pump and its lubrication system
+    _MAINTAINABLE = re.compile(r"^secondary_physics\.feedwater_system\.pump_system\.pumps\['(FWP-[1-4])'\](\.lubrication_system)?$")
+
+    def _perform_maintenance(self, pump_id):
+        env = self._env
+
+        def perform_maintenance(maintenance_type="general", **kwargs):
+            """FeedwaterPump.perform_maintenance / FeedwaterPumpLubricationSystem.perform_maintenance (pump_system.py:750,
+            pump_lubrication.py:625) on this pump, now.  Returns ``{'success': bool}``: the remaining keys of the reference's result
+            dict (duration_hours, work_performed, findings, effectiveness_score ...) are omitted.  A maintenance type the action
+            catalog does not know is the reference's "Unknown maintenance type": success False, nothing changed."""
+            names = _lib.MAINT_ACTION_NAMES
+            if maintenance_type not in names:
+                return {"success": False}
+            cid = kwargs.get("component_id")
+            if cid is None or isinstance(cid, str):      # a component_id that names no bearing: "Invalid bearing component" (-1 on the device)
+                cid = _lib.MAINT_BEARINGS.get(cid, -1)
+            ok = env.perform_maintenance(names.index(maintenance_type), pump_id, bearing=cid, target_level=kwargs.get("target_level"))
+            return {"success": bool(ok[0].item())}
+        return perform_maintenance
+
     def __getattr__(self, name):
         extras = object.__getattribute__(self, "_extras")
         if name in extras:
             return extras[name]
+        if name == "perform_maintenance":
+            m = self._MAINTAINABLE.match(self._prefix or "")
+            if m:
+                return self._perform_maintenance(m.group(1))
         return self._resolve("%s.%s" % (self._prefix, name) if self._prefix else name)
 
     def __getitem__(self, key):

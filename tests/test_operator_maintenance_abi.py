@@ -1,0 +1,196 @@
+"""CPU: operator-ordered maintenance (npb_perform_maintenance) is declared by include/npb.h, exported by libnpb.so and bound; a NULL
+handle is refused; an unknown action name is refused on the host before a device is looked for; nuclear_sim_amd.maintlog renders the
+third record kind and the automatic ones as before; and the reference fixtures under tests/golden/operator/
+(tools/make_operator_maintenance_golden.py) are not vacuous: every call that acts by construction changes the reference's pump state,
+every other call changes none.  No compute calls."""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from operator_maintenance_golden import HANDLERS, OperatorGolden, operator_fixture_names
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
+
+
+@pytest.fixture(scope="module")
+def built_lib():
+    if not os.path.exists(LIB):
+        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
+    return LIB
+
+
+def test_header_declares_the_entry_point():
+    text = open(os.path.join(ROOT, "include", "npb.h")).read()
+    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
+    assert "npb_perform_maintenance" in declared
+    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) >= 147
+    maint = open(os.path.join(ROOT, "include", "npb_maint.h")).read()
+    assert re.search(r"NPB_MAINT_EVENT_OPERATOR\s*=\s*2\b", maint)
+
+
+def test_library_exports_and_binding_declares_it(built_lib):
+    lib = ctypes.CDLL(built_lib)
+    assert hasattr(lib, "npb_perform_maintenance"), "libnpb.so does not export npb_perform_maintenance"
+    assert lib.npb_version() >= 147
+    from nuclear_sim_amd import _lib
+    L = _lib.load()
+    assert L.npb_perform_maintenance.argtypes is not None and len(L.npb_perform_maintenance.argtypes) == 7
+
+
+def test_null_handle_is_refused(built_lib):
+    from nuclear_sim_amd import _lib
+    L = _lib.load()
+    assert L.npb_perform_maintenance(None, None, None, None, None, None, None) == -1
+
+
+def test_host_catalog_is_the_librarys(built_lib):
+    """the names the host checks an order against without the library are the library's own catalog, handlers included"""
+    from nuclear_sim_amd import _lib
+    L = _lib.load()
+    assert list(_lib.MAINT_ACTION_NAMES) == list(_lib.MAINT_ACTIONS)
+    assert {a for k, a in enumerate(_lib.MAINT_ACTION_NAMES) if L.npb_maint_action_has_handler(k)} == set(HANDLERS)
+
+
+def test_unknown_action_name_is_refused_before_any_device_work():
+    """a name outside the catalog raises ValueError at once: on an object that has no handle, no library and no device behind it"""
+    from nuclear_sim_amd import _lib
+    from nuclear_sim_amd.env import BatchedPlantEnv
+    env = object.__new__(BatchedPlantEnv)
+    with pytest.raises(ValueError, match="polish_the_nameplate"):
+        BatchedPlantEnv.perform_maintenance(env, "polish_the_nameplate", 0)
+    with pytest.raises(ValueError):
+        BatchedPlantEnv.perform_maintenance(env, "oil_change", "FWP-5")
+    with pytest.raises(ValueError):
+        BatchedPlantEnv.perform_maintenance(env, "bearing_replacement", 0, bearing="left_bearing")
+    with pytest.raises(ValueError):
+        _lib.maint_action_index("oil-change")
+    assert _lib.maint_action_index("oil_top_off") == 1 and _lib.maint_action_index(7) == 7
+
+
+def test_maintlog_renders_operator_records_and_leaves_the_automatic_ones(built_lib):
+    from nuclear_sim_amd import _lib, maintlog
+    L = _lib.load()
+    A, P = _lib.MAINT_ACTIONS, _lib.MAINT_PARAMS
+    handlers = [int(L.npb_maint_action_has_handler(a)) for a in range(len(A))]
+    assert maintlog.OPERATOR == 2 and maintlog.EVENT_TYPES[2] == "operator_maintenance" and maintlog.EVENT_TYPES[:2] == ("work_order_created", "work_order_completed")
+    auto = np.zeros(4, dtype=maintlog.EVENT_DTYPE)
+    auto[0] = (10.0, 10.0, 70.0, 1, 3, 1, 1, A.index("oil_top_off"), 0, 3, 0, 0)
+    auto[1] = (70.0, 10.0, 70.0, 1, 3, 0, 1, A.index("oil_top_off"), 1, 0, 0, 0)
+    auto[2] = (5.0, 5.0, 5.0, 0, 1, 1 << 5, 3, A.index("cavitation_analysis"), 0, 5, 0, 0)
+    auto[3] = (70.0, 70.0, 310.0, 1, 4, (1 << 7) | (1 << 8), 0, A.index("bearing_replacement"), 0, 3, 1, 0)
+    ops = np.zeros(2, dtype=maintlog.EVENT_DTYPE)
+    ops[0] = (70.0, 70.0, 70.0, 1, 0, 0, 0, A.index("bearing_replacement"), maintlog.OPERATOR, 0, 3, 0)
+    ops[1] = (35.0, 35.0, 35.0, 0, 0, 0, 2, A.index("oil_change"), maintlog.OPERATOR, 0, 0, 0)
+    before = maintlog.columns(auto, A, P, handlers)
+    both = maintlog.columns(np.concatenate([ops, auto]), A, P, handlers)
+    # the operator records: after the work-order events of their plant and time
+    assert list(both["plant"]) == [0, 0, 1, 1, 1, 1]
+    assert list(both["event_type"]) == ["work_order_created", "operator_maintenance", "work_order_created", "work_order_completed",
+                                        "work_order_created", "operator_maintenance"]
+    op_rows = np.array([1, 5])
+    assert list(both["action_type"][op_rows]) == ["oil_change", "bearing_replacement"]
+    assert list(both["component_id"][op_rows]) == ["FWP-3", "FWP-1"]
+    assert list(both["work_order_id"][op_rows]) == ["", ""] and list(both["priority"][op_rows]) == ["", ""]
+    assert list(both["work_order_type"][op_rows]) == ["", ""]
+    assert list(both["created_date"][op_rows]) == [35.0, 70.0] and list(both["actual_completion_date"][op_rows]) == [35.0, 70.0]
+    assert list(both["bearing"][op_rows]) == ["", "thrust"] and list(both["trigger_parameters"][op_rows]) == ["", ""]
+    assert list(both["has_handler"][op_rows]) == [True, True]
+    assert list(both["title"][op_rows]) == ["Operator: Oil Change - FWP-3", "Operator: Bearing Replacement - FWP-1"]
+    # the automatic records: every column as it is rendered without the operator records beside them
+    keep = np.array([0, 2, 3, 4])
+    for k, v in before.items():
+        w = both[k][keep]
+        assert len(v) == 4 and all((a == b) or (a != a and b != b) for a, b in zip(v, w)), k
+    assert list(before["work_order_id"]) == ["WO-000001", "WO-000003", "WO-000003", "WO-000004"]
+    assert list(before["priority"]) == ["EMERGENCY", "HIGH", "HIGH", "HIGH"]
+    # sort_events: stable for the two kinds it knew (completion first), operator records last within (plant, time)
+    s = maintlog.sort_events(np.concatenate([ops, auto]))
+    assert list(s["kind"]) == [0, 2, 0, 1, 0, 2]
+
+
+def test_fixtures_live_in_their_own_directory():
+    """tests/golden/*.npz is what every replay test parametrises over: the operator fixtures must not be among them"""
+    from golden_util import fixture_names
+    names = operator_fixture_names()
+    assert {"om1_every_handler", "om2_with_automatic_maintenance"} <= set(names)
+    assert not [n for n in fixture_names() if n.startswith("om")]
+    for n in names:
+        assert os.path.getsize(os.path.join(ROOT, "tests", "golden", "operator", n + ".npz")) <= 360 * 1024, n
+
+
+@pytest.mark.parametrize("name", operator_fixture_names())
+def test_fixture_calls_act_where_they_should_and_nowhere_else(name):
+    """every call that has a state effect by construction changes at least one column of the pump's section in the REFERENCE, every
+    call without a handler and every "does nothing" side changes none; success is the dispatcher's"""
+    g = OperatorGolden(name)
+    assert len(g.ops) == len(g.op_before) == len(g.op_after) == len(g.op_expect_change) > 0
+    for j, o in enumerate(g.ops):
+        b, a = g.op_before[j], g.op_after[j]
+        changed = ~((b == a) | (np.isnan(b) & np.isnan(a)))
+        assert changed.any() == bool(g.op_expect_change[j]), (name, j, o, [g.op_labels[q] for q in np.nonzero(changed)[0]])
+        assert o.success == (o.action_name in HANDLERS), (name, j, o)
+        if not o.success or o.action_name in ("oil_analysis", "vibration_analysis"):
+            assert not changed.any(), (name, j, o)
+        assert 0 <= o.step < g.T and 0 <= o.pump < 4
+    # the recorded trajectory continues from the calls: the state recorded for step t is what the calls at t were made on
+    labels = [c[2] for c in g.cols]
+    for j, o in enumerate(g.ops):
+        if j and (g.ops[j - 1].step, g.ops[j - 1].pump) == (o.step, o.pump):
+            continue       # a second call on the same pump between the same two steps starts from the first one's result
+        row = g.state[list(g.state_steps).index(o.step)]
+        for q, m in enumerate(g.op_labels):
+            v = row[labels.index("pump[%d].%s" % (o.pump, m))]
+            assert (v == g.op_before[j, q]) or (np.isnan(v) and np.isnan(g.op_before[j, q])), (name, j, m)
+
+
+def test_om1_visits_every_handler_on_both_sides():
+    g = OperatorGolden("om1_every_handler")
+    A = g.actions
+    seen = {(o.action_name, o.pump == 3) for o in g.ops}
+    for h in HANDLERS:
+        assert (h, False) in seen and (h, True) in seen, "%s: not on a running pump and on the spare" % h
+    status = [c[2] for c in g.cols].index("pump[3].status")
+    assert len(set(g.state[:, status])) == 1, "the spare pump did not stay as it was"
+    assert {o.bearing for o in g.ops if o.action_name == "bearing_replacement"} == {0, 1, 2, 3}
+    assert sum(1 for o in g.ops if not o.success) >= 2
+    # conditional handlers on both sides of their condition; top-off with the default target, an explicit one, one above 100
+    for a in ("bearing_inspection", "impeller_inspection", "motor_inspection", "oil_top_off"):
+        sides = {bool(g.op_expect_change[j]) for j, o in enumerate(g.ops) if o.action_name == a}
+        assert sides == {True, False}, a
+    col = list(g.op_labels).index("oil_level")
+    levels = [(g.op_before[j, col], g.op_after[j, col]) for j, o in enumerate(g.ops) if o.action_name == "lubrication_system_check"]
+    assert any(b < 95.0 for b, _ in levels) and any(b >= 95.0 for b, _ in levels)
+    targets = [o.target_level for o in g.ops if o.action_name == "oil_top_off"]
+    assert any(np.isnan(t) for t in targets) and any(t > 100.0 for t in targets) and any(t <= 100.0 for t in targets)
+    over = [j for j, o in enumerate(g.ops) if o.action_name == "oil_top_off" and o.target_level > 100.0]
+    assert all(g.op_after[j, col] == 100.0 for j in over)
+    twice = [j for j in range(1, len(g.ops)) if (g.ops[j].step, g.ops[j].pump) == (g.ops[j - 1].step, g.ops[j - 1].pump)]
+    assert twice, "no two calls on the same pump between the same two steps"
+
+
+def test_om2_operator_calls_do_not_move_the_automatic_counters():
+    """the operator's top-off keeps FWP-1 from ever reaching its threshold; FWP-4's open order executes although its oil was changed;
+    the counters only ever move with the automatic system's own events"""
+    from work_order_events import events_from_golden
+    from nuclear_sim_amd import _lib
+    g = OperatorGolden("om2_with_automatic_maintenance")
+    labels = [c[2] for c in g.cols]
+    top_off = g.actions.index("oil_top_off")
+    wo = lambda k: g.state[:, labels.index("mpump[%d].wo_order[%d]" % (k, top_off))]
+    (change,) = [o for o in g.ops if o.action_name == "oil_change"]
+    assert change.pump == 3 and wo(3)[change.step] > 0, "no open automatic order at the operator's oil change"
+    assert (wo(3)[change.step + 1:] == 0).any(), "the open order never executes"
+    (top,) = [o for o in g.ops if o.action_name == "oil_top_off"]
+    assert top.pump == 0 and (wo(0) == 0).all() and (wo(1) > 0).any()
+    ev = events_from_golden(g, _lib.MAINT_PARAMS)
+    created = g.state[:, labels.index("maint.work_orders_created")]; performed = g.state[:, labels.index("maint.maintenance_actions_performed")]
+    for s in range(1, len(created)):
+        t = s * float(g.meta["dt"])
+        assert created[s] - created[s - 1] == ((ev["kind"] == 0) & (ev["time"] == t)).sum()
+        assert performed[s] - performed[s - 1] == ((ev["kind"] == 1) & (ev["time"] == t)).sum()
+    assert performed[-1] >= 2 and created[-1] >= 2
