@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define NPB_VERSION 147 /* 0.1.4.7: npb_perform_maintenance, NPB_MAINT_EVENT_OPERATOR (maintenance a caller orders, carried out on the device between two steps); 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
+#define NPB_VERSION 148 /* 0.1.4.8: npb_perform_component_maintenance, npb_component_* catalog queries, NPB_MAINT_EVENT_OPERATOR_COMPONENT (maintenance of steam generators, condenser and ejectors a caller orders); 0.1.4.7: npb_perform_maintenance, NPB_MAINT_EVENT_OPERATOR (maintenance a caller orders, carried out on the device between two steps); 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
 #ifndef NPB_API
 #define NPB_API __attribute__((visibility("default")))
 #endif
@@ -223,10 +223,41 @@ NPB_API size_t npb_maint_event_bytes(void);   /* sizeof(npb_maint_event_t) */
  * the maint.* / mpump.* columns, the count buffer (npb_set_maintenance_count_buffer) and the diagnostics rows do not move: a direct call
  * bypasses AutoMaintenanceSystem in the reference too.  Works with params.maint_enabled 0 or 1, in every mode and storage type.  With a
  * maintenance log set (npb_set_maintenance_log) every successful order appends one NPB_MAINT_EVENT_OPERATOR record.  Not offered: work
- * orders created by the operator (queued, delayed, counted), and maintenance of steam generators, turbine, condenser.
+ * orders created by the operator (queued, delayed, counted), and maintenance of the turbine (steam generators and condenser:
+ * npb_perform_component_maintenance).
  * NPB_EINVAL for action = NULL or pump = NULL. */
 NPB_API int npb_perform_maintenance(NpbHandle *h, const int32_t *action, const int32_t *pump, const int32_t *bearing,
                                     const double *target_level, uint8_t *success, void *stream);
+/* The same for the other components whose direct-call handlers act on carried state: perform_maintenance(maintenance_type, **kwargs) of a
+ * steam generator (steam_generator/steam_generator.py:1092-1326), the steam-generator system (steam_generator/enhanced_physics.py
+ * :1062-1191), the condenser (condenser/physics.py:1188-1372, the definition the class ends up with) and a steam-jet ejector
+ * (condenser/vacuum_pump.py:338-468), called by the USER between two steps.  Device pointers to n_plants elements; asynchronous.
+ *   action   index of the COMPONENT catalog (NPB_CA_*, include/npb_maint.h; npb_component_action_name / _kind), -1 = nothing for this
+ *            plant.  The index names the component kind, so one column may mix kinds.
+ *   unit     NULL = 0: the generator 0..2 or the ejector 0..1 (SJE-001, SJE-002); ignored by system and condenser actions.  A call the
+ *            reference's system delegates (kwarg sg_index) is the generator's action on unit sg_index.
+ *   option   NULL = NPB_CLEANING_DEFAULT: the cleaning_type kwarg as NPB_CLEANING_*, read by the scale cleanings, condenser_tube_cleaning
+ *            and vacuum_ejector_cleaning (each with its own set of named types; any other value is the handler's "else" branch)
+ *   amount   NULL = 10: the tubes_to_plug kwarg.  Carried for condenser_tube_plugging, which is NOT in the catalog (the reference's
+ *            handler raises); no catalogued handler reads it.
+ *   success  may be NULL; 1 where the reference's result says success -- every catalogued action on a unit that exists -- else 0, plants
+ *            with action -1 included.  An index outside the catalog or a unit that does not exist: success 0, state untouched, no error
+ *            code.  In a mode that does not step a component (NPB_MODE_PRIMARY: none of them, the reference then has no secondary_physics
+ *            to call; NPB_MODE_PRIMARY_SG: condenser and ejectors) its actions give success 0.
+ * Only the sections the action touches change -- one sg instance; all three for the system's actions, or sec for its coordination; cond,
+ * with chem[1] for condenser_water_treatment -- and a plant without a successful order keeps its exact bits.  water_chemistry_adjustment
+ * resets the steam-generator system's own chemistry, which is not carried (npb_params.h sgchem_*): success 1, nothing moves.  The
+ * work-order queue, maint.* / mpump.*, the count buffer and the diagnostics rows do not move; params.maint_enabled may be 0 or 1.  With
+ * a maintenance log set every successful order appends one NPB_MAINT_EVENT_OPERATOR_COMPONENT record (action = catalog index, pump byte =
+ * unit).  Not offered: turbine maintenance, work orders for these components.
+ * NPB_EINVAL for action = NULL. */
+NPB_API int npb_perform_component_maintenance(NpbHandle *h, const int32_t *action, const int32_t *unit, const int32_t *option,
+                                              const double *amount, uint8_t *success, void *stream);
+/* the COMPONENT catalog by index: type string, component kind (NPB_COMPONENT_*; -1 outside the catalog), and per kind its name */
+NPB_API int npb_component_num_actions(void);
+NPB_API const char *npb_component_action_name(int a);
+NPB_API int npb_component_action_kind(int a);
+NPB_API const char *npb_component_kind_name(int kind);
 
 /* re-initialise plants to the construction-time state; mask (device, uint8[n], NULL = all) selects plants.
  * Stands in for constructing a fresh simulator (the data-gen runner's episode start,

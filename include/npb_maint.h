@@ -13,6 +13,8 @@
  *    entry here.
  *  - the ACTION catalog: every action those thresholds, the orchestrator's promotions (maintenance_orchestrator.py
  *    :469-524) and the lubrication system's dispatcher (pump_lubrication.py:625-674) can produce.
+ *  - the COMPONENT catalog: the maintenance types a user can call directly on steam generators, condenser and ejectors
+ *    (npb_perform_component_maintenance); no threshold, work order or table row names them.
  *  - the threshold TABLE a handle carries (npb_set_maintenance_table): per catalogued parameter its rank in the
  *    configuration's dict order (the scan order; -1 = absent), threshold, comparison, action, priority, cooldown and,
  *    for bearing_replacement, which bearing.  npb_maint_table_default() is the table of the data-gen action-test
@@ -85,6 +87,64 @@ enum {
 #undef NPB__X
   NPB_MA_COUNT_
 };
+
+/* COMPONENT catalog (npb_perform_component_maintenance): the maintenance types a user can call directly on a steam generator, the
+ * steam-generator system, the condenser and a steam-jet ejector -- X(KIND, id, "maintenance type string").  The index names the handler:
+ * a type string may occur under several kinds ("routine_maintenance").  Dispatchers: SteamGenerator.perform_maintenance
+ * steam_generator/steam_generator.py:1092-1326, EnhancedSteamGeneratorPhysics.perform_maintenance steam_generator/enhanced_physics.py
+ * :1062-1191, EnhancedCondenserPhysics.perform_maintenance condenser/physics.py:1188-1372, SteamJetEjector.perform_maintenance
+ * condenser/vacuum_pump.py:338-362 ("general" = its fall-through for every other type); restated in
+ * nuclear_sim_amd/csrc/npd_component_maintenance.h.  Every entry has a handler; the inspections and tests among them read state only.
+ * Not in the catalog because the live reference raises instead of returning a result: a generator's eddy_current_testing (KeyError
+ * 'operating_years', steam_generator.py:1224) and condenser_tube_plugging (AttributeError: CondenserConfig has no tube_count,
+ * physics.py:1245). */
+#define NPB_COMPONENT_NACT 31
+enum { NPB_COMPONENT_SG = 0, NPB_COMPONENT_SGSYS = 1, NPB_COMPONENT_COND = 2, NPB_COMPONENT_EJECTOR = 3, NPB_COMPONENT_NKIND = 4 };
+#define NPB_COMPONENT_ACTIONS(X) \
+  X(SG, TSP_CHEMICAL_CLEANING,              "tsp_chemical_cleaning") \
+  X(SG, TSP_MECHANICAL_CLEANING,            "tsp_mechanical_cleaning") \
+  X(SG, TUBE_BUNDLE_INSPECTION,             "tube_bundle_inspection") \
+  X(SG, MOISTURE_SEPARATOR_MAINTENANCE,     "moisture_separator_maintenance") \
+  X(SG, SCALE_REMOVAL,                      "scale_removal") \
+  X(SG, WATER_CHEMISTRY_ADJUSTMENT,         "water_chemistry_adjustment") \
+  X(SG, SECONDARY_SIDE_CLEANING,            "secondary_side_cleaning") \
+  X(SG, TSP_INSPECTION,                     "tsp_inspection") \
+  X(SG, TSP_FLOW_TEST,                      "tsp_flow_test") \
+  X(SG, TUBE_INTERIOR_INSPECTION,           "tube_interior_inspection") \
+  X(SG, TUBE_INTERIOR_SCALE_CLEANING,       "tube_interior_scale_cleaning") \
+  X(SG, TUBE_INTERIOR_EDDY_CURRENT_TESTING, "tube_interior_eddy_current_testing") \
+  X(SG, PRIMARY_CHEMISTRY_OPTIMIZATION,     "primary_chemistry_optimization") \
+  X(SG, PRIMARY_SCALE_CLEANING,             "primary_scale_cleaning") \
+  X(SG, TUBE_EDDY_CURRENT_TESTING,          "tube_eddy_current_testing") \
+  X(SG, ROUTINE_MAINTENANCE,                "routine_maintenance") \
+  X(SGSYS, SYSTEM_COORDINATION_MAINTENANCE,  "system_coordination_maintenance") \
+  X(SGSYS, SYSTEM_STEAM_QUALITY_MAINTENANCE, "system_steam_quality_maintenance") \
+  X(SGSYS, LOAD_BALANCING_MAINTENANCE,       "load_balancing_maintenance") \
+  X(SGSYS, ROUTINE_MAINTENANCE,              "routine_maintenance") \
+  X(COND, CONDENSER_TUBE_CLEANING,          "condenser_tube_cleaning") \
+  X(COND, CONDENSER_CHEMICAL_CLEANING,      "condenser_chemical_cleaning") \
+  X(COND, CONDENSER_WATER_TREATMENT,        "condenser_water_treatment") \
+  X(COND, VACUUM_SYSTEM_TEST,               "vacuum_system_test") \
+  X(COND, VACUUM_LEAK_DETECTION,            "vacuum_leak_detection") \
+  X(EJECTOR, VACUUM_EJECTOR_CLEANING,            "vacuum_ejector_cleaning") \
+  X(EJECTOR, VACUUM_EJECTOR_NOZZLE_REPLACEMENT,  "vacuum_ejector_nozzle_replacement") \
+  X(EJECTOR, VACUUM_EJECTOR_INSPECTION,          "vacuum_ejector_inspection") \
+  X(EJECTOR, VACUUM_EJECTOR_MECHANICAL_CLEANING, "vacuum_ejector_mechanical_cleaning") \
+  X(EJECTOR, ROUTINE_MAINTENANCE,                "routine_maintenance") \
+  X(EJECTOR, GENERAL,                            "general")
+enum {
+#define NPB__X(kind, id, name) NPB_CA_##kind##_##id,
+  NPB_COMPONENT_ACTIONS(NPB__X)
+#undef NPB__X
+  NPB_CA_COUNT_
+};
+/* units per kind: generators, -, -, ejectors */
+#define NPB_COMPONENT_UNITS(kind) ((kind) == NPB_COMPONENT_SG ? 3 : (kind) == NPB_COMPONENT_EJECTOR ? 2 : 1)
+/* the cleaning_type kwarg as the option column carries it: DEFAULT = the handler's default argument ("chemical" in all three handlers that
+ * take one), OTHER = any string the handler does not name (its "else" branch) */
+enum { NPB_CLEANING_DEFAULT = 0, NPB_CLEANING_CHEMICAL = 1, NPB_CLEANING_MECHANICAL = 2, NPB_CLEANING_HYDROBLAST = 3, NPB_CLEANING_REPLACEMENT = 4,
+       NPB_CLEANING_OTHER = 5 };
+
 enum { NPB_CMP_GREATER_THAN = 0, NPB_CMP_LESS_THAN = 1, NPB_CMP_GREATER_EQUAL = 2, NPB_CMP_LESS_EQUAL = 3, NPB_CMP_EQUALS = 4, NPB_CMP_NOT_EQUALS = 5 };
 enum { NPB_PRIO_LOW = 1, NPB_PRIO_MEDIUM = 2, NPB_PRIO_HIGH = 3, NPB_PRIO_CRITICAL = 4, NPB_PRIO_EMERGENCY = 5 };
 enum { NPB_BEARING_ALL = 0, NPB_BEARING_MOTOR = 1, NPB_BEARING_PUMP = 2, NPB_BEARING_THRUST = 3 };
@@ -128,7 +188,9 @@ static inline void npb_maint_table_default(npb_maint_table_t *t) {
  * writes them out as *_work_orders.csv / *_maintenance_actions.csv (maintenance_scenario_runner.py:1071-1231). */
 /* NPB_MAINT_EVENT_OPERATOR: an action a caller ordered through npb_perform_maintenance and the dispatcher carried out at once (no work
  * order behind it): order = 0, created = planned_start = time = the plant's clock at the call, trigger = priority = 0 */
-enum { NPB_MAINT_EVENT_CREATED = 0, NPB_MAINT_EVENT_COMPLETED = 1, NPB_MAINT_EVENT_OPERATOR = 2 };
+/* NPB_MAINT_EVENT_OPERATOR_COMPONENT: the same through npb_perform_component_maintenance: action = index of the COMPONENT catalog
+ * (NPB_CA_*), the pump byte = the unit (generator 0..2, ejector 0..1; 0 for the system and the condenser), the rest as for OPERATOR */
+enum { NPB_MAINT_EVENT_CREATED = 0, NPB_MAINT_EVENT_COMPLETED = 1, NPB_MAINT_EVENT_OPERATOR = 2, NPB_MAINT_EVENT_OPERATOR_COMPONENT = 3 };
 typedef struct npb_maint_event_t {
   double time;            /* the rule's clock: prim.sim_time of the step [min], fp64 under either storage type */
   double created;         /* the order's creation time [min]; for a completion mpump.last_trigger_time[action], which is the open
@@ -137,9 +199,9 @@ typedef struct npb_maint_event_t {
   int32_t plant;          /* the plant's index within the handle */
   int32_t order;          /* the per-plant creation number n (mpump.wo_order): the reference's work-order id WO-%06d */
   uint16_t trigger;       /* creation: bit q = catalog parameter q whose last_violation_time this scan stamped; 0 for a completion */
-  uint8_t pump;           /* 0..3 = FWP-1..4 */
-  uint8_t action;         /* action catalog index (NPB_MA_*) */
-  uint8_t kind;           /* NPB_MAINT_EVENT_CREATED | NPB_MAINT_EVENT_COMPLETED | NPB_MAINT_EVENT_OPERATOR */
+  uint8_t pump;           /* 0..3 = FWP-1..4; OPERATOR_COMPONENT: the unit */
+  uint8_t action;         /* action catalog index (NPB_MA_*); OPERATOR_COMPONENT: component catalog index (NPB_CA_*) */
+  uint8_t kind;           /* NPB_MAINT_EVENT_CREATED | _COMPLETED | _OPERATOR | _OPERATOR_COMPONENT */
   uint8_t priority;       /* creation: NPB_PRIO_* of the order; 0 for a completion (the state does not keep an order's priority) */
   uint8_t bearing;        /* bearing_replacement: NPB_BEARING_* of the order (mpump.wo_bearing); else 0 */
   uint8_t reserved;
@@ -147,7 +209,8 @@ typedef struct npb_maint_event_t {
 #define NPB_MAINT_EVENT_BYTES 40
 #ifdef __cplusplus
 static_assert(sizeof(npb_maint_event_t) == NPB_MAINT_EVENT_BYTES, "npb_maint_event_t layout");
-static_assert(NPB_MAINT_NPARAM <= 16 && NPB_MAINT_NACT <= 255, "npb_maint_event_t field widths");
+static_assert(NPB_MAINT_NPARAM <= 16 && NPB_MAINT_NACT <= 255 && NPB_COMPONENT_NACT <= 255, "npb_maint_event_t field widths");
+static_assert(NPB_CA_COUNT_ == NPB_COMPONENT_NACT, "NPB_COMPONENT_NACT");
 #else
 _Static_assert(sizeof(npb_maint_event_t) == NPB_MAINT_EVENT_BYTES, "npb_maint_event_t layout");
 #endif

@@ -126,6 +126,62 @@ def maint_action_index(action) -> int:
     return int(action)
 
 
+# include/npb_maint.h NPB_COMPONENT_ACTIONS: the catalog of npb_perform_component_maintenance, (component kind, maintenance type) per
+# index -- a type string may occur under several kinds ("routine_maintenance"), the index names one handler; load() holds it
+# against the library's own catalog
+COMPONENT_KINDS = ("steam_generator", "steam_generator_system", "condenser", "ejector")
+COMPONENT_ACTIONS = tuple(
+    [("steam_generator", a) for a in (
+        "tsp_chemical_cleaning", "tsp_mechanical_cleaning", "tube_bundle_inspection", "moisture_separator_maintenance", "scale_removal",
+        "water_chemistry_adjustment", "secondary_side_cleaning", "tsp_inspection", "tsp_flow_test",
+        "tube_interior_inspection", "tube_interior_scale_cleaning", "tube_interior_eddy_current_testing", "primary_chemistry_optimization",
+        "primary_scale_cleaning", "tube_eddy_current_testing", "routine_maintenance")] +
+    [("steam_generator_system", a) for a in (
+        "system_coordination_maintenance", "system_steam_quality_maintenance", "load_balancing_maintenance", "routine_maintenance")] +
+    [("condenser", a) for a in (
+        "condenser_tube_cleaning", "condenser_chemical_cleaning", "condenser_water_treatment", "vacuum_system_test", "vacuum_leak_detection")] +
+    [("ejector", a) for a in (
+        "vacuum_ejector_cleaning", "vacuum_ejector_nozzle_replacement", "vacuum_ejector_inspection", "vacuum_ejector_mechanical_cleaning",
+        "routine_maintenance", "general")])
+COMPONENT_UNITS = {"steam_generator": 3, "steam_generator_system": 1, "condenser": 1, "ejector": 2}
+EJECTOR_IDS = ("SJE-001", "SJE-002")
+# the cleaning_type kwarg as npb_perform_component_maintenance's option column carries it (NPB_CLEANING_*); a string that is none of
+# these is the handlers' "anything else" branch
+CLEANING_TYPES = {None: 0, "chemical": 1, "mechanical": 2, "hydroblast": 3, "replacement": 4}
+CLEANING_OTHER = 5
+# handlers of the reference that are NOT offered, with the reason (DESIGN.md "Operator-ordered maintenance of steam generators and
+# condenser"): refused by name, with this message, apart from an unknown name
+COMPONENT_ACTIONS_NOT_OFFERED = {
+    ("steam_generator", "eddy_current_testing"):
+        "the reference's handler raises KeyError ('operating_years' is not a key of TSPFoulingModel.get_state_dict, "
+        "steam_generator/steam_generator.py:1224): there is no result to restate",
+    ("condenser", "condenser_tube_plugging"):
+        "the reference's handler raises AttributeError ('CondenserConfig' object has no attribute 'tube_count', condenser/physics.py:1245) "
+        "after it has moved the tube counts: there is no result to restate",
+}
+
+
+def component_action_index(component, action) -> int:
+    """(component kind, maintenance type name or index) -> index into COMPONENT_ACTIONS; ValueError for an unknown kind or name, and for
+    a handler that is not offered (host only, no library needed).  An index is taken as it is."""
+    if component not in COMPONENT_KINDS:
+        raise ValueError("unknown component %r: one of %r" % (component, COMPONENT_KINDS))
+    if not isinstance(action, str):
+        return int(action)
+    if (component, action) in COMPONENT_ACTIONS_NOT_OFFERED:
+        raise ValueError("%s maintenance %r is not offered on the device: %s" % (component, action, COMPONENT_ACTIONS_NOT_OFFERED[(component, action)]))
+    if (component, action) not in COMPONENT_ACTIONS:
+        raise ValueError("unknown %s maintenance %r: not in the component catalog (include/npb_maint.h)" % (component, action))
+    return COMPONENT_ACTIONS.index((component, action))
+
+
+def cleaning_type_index(cleaning_type) -> int:
+    """the reference's cleaning_type kwarg -> NPB_CLEANING_*; an index is taken as it is"""
+    if cleaning_type is None or isinstance(cleaning_type, str):
+        return CLEANING_TYPES.get(cleaning_type, CLEANING_OTHER)
+    return int(cleaning_type)
+
+
 def maint_table_from_thresholds(thresholds: dict) -> "NpbMaintTable":
     """The reference's thresholds dict of a feedwater pump (maintenance_system.component_configs.feedwater.thresholds of
     the configuration, = StateManager.maintenance_thresholds['FWP-1'], in ITS order) -> table.  Names that do not
@@ -233,6 +289,17 @@ def load():
         L.npb_maint_action_has_handler.argtypes = [ci]
     if hasattr(L, "npb_perform_maintenance"):     # ABI 147: maintenance the caller orders
         L.npb_perform_maintenance.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "npb_perform_component_maintenance"):     # ABI 148: maintenance of steam generators, condenser and ejectors the caller orders
+        L.npb_perform_component_maintenance.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.npb_component_action_name.restype = ctypes.c_char_p
+        L.npb_component_action_name.argtypes = [ci]
+        L.npb_component_kind_name.restype = ctypes.c_char_p
+        L.npb_component_kind_name.argtypes = [ci]
+        L.npb_component_action_kind.argtypes = [ci]
+        catalog = tuple((L.npb_component_kind_name(L.npb_component_action_kind(a)).decode(), L.npb_component_action_name(a).decode())
+                        for a in range(L.npb_component_num_actions()))
+        if catalog != COMPONENT_ACTIONS:
+            raise NpbError("libnpb.so's component catalog is not this binding's COMPONENT_ACTIONS: rebuild")
     if hasattr(L, "npb_noise_seed"):     # ABI 145: heat-source noise streams on the device
         L.npb_noise_seed.argtypes = [vp, vp, vp]
         L.npb_noise_fill.argtypes = [vp, ci, vp, vp]

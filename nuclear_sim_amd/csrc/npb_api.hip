@@ -194,6 +194,18 @@ const char *npb_maint_action_name(int a) { return a >= 0 && a < NPB_MAINT_NACT ?
 int npb_maint_action_has_handler(int a) { return a >= 0 && a < NPB_MAINT_NACT ? g_maint_actions[a].handler : 0; }
 static_assert(sizeof(g_maint_params) / sizeof(g_maint_params[0]) == NPB_MAINT_NPARAM, "parameter catalog");
 static_assert(sizeof(g_maint_actions) / sizeof(g_maint_actions[0]) == NPB_MAINT_NACT, "action catalog");
+static const struct { const char *name; int kind; } g_component_actions[] = {
+#define NPB__X(kind, id, name) {name, NPB_COMPONENT_##kind},
+  NPB_COMPONENT_ACTIONS(NPB__X)
+#undef NPB__X
+};
+static const char *const g_component_kinds[] = {"steam_generator", "steam_generator_system", "condenser", "ejector"};
+static_assert(sizeof(g_component_actions) / sizeof(g_component_actions[0]) == NPB_COMPONENT_NACT, "component catalog");
+static_assert(sizeof(g_component_kinds) / sizeof(g_component_kinds[0]) == NPB_COMPONENT_NKIND, "component kinds");
+int npb_component_num_actions(void) { return NPB_COMPONENT_NACT; }
+const char *npb_component_action_name(int a) { return a >= 0 && a < NPB_COMPONENT_NACT ? g_component_actions[a].name : nullptr; }
+int npb_component_action_kind(int a) { return a >= 0 && a < NPB_COMPONENT_NACT ? g_component_actions[a].kind : -1; }
+const char *npb_component_kind_name(int kind) { return kind >= 0 && kind < NPB_COMPONENT_NKIND ? g_component_kinds[kind] : nullptr; }
 size_t npb_state_bytes(void) { return (size_t)NPB_TOTAL_COL64 * 8; }
 /* carried fp64 members are read and written, int32 members too, output members are only written (as float);
  * the maint.* section belongs to the maintenance kernel */
@@ -370,6 +382,22 @@ int npb_perform_maintenance(NpbHandle *h, const int32_t *action, const int32_t *
    * depend on the rule's constants having been uploaded (they are only with params.maint_enabled). */
   h->K->operator_maint(h->n_plants, NPB_N(h), h->f64, action, pump, bearing, target_level, success, h->maint_log, h->maint_log_cursor,
                        h->maint_log_capacity, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+
+int npb_perform_component_maintenance(NpbHandle *h, const int32_t *action, const int32_t *unit, const int32_t *option, const double *amount,
+                                      uint8_t *success, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!action) return fail(h, NPB_EINVAL, "npb_perform_component_maintenance: the action column must not be NULL");
+  NPB_USE_DEVICE(h);
+  /* the components a mode steps are the ones it can service: the reference without its secondary side has no object to call
+   * (sim.secondary_physics is None), and primary + steam generators steps no condenser.  maint_cache_stale is left alone, as in
+   * npb_perform_maintenance: no handler here writes a pump, a stamp or the table. */
+  const unsigned kinds = h->params.mode == NPB_MODE_FULL ? 0xfu
+                       : h->params.mode == NPB_MODE_PRIMARY_SG ? (1u << NPB_COMPONENT_SG) | (1u << NPB_COMPONENT_SGSYS) : 0u;
+  h->K->operator_component_maint(h->n_plants, NPB_N(h), h->f64, action, unit, option, amount, success, kinds, h->maint_log, h->maint_log_cursor,
+                                 h->maint_log_capacity, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }

@@ -48,6 +48,11 @@ typedef struct {
   void (*operator_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *pump, const int32_t *bearing,
                          const double *target_level, uint8_t *success, npb_maint_event_t *log_records, uint32_t *log_cursor, int log_capacity,
                          hipStream_t stream);
+  /* npb_perform_component_maintenance: the caller's [n_plants] order columns (unit / option / amount / success may be NULL), the component
+   * kinds the handle's mode carries (bit k = NPB_COMPONENT_* k) and the maintenance event log's descriptor */
+  void (*operator_component_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *unit, const int32_t *option,
+                                   const double *amount, uint8_t *success, unsigned kinds, npb_maint_event_t *log_records, uint32_t *log_cursor,
+                                   int log_capacity, hipStream_t stream);
 } npb_launchers_t;
 extern npb_launchers_t npb_launch_table, npb32_launch_table;
 /* the same for either storage type */

@@ -49,6 +49,7 @@ extern "C" __attribute__((visibility("default"))) int npb_debug_set_stamp_buffer
 #include "npd_condenser.h"
 #include "npd_ph.h"
 #include "npd_maintenance.h"
+#include "npd_component_maintenance.h"
 #include "npd_init.h"
 #include "npd_reset.h"
 #include "npd_step.h"
@@ -914,6 +915,89 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_operator_maint_kernel(npd_operat
   }
 }
 
+/* operator-ordered maintenance of steam generators and condenser (npb_perform_component_maintenance): perform_maintenance(type, **kwargs)
+ * of a steam generator, the steam-generator system, the condenser or a steam-jet ejector, called by the user between two steps
+ * (npd_component_maintenance.h), for every plant whose lane of the caller's columns orders one.  The design of the pump kernel above:
+ * one wave per 64 plants reads its 64 orders, writes success and leaves when none can succeed; a wave that stays visits the component
+ * kinds and units somebody in it ordered, and only the ordering lanes load, change and store the sections their action touches --
+ * one generator; the three generators one after the other (a system action) or the system's flags alone; the condenser, with its
+ * chemistry for the water treatment.  Nothing is stored to a plant without a successful order. */
+struct npd_component_orders_t {
+  const int32_t *action, *unit, *option;      /* the caller's [n_plants] columns; unit NULL = 0, option NULL = NPB_CLEANING_DEFAULT */
+  const double *amount;                       /* [n_plants] or NULL: tubes_to_plug; no handler of the catalog reads it */
+  uint8_t *success;                           /* [n_plants] or NULL */
+  int n_plants;
+  unsigned kinds;                             /* bit k: the handle's mode carries component kind k (NPB_COMPONENT_*) */
+};
+__global__ __launch_bounds__(NPB_WAVE) void npb_operator_component_maint_kernel(npd_component_orders_t O, npd_maint_log_t L, size_t N, npd_real_t *__restrict__ f64) {
+  const size_t p = (size_t)blockIdx.x * NPB_WAVE + threadIdx.x;
+  const bool live = p < (size_t)O.n_plants;      /* the columns have n_plants elements, not the pitch */
+  int action = -1, unit = 0;
+  if (live) { action = O.action[p]; if (action >= 0 && O.unit) unit = O.unit[p]; }
+  const int kind = npd_component_kind(action);
+  if (kind == NPB_COMPONENT_SGSYS || kind == NPB_COMPONENT_COND) unit = 0;      /* one of each: the unit is ignored */
+  /* "Unknown maintenance type": an index outside the catalog; a generator or ejector that is none; a component the mode does not carry */
+  const bool ok = kind >= 0 && ((O.kinds >> kind) & 1u) && unit >= 0 && unit < NPB_COMPONENT_UNITS(kind);
+  if (live && O.success) O.success[p] = ok ? 1 : 0;
+  if (!__any(ok)) return;
+  int option = NPB_CLEANING_DEFAULT;
+  if (ok && O.option) option = O.option[p];
+  NPD_SEGMENT(f64, N, (size_t)blockIdx.x * NPB_WAVE);
+  const bool on_sg = ok && kind == NPB_COMPONENT_SG;
+  const bool on_sgsys = ok && kind == NPB_COMPONENT_SGSYS;
+  const bool on_sgs = on_sgsys && npd_sgsys_touches_generators(action);
+  if (__any(on_sg || on_sgs)) {
+    int cleaned = 0;
+#pragma unroll 1
+    for (int k = 0; k < NPB_NUM_SG; k++) {
+      const bool mine = (on_sg && unit == k) || on_sgs;
+      if (!__any(mine)) continue;
+      if (mine) {
+        npb_sg_t g;
+        NPD_LOAD(SG, npb_sg_t, g, k);
+        if (on_sg) npd_sg_maintenance(&g, action, option);
+        else npd_sgsys_maintenance_sg(&g, action, &cleaned);
+        NPD_STORE(SG, npb_sg_t, g, k);
+      }
+    }
+  }
+  if (__any(on_sgsys && !on_sgs)) {
+    if (on_sgsys && !on_sgs) {
+      npb_sec_t sec;
+      NPD_LOAD(SEC, npb_sec_t, sec, 0);
+      npd_sgsys_maintenance_sec(&sec, action);
+      NPD_STORE(SEC, npb_sec_t, sec, 0);
+    }
+  }
+  const bool on_cond = ok && (kind == NPB_COMPONENT_COND || kind == NPB_COMPONENT_EJECTOR);
+  if (__any(on_cond)) {
+    if (on_cond) {
+      npb_cond_t cd;
+      NPD_LOAD(COND, npb_cond_t, cd, 0);
+      if (kind == NPB_COMPONENT_EJECTOR) {
+#pragma unroll
+        for (int e = 0; e < NPB_NUM_EJECTORS; e++)      /* a constant index: the section stays in registers */
+          if (unit == e) npd_ejector_maintenance(&cd, e, action, option);
+      } else if (npd_cond_touches_chemistry(action)) {
+        npb_chem_t ch;      /* chem[1]: the condenser-owned WaterChemistry (include/npb_fields.h) */
+        NPD_LOAD(CHEM, npb_chem_t, ch, 1);
+        npd_cond_maintenance(&cd, &ch, action, option);
+        NPD_STORE(CHEM, npb_chem_t, ch, 1);
+      } else {
+        npd_cond_maintenance(&cd, nullptr, action, option);
+      }
+      NPD_STORE(COND, npb_cond_t, cd, 0);
+    }
+  }
+  if (L.cursor) {      /* the event log (npb_set_maintenance_log): one record per successful order, one atomic per wave */
+    const double t = NPD_F64_COL(PRIM, npb_prim_t, sim_time, 0);
+    npb_maint_event_t ev = {};
+    ev.time = t; ev.created = t; ev.planned_start = t; ev.plant = (int32_t)p;
+    ev.pump = (uint8_t)unit; ev.action = (uint8_t)action; ev.kind = NPB_MAINT_EVENT_OPERATOR_COMPONENT;
+    npd_maint_log(L, ok, ev);
+  }
+}
+
 #ifndef NPB_BUILD_F32
 /* calibration aid for the HBM traffic counters: reads every arena column and writes it back unchanged,
  * with exactly the access shape of the step kernel (8 B per lane, one 512-B line per wave and column),
@@ -1152,11 +1236,21 @@ static void NPB_LAUNCHER(operator_maint)(int n_plants, size_t npad, void *arena,
   L.records = log_records; L.cursor = log_records ? log_cursor : nullptr; L.capacity = log_records ? log_capacity : 0;
   hipLaunchKernelGGL(npb_operator_maint_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, O, L, npad, (npd_real_t *)arena);
 }
+/* npb_perform_component_maintenance: the caller's order columns; kinds = the component kinds the handle's mode carries; log_* as above */
+static void NPB_LAUNCHER(operator_component_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *unit, const int32_t *option,
+                                                   const double *amount, uint8_t *success, unsigned kinds, npb_maint_event_t *log_records,
+                                                   uint32_t *log_cursor, int log_capacity, hipStream_t stream) {
+  npd_component_orders_t O;
+  O.action = action; O.unit = unit; O.option = option; O.amount = amount; O.success = success; O.n_plants = n_plants; O.kinds = kinds;
+  npd_maint_log_t L;
+  L.records = log_records; L.cursor = log_records ? log_cursor : nullptr; L.capacity = log_records ? log_capacity : 0;
+  hipLaunchKernelGGL(npb_operator_component_maint_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, O, L, npad, (npd_real_t *)arena);
+}
 /* not const: clang emits a namespace-scope const into the device code too, where these host functions do not exist */
 extern "C" npb_launchers_t NPB_LAUNCHER(table) = {
   NPB_LAUNCHER(step), NPB_LAUNCHER(maint), NPB_LAUNCHER(observe), NPB_LAUNCHER(init), NPB_LAUNCHER(reset),
   NPB_LAUNCHER(field_get), NPB_LAUNCHER(field_set), NPB_LAUNCHER(gather), NPB_LAUNCHER(restore), NPB_LAUNCHER(episode),
-  NPB_LAUNCHER(operator_maint),
+  NPB_LAUNCHER(operator_maint), NPB_LAUNCHER(operator_component_maint),
 };
 #ifndef NPB_BUILD_F32
 /* npb_reset / npb_reset_reference / npb_restore: the episode counters (len, ret) and the carried start entries (start: -1, not from

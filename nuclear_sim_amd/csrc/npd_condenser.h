@@ -35,6 +35,14 @@ NPD_FN double npd_cond_lmtd(double d1, double d2) { /* physics.py:623-638 */
   return (d1 + d2) / 2.0;
 }
 
+/* AdvancedFoulingModel.calculate_total_fouling_resistance  physics.py:295-322 */
+NPD_FN double npd_cond_total_fouling_resistance(const npb_cond_t *cd) {
+  double total_resistance = (cd->biofouling_thickness / 1000.0) / 0.5 + (cd->scale_thickness / 1000.0) / 2.0 +
+                            (cd->corrosion_product_thickness / 1000.0) / 1.0;
+  total_resistance *= cd->fouling_distribution_factor;
+  return total_resistance;
+}
+
 typedef struct npd_condenser_result_t {
   double heat_rejection_rate, condenser_pressure, condensate_temperature;
 } npd_condenser_result_t;
@@ -100,10 +108,7 @@ NPD_FN void npd_condenser_update(npb_cond_t *cd, npb_chem_t *chem, double steam_
     cd->scale_thickness += scale_increase;
     cd->corrosion_product_thickness += corrosion_increase;
     cd->time_since_cleaning += dt;
-    double total_resistance = (cd->biofouling_thickness / 1000.0) / 0.5 + (cd->scale_thickness / 1000.0) / 2.0 +
-                              (cd->corrosion_product_thickness / 1000.0) / 1.0;
-    total_resistance *= cd->fouling_distribution_factor;
-    cd->total_fouling_resistance = total_resistance;
+    cd->total_fouling_resistance = npd_cond_total_fouling_resistance(cd);
     cd->fouling_distribution_factor = npd_pymin(1.5, 1.0 + cd->time_since_cleaning / 8760.0);
   }
 

@@ -212,6 +212,9 @@ class BatchedPlantEnv:
     Operator-ordered maintenance: ``perform_maintenance(action, pump, mask=...)`` is the reference's
     ``pump.perform_maintenance(type, **kwargs)`` for the whole batch, between two steps, on the device (npb_perform_maintenance): the
     caller decides when a feedwater pump is serviced, with the automatic maintenance off or beside it.
+    ``perform_component_maintenance(component, action, unit=..., mask=...)`` is the same for the steam generators, the
+    steam-generator system, the condenser and its steam-jet ejectors (npb_perform_component_maintenance): TSP and scale cleaning,
+    moisture-separator work, condenser cleaning and water treatment, leak repair, ejector cleaning and nozzle replacement.
 
     Heat-source noise (``noise_enabled``): ``noise_generator="host"`` (the default) draws each plant's
     ``RandomState(seed).standard_normal()`` stream on the host (``HeatSourceNoise``); ``"device"`` generates the same streams on the
@@ -472,6 +475,23 @@ class BatchedPlantEnv:
                 buf.copy_(torch.as_tensor(np.array(np.broadcast_to(a, (self.n,)))))
         return buf
 
+    def _masked_order(self, a, mask):
+        """the action column with -1 (nothing ordered) where ``mask`` is 0; None = the column as it is"""
+        if mask is None:
+            return a
+        m = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(np.array(np.broadcast_to(np.asarray(mask), (self.n,))))
+        none = self._orders.get("none")
+        if none is None:
+            with torch.cuda.device(self.device):
+                none = self._orders["none"] = torch.empty(self.n, dtype=torch.bool, device=self.device)
+                self._orders["masked"] = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        if m.device != self.device:
+            m = m.to(self.device, non_blocking=True)
+        torch.eq(m.expand(self.n), 0, out=none)
+        masked = self._orders["masked"]
+        masked.copy_(a)         # the caller's own column is left as it is
+        return masked.masked_fill_(none, _lib.MAINT_ACTION_NONE)
+
     def perform_maintenance(self, action, pump, mask=None, bearing=None, target_level=None) -> torch.Tensor:
         """Operator-ordered maintenance between two steps (npb_perform_maintenance): what the reference's
         ``pump.perform_maintenance(action, **kwargs)`` (feedwater/pump_system.py:750, the lubrication system's dispatcher
@@ -490,8 +510,9 @@ class BatchedPlantEnv:
         Only the ordered pump's state changes: no work order is created, ``info["maintenance_event_count"]`` and the ``maint.*`` /
         ``mpump.*`` columns do not move (the reference's direct call bypasses AutoMaintenanceSystem too); with the maintenance log
         on, each successful order is one ``operator_maintenance`` record.  Not covered: operator-created work orders, maintenance of
-        steam generators / turbine / condenser, and -- with ``enable_diagnostics`` -- the per-pump ``maintenance_occurred`` /
-        ``oil_top_off_occurred`` / ``maintenance_action`` diagnostics rows, which an operator action leaves alone."""
+        the turbine (steam generators and condenser: ``perform_component_maintenance``), and -- with ``enable_diagnostics`` -- the
+        per-pump ``maintenance_occurred`` / ``oil_top_off_occurred`` / ``maintenance_action`` diagnostics rows, which an operator
+        action leaves alone."""
         if isinstance(action, str):
             action = _lib.maint_action_index(action)       # ValueError for an unknown name, before anything else
         if isinstance(pump, str):
@@ -506,25 +527,56 @@ class BatchedPlantEnv:
             self._orders = {}
             with torch.cuda.device(self.device):
                 self._orders["success"] = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
-        a = self._order_column("action", action, torch.int32, _lib.maint_action_index)
-        if mask is not None:
-            m = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(np.array(np.broadcast_to(np.asarray(mask), (self.n,))))
-            none = self._orders.get("none")
-            if none is None:
-                with torch.cuda.device(self.device):
-                    none = self._orders["none"] = torch.empty(self.n, dtype=torch.bool, device=self.device)
-                    self._orders["masked"] = torch.empty(self.n, dtype=torch.int32, device=self.device)
-            if m.device != self.device:
-                m = m.to(self.device, non_blocking=True)
-            torch.eq(m.expand(self.n), 0, out=none)
-            masked = self._orders["masked"]
-            masked.copy_(a)         # the caller's own column is left as it is
-            a = masked.masked_fill_(none, _lib.MAINT_ACTION_NONE)
+        a = self._masked_order(self._order_column("action", action, torch.int32, _lib.maint_action_index), mask)
         k = self._order_column("pump", pump, torch.int32, _lib.PUMP_IDS.index)
         b = None if bearing is None else self._order_column("bearing", bearing, torch.int32, _lib.MAINT_BEARINGS.__getitem__)
         lvl = None if target_level is None else self._order_column("target_level", target_level, torch.float64, float)
         ok = self._orders["success"]
         _lib.check(self.L.npb_perform_maintenance(self._h, self._p(a), self._p(k), self._p(b), self._p(lvl), self._p(ok), self._stream()), self._h)
+        return ok
+
+    def perform_component_maintenance(self, component, action, unit=None, mask=None, cleaning_type=None, tubes_to_plug=None) -> torch.Tensor:
+        """Operator-ordered maintenance of a steam generator, the steam-generator system, the condenser or a steam-jet ejector between
+        two steps (npb_perform_component_maintenance): what the reference's ``perform_maintenance(action, **kwargs)`` of that object
+        (steam_generator/steam_generator.py:1092, steam_generator/enhanced_physics.py:1062, condenser/physics.py:1188,
+        condenser/vacuum_pump.py:338) does to every ordered plant, at once, on the device.
+
+        ``component``: ``"steam_generator"``, ``"steam_generator_system"``, ``"condenser"`` or ``"ejector"``.  ``action``: a maintenance
+        type of that component in ``_lib.COMPONENT_ACTIONS``, its catalog index, or an int32 column of catalog indices (``-1`` = nothing
+        for that plant; the index names the component, so a column may mix kinds); an unknown name raises ValueError before any device
+        work, and so does, with its own message, a handler that is not offered (``_lib.COMPONENT_ACTIONS_NOT_OFFERED``).  ``unit``: the
+        generator 0..2 or the ejector 0..1 / ``"SJE-001"`` / ``"SJE-002"``, or an int32 column; None = 0; ignored by system and condenser
+        actions.  ``mask`` as in ``perform_maintenance``.  ``cleaning_type``: None (the handler's default argument, "chemical"),
+        ``"chemical"`` / ``"mechanical"`` / ``"hydroblast"`` / ``"replacement"``, any other string (the handlers' "anything else"), an
+        NPB_CLEANING_* index or a column.  ``tubes_to_plug``: the kwarg of condenser_tube_plugging, carried by the ABI for the day that
+        handler can be offered; no offered handler reads it.  Returns the ``success`` column (uint8, the env's own buffer): 1 where the
+        reference's result says success.  No host synchronisation.
+
+        Only the sections the action touches change, on the ordering plants only.  No work order, counter, ``maint.*`` / ``mpump.*``
+        column moves; with the maintenance log on, each successful order is one ``operator_component_maintenance`` record.  The
+        state-log columns that show attributes the state does not carry (a generator's cleaning cycles and years since cleaning, the
+        chemistry's time since treatment) do not follow an operator action.  Not covered: turbine maintenance, work orders for these
+        components."""
+        if isinstance(action, str) or component not in _lib.COMPONENT_KINDS:
+            action = _lib.component_action_index(component, action)       # ValueError for an unknown kind or name, before anything else
+        if isinstance(unit, str):
+            if component != "ejector" or unit not in _lib.EJECTOR_IDS:
+                raise ValueError("unknown unit %r of a %s" % (unit, component))
+            unit = _lib.EJECTOR_IDS.index(unit)
+        if not hasattr(self.L, "npb_perform_component_maintenance"):
+            raise _lib.NpbError("libnpb.so has no npb_perform_component_maintenance (older than ABI 148): rebuild")
+        if getattr(self, "_orders", None) is None:
+            self._orders = {}
+            with torch.cuda.device(self.device):
+                self._orders["success"] = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+        a = self._masked_order(self._order_column("component_action", action, torch.int32, int), mask)
+        k = None if unit is None else self._order_column("unit", unit, torch.int32, int)
+        if isinstance(cleaning_type, str):
+            cleaning_type = _lib.cleaning_type_index(cleaning_type)
+        c = None if cleaning_type is None else self._order_column("cleaning_type", cleaning_type, torch.int32, int)
+        amount = None if tubes_to_plug is None else self._order_column("tubes_to_plug", tubes_to_plug, torch.float64, float)
+        ok = self._orders["success"]
+        _lib.check(self.L.npb_perform_component_maintenance(self._h, self._p(a), self._p(k), self._p(c), self._p(amount), self._p(ok), self._stream()), self._h)
         return ok
 
     def snapshot(self) -> None:
@@ -956,6 +1008,41 @@ class _PathProxy:
             return {"success": bool(ok[0].item())}
         return perform_maintenance
 
+    # ... and the four whose perform_maintenance is npb_perform_component_maintenance: the steam-generator system, one of its
+    # generators, the condenser, one of its steam-jet ejectors
+    _VACUUM_SYSTEM = "secondary_physics.condenser.vacuum_system"
+    _COMPONENTS = ((re.compile(r"^secondary_physics\.steam_generator_system\.steam_generators\[([0-2])\]$"), "steam_generator"),
+                   (re.compile(r"^secondary_physics\.steam_generator_system$"), "steam_generator_system"),
+                   (re.compile(r"^secondary_physics\.condenser$"), "condenser"),
+                   (re.compile(r"^secondary_physics\.condenser\.vacuum_system\.ejectors\['(SJE-00[12])'\]$"), "ejector"))
+
+    def _perform_component_maintenance(self, component, unit):
+        env = self._env
+
+        def perform_maintenance(maintenance_type=None, **kwargs):
+            """SteamGenerator / EnhancedSteamGeneratorPhysics / EnhancedCondenserPhysics / SteamJetEjector.perform_maintenance on this
+            object, now (BatchedPlantEnv.perform_component_maintenance).  Returns ``{'success': bool}``; kwargs as the reference's:
+            ``cleaning_type``, ``sg_index`` (the system delegates a generator's maintenance type to that generator).  A type the
+            catalog does not know is the reference's "Unknown maintenance type" (success False, nothing changed) -- on an ejector
+            it is the dispatcher's general maintenance, as there.  A handler that is not offered raises ValueError."""
+            comp, k = component, unit
+            if (comp, maintenance_type) in _lib.COMPONENT_ACTIONS_NOT_OFFERED:
+                _lib.component_action_index(comp, maintenance_type)
+            if (comp, maintenance_type) not in _lib.COMPONENT_ACTIONS:
+                sg_index = kwargs.get("sg_index")
+                if comp == "ejector":
+                    maintenance_type = "general"
+                elif comp == "steam_generator_system" and sg_index is not None and 0 <= sg_index < 3:
+                    comp, k = "steam_generator", int(sg_index)
+                    if (comp, maintenance_type) in _lib.COMPONENT_ACTIONS_NOT_OFFERED:
+                        _lib.component_action_index(comp, maintenance_type)
+                if (comp, maintenance_type) not in _lib.COMPONENT_ACTIONS:
+                    return {"success": False}
+            ok = env.perform_component_maintenance(comp, maintenance_type, unit=k, cleaning_type=kwargs.get("cleaning_type"),
+                                                   tubes_to_plug=kwargs.get("tubes_to_plug"))
+            return {"success": bool(ok[0].item())}
+        return perform_maintenance
+
     def __getattr__(self, name):
         extras = object.__getattribute__(self, "_extras")
         if name in extras:
@@ -964,9 +1051,18 @@ class _PathProxy:
             m = self._MAINTAINABLE.match(self._prefix or "")
             if m:
                 return self._perform_maintenance(m.group(1))
+            for pattern, component in self._COMPONENTS:
+                m = pattern.match(self._prefix or "")
+                if m:
+                    unit = 0 if not m.groups() else int(m.group(1)) if component == "steam_generator" else _lib.EJECTOR_IDS.index(m.group(1))
+                    return self._perform_component_maintenance(component, unit)
+        if name == "ejectors" and self._prefix == self._VACUUM_SYSTEM:     # its members are no plain paths of the schema
+            return _PathProxy(self._env, self._prefix + ".ejectors")
         return self._resolve("%s.%s" % (self._prefix, name) if self._prefix else name)
 
     def __getitem__(self, key):
+        if self._prefix == self._VACUUM_SYSTEM + ".ejectors" and key in _lib.EJECTOR_IDS:
+            return _PathProxy(self._env, "%s[%r]" % (self._prefix, key))
         return self._resolve("%s[%r]" % (self._prefix, key))
 
     def _assign(self, path, value):
