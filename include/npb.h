@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define NPB_VERSION 148 /* 0.1.4.8: npb_perform_component_maintenance, npb_component_* catalog queries, NPB_MAINT_EVENT_OPERATOR_COMPONENT (maintenance of steam generators, condenser and ejectors a caller orders); 0.1.4.7: npb_perform_maintenance, NPB_MAINT_EVENT_OPERATOR (maintenance a caller orders, carried out on the device between two steps); 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
+#define NPB_VERSION 149 /* 0.1.4.9: npb_perform_turbine_maintenance, npb_turbine_* catalog queries, NPB_MAINT_EVENT_OPERATOR_TURBINE (maintenance of the turbine, its bearings, lubrication system and stages a caller orders); 0.1.4.8: npb_perform_component_maintenance, npb_component_* catalog queries, NPB_MAINT_EVENT_OPERATOR_COMPONENT (maintenance of steam generators, condenser and ejectors a caller orders); 0.1.4.7: npb_perform_maintenance, NPB_MAINT_EVENT_OPERATOR (maintenance a caller orders, carried out on the device between two steps); 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
 #ifndef NPB_API
 #define NPB_API __attribute__((visibility("default")))
 #endif
@@ -223,8 +223,8 @@ NPB_API size_t npb_maint_event_bytes(void);   /* sizeof(npb_maint_event_t) */
  * the maint.* / mpump.* columns, the count buffer (npb_set_maintenance_count_buffer) and the diagnostics rows do not move: a direct call
  * bypasses AutoMaintenanceSystem in the reference too.  Works with params.maint_enabled 0 or 1, in every mode and storage type.  With a
  * maintenance log set (npb_set_maintenance_log) every successful order appends one NPB_MAINT_EVENT_OPERATOR record.  Not offered: work
- * orders created by the operator (queued, delayed, counted), and maintenance of the turbine (steam generators and condenser:
- * npb_perform_component_maintenance).
+ * orders created by the operator (queued, delayed, counted).  Steam generators and condenser: npb_perform_component_maintenance; the
+ * turbine: npb_perform_turbine_maintenance.
  * NPB_EINVAL for action = NULL or pump = NULL. */
 NPB_API int npb_perform_maintenance(NpbHandle *h, const int32_t *action, const int32_t *pump, const int32_t *bearing,
                                     const double *target_level, uint8_t *success, void *stream);
@@ -249,7 +249,7 @@ NPB_API int npb_perform_maintenance(NpbHandle *h, const int32_t *action, const i
  * resets the steam-generator system's own chemistry, which is not carried (npb_params.h sgchem_*): success 1, nothing moves.  The
  * work-order queue, maint.* / mpump.*, the count buffer and the diagnostics rows do not move; params.maint_enabled may be 0 or 1.  With
  * a maintenance log set every successful order appends one NPB_MAINT_EVENT_OPERATOR_COMPONENT record (action = catalog index, pump byte =
- * unit).  Not offered: turbine maintenance, work orders for these components.
+ * unit).  Not offered: work orders for these components.  The turbine: npb_perform_turbine_maintenance.
  * NPB_EINVAL for action = NULL. */
 NPB_API int npb_perform_component_maintenance(NpbHandle *h, const int32_t *action, const int32_t *unit, const int32_t *option,
                                               const double *amount, uint8_t *success, void *stream);
@@ -258,6 +258,34 @@ NPB_API int npb_component_num_actions(void);
 NPB_API const char *npb_component_action_name(int a);
 NPB_API int npb_component_action_kind(int a);
 NPB_API const char *npb_component_kind_name(int kind);
+/* The same for the turbine: perform_maintenance(maintenance_type) of the turbine (turbine/enhanced_physics.py:1055-1267), one of its four
+ * bearings (turbine/rotor_dynamics.py:381-564), its bearing-lubrication system (turbine/turbine_bearing_lubrication.py:481-668) and one
+ * of its fourteen stages (turbine/stage_system.py:341-377), called by the USER between two steps.  Device pointers to n_plants elements;
+ * asynchronous.
+ *   action   index of the TURBINE catalog (NPB_TA_*, include/npb_maint.h; npb_turbine_action_name / _kind), -1 = nothing for this plant.
+ *            The index names the kind, so one column may mix kinds.  The catalog holds the handlers the live reference shows closed over
+ *            the carried state; a stage's "cleaning" is not among them (include/npb_maint.h).
+ *   unit     NULL = 0: the bearing 0..3 (TB-001..TB-004; the third is the thrust bearing) or the stage 0..13 (HP-1..HP-8, LP-1..LP-6);
+ *            ignored by actions on the turbine and the lubrication system
+ *   success  may be NULL; 1 where the reference's result says success -- a catalogued action on a unit that exists, and for
+ *            thrust_bearing_adjustment the thrust bearing -- else 0, plants with action -1 included.  A stage's handler returns no
+ *            success flag: 1 for its catalogued types.  An index outside the catalog or a unit that does not exist: success 0, state
+ *            untouched, no error code.  In a mode that does not step the turbine (NPB_MODE_PRIMARY, NPB_MODE_PRIMARY_SG) every order
+ *            gives success 0.
+ * An order on the turbine, a bearing or the lubrication system changes members of turb only; an order on a stage changes that stage's
+ * stage_deposit_thickness / stage_blade_wear_factor / stage_efficiency_degradation only; a plant without a successful order keeps its
+ * exact bits.  Several catalogued handlers move no carried member (tests, inspections, analyses): success 1, nothing stored.  The
+ * work-order queue, maint.* / mpump.*, the count buffer and the diagnostics rows do not move -- the accumulator rows of the diagnostics
+ * buffer (the bearings' clearance increase, the stage system's efficiency) therefore do not follow an operator action.  With a
+ * maintenance log set every successful order appends one NPB_MAINT_EVENT_OPERATOR_TURBINE record (action = catalog index, pump byte =
+ * unit).  Not offered: work orders and automatic maintenance for the turbine.
+ * NPB_EINVAL for action = NULL. */
+NPB_API int npb_perform_turbine_maintenance(NpbHandle *h, const int32_t *action, const int32_t *unit, uint8_t *success, void *stream);
+/* the TURBINE catalog by index: type string, turbine kind (NPB_TURBINE_*; -1 outside the catalog), and per kind its name */
+NPB_API int npb_turbine_num_actions(void);
+NPB_API const char *npb_turbine_action_name(int a);
+NPB_API int npb_turbine_action_kind(int a);
+NPB_API const char *npb_turbine_kind_name(int kind);
 
 /* re-initialise plants to the construction-time state; mask (device, uint8[n], NULL = all) selects plants.
  * Stands in for constructing a fresh simulator (the data-gen runner's episode start,

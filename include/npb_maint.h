@@ -15,6 +15,8 @@
  *    :469-524) and the lubrication system's dispatcher (pump_lubrication.py:625-674) can produce.
  *  - the COMPONENT catalog: the maintenance types a user can call directly on steam generators, condenser and ejectors
  *    (npb_perform_component_maintenance); no threshold, work order or table row names them.
+ *  - the TURBINE catalog: the maintenance types a user can call directly on the turbine, its bearings, its bearing-lubrication system
+ *    and its stages (npb_perform_turbine_maintenance); a catalog of its own, because the COMPONENT catalog's size and kinds are fixed.
  *  - the threshold TABLE a handle carries (npb_set_maintenance_table): per catalogued parameter its rank in the
  *    configuration's dict order (the scan order; -1 = absent), threshold, comparison, action, priority, cooldown and,
  *    for bearing_replacement, which bearing.  npb_maint_table_default() is the table of the data-gen action-test
@@ -145,6 +147,52 @@ enum {
 enum { NPB_CLEANING_DEFAULT = 0, NPB_CLEANING_CHEMICAL = 1, NPB_CLEANING_MECHANICAL = 2, NPB_CLEANING_HYDROBLAST = 3, NPB_CLEANING_REPLACEMENT = 4,
        NPB_CLEANING_OTHER = 5 };
 
+/* TURBINE catalog (npb_perform_turbine_maintenance): the maintenance types a user can call directly on the turbine, one of its bearings,
+ * its bearing-lubrication system and one of its stages -- X(KIND, id, "maintenance type string"); a catalog of its own beside the COMPONENT
+ * catalog, with indices of its own.  Dispatchers: EnhancedTurbinePhysics.perform_maintenance turbine/enhanced_physics.py:1055-1267 (SYSTEM),
+ * BearingModel.perform_maintenance turbine/rotor_dynamics.py:381-564 (BEARING, unit 0..3), TurbineBearingLubricationSystem.perform_maintenance
+ * turbine/turbine_bearing_lubrication.py:481-668 (LUBE), TurbineStage.perform_maintenance turbine/stage_system.py:341-377 (STAGE, unit
+ * 0..13); restated in nuclear_sim_amd/csrc/npd_turbine_maintenance.h.  A handler is in the catalog exactly when the live reference shows it
+ * CLOSED over the carried state: what it writes outside include/npb_fields.h no step reads before rewriting it
+ * (tools/make_turbine_maintenance_golden.py, op_closed in tests/golden/operator_turbine/).  Handlers that move no carried member are
+ * catalogued all the same: success, nothing stored.  Not in the catalog: a stage's "cleaning", which leaves the stage's
+ * blade_condition_factor and actual_efficiency stale for the next step's expansion to read (stage_system.py:353-359, 221-224).
+ * LUBE_TURBINE_OIL_TOP_OFF is closed because the lubrication system's oil_level is 100 from construction (no step moves it, and
+ * turbine_oil_change sets it to 100): nothing is added, the dilution is 0; were the level carried, the handler would read it. */
+#define NPB_TURBINE_NACT 21
+enum { NPB_TURBINE_SYSTEM = 0, NPB_TURBINE_BEARING = 1, NPB_TURBINE_LUBE = 2, NPB_TURBINE_STAGE = 3, NPB_TURBINE_NKIND = 4 };
+#define NPB_TURBINE_ACTIONS(X) \
+  X(SYSTEM, TURBINE_PERFORMANCE_TEST,    "turbine_performance_test") \
+  X(SYSTEM, TURBINE_SYSTEM_OPTIMIZATION, "turbine_system_optimization") \
+  X(SYSTEM, TURBINE_PROTECTION_TEST,     "turbine_protection_test") \
+  X(SYSTEM, THERMAL_STRESS_ANALYSIS,     "thermal_stress_analysis") \
+  X(SYSTEM, VIBRATION_ANALYSIS,          "vibration_analysis") \
+  X(SYSTEM, ROUTINE_MAINTENANCE,         "routine_maintenance") \
+  X(BEARING, TURBINE_BEARING_INSPECTION,  "turbine_bearing_inspection") \
+  X(BEARING, TURBINE_BEARING_REPLACEMENT, "turbine_bearing_replacement") \
+  X(BEARING, BEARING_CLEARANCE_CHECK,     "bearing_clearance_check") \
+  X(BEARING, BEARING_ALIGNMENT,           "bearing_alignment") \
+  X(BEARING, THRUST_BEARING_ADJUSTMENT,   "thrust_bearing_adjustment") \
+  X(BEARING, TURBINE_OIL_CHANGE,          "turbine_oil_change") \
+  X(BEARING, ROUTINE_MAINTENANCE,         "routine_maintenance") \
+  X(LUBE, TURBINE_OIL_CHANGE,      "turbine_oil_change") \
+  X(LUBE, TURBINE_OIL_TOP_OFF,     "turbine_oil_top_off") \
+  X(LUBE, OIL_FILTER_REPLACEMENT,  "oil_filter_replacement") \
+  X(LUBE, OIL_COOLER_CLEANING,     "oil_cooler_cleaning") \
+  X(LUBE, LUBRICATION_SYSTEM_TEST, "lubrication_system_test") \
+  X(LUBE, ROUTINE_MAINTENANCE,     "routine_maintenance") \
+  X(STAGE, BLADE_REPLACEMENT, "blade_replacement") \
+  X(STAGE, OVERHAUL,          "overhaul")
+enum {
+#define NPB__X(kind, id, name) NPB_TA_##kind##_##id,
+  NPB_TURBINE_ACTIONS(NPB__X)
+#undef NPB__X
+  NPB_TA_COUNT_
+};
+/* units per kind: -, bearings, -, stages; the thrust bearing is the third (rotor_dynamics.py:829) */
+#define NPB_TURBINE_UNITS(kind) ((kind) == NPB_TURBINE_BEARING ? 4 : (kind) == NPB_TURBINE_STAGE ? 14 : 1)
+#define NPB_TURBINE_THRUST_BEARING 2
+
 enum { NPB_CMP_GREATER_THAN = 0, NPB_CMP_LESS_THAN = 1, NPB_CMP_GREATER_EQUAL = 2, NPB_CMP_LESS_EQUAL = 3, NPB_CMP_EQUALS = 4, NPB_CMP_NOT_EQUALS = 5 };
 enum { NPB_PRIO_LOW = 1, NPB_PRIO_MEDIUM = 2, NPB_PRIO_HIGH = 3, NPB_PRIO_CRITICAL = 4, NPB_PRIO_EMERGENCY = 5 };
 enum { NPB_BEARING_ALL = 0, NPB_BEARING_MOTOR = 1, NPB_BEARING_PUMP = 2, NPB_BEARING_THRUST = 3 };
@@ -190,7 +238,10 @@ static inline void npb_maint_table_default(npb_maint_table_t *t) {
  * order behind it): order = 0, created = planned_start = time = the plant's clock at the call, trigger = priority = 0 */
 /* NPB_MAINT_EVENT_OPERATOR_COMPONENT: the same through npb_perform_component_maintenance: action = index of the COMPONENT catalog
  * (NPB_CA_*), the pump byte = the unit (generator 0..2, ejector 0..1; 0 for the system and the condenser), the rest as for OPERATOR */
-enum { NPB_MAINT_EVENT_CREATED = 0, NPB_MAINT_EVENT_COMPLETED = 1, NPB_MAINT_EVENT_OPERATOR = 2, NPB_MAINT_EVENT_OPERATOR_COMPONENT = 3 };
+/* NPB_MAINT_EVENT_OPERATOR_TURBINE: the same through npb_perform_turbine_maintenance: action = index of the TURBINE catalog (NPB_TA_*),
+ * the pump byte = the unit (bearing 0..3, stage 0..13; 0 for the turbine and the lubrication system), the rest as for OPERATOR */
+enum { NPB_MAINT_EVENT_CREATED = 0, NPB_MAINT_EVENT_COMPLETED = 1, NPB_MAINT_EVENT_OPERATOR = 2, NPB_MAINT_EVENT_OPERATOR_COMPONENT = 3,
+       NPB_MAINT_EVENT_OPERATOR_TURBINE = 4 };
 typedef struct npb_maint_event_t {
   double time;            /* the rule's clock: prim.sim_time of the step [min], fp64 under either storage type */
   double created;         /* the order's creation time [min]; for a completion mpump.last_trigger_time[action], which is the open
@@ -199,9 +250,9 @@ typedef struct npb_maint_event_t {
   int32_t plant;          /* the plant's index within the handle */
   int32_t order;          /* the per-plant creation number n (mpump.wo_order): the reference's work-order id WO-%06d */
   uint16_t trigger;       /* creation: bit q = catalog parameter q whose last_violation_time this scan stamped; 0 for a completion */
-  uint8_t pump;           /* 0..3 = FWP-1..4; OPERATOR_COMPONENT: the unit */
-  uint8_t action;         /* action catalog index (NPB_MA_*); OPERATOR_COMPONENT: component catalog index (NPB_CA_*) */
-  uint8_t kind;           /* NPB_MAINT_EVENT_CREATED | _COMPLETED | _OPERATOR | _OPERATOR_COMPONENT */
+  uint8_t pump;           /* 0..3 = FWP-1..4; OPERATOR_COMPONENT / OPERATOR_TURBINE: the unit */
+  uint8_t action;         /* action catalog index (NPB_MA_*); OPERATOR_COMPONENT: component catalog index (NPB_CA_*); OPERATOR_TURBINE: NPB_TA_* */
+  uint8_t kind;           /* NPB_MAINT_EVENT_CREATED | _COMPLETED | _OPERATOR | _OPERATOR_COMPONENT | _OPERATOR_TURBINE */
   uint8_t priority;       /* creation: NPB_PRIO_* of the order; 0 for a completion (the state does not keep an order's priority) */
   uint8_t bearing;        /* bearing_replacement: NPB_BEARING_* of the order (mpump.wo_bearing); else 0 */
   uint8_t reserved;
@@ -211,6 +262,7 @@ typedef struct npb_maint_event_t {
 static_assert(sizeof(npb_maint_event_t) == NPB_MAINT_EVENT_BYTES, "npb_maint_event_t layout");
 static_assert(NPB_MAINT_NPARAM <= 16 && NPB_MAINT_NACT <= 255 && NPB_COMPONENT_NACT <= 255, "npb_maint_event_t field widths");
 static_assert(NPB_CA_COUNT_ == NPB_COMPONENT_NACT, "NPB_COMPONENT_NACT");
+static_assert(NPB_TA_COUNT_ == NPB_TURBINE_NACT && NPB_TURBINE_NACT <= 255, "NPB_TURBINE_NACT");
 #else
 _Static_assert(sizeof(npb_maint_event_t) == NPB_MAINT_EVENT_BYTES, "npb_maint_event_t layout");
 #endif

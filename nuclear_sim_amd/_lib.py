@@ -175,6 +175,47 @@ def component_action_index(component, action) -> int:
     return COMPONENT_ACTIONS.index((component, action))
 
 
+# include/npb_maint.h NPB_TURBINE_ACTIONS: the catalog of npb_perform_turbine_maintenance, (turbine kind, maintenance type) per index;
+# load() holds it against the library's own catalog.  Kinds: the turbine itself (EnhancedTurbinePhysics), one of its four bearings, its
+# bearing-lubrication system, one of its fourteen stages.
+TURBINE_KINDS = ("turbine", "bearing", "lubrication", "stage")
+TURBINE_ACTIONS = tuple(
+    [("turbine", a) for a in (
+        "turbine_performance_test", "turbine_system_optimization", "turbine_protection_test", "thermal_stress_analysis", "vibration_analysis",
+        "routine_maintenance")] +
+    [("bearing", a) for a in (
+        "turbine_bearing_inspection", "turbine_bearing_replacement", "bearing_clearance_check", "bearing_alignment", "thrust_bearing_adjustment",
+        "turbine_oil_change", "routine_maintenance")] +
+    [("lubrication", a) for a in (
+        "turbine_oil_change", "turbine_oil_top_off", "oil_filter_replacement", "oil_cooler_cleaning", "lubrication_system_test",
+        "routine_maintenance")] +
+    [("stage", a) for a in ("blade_replacement", "overhaul")])
+TURBINE_UNITS = {"turbine": 1, "bearing": 4, "lubrication": 1, "stage": 14}
+TURBINE_THRUST_BEARING = 2     # thrust_bearing_adjustment succeeds on this bearing only (rotor_dynamics.py:829)
+# handlers of the reference that are NOT offered because they are not closed over the carried state (DESIGN.md "Operator-ordered
+# maintenance of the turbine"; tests/golden/operator_turbine/ot5_not_offered.npz): refused by name, with this message
+TURBINE_ACTIONS_NOT_OFFERED = {
+    ("stage", "cleaning"):
+        "the reference's handler resets the stage's fouling_factor but leaves its blade_condition_factor and actual_efficiency at the "
+        "values of the fouled stage (turbine/stage_system.py:353-359); the next step's expansion reads both (:221-224) before it derives "
+        "them anew (:321-326), and no schema column carries them",
+}
+
+
+def turbine_action_index(component, action) -> int:
+    """(turbine kind, maintenance type name or index) -> index into TURBINE_ACTIONS; ValueError for an unknown kind or name, and for a
+    handler that is not offered (host only, no library needed).  An index is taken as it is."""
+    if component not in TURBINE_KINDS:
+        raise ValueError("unknown turbine component %r: one of %r" % (component, TURBINE_KINDS))
+    if not isinstance(action, str):
+        return int(action)
+    if (component, action) in TURBINE_ACTIONS_NOT_OFFERED:
+        raise ValueError("%s maintenance %r is not offered on the device: %s" % (component, action, TURBINE_ACTIONS_NOT_OFFERED[(component, action)]))
+    if (component, action) not in TURBINE_ACTIONS:
+        raise ValueError("unknown %s maintenance %r: not in the turbine catalog (include/npb_maint.h)" % (component, action))
+    return TURBINE_ACTIONS.index((component, action))
+
+
 def cleaning_type_index(cleaning_type) -> int:
     """the reference's cleaning_type kwarg -> NPB_CLEANING_*; an index is taken as it is"""
     if cleaning_type is None or isinstance(cleaning_type, str):
@@ -300,6 +341,17 @@ def load():
                         for a in range(L.npb_component_num_actions()))
         if catalog != COMPONENT_ACTIONS:
             raise NpbError("libnpb.so's component catalog is not this binding's COMPONENT_ACTIONS: rebuild")
+    if hasattr(L, "npb_perform_turbine_maintenance"):     # ABI 149: maintenance of the turbine the caller orders
+        L.npb_perform_turbine_maintenance.argtypes = [vp, vp, vp, vp, vp]
+        L.npb_turbine_action_name.restype = ctypes.c_char_p
+        L.npb_turbine_action_name.argtypes = [ci]
+        L.npb_turbine_kind_name.restype = ctypes.c_char_p
+        L.npb_turbine_kind_name.argtypes = [ci]
+        L.npb_turbine_action_kind.argtypes = [ci]
+        catalog = tuple((L.npb_turbine_kind_name(L.npb_turbine_action_kind(a)).decode(), L.npb_turbine_action_name(a).decode())
+                        for a in range(L.npb_turbine_num_actions()))
+        if catalog != TURBINE_ACTIONS:
+            raise NpbError("libnpb.so's turbine catalog is not this binding's TURBINE_ACTIONS: rebuild")
     if hasattr(L, "npb_noise_seed"):     # ABI 145: heat-source noise streams on the device
         L.npb_noise_seed.argtypes = [vp, vp, vp]
         L.npb_noise_fill.argtypes = [vp, ci, vp, vp]

@@ -206,6 +206,18 @@ int npb_component_num_actions(void) { return NPB_COMPONENT_NACT; }
 const char *npb_component_action_name(int a) { return a >= 0 && a < NPB_COMPONENT_NACT ? g_component_actions[a].name : nullptr; }
 int npb_component_action_kind(int a) { return a >= 0 && a < NPB_COMPONENT_NACT ? g_component_actions[a].kind : -1; }
 const char *npb_component_kind_name(int kind) { return kind >= 0 && kind < NPB_COMPONENT_NKIND ? g_component_kinds[kind] : nullptr; }
+static const struct { const char *name; int kind; } g_turbine_actions[] = {
+#define NPB__X(kind, id, name) {name, NPB_TURBINE_##kind},
+  NPB_TURBINE_ACTIONS(NPB__X)
+#undef NPB__X
+};
+static const char *const g_turbine_kinds[] = {"turbine", "bearing", "lubrication", "stage"};
+static_assert(sizeof(g_turbine_actions) / sizeof(g_turbine_actions[0]) == NPB_TURBINE_NACT, "turbine catalog");
+static_assert(sizeof(g_turbine_kinds) / sizeof(g_turbine_kinds[0]) == NPB_TURBINE_NKIND, "turbine kinds");
+int npb_turbine_num_actions(void) { return NPB_TURBINE_NACT; }
+const char *npb_turbine_action_name(int a) { return a >= 0 && a < NPB_TURBINE_NACT ? g_turbine_actions[a].name : nullptr; }
+int npb_turbine_action_kind(int a) { return a >= 0 && a < NPB_TURBINE_NACT ? g_turbine_actions[a].kind : -1; }
+const char *npb_turbine_kind_name(int kind) { return kind >= 0 && kind < NPB_TURBINE_NKIND ? g_turbine_kinds[kind] : nullptr; }
 size_t npb_state_bytes(void) { return (size_t)NPB_TOTAL_COL64 * 8; }
 /* carried fp64 members are read and written, int32 members too, output members are only written (as float);
  * the maint.* section belongs to the maintenance kernel */
@@ -398,6 +410,18 @@ int npb_perform_component_maintenance(NpbHandle *h, const int32_t *action, const
                        : h->params.mode == NPB_MODE_PRIMARY_SG ? (1u << NPB_COMPONENT_SG) | (1u << NPB_COMPONENT_SGSYS) : 0u;
   h->K->operator_component_maint(h->n_plants, NPB_N(h), h->f64, action, unit, option, amount, success, kinds, h->maint_log, h->maint_log_cursor,
                                  h->maint_log_capacity, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+
+int npb_perform_turbine_maintenance(NpbHandle *h, const int32_t *action, const int32_t *unit, uint8_t *success, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!action) return fail(h, NPB_EINVAL, "npb_perform_turbine_maintenance: the action column must not be NULL");
+  NPB_USE_DEVICE(h);
+  /* only the full plant steps the turbine: without its secondary side the reference has no object to call, and primary + steam generators
+   * carries no turbine.  maint_cache_stale is left alone, as in npb_perform_maintenance: no handler here writes a pump, a stamp or the table. */
+  h->K->operator_turbine_maint(h->n_plants, NPB_N(h), h->f64, action, unit, success, h->params.mode == NPB_MODE_FULL, h->maint_log, h->maint_log_cursor,
+                               h->maint_log_capacity, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }

@@ -53,6 +53,10 @@ typedef struct {
   void (*operator_component_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *unit, const int32_t *option,
                                    const double *amount, uint8_t *success, unsigned kinds, npb_maint_event_t *log_records, uint32_t *log_cursor,
                                    int log_capacity, hipStream_t stream);
+  /* npb_perform_turbine_maintenance: the caller's [n_plants] order columns (unit / success may be NULL), whether the handle's mode steps
+   * the turbine, and the event log */
+  void (*operator_turbine_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *unit, uint8_t *success, int turbine,
+                                 npb_maint_event_t *log_records, uint32_t *log_cursor, int log_capacity, hipStream_t stream);
 } npb_launchers_t;
 extern npb_launchers_t npb_launch_table, npb32_launch_table;
 /* the same for either storage type */

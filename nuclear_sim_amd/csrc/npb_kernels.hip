@@ -50,6 +50,7 @@ extern "C" __attribute__((visibility("default"))) int npb_debug_set_stamp_buffer
 #include "npd_ph.h"
 #include "npd_maintenance.h"
 #include "npd_component_maintenance.h"
+#include "npd_turbine_maintenance.h"
 #include "npd_init.h"
 #include "npd_reset.h"
 #include "npd_step.h"
@@ -998,6 +999,72 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_operator_component_maint_kernel(
   }
 }
 
+/* operator-ordered maintenance of the turbine (npb_perform_turbine_maintenance): perform_maintenance(type) of the turbine, one of its
+ * bearings, its bearing-lubrication system or one of its stages, called by the user between two steps (npd_turbine_maintenance.h), for
+ * every plant whose lane of the caller's columns orders one.  The design of the component kernel above: one wave per 64 plants reads
+ * its 64 orders, writes success and leaves when none can succeed.  Orders on the turbine, a bearing and the lubrication system load,
+ * change and store the turb section of the ordering lanes; an order on a stage touches that stage's three tstg columns and nothing else
+ * (the section's other 67 columns are never loaded), the wave skipping the stages nobody in it ordered.  Nothing is stored to a plant
+ * without a successful order. */
+struct npd_turbine_orders_t {
+  const int32_t *action, *unit;               /* the caller's [n_plants] columns; unit NULL = 0 */
+  uint8_t *success;                           /* [n_plants] or NULL */
+  int n_plants;
+  int turbine;                                /* the handle's mode steps the turbine */
+};
+__global__ __launch_bounds__(NPB_WAVE) void npb_operator_turbine_maint_kernel(npd_turbine_orders_t O, npd_maint_log_t L, size_t N, npd_real_t *__restrict__ f64) {
+  const size_t p = (size_t)blockIdx.x * NPB_WAVE + threadIdx.x;
+  const bool live = p < (size_t)O.n_plants;      /* the columns have n_plants elements, not the pitch */
+  int action = -1, unit = 0;
+  if (live) { action = O.action[p]; if (action >= 0 && O.unit) unit = O.unit[p]; }
+  const int kind = npd_turbine_kind(action);
+  if (kind == NPB_TURBINE_SYSTEM || kind == NPB_TURBINE_LUBE) unit = 0;      /* one of each: the unit is ignored */
+  /* "Unknown maintenance type": an index outside the catalog; a bearing or stage that is none; a thrust adjustment of a journal bearing;
+   * a mode that steps no turbine */
+  const bool ok = O.turbine && npd_turbine_order_ok(kind, action, unit);
+  if (live && O.success) O.success[p] = ok ? 1 : 0;
+  if (!__any(ok)) return;
+  NPD_SEGMENT(f64, N, (size_t)blockIdx.x * NPB_WAVE);
+  const bool on_turb = ok && kind != NPB_TURBINE_STAGE;
+  if (__any(on_turb)) {
+    if (on_turb) {
+      npb_turb_t t;
+      NPD_LOAD(TURB, npb_turb_t, t, 0);
+      if (kind == NPB_TURBINE_SYSTEM) npd_turbine_system_maintenance(&t, action);
+      else if (kind == NPB_TURBINE_LUBE) npd_turbine_lube_maintenance(&t, action);
+      else {
+#pragma unroll
+        for (int b = 0; b < 4; b++)      /* a constant index: the section stays in registers */
+          if (unit == b) npd_turbine_bearing_maintenance(&t, b, action);
+      }
+      NPD_STORE(TURB, npb_turb_t, t, 0);
+    }
+  }
+  const bool on_stage = ok && kind == NPB_TURBINE_STAGE;
+  if (__any(on_stage)) {
+#pragma unroll 1
+    for (int k = 0; k < 14; k++) {
+      const bool mine = on_stage && unit == k;
+      if (!__any(mine)) continue;
+      if (mine) {      /* tstg has carried reals only: member slot = column within the section */
+        npd_real_t *deg = (npd_real_t *)npd_gaddr(f64, N, p, NPD_SEC_COL(TSTG, 0) + NPB_F64_SLOT(npb_tstg_t, stage_efficiency_degradation) + k);
+        npd_real_t *dep = (npd_real_t *)npd_gaddr(f64, N, p, NPD_SEC_COL(TSTG, 0) + NPB_F64_SLOT(npb_tstg_t, stage_deposit_thickness) + k);
+        npd_real_t *wear = (npd_real_t *)npd_gaddr(f64, N, p, NPD_SEC_COL(TSTG, 0) + NPB_F64_SLOT(npb_tstg_t, stage_blade_wear_factor) + k);
+        double efficiency_degradation = (double)*deg, deposit_thickness = (double)*dep, blade_wear_factor = (double)*wear;
+        npd_turbine_stage_maintenance(&efficiency_degradation, &deposit_thickness, &blade_wear_factor, action);
+        *deg = (npd_real_t)efficiency_degradation; *dep = (npd_real_t)deposit_thickness; *wear = (npd_real_t)blade_wear_factor;
+      }
+    }
+  }
+  if (L.cursor) {      /* the event log (npb_set_maintenance_log): one record per successful order, one atomic per wave */
+    const double t = NPD_F64_COL(PRIM, npb_prim_t, sim_time, 0);
+    npb_maint_event_t ev = {};
+    ev.time = t; ev.created = t; ev.planned_start = t; ev.plant = (int32_t)p;
+    ev.pump = (uint8_t)unit; ev.action = (uint8_t)action; ev.kind = NPB_MAINT_EVENT_OPERATOR_TURBINE;
+    npd_maint_log(L, ok, ev);
+  }
+}
+
 #ifndef NPB_BUILD_F32
 /* calibration aid for the HBM traffic counters: reads every arena column and writes it back unchanged,
  * with exactly the access shape of the step kernel (8 B per lane, one 512-B line per wave and column),
@@ -1246,11 +1313,20 @@ static void NPB_LAUNCHER(operator_component_maint)(int n_plants, size_t npad, vo
   L.records = log_records; L.cursor = log_records ? log_cursor : nullptr; L.capacity = log_records ? log_capacity : 0;
   hipLaunchKernelGGL(npb_operator_component_maint_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, O, L, npad, (npd_real_t *)arena);
 }
+/* npb_perform_turbine_maintenance: the caller's order columns; turbine = the handle's mode steps the turbine; log_* as above */
+static void NPB_LAUNCHER(operator_turbine_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *unit, uint8_t *success,
+                                                 int turbine, npb_maint_event_t *log_records, uint32_t *log_cursor, int log_capacity, hipStream_t stream) {
+  npd_turbine_orders_t O;
+  O.action = action; O.unit = unit; O.success = success; O.n_plants = n_plants; O.turbine = turbine;
+  npd_maint_log_t L;
+  L.records = log_records; L.cursor = log_records ? log_cursor : nullptr; L.capacity = log_records ? log_capacity : 0;
+  hipLaunchKernelGGL(npb_operator_turbine_maint_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, O, L, npad, (npd_real_t *)arena);
+}
 /* not const: clang emits a namespace-scope const into the device code too, where these host functions do not exist */
 extern "C" npb_launchers_t NPB_LAUNCHER(table) = {
   NPB_LAUNCHER(step), NPB_LAUNCHER(maint), NPB_LAUNCHER(observe), NPB_LAUNCHER(init), NPB_LAUNCHER(reset),
   NPB_LAUNCHER(field_get), NPB_LAUNCHER(field_set), NPB_LAUNCHER(gather), NPB_LAUNCHER(restore), NPB_LAUNCHER(episode),
-  NPB_LAUNCHER(operator_maint), NPB_LAUNCHER(operator_component_maint),
+  NPB_LAUNCHER(operator_maint), NPB_LAUNCHER(operator_component_maint), NPB_LAUNCHER(operator_turbine_maint),
 };
 #ifndef NPB_BUILD_F32
 /* npb_reset / npb_reset_reference / npb_restore: the episode counters (len, ret) and the carried start entries (start: -1, not from

@@ -509,8 +509,9 @@ class BatchedPlantEnv:
 
         Only the ordered pump's state changes: no work order is created, ``info["maintenance_event_count"]`` and the ``maint.*`` /
         ``mpump.*`` columns do not move (the reference's direct call bypasses AutoMaintenanceSystem too); with the maintenance log
-        on, each successful order is one ``operator_maintenance`` record.  Not covered: operator-created work orders, maintenance of
-        the turbine (steam generators and condenser: ``perform_component_maintenance``), and -- with ``enable_diagnostics`` -- the
+        on, each successful order is one ``operator_maintenance`` record.  Steam generators and condenser:
+        ``perform_component_maintenance``; the turbine: ``perform_turbine_maintenance``.  Not covered: operator-created work orders,
+        and -- with ``enable_diagnostics`` -- the
         per-pump ``maintenance_occurred`` / ``oil_top_off_occurred`` / ``maintenance_action`` diagnostics rows, which an operator
         action leaves alone."""
         if isinstance(action, str):
@@ -555,8 +556,8 @@ class BatchedPlantEnv:
         Only the sections the action touches change, on the ordering plants only.  No work order, counter, ``maint.*`` / ``mpump.*``
         column moves; with the maintenance log on, each successful order is one ``operator_component_maintenance`` record.  The
         state-log columns that show attributes the state does not carry (a generator's cleaning cycles and years since cleaning, the
-        chemistry's time since treatment) do not follow an operator action.  Not covered: turbine maintenance, work orders for these
-        components."""
+        chemistry's time since treatment) do not follow an operator action.  Not covered: work orders for these components.  The
+        turbine: ``perform_turbine_maintenance``."""
         if isinstance(action, str) or component not in _lib.COMPONENT_KINDS:
             action = _lib.component_action_index(component, action)       # ValueError for an unknown kind or name, before anything else
         if isinstance(unit, str):
@@ -577,6 +578,49 @@ class BatchedPlantEnv:
         amount = None if tubes_to_plug is None else self._order_column("tubes_to_plug", tubes_to_plug, torch.float64, float)
         ok = self._orders["success"]
         _lib.check(self.L.npb_perform_component_maintenance(self._h, self._p(a), self._p(k), self._p(c), self._p(amount), self._p(ok), self._stream()), self._h)
+        return ok
+
+    def perform_turbine_maintenance(self, component, action, unit=None, mask=None) -> torch.Tensor:
+        """Operator-ordered maintenance of the turbine, one of its bearings, its bearing-lubrication system or one of its stages between
+        two steps (npb_perform_turbine_maintenance): what the reference's ``perform_maintenance(action)`` of that object
+        (turbine/enhanced_physics.py:1055, turbine/rotor_dynamics.py:381, turbine/turbine_bearing_lubrication.py:481,
+        turbine/stage_system.py:341) does to every ordered plant, at once, on the device.
+
+        ``component``: ``"turbine"``, ``"bearing"``, ``"lubrication"`` or ``"stage"``.  ``action``: a maintenance type of that component
+        in ``_lib.TURBINE_ACTIONS``, its catalog index, or an int32 column of catalog indices (``-1`` = nothing for that plant; the index
+        names the component, so a column may mix kinds); an unknown name raises ValueError before any device work, and so does, with its
+        own message, a handler that is not offered because the carried state cannot hold what it does
+        (``_lib.TURBINE_ACTIONS_NOT_OFFERED``: a stage's ``"cleaning"``).  ``unit``: the bearing 0..3 / ``"TB-001"``..``"TB-004"`` or the
+        stage 0..13 / ``"HP-1"``..``"LP-6"``, or an int32 column; None = 0; ignored by actions on the turbine and the lubrication system.
+        ``mask`` as in ``perform_maintenance``.  Returns the ``success`` column (uint8, the env's own buffer): 1 where the reference's
+        result says success; ``thrust_bearing_adjustment`` succeeds on the thrust bearing (2, ``"TB-003"``) only; in the modes that do not
+        step the turbine (``primary``, ``primary_sg``) every order gives 0.  No host synchronisation.
+
+        Only ``turb.*`` members change, or the ordered stage's ``tstg.stage_deposit_thickness`` / ``stage_blade_wear_factor`` /
+        ``stage_efficiency_degradation``, on the ordering plants only.  No work order, counter, ``maint.*`` / ``mpump.*`` column moves;
+        with the maintenance log on, each successful order is one ``operator_turbine_maintenance`` record.  With
+        ``enable_diagnostics`` the accumulator rows (the bearings' clearance increase, the stage system's efficiency) do not follow an
+        operator action, nor do the state-log columns that show attributes the state does not carry.  Not covered: work orders and
+        automatic maintenance for the turbine, and the single-plant facade (``NuclearPlantSimulator``'s turbine has no
+        ``perform_maintenance``: out of scope here)."""
+        from . import maintlog
+        if isinstance(action, str) or component not in _lib.TURBINE_KINDS:
+            action = _lib.turbine_action_index(component, action)       # ValueError for an unknown kind or name, before anything else
+        if isinstance(unit, str):
+            ids = {"bearing": maintlog.TURBINE_BEARING_IDS, "stage": maintlog.TURBINE_STAGE_IDS}.get(component, ())
+            if unit not in ids:
+                raise ValueError("unknown unit %r of a turbine %s" % (unit, component))
+            unit = ids.index(unit)
+        if not hasattr(self.L, "npb_perform_turbine_maintenance"):
+            raise _lib.NpbError("libnpb.so has no npb_perform_turbine_maintenance (older than ABI 149): rebuild")
+        if getattr(self, "_orders", None) is None:
+            self._orders = {}
+            with torch.cuda.device(self.device):
+                self._orders["success"] = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+        a = self._masked_order(self._order_column("turbine_action", action, torch.int32, int), mask)
+        k = None if unit is None else self._order_column("unit", unit, torch.int32, int)
+        ok = self._orders["success"]
+        _lib.check(self.L.npb_perform_turbine_maintenance(self._h, self._p(a), self._p(k), self._p(ok), self._stream()), self._h)
         return ok
 
     def snapshot(self) -> None:

@@ -1,8 +1,8 @@
 """The maintenance event log as the reference's data-gen runner exports it.
 
 ``npb_set_maintenance_log`` (include/npb.h) has the automatic maintenance append one ``npb_maint_event_t`` record (include/npb_maint.h)
-per work order it creates or completes, and ``npb_perform_maintenance`` / ``npb_perform_component_maintenance`` one per action a caller
-ordered.  This module turns drained
+per work order it creates or completes, and ``npb_perform_maintenance`` / ``npb_perform_component_maintenance`` /
+``npb_perform_turbine_maintenance`` one per action a caller ordered.  This module turns drained
 records into columns named as the reference's ``MaintenanceScenarioRunner.export_data`` writes its ``*_work_orders.csv`` / ``*_maintenance_actions.csv``
 (maintenance_scenario_runner.py:1071-1231) and as ``WorkOrderManager`` holds the orders (work_orders.py).  Host code only.
 """
@@ -16,13 +16,23 @@ import numpy as np
 EVENT_DTYPE = np.dtype([("time", "<f8"), ("created", "<f8"), ("planned_start", "<f8"), ("plant", "<i4"), ("order", "<i4"),
                         ("trigger", "<u2"), ("pump", "u1"), ("action", "u1"), ("kind", "u1"), ("priority", "u1"), ("bearing", "u1"),
                         ("reserved", "u1")])
-CREATED, COMPLETED, OPERATOR, OPERATOR_COMPONENT = 0, 1, 2, 3    # NPB_MAINT_EVENT_*
+CREATED, COMPLETED, OPERATOR, OPERATOR_COMPONENT, OPERATOR_TURBINE = 0, 1, 2, 3, 4    # NPB_MAINT_EVENT_*
 # OPERATOR: an action ordered through npb_perform_maintenance (BatchedPlantEnv.perform_maintenance) and carried out at once: no work
 # order (order 0, id ""), created = planned start = time = the plant's clock at the call
 # OPERATOR_COMPONENT: the same through npb_perform_component_maintenance (BatchedPlantEnv.perform_component_maintenance): ``action`` is an
 # index of the COMPONENT catalog (include/npb_maint.h NPB_COMPONENT_ACTIONS, _lib.COMPONENT_ACTIONS), the ``pump`` byte the unit
 # (generator 0..2, ejector 0..1; 0 for the system and the condenser)
-EVENT_TYPES = ("work_order_created", "work_order_completed", "operator_maintenance", "operator_component_maintenance")
+# OPERATOR_TURBINE: the same through npb_perform_turbine_maintenance (BatchedPlantEnv.perform_turbine_maintenance): ``action`` is an index of
+# the TURBINE catalog (NPB_TURBINE_ACTIONS, _lib.TURBINE_ACTIONS), the ``pump`` byte the unit (bearing 0..3, stage 0..13; 0 for the turbine and
+# the lubrication system)
+EVENT_TYPES = ("work_order_created", "work_order_completed", "operator_maintenance", "operator_component_maintenance",
+               "operator_turbine_maintenance")
+# the reference's ids of the turbine's objects as the data-gen runner's plant names them: the turbine's config.system_id, the keys of
+# rotor_dynamics.bearings and stage_system.stages, the lubrication system's config.system_id (tests/golden/operator_turbine/ot4_long_run.npz
+# records them from the live objects)
+TURBINE_ID, TURBINE_LUBRICATION_ID = "SECONDARY-COMP-001-TURB", "TB-LUB-001"
+TURBINE_BEARING_IDS = ("TB-001", "TB-002", "TB-003", "TB-004")
+TURBINE_STAGE_IDS = tuple(["HP-%d" % k for k in range(1, 9)] + ["LP-%d" % k for k in range(1, 7)])
 PRIORITY_NAMES = {1: "LOW", 2: "MEDIUM", 3: "HIGH", 4: "CRITICAL", 5: "EMERGENCY"}    # work_orders.py Priority
 BEARING_NAMES = {1: "motor", 2: "pump", 3: "thrust"}       # NPB_BEARING_*: the threshold's component_id
 
@@ -48,7 +58,8 @@ def sort_events(rec: np.ndarray) -> np.ndarray:
     operator action follows the step whose clock it carries, so it sorts behind that step's work-order events; two operator actions of
     one plant on one pump at one time keep the order they are given in (the device's)."""
     rec = np.asarray(rec, dtype=EVENT_DTYPE)
-    rank = np.where(rec["kind"] == COMPLETED, 0, np.where(rec["kind"] == OPERATOR, 2, np.where(rec["kind"] == OPERATOR_COMPONENT, 3, 1)))
+    rank = np.where(rec["kind"] == COMPLETED, 0, np.where(rec["kind"] == OPERATOR, 2, np.where(rec["kind"] == OPERATOR_COMPONENT, 3,
+                                                                                             np.where(rec["kind"] == OPERATOR_TURBINE, 4, 1))))
     return rec[np.lexsort((rec["pump"], rank, rec["time"], rec["plant"]))]
 
 
@@ -62,23 +73,35 @@ def component_id(kind: str, unit: int) -> str:
     return {"steam_generator_system": "SG-SYSTEM", "condenser": "CONDENSER"}[kind]
 
 
+def turbine_component_id(kind: str, unit: int) -> str:
+    """the reference's id of the object an operator turbine action was ordered on"""
+    if kind == "bearing":
+        return TURBINE_BEARING_IDS[unit] if 0 <= unit < len(TURBINE_BEARING_IDS) else "TB-?"
+    if kind == "stage":
+        return TURBINE_STAGE_IDS[unit] if 0 <= unit < len(TURBINE_STAGE_IDS) else "STAGE-?"
+    return {"turbine": TURBINE_ID, "lubrication": TURBINE_LUBRICATION_ID}[kind]
+
+
 def columns(rec: np.ndarray, actions: Sequence[str], params: Sequence[str], handlers: Sequence[int]) -> Dict[str, np.ndarray]:
     """Drained records -> columns, sorted by ``sort_events``.  ``actions`` / ``params`` / ``handlers``: the catalogs of
     include/npb_maint.h (``_lib.MAINT_ACTIONS``, ``_lib.MAINT_PARAMS``, ``npb_maint_action_has_handler``).  A completion takes its
     priority from its creation record when that record is among ``rec``, else it has none ("").  An operator action
-    (``event_type`` "operator_maintenance", "operator_component_maintenance") has no work order: its id, priority and work-order type are
-    "", its dates the time of the call; a component action is named from the component catalog and its object (``component_id``)."""
-    from ._lib import COMPONENT_ACTIONS
+    (``event_type`` "operator_maintenance", "operator_component_maintenance", "operator_turbine_maintenance") has no work order: its id,
+    priority and work-order type are "", its dates the time of the call; a component action is named from the component catalog and its
+    object (``component_id``), a turbine action from the turbine catalog (``turbine_component_id``)."""
+    from ._lib import COMPONENT_ACTIONS, TURBINE_ACTIONS
     rec = sort_events(rec)
     n = len(rec)
     kind = rec["kind"].astype(np.int64)
     created = kind == CREATED
     prio_of = {(int(p), int(o)): int(q) for p, o, q in zip(rec["plant"][created], rec["order"][created], rec["priority"][created])}
-    operator = (kind == OPERATOR) | (kind == OPERATOR_COMPONENT)
+    operator = (kind == OPERATOR) | (kind == OPERATOR_COMPONENT) | (kind == OPERATOR_TURBINE)
     prio = np.array([int(q) if k == CREATED else (0 if op else prio_of.get((int(p), int(o)), 0))
                      for k, op, p, o, q in zip(kind, operator, rec["plant"], rec["order"], rec["priority"])], dtype=np.int64)
-    action = [COMPONENT_ACTIONS[int(a)][1] if k == OPERATOR_COMPONENT else actions[int(a)] for a, k in zip(rec["action"], kind)]
-    component = [component_id(COMPONENT_ACTIONS[int(a)][0], int(u)) if k == OPERATOR_COMPONENT else "FWP-%d" % (int(u) + 1)
+    action = [COMPONENT_ACTIONS[int(a)][1] if k == OPERATOR_COMPONENT else TURBINE_ACTIONS[int(a)][1] if k == OPERATOR_TURBINE else actions[int(a)]
+              for a, k in zip(rec["action"], kind)]
+    component = [component_id(COMPONENT_ACTIONS[int(a)][0], int(u)) if k == OPERATOR_COMPONENT else
+                 turbine_component_id(TURBINE_ACTIONS[int(a)][0], int(u)) if k == OPERATOR_TURBINE else "FWP-%d" % (int(u) + 1)
                  for u, a, k in zip(rec["pump"], rec["action"], kind)]
     time = rec["time"].astype(np.float64)
     return {
@@ -99,7 +122,7 @@ def columns(rec: np.ndarray, actions: Sequence[str], params: Sequence[str], hand
         "actual_completion_date": np.where((kind == COMPLETED) | operator, time, np.nan),
         "bearing": np.array([BEARING_NAMES.get(int(b), "") for b in rec["bearing"]], dtype=object),
         "trigger_parameters": np.array([";".join(params[q] for q in range(len(params)) if (int(m) >> q) & 1) for m in rec["trigger"]], dtype=object),
-        "has_handler": np.array([k == OPERATOR_COMPONENT or bool(handlers[int(a)]) for a, k in zip(rec["action"], kind)], dtype=bool) if n else np.zeros(0, dtype=bool),
+        "has_handler": np.array([k in (OPERATOR_COMPONENT, OPERATOR_TURBINE) or bool(handlers[int(a)]) for a, k in zip(rec["action"], kind)], dtype=bool) if n else np.zeros(0, dtype=bool),
     }
 
 
