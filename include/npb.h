@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define NPB_VERSION 149 /* 0.1.4.9: npb_perform_turbine_maintenance, npb_turbine_* catalog queries, NPB_MAINT_EVENT_OPERATOR_TURBINE (maintenance of the turbine, its bearings, lubrication system and stages a caller orders); 0.1.4.8: npb_perform_component_maintenance, npb_component_* catalog queries, NPB_MAINT_EVENT_OPERATOR_COMPONENT (maintenance of steam generators, condenser and ejectors a caller orders); 0.1.4.7: npb_perform_maintenance, NPB_MAINT_EVENT_OPERATOR (maintenance a caller orders, carried out on the device between two steps); 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
+#define NPB_VERSION 150 /* 0.1.5.0: npb_set_component_maintenance, npb_default_component_maintenance_table, npb_component_maint_* catalog queries, npb_get / npb_set_component_maintenance_state, NPB_MAINT_EVENT_COMPONENT_CREATED / _COMPLETED (automatic maintenance of steam generators and condenser in one work-order queue with the feedwater pumps); 0.1.4.9: npb_perform_turbine_maintenance, npb_turbine_* catalog queries, NPB_MAINT_EVENT_OPERATOR_TURBINE (maintenance of the turbine, its bearings, lubrication system and stages a caller orders); 0.1.4.8: npb_perform_component_maintenance, npb_component_* catalog queries, NPB_MAINT_EVENT_OPERATOR_COMPONENT (maintenance of steam generators, condenser and ejectors a caller orders); 0.1.4.7: npb_perform_maintenance, NPB_MAINT_EVENT_OPERATOR (maintenance a caller orders, carried out on the device between two steps); 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
 #ifndef NPB_API
 #define NPB_API __attribute__((visibility("default")))
 #endif
@@ -286,6 +286,37 @@ NPB_API int npb_turbine_num_actions(void);
 NPB_API const char *npb_turbine_action_name(int a);
 NPB_API int npb_turbine_action_kind(int a);
 NPB_API const char *npb_turbine_kind_name(int kind);
+/* Automatic maintenance of the three steam generators and the condenser, in ONE work-order queue with the feedwater pumps, as the
+ * reference's AutoMaintenanceSystem runs them (nuclear_sim_amd/csrc/npd_component_auto.h): after every step the scan goes over FWP-1..4,
+ * SG-0..2 and the condenser in that order, every order created is numbered from the one counter maint.work_orders_created, and a due
+ * check carries out ONE due order, the earliest created of any component -- so switching this on also changes WHEN a pump's order is
+ * carried out.  table = the rows (include/npb_maint.h npb_component_maint_table_t; npb_default_component_maintenance_table = the
+ * data-gen composer's), NULL switches the feature off; off is the default and leaves every result as it was.  Needs
+ * params.maint_enabled and NPB_MODE_FULL (npb_step says so by name otherwise).  While it is on, npb_step launches the step kernel of a
+ * handle WITHOUT automatic maintenance and then one rule kernel for pumps and components together (npb_maint_all_kernel).
+ * The per-plant state of the rule -- a last-violation stamp per (component, row); per (component, action) the open order's number,
+ * creation time, planned start, priority and the last trigger -- lives in a side buffer the handle owns, NOT in the arena:
+ * NPB_CMAINT_SIDE_DOUBLES doubles per plant (include/npb_maint.h).  It is allocated, as a freshly built plant's, when the feature is
+ * first switched on, and treated as the mpump section is: npb_reset clears it (masked: the masked plants'), npb_reset_reference leaves it
+ * alone, npb_snapshot records it, npb_restore / the autoreset / npb_restore_bank put it back with the plant (a snapshot or bank recorded
+ * without the feature is refused by name, and so is a bank handle that has not got it on).  A checkpoint that saves the arena must save it
+ * too: npb_get_component_maintenance_state / npb_set_component_maintenance_state copy it to / from a buffer (host or device) of
+ * npb_component_maintenance_state_bytes(h) bytes, member-major: member m of plant p at [m * n_plants + p]; both synchronise the stream.
+ * The call synchronises the device before it uploads the table.  The side state is keyed by ROW (an open order and its trigger stamp
+ * are filed under the first row of their component that names the action): a second call with another table while orders are open keeps
+ * them attached to their rows, so an open order is then carried out with the action its row names in the NEW table, and a row that
+ * changed its action inherits the old action's trigger stamp.  Change a table between episodes (after npb_reset), or with no order open
+ * (wo_order all zero in the side state).
+ * With a maintenance log set the rule appends NPB_MAINT_EVENT_COMPONENT_CREATED / _COMPONENT_COMPLETED records beside the pumps'.
+ * NPB_EINVAL for a row whose comparison / priority is out of range or whose action is not a COMPONENT catalog entry of the row's kind. */
+NPB_API int npb_set_component_maintenance(NpbHandle *h, const npb_component_maint_table_t *table);
+NPB_API void npb_default_component_maintenance_table(npb_component_maint_table_t *table);
+NPB_API int npb_component_maint_num_params(void);
+NPB_API const char *npb_component_maint_param_name(int k);
+NPB_API int npb_component_maint_param_kind(int k);      /* NPB_COMPONENT_SG | NPB_COMPONENT_COND */
+NPB_API size_t npb_component_maintenance_state_bytes(const NpbHandle *h);
+NPB_API int npb_get_component_maintenance_state(NpbHandle *h, double *buf, void *stream);
+NPB_API int npb_set_component_maintenance_state(NpbHandle *h, const double *buf, void *stream);
 
 /* re-initialise plants to the construction-time state; mask (device, uint8[n], NULL = all) selects plants.
  * Stands in for constructing a fresh simulator (the data-gen runner's episode start,

@@ -247,6 +247,74 @@ def maint_table_from_thresholds(thresholds: dict) -> "NpbMaintTable":
         t.bearing[k] = MAINT_BEARINGS.get(cfg.get("component_id"), 0)
     return t
 
+# include/npb_maint.h NPB_CMAINT_PARAMS: the rows of the automatic maintenance of steam generators and condenser
+# (npb_set_component_maintenance), (component kind, name in the state log) per index; load() holds it against the library's own catalog
+CMAINT_PARAMS = (("steam_generator", "tsp_fouling_fraction"), ("steam_generator", "tube_wall_temperature"), ("steam_generator", "steam_quality"),
+                 ("condenser", "fouling_resistance"), ("condenser", "tube_leak_rate"))
+# the one action a row may name from outside COMPONENT_ACTIONS (NPB_CA_AUTO_CONDENSER_TUBE_PLUGGING): the composer's tube_leak_rate row orders
+# condenser_tube_plugging, whose handler raises in the reference; as a work order it is created, counted and completed without success
+CMAINT_AUTO_ACTIONS = {("condenser", "condenser_tube_plugging"): len(COMPONENT_ACTIONS)}
+CMAINT_NPARAM = len(CMAINT_PARAMS)
+CMAINT_COMPONENTS = ("SG-0", "SG-1", "SG-2", "condenser")      # the scan order behind FWP-1..4; slot = component * CMAINT_NROW + row
+CMAINT_NROW = 3
+CMAINT_STATE_MEMBERS = ("last_violation_time", "wo_order", "wo_created", "wo_planned_start", "wo_priority", "last_trigger_time")   # NPB_CMS_*
+CMAINT_SIDE_DOUBLES = len(CMAINT_STATE_MEMBERS) * len(CMAINT_COMPONENTS) * CMAINT_NROW
+# rows of the reference's configuration for these components whose parameter never resolves in the component's state-log row
+# (StateManager._find_parameter_in_row_data gives None: never compared): dropped, as the reference's scan drops them
+CMAINT_ROWS_UNRESOLVED = {"steam_generator": ("efficiency",), "condenser": ("tube_cleanliness", "vacuum_level", "thermal_performance_factor")}
+# rows that DO resolve on the reference and are not scanned on the device, with the reason (DESIGN.md "Automatic maintenance of steam
+# generators and condenser"): dropped by component_maint_table_from_thresholds
+CMAINT_ROWS_NOT_SCANNED = {}
+# component kinds of the reference's configuration whose rows are not scanned, with the measured reason: a table that carries one is refused
+_TURBINE_REASON = ("the only row of the turbine's stages and of the turbine that resolves on the reference is `efficiency` (< 0.30, efficiency_analysis), "
+                   "and the reference cannot fire it: every step leaves a stage's actual_efficiency at max(0.7, design - degradation) "
+                   "(turbine/stage_system.py:323-326), 0.7 at the lowest with the degradation, deposits and blade wear poked to their worst "
+                   "(tests/golden/auto_components/silent_rows.json, turbine_efficiency_probe); a table with a turbine row that could fire "
+                   "would need the stages in the scan, which they are not")
+CMAINT_KINDS_NOT_SCANNED = {"turbine": _TURBINE_REASON, "turbine_stage": _TURBINE_REASON}
+
+
+class NpbComponentMaintTable(ctypes.Structure):
+    """npb_component_maint_table_t (include/npb_maint.h): one row per parameter of CMAINT_PARAMS, the generators' rows shared by SG-0..2"""
+    _fields_ = [("threshold", ctypes.c_double * CMAINT_NPARAM), ("cooldown_hours", ctypes.c_double * CMAINT_NPARAM),
+                ("rank", ctypes.c_int * CMAINT_NPARAM), ("comparison", ctypes.c_int * CMAINT_NPARAM),
+                ("action", ctypes.c_int * CMAINT_NPARAM), ("priority", ctypes.c_int * CMAINT_NPARAM)]
+
+
+def component_maint_table_from_thresholds(thresholds: dict) -> "NpbComponentMaintTable":
+    """{"steam_generator": {...}, "condenser": {...}} -- each the reference's thresholds dict of that component
+    (StateManager.maintenance_thresholds['SG-0'] / ['SECONDARY-COMP-001-COND'], in ITS order) -> table (host only, no library needed).  A
+    missing kind has no rows.  Rows of CMAINT_ROWS_UNRESOLVED and CMAINT_ROWS_NOT_SCANNED are dropped; any other name outside
+    CMAINT_PARAMS, a comparison or priority the reference does not know, and an action outside that component's part of
+    COMPONENT_ACTIONS are refused (NpbError)."""
+    t = NpbComponentMaintTable()
+    for k in range(CMAINT_NPARAM):
+        t.rank[k] = -1
+    for kind, rows in thresholds.items():
+        if kind in CMAINT_KINDS_NOT_SCANNED:
+            raise NpbError("component thresholds of %r are not scanned on the device: %s" % (kind, CMAINT_KINDS_NOT_SCANNED[kind]))
+        if kind not in ("steam_generator", "condenser"):
+            raise NpbError("component thresholds of %r: the automatic maintenance covers 'steam_generator' and 'condenser'" % (kind,))
+        for rank, (name, cfg) in enumerate(rows.items()):
+            if name in CMAINT_ROWS_UNRESOLVED[kind] or (kind, name) in CMAINT_ROWS_NOT_SCANNED or cfg.get("threshold") is None:
+                continue
+            if (kind, name) not in CMAINT_PARAMS:
+                raise NpbError("unknown %s threshold parameter %r: not in the component parameter catalog (include/npb_maint.h NPB_CMAINT_PARAMS)" % (kind, name))
+            k = CMAINT_PARAMS.index((kind, name))
+            action, comparison = cfg.get("action"), cfg.get("comparison", "greater_than")
+            if (kind, action) not in COMPONENT_ACTIONS and (kind, action) not in CMAINT_AUTO_ACTIONS:
+                raise NpbError("maintenance action %r of %s threshold %r is not in the component catalog (include/npb_maint.h)" % (action, kind, name))
+            if comparison not in MAINT_COMPARISONS:
+                raise NpbError("unknown comparison %r of %s threshold %r" % (comparison, kind, name))
+            t.rank[k] = rank
+            t.threshold[k] = float(cfg["threshold"])
+            t.cooldown_hours[k] = float(cfg.get("cooldown_hours", 24.0))
+            t.comparison[k] = MAINT_COMPARISONS.index(comparison)
+            t.action[k] = CMAINT_AUTO_ACTIONS[(kind, action)] if (kind, action) in CMAINT_AUTO_ACTIONS else COMPONENT_ACTIONS.index((kind, action))
+            t.priority[k] = MAINT_PRIORITIES.get(str(cfg.get("priority", "MEDIUM")).upper(), 2)
+    return t
+
+
 _lib = None
 
 
@@ -352,6 +420,20 @@ def load():
                         for a in range(L.npb_turbine_num_actions()))
         if catalog != TURBINE_ACTIONS:
             raise NpbError("libnpb.so's turbine catalog is not this binding's TURBINE_ACTIONS: rebuild")
+    if hasattr(L, "npb_set_component_maintenance"):     # ABI 150: automatic maintenance of steam generators and condenser
+        L.npb_set_component_maintenance.argtypes = [vp, ctypes.POINTER(NpbComponentMaintTable)]
+        L.npb_default_component_maintenance_table.argtypes = [ctypes.POINTER(NpbComponentMaintTable)]
+        L.npb_component_maint_param_name.restype = ctypes.c_char_p
+        L.npb_component_maint_param_name.argtypes = [ci]
+        L.npb_component_maint_param_kind.argtypes = [ci]
+        L.npb_component_maintenance_state_bytes.argtypes = [vp]
+        L.npb_component_maintenance_state_bytes.restype = ctypes.c_size_t
+        L.npb_get_component_maintenance_state.argtypes = [vp, vp, vp]
+        L.npb_set_component_maintenance_state.argtypes = [vp, vp, vp]
+        catalog = tuple((L.npb_component_kind_name(L.npb_component_maint_param_kind(k)).decode(), L.npb_component_maint_param_name(k).decode())
+                        for k in range(L.npb_component_maint_num_params()))
+        if catalog != CMAINT_PARAMS:
+            raise NpbError("libnpb.so's component parameter catalog is not this binding's CMAINT_PARAMS: rebuild")
     if hasattr(L, "npb_noise_seed"):     # ABI 145: heat-source noise streams on the device
         L.npb_noise_seed.argtypes = [vp, vp, vp]
         L.npb_noise_fill.argtypes = [vp, ci, vp, vp]

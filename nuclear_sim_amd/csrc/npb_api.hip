@@ -33,6 +33,11 @@ struct NpbHandle {
   int step_kernel;                 /* 0 = chosen by batch size, 1 = one-wave kernel, 2 = two-wave kernel, 3 = its two-waves-per-SIMD build, 4 = one-wave with streaming stores, 5 = four-wave kernel (npb_set_step_kernel) */
   npb_maint_table_t maint_table;   /* thresholds of the automatic maintenance (include/npb_maint.h) */
   bool maint_table_custom;         /* set through npb_set_maintenance_table: the table is then taken as it is */
+  /* npb_set_component_maintenance: automatic maintenance of the steam generators and the condenser in one queue with the pumps' */
+  bool cm_on; npb_component_maint_table_t cm_table;
+  void *cm_side;       /* [the table as the device reads it][NPB_CMAINT_SIDE_DOUBLES][pitch] doubles (npb_kernels.hip), allocated when first switched on */
+  double *cm_snap;     /* npb_snapshot with the feature on: the side state beside the snapshot arena ([NPB_CMAINT_SIDE_DOUBLES][pitch]), or NULL */
+  double *cm_bank; size_t cm_bank_pitch, cm_bank_doubles;   /* npb_set_start_bank from a handle with the feature on: its side state, its pitch, the allocation */
   void *snap;          /* npb_snapshot: the episode-start arena, the arena's layout, or NULL */
   int32_t *ep_len; double *ep_ret; /* npb_set_autoreset: carried steps / summed reward of each plant's running episode ([pitch] each), or NULL */
   bool autoreset; int max_episode_steps;
@@ -110,6 +115,20 @@ static npb_source_t source_of(const NpbHandle *h, bool bank) {
 }
 /* npb_reset / npb_reset_reference (counters) and npb_restore: the episode counters (with counters) and the carried start entries of the
  * plants of mask (NULL = every lane of the pitch) to 0 and -1 */
+/* the component maintenance's side state as a restore takes it along (npb_kernels.h): from the snapshot's copy or the bank's.  false = the
+ * feature is on and the source was recorded without it */
+static double *cm_state(const NpbHandle *h) { return (double *)((char *)h->cm_side + npb_launch_cmaint_state_offset()); }
+static bool cm_restore_of(const NpbHandle *h, bool bank, npb_cmaint_restore_t *cm) {
+  *cm = npb_cmaint_restore_t{};
+  if (!h->cm_on) return true;
+  const double *src = bank ? h->cm_bank : h->cm_snap;
+  if (!src) return false;
+  cm->state = cm_state(h); cm->src = src; cm->pitch = h->pitch; cm->src_pitch = bank ? h->cm_bank_pitch : h->pitch;
+  return true;
+}
+static const char *const g_cm_no_snapshot = "the component maintenance is on (npb_set_component_maintenance) and the snapshot was taken without it: npb_snapshot again";
+static const char *const g_cm_no_bank = "the component maintenance is on (npb_set_component_maintenance) and the start bank was set without it: npb_set_start_bank again, "
+                                        "from a handle that has it";
 static void clear_episodes(NpbHandle *h, const uint8_t *mask, bool counters, hipStream_t stream) {
   int32_t *len = counters ? h->ep_len : nullptr;
   if (len || h->ep_start) npb_launch_episode_clear(mask, len, counters ? h->ep_ret : nullptr, h->ep_start, h->n_plants, h->pitch, stream);
@@ -309,6 +328,9 @@ int npb_destroy(NpbHandle *h) {
   if (h->convert) (void)hipFree(h->convert);
   if (h->plan_dev) (void)hipFree(h->plan_dev);
   if (h->snap) (void)hipFree(h->snap);
+  if (h->cm_side) (void)hipFree(h->cm_side);
+  if (h->cm_snap) (void)hipFree(h->cm_snap);
+  if (h->cm_bank) (void)hipFree(h->cm_bank);
   if (h->ep_len) (void)hipFree(h->ep_len);
   if (h->bank) (void)hipFree(h->bank);
   if (h->ep_start) (void)hipFree(h->ep_start);
@@ -427,11 +449,81 @@ int npb_perform_turbine_maintenance(NpbHandle *h, const int32_t *action, const i
 }
 void npb_default_maintenance_table(npb_maint_table_t *table) { if (table) npb_maint_table_default(table); }
 
+void npb_default_component_maintenance_table(npb_component_maint_table_t *table) { if (table) npb_component_maint_table_default(table); }
+static const char *const g_cmaint_params[] = {
+#define NPB__X(kind, id, name) name,
+  NPB_CMAINT_PARAMS(NPB__X)
+#undef NPB__X
+};
+static const int g_cmaint_param_kinds[] = {
+#define NPB__X(kind, id, name) NPB_COMPONENT_##kind,
+  NPB_CMAINT_PARAMS(NPB__X)
+#undef NPB__X
+};
+static_assert(sizeof(g_cmaint_params) / sizeof(g_cmaint_params[0]) == NPB_CMAINT_NPARAM, "component parameter catalog");
+int npb_component_maint_num_params(void) { return NPB_CMAINT_NPARAM; }
+const char *npb_component_maint_param_name(int k) { return k >= 0 && k < NPB_CMAINT_NPARAM ? g_cmaint_params[k] : nullptr; }
+int npb_component_maint_param_kind(int k) { return k >= 0 && k < NPB_CMAINT_NPARAM ? g_cmaint_param_kinds[k] : -1; }
+
+int npb_set_component_maintenance(NpbHandle *h, const npb_component_maint_table_t *table) {
+  if (!h) return NPB_EINVAL;
+  /* either way the rule changes hands between the step kernels and npb_maint_all_kernel, which keeps no cooldown cache: the pump
+   * stamps it has moved are unknown to the step kernels' screen */
+  h->maint_cache_stale = true;
+  if (!table) { h->cm_on = false; return NPB_OK; }
+  if (h->params.mode != NPB_MODE_FULL) return fail(h, NPB_EINVAL, "npb_set_component_maintenance: full mode only (the other modes step no condenser)");
+  for (int q = 0; q < NPB_CMAINT_NPARAM; q++) {
+    if (table->rank[q] < 0) continue;
+    if (table->comparison[q] < 0 || table->comparison[q] > NPB_CMP_NOT_EQUALS || table->priority[q] < NPB_PRIO_LOW || table->priority[q] > NPB_PRIO_EMERGENCY)
+      return fail(h, NPB_EINVAL, "npb_set_component_maintenance: comparison / priority code out of range");
+    if (table->action[q] == NPB_CA_AUTO_CONDENSER_TUBE_PLUGGING && g_cmaint_param_kinds[q] == NPB_COMPONENT_COND) continue;
+    if (table->action[q] < 0 || table->action[q] >= NPB_COMPONENT_NACT || g_component_actions[table->action[q]].kind != g_cmaint_param_kinds[q])
+      return fail(h, NPB_EINVAL, "npb_set_component_maintenance: a row's action is not an entry of the COMPONENT catalog (include/npb_maint.h) of the row's component kind");
+  }
+  NPB_USE_DEVICE(h);
+  const bool fresh = !h->cm_side;
+  if (fresh) {
+    hipError_t e = hipMalloc(&h->cm_side, npb_launch_cmaint_side_bytes(h->pitch));
+    if (e != hipSuccess) { h->cm_side = nullptr; return fail(h, NPB_EHIP, "npb_set_component_maintenance: hipMalloc of the side state failed", e); }
+  }
+  h->cm_table = *table;
+  /* the call has no stream: whatever the handle's earlier steps have in flight, on any stream, reads the old table first */
+  NPB_HIP(h, hipDeviceSynchronize());
+  NPB_HIP(h, hipMemcpy(h->cm_side, &h->cm_table, sizeof(h->cm_table), hipMemcpyHostToDevice));      /* (npd_cmaint_consts_t is the table) */
+  if (fresh) {      /* no stamp, no order; switched off and on again the side state is kept, as the mpump section is */
+    npb_launch_cmaint_init(h->cm_side, h->pitch, nullptr, h->n_plants, nullptr);
+    NPB_HIP(h, hipGetLastError());
+    NPB_HIP(h, hipDeviceSynchronize());
+  }
+  h->cm_on = true;
+  return NPB_OK;
+}
+size_t npb_component_maintenance_state_bytes(const NpbHandle *h) { return h ? (size_t)NPB_CMAINT_SIDE_DOUBLES * (size_t)h->n_plants * sizeof(double) : 0; }
+int npb_get_component_maintenance_state(NpbHandle *h, double *buf, void *stream) {
+  if (!h || !buf) return NPB_EINVAL;
+  if (!h->cm_side) return fail(h, NPB_EINVAL, "npb_get_component_maintenance_state: no side state (npb_set_component_maintenance first)");
+  NPB_USE_DEVICE(h);
+  NPB_HIP(h, hipMemcpy2DAsync(buf, (size_t)h->n_plants * sizeof(double), cm_state(h), h->pitch * sizeof(double), (size_t)h->n_plants * sizeof(double),
+                              NPB_CMAINT_SIDE_DOUBLES, hipMemcpyDefault, (hipStream_t)stream));
+  NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
+  return NPB_OK;
+}
+int npb_set_component_maintenance_state(NpbHandle *h, const double *buf, void *stream) {
+  if (!h || !buf) return NPB_EINVAL;
+  if (!h->cm_side) return fail(h, NPB_EINVAL, "npb_set_component_maintenance_state: no side state (npb_set_component_maintenance first)");
+  NPB_USE_DEVICE(h);
+  NPB_HIP(h, hipMemcpy2DAsync(cm_state(h), h->pitch * sizeof(double), buf, (size_t)h->n_plants * sizeof(double), (size_t)h->n_plants * sizeof(double),
+                              NPB_CMAINT_SIDE_DOUBLES, hipMemcpyDefault, (hipStream_t)stream));
+  NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
+  return NPB_OK;
+}
+
 int npb_reset(NpbHandle *h, const uint8_t *mask, void *stream) {
   if (!h) return NPB_EINVAL;
   NPB_USE_DEVICE(h);
   h->maint_cache_stale = true;
   h->K->init(&h->params, h->n_plants, NPB_N(h), h->f64, mask, (hipStream_t)stream);
+  if (h->cm_on) npb_launch_cmaint_init(h->cm_side, h->pitch, mask, h->n_plants, (hipStream_t)stream);      /* beside the mpump section the init kernel has just written */
   clear_episodes(h, mask, true, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
@@ -552,9 +644,17 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
     return fail(h, NPB_EINVAL, "npb_step: autoreset is on (npb_set_autoreset) and needs the done column: it must not be NULL");
   if (h->params.heat_source == NPB_HEAT_EXTERNAL && !noise_z)      /* a NULL column would read as 0 MW thermal, silently */
     return fail(h, NPB_EINVAL, "npb_step: params.heat_source is NPB_HEAT_EXTERNAL, whose thermal power arrives in the noise_z column (include/npb_params.h): it must not be NULL");
+  npb_cmaint_restore_t cm = {};      /* what the autoreset's restores take along beside the arena */
+  if (h->cm_on) {
+    if (!h->params.maint_enabled || h->params.mode != NPB_MODE_FULL)
+      return fail(h, NPB_EINVAL, "npb_step: the component maintenance is on (npb_set_component_maintenance) and needs params.maint_enabled and the full mode");
+    if (h->autoreset && !cm_restore_of(h, h->bank && h->next_slot, &cm))
+      return fail(h, NPB_EINVAL, h->bank && h->next_slot ? g_cm_no_bank : g_cm_no_snapshot);
+  }
   NPB_USE_DEVICE(h);
   npb_maint_table_t table;
   const bool maint = h->params.maint_enabled != 0;
+  const bool in_step = maint && !h->cm_on;      /* the rule inside the step kernels (pumps only); with the components on it is a launch of its own */
   if (maint) {
     table = h->maint_table;
     if (!h->maint_table_custom) {   /* with the default table the two oil_level params of ABI version 1 still set their row */
@@ -580,13 +680,15 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
   }
   h->last_kernel = h->K->step(&h->params, h->n_plants, NPB_N(h), h->f64, action, magnitude, power_setpoint,
                               noise_z, cooling_water_temp, obs, reward, done, trip_flags, info, h->step_kernel, h->diag, h->diag_pitch,
-                              maint ? &table : nullptr, maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
-  if (maint && h->params.mode != NPB_MODE_FULL)   /* a full-mode step kernel has run the rule itself, for the waves whose pump phase found something */
+                              in_step ? &table : nullptr, in_step ? h->maint_side : nullptr, in_step ? h->maint_counts : nullptr, (hipStream_t)stream);
+  if (h->cm_on)      /* the plain step kernel has run: the whole rule, pumps, generators and condenser in one queue */
+    h->K->maint_all(NPB_N(h), h->f64, h->maint_side, h->cm_side, h->maint_counts, h->n_plants, h->diag, h->diag_pitch, (hipStream_t)stream);
+  else if (maint && h->params.mode != NPB_MODE_FULL)   /* a full-mode step kernel has run the rule itself, for the waves whose pump phase found something */
     h->K->maint(NPB_N(h), h->f64, h->maint_side, h->maint_counts, h->n_plants, (hipStream_t)stream);
   if (h->autoreset)   /* from the bank while it has slots, else from the snapshot; same stream, nothing read back, the maintenance cache kept per plant by the kernel itself */
     h->K->episode(h->params.mode, h->n_plants, NPB_N(h), h->f64, source_of(h, h->bank && h->next_slot), done, reward, obs, h->ep_len, h->ep_ret,
                   h->ep_out_len, h->ep_out_ret, h->ep_out_truncated, h->ep_final_obs, h->max_episode_steps,
-                  maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
+                  maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, cm, (hipStream_t)stream);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, NPB_EHIP, "npb_step: kernel launch failed", e);
   return NPB_OK;
@@ -601,16 +703,29 @@ int npb_snapshot(NpbHandle *h, void *stream) {
     if (e != hipSuccess) { h->snap = nullptr; return fail(h, NPB_EHIP, "npb_snapshot: hipMalloc of the snapshot arena failed", e); }
   }
   NPB_HIP(h, hipMemcpyAsync(h->snap, h->f64, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (h->cm_on) {      /* the generators' and the condenser's stamps and open orders belong to the episode start as the mpump section does */
+    const size_t cm_bytes = (size_t)NPB_CMAINT_SIDE_DOUBLES * h->pitch * sizeof(double);
+    if (!h->cm_snap) {
+      hipError_t e = hipMalloc((void **)&h->cm_snap, cm_bytes);
+      if (e != hipSuccess) { h->cm_snap = nullptr; return fail(h, NPB_EHIP, "npb_snapshot: hipMalloc of the component maintenance's snapshot failed", e); }
+    }
+    NPB_HIP(h, hipMemcpyAsync(h->cm_snap, cm_state(h), cm_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  } else if (h->cm_snap) {      /* a snapshot without the feature: the older side snapshot does not belong to it */
+    NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
+    (void)hipFree(h->cm_snap); h->cm_snap = nullptr;
+  }
   return NPB_OK;
 }
 
 int npb_restore(NpbHandle *h, const uint8_t *mask, void *stream) {
   if (!h) return NPB_EINVAL;
   if (!h->snap) return fail(h, NPB_EINVAL, "npb_restore: no snapshot (npb_snapshot) to restore from");
+  npb_cmaint_restore_t cm;
+  if (!cm_restore_of(h, false, &cm)) return fail(h, NPB_EINVAL, g_cm_no_snapshot);
   NPB_USE_DEVICE(h);
   const bool maint = h->params.maint_enabled != 0;
   h->K->restore(h->n_plants, NPB_N(h), h->f64, source_of(h, false), mask, h->ep_len, h->ep_ret,
-                maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
+                maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, cm, (hipStream_t)stream);
   clear_episodes(h, mask, false, (hipStream_t)stream);     /* the restored episodes are not from the bank */
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
@@ -652,8 +767,12 @@ int npb_set_start_bank(NpbHandle *h, const NpbHandle *src, void *stream) {
     if (h->bank) (void)hipFree(h->bank);
     if (h->ep_start) (void)hipFree(h->ep_start);
     h->bank = nullptr; h->bank_bytes = 0; h->bank_N = 0; h->bank_M = 0; h->ep_start = nullptr;
+    if (h->cm_bank) (void)hipFree(h->cm_bank);
+    h->cm_bank = nullptr; h->cm_bank_pitch = 0; h->cm_bank_doubles = 0;
     return NPB_OK;
   }
+  if (h->cm_on && !src->cm_on)      /* its entries would come without stamps and open orders of the generators and the condenser */
+    return fail(h, NPB_EINVAL, "npb_set_start_bank: this handle has the component maintenance on (npb_set_component_maintenance) and the bank handle has not");
   if (src->storage != h->storage)
     return fail(h, NPB_EINVAL, "npb_set_start_bank: the bank handle's storage type differs from this handle's (npb_create_storage)");
   if (src->device != h->device)
@@ -673,6 +792,21 @@ int npb_set_start_bank(NpbHandle *h, const NpbHandle *src, void *stream) {
   }
   NPB_HIP(h, hipMemcpyAsync(h->bank, src->f64, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   h->bank_N = NPB_N(src); h->bank_M = src->n_plants;
+  if (src->cm_on) {      /* the bank's side state beside its arena, in the bank handle's pitch */
+    const size_t doubles = (size_t)NPB_CMAINT_SIDE_DOUBLES * src->pitch;
+    if (doubles > h->cm_bank_doubles) {
+      if (h->cm_bank) (void)hipFree(h->cm_bank);
+      h->cm_bank = nullptr; h->cm_bank_doubles = 0;
+      hipError_t e = hipMalloc((void **)&h->cm_bank, doubles * sizeof(double));
+      if (e != hipSuccess) { h->cm_bank = nullptr; return fail(h, NPB_EHIP, "npb_set_start_bank: hipMalloc of the bank's component maintenance state failed", e); }
+      h->cm_bank_doubles = doubles;
+    }
+    NPB_HIP(h, hipMemcpyAsync(h->cm_bank, cm_state(src), doubles * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    h->cm_bank_pitch = src->pitch;
+  } else if (h->cm_bank) {
+    NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
+    (void)hipFree(h->cm_bank); h->cm_bank = nullptr; h->cm_bank_pitch = 0; h->cm_bank_doubles = 0;
+  }
   return NPB_OK;
 }
 
@@ -687,10 +821,12 @@ int npb_set_start_slots(NpbHandle *h, int32_t *next_slot, int32_t *episode_start
 int npb_restore_bank(NpbHandle *h, const uint8_t *mask, void *stream) {
   if (!h) return NPB_EINVAL;
   if (!h->bank || !h->next_slot) return fail(h, NPB_EINVAL, "npb_restore_bank: no start bank (npb_set_start_bank) with slots (npb_set_start_slots) to restore from");
+  npb_cmaint_restore_t cm;
+  if (!cm_restore_of(h, true, &cm)) return fail(h, NPB_EINVAL, g_cm_no_bank);
   NPB_USE_DEVICE(h);
   const bool maint = h->params.maint_enabled != 0;
   h->K->restore(h->n_plants, NPB_N(h), h->f64, source_of(h, true), mask, h->ep_len, h->ep_ret,
-                maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, (hipStream_t)stream);
+                maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, cm, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }

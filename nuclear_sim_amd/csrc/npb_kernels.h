@@ -24,6 +24,9 @@ typedef struct {
   int32_t *start;           /* carried [pitch]: the entry of each plant's running episode, -1 = not from the bank */
   int32_t *out_start;       /* the caller's [n], or NULL: the episode kernel's copy of `start` as of each step */
 } npb_source_t;
+/* the side state of the component maintenance (npb_set_component_maintenance) a restore takes along: lane s of src -> lane p of state,
+ * member by member ([NPB_CMAINT_SIDE_DOUBLES][pitch] doubles each); state NULL = the feature is off */
+typedef struct { double *state; const double *src; size_t pitch, src_pitch; } npb_cmaint_restore_t;
 typedef struct {
   int (*step)(const npb_params_t *P, int n_plants, size_t npad, void *arena, const int32_t *action,
               const double *magnitude, const double *setpoint, const double *noise_z, const double *cw_temp,
@@ -39,10 +42,10 @@ typedef struct {
   void (*gather)(const void *arena, size_t npad, const int *plan_dev, int n_fields, double *out, int n, hipStream_t stream);
   /* episodes: src = the snapshot or a bank with slots (npb_source_t); maint_side / maint_counts NULL unless params.maint_enabled */
   void (*restore)(int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *mask, int32_t *len, double *ret,
-                  void *maint_side, int32_t *maint_counts, hipStream_t stream);
+                  void *maint_side, int32_t *maint_counts, npb_cmaint_restore_t cm, hipStream_t stream);
   void (*episode)(int mode, int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *done, const double *reward,
                   double *obs, int32_t *len, double *ret, int32_t *out_len, double *out_ret, uint8_t *out_truncated,
-                  double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, hipStream_t stream);
+                  double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, npb_cmaint_restore_t cm, hipStream_t stream);
   /* npb_perform_maintenance: the caller's [n_plants] order columns (bearing / target_level / success may be NULL) and the maintenance
    * event log's descriptor (log_records NULL = off) */
   void (*operator_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *pump, const int32_t *bearing,
@@ -57,6 +60,10 @@ typedef struct {
    * the turbine, and the event log */
   void (*operator_turbine_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *unit, uint8_t *success, int turbine,
                                  npb_maint_event_t *log_records, uint32_t *log_cursor, int log_capacity, hipStream_t stream);
+  /* npb_set_component_maintenance: the whole automatic-maintenance rule, pumps, generators and condenser in one queue, as a launch of its own
+   * behind the plain step kernel; maint_side = the rule's constants, cm_side = the component table and side state */
+  void (*maint_all)(size_t npad, void *arena, void *maint_side, void *cm_side, int32_t *counts, int n_plants, double *diag, size_t diag_pitch,
+                    hipStream_t stream);
 } npb_launchers_t;
 extern npb_launchers_t npb_launch_table, npb32_launch_table;
 /* the same for either storage type */
@@ -65,6 +72,9 @@ void npb_launch_maint_consts(const npb_params_t *P, const npb_maint_table_t *T, 
 size_t npb_launch_maint_consts_bytes(void);
 size_t npb_launch_maint_side_bytes(size_t npad);
 size_t npb_launch_maint_cache_offset(void);
+size_t npb_launch_cmaint_side_bytes(size_t pitch);
+size_t npb_launch_cmaint_state_offset(void);
+void npb_launch_cmaint_init(void *cm_side, size_t pitch, const uint8_t *mask, int n_plants, hipStream_t stream);
 void npb_launch_touch(size_t npad, double *arena, hipStream_t stream);
 void npb_launch_episode_clear(const uint8_t *mask, int32_t *len, double *ret, int32_t *start, int n_plants, size_t npad, hipStream_t stream);
 #ifdef __cplusplus

@@ -51,6 +51,7 @@ extern "C" __attribute__((visibility("default"))) int npb_debug_set_stamp_buffer
 #include "npd_maintenance.h"
 #include "npd_component_maintenance.h"
 #include "npd_turbine_maintenance.h"
+#include "npd_component_auto.h"
 #include "npd_init.h"
 #include "npd_reset.h"
 #include "npd_step.h"
@@ -451,6 +452,29 @@ __device__ __forceinline__ bool npd_maint_second_look(const npd_maint_screen_t &
   }
   return work;
 }
+/* the first half of that look alone: bit q = row q of the table is crossed by pump k of this lane's plant, cooldowns aside (npb_maint_all_kernel) */
+__device__ __forceinline__ uint32_t npd_maint_crossed_rows(const npd_maint_screen_t &S, const npd_real_t *f64c, size_t N, size_t p, int k) {
+  npd_real_t *f64 = const_cast<npd_real_t *>(f64c);
+  npb_pump_t pm;
+#define NPD_PM(member) pm.member = NPD_F64_COL(PUMP, npb_pump_t, member, k)
+  NPD_PM(oil_level); NPD_PM(oil_contamination); NPD_PM(lubrication_effectiveness); NPD_PM(wear_impeller); NPD_PM(cavitation_damage);
+  NPD_PM(cavitation_intensity); NPD_PM(npsh_available); NPD_PM(wear_motor_bearings); NPD_PM(wear_pump_bearings); NPD_PM(wear_thrust_bearing);
+  NPD_PM(wear_mechanical_seals); NPD_PM(vibration_level); NPD_PM(oil_temperature); NPD_PM(motor_temperature); NPD_PM(seal_leakage_rate);
+#undef NPD_PM
+  double values[NPB_MAINT_NPARAM];
+  npd_maint_values(&pm, values);
+  uint32_t hits = 0;
+#pragma unroll
+  for (int q = 0; q < NPB_MAINT_NPARAM; q++) {
+    const double v = values[q], thr = S.threshold[q];
+    const bool near_eq = fabs(v - thr) < 0.001;                                  /* _check_threshold_condition */
+    const bool hit = ((((S.want_gt >> q) & 1u) != 0) & (v > thr)) | ((((S.want_lt >> q) & 1u) != 0) & (v < thr)) |
+                     ((((S.want_eq >> q) & 1u) != 0) & (v == thr)) | ((((S.want_near >> q) & 1u) != 0) & near_eq) |
+                     ((((S.want_far >> q) & 1u) != 0) & !near_eq);
+    hits |= (uint32_t)hit << q;
+  }
+  return hits;
+}
 /* the cooldown cache of the step kernels' screen (npd_maintenance.h) for the four pumps of this lane's plant, from the stamps as
  * they are now: whenever the rule has looked at a wave */
 __device__ __forceinline__ void npd_maint_refresh_cache(const npd_maint_screen_t &S, npd_u32x4 *cache_entry, const npd_real_t *f64c, size_t N, size_t p, double t) {
@@ -466,6 +490,69 @@ __device__ __forceinline__ void npd_maint_refresh_cache(const npd_maint_screen_t
     uint32_t *e = (uint32_t *)(cache_entry + p * 2) + 2 * k;
     e[0] = mask; e[1] = __float_as_uint(until);
   }
+}
+/* ---- the two pump bodies of the rule as npd_maint_all_rule uses them.  They are npd_maint_rule_for_wave's own statements, and a change to
+ * one belongs in the other: calling these helpers from npd_maint_rule_for_wave was tried and changes the code the compiler emits for every
+ * npb_step*_maint_kernel and every instantiation of the rule (tools/compare_step_kernels.py), which the step kernels must not.
+ * A due order (pump `pick`, action `pick_action`, number `best`) is carried out: closed, its handler run, the diagnostics flags set; with the
+ * log on, ev takes the order as the arena holds it before it is closed */
+__device__ __forceinline__ void npd_maint_carry_out_pump_order(const npb_params_t &P, const npd_maint_cache_t &MC, npd_real_t *f64, size_t N, size_t p, int pick,
+                                                               int pick_action, double best, bool log_on, npb_maint_t &m, npb_maint_event_t &ev) {
+  npb_mpump_t mp;
+  NPD_MP_LOAD(pick, wo_order, NPB_MAINT_NACT); NPD_MP_LOAD(pick, wo_planned_start, NPB_MAINT_NACT);
+  mp.wo_bearing = (double)*(const npd_real_t *)npd_gaddr(f64, N, p, NPD_MP_COL(pick, wo_bearing, 0));
+  if (log_on) {      /* the order as the arena holds it, before it is closed */
+    ev.created = (double)*(const npd_real_t *)npd_gaddr(f64, N, p, NPD_MP_COL(pick, last_trigger_time, pick_action));
+    ev.planned_start = (double)*(const npd_real_t *)npd_gaddr(f64, N, p, NPD_MP_COL(pick, wo_planned_start, pick_action));
+    ev.order = (int32_t)best; ev.action = (uint8_t)pick_action;
+    ev.bearing = pick_action == NPB_MA_BEARING_REPLACEMENT ? (uint8_t)mp.wo_bearing : 0;
+  }
+  const int bearing = npd_maint_close_order(&mp, &m, pick_action);
+  NPD_MP_STORE(pick, wo_order, NPB_MAINT_NACT); NPD_MP_STORE(pick, wo_planned_start, NPB_MAINT_NACT);
+  *(npd_real_t *)npd_gaddr(f64, N, p, NPD_MP_COL(pick, wo_bearing, 0)) = (npd_real_t)mp.wo_bearing;
+  npb_pump_t pm;
+  NPD_LOAD(PUMP, npb_pump_t, pm, pick);
+  npd_maint_execute(&pm, &P, pick_action, bearing);
+  NPD_STORE(PUMP, npb_pump_t, pm, pick);
+  if (MC.diag && ((NPD_MA_HANDLER_MASK >> pick_action) & 1u)) {    /* pump_lubrication.py:642-643, 1636-1637: the flags of this step's state-log row (action types the dispatcher knows) */
+    MC.diag[(size_t)(NPB_DIAG_PUMP_MAINTENANCE_OCCURRED + pick) * MC.diag_pitch + p] = 1.0;
+    if (pick_action == NPB_MA_OIL_TOP_OFF) MC.diag[(size_t)(NPB_DIAG_PUMP_OIL_TOP_OFF_OCCURRED + pick) * MC.diag_pitch + p] = 1.0;
+    MC.diag[(size_t)(NPB_DIAG_PUMP_MAINTENANCE_ACTION + pick) * MC.diag_pitch + p] = (double)(pick_action + 1);
+  }
+}
+/* the scan of pump k with the work order it may create, stored and logged (at most one creation per pump, plant and step) */
+__device__ __forceinline__ void npd_maint_scan_pump_logged(const npd_maint_rule_consts_t *RC, npd_real_t *f64, size_t N, size_t p, int k, double t, bool log_on,
+                                                           bool live, npb_maint_t &m, npb_maint_event_t &ev, int &dirty) {
+  const npb_params_t &P = RC->P; const npb_maint_table_t &T = RC->T;
+    npb_pump_t pm;
+    NPD_LOAD(PUMP, npb_pump_t, pm, k);
+    npb_mpump_t mp;
+    NPD_LOAD(MPUMP, npb_mpump_t, mp, k);
+    const int created_before = m.work_orders_created;
+    if (npd_maint_scan_pump(&mp, &m, &P, &T, &pm, t)) {
+      dirty = 1;
+      if (log_on && m.work_orders_created != created_before) {    /* a work order was created: the action whose wo_order is the new count */
+        const double n = (double)m.work_orders_created;
+        ev.action = 0; ev.planned_start = 0.0;
+#pragma unroll
+        for (int a = 0; a < NPB_MAINT_NACT; a++)
+          if (mp.wo_order[a] == n) { ev.action = (uint8_t)a; ev.planned_start = (double)(npd_real_t)mp.wo_planned_start[a]; }
+        /* the rows this scan stamped (the arena still holds the stamps from before it) and the batched event's priority, their highest */
+        uint32_t trigger = 0; int priority = 0;
+#pragma unroll
+        for (int q = 0; q < NPB_MAINT_NPARAM; q++)
+          if (mp.last_violation_time[q] != (double)*(const npd_real_t *)npd_gaddr(f64, N, p, NPD_MP_COL(k, last_violation_time, q))) {
+            trigger |= 1u << q; priority = T.priority[q] > priority ? T.priority[q] : priority;
+          }
+        ev.created = t; ev.order = m.work_orders_created; ev.trigger = (uint16_t)trigger; ev.priority = (uint8_t)priority;
+        ev.bearing = ev.action == NPB_MA_BEARING_REPLACEMENT ? (uint8_t)mp.wo_bearing : 0;
+      }
+      NPD_STORE(MPUMP, npb_mpump_t, mp, k);
+    }
+    if (log_on) {    /* at most one creation per pump, plant and step */
+      ev.kind = NPB_MAINT_EVENT_CREATED; ev.pump = (uint8_t)k;
+      npd_maint_log(RC->L, live && m.work_orders_created != created_before, ev);
+    }
 }
 /* one wave = the 64 plants p - lane .. p - lane + 63, whose step (all its stores) is complete.  hit_bits: bit k = the screen
  * flagged pump k for some lane; due_with_orders: some lane's check falls on open orders (wave-uniform both) */
@@ -671,7 +758,8 @@ typedef uint64_t npd_word_t;
 #endif
 /* where the restore writes besides the arena: the maintenance screen's cooldown cache (zeroed = "look", npd_maintenance.h) and the
  * caller's event-count column (npb_set_maintenance_count_buffer), both NULL unless params.maint_enabled */
-struct npd_restore_side_t { npd_u32x4 *maint_entry; int32_t *maint_counts; int n_plants; };
+struct npd_restore_side_t { npd_u32x4 *maint_entry; int32_t *maint_counts; int n_plants;
+                             npb_cmaint_restore_t cm;      /* the side state of the component maintenance (npd_component_auto.h): state NULL = off */ };
 /* the bank entry a restored plant takes from its slot, and the slot and start columns it leaves behind (include/npb.h) */
 __device__ __forceinline__ int32_t npd_bank_take(const npb_source_t &B, size_t p) {
   int32_t s = B.next_slot[p] % B.M;
@@ -714,6 +802,10 @@ __device__ __forceinline__ void npd_restore_lanes(npd_real_t *__restrict__ f64, 
     const npd_real_t *f64 = from;     /* (the member macro reads `f64`, `N` and `p`: the source entry's) */
     const size_t N = Ns, p = s;
     *counts = NPD_I32_COL(MAINT, npb_maint_t, maintenance_actions_performed, 0);
+  }
+  if (R.cm.state) {                   /* the stamps and open orders of the generators and the condenser travel with the plant's */
+#pragma unroll 1
+    for (int k = 0; k < NPB_CMAINT_SIDE_DOUBLES; k++) R.cm.state[(size_t)k * R.cm.pitch + p] = R.cm.src[(size_t)k * R.cm.src_pitch + s];
   }
 }
 /* [64][W] rows held one per lane -> row-major global memory, only the rows whose bit is set in `rows` (npd_store_rows otherwise) */
@@ -1083,6 +1175,178 @@ extern "C" void npb_launch_touch(size_t npad_seg, double *f64, hipStream_t strea
 #endif
 
 /* ---- host-side launchers: one table per storage type (npb_launchers_t), which npb_api.hip calls through */
+/* ---- automatic maintenance of the feedwater pumps, the steam generators and the condenser in ONE queue (npb_set_component_maintenance;
+ * npd_component_auto.h): a launch of its own behind the PLAIN step kernel, which is the step kernel of a handle without any automatic
+ * maintenance -- the step kernels do not know this rule.  One wave = 64 plants.  The wave first screens: is a check due on open orders,
+ * is a pump's threshold crossed outside its cooldown (npd_maint_second_look), is a component's; a wave with none of that moves
+ * last_check_time where a check fell due and leaves.  Otherwise the reference's order: AutoMaintenanceSystem.update carries out one due
+ * order, the earliest created of any component; then the scan in the order of StateManager.maintenance_thresholds, FWP-1..4, SG-0..2,
+ * the condenser, every created order numbered from the one counter maint.work_orders_created. */
+/* (Behind every other kernel of the file on purpose: kernels are laid out in the code object in source order, and the step kernels, which
+ * bench.py times, keep the offsets they had before this one existed.) */
+__device__ __forceinline__ void npd_cmaint_values(const npd_real_t *f64c, size_t N, size_t p, int c, double dt, double *v) {
+  npd_real_t *f64 = const_cast<npd_real_t *>(f64c);
+  if (c == NPB_CMAINT_COND) {
+    v[0] = NPD_F64_COL(COND, npb_cond_t, total_fouling_resistance, 0);
+    v[1] = npd_cond_tube_leak_rate(NPD_F64_COL(COND, npb_cond_t, vibration_damage, 0), NPD_F64_COL(COND, npb_cond_t, corrosion_damage, 0),
+                                   NPD_F64_COL(CHEM, npb_chem_t, water_aggressiveness, 1), NPD_F64_COL(COND, npb_cond_t, active_tube_count, 0),
+                                   dt / 60.0);      /* the condenser's dt: hours (npd_step1.h) */
+    v[2] = 0.0;
+    return;
+  }
+  v[0] = NPD_F64_COL(SG, npb_sg_t, tsp_fouling_fraction, c);
+  v[1] = NPD_F64_COL(SG, npb_sg_t, tube_wall_temp, c);
+  v[2] = NPD_F64_COL(SG, npb_sg_t, steam_quality, c);
+}
+/* everything behind the screen, as a real function call (noinline), so that the screen -- what nearly every wave of nearly every step
+ * runs and leaves from -- is allocated for itself, not for the rule's registers and scratch: the pattern of npd_maint_rule_for_wave.
+ * work: this lane's check is due on open orders; scan_bits: bit k = pump k, bit 4 + c = component c has something new for some lane */
+__device__ __attribute__((noinline)) void npd_maint_all_rule(const npd_maint_rule_consts_t *RC, npd_cmaint_side_t side, npd_maint_cache_t MC, npd_real_t *f64,
+                                                             size_t N, size_t p, double t, bool work, unsigned scan_bits) {
+  const npb_params_t &P = RC->P; const npb_maint_table_t &T = RC->T;
+  npb_maint_t m;
+  NPD_LOAD(MAINT, npb_maint_t, m, 0);
+  int dirty = 0, executed = -1, executed_comp = -1;
+  const bool log_on = RC->L.cursor != nullptr, live = p < (size_t)MC.n_plants;    /* padding lanes never log */
+  npb_maint_event_t ev = {};
+  ev.time = t; ev.plant = (int32_t)p;
+  /* ---- AutoMaintenanceSystem.update: one due order, the earliest created of pumps and components, is carried out.  (A lane whose
+   * check fell due with nothing open has had its last_check_time moved by the screen; m holds that.) */
+  if (work) {
+    m.last_check_time = t;
+    dirty = 1;
+    double best = 0.0; int pick = -1, pick_action = -1;
+#pragma unroll 1
+    for (int k = 0; k < NPB_NUM_PUMPS; k++) {
+      npb_mpump_t mp;
+      NPD_MP_LOAD(k, wo_order, NPB_MAINT_NACT); NPD_MP_LOAD(k, wo_planned_start, NPB_MAINT_NACT);
+      int a; const double o = npd_maint_first_due(&mp, t, &a);
+      if (o > 0.0 && (best == 0.0 || o < best)) { best = o; pick = k; pick_action = a; }
+    }
+    int cslot; const double co = npd_cmaint_first_due(side, p, t, &cslot);
+    if (co > 0.0 && (best == 0.0 || co < best)) { best = co; pick = -1; executed_comp = cslot / NPB_CMAINT_NROW; } else cslot = -1;
+    if (pick >= 0) {      /* a pump's order */
+      npd_maint_carry_out_pump_order(P, MC, f64, N, p, pick, pick_action, best, log_on, m, ev);
+      ev.pump = (uint8_t)pick; ev.kind = NPB_MAINT_EVENT_COMPLETED;
+      executed = pick;
+    } else if (cslot >= 0) {      /* a component's: perform_maintenance(maintenance_type=action) with its default arguments */
+      const int c = executed_comp;
+      const int action = side.C->T.action[npd_cmaint_param0(c) + cslot % NPB_CMAINT_NROW];
+      ev.created = NPD_CMS(side, NPB_CMS_WO_CREATED, cslot, p);
+      ev.planned_start = NPD_CMS(side, NPB_CMS_WO_PLANNED_START, cslot, p);
+      ev.priority = (uint8_t)NPD_CMS(side, NPB_CMS_WO_PRIORITY, cslot, p);
+      ev.order = (int32_t)best; ev.action = (uint8_t)action; ev.pump = (uint8_t)(c == NPB_CMAINT_COND ? 0 : c);
+      ev.bearing = (uint8_t)(c == NPB_CMAINT_COND ? NPB_COMPONENT_COND : NPB_COMPONENT_SG);
+      ev.reserved = action == NPB_CA_AUTO_CONDENSER_TUBE_PLUGGING ? 0 : 1;      /* the one handler that raises: success = false */
+      ev.kind = NPB_MAINT_EVENT_COMPONENT_COMPLETED;
+      NPD_CMS(side, NPB_CMS_WO_ORDER, cslot, p) = 0.0; NPD_CMS(side, NPB_CMS_WO_CREATED, cslot, p) = 0.0;
+      NPD_CMS(side, NPB_CMS_WO_PLANNED_START, cslot, p) = 0.0; NPD_CMS(side, NPB_CMS_WO_PRIORITY, cslot, p) = 0.0;
+      m.maintenance_actions_performed += 1;      /* maint.executed[] counts the pumps' orders only (include/npb_fields.h) */
+      if (c == NPB_CMAINT_COND) {
+        npb_cond_t cd;
+        NPD_LOAD(COND, npb_cond_t, cd, 0);
+        if (action == NPB_CA_AUTO_CONDENSER_TUBE_PLUGGING) {      /* what the handler has done when it raises (condenser/physics.py:1236-1240, tubes_to_plug = 10) */
+          const double old_active_count = cd.active_tube_count;
+          cd.plugged_tube_count += 10;
+          cd.active_tube_count = npd_pymax(1000.0, old_active_count - 10);
+        } else if (npd_cond_touches_chemistry(action)) {
+          npb_chem_t ch;
+          NPD_LOAD(CHEM, npb_chem_t, ch, 1);
+          npd_cond_maintenance(&cd, &ch, action, NPB_CLEANING_DEFAULT);
+          NPD_STORE(CHEM, npb_chem_t, ch, 1);
+        } else {
+          npd_cond_maintenance(&cd, nullptr, action, NPB_CLEANING_DEFAULT);
+        }
+        NPD_STORE(COND, npb_cond_t, cd, 0);
+      } else {
+#pragma unroll 1
+        for (int k = 0; k < NPB_NUM_SG; k++) {
+          if (c != k) continue;
+          npb_sg_t g;
+          NPD_LOAD(SG, npb_sg_t, g, k);
+          npd_sg_maintenance(&g, action, NPB_CLEANING_DEFAULT);
+          NPD_STORE(SG, npb_sg_t, g, k);
+        }
+      }
+    }
+  }
+  if (log_on) npd_maint_log(RC->L, live && (executed >= 0 || executed_comp >= 0), ev);      /* at most one completion per plant and step */
+  ev.reserved = 0; ev.priority = 0;      /* (a component completion's success and priority: not the next records') */
+  /* ---- StateManager.collect_states: the pumps ... */
+#pragma unroll 1
+  for (int k = 0; k < NPB_NUM_PUMPS; k++) {
+    if (!((scan_bits >> k) & 1u) && !__any(executed == k)) continue;
+    npd_maint_scan_pump_logged(RC, f64, N, p, k, t, log_on, live, m, ev, dirty);
+  }
+  /* ---- ... then the generators and the condenser */
+#pragma unroll 1
+  for (int c = 0; c < NPB_CMAINT_NCOMP; c++) {
+    if (!((scan_bits >> (4 + c)) & 1u) && !__any(executed_comp == c)) continue;
+    double v[NPB_CMAINT_NROW];
+    npd_cmaint_values(f64, N, p, c, P.dt, v);
+    const uint32_t viol = npd_cmaint_violations(side, p, c, v, t);
+    int slot = -1, action = 0, priority = 0;
+    if (viol) {
+      slot = npd_cmaint_scan(side, p, c, viol, &m, &P, t, &action, &priority);
+      if (slot >= 0) dirty = 1;
+    }
+    if (log_on) {
+      ev = npb_maint_event_t{};
+      ev.time = t; ev.plant = (int32_t)p; ev.created = t; ev.order = m.work_orders_created; ev.trigger = (uint16_t)viol;
+      ev.planned_start = slot >= 0 ? NPD_CMS(side, NPB_CMS_WO_PLANNED_START, slot, p) : 0.0;
+      ev.action = (uint8_t)action; ev.priority = (uint8_t)priority; ev.pump = (uint8_t)(c == NPB_CMAINT_COND ? 0 : c);
+      ev.bearing = (uint8_t)(c == NPB_CMAINT_COND ? NPB_COMPONENT_COND : NPB_COMPONENT_SG);
+      ev.kind = NPB_MAINT_EVENT_COMPONENT_CREATED;
+      npd_maint_log(RC->L, live && slot >= 0, ev);
+    }
+  }
+  if (dirty) {
+    NPD_STORE(MAINT, npb_maint_t, m, 0);
+    if (MC.counts && p < (size_t)MC.n_plants) MC.counts[p] = m.maintenance_actions_performed;
+  }
+}
+__global__ __launch_bounds__(NPB_WAVE) void npb_maint_all_kernel(const npd_maint_rule_consts_t *RC, npd_cmaint_side_t side, npd_maint_cache_t MC, size_t N,
+                                                                 npd_real_t *__restrict__ f64) {
+  NPD_SEGMENT(f64, N, (size_t)blockIdx.x * NPB_WAVE);
+  const size_t p = (size_t)blockIdx.x * NPB_WAVE + threadIdx.x;
+  const npb_params_t &P = RC->P; const npb_maint_table_t &T = RC->T; const npd_maint_screen_t &S = RC->S;
+  const double t = NPD_F64_COL(PRIM, npb_prim_t, sim_time, 0);
+  /* ---- the screen */
+  npd_maint_due_t due;
+  npd_maint_due_load(&due, f64, N, p);
+  const bool work = npd_maint_due_decide(&due, t, P.maint_check_interval_hours * 60);      /* moves last_check_time where due with nothing open */
+  unsigned scan_bits = 0;      /* bit k: pump k, bit 4 + c: component c -- somebody in the wave has something new there */
+  {
+    /* every value first, in straight-line code, so that the loads are in flight together (a lone wave that uses each load at once waits
+     * out a memory latency per pump); then, per crossed row, that row's stamp alone, for the lanes that crossed it: a running pump's oil
+     * temperature sits above its row for the whole run, and its fifteen other stamps are not worth reading at every step */
+    uint32_t hits[NPB_NUM_PUMPS];
+    double cv[NPB_CMAINT_NCOMP][NPB_CMAINT_NROW];
+#pragma unroll
+    for (int k = 0; k < NPB_NUM_PUMPS; k++) hits[k] = npd_maint_crossed_rows(S, f64, N, p, k);
+#pragma unroll
+    for (int c = 0; c < NPB_CMAINT_NCOMP; c++) npd_cmaint_values(f64, N, p, c, P.dt, cv[c]);
+#pragma unroll
+    for (int k = 0; k < NPB_NUM_PUMPS; k++) {
+      bool fresh = false;
+#pragma unroll
+      for (int q = 0; q < NPB_MAINT_NPARAM; q++) {
+        const bool mine = ((hits[k] >> q) & 1u) != 0;
+        if (!__any(mine)) continue;
+        if (mine) {
+          const double lv = (double)*(const npd_real_t *)npd_gaddr(f64, N, p, NPD_MP_COL(k, last_violation_time, q));
+          fresh |= !((lv >= 0.0) & (t - lv < S.cooldown_minutes[q]));      /* _is_threshold_in_cooldown */
+        }
+      }
+      if (__any(fresh)) scan_bits |= 1u << k;
+    }
+#pragma unroll
+    for (int c = 0; c < NPB_CMAINT_NCOMP; c++)
+      if (__any(npd_cmaint_violations(side, p, c, cv[c], t) != 0)) scan_bits |= 16u << c;
+  }
+  if (!__any(work) && !scan_bits) return;
+  npd_maint_all_rule(RC, side, MC, f64, N, p, t, work, scan_bits);
+}
 #ifdef NPB_BUILD_F32
 #define NPB_LAUNCHER(name) npb32_launch_##name
 #else
@@ -1231,6 +1495,15 @@ static void NPB_LAUNCHER(maint)(size_t npad, void *arena, void *maint_side, int3
   hipLaunchKernelGGL(npb_maint_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, (const npd_maint_rule_consts_t *)maint_side,
                      npd_maint_cache_of(maint_side, counts, n_plants), npad, (npd_real_t *)arena);
 }
+/* the whole rule, pumps and components in one queue, behind the plain step kernel (npb_set_component_maintenance): cm_side = the handle's
+ * component side buffer (npb_launch_cmaint_side_bytes), its table uploaded */
+static void NPB_LAUNCHER(maint_all)(size_t npad, void *arena, void *maint_side, void *cm_side, int32_t *counts, int n_plants, double *diag, size_t diag_pitch,
+                                    hipStream_t stream) {
+  npd_cmaint_side_t side;
+  side.C = (const npd_cmaint_consts_t *)cm_side; side.state = (double *)((char *)cm_side + (sizeof(npd_cmaint_consts_t) + 255) / 256 * 256); side.pitch = NPD_NPAD(npad);
+  hipLaunchKernelGGL(npb_maint_all_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, (const npd_maint_rule_consts_t *)maint_side, side,
+                     npd_maint_cache_of(maint_side, counts, n_plants, diag, diag_pitch), npad, (npd_real_t *)arena);
+}
 #ifndef NPB_BUILD_F32
 /* the maintenance side buffer does not depend on the storage type (npd_maint_rule_consts_t holds no npd_real_t): one copy of
  * these.  The rule's constants as the device reads them: host_out = npb_launch_maint_consts_bytes() bytes */
@@ -1272,26 +1545,27 @@ static void NPB_LAUNCHER(init)(const npb_params_t *P, int n_plants, size_t npad,
   hipLaunchKernelGGL(npb_init_kernel, grid, block, 0, stream, *P, npad, (npd_real_t *)arena, mask, n_plants);
 }
 /* episodes (npb_snapshot / npb_restore / npb_set_autoreset): maint_side / maint_counts NULL unless params.maint_enabled */
-static npd_restore_side_t npd_restore_side_of(void *maint_side, int32_t *maint_counts, int n_plants) {
+static npd_restore_side_t npd_restore_side_of(void *maint_side, int32_t *maint_counts, int n_plants, npb_cmaint_restore_t cm) {
   npd_restore_side_t R;
   R.maint_entry = npd_maint_cache_of(maint_side, maint_counts, n_plants).entry; R.maint_counts = maint_counts; R.n_plants = n_plants;
+  R.cm = cm;
   return R;
 }
 /* src: the snapshot (npb_restore, the snapshot autoreset) or a bank with its slots (npb_restore_bank, the bank autoreset).  mask NULL
  * restores every lane of the pitch from the snapshot, the plants only from a bank (its slot columns have n entries) */
 static void NPB_LAUNCHER(restore)(int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *mask, int32_t *len, double *ret,
-                                  void *maint_side, int32_t *maint_counts, hipStream_t stream) {
+                                  void *maint_side, int32_t *maint_counts, npb_cmaint_restore_t cm, hipStream_t stream) {
   const int lanes = mask || src.next_slot ? n_plants : (int)NPD_NPAD(npad);
   hipLaunchKernelGGL(npb_restore_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, lanes, npad, (npd_real_t *)arena,
-                     src, mask, len, ret, npd_restore_side_of(maint_side, maint_counts, n_plants));
+                     src, mask, len, ret, npd_restore_side_of(maint_side, maint_counts, n_plants, cm));
 }
 static void NPB_LAUNCHER(episode)(int mode, int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *done, const double *reward,
                                   double *obs, int32_t *len, double *ret, int32_t *out_len, double *out_ret, uint8_t *out_truncated,
-                                  double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, hipStream_t stream) {
+                                  double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, npb_cmaint_restore_t cm, hipStream_t stream) {
   npd_episode_t E;
   E.len = len; E.ret = ret; E.out_len = out_len; E.out_ret = out_ret; E.out_truncated = out_truncated; E.final_obs = final_obs; E.max_steps = max_steps;
   hipLaunchKernelGGL(npb_episode_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, mode, n_plants, npad, (npd_real_t *)arena,
-                     src, done, reward, obs, E, npd_restore_side_of(maint_side, maint_counts, n_plants));
+                     src, done, reward, obs, E, npd_restore_side_of(maint_side, maint_counts, n_plants, cm));
 }
 /* npb_perform_maintenance: the caller's order columns; log_* = the maintenance event log (npb_set_maintenance_log), records NULL = off */
 static void NPB_LAUNCHER(operator_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *pump, const int32_t *bearing,
@@ -1326,7 +1600,7 @@ static void NPB_LAUNCHER(operator_turbine_maint)(int n_plants, size_t npad, void
 extern "C" npb_launchers_t NPB_LAUNCHER(table) = {
   NPB_LAUNCHER(step), NPB_LAUNCHER(maint), NPB_LAUNCHER(observe), NPB_LAUNCHER(init), NPB_LAUNCHER(reset),
   NPB_LAUNCHER(field_get), NPB_LAUNCHER(field_set), NPB_LAUNCHER(gather), NPB_LAUNCHER(restore), NPB_LAUNCHER(episode),
-  NPB_LAUNCHER(operator_maint), NPB_LAUNCHER(operator_component_maint), NPB_LAUNCHER(operator_turbine_maint),
+  NPB_LAUNCHER(operator_maint), NPB_LAUNCHER(operator_component_maint), NPB_LAUNCHER(operator_turbine_maint), NPB_LAUNCHER(maint_all),
 };
 #ifndef NPB_BUILD_F32
 /* npb_reset / npb_reset_reference / npb_restore: the episode counters (len, ret) and the carried start entries (start: -1, not from
@@ -1338,6 +1612,21 @@ __global__ void npb_episode_clear_kernel(const uint8_t *__restrict__ mask, int32
   if (len) len[p] = 0;
   if (ret) ret[p] = 0.0;
   if (start) start[p] = -1;
+}
+/* the component maintenance's side state (npd_component_auto.h) of the plants of mask (NULL = every lane of the pitch) as a freshly
+ * constructed plant has it (npb_set_component_maintenance, npb_reset) */
+__global__ void npb_cmaint_init_kernel(double *state, size_t pitch, const uint8_t *__restrict__ mask, int n_plants) {
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= pitch || (mask && (p >= (size_t)n_plants || !mask[p]))) return;
+  npd_cmaint_init(state, pitch, p);
+}
+/* the side buffer of one handle: [the table as the device reads it, a 256-byte slot][NPB_CMAINT_SIDE_DOUBLES][pitch] doubles */
+#define NPD_CMAINT_CONSTS_BYTES ((sizeof(npd_cmaint_consts_t) + 255) / 256 * 256)
+extern "C" size_t npb_launch_cmaint_side_bytes(size_t pitch) { return NPD_CMAINT_CONSTS_BYTES + (size_t)NPB_CMAINT_SIDE_DOUBLES * pitch * sizeof(double); }
+extern "C" size_t npb_launch_cmaint_state_offset(void) { return NPD_CMAINT_CONSTS_BYTES; }
+extern "C" void npb_launch_cmaint_init(void *cm_side, size_t pitch, const uint8_t *mask, int n_plants, hipStream_t stream) {
+  hipLaunchKernelGGL(npb_cmaint_init_kernel, dim3((unsigned)((pitch + 255) / 256)), dim3(256), 0, stream,
+                     (double *)((char *)cm_side + NPD_CMAINT_CONSTS_BYTES), pitch, mask, n_plants);
 }
 extern "C" void npb_launch_episode_clear(const uint8_t *mask, int32_t *len, double *ret, int32_t *start, int n_plants, size_t npad, hipStream_t stream) {
   const int n = (int)NPD_NPAD(npad);

@@ -216,6 +216,15 @@ class BatchedPlantEnv:
     steam-generator system, the condenser and its steam-jet ejectors (npb_perform_component_maintenance): TSP and scale cleaning,
     moisture-separator work, condenser cleaning and water treatment, leak repair, ejector cleaning and nozzle replacement.
 
+    Automatic maintenance of steam generators and condenser: ``component_maintenance=True`` (with ``maintenance=True``, full mode) has
+    the three generators and the condenser scanned and maintained in ONE work-order queue with the feedwater pumps, as the reference's
+    AutoMaintenanceSystem does (npb_set_component_maintenance): rows tsp_fouling_fraction / tube_wall_temperature / steam_quality per
+    generator and fouling_resistance on the condenser, one shared order counter, one due order per check -- which also changes when a
+    pump's order is carried out.  ``component_thresholds={"steam_generator": {...}, "condenser": {...}}`` replaces the composer's rows
+    (the reference's thresholds dicts, ``_lib.component_maint_table_from_thresholds``).  Its per-plant state lives in a side buffer
+    (``component_maintenance_state()`` / ``load_component_maintenance_state()``): resets, ``snapshot`` / ``restore``, the autoreset
+    and the start bank take it along; a checkpoint must save it beside ``state_arrays()``.  Off by default: nothing changes.
+
     Heat-source noise (``noise_enabled``): ``noise_generator="host"`` (the default) draws each plant's
     ``RandomState(seed).standard_normal()`` stream on the host (``HeatSourceNoise``); ``"device"`` generates the same streams on the
     device (``DeviceHeatSourceNoise``: integer state exactly numpy's, every draw within a few ulp), with no host work per step.
@@ -230,9 +239,16 @@ class BatchedPlantEnv:
                  mode: str = "full", device: int = 0, params: Optional[dict] = None, maintenance: bool = False,
                  storage: str = "f64", maintenance_thresholds: Optional[dict] = None, reactivity_components: bool = False,
                  integrator: str = "reference", autoreset: bool = False, max_episode_steps: Optional[int] = None,
-                 noise_generator: str = "host"):
+                 noise_generator: str = "host", component_maintenance: bool = False, component_thresholds: Optional[dict] = None):
         if max_episode_steps is not None and not autoreset:
             raise ValueError("max_episode_steps needs autoreset=True")
+        if component_thresholds is not None and not component_maintenance:
+            raise ValueError("component_thresholds needs component_maintenance=True")
+        if component_maintenance and not (maintenance and mode == "full"):
+            raise ValueError("component_maintenance needs maintenance=True and mode='full': the generators and the condenser share the pumps' work-order queue")
+        component_table = None
+        if component_thresholds is not None:      # an unknown parameter or action is refused before any device work
+            component_table = _lib.component_maint_table_from_thresholds(component_thresholds)
         if noise_generator not in NOISE_GENERATORS:
             raise ValueError("noise_generator must be one of %r" % (NOISE_GENERATORS,))
         if not torch.cuda.is_available():
@@ -277,6 +293,14 @@ class BatchedPlantEnv:
         if maintenance_thresholds is not None:   # the reference's thresholds dict for a feedwater pump, in its order
             table = _lib.maint_table_from_thresholds(maintenance_thresholds)
             _lib.check(self.L.npb_set_maintenance_table(self._h, ctypes.byref(table)), self._h)
+        self.component_maintenance = bool(component_maintenance)
+        if component_maintenance:      # before the first snapshot (autoreset=True takes it below), so that it records the side state
+            if not hasattr(self.L, "npb_set_component_maintenance"):
+                raise _lib.NpbError("libnpb.so has no npb_set_component_maintenance (older than ABI 150): rebuild")
+            if component_table is None:
+                component_table = _lib.NpbComponentMaintTable()
+                self.L.npb_default_component_maintenance_table(ctypes.byref(component_table))
+            _lib.check(self.L.npb_set_component_maintenance(self._h, ctypes.byref(component_table)), self._h)
         with torch.cuda.device(self.device):
             self._obs = torch.zeros((self.n, 22), dtype=torch.float64, device=self.device)
             self._reward = torch.zeros(self.n, dtype=torch.float64, device=self.device)
@@ -310,7 +334,8 @@ class BatchedPlantEnv:
     def action_test(cls, action: str, seeds: Sequence[int], dt: float = 5.0, device: int = 0, randomize: bool = True,
                     params: Optional[dict] = None, autoreset: bool = False, max_episode_steps: Optional[int] = None,
                     bank_seeds: Optional[Sequence[int]] = None, noise_generator: str = "host",
-                    maintenance_log: Optional[int] = None) -> "BatchedPlantEnv":
+                    maintenance_log: Optional[int] = None, component_maintenance: bool = False,
+                    component_thresholds: Optional[dict] = None) -> "BatchedPlantEnv":
         """One plant per seed, as data_gen's MaintenanceScenarioRunner builds them for
         ``compose_action_test_scenario(action, randomize=True, randomization_seed=seed)``
         (maintenance_scenario_runner.py:210-244): dt in minutes, ConstantHeatSource with 0.1 % noise seeded 42,
@@ -318,12 +343,15 @@ class BatchedPlantEnv:
         snapshot is taken after the initial conditions are in: each plant restarts from its own.  With ``bank_seeds`` later
         episodes start from a bank built as ``action_test(action, bank_seeds)`` with the same ``randomize``, ``dt`` and ``params``
         (``set_start_bank`` with its default slots): each restart draws a fresh scenario, as the data-gen runner's episodes do.
-        ``noise_generator`` as for the constructor; ``maintenance_log`` = a capacity: ``enable_maintenance_log(capacity)``."""
+        ``noise_generator`` as for the constructor; ``maintenance_log`` = a capacity: ``enable_maintenance_log(capacity)``.
+        ``component_maintenance`` / ``component_thresholds`` as for the constructor: the runner's plant has the automatic maintenance of
+        the steam generators and the condenser on as well (the composer's rows by default); off by default, as before."""
         if max_episode_steps is not None and not autoreset:
             raise ValueError("max_episode_steps needs autoreset=True")
         from . import scenarios
         env = cls(len(seeds), dt=dt, heat_source="constant", noise_enabled=True, noise_std_percent=0.1,
-                  noise_seeds=[42] * len(seeds), device=device, maintenance=True, params=params, noise_generator=noise_generator)
+                  noise_seeds=[42] * len(seeds), device=device, maintenance=True, params=params, noise_generator=noise_generator,
+                  component_maintenance=component_maintenance, component_thresholds=component_thresholds)
         eff = float(env.get_field("pump.lubrication_effectiveness")[0].item())
         env.set_fields(scenarios.action_test_fields(action, seeds, eff, randomize=randomize))
         # what a state log of these plants needs beside their state: the composer's provider names and the values the constructor
@@ -334,7 +362,8 @@ class BatchedPlantEnv:
             env.snapshot()
             env._enable_autoreset(max_episode_steps)
         if bank_seeds is not None:
-            bank = cls.action_test(action, bank_seeds, dt=dt, device=device, randomize=randomize, params=params)
+            bank = cls.action_test(action, bank_seeds, dt=dt, device=device, randomize=randomize, params=params,
+                                   component_maintenance=component_maintenance, component_thresholds=component_thresholds)
             env.set_start_bank(bank)
             torch.cuda.current_stream(env.device).synchronize()     # the copy has read the bank batch's arena
             bank.close()
@@ -445,11 +474,11 @@ class BatchedPlantEnv:
         """``maintenance_log_records`` as columns sorted by (plant, time, completion before creation, pump), named as the
         reference's export (nuclear_sim_amd/maintlog.py): plant, pump, action_type, event_type, timestamp_minutes / _hours,
         work_order_id, component_id, priority, work_order_type, title, created_date, planned_start_date, actual_completion_date,
-        bearing, trigger_parameters, has_handler."""
+        bearing, trigger_parameters, has_handler; with ``component_maintenance`` also success (a completed component order's result)."""
         from . import maintlog
         rec = self.maintenance_log_records(clear=clear, allow_overflow=allow_overflow)
         handlers = [int(self.L.npb_maint_action_has_handler(a)) for a in range(len(_lib.MAINT_ACTIONS))]
-        return maintlog.columns(rec, _lib.MAINT_ACTIONS, _lib.MAINT_PARAMS, handlers)
+        return maintlog.columns(rec, _lib.MAINT_ACTIONS, _lib.MAINT_PARAMS, handlers, naming=self.log_naming, with_success=self.component_maintenance)
 
     def write_maintenance_log(self, path: str, clear: bool = True, allow_overflow: bool = False) -> None:
         """Drain the log into a CSV (``.csv``) or Parquet file"""
@@ -754,6 +783,22 @@ class BatchedPlantEnv:
         for s in range(SCHEMA.total_i32):
             _lib.check(self.L.npb_get_field(self._h, 1, s, ctypes.c_void_p(i[s].data_ptr()), 1, self._stream()), self._h)
         return f, i
+
+    def component_maintenance_state(self) -> torch.Tensor:
+        """[_lib.CMAINT_SIDE_DOUBLES, n] copy of the side state of the automatic maintenance of steam generators and condenser
+        (npb_get_component_maintenance_state; rows: member of _lib.CMAINT_STATE_MEMBERS x (component of _lib.CMAINT_COMPONENTS x row),
+        include/npb_maint.h).  It is plant state that lives outside the arena: a checkpoint saves it beside ``state_arrays()``."""
+        t = torch.empty((_lib.CMAINT_SIDE_DOUBLES, self.n), dtype=torch.float64, device=self.device)
+        assert int(self.L.npb_component_maintenance_state_bytes(self._h)) == t.numel() * 8
+        _lib.check(self.L.npb_get_component_maintenance_state(self._h, self._p(t), self._stream()), self._h)
+        return t
+
+    def load_component_maintenance_state(self, state) -> None:
+        """the inverse of ``component_maintenance_state`` (npb_set_component_maintenance_state)"""
+        t = torch.as_tensor(state, dtype=torch.float64).to(self.device).contiguous()
+        if t.shape != (_lib.CMAINT_SIDE_DOUBLES, self.n):
+            raise ValueError("component maintenance state must be [%d, %d]" % (_lib.CMAINT_SIDE_DOUBLES, self.n))
+        _lib.check(self.L.npb_set_component_maintenance_state(self._h, self._p(t), self._stream()), self._h)
 
     def load_state_arrays(self, f64, i32) -> None:
         f = torch.as_tensor(f64, dtype=torch.float64).to(self.device).contiguous()

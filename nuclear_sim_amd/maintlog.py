@@ -16,7 +16,7 @@ import numpy as np
 EVENT_DTYPE = np.dtype([("time", "<f8"), ("created", "<f8"), ("planned_start", "<f8"), ("plant", "<i4"), ("order", "<i4"),
                         ("trigger", "<u2"), ("pump", "u1"), ("action", "u1"), ("kind", "u1"), ("priority", "u1"), ("bearing", "u1"),
                         ("reserved", "u1")])
-CREATED, COMPLETED, OPERATOR, OPERATOR_COMPONENT, OPERATOR_TURBINE = 0, 1, 2, 3, 4    # NPB_MAINT_EVENT_*
+CREATED, COMPLETED, OPERATOR, OPERATOR_COMPONENT, OPERATOR_TURBINE, COMPONENT_CREATED, COMPONENT_COMPLETED = 0, 1, 2, 3, 4, 5, 6    # NPB_MAINT_EVENT_*
 # OPERATOR: an action ordered through npb_perform_maintenance (BatchedPlantEnv.perform_maintenance) and carried out at once: no work
 # order (order 0, id ""), created = planned start = time = the plant's clock at the call
 # OPERATOR_COMPONENT: the same through npb_perform_component_maintenance (BatchedPlantEnv.perform_component_maintenance): ``action`` is an
@@ -25,8 +25,16 @@ CREATED, COMPLETED, OPERATOR, OPERATOR_COMPONENT, OPERATOR_TURBINE = 0, 1, 2, 3,
 # OPERATOR_TURBINE: the same through npb_perform_turbine_maintenance (BatchedPlantEnv.perform_turbine_maintenance): ``action`` is an index of
 # the TURBINE catalog (NPB_TURBINE_ACTIONS, _lib.TURBINE_ACTIONS), the ``pump`` byte the unit (bearing 0..3, stage 0..13; 0 for the turbine and
 # the lubrication system)
+# COMPONENT_CREATED / COMPONENT_COMPLETED: a work order of the automatic maintenance of a steam generator or the condenser
+# (npb_set_component_maintenance): ``action`` an index of the COMPONENT catalog, the ``pump`` byte the unit, the ``bearing`` byte the component
+# kind (0 steam generator, 2 condenser), ``priority`` on both records, ``trigger`` bit r = row r of the component (its parameters in
+# _lib.CMAINT_PARAMS order), the ``reserved`` byte of a completion = the result's success; ``order`` is the reference's number: pumps and
+# components count from one counter
 EVENT_TYPES = ("work_order_created", "work_order_completed", "operator_maintenance", "operator_component_maintenance",
-               "operator_turbine_maintenance")
+               "operator_turbine_maintenance", "work_order_created", "work_order_completed")
+# the reference's id of the condenser under each naming of the plant's providers (BatchedPlantEnv.log_naming: "composed" = the data-gen
+# composer's configuration, "default" = a default-constructed simulator's; nuclear_sim_amd/statelog.py log_column_name)
+CONDENSER_IDS = {"composed": "SECONDARY-COMP-001-COND", "default": "SECONDARY-001-COND"}
 # the reference's ids of the turbine's objects as the data-gen runner's plant names them: the turbine's config.system_id, the keys of
 # rotor_dynamics.bearings and stage_system.stages, the lubrication system's config.system_id (tests/golden/operator_turbine/ot4_long_run.npz
 # records them from the live objects)
@@ -58,7 +66,7 @@ def sort_events(rec: np.ndarray) -> np.ndarray:
     operator action follows the step whose clock it carries, so it sorts behind that step's work-order events; two operator actions of
     one plant on one pump at one time keep the order they are given in (the device's)."""
     rec = np.asarray(rec, dtype=EVENT_DTYPE)
-    rank = np.where(rec["kind"] == COMPLETED, 0, np.where(rec["kind"] == OPERATOR, 2, np.where(rec["kind"] == OPERATOR_COMPONENT, 3,
+    rank = np.where((rec["kind"] == COMPLETED) | (rec["kind"] == COMPONENT_COMPLETED), 0, np.where(rec["kind"] == OPERATOR, 2, np.where(rec["kind"] == OPERATOR_COMPONENT, 3,
                                                                                              np.where(rec["kind"] == OPERATOR_TURBINE, 4, 1))))
     return rec[np.lexsort((rec["pump"], rank, rec["time"], rec["plant"]))]
 
@@ -82,29 +90,39 @@ def turbine_component_id(kind: str, unit: int) -> str:
     return {"turbine": TURBINE_ID, "lubrication": TURBINE_LUBRICATION_ID}[kind]
 
 
-def columns(rec: np.ndarray, actions: Sequence[str], params: Sequence[str], handlers: Sequence[int]) -> Dict[str, np.ndarray]:
+def auto_component_id(kind: int, unit: int, naming: str = "default") -> str:
+    """the reference's id of the object an automatic component order names: SG-<i>, or the condenser's id under ``naming``"""
+    return "SG-%d" % unit if kind == 0 else CONDENSER_IDS[naming]
+
+
+def columns(rec: np.ndarray, actions: Sequence[str], params: Sequence[str], handlers: Sequence[int], naming: str = "default",
+            with_success: bool = False) -> Dict[str, np.ndarray]:
     """Drained records -> columns, sorted by ``sort_events``.  ``actions`` / ``params`` / ``handlers``: the catalogs of
     include/npb_maint.h (``_lib.MAINT_ACTIONS``, ``_lib.MAINT_PARAMS``, ``npb_maint_action_has_handler``).  A completion takes its
     priority from its creation record when that record is among ``rec``, else it has none ("").  An operator action
     (``event_type`` "operator_maintenance", "operator_component_maintenance", "operator_turbine_maintenance") has no work order: its id,
     priority and work-order type are "", its dates the time of the call; a component action is named from the component catalog and its
     object (``component_id``), a turbine action from the turbine catalog (``turbine_component_id``)."""
-    from ._lib import COMPONENT_ACTIONS, TURBINE_ACTIONS
+    from ._lib import CMAINT_AUTO_ACTIONS, COMPONENT_ACTIONS, TURBINE_ACTIONS
     rec = sort_events(rec)
     n = len(rec)
     kind = rec["kind"].astype(np.int64)
-    created = kind == CREATED
+    auto_comp = (kind == COMPONENT_CREATED) | (kind == COMPONENT_COMPLETED)      # orders on a generator or the condenser: named from the COMPONENT catalog
+    created = (kind == CREATED) | (kind == COMPONENT_CREATED)
     prio_of = {(int(p), int(o)): int(q) for p, o, q in zip(rec["plant"][created], rec["order"][created], rec["priority"][created])}
     operator = (kind == OPERATOR) | (kind == OPERATOR_COMPONENT) | (kind == OPERATOR_TURBINE)
-    prio = np.array([int(q) if k == CREATED else (0 if op else prio_of.get((int(p), int(o)), 0))
+    prio = np.array([int(q) if k in (CREATED, COMPONENT_CREATED, COMPONENT_COMPLETED) else (0 if op else prio_of.get((int(p), int(o)), 0))
                      for k, op, p, o, q in zip(kind, operator, rec["plant"], rec["order"], rec["priority"])], dtype=np.int64)
-    action = [COMPONENT_ACTIONS[int(a)][1] if k == OPERATOR_COMPONENT else TURBINE_ACTIONS[int(a)][1] if k == OPERATOR_TURBINE else actions[int(a)]
+    auto_names = {v: k[1] for k, v in CMAINT_AUTO_ACTIONS.items()}      # an automatic order's action from behind the catalog
+    action = [auto_names[int(a)] if int(a) in auto_names and k in (COMPONENT_CREATED, COMPONENT_COMPLETED) else
+              COMPONENT_ACTIONS[int(a)][1] if k in (OPERATOR_COMPONENT, COMPONENT_CREATED, COMPONENT_COMPLETED) else TURBINE_ACTIONS[int(a)][1] if k == OPERATOR_TURBINE else actions[int(a)]
               for a, k in zip(rec["action"], kind)]
-    component = [component_id(COMPONENT_ACTIONS[int(a)][0], int(u)) if k == OPERATOR_COMPONENT else
+    component = [auto_component_id(int(b), int(u), naming) if k in (COMPONENT_CREATED, COMPONENT_COMPLETED) else
+                 component_id(COMPONENT_ACTIONS[int(a)][0], int(u)) if k == OPERATOR_COMPONENT else
                  turbine_component_id(TURBINE_ACTIONS[int(a)][0], int(u)) if k == OPERATOR_TURBINE else "FWP-%d" % (int(u) + 1)
-                 for u, a, k in zip(rec["pump"], rec["action"], kind)]
+                 for u, a, k, b in zip(rec["pump"], rec["action"], kind, rec["bearing"])]
     time = rec["time"].astype(np.float64)
-    return {
+    out = {
         "plant": rec["plant"].astype(np.int64),
         "pump": rec["pump"].astype(np.int64),
         "action_type": np.array(action, dtype=object),
@@ -119,11 +137,23 @@ def columns(rec: np.ndarray, actions: Sequence[str], params: Sequence[str], hand
                            for a, c, op in zip(action, component, operator)], dtype=object),
         "created_date": rec["created"].astype(np.float64),
         "planned_start_date": rec["planned_start"].astype(np.float64),
-        "actual_completion_date": np.where((kind == COMPLETED) | operator, time, np.nan),
-        "bearing": np.array([BEARING_NAMES.get(int(b), "") for b in rec["bearing"]], dtype=object),
-        "trigger_parameters": np.array([";".join(params[q] for q in range(len(params)) if (int(m) >> q) & 1) for m in rec["trigger"]], dtype=object),
-        "has_handler": np.array([k in (OPERATOR_COMPONENT, OPERATOR_TURBINE) or bool(handlers[int(a)]) for a, k in zip(rec["action"], kind)], dtype=bool) if n else np.zeros(0, dtype=bool),
+        "actual_completion_date": np.where((kind == COMPLETED) | (kind == COMPONENT_COMPLETED) | operator, time, np.nan),
+        "bearing": np.array([BEARING_NAMES.get(int(b), "") if not ac else "" for b, ac in zip(rec["bearing"], auto_comp)], dtype=object),
+        "trigger_parameters": np.array([";".join(_component_rows(int(b))[q] for q in range(3) if (int(m) >> q) & 1 and q < len(_component_rows(int(b)))) if ac else
+                                        ";".join(params[q] for q in range(len(params)) if (int(m) >> q) & 1)
+                                        for m, ac, b in zip(rec["trigger"], auto_comp, rec["bearing"])], dtype=object),
+        "has_handler": np.array([k in (OPERATOR_COMPONENT, OPERATOR_TURBINE, COMPONENT_CREATED, COMPONENT_COMPLETED) or bool(handlers[int(a)])
+                                 for a, k in zip(rec["action"], kind)], dtype=bool) if n else np.zeros(0, dtype=bool),
     }
+    if with_success:      # (only where component orders can occur, so that a log of the pumps alone keeps the columns it had)
+        out["success"] = np.array([bool(s) if k == COMPONENT_COMPLETED else True for s, k in zip(rec["reserved"], kind)], dtype=bool) if n else np.zeros(0, dtype=bool)
+    return out
+
+
+def _component_rows(kind: int):
+    """the scanned parameters of a component kind (0 steam generator, 2 condenser), in row order"""
+    from ._lib import CMAINT_PARAMS, COMPONENT_KINDS
+    return [name for k, name in CMAINT_PARAMS if k == COMPONENT_KINDS[kind]]
 
 
 def table(cols: Dict[str, np.ndarray]):
