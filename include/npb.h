@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define NPB_VERSION 150 /* 0.1.5.0: npb_set_component_maintenance, npb_default_component_maintenance_table, npb_component_maint_* catalog queries, npb_get / npb_set_component_maintenance_state, NPB_MAINT_EVENT_COMPONENT_CREATED / _COMPLETED (automatic maintenance of steam generators and condenser in one work-order queue with the feedwater pumps); 0.1.4.9: npb_perform_turbine_maintenance, npb_turbine_* catalog queries, NPB_MAINT_EVENT_OPERATOR_TURBINE (maintenance of the turbine, its bearings, lubrication system and stages a caller orders); 0.1.4.8: npb_perform_component_maintenance, npb_component_* catalog queries, NPB_MAINT_EVENT_OPERATOR_COMPONENT (maintenance of steam generators, condenser and ejectors a caller orders); 0.1.4.7: npb_perform_maintenance, NPB_MAINT_EVENT_OPERATOR (maintenance a caller orders, carried out on the device between two steps); 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
+#define NPB_VERSION 151 /* 0.1.5.1: npb_carry_diagnostics, npb_diag_num_carried / npb_diag_carried_row / npb_diag_carried_fresh, npb_get / npb_set_diagnostics_state, npb_set_episode_index_buffer (the diagnostics rows the step carries travel with snapshots, start banks, the autoreset, resets and checkpoints; an episode index per plant); 0.1.5.0: npb_set_component_maintenance, npb_default_component_maintenance_table, npb_component_maint_* catalog queries, npb_get / npb_set_component_maintenance_state, NPB_MAINT_EVENT_COMPONENT_CREATED / _COMPLETED (automatic maintenance of steam generators and condenser in one work-order queue with the feedwater pumps); 0.1.4.9: npb_perform_turbine_maintenance, npb_turbine_* catalog queries, NPB_MAINT_EVENT_OPERATOR_TURBINE (maintenance of the turbine, its bearings, lubrication system and stages a caller orders); 0.1.4.8: npb_perform_component_maintenance, npb_component_* catalog queries, NPB_MAINT_EVENT_OPERATOR_COMPONENT (maintenance of steam generators, condenser and ejectors a caller orders); 0.1.4.7: npb_perform_maintenance, NPB_MAINT_EVENT_OPERATOR (maintenance a caller orders, carried out on the device between two steps); 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
 #ifndef NPB_API
 #define NPB_API __attribute__((visibility("default")))
 #endif
@@ -109,6 +109,17 @@ enum {
   NPB_DIAG_STAGE_SYSTEM_TOTAL_POWER = 169,
   NPB_DIAG_DIM = 170
 };
+/* The rows above that the step CARRIES in the caller's buffer from one step to the next -- accumulators, latches, values kept while
+ * equipment rests: plant state that lives beside the arena -- stated once: X(row, value of a freshly constructed plant), in the order
+ * npb_get_diagnostics_state / npb_set_diagnostics_state move them.  npb_diag_num_carried / _carried_row / _carried_fresh read it. */
+#define NPB_DIAG_CARRIED(X) \
+  X(NPB_DIAG_ROTOR_CLEARANCE_INCREASE + 0, 0.0) X(NPB_DIAG_ROTOR_CLEARANCE_INCREASE + 1, 0.0) X(NPB_DIAG_ROTOR_CLEARANCE_INCREASE + 2, 0.0) \
+  X(NPB_DIAG_ROTOR_CLEARANCE_INCREASE + 3, 0.0) X(NPB_DIAG_ROTOR_OVERSPEED_EVENTS, 0.0) \
+  X(NPB_DIAG_STAGE_SYSTEM_EFFICIENCY, 0.0)      /* a zero reads as 1.0 (above) */ \
+  X(NPB_DIAG_FW_VALID_TRIP_COUNT, 0.0) X(NPB_DIAG_FW_EMERGENCY_FEEDWATER, 0.0) X(NPB_DIAG_FW_STEAM_DUMP, 0.0) \
+  X(NPB_DIAG_COND_SJE_COMPRESSION_RATIO + 0, 1.0) X(NPB_DIAG_COND_SJE_COMPRESSION_RATIO + 1, 1.0) \
+  X(NPB_DIAG_COND_SJE_OPERATING_HOURS + 0, 0.0) X(NPB_DIAG_COND_SJE_OPERATING_HOURS + 1, 0.0)
+enum { NPB_DIAG_NUM_CARRIED = 13 };
 /* info["reactivity_components"] (sim.py:205; reactivity_model.py:77-125, pcm, the dict's insertion order).  Only the
  * reactor heat source has them, and only a caller that sets params.info_reactivity_components gets them: the info
  * buffer handed to npb_step must then hold a second block behind the first, [n_plants][NPB_INFO_DIM] followed by
@@ -382,6 +393,24 @@ NPB_API int npb_step(NpbHandle *h, const int32_t *action, const double *magnitud
  * device, pitch >= n_plants rounded up to a multiple of 64; NULL = off, the default).  While it is set the step runs the diagnostics build of the one-wave
  * kernel at every batch size (same results, ~1.4x the time at small batches); full mode only. */
 NPB_API int npb_set_diagnostics(NpbHandle *h, double *buf, size_t pitch);
+/* The carried rows (NPB_DIAG_CARRIED): how many, row k's number, the value row k has in a freshly constructed plant. */
+NPB_API int npb_diag_num_carried(void);
+NPB_API int npb_diag_carried_row(int k);        /* -1 outside [0, npb_diag_num_carried()) */
+NPB_API double npb_diag_carried_fresh(int k);   /* NaN outside */
+/* on != 0: the handle treats the carried rows of the caller's diagnostics buffer as plant state.  The buffer stays the live copy -- the
+ * step kernels read and write it as before -- and npb_snapshot records the rows beside the snapshot arena, npb_set_start_bank copies the
+ * bank handle's beside the bank, npb_restore / npb_restore_bank / the autoreset put them back per plant with the arena, npb_reset puts a
+ * freshly constructed plant's values and npb_reset_reference what NuclearPlantSimulator.reset() leaves (every row to its fresh value,
+ * the stage system's efficiency as 1.0, except the ejectors' compression ratios, which are kept), for the plants they reset.  Needs a buffer set by
+ * npb_set_diagnostics (so: full mode); NPB_EINVAL otherwise.  While it is on, npb_set_autoreset is accepted if the source it restores
+ * from (the snapshot, or the bank with slots) was recorded with the rows, and while both are on npb_set_diagnostics (any buffer, or
+ * NULL) and npb_carry_diagnostics(h, 0) are refused; without autoreset npb_set_diagnostics with another buffer is refused while carrying
+ * is on (switch carrying off first) and NULL switches both off.  A handle that never calls this behaves as before in every entry point. */
+NPB_API int npb_carry_diagnostics(NpbHandle *h, int on);
+/* the carried rows of every plant as [npb_diag_num_carried()][n_plants] doubles (device or host), in table order: what a checkpoint
+ * saves beside the arena.  Synchronous on `stream`.  NPB_EINVAL without carrying. */
+NPB_API int npb_get_diagnostics_state(NpbHandle *h, double *buf, void *stream);
+NPB_API int npb_set_diagnostics_state(NpbHandle *h, const double *buf, void *stream);
 
 /* Which of the two step kernels npb_step launches (same device functions in the same per-plant order: identical int32
  * columns and flags, reals equal to the last bit or two; this is a measurement / A-B aid):
@@ -435,7 +464,8 @@ NPB_API int npb_restore(NpbHandle *h, const uint8_t *mask, void *stream);
  * truncation flag.  With a start bank and slots (npb_set_start_bank, npb_set_start_slots) the reset plants are restored from their
  * bank entries instead.  Needs a snapshot, or a bank and slots; allocates the handle's carried counters (int32 length[pitch], double return[pitch]) and
  * zeroes them; npb_step then needs a non-NULL done column.  Refused (NPB_EINVAL) while npb_set_diagnostics is set, as that is
- * refused while autoreset is on: the diagnostics buffer carries plant state outside the arena.  enabled = 0 turns it off.
+ * refused while autoreset is on: the diagnostics buffer carries plant state outside the arena -- unless npb_carry_diagnostics is on
+ * and the snapshot (or the bank) was recorded with the carried rows, which the restores then take along.  enabled = 0 turns it off.
  * npb_reset, npb_reset_reference and npb_restore zero the counters of the plants they reset. */
 NPB_API int npb_set_autoreset(NpbHandle *h, int enabled, int max_episode_steps /* 0 = no limit */);
 /* the caller's output columns of the episode kernel (device; each may be NULL): length int32[n], ret double[n], truncated
@@ -463,6 +493,11 @@ NPB_API int npb_restore_bank(NpbHandle *h, const uint8_t *mask, void *stream);
  * -1 for an episode that did not start from the bank: construction, npb_reset, npb_reset_reference and npb_restore put the carried
  * entry to -1. */
 NPB_API int npb_set_episode_start_buffer(NpbHandle *h, int32_t *out_start);
+/* Episode index: with autoreset the handle counts each plant's episodes -- one int32 per plant, zeroed by npb_set_autoreset and bumped
+ * wherever the plant's episode length is zeroed (the autoreset, npb_restore, npb_restore_bank, npb_reset, npb_reset_reference).  A
+ * caller column (device int32[n], NULL = none) receives on every step the index of the episode this step's transition belonged to (a
+ * plant reset on the step: its finished episode's, as length / ret of npb_set_episode_buffers). */
+NPB_API int npb_set_episode_index_buffer(NpbHandle *h, int32_t *index);
 
 /* Heat-source noise streams on the device (constant_heat_source.py:58-62,178: each ConstantHeatSource owns a
  * np.random.RandomState(seed) and draws rng.normal(0, sigma) per step, i.e. sigma * standard_normal()).  One MT19937 per plant,

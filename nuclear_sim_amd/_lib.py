@@ -53,7 +53,8 @@ DIAG_COND_SJE_COMPRESSION_RATIO, DIAG_COND_SJE_OPERATING_HOURS, DIAG_COND_AIR_RE
 DIAG_STAGE_SYSTEM_TOTAL_POWER = 169
 DIAG_STAGE_POWER_OUTPUT = 56                # x14 (NPB_DIAG_STAGE_POWER_OUTPUT)
 # rows the step CARRIES in the caller's buffer from one step to the next (accumulators, latches, values kept while equipment
-# rests): row -> value of a freshly constructed plant.  BatchedPlantEnv.enable_diagnostics / reset put them there.
+# rests): row -> value of a freshly constructed plant, in the order of include/npb.h NPB_DIAG_CARRIED (checked against the library in
+# load(); the rows of BatchedPlantEnv.diagnostics_state()).  BatchedPlantEnv.enable_diagnostics / reset put them there.
 DIAG_CARRIED_ROWS = {**{124 + q: 0.0 for q in range(5)}, 133: 0.0, DIAG_FW_VALID_TRIP_COUNT: 0.0, DIAG_FW_EMERGENCY_FEEDWATER: 0.0,
                      DIAG_FW_STEAM_DUMP: 0.0, DIAG_COND_SJE_COMPRESSION_RATIO: 1.0, DIAG_COND_SJE_COMPRESSION_RATIO + 1: 1.0,
                      DIAG_COND_SJE_OPERATING_HOURS: 0.0, DIAG_COND_SJE_OPERATING_HOURS + 1: 0.0}
@@ -434,6 +435,18 @@ def load():
                         for k in range(L.npb_component_maint_num_params()))
         if catalog != CMAINT_PARAMS:
             raise NpbError("libnpb.so's component parameter catalog is not this binding's CMAINT_PARAMS: rebuild")
+    if hasattr(L, "npb_carry_diagnostics"):     # ABI 151: the carried diagnostics rows travel with restores, resets and checkpoints
+        L.npb_carry_diagnostics.argtypes = [vp, ci]
+        L.npb_diag_carried_row.argtypes = [ci]
+        L.npb_diag_carried_fresh.argtypes = [ci]
+        L.npb_diag_carried_fresh.restype = ctypes.c_double
+        L.npb_get_diagnostics_state.argtypes = [vp, vp, vp]
+        L.npb_set_diagnostics_state.argtypes = [vp, vp, vp]
+        L.npb_set_episode_index_buffer.argtypes = [vp, vp]
+        table = {L.npb_diag_carried_row(k): L.npb_diag_carried_fresh(k) for k in range(L.npb_diag_num_carried())}
+        if table != DIAG_CARRIED_ROWS or list(table) != list(DIAG_CARRIED_ROWS):
+            raise NpbError("libnpb.so carries the diagnostics rows %r (include/npb.h NPB_DIAG_CARRIED), this binding's DIAG_CARRIED_ROWS is %r: "
+                           "rebuild the library or update nuclear_sim_amd/_lib.py" % (table, DIAG_CARRIED_ROWS))
     if hasattr(L, "npb_noise_seed"):     # ABI 145: heat-source noise streams on the device
         L.npb_noise_seed.argtypes = [vp, vp, vp]
         L.npb_noise_fill.argtypes = [vp, ci, vp, vp]

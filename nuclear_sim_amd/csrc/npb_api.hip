@@ -26,6 +26,10 @@ struct NpbHandle {
   void *maint_side;      /* automatic maintenance: the rule's constants as the device reads them + the screen's cooldown cache (npb_kernels.hip; behind the staging column) */
   std::vector<char> maint_consts_host;
   double *diag; size_t diag_pitch; /* npb_set_diagnostics: the caller's [NPB_DIAG_DIM][diag_pitch] buffer, or NULL */
+  /* npb_carry_diagnostics: the carried rows of that buffer (include/npb.h NPB_DIAG_CARRIED) are plant state the handle takes along */
+  bool diag_carry;
+  double *diag_snap;   /* npb_snapshot while carrying: the rows beside the snapshot arena ([NPB_DIAG_NUM_CARRIED][pitch], table order), or NULL */
+  double *diag_bank; size_t diag_bank_pitch, diag_bank_doubles;   /* npb_set_start_bank from a carrying handle: its rows, its pitch, the allocation */
   int32_t *maint_counts;           /* npb_set_maintenance_count_buffer: the caller's [n_plants] int32 column, or NULL */
   npb_maint_event_t *maint_log; uint32_t *maint_log_cursor; int maint_log_capacity;   /* npb_set_maintenance_log: the caller's records and cursor, or NULL */
   bool maint_cache_stale;          /* the cooldown cache of the step kernels' maintenance screen must be zeroed before the next step */
@@ -40,6 +44,8 @@ struct NpbHandle {
   double *cm_bank; size_t cm_bank_pitch, cm_bank_doubles;   /* npb_set_start_bank from a handle with the feature on: its side state, its pitch, the allocation */
   void *snap;          /* npb_snapshot: the episode-start arena, the arena's layout, or NULL */
   int32_t *ep_len; double *ep_ret; /* npb_set_autoreset: carried steps / summed reward of each plant's running episode ([pitch] each), or NULL */
+  int32_t *ep_index;   /* with them: the number of each plant's running episode ([pitch]), bumped wherever ep_len is zeroed */
+  int32_t *ep_out_index;   /* npb_set_episode_index_buffer: the caller's column, or NULL */
   bool autoreset; int max_episode_steps;
   int32_t *ep_out_len; double *ep_out_ret; uint8_t *ep_out_truncated; double *ep_final_obs;   /* npb_set_episode_buffers: the caller's columns, or NULL */
   void *bank; size_t bank_bytes; size_t bank_N; int bank_M;   /* npb_set_start_bank: the bank arena (src's layout), its allocation, its packed pitch (NPB_N of src), its entries */
@@ -131,8 +137,31 @@ static const char *const g_cm_no_bank = "the component maintenance is on (npb_se
                                         "from a handle that has it";
 static void clear_episodes(NpbHandle *h, const uint8_t *mask, bool counters, hipStream_t stream) {
   int32_t *len = counters ? h->ep_len : nullptr;
-  if (len || h->ep_start) npb_launch_episode_clear(mask, len, counters ? h->ep_ret : nullptr, h->ep_start, h->n_plants, h->pitch, stream);
+  if (len || h->ep_start) npb_launch_episode_clear(mask, len, counters ? h->ep_ret : nullptr, h->ep_index, h->ep_start, h->n_plants, h->pitch, stream);
 }
+static npb_episode_counters_t counters_of(const NpbHandle *h) { return npb_episode_counters_t{h->ep_len, h->ep_ret, h->ep_index, h->ep_out_index}; }
+/* the carried diagnostics rows as a restore takes them along (npb_kernels.h): from the snapshot's copy or the bank's.  false = carrying
+ * is on and the source was recorded without the rows */
+static bool diag_restore_of(const NpbHandle *h, bool bank, npb_diag_restore_t *dg) {
+  *dg = npb_diag_restore_t{};
+  if (!h->diag_carry) return true;
+  const double *src = bank ? h->diag_bank : h->diag_snap;
+  if (!src) return false;
+  dg->buf = h->diag; dg->src = src; dg->pitch = h->diag_pitch; dg->src_pitch = bank ? h->diag_bank_pitch : h->pitch;
+  return true;
+}
+static const char *const g_diag_no_snapshot = "the diagnostics rows are carried (npb_carry_diagnostics) and the snapshot was taken without them: npb_snapshot again";
+static const char *const g_diag_no_bank = "the diagnostics rows are carried (npb_carry_diagnostics) and the start bank was set without them: npb_set_start_bank again, "
+                                          "from a handle that carries them";
+static const struct { int row; double fresh; } g_diag_carried[] = {
+#define NPB__X(row, fresh) {row, fresh},
+  NPB_DIAG_CARRIED(NPB__X)
+#undef NPB__X
+};
+static_assert(sizeof(g_diag_carried) / sizeof(g_diag_carried[0]) == NPB_DIAG_NUM_CARRIED, "carried diagnostics rows");
+/* what NuclearPlantSimulator.reset() leaves in the carried rows, in table order (tools/make_diag_reset_golden.py read them off the live
+ * reference: tests/golden/diag_carry/reference_reset.json); NaN = the row is kept */
+static npb_diag_carried_values_t diag_reference_reset_values();
 
 /* Where an arena lands in physical memory changes the step kernel's time when the bytes a step touches are about the
  * size of the 256 MB Infinity Cache (65 536 fp64 plants: 276 MB): handles created one after another in one process run
@@ -196,6 +225,9 @@ int npb_obs_dim(void) { return NPB_OBS_DIM; }
 int npb_info_dim(void) { return NPB_INFO_DIM; }
 int npb_info_nrho(void) { return NPB_INFO_NRHO; }
 int npb_diag_dim(void) { return NPB_DIAG_DIM; }
+int npb_diag_num_carried(void) { return NPB_DIAG_NUM_CARRIED; }
+int npb_diag_carried_row(int k) { return k >= 0 && k < NPB_DIAG_NUM_CARRIED ? g_diag_carried[k].row : -1; }
+double npb_diag_carried_fresh(int k) { return k >= 0 && k < NPB_DIAG_NUM_CARRIED ? g_diag_carried[k].fresh : __builtin_nan(""); }
 static const char *const g_maint_params[] = {
 #define NPB__X(id, name) name,
   NPB_MAINT_PARAMS(NPB__X)
@@ -331,6 +363,8 @@ int npb_destroy(NpbHandle *h) {
   if (h->cm_side) (void)hipFree(h->cm_side);
   if (h->cm_snap) (void)hipFree(h->cm_snap);
   if (h->cm_bank) (void)hipFree(h->cm_bank);
+  if (h->diag_snap) (void)hipFree(h->diag_snap);
+  if (h->diag_bank) (void)hipFree(h->diag_bank);
   if (h->ep_len) (void)hipFree(h->ep_len);
   if (h->bank) (void)hipFree(h->bank);
   if (h->ep_start) (void)hipFree(h->ep_start);
@@ -366,7 +400,51 @@ int npb_set_diagnostics(NpbHandle *h, double *buf, size_t pitch) {
   if (buf && pitch < h->pitch) return fail(h, NPB_EINVAL, "npb_set_diagnostics: pitch must be at least n_plants rounded up to 64");
   if (buf && h->autoreset)      /* the buffer carries plant state outside the arena, which a restore from the snapshot would not put back */
     return fail(h, NPB_EINVAL, "npb_set_diagnostics: autoreset is on (npb_set_autoreset); the diagnostics buffer carries plant state the snapshot does not hold");
+  if (h->diag_carry) {      /* the buffer is the live copy of plant state the handle takes along */
+    if (!buf && h->autoreset)
+      return fail(h, NPB_EINVAL, "npb_set_diagnostics: autoreset is on (npb_set_autoreset) and restores the carried diagnostics rows (npb_carry_diagnostics) "
+                                 "into this buffer: switch the autoreset off first");
+    if (buf && (buf != h->diag || pitch != h->diag_pitch))
+      return fail(h, NPB_EINVAL, "npb_set_diagnostics: the diagnostics rows are carried (npb_carry_diagnostics) in the buffer set before; "
+                                 "npb_carry_diagnostics(h, 0) first, then move them with npb_get / npb_set_diagnostics_state");
+    if (!buf) h->diag_carry = false;
+  }
   h->diag = buf; h->diag_pitch = buf ? pitch : 0;
+  return NPB_OK;
+}
+
+int npb_carry_diagnostics(NpbHandle *h, int on) {
+  if (!h) return NPB_EINVAL;
+  if (!on) {
+    if (h->diag_carry && h->autoreset)
+      return fail(h, NPB_EINVAL, "npb_carry_diagnostics: autoreset is on (npb_set_autoreset) with diagnostics, which it restores only while their rows "
+                                 "are carried: switch the autoreset off first");
+    h->diag_carry = false;
+    return NPB_OK;
+  }
+  if (!h->diag)
+    return fail(h, NPB_EINVAL, "npb_carry_diagnostics: no diagnostics buffer (npb_set_diagnostics first; full mode only): its carried rows are what is carried");
+  h->diag_carry = true;
+  return NPB_OK;
+}
+int npb_get_diagnostics_state(NpbHandle *h, double *buf, void *stream) {
+  if (!h || !buf) return NPB_EINVAL;
+  if (!h->diag_carry) return fail(h, NPB_EINVAL, "npb_get_diagnostics_state: the diagnostics rows are not carried (npb_carry_diagnostics first)");
+  NPB_USE_DEVICE(h);
+  for (int k = 0; k < NPB_DIAG_NUM_CARRIED; k++)
+    NPB_HIP(h, hipMemcpyAsync(buf + (size_t)k * h->n_plants, h->diag + (size_t)g_diag_carried[k].row * h->diag_pitch, (size_t)h->n_plants * sizeof(double),
+                              hipMemcpyDefault, (hipStream_t)stream));
+  NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
+  return NPB_OK;
+}
+int npb_set_diagnostics_state(NpbHandle *h, const double *buf, void *stream) {
+  if (!h || !buf) return NPB_EINVAL;
+  if (!h->diag_carry) return fail(h, NPB_EINVAL, "npb_set_diagnostics_state: the diagnostics rows are not carried (npb_carry_diagnostics first)");
+  NPB_USE_DEVICE(h);
+  for (int k = 0; k < NPB_DIAG_NUM_CARRIED; k++)
+    NPB_HIP(h, hipMemcpyAsync(h->diag + (size_t)g_diag_carried[k].row * h->diag_pitch, buf + (size_t)k * h->n_plants, (size_t)h->n_plants * sizeof(double),
+                              hipMemcpyDefault, (hipStream_t)stream));
+  NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
   return NPB_OK;
 }
 
@@ -524,6 +602,11 @@ int npb_reset(NpbHandle *h, const uint8_t *mask, void *stream) {
   h->maint_cache_stale = true;
   h->K->init(&h->params, h->n_plants, NPB_N(h), h->f64, mask, (hipStream_t)stream);
   if (h->cm_on) npb_launch_cmaint_init(h->cm_side, h->pitch, mask, h->n_plants, (hipStream_t)stream);      /* beside the mpump section the init kernel has just written */
+  if (h->diag_carry) {      /* the carried diagnostics rows of a freshly constructed plant */
+    npb_diag_carried_values_t fresh;
+    for (int k = 0; k < NPB_DIAG_NUM_CARRIED; k++) fresh.v[k] = g_diag_carried[k].fresh;
+    npb_launch_diag_carried_put(h->diag, h->diag_pitch, mask, h->n_plants, h->pitch, fresh, (hipStream_t)stream);
+  }
   clear_episodes(h, mask, true, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
@@ -534,6 +617,7 @@ int npb_reset_reference(NpbHandle *h, const uint8_t *mask, int start_at_steady_s
   NPB_USE_DEVICE(h);
   h->maint_cache_stale = true;
   h->K->reset(&h->params, h->n_plants, NPB_N(h), h->f64, mask, start_at_steady_state != 0, (hipStream_t)stream);
+  if (h->diag_carry) npb_launch_diag_carried_put(h->diag, h->diag_pitch, mask, h->n_plants, h->pitch, diag_reference_reset_values(), (hipStream_t)stream);
   clear_episodes(h, mask, true, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
@@ -645,6 +729,9 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
   if (h->params.heat_source == NPB_HEAT_EXTERNAL && !noise_z)      /* a NULL column would read as 0 MW thermal, silently */
     return fail(h, NPB_EINVAL, "npb_step: params.heat_source is NPB_HEAT_EXTERNAL, whose thermal power arrives in the noise_z column (include/npb_params.h): it must not be NULL");
   npb_cmaint_restore_t cm = {};      /* what the autoreset's restores take along beside the arena */
+  npb_diag_restore_t dg = {};
+  if (h->autoreset && !diag_restore_of(h, h->bank && h->next_slot, &dg))
+    return fail(h, NPB_EINVAL, h->bank && h->next_slot ? g_diag_no_bank : g_diag_no_snapshot);
   if (h->cm_on) {
     if (!h->params.maint_enabled || h->params.mode != NPB_MODE_FULL)
       return fail(h, NPB_EINVAL, "npb_step: the component maintenance is on (npb_set_component_maintenance) and needs params.maint_enabled and the full mode");
@@ -686,9 +773,9 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
   else if (maint && h->params.mode != NPB_MODE_FULL)   /* a full-mode step kernel has run the rule itself, for the waves whose pump phase found something */
     h->K->maint(NPB_N(h), h->f64, h->maint_side, h->maint_counts, h->n_plants, (hipStream_t)stream);
   if (h->autoreset)   /* from the bank while it has slots, else from the snapshot; same stream, nothing read back, the maintenance cache kept per plant by the kernel itself */
-    h->K->episode(h->params.mode, h->n_plants, NPB_N(h), h->f64, source_of(h, h->bank && h->next_slot), done, reward, obs, h->ep_len, h->ep_ret,
+    h->K->episode(h->params.mode, h->n_plants, NPB_N(h), h->f64, source_of(h, h->bank && h->next_slot), done, reward, obs, counters_of(h),
                   h->ep_out_len, h->ep_out_ret, h->ep_out_truncated, h->ep_final_obs, h->max_episode_steps,
-                  maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, cm, (hipStream_t)stream);
+                  maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, cm, dg, (hipStream_t)stream);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, NPB_EHIP, "npb_step: kernel launch failed", e);
   return NPB_OK;
@@ -714,6 +801,17 @@ int npb_snapshot(NpbHandle *h, void *stream) {
     NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
     (void)hipFree(h->cm_snap); h->cm_snap = nullptr;
   }
+  if (h->diag_carry) {      /* the carried diagnostics rows belong to the episode start too */
+    if (!h->diag_snap) {
+      hipError_t e = hipMalloc((void **)&h->diag_snap, (size_t)NPB_DIAG_NUM_CARRIED * h->pitch * sizeof(double));
+      if (e != hipSuccess) { h->diag_snap = nullptr; return fail(h, NPB_EHIP, "npb_snapshot: hipMalloc of the carried diagnostics rows' snapshot failed", e); }
+    }
+    npb_launch_diag_carried_pack(h->diag, h->diag_pitch, h->diag_snap, h->pitch, h->pitch, (hipStream_t)stream);
+    NPB_HIP(h, hipGetLastError());
+  } else if (h->diag_snap) {      /* a snapshot without them: the older copy does not belong to it */
+    NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
+    (void)hipFree(h->diag_snap); h->diag_snap = nullptr;
+  }
   return NPB_OK;
 }
 
@@ -722,10 +820,12 @@ int npb_restore(NpbHandle *h, const uint8_t *mask, void *stream) {
   if (!h->snap) return fail(h, NPB_EINVAL, "npb_restore: no snapshot (npb_snapshot) to restore from");
   npb_cmaint_restore_t cm;
   if (!cm_restore_of(h, false, &cm)) return fail(h, NPB_EINVAL, g_cm_no_snapshot);
+  npb_diag_restore_t dg;
+  if (!diag_restore_of(h, false, &dg)) return fail(h, NPB_EINVAL, g_diag_no_snapshot);
   NPB_USE_DEVICE(h);
   const bool maint = h->params.maint_enabled != 0;
-  h->K->restore(h->n_plants, NPB_N(h), h->f64, source_of(h, false), mask, h->ep_len, h->ep_ret,
-                maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, cm, (hipStream_t)stream);
+  h->K->restore(h->n_plants, NPB_N(h), h->f64, source_of(h, false), mask, counters_of(h),
+                maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, cm, dg, (hipStream_t)stream);
   clear_episodes(h, mask, false, (hipStream_t)stream);     /* the restored episodes are not from the bank */
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
@@ -737,16 +837,26 @@ int npb_set_autoreset(NpbHandle *h, int enabled, int max_episode_steps) {
   if (max_episode_steps < 0) return fail(h, NPB_EINVAL, "npb_set_autoreset: max_episode_steps must be >= 0 (0 = no limit)");
   if (!h->snap && !(h->bank && h->next_slot))
     return fail(h, NPB_EINVAL, "npb_set_autoreset: no snapshot (npb_snapshot), nor a start bank with slots (npb_set_start_bank, npb_set_start_slots), to reset to");
-  if (h->diag) return fail(h, NPB_EINVAL, "npb_set_autoreset: diagnostics are on (npb_set_diagnostics); their buffer carries plant state the snapshot does not hold");
+  if (h->diag && !h->diag_carry)
+    return fail(h, NPB_EINVAL, "npb_set_autoreset: diagnostics are on (npb_set_diagnostics); their buffer carries plant state the snapshot does not hold");
+  if (h->diag_carry) {      /* the source the autoreset will restore from must hold the rows */
+    const bool bank = h->bank && h->next_slot;
+    if (!(bank ? h->diag_bank : h->diag_snap))
+      return fail(h, NPB_EINVAL, bank ? "npb_set_autoreset: diagnostics are on and their rows carried (npb_carry_diagnostics), but the start bank was set without "
+                                        "them: npb_set_start_bank again, from a handle that carries them"
+                                      : "npb_set_autoreset: diagnostics are on and their rows carried (npb_carry_diagnostics), but the snapshot was taken "
+                                        "without them: npb_snapshot again");
+  }
   NPB_USE_DEVICE(h);
-  if (!h->ep_len) {     /* one allocation: [pitch] int32 lengths, then [pitch] double returns */
+  if (!h->ep_len) {     /* one allocation: [pitch] int32 lengths, then [pitch] double returns, then [pitch] int32 episode indices */
     const size_t len_bytes = (h->pitch * sizeof(int32_t) + 255) / 256 * 256;
-    hipError_t e = hipMalloc((void **)&h->ep_len, len_bytes + h->pitch * sizeof(double));
+    hipError_t e = hipMalloc((void **)&h->ep_len, len_bytes + h->pitch * sizeof(double) + h->pitch * sizeof(int32_t));
     if (e != hipSuccess) { h->ep_len = nullptr; return fail(h, NPB_EHIP, "npb_set_autoreset: hipMalloc of the episode counters failed", e); }
     h->ep_ret = (double *)((char *)h->ep_len + len_bytes);
+    h->ep_index = (int32_t *)(h->ep_ret + h->pitch);
   }
   const size_t len_bytes = (size_t)((char *)h->ep_ret - (char *)h->ep_len);
-  NPB_HIP(h, hipMemset(h->ep_len, 0, len_bytes + h->pitch * sizeof(double)));
+  NPB_HIP(h, hipMemset(h->ep_len, 0, len_bytes + h->pitch * sizeof(double) + h->pitch * sizeof(int32_t)));
   h->autoreset = true;
   h->max_episode_steps = max_episode_steps;
   return NPB_OK;
@@ -755,6 +865,12 @@ int npb_set_autoreset(NpbHandle *h, int enabled, int max_episode_steps) {
 int npb_set_episode_buffers(NpbHandle *h, int32_t *length, double *ret, uint8_t *truncated, double *final_obs) {
   if (!h) return NPB_EINVAL;
   h->ep_out_len = length; h->ep_out_ret = ret; h->ep_out_truncated = truncated; h->ep_final_obs = final_obs;
+  return NPB_OK;
+}
+
+int npb_set_episode_index_buffer(NpbHandle *h, int32_t *index) {
+  if (!h) return NPB_EINVAL;
+  h->ep_out_index = index;
   return NPB_OK;
 }
 
@@ -769,8 +885,12 @@ int npb_set_start_bank(NpbHandle *h, const NpbHandle *src, void *stream) {
     h->bank = nullptr; h->bank_bytes = 0; h->bank_N = 0; h->bank_M = 0; h->ep_start = nullptr;
     if (h->cm_bank) (void)hipFree(h->cm_bank);
     h->cm_bank = nullptr; h->cm_bank_pitch = 0; h->cm_bank_doubles = 0;
+    if (h->diag_bank) (void)hipFree(h->diag_bank);
+    h->diag_bank = nullptr; h->diag_bank_pitch = 0; h->diag_bank_doubles = 0;
     return NPB_OK;
   }
+  if (h->diag_carry && !src->diag_carry)      /* its entries would come without the accumulators, latches and ejector values of the diagnostics */
+    return fail(h, NPB_EINVAL, "npb_set_start_bank: this handle carries the diagnostics rows (npb_carry_diagnostics) and the bank handle does not");
   if (h->cm_on && !src->cm_on)      /* its entries would come without stamps and open orders of the generators and the condenser */
     return fail(h, NPB_EINVAL, "npb_set_start_bank: this handle has the component maintenance on (npb_set_component_maintenance) and the bank handle has not");
   if (src->storage != h->storage)
@@ -807,6 +927,22 @@ int npb_set_start_bank(NpbHandle *h, const NpbHandle *src, void *stream) {
     NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
     (void)hipFree(h->cm_bank); h->cm_bank = nullptr; h->cm_bank_pitch = 0; h->cm_bank_doubles = 0;
   }
+  if (src->diag_carry) {      /* the bank handle's live carried rows beside its arena, in its pitch */
+    const size_t doubles = (size_t)NPB_DIAG_NUM_CARRIED * src->pitch;
+    if (doubles > h->diag_bank_doubles) {
+      if (h->diag_bank) (void)hipFree(h->diag_bank);
+      h->diag_bank = nullptr; h->diag_bank_doubles = 0;
+      hipError_t e = hipMalloc((void **)&h->diag_bank, doubles * sizeof(double));
+      if (e != hipSuccess) { h->diag_bank = nullptr; return fail(h, NPB_EHIP, "npb_set_start_bank: hipMalloc of the bank's carried diagnostics rows failed", e); }
+      h->diag_bank_doubles = doubles;
+    }
+    npb_launch_diag_carried_pack(src->diag, src->diag_pitch, h->diag_bank, src->pitch, src->pitch, (hipStream_t)stream);
+    NPB_HIP(h, hipGetLastError());
+    h->diag_bank_pitch = src->pitch;
+  } else if (h->diag_bank) {
+    NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
+    (void)hipFree(h->diag_bank); h->diag_bank = nullptr; h->diag_bank_pitch = 0; h->diag_bank_doubles = 0;
+  }
   return NPB_OK;
 }
 
@@ -823,10 +959,12 @@ int npb_restore_bank(NpbHandle *h, const uint8_t *mask, void *stream) {
   if (!h->bank || !h->next_slot) return fail(h, NPB_EINVAL, "npb_restore_bank: no start bank (npb_set_start_bank) with slots (npb_set_start_slots) to restore from");
   npb_cmaint_restore_t cm;
   if (!cm_restore_of(h, true, &cm)) return fail(h, NPB_EINVAL, g_cm_no_bank);
+  npb_diag_restore_t dg;
+  if (!diag_restore_of(h, true, &dg)) return fail(h, NPB_EINVAL, g_diag_no_bank);
   NPB_USE_DEVICE(h);
   const bool maint = h->params.maint_enabled != 0;
-  h->K->restore(h->n_plants, NPB_N(h), h->f64, source_of(h, true), mask, h->ep_len, h->ep_ret,
-                maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, cm, (hipStream_t)stream);
+  h->K->restore(h->n_plants, NPB_N(h), h->f64, source_of(h, true), mask, counters_of(h),
+                maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, cm, dg, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -940,3 +1078,17 @@ int npb_observe(NpbHandle *h, double *obs, void *stream) {
 }
 
 } /* extern "C" */
+
+static npb_diag_carried_values_t diag_reference_reset_values() {
+  npb_diag_carried_values_t r;
+  for (int k = 0; k < NPB_DIAG_NUM_CARRIED; k++) {
+    const int row = g_diag_carried[k].row;
+    if (row == NPB_DIAG_COND_SJE_COMPRESSION_RATIO || row == NPB_DIAG_COND_SJE_COMPRESSION_RATIO + 1)      /* vacuum_pump.py:551-561: compression_ratio_actual is not among what reset() writes */
+      r.v[k] = __builtin_nan("");
+    else if (row == NPB_DIAG_STAGE_SYSTEM_EFFICIENCY)
+      r.v[k] = 1.0;      /* stage_system.py:1040 (the row reads a 0 as this) */
+    else
+      r.v[k] = 0.0;      /* rotor_dynamics.py:576-580, :1106-1108; protection_system.py:798-802; vacuum_pump.py:555 */
+  }
+  return r;
+}

@@ -27,6 +27,13 @@ typedef struct {
 /* the side state of the component maintenance (npb_set_component_maintenance) a restore takes along: lane s of src -> lane p of state,
  * member by member ([NPB_CMAINT_SIDE_DOUBLES][pitch] doubles each); state NULL = the feature is off */
 typedef struct { double *state; const double *src; size_t pitch, src_pitch; } npb_cmaint_restore_t;
+/* the carried diagnostics rows (include/npb.h NPB_DIAG_CARRIED, npb_carry_diagnostics) a restore takes along: entry s of src
+ * ([NPB_DIAG_NUM_CARRIED][src_pitch], table order) -> plant p of the caller's diagnostics buffer ([NPB_DIAG_DIM][pitch], indexed by the
+ * global plant number: that buffer is not segmented); buf NULL = not carried */
+typedef struct { double *buf; const double *src; size_t pitch, src_pitch; } npb_diag_restore_t;
+/* the episode counters a restore zeroes and the episode index it bumps with them (npb_set_autoreset), each [pitch] or NULL; out_index =
+ * the caller's column the episode kernel fills (npb_set_episode_index_buffer) */
+typedef struct { int32_t *len; double *ret; int32_t *index; int32_t *out_index; } npb_episode_counters_t;
 typedef struct {
   int (*step)(const npb_params_t *P, int n_plants, size_t npad, void *arena, const int32_t *action,
               const double *magnitude, const double *setpoint, const double *noise_z, const double *cw_temp,
@@ -41,11 +48,12 @@ typedef struct {
   void (*field_set)(void *arena, size_t npad, int col, int sub, int kind, const void *in, int n, hipStream_t stream);
   void (*gather)(const void *arena, size_t npad, const int *plan_dev, int n_fields, double *out, int n, hipStream_t stream);
   /* episodes: src = the snapshot or a bank with slots (npb_source_t); maint_side / maint_counts NULL unless params.maint_enabled */
-  void (*restore)(int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *mask, int32_t *len, double *ret,
-                  void *maint_side, int32_t *maint_counts, npb_cmaint_restore_t cm, hipStream_t stream);
+  void (*restore)(int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *mask, npb_episode_counters_t C,
+                  void *maint_side, int32_t *maint_counts, npb_cmaint_restore_t cm, npb_diag_restore_t dg, hipStream_t stream);
   void (*episode)(int mode, int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *done, const double *reward,
-                  double *obs, int32_t *len, double *ret, int32_t *out_len, double *out_ret, uint8_t *out_truncated,
-                  double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, npb_cmaint_restore_t cm, hipStream_t stream);
+                  double *obs, npb_episode_counters_t C, int32_t *out_len, double *out_ret, uint8_t *out_truncated,
+                  double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, npb_cmaint_restore_t cm, npb_diag_restore_t dg,
+                  hipStream_t stream);
   /* npb_perform_maintenance: the caller's [n_plants] order columns (bearing / target_level / success may be NULL) and the maintenance
    * event log's descriptor (log_records NULL = off) */
   void (*operator_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *pump, const int32_t *bearing,
@@ -76,7 +84,14 @@ size_t npb_launch_cmaint_side_bytes(size_t pitch);
 size_t npb_launch_cmaint_state_offset(void);
 void npb_launch_cmaint_init(void *cm_side, size_t pitch, const uint8_t *mask, int n_plants, hipStream_t stream);
 void npb_launch_touch(size_t npad, double *arena, hipStream_t stream);
-void npb_launch_episode_clear(const uint8_t *mask, int32_t *len, double *ret, int32_t *start, int n_plants, size_t npad, hipStream_t stream);
+void npb_launch_episode_clear(const uint8_t *mask, int32_t *len, double *ret, int32_t *index, int32_t *start, int n_plants, size_t npad, hipStream_t stream);
+/* the carried diagnostics rows of a diagnostics buffer (`live`, [NPB_DIAG_DIM][live_pitch]) into `packed`, [NPB_DIAG_NUM_CARRIED][packed_pitch] in
+ * table order, for the plants below `lanes` */
+void npb_launch_diag_carried_pack(const double *live, size_t live_pitch, double *packed, size_t packed_pitch, size_t lanes, hipStream_t stream);
+/* the plants of mask (NULL = every lane below `lanes`) to values[k] per carried row, a NaN = the row is kept */
+typedef struct { double v[NPB_DIAG_NUM_CARRIED]; } npb_diag_carried_values_t;
+void npb_launch_diag_carried_put(double *live, size_t live_pitch, const uint8_t *mask, int n_plants, size_t lanes, npb_diag_carried_values_t values,
+                                 hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -759,7 +759,8 @@ typedef uint64_t npd_word_t;
 /* where the restore writes besides the arena: the maintenance screen's cooldown cache (zeroed = "look", npd_maintenance.h) and the
  * caller's event-count column (npb_set_maintenance_count_buffer), both NULL unless params.maint_enabled */
 struct npd_restore_side_t { npd_u32x4 *maint_entry; int32_t *maint_counts; int n_plants;
-                             npb_cmaint_restore_t cm;      /* the side state of the component maintenance (npd_component_auto.h): state NULL = off */ };
+                             npb_cmaint_restore_t cm;      /* the side state of the component maintenance (npd_component_auto.h): state NULL = off */
+                             npb_diag_restore_t dg;        /* the carried diagnostics rows (npb_carry_diagnostics): buf NULL = not carried */ };
 /* the bank entry a restored plant takes from its slot, and the slot and start columns it leaves behind (include/npb.h) */
 __device__ __forceinline__ int32_t npd_bank_take(const npb_source_t &B, size_t p) {
   int32_t s = B.next_slot[p] % B.M;
@@ -807,6 +808,16 @@ __device__ __forceinline__ void npd_restore_lanes(npd_real_t *__restrict__ f64, 
 #pragma unroll 1
     for (int k = 0; k < NPB_CMAINT_SIDE_DOUBLES; k++) R.cm.state[(size_t)k * R.cm.pitch + p] = R.cm.src[(size_t)k * R.cm.src_pitch + s];
   }
+  if (R.dg.buf) {                     /* the rows the diagnostics build carries in the caller's buffer (include/npb.h NPB_DIAG_CARRIED): p is the
+                                       * global plant number, which is how that unsegmented buffer is indexed; the loads first */
+    double v[NPB_DIAG_NUM_CARRIED];
+#pragma unroll
+    for (int k = 0; k < NPB_DIAG_NUM_CARRIED; k++) v[k] = R.dg.src[(size_t)k * R.dg.src_pitch + s];
+    int k = 0;
+#define NPB__X(row, fresh) R.dg.buf[(size_t)(row) * R.dg.pitch + p] = v[k++];
+    NPB_DIAG_CARRIED(NPB__X)
+#undef NPB__X
+  }
 }
 /* [64][W] rows held one per lane -> row-major global memory, only the rows whose bit is set in `rows` (npd_store_rows otherwise) */
 template <int W>
@@ -825,6 +836,7 @@ __device__ __forceinline__ void npd_store_rows_masked(const double *row, double 
 /* the episode bookkeeping of one step, after the step kernel (and the maintenance kernel) on the same stream */
 struct npd_episode_t {
   int32_t *len; double *ret;                                  /* carried: steps and summed reward of the running episode */
+  int32_t *index; int32_t *out_index;                         /* carried: the running episode's number; the caller's column of it, or NULL */
   int32_t *out_len; double *out_ret; uint8_t *out_truncated; double *final_obs;   /* the caller's columns, each may be NULL */
   int max_steps;                                              /* 0 = no limit */
 };
@@ -847,6 +859,8 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_episode_kernel(int mode, int n_p
     if (E.out_ret) E.out_ret[p] = ret;
     if (E.out_truncated) E.out_truncated[p] = (uint8_t)truncated;
     if (src.out_start) src.out_start[p] = src.start[p];      /* the episode this step's transition belonged to */
+    if (E.out_index) E.out_index[p] = E.index[p];
+    if (reset) E.index[p] += 1;
     E.len[p] = reset ? 0 : len;
     E.ret[p] = reset ? 0.0 : ret;
   }
@@ -871,12 +885,12 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_episode_kernel(int mode, int n_p
  * any) to zero */
 __global__ __launch_bounds__(NPB_WAVE) void npb_restore_kernel(int lanes, size_t N, npd_real_t *__restrict__ f64, npb_source_t src,
                                                                const uint8_t *__restrict__ mask, int32_t *__restrict__ len, double *__restrict__ ret,
-                                                               npd_restore_side_t R) {
+                                                               int32_t *__restrict__ index, npd_restore_side_t R) {
   const size_t block_base = (size_t)blockIdx.x * NPB_WAVE;
   NPD_SEGMENT(f64, N, block_base);
   const size_t p = block_base + threadIdx.x;
   const bool reset = p < (size_t)lanes && (!mask || mask[p] != 0);
-  if (reset && len) { len[p] = 0; ret[p] = 0.0; }
+  if (reset && len) { len[p] = 0; ret[p] = 0.0; index[p] += 1; }
   if (!__any(reset)) return;
   const size_t s = reset && src.next_slot ? (size_t)npd_bank_take(src, p) : p;
   npd_restore_lanes(f64, N, p, reset, src, s, R);
@@ -1545,27 +1559,28 @@ static void NPB_LAUNCHER(init)(const npb_params_t *P, int n_plants, size_t npad,
   hipLaunchKernelGGL(npb_init_kernel, grid, block, 0, stream, *P, npad, (npd_real_t *)arena, mask, n_plants);
 }
 /* episodes (npb_snapshot / npb_restore / npb_set_autoreset): maint_side / maint_counts NULL unless params.maint_enabled */
-static npd_restore_side_t npd_restore_side_of(void *maint_side, int32_t *maint_counts, int n_plants, npb_cmaint_restore_t cm) {
+static npd_restore_side_t npd_restore_side_of(void *maint_side, int32_t *maint_counts, int n_plants, npb_cmaint_restore_t cm, npb_diag_restore_t dg) {
   npd_restore_side_t R;
   R.maint_entry = npd_maint_cache_of(maint_side, maint_counts, n_plants).entry; R.maint_counts = maint_counts; R.n_plants = n_plants;
-  R.cm = cm;
+  R.cm = cm; R.dg = dg;
   return R;
 }
 /* src: the snapshot (npb_restore, the snapshot autoreset) or a bank with its slots (npb_restore_bank, the bank autoreset).  mask NULL
  * restores every lane of the pitch from the snapshot, the plants only from a bank (its slot columns have n entries) */
-static void NPB_LAUNCHER(restore)(int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *mask, int32_t *len, double *ret,
-                                  void *maint_side, int32_t *maint_counts, npb_cmaint_restore_t cm, hipStream_t stream) {
+static void NPB_LAUNCHER(restore)(int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *mask, npb_episode_counters_t C,
+                                  void *maint_side, int32_t *maint_counts, npb_cmaint_restore_t cm, npb_diag_restore_t dg, hipStream_t stream) {
   const int lanes = mask || src.next_slot ? n_plants : (int)NPD_NPAD(npad);
   hipLaunchKernelGGL(npb_restore_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, lanes, npad, (npd_real_t *)arena,
-                     src, mask, len, ret, npd_restore_side_of(maint_side, maint_counts, n_plants, cm));
+                     src, mask, C.len, C.ret, C.index, npd_restore_side_of(maint_side, maint_counts, n_plants, cm, dg));
 }
 static void NPB_LAUNCHER(episode)(int mode, int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *done, const double *reward,
-                                  double *obs, int32_t *len, double *ret, int32_t *out_len, double *out_ret, uint8_t *out_truncated,
-                                  double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, npb_cmaint_restore_t cm, hipStream_t stream) {
+                                  double *obs, npb_episode_counters_t C, int32_t *out_len, double *out_ret, uint8_t *out_truncated,
+                                  double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, npb_cmaint_restore_t cm, npb_diag_restore_t dg,
+                                  hipStream_t stream) {
   npd_episode_t E;
-  E.len = len; E.ret = ret; E.out_len = out_len; E.out_ret = out_ret; E.out_truncated = out_truncated; E.final_obs = final_obs; E.max_steps = max_steps;
+  E.len = C.len; E.ret = C.ret; E.index = C.index; E.out_index = C.out_index; E.out_len = out_len; E.out_ret = out_ret; E.out_truncated = out_truncated; E.final_obs = final_obs; E.max_steps = max_steps;
   hipLaunchKernelGGL(npb_episode_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, mode, n_plants, npad, (npd_real_t *)arena,
-                     src, done, reward, obs, E, npd_restore_side_of(maint_side, maint_counts, n_plants, cm));
+                     src, done, reward, obs, E, npd_restore_side_of(maint_side, maint_counts, n_plants, cm, dg));
 }
 /* npb_perform_maintenance: the caller's order columns; log_* = the maintenance event log (npb_set_maintenance_log), records NULL = off */
 static void NPB_LAUNCHER(operator_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *pump, const int32_t *bearing,
@@ -1605,11 +1620,11 @@ extern "C" npb_launchers_t NPB_LAUNCHER(table) = {
 #ifndef NPB_BUILD_F32
 /* npb_reset / npb_reset_reference / npb_restore: the episode counters (len, ret) and the carried start entries (start: -1, not from
  * the bank) of the plants of mask (NULL = every lane of the pitch); each column may be NULL */
-__global__ void npb_episode_clear_kernel(const uint8_t *__restrict__ mask, int32_t *__restrict__ len, double *__restrict__ ret, int32_t *__restrict__ start,
-                                         int n_plants, int npad) {
+__global__ void npb_episode_clear_kernel(const uint8_t *__restrict__ mask, int32_t *__restrict__ len, double *__restrict__ ret, int32_t *__restrict__ index,
+                                         int32_t *__restrict__ start, int n_plants, int npad) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= npad || (mask && (p >= n_plants || !mask[p]))) return;
-  if (len) len[p] = 0;
+  if (len) { len[p] = 0; index[p] += 1; }      /* (the index is allocated with the length) */
   if (ret) ret[p] = 0.0;
   if (start) start[p] = -1;
 }
@@ -1628,8 +1643,38 @@ extern "C" void npb_launch_cmaint_init(void *cm_side, size_t pitch, const uint8_
   hipLaunchKernelGGL(npb_cmaint_init_kernel, dim3((unsigned)((pitch + 255) / 256)), dim3(256), 0, stream,
                      (double *)((char *)cm_side + NPD_CMAINT_CONSTS_BYTES), pitch, mask, n_plants);
 }
-extern "C" void npb_launch_episode_clear(const uint8_t *mask, int32_t *len, double *ret, int32_t *start, int n_plants, size_t npad, hipStream_t stream) {
+extern "C" void npb_launch_episode_clear(const uint8_t *mask, int32_t *len, double *ret, int32_t *index, int32_t *start, int n_plants, size_t npad,
+                                         hipStream_t stream) {
   const int n = (int)NPD_NPAD(npad);
-  hipLaunchKernelGGL(npb_episode_clear_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, mask, len, ret, start, n_plants, n);
+  hipLaunchKernelGGL(npb_episode_clear_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, mask, len, ret, index, start, n_plants, n);
+}
+/* the carried diagnostics rows (include/npb.h NPB_DIAG_CARRIED) of a diagnostics buffer into a packed [NPB_DIAG_NUM_CARRIED][pitch] copy in
+ * table order: npb_snapshot, npb_set_start_bank */
+__global__ void npb_diag_carried_pack_kernel(const double *__restrict__ live, size_t live_pitch, double *__restrict__ packed, size_t packed_pitch,
+                                             size_t lanes) {
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= lanes) return;
+  int k = 0;
+#define NPB__X(row, fresh) packed[(size_t)(k++) * packed_pitch + p] = live[(size_t)(row) * live_pitch + p];
+  NPB_DIAG_CARRIED(NPB__X)
+#undef NPB__X
+}
+/* npb_reset / npb_reset_reference: the carried rows of the plants of mask (NULL = every lane below `lanes`) to values.v[k]; NaN = kept */
+__global__ void npb_diag_carried_put_kernel(double *__restrict__ live, size_t live_pitch, const uint8_t *__restrict__ mask, int n_plants, size_t lanes,
+                                            npb_diag_carried_values_t values) {
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= lanes || (mask && (p >= (size_t)n_plants || !mask[p]))) return;
+  int k = 0;
+#define NPB__X(row, fresh) { const double v = values.v[k++]; if (v == v) live[(size_t)(row) * live_pitch + p] = v; }
+  NPB_DIAG_CARRIED(NPB__X)
+#undef NPB__X
+}
+extern "C" void npb_launch_diag_carried_pack(const double *live, size_t live_pitch, double *packed, size_t packed_pitch, size_t lanes, hipStream_t stream) {
+  hipLaunchKernelGGL(npb_diag_carried_pack_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, live, live_pitch, packed, packed_pitch, lanes);
+}
+extern "C" void npb_launch_diag_carried_put(double *live, size_t live_pitch, const uint8_t *mask, int n_plants, size_t lanes,
+                                            npb_diag_carried_values_t values, hipStream_t stream) {
+  hipLaunchKernelGGL(npb_diag_carried_put_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, live, live_pitch, mask, n_plants, lanes,
+                     values);
 }
 #endif

@@ -200,8 +200,17 @@ class BatchedPlantEnv:
     describe the terminal transition; ``info`` gains ``truncated``, ``final_observation`` (this step's obs of the reset plants;
     other rows are stale), ``episode_length`` and ``episode_return`` (as of this step: a reset plant's finished episode).  Only the
     plant state in the arena is restored: the pre-drawn heat-source noise stream (``HeatSourceNoise``) continues across an
-    autoreset (its filter state, in the arena, is restored), and a StateLog's history-window columns do not restart.  Autoreset
-    and ``enable_diagnostics`` exclude each other (the diagnostics buffer carries plant state the snapshot does not hold).
+    autoreset (its filter state, in the arena, is restored).  With autoreset ``info["episode_index"]`` numbers each plant's episodes
+    (the episode this step's transition belonged to; every restart, ``restore`` and ``reset`` included, starts the next).
+
+    Diagnostics with episodes: the diagnostics build of the step (``enable_diagnostics``; the state log's step-internal columns) keeps
+    thirteen values per plant from one step to the next in the diagnostics buffer, not in the arena (``_lib.DIAG_CARRIED_ROWS``:
+    bearing clearance, overspeed events, the stage system's efficiency, the feedwater protection's trip count and latches, the
+    ejectors' compression ratio and hours).  ``diagnostics=True`` switches the diagnostics on with these rows CARRIED
+    (npb_carry_diagnostics) before the first snapshot: ``snapshot`` / ``restore``, the start bank, the autoreset and the resets then
+    take them along on the device, and ``diagnostics_state()`` / ``load_diagnostics_state()`` checkpoint them.  A plain
+    ``enable_diagnostics()`` does not carry them: it and autoreset exclude each other (the diagnostics buffer carries plant state the
+    snapshot does not hold), and ``restore`` puts the rows back to a freshly constructed plant's, whatever the snapshot was taken from.
 
     Start bank: ``set_start_bank(bank_env)`` copies another batch's states (M plants, any M) into a bank the handle owns; from then
     on the autoreset, and ``restore_from_bank(mask)``, restore a plant from bank entry ``next_start_slots[p] mod M`` instead of its
@@ -239,11 +248,14 @@ class BatchedPlantEnv:
                  mode: str = "full", device: int = 0, params: Optional[dict] = None, maintenance: bool = False,
                  storage: str = "f64", maintenance_thresholds: Optional[dict] = None, reactivity_components: bool = False,
                  integrator: str = "reference", autoreset: bool = False, max_episode_steps: Optional[int] = None,
-                 noise_generator: str = "host", component_maintenance: bool = False, component_thresholds: Optional[dict] = None):
+                 noise_generator: str = "host", component_maintenance: bool = False, component_thresholds: Optional[dict] = None,
+                 diagnostics: bool = False):
         if max_episode_steps is not None and not autoreset:
             raise ValueError("max_episode_steps needs autoreset=True")
         if component_thresholds is not None and not component_maintenance:
             raise ValueError("component_thresholds needs component_maintenance=True")
+        if diagnostics and mode != "full":
+            raise ValueError("diagnostics needs mode='full': the diagnostics build is the full plant's step kernel")
         if component_maintenance and not (maintenance and mode == "full"):
             raise ValueError("component_maintenance needs maintenance=True and mode='full': the generators and the condenser share the pumps' work-order queue")
         component_table = None
@@ -326,6 +338,9 @@ class BatchedPlantEnv:
         self._keep = []
         self._episode = None
         self._bank = None
+        self._diag_buf = None; self.diagnostics = None; self._diag_carried = False
+        if diagnostics:      # before the first snapshot (autoreset=True takes it below), so that it records the carried rows
+            self.enable_diagnostics(True, carried=True)
         if autoreset:
             self.snapshot()
             self._enable_autoreset(max_episode_steps)
@@ -335,7 +350,7 @@ class BatchedPlantEnv:
                     params: Optional[dict] = None, autoreset: bool = False, max_episode_steps: Optional[int] = None,
                     bank_seeds: Optional[Sequence[int]] = None, noise_generator: str = "host",
                     maintenance_log: Optional[int] = None, component_maintenance: bool = False,
-                    component_thresholds: Optional[dict] = None) -> "BatchedPlantEnv":
+                    component_thresholds: Optional[dict] = None, diagnostics: bool = False) -> "BatchedPlantEnv":
         """One plant per seed, as data_gen's MaintenanceScenarioRunner builds them for
         ``compose_action_test_scenario(action, randomize=True, randomization_seed=seed)``
         (maintenance_scenario_runner.py:210-244): dt in minutes, ConstantHeatSource with 0.1 % noise seeded 42,
@@ -345,13 +360,15 @@ class BatchedPlantEnv:
         (``set_start_bank`` with its default slots): each restart draws a fresh scenario, as the data-gen runner's episodes do.
         ``noise_generator`` as for the constructor; ``maintenance_log`` = a capacity: ``enable_maintenance_log(capacity)``.
         ``component_maintenance`` / ``component_thresholds`` as for the constructor: the runner's plant has the automatic maintenance of
-        the steam generators and the condenser on as well (the composer's rows by default); off by default, as before."""
+        the steam generators and the condenser on as well (the composer's rows by default); off by default, as before.
+        ``diagnostics`` as for the constructor (the diagnostics build with its carried rows taken along: what ``StateLog(env,
+        diagnostics=True)`` needs on an env with episodes); the bank of ``bank_seeds`` is built with the same flag."""
         if max_episode_steps is not None and not autoreset:
             raise ValueError("max_episode_steps needs autoreset=True")
         from . import scenarios
         env = cls(len(seeds), dt=dt, heat_source="constant", noise_enabled=True, noise_std_percent=0.1,
                   noise_seeds=[42] * len(seeds), device=device, maintenance=True, params=params, noise_generator=noise_generator,
-                  component_maintenance=component_maintenance, component_thresholds=component_thresholds)
+                  component_maintenance=component_maintenance, component_thresholds=component_thresholds, diagnostics=diagnostics)
         eff = float(env.get_field("pump.lubrication_effectiveness")[0].item())
         env.set_fields(scenarios.action_test_fields(action, seeds, eff, randomize=randomize))
         # what a state log of these plants needs beside their state: the composer's provider names and the values the constructor
@@ -363,7 +380,7 @@ class BatchedPlantEnv:
             env._enable_autoreset(max_episode_steps)
         if bank_seeds is not None:
             bank = cls.action_test(action, bank_seeds, dt=dt, device=device, randomize=randomize, params=params,
-                                   component_maintenance=component_maintenance, component_thresholds=component_thresholds)
+                                   component_maintenance=component_maintenance, component_thresholds=component_thresholds, diagnostics=diagnostics)
             env.set_start_bank(bank)
             torch.cuda.current_stream(env.device).synchronize()     # the copy has read the bank batch's arena
             bank.close()
@@ -389,28 +406,61 @@ class BatchedPlantEnv:
         """the kernel the last step() actually launched, by the name rocprofv3 lists it under ("" before the first step)"""
         return self.L.npb_step_kernel_name(self.L.npb_debug_last_step_kernel(self._h)).decode()
 
-    def enable_diagnostics(self, on: bool = True):
+    def enable_diagnostics(self, on: bool = True, carried: bool = False):
         """Have every following step also write the step-internal diagnostics (include/npb.h NPB_DIAG_*: per turbine stage inlet /
         outlet pressure and temperature, power output, loading factor) into ``self.diagnostics`` ([DIAG_DIM, n] on the device,
         rows in _lib.DIAG_STAGE_VALUES order x 14 stages).  The step then runs the diagnostics build of the one-wave kernel at
-        every batch size: meant for state logging, not for throughput."""
-        if on:
+        every batch size: meant for state logging, not for throughput.
+
+        ``carried=True`` (what the constructor's ``diagnostics=True`` does) also has the handle treat the rows the step carries in
+        that buffer (_lib.DIAG_CARRIED_ROWS) as plant state (npb_carry_diagnostics): the next ``snapshot()`` records them, a start bank
+        set from a carrying env holds them, ``restore`` / ``restore_from_bank`` / the autoreset put them back per plant and the
+        resets reset them, all on the device -- Python no longer touches them -- and ``diagnostics_state()`` checkpoints them.  On an
+        env whose diagnostics are already on it keeps the buffer and its values.  With ``carried=False`` the rows are not part of any
+        snapshot: ``reset`` / ``restore`` / ``restore_from_bank`` put a freshly constructed plant's values, and autoreset is refused."""
+        if on and carried and self._diag_buf is not None:      # the buffer stays: its rows are the plant's
+            _lib.check(self.L.npb_carry_diagnostics(self._h, 1), self._h)
+            self._diag_carried = True
+        elif on:
             pitch = (self.n + 63) // 64 * 64
-            self._diag_buf = torch.zeros((_lib.DIAG_DIM, pitch), dtype=torch.float64, device=self.device)
-            self._reset_carried_diagnostics(None)
-            _lib.check(self.L.npb_set_diagnostics(self._h, ctypes.c_void_p(self._diag_buf.data_ptr()), pitch), self._h)
+            buf = torch.zeros((_lib.DIAG_DIM, pitch), dtype=torch.float64, device=self.device)
+            for row, value in _lib.DIAG_CARRIED_ROWS.items():
+                buf[row].fill_(value)
+            _lib.check(self.L.npb_set_diagnostics(self._h, ctypes.c_void_p(buf.data_ptr()), pitch), self._h)
+            self._diag_buf = buf
             self.diagnostics = self._diag_buf[:, : self.n]
+            if carried:
+                if not hasattr(self.L, "npb_carry_diagnostics"):
+                    raise _lib.NpbError("libnpb.so has no npb_carry_diagnostics (older than ABI 151): rebuild")
+                _lib.check(self.L.npb_carry_diagnostics(self._h, 1), self._h)
+            self._diag_carried = bool(carried)
         else:
-            _lib.check(self.L.npb_set_diagnostics(self._h, None, 0), self._h)
-            self._diag_buf = None; self.diagnostics = None
+            _lib.check(self.L.npb_set_diagnostics(self._h, None, 0), self._h)      # (switches the carrying off with it)
+            self._diag_buf = None; self.diagnostics = None; self._diag_carried = False
         return self.diagnostics
+
+    def diagnostics_state(self) -> torch.Tensor:
+        """[len(_lib.DIAG_CARRIED_ROWS), n] copy of the diagnostics rows the step carries (npb_get_diagnostics_state; rows in
+        _lib.DIAG_CARRIED_ROWS order).  Plant state that lives outside the arena: a checkpoint of an env with ``diagnostics=True``
+        saves it beside ``state_arrays()``.  Needs the rows carried (``diagnostics=True`` / ``enable_diagnostics(carried=True)``)."""
+        t = torch.empty((len(_lib.DIAG_CARRIED_ROWS), self.n), dtype=torch.float64, device=self.device)
+        _lib.check(self.L.npb_get_diagnostics_state(self._h, self._p(t), self._stream()), self._h)
+        return t
+
+    def load_diagnostics_state(self, state) -> None:
+        """the inverse of ``diagnostics_state`` (npb_set_diagnostics_state)"""
+        t = torch.as_tensor(state, dtype=torch.float64).to(self.device).contiguous()
+        if t.shape != (len(_lib.DIAG_CARRIED_ROWS), self.n):
+            raise ValueError("diagnostics state must be [%d, %d]" % (len(_lib.DIAG_CARRIED_ROWS), self.n))
+        _lib.check(self.L.npb_set_diagnostics_state(self._h, self._p(t), self._stream()), self._h)
 
     def _reset_carried_diagnostics(self, mask) -> None:
         """The diagnostics rows the step carries from one step to the next (accumulators, latches, values kept while equipment
         rests: _lib.DIAG_CARRIED_ROWS) back to a freshly constructed plant's, for the masked plants: they are plant state that lives
-        in this buffer instead of the arena, so every reset must take them along."""
+        in this buffer instead of the arena, so every reset must take them along.  With the rows carried
+        (``enable_diagnostics(carried=True)``) the device does that, with what the snapshot or the bank holds: nothing to do here."""
         buf = getattr(self, "_diag_buf", None)
-        if buf is None:
+        if buf is None or self._diag_carried:
             return
         for row, value in _lib.DIAG_CARRIED_ROWS.items():
             if mask is None:
@@ -708,10 +758,14 @@ class BatchedPlantEnv:
                              "final_observation": torch.zeros((self.n, 22), dtype=torch.float64, device=self.device),
                              "episode_length": torch.zeros(self.n, dtype=torch.int32, device=self.device),
                              "episode_return": torch.zeros(self.n, dtype=torch.float64, device=self.device)}
+            if hasattr(self.L, "npb_set_episode_index_buffer"):
+                self._episode["episode_index"] = torch.zeros(self.n, dtype=torch.int32, device=self.device)
         _lib.check(self.L.npb_set_autoreset(self._h, 1, int(max_episode_steps or 0)), self._h)
         e = self._episode
         _lib.check(self.L.npb_set_episode_buffers(self._h, self._p(e["episode_length"]), self._p(e["episode_return"]), self._p(e["truncated"]),
                                                   self._p(e["final_observation"])), self._h)
+        if "episode_index" in e:
+            _lib.check(self.L.npb_set_episode_index_buffer(self._h, self._p(e["episode_index"])), self._h)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -775,7 +829,9 @@ class BatchedPlantEnv:
                 self.set_field(key, v)
 
     def state_arrays(self):
-        """(f64[total_f64, n], i32[total_i32, n]) copies of the whole arena (testing / checkpointing)."""
+        """(f64[total_f64, n], i32[total_i32, n]) copies of the whole arena (testing / checkpointing).  A full checkpoint is up to three
+        things: these arrays, ``component_maintenance_state()`` where ``component_maintenance`` is on, and ``diagnostics_state()`` on an
+        env with ``diagnostics=True`` (the rows the diagnostics build carries from step to step live in its buffer, not in the arena)."""
         f = torch.empty((SCHEMA.total_f64, self.n), dtype=torch.float64, device=self.device)
         i = torch.empty((SCHEMA.total_i32, self.n), dtype=torch.int32, device=self.device)
         for s in range(SCHEMA.total_f64):
@@ -801,6 +857,8 @@ class BatchedPlantEnv:
         _lib.check(self.L.npb_set_component_maintenance_state(self._h, self._p(t), self._stream()), self._h)
 
     def load_state_arrays(self, f64, i32) -> None:
+        """the inverse of ``state_arrays``; a full checkpoint also loads ``load_component_maintenance_state`` where that feature is on
+        and ``load_diagnostics_state`` on an env with ``diagnostics=True`` (see ``state_arrays``)"""
         f = torch.as_tensor(f64, dtype=torch.float64).to(self.device).contiguous()
         i = torch.as_tensor(i32, dtype=torch.int32).to(self.device).contiguous()
         for s in range(SCHEMA.total_f64):

@@ -580,8 +580,34 @@ def log_column_name(name: str, naming: str) -> str:
     return name
 
 
+def _episode_windows(fn, sources, episode, episode_step) -> np.ndarray:
+    """A history-window function (history_log_columns) over [samples, plants] series, per (plant, episode): over the episode's rows with
+    episode_step >= 1 when they are steps 1, 2, 3 ... without a gap, NaN everywhere else"""
+    ns, npl = episode.shape
+    out = np.full((ns, npl), np.nan)
+    for j in range(npl):
+        live = episode_step[:, j] >= 1
+        for e in np.unique(episode[live, j]):
+            rows = np.nonzero(live & (episode[:, j] == e))[0]
+            if np.array_equal(episode_step[rows, j], np.arange(1, len(rows) + 1)):
+                out[rows, j] = np.asarray(fn(*[src[rows, j:j + 1] for src in sources]), dtype=np.float64)[:, 0]
+    return out
+
+
 class StateLog:
-    """Device-resident ring of samples of selected state members of every plant."""
+    """Device-resident ring of samples of selected state members of every plant.
+
+    On an env with autoreset (episodes) each sample also records, per plant, ``episode`` -- the number of the episode the plant is in
+    after the step (``info["episode_index"]``, plus one where the step ended an episode) -- and ``episode_step``, the steps since the
+    plant's last restart: 0 on the row sampled right after a step in which the plant restarted.  ``table()`` adds both as int64 columns
+    (only for such an env: other tables keep their columns).  An ``episode_step == 0`` row is a mixed row: its state-member columns (and
+    what is derived from them) show the restored start state, its step-internal columns -- the diagnostics, the keys of the step's
+    result, ``done`` -- the terminal step's values; rows with ``episode_step = k >= 1`` are the reference's log row of step k of a run
+    from that start state.  The history-window columns are formed per (plant, episode) over that episode's rows ``episode_step >= 1``
+    only, when the log holds them from step 1 on without a gap; they are NaN elsewhere (an episode whose step 1 is not in the log, and
+    every ``episode_step == 0`` row).  ``record()`` belongs right behind ``step()``: a ``restore`` in between is seen at the next step.
+    ``diagnostics=True`` on such an env needs the env built with ``diagnostics=True`` (its carried diagnostics rows restart with the
+    plant); otherwise it raises."""
 
     def __init__(self, env, fields: Optional[Sequence[str]] = None, every: int = 1, capacity: int = 256, diagnostics: bool = False):
         self.env = env
@@ -601,6 +627,12 @@ class StateLog:
         self._res = torch.empty((self.capacity, len(self._res_keys), env.n), dtype=torch.float64, device=env.device) if self._res_keys else None
         # step-internal diagnostics (reference layout, full mode): switches the env to the diagnostics build of the step kernel
         self._diag = None
+        self._episodic = getattr(env, "_episode", None) is not None and "episode_index" in env._episode
+        if diagnostics and self._res_keys and self._episodic and not getattr(env, "_diag_carried", False):
+            raise _lib.NpbError("StateLog(env, diagnostics=True) on an env with autoreset needs the diagnostics rows carried across restarts: build the "
+                                "env with diagnostics=True (BatchedPlantEnv(..., diagnostics=True) / action_test(..., diagnostics=True))")
+        # episodes: (episode, episode_step) of every plant per sample
+        self._ep = torch.empty((self.capacity, 2, env.n), dtype=torch.int32, device=env.device) if self._episodic else None
         if diagnostics and self._res_keys:
             if getattr(env, "diagnostics", None) is None:
                 env.enable_diagnostics(True)
@@ -633,6 +665,11 @@ class StateLog:
             self._diag[row].copy_(self.env.diagnostics)
         if self._done is not None:
             self._done[row].copy_(self.env._done)
+        if self._ep is not None:      # as of the step just taken: a plant it reset is at step 0 of its next episode
+            e = self.env._episode
+            ended = (self.env._done != 0) | (e["truncated"] != 0)
+            self._ep[row, 0] = e["episode_index"] + ended.to(torch.int32)
+            self._ep[row, 1] = torch.where(ended, torch.zeros_like(e["episode_length"]), e["episode_length"])
         self._times.append(float(time_minutes)); self._steps.append(int(step))
 
     def maybe_record(self, step: int, time_minutes: float) -> bool:
@@ -658,6 +695,10 @@ class StateLog:
         cols = {"step": np.repeat(np.asarray(self._steps, dtype=np.int64), npl),
                 "time": np.repeat(np.asarray(self._times, dtype=np.float64), npl),
                 "plant": np.tile(idx.astype(np.int64), ns)}
+        ep = None
+        if self._ep is not None:
+            ep = self._ep[:len(self._times)].cpu().numpy()[:, :, idx].astype(np.int64)
+            cols["episode"] = ep[:, 0, :].reshape(-1); cols["episode_step"] = ep[:, 1, :].reshape(-1)
         if self._reference_layout:
             index = {c[2]: f for f, c in enumerate(self.columns)}
             for name, (label, factor) in sorted(reference_log_columns().items()):
@@ -680,7 +721,11 @@ class StateLog:
             done = self._done[:len(self._times)].cpu().numpy()[:, idx].reshape(-1).astype(np.float64)
             for name, what in sorted(output_log_columns().items()):
                 cols[name] = done
-            if self._steps == list(range(1, ns + 1)):      # every step since the reset: the windowed columns can be formed
+            if ep is not None:      # episodes: the windows restart with each plant's episode
+                for name, (sources, fn) in sorted(history_log_columns().items()):
+                    if all(src in cols for src in sources):
+                        cols[name] = _episode_windows(fn, [cols[src].reshape(ns, npl) for src in sources], ep[:, 0, :], ep[:, 1, :]).reshape(-1)
+            elif self._steps == list(range(1, ns + 1)):      # every step since the reset: the windowed columns can be formed
                 for name, (sources, fn) in sorted(history_log_columns().items()):
                     if all(src in cols for src in sources):
                         cols[name] = np.asarray(fn(*[cols[src].reshape(ns, npl) for src in sources]), dtype=np.float64).reshape(-1)
