@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define NPB_VERSION 151 /* 0.1.5.1: npb_carry_diagnostics, npb_diag_num_carried / npb_diag_carried_row / npb_diag_carried_fresh, npb_get / npb_set_diagnostics_state, npb_set_episode_index_buffer (the diagnostics rows the step carries travel with snapshots, start banks, the autoreset, resets and checkpoints; an episode index per plant); 0.1.5.0: npb_set_component_maintenance, npb_default_component_maintenance_table, npb_component_maint_* catalog queries, npb_get / npb_set_component_maintenance_state, NPB_MAINT_EVENT_COMPONENT_CREATED / _COMPLETED (automatic maintenance of steam generators and condenser in one work-order queue with the feedwater pumps); 0.1.4.9: npb_perform_turbine_maintenance, npb_turbine_* catalog queries, NPB_MAINT_EVENT_OPERATOR_TURBINE (maintenance of the turbine, its bearings, lubrication system and stages a caller orders); 0.1.4.8: npb_perform_component_maintenance, npb_component_* catalog queries, NPB_MAINT_EVENT_OPERATOR_COMPONENT (maintenance of steam generators, condenser and ejectors a caller orders); 0.1.4.7: npb_perform_maintenance, NPB_MAINT_EVENT_OPERATOR (maintenance a caller orders, carried out on the device between two steps); 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
+#define NPB_VERSION 152 /* 0.1.5.2: npb_profile_seed, npb_profile_fill, npb_profile_ramp, npb_profile_get_state, npb_profile_set_state (the data-gen runner's power profile drawn on the device, per plant); 0.1.5.1: npb_carry_diagnostics, npb_diag_num_carried / npb_diag_carried_row / npb_diag_carried_fresh, npb_get / npb_set_diagnostics_state, npb_set_episode_index_buffer (the diagnostics rows the step carries travel with snapshots, start banks, the autoreset, resets and checkpoints; an episode index per plant); 0.1.5.0: npb_set_component_maintenance, npb_default_component_maintenance_table, npb_component_maint_* catalog queries, npb_get / npb_set_component_maintenance_state, NPB_MAINT_EVENT_COMPONENT_CREATED / _COMPLETED (automatic maintenance of steam generators and condenser in one work-order queue with the feedwater pumps); 0.1.4.9: npb_perform_turbine_maintenance, npb_turbine_* catalog queries, NPB_MAINT_EVENT_OPERATOR_TURBINE (maintenance of the turbine, its bearings, lubrication system and stages a caller orders); 0.1.4.8: npb_perform_component_maintenance, npb_component_* catalog queries, NPB_MAINT_EVENT_OPERATOR_COMPONENT (maintenance of steam generators, condenser and ejectors a caller orders); 0.1.4.7: npb_perform_maintenance, NPB_MAINT_EVENT_OPERATOR (maintenance a caller orders, carried out on the device between two steps); 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
 #ifndef NPB_API
 #define NPB_API __attribute__((visibility("default")))
 #endif
@@ -517,6 +517,46 @@ NPB_API int npb_noise_fill(NpbHandle *h, int k, double *out, void *stream);
  * the device.  It refuses pos outside [0, 624] and has_gauss outside {0, 1}. */
 NPB_API int npb_noise_get_state(NpbHandle *h, uint32_t *key, int32_t *pos, int32_t *has_gauss, double *cached, void *stream);
 NPB_API int npb_noise_set_state(NpbHandle *h, const uint32_t *key, const int32_t *pos, const int32_t *has_gauss, const double *cached, void *stream);
+
+/* The data-gen runner's power profile on the device, per plant (maintenance_scenario_runner.py:586-671; nuclear_sim_amd/scenarios.py
+ * power_profile_rows is the readable statement).  Per run of `steps` rows the runner draws z = np.random.normal(0, 1, steps) from numpy's
+ * global legacy stream and makes, in this order,
+ *   raw = clip(base + min(0.2, std) * z, 20, 105)
+ *   sm[i] = (raw[i-1] + raw[i] + raw[i+1]) / 3.0 for 0 < i < steps - 1, sm = raw at both ends (and everywhere if steps < 3)
+ *   target[0] = sm[0];     target[i] = sm[i] if |sm[i] - target[i-1]| <= 0.05, else target[i-1] -/+ 0.05         (logged as target_power)
+ *   setpoint[0] = target[0]; setpoint[i] = target[i] if |target[i] - setpoint[i-1]| <= 0.02, else setpoint[i-1] -/+ 0.02 (given to the heat source)
+ * Here every plant has a stream of its own: a SECOND set of MT19937 generators in the handle (the layout of the heat-source noise's,
+ * about 2.5 KB a plant again, allocated on first use, freed by npb_destroy; independent of npb_noise_*, so both can be on) drawn by the
+ * same fill kernel into a block the handle owns, and a filter kernel that turns the block into rows.  Given the draws, the filter's rows
+ * are exactly numpy's (no contraction, IEEE division); the draws are within a few ulp of numpy's, as npb_noise_fill's are.
+ * All plants advance together: the handle keeps ONE position, the rows made of the current profile.  A block may cross a profile's end:
+ * the profile's last row takes no draw, and the next row starts the next profile of the same horizon from the next draw, its ramp
+ * afresh (first setpoint = first target) -- a second runner on the same stream.
+ * Generator state: after R rows in all (q whole profiles and r = R mod steps rows of the next) every generator is numpy's
+ * RandomState(seed) after R standard_normal() calls -- plus ONE, the moving average's look-ahead, when steps >= 3 and r >= 1.  At a
+ * profile's end (r = 0) it is exactly numpy's after q * steps draws.
+ * npb_profile_seed: plant p's stream becomes RandomState(seeds[p]) (host int64[n]; NPB_EINVAL outside [0, 2^32)), position 0, profiles of
+ * `steps` >= 1 rows.  base / std: the load profile's base_power_percent / noise_std_percent, host doubles -- NULL (90.0 / 2.0, the
+ * runner's defaults), n_base / n_std = 1 (one value for all) or n (one per plant).  seeds = NULL frees the profile.  Returns once done. */
+NPB_API int npb_profile_seed(NpbHandle *h, const int64_t *seeds, int steps, const double *base, int n_base, const double *std, int n_std, void *stream);
+/* the next k rows of every plant, enqueued on `stream`: setpoint_out, target_out, z_out device double[k][n] (row t of plant p at
+ * [t * n + p]); target_out and z_out may be NULL.  z_out[t] is the draw behind row t's raw value: power_profile_rows(z_out) must equal
+ * the other two bit for bit.  Allocates only when k exceeds every earlier k (the draw block grows; that call waits for the stream).
+ * NPB_EINVAL before npb_profile_seed, for k < 1 and for a NULL setpoint_out. */
+NPB_API int npb_profile_fill(NpbHandle *h, int k, double *setpoint_out, double *target_out, double *z_out, void *stream);
+/* The ramp stage alone, on the caller's targets (_set_target_power for any block): setpoint_out[t] from target_in[t] (device
+ * double[k][n] each; they may be the same block) and the previous setpoint the handle carries per plant from call to call -- NaN at
+ * first, which means "first call": that setpoint is its target.  No profile needed.  k = 0 with both blocks NULL forgets the carried
+ * setpoints.  NPB_EINVAL for k < 1 or a NULL block otherwise. */
+NPB_API int npb_profile_ramp(NpbHandle *h, int k, const double *target_in, double *setpoint_out, void *stream);
+/* Checkpoints (host buffers, synchronous on `stream`): the generators as npb_noise_get_state gives them (numpy's get_state() layout),
+ * the filter's carried values, double[5][n]: the clipped raw value of the row before the next and of the next row (the look-ahead), the
+ * draw behind the latter, the previous target, the previous setpoint (meaningful from position 1 on), and the position.  The horizon
+ * and the load profiles are configuration: npb_profile_set_state needs npb_profile_seed (same steps, base, std) first and refuses,
+ * beside what npb_noise_set_state refuses, a position outside [0, steps). */
+NPB_API int npb_profile_get_state(NpbHandle *h, uint32_t *key, int32_t *pos, int32_t *has_gauss, double *cached, double *carried, int32_t *position, void *stream);
+NPB_API int npb_profile_set_state(NpbHandle *h, const uint32_t *key, const int32_t *pos, const int32_t *has_gauss, const double *cached, const double *carried,
+                                  int32_t position, void *stream);
 
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the

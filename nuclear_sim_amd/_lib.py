@@ -452,6 +452,12 @@ def load():
         L.npb_noise_fill.argtypes = [vp, ci, vp, vp]
         L.npb_noise_get_state.argtypes = [vp, vp, vp, vp, vp, vp]
         L.npb_noise_set_state.argtypes = [vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "npb_profile_seed"):     # ABI 152: the data-gen runner's power profile on the device
+        L.npb_profile_seed.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp]
+        L.npb_profile_fill.argtypes = [vp, ci, vp, vp, vp, vp]
+        L.npb_profile_ramp.argtypes = [vp, ci, vp, vp, vp]
+        L.npb_profile_get_state.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+        L.npb_profile_set_state.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp]
     if L.npb_num_f64() != SCHEMA.total_f64 or L.npb_num_i32() != SCHEMA.total_i32:
         raise NpbError("libnpb.so was built against a different include/npb_fields.h (%d/%d vs %d/%d): rebuild"
                        % (L.npb_num_f64(), L.npb_num_i32(), SCHEMA.total_f64, SCHEMA.total_i32))

@@ -53,6 +53,10 @@ struct NpbHandle {
   int32_t *next_slot; int32_t *slot_start; int slot_advance;  /* npb_set_start_slots: the caller's columns (next_slot NULL = no slots) */
   int32_t *ep_out_start;                                       /* npb_set_episode_start_buffer: the caller's column, or NULL */
   void *noise; npb_noise_t noise_g;  /* npb_noise_seed / npb_noise_set_state: the heat-source noise generators (npb_noise.hip), or NULL */
+  /* npb_profile_seed: the power profile's generators (a second npb_noise_t), its per-plant columns ([NPB_PROFILE_SIDE][pitch]), its
+   * horizon and the rows made of the current profile (all plants advance together), and the block its draws go through */
+  void *prof; npb_noise_t prof_g; double *prof_side; int prof_steps, prof_pos; double *prof_z; size_t prof_z_rows;
+  double *ramp_prev;   /* npb_profile_ramp: the previous setpoint of every plant ([pitch], NaN = none yet), allocated on first use */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
   std::vector<int> plan_key;
   std::string error;
@@ -369,6 +373,10 @@ int npb_destroy(NpbHandle *h) {
   if (h->bank) (void)hipFree(h->bank);
   if (h->ep_start) (void)hipFree(h->ep_start);
   if (h->noise) (void)hipFree(h->noise);
+  if (h->prof) (void)hipFree(h->prof);
+  if (h->prof_side) (void)hipFree(h->prof_side);
+  if (h->prof_z) (void)hipFree(h->prof_z);
+  if (h->ramp_prev) (void)hipFree(h->ramp_prev);
   delete h;
   return NPB_OK;
 }
@@ -1055,6 +1063,146 @@ int npb_noise_set_state(NpbHandle *h, const uint32_t *key, const int32_t *pos, c
   NPB_HIP(h, hipMemcpyAsync(h->noise_g.has_gauss, has_gauss, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
   NPB_HIP(h, hipMemcpyAsync(h->noise_g.gauss, cached, n * sizeof(double), hipMemcpyHostToDevice, st));
   NPB_HIP(h, hipStreamSynchronize(st));    /* rows and the caller's buffers are read until the copies are done */
+  return NPB_OK;
+}
+
+/* ---- the data-gen runner's power profile (include/npb.h) */
+static void profile_free(NpbHandle *h) {
+  if (h->prof) (void)hipFree(h->prof);
+  if (h->prof_side) (void)hipFree(h->prof_side);
+  if (h->prof_z) (void)hipFree(h->prof_z);
+  h->prof = nullptr; h->prof_side = nullptr; h->prof_z = nullptr; h->prof_z_rows = 0; h->prof_steps = 0; h->prof_pos = 0;
+}
+
+int npb_profile_seed(NpbHandle *h, const int64_t *seeds, int steps, const double *base, int n_base, const double *std, int n_std, void *stream) {
+  if (!h) return NPB_EINVAL;
+  NPB_USE_DEVICE(h);
+  hipStream_t st = (hipStream_t)stream;
+  if (!seeds) {
+    if (h->prof) NPB_HIP(h, hipStreamSynchronize(st));
+    profile_free(h);
+    return NPB_OK;
+  }
+  const int n = h->n_plants;
+  if (steps < 1) return fail(h, NPB_EINVAL, "npb_profile_seed: steps must be >= 1");
+  if ((base && n_base != 1 && n_base != n) || (std && n_std != 1 && n_std != n))
+    return fail(h, NPB_EINVAL, "npb_profile_seed: base and std are each NULL, one value or one value per plant");
+  std::vector<uint32_t> s32((size_t)n);
+  for (int p = 0; p < n; p++) {
+    if (seeds[p] < 0 || seeds[p] > (int64_t)0xffffffffLL)
+      return fail(h, NPB_EINVAL, "npb_profile_seed: a seed is outside [0, 2^32), which numpy.random.RandomState refuses");
+    s32[p] = (uint32_t)seeds[p];
+  }
+  const size_t pitch = h->pitch;
+  if (!h->prof) {
+    hipError_t e = hipMalloc(&h->prof, npb_noise_bytes(pitch));
+    if (e == hipSuccess) e = hipMalloc((void **)&h->prof_side, (size_t)NPB_PROFILE_SIDE * pitch * sizeof(double));
+    if (e != hipSuccess) { profile_free(h); return fail(h, NPB_EHIP, "npb_profile_seed: hipMalloc of the profile generators failed", e); }
+    h->prof_g = npb_noise_layout(h->prof, pitch);
+  }
+  /* the load profile's two columns, the runner's cap on the noise taken here; the carried rows start at 0 (position 0 reads none) */
+  std::vector<double> side((size_t)NPB_PROFILE_SIDE * pitch, 0.0);
+  for (int p = 0; p < n; p++) {
+    const double b = base ? base[n_base == 1 ? 0 : p] : 90.0, sd = std ? std[n_std == 1 ? 0 : p] : 2.0;
+    side[(size_t)NPB_PROFILE_BASE * pitch + p] = b;
+    side[(size_t)NPB_PROFILE_SCALE * pitch + p] = sd < 0.2 ? sd : 0.2;      /* min(0.2, std), a NaN std -> 0.2 as Python's min has it */
+  }
+  NPB_HIP(h, hipMemcpyAsync(h->prof_side, side.data(), side.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(h->prof_g.pos, s32.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  npb_launch_noise_seed(h->prof_g, n, st);
+  NPB_HIP(h, hipGetLastError());
+  NPB_HIP(h, hipStreamSynchronize(st));    /* side and s32 are read until the copies are done */
+  h->prof_steps = steps; h->prof_pos = 0;
+  return NPB_OK;
+}
+
+int npb_profile_fill(NpbHandle *h, int k, double *setpoint_out, double *target_out, double *z_out, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->prof) return fail(h, NPB_EINVAL, "npb_profile_fill: no profile (npb_profile_seed first)");
+  if (k < 1 || !setpoint_out) return fail(h, NPB_EINVAL, "npb_profile_fill: k must be >= 1 and setpoint_out non-NULL");
+  NPB_USE_DEVICE(h);
+  hipStream_t st = (hipStream_t)stream;
+  const int n = h->n_plants, draws = npb_profile_draws(h->prof_steps, h->prof_pos, k);
+  if ((size_t)draws > h->prof_z_rows) {      /* the draw block grows to the largest block asked for (at most k + 1 rows) */
+    NPB_HIP(h, hipStreamSynchronize(st));
+    if (h->prof_z) (void)hipFree(h->prof_z);
+    h->prof_z = nullptr; h->prof_z_rows = 0;
+    hipError_t e = hipMalloc((void **)&h->prof_z, (size_t)draws * n * sizeof(double));
+    if (e != hipSuccess) { h->prof_z = nullptr; return fail(h, NPB_EHIP, "npb_profile_fill: hipMalloc of the draw block failed", e); }
+    h->prof_z_rows = (size_t)draws;
+  }
+  if (draws > 0) npb_launch_noise_fill(h->prof_g, n, draws, h->prof_z, st);
+  npb_launch_profile_rows(n, k, h->prof_steps, h->prof_pos, h->prof_side, h->pitch, h->prof_z, setpoint_out, target_out, z_out, st);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, NPB_EHIP, "npb_profile_fill: kernel launch failed", e);
+  h->prof_pos = (int)(((long long)h->prof_pos + k) % h->prof_steps);
+  return NPB_OK;
+}
+
+int npb_profile_ramp(NpbHandle *h, int k, const double *target_in, double *setpoint_out, void *stream) {
+  if (!h) return NPB_EINVAL;
+  const bool forget = k == 0 && !target_in && !setpoint_out;
+  if (!forget && (k < 1 || !target_in || !setpoint_out)) return fail(h, NPB_EINVAL, "npb_profile_ramp: k must be >= 1 and both blocks non-NULL (or 0, NULL, NULL: forget the carried setpoints)");
+  NPB_USE_DEVICE(h);
+  hipStream_t st = (hipStream_t)stream;
+  if (!h->ramp_prev || forget) {
+    if (!h->ramp_prev) {
+      hipError_t e = hipMalloc((void **)&h->ramp_prev, h->pitch * sizeof(double));
+      if (e != hipSuccess) { h->ramp_prev = nullptr; return fail(h, NPB_EHIP, "npb_profile_ramp: hipMalloc failed", e); }
+    }
+    npb_launch_profile_set(h->ramp_prev, h->pitch, __builtin_nan(""), st);
+  }
+  if (!forget) npb_launch_profile_ramp(h->n_plants, k, target_in, setpoint_out, h->ramp_prev, st);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, NPB_EHIP, "npb_profile_ramp: kernel launch failed", e);
+  return NPB_OK;
+}
+
+int npb_profile_get_state(NpbHandle *h, uint32_t *key, int32_t *pos, int32_t *has_gauss, double *cached, double *carried, int32_t *position, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->prof) return fail(h, NPB_EINVAL, "npb_profile_get_state: no profile (npb_profile_seed first)");
+  if (!key || !pos || !has_gauss || !cached || !carried || !position) return fail(h, NPB_EINVAL, "npb_profile_get_state: NULL output");
+  NPB_USE_DEVICE(h);
+  const size_t n = (size_t)h->n_plants, pitch = h->pitch;
+  std::vector<uint32_t> rows((size_t)NPB_MT_N * n);     /* [624][n], then transposed to numpy's [n][624] */
+  hipStream_t st = (hipStream_t)stream;
+  NPB_HIP(h, hipMemcpy2DAsync(rows.data(), n * sizeof(uint32_t), h->prof_g.key, pitch * sizeof(uint32_t), n * sizeof(uint32_t), NPB_MT_N, hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpyAsync(pos, h->prof_g.pos, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpyAsync(has_gauss, h->prof_g.has_gauss, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpyAsync(cached, h->prof_g.gauss, n * sizeof(double), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpy2DAsync(carried, n * sizeof(double), h->prof_side + (size_t)NPB_PROFILE_CARRIED * pitch, pitch * sizeof(double), n * sizeof(double),
+                              NPB_PROFILE_NUM_CARRIED, hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipStreamSynchronize(st));
+  for (size_t i = 0; i < (size_t)NPB_MT_N; i++)
+    for (size_t p = 0; p < n; p++) key[p * NPB_MT_N + i] = rows[i * n + p];
+  *position = h->prof_pos;
+  return NPB_OK;
+}
+
+int npb_profile_set_state(NpbHandle *h, const uint32_t *key, const int32_t *pos, const int32_t *has_gauss, const double *cached, const double *carried,
+                          int32_t position, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->prof) return fail(h, NPB_EINVAL, "npb_profile_set_state: no profile (npb_profile_seed first: it sets the horizon and the load profiles)");
+  if (!key || !pos || !has_gauss || !cached || !carried) return fail(h, NPB_EINVAL, "npb_profile_set_state: NULL input");
+  if (position < 0 || position >= h->prof_steps) return fail(h, NPB_EINVAL, "npb_profile_set_state: position outside [0, steps)");
+  const size_t n = (size_t)h->n_plants, pitch = h->pitch;
+  for (size_t p = 0; p < n; p++) {
+    if (pos[p] < 0 || pos[p] > NPB_MT_N) return fail(h, NPB_EINVAL, "npb_profile_set_state: pos outside [0, 624]");
+    if (has_gauss[p] != 0 && has_gauss[p] != 1) return fail(h, NPB_EINVAL, "npb_profile_set_state: has_gauss outside {0, 1}");
+  }
+  NPB_USE_DEVICE(h);
+  std::vector<uint32_t> rows((size_t)NPB_MT_N * n);
+  for (size_t i = 0; i < (size_t)NPB_MT_N; i++)
+    for (size_t p = 0; p < n; p++) rows[i * n + p] = key[p * NPB_MT_N + i];
+  hipStream_t st = (hipStream_t)stream;
+  NPB_HIP(h, hipMemcpy2DAsync(h->prof_g.key, pitch * sizeof(uint32_t), rows.data(), n * sizeof(uint32_t), n * sizeof(uint32_t), NPB_MT_N, hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(h->prof_g.pos, pos, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(h->prof_g.has_gauss, has_gauss, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(h->prof_g.gauss, cached, n * sizeof(double), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpy2DAsync(h->prof_side + (size_t)NPB_PROFILE_CARRIED * pitch, pitch * sizeof(double), carried, n * sizeof(double), n * sizeof(double),
+                              NPB_PROFILE_NUM_CARRIED, hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipStreamSynchronize(st));    /* rows and the caller's buffers are read until the copies are done */
+  h->prof_pos = position;
   return NPB_OK;
 }
 

@@ -1,4 +1,5 @@
-/* npb_noise.h -- host-callable launchers of the heat-source noise generator (npb_noise.hip; internal to libnpb.so).
+/* npb_noise.h -- host-callable launchers of the heat-source noise generator and of the power profile's filter (npb_noise.hip;
+ * internal to libnpb.so).
  * One MT19937 stream per plant, numpy's legacy RandomState: key [624][pitch] uint32 (word i of every plant contiguous),
  * pos / has_gauss int32 [pitch], gauss double [pitch]. */
 #ifndef NPB_NOISE_H
@@ -24,6 +25,26 @@ npb_noise_t npb_noise_layout(void *base, size_t pitch);
 void npb_launch_noise_seed(npb_noise_t g, int n_plants, hipStream_t stream);
 /* the next k standard_normal() draws of every plant into out[t * n_plants + p] */
 void npb_launch_noise_fill(npb_noise_t g, int n_plants, int k, double *out, hipStream_t stream);
+
+/* The data-gen runner's power profile (include/npb.h, npb_profile_*): rows from a block of draws of the profile's own generators.
+ * Per plant, [NPB_PROFILE_SIDE][pitch] doubles: its load profile (base, and min(0.2, std) already taken) and what the filter carries
+ * from one row to the next -- the clipped raw values of the previous row and of this one (this one's is the moving average's one-draw
+ * look-ahead of the previous row), the draw behind the latter, the previous target and the previous setpoint. */
+enum { NPB_PROFILE_BASE = 0, NPB_PROFILE_SCALE, NPB_PROFILE_CARRIED, /* then the carried values, in npb_profile_get_state's order: */
+       NPB_PROFILE_RAW_PREV = NPB_PROFILE_CARRIED, NPB_PROFILE_RAW, NPB_PROFILE_Z, NPB_PROFILE_TARGET, NPB_PROFILE_SETPOINT, NPB_PROFILE_SIDE };
+#define NPB_PROFILE_NUM_CARRIED (NPB_PROFILE_SIDE - NPB_PROFILE_CARRIED)
+/* draws that rows [pos, pos + k) of profiles of `steps` rows consume (pos: rows already made of the current profile, 0 <= pos < steps):
+ * the kernel's own count, so the block it is given is exactly as long as what it reads */
+int npb_profile_draws(int steps, int pos, int k);
+/* k rows from position pos on: draws [npb_profile_draws(steps, pos, k)][n_plants] in, setpoint_out / target_out / z_out [k][n_plants]
+ * out (the last two may be NULL); side is read and its carried rows written */
+void npb_launch_profile_rows(int n_plants, int k, int steps, int pos, double *side, size_t pitch, const double *draws,
+                             double *setpoint_out, double *target_out, double *z_out, hipStream_t stream);
+/* the ramp stage alone: setpoint_out[t] from target_in[t] ([k][n_plants] each; they may be the same block) and the carried previous
+ * setpoint prev [n_plants] (NaN = none yet: the first setpoint is the first target), which is updated */
+void npb_launch_profile_ramp(int n_plants, int k, const double *target_in, double *setpoint_out, double *prev, hipStream_t stream);
+/* v into x[0 .. count) */
+void npb_launch_profile_set(double *x, size_t count, double v, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

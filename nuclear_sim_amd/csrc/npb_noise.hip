@@ -13,6 +13,9 @@
  *
  * One lane per plant.  Lanes reject independently and so run out of words at different draws; a lane that does waits, and the
  * wave twists every waiting lane in one pass, so the 624-word loop is run once per generation for the wave, not once per lane.
+ *
+ * The same generator, on a second set of states, feeds the data-gen runner's power profile: npb_profile_rows_kernel (below) turns a
+ * block of its draws into target and setpoint rows, and has the ramp stage alone as a second entry.
  */
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -147,9 +150,110 @@ __global__ __launch_bounds__(64) void npb_noise_fill_kernel(npb_noise_t g, int n
   g.gauss[p] = cached;
 }
 
+/* ---- the data-gen runner's power profile (maintenance_scenario_runner.py:586-671; nuclear_sim_amd/scenarios.py power_profile_rows
+ * is the readable statement).  One lane per plant walks the block's rows; every operation is the reference's, in its order, under
+ * this file's flags (no contraction, IEEE division), so the rows are exactly what numpy makes of the same draws. */
+
+/* np.clip(x, 20.0, 105.0) */
+__device__ __forceinline__ double profile_raw(double base, double scale, double z) { return fmin(fmax(base + scale * z, 20.0), 105.0); }
+
+/* _apply_power_rate_limit's and _set_target_power's step: wanted if it is within rate of previous, else previous -/+ rate */
+__device__ __forceinline__ double limited(double previous, double wanted, double rate) {
+  const double change = wanted - previous;
+  if (fabs(change) > rate) return change > 0 ? previous + rate : previous - rate;
+  return wanted;
+}
+
+/* draws row i of a profile of T rows takes from the block: the moving average (T >= 3) looks one draw ahead, so row 0 takes its own
+ * draw and row 1's, rows 1 .. T - 2 take the next row's, and the last row none; without it (T < 3) every row takes its own */
+__host__ __device__ __forceinline__ int profile_row_draws(int T, int i) { return T < 3 ? 1 : i == 0 ? 2 : i < T - 1 ? 1 : 0; }
+
+template <bool RAMP_ONLY>
+__global__ __launch_bounds__(256) void npb_profile_rows_kernel(int n_plants, int k, int T, int pos, double *side, size_t pitch,
+                                                               const double *draws, const double *target_in, double *setpoint_out,
+                                                               double *target_out, double *z_out, double *ramp_prev) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_plants) return;
+  const size_t n = (size_t)n_plants;
+  if (RAMP_ONLY) {
+    double sp = ramp_prev[p];
+    for (int t = 0; t < k; t++) {
+      const double target = target_in[(size_t)t * n + p];
+      sp = isnan(sp) ? target : limited(sp, target, 0.02);
+      setpoint_out[(size_t)t * n + p] = sp;
+    }
+    ramp_prev[p] = sp;
+    return;
+  }
+  double *s = side + p;
+  const double base = s[NPB_PROFILE_BASE * pitch], scale = s[NPB_PROFILE_SCALE * pitch];
+  double raw_prev = s[NPB_PROFILE_RAW_PREV * pitch], raw = s[NPB_PROFILE_RAW * pitch], z = s[NPB_PROFILE_Z * pitch];
+  double target = s[NPB_PROFILE_TARGET * pitch], setpoint = s[NPB_PROFILE_SETPOINT * pitch];
+  const double *d = draws + p;      /* the next draw of this lane */
+  int i = pos;
+  for (int t = 0; t < k; t++) {
+    double sm = raw;                 /* the smoothed value of row i; z: the draw behind its raw value */
+    if (T < 3 || i == 0) {
+      z = *d; d += n;
+      raw = profile_raw(base, scale, z);
+      sm = raw;
+    }
+    if (T >= 3) {
+      const double z_row = z;
+      if (i < T - 1) {               /* the look-ahead: raw[i + 1] */
+        z = *d; d += n;
+        const double ahead = profile_raw(base, scale, z);
+        if (i > 0) sm = (raw_prev + raw + ahead) / 3.0;
+        raw_prev = raw; raw = ahead;
+      } else {
+        sm = raw;                    /* the last row is left unsmoothed and draws nothing */
+      }
+      if (z_out) z_out[(size_t)t * n + p] = z_row;
+    } else if (z_out) {
+      z_out[(size_t)t * n + p] = z;
+    }
+    target = i == 0 ? sm : limited(target, sm, 0.05);
+    setpoint = i == 0 ? target : limited(setpoint, target, 0.02);    /* a new profile's ramp starts on its first target */
+    if (target_out) target_out[(size_t)t * n + p] = target;
+    setpoint_out[(size_t)t * n + p] = setpoint;
+    if (++i == T) i = 0;
+  }
+  s[NPB_PROFILE_RAW_PREV * pitch] = raw_prev; s[NPB_PROFILE_RAW * pitch] = raw; s[NPB_PROFILE_Z * pitch] = z;
+  s[NPB_PROFILE_TARGET * pitch] = target; s[NPB_PROFILE_SETPOINT * pitch] = setpoint;
+}
+
+__global__ __launch_bounds__(256) void npb_profile_set_kernel(double *x, size_t count, double v) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) x[i] = v;
+}
+
 }  // namespace
 
 extern "C" {
+
+int npb_profile_draws(int steps, int pos, int k) {
+  int draws = 0;
+  for (int t = 0, i = pos; t < k; t++) {
+    draws += profile_row_draws(steps, i);
+    if (++i == steps) i = 0;
+  }
+  return draws;
+}
+
+void npb_launch_profile_rows(int n_plants, int k, int steps, int pos, double *side, size_t pitch, const double *draws,
+                             double *setpoint_out, double *target_out, double *z_out, hipStream_t stream) {
+  hipLaunchKernelGGL(npb_profile_rows_kernel<false>, dim3((n_plants + 255) / 256), dim3(256), 0, stream, n_plants, k, steps, pos, side, pitch,
+                     draws, (const double *)nullptr, setpoint_out, target_out, z_out, (double *)nullptr);
+}
+
+void npb_launch_profile_ramp(int n_plants, int k, const double *target_in, double *setpoint_out, double *prev, hipStream_t stream) {
+  hipLaunchKernelGGL(npb_profile_rows_kernel<true>, dim3((n_plants + 255) / 256), dim3(256), 0, stream, n_plants, k, 1, 0, (double *)nullptr, (size_t)0,
+                     (const double *)nullptr, target_in, setpoint_out, (double *)nullptr, (double *)nullptr, prev);
+}
+
+void npb_launch_profile_set(double *x, size_t count, double v, hipStream_t stream) {
+  if (count) hipLaunchKernelGGL(npb_profile_set_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, x, count, v);
+}
 
 size_t npb_noise_bytes(size_t pitch) { return pitch * ((size_t)MT_N * sizeof(uint32_t) + 2 * sizeof(int32_t) + sizeof(double)); }
 

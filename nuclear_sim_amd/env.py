@@ -136,6 +136,93 @@ class DeviceHeatSourceNoise:
         self._pos = self._block
 
 
+class PowerProfile:
+    """The data-gen runner's power profile, drawn on the device per plant (npb_profile_seed / npb_profile_fill): what
+    ``MaintenanceScenarioRunner._generate_power_profile(steps)`` and ``_set_target_power`` (maintenance_scenario_runner.py:586-671)
+    make of ``np.random.normal(0, 1, steps)`` -- noise of min(0.2, std) % around the base power clipped to [20, 105] %, a 3-point
+    moving average, at most 0.05 % a step, then the heat source's ramp of at most 0.02 % a step -- for a stream seeded per plant
+    (``RandomState(seed)``) just before the runner draws.  ``scenarios.power_profile_rows`` is the same in numpy.  The generators are
+    a second set in ``env``'s handle, independent of the heat-source noise's.  ``base_power_percent`` / ``noise_std_percent`` are
+    scalars or one value per plant (the composer's template has 90 / 2.0 and 98 / 0.2 profiles; a fleet may mix them).
+
+    ``next()`` hands out ``(setpoint_row, target_row)``, [n] float64 device rows: the setpoint is what ``step(power_setpoint=...)``
+    takes, the target what the runner logs as target_power.  A [block, n] block is refilled when it runs out; each refill is a fresh
+    tensor, so rows handed out earlier stay valid.  After ``steps`` rows the next profile of the same horizon begins from the next
+    draw, its ramp afresh (the first setpoint is the first target), as a second runner in the same process would.
+
+    ``get_state()`` / ``set_state()``: the generators in numpy's ``get_state()`` layout, the filter's carried values [5, n] and the
+    position in the current profile.  As with ``DeviceHeatSourceNoise`` the state is the handle's -- after the current block, not
+    after the last row handed out -- and ``set_state`` drops the rest of the block; it belongs on a ``PowerProfile`` built with the
+    same ``steps`` and load profiles.  A second instance on the same env re-seeds the handle's profile."""
+
+    def __init__(self, env: "BatchedPlantEnv", seeds: Sequence[int], steps: int, base_power_percent=90.0, noise_std_percent=2.0,
+                 block: int = 256):
+        if int(block) < 1:
+            raise ValueError("block must be >= 1")
+        if int(steps) < 1:
+            raise ValueError("steps must be >= 1")
+        if not hasattr(env.L, "npb_profile_seed"):
+            raise _lib.NpbError("libnpb.so has no npb_profile_seed (older than ABI 152): rebuild")
+        s = np.ascontiguousarray(np.asarray(seeds, dtype=np.int64).reshape(-1))
+        if s.size != env.n:
+            raise ValueError("one seed per plant: %d seeds for %d plants" % (s.size, env.n))
+        cols = []
+        for name, v in (("base_power_percent", base_power_percent), ("noise_std_percent", noise_std_percent)):
+            a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
+            if a.size not in (1, env.n):
+                raise ValueError("%s: one value, or one per plant (%d for %d plants)" % (name, a.size, env.n))
+            cols.append(a)
+        self._env = env
+        self._block = int(block)
+        self.steps = int(steps)
+        _lib.check(env.L.npb_profile_seed(env._h, s.ctypes.data_as(ctypes.c_void_p), self.steps,
+                                          cols[0].ctypes.data_as(ctypes.c_void_p), cols[0].size,
+                                          cols[1].ctypes.data_as(ctypes.c_void_p), cols[1].size, env._stream()), env._h)
+        self._buf = None
+        self._pos = self._block
+
+    def fill(self, k: int, with_draws: bool = False):
+        """the next ``k`` rows as fresh [k, n] tensors ``(setpoint, target)`` -- with ``with_draws`` also the draw behind each row's raw
+        value, ``(setpoint, target, z)``: ``scenarios.power_profile_rows(z)`` of a whole profile equals the other two bit for bit"""
+        env = self._env
+        with torch.cuda.device(env.device):
+            out = torch.empty((3 if with_draws else 2, int(k), env.n), dtype=torch.float64, device=env.device)
+        _lib.check(env.L.npb_profile_fill(env._h, int(k), ctypes.c_void_p(out[0].data_ptr()), ctypes.c_void_p(out[1].data_ptr()),
+                                          ctypes.c_void_p(out[2].data_ptr()) if with_draws else None, env._stream()), env._h)
+        return tuple(out)
+
+    def next(self):
+        if self._pos >= self._block:
+            self._buf = self.fill(self._block)
+            self._pos = 0
+        out = self._buf[0][self._pos], self._buf[1][self._pos]
+        self._pos += 1
+        return out
+
+    def get_state(self):
+        """(key [n, 624] uint32, pos [n] int32, has_gauss [n] int32, cached [n] float64, carried [5, n] float64, position)"""
+        env, n = self._env, self._env.n
+        key = np.empty((n, 624), dtype=np.uint32)
+        pos, has_gauss = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        cached, carried = np.empty(n, dtype=np.float64), np.empty((5, n), dtype=np.float64)
+        position = ctypes.c_int32(0)
+        _lib.check(env.L.npb_profile_get_state(env._h, *(a.ctypes.data_as(ctypes.c_void_p) for a in (key, pos, has_gauss, cached, carried)),
+                                               ctypes.byref(position), env._stream()), env._h)
+        return key, pos, has_gauss, cached, carried, int(position.value)
+
+    def set_state(self, key, pos, has_gauss, cached, carried, position) -> None:
+        """load a state as ``get_state`` returns it; the rest of the block is dropped"""
+        env, n = self._env, self._env.n
+        arrays = (np.ascontiguousarray(np.broadcast_to(np.asarray(key, dtype=np.uint32), (n, 624))),
+                  np.ascontiguousarray(np.broadcast_to(np.asarray(pos, dtype=np.int32), (n,))),
+                  np.ascontiguousarray(np.broadcast_to(np.asarray(has_gauss, dtype=np.int32), (n,))),
+                  np.ascontiguousarray(np.broadcast_to(np.asarray(cached, dtype=np.float64), (n,))),
+                  np.ascontiguousarray(np.broadcast_to(np.asarray(carried, dtype=np.float64), (5, n))))
+        _lib.check(env.L.npb_profile_set_state(env._h, *(a.ctypes.data_as(ctypes.c_void_p) for a in arrays), int(position), env._stream()), env._h)
+        self._buf = None
+        self._pos = self._block
+
+
 NOISE_GENERATORS = ("host", "device")
 
 
@@ -238,6 +325,16 @@ class BatchedPlantEnv:
     ``RandomState(seed).standard_normal()`` stream on the host (``HeatSourceNoise``); ``"device"`` generates the same streams on the
     device (``DeviceHeatSourceNoise``: integer state exactly numpy's, every draw within a few ulp), with no host work per step.
     Either way ``reset()`` of the whole batch re-seeds seeded streams; a masked reset, ``restore`` and the autoreset keep them going.
+
+    Power profile (``power_profile=dict(seeds=..., steps=..., base_power_percent=90.0, noise_std_percent=2.0, block=256)``): the
+    data-gen runner's load profile and ramp drawn on the device per plant (``PowerProfile``), so that an episode needs no per-step
+    host input.  ``step()`` with ``power_setpoint=None`` then takes the next row as its setpoint and returns the pre-ramp row, what
+    the runner logs, as ``info["target_power"]``; an explicit ``power_setpoint`` wins, consumes no row and gives no
+    ``info["target_power"]``.  ``reset()`` of the whole batch re-seeds the profile, as it re-seeds the noise; a masked reset,
+    ``restore``, the start bank and the autoreset leave it running, as they leave the noise stream: all plants share one position
+    in the profile.  With ``max_episode_steps == steps`` a truncated plant's next episode therefore begins exactly with the next
+    profile (a plant that ends earlier restarts mid-profile).  ``ramp_setpoints(targets)`` is the ramp stage alone, for targets of
+    the caller's own.
     """
 
     action_space_size = 15       # NuclearPlantEnv sim.py:916
@@ -249,9 +346,16 @@ class BatchedPlantEnv:
                  storage: str = "f64", maintenance_thresholds: Optional[dict] = None, reactivity_components: bool = False,
                  integrator: str = "reference", autoreset: bool = False, max_episode_steps: Optional[int] = None,
                  noise_generator: str = "host", component_maintenance: bool = False, component_thresholds: Optional[dict] = None,
-                 diagnostics: bool = False):
+                 diagnostics: bool = False, power_profile: Optional[dict] = None):
         if max_episode_steps is not None and not autoreset:
             raise ValueError("max_episode_steps needs autoreset=True")
+        if power_profile is not None:
+            if heat_source == "external":
+                raise ValueError("power_profile drives the heat source's setpoint: not with heat_source='external'")
+            unknown = set(power_profile) - {"seeds", "steps", "base_power_percent", "noise_std_percent", "block"}
+            if unknown or "seeds" not in power_profile or "steps" not in power_profile:
+                raise ValueError("power_profile needs seeds and steps, and may have base_power_percent, noise_std_percent and block%s"
+                                 % (": unknown %r" % sorted(unknown) if unknown else ""))
         if component_thresholds is not None and not component_maintenance:
             raise ValueError("component_thresholds needs component_maintenance=True")
         if diagnostics and mode != "full":
@@ -335,6 +439,10 @@ class BatchedPlantEnv:
         self._noise_seeds = None if noise_seeds is None else np.asarray(noise_seeds, dtype=np.int64).copy()
         if noise_enabled and noise_seeds is not None:
             self._noise = self._make_noise(noise_seeds)
+        self._profile = None
+        self._profile_args = None if power_profile is None else dict(power_profile)
+        if power_profile is not None:
+            self._profile = PowerProfile(self, **self._profile_args)
         self._keep = []
         self._episode = None
         self._bank = None
@@ -350,7 +458,8 @@ class BatchedPlantEnv:
                     params: Optional[dict] = None, autoreset: bool = False, max_episode_steps: Optional[int] = None,
                     bank_seeds: Optional[Sequence[int]] = None, noise_generator: str = "host",
                     maintenance_log: Optional[int] = None, component_maintenance: bool = False,
-                    component_thresholds: Optional[dict] = None, diagnostics: bool = False) -> "BatchedPlantEnv":
+                    component_thresholds: Optional[dict] = None, diagnostics: bool = False,
+                    power_profile_steps: Optional[int] = None) -> "BatchedPlantEnv":
         """One plant per seed, as data_gen's MaintenanceScenarioRunner builds them for
         ``compose_action_test_scenario(action, randomize=True, randomization_seed=seed)``
         (maintenance_scenario_runner.py:210-244): dt in minutes, ConstantHeatSource with 0.1 % noise seeded 42,
@@ -362,13 +471,19 @@ class BatchedPlantEnv:
         ``component_maintenance`` / ``component_thresholds`` as for the constructor: the runner's plant has the automatic maintenance of
         the steam generators and the condenser on as well (the composer's rows by default); off by default, as before.
         ``diagnostics`` as for the constructor (the diagnostics build with its carried rows taken along: what ``StateLog(env,
-        diagnostics=True)`` needs on an env with episodes); the bank of ``bank_seeds`` is built with the same flag."""
+        diagnostics=True)`` needs on an env with episodes); the bank of ``bank_seeds`` is built with the same flag.
+        ``power_profile_steps`` = T attaches the runner's power profile of T steps (``power_profile=dict(seeds=seeds, steps=T)``: the
+        composer's 90 % / 2.0 % load profile), so ``step()`` needs no setpoint.  The profile seeds are the scenario seeds.  This is
+        NOT the profile the live runner draws for that scenario seed: its global stream is further along by then, by whatever the
+        composer's randomiser drew from it, and that consumption is not restated.  What is reproduced is the runner's profile for
+        a stream seeded just before it (np.random.seed(seed) immediately before run_scenario)."""
         if max_episode_steps is not None and not autoreset:
             raise ValueError("max_episode_steps needs autoreset=True")
         from . import scenarios
         env = cls(len(seeds), dt=dt, heat_source="constant", noise_enabled=True, noise_std_percent=0.1,
                   noise_seeds=[42] * len(seeds), device=device, maintenance=True, params=params, noise_generator=noise_generator,
-                  component_maintenance=component_maintenance, component_thresholds=component_thresholds, diagnostics=diagnostics)
+                  component_maintenance=component_maintenance, component_thresholds=component_thresholds, diagnostics=diagnostics,
+                  power_profile=None if power_profile_steps is None else dict(seeds=list(seeds), steps=int(power_profile_steps)))
         eff = float(env.get_field("pump.lubrication_effectiveness")[0].item())
         env.set_fields(scenarios.action_test_fields(action, seeds, eff, randomize=randomize))
         # what a state log of these plants needs beside their state: the composer's provider names and the values the constructor
@@ -898,7 +1013,24 @@ class BatchedPlantEnv:
             # share one pre-drawn stream here, so only a reset of the whole batch can restart it.
             if mask is None and self._noise is not None and self._noise_seeds is not None:
                 self._noise = self._make_noise(self._noise_seeds)
+            if mask is None and self._profile is not None:      # and a freshly started runner a freshly drawn profile
+                self._profile = PowerProfile(self, **self._profile_args)
         return self.get_observation()
+
+    def ramp_setpoints(self, targets: torch.Tensor) -> torch.Tensor:
+        """The runner's ``_set_target_power`` for a block of targets ([k, n] float64 on the device, or one [n] row): the setpoints
+        the heat source is to be given, each at most 0.02 % from the one before (npb_profile_ramp).  The previous setpoint is carried
+        in the handle from call to call; the very first call starts on its first target.  ``forget_ramp()`` starts afresh."""
+        t = targets.reshape(-1, self.n)
+        if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+            t = t.to(device=self.device, dtype=torch.float64).contiguous()
+        out = torch.empty_like(t)
+        _lib.check(self.L.npb_profile_ramp(self._h, t.shape[0], ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(out.data_ptr()), self._stream()), self._h)
+        return out.reshape(targets.shape)
+
+    def forget_ramp(self) -> None:
+        """drop the setpoints ``ramp_setpoints`` carries: its next call starts on its first target"""
+        _lib.check(self.L.npb_profile_ramp(self._h, 0, None, None, self._stream()), self._h)
 
     def get_observation(self) -> torch.Tensor:
         _lib.check(self.L.npb_observe(self._h, self._p(self._obs), self._stream()), self._h)
@@ -931,6 +1063,9 @@ class BatchedPlantEnv:
             raise ValueError("thermal_power_mw / power_percent are the inputs of heat_source='external'")
         a = self._col(None if action is None else action, torch.int32)
         m = self._col(magnitude, torch.float64)
+        target_power = None
+        if power_setpoint is None and self._profile is not None:
+            power_setpoint, target_power = self._profile.next()
         sp = self._col(power_setpoint, torch.float64)
         cw = self._col(cooling_water_temp, torch.float64)
         if noise_z is None and self._noise is None and self.params.hs_noise_enabled:
@@ -948,6 +1083,8 @@ class BatchedPlantEnv:
             info["reactivity_components"] = {name: self._rho[:, j] for j, name in enumerate(_lib.REACTIVITY_COMPONENTS)}
         info["trip_flags"] = self._flags
         info["scram_activated"] = self._done
+        if target_power is not None:   # the power profile's row before the ramp: the runner's target_power for this step
+            info["target_power"] = target_power
         if self.params.maint_enabled:  # bit-exact counterpart of AutoMaintenanceSystem.maintenance_actions_performed
             # a column the step keeps current (npb_set_maintenance_count_buffer): no gather launch per step
             info["maintenance_event_count"] = self._event_counts if self._event_counts is not None else self.get_field("maint.maintenance_actions_performed")

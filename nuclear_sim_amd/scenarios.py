@@ -693,3 +693,56 @@ def action_test_fields(action: str, seeds: Sequence[int], lubrication_effectiven
     for k in range(4):
         f[("turb.bearing_metal_temp", 0, k)] = np.full(1, ACTION_TEST_TEMPLATE["turbine"]["bearing_temperatures"][k])
     return f
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The data-gen runner's power profile (MaintenanceScenarioRunner, maintenance_scenario_runner.py:586-671), as columns.
+# This is the readable statement; the device draws the same rows (include/npb.h npb_profile_*, env.PowerProfile).
+PROFILE_NOISE_CAP = 0.2        # _generate_power_profile: noise_std = min(0.2, noise_std)
+PROFILE_CLIP = (20.0, 105.0)   # np.clip(power_profile, 20.0, 105.0)
+PROFILE_RATE_LIMIT = 0.05      # _apply_power_rate_limit: % per step
+PROFILE_RAMP_RATE = 0.02       # _set_target_power: % per step
+
+
+def _limited(previous, wanted, rate):
+    """one step of either limiter: ``wanted`` if it is within ``rate`` of ``previous``, else ``previous`` -/+ ``rate``"""
+    change = wanted - previous
+    return np.where(np.abs(change) > rate, np.where(change > 0, previous + rate, previous - rate), wanted)
+
+
+def power_profile_ramp(target, previous=None):
+    """``_set_target_power`` (:651-671) over the rows of ``target`` ([k, n] or [k]): the setpoints the heat source is given, and the
+    last of them (what the next call carries as ``previous``).  ``previous`` None, or NaN for a plant, is the runner's first call:
+    the first setpoint is the first target."""
+    target = np.asarray(target, dtype=np.float64)
+    out = np.empty_like(target)
+    prev = np.full(target.shape[1:], np.nan) if previous is None else np.array(np.broadcast_to(np.asarray(previous, dtype=np.float64), target.shape[1:]))
+    for i in range(target.shape[0]):
+        prev = np.where(np.isnan(prev), target[i], prev)
+        prev = _limited(prev, target[i], PROFILE_RAMP_RATE)
+        out[i] = prev
+    return out, prev
+
+
+def power_profile_rows(z, base=90.0, std=2.0):
+    """One whole profile per plant from its standard normals: ``z`` [T, n] (``np.random.normal(0, 1, T)`` of the runner, one column per
+    plant), ``base`` / ``std`` the load profile's base_power_percent / noise_std_percent (scalars or [n]).  Returns
+    ``(target, setpoint)``, both [T, n]: ``target`` is ``_generate_power_profile(T)`` -- base + min(0.2, std) * z clipped to
+    [20, 105], a 3-point moving average that leaves both ends alone (T >= 3), then at most 0.05 % a step -- which the runner logs as
+    target_power; ``setpoint`` is what ``_set_target_power`` gives the heat source: at most 0.02 % a step towards the target, starting
+    on it.  Every operation is the reference's, in its order, so the rows equal its own bit for bit."""
+    z = np.asarray(z, dtype=np.float64)
+    if z.ndim == 1:
+        z = z[:, None]
+    T = z.shape[0]
+    base = np.broadcast_to(np.asarray(base, dtype=np.float64), z.shape[1:])
+    s = np.minimum(PROFILE_NOISE_CAP, np.broadcast_to(np.asarray(std, dtype=np.float64), z.shape[1:]))
+    raw = np.clip(base + s * z, *PROFILE_CLIP)
+    sm = raw.copy()
+    if T >= 3:
+        sm[1:-1] = (raw[:-2] + raw[1:-1] + raw[2:]) / 3.0
+    target = sm.copy()
+    for i in range(1, T):
+        target[i] = _limited(target[i - 1], sm[i], PROFILE_RATE_LIMIT)
+    setpoint, _ = power_profile_ramp(target)
+    return target, setpoint

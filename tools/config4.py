@@ -7,6 +7,7 @@ the step loop, the histogram of per-plant oil_top_off executions and the counter
 
   python3 tools/config4.py                       # 32 768 plants on one GPU (the per-GPU share of the 262 144 of C4)
   python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 tools/config4.py --plants 262144
+  python3 tools/config4.py --profile             # the runner's own load profile and ramp, drawn on the device per plant (--steps rows)
 Counts against the CPU restatement on sampled seeds are a test (tests/test_gpu_parity.py, test_config4_*)."""
 import argparse
 import json
@@ -25,6 +26,9 @@ def main():
     ap.add_argument("--plants", type=int, default=32768, help="global number of plants (= seeds 0 .. plants-1)")
     ap.add_argument("--steps", type=int, default=120)
     ap.add_argument("--dt", type=float, default=1.0, help="minutes per step (the runner's unit)")
+    ap.add_argument("--profile", action="store_true",
+                    help="step against the data-gen runner's power profile of --steps rows, drawn on the device per plant "
+                         "(BatchedPlantEnv.action_test(power_profile_steps=...)), instead of the constant 90 %% column")
     args = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -47,11 +51,13 @@ def main():
     lo, hi = shard_range(args.plants, rank, world)
     n = hi - lo
     t0 = time.perf_counter()
-    env = BatchedPlantEnv.action_test("oil_top_off", list(range(lo, hi)), dt=args.dt, device=local_rank)
+    env = BatchedPlantEnv.action_test("oil_top_off", list(range(lo, hi)), dt=args.dt, device=local_rank,
+                                      power_profile_steps=args.steps if args.profile else None)
     torch.cuda.synchronize(dev)
     setup_s = time.perf_counter() - t0
-    # the runner ramps the heat source towards its profile; here a fixed 90 % target, the noise from the per-plant stream
-    target = torch.full((n,), 90.0, dtype=torch.float64, device=dev)
+    # the runner ramps the heat source towards its profile: with --profile the env draws that profile and ramp itself (target None:
+    # step() takes its next row); by default a fixed 90 % target.  Either way the noise comes from the per-plant stream
+    target = None if args.profile else torch.full((n,), 90.0, dtype=torch.float64, device=dev)
     for _ in range(3):
         env.step(power_setpoint=target)          # warm-up (part of the episode; the count below covers all steps)
     torch.cuda.synchronize(dev)
@@ -84,7 +90,8 @@ def main():
             "plant_env_steps_per_s": args.plants * (args.steps - 3) / loop_s, "ms_per_step": loop_s / (args.steps - 3) * 1e3,
             "oil_top_off_executions_histogram": {str(k): int(v) for k, v in enumerate(h) if v},
             "scrammed_plants": int(counters[0]), "plants_with_pump_trip": int(counters[1]),
-            "oil_top_off_executions": int(counters[2]), "work_orders_created": int(counters[3])}), flush=True)
+            "oil_top_off_executions": int(counters[2]), "work_orders_created": int(counters[3]),
+            **({"power_setpoint": "the runner's profile of %d steps, drawn on the device per plant" % args.steps} if args.profile else {})}), flush=True)
     if world > 1:
         dist.barrier(); dist.destroy_process_group()
 
