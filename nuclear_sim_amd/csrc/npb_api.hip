@@ -12,6 +12,9 @@
 #include "npb_kernels.h"
 #include "npb_noise.h"
 
+/* a side block's rows as recorded with a snapshot or a bank: a packed [rows][pitch] copy beside that arena, or NULL; its allocation */
+struct SideCopy { double *rows; size_t pitch, doubles; };
+
 struct NpbHandle {
   npb_params_t params;
   int n_plants;
@@ -28,10 +31,8 @@ struct NpbHandle {
   double *diag; size_t diag_pitch; /* npb_set_diagnostics: the caller's [NPB_DIAG_DIM][diag_pitch] buffer, or NULL */
   /* npb_carry_diagnostics: the carried rows of that buffer (include/npb.h NPB_DIAG_CARRIED) are plant state the handle takes along */
   bool diag_carry;
-  double *diag_snap;   /* npb_snapshot while carrying: the rows beside the snapshot arena ([NPB_DIAG_NUM_CARRIED][pitch], table order), or NULL */
-  double *diag_bank; size_t diag_bank_pitch, diag_bank_doubles;   /* npb_set_start_bank from a carrying handle: its rows, its pitch, the allocation */
   int32_t *maint_counts;           /* npb_set_maintenance_count_buffer: the caller's [n_plants] int32 column, or NULL */
-  npb_maint_event_t *maint_log; uint32_t *maint_log_cursor; int maint_log_capacity;   /* npb_set_maintenance_log: the caller's records and cursor, or NULL */
+  npd_maint_log_t maint_log;       /* npb_set_maintenance_log: the caller's records and cursor, or NULL; no records = no cursor and capacity 0 */
   bool maint_cache_stale;          /* the cooldown cache of the step kernels' maintenance screen must be zeroed before the next step */
   int last_kernel;                 /* NPB_KERNEL_*: what the last npb_step launched */
   int step_kernel;                 /* 0 = chosen by batch size, 1 = one-wave kernel, 2 = two-wave kernel, 3 = its two-waves-per-SIMD build, 4 = one-wave with streaming stores, 5 = four-wave kernel (npb_set_step_kernel) */
@@ -40,8 +41,9 @@ struct NpbHandle {
   /* npb_set_component_maintenance: automatic maintenance of the steam generators and the condenser in one queue with the pumps' */
   bool cm_on; npb_component_maint_table_t cm_table;
   void *cm_side;       /* [the table as the device reads it][NPB_CMAINT_SIDE_DOUBLES][pitch] doubles (npb_kernels.hip), allocated when first switched on */
-  double *cm_snap;     /* npb_snapshot with the feature on: the side state beside the snapshot arena ([NPB_CMAINT_SIDE_DOUBLES][pitch]), or NULL */
-  double *cm_bank; size_t cm_bank_pitch, cm_bank_doubles;   /* npb_set_start_bank from a handle with the feature on: its side state, its pitch, the allocation */
+  /* the side blocks (g_side below) as npb_snapshot recorded them from this handle and as npb_set_start_bank did from the bank handle, in
+   * that handle's pitch */
+  struct { SideCopy snap, bank; } side[NPB_SIDE_COUNT];
   void *snap;          /* npb_snapshot: the episode-start arena, the arena's layout, or NULL */
   int32_t *ep_len; double *ep_ret; /* npb_set_autoreset: carried steps / summed reward of each plant's running episode ([pitch] each), or NULL */
   int32_t *ep_index;   /* with them: the number of each plant's running episode ([pitch]), bumped wherever ep_len is zeroed */
@@ -123,40 +125,91 @@ static npb_source_t source_of(const NpbHandle *h, bool bank) {
   S.next_slot = h->next_slot; S.episode_start = h->slot_start; S.advance = h->slot_advance; S.start = h->ep_start; S.out_start = h->ep_out_start;
   return S;
 }
+static double *cm_state(const NpbHandle *h) { return (double *)((char *)h->cm_side + npb_launch_cmaint_state_offset()); }
+
+/* ---- side blocks: per-plant fp64 rows that belong to a plant's state and live beside the arena (npb_kernels.h).  Every episode path takes
+ * them along through this one table: npb_snapshot and npb_set_start_bank record them, npb_restore, npb_restore_bank and the autoreset of
+ * npb_step put them back.  A further block is an entry here and its copy loop in npd_restore_lanes (npb_kernels.hip). */
+struct SideBlock {
+  int rows;                                           /* per plant */
+  bool (*on)(const NpbHandle *h);
+  hipError_t (*pack)(const NpbHandle *h, double *packed, hipStream_t stream);   /* h's live rows into a packed [rows][h->pitch] copy */
+  npb_side_restore_t (*live)(const NpbHandle *h);     /* where a restore puts them: the live rows and their pitch */
+  const char *no_snapshot, *no_bank;                  /* the block is on and the snapshot / the bank was recorded without it */
+  const char *bank_lacks;                             /* npb_set_start_bank: this handle has it and the bank handle has not */
+  const char *snapshot_nomem, *bank_nomem;            /* hipMalloc of the copy failed */
+};
+static const SideBlock g_side[NPB_SIDE_COUNT] = {
+  /* NPB_SIDE_CMAINT: the generators' and the condenser's stamps and open orders belong to the episode start as the mpump section does */
+  { NPB_CMAINT_SIDE_DOUBLES,
+    [](const NpbHandle *h) { return h->cm_on; },
+    [](const NpbHandle *h, double *packed, hipStream_t stream) {
+      return hipMemcpyAsync(packed, cm_state(h), (size_t)NPB_CMAINT_SIDE_DOUBLES * h->pitch * sizeof(double), hipMemcpyDeviceToDevice, stream); },
+    [](const NpbHandle *h) { return npb_side_restore_t{cm_state(h), nullptr, h->pitch, 0}; },
+    "the component maintenance is on (npb_set_component_maintenance) and the snapshot was taken without it: npb_snapshot again",
+    "the component maintenance is on (npb_set_component_maintenance) and the start bank was set without it: npb_set_start_bank again, from a handle that has it",
+    "npb_set_start_bank: this handle has the component maintenance on (npb_set_component_maintenance) and the bank handle has not",
+    "npb_snapshot: hipMalloc of the component maintenance's snapshot failed",
+    "npb_set_start_bank: hipMalloc of the bank's component maintenance state failed" },
+  /* NPB_SIDE_DIAG: the carried rows of the caller's diagnostics buffer (accumulators, latches, ejector values), packed in table order */
+  { NPB_DIAG_NUM_CARRIED,
+    [](const NpbHandle *h) { return h->diag_carry; },
+    [](const NpbHandle *h, double *packed, hipStream_t stream) {
+      npb_launch_diag_carried_pack(h->diag, h->diag_pitch, packed, h->pitch, h->pitch, stream);
+      return hipGetLastError(); },
+    [](const NpbHandle *h) { return npb_side_restore_t{h->diag, nullptr, h->diag_pitch, 0}; },
+    "the diagnostics rows are carried (npb_carry_diagnostics) and the snapshot was taken without them: npb_snapshot again",
+    "the diagnostics rows are carried (npb_carry_diagnostics) and the start bank was set without them: npb_set_start_bank again, from a handle that carries them",
+    "npb_set_start_bank: this handle carries the diagnostics rows (npb_carry_diagnostics) and the bank handle does not",
+    "npb_snapshot: hipMalloc of the carried diagnostics rows' snapshot failed",
+    "npb_set_start_bank: hipMalloc of the bank's carried diagnostics rows failed" },
+};
+static void side_free(SideCopy *c) {
+  if (c->rows) (void)hipFree(c->rows);
+  *c = SideCopy{};
+}
+/* npb_snapshot (src = h, bank false) / npb_set_start_bank: block b of src into h's snapshot or bank copy, in src's pitch.  A source that
+ * has the block off leaves no copy: an older one does not belong to this snapshot or bank */
+static int side_record(NpbHandle *h, int b, bool bank, const NpbHandle *src, hipStream_t stream) {
+  const SideBlock &B = g_side[b];
+  SideCopy *c = bank ? &h->side[b].bank : &h->side[b].snap;
+  if (!B.on(src)) {
+    if (c->rows) { NPB_HIP(h, hipStreamSynchronize(stream)); side_free(c); }
+    return NPB_OK;
+  }
+  const size_t doubles = (size_t)B.rows * src->pitch;
+  if (doubles > c->doubles) {
+    side_free(c);
+    hipError_t e = hipMalloc((void **)&c->rows, doubles * sizeof(double));
+    if (e != hipSuccess) { c->rows = nullptr; return fail(h, NPB_EHIP, bank ? B.bank_nomem : B.snapshot_nomem, e); }
+    c->doubles = doubles;
+  }
+  NPB_HIP(h, B.pack(src, c->rows, stream));
+  c->pitch = src->pitch;
+  return NPB_OK;
+}
+/* what a restore from the snapshot or the bank takes along beside the arena.  Returns the first block, in table order or with the last
+ * block first, that is on while the source was recorded without it (side_refusal has the message), or -1 */
+static int side_restores_of(const NpbHandle *h, bool bank, bool last_first, npb_side_restores_t *out) {
+  *out = npb_side_restores_t{};
+  for (int i = 0; i < NPB_SIDE_COUNT; i++) {
+    const int b = last_first ? NPB_SIDE_COUNT - 1 - i : i;
+    if (!g_side[b].on(h)) continue;
+    const SideCopy &c = bank ? h->side[b].bank : h->side[b].snap;
+    if (!c.rows) return b;
+    out->block[b] = g_side[b].live(h);
+    out->block[b].src = c.rows; out->block[b].src_pitch = c.pitch;
+  }
+  return -1;
+}
+static const char *side_refusal(int b, bool bank) { return bank ? g_side[b].no_bank : g_side[b].no_snapshot; }
 /* npb_reset / npb_reset_reference (counters) and npb_restore: the episode counters (with counters) and the carried start entries of the
  * plants of mask (NULL = every lane of the pitch) to 0 and -1 */
-/* the component maintenance's side state as a restore takes it along (npb_kernels.h): from the snapshot's copy or the bank's.  false = the
- * feature is on and the source was recorded without it */
-static double *cm_state(const NpbHandle *h) { return (double *)((char *)h->cm_side + npb_launch_cmaint_state_offset()); }
-static bool cm_restore_of(const NpbHandle *h, bool bank, npb_cmaint_restore_t *cm) {
-  *cm = npb_cmaint_restore_t{};
-  if (!h->cm_on) return true;
-  const double *src = bank ? h->cm_bank : h->cm_snap;
-  if (!src) return false;
-  cm->state = cm_state(h); cm->src = src; cm->pitch = h->pitch; cm->src_pitch = bank ? h->cm_bank_pitch : h->pitch;
-  return true;
-}
-static const char *const g_cm_no_snapshot = "the component maintenance is on (npb_set_component_maintenance) and the snapshot was taken without it: npb_snapshot again";
-static const char *const g_cm_no_bank = "the component maintenance is on (npb_set_component_maintenance) and the start bank was set without it: npb_set_start_bank again, "
-                                        "from a handle that has it";
 static void clear_episodes(NpbHandle *h, const uint8_t *mask, bool counters, hipStream_t stream) {
   int32_t *len = counters ? h->ep_len : nullptr;
   if (len || h->ep_start) npb_launch_episode_clear(mask, len, counters ? h->ep_ret : nullptr, h->ep_index, h->ep_start, h->n_plants, h->pitch, stream);
 }
 static npb_episode_counters_t counters_of(const NpbHandle *h) { return npb_episode_counters_t{h->ep_len, h->ep_ret, h->ep_index, h->ep_out_index}; }
-/* the carried diagnostics rows as a restore takes them along (npb_kernels.h): from the snapshot's copy or the bank's.  false = carrying
- * is on and the source was recorded without the rows */
-static bool diag_restore_of(const NpbHandle *h, bool bank, npb_diag_restore_t *dg) {
-  *dg = npb_diag_restore_t{};
-  if (!h->diag_carry) return true;
-  const double *src = bank ? h->diag_bank : h->diag_snap;
-  if (!src) return false;
-  dg->buf = h->diag; dg->src = src; dg->pitch = h->diag_pitch; dg->src_pitch = bank ? h->diag_bank_pitch : h->pitch;
-  return true;
-}
-static const char *const g_diag_no_snapshot = "the diagnostics rows are carried (npb_carry_diagnostics) and the snapshot was taken without them: npb_snapshot again";
-static const char *const g_diag_no_bank = "the diagnostics rows are carried (npb_carry_diagnostics) and the start bank was set without them: npb_set_start_bank again, "
-                                          "from a handle that carries them";
 static const struct { int row; double fresh; } g_diag_carried[] = {
 #define NPB__X(row, fresh) {row, fresh},
   NPB_DIAG_CARRIED(NPB__X)
@@ -189,10 +242,12 @@ static void probe_placement(NpbHandle *h, size_t step_columns) {
   /* the clocks first: after an idle period the step kernel needs ~170 launches to reach its steady time (bench.py,
    * "preconditioning"), and the first candidate would otherwise be timed on the ramp -- a 5-7 % bias against it, half of
    * the effect being selected on.  Untimed launches on candidate 0 until ~20 ms have passed. */
-  h->K->init(&h->params, h->n_plants, NPB_N(h), cand[0], nullptr, nullptr);
-  for (int k = 0; k < 200; k++)
-    (void)h->K->step(&h->params, h->n_plants, NPB_N(h), cand[0], nullptr, nullptr, nullptr, nullptr, nullptr,
+  const auto step = [h](void *arena) {      /* no inputs, no outputs, no diagnostics, no maintenance */
+    (void)h->K->step(&h->params, h->n_plants, NPB_N(h), arena, nullptr, nullptr, nullptr, nullptr, nullptr,
                      nullptr, nullptr, nullptr, nullptr, nullptr, h->step_kernel, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
+  };
+  h->K->init(&h->params, h->n_plants, NPB_N(h), cand[0], nullptr, nullptr);
+  for (int k = 0; k < 200; k++) step(cand[0]);
   if (hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); (void)hipEventDestroy(a); (void)hipEventDestroy(b); return; }
   int n = 0;
   for (; n < max_candidates; n++) {
@@ -201,8 +256,7 @@ static void probe_placement(NpbHandle *h, size_t step_columns) {
     float best = 1e30f;
     for (int k = 0; k < launches; k++) {
       (void)hipEventRecord(a, nullptr);
-      (void)h->K->step(&h->params, h->n_plants, NPB_N(h), cand[n], nullptr, nullptr, nullptr, nullptr, nullptr,
-                       nullptr, nullptr, nullptr, nullptr, nullptr, h->step_kernel, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
+      step(cand[n]);
       (void)hipEventRecord(b, nullptr);
       if (hipEventSynchronize(b) != hipSuccess) { best = 1e30f; break; }
       float t = 0;
@@ -365,10 +419,7 @@ int npb_destroy(NpbHandle *h) {
   if (h->plan_dev) (void)hipFree(h->plan_dev);
   if (h->snap) (void)hipFree(h->snap);
   if (h->cm_side) (void)hipFree(h->cm_side);
-  if (h->cm_snap) (void)hipFree(h->cm_snap);
-  if (h->cm_bank) (void)hipFree(h->cm_bank);
-  if (h->diag_snap) (void)hipFree(h->diag_snap);
-  if (h->diag_bank) (void)hipFree(h->diag_bank);
+  for (auto &sd : h->side) { side_free(&sd.snap); side_free(&sd.bank); }
   if (h->ep_len) (void)hipFree(h->ep_len);
   if (h->bank) (void)hipFree(h->bank);
   if (h->ep_start) (void)hipFree(h->ep_start);
@@ -481,9 +532,7 @@ int npb_set_maintenance_log(NpbHandle *h, void *records, int capacity, uint32_t 
   if (records && !cursor) return fail(h, NPB_EINVAL, "npb_set_maintenance_log: records without a cursor");
   if (!records && capacity > 0) return fail(h, NPB_EINVAL, "npb_set_maintenance_log: a capacity without records");
   if (((uintptr_t)records & 7u) || ((uintptr_t)cursor & 3u)) return fail(h, NPB_EINVAL, "npb_set_maintenance_log: records must be 8-byte and the cursor 4-byte aligned");
-  h->maint_log = (npb_maint_event_t *)records;
-  h->maint_log_cursor = records ? cursor : nullptr;
-  h->maint_log_capacity = records ? capacity : 0;
+  h->maint_log = npd_maint_log_t{(npb_maint_event_t *)records, records ? cursor : nullptr, records ? capacity : 0};
   h->maint_cache_stale = true;     /* the log's descriptor travels with the rule's constants: uploaded before the next step */
   return NPB_OK;
 }
@@ -500,8 +549,7 @@ int npb_perform_maintenance(NpbHandle *h, const int32_t *action, const int32_t *
    * fresh from the pump phase's registers at every step (npd_maint_pump_hit).  Nor does the caller's count column move: an operator
    * action is not counted in maintenance_actions_performed.  The log's descriptor travels as a kernel argument, so the call does not
    * depend on the rule's constants having been uploaded (they are only with params.maint_enabled). */
-  h->K->operator_maint(h->n_plants, NPB_N(h), h->f64, action, pump, bearing, target_level, success, h->maint_log, h->maint_log_cursor,
-                       h->maint_log_capacity, (hipStream_t)stream);
+  h->K->operator_maint(h->n_plants, NPB_N(h), h->f64, action, pump, bearing, target_level, success, h->maint_log, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -516,8 +564,8 @@ int npb_perform_component_maintenance(NpbHandle *h, const int32_t *action, const
    * npb_perform_maintenance: no handler here writes a pump, a stamp or the table. */
   const unsigned kinds = h->params.mode == NPB_MODE_FULL ? 0xfu
                        : h->params.mode == NPB_MODE_PRIMARY_SG ? (1u << NPB_COMPONENT_SG) | (1u << NPB_COMPONENT_SGSYS) : 0u;
-  h->K->operator_component_maint(h->n_plants, NPB_N(h), h->f64, action, unit, option, amount, success, kinds, h->maint_log, h->maint_log_cursor,
-                                 h->maint_log_capacity, (hipStream_t)stream);
+  h->K->operator_component_maint(h->n_plants, NPB_N(h), h->f64, action, unit, option, amount, success, kinds, h->maint_log,
+                                 (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -528,8 +576,8 @@ int npb_perform_turbine_maintenance(NpbHandle *h, const int32_t *action, const i
   NPB_USE_DEVICE(h);
   /* only the full plant steps the turbine: without its secondary side the reference has no object to call, and primary + steam generators
    * carries no turbine.  maint_cache_stale is left alone, as in npb_perform_maintenance: no handler here writes a pump, a stamp or the table. */
-  h->K->operator_turbine_maint(h->n_plants, NPB_N(h), h->f64, action, unit, success, h->params.mode == NPB_MODE_FULL, h->maint_log, h->maint_log_cursor,
-                               h->maint_log_capacity, (hipStream_t)stream);
+  h->K->operator_turbine_maint(h->n_plants, NPB_N(h), h->f64, action, unit, success, h->params.mode == NPB_MODE_FULL, h->maint_log,
+                               (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -736,16 +784,15 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
     return fail(h, NPB_EINVAL, "npb_step: autoreset is on (npb_set_autoreset) and needs the done column: it must not be NULL");
   if (h->params.heat_source == NPB_HEAT_EXTERNAL && !noise_z)      /* a NULL column would read as 0 MW thermal, silently */
     return fail(h, NPB_EINVAL, "npb_step: params.heat_source is NPB_HEAT_EXTERNAL, whose thermal power arrives in the noise_z column (include/npb_params.h): it must not be NULL");
-  npb_cmaint_restore_t cm = {};      /* what the autoreset's restores take along beside the arena */
-  npb_diag_restore_t dg = {};
-  if (h->autoreset && !diag_restore_of(h, h->bank && h->next_slot, &dg))
-    return fail(h, NPB_EINVAL, h->bank && h->next_slot ? g_diag_no_bank : g_diag_no_snapshot);
-  if (h->cm_on) {
-    if (!h->params.maint_enabled || h->params.mode != NPB_MODE_FULL)
-      return fail(h, NPB_EINVAL, "npb_step: the component maintenance is on (npb_set_component_maintenance) and needs params.maint_enabled and the full mode");
-    if (h->autoreset && !cm_restore_of(h, h->bank && h->next_slot, &cm))
-      return fail(h, NPB_EINVAL, h->bank && h->next_slot ? g_cm_no_bank : g_cm_no_snapshot);
-  }
+  /* what the autoreset's restores take along beside the arena, from the bank while it has slots, else from the snapshot.  The step
+   * reports a source without the diagnostics rows first, then the component maintenance's own needs, then a source without its state */
+  const bool from_bank = h->bank && h->next_slot;
+  npb_side_restores_t side = {};
+  const int refused = h->autoreset ? side_restores_of(h, from_bank, true, &side) : -1;
+  if (refused == NPB_SIDE_DIAG) return fail(h, NPB_EINVAL, side_refusal(refused, from_bank));
+  if (h->cm_on && (!h->params.maint_enabled || h->params.mode != NPB_MODE_FULL))
+    return fail(h, NPB_EINVAL, "npb_step: the component maintenance is on (npb_set_component_maintenance) and needs params.maint_enabled and the full mode");
+  if (refused >= 0) return fail(h, NPB_EINVAL, side_refusal(refused, from_bank));
   NPB_USE_DEVICE(h);
   npb_maint_table_t table;
   const bool maint = h->params.maint_enabled != 0;
@@ -760,7 +807,7 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
       /* parameters, table, state or clock may have changed since the last step: the rule's constants go to the device anew and
        * the screen's cooldown cache is zeroed (= nothing known: every wave is looked at once and its entries rebuilt) */
       h->maint_consts_host.resize(npb_launch_maint_consts_bytes());
-      npb_launch_maint_consts(&h->params, &table, h->maint_log, h->maint_log_cursor, h->maint_log_capacity, h->maint_consts_host.data());
+      npb_launch_maint_consts(&h->params, &table, h->maint_log, h->maint_consts_host.data());
       NPB_HIP(h, hipMemcpyAsync(h->maint_side, h->maint_consts_host.data(), h->maint_consts_host.size(), hipMemcpyHostToDevice, (hipStream_t)stream));
       NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));      /* the host copy may change again before an asynchronous copy would read it */
       NPB_HIP(h, hipMemsetAsync((char *)h->maint_side + npb_launch_maint_cache_offset(), 0, npb_launch_maint_side_bytes(h->pitch) - npb_launch_maint_cache_offset(),
@@ -780,10 +827,10 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
     h->K->maint_all(NPB_N(h), h->f64, h->maint_side, h->cm_side, h->maint_counts, h->n_plants, h->diag, h->diag_pitch, (hipStream_t)stream);
   else if (maint && h->params.mode != NPB_MODE_FULL)   /* a full-mode step kernel has run the rule itself, for the waves whose pump phase found something */
     h->K->maint(NPB_N(h), h->f64, h->maint_side, h->maint_counts, h->n_plants, (hipStream_t)stream);
-  if (h->autoreset)   /* from the bank while it has slots, else from the snapshot; same stream, nothing read back, the maintenance cache kept per plant by the kernel itself */
-    h->K->episode(h->params.mode, h->n_plants, NPB_N(h), h->f64, source_of(h, h->bank && h->next_slot), done, reward, obs, counters_of(h),
+  if (h->autoreset)   /* same stream, nothing read back, the maintenance cache kept per plant by the kernel itself */
+    h->K->episode(h->params.mode, h->n_plants, NPB_N(h), h->f64, source_of(h, from_bank), done, reward, obs, counters_of(h),
                   h->ep_out_len, h->ep_out_ret, h->ep_out_truncated, h->ep_final_obs, h->max_episode_steps,
-                  maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, cm, dg, (hipStream_t)stream);
+                  maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, side, (hipStream_t)stream);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, NPB_EHIP, "npb_step: kernel launch failed", e);
   return NPB_OK;
@@ -798,45 +845,28 @@ int npb_snapshot(NpbHandle *h, void *stream) {
     if (e != hipSuccess) { h->snap = nullptr; return fail(h, NPB_EHIP, "npb_snapshot: hipMalloc of the snapshot arena failed", e); }
   }
   NPB_HIP(h, hipMemcpyAsync(h->snap, h->f64, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  if (h->cm_on) {      /* the generators' and the condenser's stamps and open orders belong to the episode start as the mpump section does */
-    const size_t cm_bytes = (size_t)NPB_CMAINT_SIDE_DOUBLES * h->pitch * sizeof(double);
-    if (!h->cm_snap) {
-      hipError_t e = hipMalloc((void **)&h->cm_snap, cm_bytes);
-      if (e != hipSuccess) { h->cm_snap = nullptr; return fail(h, NPB_EHIP, "npb_snapshot: hipMalloc of the component maintenance's snapshot failed", e); }
-    }
-    NPB_HIP(h, hipMemcpyAsync(h->cm_snap, cm_state(h), cm_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  } else if (h->cm_snap) {      /* a snapshot without the feature: the older side snapshot does not belong to it */
-    NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
-    (void)hipFree(h->cm_snap); h->cm_snap = nullptr;
-  }
-  if (h->diag_carry) {      /* the carried diagnostics rows belong to the episode start too */
-    if (!h->diag_snap) {
-      hipError_t e = hipMalloc((void **)&h->diag_snap, (size_t)NPB_DIAG_NUM_CARRIED * h->pitch * sizeof(double));
-      if (e != hipSuccess) { h->diag_snap = nullptr; return fail(h, NPB_EHIP, "npb_snapshot: hipMalloc of the carried diagnostics rows' snapshot failed", e); }
-    }
-    npb_launch_diag_carried_pack(h->diag, h->diag_pitch, h->diag_snap, h->pitch, h->pitch, (hipStream_t)stream);
-    NPB_HIP(h, hipGetLastError());
-  } else if (h->diag_snap) {      /* a snapshot without them: the older copy does not belong to it */
-    NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
-    (void)hipFree(h->diag_snap); h->diag_snap = nullptr;
-  }
+  for (int b = 0; b < NPB_SIDE_COUNT; b++)      /* the side blocks belong to the episode start too */
+    if (int rc = side_record(h, b, false, h, (hipStream_t)stream)) return rc;
+  return NPB_OK;
+}
+
+/* npb_restore / npb_restore_bank: the plants of mask from the snapshot or from their bank entries, the side blocks with them */
+static int restore_from(NpbHandle *h, bool bank, const uint8_t *mask, hipStream_t stream) {
+  npb_side_restores_t side;
+  if (const int b = side_restores_of(h, bank, false, &side); b >= 0) return fail(h, NPB_EINVAL, side_refusal(b, bank));
+  NPB_USE_DEVICE(h);
+  const bool maint = h->params.maint_enabled != 0;
+  h->K->restore(h->n_plants, NPB_N(h), h->f64, source_of(h, bank), mask, counters_of(h),
+                maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, side, stream);
+  if (!bank) clear_episodes(h, mask, false, stream);     /* the restored episodes are not from the bank */
+  NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
 
 int npb_restore(NpbHandle *h, const uint8_t *mask, void *stream) {
   if (!h) return NPB_EINVAL;
   if (!h->snap) return fail(h, NPB_EINVAL, "npb_restore: no snapshot (npb_snapshot) to restore from");
-  npb_cmaint_restore_t cm;
-  if (!cm_restore_of(h, false, &cm)) return fail(h, NPB_EINVAL, g_cm_no_snapshot);
-  npb_diag_restore_t dg;
-  if (!diag_restore_of(h, false, &dg)) return fail(h, NPB_EINVAL, g_diag_no_snapshot);
-  NPB_USE_DEVICE(h);
-  const bool maint = h->params.maint_enabled != 0;
-  h->K->restore(h->n_plants, NPB_N(h), h->f64, source_of(h, false), mask, counters_of(h),
-                maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, cm, dg, (hipStream_t)stream);
-  clear_episodes(h, mask, false, (hipStream_t)stream);     /* the restored episodes are not from the bank */
-  NPB_HIP(h, hipGetLastError());
-  return NPB_OK;
+  return restore_from(h, false, mask, (hipStream_t)stream);
 }
 
 int npb_set_autoreset(NpbHandle *h, int enabled, int max_episode_steps) {
@@ -847,9 +877,12 @@ int npb_set_autoreset(NpbHandle *h, int enabled, int max_episode_steps) {
     return fail(h, NPB_EINVAL, "npb_set_autoreset: no snapshot (npb_snapshot), nor a start bank with slots (npb_set_start_bank, npb_set_start_slots), to reset to");
   if (h->diag && !h->diag_carry)
     return fail(h, NPB_EINVAL, "npb_set_autoreset: diagnostics are on (npb_set_diagnostics); their buffer carries plant state the snapshot does not hold");
-  if (h->diag_carry) {      /* the source the autoreset will restore from must hold the rows */
+  /* The source the autoreset will restore from must hold the diagnostics rows: that is refused here, at once and in this function's
+   * own two texts.  A source without the component maintenance's state is refused only by the next npb_step (side_restores_of).  Both
+   * are as callers know them: not to be evened out */
+  if (h->diag_carry) {
     const bool bank = h->bank && h->next_slot;
-    if (!(bank ? h->diag_bank : h->diag_snap))
+    if (!(bank ? h->side[NPB_SIDE_DIAG].bank : h->side[NPB_SIDE_DIAG].snap).rows)
       return fail(h, NPB_EINVAL, bank ? "npb_set_autoreset: diagnostics are on and their rows carried (npb_carry_diagnostics), but the start bank was set without "
                                         "them: npb_set_start_bank again, from a handle that carries them"
                                       : "npb_set_autoreset: diagnostics are on and their rows carried (npb_carry_diagnostics), but the snapshot was taken "
@@ -891,16 +924,11 @@ int npb_set_start_bank(NpbHandle *h, const NpbHandle *src, void *stream) {
     if (h->bank) (void)hipFree(h->bank);
     if (h->ep_start) (void)hipFree(h->ep_start);
     h->bank = nullptr; h->bank_bytes = 0; h->bank_N = 0; h->bank_M = 0; h->ep_start = nullptr;
-    if (h->cm_bank) (void)hipFree(h->cm_bank);
-    h->cm_bank = nullptr; h->cm_bank_pitch = 0; h->cm_bank_doubles = 0;
-    if (h->diag_bank) (void)hipFree(h->diag_bank);
-    h->diag_bank = nullptr; h->diag_bank_pitch = 0; h->diag_bank_doubles = 0;
+    for (auto &sd : h->side) side_free(&sd.bank);
     return NPB_OK;
   }
-  if (h->diag_carry && !src->diag_carry)      /* its entries would come without the accumulators, latches and ejector values of the diagnostics */
-    return fail(h, NPB_EINVAL, "npb_set_start_bank: this handle carries the diagnostics rows (npb_carry_diagnostics) and the bank handle does not");
-  if (h->cm_on && !src->cm_on)      /* its entries would come without stamps and open orders of the generators and the condenser */
-    return fail(h, NPB_EINVAL, "npb_set_start_bank: this handle has the component maintenance on (npb_set_component_maintenance) and the bank handle has not");
+  for (int b = NPB_SIDE_COUNT - 1; b >= 0; b--)      /* the bank's entries would come without the block's rows; the last block is reported first */
+    if (g_side[b].on(h) && !g_side[b].on(src)) return fail(h, NPB_EINVAL, g_side[b].bank_lacks);
   if (src->storage != h->storage)
     return fail(h, NPB_EINVAL, "npb_set_start_bank: the bank handle's storage type differs from this handle's (npb_create_storage)");
   if (src->device != h->device)
@@ -920,37 +948,8 @@ int npb_set_start_bank(NpbHandle *h, const NpbHandle *src, void *stream) {
   }
   NPB_HIP(h, hipMemcpyAsync(h->bank, src->f64, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   h->bank_N = NPB_N(src); h->bank_M = src->n_plants;
-  if (src->cm_on) {      /* the bank's side state beside its arena, in the bank handle's pitch */
-    const size_t doubles = (size_t)NPB_CMAINT_SIDE_DOUBLES * src->pitch;
-    if (doubles > h->cm_bank_doubles) {
-      if (h->cm_bank) (void)hipFree(h->cm_bank);
-      h->cm_bank = nullptr; h->cm_bank_doubles = 0;
-      hipError_t e = hipMalloc((void **)&h->cm_bank, doubles * sizeof(double));
-      if (e != hipSuccess) { h->cm_bank = nullptr; return fail(h, NPB_EHIP, "npb_set_start_bank: hipMalloc of the bank's component maintenance state failed", e); }
-      h->cm_bank_doubles = doubles;
-    }
-    NPB_HIP(h, hipMemcpyAsync(h->cm_bank, cm_state(src), doubles * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    h->cm_bank_pitch = src->pitch;
-  } else if (h->cm_bank) {
-    NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
-    (void)hipFree(h->cm_bank); h->cm_bank = nullptr; h->cm_bank_pitch = 0; h->cm_bank_doubles = 0;
-  }
-  if (src->diag_carry) {      /* the bank handle's live carried rows beside its arena, in its pitch */
-    const size_t doubles = (size_t)NPB_DIAG_NUM_CARRIED * src->pitch;
-    if (doubles > h->diag_bank_doubles) {
-      if (h->diag_bank) (void)hipFree(h->diag_bank);
-      h->diag_bank = nullptr; h->diag_bank_doubles = 0;
-      hipError_t e = hipMalloc((void **)&h->diag_bank, doubles * sizeof(double));
-      if (e != hipSuccess) { h->diag_bank = nullptr; return fail(h, NPB_EHIP, "npb_set_start_bank: hipMalloc of the bank's carried diagnostics rows failed", e); }
-      h->diag_bank_doubles = doubles;
-    }
-    npb_launch_diag_carried_pack(src->diag, src->diag_pitch, h->diag_bank, src->pitch, src->pitch, (hipStream_t)stream);
-    NPB_HIP(h, hipGetLastError());
-    h->diag_bank_pitch = src->pitch;
-  } else if (h->diag_bank) {
-    NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
-    (void)hipFree(h->diag_bank); h->diag_bank = nullptr; h->diag_bank_pitch = 0; h->diag_bank_doubles = 0;
-  }
+  for (int b = 0; b < NPB_SIDE_COUNT; b++)      /* the bank handle's side blocks beside its arena, in its pitch */
+    if (int rc = side_record(h, b, true, src, (hipStream_t)stream)) return rc;
   return NPB_OK;
 }
 
@@ -965,16 +964,7 @@ int npb_set_start_slots(NpbHandle *h, int32_t *next_slot, int32_t *episode_start
 int npb_restore_bank(NpbHandle *h, const uint8_t *mask, void *stream) {
   if (!h) return NPB_EINVAL;
   if (!h->bank || !h->next_slot) return fail(h, NPB_EINVAL, "npb_restore_bank: no start bank (npb_set_start_bank) with slots (npb_set_start_slots) to restore from");
-  npb_cmaint_restore_t cm;
-  if (!cm_restore_of(h, true, &cm)) return fail(h, NPB_EINVAL, g_cm_no_bank);
-  npb_diag_restore_t dg;
-  if (!diag_restore_of(h, true, &dg)) return fail(h, NPB_EINVAL, g_diag_no_bank);
-  NPB_USE_DEVICE(h);
-  const bool maint = h->params.maint_enabled != 0;
-  h->K->restore(h->n_plants, NPB_N(h), h->f64, source_of(h, true), mask, counters_of(h),
-                maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, cm, dg, (hipStream_t)stream);
-  NPB_HIP(h, hipGetLastError());
-  return NPB_OK;
+  return restore_from(h, true, mask, (hipStream_t)stream);
 }
 
 int npb_set_episode_start_buffer(NpbHandle *h, int32_t *out_start) {
@@ -983,10 +973,53 @@ int npb_set_episode_start_buffer(NpbHandle *h, int32_t *out_start) {
   return NPB_OK;
 }
 
+/* ---- the Mersenne-Twister generators (npb_noise_t: the heat-source noise's and the power profile's), between the device's [624][pitch]
+ * key columns and numpy's get_state() layout, [n][624]; `who` = the ABI entry, for the messages */
+static int fail_who(NpbHandle *h, const char *who, const char *what) { return fail(h, NPB_EINVAL, (std::string(who) + what).c_str()); }
+static int seeds_narrow(NpbHandle *h, const char *who, const int64_t *seeds, uint32_t *s32) {
+  for (int p = 0; p < h->n_plants; p++) {
+    if (seeds[p] < 0 || seeds[p] > (int64_t)0xffffffffLL) return fail_who(h, who, ": a seed is outside [0, 2^32), which numpy.random.RandomState refuses");
+    s32[p] = (uint32_t)seeds[p];
+  }
+  return NPB_OK;
+}
+static int mt_state_check(NpbHandle *h, const char *who, const int32_t *pos, const int32_t *has_gauss) {
+  for (int p = 0; p < h->n_plants; p++) {
+    if (pos[p] < 0 || pos[p] > NPB_MT_N) return fail_who(h, who, ": pos outside [0, 624]");
+    if (has_gauss[p] != 0 && has_gauss[p] != 1) return fail_who(h, who, ": has_gauss outside {0, 1}");
+  }
+  return NPB_OK;
+}
+/* both wait for the stream: the staging rows and the caller's buffers are in use until the copies are done */
+static int mt_state_download(NpbHandle *h, const npb_noise_t &g, uint32_t *key, int32_t *pos, int32_t *has_gauss, double *cached, hipStream_t st) {
+  const size_t n = (size_t)h->n_plants;
+  std::vector<uint32_t> rows((size_t)NPB_MT_N * n);
+  NPB_HIP(h, hipMemcpy2DAsync(rows.data(), n * sizeof(uint32_t), g.key, h->pitch * sizeof(uint32_t), n * sizeof(uint32_t), NPB_MT_N, hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpyAsync(pos, g.pos, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpyAsync(has_gauss, g.has_gauss, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpyAsync(cached, g.gauss, n * sizeof(double), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipStreamSynchronize(st));
+  for (size_t i = 0; i < (size_t)NPB_MT_N; i++)
+    for (size_t p = 0; p < n; p++) key[p * NPB_MT_N + i] = rows[i * n + p];
+  return NPB_OK;
+}
+static int mt_state_upload(NpbHandle *h, const npb_noise_t &g, const uint32_t *key, const int32_t *pos, const int32_t *has_gauss, const double *cached, hipStream_t st) {
+  const size_t n = (size_t)h->n_plants;
+  std::vector<uint32_t> rows((size_t)NPB_MT_N * n);
+  for (size_t i = 0; i < (size_t)NPB_MT_N; i++)
+    for (size_t p = 0; p < n; p++) rows[i * n + p] = key[p * NPB_MT_N + i];
+  NPB_HIP(h, hipMemcpy2DAsync(g.key, h->pitch * sizeof(uint32_t), rows.data(), n * sizeof(uint32_t), n * sizeof(uint32_t), NPB_MT_N, hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(g.pos, pos, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(g.has_gauss, has_gauss, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(g.gauss, cached, n * sizeof(double), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipStreamSynchronize(st));
+  return NPB_OK;
+}
+
 static int noise_alloc(NpbHandle *h, const char *who) {
   if (h->noise) return NPB_OK;
   hipError_t e = hipMalloc(&h->noise, npb_noise_bytes(h->pitch));
-  if (e != hipSuccess) { h->noise = nullptr; std::string m = who; m += ": hipMalloc of the noise generators failed"; return fail(h, NPB_EHIP, m.c_str(), e); }
+  if (e != hipSuccess) { h->noise = nullptr; return fail(h, NPB_EHIP, (std::string(who) + ": hipMalloc of the noise generators failed").c_str(), e); }
   h->noise_g = npb_noise_layout(h->noise, h->pitch);
   return NPB_OK;
 }
@@ -1001,11 +1034,7 @@ int npb_noise_seed(NpbHandle *h, const int64_t *seeds, void *stream) {
   }
   const int n = h->n_plants;
   std::vector<uint32_t> s32((size_t)n);
-  for (int p = 0; p < n; p++) {
-    if (seeds[p] < 0 || seeds[p] > (int64_t)0xffffffffLL)
-      return fail(h, NPB_EINVAL, "npb_noise_seed: a seed is outside [0, 2^32), which numpy.random.RandomState refuses");
-    s32[p] = (uint32_t)seeds[p];
-  }
+  if (int rc = seeds_narrow(h, "npb_noise_seed", seeds, s32.data())) return rc;
   if (int rc = noise_alloc(h, "npb_noise_seed")) return rc;
   /* the seeds travel in the pos column, which the seed kernel then overwrites */
   NPB_HIP(h, hipMemcpyAsync(h->noise_g.pos, s32.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, (hipStream_t)stream));
@@ -1031,39 +1060,16 @@ int npb_noise_get_state(NpbHandle *h, uint32_t *key, int32_t *pos, int32_t *has_
   if (!h->noise) return fail(h, NPB_EINVAL, "npb_noise_get_state: no noise generators (npb_noise_seed or npb_noise_set_state first)");
   if (!key || !pos || !has_gauss || !cached) return fail(h, NPB_EINVAL, "npb_noise_get_state: NULL output");
   NPB_USE_DEVICE(h);
-  const size_t n = (size_t)h->n_plants, pitch = h->pitch;
-  std::vector<uint32_t> rows((size_t)NPB_MT_N * n);     /* [624][n], then transposed to numpy's [n][624] */
-  hipStream_t st = (hipStream_t)stream;
-  NPB_HIP(h, hipMemcpy2DAsync(rows.data(), n * sizeof(uint32_t), h->noise_g.key, pitch * sizeof(uint32_t), n * sizeof(uint32_t), NPB_MT_N, hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipMemcpyAsync(pos, h->noise_g.pos, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipMemcpyAsync(has_gauss, h->noise_g.has_gauss, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipMemcpyAsync(cached, h->noise_g.gauss, n * sizeof(double), hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipStreamSynchronize(st));
-  for (size_t i = 0; i < (size_t)NPB_MT_N; i++)
-    for (size_t p = 0; p < n; p++) key[p * NPB_MT_N + i] = rows[i * n + p];
-  return NPB_OK;
+  return mt_state_download(h, h->noise_g, key, pos, has_gauss, cached, (hipStream_t)stream);
 }
 
 int npb_noise_set_state(NpbHandle *h, const uint32_t *key, const int32_t *pos, const int32_t *has_gauss, const double *cached, void *stream) {
   if (!h) return NPB_EINVAL;
   if (!key || !pos || !has_gauss || !cached) return fail(h, NPB_EINVAL, "npb_noise_set_state: NULL input");
-  const size_t n = (size_t)h->n_plants, pitch = h->pitch;
-  for (size_t p = 0; p < n; p++) {
-    if (pos[p] < 0 || pos[p] > NPB_MT_N) return fail(h, NPB_EINVAL, "npb_noise_set_state: pos outside [0, 624]");
-    if (has_gauss[p] != 0 && has_gauss[p] != 1) return fail(h, NPB_EINVAL, "npb_noise_set_state: has_gauss outside {0, 1}");
-  }
+  if (int rc = mt_state_check(h, "npb_noise_set_state", pos, has_gauss)) return rc;
   NPB_USE_DEVICE(h);
   if (int rc = noise_alloc(h, "npb_noise_set_state")) return rc;
-  std::vector<uint32_t> rows((size_t)NPB_MT_N * n);
-  for (size_t i = 0; i < (size_t)NPB_MT_N; i++)
-    for (size_t p = 0; p < n; p++) rows[i * n + p] = key[p * NPB_MT_N + i];
-  hipStream_t st = (hipStream_t)stream;
-  NPB_HIP(h, hipMemcpy2DAsync(h->noise_g.key, pitch * sizeof(uint32_t), rows.data(), n * sizeof(uint32_t), n * sizeof(uint32_t), NPB_MT_N, hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipMemcpyAsync(h->noise_g.pos, pos, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipMemcpyAsync(h->noise_g.has_gauss, has_gauss, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipMemcpyAsync(h->noise_g.gauss, cached, n * sizeof(double), hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipStreamSynchronize(st));    /* rows and the caller's buffers are read until the copies are done */
-  return NPB_OK;
+  return mt_state_upload(h, h->noise_g, key, pos, has_gauss, cached, (hipStream_t)stream);
 }
 
 /* ---- the data-gen runner's power profile (include/npb.h) */
@@ -1088,11 +1094,7 @@ int npb_profile_seed(NpbHandle *h, const int64_t *seeds, int steps, const double
   if ((base && n_base != 1 && n_base != n) || (std && n_std != 1 && n_std != n))
     return fail(h, NPB_EINVAL, "npb_profile_seed: base and std are each NULL, one value or one value per plant");
   std::vector<uint32_t> s32((size_t)n);
-  for (int p = 0; p < n; p++) {
-    if (seeds[p] < 0 || seeds[p] > (int64_t)0xffffffffLL)
-      return fail(h, NPB_EINVAL, "npb_profile_seed: a seed is outside [0, 2^32), which numpy.random.RandomState refuses");
-    s32[p] = (uint32_t)seeds[p];
-  }
+  if (int rc = seeds_narrow(h, "npb_profile_seed", seeds, s32.data())) return rc;
   const size_t pitch = h->pitch;
   if (!h->prof) {
     hipError_t e = hipMalloc(&h->prof, npb_noise_bytes(pitch));
@@ -1164,17 +1166,10 @@ int npb_profile_get_state(NpbHandle *h, uint32_t *key, int32_t *pos, int32_t *ha
   if (!key || !pos || !has_gauss || !cached || !carried || !position) return fail(h, NPB_EINVAL, "npb_profile_get_state: NULL output");
   NPB_USE_DEVICE(h);
   const size_t n = (size_t)h->n_plants, pitch = h->pitch;
-  std::vector<uint32_t> rows((size_t)NPB_MT_N * n);     /* [624][n], then transposed to numpy's [n][624] */
   hipStream_t st = (hipStream_t)stream;
-  NPB_HIP(h, hipMemcpy2DAsync(rows.data(), n * sizeof(uint32_t), h->prof_g.key, pitch * sizeof(uint32_t), n * sizeof(uint32_t), NPB_MT_N, hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipMemcpyAsync(pos, h->prof_g.pos, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipMemcpyAsync(has_gauss, h->prof_g.has_gauss, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipMemcpyAsync(cached, h->prof_g.gauss, n * sizeof(double), hipMemcpyDeviceToHost, st));
   NPB_HIP(h, hipMemcpy2DAsync(carried, n * sizeof(double), h->prof_side + (size_t)NPB_PROFILE_CARRIED * pitch, pitch * sizeof(double), n * sizeof(double),
                               NPB_PROFILE_NUM_CARRIED, hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipStreamSynchronize(st));
-  for (size_t i = 0; i < (size_t)NPB_MT_N; i++)
-    for (size_t p = 0; p < n; p++) key[p * NPB_MT_N + i] = rows[i * n + p];
+  if (int rc = mt_state_download(h, h->prof_g, key, pos, has_gauss, cached, st)) return rc;      /* (waits for the stream) */
   *position = h->prof_pos;
   return NPB_OK;
 }
@@ -1185,23 +1180,13 @@ int npb_profile_set_state(NpbHandle *h, const uint32_t *key, const int32_t *pos,
   if (!h->prof) return fail(h, NPB_EINVAL, "npb_profile_set_state: no profile (npb_profile_seed first: it sets the horizon and the load profiles)");
   if (!key || !pos || !has_gauss || !cached || !carried) return fail(h, NPB_EINVAL, "npb_profile_set_state: NULL input");
   if (position < 0 || position >= h->prof_steps) return fail(h, NPB_EINVAL, "npb_profile_set_state: position outside [0, steps)");
-  const size_t n = (size_t)h->n_plants, pitch = h->pitch;
-  for (size_t p = 0; p < n; p++) {
-    if (pos[p] < 0 || pos[p] > NPB_MT_N) return fail(h, NPB_EINVAL, "npb_profile_set_state: pos outside [0, 624]");
-    if (has_gauss[p] != 0 && has_gauss[p] != 1) return fail(h, NPB_EINVAL, "npb_profile_set_state: has_gauss outside {0, 1}");
-  }
+  if (int rc = mt_state_check(h, "npb_profile_set_state", pos, has_gauss)) return rc;
   NPB_USE_DEVICE(h);
-  std::vector<uint32_t> rows((size_t)NPB_MT_N * n);
-  for (size_t i = 0; i < (size_t)NPB_MT_N; i++)
-    for (size_t p = 0; p < n; p++) rows[i * n + p] = key[p * NPB_MT_N + i];
+  const size_t n = (size_t)h->n_plants, pitch = h->pitch;
   hipStream_t st = (hipStream_t)stream;
-  NPB_HIP(h, hipMemcpy2DAsync(h->prof_g.key, pitch * sizeof(uint32_t), rows.data(), n * sizeof(uint32_t), n * sizeof(uint32_t), NPB_MT_N, hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipMemcpyAsync(h->prof_g.pos, pos, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipMemcpyAsync(h->prof_g.has_gauss, has_gauss, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipMemcpyAsync(h->prof_g.gauss, cached, n * sizeof(double), hipMemcpyHostToDevice, st));
   NPB_HIP(h, hipMemcpy2DAsync(h->prof_side + (size_t)NPB_PROFILE_CARRIED * pitch, pitch * sizeof(double), carried, n * sizeof(double), n * sizeof(double),
                               NPB_PROFILE_NUM_CARRIED, hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipStreamSynchronize(st));    /* rows and the caller's buffers are read until the copies are done */
+  if (int rc = mt_state_upload(h, h->prof_g, key, pos, has_gauss, cached, st)) return rc;      /* (waits for the stream) */
   h->prof_pos = position;
   return NPB_OK;
 }

@@ -24,13 +24,16 @@ typedef struct {
   int32_t *start;           /* carried [pitch]: the entry of each plant's running episode, -1 = not from the bank */
   int32_t *out_start;       /* the caller's [n], or NULL: the episode kernel's copy of `start` as of each step */
 } npb_source_t;
-/* the side state of the component maintenance (npb_set_component_maintenance) a restore takes along: lane s of src -> lane p of state,
- * member by member ([NPB_CMAINT_SIDE_DOUBLES][pitch] doubles each); state NULL = the feature is off */
-typedef struct { double *state; const double *src; size_t pitch, src_pitch; } npb_cmaint_restore_t;
-/* the carried diagnostics rows (include/npb.h NPB_DIAG_CARRIED, npb_carry_diagnostics) a restore takes along: entry s of src
- * ([NPB_DIAG_NUM_CARRIED][src_pitch], table order) -> plant p of the caller's diagnostics buffer ([NPB_DIAG_DIM][pitch], indexed by the
- * global plant number: that buffer is not segmented); buf NULL = not carried */
-typedef struct { double *buf; const double *src; size_t pitch, src_pitch; } npb_diag_restore_t;
+/* a side block: per-plant fp64 rows that belong to a plant's state and live beside the arena.  A restore takes each along: entry s of
+ * src (a packed [rows][src_pitch] copy, recorded with the snapshot or the bank) -> plant p of the live rows; live NULL = the block is off.
+ * NPB_SIDE_CMAINT: the side state of the component maintenance (npb_set_component_maintenance), live = [NPB_CMAINT_SIDE_DOUBLES][pitch], copied
+ * member by member.  NPB_SIDE_DIAG: the carried diagnostics rows (include/npb.h NPB_DIAG_CARRIED, npb_carry_diagnostics), src in table order,
+ * live = the caller's diagnostics buffer ([NPB_DIAG_DIM][pitch], indexed by the global plant number: that buffer is not segmented) */
+enum { NPB_SIDE_CMAINT, NPB_SIDE_DIAG, NPB_SIDE_COUNT };
+typedef struct { double *live; const double *src; size_t pitch, src_pitch; } npb_side_restore_t;
+typedef struct { npb_side_restore_t block[NPB_SIDE_COUNT]; } npb_side_restores_t;
+/* the maintenance event log (npb_set_maintenance_log): the caller's records and cursor; cursor NULL = off */
+typedef struct npd_maint_log_t { npb_maint_event_t *records; uint32_t *cursor; int capacity; } npd_maint_log_t;
 /* the episode counters a restore zeroes and the episode index it bumps with them (npb_set_autoreset), each [pitch] or NULL; out_index =
  * the caller's column the episode kernel fills (npb_set_episode_index_buffer) */
 typedef struct { int32_t *len; double *ret; int32_t *index; int32_t *out_index; } npb_episode_counters_t;
@@ -49,25 +52,22 @@ typedef struct {
   void (*gather)(const void *arena, size_t npad, const int *plan_dev, int n_fields, double *out, int n, hipStream_t stream);
   /* episodes: src = the snapshot or a bank with slots (npb_source_t); maint_side / maint_counts NULL unless params.maint_enabled */
   void (*restore)(int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *mask, npb_episode_counters_t C,
-                  void *maint_side, int32_t *maint_counts, npb_cmaint_restore_t cm, npb_diag_restore_t dg, hipStream_t stream);
+                  void *maint_side, int32_t *maint_counts, npb_side_restores_t side, hipStream_t stream);
   void (*episode)(int mode, int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *done, const double *reward,
                   double *obs, npb_episode_counters_t C, int32_t *out_len, double *out_ret, uint8_t *out_truncated,
-                  double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, npb_cmaint_restore_t cm, npb_diag_restore_t dg,
-                  hipStream_t stream);
+                  double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, npb_side_restores_t side, hipStream_t stream);
   /* npb_perform_maintenance: the caller's [n_plants] order columns (bearing / target_level / success may be NULL) and the maintenance
-   * event log's descriptor (log_records NULL = off) */
+   * event log */
   void (*operator_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *pump, const int32_t *bearing,
-                         const double *target_level, uint8_t *success, npb_maint_event_t *log_records, uint32_t *log_cursor, int log_capacity,
-                         hipStream_t stream);
+                         const double *target_level, uint8_t *success, npd_maint_log_t log, hipStream_t stream);
   /* npb_perform_component_maintenance: the caller's [n_plants] order columns (unit / option / amount / success may be NULL), the component
-   * kinds the handle's mode carries (bit k = NPB_COMPONENT_* k) and the maintenance event log's descriptor */
+   * kinds the handle's mode carries (bit k = NPB_COMPONENT_* k) and the maintenance event log */
   void (*operator_component_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *unit, const int32_t *option,
-                                   const double *amount, uint8_t *success, unsigned kinds, npb_maint_event_t *log_records, uint32_t *log_cursor,
-                                   int log_capacity, hipStream_t stream);
+                                   const double *amount, uint8_t *success, unsigned kinds, npd_maint_log_t log, hipStream_t stream);
   /* npb_perform_turbine_maintenance: the caller's [n_plants] order columns (unit / success may be NULL), whether the handle's mode steps
    * the turbine, and the event log */
   void (*operator_turbine_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *unit, uint8_t *success, int turbine,
-                                 npb_maint_event_t *log_records, uint32_t *log_cursor, int log_capacity, hipStream_t stream);
+                                 npd_maint_log_t log, hipStream_t stream);
   /* npb_set_component_maintenance: the whole automatic-maintenance rule, pumps, generators and condenser in one queue, as a launch of its own
    * behind the plain step kernel; maint_side = the rule's constants, cm_side = the component table and side state */
   void (*maint_all)(size_t npad, void *arena, void *maint_side, void *cm_side, int32_t *counts, int n_plants, double *diag, size_t diag_pitch,
@@ -75,8 +75,7 @@ typedef struct {
 } npb_launchers_t;
 extern npb_launchers_t npb_launch_table, npb32_launch_table;
 /* the same for either storage type */
-void npb_launch_maint_consts(const npb_params_t *P, const npb_maint_table_t *T, npb_maint_event_t *log_records, uint32_t *log_cursor,
-                             int log_capacity, void *host_out);
+void npb_launch_maint_consts(const npb_params_t *P, const npb_maint_table_t *T, npd_maint_log_t log, void *host_out);
 size_t npb_launch_maint_consts_bytes(void);
 size_t npb_launch_maint_side_bytes(size_t npad);
 size_t npb_launch_maint_cache_offset(void);

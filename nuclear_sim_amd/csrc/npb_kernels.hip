@@ -401,8 +401,6 @@ struct npd_maint_screen_t {
   double cooldown_minutes[NPB_MAINT_NPARAM];
   uint32_t want_gt, want_lt, want_eq, want_near, want_far;    /* bit q: row q fires on value > / < / == threshold, |value - threshold| < / >= 0.001 */
 };
-/* the maintenance event log (npb_set_maintenance_log): the caller's records and cursor; cursor NULL = off */
-struct npd_maint_log_t { npb_maint_event_t *records; uint32_t *cursor; int capacity; };
 struct npd_maint_rule_consts_t { npb_params_t P; npb_maint_table_t T; npd_maint_screen_t S; npd_maint_log_t L; };
 /* one event site of a wave: the lanes with `want` take consecutive slots of the log through one device-scope atomic of the
  * wave's first active lane (ballot, mbcnt, readfirstlane).  The cursor counts every event; a slot at or past the capacity is
@@ -759,8 +757,8 @@ typedef uint64_t npd_word_t;
 /* where the restore writes besides the arena: the maintenance screen's cooldown cache (zeroed = "look", npd_maintenance.h) and the
  * caller's event-count column (npb_set_maintenance_count_buffer), both NULL unless params.maint_enabled */
 struct npd_restore_side_t { npd_u32x4 *maint_entry; int32_t *maint_counts; int n_plants;
-                             npb_cmaint_restore_t cm;      /* the side state of the component maintenance (npd_component_auto.h): state NULL = off */
-                             npb_diag_restore_t dg;        /* the carried diagnostics rows (npb_carry_diagnostics): buf NULL = not carried */ };
+                             npb_side_restore_t cm;        /* the side state of the component maintenance (npd_component_auto.h): live NULL = off */
+                             npb_side_restore_t dg;        /* the carried diagnostics rows (npb_carry_diagnostics): live NULL = not carried */ };
 /* the bank entry a restored plant takes from its slot, and the slot and start columns it leaves behind (include/npb.h) */
 __device__ __forceinline__ int32_t npd_bank_take(const npb_source_t &B, size_t p) {
   int32_t s = B.next_slot[p] % B.M;
@@ -804,17 +802,17 @@ __device__ __forceinline__ void npd_restore_lanes(npd_real_t *__restrict__ f64, 
     const size_t N = Ns, p = s;
     *counts = NPD_I32_COL(MAINT, npb_maint_t, maintenance_actions_performed, 0);
   }
-  if (R.cm.state) {                   /* the stamps and open orders of the generators and the condenser travel with the plant's */
+  if (R.cm.live) {                    /* the stamps and open orders of the generators and the condenser travel with the plant's */
 #pragma unroll 1
-    for (int k = 0; k < NPB_CMAINT_SIDE_DOUBLES; k++) R.cm.state[(size_t)k * R.cm.pitch + p] = R.cm.src[(size_t)k * R.cm.src_pitch + s];
+    for (int k = 0; k < NPB_CMAINT_SIDE_DOUBLES; k++) R.cm.live[(size_t)k * R.cm.pitch + p] = R.cm.src[(size_t)k * R.cm.src_pitch + s];
   }
-  if (R.dg.buf) {                     /* the rows the diagnostics build carries in the caller's buffer (include/npb.h NPB_DIAG_CARRIED): p is the
+  if (R.dg.live) {                    /* the rows the diagnostics build carries in the caller's buffer (include/npb.h NPB_DIAG_CARRIED): p is the
                                        * global plant number, which is how that unsegmented buffer is indexed; the loads first */
     double v[NPB_DIAG_NUM_CARRIED];
 #pragma unroll
     for (int k = 0; k < NPB_DIAG_NUM_CARRIED; k++) v[k] = R.dg.src[(size_t)k * R.dg.src_pitch + s];
     int k = 0;
-#define NPB__X(row, fresh) R.dg.buf[(size_t)(row) * R.dg.pitch + p] = v[k++];
+#define NPB__X(row, fresh) R.dg.live[(size_t)(row) * R.dg.pitch + p] = v[k++];
     NPB_DIAG_CARRIED(NPB__X)
 #undef NPB__X
   }
@@ -1521,12 +1519,10 @@ static void NPB_LAUNCHER(maint_all)(size_t npad, void *arena, void *maint_side, 
 #ifndef NPB_BUILD_F32
 /* the maintenance side buffer does not depend on the storage type (npd_maint_rule_consts_t holds no npd_real_t): one copy of
  * these.  The rule's constants as the device reads them: host_out = npb_launch_maint_consts_bytes() bytes */
-extern "C" void npb_launch_maint_consts(const npb_params_t *P, const npb_maint_table_t *T, npb_maint_event_t *log_records, uint32_t *log_cursor,
-                                        int log_capacity, void *host_out) {
+extern "C" void npb_launch_maint_consts(const npb_params_t *P, const npb_maint_table_t *T, npd_maint_log_t log, void *host_out) {
   npd_maint_rule_consts_t *RC = (npd_maint_rule_consts_t *)host_out;
   memset(RC, 0, sizeof(*RC));
-  RC->P = *P; RC->T = *T;
-  RC->L.records = log_records; RC->L.cursor = log_records ? log_cursor : nullptr; RC->L.capacity = log_records ? log_capacity : 0;
+  RC->P = *P; RC->T = *T; RC->L = log;
   npd_maint_screen_t &S = RC->S;
   for (int q = 0; q < NPB_MAINT_NPARAM; q++) {
     S.threshold[q] = T->threshold[q];
@@ -1559,56 +1555,47 @@ static void NPB_LAUNCHER(init)(const npb_params_t *P, int n_plants, size_t npad,
   hipLaunchKernelGGL(npb_init_kernel, grid, block, 0, stream, *P, npad, (npd_real_t *)arena, mask, n_plants);
 }
 /* episodes (npb_snapshot / npb_restore / npb_set_autoreset): maint_side / maint_counts NULL unless params.maint_enabled */
-static npd_restore_side_t npd_restore_side_of(void *maint_side, int32_t *maint_counts, int n_plants, npb_cmaint_restore_t cm, npb_diag_restore_t dg) {
+static npd_restore_side_t npd_restore_side_of(void *maint_side, int32_t *maint_counts, int n_plants, const npb_side_restores_t &side) {
   npd_restore_side_t R;
   R.maint_entry = npd_maint_cache_of(maint_side, maint_counts, n_plants).entry; R.maint_counts = maint_counts; R.n_plants = n_plants;
-  R.cm = cm; R.dg = dg;
+  R.cm = side.block[NPB_SIDE_CMAINT]; R.dg = side.block[NPB_SIDE_DIAG];
   return R;
 }
 /* src: the snapshot (npb_restore, the snapshot autoreset) or a bank with its slots (npb_restore_bank, the bank autoreset).  mask NULL
  * restores every lane of the pitch from the snapshot, the plants only from a bank (its slot columns have n entries) */
 static void NPB_LAUNCHER(restore)(int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *mask, npb_episode_counters_t C,
-                                  void *maint_side, int32_t *maint_counts, npb_cmaint_restore_t cm, npb_diag_restore_t dg, hipStream_t stream) {
+                                  void *maint_side, int32_t *maint_counts, npb_side_restores_t side, hipStream_t stream) {
   const int lanes = mask || src.next_slot ? n_plants : (int)NPD_NPAD(npad);
   hipLaunchKernelGGL(npb_restore_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, lanes, npad, (npd_real_t *)arena,
-                     src, mask, C.len, C.ret, C.index, npd_restore_side_of(maint_side, maint_counts, n_plants, cm, dg));
+                     src, mask, C.len, C.ret, C.index, npd_restore_side_of(maint_side, maint_counts, n_plants, side));
 }
 static void NPB_LAUNCHER(episode)(int mode, int n_plants, size_t npad, void *arena, npb_source_t src, const uint8_t *done, const double *reward,
                                   double *obs, npb_episode_counters_t C, int32_t *out_len, double *out_ret, uint8_t *out_truncated,
-                                  double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, npb_cmaint_restore_t cm, npb_diag_restore_t dg,
-                                  hipStream_t stream) {
+                                  double *final_obs, int max_steps, void *maint_side, int32_t *maint_counts, npb_side_restores_t side, hipStream_t stream) {
   npd_episode_t E;
   E.len = C.len; E.ret = C.ret; E.index = C.index; E.out_index = C.out_index; E.out_len = out_len; E.out_ret = out_ret; E.out_truncated = out_truncated; E.final_obs = final_obs; E.max_steps = max_steps;
   hipLaunchKernelGGL(npb_episode_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, mode, n_plants, npad, (npd_real_t *)arena,
-                     src, done, reward, obs, E, npd_restore_side_of(maint_side, maint_counts, n_plants, cm, dg));
+                     src, done, reward, obs, E, npd_restore_side_of(maint_side, maint_counts, n_plants, side));
 }
-/* npb_perform_maintenance: the caller's order columns; log_* = the maintenance event log (npb_set_maintenance_log), records NULL = off */
+/* npb_perform_maintenance: the caller's order columns; L = the maintenance event log (npb_set_maintenance_log) */
 static void NPB_LAUNCHER(operator_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *pump, const int32_t *bearing,
-                                         const double *target_level, uint8_t *success, npb_maint_event_t *log_records, uint32_t *log_cursor,
-                                         int log_capacity, hipStream_t stream) {
+                                         const double *target_level, uint8_t *success, npd_maint_log_t L, hipStream_t stream) {
   npd_operator_orders_t O;
   O.action = action; O.pump = pump; O.bearing = bearing; O.target_level = target_level; O.success = success; O.n_plants = n_plants;
-  npd_maint_log_t L;
-  L.records = log_records; L.cursor = log_records ? log_cursor : nullptr; L.capacity = log_records ? log_capacity : 0;
   hipLaunchKernelGGL(npb_operator_maint_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, O, L, npad, (npd_real_t *)arena);
 }
-/* npb_perform_component_maintenance: the caller's order columns; kinds = the component kinds the handle's mode carries; log_* as above */
+/* npb_perform_component_maintenance: the caller's order columns; kinds = the component kinds the handle's mode carries; L as above */
 static void NPB_LAUNCHER(operator_component_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *unit, const int32_t *option,
-                                                   const double *amount, uint8_t *success, unsigned kinds, npb_maint_event_t *log_records,
-                                                   uint32_t *log_cursor, int log_capacity, hipStream_t stream) {
+                                                   const double *amount, uint8_t *success, unsigned kinds, npd_maint_log_t L, hipStream_t stream) {
   npd_component_orders_t O;
   O.action = action; O.unit = unit; O.option = option; O.amount = amount; O.success = success; O.n_plants = n_plants; O.kinds = kinds;
-  npd_maint_log_t L;
-  L.records = log_records; L.cursor = log_records ? log_cursor : nullptr; L.capacity = log_records ? log_capacity : 0;
   hipLaunchKernelGGL(npb_operator_component_maint_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, O, L, npad, (npd_real_t *)arena);
 }
-/* npb_perform_turbine_maintenance: the caller's order columns; turbine = the handle's mode steps the turbine; log_* as above */
+/* npb_perform_turbine_maintenance: the caller's order columns; turbine = the handle's mode steps the turbine; L as above */
 static void NPB_LAUNCHER(operator_turbine_maint)(int n_plants, size_t npad, void *arena, const int32_t *action, const int32_t *unit, uint8_t *success,
-                                                 int turbine, npb_maint_event_t *log_records, uint32_t *log_cursor, int log_capacity, hipStream_t stream) {
+                                                 int turbine, npd_maint_log_t L, hipStream_t stream) {
   npd_turbine_orders_t O;
   O.action = action; O.unit = unit; O.success = success; O.n_plants = n_plants; O.turbine = turbine;
-  npd_maint_log_t L;
-  L.records = log_records; L.cursor = log_records ? log_cursor : nullptr; L.capacity = log_records ? log_capacity : 0;
   hipLaunchKernelGGL(npb_operator_turbine_maint_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, O, L, npad, (npd_real_t *)arena);
 }
 /* not const: clang emits a namespace-scope const into the device code too, where these host functions do not exist */

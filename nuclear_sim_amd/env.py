@@ -650,6 +650,13 @@ class BatchedPlantEnv:
         from . import maintlog
         maintlog.write(self.maintenance_log(clear=clear, allow_overflow=allow_overflow), path)
 
+    def _order_buffers(self):
+        """the buffers the perform_*_maintenance methods keep for their order columns, with the ``success`` column they all return"""
+        if getattr(self, "_orders", None) is None:
+            self._orders = {}
+            with torch.cuda.device(self.device):
+                self._orders["success"] = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+
     def _order_column(self, key, value, dtype, to_number):
         """one column of perform_maintenance's order: a device tensor of the right type is passed as it is, anything else lands in a
         buffer the env keeps (a scalar by fill_, an array by one copy); ``to_number`` maps a name to its index"""
@@ -718,10 +725,7 @@ class BatchedPlantEnv:
             raise ValueError("unknown bearing %r: one of %r" % (bearing, [k for k in _lib.MAINT_BEARINGS if k]))
         if not hasattr(self.L, "npb_perform_maintenance"):
             raise _lib.NpbError("libnpb.so has no npb_perform_maintenance (older than ABI 147): rebuild")
-        if getattr(self, "_orders", None) is None:
-            self._orders = {}
-            with torch.cuda.device(self.device):
-                self._orders["success"] = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+        self._order_buffers()
         a = self._masked_order(self._order_column("action", action, torch.int32, _lib.maint_action_index), mask)
         k = self._order_column("pump", pump, torch.int32, _lib.PUMP_IDS.index)
         b = None if bearing is None else self._order_column("bearing", bearing, torch.int32, _lib.MAINT_BEARINGS.__getitem__)
@@ -760,10 +764,7 @@ class BatchedPlantEnv:
             unit = _lib.EJECTOR_IDS.index(unit)
         if not hasattr(self.L, "npb_perform_component_maintenance"):
             raise _lib.NpbError("libnpb.so has no npb_perform_component_maintenance (older than ABI 148): rebuild")
-        if getattr(self, "_orders", None) is None:
-            self._orders = {}
-            with torch.cuda.device(self.device):
-                self._orders["success"] = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+        self._order_buffers()
         a = self._masked_order(self._order_column("component_action", action, torch.int32, int), mask)
         k = None if unit is None else self._order_column("unit", unit, torch.int32, int)
         if isinstance(cleaning_type, str):
@@ -807,10 +808,7 @@ class BatchedPlantEnv:
             unit = ids.index(unit)
         if not hasattr(self.L, "npb_perform_turbine_maintenance"):
             raise _lib.NpbError("libnpb.so has no npb_perform_turbine_maintenance (older than ABI 149): rebuild")
-        if getattr(self, "_orders", None) is None:
-            self._orders = {}
-            with torch.cuda.device(self.device):
-                self._orders["success"] = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+        self._order_buffers()
         a = self._masked_order(self._order_column("turbine_action", action, torch.int32, int), mask)
         k = None if unit is None else self._order_column("unit", unit, torch.int32, int)
         ok = self._orders["success"]
@@ -917,15 +915,10 @@ class BatchedPlantEnv:
 
     # ------------------------------------------------------------------ state columns
     def get_field(self, name: str, instance: int = 0, k: int = 0) -> torch.Tensor:
-        kind, slot = SCHEMA.slot(name, instance, k)
-        t = torch.empty(self.n, dtype=torch.float64 if kind == "f64" else torch.int32, device=self.device)
-        _lib.check(self.L.npb_get_field(self._h, 0 if kind == "f64" else 1, slot, self._p(t), 1, self._stream()), self._h)
-        return t
+        return self._get_slot(*SCHEMA.slot(name, instance, k))
 
     def set_field(self, name: str, value, instance: int = 0, k: int = 0) -> None:
-        kind, slot = SCHEMA.slot(name, instance, k)
-        t = self._col(value, torch.float64 if kind == "f64" else torch.int32)
-        _lib.check(self.L.npb_set_field(self._h, 0 if kind == "f64" else 1, slot, self._p(t), 1, self._stream()), self._h)
+        self._set_slot(*SCHEMA.slot(name, instance, k), value)
 
     def _get_slot(self, kind: str, slot: int) -> torch.Tensor:
         t = torch.empty(self.n, dtype=torch.float64 if kind == "f64" else torch.int32, device=self.device)
