@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define NPB_VERSION 152 /* 0.1.5.2: npb_profile_seed, npb_profile_fill, npb_profile_ramp, npb_profile_get_state, npb_profile_set_state (the data-gen runner's power profile drawn on the device, per plant); 0.1.5.1: npb_carry_diagnostics, npb_diag_num_carried / npb_diag_carried_row / npb_diag_carried_fresh, npb_get / npb_set_diagnostics_state, npb_set_episode_index_buffer (the diagnostics rows the step carries travel with snapshots, start banks, the autoreset, resets and checkpoints; an episode index per plant); 0.1.5.0: npb_set_component_maintenance, npb_default_component_maintenance_table, npb_component_maint_* catalog queries, npb_get / npb_set_component_maintenance_state, NPB_MAINT_EVENT_COMPONENT_CREATED / _COMPLETED (automatic maintenance of steam generators and condenser in one work-order queue with the feedwater pumps); 0.1.4.9: npb_perform_turbine_maintenance, npb_turbine_* catalog queries, NPB_MAINT_EVENT_OPERATOR_TURBINE (maintenance of the turbine, its bearings, lubrication system and stages a caller orders); 0.1.4.8: npb_perform_component_maintenance, npb_component_* catalog queries, NPB_MAINT_EVENT_OPERATOR_COMPONENT (maintenance of steam generators, condenser and ejectors a caller orders); 0.1.4.7: npb_perform_maintenance, NPB_MAINT_EVENT_OPERATOR (maintenance a caller orders, carried out on the device between two steps); 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
+#define NPB_VERSION 153 /* 0.1.5.3: npb_sampler_create, npb_sampler_sample, npb_sampler_destroy (a state log samples a watch list of plants, arena members and side buffers, in one launch); 0.1.5.2: npb_profile_seed, npb_profile_fill, npb_profile_ramp, npb_profile_get_state, npb_profile_set_state (the data-gen runner's power profile drawn on the device, per plant); 0.1.5.1: npb_carry_diagnostics, npb_diag_num_carried / npb_diag_carried_row / npb_diag_carried_fresh, npb_get / npb_set_diagnostics_state, npb_set_episode_index_buffer (the diagnostics rows the step carries travel with snapshots, start banks, the autoreset, resets and checkpoints; an episode index per plant); 0.1.5.0: npb_set_component_maintenance, npb_default_component_maintenance_table, npb_component_maint_* catalog queries, npb_get / npb_set_component_maintenance_state, NPB_MAINT_EVENT_COMPONENT_CREATED / _COMPLETED (automatic maintenance of steam generators and condenser in one work-order queue with the feedwater pumps); 0.1.4.9: npb_perform_turbine_maintenance, npb_turbine_* catalog queries, NPB_MAINT_EVENT_OPERATOR_TURBINE (maintenance of the turbine, its bearings, lubrication system and stages a caller orders); 0.1.4.8: npb_perform_component_maintenance, npb_component_* catalog queries, NPB_MAINT_EVENT_OPERATOR_COMPONENT (maintenance of steam generators, condenser and ejectors a caller orders); 0.1.4.7: npb_perform_maintenance, NPB_MAINT_EVENT_OPERATOR (maintenance a caller orders, carried out on the device between two steps); 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
 #ifndef NPB_API
 #define NPB_API __attribute__((visibility("default")))
 #endif
@@ -350,6 +350,30 @@ NPB_API int npb_set_field(NpbHandle *h, int kind, int slot, const void *buf, int
  * which walks every provider's get_state_dict() and appends one pandas row per step.  kinds / slots are host arrays;
  * the request is remembered, so repeating it costs one kernel launch. */
 NPB_API int npb_gather_fields(NpbHandle *h, int n_fields, const int *kinds, const int *slots, double *out, void *stream);
+/* A SAMPLER: the sampling step of a state log that follows a watch list of plants while the whole batch runs.  Created once from a
+ * request, used once per sample: npb_sampler_sample is ONE kernel launch on `stream` that writes, widened to double, row r of watched
+ * plant j to out[r * n_watched + j] (device, [rows][n_watched]) -- first the n_fields arena members (kinds / slots as npb_gather_fields
+ * takes them), then the rows of every side source in request order.  A side source is a caller-owned DEVICE buffer that holds per-plant
+ * values beside the arena (the diagnostics buffer, the step's info block, done, the episode columns): row q of plant p is element
+ * base[q * row_stride + p * plant_stride] of the given type, strides in elements.  The caller keeps these buffers alive and in place
+ * while the sampler exists.  The plant ids (host int32[n_watched]) keep the caller's order: consecutive ids make consecutive lanes,
+ * which coalesce; every id of a scattered list costs a cache line per row.
+ * npb_sampler_create validates the whole request before any device work and refuses by name (npb_last_error): n_watched <= 0, an id
+ * outside [0, n_plants), a duplicate id, a bad kind or slot, a side source with a NULL base, an unknown type or rows <= 0, a request
+ * without rows.  It uploads plan and ids once (synchronously); npb_sampler_sample uploads nothing and does not synchronise.  Samplers
+ * share nothing with npb_gather_fields' remembered request or with one another.  *sampler = an id >= 0 of this handle.
+ * npb_sampler_destroy frees one (a pending npb_sampler_sample on `stream`s the caller has not synchronised must have finished);
+ * npb_destroy frees the rest.  An unknown or destroyed id is NPB_EINVAL. */
+enum { NPB_SAMPLE_F64 = 0, NPB_SAMPLE_F32 = 1, NPB_SAMPLE_I32 = 2, NPB_SAMPLE_U8 = 3 };
+typedef struct { const void *base; int type; int rows; int64_t row_stride, plant_stride; } npb_sample_source_t;
+typedef struct {
+  int n_watched; const int32_t *plants;                 /* host */
+  int n_fields; const int *kinds; const int *slots;     /* host; n_fields may be 0 */
+  int n_sources; const npb_sample_source_t *sources;    /* host array of descriptors of device buffers; n_sources may be 0 */
+} npb_sampler_desc_t;
+NPB_API int npb_sampler_create(NpbHandle *h, const npb_sampler_desc_t *desc, int *sampler);
+NPB_API int npb_sampler_sample(NpbHandle *h, int sampler, double *out, void *stream);
+NPB_API int npb_sampler_destroy(NpbHandle *h, int sampler);
 /* raw arena (checkpointing, external kernels): one allocation of equally wide columns, column-major with `pitch`
  * plants per column; the members of the schema are mapped onto columns as include/npb_fields.h describes.  A handle of
  * more than 45 056 plants keeps its arena in SEGMENTS (npb_state_arena_segment(h) plants each -- 16 384 --, 0 = not

@@ -316,6 +316,23 @@ def component_maint_table_from_thresholds(thresholds: dict) -> "NpbComponentMain
     return t
 
 
+# include/npb.h NPB_SAMPLE_*: element types of a sampler's side sources
+SAMPLE_TYPES = {"f64": 0, "f32": 1, "i32": 2, "u8": 3}
+
+
+class NpbSampleSource(ctypes.Structure):
+    """npb_sample_source_t (include/npb.h): a caller-owned device buffer of per-plant rows, strides in elements"""
+    _fields_ = [("base", ctypes.c_void_p), ("type", ctypes.c_int), ("rows", ctypes.c_int),
+                ("row_stride", ctypes.c_int64), ("plant_stride", ctypes.c_int64)]
+
+
+class NpbSamplerDesc(ctypes.Structure):
+    """npb_sampler_desc_t (include/npb.h): the request of npb_sampler_create; every array on the host"""
+    _fields_ = [("n_watched", ctypes.c_int), ("plants", ctypes.POINTER(ctypes.c_int32)),
+                ("n_fields", ctypes.c_int), ("kinds", ctypes.POINTER(ctypes.c_int)), ("slots", ctypes.POINTER(ctypes.c_int)),
+                ("n_sources", ctypes.c_int), ("sources", ctypes.POINTER(NpbSampleSource))]
+
+
 _lib = None
 
 
@@ -458,6 +475,10 @@ def load():
         L.npb_profile_ramp.argtypes = [vp, ci, vp, vp, vp]
         L.npb_profile_get_state.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
         L.npb_profile_set_state.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp]
+    if hasattr(L, "npb_sampler_create"):     # ABI 153: a state log samples a watch list of plants
+        L.npb_sampler_create.argtypes = [vp, ctypes.POINTER(NpbSamplerDesc), ctypes.POINTER(ci)]
+        L.npb_sampler_sample.argtypes = [vp, ci, vp, vp]
+        L.npb_sampler_destroy.argtypes = [vp, ci]
     if L.npb_num_f64() != SCHEMA.total_f64 or L.npb_num_i32() != SCHEMA.total_i32:
         raise NpbError("libnpb.so was built against a different include/npb_fields.h (%d/%d vs %d/%d): rebuild"
                        % (L.npb_num_f64(), L.npb_num_i32(), SCHEMA.total_f64, SCHEMA.total_i32))

@@ -15,6 +15,9 @@
 /* a side block's rows as recorded with a snapshot or a bank: a packed [rows][pitch] copy beside that arena, or NULL; its allocation */
 struct SideCopy { double *rows; size_t pitch, doubles; };
 
+/* npb_sampler_create: what one sampler keeps on the device, one allocation: [side rows][plan: 3 ints per field][plant ids] */
+struct Sampler { void *dev; const npb_sample_row_t *side; const int *plan; const int32_t *ids; int n_fields, n_rows, n_watched; };
+
 struct NpbHandle {
   npb_params_t params;
   int n_plants;
@@ -61,6 +64,7 @@ struct NpbHandle {
   double *ramp_prev;   /* npb_profile_ramp: the previous setpoint of every plant ([pitch], NaN = none yet), allocated on first use */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
   std::vector<int> plan_key;
+  std::vector<Sampler *> samplers;   /* npb_sampler_create: by id; a destroyed one leaves a NULL entry */
   std::string error;
 };
 
@@ -428,6 +432,7 @@ int npb_destroy(NpbHandle *h) {
   if (h->prof_side) (void)hipFree(h->prof_side);
   if (h->prof_z) (void)hipFree(h->prof_z);
   if (h->ramp_prev) (void)hipFree(h->ramp_prev);
+  for (Sampler *sm : h->samplers) if (sm) { (void)hipFree(sm->dev); delete sm; }
   delete h;
   return NPB_OK;
 }
@@ -739,6 +744,99 @@ int npb_gather_fields(NpbHandle *h, int n_fields, const int *kinds, const int *s
   }
   h->K->gather(h->f64, NPB_N(h), h->plan_dev, n_fields, out, h->n_plants, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+
+/* samplers: a watch list of plants, arena members and side buffers in one launch per sample (include/npb.h) */
+int npb_sampler_create(NpbHandle *h, const npb_sampler_desc_t *desc, int *sampler) {
+  if (!h) return fail(nullptr, NPB_EINVAL, "npb_sampler_create: NULL handle");
+  if (!desc || !sampler) return fail(h, NPB_EINVAL, "npb_sampler_create: NULL request or NULL sampler id");
+  *sampler = -1;
+  char msg[192];
+  if (desc->n_watched <= 0 || !desc->plants) return fail(h, NPB_EINVAL, "npb_sampler_create: n_watched must be at least 1, with its plant ids");
+  std::vector<bool> seen((size_t)h->n_plants, false);
+  for (int j = 0; j < desc->n_watched; j++) {
+    const int32_t p = desc->plants[j];
+    if (p < 0 || p >= h->n_plants) {
+      snprintf(msg, sizeof msg, "npb_sampler_create: plant id %d is outside [0, %d)", (int)p, h->n_plants);
+      return fail(h, NPB_EINVAL, msg);
+    }
+    if (seen[(size_t)p]) {
+      snprintf(msg, sizeof msg, "npb_sampler_create: plant id %d is listed twice", (int)p);
+      return fail(h, NPB_EINVAL, msg);
+    }
+    seen[(size_t)p] = true;
+  }
+  if (desc->n_fields < 0 || desc->n_fields > NPB_TOTAL_F64 + NPB_TOTAL_I32 || (desc->n_fields > 0 && (!desc->kinds || !desc->slots)))
+    return fail(h, NPB_EINVAL, "npb_sampler_create: bad number of fields, or fields without kinds / slots");
+  std::vector<int> plan(3 * (size_t)desc->n_fields);
+  for (int f = 0; f < desc->n_fields; f++)
+    if ((desc->kinds[f] != NPB_KIND_F64 && desc->kinds[f] != NPB_KIND_I32) ||
+        !locate(h->storage, desc->kinds[f], desc->slots[f], &plan[3 * f], &plan[3 * f + 1], &plan[3 * f + 2])) {
+      snprintf(msg, sizeof msg, "npb_sampler_create: bad field kind or slot (field %d: kind %d, slot %d)", f, desc->kinds[f], desc->slots[f]);
+      return fail(h, NPB_EINVAL, msg);
+    }
+  if (desc->n_sources < 0 || (desc->n_sources > 0 && !desc->sources)) return fail(h, NPB_EINVAL, "npb_sampler_create: side sources without their descriptors");
+  static const size_t width[] = {sizeof(double), sizeof(float), sizeof(int32_t), sizeof(uint8_t)};     /* NPB_SAMPLE_* */
+  std::vector<npb_sample_row_t> side;
+  for (int k = 0; k < desc->n_sources; k++) {
+    const npb_sample_source_t &S = desc->sources[k];
+    if (!S.base) { snprintf(msg, sizeof msg, "npb_sampler_create: side source %d has a NULL base", k); return fail(h, NPB_EINVAL, msg); }
+    if (S.type < NPB_SAMPLE_F64 || S.type > NPB_SAMPLE_U8) {
+      snprintf(msg, sizeof msg, "npb_sampler_create: side source %d has the unknown element type %d", k, S.type);
+      return fail(h, NPB_EINVAL, msg);
+    }
+    if (S.rows <= 0 || S.row_stride < 0 || S.plant_stride < 0) {
+      snprintf(msg, sizeof msg, "npb_sampler_create: side source %d needs rows >= 1 and strides >= 0", k);
+      return fail(h, NPB_EINVAL, msg);
+    }
+    for (int q = 0; q < S.rows; q++)
+      side.push_back(npb_sample_row_t{(const char *)S.base + (size_t)q * (size_t)S.row_stride * width[S.type], S.plant_stride, S.type, 0});
+  }
+  const size_t n_rows = (size_t)desc->n_fields + side.size();
+  if (n_rows == 0 || n_rows > 65535) return fail(h, NPB_EINVAL, "npb_sampler_create: a request needs between 1 and 65 535 rows");
+  NPB_USE_DEVICE(h);
+  /* one allocation, the widest alignment first */
+  const size_t side_bytes = side.size() * sizeof(npb_sample_row_t), plan_bytes = plan.size() * sizeof(int), ids_bytes = (size_t)desc->n_watched * sizeof(int32_t);
+  std::vector<char> host(side_bytes + plan_bytes + ids_bytes);
+  if (side_bytes) memcpy(host.data(), side.data(), side_bytes);
+  if (plan_bytes) memcpy(host.data() + side_bytes, plan.data(), plan_bytes);
+  memcpy(host.data() + side_bytes + plan_bytes, desc->plants, ids_bytes);
+  void *dev = nullptr;
+  hipError_t e = hipMalloc(&dev, host.size());
+  if (e != hipSuccess) return fail(h, NPB_ENOMEM, "npb_sampler_create: hipMalloc of the sampler's plan failed", e);
+  e = hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { (void)hipFree(dev); return fail(h, NPB_EHIP, "npb_sampler_create: upload of the sampler's plan failed", e); }
+  Sampler *sm = new Sampler{dev, (const npb_sample_row_t *)dev, (const int *)((const char *)dev + side_bytes),
+                            (const int32_t *)((const char *)dev + side_bytes + plan_bytes), desc->n_fields, (int)n_rows, desc->n_watched};
+  size_t id = 0;
+  while (id < h->samplers.size() && h->samplers[id]) id++;
+  if (id == h->samplers.size()) h->samplers.push_back(sm); else h->samplers[id] = sm;
+  *sampler = (int)id;
+  return NPB_OK;
+}
+
+int npb_sampler_sample(NpbHandle *h, int sampler, double *out, void *stream) {
+  if (!h) return fail(nullptr, NPB_EINVAL, "npb_sampler_sample: NULL handle");
+  if (sampler < 0 || (size_t)sampler >= h->samplers.size() || !h->samplers[(size_t)sampler])
+    return fail(h, NPB_EINVAL, "npb_sampler_sample: unknown or destroyed sampler id");
+  if (!out) return fail(h, NPB_EINVAL, "npb_sampler_sample: NULL output buffer");
+  NPB_USE_DEVICE(h);
+  const Sampler *sm = h->samplers[(size_t)sampler];
+  h->K->sample(h->f64, NPB_N(h), sm->plan, sm->n_fields, sm->side, sm->n_rows, sm->ids, sm->n_watched, out, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+
+int npb_sampler_destroy(NpbHandle *h, int sampler) {
+  if (!h) return fail(nullptr, NPB_EINVAL, "npb_sampler_destroy: NULL handle");
+  if (sampler < 0 || (size_t)sampler >= h->samplers.size() || !h->samplers[(size_t)sampler])
+    return fail(h, NPB_EINVAL, "npb_sampler_destroy: unknown or destroyed sampler id");
+  NPB_USE_DEVICE(h);
+  Sampler *sm = h->samplers[(size_t)sampler];
+  h->samplers[(size_t)sampler] = nullptr;
+  (void)hipFree(sm->dev);      /* (hipFree waits for the device: a sample still in flight finishes first) */
+  delete sm;
   return NPB_OK;
 }
 

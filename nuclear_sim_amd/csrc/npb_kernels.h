@@ -37,6 +37,9 @@ typedef struct npd_maint_log_t { npb_maint_event_t *records; uint32_t *cursor; i
 /* the episode counters a restore zeroes and the episode index it bumps with them (npb_set_autoreset), each [pitch] or NULL; out_index =
  * the caller's column the episode kernel fills (npb_set_episode_index_buffer) */
 typedef struct { int32_t *len; double *ret; int32_t *index; int32_t *out_index; } npb_episode_counters_t;
+/* one side row of a sampler (npb_sampler_create): watched plant p's value is element p * plant_stride of `row` (the source's base moved
+ * to the row), of type NPB_SAMPLE_* */
+typedef struct { const void *row; int64_t plant_stride; int type; int pad_; } npb_sample_row_t;
 typedef struct {
   int (*step)(const npb_params_t *P, int n_plants, size_t npad, void *arena, const int32_t *action,
               const double *magnitude, const double *setpoint, const double *noise_z, const double *cw_temp,
@@ -72,6 +75,10 @@ typedef struct {
    * behind the plain step kernel; maint_side = the rule's constants, cm_side = the component table and side state */
   void (*maint_all)(size_t npad, void *arena, void *maint_side, void *cm_side, int32_t *counts, int n_plants, double *diag, size_t diag_pitch,
                     hipStream_t stream);
+  /* npb_sampler_sample: rows = n_fields arena members (plan_dev as for gather) then the side rows, of the plants ids_dev[0 .. n_watched):
+   * out[r * n_watched + j], one launch */
+  void (*sample)(const void *arena, size_t npad, const int *plan_dev, int n_fields, const npb_sample_row_t *side_dev, int n_rows,
+                 const int32_t *ids_dev, int n_watched, double *out, hipStream_t stream);
 } npb_launchers_t;
 extern npb_launchers_t npb_launch_table, npb32_launch_table;
 /* the same for either storage type */

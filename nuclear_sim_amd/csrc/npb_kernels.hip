@@ -1598,11 +1598,14 @@ static void NPB_LAUNCHER(operator_turbine_maint)(int n_plants, size_t npad, void
   O.action = action; O.unit = unit; O.success = success; O.n_plants = n_plants; O.turbine = turbine;
   hipLaunchKernelGGL(npb_operator_turbine_maint_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, O, L, npad, (npd_real_t *)arena);
 }
+static void NPB_LAUNCHER(sample)(const void *arena, size_t npad, const int *plan_dev, int n_fields, const npb_sample_row_t *side_dev, int n_rows,
+                                 const int32_t *ids_dev, int n_watched, double *out, hipStream_t stream);     /* behind every other kernel, at the end of the file */
 /* not const: clang emits a namespace-scope const into the device code too, where these host functions do not exist */
 extern "C" npb_launchers_t NPB_LAUNCHER(table) = {
   NPB_LAUNCHER(step), NPB_LAUNCHER(maint), NPB_LAUNCHER(observe), NPB_LAUNCHER(init), NPB_LAUNCHER(reset),
   NPB_LAUNCHER(field_get), NPB_LAUNCHER(field_set), NPB_LAUNCHER(gather), NPB_LAUNCHER(restore), NPB_LAUNCHER(episode),
   NPB_LAUNCHER(operator_maint), NPB_LAUNCHER(operator_component_maint), NPB_LAUNCHER(operator_turbine_maint), NPB_LAUNCHER(maint_all),
+  NPB_LAUNCHER(sample),
 };
 #ifndef NPB_BUILD_F32
 /* npb_reset / npb_reset_reference / npb_restore: the episode counters (len, ret) and the carried start entries (start: -1, not from
@@ -1665,3 +1668,36 @@ extern "C" void npb_launch_diag_carried_put(double *live, size_t live_pitch, con
                      values);
 }
 #endif
+/* the state log's sampling step for a watch list (npb_sampler_sample): one grid row per output row, lanes over the watched plants.
+ * Row r < n_fields is an arena member, addressed as npb_gather_kernel addresses it with the plant ids[j] in place of the lane; the rows
+ * behind are side rows (npb_sample_row_t): caller-owned buffers beside the arena.  Every value is widened to double: out[r * n_watched + j].
+ * The row's descriptor is uniform over the block (scalar loads); consecutive ids read consecutive elements */
+__global__ void npb_sample_kernel(const npd_real_t *__restrict__ arena, size_t N, const int *__restrict__ plan, int n_fields,
+                                  const npb_sample_row_t *__restrict__ side, const int32_t *__restrict__ ids, double *__restrict__ out, int n_watched) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+  if (j >= n_watched) return;
+  const size_t p = (size_t)ids[j];
+  double v;
+  if (r < n_fields) {
+    const int col = plan[3 * r], sub = plan[3 * r + 1], kind = plan[3 * r + 2];
+    NPD_SEGMENT(arena, N, p);
+    const char *e = (const char *)(arena + (size_t)col * N + p);
+    if (kind == 0) v = (double)*(const npd_real_t *)e;
+    else if (kind == 1) v = (double)*(const float *)(e + sub * 4);
+    else v = (double)*(const int32_t *)(e + sub * 4);
+  } else {
+    const npb_sample_row_t S = side[r - n_fields];
+    const int64_t e = (int64_t)p * S.plant_stride;
+    if (S.type == NPB_SAMPLE_F64) v = ((const double *)S.row)[e];
+    else if (S.type == NPB_SAMPLE_F32) v = (double)((const float *)S.row)[e];
+    else if (S.type == NPB_SAMPLE_I32) v = (double)((const int32_t *)S.row)[e];
+    else v = (double)((const uint8_t *)S.row)[e];
+  }
+  out[(size_t)r * n_watched + j] = v;
+}
+static void NPB_LAUNCHER(sample)(const void *arena, size_t npad, const int *plan_dev, int n_fields, const npb_sample_row_t *side_dev, int n_rows,
+                                 const int32_t *ids_dev, int n_watched, double *out, hipStream_t stream) {
+  const int block = n_watched <= 64 ? 64 : 256;      /* a short watch list: one wave per row, no idle waves */
+  hipLaunchKernelGGL(npb_sample_kernel, dim3((n_watched + block - 1) / block, n_rows), dim3(block), 0, stream, (const npd_real_t *)arena, npad, plan_dev,
+                     n_fields, side_dev, ids_dev, out, n_watched);
+}

@@ -459,7 +459,7 @@ class BatchedPlantEnv:
                     bank_seeds: Optional[Sequence[int]] = None, noise_generator: str = "host",
                     maintenance_log: Optional[int] = None, component_maintenance: bool = False,
                     component_thresholds: Optional[dict] = None, diagnostics: bool = False,
-                    power_profile_steps: Optional[int] = None) -> "BatchedPlantEnv":
+                    power_profile_steps: Optional[int] = None, storage: str = "f64") -> "BatchedPlantEnv":
         """One plant per seed, as data_gen's MaintenanceScenarioRunner builds them for
         ``compose_action_test_scenario(action, randomize=True, randomization_seed=seed)``
         (maintenance_scenario_runner.py:210-244): dt in minutes, ConstantHeatSource with 0.1 % noise seeded 42,
@@ -476,13 +476,14 @@ class BatchedPlantEnv:
         composer's 90 % / 2.0 % load profile), so ``step()`` needs no setpoint.  The profile seeds are the scenario seeds.  This is
         NOT the profile the live runner draws for that scenario seed: its global stream is further along by then, by whatever the
         composer's randomiser drew from it, and that consumption is not restated.  What is reproduced is the runner's profile for
-        a stream seeded just before it (np.random.seed(seed) immediately before run_scenario)."""
+        a stream seeded just before it (np.random.seed(seed) immediately before run_scenario).  ``storage`` as for the constructor
+        (a bank of ``bank_seeds`` is built with the same)."""
         if max_episode_steps is not None and not autoreset:
             raise ValueError("max_episode_steps needs autoreset=True")
         from . import scenarios
         env = cls(len(seeds), dt=dt, heat_source="constant", noise_enabled=True, noise_std_percent=0.1,
                   noise_seeds=[42] * len(seeds), device=device, maintenance=True, params=params, noise_generator=noise_generator,
-                  component_maintenance=component_maintenance, component_thresholds=component_thresholds, diagnostics=diagnostics,
+                  component_maintenance=component_maintenance, component_thresholds=component_thresholds, diagnostics=diagnostics, storage=storage,
                   power_profile=None if power_profile_steps is None else dict(seeds=list(seeds), steps=int(power_profile_steps)))
         eff = float(env.get_field("pump.lubrication_effectiveness")[0].item())
         env.set_fields(scenarios.action_test_fields(action, seeds, eff, randomize=randomize))
@@ -495,7 +496,7 @@ class BatchedPlantEnv:
             env._enable_autoreset(max_episode_steps)
         if bank_seeds is not None:
             bank = cls.action_test(action, bank_seeds, dt=dt, device=device, randomize=randomize, params=params,
-                                   component_maintenance=component_maintenance, component_thresholds=component_thresholds, diagnostics=diagnostics)
+                                   component_maintenance=component_maintenance, component_thresholds=component_thresholds, diagnostics=diagnostics, storage=storage)
             env.set_start_bank(bank)
             torch.cuda.current_stream(env.device).synchronize()     # the copy has read the bank batch's arena
             bank.close()
@@ -879,6 +880,17 @@ class BatchedPlantEnv:
                                                   self._p(e["final_observation"])), self._h)
         if "episode_index" in e:
             _lib.check(self.L.npb_set_episode_index_buffer(self._h, self._p(e["episode_index"])), self._h)
+
+    def log_sources(self) -> Dict[str, torch.Tensor]:
+        """The buffers beside the arena that a state log with a watch list samples (nuclear_sim_amd/statelog.py, ``sample_request``): the
+        step's info block, its ``done`` column, the diagnostics buffer while the diagnostics are on and the episode columns of an env
+        with autoreset.  The env owns them; the log reads them through its sampler (npb_sampler_create)."""
+        out = {"info": self._info_buf, "done": self._done}
+        if self._diag_buf is not None:
+            out["diagnostics"] = self._diag_buf
+        if self._episode is not None:
+            out.update({k: self._episode[k] for k in ("truncated", "episode_index", "episode_length") if k in self._episode})
+        return out
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
