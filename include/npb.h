@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define NPB_VERSION 153 /* 0.1.5.3: npb_sampler_create, npb_sampler_sample, npb_sampler_destroy (a state log samples a watch list of plants, arena members and side buffers, in one launch); 0.1.5.2: npb_profile_seed, npb_profile_fill, npb_profile_ramp, npb_profile_get_state, npb_profile_set_state (the data-gen runner's power profile drawn on the device, per plant); 0.1.5.1: npb_carry_diagnostics, npb_diag_num_carried / npb_diag_carried_row / npb_diag_carried_fresh, npb_get / npb_set_diagnostics_state, npb_set_episode_index_buffer (the diagnostics rows the step carries travel with snapshots, start banks, the autoreset, resets and checkpoints; an episode index per plant); 0.1.5.0: npb_set_component_maintenance, npb_default_component_maintenance_table, npb_component_maint_* catalog queries, npb_get / npb_set_component_maintenance_state, NPB_MAINT_EVENT_COMPONENT_CREATED / _COMPLETED (automatic maintenance of steam generators and condenser in one work-order queue with the feedwater pumps); 0.1.4.9: npb_perform_turbine_maintenance, npb_turbine_* catalog queries, NPB_MAINT_EVENT_OPERATOR_TURBINE (maintenance of the turbine, its bearings, lubrication system and stages a caller orders); 0.1.4.8: npb_perform_component_maintenance, npb_component_* catalog queries, NPB_MAINT_EVENT_OPERATOR_COMPONENT (maintenance of steam generators, condenser and ejectors a caller orders); 0.1.4.7: npb_perform_maintenance, NPB_MAINT_EVENT_OPERATOR (maintenance a caller orders, carried out on the device between two steps); 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
+#define NPB_VERSION 154 /* 0.1.5.4: npb_set_maintenance_summary, npb_maint_summary_fold, npb_maint_summary_clear, npb_maint_summary_check (the maintenance event log folded into a per-plant work-order summary on the device); 0.1.5.3: npb_sampler_create, npb_sampler_sample, npb_sampler_destroy (a state log samples a watch list of plants, arena members and side buffers, in one launch); 0.1.5.2: npb_profile_seed, npb_profile_fill, npb_profile_ramp, npb_profile_get_state, npb_profile_set_state (the data-gen runner's power profile drawn on the device, per plant); 0.1.5.1: npb_carry_diagnostics, npb_diag_num_carried / npb_diag_carried_row / npb_diag_carried_fresh, npb_get / npb_set_diagnostics_state, npb_set_episode_index_buffer (the diagnostics rows the step carries travel with snapshots, start banks, the autoreset, resets and checkpoints; an episode index per plant); 0.1.5.0: npb_set_component_maintenance, npb_default_component_maintenance_table, npb_component_maint_* catalog queries, npb_get / npb_set_component_maintenance_state, NPB_MAINT_EVENT_COMPONENT_CREATED / _COMPLETED (automatic maintenance of steam generators and condenser in one work-order queue with the feedwater pumps); 0.1.4.9: npb_perform_turbine_maintenance, npb_turbine_* catalog queries, NPB_MAINT_EVENT_OPERATOR_TURBINE (maintenance of the turbine, its bearings, lubrication system and stages a caller orders); 0.1.4.8: npb_perform_component_maintenance, npb_component_* catalog queries, NPB_MAINT_EVENT_OPERATOR_COMPONENT (maintenance of steam generators, condenser and ejectors a caller orders); 0.1.4.7: npb_perform_maintenance, NPB_MAINT_EVENT_OPERATOR (maintenance a caller orders, carried out on the device between two steps); 0.1.4.6: npb_set_maintenance_log, npb_maint_event_bytes (work orders created and completed, logged on the device); 0.1.4.5: npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state (heat-source noise streams on the device); 0.1.4.4: npb_set_start_bank, npb_set_start_slots, npb_restore_bank, npb_set_episode_start_buffer (episodes restart from a bank of start states); 0.1.4.3: npb_snapshot, npb_restore, npb_set_autoreset, npb_set_episode_buffers (episodes: same-step autoreset, truncation); 0.1.4.2: NPB_DIAG_DIM 170 (state-log rows of round 4), npb_state_arena_layout, NPB_EINVAL for NPB_HEAT_EXTERNAL without its input column; 0.1.4.1: npb_state_arena_segment (segmented arenas), step-kernel variant 5, NPB_DIAG_DIM 136; 0.1.4: npb_debug_last_step_kernel, npb_info_dim / npb_obs_dim / npb_diag_dim, maintenance catalogs by index; 0.1.3.1: params.kinetics_rk4_substeps; 0.1.3: NPB_MODE_PRIMARY, reactivity components behind the info block (params.info_reactivity_components); 0.1.2: npb_reset_reference, maintenance table (npb_maint.h, mpump.* columns); 0.1.1: one arena of equally wide columns, npb_locate_field, npb_gather_fields, npb_create_storage */
 #ifndef NPB_API
 #define NPB_API __attribute__((visibility("default")))
 #endif
@@ -217,6 +217,35 @@ NPB_API int npb_set_maintenance_count_buffer(NpbHandle *h, int32_t *counts);
  * capacity, records without a cursor, a capacity without records, or misaligned buffers. */
 NPB_API int npb_set_maintenance_log(NpbHandle *h, void *records, int capacity, uint32_t *cursor);
 NPB_API size_t npb_maint_event_bytes(void);   /* sizeof(npb_maint_event_t) */
+/* The per-plant work-order summary: the maintenance event log folded into first-created / first-completed times and created / completed
+ * counts per (key, plant) (include/npb_maint.h npb_maint_summary_desc_t: the keys, the caller's four tables, since_minutes).  A table of that
+ * size never overflows and never needs draining; it stays on the device beside obs and info.  Needs a maintenance log
+ * (npb_set_maintenance_log): a fold reads the records [*folded, min(*cursor, capacity)) and updates the tables, in one launch of a fixed
+ * grid that takes its range from the device words; the host never learns the cursor and nothing synchronises.  With a summary set,
+ * npb_step folds behind its rule kernel(s) and each of npb_perform_maintenance / _component_maintenance / _turbine_maintenance behind its
+ * kernel, so the summary is current after every call that can append records; npb_maint_summary_fold folds explicitly.
+ * The two device words `folded` and `dropped` (uint32, the caller's, zero to begin with) are the summary's bookkeeping:
+ *   keep mode (consume = 0): the log stays the caller's to drain.  After a fold *folded = min(*cursor, capacity) and *dropped =
+ *     max(*cursor - capacity, 0).  A caller that zeroes the cursor zeroes *folded with it.
+ *   consume mode (consume = 1): the log is only a staging ring of the summary.  After a fold *dropped += max(*cursor - capacity, 0),
+ *     *cursor = 0 and *folded = 0: the log never fills up over a long run.  It needs capacity >= n_plants -- a capacity the events of
+ *     one call can exceed whenever every plant has one would lose events silently as a matter of course; what is lost beyond that is
+ *     counted in *dropped, never hidden.
+ * The cursor is rewritten by the last block to finish (one atomic ticket), after every record of the fold has been read; no block waits
+ * for another.  The fold must run on the stream the appending calls run on.
+ * The summary is output only, like the log: npb_snapshot / npb_restore, the autoreset and the start bank neither read nor reset it; a
+ * caller who wants per-episode summaries clears the plants it restarted (npb_maint_summary_clear).  desc = NULL turns it off, and so does
+ * turning the log off; a handle without a summary behaves exactly as before.
+ * NPB_EINVAL, with the reason in npb_last_error, for: no maintenance log set; n_keys outside 1..NPB_MAINT_SUMMARY_MAX_KEYS; a catalog,
+ * action or unit outside its catalog; a `kinds` without a kind of the key's catalog; a NULL or misaligned table or word; consume with a
+ * log capacity below n_plants.  npb_maint_summary_check is that check alone, without a handle: NULL = accepted, else the reason
+ * (log_capacity < 0 = no log set). */
+NPB_API int npb_set_maintenance_summary(NpbHandle *h, const npb_maint_summary_desc_t *desc);
+NPB_API const char *npb_maint_summary_check(const npb_maint_summary_desc_t *desc, int log_capacity, int n_plants);
+NPB_API int npb_maint_summary_fold(NpbHandle *h, void *stream);
+/* the rows of the plants of mask (device uint8[n_plants]; NULL = all) back to +inf and 0, for every key; asynchronous on `stream`.
+ * NPB_EINVAL without a summary. */
+NPB_API int npb_maint_summary_clear(NpbHandle *h, const uint8_t *mask, void *stream);
 /* Operator-ordered maintenance: FeedwaterPump.perform_maintenance(maintenance_type, **kwargs) (feedwater/pump_system.py:750), i.e. the
  * lubrication system's dispatcher (feedwater/pump_lubrication.py:625-674), called by the USER between two steps: for every plant p
  * with action[p] >= 0, what that call does to pump pump[p] (0..3 = FWP-1..4) of the plant, at once -- no work order, no delay.  All

@@ -335,6 +335,47 @@ typedef struct npb_maint_event_t {
   uint8_t reserved;
 } npb_maint_event_t;
 #define NPB_MAINT_EVENT_BYTES 40
+
+/* ---- the per-plant work-order summary (npb_set_maintenance_summary): the event log folded, on the device, into four numbers per (key, plant)
+ * -- what the data-gen runner returns of a finished scenario (whether the target action fired, work orders created and executed after
+ * tracking_start_hours, and when: maintenance_scenario_runner.py:431-468) and what the timing optimiser reads of a probe run (the time the
+ * target action first fired: optimization/timing_optimizer.py:273-320).
+ * A key selects records: `catalog` NPB_MAINT_CATALOG_* (a record's catalog follows from its kind: NPB_MAINT_EVENT_CREATED, _COMPLETED and
+ * _OPERATOR are feedwater, _OPERATOR_COMPONENT, _COMPONENT_CREATED and _COMPONENT_COMPLETED are component, _OPERATOR_TURBINE is turbine),
+ * `action` the index into that catalog (NPB_MA_* / NPB_CA_*, NPB_CA_AUTO_CONDENSER_TUBE_PLUGGING included / NPB_TA_*) or -1 = any action of
+ * it, `unit` the record's pump / unit byte or -1 = any, `kinds` a mask over NPB_MAINT_EVENT_*: bit k = records of kind k match.  One
+ * record may match several keys.
+ * For key j and plant p the caller owns four device tables, member-major, element [j * n_plants + p]:
+ *   first_created    double, +inf = never     n_created    int32
+ *   first_completed  double, +inf = never     n_completed  int32
+ * A matching record of a creation kind (_CREATED, _COMPONENT_CREATED) feeds the created pair, one of any other kind the completed pair: an
+ * operator action counts as a completion at the time of the call.  The time is the record's `time` [plant minutes, fp64 under either
+ * storage type]; records with time < since_minutes are dropped (the runner's tracking_start_hours).
+ * Several records of one fold may hit one cell (the four pumps of a plant can each create oil_top_off in one step): counts move by integer
+ * atomic adds, times by a 64-bit UNSIGNED atomic minimum on the double's bit pattern.  PRECONDITION: every record's time is >= +0.0 -- a
+ * plant's clock starts at 0 and only grows -- so that the order of the bit patterns is the order of the values; a negative time, -0.0 or a
+ * NaN has a larger pattern than +inf and never wins.  The tables are therefore a function of the SET of records folded, bit for bit,
+ * whatever order the device visits them in.  The caller initialises them with the bit pattern of +inf and 0 (npb_maint_summary_clear). */
+#define NPB_MAINT_SUMMARY_MAX_KEYS 16
+enum { NPB_MAINT_CATALOG_FEEDWATER = 0, NPB_MAINT_CATALOG_COMPONENT = 1, NPB_MAINT_CATALOG_TURBINE = 2, NPB_MAINT_NCATALOG = 3 };
+/* the record kinds of each catalog, as masks over NPB_MAINT_EVENT_*, and the creation kinds among them */
+#define NPB_MAINT_CATALOG_KINDS(c) ((c) == NPB_MAINT_CATALOG_FEEDWATER ? 0x07u : (c) == NPB_MAINT_CATALOG_COMPONENT ? 0x68u : (c) == NPB_MAINT_CATALOG_TURBINE ? 0x10u : 0u)
+#define NPB_MAINT_CREATION_KINDS 0x21u
+typedef struct npb_maint_summary_key_t {
+  int32_t catalog;        /* NPB_MAINT_CATALOG_* */
+  int32_t action;         /* index into the catalog, -1 = any */
+  int32_t unit;           /* pump 0..3 / the component's or the turbine part's unit, -1 = any */
+  uint32_t kinds;         /* bit k = NPB_MAINT_EVENT_* k matches; at least one kind of the key's catalog */
+} npb_maint_summary_key_t;
+typedef struct npb_maint_summary_desc_t {
+  int32_t n_keys;         /* 1 .. NPB_MAINT_SUMMARY_MAX_KEYS */
+  int32_t consume;        /* 0 = keep mode, 1 = consume mode (include/npb.h npb_set_maintenance_summary) */
+  double since_minutes;
+  npb_maint_summary_key_t keys[NPB_MAINT_SUMMARY_MAX_KEYS];
+  double *first_created, *first_completed;      /* device, [n_keys][n_plants], 8-byte aligned */
+  int32_t *n_created, *n_completed;             /* device, [n_keys][n_plants], 4-byte aligned */
+  uint32_t *folded, *dropped;                   /* device, one word each, 4-byte aligned */
+} npb_maint_summary_desc_t;
 #ifdef __cplusplus
 static_assert(sizeof(npb_maint_event_t) == NPB_MAINT_EVENT_BYTES, "npb_maint_event_t layout");
 static_assert(NPB_MAINT_NPARAM <= 16 && NPB_MAINT_NACT <= 255 && NPB_COMPONENT_NACT <= 255, "npb_maint_event_t field widths");

@@ -333,6 +333,63 @@ class NpbSamplerDesc(ctypes.Structure):
                 ("n_sources", ctypes.c_int), ("sources", ctypes.POINTER(NpbSampleSource))]
 
 
+# include/npb_maint.h npb_maint_summary_desc_t: the per-plant work-order summary (npb_set_maintenance_summary)
+SUMMARY_MAX_KEYS = 16
+SUMMARY_CATALOGS = ("feedwater", "component", "turbine")      # NPB_MAINT_CATALOG_*
+# the record kinds (NPB_MAINT_EVENT_*) of each catalog: (work-order kinds, operator kinds); every kind of a catalog but its creation
+# kind feeds the completed pair
+SUMMARY_KINDS = {"feedwater": ((0, 1), (2,)), "component": ((5, 6), (3,)), "turbine": ((), (4,))}
+SUMMARY_CREATION_KINDS = (0, 5)
+
+
+class NpbMaintSummaryKey(ctypes.Structure):
+    """npb_maint_summary_key_t"""
+    _fields_ = [("catalog", ctypes.c_int32), ("action", ctypes.c_int32), ("unit", ctypes.c_int32), ("kinds", ctypes.c_uint32)]
+
+
+class NpbMaintSummaryDesc(ctypes.Structure):
+    """npb_maint_summary_desc_t: the keys, the caller's four [n_keys][n_plants] device tables and its two bookkeeping words"""
+    _fields_ = [("n_keys", ctypes.c_int32), ("consume", ctypes.c_int32), ("since_minutes", ctypes.c_double),
+                ("keys", NpbMaintSummaryKey * SUMMARY_MAX_KEYS),
+                ("first_created", ctypes.c_void_p), ("first_completed", ctypes.c_void_p),
+                ("n_created", ctypes.c_void_p), ("n_completed", ctypes.c_void_p),
+                ("folded", ctypes.c_void_p), ("dropped", ctypes.c_void_p)]
+
+
+def summary_key(key, operator: bool = False):
+    """One key of ``BatchedPlantEnv.enable_maintenance_summary`` -> (catalog, action, unit, kinds) as npb_maint_summary_key_t holds them
+    (host only, no library needed).  ``key`` is a plain action name of the feedwater catalog, or (catalog_name, action_name_or_None,
+    unit_or_None); a component or turbine action may be given as (kind, name), as ``component_action_index`` / ``turbine_action_index``
+    take it, since a bare name can occur under several kinds; an index is taken as it is.  The kinds are the work-order kinds of the
+    catalog; ``operator`` adds the operator kinds.  ValueError for an unknown catalog or name and for a key that can match nothing (the
+    turbine has no work orders: its keys need ``operator=True``)."""
+    if isinstance(key, str):
+        key = ("feedwater", key, None)
+    catalog, action, unit = key
+    if catalog not in SUMMARY_CATALOGS:
+        raise ValueError("unknown catalog %r: one of %r" % (catalog, SUMMARY_CATALOGS))
+    if action is None:
+        a = -1
+    elif catalog == "feedwater":
+        a = maint_action_index(action)
+    elif isinstance(action, tuple):
+        a = CMAINT_AUTO_ACTIONS[action] if catalog == "component" and action in CMAINT_AUTO_ACTIONS else \
+            component_action_index(*action) if catalog == "component" else turbine_action_index(*action)
+    elif isinstance(action, str):
+        names = [k for k, (_kind, name) in enumerate(COMPONENT_ACTIONS if catalog == "component" else TURBINE_ACTIONS) if name == action]
+        names += [v for (k, name), v in CMAINT_AUTO_ACTIONS.items() if catalog == "component" and name == action]
+        if len(names) != 1:
+            raise ValueError("%s maintenance %r names %d entries of the %s catalog: give it as (kind, name)" % (catalog, action, len(names), catalog))
+        a = names[0]
+    else:
+        a = int(action)
+    work, oper = SUMMARY_KINDS[catalog]
+    kinds = sum(1 << k for k in work + (oper if operator else ()))
+    if not kinds:
+        raise ValueError("a key of the %s catalog matches nothing without operator=True: it has no work orders" % catalog)
+    return SUMMARY_CATALOGS.index(catalog), a, -1 if unit is None else int(unit), kinds
+
+
 _lib = None
 
 
@@ -479,6 +536,12 @@ def load():
         L.npb_sampler_create.argtypes = [vp, ctypes.POINTER(NpbSamplerDesc), ctypes.POINTER(ci)]
         L.npb_sampler_sample.argtypes = [vp, ci, vp, vp]
         L.npb_sampler_destroy.argtypes = [vp, ci]
+    if hasattr(L, "npb_set_maintenance_summary"):     # ABI 154: the event log folded into a per-plant work-order summary
+        L.npb_set_maintenance_summary.argtypes = [vp, ctypes.POINTER(NpbMaintSummaryDesc)]
+        L.npb_maint_summary_check.argtypes = [ctypes.POINTER(NpbMaintSummaryDesc), ci, ci]
+        L.npb_maint_summary_check.restype = ctypes.c_char_p
+        L.npb_maint_summary_fold.argtypes = [vp, vp]
+        L.npb_maint_summary_clear.argtypes = [vp, vp, vp]
     if L.npb_num_f64() != SCHEMA.total_f64 or L.npb_num_i32() != SCHEMA.total_i32:
         raise NpbError("libnpb.so was built against a different include/npb_fields.h (%d/%d vs %d/%d): rebuild"
                        % (L.npb_num_f64(), L.npb_num_i32(), SCHEMA.total_f64, SCHEMA.total_i32))

@@ -37,6 +37,9 @@ struct NpbHandle {
   int32_t *maint_counts;           /* npb_set_maintenance_count_buffer: the caller's [n_plants] int32 column, or NULL */
   npd_maint_log_t maint_log;       /* npb_set_maintenance_log: the caller's records and cursor, or NULL; no records = no cursor and capacity 0 */
   bool maint_cache_stale;          /* the cooldown cache of the step kernels' maintenance screen must be zeroed before the next step */
+  /* npb_set_maintenance_summary: the caller's keys, tables and words, and the fold kernel's ticket word (device, zero between folds; allocated
+   * when a summary is first set) */
+  bool summary_on; npb_maint_summary_desc_t summary; uint32_t *summary_ticket;
   int last_kernel;                 /* NPB_KERNEL_*: what the last npb_step launched */
   int step_kernel;                 /* 0 = chosen by batch size, 1 = one-wave kernel, 2 = two-wave kernel, 3 = its two-waves-per-SIMD build, 4 = one-wave with streaming stores, 5 = four-wave kernel (npb_set_step_kernel) */
   npb_maint_table_t maint_table;   /* thresholds of the automatic maintenance (include/npb_maint.h) */
@@ -423,6 +426,7 @@ int npb_destroy(NpbHandle *h) {
   if (h->plan_dev) (void)hipFree(h->plan_dev);
   if (h->snap) (void)hipFree(h->snap);
   if (h->cm_side) (void)hipFree(h->cm_side);
+  if (h->summary_ticket) (void)hipFree(h->summary_ticket);
   for (auto &sd : h->side) { side_free(&sd.snap); side_free(&sd.bank); }
   if (h->ep_len) (void)hipFree(h->ep_len);
   if (h->bank) (void)hipFree(h->bank);
@@ -537,11 +541,78 @@ int npb_set_maintenance_log(NpbHandle *h, void *records, int capacity, uint32_t 
   if (records && !cursor) return fail(h, NPB_EINVAL, "npb_set_maintenance_log: records without a cursor");
   if (!records && capacity > 0) return fail(h, NPB_EINVAL, "npb_set_maintenance_log: a capacity without records");
   if (((uintptr_t)records & 7u) || ((uintptr_t)cursor & 3u)) return fail(h, NPB_EINVAL, "npb_set_maintenance_log: records must be 8-byte and the cursor 4-byte aligned");
+  if (h->summary_on && records && h->summary.consume && capacity < h->n_plants)      /* the summary's own condition on the log it consumes */
+    return fail(h, NPB_EINVAL, npb_maint_summary_check(&h->summary, capacity, h->n_plants));
   h->maint_log = npd_maint_log_t{(npb_maint_event_t *)records, records ? cursor : nullptr, records ? capacity : 0};
   h->maint_cache_stale = true;     /* the log's descriptor travels with the rule's constants: uploaded before the next step */
+  if (!records) h->summary_on = false;      /* no log, nothing to fold */
   return NPB_OK;
 }
 size_t npb_maint_event_bytes(void) { return sizeof(npb_maint_event_t); }
+
+/* the per-plant work-order summary (include/npb.h npb_set_maintenance_summary, npd_maint_summary.h) */
+const char *npb_maint_summary_check(const npb_maint_summary_desc_t *D, int log_capacity, int n_plants) {
+  if (!D) return "npb_set_maintenance_summary: no descriptor";
+  if (log_capacity < 0) return "npb_set_maintenance_summary: no maintenance log set (npb_set_maintenance_log first): the summary is folded from its records";
+  if (D->n_keys < 1 || D->n_keys > NPB_MAINT_SUMMARY_MAX_KEYS) return "npb_set_maintenance_summary: n_keys must be 1..16 (NPB_MAINT_SUMMARY_MAX_KEYS)";
+  for (int j = 0; j < D->n_keys; j++) {
+    const npb_maint_summary_key_t &K = D->keys[j];
+    if (K.catalog < 0 || K.catalog >= NPB_MAINT_NCATALOG) return "npb_set_maintenance_summary: a key's catalog is none of NPB_MAINT_CATALOG_*";
+    /* actions of the catalog (the component catalog with the one automatic action behind it) and the units of the action's kind, or of
+     * the catalog's widest kind for "any action" */
+    const int nact = K.catalog == NPB_MAINT_CATALOG_FEEDWATER ? NPB_MAINT_NACT : K.catalog == NPB_MAINT_CATALOG_COMPONENT ? NPB_COMPONENT_NACT + 1 : NPB_TURBINE_NACT;
+    if (K.action < -1 || K.action >= nact) return "npb_set_maintenance_summary: a key's action is outside its catalog (-1 = any)";
+    int units;
+    if (K.catalog == NPB_MAINT_CATALOG_FEEDWATER) units = NPB_NUM_PUMPS;
+    else if (K.catalog == NPB_MAINT_CATALOG_COMPONENT)
+      units = K.action < 0 ? NPB_COMPONENT_UNITS(NPB_COMPONENT_SG) : K.action == NPB_CA_AUTO_CONDENSER_TUBE_PLUGGING ? 1 : NPB_COMPONENT_UNITS(g_component_actions[K.action].kind);
+    else units = K.action < 0 ? NPB_TURBINE_UNITS(NPB_TURBINE_STAGE) : NPB_TURBINE_UNITS(g_turbine_actions[K.action].kind);
+    if (K.unit < -1 || K.unit >= units) return "npb_set_maintenance_summary: a key's unit is outside its catalog (-1 = any)";
+    if (!(K.kinds & NPB_MAINT_CATALOG_KINDS(K.catalog))) return "npb_set_maintenance_summary: a key's kinds are empty: no NPB_MAINT_EVENT_* kind of its catalog";
+  }
+  if (!D->first_created || !D->first_completed || !D->n_created || !D->n_completed || !D->folded || !D->dropped)
+    return "npb_set_maintenance_summary: the four tables and the folded / dropped words must not be NULL";
+  if (((uintptr_t)D->first_created & 7u) || ((uintptr_t)D->first_completed & 7u) || ((uintptr_t)D->n_created & 3u) || ((uintptr_t)D->n_completed & 3u) ||
+      ((uintptr_t)D->folded & 3u) || ((uintptr_t)D->dropped & 3u))
+    return "npb_set_maintenance_summary: the time tables must be 8-byte, the count tables and the words 4-byte aligned";
+  if (D->consume && log_capacity < n_plants)
+    return "npb_set_maintenance_summary: consume mode needs a log capacity of at least n_plants records, or it loses events as a matter of course";
+  return nullptr;
+}
+int npb_set_maintenance_summary(NpbHandle *h, const npb_maint_summary_desc_t *desc) {
+  if (!h) return NPB_EINVAL;
+  if (!desc) { h->summary_on = false; return NPB_OK; }
+  if (const char *why = npb_maint_summary_check(desc, h->maint_log.cursor ? h->maint_log.capacity : -1, h->n_plants)) return fail(h, NPB_EINVAL, why);
+  if (!h->summary_ticket) {
+    NPB_USE_DEVICE(h);
+    hipError_t e = hipMalloc((void **)&h->summary_ticket, 256);
+    if (e != hipSuccess) { h->summary_ticket = nullptr; return fail(h, NPB_EHIP, "npb_set_maintenance_summary: hipMalloc of the ticket word failed", e); }
+    NPB_HIP(h, hipMemset(h->summary_ticket, 0, 256));
+  }
+  h->summary = *desc;
+  h->summary_on = true;
+  return NPB_OK;
+}
+/* behind every kernel that can append records, on its stream */
+static void summary_fold(NpbHandle *h, hipStream_t stream) {
+  if (h->summary_on) npb_launch_maint_summary_fold(&h->summary, h->maint_log, h->summary_ticket, h->n_plants, stream);
+}
+int npb_maint_summary_fold(NpbHandle *h, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->summary_on) return fail(h, NPB_EINVAL, "npb_maint_summary_fold: no summary set (npb_set_maintenance_summary first)");
+  NPB_USE_DEVICE(h);
+  summary_fold(h, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_maint_summary_clear(NpbHandle *h, const uint8_t *mask, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->summary_on) return fail(h, NPB_EINVAL, "npb_maint_summary_clear: no summary set (npb_set_maintenance_summary first)");
+  NPB_USE_DEVICE(h);
+  npb_launch_maint_summary_clear(&h->summary, mask, h->n_plants, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
 
 int npb_perform_maintenance(NpbHandle *h, const int32_t *action, const int32_t *pump, const int32_t *bearing, const double *target_level,
                             uint8_t *success, void *stream) {
@@ -555,6 +626,7 @@ int npb_perform_maintenance(NpbHandle *h, const int32_t *action, const int32_t *
    * action is not counted in maintenance_actions_performed.  The log's descriptor travels as a kernel argument, so the call does not
    * depend on the rule's constants having been uploaded (they are only with params.maint_enabled). */
   h->K->operator_maint(h->n_plants, NPB_N(h), h->f64, action, pump, bearing, target_level, success, h->maint_log, (hipStream_t)stream);
+  summary_fold(h, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -571,6 +643,7 @@ int npb_perform_component_maintenance(NpbHandle *h, const int32_t *action, const
                        : h->params.mode == NPB_MODE_PRIMARY_SG ? (1u << NPB_COMPONENT_SG) | (1u << NPB_COMPONENT_SGSYS) : 0u;
   h->K->operator_component_maint(h->n_plants, NPB_N(h), h->f64, action, unit, option, amount, success, kinds, h->maint_log,
                                  (hipStream_t)stream);
+  summary_fold(h, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -583,6 +656,7 @@ int npb_perform_turbine_maintenance(NpbHandle *h, const int32_t *action, const i
    * carries no turbine.  maint_cache_stale is left alone, as in npb_perform_maintenance: no handler here writes a pump, a stamp or the table. */
   h->K->operator_turbine_maint(h->n_plants, NPB_N(h), h->f64, action, unit, success, h->params.mode == NPB_MODE_FULL, h->maint_log,
                                (hipStream_t)stream);
+  summary_fold(h, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -925,6 +999,7 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
     h->K->maint_all(NPB_N(h), h->f64, h->maint_side, h->cm_side, h->maint_counts, h->n_plants, h->diag, h->diag_pitch, (hipStream_t)stream);
   else if (maint && h->params.mode != NPB_MODE_FULL)   /* a full-mode step kernel has run the rule itself, for the waves whose pump phase found something */
     h->K->maint(NPB_N(h), h->f64, h->maint_side, h->maint_counts, h->n_plants, (hipStream_t)stream);
+  if (maint) summary_fold(h, (hipStream_t)stream);      /* the rule has appended this step's records: the summary is current when the call returns */
   if (h->autoreset)   /* same stream, nothing read back, the maintenance cache kept per plant by the kernel itself */
     h->K->episode(h->params.mode, h->n_plants, NPB_N(h), h->f64, source_of(h, from_bank), done, reward, obs, counters_of(h),
                   h->ep_out_len, h->ep_out_ret, h->ep_out_truncated, h->ep_final_obs, h->max_episode_steps,

@@ -98,6 +98,11 @@ void npb_launch_diag_carried_pack(const double *live, size_t live_pitch, double 
 typedef struct { double v[NPB_DIAG_NUM_CARRIED]; } npb_diag_carried_values_t;
 void npb_launch_diag_carried_put(double *live, size_t live_pitch, const uint8_t *mask, int n_plants, size_t lanes, npb_diag_carried_values_t values,
                                  hipStream_t stream);
+/* npb_set_maintenance_summary (npd_maint_summary.h): one fold of the log's records [*D->folded, min(*log.cursor, log.capacity)) into the
+ * caller's tables, the bookkeeping words rewritten by the last block (ticket: the handle's device word, zero between folds); and the rows of
+ * the plants of mask (NULL = all) back to +inf and 0 */
+void npb_launch_maint_summary_fold(const npb_maint_summary_desc_t *D, npd_maint_log_t log, uint32_t *ticket, int n_plants, hipStream_t stream);
+void npb_launch_maint_summary_clear(const npb_maint_summary_desc_t *D, const uint8_t *mask, int n_plants, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

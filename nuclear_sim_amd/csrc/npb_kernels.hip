@@ -1667,6 +1667,8 @@ extern "C" void npb_launch_diag_carried_put(double *live, size_t live_pitch, con
   hipLaunchKernelGGL(npb_diag_carried_put_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, live, live_pitch, mask, n_plants, lanes,
                      values);
 }
+/* the per-plant work-order summary folded from the event log (npb_set_maintenance_summary): its kernels and launchers */
+#include "npd_maint_summary.h"
 #endif
 /* the state log's sampling step for a watch list (npb_sampler_sample): one grid row per output row, lanes over the watched plants.
  * Row r < n_fields is an arena member, addressed as npb_gather_kernel addresses it with the plant ids[j] in place of the lane; the rows

@@ -321,6 +321,15 @@ class BatchedPlantEnv:
     (``component_maintenance_state()`` / ``load_component_maintenance_state()``): resets, ``snapshot`` / ``restore``, the autoreset
     and the start bank take it along; a checkpoint must save it beside ``state_arrays()``.  Off by default: nothing changes.
 
+    Work-order summary: ``enable_maintenance_summary(keys, since_minutes=...)`` has the device fold the maintenance events into four
+    numbers per (key, plant) -- when the first matching work order was created and when the first was completed, and how many were
+    (npb_set_maintenance_summary) -- which is what the data-gen runner returns of a finished scenario and what its timing optimiser
+    reads of a probe run.  ``maintenance_summary()`` returns them as ``[n_keys, n]`` device tensors, the env's own buffers as ``info``
+    is, current after every ``step`` and ``perform_*_maintenance`` call and never synchronised; nothing overflows and nothing needs
+    draining, however long the run.  ``step()`` puts nothing new into ``info``.  Output only, like the event log: ``snapshot``,
+    ``restore``, the autoreset and the start bank leave it alone, ``clear_maintenance_summary(mask)`` starts plants afresh.
+    ``nuclear_sim_amd.timing`` builds the optimiser's question on it: ``trigger_times`` for a batch of probes, ``sweep`` for the search.
+
     Heat-source noise (``noise_enabled``): ``noise_generator="host"`` (the default) draws each plant's
     ``RandomState(seed).standard_normal()`` stream on the host (``HeatSourceNoise``); ``"device"`` generates the same streams on the
     device (``DeviceHeatSourceNoise``: integer state exactly numpy's, every draw within a few ulp), with no host work per step.
@@ -592,9 +601,10 @@ class BatchedPlantEnv:
         not written, until the next drain.  ``None`` turns the log off.  The log is output only: ``snapshot``, ``restore``, the
         autoreset and the start bank neither read nor reset it, so a plant's episodes are told apart by time alone, and after a
         restore its work-order numbers restart from the restored counters, as a fresh reference simulator's would."""
-        if capacity is None:
+        if capacity is None:      # (without a log there is nothing to fold: the library turns a summary off with it)
             _lib.check(self.L.npb_set_maintenance_log(self._h, None, 0, None), self._h)
             self._mlog = None
+            self._msum = None
             return
         if not self.params.maint_enabled:
             raise ValueError("the maintenance log needs the automatic maintenance (maintenance=True)")
@@ -611,12 +621,22 @@ class BatchedPlantEnv:
         # the drain's landing place: pinned host memory, so that a drain is a DMA copy rather than a staged one
         self._mlog = {"records": records, "cursor": cursor, "capacity": cap, "host": torch.empty(records.numel(), dtype=torch.uint8, pin_memory=True),
                       "host_cursor": torch.empty(1, dtype=torch.int32, pin_memory=True)}
+        ms = getattr(self, "_msum", None)
+        if ms is not None:      # a summary that consumed a staging log of its own now folds the caller's log, and leaves it to the caller
+            ms["desc"].consume = 0
+            ms["words"].zero_()
+            _lib.check(self.L.npb_set_maintenance_summary(self._h, ctypes.byref(ms["desc"])), self._h)
+            ms["consume"] = False
 
     def maintenance_log_records(self, clear: bool = True, allow_overflow: bool = False) -> np.ndarray:
         """Drain the log on the env's stream: the records (numpy, ``maintlog.EVENT_DTYPE``) in the device's order.  An overflowed
         log raises, naming how many events were dropped, and is left as it is, unless ``allow_overflow``."""
         from . import maintlog
         ml = getattr(self, "_mlog", None)
+        ms = getattr(self, "_msum", None)
+        if ms is not None and ms["consume"]:
+            raise _lib.NpbError("the maintenance summary consumes the log (enable_maintenance_summary's staging ring): there is nothing to "
+                                "drain; enable_maintenance_summary(..., keep_log=True) keeps the records")
         if ml is None:
             raise _lib.NpbError("no maintenance log: enable_maintenance_log() first")
         stream = torch.cuda.current_stream(self.device)
@@ -634,6 +654,8 @@ class BatchedPlantEnv:
         rec = ml["host"][:nb].numpy().view(maintlog.EVENT_DTYPE).copy()
         if clear:
             ml["cursor"].zero_()
+            if ms is not None:      # the summary has folded what was drained: its mark goes back with the cursor
+                ms["words"][0].zero_()
         return rec
 
     def maintenance_log(self, clear: bool = True, allow_overflow: bool = False) -> Dict[str, np.ndarray]:
@@ -650,6 +672,86 @@ class BatchedPlantEnv:
         """Drain the log into a CSV (``.csv``) or Parquet file"""
         from . import maintlog
         maintlog.write(self.maintenance_log(clear=clear, allow_overflow=allow_overflow), path)
+
+    def enable_maintenance_summary(self, keys, since_minutes: float = 0.0, keep_log: bool = False, operator: bool = False,
+                                   log_capacity: Optional[int] = None, include_logged: bool = False) -> None:
+        """Have the device fold the maintenance events into a per-plant summary (npb_set_maintenance_summary): per key and plant the time
+        the first matching work order was created and the first was completed, and how many were -- what the data-gen runner returns of a
+        finished scenario (maintenance_scenario_runner.py:431-468) and what the timing optimiser reads of a probe run
+        (timing_optimizer.py:273-320), without draining anything.  ``keys``: up to 16, each a plain action name of the feedwater catalog or
+        ``(catalog_name, action_name_or_None, unit_or_None)`` with the catalogs "feedwater", "component", "turbine" (None = any;
+        ``_lib.summary_key``).  A key matches the work-order records of its catalog; ``operator=True`` adds the actions a caller ordered
+        (``perform_*_maintenance``), which count as completions at the time of the call.  Records before ``since_minutes`` (plant clock) are
+        dropped: the runner's tracking_start_hours.  ``None`` for ``keys`` turns the summary off.
+
+        The summary is folded from the event log behind every step and every ``perform_*_maintenance`` call, on the device, with no
+        synchronisation.  Without a log of the caller's (``enable_maintenance_log``) it allocates a staging log of ``max(4 * n, 4096)``
+        records (``log_capacity`` overrides it; at least n) -- four creations per plant and step -- and consumes it at every fold, so nothing fills up over a long run and
+        ``maintenance_log*()`` refuses; with the caller's log, or with ``keep_log=True``, the records stay for the caller to drain.  Events
+        that did not fit the log are counted in ``maintenance_summary()["dropped"]``.  ``include_logged=True`` also folds, at once, the
+        records the caller's log already holds: an existing log summarised under new keys.  Output only, like the log: ``snapshot``,
+        ``restore``, the autoreset and the start bank leave it alone; ``clear_maintenance_summary(mask)`` starts the masked plants afresh."""
+        if keys is None:
+            if getattr(self, "_msum", None) is not None:
+                _lib.check(self.L.npb_set_maintenance_summary(self._h, None), self._h)
+                if self._msum["own_log"]:
+                    self._msum = None
+                    self.enable_maintenance_log(None)
+                self._msum = None
+            return
+        K = [_lib.summary_key(k, operator=operator) for k in keys]      # an unknown name is refused before any device work
+        if not 1 <= len(K) <= _lib.SUMMARY_MAX_KEYS:
+            raise ValueError("a maintenance summary has 1 to %d keys, not %d" % (_lib.SUMMARY_MAX_KEYS, len(K)))
+        if not hasattr(self.L, "npb_set_maintenance_summary"):
+            raise _lib.NpbError("libnpb.so has no npb_set_maintenance_summary (older than ABI 154): rebuild")
+        prev = getattr(self, "_msum", None)
+        own_log = getattr(self, "_mlog", None) is None or (prev is not None and prev["own_log"])
+        if own_log:
+            self._msum = None
+            self.enable_maintenance_log(max(4 * self.n, 4096) if log_capacity is None else int(log_capacity))
+        consume = own_log and not keep_log
+        with torch.cuda.device(self.device):
+            times = torch.full((2, len(K), self.n), float("inf"), dtype=torch.float64, device=self.device)
+            counts = torch.zeros((2, len(K), self.n), dtype=torch.int32, device=self.device)
+            words = torch.zeros(2, dtype=torch.int32, device=self.device)      # folded, dropped: uint32 on the device
+        d = _lib.NpbMaintSummaryDesc()
+        d.n_keys, d.consume, d.since_minutes = len(K), int(consume), float(since_minutes)
+        for j, (catalog, action, unit, kinds) in enumerate(K):
+            d.keys[j].catalog, d.keys[j].action, d.keys[j].unit, d.keys[j].kinds = catalog, action, unit, kinds
+        d.first_created, d.first_completed = times[0].data_ptr(), times[1].data_ptr()
+        d.n_created, d.n_completed = counts[0].data_ptr(), counts[1].data_ptr()
+        d.folded, d.dropped = words[0:].data_ptr(), words[1:].data_ptr()
+        if not consume and not include_logged:      # records already in the caller's log are not this summary's: it starts at the cursor
+            words[0:1].copy_(self._mlog["cursor"])      # (a cursor past the capacity: the fold starts at the capacity)
+        _lib.check(self.L.npb_set_maintenance_summary(self._h, ctypes.byref(d)), self._h)
+        self._msum = {"desc": d, "times": times, "counts": counts, "words": words, "keys": K, "consume": consume, "own_log": own_log}
+        if include_logged:      # summarise what the caller's log already holds, under these keys, at once
+            self.fold_maintenance_summary()
+
+    def maintenance_summary(self) -> Dict[str, torch.Tensor]:
+        """The summary's tables, [n_keys, n] each, on the device: ``first_created`` / ``first_completed`` (plant minutes, float64, +inf =
+        never), ``n_created`` / ``n_completed`` (int32), and ``dropped`` (a 0-d int32 tensor: events the log had no room for, which the
+        summary therefore never saw).  The env's own buffers, as ``info`` is: current after every ``step`` and ``perform_*_maintenance``,
+        valid in stream order, never synchronised here."""
+        ms = getattr(self, "_msum", None)
+        if ms is None:
+            raise _lib.NpbError("no maintenance summary: enable_maintenance_summary() first")
+        return {"first_created": ms["times"][0], "first_completed": ms["times"][1], "n_created": ms["counts"][0],
+                "n_completed": ms["counts"][1], "dropped": ms["words"][1]}
+
+    def clear_maintenance_summary(self, mask=None) -> None:
+        """the summary rows of the masked plants (None = all) back to "never" and 0 (npb_maint_summary_clear): what a caller does for the
+        plants it restarted when it wants per-episode summaries"""
+        if getattr(self, "_msum", None) is None:
+            raise _lib.NpbError("no maintenance summary: enable_maintenance_summary() first")
+        m = None if mask is None else self._col(mask, torch.uint8)
+        _lib.check(self.L.npb_maint_summary_clear(self._h, None if m is None else self._p(m), self._stream()), self._h)
+
+    def fold_maintenance_summary(self) -> None:
+        """fold the log into the summary now (npb_maint_summary_fold); ``step`` and the ``perform_*_maintenance`` calls do it themselves"""
+        if getattr(self, "_msum", None) is None:
+            raise _lib.NpbError("no maintenance summary: enable_maintenance_summary() first")
+        _lib.check(self.L.npb_maint_summary_fold(self._h, self._stream()), self._h)
 
     def _order_buffers(self):
         """the buffers the perform_*_maintenance methods keep for their order columns, with the ``success`` column they all return"""

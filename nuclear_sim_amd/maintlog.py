@@ -156,6 +156,46 @@ def _component_rows(kind: int):
     return [name for k, name in CMAINT_PARAMS if k == COMPONENT_KINDS[kind]]
 
 
+def summary_keys(keys, operator: bool = False):
+    """the keys of a summary as (catalog, action, unit, kinds) integers (include/npb_maint.h npb_maint_summary_key_t): each a plain
+    feedwater action name, a (catalog_name, action_or_None, unit_or_None) triple (``_lib.summary_key``), or four integers taken as they are"""
+    from ._lib import summary_key
+    return [tuple(int(x) for x in k) if not isinstance(k, str) and len(k) == 4 else summary_key(k, operator=operator) for k in keys]
+
+
+def summarize(records: np.ndarray, keys, n_plants: int, since_minutes: float = 0.0, operator: bool = False) -> Dict[str, np.ndarray]:
+    """The per-plant work-order summary of drained records: what the device folds the log into (npb_set_maintenance_summary), restated
+    over numpy -- the reduction the device's tables are held to, bit for bit.  Per key j and plant p: ``first_created`` /
+    ``first_completed`` (float64 [n_keys, n_plants], +inf = never) and ``n_created`` / ``n_completed`` (int32).  A record's catalog follows
+    from its kind (0, 1, 2 feedwater; 3, 5, 6 component; 4 turbine); it matches a key of its catalog whose ``kinds`` mask has its kind and
+    whose action and unit are its own or -1; a creation kind (CREATED, COMPONENT_CREATED) feeds the created pair, any other the completed
+    pair; records with ``time < since_minutes`` are dropped (the data-gen runner's tracking_start_hours,
+    maintenance_scenario_runner.py:431-468).  ``keys`` as ``summary_keys`` takes them."""
+    from ._lib import SUMMARY_CATALOGS, SUMMARY_CREATION_KINDS, SUMMARY_KINDS
+    rec = np.asarray(records, dtype=EVENT_DTYPE)
+    K = summary_keys(keys, operator=operator)
+    n = int(n_plants)
+    out = {"first_created": np.full((len(K), n), np.inf), "first_completed": np.full((len(K), n), np.inf),
+           "n_created": np.zeros((len(K), n), dtype=np.int32), "n_completed": np.zeros((len(K), n), dtype=np.int32)}
+    catalog_of = np.full(256, -1, dtype=np.int64)
+    for c, name in enumerate(SUMMARY_CATALOGS):
+        for k in SUMMARY_KINDS[name][0] + SUMMARY_KINDS[name][1]:
+            catalog_of[k] = c
+    kind = rec["kind"].astype(np.int64)
+    live = (~(rec["time"] < since_minutes)) & (rec["plant"] >= 0) & (rec["plant"] < n) & (catalog_of[kind] >= 0)
+    creation = np.isin(kind, SUMMARY_CREATION_KINDS)
+    for j, (catalog, action, unit, kinds) in enumerate(K):
+        m = live & (catalog_of[kind] == catalog) & (((kinds >> np.minimum(kind, 62)) & 1) == 1)
+        if action >= 0:
+            m &= rec["action"] == action
+        if unit >= 0:
+            m &= rec["pump"] == unit
+        for sel, first, count in ((m & creation, "first_created", "n_created"), (m & ~creation, "first_completed", "n_completed")):
+            np.minimum.at(out[first][j], rec["plant"][sel], rec["time"][sel])
+            np.add.at(out[count][j], rec["plant"][sel], 1)
+    return out
+
+
 def table(cols: Dict[str, np.ndarray]):
     """pyarrow Table of ``columns``' output"""
     import pyarrow as pa
