@@ -582,7 +582,9 @@ NPB_API int npb_noise_set_state(NpbHandle *h, const uint32_t *key, const int32_t
  * about 2.5 KB a plant again, allocated on first use, freed by npb_destroy; independent of npb_noise_*, so both can be on) drawn by the
  * same fill kernel into a block the handle owns, and a filter kernel that turns the block into rows.  Given the draws, the filter's rows
  * are exactly numpy's (no contraction, IEEE division); the draws are within a few ulp of numpy's, as npb_noise_fill's are.
- * All plants advance together: the handle keeps ONE position, the rows made of the current profile.  A block may cross a profile's end:
+ * All plants advance together: the handle keeps ONE position, the rows made of the current profile -- unless episode streams are on
+ * (npb_set_episode_streams below), where every plant has a position of its own and restarts its profile with its episode.  A block may
+ * cross a profile's end:
  * the profile's last row takes no draw, and the next row starts the next profile of the same horizon from the next draw, its ramp
  * afresh (first setpoint = first target) -- a second runner on the same stream.
  * Generator state: after R rows in all (q whole profiles and r = R mod steps rows of the next) every generator is numpy's
@@ -610,6 +612,57 @@ NPB_API int npb_profile_ramp(NpbHandle *h, int k, const double *target_in, doubl
 NPB_API int npb_profile_get_state(NpbHandle *h, uint32_t *key, int32_t *pos, int32_t *has_gauss, double *cached, double *carried, int32_t *position, void *stream);
 NPB_API int npb_profile_set_state(NpbHandle *h, const uint32_t *key, const int32_t *pos, const int32_t *has_gauss, const double *cached, const double *carried,
                                   int32_t position, void *stream);
+
+/* Episode streams: each plant's heat-source noise and power profile restart with its episode.  Off (the default) the two streams run
+ * on across restarts as described above; on, every (plant, episode) takes the rows a freshly built runner of its scenario would: the
+ * reference's runner builds a new ConstantHeatSource(seed 42) and draws a new load profile for every run
+ * (maintenance_scenario_runner.py:210-244, :586-671).  nuclear_sim_amd/scenarios.py episode_stream_rows is the readable statement.
+ * While the mode is on the HANDLE owns the streams' consumption: [block][n] blocks of noise, setpoint and target rows of its own, one
+ * cursor per stream, and per plant the row of its current profile (int32) in place of the single position.  npb_step given a NULL noise_z
+ * (with noise generators) or a NULL power_setpoint (with a profile) takes the handle's current row of that stream and moves that cursor;
+ * an explicit column is used as before and consumes no row of that stream.  A block that has run out is made again, for every plant from
+ * where its streams are, before the step that needs it.  Nothing is read back and nothing synchronises.
+ * A plant RESTARTS wherever its episode index is bumped: the autoreset behind npb_step, npb_restore, npb_restore_bank, and npb_reset /
+ * npb_reset_reference for the plants of their mask.  On the same stream, behind that call's own kernels, a restart kernel then gives the
+ * plant both streams of its new episode from their beginning: both generators seeded anew, the profile's position, rows made and carried
+ * values zeroed -- the ramp starts afresh, first setpoint = first target --, and the rows drawn ahead for it in the handle's blocks made
+ * again from the new streams, so that no row of the old episode reaches a step.  (On a block's last row nothing is pending: the next
+ * refill begins the new episode.)  The j-th step after a restart that takes a stream's row takes draw j of the new noise stream, and row
+ * j mod steps of consecutive profiles of the new profile stream.  Seeds: a restart that took bank entry s (what episode_start reports)
+ * uses bank_noise_seeds[s] / bank_profile_seeds[s] where that table was given; every other restart -- from the snapshot, a reset, no
+ * table -- uses the plant's own seed again, as given to npb_noise_seed / npb_profile_seed (the handle keeps them), so a restart from the
+ * snapshot repeats the plant's first episode exactly.  base / std stay with the plant position.
+ * Generator state, per plant: after m rows made since its restart (rows taken plus rows drawn ahead and not yet taken) its noise
+ * generator is numpy's after m calls and its profile generator after m calls plus the one look-ahead when steps >= 3 and m % steps >= 1:
+ * the rule stated above for the whole batch.  A lane draws exactly what its rows use.
+ * npb_set_episode_streams(h, desc, stream): desc = NULL switches the mode off.  It works on whichever of the two generator sets the
+ * handle has (npb_noise_seed, npb_profile_seed); switching on -- and switching off -- is itself a restart of every plant from its own
+ * seeds, with nothing drawn ahead (off: the profile's single position is 0 again).  It needs the autoreset on (npb_set_autoreset: the
+ * restarts are read off the episode index it keeps).  The three output columns (device double[n], the caller's, each may be NULL) receive
+ * the rows each step takes from the handle's streams: noise_out the noise_z, setpoint_out the setpoint, target_out the row before the
+ * ramp (the runner's target_power); a step given that column explicitly leaves them as they were.  They are written on the step's stream
+ * in the restart kernel's launch behind the step, not in a launch of their own.
+ * Everything is validated before any device work and refused by name (npb_last_error; npb_episode_streams_check is that check alone,
+ * without a handle: NULL = accepted): no generators; block < 1; a table without a bank; n_bank_seeds that is not the bank's entry count;
+ * a table seed outside [0, 2^32); generators that were only ever loaded (npb_noise_set_state) and have no seed; no autoreset.  While
+ * tables are set, npb_set_start_bank with another entry count, or with NULL, is REFUSED: switch the mode off first.
+ * While the mode is on npb_noise_fill, npb_profile_fill, npb_noise_set_state, npb_profile_set_state, npb_noise_seed and npb_profile_seed
+ * are refused (NPB_EINVAL, naming the mode); npb_noise_get_state and npb_profile_get_state keep working, the latter reporting position
+ * -1, and npb_profile_get_positions gives the per-plant values (host int32[n] each, either may be NULL; synchronous on `stream`;
+ * NPB_EINVAL without the mode or without a profile).
+ * NOT part of this: checkpointing a handle in this mode in the middle of a block -- the rows drawn ahead and the cursors are not
+ * exported, and the get_state calls give the generators as they are after the rows made.  The arena's own state is unaffected. */
+typedef struct {
+  int block;                                   /* rows per refill, >= 1 */
+  const int64_t *bank_noise_seeds;             /* host int64[n_bank_seeds] or NULL */
+  const int64_t *bank_profile_seeds;           /* host int64[n_bank_seeds] or NULL */
+  int n_bank_seeds;                            /* the bank's entry count when a table is given */
+  double *noise_out, *setpoint_out, *target_out;   /* device double[n] each, or NULL */
+} npb_episode_streams_desc_t;
+NPB_API int npb_set_episode_streams(NpbHandle *h, const npb_episode_streams_desc_t *desc, void *stream);
+/* has_generators: the handle has noise generators or a profile; bank_entries: 0 = no bank */
+NPB_API const char *npb_episode_streams_check(const npb_episode_streams_desc_t *desc, int has_generators, int bank_entries);
+NPB_API int npb_profile_get_positions(NpbHandle *h, int32_t *position /* host [n] */, int32_t *rows_made /* host [n], since the last restart */, void *stream);
 
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the

@@ -9,6 +9,8 @@ from __future__ import annotations
 import ctypes
 import os
 
+import numpy as np
+
 from .schema import PARAMS, SCHEMA
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -390,6 +392,27 @@ def summary_key(key, operator: bool = False):
     return SUMMARY_CATALOGS.index(catalog), a, -1 if unit is None else int(unit), kinds
 
 
+class NpbEpisodeStreamsDesc(ctypes.Structure):
+    """npb_episode_streams_desc_t: the block size, the optional per-bank-entry seed tables (host int64) and the caller's three output columns"""
+    _fields_ = [("block", ctypes.c_int), ("bank_noise_seeds", ctypes.c_void_p), ("bank_profile_seeds", ctypes.c_void_p),
+                ("n_bank_seeds", ctypes.c_int), ("noise_out", ctypes.c_void_p), ("setpoint_out", ctypes.c_void_p), ("target_out", ctypes.c_void_p)]
+
+
+def episode_streams_desc(block, bank_noise_seeds=None, bank_profile_seeds=None, outputs=(None, None, None)):
+    """(desc, keep): an NpbEpisodeStreamsDesc and the host arrays it points into (host only, no library needed).  A table is a sequence of
+    seeds, one per bank entry; both tables, where both are given, have the same length.  ``outputs``: three device addresses or None."""
+    tables = [None if t is None else np.ascontiguousarray(np.asarray(t, dtype=np.int64).reshape(-1)) for t in (bank_noise_seeds, bank_profile_seeds)]
+    sizes = {t.size for t in tables if t is not None}
+    if len(sizes) > 1:
+        raise ValueError("bank_noise_seeds and bank_profile_seeds: one seed per bank entry each (%s)" % sorted(sizes))
+    d = NpbEpisodeStreamsDesc()
+    d.block = int(block)
+    d.bank_noise_seeds, d.bank_profile_seeds = (None if t is None else t.ctypes.data for t in tables)
+    d.n_bank_seeds = sizes.pop() if sizes else 0
+    d.noise_out, d.setpoint_out, d.target_out = outputs
+    return d, tables
+
+
 _lib = None
 
 
@@ -542,6 +565,11 @@ def load():
         L.npb_maint_summary_check.restype = ctypes.c_char_p
         L.npb_maint_summary_fold.argtypes = [vp, vp]
         L.npb_maint_summary_clear.argtypes = [vp, vp, vp]
+    if hasattr(L, "npb_set_episode_streams"):     # (ABI 154 still) each plant's noise and power profile restart with its episode
+        L.npb_set_episode_streams.argtypes = [vp, ctypes.POINTER(NpbEpisodeStreamsDesc), vp]
+        L.npb_episode_streams_check.argtypes = [ctypes.POINTER(NpbEpisodeStreamsDesc), ci, ci]
+        L.npb_episode_streams_check.restype = ctypes.c_char_p
+        L.npb_profile_get_positions.argtypes = [vp, vp, vp, vp]
     if L.npb_num_f64() != SCHEMA.total_f64 or L.npb_num_i32() != SCHEMA.total_i32:
         raise NpbError("libnpb.so was built against a different include/npb_fields.h (%d/%d vs %d/%d): rebuild"
                        % (L.npb_num_f64(), L.npb_num_i32(), SCHEMA.total_f64, SCHEMA.total_i32))

@@ -64,6 +64,11 @@ struct NpbHandle {
   /* npb_profile_seed: the power profile's generators (a second npb_noise_t), its per-plant columns ([NPB_PROFILE_SIDE][pitch]), its
    * horizon and the rows made of the current profile (all plants advance together), and the block its draws go through */
   void *prof; npb_noise_t prof_g; double *prof_side; int prof_steps, prof_pos; double *prof_z; size_t prof_z_rows;
+  /* the seeds npb_noise_seed / npb_profile_seed were last given: each plant's own, which a restart under episode streams uses again */
+  std::vector<uint32_t> noise_seeds, prof_seeds;
+  /* npb_set_episode_streams: the mode's blocks, per-plant columns and seed tables (one allocation, es_mem), as the kernels read them; the
+   * next row of each block a step takes (block = none left); the caller's output columns; whether bank seed tables were given */
+  bool es_on; npb_episode_streams_t es; void *es_mem; int es_noise_cur, es_prof_cur; double *es_noise_out, *es_setpoint_out, *es_target_out; bool es_tables;
   double *ramp_prev;   /* npb_profile_ramp: the previous setpoint of every plant ([pitch], NaN = none yet), allocated on first use */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
   std::vector<int> plan_key;
@@ -217,6 +222,12 @@ static void clear_episodes(NpbHandle *h, const uint8_t *mask, bool counters, hip
   if (len || h->ep_start) npb_launch_episode_clear(mask, len, counters ? h->ep_ret : nullptr, h->ep_index, h->ep_start, h->n_plants, h->pitch, stream);
 }
 static npb_episode_counters_t counters_of(const NpbHandle *h) { return npb_episode_counters_t{h->ep_len, h->ep_ret, h->ep_index, h->ep_out_index}; }
+/* episode streams: the plants whose episode index the call before has bumped begin their streams anew, behind that call's kernels.
+ * from_bank: the restart took bank entries, which the carried start column names */
+static void restart_streams(NpbHandle *h, bool from_bank, hipStream_t stream, const npb_episode_streams_take_t *take = nullptr) {
+  if (h->es_on) npb_launch_episode_streams_restart(&h->es, h->es_noise_cur, h->es_prof_cur, from_bank ? h->ep_start : nullptr, 0, take, stream);
+}
+static const char *const g_es_owns = ": episode streams are on (npb_set_episode_streams) and the handle owns the streams' consumption; switch the mode off first";
 static const struct { int row; double fresh; } g_diag_carried[] = {
 #define NPB__X(row, fresh) {row, fresh},
   NPB_DIAG_CARRIED(NPB__X)
@@ -436,6 +447,7 @@ int npb_destroy(NpbHandle *h) {
   if (h->prof_side) (void)hipFree(h->prof_side);
   if (h->prof_z) (void)hipFree(h->prof_z);
   if (h->ramp_prev) (void)hipFree(h->ramp_prev);
+  if (h->es_mem) (void)hipFree(h->es_mem);
   for (Sampler *sm : h->samplers) if (sm) { (void)hipFree(sm->dev); delete sm; }
   delete h;
   return NPB_OK;
@@ -743,6 +755,7 @@ int npb_reset(NpbHandle *h, const uint8_t *mask, void *stream) {
     npb_launch_diag_carried_put(h->diag, h->diag_pitch, mask, h->n_plants, h->pitch, fresh, (hipStream_t)stream);
   }
   clear_episodes(h, mask, true, (hipStream_t)stream);
+  restart_streams(h, false, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -754,6 +767,7 @@ int npb_reset_reference(NpbHandle *h, const uint8_t *mask, int start_at_steady_s
   h->K->reset(&h->params, h->n_plants, NPB_N(h), h->f64, mask, start_at_steady_state != 0, (hipStream_t)stream);
   if (h->diag_carry) npb_launch_diag_carried_put(h->diag, h->diag_pitch, mask, h->n_plants, h->pitch, diag_reference_reset_values(), (hipStream_t)stream);
   clear_episodes(h, mask, true, (hipStream_t)stream);
+  restart_streams(h, false, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -966,6 +980,26 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
     return fail(h, NPB_EINVAL, "npb_step: the component maintenance is on (npb_set_component_maintenance) and needs params.maint_enabled and the full mode");
   if (refused >= 0) return fail(h, NPB_EINVAL, side_refusal(refused, from_bank));
   NPB_USE_DEVICE(h);
+  npb_episode_streams_take_t es_take = {};
+  if (h->es_on) {      /* episode streams: a column the caller leaves out is the handle's current row of that stream */
+    const npb_episode_streams_t &S = h->es;
+    const bool take_noise = S.noise.key && !noise_z, take_prof = S.prof.key && !power_setpoint;
+    const bool fill_noise = take_noise && h->es_noise_cur >= S.block, fill_prof = take_prof && h->es_prof_cur >= S.block;
+    if (fill_noise || fill_prof) {
+      npb_launch_episode_streams_fill(&S, fill_noise ? 0 : S.block, fill_prof ? 0 : S.block, (hipStream_t)stream);
+      if (fill_noise) h->es_noise_cur = 0;
+      if (fill_prof) h->es_prof_cur = 0;
+    }
+    const double *target = nullptr;
+    if (take_noise) noise_z = S.noise_rows + (size_t)h->es_noise_cur++ * h->n_plants;
+    if (take_prof) {
+      power_setpoint = S.setpoint_rows + (size_t)h->es_prof_cur * h->n_plants;
+      target = S.target_rows + (size_t)h->es_prof_cur++ * h->n_plants;
+    }
+    /* the rows taken go into the caller's columns in the restart kernel's launch behind the step (the mode needs the autoreset) */
+    es_take = npb_episode_streams_take_t{noise_z, power_setpoint, target, take_noise ? h->es_noise_out : nullptr, take_prof ? h->es_setpoint_out : nullptr,
+                                         take_prof ? h->es_target_out : nullptr};
+  }
   npb_maint_table_t table;
   const bool maint = h->params.maint_enabled != 0;
   const bool in_step = maint && !h->cm_on;      /* the rule inside the step kernels (pumps only); with the components on it is a launch of its own */
@@ -1004,6 +1038,7 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
     h->K->episode(h->params.mode, h->n_plants, NPB_N(h), h->f64, source_of(h, from_bank), done, reward, obs, counters_of(h),
                   h->ep_out_len, h->ep_out_ret, h->ep_out_truncated, h->ep_final_obs, h->max_episode_steps,
                   maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, side, (hipStream_t)stream);
+  if (h->autoreset) restart_streams(h, from_bank, (hipStream_t)stream, &es_take);      /* the plants the episode kernel has just restarted */
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, NPB_EHIP, "npb_step: kernel launch failed", e);
   return NPB_OK;
@@ -1032,6 +1067,7 @@ static int restore_from(NpbHandle *h, bool bank, const uint8_t *mask, hipStream_
   h->K->restore(h->n_plants, NPB_N(h), h->f64, source_of(h, bank), mask, counters_of(h),
                 maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, side, stream);
   if (!bank) clear_episodes(h, mask, false, stream);     /* the restored episodes are not from the bank */
+  restart_streams(h, bank, stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -1044,7 +1080,10 @@ int npb_restore(NpbHandle *h, const uint8_t *mask, void *stream) {
 
 int npb_set_autoreset(NpbHandle *h, int enabled, int max_episode_steps) {
   if (!h) return NPB_EINVAL;
-  if (!enabled) { h->autoreset = false; return NPB_OK; }
+  if (!enabled) {
+    if (h->es_on) return fail(h, NPB_EINVAL, "npb_set_autoreset: episode streams are on (npb_set_episode_streams) and read the restarts off the autoreset's episode index; switch the mode off first");
+    h->autoreset = false; return NPB_OK;
+  }
   if (max_episode_steps < 0) return fail(h, NPB_EINVAL, "npb_set_autoreset: max_episode_steps must be >= 0 (0 = no limit)");
   if (!h->snap && !(h->bank && h->next_slot))
     return fail(h, NPB_EINVAL, "npb_set_autoreset: no snapshot (npb_snapshot), nor a start bank with slots (npb_set_start_bank, npb_set_start_slots), to reset to");
@@ -1071,6 +1110,7 @@ int npb_set_autoreset(NpbHandle *h, int enabled, int max_episode_steps) {
   }
   const size_t len_bytes = (size_t)((char *)h->ep_ret - (char *)h->ep_len);
   NPB_HIP(h, hipMemset(h->ep_len, 0, len_bytes + h->pitch * sizeof(double) + h->pitch * sizeof(int32_t)));
+  if (h->es_on) NPB_HIP(h, hipMemset(h->es.seen_index, 0, h->pitch * sizeof(int32_t)));      /* zeroing the indices restarts nothing */
   h->autoreset = true;
   h->max_episode_steps = max_episode_steps;
   return NPB_OK;
@@ -1090,6 +1130,9 @@ int npb_set_episode_index_buffer(NpbHandle *h, int32_t *index) {
 
 int npb_set_start_bank(NpbHandle *h, const NpbHandle *src, void *stream) {
   if (!h) return NPB_EINVAL;
+  if (h->es_on && h->es_tables && (!src || src->n_plants != h->es.bank_entries))
+    return fail(h, NPB_EINVAL, "npb_set_start_bank: episode streams are on with bank seed tables (npb_set_episode_streams) of the present bank's entry count; "
+                               "switch the mode off first, then set it again with tables for the new bank");
   NPB_USE_DEVICE(h);
   if (!src) {
     if (h->autoreset && !h->snap)
@@ -1199,10 +1242,11 @@ static int noise_alloc(NpbHandle *h, const char *who) {
 
 int npb_noise_seed(NpbHandle *h, const int64_t *seeds, void *stream) {
   if (!h) return NPB_EINVAL;
+  if (h->es_on) return fail_who(h, "npb_noise_seed", g_es_owns);
   NPB_USE_DEVICE(h);
   if (!seeds) {
     if (h->noise) { NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream)); (void)hipFree(h->noise); }
-    h->noise = nullptr;
+    h->noise = nullptr; h->noise_seeds.clear();
     return NPB_OK;
   }
   const int n = h->n_plants;
@@ -1214,11 +1258,13 @@ int npb_noise_seed(NpbHandle *h, const int64_t *seeds, void *stream) {
   npb_launch_noise_seed(h->noise_g, n, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));    /* s32 is read until the copy is done */
+  h->noise_seeds = std::move(s32);
   return NPB_OK;
 }
 
 int npb_noise_fill(NpbHandle *h, int k, double *out, void *stream) {
   if (!h) return NPB_EINVAL;
+  if (h->es_on) return fail_who(h, "npb_noise_fill", g_es_owns);
   if (!h->noise) return fail(h, NPB_EINVAL, "npb_noise_fill: no noise generators (npb_noise_seed or npb_noise_set_state first)");
   if (k < 1 || !out) return fail(h, NPB_EINVAL, "npb_noise_fill: k must be >= 1 and out non-NULL");
   NPB_USE_DEVICE(h);
@@ -1238,6 +1284,7 @@ int npb_noise_get_state(NpbHandle *h, uint32_t *key, int32_t *pos, int32_t *has_
 
 int npb_noise_set_state(NpbHandle *h, const uint32_t *key, const int32_t *pos, const int32_t *has_gauss, const double *cached, void *stream) {
   if (!h) return NPB_EINVAL;
+  if (h->es_on) return fail_who(h, "npb_noise_set_state", g_es_owns);
   if (!key || !pos || !has_gauss || !cached) return fail(h, NPB_EINVAL, "npb_noise_set_state: NULL input");
   if (int rc = mt_state_check(h, "npb_noise_set_state", pos, has_gauss)) return rc;
   NPB_USE_DEVICE(h);
@@ -1251,10 +1298,12 @@ static void profile_free(NpbHandle *h) {
   if (h->prof_side) (void)hipFree(h->prof_side);
   if (h->prof_z) (void)hipFree(h->prof_z);
   h->prof = nullptr; h->prof_side = nullptr; h->prof_z = nullptr; h->prof_z_rows = 0; h->prof_steps = 0; h->prof_pos = 0;
+  h->prof_seeds.clear();
 }
 
 int npb_profile_seed(NpbHandle *h, const int64_t *seeds, int steps, const double *base, int n_base, const double *std, int n_std, void *stream) {
   if (!h) return NPB_EINVAL;
+  if (h->es_on) return fail_who(h, "npb_profile_seed", g_es_owns);
   NPB_USE_DEVICE(h);
   hipStream_t st = (hipStream_t)stream;
   if (!seeds) {
@@ -1288,11 +1337,13 @@ int npb_profile_seed(NpbHandle *h, const int64_t *seeds, int steps, const double
   NPB_HIP(h, hipGetLastError());
   NPB_HIP(h, hipStreamSynchronize(st));    /* side and s32 are read until the copies are done */
   h->prof_steps = steps; h->prof_pos = 0;
+  h->prof_seeds = std::move(s32);
   return NPB_OK;
 }
 
 int npb_profile_fill(NpbHandle *h, int k, double *setpoint_out, double *target_out, double *z_out, void *stream) {
   if (!h) return NPB_EINVAL;
+  if (h->es_on) return fail_who(h, "npb_profile_fill", g_es_owns);
   if (!h->prof) return fail(h, NPB_EINVAL, "npb_profile_fill: no profile (npb_profile_seed first)");
   if (k < 1 || !setpoint_out) return fail(h, NPB_EINVAL, "npb_profile_fill: k must be >= 1 and setpoint_out non-NULL");
   NPB_USE_DEVICE(h);
@@ -1343,13 +1394,14 @@ int npb_profile_get_state(NpbHandle *h, uint32_t *key, int32_t *pos, int32_t *ha
   NPB_HIP(h, hipMemcpy2DAsync(carried, n * sizeof(double), h->prof_side + (size_t)NPB_PROFILE_CARRIED * pitch, pitch * sizeof(double), n * sizeof(double),
                               NPB_PROFILE_NUM_CARRIED, hipMemcpyDeviceToHost, st));
   if (int rc = mt_state_download(h, h->prof_g, key, pos, has_gauss, cached, st)) return rc;      /* (waits for the stream) */
-  *position = h->prof_pos;
+  *position = h->es_on ? -1 : h->prof_pos;      /* episode streams: every plant has its own (npb_profile_get_positions) */
   return NPB_OK;
 }
 
 int npb_profile_set_state(NpbHandle *h, const uint32_t *key, const int32_t *pos, const int32_t *has_gauss, const double *cached, const double *carried,
                           int32_t position, void *stream) {
   if (!h) return NPB_EINVAL;
+  if (h->es_on) return fail_who(h, "npb_profile_set_state", g_es_owns);
   if (!h->prof) return fail(h, NPB_EINVAL, "npb_profile_set_state: no profile (npb_profile_seed first: it sets the horizon and the load profiles)");
   if (!key || !pos || !has_gauss || !cached || !carried) return fail(h, NPB_EINVAL, "npb_profile_set_state: NULL input");
   if (position < 0 || position >= h->prof_steps) return fail(h, NPB_EINVAL, "npb_profile_set_state: position outside [0, steps)");
@@ -1361,6 +1413,107 @@ int npb_profile_set_state(NpbHandle *h, const uint32_t *key, const int32_t *pos,
                               NPB_PROFILE_NUM_CARRIED, hipMemcpyHostToDevice, st));
   if (int rc = mt_state_upload(h, h->prof_g, key, pos, has_gauss, cached, st)) return rc;      /* (waits for the stream) */
   h->prof_pos = position;
+  return NPB_OK;
+}
+
+/* ---- episode streams (include/npb.h) */
+const char *npb_episode_streams_check(const npb_episode_streams_desc_t *desc, int has_generators, int bank_entries) {
+  if (!desc) return nullptr;
+  if (!has_generators) return "npb_set_episode_streams: no generators (npb_noise_seed or npb_profile_seed first): there is no stream to restart";
+  if (desc->block < 1) return "npb_set_episode_streams: block must be >= 1";
+  const bool tables = desc->bank_noise_seeds || desc->bank_profile_seeds;
+  if (tables && bank_entries <= 0) return "npb_set_episode_streams: bank seed tables without a start bank (npb_set_start_bank first)";
+  if (tables && desc->n_bank_seeds != bank_entries) return "npb_set_episode_streams: n_bank_seeds is not the start bank's entry count";
+  for (const int64_t *t : {desc->bank_noise_seeds, desc->bank_profile_seeds})
+    for (int s = 0; t && s < desc->n_bank_seeds; s++)
+      if (t[s] < 0 || t[s] > (int64_t)0xffffffffLL) return "npb_set_episode_streams: a bank seed is outside [0, 2^32), which numpy.random.RandomState refuses";
+  return nullptr;
+}
+
+/* every plant's generators of one set back to its own seed: the seeds travel in the pos column (npb_launch_noise_seed) */
+static int reseed_own(NpbHandle *h, const npb_noise_t &g, const std::vector<uint32_t> &seeds, hipStream_t st) {
+  NPB_HIP(h, hipMemcpyAsync(g.pos, seeds.data(), (size_t)h->n_plants * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  npb_launch_noise_seed(g, h->n_plants, st);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+
+int npb_set_episode_streams(NpbHandle *h, const npb_episode_streams_desc_t *desc, void *stream) {
+  if (!h) return NPB_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (!desc) {      /* off: every plant's streams from its own seeds again, as npb_noise_seed / npb_profile_seed left them */
+    if (!h->es_on) return NPB_OK;
+    NPB_USE_DEVICE(h);
+    if (h->noise) if (int rc = reseed_own(h, h->noise_g, h->noise_seeds, st)) return rc;
+    if (h->prof) {
+      if (int rc = reseed_own(h, h->prof_g, h->prof_seeds, st)) return rc;
+      NPB_HIP(h, hipMemsetAsync(h->prof_side + (size_t)NPB_PROFILE_CARRIED * h->pitch, 0, (size_t)NPB_PROFILE_NUM_CARRIED * h->pitch * sizeof(double), st));
+      h->prof_pos = 0;
+    }
+    NPB_HIP(h, hipStreamSynchronize(st));      /* nothing may still read the blocks when they are freed */
+    (void)hipFree(h->es_mem);
+    h->es_mem = nullptr; h->es_on = false; h->es_tables = false; h->es = npb_episode_streams_t{};
+    return NPB_OK;
+  }
+  if (const char *why = npb_episode_streams_check(desc, h->noise || h->prof, h->bank ? h->bank_M : 0)) return fail(h, NPB_EINVAL, why);
+  if ((h->noise && h->noise_seeds.empty()) || (h->prof && h->prof_seeds.empty()))
+    return fail(h, NPB_EINVAL, "npb_set_episode_streams: the noise generators were only ever loaded (npb_noise_set_state) and have no seed to restart from: npb_noise_seed first");
+  if (!h->autoreset)
+    return fail(h, NPB_EINVAL, "npb_set_episode_streams: needs the autoreset (npb_set_autoreset first): the restarts are read off the episode index it keeps");
+  NPB_USE_DEVICE(h);
+  if (h->es_on) if (int rc = npb_set_episode_streams(h, nullptr, stream)) return rc;      /* set again: from scratch */
+  const size_t n = (size_t)h->n_plants, pitch = h->pitch, block = (size_t)desc->block;
+  const bool tables = desc->bank_noise_seeds || desc->bank_profile_seeds;
+  const size_t M = tables ? (size_t)desc->n_bank_seeds : 0;
+  /* one allocation: the doubles, then the 4-byte columns */
+  const size_t doubles = (h->noise ? block * n : 0) + (h->prof ? (3 * block + 1) * n : 0);
+  const size_t words = 5 * pitch + 2 * M;
+  hipError_t e = hipMalloc(&h->es_mem, doubles * sizeof(double) + words * sizeof(uint32_t));
+  if (e != hipSuccess) { h->es_mem = nullptr; return fail(h, NPB_EHIP, "npb_set_episode_streams: hipMalloc of the handle's blocks failed", e); }
+  npb_episode_streams_t S = {};
+  S.n_plants = h->n_plants; S.block = desc->block; S.pitch = pitch;
+  double *d = (double *)h->es_mem;
+  if (h->noise) { S.noise = h->noise_g; S.noise_rows = d; d += block * n; }
+  if (h->prof) {
+    S.prof = h->prof_g; S.prof_side = h->prof_side; S.steps = h->prof_steps;
+    S.setpoint_rows = d; d += block * n; S.target_rows = d; d += block * n; S.draws = d; d += (block + 1) * n;
+  }
+  uint32_t *w = (uint32_t *)d;
+  S.position = (int32_t *)w; S.rows_made = (int32_t *)(w + pitch); S.seen_index = (int32_t *)(w + 2 * pitch);
+  uint32_t *own_noise = w + 3 * pitch, *own_prof = w + 4 * pitch, *bank_noise = w + 5 * pitch, *bank_prof = w + 5 * pitch + M;
+  S.own_noise_seed = own_noise; S.own_profile_seed = own_prof;
+  S.episode_index = h->ep_index;
+  /* the 4-byte columns as the host lays them out: zeros, the plants' own seeds, the tables */
+  std::vector<uint32_t> host(words, 0u);
+  for (size_t p = 0; p < n; p++) {
+    if (h->noise) host[3 * pitch + p] = h->noise_seeds[p];
+    if (h->prof) host[4 * pitch + p] = h->prof_seeds[p];
+  }
+  for (size_t s = 0; s < M; s++) {
+    if (desc->bank_noise_seeds) host[5 * pitch + s] = (uint32_t)desc->bank_noise_seeds[s];
+    if (desc->bank_profile_seeds) host[5 * pitch + M + s] = (uint32_t)desc->bank_profile_seeds[s];
+  }
+  if (tables) { S.bank_entries = (int)M; S.bank_noise_seed = desc->bank_noise_seeds ? bank_noise : nullptr; S.bank_profile_seed = desc->bank_profile_seeds ? bank_prof : nullptr; }
+  e = hipMemcpyAsync(w, host.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+  /* every plant begins both streams anew from its own seed, nothing drawn ahead: the first step that takes a row fills the block */
+  if (e == hipSuccess) { npb_launch_episode_streams_restart(&S, S.block, S.block, nullptr, 1, nullptr, st); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);      /* host is read until the copy is done */
+  if (e != hipSuccess) { (void)hipFree(h->es_mem); h->es_mem = nullptr; return fail(h, NPB_EHIP, "npb_set_episode_streams: seeding the streams failed", e); }
+  h->es = S; h->es_on = true; h->es_tables = tables;
+  h->es_noise_cur = h->es_prof_cur = S.block;
+  h->es_noise_out = desc->noise_out; h->es_setpoint_out = desc->setpoint_out; h->es_target_out = desc->target_out;
+  return NPB_OK;
+}
+
+int npb_profile_get_positions(NpbHandle *h, int32_t *position, int32_t *rows_made, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->es_on) return fail(h, NPB_EINVAL, "npb_profile_get_positions: episode streams are off (npb_set_episode_streams); npb_profile_get_state has the one position");
+  if (!h->es.prof.key) return fail(h, NPB_EINVAL, "npb_profile_get_positions: no profile (npb_profile_seed before npb_set_episode_streams)");
+  NPB_USE_DEVICE(h);
+  hipStream_t st = (hipStream_t)stream;
+  if (position) NPB_HIP(h, hipMemcpyAsync(position, h->es.position, (size_t)h->n_plants * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (rows_made) NPB_HIP(h, hipMemcpyAsync(rows_made, h->es.rows_made, (size_t)h->n_plants * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipStreamSynchronize(st));
   return NPB_OK;
 }
 

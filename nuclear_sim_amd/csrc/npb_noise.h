@@ -45,6 +45,33 @@ void npb_launch_profile_rows(int n_plants, int k, int steps, int pos, double *si
 void npb_launch_profile_ramp(int n_plants, int k, const double *target_in, double *setpoint_out, double *prev, hipStream_t stream);
 /* v into x[0 .. count) */
 void npb_launch_profile_set(double *x, size_t count, double v, hipStream_t stream);
+
+/* Episode streams (include/npb.h npb_set_episode_streams): what the handle owns while the mode is on, as the kernels read it.  A stream
+ * the handle has no generators for has key = NULL and its rows NULL. */
+typedef struct {
+  int n_plants, block, steps;                          /* steps: the profile's horizon */
+  size_t pitch;
+  npb_noise_t noise, prof;
+  double *prof_side;                                   /* [NPB_PROFILE_SIDE][pitch], the profile's own */
+  double *noise_rows, *setpoint_rows, *target_rows;    /* [block][n_plants] */
+  double *draws;                                       /* [block + 1][n_plants]: the profile's draws on their way to rows */
+  int32_t *position, *rows_made;                       /* [pitch]: row of the current profile the next row made is, rows made since the restart */
+  const uint32_t *own_noise_seed, *own_profile_seed;   /* [pitch]: as given to npb_noise_seed / npb_profile_seed */
+  const uint32_t *bank_noise_seed, *bank_profile_seed; /* [bank_entries] each, or NULL */
+  int bank_entries;
+  const int32_t *episode_index;                        /* [pitch], the handle's (npb_set_autoreset) */
+  int32_t *seen_index;                                 /* [pitch]: its value when the plant's streams last began */
+} npb_episode_streams_t;
+typedef struct { const double *noise, *setpoint, *target; double *noise_out, *setpoint_out, *target_out; } npb_episode_streams_take_t;
+/* rows [noise_from, block) of the noise block and [prof_from, block) of the profile's for every plant, from where its streams are
+ * (from = block: that stream is left alone) */
+void npb_launch_episode_streams_fill(const npb_episode_streams_t *S, int noise_from, int prof_from, hipStream_t stream);
+/* the plants whose episode index is not the one seen (all != 0: every plant): streams seeded anew -- from the bank tables' entry
+ * start[p] where start is given, the entry is one and the table exists, else from the plant's own seed --, position, rows made and
+ * carried values zeroed, seen = index, and the same rows made from the new streams' beginning.  take (NULL = none): one [n_plants] row
+ * each that the launch first copies into the caller's column; a pair with a NULL output is skipped */
+void npb_launch_episode_streams_restart(const npb_episode_streams_t *S, int noise_from, int prof_from, const int32_t *start, int all,
+                                        const npb_episode_streams_take_t *take, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

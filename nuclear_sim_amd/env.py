@@ -105,6 +105,7 @@ class DeviceHeatSourceNoise:
 
     def next(self) -> torch.Tensor:
         env = self._env
+        env._refuse_in_episode_streams("DeviceHeatSourceNoise.next()")
         if self._pos >= self._block:
             with torch.cuda.device(env.device):
                 self._buf = torch.empty((self._block, env.n), dtype=torch.float64, device=env.device)
@@ -127,6 +128,7 @@ class DeviceHeatSourceNoise:
     def set_state(self, key, pos, has_gauss, cached) -> None:
         """load every plant's generator state (numpy's layout, as ``get_state`` returns it); the rest of the block is dropped"""
         env, n = self._env, self._env.n
+        env._refuse_in_episode_streams("DeviceHeatSourceNoise.set_state()")
         arrays = (np.ascontiguousarray(np.broadcast_to(np.asarray(key, dtype=np.uint32), (n, 624))),
                   np.ascontiguousarray(np.broadcast_to(np.asarray(pos, dtype=np.int32), (n,))),
                   np.ascontiguousarray(np.broadcast_to(np.asarray(has_gauss, dtype=np.int32), (n,))),
@@ -185,6 +187,7 @@ class PowerProfile:
         """the next ``k`` rows as fresh [k, n] tensors ``(setpoint, target)`` -- with ``with_draws`` also the draw behind each row's raw
         value, ``(setpoint, target, z)``: ``scenarios.power_profile_rows(z)`` of a whole profile equals the other two bit for bit"""
         env = self._env
+        env._refuse_in_episode_streams("PowerProfile.fill()")
         with torch.cuda.device(env.device):
             out = torch.empty((3 if with_draws else 2, int(k), env.n), dtype=torch.float64, device=env.device)
         _lib.check(env.L.npb_profile_fill(env._h, int(k), ctypes.c_void_p(out[0].data_ptr()), ctypes.c_void_p(out[1].data_ptr()),
@@ -192,6 +195,7 @@ class PowerProfile:
         return tuple(out)
 
     def next(self):
+        self._env._refuse_in_episode_streams("PowerProfile.next()")
         if self._pos >= self._block:
             self._buf = self.fill(self._block)
             self._pos = 0
@@ -200,7 +204,8 @@ class PowerProfile:
         return out
 
     def get_state(self):
-        """(key [n, 624] uint32, pos [n] int32, has_gauss [n] int32, cached [n] float64, carried [5, n] float64, position)"""
+        """(key [n, 624] uint32, pos [n] int32, has_gauss [n] int32, cached [n] float64, carried [5, n] float64, position); with
+        episode streams on the position is -1: every plant has its own (``BatchedPlantEnv.profile_positions()``)"""
         env, n = self._env, self._env.n
         key = np.empty((n, 624), dtype=np.uint32)
         pos, has_gauss = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
@@ -213,6 +218,7 @@ class PowerProfile:
     def set_state(self, key, pos, has_gauss, cached, carried, position) -> None:
         """load a state as ``get_state`` returns it; the rest of the block is dropped"""
         env, n = self._env, self._env.n
+        env._refuse_in_episode_streams("PowerProfile.set_state()")
         arrays = (np.ascontiguousarray(np.broadcast_to(np.asarray(key, dtype=np.uint32), (n, 624))),
                   np.ascontiguousarray(np.broadcast_to(np.asarray(pos, dtype=np.int32), (n,))),
                   np.ascontiguousarray(np.broadcast_to(np.asarray(has_gauss, dtype=np.int32), (n,))),
@@ -287,7 +293,7 @@ class BatchedPlantEnv:
     describe the terminal transition; ``info`` gains ``truncated``, ``final_observation`` (this step's obs of the reset plants;
     other rows are stale), ``episode_length`` and ``episode_return`` (as of this step: a reset plant's finished episode).  Only the
     plant state in the arena is restored: the pre-drawn heat-source noise stream (``HeatSourceNoise``) continues across an
-    autoreset (its filter state, in the arena, is restored).  With autoreset ``info["episode_index"]`` numbers each plant's episodes
+    autoreset (its filter state, in the arena, is restored) -- unless ``episode_streams=True`` (below).  With autoreset ``info["episode_index"]`` numbers each plant's episodes
     (the episode this step's transition belonged to; every restart, ``restore`` and ``reset`` included, starts the next).
 
     Diagnostics with episodes: the diagnostics build of the step (``enable_diagnostics``; the state log's step-internal columns) keeps
@@ -342,8 +348,20 @@ class BatchedPlantEnv:
     ``info["target_power"]``.  ``reset()`` of the whole batch re-seeds the profile, as it re-seeds the noise; a masked reset,
     ``restore``, the start bank and the autoreset leave it running, as they leave the noise stream: all plants share one position
     in the profile.  With ``max_episode_steps == steps`` a truncated plant's next episode therefore begins exactly with the next
-    profile (a plant that ends earlier restarts mid-profile).  ``ramp_setpoints(targets)`` is the ramp stage alone, for targets of
-    the caller's own.
+    profile (a plant that ends earlier restarts mid-profile, unless ``episode_streams=True``).  ``ramp_setpoints(targets)`` is the
+    ramp stage alone, for targets of the caller's own.
+
+    Episode streams (``episode_streams=True``; needs ``autoreset=True`` and, with noise, ``noise_generator="device"``): each plant's
+    noise stream and power profile restart with its episode (npb_set_episode_streams), so that every (plant, episode) is the run a
+    fresh env of that scenario would make, as the data-gen runner builds a new heat source and draws a new profile for every run.  The
+    handle then owns the streams: ``step()`` passes no column unless the caller gives one (which wins and consumes no row, as before),
+    every plant has its own position in its profile, and wherever a plant's episode index is bumped -- the autoreset, ``restore``,
+    ``restore_from_bank``, ``reset`` -- its generators are seeded anew and the rows drawn ahead for it are made again from the new
+    streams, on the device.  A restart from a bank entry ``s`` takes ``bank_noise_seeds[s]`` / ``bank_profile_seeds[s]`` where
+    ``enable_episode_streams`` was given that table, every other restart the plant's own seeds, so a restart from the snapshot repeats
+    the plant's first episode.  ``stream_rows`` holds the rows the last step took (``noise``, ``setpoint``, ``target``; the env's own
+    buffers), ``info["target_power"]`` is its target row.  ``scenarios.episode_stream_rows`` states the contract in numpy.  The stream
+    classes' ``next()`` / ``fill()`` / ``set_state()`` raise while the mode is on.  Off by default: nothing changes.
     """
 
     action_space_size = 15       # NuclearPlantEnv sim.py:916
@@ -355,9 +373,11 @@ class BatchedPlantEnv:
                  storage: str = "f64", maintenance_thresholds: Optional[dict] = None, reactivity_components: bool = False,
                  integrator: str = "reference", autoreset: bool = False, max_episode_steps: Optional[int] = None,
                  noise_generator: str = "host", component_maintenance: bool = False, component_thresholds: Optional[dict] = None,
-                 diagnostics: bool = False, power_profile: Optional[dict] = None):
+                 diagnostics: bool = False, power_profile: Optional[dict] = None, episode_streams: bool = False):
         if max_episode_steps is not None and not autoreset:
             raise ValueError("max_episode_steps needs autoreset=True")
+        if episode_streams:      # refused before any device work
+            self._check_episode_streams(autoreset, noise_enabled, noise_generator, noise_seeds is not None, power_profile is not None)
         if power_profile is not None:
             if heat_source == "external":
                 raise ValueError("power_profile drives the heat source's setpoint: not with heat_source='external'")
@@ -444,6 +464,7 @@ class BatchedPlantEnv:
                 self._event_counts = torch.zeros(self.n, dtype=torch.int32, device=self.device)
             _lib.check(self.L.npb_set_maintenance_count_buffer(self._h, ctypes.c_void_p(self._event_counts.data_ptr())), self._h)
         self._noise = None
+        self._streams = None
         self.noise_generator = noise_generator
         self._noise_seeds = None if noise_seeds is None else np.asarray(noise_seeds, dtype=np.int64).copy()
         if noise_enabled and noise_seeds is not None:
@@ -461,6 +482,20 @@ class BatchedPlantEnv:
         if autoreset:
             self.snapshot()
             self._enable_autoreset(max_episode_steps)
+        if episode_streams:
+            self.enable_episode_streams()
+
+    @staticmethod
+    def _check_episode_streams(autoreset, noise_enabled, noise_generator, noise_seeded, profile) -> None:
+        """what ``episode_streams=True`` needs of the other keywords"""
+        if not autoreset:
+            raise ValueError("episode_streams needs autoreset=True: the streams restart where the plants' episodes do")
+        if noise_enabled and noise_generator != "device":
+            raise ValueError("episode_streams needs noise_generator='device': the host generator's pre-drawn stream cannot restart per plant on the device")
+        if noise_enabled and not noise_seeded:
+            raise ValueError("episode_streams needs noise_seeds: an unseeded stream has no beginning to restart from")
+        if not noise_enabled and not profile:
+            raise ValueError("episode_streams needs a stream to restart: noise_enabled with noise_seeds, or a power_profile")
 
     @classmethod
     def action_test(cls, action: str, seeds: Sequence[int], dt: float = 5.0, device: int = 0, randomize: bool = True,
@@ -468,7 +503,7 @@ class BatchedPlantEnv:
                     bank_seeds: Optional[Sequence[int]] = None, noise_generator: str = "host",
                     maintenance_log: Optional[int] = None, component_maintenance: bool = False,
                     component_thresholds: Optional[dict] = None, diagnostics: bool = False,
-                    power_profile_steps: Optional[int] = None, storage: str = "f64") -> "BatchedPlantEnv":
+                    power_profile_steps: Optional[int] = None, storage: str = "f64", episode_streams: bool = False) -> "BatchedPlantEnv":
         """One plant per seed, as data_gen's MaintenanceScenarioRunner builds them for
         ``compose_action_test_scenario(action, randomize=True, randomization_seed=seed)``
         (maintenance_scenario_runner.py:210-244): dt in minutes, ConstantHeatSource with 0.1 % noise seeded 42,
@@ -486,9 +521,15 @@ class BatchedPlantEnv:
         NOT the profile the live runner draws for that scenario seed: its global stream is further along by then, by whatever the
         composer's randomiser drew from it, and that consumption is not restated.  What is reproduced is the runner's profile for
         a stream seeded just before it (np.random.seed(seed) immediately before run_scenario).  ``storage`` as for the constructor
-        (a bank of ``bank_seeds`` is built with the same)."""
+        (a bank of ``bank_seeds`` is built with the same).
+        ``episode_streams`` as for the constructor (it needs ``autoreset`` and ``noise_generator="device"``): every episode then begins
+        the runner's streams anew -- a restart from bank entry ``s`` the noise of ``RandomState(42)`` and the profile of
+        ``RandomState(bank_seeds[s])`` (``bank_noise_seeds=[42] * M``, ``bank_profile_seeds=bank_seeds``), a restart from the plant's own
+        snapshot its own -- so each (plant, episode) is bit for bit the run of a fresh ``action_test(action, [that scenario's seed])``."""
         if max_episode_steps is not None and not autoreset:
             raise ValueError("max_episode_steps needs autoreset=True")
+        if episode_streams:      # refused before any device work
+            cls._check_episode_streams(autoreset, True, noise_generator, True, power_profile_steps is not None)
         from . import scenarios
         env = cls(len(seeds), dt=dt, heat_source="constant", noise_enabled=True, noise_std_percent=0.1,
                   noise_seeds=[42] * len(seeds), device=device, maintenance=True, params=params, noise_generator=noise_generator,
@@ -511,6 +552,12 @@ class BatchedPlantEnv:
             bank.close()
         if maintenance_log is not None:
             env.enable_maintenance_log(maintenance_log)
+        if episode_streams:      # after the bank: the tables are checked against its entries
+            if bank_seeds is None:
+                env.enable_episode_streams()
+            else:
+                env.enable_episode_streams(bank_noise_seeds=[42] * len(bank_seeds),
+                                           bank_profile_seeds=None if power_profile_steps is None else list(bank_seeds))
         return env
 
     # ------------------------------------------------------------------ helpers
@@ -983,6 +1030,49 @@ class BatchedPlantEnv:
         if "episode_index" in e:
             _lib.check(self.L.npb_set_episode_index_buffer(self._h, self._p(e["episode_index"])), self._h)
 
+    def enable_episode_streams(self, block: int = 64, bank_noise_seeds=None, bank_profile_seeds=None) -> None:
+        """Switch episode streams on (the class docstring; npb_set_episode_streams): the handle draws both streams ``block`` rows at a
+        time and restarts a plant's with its episode.  ``bank_noise_seeds`` / ``bank_profile_seeds``: one seed per entry of the start
+        bank, for the restarts that take that entry; without a table such a restart uses the plant's own seed again.  Switching on is
+        itself a restart of every plant from its own seeds.  Needs autoreset and device generators."""
+        if not hasattr(self.L, "npb_set_episode_streams"):
+            raise _lib.NpbError("libnpb.so has no npb_set_episode_streams: rebuild")
+        if self._noise is not None and not isinstance(self._noise, DeviceHeatSourceNoise):
+            raise ValueError("episode_streams needs noise_generator='device': the host generator's pre-drawn stream cannot restart per plant on the device")
+        with torch.cuda.device(self.device):
+            out = torch.zeros((3, self.n), dtype=torch.float64, device=self.device)
+        desc, keep = _lib.episode_streams_desc(block, bank_noise_seeds, bank_profile_seeds, [int(out[k].data_ptr()) for k in range(3)])
+        _lib.check(self.L.npb_set_episode_streams(self._h, ctypes.byref(desc), self._stream()), self._h)
+        del keep      # (the call has copied the tables)
+        self._streams = {"noise": out[0], "setpoint": out[1], "target": out[2]}
+
+    def disable_episode_streams(self) -> None:
+        """Episode streams off again: every plant's streams begin anew from its own seeds, and run on across restarts as before."""
+        _lib.check(self.L.npb_set_episode_streams(self._h, None, self._stream()), self._h)
+        self._streams = None
+        for stream in (self._noise, self._profile):      # nothing of a block handed out before the mode is left
+            if stream is not None:
+                stream._buf, stream._pos = None, stream._block
+
+    @property
+    def stream_rows(self) -> Optional[Dict[str, torch.Tensor]]:
+        """episode streams: the rows the last ``step()`` took from the handle's streams, [n] float64 each (the env's own buffers, written
+        again by the next step; a stream the caller overrode on that step keeps its earlier row); None while the mode is off"""
+        return self._streams
+
+    def profile_positions(self):
+        """episode streams: ``(position, rows_made)`` of every plant's power profile, int32 [n] numpy arrays -- the row of its current
+        profile the next row made for it is, and the rows made for it since its restart, drawn ahead included (npb_profile_get_positions)"""
+        position, rows_made = np.empty(self.n, dtype=np.int32), np.empty(self.n, dtype=np.int32)
+        _lib.check(self.L.npb_profile_get_positions(self._h, position.ctypes.data_as(ctypes.c_void_p), rows_made.ctypes.data_as(ctypes.c_void_p),
+                                                    self._stream()), self._h)
+        return position, rows_made
+
+    def _refuse_in_episode_streams(self, who: str) -> None:
+        if self._streams is not None:
+            raise _lib.NpbError("%s: episode streams are on, and the handle owns the streams' consumption (step() takes its rows; "
+                                "disable_episode_streams() first)" % who)
+
     def log_sources(self) -> Dict[str, torch.Tensor]:
         """The buffers beside the arena that a state log with a watch list samples (nuclear_sim_amd/statelog.py, ``sample_request``): the
         step's info block, its ``done`` column, the diagnostics buffer while the diagnostics are on and the episode columns of an env
@@ -1118,9 +1208,10 @@ class BatchedPlantEnv:
             # a freshly constructed simulator has a freshly seeded heat-source generator (the reference's own reset() keeps
             # drawing from the old one: constant_heat_source.py:185-194 does not touch the RNG).  Plants that share a seed
             # share one pre-drawn stream here, so only a reset of the whole batch can restart it.
-            if mask is None and self._noise is not None and self._noise_seeds is not None:
+            # With episode streams the handle has restarted the streams of exactly the plants it reset, on the device.
+            if mask is None and self._noise is not None and self._noise_seeds is not None and self._streams is None:
                 self._noise = self._make_noise(self._noise_seeds)
-            if mask is None and self._profile is not None:      # and a freshly started runner a freshly drawn profile
+            if mask is None and self._profile is not None and self._streams is None:      # and a freshly started runner a freshly drawn profile
                 self._profile = PowerProfile(self, **self._profile_args)
         return self.get_observation()
 
@@ -1172,14 +1263,17 @@ class BatchedPlantEnv:
         m = self._col(magnitude, torch.float64)
         target_power = None
         if power_setpoint is None and self._profile is not None:
-            power_setpoint, target_power = self._profile.next()
+            if self._streams is not None:      # episode streams: no column; the handle takes its own row and reports it
+                target_power = self._streams["target"]
+            else:
+                power_setpoint, target_power = self._profile.next()
         sp = self._col(power_setpoint, torch.float64)
         cw = self._col(cooling_water_temp, torch.float64)
         if noise_z is None and self._noise is None and self.params.hs_noise_enabled:
             # ConstantHeatSource(noise_enabled=True, noise_seed=None) draws from an unseeded generator
             # (constant_heat_source.py:58-62): one fresh, unseeded stream per plant
             self._noise = self._make_noise(np.random.SeedSequence().generate_state(self.n, dtype=np.uint32))
-        if noise_z is None and self._noise is not None:
+        if noise_z is None and self._noise is not None and self._streams is None:
             noise_z = self._noise.next()
         z = self._col(noise_z, torch.float64)
         _lib.check(self.L.npb_step(self._h, self._p(a), self._p(m), self._p(sp), self._p(z), self._p(cw),

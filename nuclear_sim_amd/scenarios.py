@@ -746,3 +746,41 @@ def power_profile_rows(z, base=90.0, std=2.0):
         target[i] = _limited(target[i - 1], sm[i], PROFILE_RATE_LIMIT)
     setpoint, _ = power_profile_ramp(target)
     return target, setpoint
+
+
+def episode_stream_rows(restarts, steps, T=None, base=90.0, std=2.0, takes_noise=None, takes_profile=None):
+    """Episode streams (include/npb.h npb_set_episode_streams; ``BatchedPlantEnv(episode_streams=True)``), the readable statement: the
+    rows each of ``steps`` steps takes, ``(noise, target, setpoint)``, [steps, n] each.
+
+    ``restarts[p]`` lists plant p's restarts as ``(step, noise_seed, profile_seed)``: before step ``step`` takes its rows the plant's
+    streams begin anew, the noise as ``RandomState(noise_seed)`` and the profile as ``RandomState(profile_seed)`` (a seed of None: the
+    env has no such stream; its rows are NaN).  The first entry is the plant's start, step 0; of several restarts before the same step
+    the last counts (a restart that no row follows leaves nothing).  A restart behind step t -- the autoreset of step t, a ``restore``
+    after it -- is a restart before step t + 1.  Between restarts the j-th step that takes a row takes draw j of the noise stream,
+    ``standard_normal()``, and row j mod T of consecutive profiles of T rows of the profile stream, each profile
+    ``power_profile_rows(standard_normal(T), base, std)``: its ramp begins on its first target.  ``takes_noise`` / ``takes_profile``
+    (bool [steps], default all): a step given that column by the caller takes no row of that stream (NaN here) and consumes none.
+    ``base`` / ``std`` are scalars or one value per plant and stay with the plant."""
+    n = len(restarts)
+    takes_n = np.ones(steps, dtype=bool) if takes_noise is None else np.asarray(takes_noise, dtype=bool)
+    takes_p = np.ones(steps, dtype=bool) if takes_profile is None else np.asarray(takes_profile, dtype=bool)
+    base = np.broadcast_to(np.asarray(base, dtype=np.float64), (n,))
+    std = np.broadcast_to(np.asarray(std, dtype=np.float64), (n,))
+    noise, target, setpoint = (np.full((steps, n), np.nan) for _ in range(3))
+    for p, plant in enumerate(restarts):
+        plant = sorted(plant, key=lambda r: r[0])          # (stable: the last of several before one step stays last)
+        if not plant or plant[0][0] != 0:
+            raise ValueError("plant %d: the first restart is the plant's start, before step 0" % p)
+        for k, (lo, noise_seed, profile_seed) in enumerate(plant):
+            hi = plant[k + 1][0] if k + 1 < len(plant) else steps
+            at_n = lo + np.flatnonzero(takes_n[lo:hi])
+            at_p = lo + np.flatnonzero(takes_p[lo:hi])
+            if noise_seed is not None and at_n.size:
+                noise[at_n, p] = np.random.RandomState(int(noise_seed)).standard_normal(at_n.size)
+            if profile_seed is not None and at_p.size:
+                rng = np.random.RandomState(int(profile_seed))
+                for j in range(0, at_p.size, T):           # the runner draws a whole profile; an episode may end inside it
+                    tg, sp = power_profile_rows(rng.standard_normal(T), base[p], std[p])
+                    rows = at_p[j:j + T]
+                    target[rows, p], setpoint[rows, p] = tg[:rows.size, 0], sp[:rows.size, 0]
+    return noise, target, setpoint
