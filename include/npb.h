@@ -664,6 +664,62 @@ NPB_API int npb_set_episode_streams(NpbHandle *h, const npb_episode_streams_desc
 NPB_API const char *npb_episode_streams_check(const npb_episode_streams_desc_t *desc, int has_generators, int bank_entries);
 NPB_API int npb_profile_get_positions(NpbHandle *h, int32_t *position /* host [n] */, int32_t *rows_made /* host [n], since the last restart */, void *stream);
 
+/* Episode records: a device-side log of FINISHED episodes, each record complete -- who, which episode, from which bank entry, how long, the
+ * return, how it ended, when on the plant's clock, optionally the terminal observation and that episode's work-order summary -- so that a run
+ * of any length yields the table of its episodes with one read-back whenever the caller chooses, instead of one per step (the episode
+ * columns of npb_set_episode_buffers are overwritten by every step).
+ * The record is a struct of arrays the caller owns (device), `capacity` entries per column:
+ *   plant int32        handle-local plant number
+ *   episode int32      the plant's episode index (npb_set_episode_index_buffer)
+ *   start int32        the bank entry the episode started from; -1 if there is no bank or the episode did not begin from it
+ *   length int32       steps of the episode, the terminal one included
+ *   flags int32        bit 0 terminated (done), bit 1 truncated (max_episode_steps); termination wins, as in npb_set_autoreset
+ *   trip_flags uint32  the terminal step's trip_flags column; 0 if npb_step was given NULL
+ *   step int32         number of npb_step calls since the records were switched on, the terminal one = 0 for the first
+ *   ret double         summed reward of the episode (the carried sum; unchanged by a step given reward = NULL)
+ *   end_time double    prim.sim_time after the terminal step, as npb_get_field returns it under the handle's storage type: the clock the
+ *                      maintenance records' `time` comes from
+ *   final_obs double [capacity][NPB_OBS_DIM] row-major, NULL = not recorded: the step's obs row before the autoreset replaces it.  While it
+ *                      is set npb_step refuses obs = NULL.
+ *   first_created, first_completed double [n_keys][capacity], n_created, n_completed int32 [n_keys][capacity]: the plant's cells of the
+ *                      handle's work-order summary (npb_set_maintenance_summary) as of the terminal step, element [key * capacity + slot];
+ *                      all four or none (NULL)
+ *   cursor uint32      one word: slots handed out
+ * While records are on npb_step launches one more kernel on its stream, behind the summary fold and before the episode kernel -- so the
+ * arena, the step's output columns and the carried episode counters still describe the episode that ended and the summary holds the step's
+ * events.  It decides "ended" by the episode kernel's own rule; a wave without an ended plant writes nothing.  The ended plants of one wave
+ * take consecutive slots in plant order with ONE atomic add to *cursor; waves arrive in no particular order.  A record is stored only
+ * while slot < capacity: a cursor past the capacity counts the episodes that were dropped, as the maintenance log's does.  The caller
+ * drains on its stream: read the cursor, copy min(cursor, capacity) entries of each column, zero the cursor.
+ * clear_summary != 0: the summary cells of every ended plant go back to +inf / 0 for every key -- whether or not its record fitted -- so
+ * the summary restarts with the episode and each record holds the work orders of its own episode only.  Off, the summary goes on counting
+ * across restarts as before.
+ * The records are output only: npb_snapshot / npb_restore, the start bank and checkpoints neither read nor reset them.  An episode the
+ * caller ABANDONS -- npb_restore, npb_restore_bank, npb_reset, npb_reset_reference of a running plant -- bumps the plant's episode index
+ * and writes NO record (and clears no summary row): records are of episodes that ended by done or truncation.
+ * npb_set_episode_records(h, desc): desc = NULL turns the records off; the descriptor is copied and the step counter starts at 0.
+ * NPB_EINVAL, with the reason in npb_last_error, for: no autoreset (npb_set_autoreset first); capacity < 1; a NULL or misaligned mandatory
+ * column or cursor (doubles 8-byte, the others 4-byte); summary columns, or clear_summary, without a summary set; only part of the four
+ * summary tables.  npb_episode_records_check is that check alone, without a handle (summary_keys = the summary's n_keys, 0 = none set):
+ * NULL = accepted, else the reason.
+ * While records that copy or clear the summary are on, npb_set_maintenance_summary (another descriptor, or NULL) and
+ * npb_set_maintenance_log(NULL) are refused; while any records are on npb_set_autoreset(h, 0) is refused: switch the records off first.
+ * A handle that never calls this behaves as before in every entry point. */
+typedef struct npb_episode_records_desc_t {
+  int32_t capacity;                             /* entries per column, >= 1 */
+  int32_t clear_summary;                        /* != 0: an ended plant's summary cells back to +inf / 0 */
+  int32_t *plant, *episode, *start, *length, *flags;
+  uint32_t *trip_flags;
+  int32_t *step;
+  double *ret, *end_time;
+  double *final_obs;                            /* [capacity][NPB_OBS_DIM] or NULL */
+  double *first_created, *first_completed;      /* [n_keys][capacity], all four or none */
+  int32_t *n_created, *n_completed;
+  uint32_t *cursor;                             /* one word */
+} npb_episode_records_desc_t;
+NPB_API int npb_set_episode_records(NpbHandle *h, const npb_episode_records_desc_t *desc);
+NPB_API const char *npb_episode_records_check(const npb_episode_records_desc_t *desc, int has_autoreset, int summary_keys);
+
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the
  * rocprofv3 FETCH_SIZE / WRITE_SIZE counters (tools/profile_traffic.py). */

@@ -398,6 +398,19 @@ class NpbEpisodeStreamsDesc(ctypes.Structure):
                 ("n_bank_seeds", ctypes.c_int), ("noise_out", ctypes.c_void_p), ("setpoint_out", ctypes.c_void_p), ("target_out", ctypes.c_void_p)]
 
 
+class NpbEpisodeRecordsDesc(ctypes.Structure):
+    """npb_episode_records_desc_t: the caller's record columns (device, ``capacity`` entries each), the optional terminal-observation block
+    and summary tables, and the cursor word"""
+    _fields_ = [("capacity", ctypes.c_int32), ("clear_summary", ctypes.c_int32)] + \
+               [(name, ctypes.c_void_p) for name in ("plant", "episode", "start", "length", "flags", "trip_flags", "step", "ret", "end_time", "final_obs",
+                                                     "first_created", "first_completed", "n_created", "n_completed", "cursor")]
+
+
+# the record's mandatory columns in descriptor order, with their numpy types (BatchedPlantEnv.enable_episode_records)
+EPISODE_RECORD_COLUMNS = (("plant", np.int32), ("episode", np.int32), ("start", np.int32), ("length", np.int32), ("flags", np.int32),
+                          ("trip_flags", np.uint32), ("step", np.int32), ("ret", np.float64), ("end_time", np.float64))
+
+
 def episode_streams_desc(block, bank_noise_seeds=None, bank_profile_seeds=None, outputs=(None, None, None)):
     """(desc, keep): an NpbEpisodeStreamsDesc and the host arrays it points into (host only, no library needed).  A table is a sequence of
     seeds, one per bank entry; both tables, where both are given, have the same length.  ``outputs``: three device addresses or None."""
@@ -570,6 +583,10 @@ def load():
         L.npb_episode_streams_check.argtypes = [ctypes.POINTER(NpbEpisodeStreamsDesc), ci, ci]
         L.npb_episode_streams_check.restype = ctypes.c_char_p
         L.npb_profile_get_positions.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "npb_set_episode_records"):     # a device-side log of finished episodes, with their work-order summary
+        L.npb_set_episode_records.argtypes = [vp, ctypes.POINTER(NpbEpisodeRecordsDesc)]
+        L.npb_episode_records_check.argtypes = [ctypes.POINTER(NpbEpisodeRecordsDesc), ci, ci]
+        L.npb_episode_records_check.restype = ctypes.c_char_p
     if L.npb_num_f64() != SCHEMA.total_f64 or L.npb_num_i32() != SCHEMA.total_i32:
         raise NpbError("libnpb.so was built against a different include/npb_fields.h (%d/%d vs %d/%d): rebuild"
                        % (L.npb_num_f64(), L.npb_num_i32(), SCHEMA.total_f64, SCHEMA.total_i32))

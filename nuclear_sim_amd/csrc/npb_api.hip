@@ -69,6 +69,8 @@ struct NpbHandle {
   /* npb_set_episode_streams: the mode's blocks, per-plant columns and seed tables (one allocation, es_mem), as the kernels read them; the
    * next row of each block a step takes (block = none left); the caller's output columns; whether bank seed tables were given */
   bool es_on; npb_episode_streams_t es; void *es_mem; int es_noise_cur, es_prof_cur; double *es_noise_out, *es_setpoint_out, *es_target_out; bool es_tables;
+  /* npb_set_episode_records: the caller's record columns and cursor, and the npb_step calls since they were switched on */
+  bool er_on; npb_episode_records_desc_t er; int er_step;
   double *ramp_prev;   /* npb_profile_ramp: the previous setpoint of every plant ([pitch], NaN = none yet), allocated on first use */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
   std::vector<int> plan_key;
@@ -547,12 +549,16 @@ int npb_set_maintenance_count_buffer(NpbHandle *h, int32_t *counts) {
   h->maint_cache_stale = true;     /* filled whole before the next step */
   return NPB_OK;
 }
+/* the episode records read or clear the handle's summary tables: the summary then stays as it is */
+static bool er_uses_summary(const NpbHandle *h) { return h->er_on && (h->er.first_created || h->er.clear_summary); }
 int npb_set_maintenance_log(NpbHandle *h, void *records, int capacity, uint32_t *cursor) {
   if (!h) return NPB_EINVAL;
   if (capacity < 0) return fail(h, NPB_EINVAL, "npb_set_maintenance_log: capacity must be >= 0");
   if (records && !cursor) return fail(h, NPB_EINVAL, "npb_set_maintenance_log: records without a cursor");
   if (!records && capacity > 0) return fail(h, NPB_EINVAL, "npb_set_maintenance_log: a capacity without records");
   if (((uintptr_t)records & 7u) || ((uintptr_t)cursor & 3u)) return fail(h, NPB_EINVAL, "npb_set_maintenance_log: records must be 8-byte and the cursor 4-byte aligned");
+  if (!records && er_uses_summary(h))
+    return fail(h, NPB_EINVAL, "npb_set_maintenance_log: episode records that copy or clear the work-order summary are on (npb_set_episode_records), and without a log there is no summary; switch the records off first");
   if (h->summary_on && records && h->summary.consume && capacity < h->n_plants)      /* the summary's own condition on the log it consumes */
     return fail(h, NPB_EINVAL, npb_maint_summary_check(&h->summary, capacity, h->n_plants));
   h->maint_log = npd_maint_log_t{(npb_maint_event_t *)records, records ? cursor : nullptr, records ? capacity : 0};
@@ -593,6 +599,8 @@ const char *npb_maint_summary_check(const npb_maint_summary_desc_t *D, int log_c
 }
 int npb_set_maintenance_summary(NpbHandle *h, const npb_maint_summary_desc_t *desc) {
   if (!h) return NPB_EINVAL;
+  if (er_uses_summary(h))
+    return fail(h, NPB_EINVAL, "npb_set_maintenance_summary: episode records that copy or clear the work-order summary are on (npb_set_episode_records) and hold its tables and key count; switch the records off first");
   if (!desc) { h->summary_on = false; return NPB_OK; }
   if (const char *why = npb_maint_summary_check(desc, h->maint_log.cursor ? h->maint_log.capacity : -1, h->n_plants)) return fail(h, NPB_EINVAL, why);
   if (!h->summary_ticket) {
@@ -968,6 +976,8 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
   if (!h) return NPB_EINVAL;
   if (h->autoreset && !done)      /* the episode kernel reads the step's terminations from the done column */
     return fail(h, NPB_EINVAL, "npb_step: autoreset is on (npb_set_autoreset) and needs the done column: it must not be NULL");
+  if (h->er_on && h->er.final_obs && !obs)
+    return fail(h, NPB_EINVAL, "npb_step: episode records with final_obs are on (npb_set_episode_records) and copy the terminal row of the obs column: it must not be NULL");
   if (h->params.heat_source == NPB_HEAT_EXTERNAL && !noise_z)      /* a NULL column would read as 0 MW thermal, silently */
     return fail(h, NPB_EINVAL, "npb_step: params.heat_source is NPB_HEAT_EXTERNAL, whose thermal power arrives in the noise_z column (include/npb_params.h): it must not be NULL");
   /* what the autoreset's restores take along beside the arena, from the bank while it has slots, else from the snapshot.  The step
@@ -1034,6 +1044,9 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
   else if (maint && h->params.mode != NPB_MODE_FULL)   /* a full-mode step kernel has run the rule itself, for the waves whose pump phase found something */
     h->K->maint(NPB_N(h), h->f64, h->maint_side, h->maint_counts, h->n_plants, (hipStream_t)stream);
   if (maint) summary_fold(h, (hipStream_t)stream);      /* the rule has appended this step's records: the summary is current when the call returns */
+  if (h->er_on && h->autoreset)      /* the episodes that end on this step, recorded while everything still describes them; then their summary rows cleared */
+    h->K->episode_records(h->n_plants, NPB_N(h), h->f64, done, reward, obs, trip_flags, counters_of(h), h->ep_start,
+                          h->max_episode_steps, h->er_step++, &h->er, er_uses_summary(h) ? &h->summary : nullptr, (hipStream_t)stream);
   if (h->autoreset)   /* same stream, nothing read back, the maintenance cache kept per plant by the kernel itself */
     h->K->episode(h->params.mode, h->n_plants, NPB_N(h), h->f64, source_of(h, from_bank), done, reward, obs, counters_of(h),
                   h->ep_out_len, h->ep_out_ret, h->ep_out_truncated, h->ep_final_obs, h->max_episode_steps,
@@ -1082,6 +1095,7 @@ int npb_set_autoreset(NpbHandle *h, int enabled, int max_episode_steps) {
   if (!h) return NPB_EINVAL;
   if (!enabled) {
     if (h->es_on) return fail(h, NPB_EINVAL, "npb_set_autoreset: episode streams are on (npb_set_episode_streams) and read the restarts off the autoreset's episode index; switch the mode off first");
+    if (h->er_on) return fail(h, NPB_EINVAL, "npb_set_autoreset: episode records are on (npb_set_episode_records) and record the episodes the autoreset ends; switch the records off first");
     h->autoreset = false; return NPB_OK;
   }
   if (max_episode_steps < 0) return fail(h, NPB_EINVAL, "npb_set_autoreset: max_episode_steps must be >= 0 (0 = no limit)");
@@ -1413,6 +1427,32 @@ int npb_profile_set_state(NpbHandle *h, const uint32_t *key, const int32_t *pos,
                               NPB_PROFILE_NUM_CARRIED, hipMemcpyHostToDevice, st));
   if (int rc = mt_state_upload(h, h->prof_g, key, pos, has_gauss, cached, st)) return rc;      /* (waits for the stream) */
   h->prof_pos = position;
+  return NPB_OK;
+}
+
+/* ---- episode records (include/npb.h) */
+const char *npb_episode_records_check(const npb_episode_records_desc_t *D, int has_autoreset, int summary_keys) {
+  if (!D) return nullptr;
+  if (!has_autoreset) return "npb_set_episode_records: no autoreset (npb_set_autoreset first): the records are of the episodes it ends";
+  if (D->capacity < 1) return "npb_set_episode_records: capacity must be >= 1";
+  if (!D->plant || !D->episode || !D->start || !D->length || !D->flags || !D->trip_flags || !D->step || !D->ret || !D->end_time || !D->cursor)
+    return "npb_set_episode_records: the columns plant, episode, start, length, flags, trip_flags, step, ret, end_time and the cursor must not be NULL";
+  if (((uintptr_t)D->plant & 3u) || ((uintptr_t)D->episode & 3u) || ((uintptr_t)D->start & 3u) || ((uintptr_t)D->length & 3u) || ((uintptr_t)D->flags & 3u) ||
+      ((uintptr_t)D->trip_flags & 3u) || ((uintptr_t)D->step & 3u) || ((uintptr_t)D->cursor & 3u) || ((uintptr_t)D->ret & 7u) || ((uintptr_t)D->end_time & 7u) ||
+      ((uintptr_t)D->final_obs & 7u) || ((uintptr_t)D->first_created & 7u) || ((uintptr_t)D->first_completed & 7u) || ((uintptr_t)D->n_created & 3u) ||
+      ((uintptr_t)D->n_completed & 3u))
+    return "npb_set_episode_records: the double columns must be 8-byte, the int32 columns and the cursor 4-byte aligned";
+  const int tables = (D->first_created != nullptr) + (D->first_completed != nullptr) + (D->n_created != nullptr) + (D->n_completed != nullptr);
+  if (tables != 0 && tables != 4) return "npb_set_episode_records: only part of the four summary tables given (first_created, first_completed, n_created, n_completed): all or none";
+  if (tables && summary_keys <= 0) return "npb_set_episode_records: summary columns without a work-order summary set (npb_set_maintenance_summary first)";
+  if (D->clear_summary && summary_keys <= 0) return "npb_set_episode_records: clear_summary without a work-order summary set (npb_set_maintenance_summary first)";
+  return nullptr;
+}
+int npb_set_episode_records(NpbHandle *h, const npb_episode_records_desc_t *desc) {
+  if (!h) return NPB_EINVAL;
+  if (!desc) { h->er_on = false; return NPB_OK; }
+  if (const char *why = npb_episode_records_check(desc, h->autoreset ? 1 : 0, h->summary_on ? h->summary.n_keys : 0)) return fail(h, NPB_EINVAL, why);
+  h->er = *desc; h->er_step = 0; h->er_on = true;
   return NPB_OK;
 }
 

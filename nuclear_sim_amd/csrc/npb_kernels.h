@@ -79,6 +79,12 @@ typedef struct {
    * out[r * n_watched + j], one launch */
   void (*sample)(const void *arena, size_t npad, const int *plan_dev, int n_fields, const npb_sample_row_t *side_dev, int n_rows,
                  const int32_t *ids_dev, int n_watched, double *out, hipStream_t stream);
+  /* npb_set_episode_records: one record per episode that ends on this step, before the episode kernel does its bookkeeping.  C / start: the
+   * handle's carried counters and bank entries (start NULL = no bank); step: npb_step calls since the records were switched on; summary: the
+   * handle's work-order summary while the records copy or clear it, else NULL */
+  void (*episode_records)(int n_plants, size_t npad, const void *arena, const uint8_t *done, const double *reward, const double *obs,
+                          const uint32_t *trip_flags, npb_episode_counters_t C, const int32_t *start, int max_steps, int step,
+                          const npb_episode_records_desc_t *D, const npb_maint_summary_desc_t *summary, hipStream_t stream);
 } npb_launchers_t;
 extern npb_launchers_t npb_launch_table, npb32_launch_table;
 /* the same for either storage type */

@@ -1600,12 +1600,15 @@ static void NPB_LAUNCHER(operator_turbine_maint)(int n_plants, size_t npad, void
 }
 static void NPB_LAUNCHER(sample)(const void *arena, size_t npad, const int *plan_dev, int n_fields, const npb_sample_row_t *side_dev, int n_rows,
                                  const int32_t *ids_dev, int n_watched, double *out, hipStream_t stream);     /* behind every other kernel, at the end of the file */
+static void NPB_LAUNCHER(episode_records)(int n_plants, size_t npad, const void *arena, const uint8_t *done, const double *reward, const double *obs,
+                                          const uint32_t *trip_flags, npb_episode_counters_t C, const int32_t *start, int max_steps, int step,
+                                          const npb_episode_records_desc_t *D, const npb_maint_summary_desc_t *summary, hipStream_t stream);     /* the same */
 /* not const: clang emits a namespace-scope const into the device code too, where these host functions do not exist */
 extern "C" npb_launchers_t NPB_LAUNCHER(table) = {
   NPB_LAUNCHER(step), NPB_LAUNCHER(maint), NPB_LAUNCHER(observe), NPB_LAUNCHER(init), NPB_LAUNCHER(reset),
   NPB_LAUNCHER(field_get), NPB_LAUNCHER(field_set), NPB_LAUNCHER(gather), NPB_LAUNCHER(restore), NPB_LAUNCHER(episode),
   NPB_LAUNCHER(operator_maint), NPB_LAUNCHER(operator_component_maint), NPB_LAUNCHER(operator_turbine_maint), NPB_LAUNCHER(maint_all),
-  NPB_LAUNCHER(sample),
+  NPB_LAUNCHER(sample), NPB_LAUNCHER(episode_records),
 };
 #ifndef NPB_BUILD_F32
 /* npb_reset / npb_reset_reference / npb_restore: the episode counters (len, ret) and the carried start entries (start: -1, not from
@@ -1702,4 +1705,92 @@ static void NPB_LAUNCHER(sample)(const void *arena, size_t npad, const int *plan
   const int block = n_watched <= 64 ? 64 : 256;      /* a short watch list: one wave per row, no idle waves */
   hipLaunchKernelGGL(npb_sample_kernel, dim3((n_watched + block - 1) / block, n_rows), dim3(block), 0, stream, (const npd_real_t *)arena, npad, plan_dev,
                      n_fields, side_dev, ids_dev, out, n_watched);
+}
+
+/* npb_set_episode_records: the record of every episode that ends on this step, behind the step kernel, the rule and the summary fold and
+ * BEFORE the episode kernel, which then does the bookkeeping and the restore as it always does: here the arena, the step's output columns
+ * and the carried counters still describe the episode that ended.  Nothing of them is written */
+struct npd_episode_records_t {
+  npb_episode_records_desc_t D;                               /* the caller's columns and cursor */
+  const int32_t *len; const double *ret; const int32_t *index; const int32_t *start;      /* carried [pitch]; start NULL = no bank */
+  double *s_first_created, *s_first_completed; int32_t *s_n_created, *s_n_completed;      /* the handle's summary tables [n_keys][n_plants], or NULL */
+  int n_keys;
+  int max_steps;                                              /* 0 = no limit */
+  int step;                                                   /* npb_step calls since the records were switched on */
+};
+__global__ __launch_bounds__(NPB_WAVE) void npb_episode_records_kernel(int n_plants, size_t N, const npd_real_t *__restrict__ f64, const uint8_t *__restrict__ done,
+                                                                       const double *__restrict__ reward, const double *__restrict__ obs,
+                                                                       const uint32_t *__restrict__ trip_flags, npd_episode_records_t R) {
+  const size_t block_base = (size_t)blockIdx.x * NPB_WAVE;
+  NPD_SEGMENT(f64, N, block_base);
+  const size_t p = block_base + threadIdx.x;
+  bool terminated = false, truncated = false;
+  int32_t len = 0;
+  double ret = 0.0;
+  if (p < (size_t)n_plants) {           /* the outcome as npb_episode_kernel decides it, behind this kernel on the same columns */
+    terminated = done[p] != 0;
+    len = R.len[p] + 1;
+    ret = reward ? R.ret[p] + reward[p] : R.ret[p];
+    truncated = R.max_steps > 0 && len >= R.max_steps && !terminated;     /* termination wins */
+  }
+  const bool ended = terminated || truncated;
+  if (!__any(ended)) return;
+  /* slots: the ended lanes of the wave take consecutive ones in plant order, one atomic for the wave */
+  const uint64_t rows = __ballot(ended);
+  const int lane = threadIdx.x, leader = __ffsll((unsigned long long)rows) - 1;
+  uint32_t base = 0;
+  if (lane == leader) base = __hip_atomic_fetch_add(R.D.cursor, (uint32_t)__popcll(rows), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  base = (uint32_t)__shfl((int)base, leader);
+  const uint32_t cap = (uint32_t)R.D.capacity;
+  const uint32_t slot = base + (uint32_t)__popcll(rows & ((1ull << lane) - 1ull));
+  const bool store = ended && slot < cap;
+  if (store) {
+    R.D.plant[slot] = (int32_t)p;
+    R.D.episode[slot] = R.index[p];
+    R.D.start[slot] = R.start ? R.start[p] : -1;
+    R.D.length[slot] = len;
+    R.D.flags[slot] = (terminated ? 1 : 0) | (truncated ? 2 : 0);
+    R.D.trip_flags[slot] = trip_flags ? trip_flags[p] : 0u;
+    R.D.step[slot] = R.step;
+    R.D.ret[slot] = ret;
+    R.D.end_time[slot] = NPD_F64_COL(PRIM, npb_prim_t, sim_time, 0);
+  }
+  if (R.D.final_obs && obs) {           /* the terminal observation: the wave's rows are consecutive in obs, and so are its slots */
+#pragma unroll
+    for (int k = 0; k < NPB_OBS_DIM; k++) {
+      const int idx = k * NPB_WAVE + lane, r = idx / NPB_OBS_DIM, c = idx % NPB_OBS_DIM;
+      const uint32_t slot_r = base + (uint32_t)__popcll(rows & ((1ull << r) - 1ull));
+      if (((rows >> r) & 1u) && slot_r < cap) R.D.final_obs[(size_t)slot_r * NPB_OBS_DIM + c] = obs[block_base * NPB_OBS_DIM + idx];
+    }
+  }
+  if (!ended || !R.s_first_created) return;
+  const bool copy = store && R.D.first_created;
+  for (int j = 0; j < R.n_keys; j++) {  /* the plant's summary cells as of this step (the fold ran before this launch), then "never" and 0 again */
+    const size_t cell = (size_t)j * (size_t)n_plants + p;
+    if (copy) {
+      const size_t out = (size_t)j * (size_t)cap + slot;
+      R.D.first_created[out] = R.s_first_created[cell];
+      R.D.first_completed[out] = R.s_first_completed[cell];
+      R.D.n_created[out] = R.s_n_created[cell];
+      R.D.n_completed[out] = R.s_n_completed[cell];
+    }
+    if (R.D.clear_summary) {
+      ((uint64_t *)R.s_first_created)[cell] = 0x7ff0000000000000ull;
+      ((uint64_t *)R.s_first_completed)[cell] = 0x7ff0000000000000ull;
+      R.s_n_created[cell] = 0;
+      R.s_n_completed[cell] = 0;
+    }
+  }
+}
+/* C: the handle's carried counters; start: its carried bank entries or NULL; summary: the handle's summary while the records copy or clear it, else NULL */
+static void NPB_LAUNCHER(episode_records)(int n_plants, size_t npad, const void *arena, const uint8_t *done, const double *reward, const double *obs,
+                                          const uint32_t *trip_flags, npb_episode_counters_t C, const int32_t *start, int max_steps, int step,
+                                          const npb_episode_records_desc_t *D, const npb_maint_summary_desc_t *summary, hipStream_t stream) {
+  npd_episode_records_t R;
+  R.D = *D; R.len = C.len; R.ret = C.ret; R.index = C.index; R.start = start; R.max_steps = max_steps; R.step = step;
+  R.s_first_created = summary ? summary->first_created : nullptr; R.s_first_completed = summary ? summary->first_completed : nullptr;
+  R.s_n_created = summary ? summary->n_created : nullptr; R.s_n_completed = summary ? summary->n_completed : nullptr;
+  R.n_keys = summary ? summary->n_keys : 0;
+  hipLaunchKernelGGL(npb_episode_records_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, n_plants, npad,
+                     (const npd_real_t *)arena, done, reward, obs, trip_flags, R);
 }

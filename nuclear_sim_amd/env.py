@@ -362,6 +362,15 @@ class BatchedPlantEnv:
     the plant's first episode.  ``stream_rows`` holds the rows the last step took (``noise``, ``setpoint``, ``target``; the env's own
     buffers), ``info["target_power"]`` is its target row.  ``scenarios.episode_stream_rows`` states the contract in numpy.  The stream
     classes' ``next()`` / ``fill()`` / ``set_state()`` raise while the mode is on.  Off by default: nothing changes.
+
+    Episode records (``enable_episode_records()``; needs ``autoreset=True``): the episode columns of ``info`` are overwritten by every
+    step, so whoever wants the finished episodes would have to read ``done | truncated`` back after each.  With records on the device
+    appends, behind every step, one record per plant whose episode ended on it (npb_set_episode_records) -- plant, episode index, bank
+    entry, length, return, terminated / truncated, trip flags, step number, plant clock, optionally the terminal observation and the
+    plant's rows of the work-order summary, which are then cleared so that the next episode's summary is its own -- and
+    ``episode_records()`` drains them, sorted by (step, plant), whenever the caller chooses; ``write_episode_records(path)`` writes the
+    table.  ``nuclear_sim_amd.timing.banked_trigger_times`` streams M scenarios through fewer lanes on it.  Output only; an episode
+    the caller abandons (``restore``, ``restore_from_bank``, ``reset``) leaves no record.  Off by default: nothing changes.
     """
 
     action_space_size = 15       # NuclearPlantEnv sim.py:916
@@ -503,7 +512,8 @@ class BatchedPlantEnv:
                     bank_seeds: Optional[Sequence[int]] = None, noise_generator: str = "host",
                     maintenance_log: Optional[int] = None, component_maintenance: bool = False,
                     component_thresholds: Optional[dict] = None, diagnostics: bool = False,
-                    power_profile_steps: Optional[int] = None, storage: str = "f64", episode_streams: bool = False) -> "BatchedPlantEnv":
+                    power_profile_steps: Optional[int] = None, storage: str = "f64", episode_streams: bool = False,
+                    episode_records=None) -> "BatchedPlantEnv":
         """One plant per seed, as data_gen's MaintenanceScenarioRunner builds them for
         ``compose_action_test_scenario(action, randomize=True, randomization_seed=seed)``
         (maintenance_scenario_runner.py:210-244): dt in minutes, ConstantHeatSource with 0.1 % noise seeded 42,
@@ -525,11 +535,15 @@ class BatchedPlantEnv:
         ``episode_streams`` as for the constructor (it needs ``autoreset`` and ``noise_generator="device"``): every episode then begins
         the runner's streams anew -- a restart from bank entry ``s`` the noise of ``RandomState(42)`` and the profile of
         ``RandomState(bank_seeds[s])`` (``bank_noise_seeds=[42] * M``, ``bank_profile_seeds=bank_seeds``), a restart from the plant's own
-        snapshot its own -- so each (plant, episode) is bit for bit the run of a fresh ``action_test(action, [that scenario's seed])``."""
+        snapshot its own -- so each (plant, episode) is bit for bit the run of a fresh ``action_test(action, [that scenario's seed])``.
+        ``episode_records`` = a capacity, or True for the default one: ``enable_episode_records(capacity)`` (needs ``autoreset``; a
+        summary enabled later is not part of these records -- call ``enable_episode_records`` after ``enable_maintenance_summary`` for that)."""
         if max_episode_steps is not None and not autoreset:
             raise ValueError("max_episode_steps needs autoreset=True")
         if episode_streams:      # refused before any device work
             cls._check_episode_streams(autoreset, True, noise_generator, True, power_profile_steps is not None)
+        if episode_records is not None and episode_records is not False and not autoreset:
+            raise ValueError("episode_records needs autoreset=True: the records are the episodes the autoreset ends")
         from . import scenarios
         env = cls(len(seeds), dt=dt, heat_source="constant", noise_enabled=True, noise_std_percent=0.1,
                   noise_seeds=[42] * len(seeds), device=device, maintenance=True, params=params, noise_generator=noise_generator,
@@ -558,6 +572,8 @@ class BatchedPlantEnv:
             else:
                 env.enable_episode_streams(bank_noise_seeds=[42] * len(bank_seeds),
                                            bank_profile_seeds=None if power_profile_steps is None else list(bank_seeds))
+        if episode_records is not None and episode_records is not False:
+            env.enable_episode_records(None if episode_records is True else int(episode_records))
         return env
 
     # ------------------------------------------------------------------ helpers
@@ -738,6 +754,9 @@ class BatchedPlantEnv:
         that did not fit the log are counted in ``maintenance_summary()["dropped"]``.  ``include_logged=True`` also folds, at once, the
         records the caller's log already holds: an existing log summarised under new keys.  Output only, like the log: ``snapshot``,
         ``restore``, the autoreset and the start bank leave it alone; ``clear_maintenance_summary(mask)`` starts the masked plants afresh."""
+        er = getattr(self, "_erec", None)
+        if er is not None and (er["n_keys"] or er["desc"].clear_summary):
+            raise _lib.NpbError("episode records that copy or clear the maintenance summary are on: disable_episode_records() first")
         if keys is None:
             if getattr(self, "_msum", None) is not None:
                 _lib.check(self.L.npb_set_maintenance_summary(self._h, None), self._h)
@@ -799,6 +818,118 @@ class BatchedPlantEnv:
         if getattr(self, "_msum", None) is None:
             raise _lib.NpbError("no maintenance summary: enable_maintenance_summary() first")
         _lib.check(self.L.npb_maint_summary_fold(self._h, self._stream()), self._h)
+
+    def enable_episode_records(self, capacity: Optional[int] = None, final_obs: bool = False, summary: Optional[bool] = None,
+                               clear_summary: Optional[bool] = None, *, off: bool = False) -> None:
+        """Have the device keep a log of FINISHED episodes (npb_set_episode_records): behind every step, one record per plant whose episode
+        ended on it -- plant, episode index, bank entry it started from, length, return, terminated / truncated, the step's trip flags, the
+        step number, the plant clock, with ``final_obs`` the terminal observation and with ``summary`` that episode's rows of the work-order
+        summary -- which ``episode_records()`` drains whenever the caller chooses.  Needs autoreset.  ``capacity`` records are allocated
+        (None = ``max(4 * n, 4096)``); episodes past them are counted, not written, until the next drain.  ``summary`` and
+        ``clear_summary`` default to whether a maintenance summary is enabled; ``clear_summary`` puts an ended plant's summary rows back to
+        "never" / 0 on the device, so that every record holds the work orders of its own episode (off, the summary goes on counting across
+        restarts, as it does without records).  ``off=True`` turns the records off and releases the buffers.  An episode the caller
+        abandons (``restore``, ``restore_from_bank``, ``reset``) starts the next index and leaves no record."""
+        if off:
+            if getattr(self, "_erec", None) is not None:
+                _lib.check(self.L.npb_set_episode_records(self._h, None), self._h)
+            self._erec = None
+            return
+        if not hasattr(self.L, "npb_set_episode_records"):
+            raise _lib.NpbError("libnpb.so has no npb_set_episode_records: rebuild")
+        if self._episode is None:
+            raise ValueError("episode records need autoreset=True: they are the episodes the autoreset ends")
+        has_summary = getattr(self, "_msum", None) is not None
+        summary = has_summary if summary is None else bool(summary)
+        clear_summary = has_summary if clear_summary is None else bool(clear_summary)
+        if (summary or clear_summary) and not has_summary:
+            raise ValueError("episode records with summary / clear_summary need enable_maintenance_summary() first")
+        cap = max(4 * self.n, 4096) if capacity is None else int(capacity)
+        if cap < 1:
+            raise ValueError("capacity must be >= 1")
+        n_keys = len(self._msum["keys"]) if summary else 0
+        d = _lib.NpbEpisodeRecordsDesc()
+        d.capacity, d.clear_summary = cap, int(clear_summary)
+        dev, host = {}, {}
+
+        def column(name, shape, dtype):
+            dev[name] = torch.zeros(shape, dtype=dtype, device=self.device)
+            host[name] = torch.empty(shape, dtype=dtype, pin_memory=True)      # the drain's landing place, as the maintenance log's
+            setattr(d, name, dev[name].data_ptr())
+        with torch.cuda.device(self.device):
+            for name, np_type in _lib.EPISODE_RECORD_COLUMNS:      # (uint32 trip flags travel as int32 bits)
+                column(name, (cap,), torch.float64 if np_type is np.float64 else torch.int32)
+            if final_obs:
+                column("final_obs", (cap, 22), torch.float64)
+            if summary:
+                for name in ("first_created", "first_completed"):
+                    column(name, (n_keys, cap), torch.float64)
+                for name in ("n_created", "n_completed"):
+                    column(name, (n_keys, cap), torch.int32)
+            cursor = torch.zeros(1, dtype=torch.int32, device=self.device)     # a uint32 on the device
+        d.cursor = cursor.data_ptr()
+        _lib.check(self.L.npb_set_episode_records(self._h, ctypes.byref(d)), self._h)
+        self._erec = {"desc": d, "dev": dev, "host": host, "cursor": cursor, "host_cursor": torch.empty(1, dtype=torch.int32, pin_memory=True),
+                      "capacity": cap, "n_keys": n_keys}
+
+    def disable_episode_records(self) -> None:
+        """episode records off; the buffers are released"""
+        self.enable_episode_records(off=True)
+
+    def episode_records(self, clear: bool = True, allow_overflow: bool = False) -> Dict[str, np.ndarray]:
+        """Drain the episode records on the env's stream: numpy columns of m records sorted by (step, plant) -- ``plant``, ``episode``,
+        ``start`` (-1 = not from the bank), ``length``, ``flags``, ``terminated`` / ``truncated`` (bool), ``trip_flags`` (uint32), ``step``
+        (steps since the records were enabled, 0 = the first), ``ret``, ``end_time`` (plant minutes); with ``final_obs``
+        ``final_observation`` [m, 22]; with ``summary`` ``first_created`` / ``first_completed`` (float64, +inf = never) and ``n_created`` /
+        ``n_completed`` (int32), [m, n_keys].  An overflowed log raises, naming how many episodes were dropped, and is left as it is,
+        unless ``allow_overflow`` (which of one step's episodes fitted is then not defined)."""
+        er = getattr(self, "_erec", None)
+        if er is None:
+            raise _lib.NpbError("no episode records: enable_episode_records() first")
+        stream = torch.cuda.current_stream(self.device)
+        er["host_cursor"].copy_(er["cursor"], non_blocking=True)
+        stream.synchronize()
+        count = int(er["host_cursor"][0]) & 0xFFFFFFFF
+        cap = er["capacity"]
+        if count > cap and not allow_overflow:
+            raise _lib.NpbError("episode records overflowed: %d episodes, capacity %d, %d dropped (enable_episode_records with a larger "
+                                "capacity, drain more often, or pass allow_overflow=True)" % (count, cap, count - cap))
+        m = min(count, cap)
+        raw = {}
+        if m:
+            for name, t in er["dev"].items():
+                if t.dim() == 2 and name != "final_obs":
+                    er["host"][name][:, :m].copy_(t[:, :m], non_blocking=True)
+                else:
+                    er["host"][name][:m].copy_(t[:m], non_blocking=True)
+            stream.synchronize()
+        for name, t in er["host"].items():
+            a = t.numpy()
+            raw[name] = (a[:, :m].T if (a.ndim == 2 and name != "final_obs") else a[:m]).copy()
+        if clear:
+            er["cursor"].zero_()
+        order = np.lexsort((raw["plant"], raw["step"]))
+        out = {name: raw[name][order] for name, _ in _lib.EPISODE_RECORD_COLUMNS}
+        out["trip_flags"] = out["trip_flags"].view(np.uint32)
+        out["terminated"], out["truncated"] = (out["flags"] & 1) != 0, (out["flags"] & 2) != 0
+        if "final_obs" in raw:
+            out["final_observation"] = raw["final_obs"][order]
+        for name in ("first_created", "first_completed", "n_created", "n_completed"):
+            if name in raw:
+                out[name] = np.ascontiguousarray(raw[name][order])
+        return out
+
+    def write_episode_records(self, path: str, clear: bool = True, allow_overflow: bool = False) -> None:
+        """Drain the episode records into a CSV (``.csv``) or Parquet file: one row per episode; the terminal observation as
+        ``final_observation_0`` .. ``_21`` and the summary tables as ``first_created_0`` .. per key"""
+        from . import maintlog
+        cols = {}
+        for name, a in self.episode_records(clear=clear, allow_overflow=allow_overflow).items():
+            if a.ndim == 1:
+                cols[name] = a
+            else:
+                cols.update({"%s_%d" % (name, j): np.ascontiguousarray(a[:, j]) for j in range(a.shape[1])})
+        maintlog.write(cols, path)
 
     def _order_buffers(self):
         """the buffers the perform_*_maintenance methods keep for their order columns, with the ``success`` column they all return"""
@@ -1088,6 +1219,7 @@ class BatchedPlantEnv:
         if getattr(self, "_h", None) is not None and self._h.value:
             self.L.npb_destroy(self._h)
             self._h = ctypes.c_void_p()
+        self._erec = None      # the episode records' buffers go with the handle
 
     def __del__(self):
         try:

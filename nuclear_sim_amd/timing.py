@@ -6,7 +6,7 @@ simulations one after the other to move the time onto a target (:121-195).  Here
 same action-test scenario (``BatchedPlantEnv.action_test``) with one state field overridden per plant, the device's work-order summary
 (``enable_maintenance_summary``) records per plant when the action's first work order was created and completed, and the only thing
 the host reads while the batch runs is one flag every 32 steps.  ``sweep`` is the optimiser's search as grid refinement over such
-batches.  It does not restate the reference's walk through configuration paths or its table of parameter bounds: the caller names the
+batches, and ``banked_trigger_times`` streams M scenarios through fewer lanes with the start bank and the episode records.  It does not restate the reference's walk through configuration paths or its table of parameter bounds: the caller names the
 state field and the interval.
 """
 from __future__ import annotations
@@ -96,3 +96,67 @@ def sweep(action: str, seed: int, field, lo: float, hi: float, target_hours: flo
     return {"value": None if best is None else best[0], "hours": None if best is None else best[1],
             "error_hours": None if best is None else best[2], "converged": best is not None and best[2] <= float(tolerance_hours),
             "rounds": done, "probes": np.array(probes, dtype=np.float64).reshape(-1, 3)}
+
+
+def banked_trigger_times(action: str, seeds: Sequence[int], hours: float, lanes: int, dt: float = 1.0, unit: Optional[int] = None,
+                         power_setpoint: float = 90.0, device: int = 0, randomize: bool = True, params: Optional[dict] = None,
+                         storage: str = "f64", capacity: Optional[int] = None) -> Dict[str, np.ndarray]:
+    """``trigger_times`` for M = ``len(seeds)`` scenarios streamed through ``lanes`` <= M plants: one env whose start bank holds the M
+    scenarios (``action_test(..., bank_seeds=seeds, autoreset=True, max_episode_steps=int(hours * 60 / dt), noise_generator="device",
+    episode_streams=True)``, slots ``arange(lanes) % M`` advancing by ``lanes``), a work-order summary of one key, and episode records that
+    carry each finished episode's summary rows and clear them (``enable_episode_records``).  Every episode that starts from bank entry s
+    is the run a fresh env of ``seeds[s]`` makes, so its record is that scenario's answer.
+
+    Each plant's first episode runs before its first restart from the bank; those records (``start == -1``) are ignored.  Plant p then
+    takes entries p, p + lanes, ... and no episode is longer than ``max_episode_steps``, so after ``(1 + ceil(M / lanes)) *
+    max_episode_steps`` steps every entry has a finished episode: the run stops there without ever reading a flag back.  The records are
+    drained once per ``max_episode_steps`` steps.  Where terminations let an entry be played more than once, its first record (by step,
+    then plant) is taken.
+
+    Returns, per seed, ``trigger_times``' keys -- ``first_created_hours`` / ``first_completed_hours`` (the summary's plant-clock minutes
+    / 60, NaN = never), ``n_created``, ``n_completed``, and ``steps`` (here: steps the env ran), ``dropped`` -- plus ``length`` (the
+    episode's steps) and ``terminated`` (it ended by a scram rather than by the step limit)."""
+    import torch
+    from .env import BatchedPlantEnv
+    seeds = [int(s) for s in seeds]
+    M, lanes = len(seeds), int(lanes)
+    if not 1 <= lanes <= M:
+        raise ValueError("lanes must be 1 .. len(seeds) = %d, not %d" % (M, lanes))
+    L = int(hours * 60 / dt)
+    if L < 1:
+        raise ValueError("hours * 60 / dt must be at least one step")
+    env = BatchedPlantEnv.action_test(action, seeds[:lanes], dt=dt, device=device, randomize=randomize, params=params, storage=storage,
+                                      bank_seeds=seeds, autoreset=True, max_episode_steps=L, noise_generator="device", episode_streams=True)
+    try:
+        env.enable_maintenance_summary([("feedwater", action, unit)])
+        env.enable_episode_records(capacity, summary=True, clear_summary=True)
+        sp = torch.full((lanes,), float(power_setpoint), dtype=torch.float64, device=env.device)
+        total = (1 + -(-M // lanes)) * L
+        out = {"first_created_hours": np.full(M, np.nan), "first_completed_hours": np.full(M, np.nan),
+               "n_created": np.zeros(M, dtype=np.int32), "n_completed": np.zeros(M, dtype=np.int32),
+               "length": np.zeros(M, dtype=np.int32), "terminated": np.zeros(M, dtype=bool)}
+        seen = np.zeros(M, dtype=bool)
+
+        def drain():
+            rec = env.episode_records()
+            for k in np.flatnonzero(rec["start"] >= 0):      # sorted by (step, plant): an entry's first record wins
+                s = int(rec["start"][k])
+                if seen[s]:
+                    continue
+                seen[s] = True
+                created, completed = rec["first_created"][k, 0] / 60.0, rec["first_completed"][k, 0] / 60.0
+                out["first_created_hours"][s] = created if np.isfinite(created) else np.nan
+                out["first_completed_hours"][s] = completed if np.isfinite(completed) else np.nan
+                out["n_created"][s], out["n_completed"][s] = rec["n_created"][k, 0], rec["n_completed"][k, 0]
+                out["length"][s], out["terminated"][s] = rec["length"][k], rec["terminated"][k]
+        for step in range(1, total + 1):
+            env.step(power_setpoint=sp)
+            if step % L == 0:
+                drain()
+        if not seen.all():
+            raise RuntimeError("banked_trigger_times: bank entries %r have no finished episode after %d steps" % (np.flatnonzero(~seen).tolist(), total))
+        out["steps"] = total
+        out["dropped"] = int(env.maintenance_summary()["dropped"].item())
+        return out
+    finally:
+        env.close()
