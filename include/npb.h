@@ -720,6 +720,69 @@ typedef struct npb_episode_records_desc_t {
 NPB_API int npb_set_episode_records(NpbHandle *h, const npb_episode_records_desc_t *desc);
 NPB_API const char *npb_episode_records_check(const npb_episode_records_desc_t *desc, int has_autoreset, int summary_keys);
 
+/* Column statistics: what a plant's STATE did, folded on the device into a handful of numbers per (column, plant) -- the lowest oil level,
+ * the peak tube-wall temperature, the mean electrical power, how long a level sat beyond a limit and when it first got there -- instead
+ * of a time series that somebody has to drain.  A column is an arena member (kinds / slots, as npb_gather_fields and npb_sampler_create
+ * take them) or a side row: a caller-owned DEVICE buffer of one value per plant (npb_sample_source_t with rows == 1: an info column, an
+ * obs column, the reward, a diagnostics row).  Members come first, then the side rows, n_cols = n_fields + n_sources <=
+ * NPB_COLUMN_STATS_MAX.  Every sample is widened to double as npb_sample_kernel widens it, and folded into the caller's device tables:
+ *   n_samples int32 [n_plants]             samples folded (mandatory)
+ *   min, max  double [n_cols][n_plants]    v < min ? v : min, v > max ? v : max: a NaN sample replaces neither; empty +inf / -inf
+ *   sum, sumsq double [n_cols][n_plants]   sum + v, sumsq + v * v (the product rounded before the add: the library is built with
+ *                                          -ffp-contract=off), sequential in step order; empty 0
+ *   last double [n_cols][n_plants]         the latest sample; empty NaN
+ *   first_beyond double [n_cols][n_plants] for a column with a limit (direction[c] = +1: v > limit[c], -1: v < limit[c], 0: no limit): the
+ *                                          plant clock prim.sim_time (as npb_get_field returns it) after the first step whose sample was
+ *                                          beyond the limit; empty +inf = never
+ *   n_beyond int32 [n_cols][n_plants]      samples that were beyond the limit; empty 0
+ * element [column * n_plants + plant].  Any table but n_samples may be NULL: not kept, not touched.  The caller initialises the tables
+ * with the empty values, or calls npb_column_stats_clear.  nuclear_sim_amd/colstats.py states the fold in numpy; the device produces its
+ * bits.
+ * With stats set npb_step launches ONE more kernel on its stream (grid (ceil(n / 256), n_cols), a thread per cell, no atomics): behind the
+ * step kernel, the rule and the work-order summary fold, BEFORE the episode-records kernel and the episode kernel -- the sample is the
+ * end-of-step state of the episode the step belonged to, before any restore.  npb_column_stats_fold is the same launch on request;
+ * npb_column_stats_clear puts the plants of mask (device uint8 [n_plants], NULL = all) back to the empty values in every table kept.  Both
+ * are NPB_EINVAL without stats.  The npb_perform_*_maintenance calls do not fold.
+ * Output only, like the work-order summary: npb_snapshot / npb_restore, the resets, the start bank, the autoreset and checkpoints neither
+ * read nor reset the tables.
+ * npb_set_column_stats(h, desc): desc = NULL turns the stats off.  The descriptor is copied (its host arrays too).  NPB_EINVAL with the reason
+ * in npb_last_error, before any device work, for what npb_column_stats_check refuses -- that check alone, without a handle, NULL =
+ * accepted, else the reason: a column count outside 1..NPB_COLUMN_STATS_MAX; a bad kind or slot; a source with a NULL base, an unknown
+ * type or rows != 1; a direction outside {-1, 0, +1}; a NaN limit; a NULL n_samples; a misaligned table (doubles 8-byte, int32 4-byte);
+ * first_beyond or n_beyond with no limit set.  NPB_VERSION stays 154: a binding detects the entry points by name.
+ * A handle that never calls this behaves as before in every entry point. */
+#define NPB_COLUMN_STATS_MAX 32
+typedef struct npb_column_stats_desc_t {
+  int n_fields; const int *kinds; const int *slots;      /* host; arena members, n_fields may be 0 */
+  int n_sources; const npb_sample_source_t *sources;     /* host descriptors of one-row device buffers; n_sources may be 0 */
+  const int *direction;                                  /* host [n_cols]: +1, -1, 0 = no limit; NULL = no limits */
+  const double *limit;                                   /* host [n_cols]; read where direction != 0 */
+  double *min, *max, *sum, *sumsq, *last, *first_beyond; /* device [n_cols][n_plants], each or NULL */
+  int32_t *n_beyond;                                     /* device [n_cols][n_plants] or NULL */
+  int32_t *n_samples;                                    /* device [n_plants] */
+} npb_column_stats_desc_t;
+NPB_API int npb_set_column_stats(NpbHandle *h, const npb_column_stats_desc_t *desc);
+NPB_API const char *npb_column_stats_check(const npb_column_stats_desc_t *desc, int n_plants);
+NPB_API int npb_column_stats_fold(NpbHandle *h, void *stream);
+NPB_API int npb_column_stats_clear(NpbHandle *h, const uint8_t *mask, void *stream);
+/* The statistics of each EPISODE in its record (npb_set_episode_records): a descriptor of its own, so that npb_episode_records_desc_t
+ * keeps its layout.  Record-side columns double / int32 [n_cols][capacity], element [column * capacity + slot], and n_samples int32
+ * [capacity], each NULL or set -- set only where the handle keeps that statistic.  npb_episode_records_kernel then copies an ended plant's
+ * cells into its slot as it copies the work-order summary's, and with clear != 0 puts them back to the empty values, whether or not the
+ * record fitted: each record then holds the statistics of its own episode and n_samples == length.  Needs records and stats both on
+ * (NPB_EINVAL otherwise, and for a misaligned column).  While it is set npb_set_column_stats (another descriptor, or NULL) is refused;
+ * desc = NULL drops it, and so does EVERY successful npb_set_episode_records, with a descriptor or with NULL: the record-side columns
+ * belong to one set of record columns and their capacity, so a caller who sets the records again calls this again behind it.  The
+ * handle keeps what the kernel reads of both descriptors in device memory of its own and hands the kernel one pointer; the call
+ * uploads it synchronously.  Off, the records kernel stores exactly what it stored before. */
+typedef struct npb_episode_record_stats_desc_t {
+  double *min, *max, *sum, *sumsq, *last, *first_beyond; /* device [n_cols][capacity], each or NULL */
+  int32_t *n_beyond;                                     /* device [n_cols][capacity] or NULL */
+  int32_t *n_samples;                                    /* device [capacity] or NULL */
+  int clear;                                             /* != 0: an ended plant's cells back to the empty values */
+} npb_episode_record_stats_desc_t;
+NPB_API int npb_set_episode_record_stats(NpbHandle *h, const npb_episode_record_stats_desc_t *desc);
+
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the
  * rocprofv3 FETCH_SIZE / WRITE_SIZE counters (tools/profile_traffic.py). */

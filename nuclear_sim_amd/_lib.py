@@ -411,6 +411,81 @@ EPISODE_RECORD_COLUMNS = (("plant", np.int32), ("episode", np.int32), ("start", 
                           ("trip_flags", np.uint32), ("step", np.int32), ("ret", np.float64), ("end_time", np.float64))
 
 
+# include/npb.h npb_column_stats_desc_t: per-plant column statistics folded on the device (npb_set_column_stats)
+COLUMN_STATS_MAX = 32
+COLUMN_STATS = ("min", "max", "sum", "sumsq", "last", "first_beyond", "n_beyond")      # the per-cell tables in descriptor order (colstats.STATS)
+COLUMN_STATS_NEED_LIMIT = ("first_beyond", "n_beyond")
+
+
+class NpbColumnStatsDesc(ctypes.Structure):
+    """npb_column_stats_desc_t: arena members and one-row side sources (host arrays), the limits (host arrays) and the caller's device tables"""
+    _fields_ = [("n_fields", ctypes.c_int), ("kinds", ctypes.POINTER(ctypes.c_int)), ("slots", ctypes.POINTER(ctypes.c_int)),
+                ("n_sources", ctypes.c_int), ("sources", ctypes.POINTER(NpbSampleSource)),
+                ("direction", ctypes.POINTER(ctypes.c_int)), ("limit", ctypes.POINTER(ctypes.c_double))] + \
+               [(name, ctypes.c_void_p) for name in COLUMN_STATS + ("n_samples",)]
+
+
+class NpbEpisodeRecordStatsDesc(ctypes.Structure):
+    """npb_episode_record_stats_desc_t: the record-side columns [n_cols][capacity] of each statistic, n_samples [capacity], and ``clear``"""
+    _fields_ = [(name, ctypes.c_void_p) for name in COLUMN_STATS + ("n_samples",)] + [("clear", ctypes.c_int)]
+
+
+def column_stats_request(columns, limits=None, stats=("min", "max", "sum", "sumsq", "last"), info_columns=None) -> dict:
+    """What ``BatchedPlantEnv.enable_column_stats`` asks of npb_set_column_stats, from the caller's words; a pure function, host only, so an
+    unknown name, index or statistic is refused (ValueError) before any device work.  ``columns``: a state member as ``set_fields`` keys it
+    (``name``, ``(name, instance)`` or ``(name, instance, k)``), ``("info", column_name)``, ``("obs", i)`` or ``"reward"``.  ``limits``:
+    ``{column_index: (">" | "<", value)}``, the index into ``columns``.  ``stats``: names of ``COLUMN_STATS``.
+    Returns {"members": [(kind, slot)] -- 0 f64 / 1 i32, as npb_gather_fields takes them --, "sides": [(buffer, element offset, plant stride)]
+    with buffer "info" | "obs" | "reward" (float64 device buffers of the env), "order": for every entry of ``columns`` its column on the
+    device (members come first there, then the side rows), "direction" / "limit": lists per DEVICE column, "stats": the tables kept, in
+    descriptor order}."""
+    if info_columns is None:
+        from .env import INFO_COLUMNS as info_columns
+    columns = list(columns)
+    if not 1 <= len(columns) <= COLUMN_STATS_MAX:
+        raise ValueError("column statistics take 1 to %d columns, not %d" % (COLUMN_STATS_MAX, len(columns)))
+    stats = (stats,) if isinstance(stats, str) else tuple(stats)
+    for name in stats:
+        if name not in COLUMN_STATS:
+            raise ValueError("unknown statistic %r: one of %r" % (name, COLUMN_STATS))
+    members, sides, where = [], [], []
+    for col in columns:
+        key = (col,) if isinstance(col, str) else tuple(col)
+        if key == ("reward",):
+            where.append(("side", len(sides))); sides.append(("reward", 0, 1))
+        elif key and key[0] == "info":
+            if len(key) != 2 or key[1] not in info_columns:
+                raise ValueError("unknown info column %r: one of %r" % (key[1:], tuple(info_columns)))
+            where.append(("side", len(sides))); sides.append(("info", list(info_columns).index(key[1]), len(info_columns)))
+        elif key and key[0] == "obs":
+            if len(key) != 2 or isinstance(key[1], bool) or not isinstance(key[1], (int, np.integer)) or not 0 <= key[1] < OBS_DIM:
+                raise ValueError("unknown obs column %r: ('obs', i) with 0 <= i < %d" % (key[1:], OBS_DIM))
+            where.append(("side", len(sides))); sides.append(("obs", int(key[1]), OBS_DIM))
+        else:
+            if not key or not isinstance(key[0], str) or key[0] not in SCHEMA.by_name or len(key) > 3:
+                raise ValueError("unknown column %r: a state member (name, (name, instance) or (name, instance, k)), ('info', name), "
+                                 "('obs', i) or 'reward'" % (col,))
+            try:
+                kind, slot = SCHEMA.slot(key[0], *[int(x) for x in key[1:]])
+            except IndexError:
+                raise ValueError("column %r: no such instance or element of %s" % (col, key[0])) from None
+            where.append(("member", len(members))); members.append((0 if kind == "f64" else 1, slot))
+    order = [i if kind == "member" else len(members) + i for kind, i in where]
+    direction, limit = [0] * len(columns), [0.0] * len(columns)
+    for c, lim in (limits or {}).items():
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c < len(columns):
+            raise ValueError("limit on column %r: the columns are 0 .. %d" % (c, len(columns) - 1))
+        if not isinstance(lim, (tuple, list)) or len(lim) != 2 or lim[0] not in (">", "<"):
+            raise ValueError("the limit of column %d must be ('>' | '<', value), not %r" % (c, lim))
+        if np.isnan(float(lim[1])):
+            raise ValueError("the limit of column %d is NaN" % c)
+        direction[order[c]], limit[order[c]] = (1 if lim[0] == ">" else -1), float(lim[1])
+    if any(name in COLUMN_STATS_NEED_LIMIT for name in stats) and not any(direction):
+        raise ValueError("the statistics %r need a limit on some column" % (COLUMN_STATS_NEED_LIMIT,))
+    return {"members": members, "sides": sides, "order": order, "direction": direction, "limit": limit,
+            "stats": tuple(name for name in COLUMN_STATS if name in stats)}
+
+
 def episode_streams_desc(block, bank_noise_seeds=None, bank_profile_seeds=None, outputs=(None, None, None)):
     """(desc, keep): an NpbEpisodeStreamsDesc and the host arrays it points into (host only, no library needed).  A table is a sequence of
     seeds, one per bank entry; both tables, where both are given, have the same length.  ``outputs``: three device addresses or None."""
@@ -587,6 +662,13 @@ def load():
         L.npb_set_episode_records.argtypes = [vp, ctypes.POINTER(NpbEpisodeRecordsDesc)]
         L.npb_episode_records_check.argtypes = [ctypes.POINTER(NpbEpisodeRecordsDesc), ci, ci]
         L.npb_episode_records_check.restype = ctypes.c_char_p
+    if hasattr(L, "npb_set_column_stats"):     # per-plant column statistics folded behind every step, and their copy into the episode records
+        L.npb_set_column_stats.argtypes = [vp, ctypes.POINTER(NpbColumnStatsDesc)]
+        L.npb_column_stats_check.argtypes = [ctypes.POINTER(NpbColumnStatsDesc), ci]
+        L.npb_column_stats_check.restype = ctypes.c_char_p
+        L.npb_column_stats_fold.argtypes = [vp, vp]
+        L.npb_column_stats_clear.argtypes = [vp, vp, vp]
+        L.npb_set_episode_record_stats.argtypes = [vp, ctypes.POINTER(NpbEpisodeRecordStatsDesc)]
     if L.npb_num_f64() != SCHEMA.total_f64 or L.npb_num_i32() != SCHEMA.total_i32:
         raise NpbError("libnpb.so was built against a different include/npb_fields.h (%d/%d vs %d/%d): rebuild"
                        % (L.npb_num_f64(), L.npb_num_i32(), SCHEMA.total_f64, SCHEMA.total_i32))

@@ -71,6 +71,10 @@ struct NpbHandle {
   bool es_on; npb_episode_streams_t es; void *es_mem; int es_noise_cur, es_prof_cur; double *es_noise_out, *es_setpoint_out, *es_target_out; bool es_tables;
   /* npb_set_episode_records: the caller's record columns and cursor, and the npb_step calls since they were switched on */
   bool er_on; npb_episode_records_desc_t er; int er_step;
+  /* npb_set_column_stats: the columns on the device (cs.cols, one allocation; NULL = off) and the caller's tables; npb_set_episode_record_stats:
+   * the record-side columns that take them */
+  npb_column_stats_t cs; bool ers_on; npb_episode_record_stats_desc_t ers;
+  npb_record_stats_t *ers_dev;      /* what the records kernel reads of both (device, allocated on first use, uploaded by npb_set_episode_record_stats) */
   double *ramp_prev;   /* npb_profile_ramp: the previous setpoint of every plant ([pitch], NaN = none yet), allocated on first use */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
   std::vector<int> plan_key;
@@ -450,6 +454,8 @@ int npb_destroy(NpbHandle *h) {
   if (h->prof_z) (void)hipFree(h->prof_z);
   if (h->ramp_prev) (void)hipFree(h->ramp_prev);
   if (h->es_mem) (void)hipFree(h->es_mem);
+  if (h->cs.cols) (void)hipFree((void *)h->cs.cols);
+  if (h->ers_dev) (void)hipFree(h->ers_dev);
   for (Sampler *sm : h->samplers) if (sm) { (void)hipFree(sm->dev); delete sm; }
   delete h;
   return NPB_OK;
@@ -1044,9 +1050,12 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
   else if (maint && h->params.mode != NPB_MODE_FULL)   /* a full-mode step kernel has run the rule itself, for the waves whose pump phase found something */
     h->K->maint(NPB_N(h), h->f64, h->maint_side, h->maint_counts, h->n_plants, (hipStream_t)stream);
   if (maint) summary_fold(h, (hipStream_t)stream);      /* the rule has appended this step's records: the summary is current when the call returns */
+  if (h->cs.cols)      /* the end-of-step state of the episode this step belonged to, before any restore */
+    h->K->column_stats_fold(h->f64, NPB_N(h), &h->cs, h->n_plants, (hipStream_t)stream);
   if (h->er_on && h->autoreset)      /* the episodes that end on this step, recorded while everything still describes them; then their summary rows cleared */
     h->K->episode_records(h->n_plants, NPB_N(h), h->f64, done, reward, obs, trip_flags, counters_of(h), h->ep_start,
-                          h->max_episode_steps, h->er_step++, &h->er, er_uses_summary(h) ? &h->summary : nullptr, (hipStream_t)stream);
+                          h->max_episode_steps, h->er_step++, &h->er, er_uses_summary(h) ? &h->summary : nullptr,
+                          h->ers_on ? h->ers_dev : nullptr, (hipStream_t)stream);
   if (h->autoreset)   /* same stream, nothing read back, the maintenance cache kept per plant by the kernel itself */
     h->K->episode(h->params.mode, h->n_plants, NPB_N(h), h->f64, source_of(h, from_bank), done, reward, obs, counters_of(h),
                   h->ep_out_len, h->ep_out_ret, h->ep_out_truncated, h->ep_final_obs, h->max_episode_steps,
@@ -1450,9 +1459,119 @@ const char *npb_episode_records_check(const npb_episode_records_desc_t *D, int h
 }
 int npb_set_episode_records(NpbHandle *h, const npb_episode_records_desc_t *desc) {
   if (!h) return NPB_EINVAL;
-  if (!desc) { h->er_on = false; return NPB_OK; }
+  if (!desc) { h->er_on = false; h->ers_on = false; return NPB_OK; }      /* (the record-side statistics go with the records) */
   if (const char *why = npb_episode_records_check(desc, h->autoreset ? 1 : 0, h->summary_on ? h->summary.n_keys : 0)) return fail(h, NPB_EINVAL, why);
-  h->er = *desc; h->er_step = 0; h->er_on = true;
+  /* new record columns, perhaps of another capacity: the record-side statistics columns belonged to the old ones and are dropped with
+   * them (npb_set_episode_record_stats again, behind this call, for the new ones) */
+  h->er = *desc; h->er_step = 0; h->er_on = true; h->ers_on = false;
+  return NPB_OK;
+}
+
+/* ---- column statistics (include/npb.h, npd_column_stats.h) */
+const char *npb_column_stats_check(const npb_column_stats_desc_t *D, int n_plants) {
+  if (!D) return nullptr;
+  if (n_plants < 1) return "npb_set_column_stats: n_plants must be >= 1";
+  if (D->n_fields < 0 || D->n_sources < 0 || (int64_t)D->n_fields + D->n_sources < 1 || (int64_t)D->n_fields + D->n_sources > NPB_COLUMN_STATS_MAX)
+    return "npb_set_column_stats: the column count (n_fields + n_sources) must be 1 .. NPB_COLUMN_STATS_MAX (32)";
+  if ((D->n_fields > 0 && (!D->kinds || !D->slots)) || (D->n_sources > 0 && !D->sources))
+    return "npb_set_column_stats: fields without kinds / slots, or side sources without their descriptors";
+  for (int f = 0; f < D->n_fields; f++) {
+    int col, sub, access;
+    if ((D->kinds[f] != NPB_KIND_F64 && D->kinds[f] != NPB_KIND_I32) || !locate(NPB_STORAGE_F64, D->kinds[f], D->slots[f], &col, &sub, &access))
+      return "npb_set_column_stats: bad field kind or slot";
+  }
+  for (int k = 0; k < D->n_sources; k++) {
+    const npb_sample_source_t &S = D->sources[k];
+    if (!S.base) return "npb_set_column_stats: a side source has a NULL base";
+    if (S.type < NPB_SAMPLE_F64 || S.type > NPB_SAMPLE_U8) return "npb_set_column_stats: a side source has an unknown element type";
+    if (S.rows != 1) return "npb_set_column_stats: a side source must have rows == 1 (one value per plant)";
+    if (S.plant_stride < 0) return "npb_set_column_stats: a side source needs a plant stride >= 0";
+  }
+  const int n_cols = D->n_fields + D->n_sources;
+  bool limited = false;
+  for (int c = 0; D->direction && c < n_cols; c++) {
+    if (D->direction[c] < -1 || D->direction[c] > 1) return "npb_set_column_stats: a direction outside {-1, 0, +1}";
+    if (D->direction[c] != 0) {
+      if (!D->limit || D->limit[c] != D->limit[c]) return "npb_set_column_stats: a NaN limit (or a direction without the limit array)";
+      limited = true;
+    }
+  }
+  if (!D->n_samples) return "npb_set_column_stats: n_samples must not be NULL";
+  if (((uintptr_t)D->min & 7u) || ((uintptr_t)D->max & 7u) || ((uintptr_t)D->sum & 7u) || ((uintptr_t)D->sumsq & 7u) || ((uintptr_t)D->last & 7u) ||
+      ((uintptr_t)D->first_beyond & 7u) || ((uintptr_t)D->n_beyond & 3u) || ((uintptr_t)D->n_samples & 3u))
+    return "npb_set_column_stats: a misaligned table: the double tables must be 8-byte, the int32 tables 4-byte aligned";
+  if ((D->first_beyond || D->n_beyond) && !limited) return "npb_set_column_stats: limit tables (first_beyond, n_beyond) without a limit on any column";
+  return nullptr;
+}
+int npb_set_column_stats(NpbHandle *h, const npb_column_stats_desc_t *desc) {
+  if (!h) return NPB_EINVAL;
+  if (h->ers_on)
+    return fail(h, NPB_EINVAL, "npb_set_column_stats: episode records that copy or clear the column statistics are on (npb_set_episode_record_stats) and hold its tables and column count; switch them off first");
+  if (const char *why = npb_column_stats_check(desc, h->n_plants)) return fail(h, NPB_EINVAL, why);
+  NPB_USE_DEVICE(h);
+  if (!desc) {
+    if (h->cs.cols) (void)hipFree((void *)h->cs.cols);      /* (hipFree waits for the device: a fold still in flight finishes first) */
+    h->cs = npb_column_stats_t{};
+    return NPB_OK;
+  }
+  const int n_cols = desc->n_fields + desc->n_sources;
+  npb_colstat_col_t cols[NPB_COLUMN_STATS_MAX] = {};
+  for (int c = 0; c < n_cols; c++) {
+    npb_colstat_col_t &C = cols[c];
+    if (c < desc->n_fields) {
+      if (!locate(h->storage, desc->kinds[c], desc->slots[c], &C.col, &C.sub, &C.kind)) return fail(h, NPB_EINVAL, "npb_set_column_stats: bad field kind or slot");
+    } else {
+      const npb_sample_source_t &S = desc->sources[c - desc->n_fields];
+      C.row = S.base; C.plant_stride = S.plant_stride; C.kind = 3 + S.type;
+    }
+    C.direction = desc->direction ? desc->direction[c] : 0;
+    C.limit = C.direction ? desc->limit[c] : 0.0;
+  }
+  void *dev = nullptr;
+  hipError_t e = hipMalloc(&dev, sizeof cols);
+  if (e != hipSuccess) return fail(h, NPB_ENOMEM, "npb_set_column_stats: hipMalloc of the column table failed", e);
+  e = hipMemcpy(dev, cols, sizeof cols, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { (void)hipFree(dev); return fail(h, NPB_EHIP, "npb_set_column_stats: upload of the column table failed", e); }
+  if (h->cs.cols) (void)hipFree((void *)h->cs.cols);
+  h->cs = npb_column_stats_t{(const npb_colstat_col_t *)dev, n_cols, desc->min, desc->max, desc->sum, desc->sumsq, desc->last, desc->first_beyond,
+                             desc->n_beyond, desc->n_samples};
+  return NPB_OK;
+}
+int npb_column_stats_fold(NpbHandle *h, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->cs.cols) return fail(h, NPB_EINVAL, "npb_column_stats_fold: no column statistics set (npb_set_column_stats first)");
+  NPB_USE_DEVICE(h);
+  h->K->column_stats_fold(h->f64, NPB_N(h), &h->cs, h->n_plants, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_column_stats_clear(NpbHandle *h, const uint8_t *mask, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->cs.cols) return fail(h, NPB_EINVAL, "npb_column_stats_clear: no column statistics set (npb_set_column_stats first)");
+  NPB_USE_DEVICE(h);
+  npb_launch_column_stats_clear(&h->cs, mask, h->n_plants, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_set_episode_record_stats(NpbHandle *h, const npb_episode_record_stats_desc_t *D) {
+  if (!h) return NPB_EINVAL;
+  if (!D) { h->ers_on = false; return NPB_OK; }
+  if (!h->er_on) return fail(h, NPB_EINVAL, "npb_set_episode_record_stats: no episode records (npb_set_episode_records first)");
+  if (!h->cs.cols) return fail(h, NPB_EINVAL, "npb_set_episode_record_stats: no column statistics set (npb_set_column_stats first)");
+  if (((uintptr_t)D->min & 7u) || ((uintptr_t)D->max & 7u) || ((uintptr_t)D->sum & 7u) || ((uintptr_t)D->sumsq & 7u) || ((uintptr_t)D->last & 7u) ||
+      ((uintptr_t)D->first_beyond & 7u) || ((uintptr_t)D->n_beyond & 3u) || ((uintptr_t)D->n_samples & 3u))
+    return fail(h, NPB_EINVAL, "npb_set_episode_record_stats: the double columns must be 8-byte, the int32 columns 4-byte aligned");
+  if ((D->min && !h->cs.min) || (D->max && !h->cs.max) || (D->sum && !h->cs.sum) || (D->sumsq && !h->cs.sumsq) || (D->last && !h->cs.last) ||
+      (D->first_beyond && !h->cs.first_beyond) || (D->n_beyond && !h->cs.n_beyond))
+    return fail(h, NPB_EINVAL, "npb_set_episode_record_stats: a record-side column for a statistic the handle does not keep (its table in npb_set_column_stats is NULL)");
+  NPB_USE_DEVICE(h);
+  if (!h->ers_dev) {
+    hipError_t e = hipMalloc((void **)&h->ers_dev, sizeof(npb_record_stats_t));
+    if (e != hipSuccess) { h->ers_dev = nullptr; return fail(h, NPB_ENOMEM, "npb_set_episode_record_stats: hipMalloc of the device copy failed", e); }
+  }
+  const npb_record_stats_t host = {h->cs, *D};
+  NPB_HIP(h, hipMemcpy(h->ers_dev, &host, sizeof host, hipMemcpyHostToDevice));      /* (synchronous: a records kernel in flight has finished) */
+  h->ers = *D; h->ers_on = true;
   return NPB_OK;
 }
 

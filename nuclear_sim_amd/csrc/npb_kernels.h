@@ -40,6 +40,19 @@ typedef struct { int32_t *len; double *ret; int32_t *index; int32_t *out_index; 
 /* one side row of a sampler (npb_sampler_create): watched plant p's value is element p * plant_stride of `row` (the source's base moved
  * to the row), of type NPB_SAMPLE_* */
 typedef struct { const void *row; int64_t plant_stride; int type; int pad_; } npb_sample_row_t;
+/* one column of npb_set_column_stats as the fold kernel reads it.  kind 0 / 1 / 2: an arena member (col, sub; 0 carried real, 1 output real
+ * stored as float, 2 int32); kind 3 + NPB_SAMPLE_*: a side row, plant p's value is element p * plant_stride of `row`.  direction / limit:
+ * the column's limit (0 = none) */
+typedef struct { const void *row; int64_t plant_stride; int col, sub, kind, direction; double limit; } npb_colstat_col_t;
+/* the handle's column statistics: the columns (device, n_cols of them; cols NULL = stats off) and the caller's tables as the descriptor
+ * names them, [n_cols][n_plants] each or NULL, n_samples [n_plants] */
+typedef struct {
+  const npb_colstat_col_t *cols; int n_cols;
+  double *min, *max, *sum, *sumsq, *last, *first_beyond; int32_t *n_beyond, *n_samples;
+} npb_column_stats_t;
+/* npb_set_episode_record_stats: what the records kernel needs of the statistics, kept in DEVICE memory by the handle and passed as one
+ * pointer (NULL = off), so that the kernel's argument block, and with it the kernel without statistics, stays what it was */
+typedef struct { npb_column_stats_t st; npb_episode_record_stats_desc_t rs; } npb_record_stats_t;
 typedef struct {
   int (*step)(const npb_params_t *P, int n_plants, size_t npad, void *arena, const int32_t *action,
               const double *magnitude, const double *setpoint, const double *noise_z, const double *cw_temp,
@@ -81,10 +94,14 @@ typedef struct {
                  const int32_t *ids_dev, int n_watched, double *out, hipStream_t stream);
   /* npb_set_episode_records: one record per episode that ends on this step, before the episode kernel does its bookkeeping.  C / start: the
    * handle's carried counters and bank entries (start NULL = no bank); step: npb_step calls since the records were switched on; summary: the
-   * handle's work-order summary while the records copy or clear it, else NULL */
+   * handle's work-order summary while the records copy or clear it, else NULL; record_stats: the handle's device copy of its column
+   * statistics and of the record-side columns that take them (npb_set_episode_record_stats), or NULL */
   void (*episode_records)(int n_plants, size_t npad, const void *arena, const uint8_t *done, const double *reward, const double *obs,
                           const uint32_t *trip_flags, npb_episode_counters_t C, const int32_t *start, int max_steps, int step,
-                          const npb_episode_records_desc_t *D, const npb_maint_summary_desc_t *summary, hipStream_t stream);
+                          const npb_episode_records_desc_t *D, const npb_maint_summary_desc_t *summary, const npb_record_stats_t *record_stats,
+                          hipStream_t stream);
+  /* npb_set_column_stats (npd_column_stats.h): one sample of every column of every plant folded into the tables, one launch */
+  void (*column_stats_fold)(const void *arena, size_t npad, const npb_column_stats_t *S, int n_plants, hipStream_t stream);
 } npb_launchers_t;
 extern npb_launchers_t npb_launch_table, npb32_launch_table;
 /* the same for either storage type */
@@ -109,6 +126,8 @@ void npb_launch_diag_carried_put(double *live, size_t live_pitch, const uint8_t 
  * the plants of mask (NULL = all) back to +inf and 0 */
 void npb_launch_maint_summary_fold(const npb_maint_summary_desc_t *D, npd_maint_log_t log, uint32_t *ticket, int n_plants, hipStream_t stream);
 void npb_launch_maint_summary_clear(const npb_maint_summary_desc_t *D, const uint8_t *mask, int n_plants, hipStream_t stream);
+/* npb_column_stats_clear (npd_column_stats.h): the cells of the plants of mask (NULL = all) back to the empty values in every table kept */
+void npb_launch_column_stats_clear(const npb_column_stats_t *S, const uint8_t *mask, int n_plants, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

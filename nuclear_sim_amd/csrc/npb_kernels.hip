@@ -1602,13 +1602,15 @@ static void NPB_LAUNCHER(sample)(const void *arena, size_t npad, const int *plan
                                  const int32_t *ids_dev, int n_watched, double *out, hipStream_t stream);     /* behind every other kernel, at the end of the file */
 static void NPB_LAUNCHER(episode_records)(int n_plants, size_t npad, const void *arena, const uint8_t *done, const double *reward, const double *obs,
                                           const uint32_t *trip_flags, npb_episode_counters_t C, const int32_t *start, int max_steps, int step,
-                                          const npb_episode_records_desc_t *D, const npb_maint_summary_desc_t *summary, hipStream_t stream);     /* the same */
+                                          const npb_episode_records_desc_t *D, const npb_maint_summary_desc_t *summary, const npb_record_stats_t *record_stats,
+                                          hipStream_t stream);     /* the same */
+static void NPB_LAUNCHER(column_stats_fold)(const void *arena, size_t npad, const npb_column_stats_t *S, int n_plants, hipStream_t stream);     /* the same */
 /* not const: clang emits a namespace-scope const into the device code too, where these host functions do not exist */
 extern "C" npb_launchers_t NPB_LAUNCHER(table) = {
   NPB_LAUNCHER(step), NPB_LAUNCHER(maint), NPB_LAUNCHER(observe), NPB_LAUNCHER(init), NPB_LAUNCHER(reset),
   NPB_LAUNCHER(field_get), NPB_LAUNCHER(field_set), NPB_LAUNCHER(gather), NPB_LAUNCHER(restore), NPB_LAUNCHER(episode),
   NPB_LAUNCHER(operator_maint), NPB_LAUNCHER(operator_component_maint), NPB_LAUNCHER(operator_turbine_maint), NPB_LAUNCHER(maint_all),
-  NPB_LAUNCHER(sample), NPB_LAUNCHER(episode_records),
+  NPB_LAUNCHER(sample), NPB_LAUNCHER(episode_records), NPB_LAUNCHER(column_stats_fold),
 };
 #ifndef NPB_BUILD_F32
 /* npb_reset / npb_reset_reference / npb_restore: the episode counters (len, ret) and the carried start entries (start: -1, not from
@@ -1717,6 +1719,8 @@ struct npd_episode_records_t {
   int n_keys;
   int max_steps;                                              /* 0 = no limit */
   int step;                                                   /* npb_step calls since the records were switched on */
+  const npb_record_stats_t *stats;                            /* device: the handle's column statistics and the record-side columns that take them
+                                                               * (npb_set_episode_record_stats), read by ended lanes only; NULL = not taken */
 };
 __global__ __launch_bounds__(NPB_WAVE) void npb_episode_records_kernel(int n_plants, size_t N, const npd_real_t *__restrict__ f64, const uint8_t *__restrict__ done,
                                                                        const double *__restrict__ reward, const double *__restrict__ obs,
@@ -1763,9 +1767,9 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_episode_records_kernel(int n_pla
       if (((rows >> r) & 1u) && slot_r < cap) R.D.final_obs[(size_t)slot_r * NPB_OBS_DIM + c] = obs[block_base * NPB_OBS_DIM + idx];
     }
   }
-  if (!ended || !R.s_first_created) return;
+  if (!ended) return;
   const bool copy = store && R.D.first_created;
-  for (int j = 0; j < R.n_keys; j++) {  /* the plant's summary cells as of this step (the fold ran before this launch), then "never" and 0 again */
+  for (int j = 0; R.s_first_created && j < R.n_keys; j++) {  /* the plant's summary cells as of this step (the fold ran before this launch), then "never" and 0 again */
     const size_t cell = (size_t)j * (size_t)n_plants + p;
     if (copy) {
       const size_t out = (size_t)j * (size_t)cap + slot;
@@ -1781,12 +1785,35 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_episode_records_kernel(int n_pla
       R.s_n_completed[cell] = 0;
     }
   }
+  if (!R.stats) return;
+  /* the plant's column statistics as of this step (their fold ran before this launch), then the empty values again (npd_column_stats.h) */
+  const npb_column_stats_t st = R.stats->st;
+  const npb_episode_record_stats_desc_t rs = R.stats->rs;
+  if (store && rs.n_samples) rs.n_samples[slot] = st.n_samples[p];
+  if (rs.clear) st.n_samples[p] = 0;
+#define NPD_RECORD_STAT(name, empty) \
+    if (store && rs.name) rs.name[(size_t)c * (size_t)cap + slot] = st.name[cell]; \
+    if (rs.clear && st.name) st.name[cell] = (empty);
+  for (int c = 0; c < st.n_cols; c++) {
+    const size_t cell = (size_t)c * (size_t)n_plants + p;
+    NPD_RECORD_STAT(min, __longlong_as_double(0x7ff0000000000000ll))
+    NPD_RECORD_STAT(max, __longlong_as_double((long long)0xfff0000000000000ull))
+    NPD_RECORD_STAT(sum, 0.0)
+    NPD_RECORD_STAT(sumsq, 0.0)
+    NPD_RECORD_STAT(last, __longlong_as_double(0x7ff8000000000000ll))
+    NPD_RECORD_STAT(first_beyond, __longlong_as_double(0x7ff0000000000000ll))
+    NPD_RECORD_STAT(n_beyond, 0)
+  }
+#undef NPD_RECORD_STAT
 }
-/* C: the handle's carried counters; start: its carried bank entries or NULL; summary: the handle's summary while the records copy or clear it, else NULL */
+/* C: the handle's carried counters; start: its carried bank entries or NULL; summary: the handle's summary while the records copy or clear it, else NULL;
+ * record_stats: the handle's device copy of its column statistics and the record-side columns that take them, or NULL */
 static void NPB_LAUNCHER(episode_records)(int n_plants, size_t npad, const void *arena, const uint8_t *done, const double *reward, const double *obs,
                                           const uint32_t *trip_flags, npb_episode_counters_t C, const int32_t *start, int max_steps, int step,
-                                          const npb_episode_records_desc_t *D, const npb_maint_summary_desc_t *summary, hipStream_t stream) {
+                                          const npb_episode_records_desc_t *D, const npb_maint_summary_desc_t *summary, const npb_record_stats_t *record_stats,
+                                          hipStream_t stream) {
   npd_episode_records_t R;
+  R.stats = record_stats;
   R.D = *D; R.len = C.len; R.ret = C.ret; R.index = C.index; R.start = start; R.max_steps = max_steps; R.step = step;
   R.s_first_created = summary ? summary->first_created : nullptr; R.s_first_completed = summary ? summary->first_completed : nullptr;
   R.s_n_created = summary ? summary->n_created : nullptr; R.s_n_completed = summary ? summary->n_completed : nullptr;
@@ -1794,3 +1821,6 @@ static void NPB_LAUNCHER(episode_records)(int n_plants, size_t npad, const void 
   hipLaunchKernelGGL(npb_episode_records_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, n_plants, npad,
                      (const npd_real_t *)arena, done, reward, obs, trip_flags, R);
 }
+
+/* the per-plant column statistics (npb_set_column_stats): the fold kernel, the clear kernel and their launchers */
+#include "npd_column_stats.h"

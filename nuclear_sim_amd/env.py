@@ -371,6 +371,16 @@ class BatchedPlantEnv:
     ``episode_records()`` drains them, sorted by (step, plant), whenever the caller chooses; ``write_episode_records(path)`` writes the
     table.  ``nuclear_sim_amd.timing.banked_trigger_times`` streams M scenarios through fewer lanes on it.  Output only; an episode
     the caller abandons (``restore``, ``restore_from_bank``, ``reset``) leaves no record.  Off by default: nothing changes.
+
+    Column statistics (``enable_column_stats(columns, limits)``): what a plant's state did over a run or an episode, as a handful of
+    numbers per (column, plant) instead of a time series -- min, max, sum and sum of squares (``colstats.moments``: mean and variance),
+    the last value, and for a column with a limit the plant clock when it first went beyond it and how many samples were beyond.  A
+    column is a state member, an info column, an obs column or the reward; one more launch behind every step folds the end-of-step
+    sample of every plant into the env's tables (npb_set_column_stats), which ``column_stats()`` returns without synchronising;
+    ``clear_column_stats(mask)`` starts the masked plants afresh and ``fold_column_stats()`` folds the current state once more on request.
+    ``nuclear_sim_amd.colstats.fold`` states the fold in numpy and the device gives its bits.  With episode records on, each record
+    carries the statistics of its own episode (``stat_min`` ...), and the tables restart with the episode.  Output only, like the
+    work-order summary.  Off by default: nothing changes.
     """
 
     action_space_size = 15       # NuclearPlantEnv sim.py:916
@@ -820,7 +830,8 @@ class BatchedPlantEnv:
         _lib.check(self.L.npb_maint_summary_fold(self._h, self._stream()), self._h)
 
     def enable_episode_records(self, capacity: Optional[int] = None, final_obs: bool = False, summary: Optional[bool] = None,
-                               clear_summary: Optional[bool] = None, *, off: bool = False) -> None:
+                               clear_summary: Optional[bool] = None, *, off: bool = False, stats: Optional[bool] = None,
+                               clear_stats: Optional[bool] = None) -> None:
         """Have the device keep a log of FINISHED episodes (npb_set_episode_records): behind every step, one record per plant whose episode
         ended on it -- plant, episode index, bank entry it started from, length, return, terminated / truncated, the step's trip flags, the
         step number, the plant clock, with ``final_obs`` the terminal observation and with ``summary`` that episode's rows of the work-order
@@ -828,8 +839,12 @@ class BatchedPlantEnv:
         (None = ``max(4 * n, 4096)``); episodes past them are counted, not written, until the next drain.  ``summary`` and
         ``clear_summary`` default to whether a maintenance summary is enabled; ``clear_summary`` puts an ended plant's summary rows back to
         "never" / 0 on the device, so that every record holds the work orders of its own episode (off, the summary goes on counting across
-        restarts, as it does without records).  ``off=True`` turns the records off and releases the buffers.  An episode the caller
-        abandons (``restore``, ``restore_from_bank``, ``reset``) starts the next index and leaves no record."""
+        restarts, as it does without records).  ``stats`` and ``clear_stats`` default to whether column statistics are enabled
+        (``enable_column_stats``): with ``stats`` every record carries the plant's cells of each table kept as of the terminal step
+        (``stat_min`` ... [m, n_cols] and ``stat_n_samples``), and ``clear_stats`` puts an ended plant's cells back to the empty values,
+        so that each record holds the statistics of its own episode and ``stat_n_samples == length``.  ``off=True`` turns the records off
+        and releases the buffers.  An episode the caller abandons (``restore``, ``restore_from_bank``, ``reset``) starts the next index
+        and leaves no record."""
         if off:
             if getattr(self, "_erec", None) is not None:
                 _lib.check(self.L.npb_set_episode_records(self._h, None), self._h)
@@ -844,6 +859,11 @@ class BatchedPlantEnv:
         clear_summary = has_summary if clear_summary is None else bool(clear_summary)
         if (summary or clear_summary) and not has_summary:
             raise ValueError("episode records with summary / clear_summary need enable_maintenance_summary() first")
+        cst = getattr(self, "_cstats", None)
+        stats = (cst is not None) if stats is None else bool(stats)
+        clear_stats = (cst is not None) if clear_stats is None else bool(clear_stats)
+        if (stats or clear_stats) and cst is None:
+            raise ValueError("episode records with stats / clear_stats need enable_column_stats() first")
         cap = max(4 * self.n, 4096) if capacity is None else int(capacity)
         if cap < 1:
             raise ValueError("capacity must be >= 1")
@@ -852,10 +872,10 @@ class BatchedPlantEnv:
         d.capacity, d.clear_summary = cap, int(clear_summary)
         dev, host = {}, {}
 
-        def column(name, shape, dtype):
+        def column(name, shape, dtype, desc=d, member=None):
             dev[name] = torch.zeros(shape, dtype=dtype, device=self.device)
             host[name] = torch.empty(shape, dtype=dtype, pin_memory=True)      # the drain's landing place, as the maintenance log's
-            setattr(d, name, dev[name].data_ptr())
+            setattr(desc, member or name, dev[name].data_ptr())
         with torch.cuda.device(self.device):
             for name, np_type in _lib.EPISODE_RECORD_COLUMNS:      # (uint32 trip flags travel as int32 bits)
                 column(name, (cap,), torch.float64 if np_type is np.float64 else torch.int32)
@@ -867,10 +887,29 @@ class BatchedPlantEnv:
                 for name in ("n_created", "n_completed"):
                     column(name, (n_keys, cap), torch.int32)
             cursor = torch.zeros(1, dtype=torch.int32, device=self.device)     # a uint32 on the device
+            rs = None
+            if stats or clear_stats:      # the record-side columns of the statistics, as "stat_<name>"
+                rs = _lib.NpbEpisodeRecordStatsDesc()
+                rs.clear = int(clear_stats)
+                if stats:
+                    for name in cst["stats"] + ("n_samples",):
+                        int_table = name in ("n_beyond", "n_samples")
+                        column("stat_" + name, (cap,) if name == "n_samples" else (len(cst["order"]), cap), torch.int32 if int_table else torch.float64,
+                               desc=rs, member=name)
         d.cursor = cursor.data_ptr()
         _lib.check(self.L.npb_set_episode_records(self._h, ctypes.byref(d)), self._h)
+        self._erec = None      # (new record columns: the handle has dropped the statistics columns of the old ones with them)
+        if rs is None:
+            if hasattr(self.L, "npb_set_episode_record_stats"):
+                _lib.check(self.L.npb_set_episode_record_stats(self._h, None), self._h)
+        else:
+            try:
+                _lib.check(self.L.npb_set_episode_record_stats(self._h, ctypes.byref(rs)), self._h)
+            except _lib.NpbError:
+                self.L.npb_set_episode_records(self._h, None)
+                raise
         self._erec = {"desc": d, "dev": dev, "host": host, "cursor": cursor, "host_cursor": torch.empty(1, dtype=torch.int32, pin_memory=True),
-                      "capacity": cap, "n_keys": n_keys}
+                      "capacity": cap, "n_keys": n_keys, "stats": rs, "stat_order": list(cst["order"]) if stats else None}
 
     def disable_episode_records(self) -> None:
         """episode records off; the buffers are released"""
@@ -881,7 +920,8 @@ class BatchedPlantEnv:
         ``start`` (-1 = not from the bank), ``length``, ``flags``, ``terminated`` / ``truncated`` (bool), ``trip_flags`` (uint32), ``step``
         (steps since the records were enabled, 0 = the first), ``ret``, ``end_time`` (plant minutes); with ``final_obs``
         ``final_observation`` [m, 22]; with ``summary`` ``first_created`` / ``first_completed`` (float64, +inf = never) and ``n_created`` /
-        ``n_completed`` (int32), [m, n_keys].  An overflowed log raises, naming how many episodes were dropped, and is left as it is,
+        ``n_completed`` (int32), [m, n_keys]; with ``stats`` ``stat_min`` ... (the tables ``enable_column_stats`` keeps) [m, n_cols] and
+        ``stat_n_samples``.  An overflowed log raises, naming how many episodes were dropped, and is left as it is,
         unless ``allow_overflow`` (which of one step's episodes fitted is then not defined)."""
         er = getattr(self, "_erec", None)
         if er is None:
@@ -917,11 +957,16 @@ class BatchedPlantEnv:
         for name in ("first_created", "first_completed", "n_created", "n_completed"):
             if name in raw:
                 out[name] = np.ascontiguousarray(raw[name][order])
+        for name in raw:      # the episode's column statistics, [m, n_cols] in the caller's column order
+            if name.startswith("stat_"):
+                a = raw[name][order]
+                out[name] = np.ascontiguousarray(a if a.ndim == 1 else a[:, er["stat_order"]])
         return out
 
     def write_episode_records(self, path: str, clear: bool = True, allow_overflow: bool = False) -> None:
         """Drain the episode records into a CSV (``.csv``) or Parquet file: one row per episode; the terminal observation as
-        ``final_observation_0`` .. ``_21`` and the summary tables as ``first_created_0`` .. per key"""
+        ``final_observation_0`` .. ``_21``, the summary tables as ``first_created_0`` .. per key and the column statistics as
+        ``stat_min_0`` .. per column"""
         from . import maintlog
         cols = {}
         for name, a in self.episode_records(clear=clear, allow_overflow=allow_overflow).items():
@@ -930,6 +975,75 @@ class BatchedPlantEnv:
             else:
                 cols.update({"%s_%d" % (name, j): np.ascontiguousarray(a[:, j]) for j in range(a.shape[1])})
         maintlog.write(cols, path)
+
+    def enable_column_stats(self, columns, limits=None, stats=("min", "max", "sum", "sumsq", "last")) -> None:
+        """Have the device fold per-plant statistics of ``columns`` behind every step (npb_set_column_stats): one more launch, a thread per
+        (column, plant), the sample being the end-of-step state of the episode the step belonged to, before any restore.  ``columns``: up
+        to 32, each a state member as ``set_fields`` keys it (``name``, ``(name, instance)`` or ``(name, instance, k)``), ``("info",
+        column_name)``, ``("obs", i)`` or ``"reward"``.  ``limits``: ``{column_index: (">" | "<", value)}``; ``stats``: the tables to keep,
+        of "min", "max", "sum", "sumsq", "last" and, for columns with a limit, "first_beyond" (the plant clock after the first step whose
+        sample was beyond the limit, +inf = never) and "n_beyond" (samples beyond it).  ``nuclear_sim_amd.colstats.fold`` is the same in
+        numpy, bit for bit.  ``None`` for ``columns`` turns it off.  Output only, like the maintenance summary: ``snapshot``, ``restore``,
+        the resets, the autoreset and the start bank leave the tables alone; ``clear_column_stats(mask)`` starts the masked plants afresh,
+        and episode records enabled afterwards do so for every episode that ends (``enable_episode_records(stats=..., clear_stats=...)``)."""
+        er = getattr(self, "_erec", None)
+        if er is not None and er.get("stats") is not None:
+            raise _lib.NpbError("episode records that copy or clear the column statistics are on: disable_episode_records() first")
+        if columns is None:
+            if getattr(self, "_cstats", None) is not None:
+                _lib.check(self.L.npb_set_column_stats(self._h, None), self._h)
+            self._cstats = None
+            return
+        req = _lib.column_stats_request(columns, limits, stats, INFO_COLUMNS)      # an unknown name, index or statistic is refused here
+        if not hasattr(self.L, "npb_set_column_stats"):
+            raise _lib.NpbError("libnpb.so has no npb_set_column_stats: rebuild")
+        nm, ns = len(req["members"]), len(req["sides"])
+        n_cols = nm + ns
+        d = _lib.NpbColumnStatsDesc()
+        kinds = (ctypes.c_int * max(nm, 1))(*[m[0] for m in req["members"]])
+        slots = (ctypes.c_int * max(nm, 1))(*[m[1] for m in req["members"]])
+        side = (_lib.NpbSampleSource * max(ns, 1))()
+        buffers = {"info": self._info_buf, "obs": self._obs, "reward": self._reward}
+        for k, (name, offset, stride) in enumerate(req["sides"]):
+            side[k].base = buffers[name].data_ptr() + 8 * offset; side[k].type = _lib.SAMPLE_TYPES["f64"]; side[k].rows = 1
+            side[k].row_stride = 0; side[k].plant_stride = stride
+        direction, limit = (ctypes.c_int * n_cols)(*req["direction"]), (ctypes.c_double * n_cols)(*req["limit"])
+        d.n_fields, d.kinds, d.slots, d.n_sources, d.sources, d.direction, d.limit = nm, kinds, slots, ns, side, direction, limit
+        from . import colstats
+        tables = {}
+        with torch.cuda.device(self.device):
+            for name in req["stats"]:
+                tables[name] = torch.full((n_cols, self.n), colstats.EMPTY[name], dtype=torch.int32 if name == "n_beyond" else torch.float64,
+                                          device=self.device)
+                setattr(d, name, tables[name].data_ptr())
+            tables["n_samples"] = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        d.n_samples = tables["n_samples"].data_ptr()
+        _lib.check(self.L.npb_set_column_stats(self._h, ctypes.byref(d)), self._h)
+        self._cstats = {"tables": tables, "stats": req["stats"], "order": req["order"], "columns": list(columns)}
+
+    def column_stats(self) -> Dict[str, torch.Tensor]:
+        """The statistics' tables, [n_cols, n] each in the order of ``columns``, and ``n_samples`` [n], on the device, never synchronised
+        here.  Where ``columns`` lists every state member ahead of every info / obs / reward column -- the order the device keeps them in
+        -- these are the env's own buffers, as ``maintenance_summary()``'s are: current after every later ``step`` too.  For a request in
+        any other order the tables are an indexed COPY made now, in stream order: it does not follow later steps; call again."""
+        cs = getattr(self, "_cstats", None)
+        if cs is None:
+            raise _lib.NpbError("no column statistics: enable_column_stats() first")
+        identity = cs["order"] == list(range(len(cs["order"])))
+        return {name: t if (identity or t.dim() == 1) else t[cs["order"]] for name, t in cs["tables"].items()}
+
+    def clear_column_stats(self, mask=None) -> None:
+        """the cells of the masked plants (None = all) back to the empty values in every table (npb_column_stats_clear)"""
+        if getattr(self, "_cstats", None) is None:
+            raise _lib.NpbError("no column statistics: enable_column_stats() first")
+        m = None if mask is None else self._col(mask, torch.uint8)
+        _lib.check(self.L.npb_column_stats_clear(self._h, None if m is None else self._p(m), self._stream()), self._h)
+
+    def fold_column_stats(self) -> None:
+        """fold one sample of the current state now (npb_column_stats_fold); ``step`` does it itself"""
+        if getattr(self, "_cstats", None) is None:
+            raise _lib.NpbError("no column statistics: enable_column_stats() first")
+        _lib.check(self.L.npb_column_stats_fold(self._h, self._stream()), self._h)
 
     def _order_buffers(self):
         """the buffers the perform_*_maintenance methods keep for their order columns, with the ``success`` column they all return"""
@@ -1220,6 +1334,7 @@ class BatchedPlantEnv:
             self.L.npb_destroy(self._h)
             self._h = ctypes.c_void_p()
         self._erec = None      # the episode records' buffers go with the handle
+        self._cstats = None
 
     def __del__(self):
         try:
