@@ -783,6 +783,77 @@ typedef struct npb_episode_record_stats_desc_t {
 } npb_episode_record_stats_desc_t;
 NPB_API int npb_set_episode_record_stats(NpbHandle *h, const npb_episode_record_stats_desc_t *desc);
 
+/* Event windows: what a plant looked like AROUND a trip, a work order or a limit being crossed, without logging every plant and without
+ * choosing the plants beforehand -- a trigger, as an oscilloscope has one.  Every plant keeps the last H = pre + 1 + post samples of up to
+ * NPB_EVENT_WINDOW_COLS_MAX columns (and its clock, prim.sim_time) in a ring the handle owns; a trigger arms a capture, and `post` steps
+ * later the window -- `pre` samples before the trigger, the trigger sample, `post` after -- goes into a record of the caller's, drained
+ * whenever the caller chooses.  The volume of output follows the events, not plants x steps.
+ * Recorded columns: n_fields / kinds / slots and n_sources / sources exactly as npb_column_stats_desc_t takes them (members first, then the
+ * one-row side sources), widened to double as npb_sample_kernel widens them; n_cols = n_fields + n_sources.
+ * Triggers: 1 .. NPB_EVENT_WINDOW_TRIGGERS_MAX, each a column of its own (an arena member, or a side source; it need not be recorded) and
+ * a mode, comparing the sample v with the previous sample prev of the same plant:
+ *   NPB_TRIGGER_BITS_RISE(mask)             integer column (an int32 member, an I32 or U8 source): (v & mask) & ~(prev & mask) != 0
+ *   NPB_TRIGGER_INCREASE                    v > prev; a NaN on either side does not fire
+ *   NPB_TRIGGER_BEYOND(direction, limit)    the edge only: beyond now (+1: v > limit, -1: v < limit, the statistics' rule) and not beyond at
+ *                                           the previous sample
+ * With windows set npb_step launches ONE more kernel on its stream, one wave per 64 plants: behind the column-statistics fold and BEFORE
+ * the episode-records kernel and the episode kernel -- the sample is the end-of-step state of the episode the step belonged to, and the
+ * work-order summary already holds this step's events.  For plant p at sample s (0 = the first npb_step after the set):
+ *   1. where the handle carries an episode index (npb_set_autoreset) and it differs from the one last seen, the plant was restarted since
+ *      the last sample (autoreset, npb_restore*, npb_reset*): its ring is empty, it is unprimed, and an armed capture is dropped without a
+ *      record.  Without an episode index npb_event_windows_clear(mask) does the same on request (mask: device uint8 [n_plants], NULL = all).
+ *   2. ring row s % H takes the recorded columns and the clock; valid = min(valid + 1, H).
+ *   3. every trigger is evaluated against prev, then prev = v.  The first sample of an unprimed plant only primes: it never fires.
+ *   4. idle and a trigger fired: armed, due = s + post, n_pre = min(pre, valid - 1), and the lowest trigger that fired, the fired set, s
+ *      and the clock are kept.  Armed already and a trigger fires: retriggers += 1, nothing else.
+ *   5. the capture is taken when s == due; and, with flags bit 0 set and n_post = s - trigger step, when the plant is armed and its episode
+ *      ends on this step by the episode kernel's rule (done, or carried length + 1 >= max_episode_steps; autoreset on).  The plant is idle again.
+ * Record r (slots are handed out like the episode records': cursor counts every capture, those at or past `capacity` are dropped and
+ * counted): plant, episode (the carried index, 0 without one), trigger, step (the trigger's sample number), n_pre, n_post, flags,
+ * retriggers int32; fired uint32; time double (prim.sim_time as npb_get_field returns it, at the trigger sample); times double [H] and
+ * values double [H][n_cols]: row k is sample step + k - pre, so the trigger sample is row `pre`; rows outside [pre - n_pre, pre + n_post]
+ * are NaN in both.  nuclear_sim_amd/eventwin.py states all of this in numpy; the device produces its bits.
+ * npb_set_event_windows(h, desc): desc = NULL turns the windows off and frees what the handle allocated (npb_event_windows_bytes: the ring
+ * double [H][n_cols + 1][n_plants], prev double [n_triggers][n_plants], and nine 4- or 8-byte words per plant -- the primed flag is
+ * valid > 0).  A failed allocation is NPB_EHIP with the byte count in the message, and what was set before stays.  NPB_EINVAL with the
+ * reason in npb_last_error, before any device work, for what npb_event_windows_check refuses -- that check alone, without a handle, NULL =
+ * accepted, else the reason: counts outside their ranges (columns, triggers, pre, post, H <= NPB_EVENT_WINDOW_ROWS_MAX, capacity >= 1); a
+ * bad kind or slot; a side source with a NULL base, an unknown type or rows != 1; BITS_RISE on a real-valued column or with mask 0; an
+ * unknown mode; a NaN limit or a direction outside {-1, +1} for BEYOND; a NULL or misaligned record column or cursor (doubles 8-byte, the
+ * others 4-byte).  has_autoreset is taken for symmetry with npb_episode_records_check and refuses nothing.
+ * Output only: npb_snapshot / npb_restore, the start bank and checkpoints neither read nor write it.  NPB_VERSION stays 154: a binding
+ * detects the entry points by name.  A handle that never calls this behaves as before in every entry point. */
+#define NPB_EVENT_WINDOW_COLS_MAX 16
+#define NPB_EVENT_WINDOW_TRIGGERS_MAX 8
+#define NPB_EVENT_WINDOW_ROWS_MAX 1024
+enum { NPB_TRIGGER_MODE_BITS_RISE = 0, NPB_TRIGGER_MODE_INCREASE = 1, NPB_TRIGGER_MODE_BEYOND = 2 };
+/* the last four members of an npb_event_trigger_t initialiser */
+#define NPB_TRIGGER_BITS_RISE(mask) NPB_TRIGGER_MODE_BITS_RISE, (uint32_t)(mask), 0, 0.0
+#define NPB_TRIGGER_INCREASE NPB_TRIGGER_MODE_INCREASE, 0u, 0, 0.0
+#define NPB_TRIGGER_BEYOND(direction, limit) NPB_TRIGGER_MODE_BEYOND, 0u, (direction), (limit)
+typedef struct npb_event_trigger_t {
+  int from_source;               /* 0: the arena member (kind, slot); != 0: `source`, one value per plant */
+  int kind, slot;
+  npb_sample_source_t source;
+  int mode; uint32_t mask; int direction; double limit;
+} npb_event_trigger_t;
+typedef struct npb_event_windows_desc_t {
+  int n_fields; const int *kinds; const int *slots;      /* host; arena members, n_fields may be 0 */
+  int n_sources; const npb_sample_source_t *sources;     /* host descriptors of one-row device buffers; n_sources may be 0 */
+  int n_triggers; const npb_event_trigger_t *triggers;   /* host */
+  int pre, post, capacity;
+  int32_t *plant, *episode, *trigger, *step, *n_pre, *n_post, *flags, *retriggers;      /* device [capacity] */
+  uint32_t *fired;                                       /* device [capacity] */
+  double *time;                                          /* device [capacity] */
+  double *times;                                         /* device [capacity][H] */
+  double *values;                                        /* device [capacity][H][n_cols] */
+  uint32_t *cursor;                                      /* device, one word: captures so far */
+} npb_event_windows_desc_t;
+NPB_API int npb_set_event_windows(NpbHandle *h, const npb_event_windows_desc_t *desc);
+NPB_API const char *npb_event_windows_check(const npb_event_windows_desc_t *desc, int n_plants, int has_autoreset);
+NPB_API int npb_event_windows_clear(NpbHandle *h, const uint8_t *mask, void *stream);
+NPB_API size_t npb_event_windows_bytes(const npb_event_windows_desc_t *desc, int n_plants);
+
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the
  * rocprofv3 FETCH_SIZE / WRITE_SIZE counters (tools/profile_traffic.py). */

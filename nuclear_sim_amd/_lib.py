@@ -486,6 +486,92 @@ def column_stats_request(columns, limits=None, stats=("min", "max", "sum", "sums
             "stats": tuple(name for name in COLUMN_STATS if name in stats)}
 
 
+# include/npb.h npb_event_windows_desc_t: state windows around events, captured on the device (npb_set_event_windows)
+EVENT_WINDOW_COLS_MAX, EVENT_WINDOW_TRIGGERS_MAX, EVENT_WINDOW_ROWS_MAX = 16, 8, 1024
+TRIGGER_MODES = {"bits_rise": 0, "increase": 1, "beyond": 2}      # NPB_TRIGGER_MODE_*
+EVENT_WINDOW_WORDS = ("plant", "episode", "trigger", "step", "n_pre", "n_post", "flags", "retriggers")      # the int32 record columns (eventwin.WORD_COLUMNS)
+
+
+class NpbEventTrigger(ctypes.Structure):
+    """npb_event_trigger_t: the trigger's column (an arena member, or a one-row side source) and its mode"""
+    _fields_ = [("from_source", ctypes.c_int), ("kind", ctypes.c_int), ("slot", ctypes.c_int), ("source", NpbSampleSource),
+                ("mode", ctypes.c_int), ("mask", ctypes.c_uint32), ("direction", ctypes.c_int), ("limit", ctypes.c_double)]
+
+
+class NpbEventWindowsDesc(ctypes.Structure):
+    """npb_event_windows_desc_t: recorded columns and triggers (host arrays), the window shape, and the caller's device record columns"""
+    _fields_ = [("n_fields", ctypes.c_int), ("kinds", ctypes.POINTER(ctypes.c_int)), ("slots", ctypes.POINTER(ctypes.c_int)),
+                ("n_sources", ctypes.c_int), ("sources", ctypes.POINTER(NpbSampleSource)),
+                ("n_triggers", ctypes.c_int), ("triggers", ctypes.POINTER(NpbEventTrigger)),
+                ("pre", ctypes.c_int), ("post", ctypes.c_int), ("capacity", ctypes.c_int)] + \
+               [(name, ctypes.c_void_p) for name in EVENT_WINDOW_WORDS + ("fired", "time", "times", "values", "cursor")]
+
+
+def event_windows_request(columns, triggers, pre, post, info_columns=None, summary_keys: int = 0) -> dict:
+    """What ``BatchedPlantEnv.enable_event_windows`` asks of npb_set_event_windows, from the caller's words; a pure function, host only, so
+    an unknown name or a trigger that cannot work is refused (ValueError) before any device work.  ``columns`` as ``column_stats_request``
+    takes them, 1 to 16.  ``triggers``: 1 to 8, each ``("trip", mask)`` (rising bits of the step's trip flags), ``("done",)``,
+    ``("work_order", key_index)`` / ``("completed", key_index)`` (the summary's n_created / n_completed row of that key goes up: needs
+    ``summary_keys`` > key_index, the keys of ``enable_maintenance_summary``), ``("maintenance",)`` (the event count goes up) or
+    ``(column, ">" | "<", value)`` (the edge of a limit on any column).
+    Returns {"members", "sides", "order": as ``column_stats_request``; "triggers": per trigger {"member": (kind, slot) or None, "side":
+    (buffer, element offset, plant stride, element type) or None, "mode": "bits_rise" | "increase" | "beyond", "mask", "direction",
+    "limit"} with the side buffers "info" | "obs" | "reward" | "flags" | "done" | "n_created" | "n_completed" (for the last two the
+    offset is the key's row); "numpy": the triggers as ``eventwin.record`` takes them; "pre", "post"}."""
+    columns = list(columns)
+    if not 1 <= len(columns) <= EVENT_WINDOW_COLS_MAX:
+        raise ValueError("event windows take 1 to %d columns, not %d" % (EVENT_WINDOW_COLS_MAX, len(columns)))
+    req = column_stats_request(columns, None, ("last",), info_columns)
+    triggers = list(triggers)
+    if not 1 <= len(triggers) <= EVENT_WINDOW_TRIGGERS_MAX:
+        raise ValueError("event windows take 1 to %d triggers, not %d" % (EVENT_WINDOW_TRIGGERS_MAX, len(triggers)))
+    pre, post = int(pre), int(post)
+    if pre < 0 or post < 0 or pre + 1 + post > EVENT_WINDOW_ROWS_MAX:
+        raise ValueError("event windows need pre >= 0, post >= 0 and pre + 1 + post <= %d" % EVENT_WINDOW_ROWS_MAX)
+    out, as_numpy = [], []
+    for t in triggers:
+        t = (t,) if isinstance(t, str) else tuple(t)
+        T = {"member": None, "side": None, "mode": "increase", "mask": 0, "direction": 0, "limit": 0.0}
+        if len(t) == 2 and t[0] == "trip":
+            mask = int(t[1])
+            if not 0 < mask <= 0xFFFFFFFF:
+                raise ValueError("the ('trip', mask) trigger needs 0 < mask < 2**32, not %r" % (t[1],))
+            T.update(side=("flags", 0, 1, "i32"), mode="bits_rise", mask=mask)
+            as_numpy.append(("bits", mask))
+        elif t == ("done",):
+            T.update(side=("done", 0, 1, "u8"), mode="bits_rise", mask=1)
+            as_numpy.append(("bits", 1))
+        elif len(t) == 2 and t[0] in ("work_order", "completed"):
+            k = t[1]
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+                raise ValueError("the %r trigger takes the index of a summary key, not %r" % (t[0], k))
+            if summary_keys < 1:
+                raise ValueError("the %r trigger reads the maintenance summary: enable_maintenance_summary() first" % (t[0],))
+            if not 0 <= k < summary_keys:
+                raise ValueError("the %r trigger: the summary's keys are 0 .. %d, not %d" % (t[0], summary_keys - 1, k))
+            T.update(side=("n_created" if t[0] == "work_order" else "n_completed", int(k), 1, "i32"))
+            as_numpy.append(("increase",))
+        elif t == ("maintenance",):
+            kind, slot = SCHEMA.slot("maint.maintenance_actions_performed")
+            T.update(member=(0 if kind == "f64" else 1, slot))
+            as_numpy.append(("increase",))
+        elif len(t) == 3 and t[1] in (">", "<"):
+            if np.isnan(float(t[2])):
+                raise ValueError("the limit of trigger %r is NaN" % (t,))
+            one = column_stats_request([t[0]], None, ("last",), info_columns)
+            if one["members"]:
+                T.update(member=one["members"][0])
+            else:
+                T.update(side=one["sides"][0] + ("f64",))
+            T.update(mode="beyond", direction=1 if t[1] == ">" else -1, limit=float(t[2]))
+            as_numpy.append((t[1], float(t[2])))
+        else:
+            raise ValueError("unknown trigger %r: ('trip', mask), ('done',), ('work_order', key_index), ('completed', key_index), "
+                             "('maintenance',) or (column, '>' | '<', value)" % (t,))
+        out.append(T)
+    return {"members": req["members"], "sides": req["sides"], "order": req["order"], "triggers": out, "numpy": as_numpy, "pre": pre, "post": post}
+
+
 def episode_streams_desc(block, bank_noise_seeds=None, bank_profile_seeds=None, outputs=(None, None, None)):
     """(desc, keep): an NpbEpisodeStreamsDesc and the host arrays it points into (host only, no library needed).  A table is a sequence of
     seeds, one per bank entry; both tables, where both are given, have the same length.  ``outputs``: three device addresses or None."""
@@ -669,6 +755,13 @@ def load():
         L.npb_column_stats_fold.argtypes = [vp, vp]
         L.npb_column_stats_clear.argtypes = [vp, vp, vp]
         L.npb_set_episode_record_stats.argtypes = [vp, ctypes.POINTER(NpbEpisodeRecordStatsDesc)]
+    if hasattr(L, "npb_set_event_windows"):     # state windows around events, captured behind every step
+        L.npb_set_event_windows.argtypes = [vp, ctypes.POINTER(NpbEventWindowsDesc)]
+        L.npb_event_windows_check.argtypes = [ctypes.POINTER(NpbEventWindowsDesc), ci, ci]
+        L.npb_event_windows_check.restype = ctypes.c_char_p
+        L.npb_event_windows_clear.argtypes = [vp, vp, vp]
+        L.npb_event_windows_bytes.argtypes = [ctypes.POINTER(NpbEventWindowsDesc), ci]
+        L.npb_event_windows_bytes.restype = ctypes.c_size_t
     if L.npb_num_f64() != SCHEMA.total_f64 or L.npb_num_i32() != SCHEMA.total_i32:
         raise NpbError("libnpb.so was built against a different include/npb_fields.h (%d/%d vs %d/%d): rebuild"
                        % (L.npb_num_f64(), L.npb_num_i32(), SCHEMA.total_f64, SCHEMA.total_i32))

@@ -75,6 +75,9 @@ struct NpbHandle {
    * the record-side columns that take them */
   npb_column_stats_t cs; bool ers_on; npb_episode_record_stats_desc_t ers;
   npb_record_stats_t *ers_dev;      /* what the records kernel reads of both (device, allocated on first use, uploaded by npb_set_episode_record_stats) */
+  /* npb_set_event_windows: the columns, triggers, ring and bookkeeping on the device (ew.cols = the one allocation of ew_bytes; NULL =
+   * off), the caller's record columns, and the npb_step calls since they were set */
+  npb_event_windows_t ew; size_t ew_bytes; int ew_step;
   double *ramp_prev;   /* npb_profile_ramp: the previous setpoint of every plant ([pitch], NaN = none yet), allocated on first use */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
   std::vector<int> plan_key;
@@ -456,6 +459,7 @@ int npb_destroy(NpbHandle *h) {
   if (h->es_mem) (void)hipFree(h->es_mem);
   if (h->cs.cols) (void)hipFree((void *)h->cs.cols);
   if (h->ers_dev) (void)hipFree(h->ers_dev);
+  if (h->ew.cols) (void)hipFree((void *)h->ew.cols);
   for (Sampler *sm : h->samplers) if (sm) { (void)hipFree(sm->dev); delete sm; }
   delete h;
   return NPB_OK;
@@ -1052,6 +1056,9 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
   if (maint) summary_fold(h, (hipStream_t)stream);      /* the rule has appended this step's records: the summary is current when the call returns */
   if (h->cs.cols)      /* the end-of-step state of the episode this step belonged to, before any restore */
     h->K->column_stats_fold(h->f64, NPB_N(h), &h->cs, h->n_plants, (hipStream_t)stream);
+  if (h->ew.cols)      /* the same sample into every plant's ring, the triggers, the windows that are due -- or cut short by an episode that ends here */
+    h->K->event_windows(h->f64, NPB_N(h), &h->ew, h->n_plants, h->ew_step++, h->ep_index, h->autoreset ? h->ep_len : nullptr, done,
+                        h->max_episode_steps, (hipStream_t)stream);
   if (h->er_on && h->autoreset)      /* the episodes that end on this step, recorded while everything still describes them; then their summary rows cleared */
     h->K->episode_records(h->n_plants, NPB_N(h), h->f64, done, reward, obs, trip_flags, counters_of(h), h->ep_start,
                           h->max_episode_steps, h->er_step++, &h->er, er_uses_summary(h) ? &h->summary : nullptr,
@@ -1464,6 +1471,144 @@ int npb_set_episode_records(NpbHandle *h, const npb_episode_records_desc_t *desc
   /* new record columns, perhaps of another capacity: the record-side statistics columns belonged to the old ones and are dropped with
    * them (npb_set_episode_record_stats again, behind this call, for the new ones) */
   h->er = *desc; h->er_step = 0; h->er_on = true; h->ers_on = false;
+  return NPB_OK;
+}
+
+/* ---- event windows (include/npb.h, npd_event_windows.h) */
+static const char *ew_source_refusal(const npb_sample_source_t &S) {
+  if (!S.base) return "npb_set_event_windows: a side source has a NULL base";
+  if (S.type < NPB_SAMPLE_F64 || S.type > NPB_SAMPLE_U8) return "npb_set_event_windows: a side source has an unknown element type";
+  if (S.rows != 1) return "npb_set_event_windows: a side source must have rows == 1 (one value per plant)";
+  if (S.plant_stride < 0) return "npb_set_event_windows: a side source needs a plant stride >= 0";
+  return nullptr;
+}
+const char *npb_event_windows_check(const npb_event_windows_desc_t *D, int n_plants, int has_autoreset) {
+  (void)has_autoreset;
+  if (!D) return nullptr;
+  if (n_plants < 1) return "npb_set_event_windows: n_plants must be >= 1";
+  if (D->n_fields < 0 || D->n_sources < 0 || (int64_t)D->n_fields + D->n_sources < 1 || (int64_t)D->n_fields + D->n_sources > NPB_EVENT_WINDOW_COLS_MAX)
+    return "npb_set_event_windows: the column count (n_fields + n_sources) must be 1 .. NPB_EVENT_WINDOW_COLS_MAX (16)";
+  if (D->n_triggers < 1 || D->n_triggers > NPB_EVENT_WINDOW_TRIGGERS_MAX || !D->triggers)
+    return "npb_set_event_windows: the trigger count must be 1 .. NPB_EVENT_WINDOW_TRIGGERS_MAX (8), with their descriptors";
+  if (D->pre < 0 || D->post < 0 || (int64_t)D->pre + 1 + D->post > NPB_EVENT_WINDOW_ROWS_MAX)
+    return "npb_set_event_windows: the window shape needs pre >= 0, post >= 0 and pre + 1 + post <= NPB_EVENT_WINDOW_ROWS_MAX (1024)";
+  if (D->capacity < 1) return "npb_set_event_windows: capacity must be >= 1";
+  if ((D->n_fields > 0 && (!D->kinds || !D->slots)) || (D->n_sources > 0 && !D->sources))
+    return "npb_set_event_windows: fields without kinds / slots, or side sources without their descriptors";
+  int col, sub, access;
+  for (int f = 0; f < D->n_fields; f++)
+    if ((D->kinds[f] != NPB_KIND_F64 && D->kinds[f] != NPB_KIND_I32) || !locate(NPB_STORAGE_F64, D->kinds[f], D->slots[f], &col, &sub, &access))
+      return "npb_set_event_windows: bad field kind or slot";
+  for (int k = 0; k < D->n_sources; k++)
+    if (const char *why = ew_source_refusal(D->sources[k])) return why;
+  for (int t = 0; t < D->n_triggers; t++) {
+    const npb_event_trigger_t &T = D->triggers[t];
+    bool integer;
+    if (T.from_source) {
+      if (const char *why = ew_source_refusal(T.source)) return why;
+      integer = T.source.type == NPB_SAMPLE_I32 || T.source.type == NPB_SAMPLE_U8;
+    } else {
+      if ((T.kind != NPB_KIND_F64 && T.kind != NPB_KIND_I32) || !locate(NPB_STORAGE_F64, T.kind, T.slot, &col, &sub, &access))
+        return "npb_set_event_windows: bad field kind or slot";
+      integer = T.kind == NPB_KIND_I32;
+    }
+    if (T.mode == NPB_TRIGGER_MODE_BITS_RISE) {
+      if (!integer) return "npb_set_event_windows: NPB_TRIGGER_BITS_RISE on a real-valued column (it needs an int32 member, or an I32 or U8 source)";
+      if (T.mask == 0u) return "npb_set_event_windows: NPB_TRIGGER_BITS_RISE with mask 0";
+    } else if (T.mode == NPB_TRIGGER_MODE_BEYOND) {
+      if (T.direction != 1 && T.direction != -1) return "npb_set_event_windows: NPB_TRIGGER_BEYOND with a direction outside {-1, +1}";
+      if (T.limit != T.limit) return "npb_set_event_windows: NPB_TRIGGER_BEYOND with a NaN limit";
+    } else if (T.mode != NPB_TRIGGER_MODE_INCREASE) {
+      return "npb_set_event_windows: an unknown trigger mode";
+    }
+  }
+  const void *words[] = {D->plant, D->episode, D->trigger, D->step, D->n_pre, D->n_post, D->flags, D->retriggers, D->fired, D->cursor};
+  for (const void *w : words) {
+    if (!w) return "npb_set_event_windows: a NULL record column or cursor";
+    if ((uintptr_t)w & 3u) return "npb_set_event_windows: a misaligned record column: the double columns must be 8-byte, the others and the cursor 4-byte aligned";
+  }
+  const void *doubles[] = {D->time, D->times, D->values};
+  for (const void *w : doubles) {
+    if (!w) return "npb_set_event_windows: a NULL record column or cursor";
+    if ((uintptr_t)w & 7u) return "npb_set_event_windows: a misaligned record column: the double columns must be 8-byte, the others and the cursor 4-byte aligned";
+  }
+  return nullptr;
+}
+/* the handle's one allocation: [the columns][the triggers] | ring | prev | a_time | the eight 4-byte words per plant; every part 8-byte aligned */
+static size_t ew_table_bytes() {
+  return NPB_EVENT_WINDOW_COLS_MAX * sizeof(npb_colstat_col_t) + NPB_EVENT_WINDOW_TRIGGERS_MAX * sizeof(npb_event_trigger_col_t);
+}
+size_t npb_event_windows_bytes(const npb_event_windows_desc_t *D, int n_plants) {
+  if (!D || npb_event_windows_check(D, n_plants, 0)) return 0;
+  const size_t n = (size_t)n_plants, H = (size_t)D->pre + 1 + (size_t)D->post, n_cols = (size_t)D->n_fields + (size_t)D->n_sources;
+  const size_t words = (8 * n * sizeof(int32_t) + 7) / 8 * 8;
+  return ew_table_bytes() + (H * (n_cols + 1) + (size_t)D->n_triggers + 1) * n * sizeof(double) + words;
+}
+int npb_set_event_windows(NpbHandle *h, const npb_event_windows_desc_t *desc) {
+  if (!h) return NPB_EINVAL;
+  if (const char *why = npb_event_windows_check(desc, h->n_plants, h->autoreset ? 1 : 0)) return fail(h, NPB_EINVAL, why);
+  NPB_USE_DEVICE(h);
+  if (!desc) {
+    if (h->ew.cols) (void)hipFree((void *)h->ew.cols);      /* (hipFree waits for the device: a launch still in flight finishes first) */
+    h->ew = npb_event_windows_t{}; h->ew_bytes = 0;
+    return NPB_OK;
+  }
+  struct { npb_colstat_col_t cols[NPB_EVENT_WINDOW_COLS_MAX]; npb_event_trigger_col_t triggers[NPB_EVENT_WINDOW_TRIGGERS_MAX]; } table = {};
+  static_assert(sizeof table == NPB_EVENT_WINDOW_COLS_MAX * sizeof(npb_colstat_col_t) + NPB_EVENT_WINDOW_TRIGGERS_MAX * sizeof(npb_event_trigger_col_t), "packed");
+  const int n_cols = desc->n_fields + desc->n_sources;
+  for (int c = 0; c < n_cols; c++) {
+    npb_colstat_col_t &C = table.cols[c];
+    if (c < desc->n_fields) {
+      if (!locate(h->storage, desc->kinds[c], desc->slots[c], &C.col, &C.sub, &C.kind)) return fail(h, NPB_EINVAL, "npb_set_event_windows: bad field kind or slot");
+    } else {
+      const npb_sample_source_t &S = desc->sources[c - desc->n_fields];
+      C.row = S.base; C.plant_stride = S.plant_stride; C.kind = 3 + S.type;
+    }
+  }
+  for (int t = 0; t < desc->n_triggers; t++) {
+    const npb_event_trigger_t &T = desc->triggers[t];
+    npb_event_trigger_col_t &O = table.triggers[t];
+    if (T.from_source) { O.c.row = T.source.base; O.c.plant_stride = T.source.plant_stride; O.c.kind = 3 + T.source.type; }
+    else if (!locate(h->storage, T.kind, T.slot, &O.c.col, &O.c.sub, &O.c.kind)) return fail(h, NPB_EINVAL, "npb_set_event_windows: bad field kind or slot");
+    O.mode = T.mode; O.mask = T.mask;
+    if (T.mode == NPB_TRIGGER_MODE_BEYOND) { O.c.direction = T.direction; O.c.limit = T.limit; }
+  }
+  const size_t bytes = npb_event_windows_bytes(desc, h->n_plants), n = (size_t)h->n_plants, H = (size_t)desc->pre + 1 + (size_t)desc->post;
+  char *dev = nullptr;
+  hipError_t e = hipMalloc((void **)&dev, bytes);
+  if (e != hipSuccess) {
+    char what[160];
+    snprintf(what, sizeof what, "npb_set_event_windows: hipMalloc of the ring and the bookkeeping (%zu bytes) failed", bytes);
+    return fail(h, NPB_EHIP, what, e);
+  }
+  npb_event_windows_t W = {};
+  W.cols = (const npb_colstat_col_t *)dev; W.triggers = (const npb_event_trigger_col_t *)(dev + sizeof table.cols);
+  W.n_cols = n_cols; W.n_triggers = desc->n_triggers; W.pre = desc->pre; W.post = desc->post;
+  W.ring = (double *)(dev + sizeof table);
+  W.prev = W.ring + H * (size_t)(n_cols + 1) * n;
+  W.a_time = W.prev + (size_t)desc->n_triggers * n;
+  int32_t *words = (int32_t *)(W.a_time + n);
+  W.valid = words; W.due = words + n; W.seen = words + 2 * n; W.a_step = words + 3 * n; W.a_n_pre = words + 4 * n; W.a_trigger = words + 5 * n;
+  W.a_retriggers = words + 6 * n; W.a_fired = (uint32_t *)(words + 7 * n);
+  W.D = npb_event_window_records_t{desc->capacity, desc->plant, desc->episode, desc->trigger, desc->step, desc->n_pre, desc->n_post, desc->flags,
+                                   desc->retriggers, desc->fired, desc->time, desc->times, desc->values, desc->cursor};
+  /* the tables up, everything else zero (the indices last seen too: a first sample that finds another index empties an empty ring), every
+   * plant unprimed and idle; synchronous, so the host copies may go */
+  e = hipMemset(dev, 0, bytes);
+  if (e == hipSuccess) e = hipMemcpy(dev, &table, sizeof table, hipMemcpyHostToDevice);
+  if (e == hipSuccess) { npb_launch_event_windows_clear(&W, nullptr, h->n_plants, nullptr); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess) { (void)hipFree(dev); return fail(h, NPB_EHIP, "npb_set_event_windows: setting up the ring and the bookkeeping failed", e); }
+  if (h->ew.cols) (void)hipFree((void *)h->ew.cols);
+  h->ew = W; h->ew_bytes = bytes; h->ew_step = 0;
+  return NPB_OK;
+}
+int npb_event_windows_clear(NpbHandle *h, const uint8_t *mask, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->ew.cols) return fail(h, NPB_EINVAL, "npb_event_windows_clear: no event windows set (npb_set_event_windows first)");
+  NPB_USE_DEVICE(h);
+  npb_launch_event_windows_clear(&h->ew, mask, h->n_plants, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
 

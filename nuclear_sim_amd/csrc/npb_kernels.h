@@ -53,6 +53,26 @@ typedef struct {
 /* npb_set_episode_record_stats: what the records kernel needs of the statistics, kept in DEVICE memory by the handle and passed as one
  * pointer (NULL = off), so that the kernel's argument block, and with it the kernel without statistics, stays what it was */
 typedef struct { npb_column_stats_t st; npb_episode_record_stats_desc_t rs; } npb_record_stats_t;
+/* npb_set_event_windows (npd_event_windows.h): one trigger as the kernel reads it -- its column (direction / limit: those of
+ * NPB_TRIGGER_MODE_BEYOND), the mode and the mask of NPB_TRIGGER_MODE_BITS_RISE */
+typedef struct { npb_colstat_col_t c; int mode; uint32_t mask; } npb_event_trigger_col_t;
+/* the caller's record columns, `capacity` entries each (npb_event_windows_desc_t) */
+typedef struct {
+  int capacity;
+  int32_t *plant, *episode, *trigger, *step, *n_pre, *n_post, *flags, *retriggers; uint32_t *fired;
+  double *time, *times, *values; uint32_t *cursor;
+} npb_event_window_records_t;
+/* the handle's event windows: the recorded columns and the triggers (device, one allocation with everything below; cols NULL = off), the
+ * window shape, and the state the handle owns -- the ring [H][n_cols + 1][n_plants] (the plant clock as the extra column), the previous
+ * value of every trigger source [n_triggers][n_plants], and per plant: samples in the ring (0 = unprimed), the step a capture is due (-1 =
+ * idle), the episode index last seen, and of an armed capture the trigger step, its n_pre, the lowest trigger, the fired set, the
+ * triggers since, and the plant clock */
+typedef struct {
+  const npb_colstat_col_t *cols; const npb_event_trigger_col_t *triggers; int n_cols, n_triggers, pre, post;
+  double *ring, *prev, *a_time;
+  int32_t *valid, *due, *seen, *a_step, *a_n_pre, *a_trigger, *a_retriggers; uint32_t *a_fired;
+  npb_event_window_records_t D;
+} npb_event_windows_t;
 typedef struct {
   int (*step)(const npb_params_t *P, int n_plants, size_t npad, void *arena, const int32_t *action,
               const double *magnitude, const double *setpoint, const double *noise_z, const double *cw_temp,
@@ -102,6 +122,11 @@ typedef struct {
                           hipStream_t stream);
   /* npb_set_column_stats (npd_column_stats.h): one sample of every column of every plant folded into the tables, one launch */
   void (*column_stats_fold)(const void *arena, size_t npad, const npb_column_stats_t *S, int n_plants, hipStream_t stream);
+  /* npb_set_event_windows (npd_event_windows.h): the sample of this step into every plant's ring, the triggers, and the windows that are
+   * due.  step: npb_step calls since the windows were set; index: the handle's carried episode indices or NULL; len / done / max_steps:
+   * the carried lengths and the step's done column while the autoreset is on (the episode kernel's rule), else len NULL */
+  void (*event_windows)(const void *arena, size_t npad, const npb_event_windows_t *W, int n_plants, int step, const int32_t *index,
+                        const int32_t *len, const uint8_t *done, int max_steps, hipStream_t stream);
 } npb_launchers_t;
 extern npb_launchers_t npb_launch_table, npb32_launch_table;
 /* the same for either storage type */
@@ -128,6 +153,8 @@ void npb_launch_maint_summary_fold(const npb_maint_summary_desc_t *D, npd_maint_
 void npb_launch_maint_summary_clear(const npb_maint_summary_desc_t *D, const uint8_t *mask, int n_plants, hipStream_t stream);
 /* npb_column_stats_clear (npd_column_stats.h): the cells of the plants of mask (NULL = all) back to the empty values in every table kept */
 void npb_launch_column_stats_clear(const npb_column_stats_t *S, const uint8_t *mask, int n_plants, hipStream_t stream);
+/* npb_event_windows_clear (npd_event_windows.h): the plants of mask (NULL = all) unprimed, their rings empty, an armed capture dropped */
+void npb_launch_event_windows_clear(const npb_event_windows_t *W, const uint8_t *mask, int n_plants, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -1605,12 +1605,14 @@ static void NPB_LAUNCHER(episode_records)(int n_plants, size_t npad, const void 
                                           const npb_episode_records_desc_t *D, const npb_maint_summary_desc_t *summary, const npb_record_stats_t *record_stats,
                                           hipStream_t stream);     /* the same */
 static void NPB_LAUNCHER(column_stats_fold)(const void *arena, size_t npad, const npb_column_stats_t *S, int n_plants, hipStream_t stream);     /* the same */
+static void NPB_LAUNCHER(event_windows)(const void *arena, size_t npad, const npb_event_windows_t *W, int n_plants, int step, const int32_t *index,
+                                        const int32_t *len, const uint8_t *done, int max_steps, hipStream_t stream);     /* the same */
 /* not const: clang emits a namespace-scope const into the device code too, where these host functions do not exist */
 extern "C" npb_launchers_t NPB_LAUNCHER(table) = {
   NPB_LAUNCHER(step), NPB_LAUNCHER(maint), NPB_LAUNCHER(observe), NPB_LAUNCHER(init), NPB_LAUNCHER(reset),
   NPB_LAUNCHER(field_get), NPB_LAUNCHER(field_set), NPB_LAUNCHER(gather), NPB_LAUNCHER(restore), NPB_LAUNCHER(episode),
   NPB_LAUNCHER(operator_maint), NPB_LAUNCHER(operator_component_maint), NPB_LAUNCHER(operator_turbine_maint), NPB_LAUNCHER(maint_all),
-  NPB_LAUNCHER(sample), NPB_LAUNCHER(episode_records), NPB_LAUNCHER(column_stats_fold),
+  NPB_LAUNCHER(sample), NPB_LAUNCHER(episode_records), NPB_LAUNCHER(column_stats_fold), NPB_LAUNCHER(event_windows),
 };
 #ifndef NPB_BUILD_F32
 /* npb_reset / npb_reset_reference / npb_restore: the episode counters (len, ret) and the carried start entries (start: -1, not from
@@ -1824,3 +1826,6 @@ static void NPB_LAUNCHER(episode_records)(int n_plants, size_t npad, const void 
 
 /* the per-plant column statistics (npb_set_column_stats): the fold kernel, the clear kernel and their launchers */
 #include "npd_column_stats.h"
+
+/* state windows around events (npb_set_event_windows): the per-step kernel, the clear kernel and their launchers */
+#include "npd_event_windows.h"

@@ -381,6 +381,15 @@ class BatchedPlantEnv:
     ``nuclear_sim_amd.colstats.fold`` states the fold in numpy and the device gives its bits.  With episode records on, each record
     carries the statistics of its own episode (``stat_min`` ...), and the tables restart with the episode.  Output only, like the
     work-order summary.  Off by default: nothing changes.
+
+    Event windows (``enable_event_windows(columns, triggers, pre, post)``): what a plant looked like around a trip, a work order or a
+    limit being crossed, with no state log of every plant and no watch list chosen beforehand.  Every plant keeps its last ``pre + 1 +
+    post`` samples of up to 16 columns in a ring on the device; a trigger (rising trip bits, ``done``, a new work order or completion, the
+    event count, a column crossing a limit) arms a capture, and ``post`` steps later -- or when the episode ends first -- the window goes
+    into a record (npb_set_event_windows: one more launch behind every step, nothing read back).  ``event_windows()`` drains the records
+    whenever the caller chooses, ``write_event_windows(path)`` writes them, ``clear_event_windows(mask)`` forgets the masked plants'
+    history.  ``nuclear_sim_amd.eventwin.record`` states the capture in numpy and the device gives its bits.  Output only.  Off by
+    default: nothing changes.
     """
 
     action_space_size = 15       # NuclearPlantEnv sim.py:916
@@ -767,6 +776,9 @@ class BatchedPlantEnv:
         er = getattr(self, "_erec", None)
         if er is not None and (er["n_keys"] or er["desc"].clear_summary):
             raise _lib.NpbError("episode records that copy or clear the maintenance summary are on: disable_episode_records() first")
+        ew = getattr(self, "_ewin", None)
+        if ew is not None and ew["summary"] is not None:
+            raise _lib.NpbError("event windows with a work_order / completed trigger read the maintenance summary's tables: enable_event_windows(None) first")
         if keys is None:
             if getattr(self, "_msum", None) is not None:
                 _lib.check(self.L.npb_set_maintenance_summary(self._h, None), self._h)
@@ -1044,6 +1056,132 @@ class BatchedPlantEnv:
         if getattr(self, "_cstats", None) is None:
             raise _lib.NpbError("no column statistics: enable_column_stats() first")
         _lib.check(self.L.npb_column_stats_fold(self._h, self._stream()), self._h)
+
+    def enable_event_windows(self, columns, triggers=None, pre: int = 8, post: int = 8, capacity: Optional[int] = None) -> None:
+        """Have the device capture a window of ``columns`` around every event (npb_set_event_windows): each plant keeps its last
+        ``pre + 1 + post`` end-of-step samples in a ring on the device; a trigger arms a capture, and ``post`` steps later the window --
+        ``pre`` samples before the trigger, the trigger sample, ``post`` after -- goes into a record that ``event_windows()`` drains
+        whenever the caller chooses.  One more launch behind every step, nothing read back.  ``columns``: 1 to 16, keyed as
+        ``enable_column_stats`` keys them.  ``triggers``: 1 to 8, each ``("trip", mask)`` (rising bits of the step's trip flags),
+        ``("done",)``, ``("work_order", key_index)`` / ``("completed", key_index)`` (a new work order / completion under that key of
+        ``enable_maintenance_summary``, which must be on), ``("maintenance",)`` (the event count goes up) or ``(column, ">" | "<",
+        value)`` (the edge of a limit).  ``capacity`` records are allocated (None = ``max(n, 4096)``); captures past them are counted,
+        not written, until the next drain.  A capture whose episode ends before ``post`` more steps is taken at once (``early``); a
+        restart (autoreset, ``restore``, ``reset``; without autoreset ``clear_event_windows(mask)``) empties the plant's ring and drops an
+        armed capture.  ``nuclear_sim_amd.eventwin.record`` is the same in numpy, bit for bit.  ``None`` for ``columns`` turns it off.
+        Output only: ``snapshot``, ``restore`` and the start bank leave it alone.  While it is on, the maintenance summary a
+        ``work_order`` trigger reads must stay as it is."""
+        if columns is None:
+            if getattr(self, "_ewin", None) is not None:
+                _lib.check(self.L.npb_set_event_windows(self._h, None), self._h)
+            self._ewin = None
+            return
+        ms = getattr(self, "_msum", None)
+        req = _lib.event_windows_request(columns, triggers or (), pre, post, INFO_COLUMNS, 0 if ms is None else len(ms["keys"]))
+        if not hasattr(self.L, "npb_set_event_windows"):
+            raise _lib.NpbError("libnpb.so has no npb_set_event_windows: rebuild")
+        cap = max(self.n, 4096) if capacity is None else int(capacity)
+        if cap < 1:
+            raise ValueError("capacity must be >= 1")
+        nm, ns, nt = len(req["members"]), len(req["sides"]), len(req["triggers"])
+        n_cols, H = nm + ns, req["pre"] + 1 + req["post"]
+        d = _lib.NpbEventWindowsDesc()
+        kinds = (ctypes.c_int * max(nm, 1))(*[m[0] for m in req["members"]])
+        slots = (ctypes.c_int * max(nm, 1))(*[m[1] for m in req["members"]])
+        side = (_lib.NpbSampleSource * max(ns, 1))()
+        buffers = {"info": self._info_buf, "obs": self._obs, "reward": self._reward, "flags": self._flags, "done": self._done}
+        if ms is not None:
+            buffers.update(n_created=ms["counts"][0], n_completed=ms["counts"][1])
+        width = {"f64": 8, "i32": 4, "u8": 1}
+
+        def source(S, name, offset, stride, kind="f64"):
+            rows = offset * self.n if name in ("n_created", "n_completed") else offset      # (a summary table is [n_keys][n])
+            S.base = buffers[name].data_ptr() + width[kind] * rows; S.type = _lib.SAMPLE_TYPES[kind]; S.rows = 1
+            S.row_stride = 0; S.plant_stride = stride
+        for k, where in enumerate(req["sides"]):
+            source(side[k], *where)
+        trig = (_lib.NpbEventTrigger * nt)()
+        for k, T in enumerate(req["triggers"]):
+            if T["member"] is not None:
+                trig[k].from_source, trig[k].kind, trig[k].slot = 0, T["member"][0], T["member"][1]
+            else:
+                trig[k].from_source = 1
+                source(trig[k].source, *T["side"])
+            trig[k].mode, trig[k].mask, trig[k].direction, trig[k].limit = _lib.TRIGGER_MODES[T["mode"]], T["mask"], T["direction"], T["limit"]
+        d.n_fields, d.kinds, d.slots, d.n_sources, d.sources, d.n_triggers, d.triggers = nm, kinds, slots, ns, side, nt, trig
+        d.pre, d.post, d.capacity = req["pre"], req["post"], cap
+        dev, host = {}, {}
+        with torch.cuda.device(self.device):
+            shapes = [(name, (cap,), torch.int32) for name in _lib.EVENT_WINDOW_WORDS + ("fired",)]      # (the uint32 fired set travels as int32 bits)
+            shapes += [("time", (cap,), torch.float64), ("times", (cap, H), torch.float64), ("values", (cap, H, n_cols), torch.float64)]
+            for name, shape, dtype in shapes:
+                dev[name] = torch.zeros(shape, dtype=dtype, device=self.device)
+                host[name] = torch.empty(shape, dtype=dtype, pin_memory=True)      # the drain's landing place, as the episode records'
+                setattr(d, name, dev[name].data_ptr())
+            cursor = torch.zeros(1, dtype=torch.int32, device=self.device)     # a uint32 on the device
+        d.cursor = cursor.data_ptr()
+        _lib.check(self.L.npb_set_event_windows(self._h, ctypes.byref(d)), self._h)
+        self._ewin = {"desc": d, "keep": (kinds, slots, side, trig), "dev": dev, "host": host, "cursor": cursor,
+                      "host_cursor": torch.empty(1, dtype=torch.int32, pin_memory=True), "capacity": cap, "order": req["order"],
+                      "columns": list(columns), "pre": req["pre"], "post": req["post"], "triggers": req["numpy"],
+                      "bytes": int(self.L.npb_event_windows_bytes(ctypes.byref(d), self.n)),
+                      "summary": ms["counts"] if any(T["side"] and T["side"][0] in ("n_created", "n_completed") for T in req["triggers"]) else None}
+
+    def event_windows(self, clear: bool = True, allow_overflow: bool = False) -> Dict[str, np.ndarray]:
+        """Drain the event windows on the env's stream, one read-back: numpy columns of m records sorted by (capture step, plant) --
+        ``plant``, ``episode``, ``trigger`` (the lowest trigger that fired), ``step`` (the trigger's step since the windows were enabled,
+        0 = the first), ``n_pre``, ``n_post``, ``flags``, ``retriggers`` (int32), ``fired`` (uint32: every trigger that fired on that
+        step), ``time`` (the plant clock at the trigger), ``times`` [m, H], ``values`` [m, H, n_cols] in the order of ``columns`` (row
+        ``pre`` is the trigger sample; rows outside ``[pre - n_pre, pre + n_post]`` are NaN) and ``early`` = ``flags & 1``.  An
+        overflowed log raises, naming how many captures were dropped, and is left as it is, unless ``allow_overflow`` (which of one
+        step's captures fitted is then not defined)."""
+        ew = getattr(self, "_ewin", None)
+        if ew is None:
+            raise _lib.NpbError("no event windows: enable_event_windows() first")
+        stream = torch.cuda.current_stream(self.device)
+        ew["host_cursor"].copy_(ew["cursor"], non_blocking=True)
+        stream.synchronize()
+        count = int(ew["host_cursor"][0]) & 0xFFFFFFFF
+        cap = ew["capacity"]
+        if count > cap and not allow_overflow:
+            raise _lib.NpbError("event windows overflowed: %d captures, capacity %d, %d dropped (enable_event_windows with a larger "
+                                "capacity, drain more often, or pass allow_overflow=True)" % (count, cap, count - cap))
+        m = min(count, cap)
+        if m:
+            for name, t in ew["dev"].items():
+                ew["host"][name][:m].copy_(t[:m], non_blocking=True)
+            stream.synchronize()
+        raw = {name: t.numpy()[:m].copy() for name, t in ew["host"].items()}
+        if clear:
+            ew["cursor"].zero_()
+        order = np.lexsort((raw["plant"], raw["step"] + raw["n_post"]))
+        out = {name: np.ascontiguousarray(a[order]) for name, a in raw.items()}
+        out["fired"] = out["fired"].view(np.uint32)
+        out["values"] = np.ascontiguousarray(out["values"][:, :, ew["order"]])
+        out["early"] = (out["flags"] & 1) != 0
+        return out
+
+    def write_event_windows(self, path: str, clear: bool = True, allow_overflow: bool = False) -> None:
+        """Drain the event windows into a CSV (``.csv``) or Parquet file: one row per capture; the clock of row offset k (-pre .. post)
+        as ``time_m<k>`` / ``time_p<k>`` and recorded column c at that offset as ``c<c>_m<k>`` / ``c<c>_p<k>``"""
+        from . import maintlog
+        rec = self.event_windows(clear=clear, allow_overflow=allow_overflow)
+        pre = self._ewin["pre"]
+        cols = {name: a for name, a in rec.items() if a.ndim == 1}
+        for k in range(rec["times"].shape[1]):
+            tag = "m%d" % (pre - k) if k < pre else "p%d" % (k - pre)
+            cols["time_" + tag] = np.ascontiguousarray(rec["times"][:, k])
+            for c in range(rec["values"].shape[2]):
+                cols["c%d_%s" % (c, tag)] = np.ascontiguousarray(rec["values"][:, k, c])
+        maintlog.write(cols, path)
+
+    def clear_event_windows(self, mask=None) -> None:
+        """the masked plants (None = all) unprimed, their rings empty, an armed capture dropped without a record
+        (npb_event_windows_clear): what a caller without autoreset does for the plants it restarted"""
+        if getattr(self, "_ewin", None) is None:
+            raise _lib.NpbError("no event windows: enable_event_windows() first")
+        m = None if mask is None else self._col(mask, torch.uint8)
+        _lib.check(self.L.npb_event_windows_clear(self._h, None if m is None else self._p(m), self._stream()), self._h)
 
     def _order_buffers(self):
         """the buffers the perform_*_maintenance methods keep for their order columns, with the ``success`` column they all return"""
@@ -1335,6 +1473,7 @@ class BatchedPlantEnv:
             self._h = ctypes.c_void_p()
         self._erec = None      # the episode records' buffers go with the handle
         self._cstats = None
+        self._ewin = None      # (the handle has freed the ring; the record columns go with it)
 
     def __del__(self):
         try:
