@@ -854,6 +854,108 @@ NPB_API const char *npb_event_windows_check(const npb_event_windows_desc_t *desc
 NPB_API int npb_event_windows_clear(NpbHandle *h, const uint8_t *mask, void *stream);
 NPB_API size_t npb_event_windows_bytes(const npb_event_windows_desc_t *desc, int n_plants);
 
+/* Tasks: the caller's own reward and termination rule, formed on the device behind every step -- the one part of an RL or data-generation
+ * job that every user defines themselves.  Without a task the episode machinery (npb_set_autoreset, the episode records, the event
+ * windows' early captures) ends an episode on the reference's scram pulse or on max_episode_steps and sums the reference's reward; with a
+ * task it uses the task's `done` and `reward` columns in place of the step's: an episode can end because the turbine tripped, because a
+ * pump's oil level fell through a limit or because a value went non-finite, and a work order can cost something.
+ * Columns (npb_task_column_t) are named as npb_event_trigger_t names its column: an arena member (kind, slot), or with from_source != 0 a
+ * one-row npb_sample_source_t (an info or obs column, the step's reward / done / trip_flags buffers, a row of the work-order summary, the
+ * event-count column), every value widened to double as npb_sample_kernel widens it.
+ * Reward terms, 0 .. NPB_TASK_TERMS_MAX, each a column v, a weight w and a kind (ref = the constant `ref`, or with ref_from_column != 0 the
+ * sample of ref_column; prev = the same plant's previous sample of the column):
+ *   NPB_TASK_VALUE     f = v
+ *   NPB_TASK_ABS_ERR   f = fabs(v - ref)
+ *   NPB_TASK_SQ_ERR    f = (v - ref) * (v - ref)
+ *   NPB_TASK_BEYOND    f = 1.0 if beyond the limit by the statistics' rule (direction +1: v > limit, -1: v < limit), else 0.0
+ *   NPB_TASK_EXCESS    f = +1: v > limit ? v - limit : 0.0;  -1: v < limit ? limit - v : 0.0
+ *   NPB_TASK_BITS      integer column: f = ((v & mask) != 0) ? 1.0 : 0.0
+ *   NPB_TASK_DELTA     f = v - prev; 0.0 on the first sample of an UNPRIMED plant.  A plant is unprimed when the task is set, when the
+ *                      handle carries an episode index (npb_set_autoreset) and it differs from the one last seen (the event windows' rule:
+ *                      autoreset, npb_restore*, npb_reset*), and after npb_task_clear(mask).  This is how an event count, a work-order
+ *                      count of the summary or a maintenance counter gets a price.
+ *   reward = bias + w_0 * f_0 + w_1 * f_1 + ... accumulated sequentially in term order, each product rounded before its add (the library
+ *   is built with -ffp-contract=off).  A NaN sample gives a NaN reward through VALUE, ABS_ERR, SQ_ERR and DELTA (whatever the weight, 0
+ *   included); BEYOND and EXCESS compare, so a NaN sample gives 0.0 there.  The step's own reward is a term like any other -- a source on
+ *   the reward buffer given to npb_step -- so "the reference's reward plus extras" is one VALUE term of weight 1.
+ * Termination rules, 0 .. NPB_TASK_RULES_MAX, each a column, a mode and a terminal_reward:
+ *   NPB_TASK_RULE_BITS_ANY(mask)             integer column: (v & mask) != 0
+ *   NPB_TASK_RULE_BEYOND(direction, limit)   beyond the limit, as above
+ *   NPB_TASK_RULE_NONFINITE                  !(fabs(v) <= DBL_MAX): a NaN or an infinity
+ *   cause = one bit per rule that fired (bit r = rule r), done = cause != 0, and the terminal rewards of the fired rules are added to the
+ *   reward behind the terms, in rule order.  Rules are LEVELS, not edges: with the autoreset on the plant restarts on that very step and
+ *   the level is gone at the next sample; without it a level keeps reporting done on every step for as long as it holds.  The reference's
+ *   scram pulse is the rule BITS_ANY(0xff) on the done buffer given to npb_step; a task without that rule no longer ends episodes on a
+ *   scram -- the caller's choice.
+ * Outputs, device buffers of the caller's: reward double [n_plants] and done uint8 [n_plants], mandatory; cause uint32 [n_plants] or NULL;
+ * terms double [n_terms][n_plants] or NULL: each term's w * f, element [term * n_plants + plant], for reward decomposition.  The handle
+ * owns the previous samples of the DELTA terms ([n_delta][n_plants], in term order), a primed flag and the episode index last seen per
+ * plant; npb_task_get_state / npb_task_set_state move them to and from host arrays for checkpoints (prev double [n_delta][n_plants] --
+ * may be NULL when the task has no DELTA term --, primed int32 [n_plants], seen int32 [n_plants]; synchronous on `stream`; NPB_EINVAL
+ * without a task).
+ * With a task set npb_step launches ONE more kernel on its stream (npd_task.h; one thread per plant, one wave per 64, no LDS, no atomics):
+ * behind the step kernel, the maintenance rule and the work-order summary fold -- a term may read this step's event count and summary
+ * rows -- and BEFORE the column-statistics fold, the event-windows kernel, the episode-records kernel and the episode kernel, which are
+ * then handed the task's done and reward columns in place of the caller's.  The reward / done buffers given to npb_step still receive
+ * exactly what the step kernel writes.  No step, restore or episode kernel changes.
+ * npb_set_task(h, desc): desc = NULL turns the task off; the descriptor is copied (its host arrays too), every plant unprimed.  NPB_EINVAL
+ * with the reason in npb_last_error, before any device work, for what npb_task_check refuses -- that check alone, without a handle, NULL
+ * = accepted, else the reason: n_plants < 1; a term or rule count out of range (or a count without its array); a task with neither terms
+ * nor rules; a bad kind or slot; a source with a NULL base, an unknown type or rows != 1; an unknown term kind or rule mode; BITS or
+ * BITS_ANY on a real-valued column, or with mask 0; a direction outside {-1, +1} where one is needed; a NaN weight, limit, ref, bias or
+ * terminal reward; a NULL reward or done output; a misaligned output (doubles 8-byte, cause 4-byte).  While npb_set_episode_record_task
+ * is set npb_set_task (another descriptor, or NULL) is refused.
+ * npb_set_episode_record_task(h, cause): why an episode ended, in its record (npb_set_episode_records) -- cause int32 [capacity] on the
+ * device takes the ended plant's cause word (its bits) beside the record's other columns.  A descriptor of its own, so that
+ * npb_episode_records_desc_t keeps its layout, under the rules of npb_set_episode_record_stats: it needs records and a task both on
+ * (NPB_EINVAL otherwise, for a misaligned column, and for a task that keeps no cause column); NULL drops it, and so does EVERY successful
+ * npb_set_episode_records.  Off, the records kernel stores exactly what it stored before.
+ * NPB_VERSION stays 154: a binding detects the entry points by name.  A handle that never calls this behaves as before in every entry
+ * point. */
+#define NPB_TASK_TERMS_MAX 16
+#define NPB_TASK_RULES_MAX 8
+enum { NPB_TASK_VALUE = 0, NPB_TASK_ABS_ERR = 1, NPB_TASK_SQ_ERR = 2, NPB_TASK_BEYOND = 3, NPB_TASK_EXCESS = 4, NPB_TASK_BITS = 5, NPB_TASK_DELTA = 6 };
+enum { NPB_TASK_RULE_MODE_BITS_ANY = 0, NPB_TASK_RULE_MODE_BEYOND = 1, NPB_TASK_RULE_MODE_NONFINITE = 2 };
+/* the members mode, mask, direction, limit of an npb_task_rule_t initialiser */
+#define NPB_TASK_RULE_BITS_ANY(mask) NPB_TASK_RULE_MODE_BITS_ANY, (uint32_t)(mask), 0, 0.0
+#define NPB_TASK_RULE_BEYOND(direction, limit) NPB_TASK_RULE_MODE_BEYOND, 0u, (direction), (limit)
+#define NPB_TASK_RULE_NONFINITE NPB_TASK_RULE_MODE_NONFINITE, 0u, 0, 0.0
+typedef struct npb_task_column_t {
+  int from_source;               /* 0: the arena member (kind, slot); != 0: `source`, one value per plant */
+  int kind, slot;
+  npb_sample_source_t source;
+} npb_task_column_t;
+typedef struct npb_task_term_t {
+  npb_task_column_t column;
+  double weight;
+  int kind;                      /* NPB_TASK_* */
+  int ref_from_column;           /* ABS_ERR, SQ_ERR: 0 = the constant `ref`, != 0 = ref_column */
+  double ref;
+  npb_task_column_t ref_column;
+  int direction; double limit;   /* BEYOND, EXCESS */
+  uint32_t mask;                 /* BITS */
+} npb_task_term_t;
+typedef struct npb_task_rule_t {
+  npb_task_column_t column;
+  int mode; uint32_t mask; int direction; double limit;
+  double terminal_reward;
+} npb_task_rule_t;
+typedef struct npb_task_desc_t {
+  int n_terms; const npb_task_term_t *terms;      /* host */
+  int n_rules; const npb_task_rule_t *rules;      /* host */
+  double bias;
+  double *reward;                /* device [n_plants] */
+  uint8_t *done;                 /* device [n_plants] */
+  uint32_t *cause;               /* device [n_plants] or NULL */
+  double *terms_out;             /* device [n_terms][n_plants] or NULL */
+} npb_task_desc_t;
+NPB_API int npb_set_task(NpbHandle *h, const npb_task_desc_t *desc);
+NPB_API const char *npb_task_check(const npb_task_desc_t *desc, int n_plants);
+NPB_API int npb_task_clear(NpbHandle *h, const uint8_t *mask, void *stream);
+NPB_API int npb_task_get_state(NpbHandle *h, double *prev, int32_t *primed, int32_t *seen, void *stream);
+NPB_API int npb_task_set_state(NpbHandle *h, const double *prev, const int32_t *primed, const int32_t *seen, void *stream);
+NPB_API int npb_set_episode_record_task(NpbHandle *h, int32_t *cause /* device [capacity] */);
+
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the
  * rocprofv3 FETCH_SIZE / WRITE_SIZE counters (tools/profile_traffic.py). */

@@ -430,11 +430,12 @@ class NpbEpisodeRecordStatsDesc(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name in COLUMN_STATS + ("n_samples",)] + [("clear", ctypes.c_int)]
 
 
-def column_stats_request(columns, limits=None, stats=("min", "max", "sum", "sumsq", "last"), info_columns=None) -> dict:
+def column_stats_request(columns, limits=None, stats=("min", "max", "sum", "sumsq", "last"), info_columns=None, task: bool = False) -> dict:
     """What ``BatchedPlantEnv.enable_column_stats`` asks of npb_set_column_stats, from the caller's words; a pure function, host only, so an
     unknown name, index or statistic is refused (ValueError) before any device work.  ``columns``: a state member as ``set_fields`` keys it
     (``name``, ``(name, instance)`` or ``(name, instance, k)``), ``("info", column_name)``, ``("obs", i)`` or ``"reward"``.  ``limits``:
-    ``{column_index: (">" | "<", value)}``, the index into ``columns``.  ``stats``: names of ``COLUMN_STATS``.
+    ``{column_index: (">" | "<", value)}``, the index into ``columns``.  ``stats``: names of ``COLUMN_STATS``.  ``task``: a task is set
+    (``BatchedPlantEnv.set_task``), so ``"task_reward"`` -- the task's reward column, buffer "task_reward" -- is a column too.
     Returns {"members": [(kind, slot)] -- 0 f64 / 1 i32, as npb_gather_fields takes them --, "sides": [(buffer, element offset, plant stride)]
     with buffer "info" | "obs" | "reward" (float64 device buffers of the env), "order": for every entry of ``columns`` its column on the
     device (members come first there, then the side rows), "direction" / "limit": lists per DEVICE column, "stats": the tables kept, in
@@ -453,6 +454,10 @@ def column_stats_request(columns, limits=None, stats=("min", "max", "sum", "sums
         key = (col,) if isinstance(col, str) else tuple(col)
         if key == ("reward",):
             where.append(("side", len(sides))); sides.append(("reward", 0, 1))
+        elif key == ("task_reward",):
+            if not task:
+                raise ValueError("the column 'task_reward' needs a task: set_task() first")
+            where.append(("side", len(sides))); sides.append(("task_reward", 0, 1))
         elif key and key[0] == "info":
             if len(key) != 2 or key[1] not in info_columns:
                 raise ValueError("unknown info column %r: one of %r" % (key[1:], tuple(info_columns)))
@@ -507,13 +512,14 @@ class NpbEventWindowsDesc(ctypes.Structure):
                [(name, ctypes.c_void_p) for name in EVENT_WINDOW_WORDS + ("fired", "time", "times", "values", "cursor")]
 
 
-def event_windows_request(columns, triggers, pre, post, info_columns=None, summary_keys: int = 0) -> dict:
+def event_windows_request(columns, triggers, pre, post, info_columns=None, summary_keys: int = 0, task: bool = False) -> dict:
     """What ``BatchedPlantEnv.enable_event_windows`` asks of npb_set_event_windows, from the caller's words; a pure function, host only, so
     an unknown name or a trigger that cannot work is refused (ValueError) before any device work.  ``columns`` as ``column_stats_request``
     takes them, 1 to 16.  ``triggers``: 1 to 8, each ``("trip", mask)`` (rising bits of the step's trip flags), ``("done",)``,
     ``("work_order", key_index)`` / ``("completed", key_index)`` (the summary's n_created / n_completed row of that key goes up: needs
     ``summary_keys`` > key_index, the keys of ``enable_maintenance_summary``), ``("maintenance",)`` (the event count goes up) or
-    ``(column, ">" | "<", value)`` (the edge of a limit on any column).
+    ``(column, ">" | "<", value)`` (the edge of a limit on any column).  ``task``: a task is set (``BatchedPlantEnv.set_task``), so
+    ``"task_reward"`` is a column and ``("task", mask)`` -- rising bits of the task's cause column, side buffer "task_cause" -- a trigger.
     Returns {"members", "sides", "order": as ``column_stats_request``; "triggers": per trigger {"member": (kind, slot) or None, "side":
     (buffer, element offset, plant stride, element type) or None, "mode": "bits_rise" | "increase" | "beyond", "mask", "direction",
     "limit"} with the side buffers "info" | "obs" | "reward" | "flags" | "done" | "n_created" | "n_completed" (for the last two the
@@ -521,7 +527,7 @@ def event_windows_request(columns, triggers, pre, post, info_columns=None, summa
     columns = list(columns)
     if not 1 <= len(columns) <= EVENT_WINDOW_COLS_MAX:
         raise ValueError("event windows take 1 to %d columns, not %d" % (EVENT_WINDOW_COLS_MAX, len(columns)))
-    req = column_stats_request(columns, None, ("last",), info_columns)
+    req = column_stats_request(columns, None, ("last",), info_columns, task)
     triggers = list(triggers)
     if not 1 <= len(triggers) <= EVENT_WINDOW_TRIGGERS_MAX:
         raise ValueError("event windows take 1 to %d triggers, not %d" % (EVENT_WINDOW_TRIGGERS_MAX, len(triggers)))
@@ -537,6 +543,14 @@ def event_windows_request(columns, triggers, pre, post, info_columns=None, summa
             if not 0 < mask <= 0xFFFFFFFF:
                 raise ValueError("the ('trip', mask) trigger needs 0 < mask < 2**32, not %r" % (t[1],))
             T.update(side=("flags", 0, 1, "i32"), mode="bits_rise", mask=mask)
+            as_numpy.append(("bits", mask))
+        elif len(t) == 2 and t[0] == "task":
+            mask = int(t[1])
+            if not task:
+                raise ValueError("the ('task', mask) trigger needs a task: set_task() first")
+            if not 0 < mask <= 0xFFFFFFFF:
+                raise ValueError("the ('task', mask) trigger needs 0 < mask < 2**32, not %r" % (t[1],))
+            T.update(side=("task_cause", 0, 1, "i32"), mode="bits_rise", mask=mask)
             as_numpy.append(("bits", mask))
         elif t == ("done",):
             T.update(side=("done", 0, 1, "u8"), mode="bits_rise", mask=1)
@@ -558,7 +572,7 @@ def event_windows_request(columns, triggers, pre, post, info_columns=None, summa
         elif len(t) == 3 and t[1] in (">", "<"):
             if np.isnan(float(t[2])):
                 raise ValueError("the limit of trigger %r is NaN" % (t,))
-            one = column_stats_request([t[0]], None, ("last",), info_columns)
+            one = column_stats_request([t[0]], None, ("last",), info_columns, task)
             if one["members"]:
                 T.update(member=one["members"][0])
             else:
@@ -570,6 +584,163 @@ def event_windows_request(columns, triggers, pre, post, info_columns=None, summa
                              "('maintenance',) or (column, '>' | '<', value)" % (t,))
         out.append(T)
     return {"members": req["members"], "sides": req["sides"], "order": req["order"], "triggers": out, "numpy": as_numpy, "pre": pre, "post": post}
+
+
+# include/npb.h npb_task_desc_t: the caller's reward terms and termination rules, formed on the device behind every step (npb_set_task)
+TASK_TERMS_MAX, TASK_RULES_MAX = 16, 8
+TASK_KINDS = {"value": 0, "abs_err": 1, "sq_err": 2, "beyond": 3, "excess": 4, "bits": 5, "delta": 6}      # NPB_TASK_* (task.KINDS)
+TASK_MODES = {"bits_any": 0, "beyond": 1, "nonfinite": 2}                                                # NPB_TASK_RULE_MODE_* (task.MODES)
+
+
+class NpbTaskColumn(ctypes.Structure):
+    """npb_task_column_t: an arena member, or a one-row side source"""
+    _fields_ = [("from_source", ctypes.c_int), ("kind", ctypes.c_int), ("slot", ctypes.c_int), ("source", NpbSampleSource)]
+
+
+class NpbTaskTerm(ctypes.Structure):
+    """npb_task_term_t: one reward term"""
+    _fields_ = [("column", NpbTaskColumn), ("weight", ctypes.c_double), ("kind", ctypes.c_int), ("ref_from_column", ctypes.c_int),
+                ("ref", ctypes.c_double), ("ref_column", NpbTaskColumn), ("direction", ctypes.c_int), ("limit", ctypes.c_double),
+                ("mask", ctypes.c_uint32)]
+
+
+class NpbTaskRule(ctypes.Structure):
+    """npb_task_rule_t: one termination rule"""
+    _fields_ = [("column", NpbTaskColumn), ("mode", ctypes.c_int), ("mask", ctypes.c_uint32), ("direction", ctypes.c_int),
+                ("limit", ctypes.c_double), ("terminal_reward", ctypes.c_double)]
+
+
+class NpbTaskDesc(ctypes.Structure):
+    """npb_task_desc_t: the terms and rules (host arrays), the bias and the caller's device output columns"""
+    _fields_ = [("n_terms", ctypes.c_int), ("terms", ctypes.POINTER(NpbTaskTerm)), ("n_rules", ctypes.c_int), ("rules", ctypes.POINTER(NpbTaskRule)),
+                ("bias", ctypes.c_double), ("reward", ctypes.c_void_p), ("done", ctypes.c_void_p), ("cause", ctypes.c_void_p),
+                ("terms_out", ctypes.c_void_p)]
+
+
+def task_request(reward=(), terminate=(), bias: float = 0.0, info_columns=None, summary_keys: int = 0) -> dict:
+    """What ``BatchedPlantEnv.set_task`` asks of npb_set_task, from the caller's words; a pure function, host only, so a word that cannot
+    work is refused (ValueError, naming it) before any device work.
+    A column is keyed as ``column_stats_request`` keys it -- a state member, ``("info", name)``, ``("obs", i)``, ``"reward"`` (the step's
+    own reward) -- or is one of the integer sides ``"flags"`` (the step's trip flags), ``"done"`` (the reference's scram pulse),
+    ``("work_order", key_index)`` / ``("completed", key_index)`` (the summary's n_created / n_completed row of that key: needs
+    ``summary_keys`` > key_index) and ``"maintenance"`` (the event count).
+    ``reward``: 0 to 16 terms, ``(column, weight)`` (the value itself) or ``(column, weight, kind, ...)``: ``"value"``; ``"abs_err", ref``
+    / ``"sq_err", ref`` with ref a number or a second column; ``"beyond", ">" | "<", limit`` / ``"excess", ">" | "<", limit``; ``"bits",
+    mask`` on an integer column; ``"delta"``.  ``terminate``: 0 to 8 rules, ``("done",)`` (the reference's scram pulse), ``("trip",
+    mask)`` (any of those trip flags set), ``(column, ">" | "<", value)`` or ``(column, "nonfinite")``, each with an optional trailing
+    terminal reward.
+    Returns {"columns": per column read {"member": (kind, slot) or None, "side": (buffer, element offset, plant stride, element type) or
+    None, "integer": bool} with the side buffers of ``event_windows_request``; "terms": per term {"col", "weight", "kind", "ref" (a number,
+    or ("col", index)), "direction", "limit", "mask"}; "rules": per rule {"col", "mode", "mask", "direction", "limit", "terminal_reward"};
+    "bias"} -- "terms", "rules" and "bias" are the spec ``task.evaluate`` takes, over the rows of "columns"."""
+    reward, terminate = list(reward or ()), list(terminate or ())
+    if len(reward) > TASK_TERMS_MAX:
+        raise ValueError("a task takes 0 to %d reward terms, not %d" % (TASK_TERMS_MAX, len(reward)))
+    if len(terminate) > TASK_RULES_MAX:
+        raise ValueError("a task takes 0 to %d termination rules, not %d" % (TASK_RULES_MAX, len(terminate)))
+    if not reward and not terminate:
+        raise ValueError("a task needs a reward term or a termination rule")
+    bias = float(bias)
+    if np.isnan(bias):
+        raise ValueError("the bias is NaN")
+    columns, index = [], {}
+
+    def column(col):
+        key = (col,) if isinstance(col, str) else tuple(col)
+        if key in index:
+            return index[key]
+        C = {"member": None, "side": None, "integer": False}
+        if key == ("flags",):
+            C.update(side=("flags", 0, 1, "i32"), integer=True)
+        elif key == ("done",):
+            C.update(side=("done", 0, 1, "u8"), integer=True)
+        elif key == ("maintenance",):
+            kind, slot = SCHEMA.slot("maint.maintenance_actions_performed")
+            C.update(member=(0 if kind == "f64" else 1, slot), integer=kind != "f64")
+        elif len(key) == 2 and key[0] in ("work_order", "completed"):
+            k = key[1]
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+                raise ValueError("the %r column takes the index of a summary key, not %r" % (key[0], k))
+            if summary_keys < 1:
+                raise ValueError("the %r column reads the maintenance summary: enable_maintenance_summary() first" % (key[0],))
+            if not 0 <= k < summary_keys:
+                raise ValueError("the %r column: the summary's keys are 0 .. %d, not %d" % (key[0], summary_keys - 1, k))
+            C.update(side=("n_created" if key[0] == "work_order" else "n_completed", int(k), 1, "i32"), integer=True)
+        else:
+            one = column_stats_request([col], None, ("last",), info_columns)      # (an unknown name is refused there)
+            if one["members"]:
+                C.update(member=one["members"][0], integer=one["members"][0][0] == 1)
+            else:
+                C.update(side=one["sides"][0] + ("f64",))
+        index[key] = len(columns)
+        columns.append(C)
+        return index[key]
+
+    def number(x, what, where):
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise ValueError("%s: %s must be a number, not %r" % (where, what, x))
+        if np.isnan(float(x)):
+            raise ValueError("%s: %s is NaN" % (where, what))
+        return float(x)
+
+    def bit_mask(x, where):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 0 < int(x) <= 0xFFFFFFFF:
+            raise ValueError("%s: needs 0 < mask < 2**32, not %r" % (where, x))
+        return int(x)
+
+    terms = []
+    for i, term in enumerate(reward):
+        where = "reward term %d %r" % (i, term)
+        if not isinstance(term, (tuple, list)) or len(term) < 2:
+            raise ValueError("%s: a term is (column, weight) or (column, weight, kind, ...)" % where)
+        term = tuple(term)
+        T = {"col": column(term[0]), "weight": number(term[1], "the weight", where), "kind": term[2] if len(term) > 2 else "value",
+             "ref": 0.0, "direction": 0, "limit": 0.0, "mask": 0}
+        kind, rest = T["kind"], term[3:]
+        if not isinstance(kind, str) or kind not in TASK_KINDS:
+            raise ValueError("%s: unknown kind %r: one of %r" % (where, kind, tuple(TASK_KINDS)))
+        if kind in ("value", "delta"):
+            if rest:
+                raise ValueError("%s: a %r term takes nothing behind its kind" % (where, kind))
+        elif kind in ("abs_err", "sq_err"):
+            if len(rest) != 1:
+                raise ValueError("%s: a %r term is (column, weight, %r, ref)" % (where, kind, kind))
+            T["ref"] = ("col", column(rest[0])) if isinstance(rest[0], (str, tuple, list)) else number(rest[0], "the ref", where)
+        elif kind in ("beyond", "excess"):
+            if len(rest) != 2 or rest[0] not in (">", "<"):
+                raise ValueError("%s: a %r term is (column, weight, %r, '>' | '<', limit)" % (where, kind, kind))
+            T["direction"], T["limit"] = (1 if rest[0] == ">" else -1), number(rest[1], "the limit", where)
+        else:
+            if len(rest) != 1:
+                raise ValueError("%s: a 'bits' term is (column, weight, 'bits', mask)" % where)
+            if not columns[T["col"]]["integer"]:
+                raise ValueError("%s: a 'bits' term needs an integer column" % where)
+            T["mask"] = bit_mask(rest[0], where)
+        terms.append(T)
+    rules = []
+    for i, rule in enumerate(terminate):
+        where = "termination rule %d %r" % (i, rule)
+        t = (rule,) if isinstance(rule, str) else tuple(rule)
+        R = {"col": None, "mode": None, "mask": 0, "direction": 0, "limit": 0.0, "terminal_reward": 0.0}
+        if len(t) in (2, 3) and isinstance(t[1], str) and t[1] == "nonfinite":
+            R.update(col=column(t[0]), mode="nonfinite")
+            tail = t[2:]
+        elif len(t) in (3, 4) and isinstance(t[1], str) and t[1] in (">", "<"):
+            R.update(col=column(t[0]), mode="beyond", direction=1 if t[1] == ">" else -1, limit=number(t[2], "the limit", where))
+            tail = t[3:]
+        elif len(t) in (2, 3) and t[0] == "trip":
+            R.update(col=column("flags"), mode="bits_any", mask=bit_mask(t[1], where))
+            tail = t[2:]
+        elif len(t) in (1, 2) and t[0] == "done":
+            R.update(col=column("done"), mode="bits_any", mask=0xFF)
+            tail = t[1:]
+        else:
+            raise ValueError("%s: a rule is ('done',), ('trip', mask), (column, '>' | '<', value) or (column, 'nonfinite'), each with an "
+                             "optional trailing terminal reward" % where)
+        if tail:
+            R["terminal_reward"] = number(tail[0], "the terminal reward", where)
+        rules.append(R)
+    return {"columns": columns, "terms": terms, "rules": rules, "bias": bias}
 
 
 def episode_streams_desc(block, bank_noise_seeds=None, bank_profile_seeds=None, outputs=(None, None, None)):
@@ -755,6 +926,14 @@ def load():
         L.npb_column_stats_fold.argtypes = [vp, vp]
         L.npb_column_stats_clear.argtypes = [vp, vp, vp]
         L.npb_set_episode_record_stats.argtypes = [vp, ctypes.POINTER(NpbEpisodeRecordStatsDesc)]
+    if hasattr(L, "npb_set_task"):     # the caller's reward terms and termination rules, formed behind every step
+        L.npb_set_task.argtypes = [vp, ctypes.POINTER(NpbTaskDesc)]
+        L.npb_task_check.argtypes = [ctypes.POINTER(NpbTaskDesc), ci]
+        L.npb_task_check.restype = ctypes.c_char_p
+        L.npb_task_clear.argtypes = [vp, vp, vp]
+        L.npb_task_get_state.argtypes = [vp, vp, vp, vp, vp]
+        L.npb_task_set_state.argtypes = [vp, vp, vp, vp, vp]
+        L.npb_set_episode_record_task.argtypes = [vp, vp]
     if hasattr(L, "npb_set_event_windows"):     # state windows around events, captured behind every step
         L.npb_set_event_windows.argtypes = [vp, ctypes.POINTER(NpbEventWindowsDesc)]
         L.npb_event_windows_check.argtypes = [ctypes.POINTER(NpbEventWindowsDesc), ci, ci]

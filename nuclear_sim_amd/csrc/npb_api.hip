@@ -78,6 +78,9 @@ struct NpbHandle {
   /* npb_set_event_windows: the columns, triggers, ring and bookkeeping on the device (ew.cols = the one allocation of ew_bytes; NULL =
    * off), the caller's record columns, and the npb_step calls since they were set */
   npb_event_windows_t ew; size_t ew_bytes; int ew_step;
+  /* npb_set_task: the terms, rules, previous samples and bookkeeping on the device (task.terms = the one allocation; NULL = off) and the
+   * caller's outputs; npb_set_episode_record_task: the record-side column that takes the cause word */
+  npb_task_t task; bool ert_on; int32_t *ert_cause;
   double *ramp_prev;   /* npb_profile_ramp: the previous setpoint of every plant ([pitch], NaN = none yet), allocated on first use */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
   std::vector<int> plan_key;
@@ -460,6 +463,7 @@ int npb_destroy(NpbHandle *h) {
   if (h->cs.cols) (void)hipFree((void *)h->cs.cols);
   if (h->ers_dev) (void)hipFree(h->ers_dev);
   if (h->ew.cols) (void)hipFree((void *)h->ew.cols);
+  if (h->task.terms) (void)hipFree((void *)h->task.terms);
   for (Sampler *sm : h->samplers) if (sm) { (void)hipFree(sm->dev); delete sm; }
   delete h;
   return NPB_OK;
@@ -1054,6 +1058,10 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
   else if (maint && h->params.mode != NPB_MODE_FULL)   /* a full-mode step kernel has run the rule itself, for the waves whose pump phase found something */
     h->K->maint(NPB_N(h), h->f64, h->maint_side, h->maint_counts, h->n_plants, (hipStream_t)stream);
   if (maint) summary_fold(h, (hipStream_t)stream);      /* the rule has appended this step's records: the summary is current when the call returns */
+  if (h->task.terms) {      /* the caller's reward and termination rule: everything below that deals with episodes reads the task's columns in place of the step's */
+    h->K->task(h->f64, NPB_N(h), &h->task, h->n_plants, h->ep_index, (hipStream_t)stream);
+    done = h->task.done; reward = h->task.reward;
+  }
   if (h->cs.cols)      /* the end-of-step state of the episode this step belonged to, before any restore */
     h->K->column_stats_fold(h->f64, NPB_N(h), &h->cs, h->n_plants, (hipStream_t)stream);
   if (h->ew.cols)      /* the same sample into every plant's ring, the triggers, the windows that are due -- or cut short by an episode that ends here */
@@ -1062,7 +1070,7 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
   if (h->er_on && h->autoreset)      /* the episodes that end on this step, recorded while everything still describes them; then their summary rows cleared */
     h->K->episode_records(h->n_plants, NPB_N(h), h->f64, done, reward, obs, trip_flags, counters_of(h), h->ep_start,
                           h->max_episode_steps, h->er_step++, &h->er, er_uses_summary(h) ? &h->summary : nullptr,
-                          h->ers_on ? h->ers_dev : nullptr, (hipStream_t)stream);
+                          (h->ers_on || h->ert_on) ? h->ers_dev : nullptr, (hipStream_t)stream);
   if (h->autoreset)   /* same stream, nothing read back, the maintenance cache kept per plant by the kernel itself */
     h->K->episode(h->params.mode, h->n_plants, NPB_N(h), h->f64, source_of(h, from_bank), done, reward, obs, counters_of(h),
                   h->ep_out_len, h->ep_out_ret, h->ep_out_truncated, h->ep_final_obs, h->max_episode_steps,
@@ -1466,11 +1474,11 @@ const char *npb_episode_records_check(const npb_episode_records_desc_t *D, int h
 }
 int npb_set_episode_records(NpbHandle *h, const npb_episode_records_desc_t *desc) {
   if (!h) return NPB_EINVAL;
-  if (!desc) { h->er_on = false; h->ers_on = false; return NPB_OK; }      /* (the record-side statistics go with the records) */
+  if (!desc) { h->er_on = false; h->ers_on = false; h->ert_on = false; return NPB_OK; }      /* (the record-side statistics and cause column go with the records) */
   if (const char *why = npb_episode_records_check(desc, h->autoreset ? 1 : 0, h->summary_on ? h->summary.n_keys : 0)) return fail(h, NPB_EINVAL, why);
   /* new record columns, perhaps of another capacity: the record-side statistics columns belonged to the old ones and are dropped with
    * them (npb_set_episode_record_stats again, behind this call, for the new ones) */
-  h->er = *desc; h->er_step = 0; h->er_on = true; h->ers_on = false;
+  h->er = *desc; h->er_step = 0; h->er_on = true; h->ers_on = false; h->ert_on = false;      /* (the cause column too: npb_set_episode_record_task again) */
   return NPB_OK;
 }
 
@@ -1698,9 +1706,29 @@ int npb_column_stats_clear(NpbHandle *h, const uint8_t *mask, void *stream) {
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
+/* what the records kernel reads beside its own descriptor -- the column statistics with their record-side columns, the task's cause column
+ * with its own -- into the handle's device copy (allocated on first use); synchronous: a records kernel in flight has finished */
+static int upload_record_side(NpbHandle *h, const char *who, const npb_episode_record_stats_desc_t *rs, int32_t *cause) {
+  if (!h->ers_dev) {
+    hipError_t e = hipMalloc((void **)&h->ers_dev, sizeof(npb_record_stats_t));
+    if (e != hipSuccess) { h->ers_dev = nullptr; return fail(h, NPB_ENOMEM, (std::string(who) + ": hipMalloc of the device copy failed").c_str(), e); }
+  }
+  npb_record_stats_t host = {};
+  if (rs) { host.st = h->cs; host.rs = *rs; }
+  if (cause) { host.task_cause = h->task.cause; host.cause = cause; }
+  NPB_HIP(h, hipMemcpy(h->ers_dev, &host, sizeof host, hipMemcpyHostToDevice));
+  return NPB_OK;
+}
 int npb_set_episode_record_stats(NpbHandle *h, const npb_episode_record_stats_desc_t *D) {
   if (!h) return NPB_EINVAL;
-  if (!D) { h->ers_on = false; return NPB_OK; }
+  if (!D) {
+    if (h->ers_on && h->ert_on) {      /* the cause column stays: the device copy without the statistics */
+      NPB_USE_DEVICE(h);
+      if (int rc = upload_record_side(h, "npb_set_episode_record_stats", nullptr, h->ert_cause)) return rc;
+    }
+    h->ers_on = false;
+    return NPB_OK;
+  }
   if (!h->er_on) return fail(h, NPB_EINVAL, "npb_set_episode_record_stats: no episode records (npb_set_episode_records first)");
   if (!h->cs.cols) return fail(h, NPB_EINVAL, "npb_set_episode_record_stats: no column statistics set (npb_set_column_stats first)");
   if (((uintptr_t)D->min & 7u) || ((uintptr_t)D->max & 7u) || ((uintptr_t)D->sum & 7u) || ((uintptr_t)D->sumsq & 7u) || ((uintptr_t)D->last & 7u) ||
@@ -1710,13 +1738,188 @@ int npb_set_episode_record_stats(NpbHandle *h, const npb_episode_record_stats_de
       (D->first_beyond && !h->cs.first_beyond) || (D->n_beyond && !h->cs.n_beyond))
     return fail(h, NPB_EINVAL, "npb_set_episode_record_stats: a record-side column for a statistic the handle does not keep (its table in npb_set_column_stats is NULL)");
   NPB_USE_DEVICE(h);
-  if (!h->ers_dev) {
-    hipError_t e = hipMalloc((void **)&h->ers_dev, sizeof(npb_record_stats_t));
-    if (e != hipSuccess) { h->ers_dev = nullptr; return fail(h, NPB_ENOMEM, "npb_set_episode_record_stats: hipMalloc of the device copy failed", e); }
-  }
-  const npb_record_stats_t host = {h->cs, *D};
-  NPB_HIP(h, hipMemcpy(h->ers_dev, &host, sizeof host, hipMemcpyHostToDevice));      /* (synchronous: a records kernel in flight has finished) */
+  if (int rc = upload_record_side(h, "npb_set_episode_record_stats", D, h->ert_on ? h->ert_cause : nullptr)) return rc;
   h->ers = *D; h->ers_on = true;
+  return NPB_OK;
+}
+
+/* ---- tasks (include/npb.h, npd_task.h) */
+static const char *task_column_refusal(const npb_task_column_t &C, bool *integer) {
+  if (C.from_source) {
+    const npb_sample_source_t &S = C.source;
+    if (!S.base) return "npb_set_task: a side source has a NULL base";
+    if (S.type < NPB_SAMPLE_F64 || S.type > NPB_SAMPLE_U8) return "npb_set_task: a side source has an unknown element type";
+    if (S.rows != 1) return "npb_set_task: a side source must have rows == 1 (one value per plant)";
+    if (S.plant_stride < 0) return "npb_set_task: a side source needs a plant stride >= 0";
+    *integer = S.type == NPB_SAMPLE_I32 || S.type == NPB_SAMPLE_U8;
+    return nullptr;
+  }
+  int col, sub, access;
+  if ((C.kind != NPB_KIND_F64 && C.kind != NPB_KIND_I32) || !locate(NPB_STORAGE_F64, C.kind, C.slot, &col, &sub, &access)) return "npb_set_task: bad field kind or slot";
+  *integer = C.kind == NPB_KIND_I32;
+  return nullptr;
+}
+const char *npb_task_check(const npb_task_desc_t *D, int n_plants) {
+  if (!D) return nullptr;
+  if (n_plants < 1) return "npb_set_task: n_plants must be >= 1";
+  if (D->n_terms < 0 || D->n_terms > NPB_TASK_TERMS_MAX || (D->n_terms > 0 && !D->terms))
+    return "npb_set_task: the term count must be 0 .. NPB_TASK_TERMS_MAX (16), with their descriptors";
+  if (D->n_rules < 0 || D->n_rules > NPB_TASK_RULES_MAX || (D->n_rules > 0 && !D->rules))
+    return "npb_set_task: the rule count must be 0 .. NPB_TASK_RULES_MAX (8), with their descriptors";
+  if (D->n_terms + D->n_rules == 0) return "npb_set_task: a task with neither reward terms nor termination rules";
+  if (D->bias != D->bias) return "npb_set_task: a NaN bias";
+  for (int t = 0; t < D->n_terms; t++) {
+    const npb_task_term_t &T = D->terms[t];
+    bool integer = false, ref_integer = false;
+    if (const char *why = task_column_refusal(T.column, &integer)) return why;
+    if (T.kind < NPB_TASK_VALUE || T.kind > NPB_TASK_DELTA) return "npb_set_task: an unknown term kind";
+    if (T.weight != T.weight) return "npb_set_task: a NaN weight";
+    if (T.kind == NPB_TASK_ABS_ERR || T.kind == NPB_TASK_SQ_ERR) {
+      if (T.ref_from_column) { if (const char *why = task_column_refusal(T.ref_column, &ref_integer)) return why; }
+      else if (T.ref != T.ref) return "npb_set_task: a NaN ref";
+    } else if (T.kind == NPB_TASK_BEYOND || T.kind == NPB_TASK_EXCESS) {
+      if (T.direction != 1 && T.direction != -1) return "npb_set_task: a BEYOND or EXCESS term with a direction outside {-1, +1}";
+      if (T.limit != T.limit) return "npb_set_task: a NaN limit";
+    } else if (T.kind == NPB_TASK_BITS) {
+      if (!integer) return "npb_set_task: NPB_TASK_BITS on a real-valued column (it needs an int32 member, or an I32 or U8 source)";
+      if (T.mask == 0u) return "npb_set_task: NPB_TASK_BITS with mask 0";
+    }
+  }
+  for (int r = 0; r < D->n_rules; r++) {
+    const npb_task_rule_t &R = D->rules[r];
+    bool integer = false;
+    if (const char *why = task_column_refusal(R.column, &integer)) return why;
+    if (R.terminal_reward != R.terminal_reward) return "npb_set_task: a NaN terminal reward";
+    if (R.mode == NPB_TASK_RULE_MODE_BITS_ANY) {
+      if (!integer) return "npb_set_task: NPB_TASK_RULE_BITS_ANY on a real-valued column (it needs an int32 member, or an I32 or U8 source)";
+      if (R.mask == 0u) return "npb_set_task: NPB_TASK_RULE_BITS_ANY with mask 0";
+    } else if (R.mode == NPB_TASK_RULE_MODE_BEYOND) {
+      if (R.direction != 1 && R.direction != -1) return "npb_set_task: NPB_TASK_RULE_BEYOND with a direction outside {-1, +1}";
+      if (R.limit != R.limit) return "npb_set_task: a NaN limit";
+    } else if (R.mode != NPB_TASK_RULE_MODE_NONFINITE) {
+      return "npb_set_task: an unknown rule mode";
+    }
+  }
+  if (!D->reward || !D->done) return "npb_set_task: a NULL output: the reward and done columns are mandatory";
+  if (((uintptr_t)D->reward & 7u) || ((uintptr_t)D->terms_out & 7u) || ((uintptr_t)D->cause & 3u))
+    return "npb_set_task: a misaligned output: the double columns must be 8-byte, the cause column 4-byte aligned";
+  return nullptr;
+}
+/* a column as the kernel reads it, under the handle's storage type */
+static bool task_column(const NpbHandle *h, const npb_task_column_t &C, npb_colstat_col_t *O) {
+  if (C.from_source) { O->row = C.source.base; O->plant_stride = C.source.plant_stride; O->kind = 3 + C.source.type; return true; }
+  return locate(h->storage, C.kind, C.slot, &O->col, &O->sub, &O->kind);
+}
+int npb_set_task(NpbHandle *h, const npb_task_desc_t *desc) {
+  if (!h) return NPB_EINVAL;
+  if (h->ert_on)
+    return fail(h, NPB_EINVAL, "npb_set_task: episode records that copy the task's cause word are on (npb_set_episode_record_task) and hold its cause column; drop that first");
+  if (const char *why = npb_task_check(desc, h->n_plants)) return fail(h, NPB_EINVAL, why);
+  NPB_USE_DEVICE(h);
+  if (!desc) {
+    if (h->task.terms) (void)hipFree((void *)h->task.terms);      /* (hipFree waits for the device: a launch still in flight finishes first) */
+    h->task = npb_task_t{};
+    return NPB_OK;
+  }
+  /* the handle's one allocation: [the terms][the rules] | prev [n_delta][n] | primed [n] | seen [n]; every part 8-byte aligned */
+  struct { npb_task_term_col_t terms[NPB_TASK_TERMS_MAX]; npb_task_rule_col_t rules[NPB_TASK_RULES_MAX]; } table = {};
+  static_assert(sizeof table == NPB_TASK_TERMS_MAX * sizeof(npb_task_term_col_t) + NPB_TASK_RULES_MAX * sizeof(npb_task_rule_col_t) && sizeof table % 8 == 0, "packed");
+  int n_delta = 0;
+  for (int t = 0; t < desc->n_terms; t++) {
+    const npb_task_term_t &T = desc->terms[t];
+    npb_task_term_col_t &O = table.terms[t];
+    if (!task_column(h, T.column, &O.c)) return fail(h, NPB_EINVAL, "npb_set_task: bad field kind or slot");
+    O.w = T.weight; O.kind = T.kind; O.prev_row = -1;
+    if (T.kind == NPB_TASK_ABS_ERR || T.kind == NPB_TASK_SQ_ERR) {
+      if (T.ref_from_column) { O.ref_col = 1; if (!task_column(h, T.ref_column, &O.r)) return fail(h, NPB_EINVAL, "npb_set_task: bad field kind or slot"); }
+      else O.ref = T.ref;
+    } else if (T.kind == NPB_TASK_BEYOND || T.kind == NPB_TASK_EXCESS) { O.c.direction = T.direction; O.c.limit = T.limit; }
+    else if (T.kind == NPB_TASK_BITS) O.mask = T.mask;
+    else if (T.kind == NPB_TASK_DELTA) O.prev_row = n_delta++;
+  }
+  for (int r = 0; r < desc->n_rules; r++) {
+    const npb_task_rule_t &R = desc->rules[r];
+    npb_task_rule_col_t &O = table.rules[r];
+    if (!task_column(h, R.column, &O.c)) return fail(h, NPB_EINVAL, "npb_set_task: bad field kind or slot");
+    O.terminal = R.terminal_reward; O.mode = R.mode; O.mask = R.mask;
+    if (R.mode == NPB_TASK_RULE_MODE_BEYOND) { O.c.direction = R.direction; O.c.limit = R.limit; }
+  }
+  const size_t n = (size_t)h->n_plants, words = (2 * n * sizeof(int32_t) + 7) / 8 * 8;
+  const size_t bytes = sizeof table + (size_t)n_delta * n * sizeof(double) + words;
+  char *dev = nullptr;
+  hipError_t e = hipMalloc((void **)&dev, bytes);
+  if (e != hipSuccess) {
+    char what[160];
+    snprintf(what, sizeof what, "npb_set_task: hipMalloc of the tables and the previous samples (%zu bytes) failed", bytes);
+    return fail(h, NPB_EHIP, what, e);
+  }
+  npb_task_t T = {};
+  T.terms = (const npb_task_term_col_t *)dev; T.rules = (const npb_task_rule_col_t *)(dev + sizeof table.terms);
+  T.n_terms = desc->n_terms; T.n_rules = desc->n_rules; T.n_delta = n_delta; T.bias = desc->bias;
+  T.reward = desc->reward; T.done = desc->done; T.cause = desc->cause; T.terms_out = desc->terms_out;
+  T.prev = (double *)(dev + sizeof table);
+  T.primed = (int32_t *)(T.prev + (size_t)n_delta * n); T.seen = T.primed + n;
+  /* the tables up, everything else zero: every plant unprimed (the indices last seen too: a first sample that finds another index
+   * unprimes an unprimed plant); synchronous, so the host copies may go */
+  e = hipMemset(dev, 0, bytes);
+  if (e == hipSuccess) e = hipMemcpy(dev, &table, sizeof table, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess) { (void)hipFree(dev); return fail(h, NPB_EHIP, "npb_set_task: setting up the tables and the previous samples failed", e); }
+  if (h->task.terms) (void)hipFree((void *)h->task.terms);
+  h->task = T;
+  return NPB_OK;
+}
+int npb_task_clear(NpbHandle *h, const uint8_t *mask, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->task.terms) return fail(h, NPB_EINVAL, "npb_task_clear: no task set (npb_set_task first)");
+  NPB_USE_DEVICE(h);
+  npb_launch_task_clear(&h->task, mask, h->n_plants, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_task_get_state(NpbHandle *h, double *prev, int32_t *primed, int32_t *seen, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->task.terms) return fail(h, NPB_EINVAL, "npb_task_get_state: no task set (npb_set_task first)");
+  if (!primed || !seen || (h->task.n_delta > 0 && !prev)) return fail(h, NPB_EINVAL, "npb_task_get_state: NULL output (prev may be NULL only for a task without DELTA terms)");
+  NPB_USE_DEVICE(h);
+  const size_t n = (size_t)h->n_plants;
+  hipStream_t st = (hipStream_t)stream;
+  if (h->task.n_delta > 0) NPB_HIP(h, hipMemcpyAsync(prev, h->task.prev, (size_t)h->task.n_delta * n * sizeof(double), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpyAsync(primed, h->task.primed, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpyAsync(seen, h->task.seen, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipStreamSynchronize(st));
+  return NPB_OK;
+}
+int npb_task_set_state(NpbHandle *h, const double *prev, const int32_t *primed, const int32_t *seen, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->task.terms) return fail(h, NPB_EINVAL, "npb_task_set_state: no task set (npb_set_task first)");
+  if (!primed || !seen || (h->task.n_delta > 0 && !prev)) return fail(h, NPB_EINVAL, "npb_task_set_state: NULL input (prev may be NULL only for a task without DELTA terms)");
+  NPB_USE_DEVICE(h);
+  const size_t n = (size_t)h->n_plants;
+  hipStream_t st = (hipStream_t)stream;
+  if (h->task.n_delta > 0) NPB_HIP(h, hipMemcpyAsync(h->task.prev, prev, (size_t)h->task.n_delta * n * sizeof(double), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(h->task.primed, primed, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(h->task.seen, seen, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipStreamSynchronize(st));      /* the host arrays may go */
+  return NPB_OK;
+}
+int npb_set_episode_record_task(NpbHandle *h, int32_t *cause) {
+  if (!h) return NPB_EINVAL;
+  if (!cause) {
+    if (h->ert_on && h->ers_on) {      /* the statistics stay: the device copy without the cause column */
+      NPB_USE_DEVICE(h);
+      if (int rc = upload_record_side(h, "npb_set_episode_record_task", &h->ers, nullptr)) return rc;
+    }
+    h->ert_on = false; h->ert_cause = nullptr;
+    return NPB_OK;
+  }
+  if (!h->er_on) return fail(h, NPB_EINVAL, "npb_set_episode_record_task: no episode records (npb_set_episode_records first)");
+  if (!h->task.terms) return fail(h, NPB_EINVAL, "npb_set_episode_record_task: no task set (npb_set_task first)");
+  if (!h->task.cause) return fail(h, NPB_EINVAL, "npb_set_episode_record_task: the task keeps no cause column (its cause output in npb_set_task is NULL)");
+  if ((uintptr_t)cause & 3u) return fail(h, NPB_EINVAL, "npb_set_episode_record_task: the cause column must be 4-byte aligned");
+  NPB_USE_DEVICE(h);
+  if (int rc = upload_record_side(h, "npb_set_episode_record_task", h->ers_on ? &h->ers : nullptr, cause)) return rc;
+  h->ert_on = true; h->ert_cause = cause;
   return NPB_OK;
 }
 

@@ -52,7 +52,24 @@ typedef struct {
 } npb_column_stats_t;
 /* npb_set_episode_record_stats: what the records kernel needs of the statistics, kept in DEVICE memory by the handle and passed as one
  * pointer (NULL = off), so that the kernel's argument block, and with it the kernel without statistics, stays what it was */
-typedef struct { npb_column_stats_t st; npb_episode_record_stats_desc_t rs; } npb_record_stats_t;
+typedef struct {
+  npb_column_stats_t st; npb_episode_record_stats_desc_t rs;
+  /* npb_set_episode_record_task: the task's cause column [n_plants] and the record-side column [capacity] that takes it; NULL = not taken.
+   * Without npb_set_episode_record_stats st and rs are zero here: no column, no table, nothing cleared */
+  const uint32_t *task_cause; int32_t *cause;
+} npb_record_stats_t;
+/* npb_set_task (npd_task.h): one reward term and one termination rule as the kernel reads them.  c: the column (direction / limit: those of
+ * BEYOND and EXCESS); r: the second column of ABS_ERR / SQ_ERR where ref_col != 0, else `ref`; prev_row: the DELTA term's row of the
+ * previous-sample table, -1 for every other kind */
+typedef struct { npb_colstat_col_t c, r; double w, ref; int kind, ref_col; uint32_t mask; int prev_row; } npb_task_term_col_t;
+typedef struct { npb_colstat_col_t c; double terminal; int mode; uint32_t mask; } npb_task_rule_col_t;
+/* the handle's task: the terms and rules (device, one allocation with the state below; terms NULL = off), the caller's outputs, and the
+ * state the handle owns -- prev double [n_delta][n_plants], and per plant the primed flag and the episode index last seen */
+typedef struct {
+  const npb_task_term_col_t *terms; const npb_task_rule_col_t *rules; int n_terms, n_rules, n_delta; double bias;
+  double *reward; uint8_t *done; uint32_t *cause; double *terms_out;
+  double *prev; int32_t *primed, *seen;
+} npb_task_t;
 /* npb_set_event_windows (npd_event_windows.h): one trigger as the kernel reads it -- its column (direction / limit: those of
  * NPB_TRIGGER_MODE_BEYOND), the mode and the mask of NPB_TRIGGER_MODE_BITS_RISE */
 typedef struct { npb_colstat_col_t c; int mode; uint32_t mask; } npb_event_trigger_col_t;
@@ -127,6 +144,9 @@ typedef struct {
    * the carried lengths and the step's done column while the autoreset is on (the episode kernel's rule), else len NULL */
   void (*event_windows)(const void *arena, size_t npad, const npb_event_windows_t *W, int n_plants, int step, const int32_t *index,
                         const int32_t *len, const uint8_t *done, int max_steps, hipStream_t stream);
+  /* npb_set_task (npd_task.h): every plant's task reward, termination flag and cause word from the end-of-step state and the step's
+   * outputs; index: the handle's carried episode indices or NULL */
+  void (*task)(const void *arena, size_t npad, const npb_task_t *T, int n_plants, const int32_t *index, hipStream_t stream);
 } npb_launchers_t;
 extern npb_launchers_t npb_launch_table, npb32_launch_table;
 /* the same for either storage type */
@@ -155,6 +175,8 @@ void npb_launch_maint_summary_clear(const npb_maint_summary_desc_t *D, const uin
 void npb_launch_column_stats_clear(const npb_column_stats_t *S, const uint8_t *mask, int n_plants, hipStream_t stream);
 /* npb_event_windows_clear (npd_event_windows.h): the plants of mask (NULL = all) unprimed, their rings empty, an armed capture dropped */
 void npb_launch_event_windows_clear(const npb_event_windows_t *W, const uint8_t *mask, int n_plants, hipStream_t stream);
+/* npb_task_clear (npd_task.h): the plants of mask (NULL = all) unprimed */
+void npb_launch_task_clear(const npb_task_t *T, const uint8_t *mask, int n_plants, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -1607,12 +1607,14 @@ static void NPB_LAUNCHER(episode_records)(int n_plants, size_t npad, const void 
 static void NPB_LAUNCHER(column_stats_fold)(const void *arena, size_t npad, const npb_column_stats_t *S, int n_plants, hipStream_t stream);     /* the same */
 static void NPB_LAUNCHER(event_windows)(const void *arena, size_t npad, const npb_event_windows_t *W, int n_plants, int step, const int32_t *index,
                                         const int32_t *len, const uint8_t *done, int max_steps, hipStream_t stream);     /* the same */
+static void NPB_LAUNCHER(task)(const void *arena, size_t npad, const npb_task_t *T, int n_plants, const int32_t *index, hipStream_t stream);     /* the same */
 /* not const: clang emits a namespace-scope const into the device code too, where these host functions do not exist */
 extern "C" npb_launchers_t NPB_LAUNCHER(table) = {
   NPB_LAUNCHER(step), NPB_LAUNCHER(maint), NPB_LAUNCHER(observe), NPB_LAUNCHER(init), NPB_LAUNCHER(reset),
   NPB_LAUNCHER(field_get), NPB_LAUNCHER(field_set), NPB_LAUNCHER(gather), NPB_LAUNCHER(restore), NPB_LAUNCHER(episode),
   NPB_LAUNCHER(operator_maint), NPB_LAUNCHER(operator_component_maint), NPB_LAUNCHER(operator_turbine_maint), NPB_LAUNCHER(maint_all),
   NPB_LAUNCHER(sample), NPB_LAUNCHER(episode_records), NPB_LAUNCHER(column_stats_fold), NPB_LAUNCHER(event_windows),
+  NPB_LAUNCHER(task),
 };
 #ifndef NPB_BUILD_F32
 /* npb_reset / npb_reset_reference / npb_restore: the episode counters (len, ret) and the carried start entries (start: -1, not from
@@ -1788,6 +1790,7 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_episode_records_kernel(int n_pla
     }
   }
   if (!R.stats) return;
+  if (store && R.stats->cause) R.stats->cause[slot] = (int32_t)R.stats->task_cause[p];      /* why it ended: the task's cause word (npb_set_episode_record_task) */
   /* the plant's column statistics as of this step (their fold ran before this launch), then the empty values again (npd_column_stats.h) */
   const npb_column_stats_t st = R.stats->st;
   const npb_episode_record_stats_desc_t rs = R.stats->rs;
@@ -1829,3 +1832,6 @@ static void NPB_LAUNCHER(episode_records)(int n_plants, size_t npad, const void 
 
 /* state windows around events (npb_set_event_windows): the per-step kernel, the clear kernel and their launchers */
 #include "npd_event_windows.h"
+
+/* the caller's reward terms and termination rules (npb_set_task): the per-step kernel, the clear kernel and their launchers */
+#include "npd_task.h"

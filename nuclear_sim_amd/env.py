@@ -922,6 +922,26 @@ class BatchedPlantEnv:
                 raise
         self._erec = {"desc": d, "dev": dev, "host": host, "cursor": cursor, "host_cursor": torch.empty(1, dtype=torch.int32, pin_memory=True),
                       "capacity": cap, "n_keys": n_keys, "stats": rs, "stat_order": list(cst["order"]) if stats else None}
+        self._record_task_cause()
+
+    def _record_task_cause(self) -> None:
+        """while records and a task are both on every record carries the task's cause word (npb_set_episode_record_task); the handle drops
+        the column with every new set of record columns, so this follows ``enable_episode_records`` and ``set_task``"""
+        er = getattr(self, "_erec", None)
+        if er is None or getattr(self, "_task", None) is None:
+            return
+        if "cause" not in er["dev"]:
+            with torch.cuda.device(self.device):
+                er["dev"]["cause"] = torch.zeros(er["capacity"], dtype=torch.int32, device=self.device)      # (uint32 bits travel as int32)
+            er["host"]["cause"] = torch.empty(er["capacity"], dtype=torch.int32, pin_memory=True)
+        _lib.check(self.L.npb_set_episode_record_task(self._h, self._p(er["dev"]["cause"])), self._h)
+
+    def _drop_record_task_cause(self) -> None:
+        """the records without the cause column (the handle refuses another task, or none, while they hold the old one's)"""
+        er = getattr(self, "_erec", None)
+        if er is not None and "cause" in er["dev"]:
+            _lib.check(self.L.npb_set_episode_record_task(self._h, None), self._h)
+            del er["dev"]["cause"], er["host"]["cause"]
 
     def disable_episode_records(self) -> None:
         """episode records off; the buffers are released"""
@@ -933,7 +953,8 @@ class BatchedPlantEnv:
         (steps since the records were enabled, 0 = the first), ``ret``, ``end_time`` (plant minutes); with ``final_obs``
         ``final_observation`` [m, 22]; with ``summary`` ``first_created`` / ``first_completed`` (float64, +inf = never) and ``n_created`` /
         ``n_completed`` (int32), [m, n_keys]; with ``stats`` ``stat_min`` ... (the tables ``enable_column_stats`` keeps) [m, n_cols] and
-        ``stat_n_samples``.  An overflowed log raises, naming how many episodes were dropped, and is left as it is,
+        ``stat_n_samples``; while a task is set (``set_task``) ``cause`` (uint32: the rules that ended the episode, 0 = none did).  An
+        overflowed log raises, naming how many episodes were dropped, and is left as it is,
         unless ``allow_overflow`` (which of one step's episodes fitted is then not defined)."""
         er = getattr(self, "_erec", None)
         if er is None:
@@ -966,6 +987,8 @@ class BatchedPlantEnv:
         out["terminated"], out["truncated"] = (out["flags"] & 1) != 0, (out["flags"] & 2) != 0
         if "final_obs" in raw:
             out["final_observation"] = raw["final_obs"][order]
+        if "cause" in raw:
+            out["cause"] = np.ascontiguousarray(raw["cause"][order]).view(np.uint32)
         for name in ("first_created", "first_completed", "n_created", "n_completed"):
             if name in raw:
                 out[name] = np.ascontiguousarray(raw[name][order])
@@ -992,7 +1015,8 @@ class BatchedPlantEnv:
         """Have the device fold per-plant statistics of ``columns`` behind every step (npb_set_column_stats): one more launch, a thread per
         (column, plant), the sample being the end-of-step state of the episode the step belonged to, before any restore.  ``columns``: up
         to 32, each a state member as ``set_fields`` keys it (``name``, ``(name, instance)`` or ``(name, instance, k)``), ``("info",
-        column_name)``, ``("obs", i)`` or ``"reward"``.  ``limits``: ``{column_index: (">" | "<", value)}``; ``stats``: the tables to keep,
+        column_name)``, ``("obs", i)``, ``"reward"`` or, while a task is set (``set_task``), ``"task_reward"``.  ``limits``:
+        ``{column_index: (">" | "<", value)}``; ``stats``: the tables to keep,
         of "min", "max", "sum", "sumsq", "last" and, for columns with a limit, "first_beyond" (the plant clock after the first step whose
         sample was beyond the limit, +inf = never) and "n_beyond" (samples beyond it).  ``nuclear_sim_amd.colstats.fold`` is the same in
         numpy, bit for bit.  ``None`` for ``columns`` turns it off.  Output only, like the maintenance summary: ``snapshot``, ``restore``,
@@ -1006,7 +1030,8 @@ class BatchedPlantEnv:
                 _lib.check(self.L.npb_set_column_stats(self._h, None), self._h)
             self._cstats = None
             return
-        req = _lib.column_stats_request(columns, limits, stats, INFO_COLUMNS)      # an unknown name, index or statistic is refused here
+        tk = getattr(self, "_task", None)
+        req = _lib.column_stats_request(columns, limits, stats, INFO_COLUMNS, tk is not None)      # an unknown name, index or statistic is refused here
         if not hasattr(self.L, "npb_set_column_stats"):
             raise _lib.NpbError("libnpb.so has no npb_set_column_stats: rebuild")
         nm, ns = len(req["members"]), len(req["sides"])
@@ -1016,6 +1041,8 @@ class BatchedPlantEnv:
         slots = (ctypes.c_int * max(nm, 1))(*[m[1] for m in req["members"]])
         side = (_lib.NpbSampleSource * max(ns, 1))()
         buffers = {"info": self._info_buf, "obs": self._obs, "reward": self._reward}
+        if tk is not None:
+            buffers["task_reward"] = tk["reward"]
         for k, (name, offset, stride) in enumerate(req["sides"]):
             side[k].base = buffers[name].data_ptr() + 8 * offset; side[k].type = _lib.SAMPLE_TYPES["f64"]; side[k].rows = 1
             side[k].row_stride = 0; side[k].plant_stride = stride
@@ -1031,7 +1058,8 @@ class BatchedPlantEnv:
             tables["n_samples"] = torch.zeros(self.n, dtype=torch.int32, device=self.device)
         d.n_samples = tables["n_samples"].data_ptr()
         _lib.check(self.L.npb_set_column_stats(self._h, ctypes.byref(d)), self._h)
-        self._cstats = {"tables": tables, "stats": req["stats"], "order": req["order"], "columns": list(columns)}
+        self._cstats = {"tables": tables, "stats": req["stats"], "order": req["order"], "columns": list(columns),
+                        "task": any(side[0] == "task_reward" for side in req["sides"])}
 
     def column_stats(self) -> Dict[str, torch.Tensor]:
         """The statistics' tables, [n_cols, n] each in the order of ``columns``, and ``n_samples`` [n], on the device, never synchronised
@@ -1064,8 +1092,9 @@ class BatchedPlantEnv:
         whenever the caller chooses.  One more launch behind every step, nothing read back.  ``columns``: 1 to 16, keyed as
         ``enable_column_stats`` keys them.  ``triggers``: 1 to 8, each ``("trip", mask)`` (rising bits of the step's trip flags),
         ``("done",)``, ``("work_order", key_index)`` / ``("completed", key_index)`` (a new work order / completion under that key of
-        ``enable_maintenance_summary``, which must be on), ``("maintenance",)`` (the event count goes up) or ``(column, ">" | "<",
-        value)`` (the edge of a limit).  ``capacity`` records are allocated (None = ``max(n, 4096)``); captures past them are counted,
+        ``enable_maintenance_summary``, which must be on), ``("maintenance",)`` (the event count goes up), ``(column, ">" | "<",
+        value)`` (the edge of a limit) or, while a task is set (``set_task``), ``("task", mask)`` (rising bits of the task's cause column;
+        ``"task_reward"`` is then a column too).  ``capacity`` records are allocated (None = ``max(n, 4096)``); captures past them are counted,
         not written, until the next drain.  A capture whose episode ends before ``post`` more steps is taken at once (``early``); a
         restart (autoreset, ``restore``, ``reset``; without autoreset ``clear_event_windows(mask)``) empties the plant's ring and drops an
         armed capture.  ``nuclear_sim_amd.eventwin.record`` is the same in numpy, bit for bit.  ``None`` for ``columns`` turns it off.
@@ -1077,7 +1106,8 @@ class BatchedPlantEnv:
             self._ewin = None
             return
         ms = getattr(self, "_msum", None)
-        req = _lib.event_windows_request(columns, triggers or (), pre, post, INFO_COLUMNS, 0 if ms is None else len(ms["keys"]))
+        tk = getattr(self, "_task", None)
+        req = _lib.event_windows_request(columns, triggers or (), pre, post, INFO_COLUMNS, 0 if ms is None else len(ms["keys"]), tk is not None)
         if not hasattr(self.L, "npb_set_event_windows"):
             raise _lib.NpbError("libnpb.so has no npb_set_event_windows: rebuild")
         cap = max(self.n, 4096) if capacity is None else int(capacity)
@@ -1092,6 +1122,8 @@ class BatchedPlantEnv:
         buffers = {"info": self._info_buf, "obs": self._obs, "reward": self._reward, "flags": self._flags, "done": self._done}
         if ms is not None:
             buffers.update(n_created=ms["counts"][0], n_completed=ms["counts"][1])
+        if tk is not None:
+            buffers.update(task_reward=tk["reward"], task_cause=tk["cause"])
         width = {"f64": 8, "i32": 4, "u8": 1}
 
         def source(S, name, offset, stride, kind="f64"):
@@ -1125,7 +1157,9 @@ class BatchedPlantEnv:
                       "host_cursor": torch.empty(1, dtype=torch.int32, pin_memory=True), "capacity": cap, "order": req["order"],
                       "columns": list(columns), "pre": req["pre"], "post": req["post"], "triggers": req["numpy"],
                       "bytes": int(self.L.npb_event_windows_bytes(ctypes.byref(d), self.n)),
-                      "summary": ms["counts"] if any(T["side"] and T["side"][0] in ("n_created", "n_completed") for T in req["triggers"]) else None}
+                      "summary": ms["counts"] if any(T["side"] and T["side"][0] in ("n_created", "n_completed") for T in req["triggers"]) else None,
+                      "task": any(side[0] == "task_reward" for side in req["sides"]) or
+                              any(T["side"] and T["side"][0] in ("task_reward", "task_cause") for T in req["triggers"])}
 
     def event_windows(self, clear: bool = True, allow_overflow: bool = False) -> Dict[str, np.ndarray]:
         """Drain the event windows on the env's stream, one read-back: numpy columns of m records sorted by (capture step, plant) --
@@ -1182,6 +1216,158 @@ class BatchedPlantEnv:
             raise _lib.NpbError("no event windows: enable_event_windows() first")
         m = None if mask is None else self._col(mask, torch.uint8)
         _lib.check(self.L.npb_event_windows_clear(self._h, None if m is None else self._p(m), self._stream()), self._h)
+
+    def _task_buffers(self):
+        """the env's buffers a task's side columns point into, by the names ``_lib.task_request`` gives them"""
+        buffers = {"info": self._info_buf, "obs": self._obs, "reward": self._reward, "flags": self._flags, "done": self._done}
+        ms = getattr(self, "_msum", None)
+        if ms is not None:
+            buffers.update(n_created=ms["counts"][0], n_completed=ms["counts"][1])
+        return buffers
+
+    def _task_readers(self):
+        """what reads the task's output columns: (name, settings) of the column statistics and the event windows that do"""
+        return [(what, user) for what, user in (("column statistics", getattr(self, "_cstats", None)), ("event windows", getattr(self, "_ewin", None)))
+                if user is not None and user.get("task")]
+
+    def set_task(self, reward=(), terminate=(), bias: float = 0.0, keep_terms: bool = False) -> None:
+        """Define the reward and the termination rule on the device (npb_set_task): behind every step one more launch forms a per-plant
+        task reward, a termination flag and a cause word from the end-of-step state and the step's outputs, and everything that deals
+        with episodes -- the same-step autoreset, ``info["episode_return"]``, the episode records, the event windows' ``early`` captures
+        -- uses them in place of the reference's reward and scram pulse.  Nothing is read back.
+        ``reward``: 0 to 16 terms, ``(column, weight)`` or ``(column, weight, kind, ...)`` with kind ``"value"``, ``"abs_err", ref``,
+        ``"sq_err", ref`` (ref a number or a second column), ``"beyond", ">" | "<", limit``, ``"excess", ">" | "<", limit``, ``"bits",
+        mask`` (an integer column) or ``"delta"`` (this sample minus the plant's previous one; 0 on the first sample of an episode): the
+        reward is ``bias + w_0 * f_0 + w_1 * f_1 + ...``.  Columns are keyed as ``enable_column_stats`` keys them (``"reward"`` is the
+        step's own reward, so "the reference's reward plus extras" is one ``("reward", 1.0)`` term), or are one of the integer sides
+        ``"flags"``, ``"done"``, ``("work_order", key_index)`` / ``("completed", key_index)`` (``enable_maintenance_summary`` first, and
+        it must then stay as it is) and ``"maintenance"`` (the event count).
+        ``terminate``: 0 to 8 rules, ``("done",)`` (the reference's scram pulse), ``("trip", mask)``, ``(column, ">" | "<", value)`` or
+        ``(column, "nonfinite")``, each with an optional trailing terminal reward, added when the rule fires.  Rules are levels: with
+        autoreset the plant restarts on that step; without it a level keeps reporting for as long as it holds.  A task without
+        ``("done",)`` no longer ends episodes on a scram.
+        With a task on ``step()`` returns the task's reward and done, and adds ``info["reference_reward"]``, ``info["task_cause"]``
+        (uint32 bits as int32: bit r = rule r fired) and, with ``keep_terms``, ``info["task_terms"]`` [n_terms, n] (each term's w * f);
+        ``info["scram_activated"]`` stays the step's column.  ``episode_records()`` gains ``cause``.  ``nuclear_sim_amd.task.evaluate``
+        is the same in numpy, bit for bit.  ``set_task(None)`` turns it off; while column statistics or event windows read
+        ``"task_reward"`` / ``("task", mask)`` that, and a new task, are refused: turn them off first."""
+        old = getattr(self, "_task", None)
+        if reward is None and not terminate:
+            if old is None:
+                return
+            for what, _user in self._task_readers():
+                raise _lib.NpbError("set_task(None): the %s read 'task_reward' / ('task', mask): turn them off first" % what)
+            self._drop_record_task_cause()
+            _lib.check(self.L.npb_set_task(self._h, None), self._h)
+            self._task = None
+            return
+        ms = getattr(self, "_msum", None)
+        req = _lib.task_request(reward, terminate, bias, INFO_COLUMNS, 0 if ms is None else len(ms["keys"]))      # a bad word is refused here
+        if not hasattr(self.L, "npb_set_task"):
+            raise _lib.NpbError("libnpb.so has no npb_set_task: rebuild")
+        for what, _user in self._task_readers():      # (they hold the old task's output columns)
+            raise _lib.NpbError("set_task: the %s read 'task_reward' / ('task', mask) of the task that is set: turn them off first" % what)
+        buffers = self._task_buffers()
+        width = {"f64": 8, "i32": 4, "u8": 1}
+
+        def column(C, where):
+            if where["member"] is not None:
+                C.from_source, C.kind, C.slot = 0, where["member"][0], where["member"][1]
+                return
+            name, offset, stride, kind = where["side"]
+            rows = offset * self.n if name in ("n_created", "n_completed") else offset      # (a summary table is [n_keys][n])
+            C.from_source = 1
+            C.source.base = buffers[name].data_ptr() + width[kind] * rows; C.source.type = _lib.SAMPLE_TYPES[kind]; C.source.rows = 1
+            C.source.row_stride = 0; C.source.plant_stride = stride
+        nt, nr = len(req["terms"]), len(req["rules"])
+        terms, rules = (_lib.NpbTaskTerm * max(nt, 1))(), (_lib.NpbTaskRule * max(nr, 1))()
+        for k, T in enumerate(req["terms"]):
+            column(terms[k].column, req["columns"][T["col"]])
+            terms[k].weight, terms[k].kind = T["weight"], _lib.TASK_KINDS[T["kind"]]
+            if isinstance(T["ref"], tuple):
+                terms[k].ref_from_column = 1
+                column(terms[k].ref_column, req["columns"][T["ref"][1]])
+            else:
+                terms[k].ref = T["ref"]
+            terms[k].direction, terms[k].limit, terms[k].mask = T["direction"], T["limit"], T["mask"]
+        for k, R in enumerate(req["rules"]):
+            column(rules[k].column, req["columns"][R["col"]])
+            rules[k].mode, rules[k].mask, rules[k].direction, rules[k].limit = _lib.TASK_MODES[R["mode"]], R["mask"], R["direction"], R["limit"]
+            rules[k].terminal_reward = R["terminal_reward"]
+        d = _lib.NpbTaskDesc()
+        d.n_terms, d.terms, d.n_rules, d.rules, d.bias = nt, terms, nr, rules, req["bias"]
+        with torch.cuda.device(self.device):
+            out = {"reward": torch.zeros(self.n, dtype=torch.float64, device=self.device),
+                   "done": torch.zeros(self.n, dtype=torch.uint8, device=self.device),
+                   "cause": torch.zeros(self.n, dtype=torch.int32, device=self.device),      # a uint32 on the device
+                   "terms": torch.zeros((nt, self.n), dtype=torch.float64, device=self.device) if keep_terms and nt else None}
+        d.reward, d.done, d.cause = out["reward"].data_ptr(), out["done"].data_ptr(), out["cause"].data_ptr()
+        d.terms_out = None if out["terms"] is None else out["terms"].data_ptr()
+        self._drop_record_task_cause()
+        try:
+            _lib.check(self.L.npb_set_task(self._h, ctypes.byref(d)), self._h)
+        except _lib.NpbError:
+            self._record_task_cause()      # (what was set before stays, its cause column in the records too)
+            raise
+        self._task = dict(out, request=req, n_delta=sum(T["kind"] == "delta" for T in req["terms"]),
+                          summary=ms["counts"] if any(C["side"] and C["side"][0] in ("n_created", "n_completed") for C in req["columns"]) else None)
+        self._record_task_cause()
+
+    def task_spec(self) -> dict:
+        """the task as ``nuclear_sim_amd.task.evaluate`` takes it -- {"bias", "terms", "rules"} over the rows of ``task_samples()``"""
+        if getattr(self, "_task", None) is None:
+            raise _lib.NpbError("no task: set_task() first")
+        req = self._task["request"]
+        return {"bias": req["bias"], "terms": req["terms"], "rules": req["rules"]}
+
+    def task_samples(self) -> torch.Tensor:
+        """The columns the task reads as they are NOW, widened to float64, [n_cols, n] on the device (gather launches and copies: for
+        checks and debugging, not for the hot path).  Behind a ``step()`` without autoreset these are the samples the task was formed
+        from; a plant the autoreset restarted shows its start state."""
+        if getattr(self, "_task", None) is None:
+            raise _lib.NpbError("no task: set_task() first")
+        buffers = self._task_buffers()
+        rows = []
+        for C in self._task["request"]["columns"]:
+            if C["member"] is not None:
+                rows.append(self._get_slot("f64" if C["member"][0] == 0 else "i32", C["member"][1]).to(torch.float64))
+            else:
+                name, offset, stride, _kind = C["side"]
+                b = buffers[name]
+                rows.append((b.reshape(-1, self.n)[offset] if name in ("n_created", "n_completed") else b.reshape(-1)[offset::stride][:self.n]).to(torch.float64))
+        return torch.stack(rows)
+
+    def clear_task(self, mask=None) -> None:
+        """the masked plants (None = all) unprimed: their next ``"delta"`` samples are 0 (npb_task_clear) -- what a caller without
+        autoreset does for the plants it restarted"""
+        if getattr(self, "_task", None) is None:
+            raise _lib.NpbError("no task: set_task() first")
+        m = None if mask is None else self._col(mask, torch.uint8)
+        _lib.check(self.L.npb_task_clear(self._h, None if m is None else self._p(m), self._stream()), self._h)
+
+    def task_state(self) -> Dict[str, np.ndarray]:
+        """The task's own state for a checkpoint (npb_task_get_state), beside ``state_arrays()``: ``prev`` float64 [n_delta, n] (the
+        previous samples of the ``"delta"`` terms, in term order), ``primed`` and ``seen`` int32 [n] (the plant has a previous sample;
+        the episode index last seen)."""
+        if getattr(self, "_task", None) is None:
+            raise _lib.NpbError("no task: set_task() first")
+        nd = self._task["n_delta"]
+        out = {"prev": np.zeros((nd, self.n)), "primed": np.zeros(self.n, dtype=np.int32), "seen": np.zeros(self.n, dtype=np.int32)}
+        _lib.check(self.L.npb_task_get_state(self._h, out["prev"].ctypes.data if nd else None, out["primed"].ctypes.data, out["seen"].ctypes.data,
+                                             self._stream()), self._h)
+        return out
+
+    def load_task_state(self, state) -> None:
+        """put back what ``task_state()`` returned (npb_task_set_state): the task must be the one it was taken under"""
+        if getattr(self, "_task", None) is None:
+            raise _lib.NpbError("no task: set_task() first")
+        nd = self._task["n_delta"]
+        prev = np.ascontiguousarray(state["prev"], dtype=np.float64)
+        if prev.shape != (nd, self.n):
+            raise ValueError("task state: prev must be [%d, %d] (the task's 'delta' terms x plants), not %r" % (nd, self.n, prev.shape))
+        primed = np.ascontiguousarray(np.asarray(state["primed"], dtype=np.int32).reshape(self.n))
+        seen = np.ascontiguousarray(np.asarray(state["seen"], dtype=np.int32).reshape(self.n))
+        _lib.check(self.L.npb_task_set_state(self._h, prev.ctypes.data if nd else None, primed.ctypes.data, seen.ctypes.data, self._stream()), self._h)
 
     def _order_buffers(self):
         """the buffers the perform_*_maintenance methods keep for their order columns, with the ``success`` column they all return"""
@@ -1474,6 +1660,7 @@ class BatchedPlantEnv:
         self._erec = None      # the episode records' buffers go with the handle
         self._cstats = None
         self._ewin = None      # (the handle has freed the ring; the record columns go with it)
+        self._task = None
 
     def __del__(self):
         try:
@@ -1670,6 +1857,12 @@ class BatchedPlantEnv:
             info["reactivity_components"] = {name: self._rho[:, j] for j, name in enumerate(_lib.REACTIVITY_COMPONENTS)}
         info["trip_flags"] = self._flags
         info["scram_activated"] = self._done
+        task = getattr(self, "_task", None)
+        if task is not None:      # the caller's reward and termination rule, formed behind the step (set_task)
+            info["reference_reward"] = self._reward
+            info["task_cause"] = task["cause"]
+            if task["terms"] is not None:
+                info["task_terms"] = task["terms"]
         if target_power is not None:   # the power profile's row before the ramp: the runner's target_power for this step
             info["target_power"] = target_power
         if self.params.maint_enabled:  # bit-exact counterpart of AutoMaintenanceSystem.maintenance_actions_performed
@@ -1679,6 +1872,8 @@ class BatchedPlantEnv:
             info.update(self._episode)
             if self._bank is not None:    # the episode kernel's, restoring from the bank: the bank entry this transition's episode started from
                 info["episode_start"] = self._episode_start_out
+        if task is not None:
+            return self._obs, task["reward"], task["done"], info
         return self._obs, self._reward, self._done, info
 
 
