@@ -430,6 +430,71 @@ class NpbEpisodeRecordStatsDesc(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name in COLUMN_STATS + ("n_samples",)] + [("clear", ctypes.c_int)]
 
 
+def _bit_mask(x, who, through_int: bool = False) -> int:
+    """THE mask check of the bit triggers, terms and rules.  ``through_int``: the triggers pass their word through int() first (4.0 and True
+    are masks there), the task does not"""
+    mask = int(x) if through_int else x
+    if isinstance(mask, bool) or not isinstance(mask, (int, np.integer)) or not 0 < int(mask) <= 0xFFFFFFFF:
+        raise ValueError("%s needs 0 < mask < 2**32, not %r" % (who, x))
+    return int(mask)
+
+
+def _summary_side(word, k, summary_keys, what):
+    """THE check of ``("work_order" | "completed", key_index)``, and the side row it names: the summary's n_created / n_completed row of that
+    key.  ``what``: "trigger" or "column", for the message"""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError("the %r %s takes the index of a summary key, not %r" % (word, what, k))
+    if summary_keys < 1:
+        raise ValueError("the %r %s reads the maintenance summary: enable_maintenance_summary() first" % (word, what))
+    if not 0 <= k < summary_keys:
+        raise ValueError("the %r %s: the summary's keys are 0 .. %d, not %d" % (word, what, summary_keys - 1, k))
+    return ("n_created" if word == "work_order" else "n_completed", int(k), 1, "i32")
+
+
+def column_word(col, info_columns=None, task: bool = False, integer_sides: bool = False, summary_keys: int = 0) -> dict:
+    """THE resolver of a per-plant column word, for ``column_stats_request``, ``event_windows_request``, ``task_request`` and whoever reads
+    a column next; a pure function, an unknown word is refused (ValueError).  Every vocabulary has the state members as ``set_fields`` keys
+    them (``name``, ``(name, instance)`` or ``(name, instance, k)``), ``("info", column_name)``, ``("obs", i)`` and ``"reward"``.  ``task``:
+    a task is set, so ``"task_reward"`` is a word too (statistics and windows; a task's own columns never admit it).  ``integer_sides``:
+    the task's further words ``"flags"``, ``"done"``, ``"maintenance"`` and ``("work_order" | "completed", key_index)`` with ``summary_keys``
+    keys in the summary.  Returns {"member": (kind, slot) -- 0 f64 / 1 i32, as npb_gather_fields takes them -- or None, "side": (buffer,
+    element offset, plant stride, element type) over the buffers of ``BatchedPlantEnv._side_buffers`` or None, "integer": bool}."""
+    if info_columns is None:
+        from .env import INFO_COLUMNS as info_columns
+    key = (col,) if isinstance(col, str) else tuple(col)
+    member = side = None
+    if integer_sides and key in (("flags",), ("done",)):
+        side = (key[0], 0, 1, "i32" if key[0] == "flags" else "u8")
+    elif integer_sides and len(key) == 2 and key[0] in ("work_order", "completed"):
+        side = _summary_side(key[0], key[1], summary_keys, "column")
+    elif key == ("reward",):
+        side = ("reward", 0, 1, "f64")
+    elif key == ("task_reward",):
+        if not task:
+            raise ValueError("the column 'task_reward' needs a task: set_task() first")
+        side = ("task_reward", 0, 1, "f64")
+    elif key and key[0] == "info":
+        if len(key) != 2 or key[1] not in info_columns:
+            raise ValueError("unknown info column %r: one of %r" % (key[1:], tuple(info_columns)))
+        side = ("info", list(info_columns).index(key[1]), len(info_columns), "f64")
+    elif key and key[0] == "obs":
+        if len(key) != 2 or isinstance(key[1], bool) or not isinstance(key[1], (int, np.integer)) or not 0 <= key[1] < OBS_DIM:
+            raise ValueError("unknown obs column %r: ('obs', i) with 0 <= i < %d" % (key[1:], OBS_DIM))
+        side = ("obs", int(key[1]), OBS_DIM, "f64")
+    else:
+        if integer_sides and key == ("maintenance",):
+            key = ("maint.maintenance_actions_performed",)
+        if not key or not isinstance(key[0], str) or key[0] not in SCHEMA.by_name or len(key) > 3:
+            raise ValueError("unknown column %r: a state member (name, (name, instance) or (name, instance, k)), ('info', name), "
+                             "('obs', i) or 'reward'" % (col,))
+        try:
+            kind, slot = SCHEMA.slot(key[0], *[int(x) for x in key[1:]])
+        except IndexError:
+            raise ValueError("column %r: no such instance or element of %s" % (col, key[0])) from None
+        member = (0 if kind == "f64" else 1, slot)
+    return {"member": member, "side": side, "integer": member[0] == 1 if member else side[3] in ("i32", "u8")}
+
+
 def column_stats_request(columns, limits=None, stats=("min", "max", "sum", "sumsq", "last"), info_columns=None, task: bool = False) -> dict:
     """What ``BatchedPlantEnv.enable_column_stats`` asks of npb_set_column_stats, from the caller's words; a pure function, host only, so an
     unknown name, index or statistic is refused (ValueError) before any device work.  ``columns``: a state member as ``set_fields`` keys it
@@ -440,8 +505,6 @@ def column_stats_request(columns, limits=None, stats=("min", "max", "sum", "sums
     with buffer "info" | "obs" | "reward" (float64 device buffers of the env), "order": for every entry of ``columns`` its column on the
     device (members come first there, then the side rows), "direction" / "limit": lists per DEVICE column, "stats": the tables kept, in
     descriptor order}."""
-    if info_columns is None:
-        from .env import INFO_COLUMNS as info_columns
     columns = list(columns)
     if not 1 <= len(columns) <= COLUMN_STATS_MAX:
         raise ValueError("column statistics take 1 to %d columns, not %d" % (COLUMN_STATS_MAX, len(columns)))
@@ -451,30 +514,11 @@ def column_stats_request(columns, limits=None, stats=("min", "max", "sum", "sums
             raise ValueError("unknown statistic %r: one of %r" % (name, COLUMN_STATS))
     members, sides, where = [], [], []
     for col in columns:
-        key = (col,) if isinstance(col, str) else tuple(col)
-        if key == ("reward",):
-            where.append(("side", len(sides))); sides.append(("reward", 0, 1))
-        elif key == ("task_reward",):
-            if not task:
-                raise ValueError("the column 'task_reward' needs a task: set_task() first")
-            where.append(("side", len(sides))); sides.append(("task_reward", 0, 1))
-        elif key and key[0] == "info":
-            if len(key) != 2 or key[1] not in info_columns:
-                raise ValueError("unknown info column %r: one of %r" % (key[1:], tuple(info_columns)))
-            where.append(("side", len(sides))); sides.append(("info", list(info_columns).index(key[1]), len(info_columns)))
-        elif key and key[0] == "obs":
-            if len(key) != 2 or isinstance(key[1], bool) or not isinstance(key[1], (int, np.integer)) or not 0 <= key[1] < OBS_DIM:
-                raise ValueError("unknown obs column %r: ('obs', i) with 0 <= i < %d" % (key[1:], OBS_DIM))
-            where.append(("side", len(sides))); sides.append(("obs", int(key[1]), OBS_DIM))
+        C = column_word(col, info_columns, task)
+        if C["member"]:
+            where.append(("member", len(members))); members.append(C["member"])
         else:
-            if not key or not isinstance(key[0], str) or key[0] not in SCHEMA.by_name or len(key) > 3:
-                raise ValueError("unknown column %r: a state member (name, (name, instance) or (name, instance, k)), ('info', name), "
-                                 "('obs', i) or 'reward'" % (col,))
-            try:
-                kind, slot = SCHEMA.slot(key[0], *[int(x) for x in key[1:]])
-            except IndexError:
-                raise ValueError("column %r: no such instance or element of %s" % (col, key[0])) from None
-            where.append(("member", len(members))); members.append((0 if kind == "f64" else 1, slot))
+            where.append(("side", len(sides))); sides.append(C["side"][:3])      # (every side of this vocabulary is a float64 buffer)
     order = [i if kind == "member" else len(members) + i for kind, i in where]
     direction, limit = [0] * len(columns), [0.0] * len(columns)
     for c, lim in (limits or {}).items():
@@ -539,45 +583,30 @@ def event_windows_request(columns, triggers, pre, post, info_columns=None, summa
         t = (t,) if isinstance(t, str) else tuple(t)
         T = {"member": None, "side": None, "mode": "increase", "mask": 0, "direction": 0, "limit": 0.0}
         if len(t) == 2 and t[0] == "trip":
-            mask = int(t[1])
-            if not 0 < mask <= 0xFFFFFFFF:
-                raise ValueError("the ('trip', mask) trigger needs 0 < mask < 2**32, not %r" % (t[1],))
+            mask = _bit_mask(t[1], "the ('trip', mask) trigger", through_int=True)
             T.update(side=("flags", 0, 1, "i32"), mode="bits_rise", mask=mask)
             as_numpy.append(("bits", mask))
         elif len(t) == 2 and t[0] == "task":
-            mask = int(t[1])
+            int(t[1])      # (a mask that is no number is refused first, then the missing task, then the range: the order is kept)
             if not task:
                 raise ValueError("the ('task', mask) trigger needs a task: set_task() first")
-            if not 0 < mask <= 0xFFFFFFFF:
-                raise ValueError("the ('task', mask) trigger needs 0 < mask < 2**32, not %r" % (t[1],))
+            mask = _bit_mask(t[1], "the ('task', mask) trigger", through_int=True)
             T.update(side=("task_cause", 0, 1, "i32"), mode="bits_rise", mask=mask)
             as_numpy.append(("bits", mask))
         elif t == ("done",):
             T.update(side=("done", 0, 1, "u8"), mode="bits_rise", mask=1)
             as_numpy.append(("bits", 1))
         elif len(t) == 2 and t[0] in ("work_order", "completed"):
-            k = t[1]
-            if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
-                raise ValueError("the %r trigger takes the index of a summary key, not %r" % (t[0], k))
-            if summary_keys < 1:
-                raise ValueError("the %r trigger reads the maintenance summary: enable_maintenance_summary() first" % (t[0],))
-            if not 0 <= k < summary_keys:
-                raise ValueError("the %r trigger: the summary's keys are 0 .. %d, not %d" % (t[0], summary_keys - 1, k))
-            T.update(side=("n_created" if t[0] == "work_order" else "n_completed", int(k), 1, "i32"))
+            T.update(side=_summary_side(t[0], t[1], summary_keys, "trigger"))
             as_numpy.append(("increase",))
         elif t == ("maintenance",):
-            kind, slot = SCHEMA.slot("maint.maintenance_actions_performed")
-            T.update(member=(0 if kind == "f64" else 1, slot))
+            T.update(member=column_word("maintenance", info_columns, integer_sides=True)["member"])
             as_numpy.append(("increase",))
         elif len(t) == 3 and t[1] in (">", "<"):
             if np.isnan(float(t[2])):
                 raise ValueError("the limit of trigger %r is NaN" % (t,))
-            one = column_stats_request([t[0]], None, ("last",), info_columns, task)
-            if one["members"]:
-                T.update(member=one["members"][0])
-            else:
-                T.update(side=one["sides"][0] + ("f64",))
-            T.update(mode="beyond", direction=1 if t[1] == ">" else -1, limit=float(t[2]))
+            C = column_word(t[0], info_columns, task)
+            T.update(member=C["member"], side=C["side"], mode="beyond", direction=1 if t[1] == ">" else -1, limit=float(t[2]))
             as_numpy.append((t[1], float(t[2])))
         else:
             raise ValueError("unknown trigger %r: ('trip', mask), ('done',), ('work_order', key_index), ('completed', key_index), "
@@ -649,29 +678,7 @@ def task_request(reward=(), terminate=(), bias: float = 0.0, info_columns=None, 
         key = (col,) if isinstance(col, str) else tuple(col)
         if key in index:
             return index[key]
-        C = {"member": None, "side": None, "integer": False}
-        if key == ("flags",):
-            C.update(side=("flags", 0, 1, "i32"), integer=True)
-        elif key == ("done",):
-            C.update(side=("done", 0, 1, "u8"), integer=True)
-        elif key == ("maintenance",):
-            kind, slot = SCHEMA.slot("maint.maintenance_actions_performed")
-            C.update(member=(0 if kind == "f64" else 1, slot), integer=kind != "f64")
-        elif len(key) == 2 and key[0] in ("work_order", "completed"):
-            k = key[1]
-            if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
-                raise ValueError("the %r column takes the index of a summary key, not %r" % (key[0], k))
-            if summary_keys < 1:
-                raise ValueError("the %r column reads the maintenance summary: enable_maintenance_summary() first" % (key[0],))
-            if not 0 <= k < summary_keys:
-                raise ValueError("the %r column: the summary's keys are 0 .. %d, not %d" % (key[0], summary_keys - 1, k))
-            C.update(side=("n_created" if key[0] == "work_order" else "n_completed", int(k), 1, "i32"), integer=True)
-        else:
-            one = column_stats_request([col], None, ("last",), info_columns)      # (an unknown name is refused there)
-            if one["members"]:
-                C.update(member=one["members"][0], integer=one["members"][0][0] == 1)
-            else:
-                C.update(side=one["sides"][0] + ("f64",))
+        C = column_word(col, info_columns, integer_sides=True, summary_keys=summary_keys)      # (an unknown word is refused there)
         index[key] = len(columns)
         columns.append(C)
         return index[key]
@@ -682,11 +689,6 @@ def task_request(reward=(), terminate=(), bias: float = 0.0, info_columns=None, 
         if np.isnan(float(x)):
             raise ValueError("%s: %s is NaN" % (where, what))
         return float(x)
-
-    def bit_mask(x, where):
-        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 0 < int(x) <= 0xFFFFFFFF:
-            raise ValueError("%s: needs 0 < mask < 2**32, not %r" % (where, x))
-        return int(x)
 
     terms = []
     for i, term in enumerate(reward):
@@ -715,7 +717,7 @@ def task_request(reward=(), terminate=(), bias: float = 0.0, info_columns=None, 
                 raise ValueError("%s: a 'bits' term is (column, weight, 'bits', mask)" % where)
             if not columns[T["col"]]["integer"]:
                 raise ValueError("%s: a 'bits' term needs an integer column" % where)
-            T["mask"] = bit_mask(rest[0], where)
+            T["mask"] = _bit_mask(rest[0], where + ":")
         terms.append(T)
     rules = []
     for i, rule in enumerate(terminate):
@@ -729,7 +731,7 @@ def task_request(reward=(), terminate=(), bias: float = 0.0, info_columns=None, 
             R.update(col=column(t[0]), mode="beyond", direction=1 if t[1] == ">" else -1, limit=number(t[2], "the limit", where))
             tail = t[3:]
         elif len(t) in (2, 3) and t[0] == "trip":
-            R.update(col=column("flags"), mode="bits_any", mask=bit_mask(t[1], where))
+            R.update(col=column("flags"), mode="bits_any", mask=_bit_mask(t[1], where + ":"))
             tail = t[2:]
         elif len(t) in (1, 2) and t[0] == "done":
             R.update(col=column("done"), mode="bits_any", mask=0xFF)

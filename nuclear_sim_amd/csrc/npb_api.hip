@@ -304,6 +304,53 @@ static void probe_placement(NpbHandle *h, size_t step_columns) {
   (void)hipEventDestroy(a); (void)hipEventDestroy(b);
 }
 
+/* ---- a per-plant column: THE host-side definition for the column statistics, the event windows and the task (and whoever reads a column
+ * next): one view of the descriptor's three spellings, one refusal, one translation into what npd_column_read reads (npb_kernels.hip) */
+struct column_view { int kind, slot; const npb_sample_source_t *source; };      /* the arena member (kind, slot), or source != NULL: the caller's side source */
+static column_view column_of(int kind, int slot) { return column_view{kind, slot, nullptr}; }
+static column_view column_of(const npb_sample_source_t &S) { return column_view{0, 0, &S}; }
+/* the {from_source, kind, slot, source} head that npb_event_trigger_t and npb_task_column_t share */
+template <class Head> static column_view column_of(const Head &C) { return C.from_source ? column_of(C.source) : column_of(C.kind, C.slot); }
+/* column c of a descriptor that lists kinds[] / slots[] and then sources[] (npb_column_stats_desc_t, npb_event_windows_desc_t) */
+template <class Desc> static column_view column_of(const Desc *D, int c) {
+  return c < D->n_fields ? column_of(D->kinds[c], D->slots[c]) : column_of(D->sources[c - D->n_fields]);
+}
+/* the five refusals under an entry point's own prefix: static strings, since the *_check functions hand them out without a handle */
+enum { COLUMN_BAD_FIELD, COLUMN_NULL_BASE, COLUMN_BAD_TYPE, COLUMN_ROWS, COLUMN_STRIDE, COLUMN_REFUSALS_COUNT };
+#define COLUMN_REFUSALS(who) { who ": bad field kind or slot", who ": a side source has a NULL base", who ": a side source has an unknown element type", \
+                               who ": a side source must have rows == 1 (one value per plant)", who ": a side source needs a plant stride >= 0" }
+static const char *const g_cs_column[COLUMN_REFUSALS_COUNT] = COLUMN_REFUSALS("npb_set_column_stats");
+static const char *const g_ew_column[COLUMN_REFUSALS_COUNT] = COLUMN_REFUSALS("npb_set_event_windows");
+static const char *const g_task_column[COLUMN_REFUSALS_COUNT] = COLUMN_REFUSALS("npb_set_task");
+/* why a column is refused (who: the caller's table above), or NULL; integer (may be NULL): whether its values are integers, which bit masks need */
+static const char *column_refusal(const char *const *who, column_view C, bool *integer) {
+  bool is_integer;
+  if (C.source) {
+    const npb_sample_source_t &S = *C.source;
+    if (!S.base) return who[COLUMN_NULL_BASE];
+    if (S.type < NPB_SAMPLE_F64 || S.type > NPB_SAMPLE_U8) return who[COLUMN_BAD_TYPE];
+    if (S.rows != 1) return who[COLUMN_ROWS];
+    if (S.plant_stride < 0) return who[COLUMN_STRIDE];
+    is_integer = S.type == NPB_SAMPLE_I32 || S.type == NPB_SAMPLE_U8;
+  } else {
+    int col, sub, access;
+    if ((C.kind != NPB_KIND_F64 && C.kind != NPB_KIND_I32) || !locate(NPB_STORAGE_F64, C.kind, C.slot, &col, &sub, &access)) return who[COLUMN_BAD_FIELD];
+    is_integer = C.kind == NPB_KIND_I32;
+  }
+  if (integer) *integer = is_integer;
+  return nullptr;
+}
+/* the column as the kernels read it, under the handle's storage type (direction / limit stay the caller's); false: no such member */
+static bool column_build(const NpbHandle *h, column_view C, npb_colstat_col_t *O) {
+  if (C.source) { O->row = C.source->base; O->plant_stride = C.source->plant_stride; O->kind = 3 + C.source->type; return true; }
+  return locate(h->storage, C.kind, C.slot, &O->col, &O->sub, &O->kind);
+}
+/* the eight statistics tables of npb_column_stats_desc_t and npb_episode_record_stats_desc_t: doubles 8-byte, int32 4-byte aligned */
+template <class Tables> static bool stat_tables_misaligned(const Tables *D) {
+  return ((uintptr_t)D->min & 7u) || ((uintptr_t)D->max & 7u) || ((uintptr_t)D->sum & 7u) || ((uintptr_t)D->sumsq & 7u) || ((uintptr_t)D->last & 7u) ||
+         ((uintptr_t)D->first_beyond & 7u) || ((uintptr_t)D->n_beyond & 3u) || ((uintptr_t)D->n_samples & 3u);
+}
+
 extern "C" {
 
 int npb_version(void) { return NPB_VERSION; }
@@ -1483,13 +1530,6 @@ int npb_set_episode_records(NpbHandle *h, const npb_episode_records_desc_t *desc
 }
 
 /* ---- event windows (include/npb.h, npd_event_windows.h) */
-static const char *ew_source_refusal(const npb_sample_source_t &S) {
-  if (!S.base) return "npb_set_event_windows: a side source has a NULL base";
-  if (S.type < NPB_SAMPLE_F64 || S.type > NPB_SAMPLE_U8) return "npb_set_event_windows: a side source has an unknown element type";
-  if (S.rows != 1) return "npb_set_event_windows: a side source must have rows == 1 (one value per plant)";
-  if (S.plant_stride < 0) return "npb_set_event_windows: a side source needs a plant stride >= 0";
-  return nullptr;
-}
 const char *npb_event_windows_check(const npb_event_windows_desc_t *D, int n_plants, int has_autoreset) {
   (void)has_autoreset;
   if (!D) return nullptr;
@@ -1503,23 +1543,12 @@ const char *npb_event_windows_check(const npb_event_windows_desc_t *D, int n_pla
   if (D->capacity < 1) return "npb_set_event_windows: capacity must be >= 1";
   if ((D->n_fields > 0 && (!D->kinds || !D->slots)) || (D->n_sources > 0 && !D->sources))
     return "npb_set_event_windows: fields without kinds / slots, or side sources without their descriptors";
-  int col, sub, access;
-  for (int f = 0; f < D->n_fields; f++)
-    if ((D->kinds[f] != NPB_KIND_F64 && D->kinds[f] != NPB_KIND_I32) || !locate(NPB_STORAGE_F64, D->kinds[f], D->slots[f], &col, &sub, &access))
-      return "npb_set_event_windows: bad field kind or slot";
-  for (int k = 0; k < D->n_sources; k++)
-    if (const char *why = ew_source_refusal(D->sources[k])) return why;
+  for (int c = 0; c < D->n_fields + D->n_sources; c++)
+    if (const char *why = column_refusal(g_ew_column, column_of(D, c), nullptr)) return why;
   for (int t = 0; t < D->n_triggers; t++) {
     const npb_event_trigger_t &T = D->triggers[t];
-    bool integer;
-    if (T.from_source) {
-      if (const char *why = ew_source_refusal(T.source)) return why;
-      integer = T.source.type == NPB_SAMPLE_I32 || T.source.type == NPB_SAMPLE_U8;
-    } else {
-      if ((T.kind != NPB_KIND_F64 && T.kind != NPB_KIND_I32) || !locate(NPB_STORAGE_F64, T.kind, T.slot, &col, &sub, &access))
-        return "npb_set_event_windows: bad field kind or slot";
-      integer = T.kind == NPB_KIND_I32;
-    }
+    bool integer = false;
+    if (const char *why = column_refusal(g_ew_column, column_of(T), &integer)) return why;
     if (T.mode == NPB_TRIGGER_MODE_BITS_RISE) {
       if (!integer) return "npb_set_event_windows: NPB_TRIGGER_BITS_RISE on a real-valued column (it needs an int32 member, or an I32 or U8 source)";
       if (T.mask == 0u) return "npb_set_event_windows: NPB_TRIGGER_BITS_RISE with mask 0";
@@ -1564,20 +1593,12 @@ int npb_set_event_windows(NpbHandle *h, const npb_event_windows_desc_t *desc) {
   struct { npb_colstat_col_t cols[NPB_EVENT_WINDOW_COLS_MAX]; npb_event_trigger_col_t triggers[NPB_EVENT_WINDOW_TRIGGERS_MAX]; } table = {};
   static_assert(sizeof table == NPB_EVENT_WINDOW_COLS_MAX * sizeof(npb_colstat_col_t) + NPB_EVENT_WINDOW_TRIGGERS_MAX * sizeof(npb_event_trigger_col_t), "packed");
   const int n_cols = desc->n_fields + desc->n_sources;
-  for (int c = 0; c < n_cols; c++) {
-    npb_colstat_col_t &C = table.cols[c];
-    if (c < desc->n_fields) {
-      if (!locate(h->storage, desc->kinds[c], desc->slots[c], &C.col, &C.sub, &C.kind)) return fail(h, NPB_EINVAL, "npb_set_event_windows: bad field kind or slot");
-    } else {
-      const npb_sample_source_t &S = desc->sources[c - desc->n_fields];
-      C.row = S.base; C.plant_stride = S.plant_stride; C.kind = 3 + S.type;
-    }
-  }
+  for (int c = 0; c < n_cols; c++)
+    if (!column_build(h, column_of(desc, c), &table.cols[c])) return fail(h, NPB_EINVAL, g_ew_column[COLUMN_BAD_FIELD]);
   for (int t = 0; t < desc->n_triggers; t++) {
     const npb_event_trigger_t &T = desc->triggers[t];
     npb_event_trigger_col_t &O = table.triggers[t];
-    if (T.from_source) { O.c.row = T.source.base; O.c.plant_stride = T.source.plant_stride; O.c.kind = 3 + T.source.type; }
-    else if (!locate(h->storage, T.kind, T.slot, &O.c.col, &O.c.sub, &O.c.kind)) return fail(h, NPB_EINVAL, "npb_set_event_windows: bad field kind or slot");
+    if (!column_build(h, column_of(T), &O.c)) return fail(h, NPB_EINVAL, g_ew_column[COLUMN_BAD_FIELD]);
     O.mode = T.mode; O.mask = T.mask;
     if (T.mode == NPB_TRIGGER_MODE_BEYOND) { O.c.direction = T.direction; O.c.limit = T.limit; }
   }
@@ -1628,19 +1649,9 @@ const char *npb_column_stats_check(const npb_column_stats_desc_t *D, int n_plant
     return "npb_set_column_stats: the column count (n_fields + n_sources) must be 1 .. NPB_COLUMN_STATS_MAX (32)";
   if ((D->n_fields > 0 && (!D->kinds || !D->slots)) || (D->n_sources > 0 && !D->sources))
     return "npb_set_column_stats: fields without kinds / slots, or side sources without their descriptors";
-  for (int f = 0; f < D->n_fields; f++) {
-    int col, sub, access;
-    if ((D->kinds[f] != NPB_KIND_F64 && D->kinds[f] != NPB_KIND_I32) || !locate(NPB_STORAGE_F64, D->kinds[f], D->slots[f], &col, &sub, &access))
-      return "npb_set_column_stats: bad field kind or slot";
-  }
-  for (int k = 0; k < D->n_sources; k++) {
-    const npb_sample_source_t &S = D->sources[k];
-    if (!S.base) return "npb_set_column_stats: a side source has a NULL base";
-    if (S.type < NPB_SAMPLE_F64 || S.type > NPB_SAMPLE_U8) return "npb_set_column_stats: a side source has an unknown element type";
-    if (S.rows != 1) return "npb_set_column_stats: a side source must have rows == 1 (one value per plant)";
-    if (S.plant_stride < 0) return "npb_set_column_stats: a side source needs a plant stride >= 0";
-  }
   const int n_cols = D->n_fields + D->n_sources;
+  for (int c = 0; c < n_cols; c++)
+    if (const char *why = column_refusal(g_cs_column, column_of(D, c), nullptr)) return why;
   bool limited = false;
   for (int c = 0; D->direction && c < n_cols; c++) {
     if (D->direction[c] < -1 || D->direction[c] > 1) return "npb_set_column_stats: a direction outside {-1, 0, +1}";
@@ -1650,9 +1661,7 @@ const char *npb_column_stats_check(const npb_column_stats_desc_t *D, int n_plant
     }
   }
   if (!D->n_samples) return "npb_set_column_stats: n_samples must not be NULL";
-  if (((uintptr_t)D->min & 7u) || ((uintptr_t)D->max & 7u) || ((uintptr_t)D->sum & 7u) || ((uintptr_t)D->sumsq & 7u) || ((uintptr_t)D->last & 7u) ||
-      ((uintptr_t)D->first_beyond & 7u) || ((uintptr_t)D->n_beyond & 3u) || ((uintptr_t)D->n_samples & 3u))
-    return "npb_set_column_stats: a misaligned table: the double tables must be 8-byte, the int32 tables 4-byte aligned";
+  if (stat_tables_misaligned(D)) return "npb_set_column_stats: a misaligned table: the double tables must be 8-byte, the int32 tables 4-byte aligned";
   if ((D->first_beyond || D->n_beyond) && !limited) return "npb_set_column_stats: limit tables (first_beyond, n_beyond) without a limit on any column";
   return nullptr;
 }
@@ -1671,12 +1680,7 @@ int npb_set_column_stats(NpbHandle *h, const npb_column_stats_desc_t *desc) {
   npb_colstat_col_t cols[NPB_COLUMN_STATS_MAX] = {};
   for (int c = 0; c < n_cols; c++) {
     npb_colstat_col_t &C = cols[c];
-    if (c < desc->n_fields) {
-      if (!locate(h->storage, desc->kinds[c], desc->slots[c], &C.col, &C.sub, &C.kind)) return fail(h, NPB_EINVAL, "npb_set_column_stats: bad field kind or slot");
-    } else {
-      const npb_sample_source_t &S = desc->sources[c - desc->n_fields];
-      C.row = S.base; C.plant_stride = S.plant_stride; C.kind = 3 + S.type;
-    }
+    if (!column_build(h, column_of(desc, c), &C)) return fail(h, NPB_EINVAL, g_cs_column[COLUMN_BAD_FIELD]);
     C.direction = desc->direction ? desc->direction[c] : 0;
     C.limit = C.direction ? desc->limit[c] : 0.0;
   }
@@ -1731,9 +1735,7 @@ int npb_set_episode_record_stats(NpbHandle *h, const npb_episode_record_stats_de
   }
   if (!h->er_on) return fail(h, NPB_EINVAL, "npb_set_episode_record_stats: no episode records (npb_set_episode_records first)");
   if (!h->cs.cols) return fail(h, NPB_EINVAL, "npb_set_episode_record_stats: no column statistics set (npb_set_column_stats first)");
-  if (((uintptr_t)D->min & 7u) || ((uintptr_t)D->max & 7u) || ((uintptr_t)D->sum & 7u) || ((uintptr_t)D->sumsq & 7u) || ((uintptr_t)D->last & 7u) ||
-      ((uintptr_t)D->first_beyond & 7u) || ((uintptr_t)D->n_beyond & 3u) || ((uintptr_t)D->n_samples & 3u))
-    return fail(h, NPB_EINVAL, "npb_set_episode_record_stats: the double columns must be 8-byte, the int32 columns 4-byte aligned");
+  if (stat_tables_misaligned(D)) return fail(h, NPB_EINVAL, "npb_set_episode_record_stats: the double columns must be 8-byte, the int32 columns 4-byte aligned");
   if ((D->min && !h->cs.min) || (D->max && !h->cs.max) || (D->sum && !h->cs.sum) || (D->sumsq && !h->cs.sumsq) || (D->last && !h->cs.last) ||
       (D->first_beyond && !h->cs.first_beyond) || (D->n_beyond && !h->cs.n_beyond))
     return fail(h, NPB_EINVAL, "npb_set_episode_record_stats: a record-side column for a statistic the handle does not keep (its table in npb_set_column_stats is NULL)");
@@ -1744,21 +1746,6 @@ int npb_set_episode_record_stats(NpbHandle *h, const npb_episode_record_stats_de
 }
 
 /* ---- tasks (include/npb.h, npd_task.h) */
-static const char *task_column_refusal(const npb_task_column_t &C, bool *integer) {
-  if (C.from_source) {
-    const npb_sample_source_t &S = C.source;
-    if (!S.base) return "npb_set_task: a side source has a NULL base";
-    if (S.type < NPB_SAMPLE_F64 || S.type > NPB_SAMPLE_U8) return "npb_set_task: a side source has an unknown element type";
-    if (S.rows != 1) return "npb_set_task: a side source must have rows == 1 (one value per plant)";
-    if (S.plant_stride < 0) return "npb_set_task: a side source needs a plant stride >= 0";
-    *integer = S.type == NPB_SAMPLE_I32 || S.type == NPB_SAMPLE_U8;
-    return nullptr;
-  }
-  int col, sub, access;
-  if ((C.kind != NPB_KIND_F64 && C.kind != NPB_KIND_I32) || !locate(NPB_STORAGE_F64, C.kind, C.slot, &col, &sub, &access)) return "npb_set_task: bad field kind or slot";
-  *integer = C.kind == NPB_KIND_I32;
-  return nullptr;
-}
 const char *npb_task_check(const npb_task_desc_t *D, int n_plants) {
   if (!D) return nullptr;
   if (n_plants < 1) return "npb_set_task: n_plants must be >= 1";
@@ -1770,12 +1757,12 @@ const char *npb_task_check(const npb_task_desc_t *D, int n_plants) {
   if (D->bias != D->bias) return "npb_set_task: a NaN bias";
   for (int t = 0; t < D->n_terms; t++) {
     const npb_task_term_t &T = D->terms[t];
-    bool integer = false, ref_integer = false;
-    if (const char *why = task_column_refusal(T.column, &integer)) return why;
+    bool integer = false;
+    if (const char *why = column_refusal(g_task_column, column_of(T.column), &integer)) return why;
     if (T.kind < NPB_TASK_VALUE || T.kind > NPB_TASK_DELTA) return "npb_set_task: an unknown term kind";
     if (T.weight != T.weight) return "npb_set_task: a NaN weight";
     if (T.kind == NPB_TASK_ABS_ERR || T.kind == NPB_TASK_SQ_ERR) {
-      if (T.ref_from_column) { if (const char *why = task_column_refusal(T.ref_column, &ref_integer)) return why; }
+      if (T.ref_from_column) { if (const char *why = column_refusal(g_task_column, column_of(T.ref_column), nullptr)) return why; }
       else if (T.ref != T.ref) return "npb_set_task: a NaN ref";
     } else if (T.kind == NPB_TASK_BEYOND || T.kind == NPB_TASK_EXCESS) {
       if (T.direction != 1 && T.direction != -1) return "npb_set_task: a BEYOND or EXCESS term with a direction outside {-1, +1}";
@@ -1788,7 +1775,7 @@ const char *npb_task_check(const npb_task_desc_t *D, int n_plants) {
   for (int r = 0; r < D->n_rules; r++) {
     const npb_task_rule_t &R = D->rules[r];
     bool integer = false;
-    if (const char *why = task_column_refusal(R.column, &integer)) return why;
+    if (const char *why = column_refusal(g_task_column, column_of(R.column), &integer)) return why;
     if (R.terminal_reward != R.terminal_reward) return "npb_set_task: a NaN terminal reward";
     if (R.mode == NPB_TASK_RULE_MODE_BITS_ANY) {
       if (!integer) return "npb_set_task: NPB_TASK_RULE_BITS_ANY on a real-valued column (it needs an int32 member, or an I32 or U8 source)";
@@ -1804,11 +1791,6 @@ const char *npb_task_check(const npb_task_desc_t *D, int n_plants) {
   if (((uintptr_t)D->reward & 7u) || ((uintptr_t)D->terms_out & 7u) || ((uintptr_t)D->cause & 3u))
     return "npb_set_task: a misaligned output: the double columns must be 8-byte, the cause column 4-byte aligned";
   return nullptr;
-}
-/* a column as the kernel reads it, under the handle's storage type */
-static bool task_column(const NpbHandle *h, const npb_task_column_t &C, npb_colstat_col_t *O) {
-  if (C.from_source) { O->row = C.source.base; O->plant_stride = C.source.plant_stride; O->kind = 3 + C.source.type; return true; }
-  return locate(h->storage, C.kind, C.slot, &O->col, &O->sub, &O->kind);
 }
 int npb_set_task(NpbHandle *h, const npb_task_desc_t *desc) {
   if (!h) return NPB_EINVAL;
@@ -1828,10 +1810,10 @@ int npb_set_task(NpbHandle *h, const npb_task_desc_t *desc) {
   for (int t = 0; t < desc->n_terms; t++) {
     const npb_task_term_t &T = desc->terms[t];
     npb_task_term_col_t &O = table.terms[t];
-    if (!task_column(h, T.column, &O.c)) return fail(h, NPB_EINVAL, "npb_set_task: bad field kind or slot");
+    if (!column_build(h, column_of(T.column), &O.c)) return fail(h, NPB_EINVAL, g_task_column[COLUMN_BAD_FIELD]);
     O.w = T.weight; O.kind = T.kind; O.prev_row = -1;
     if (T.kind == NPB_TASK_ABS_ERR || T.kind == NPB_TASK_SQ_ERR) {
-      if (T.ref_from_column) { O.ref_col = 1; if (!task_column(h, T.ref_column, &O.r)) return fail(h, NPB_EINVAL, "npb_set_task: bad field kind or slot"); }
+      if (T.ref_from_column) { O.ref_col = 1; if (!column_build(h, column_of(T.ref_column), &O.r)) return fail(h, NPB_EINVAL, g_task_column[COLUMN_BAD_FIELD]); }
       else O.ref = T.ref;
     } else if (T.kind == NPB_TASK_BEYOND || T.kind == NPB_TASK_EXCESS) { O.c.direction = T.direction; O.c.limit = T.limit; }
     else if (T.kind == NPB_TASK_BITS) O.mask = T.mask;
@@ -1840,7 +1822,7 @@ int npb_set_task(NpbHandle *h, const npb_task_desc_t *desc) {
   for (int r = 0; r < desc->n_rules; r++) {
     const npb_task_rule_t &R = desc->rules[r];
     npb_task_rule_col_t &O = table.rules[r];
-    if (!task_column(h, R.column, &O.c)) return fail(h, NPB_EINVAL, "npb_set_task: bad field kind or slot");
+    if (!column_build(h, column_of(R.column), &O.c)) return fail(h, NPB_EINVAL, g_task_column[COLUMN_BAD_FIELD]);
     O.terminal = R.terminal_reward; O.mode = R.mode; O.mask = R.mask;
     if (R.mode == NPB_TASK_RULE_MODE_BEYOND) { O.c.direction = R.direction; O.c.limit = R.limit; }
   }

@@ -1712,6 +1712,26 @@ static void NPB_LAUNCHER(sample)(const void *arena, size_t npad, const int *plan
   hipLaunchKernelGGL(npb_sample_kernel, dim3((n_watched + block - 1) / block, n_rows), dim3(block), 0, stream, (const npd_real_t *)arena, npad, plan_dev,
                      n_fields, side_dev, ids_dev, out, n_watched);
 }
+/* THE reader of a per-plant column (npb_colstat_col_t, npb_kernels.h): one value of plant p, widened to double as npb_sample_kernel widens
+ * it.  f64 / N: the arena and its pitch AFTER NPD_SEGMENT (the fold applies it per thread, the windows and the task per wave: that stays
+ * with the kernels).  The call site names how the descriptor arrives, because this compiler's code depends on it: a copy of the fold's
+ * (D = npb_colstat_col_t) keeps its side-row loads global_load_*, where a reference makes them flat_load_* with lgkmcnt waits; a reference
+ * into the kernel's argument (D = const npb_colstat_col_t &) keeps the windows' and the task's loads where they are, where a copy
+ * reorders them (tools/compare_step_kernels.py shows either) */
+template <class D> __device__ __forceinline__ double npd_column_read(const npd_real_t *f64, size_t N, size_t p, D C) {
+  if (C.kind < 3) {
+    const char *e = (const char *)(f64 + (size_t)C.col * N + p);
+    if (C.kind == 0) return (double)*(const npd_real_t *)e;
+    if (C.kind == 1) return (double)*(const float *)(e + C.sub * 4);
+    return (double)*(const int32_t *)(e + C.sub * 4);
+  }
+  const int64_t e = (int64_t)p * C.plant_stride;
+  const int type = C.kind - 3;
+  if (type == NPB_SAMPLE_F64) return ((const double *)C.row)[e];
+  if (type == NPB_SAMPLE_F32) return (double)((const float *)C.row)[e];
+  if (type == NPB_SAMPLE_I32) return (double)((const int32_t *)C.row)[e];
+  return (double)((const uint8_t *)C.row)[e];
+}
 
 /* npb_set_episode_records: the record of every episode that ends on this step, behind the step kernel, the rule and the summary fold and
  * BEFORE the episode kernel, which then does the bookkeeping and the restore as it always does: here the arena, the step's output columns

@@ -24,20 +24,7 @@ __global__ __launch_bounds__(NPD_COLSTAT_BLOCK) void npb_column_stats_fold_kerne
   if (p >= (size_t)n_plants) return;
   const npb_colstat_col_t C = S.cols[c];
   NPD_SEGMENT(f64, N, p);
-  double v;
-  if (C.kind < 3) {
-    const char *e = (const char *)(f64 + (size_t)C.col * N + p);
-    if (C.kind == 0) v = (double)*(const npd_real_t *)e;
-    else if (C.kind == 1) v = (double)*(const float *)(e + C.sub * 4);
-    else v = (double)*(const int32_t *)(e + C.sub * 4);
-  } else {
-    const int64_t e = (int64_t)p * C.plant_stride;
-    const int type = C.kind - 3;
-    if (type == NPB_SAMPLE_F64) v = ((const double *)C.row)[e];
-    else if (type == NPB_SAMPLE_F32) v = (double)((const float *)C.row)[e];
-    else if (type == NPB_SAMPLE_I32) v = (double)((const int32_t *)C.row)[e];
-    else v = (double)((const uint8_t *)C.row)[e];
-  }
+  const double v = npd_column_read<npb_colstat_col_t>(f64, N, p, C);
   const size_t cell = (size_t)c * (size_t)n_plants + p;
   if (S.min && v < S.min[cell]) S.min[cell] = v;      /* (a NaN sample compares false: it replaces neither) */
   if (S.max && v > S.max[cell]) S.max[cell] = v;

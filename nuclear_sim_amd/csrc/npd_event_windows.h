@@ -16,22 +16,6 @@
 
 #define NPD_EVW_NAN __longlong_as_double(0x7ff8000000000000ll)
 
-/* one value of a column, widened to double as npb_sample_kernel widens it (f64 / N: the arena moved to the plant's segment) */
-__device__ __forceinline__ double npd_evw_read(const npd_real_t *f64, size_t N, size_t p, const npb_colstat_col_t &C) {
-  if (C.kind < 3) {
-    const char *e = (const char *)(f64 + (size_t)C.col * N + p);
-    if (C.kind == 0) return (double)*(const npd_real_t *)e;
-    if (C.kind == 1) return (double)*(const float *)(e + C.sub * 4);
-    return (double)*(const int32_t *)(e + C.sub * 4);
-  }
-  const int64_t e = (int64_t)p * C.plant_stride;
-  const int type = C.kind - 3;
-  if (type == NPB_SAMPLE_F64) return ((const double *)C.row)[e];
-  if (type == NPB_SAMPLE_F32) return (double)((const float *)C.row)[e];
-  if (type == NPB_SAMPLE_I32) return (double)((const int32_t *)C.row)[e];
-  return (double)((const uint8_t *)C.row)[e];
-}
-
 __global__ __launch_bounds__(NPB_WAVE) void npb_event_windows_kernel(const npd_real_t *__restrict__ f64, size_t N, npb_event_windows_t W, int n_plants,
                                                                      int step, const int32_t *__restrict__ index, const int32_t *__restrict__ len,
                                                                      const uint8_t *__restrict__ done, int max_steps) {
@@ -53,12 +37,12 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_event_windows_kernel(const npd_r
      * stores column by column pays it once per column.  Unrolled over the maxima with wave-uniform guards: the arrays stay in registers */
     double v[NPB_EVENT_WINDOW_COLS_MAX], tv[NPB_EVENT_WINDOW_TRIGGERS_MAX], pv[NPB_EVENT_WINDOW_TRIGGERS_MAX];
 #pragma unroll
-    for (int c = 0; c < NPB_EVENT_WINDOW_COLS_MAX; c++) v[c] = c < W.n_cols ? npd_evw_read(f64, N, p, W.cols[c]) : 0.0;
+    for (int c = 0; c < NPB_EVENT_WINDOW_COLS_MAX; c++) v[c] = c < W.n_cols ? npd_column_read<const npb_colstat_col_t &>(f64, N, p, W.cols[c]) : 0.0;
     const double clock = NPD_F64_COL(PRIM, npb_prim_t, sim_time, 0);
 #pragma unroll
     for (int t = 0; t < NPB_EVENT_WINDOW_TRIGGERS_MAX; t++) {
       tv[t] = pv[t] = 0.0;
-      if (t < W.n_triggers) { tv[t] = npd_evw_read(f64, N, p, W.triggers[t].c); pv[t] = W.prev[(size_t)t * n + p]; }
+      if (t < W.n_triggers) { tv[t] = npd_column_read<const npb_colstat_col_t &>(f64, N, p, W.triggers[t].c); pv[t] = W.prev[(size_t)t * n + p]; }
     }
     /* 2. the sample into ring row step % H */
     double *row = W.ring + (size_t)(step % H) * stride * n + p;

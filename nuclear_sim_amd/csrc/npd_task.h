@@ -29,13 +29,13 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_task_kernel(const npd_real_t *__
   for (int t = 0; t < NPB_TASK_TERMS_MAX; t++) {
     v[t] = ref[t] = pv[t] = 0.0;
     if (t < T.n_terms) {
-      v[t] = npd_evw_read(f64, N, p, T.terms[t].c);
-      ref[t] = T.terms[t].ref_col ? npd_evw_read(f64, N, p, T.terms[t].r) : T.terms[t].ref;
+      v[t] = npd_column_read<const npb_colstat_col_t &>(f64, N, p, T.terms[t].c);
+      ref[t] = T.terms[t].ref_col ? npd_column_read<const npb_colstat_col_t &>(f64, N, p, T.terms[t].r) : T.terms[t].ref;
       if (T.terms[t].prev_row >= 0) pv[t] = T.prev[(size_t)T.terms[t].prev_row * n + p];
     }
   }
 #pragma unroll
-  for (int r = 0; r < NPB_TASK_RULES_MAX; r++) rv[r] = r < T.n_rules ? npd_evw_read(f64, N, p, T.rules[r].c) : 0.0;
+  for (int r = 0; r < NPB_TASK_RULES_MAX; r++) rv[r] = r < T.n_rules ? npd_column_read<const npb_colstat_col_t &>(f64, N, p, T.rules[r].c) : 0.0;
   if (episode != seen) primed = 0;      /* restarted since the last sample (autoreset, npb_restore*, npb_reset*): the event windows' rule */
   /* 2. the terms: reward = bias + w_0 * f_0 + ..., sequentially, each product rounded before its add */
   double reward = T.bias, wf[NPB_TASK_TERMS_MAX];

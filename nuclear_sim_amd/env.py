@@ -1011,6 +1011,35 @@ class BatchedPlantEnv:
                 cols.update({"%s_%d" % (name, j): np.ascontiguousarray(a[:, j]) for j in range(a.shape[1])})
         maintlog.write(cols, path)
 
+    def _side_buffers(self) -> dict:
+        """THE buffers a per-plant column's side source may point into, by the names ``_lib.column_word`` gives them: the step's outputs,
+        the summary's two count tables while a summary is on, the task's reward and cause while a task is on.  Which of them a feature
+        accepts is decided by its vocabulary in ``_lib``, not by what is listed here"""
+        buffers = {"info": self._info_buf, "obs": self._obs, "reward": self._reward, "flags": self._flags, "done": self._done}
+        ms, tk = getattr(self, "_msum", None), getattr(self, "_task", None)
+        if ms is not None:
+            buffers.update(n_created=ms["counts"][0], n_completed=ms["counts"][1])
+        if tk is not None:
+            buffers.update(task_reward=tk["reward"], task_cause=tk["cause"])
+        return buffers
+
+    def _side_first(self, name, offset) -> int:
+        """the element of side buffer ``name`` that holds plant 0's value of the column at ``offset``: a summary table is [n_keys][n]"""
+        return offset * self.n if name in ("n_created", "n_completed") else offset
+
+    def _fill_source(self, S, buffers, name, offset, stride, kind="f64") -> None:
+        """fill the NpbSampleSource ``S`` from a side column as ``_lib.column_word`` names it: one value per plant"""
+        S.base = buffers[name].data_ptr() + {"f64": 8, "i32": 4, "u8": 1}[kind] * self._side_first(name, offset)
+        S.type, S.rows, S.row_stride, S.plant_stride = _lib.SAMPLE_TYPES[kind], 1, 0, stride
+
+    def _fill_column(self, C, buffers, where) -> None:
+        """fill the {from_source, kind, slot, source} head of an NpbEventTrigger or NpbTaskColumn from ``_lib.column_word``'s answer"""
+        if where["member"] is not None:
+            C.from_source, (C.kind, C.slot) = 0, where["member"]
+        else:
+            C.from_source = 1
+            self._fill_source(C.source, buffers, *where["side"])
+
     def enable_column_stats(self, columns, limits=None, stats=("min", "max", "sum", "sumsq", "last")) -> None:
         """Have the device fold per-plant statistics of ``columns`` behind every step (npb_set_column_stats): one more launch, a thread per
         (column, plant), the sample being the end-of-step state of the episode the step belonged to, before any restore.  ``columns``: up
@@ -1040,12 +1069,9 @@ class BatchedPlantEnv:
         kinds = (ctypes.c_int * max(nm, 1))(*[m[0] for m in req["members"]])
         slots = (ctypes.c_int * max(nm, 1))(*[m[1] for m in req["members"]])
         side = (_lib.NpbSampleSource * max(ns, 1))()
-        buffers = {"info": self._info_buf, "obs": self._obs, "reward": self._reward}
-        if tk is not None:
-            buffers["task_reward"] = tk["reward"]
-        for k, (name, offset, stride) in enumerate(req["sides"]):
-            side[k].base = buffers[name].data_ptr() + 8 * offset; side[k].type = _lib.SAMPLE_TYPES["f64"]; side[k].rows = 1
-            side[k].row_stride = 0; side[k].plant_stride = stride
+        buffers = self._side_buffers()
+        for k, where in enumerate(req["sides"]):
+            self._fill_source(side[k], buffers, *where)
         direction, limit = (ctypes.c_int * n_cols)(*req["direction"]), (ctypes.c_double * n_cols)(*req["limit"])
         d.n_fields, d.kinds, d.slots, d.n_sources, d.sources, d.direction, d.limit = nm, kinds, slots, ns, side, direction, limit
         from . import colstats
@@ -1119,26 +1145,12 @@ class BatchedPlantEnv:
         kinds = (ctypes.c_int * max(nm, 1))(*[m[0] for m in req["members"]])
         slots = (ctypes.c_int * max(nm, 1))(*[m[1] for m in req["members"]])
         side = (_lib.NpbSampleSource * max(ns, 1))()
-        buffers = {"info": self._info_buf, "obs": self._obs, "reward": self._reward, "flags": self._flags, "done": self._done}
-        if ms is not None:
-            buffers.update(n_created=ms["counts"][0], n_completed=ms["counts"][1])
-        if tk is not None:
-            buffers.update(task_reward=tk["reward"], task_cause=tk["cause"])
-        width = {"f64": 8, "i32": 4, "u8": 1}
-
-        def source(S, name, offset, stride, kind="f64"):
-            rows = offset * self.n if name in ("n_created", "n_completed") else offset      # (a summary table is [n_keys][n])
-            S.base = buffers[name].data_ptr() + width[kind] * rows; S.type = _lib.SAMPLE_TYPES[kind]; S.rows = 1
-            S.row_stride = 0; S.plant_stride = stride
+        buffers = self._side_buffers()
         for k, where in enumerate(req["sides"]):
-            source(side[k], *where)
+            self._fill_source(side[k], buffers, *where)
         trig = (_lib.NpbEventTrigger * nt)()
         for k, T in enumerate(req["triggers"]):
-            if T["member"] is not None:
-                trig[k].from_source, trig[k].kind, trig[k].slot = 0, T["member"][0], T["member"][1]
-            else:
-                trig[k].from_source = 1
-                source(trig[k].source, *T["side"])
+            self._fill_column(trig[k], buffers, T)
             trig[k].mode, trig[k].mask, trig[k].direction, trig[k].limit = _lib.TRIGGER_MODES[T["mode"]], T["mask"], T["direction"], T["limit"]
         d.n_fields, d.kinds, d.slots, d.n_sources, d.sources, d.n_triggers, d.triggers = nm, kinds, slots, ns, side, nt, trig
         d.pre, d.post, d.capacity = req["pre"], req["post"], cap
@@ -1217,14 +1229,6 @@ class BatchedPlantEnv:
         m = None if mask is None else self._col(mask, torch.uint8)
         _lib.check(self.L.npb_event_windows_clear(self._h, None if m is None else self._p(m), self._stream()), self._h)
 
-    def _task_buffers(self):
-        """the env's buffers a task's side columns point into, by the names ``_lib.task_request`` gives them"""
-        buffers = {"info": self._info_buf, "obs": self._obs, "reward": self._reward, "flags": self._flags, "done": self._done}
-        ms = getattr(self, "_msum", None)
-        if ms is not None:
-            buffers.update(n_created=ms["counts"][0], n_completed=ms["counts"][1])
-        return buffers
-
     def _task_readers(self):
         """what reads the task's output columns: (name, settings) of the column statistics and the event windows that do"""
         return [(what, user) for what, user in (("column statistics", getattr(self, "_cstats", None)), ("event windows", getattr(self, "_ewin", None)))
@@ -1267,31 +1271,20 @@ class BatchedPlantEnv:
             raise _lib.NpbError("libnpb.so has no npb_set_task: rebuild")
         for what, _user in self._task_readers():      # (they hold the old task's output columns)
             raise _lib.NpbError("set_task: the %s read 'task_reward' / ('task', mask) of the task that is set: turn them off first" % what)
-        buffers = self._task_buffers()
-        width = {"f64": 8, "i32": 4, "u8": 1}
-
-        def column(C, where):
-            if where["member"] is not None:
-                C.from_source, C.kind, C.slot = 0, where["member"][0], where["member"][1]
-                return
-            name, offset, stride, kind = where["side"]
-            rows = offset * self.n if name in ("n_created", "n_completed") else offset      # (a summary table is [n_keys][n])
-            C.from_source = 1
-            C.source.base = buffers[name].data_ptr() + width[kind] * rows; C.source.type = _lib.SAMPLE_TYPES[kind]; C.source.rows = 1
-            C.source.row_stride = 0; C.source.plant_stride = stride
+        buffers = self._side_buffers()
         nt, nr = len(req["terms"]), len(req["rules"])
         terms, rules = (_lib.NpbTaskTerm * max(nt, 1))(), (_lib.NpbTaskRule * max(nr, 1))()
         for k, T in enumerate(req["terms"]):
-            column(terms[k].column, req["columns"][T["col"]])
+            self._fill_column(terms[k].column, buffers, req["columns"][T["col"]])
             terms[k].weight, terms[k].kind = T["weight"], _lib.TASK_KINDS[T["kind"]]
             if isinstance(T["ref"], tuple):
                 terms[k].ref_from_column = 1
-                column(terms[k].ref_column, req["columns"][T["ref"][1]])
+                self._fill_column(terms[k].ref_column, buffers, req["columns"][T["ref"][1]])
             else:
                 terms[k].ref = T["ref"]
             terms[k].direction, terms[k].limit, terms[k].mask = T["direction"], T["limit"], T["mask"]
         for k, R in enumerate(req["rules"]):
-            column(rules[k].column, req["columns"][R["col"]])
+            self._fill_column(rules[k].column, buffers, req["columns"][R["col"]])
             rules[k].mode, rules[k].mask, rules[k].direction, rules[k].limit = _lib.TASK_MODES[R["mode"]], R["mask"], R["direction"], R["limit"]
             rules[k].terminal_reward = R["terminal_reward"]
         d = _lib.NpbTaskDesc()
@@ -1326,15 +1319,14 @@ class BatchedPlantEnv:
         from; a plant the autoreset restarted shows its start state."""
         if getattr(self, "_task", None) is None:
             raise _lib.NpbError("no task: set_task() first")
-        buffers = self._task_buffers()
+        buffers = self._side_buffers()
         rows = []
         for C in self._task["request"]["columns"]:
             if C["member"] is not None:
                 rows.append(self._get_slot("f64" if C["member"][0] == 0 else "i32", C["member"][1]).to(torch.float64))
             else:
                 name, offset, stride, _kind = C["side"]
-                b = buffers[name]
-                rows.append((b.reshape(-1, self.n)[offset] if name in ("n_created", "n_completed") else b.reshape(-1)[offset::stride][:self.n]).to(torch.float64))
+                rows.append(buffers[name].reshape(-1)[self._side_first(name, offset)::stride][:self.n].to(torch.float64))
         return torch.stack(rows)
 
     def clear_task(self, mask=None) -> None:

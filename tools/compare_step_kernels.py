@@ -51,7 +51,7 @@ def resources(path):
         if m:
             cur = m.group(1); out[cur] = []
             continue
-        m = re.search(r"remark: [^:]*:\d+:\d+: (.*)\[-Rpass-analysis", ln)
+        m = re.search(r"remark: (?:[^:\s]*:\d+:\d+: )?\s*(.*?)\s*\[-Rpass-analysis", ln)      # (the location leads the line, or follows "remark:")
         if m and cur:
             out[cur].append(m.group(1).strip())
     return out
@@ -77,7 +77,7 @@ def main(argv):
         bad += len(differ)
         print("%s storage: %d step kernels and rule instantiations, %d instructions and directives: %s" % (
             st, len(step), sum(len(a[k].splitlines()) for k in step), "identical, resource tables too" if not differ else "DIFFERENT: %s" % differ))
-        print("  other functions changed:", sorted(k for k in a if k not in step and (k not in b or a[k] != b[k])))
+        print("  other functions changed:", sorted(k for k in a if k not in step and (k not in b or a[k] != b[k] or ra.get(k) != rb.get(k))))
         print("  new functions:", sorted(k for k in b if k not in a))
     return 1 if bad else 0
 
