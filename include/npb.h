@@ -956,6 +956,81 @@ NPB_API int npb_task_get_state(NpbHandle *h, double *prev, int32_t *primed, int3
 NPB_API int npb_task_set_state(NpbHandle *h, const double *prev, const int32_t *primed, const int32_t *seen, void *stream);
 NPB_API int npb_set_episode_record_task(NpbHandle *h, int32_t *cause /* device [capacity] */);
 
+/* Features: the caller's policy inputs, formed on the device behind every step -- the observation side of the task.  The caller names 1 ..
+ * NPB_FEATURES_COLS_MAX columns, each with a transform, and a stack depth K (1 .. NPB_FEATURES_STACK_MAX, K * C <= NPB_FEATURES_CELLS_MAX);
+ * the handle keeps `out`, a contiguous row-major [n_plants][K][C] tensor of float (NPB_FEATURES_F32) or double (NPB_FEATURES_F64) of the
+ * caller's, holding every plant's last K frames: out[p][K - 1] is the newest frame, out[p][0] the oldest.  No half types.
+ * Columns are named as the task names them (npb_task_column_t), every sample v widened to double as npb_sample_kernel widens it.  Kinds:
+ *   NPB_FEATURE_AFFINE       y = (v - ref) * scale, ref the constant `ref` or with ref_from_column != 0 the sample of ref_column (a setpoint
+ *                            error); the subtraction is rounded before the product (the library is built with -ffp-contract=off)
+ *   NPB_FEATURE_BITS(mask)   integer column: y = ((v & mask) != 0) ? 1.0 : 0.0
+ * and behind the kind, in this order: if y is a NaN and nan_to is not, y = nan_to (with a NaN nan_to a NaN stays, as THE quiet NaN, sign
+ * clear and no payload: 0x7ff8000000000000, as float 0x7fc00000); y = y < lo ? lo : y, then y = y > hi ? hi : y (lo = -inf, hi = +inf: no
+ * clip; a NaN passes both comparisons); for float output the narrowing rounds to nearest even, overflows to an infinity and keeps
+ * subnormals.
+ * A FRESH frame is the frame of a plant whose step outputs do not describe its current state: after a restore or a reset, before any step
+ * of the new episode.  In a fresh frame an arena member is read live, and so is a source with fresh_live != 0 (the obs buffer given to
+ * npb_step, which the episode kernel rewrites for a restarted plant); every other source takes its raw value `fresh` (for a ref_column
+ * without ref_fresh_live: the constant `ref`), which then goes through the same transform.  That makes the restart frame well defined
+ * although reward, info and trip_flags keep describing the terminal transition (npb_set_autoreset).
+ * The handle keeps per plant a primed flag and the episode index last seen (the task's rule).  With features set npb_step launches one
+ * kernel more, or with the autoreset on two (npd_features.h; one wave per 64 plants, the frame transposed through LDS, no atomics):
+ *   pass A, behind the event-windows kernel and before the episode-records and episode kernels: a primed plant whose episode index is the
+ *     one seen shifts its stack by one frame and appends this step's frame, all columns live; an unprimed plant, or one whose index
+ *     differs (restored by the caller between steps), has all K slots filled with this step's frame.  Both: primed = 1, seen = index.
+ *   pass B, behind the episode kernel, only with the autoreset on: a plant whose carried episode index now differs from `seen` was
+ *     restarted on this step.  With a `final` buffer ([n_plants][K][C], the type of out) its whole stack -- the terminal frame pass A just
+ *     appended included -- is first copied to final[p]; the rows of the other plants stay as they were (as final_obs).  Then all K slots
+ *     take the fresh frame of the restored state, and seen = index.
+ * npb_features_prime: the unprimed plants get all K slots filled with the fresh frame of their current state and become primed; primed
+ * plants are untouched -- the initial observation before the first step, and the observation after a reset.  npb_features_clear: the
+ * plants of mask (device uint8 [n_plants], NULL = all) become unprimed.  npb_features_get_state / npb_features_set_state move primed and
+ * seen (int32 [n_plants] each) to and from host arrays for checkpoints, synchronous on `stream`; the stack itself is the caller's buffer.
+ * These four return NPB_EINVAL when no features are set.
+ * npb_set_features(h, desc): desc = NULL turns the features off; the descriptor is copied (its host array too), every plant unprimed.
+ * NPB_EINVAL with the reason in npb_last_error, before any device work, for what npb_features_check refuses -- that check alone, without a
+ * handle, NULL = accepted, else the reason: n_plants < 1; a column count or stack depth out of range (or a count without its array), or K
+ * * C > NPB_FEATURES_CELLS_MAX; a bad kind or slot; a source with a NULL base, an unknown type or rows != 1; an unknown feature kind;
+ * BITS on a real-valued column, or with mask 0; a NaN scale, ref, lo, hi or fresh; lo > hi; an unknown out type; a NULL or misaligned
+ * out, or a misaligned final (4-byte for float, 8-byte for double).
+ * No step, restore or episode kernel changes.  Not here: the terminal stack in the episode records, half-precision output, a delta or rate
+ * kind (the stack carries it), running statistics updated on the device.
+ * NPB_VERSION stays 154: a binding detects the entry points by name.  A handle that never calls this behaves as before in every entry
+ * point. */
+#define NPB_FEATURES_COLS_MAX 64
+#define NPB_FEATURES_STACK_MAX 16
+#define NPB_FEATURES_CELLS_MAX 256
+enum { NPB_FEATURE_KIND_AFFINE = 0, NPB_FEATURE_KIND_BITS = 1 };
+enum { NPB_FEATURES_F32 = 0, NPB_FEATURES_F64 = 1 };
+/* the members kind, mask of an npb_feature_column_t initialiser */
+#define NPB_FEATURE_AFFINE NPB_FEATURE_KIND_AFFINE, 0u
+#define NPB_FEATURE_BITS(mask) NPB_FEATURE_KIND_BITS, (uint32_t)(mask)
+typedef struct npb_feature_column_t {
+  npb_task_column_t column;
+  int kind; uint32_t mask;       /* NPB_FEATURE_AFFINE, or NPB_FEATURE_BITS(mask) */
+  double scale;                  /* AFFINE */
+  int ref_from_column;           /* AFFINE: 0 = the constant `ref`, != 0 = ref_column */
+  double ref;
+  npb_task_column_t ref_column;
+  double lo, hi;                 /* the clip; -inf / +inf = none */
+  double nan_to;                 /* what a NaN becomes; a NaN = it stays */
+  double fresh;                  /* a source's raw value in a fresh frame */
+  int fresh_live, ref_fresh_live; /* != 0: the source is current after a restore and is read in a fresh frame too */
+} npb_feature_column_t;
+typedef struct npb_features_desc_t {
+  int n_columns; const npb_feature_column_t *columns;      /* host */
+  int stack;                     /* K */
+  int out_type;                  /* NPB_FEATURES_F32 | NPB_FEATURES_F64 */
+  void *out;                     /* device [n_plants][stack][n_columns] */
+  void *final;                   /* device, the same shape, or NULL */
+} npb_features_desc_t;
+NPB_API int npb_set_features(NpbHandle *h, const npb_features_desc_t *desc);
+NPB_API const char *npb_features_check(const npb_features_desc_t *desc, int n_plants);
+NPB_API int npb_features_prime(NpbHandle *h, void *stream);
+NPB_API int npb_features_clear(NpbHandle *h, const uint8_t *mask, void *stream);
+NPB_API int npb_features_get_state(NpbHandle *h, int32_t *primed, int32_t *seen, void *stream);
+NPB_API int npb_features_set_state(NpbHandle *h, const int32_t *primed, const int32_t *seen, void *stream);
+
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the
  * rocprofv3 FETCH_SIZE / WRITE_SIZE counters (tools/profile_traffic.py). */

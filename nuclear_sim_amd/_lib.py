@@ -745,6 +745,113 @@ def task_request(reward=(), terminate=(), bias: float = 0.0, info_columns=None, 
     return {"columns": columns, "terms": terms, "rules": rules, "bias": bias}
 
 
+# include/npb.h npb_features_desc_t: the caller's policy inputs, a stack of transformed frames kept on the device (npb_set_features)
+FEATURES_COLS_MAX, FEATURES_STACK_MAX, FEATURES_CELLS_MAX = 64, 16, 256
+FEATURE_KINDS = {"affine": 0, "bits": 1}               # NPB_FEATURE_KIND_* (features.KINDS)
+FEATURE_DTYPES = {"float32": 0, "float64": 1}          # NPB_FEATURES_F32 / NPB_FEATURES_F64 (features.DTYPES)
+FEATURE_OPTIONS = ("scale", "ref", "clip", "nan_to", "bits", "fresh", "ref_fresh")
+
+
+class NpbFeatureColumn(ctypes.Structure):
+    """npb_feature_column_t: one column and its transform"""
+    _fields_ = [("column", NpbTaskColumn), ("kind", ctypes.c_int), ("mask", ctypes.c_uint32), ("scale", ctypes.c_double),
+                ("ref_from_column", ctypes.c_int), ("ref", ctypes.c_double), ("ref_column", NpbTaskColumn), ("lo", ctypes.c_double),
+                ("hi", ctypes.c_double), ("nan_to", ctypes.c_double), ("fresh", ctypes.c_double), ("fresh_live", ctypes.c_int),
+                ("ref_fresh_live", ctypes.c_int)]
+
+
+class NpbFeaturesDesc(ctypes.Structure):
+    """npb_features_desc_t: the columns (a host array), the stack depth, the output type and the caller's device tensors"""
+    _fields_ = [("n_columns", ctypes.c_int), ("columns", ctypes.POINTER(NpbFeatureColumn)), ("stack", ctypes.c_int), ("out_type", ctypes.c_int),
+                ("out", ctypes.c_void_p), ("final", ctypes.c_void_p)]
+
+
+def features_request(columns, stack: int = 1, dtype="float32", info_columns=None, task: bool = False, summary_keys: int = 0) -> dict:
+    """What ``BatchedPlantEnv.set_features`` asks of npb_set_features, from the caller's words; a pure function, host only, so a word that
+    cannot work is refused (ValueError, naming it) before any device work.
+    ``columns``: 1 to 64, each a column word or ``(word, options)``.  A word is what ``column_word`` resolves: a state member,
+    ``("info", name)``, ``("obs", i)``, ``"reward"``, ``"flags"``, ``"done"``, ``"maintenance"``, ``("work_order" | "completed", key_index)``
+    (``summary_keys`` > key_index) and, with ``task``, ``"task_reward"``.  ``options``: a dict of ``"scale"``, ``"ref"`` (a number, or a
+    second column word: a setpoint error), ``"clip": (lo, hi)`` (None = that side open), ``"nan_to"``, ``"bits": mask`` (an integer column:
+    1.0 where any of the bits is set; it excludes scale and ref), ``"fresh"`` (the raw value a side column takes in a fresh frame, default
+    0.0) and ``"ref_fresh"`` (the same for a second column).  ``stack``: K, 1 to 16 with K * C <= 256.  ``dtype``: float32 or float64, as
+    a name, a numpy dtype or a torch dtype.
+    Returns {"columns": per column read what ``column_word`` answers, "spec": {"stack", "dtype", "columns"} -- what ``features.Stack`` and
+    ``features.frame`` take, over the rows of "columns"; a member and the observation are ``live`` in a fresh frame}."""
+    columns = list(columns) if isinstance(columns, (list, tuple)) else [columns]
+    if not 1 <= len(columns) <= FEATURES_COLS_MAX:
+        raise ValueError("features take 1 to %d columns, not %d" % (FEATURES_COLS_MAX, len(columns)))
+    if isinstance(stack, bool) or not isinstance(stack, (int, np.integer)) or not 1 <= stack <= FEATURES_STACK_MAX:
+        raise ValueError("the stack depth must be 1 .. %d, not %r" % (FEATURES_STACK_MAX, stack))
+    if stack * len(columns) > FEATURES_CELLS_MAX:
+        raise ValueError("stack * columns must be <= %d, not %d * %d" % (FEATURES_CELLS_MAX, stack, len(columns)))
+    try:
+        name = np.dtype(dtype).name
+    except TypeError:      # (a torch dtype: "torch.float32")
+        name = str(dtype).rsplit(".", 1)[-1]
+    if name not in FEATURE_DTYPES:
+        raise ValueError("the output type must be float32 or float64 (no half types), not %r" % (dtype,))
+    rows, index = [], {}
+
+    def row(col):
+        key = (col,) if isinstance(col, str) else tuple(col)
+        if key not in index:
+            C = column_word(col, info_columns, task, integer_sides=True, summary_keys=summary_keys)      # (an unknown word is refused there)
+            index[key] = len(rows)
+            rows.append(C)
+        return index[key]
+
+    def live(r):
+        return rows[r]["member"] is not None or rows[r]["side"][0] == "obs"
+
+    def number(x, what, where, nan_ok=False):
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise ValueError("%s: %s must be a number, not %r" % (where, what, x))
+        if not nan_ok and np.isnan(float(x)):
+            raise ValueError("%s: %s is NaN" % (where, what))
+        return float(x)
+
+    spec = []
+    for i, col in enumerate(columns):
+        where = "feature column %d %r" % (i, col)
+        word, opts = col, {}
+        if isinstance(col, (tuple, list)) and len(col) == 2 and isinstance(col[1], dict):
+            word, opts = col
+        for key in opts:
+            if key not in FEATURE_OPTIONS:
+                raise ValueError("%s: unknown option %r: one of %r" % (where, key, FEATURE_OPTIONS))
+        r = row(word)
+        D = {"col": r, "kind": "affine", "scale": 1.0, "ref": 0.0, "lo": -np.inf, "hi": np.inf, "nan_to": np.nan, "mask": 0, "fresh": 0.0,
+             "ref_fresh": 0.0, "live": live(r), "ref_live": False}
+        if "bits" in opts:
+            if "scale" in opts or "ref" in opts:
+                raise ValueError("%s: 'bits' excludes 'scale' and 'ref'" % where)
+            if not rows[r]["integer"]:
+                raise ValueError("%s: 'bits' needs an integer column" % where)
+            D["kind"], D["mask"] = "bits", _bit_mask(opts["bits"], where + ":")
+        else:
+            D["scale"] = number(opts.get("scale", 1.0), "the scale", where)
+            ref = opts.get("ref", 0.0)
+            if isinstance(ref, (str, tuple, list)):
+                rr = row(ref)
+                D["ref"], D["ref_live"] = ("col", rr), live(rr)
+                D["ref_fresh"] = number(opts.get("ref_fresh", 0.0), "ref_fresh", where)
+            else:
+                D["ref"] = number(ref, "the ref", where)
+        if "clip" in opts:
+            clip = opts["clip"]
+            if not isinstance(clip, (tuple, list)) or len(clip) != 2:
+                raise ValueError("%s: 'clip' is (lo, hi), either None for an open side" % where)
+            D["lo"] = -np.inf if clip[0] is None else number(clip[0], "the lower clip limit", where)
+            D["hi"] = np.inf if clip[1] is None else number(clip[1], "the upper clip limit", where)
+            if D["lo"] > D["hi"]:
+                raise ValueError("%s: a clip with lo > hi" % where)
+        D["nan_to"] = number(opts.get("nan_to", np.nan), "nan_to", where, nan_ok=True)
+        D["fresh"] = number(opts.get("fresh", 0.0), "fresh", where)
+        spec.append(D)
+    return {"columns": rows, "spec": {"stack": int(stack), "dtype": name, "columns": spec}}
+
+
 def episode_streams_desc(block, bank_noise_seeds=None, bank_profile_seeds=None, outputs=(None, None, None)):
     """(desc, keep): an NpbEpisodeStreamsDesc and the host arrays it points into (host only, no library needed).  A table is a sequence of
     seeds, one per bank entry; both tables, where both are given, have the same length.  ``outputs``: three device addresses or None."""
@@ -936,6 +1043,14 @@ def load():
         L.npb_task_get_state.argtypes = [vp, vp, vp, vp, vp]
         L.npb_task_set_state.argtypes = [vp, vp, vp, vp, vp]
         L.npb_set_episode_record_task.argtypes = [vp, vp]
+    if hasattr(L, "npb_set_features"):     # the caller's policy inputs: a stack of transformed frames kept behind every step
+        L.npb_set_features.argtypes = [vp, ctypes.POINTER(NpbFeaturesDesc)]
+        L.npb_features_check.argtypes = [ctypes.POINTER(NpbFeaturesDesc), ci]
+        L.npb_features_check.restype = ctypes.c_char_p
+        L.npb_features_prime.argtypes = [vp, vp]
+        L.npb_features_clear.argtypes = [vp, vp, vp]
+        L.npb_features_get_state.argtypes = [vp, vp, vp, vp]
+        L.npb_features_set_state.argtypes = [vp, vp, vp, vp]
     if hasattr(L, "npb_set_event_windows"):     # state windows around events, captured behind every step
         L.npb_set_event_windows.argtypes = [vp, ctypes.POINTER(NpbEventWindowsDesc)]
         L.npb_event_windows_check.argtypes = [ctypes.POINTER(NpbEventWindowsDesc), ci, ci]

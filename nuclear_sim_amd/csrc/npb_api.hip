@@ -81,6 +81,8 @@ struct NpbHandle {
   /* npb_set_task: the terms, rules, previous samples and bookkeeping on the device (task.terms = the one allocation; NULL = off) and the
    * caller's outputs; npb_set_episode_record_task: the record-side column that takes the cause word */
   npb_task_t task; bool ert_on; int32_t *ert_cause;
+  /* npb_set_features: the columns and the bookkeeping on the device (feat.cols = the one allocation; NULL = off) and the caller's tensors */
+  npb_features_t feat;
   double *ramp_prev;   /* npb_profile_ramp: the previous setpoint of every plant ([pitch], NaN = none yet), allocated on first use */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
   std::vector<int> plan_key;
@@ -322,6 +324,7 @@ enum { COLUMN_BAD_FIELD, COLUMN_NULL_BASE, COLUMN_BAD_TYPE, COLUMN_ROWS, COLUMN_
 static const char *const g_cs_column[COLUMN_REFUSALS_COUNT] = COLUMN_REFUSALS("npb_set_column_stats");
 static const char *const g_ew_column[COLUMN_REFUSALS_COUNT] = COLUMN_REFUSALS("npb_set_event_windows");
 static const char *const g_task_column[COLUMN_REFUSALS_COUNT] = COLUMN_REFUSALS("npb_set_task");
+static const char *const g_feat_column[COLUMN_REFUSALS_COUNT] = COLUMN_REFUSALS("npb_set_features");
 /* why a column is refused (who: the caller's table above), or NULL; integer (may be NULL): whether its values are integers, which bit masks need */
 static const char *column_refusal(const char *const *who, column_view C, bool *integer) {
   bool is_integer;
@@ -511,6 +514,7 @@ int npb_destroy(NpbHandle *h) {
   if (h->ers_dev) (void)hipFree(h->ers_dev);
   if (h->ew.cols) (void)hipFree((void *)h->ew.cols);
   if (h->task.terms) (void)hipFree((void *)h->task.terms);
+  if (h->feat.cols) (void)hipFree((void *)h->feat.cols);
   for (Sampler *sm : h->samplers) if (sm) { (void)hipFree(sm->dev); delete sm; }
   delete h;
   return NPB_OK;
@@ -1114,6 +1118,8 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
   if (h->ew.cols)      /* the same sample into every plant's ring, the triggers, the windows that are due -- or cut short by an episode that ends here */
     h->K->event_windows(h->f64, NPB_N(h), &h->ew, h->n_plants, h->ew_step++, h->ep_index, h->autoreset ? h->ep_len : nullptr, done,
                         h->max_episode_steps, (hipStream_t)stream);
+  if (h->feat.cols)      /* pass A: this step's frame into every plant's stack, while everything still describes the episode it belongs to */
+    h->K->features(h->f64, NPB_N(h), &h->feat, h->n_plants, 0, h->ep_index, (hipStream_t)stream);
   if (h->er_on && h->autoreset)      /* the episodes that end on this step, recorded while everything still describes them; then their summary rows cleared */
     h->K->episode_records(h->n_plants, NPB_N(h), h->f64, done, reward, obs, trip_flags, counters_of(h), h->ep_start,
                           h->max_episode_steps, h->er_step++, &h->er, er_uses_summary(h) ? &h->summary : nullptr,
@@ -1123,6 +1129,8 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
                   h->ep_out_len, h->ep_out_ret, h->ep_out_truncated, h->ep_final_obs, h->max_episode_steps,
                   maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, side, (hipStream_t)stream);
   if (h->autoreset) restart_streams(h, from_bank, (hipStream_t)stream, &es_take);      /* the plants the episode kernel has just restarted */
+  if (h->feat.cols && h->autoreset)      /* pass B: their stacks into `final`, then the fresh frame of the restored state */
+    h->K->features(h->f64, NPB_N(h), &h->feat, h->n_plants, 1, h->ep_index, (hipStream_t)stream);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, NPB_EHIP, "npb_step: kernel launch failed", e);
   return NPB_OK;
@@ -1902,6 +1910,127 @@ int npb_set_episode_record_task(NpbHandle *h, int32_t *cause) {
   NPB_USE_DEVICE(h);
   if (int rc = upload_record_side(h, "npb_set_episode_record_task", h->ers_on ? &h->ers : nullptr, cause)) return rc;
   h->ert_on = true; h->ert_cause = cause;
+  return NPB_OK;
+}
+
+/* ---- features (include/npb.h, npd_features.h) */
+const char *npb_features_check(const npb_features_desc_t *D, int n_plants) {
+  if (!D) return nullptr;
+  if (n_plants < 1) return "npb_set_features: n_plants must be >= 1";
+  if (D->n_columns < 1 || D->n_columns > NPB_FEATURES_COLS_MAX || !D->columns)
+    return "npb_set_features: the column count must be 1 .. NPB_FEATURES_COLS_MAX (64), with their descriptors";
+  if (D->stack < 1 || D->stack > NPB_FEATURES_STACK_MAX) return "npb_set_features: the stack depth must be 1 .. NPB_FEATURES_STACK_MAX (16)";
+  if (D->stack * D->n_columns > NPB_FEATURES_CELLS_MAX) return "npb_set_features: stack * columns must be <= NPB_FEATURES_CELLS_MAX (256)";
+  for (int c = 0; c < D->n_columns; c++) {
+    const npb_feature_column_t &F = D->columns[c];
+    bool integer = false;
+    if (const char *why = column_refusal(g_feat_column, column_of(F.column), &integer)) return why;
+    if (F.kind == NPB_FEATURE_KIND_AFFINE) {
+      if (F.scale != F.scale) return "npb_set_features: a NaN scale";
+      if (F.ref != F.ref) return "npb_set_features: a NaN ref";
+      if (F.ref_from_column) { if (const char *why = column_refusal(g_feat_column, column_of(F.ref_column), nullptr)) return why; }
+    } else if (F.kind == NPB_FEATURE_KIND_BITS) {
+      if (!integer) return "npb_set_features: NPB_FEATURE_BITS on a real-valued column (it needs an int32 member, or an I32 or U8 source)";
+      if (F.mask == 0u) return "npb_set_features: NPB_FEATURE_BITS with mask 0";
+    } else {
+      return "npb_set_features: an unknown feature kind";
+    }
+    if (F.lo != F.lo || F.hi != F.hi) return "npb_set_features: a NaN clip limit (lo, hi)";
+    if (F.lo > F.hi) return "npb_set_features: a clip with lo > hi";
+    if (F.fresh != F.fresh) return "npb_set_features: a NaN fresh value";
+  }
+  if (D->out_type != NPB_FEATURES_F32 && D->out_type != NPB_FEATURES_F64) return "npb_set_features: an unknown out type";
+  if (!D->out) return "npb_set_features: a NULL out tensor";
+  const uintptr_t low = D->out_type == NPB_FEATURES_F64 ? 7u : 3u;
+  if (((uintptr_t)D->out & low) || ((uintptr_t)D->final & low))
+    return "npb_set_features: a misaligned tensor: out and final must be 4-byte aligned for float, 8-byte for double";
+  return nullptr;
+}
+int npb_set_features(NpbHandle *h, const npb_features_desc_t *desc) {
+  if (!h) return NPB_EINVAL;
+  if (const char *why = npb_features_check(desc, h->n_plants)) return fail(h, NPB_EINVAL, why);
+  NPB_USE_DEVICE(h);
+  if (!desc) {
+    if (h->feat.cols) (void)hipFree((void *)h->feat.cols);      /* (hipFree waits for the device: a launch still in flight finishes first) */
+    h->feat = npb_features_t{};
+    return NPB_OK;
+  }
+  /* the handle's one allocation: [the columns] | primed [n] | seen [n] */
+  std::vector<npb_feature_col_t> table(NPB_FEATURES_COLS_MAX);
+  for (int c = 0; c < desc->n_columns; c++) {
+    const npb_feature_column_t &F = desc->columns[c];
+    npb_feature_col_t &O = table[c];
+    O = npb_feature_col_t{};
+    if (!column_build(h, column_of(F.column), &O.c)) return fail(h, NPB_EINVAL, g_feat_column[COLUMN_BAD_FIELD]);
+    O.kind = F.kind; O.mask = F.mask; O.scale = F.scale; O.ref = F.ref; O.lo = F.lo; O.hi = F.hi; O.nan_to = F.nan_to; O.fresh = F.fresh;
+    if (F.nan_to != F.nan_to) { const uint64_t quiet = 0x7ff8000000000000ull; memcpy(&O.nan_to, &quiet, sizeof quiet); }      /* the NaN that stays: sign clear, no payload */
+    O.live = (!F.column.from_source || F.fresh_live) ? 1 : 0;
+    if (F.kind == NPB_FEATURE_KIND_AFFINE && F.ref_from_column) {
+      O.ref_col = 1;
+      if (!column_build(h, column_of(F.ref_column), &O.r)) return fail(h, NPB_EINVAL, g_feat_column[COLUMN_BAD_FIELD]);
+      if (!F.ref_column.from_source || F.ref_fresh_live) O.live |= 2;
+    }
+  }
+  const size_t n = (size_t)h->n_plants, table_bytes = table.size() * sizeof(npb_feature_col_t), bytes = table_bytes + 2 * n * sizeof(int32_t);
+  static_assert(sizeof(npb_feature_col_t) % 8 == 0, "packed");
+  char *dev = nullptr;
+  hipError_t e = hipMalloc((void **)&dev, bytes);
+  if (e != hipSuccess) {
+    char what[160];
+    snprintf(what, sizeof what, "npb_set_features: hipMalloc of the columns and the bookkeeping (%zu bytes) failed", bytes);
+    return fail(h, NPB_EHIP, what, e);
+  }
+  npb_features_t F = {};
+  F.cols = (const npb_feature_col_t *)dev; F.n_cols = desc->n_columns; F.stack = desc->stack; F.out_f64 = desc->out_type == NPB_FEATURES_F64;
+  F.out = desc->out; F.final = desc->final;
+  F.primed = (int32_t *)(dev + table_bytes); F.seen = F.primed + n;
+  /* the columns up, everything else zero: every plant unprimed; synchronous, so the host copy may go */
+  e = hipMemset(dev, 0, bytes);
+  if (e == hipSuccess) e = hipMemcpy(dev, table.data(), table_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess) { (void)hipFree(dev); return fail(h, NPB_EHIP, "npb_set_features: setting up the columns and the bookkeeping failed", e); }
+  if (h->feat.cols) (void)hipFree((void *)h->feat.cols);
+  h->feat = F;
+  return NPB_OK;
+}
+int npb_features_prime(NpbHandle *h, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->feat.cols) return fail(h, NPB_EINVAL, "npb_features_prime: no features set (npb_set_features first)");
+  NPB_USE_DEVICE(h);
+  h->K->features(h->f64, NPB_N(h), &h->feat, h->n_plants, 2, h->ep_index, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_features_clear(NpbHandle *h, const uint8_t *mask, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->feat.cols) return fail(h, NPB_EINVAL, "npb_features_clear: no features set (npb_set_features first)");
+  NPB_USE_DEVICE(h);
+  npb_launch_features_clear(&h->feat, mask, h->n_plants, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_features_get_state(NpbHandle *h, int32_t *primed, int32_t *seen, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->feat.cols) return fail(h, NPB_EINVAL, "npb_features_get_state: no features set (npb_set_features first)");
+  if (!primed || !seen) return fail(h, NPB_EINVAL, "npb_features_get_state: NULL output");
+  NPB_USE_DEVICE(h);
+  const size_t n = (size_t)h->n_plants;
+  hipStream_t st = (hipStream_t)stream;
+  NPB_HIP(h, hipMemcpyAsync(primed, h->feat.primed, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpyAsync(seen, h->feat.seen, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipStreamSynchronize(st));
+  return NPB_OK;
+}
+int npb_features_set_state(NpbHandle *h, const int32_t *primed, const int32_t *seen, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->feat.cols) return fail(h, NPB_EINVAL, "npb_features_set_state: no features set (npb_set_features first)");
+  if (!primed || !seen) return fail(h, NPB_EINVAL, "npb_features_set_state: NULL input");
+  NPB_USE_DEVICE(h);
+  const size_t n = (size_t)h->n_plants;
+  hipStream_t st = (hipStream_t)stream;
+  NPB_HIP(h, hipMemcpyAsync(h->feat.primed, primed, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(h->feat.seen, seen, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipStreamSynchronize(st));      /* the host arrays may go */
   return NPB_OK;
 }
 

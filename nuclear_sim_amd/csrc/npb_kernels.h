@@ -90,6 +90,17 @@ typedef struct {
   int32_t *valid, *due, *seen, *a_step, *a_n_pre, *a_trigger, *a_retriggers; uint32_t *a_fired;
   npb_event_window_records_t D;
 } npb_event_windows_t;
+/* npb_set_features (npd_features.h): one column as the kernel reads it.  c: the column; r: the second column where ref_col != 0 (a setpoint
+ * error), else the constant `ref`; kind: NPB_FEATURE_KIND_*; live: bit 0 / bit 1 = c / r is read in a FRESH frame too (an arena member, or a
+ * source the caller marked live), else c takes `fresh` and r takes `ref` there */
+typedef struct { npb_colstat_col_t c, r; double scale, ref, lo, hi, nan_to, fresh; int kind, ref_col; uint32_t mask; int live; } npb_feature_col_t;
+/* the handle's features: the columns (device, one allocation with the state below; cols NULL = off), the stack depth, the caller's out
+ * [n_plants][stack][n_cols] and final (or NULL) of float or double, and per plant the primed flag and the episode index last seen */
+typedef struct {
+  const npb_feature_col_t *cols; int n_cols, stack, out_f64;
+  void *out, *final;
+  int32_t *primed, *seen;
+} npb_features_t;
 typedef struct {
   int (*step)(const npb_params_t *P, int n_plants, size_t npad, void *arena, const int32_t *action,
               const double *magnitude, const double *setpoint, const double *noise_z, const double *cw_temp,
@@ -147,6 +158,10 @@ typedef struct {
   /* npb_set_task (npd_task.h): every plant's task reward, termination flag and cause word from the end-of-step state and the step's
    * outputs; index: the handle's carried episode indices or NULL */
   void (*task)(const void *arena, size_t npad, const npb_task_t *T, int n_plants, const int32_t *index, hipStream_t stream);
+  /* npb_set_features (npd_features.h): mode 0 = this step's frame into every plant's stack (shift or fill), 1 = the plants the episode
+   * kernel restarted (their stacks to `final`, then the fresh frame), 2 = the unprimed plants' fresh frame; index: the handle's carried
+   * episode indices or NULL */
+  void (*features)(const void *arena, size_t npad, const npb_features_t *F, int n_plants, int mode, const int32_t *index, hipStream_t stream);
 } npb_launchers_t;
 extern npb_launchers_t npb_launch_table, npb32_launch_table;
 /* the same for either storage type */
@@ -177,6 +192,8 @@ void npb_launch_column_stats_clear(const npb_column_stats_t *S, const uint8_t *m
 void npb_launch_event_windows_clear(const npb_event_windows_t *W, const uint8_t *mask, int n_plants, hipStream_t stream);
 /* npb_task_clear (npd_task.h): the plants of mask (NULL = all) unprimed */
 void npb_launch_task_clear(const npb_task_t *T, const uint8_t *mask, int n_plants, hipStream_t stream);
+/* npb_features_clear (npd_features.h): the plants of mask (NULL = all) unprimed */
+void npb_launch_features_clear(const npb_features_t *F, const uint8_t *mask, int n_plants, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -1230,8 +1230,9 @@ class BatchedPlantEnv:
         _lib.check(self.L.npb_event_windows_clear(self._h, None if m is None else self._p(m), self._stream()), self._h)
 
     def _task_readers(self):
-        """what reads the task's output columns: (name, settings) of the column statistics and the event windows that do"""
-        return [(what, user) for what, user in (("column statistics", getattr(self, "_cstats", None)), ("event windows", getattr(self, "_ewin", None)))
+        """what reads the task's output columns: (name, settings) of the column statistics, the event windows and the features that do"""
+        return [(what, user) for what, user in (("column statistics", getattr(self, "_cstats", None)), ("event windows", getattr(self, "_ewin", None)),
+                                                ("features", getattr(self, "_feat", None)))
                 if user is not None and user.get("task")]
 
     def set_task(self, reward=(), terminate=(), bias: float = 0.0, keep_terms: bool = False) -> None:
@@ -1360,6 +1361,133 @@ class BatchedPlantEnv:
         primed = np.ascontiguousarray(np.asarray(state["primed"], dtype=np.int32).reshape(self.n))
         seen = np.ascontiguousarray(np.asarray(state["seen"], dtype=np.int32).reshape(self.n))
         _lib.check(self.L.npb_task_set_state(self._h, prev.ctypes.data if nd else None, primed.ctypes.data, seen.ctypes.data, self._stream()), self._h)
+
+    def set_features(self, columns, stack: int = 1, dtype=torch.float32, final: Optional[bool] = None, as_observation: bool = False) -> None:
+        """Define what the policy reads, on the device (npb_set_features): behind every step one more launch -- two with autoreset --
+        keeps a contiguous ``[n, stack, len(columns)]`` tensor of every plant's last ``stack`` frames, ``[:, -1]`` the newest.  Nothing is
+        read back.
+        ``columns``: 1 to 64, each a column word or ``(word, options)``.  Words are keyed as ``set_task`` keys its columns: a state member,
+        ``("info", name)``, ``("obs", i)``, ``"reward"``, ``"flags"``, ``"done"``, ``"maintenance"``, ``("work_order" | "completed",
+        key_index)`` and, while a task is set, ``"task_reward"``.  ``options``: ``{"scale": s, "ref": r}`` gives ``(v - r) * s`` with r a
+        number or a second column word (a setpoint error); ``{"bits": mask}`` on an integer column gives 1.0 where any of the bits is set;
+        then ``"nan_to"`` replaces a NaN and ``"clip": (lo, hi)`` clips; ``"fresh"`` (default 0.0) is the raw value a side column takes in
+        the frame of a plant that has just been restarted -- its reward, info and flags still describe the terminal transition; state
+        members and the observation are read live there.  ``dtype``: ``torch.float32`` or ``torch.float64``; ``stack * len(columns) <=
+        256``.  ``nuclear_sim_amd.features`` is the same in numpy, bit for bit, and ``features.spec_from_stats`` turns a dry run's column
+        statistics into ``ref`` / ``scale``.
+        A plant's stack restarts with its episode: the same-step autoreset refills it with the frame of the restored state, and the stack
+        that ended -- the terminal frame included -- is kept in ``final_features()`` (``final``: default on with autoreset); ``reset``,
+        ``restore`` and ``restore_from_bank`` refill the plants they reset.  With features on ``step()`` adds ``info["features"]`` and,
+        with autoreset, ``info["final_features"]``; with ``as_observation`` it returns the features in place of the observation (which
+        stays in ``info["observation"]``).  ``set_features(None)`` turns it off."""
+        if columns is None:
+            if getattr(self, "_feat", None) is not None:
+                _lib.check(self.L.npb_set_features(self._h, None), self._h)
+            self._feat = None
+            return
+        ms, tk = getattr(self, "_msum", None), getattr(self, "_task", None)
+        req = _lib.features_request(columns, stack, dtype, INFO_COLUMNS, tk is not None, 0 if ms is None else len(ms["keys"]))      # a bad word is refused here
+        if not hasattr(self.L, "npb_set_features"):
+            raise _lib.NpbError("libnpb.so has no npb_set_features: rebuild")
+        spec, rows, buffers = req["spec"], req["columns"], self._side_buffers()
+        C = len(spec["columns"])
+        cols = (_lib.NpbFeatureColumn * C)()
+        for k, D in enumerate(spec["columns"]):
+            F = cols[k]
+            self._fill_column(F.column, buffers, rows[D["col"]])
+            F.kind, F.mask, F.scale, F.lo, F.hi, F.nan_to, F.fresh = _lib.FEATURE_KINDS[D["kind"]], D["mask"], D["scale"], D["lo"], D["hi"], D["nan_to"], D["fresh"]
+            F.fresh_live = int(D["live"])
+            if isinstance(D["ref"], tuple):
+                F.ref_from_column, F.ref, F.ref_fresh_live = 1, D["ref_fresh"], int(D["ref_live"])
+                self._fill_column(F.ref_column, buffers, rows[D["ref"][1]])
+            else:
+                F.ref = D["ref"]
+        tdtype = torch.float64 if spec["dtype"] == "float64" else torch.float32
+        keep_final = (self._episode is not None) if final is None else bool(final)
+        with torch.cuda.device(self.device):
+            out = torch.zeros((self.n, spec["stack"], C), dtype=tdtype, device=self.device)
+            fin = torch.zeros((self.n, spec["stack"], C), dtype=tdtype, device=self.device) if keep_final else None
+        d = _lib.NpbFeaturesDesc()
+        d.n_columns, d.columns, d.stack, d.out_type = C, cols, spec["stack"], _lib.FEATURE_DTYPES[spec["dtype"]]
+        d.out, d.final = out.data_ptr(), None if fin is None else fin.data_ptr()
+        _lib.check(self.L.npb_set_features(self._h, ctypes.byref(d)), self._h)      # (refused: what was set before stays)
+        self._feat = {"out": out, "final": fin, "request": req, "as_observation": bool(as_observation), "unprimed": True,
+                      "summary": ms["counts"] if any(R["side"] and R["side"][0] in ("n_created", "n_completed") for R in rows) else None,
+                      "task": tk if any(R["side"] and R["side"][0] == "task_reward" for R in rows) else None}
+
+    def _features_on(self) -> dict:
+        if getattr(self, "_feat", None) is None:
+            raise _lib.NpbError("no features: set_features() first")
+        return self._feat
+
+    def features(self) -> torch.Tensor:
+        """The ``[n, stack, n_columns]`` tensor, the same storage on every call and current after every ``step``.  Plants without a frame
+        yet -- before the first step, after ``clear_features`` -- first get the frame of their current state in every slot
+        (npb_features_prime)."""
+        ft = self._features_on()
+        if ft["unprimed"]:
+            self.get_observation()      # (a fresh frame reads the observation live)
+            _lib.check(self.L.npb_features_prime(self._h, self._stream()), self._h)
+            ft["unprimed"] = False
+        return ft["out"]
+
+    def final_features(self) -> torch.Tensor:
+        """``[n, stack, n_columns]``: row p is the stack, terminal frame included, of the last episode of plant p that the autoreset ended;
+        the rows of the other plants stay as they were (as ``info["final_observation"]``)"""
+        ft = self._features_on()
+        if ft["final"] is None:
+            raise _lib.NpbError("no final features: set_features(..., final=True), with autoreset")
+        return ft["final"]
+
+    def clear_features(self, mask=None) -> None:
+        """the masked plants (None = all) unprimed: their next frame fills every slot of their stack (npb_features_clear)"""
+        ft = self._features_on()
+        m = None if mask is None else self._col(mask, torch.uint8)
+        _lib.check(self.L.npb_features_clear(self._h, None if m is None else self._p(m), self._stream()), self._h)
+        ft["unprimed"] = True
+
+    def _refill_features(self, mask) -> None:
+        """behind ``reset`` / ``restore`` / ``restore_from_bank``: the plants they reset show the frame of their new state"""
+        if getattr(self, "_feat", None) is not None:
+            self.clear_features(mask)
+            self.features()
+
+    def features_state(self) -> Dict[str, np.ndarray]:
+        """The features' own state for a checkpoint (npb_features_get_state), beside ``state_arrays()`` and a copy of ``features()``:
+        ``primed`` and ``seen`` int32 [n] (the plant has a frame; the episode index last seen)."""
+        self._features_on()
+        out = {"primed": np.zeros(self.n, dtype=np.int32), "seen": np.zeros(self.n, dtype=np.int32)}
+        _lib.check(self.L.npb_features_get_state(self._h, out["primed"].ctypes.data, out["seen"].ctypes.data, self._stream()), self._h)
+        return out
+
+    def load_features_state(self, state, stack=None) -> None:
+        """put back what ``features_state()`` returned (npb_features_set_state) and, with ``stack``, a saved copy of ``features()``"""
+        ft = self._features_on()
+        primed = np.ascontiguousarray(np.asarray(state["primed"], dtype=np.int32).reshape(self.n))
+        seen = np.ascontiguousarray(np.asarray(state["seen"], dtype=np.int32).reshape(self.n))
+        _lib.check(self.L.npb_features_set_state(self._h, primed.ctypes.data, seen.ctypes.data, self._stream()), self._h)
+        if stack is not None:
+            ft["out"].copy_(torch.as_tensor(stack).to(device=self.device, dtype=ft["out"].dtype).reshape(ft["out"].shape))
+        ft["unprimed"] = not bool(primed.all())
+
+    def features_spec(self) -> dict:
+        """the request as data: {"columns": what each row read is (``_lib.column_word``), "spec": what ``nuclear_sim_amd.features`` takes
+        over those rows}"""
+        return self._features_on()["request"]
+
+    def features_samples(self) -> torch.Tensor:
+        """The rows the features read as they are NOW, widened to float64, [n_rows, n] on the device (gather launches and copies: for checks
+        and debugging, not for the hot path), as ``task_samples`` gives the task's."""
+        ft = self._features_on()
+        buffers = self._side_buffers()
+        rows = []
+        for C in ft["request"]["columns"]:
+            if C["member"] is not None:
+                rows.append(self._get_slot("f64" if C["member"][0] == 0 else "i32", C["member"][1]).to(torch.float64))
+            else:
+                name, offset, stride, _kind = C["side"]
+                rows.append(buffers[name].reshape(-1)[self._side_first(name, offset)::stride][:self.n].to(torch.float64))
+        return torch.stack(rows)
 
     def _order_buffers(self):
         """the buffers the perform_*_maintenance methods keep for their order columns, with the ``success`` column they all return"""
@@ -1537,6 +1665,7 @@ class BatchedPlantEnv:
         m = self._col(mask, torch.uint8)
         self._reset_carried_diagnostics(m)
         _lib.check(self.L.npb_restore(self._h, self._p(m), self._stream()), self._h)
+        self._refill_features(m)
         return self.get_observation()
 
     def set_start_bank(self, bank_env: Optional["BatchedPlantEnv"], slots=None, advance: Optional[int] = None) -> None:
@@ -1573,6 +1702,7 @@ class BatchedPlantEnv:
         m = self._col(mask, torch.uint8)
         self._reset_carried_diagnostics(m)
         _lib.check(self.L.npb_restore_bank(self._h, self._p(m), self._stream()), self._h)
+        self._refill_features(m)
         return self.get_observation()
 
     def _enable_autoreset(self, max_episode_steps: Optional[int]) -> None:
@@ -1653,6 +1783,7 @@ class BatchedPlantEnv:
         self._cstats = None
         self._ewin = None      # (the handle has freed the ring; the record columns go with it)
         self._task = None
+        self._feat = None
 
     def __del__(self):
         try:
@@ -1778,6 +1909,7 @@ class BatchedPlantEnv:
                 self._noise = self._make_noise(self._noise_seeds)
             if mask is None and self._profile is not None and self._streams is None:      # and a freshly started runner a freshly drawn profile
                 self._profile = PowerProfile(self, **self._profile_args)
+        self._refill_features(m)
         return self.get_observation()
 
     def ramp_setpoints(self, targets: torch.Tensor) -> torch.Tensor:
@@ -1864,9 +1996,19 @@ class BatchedPlantEnv:
             info.update(self._episode)
             if self._bank is not None:    # the episode kernel's, restoring from the bank: the bank entry this transition's episode started from
                 info["episode_start"] = self._episode_start_out
+        obs = self._obs
+        feat = getattr(self, "_feat", None)
+        if feat is not None:      # the caller's policy inputs, kept behind the step (set_features)
+            feat["unprimed"] = False
+            info["features"] = feat["out"]
+            if self._episode is not None and feat["final"] is not None:
+                info["final_features"] = feat["final"]
+            if feat["as_observation"]:
+                info["observation"] = obs
+                obs = feat["out"]
         if task is not None:
-            return self._obs, task["reward"], task["done"], info
-        return self._obs, self._reward, self._done, info
+            return obs, task["reward"], task["done"], info
+        return obs, self._reward, self._done, info
 
 
 def secondary_result(info: Dict[str, torch.Tensor], members: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
