@@ -1031,6 +1031,93 @@ NPB_API int npb_features_clear(NpbHandle *h, const uint8_t *mask, void *stream);
 NPB_API int npb_features_get_state(NpbHandle *h, int32_t *primed, int32_t *seen, void *stream);
 NPB_API int npb_features_set_state(NpbHandle *h, const int32_t *primed, const int32_t *seen, void *stream);
 
+/* Controls: the caller's policy outputs, decoded on the device in front of every step -- the action side of the task and the features.
+ * The caller names 1 .. NPB_CONTROLS_AXES_MAX axes; axis a reads element [p][a] of `in`, a contiguous row-major [n_plants][n_axes] tensor
+ * of float (NPB_CONTROLS_F32) or double (NPB_CONTROLS_F64) of the caller's, bound once.  No half types.  With controls set npb_step launches
+ * one kernel more (npd_controls.h; one wave per 64 plants, the wave's rows loaded with unit stride and transposed through LDS, no atomics),
+ * after the episode streams have taken their rows and in front of the step kernel.
+ * The transform of an element x, widened to double, every step rounded on its own (the library is built with -ffp-contract=off):
+ *   1. a NaN x becomes nan_to (finite);  2. y = x * scale + offset;  3. y = y < lo ? lo : y, then y = y > hi ? hi : y;
+ *   4. NPB_CONTROL_RATE only: fabs(y) < deadband gives y = 0.0 (fabs(y) == deadband stays).
+ * The kinds:
+ *   NPB_CONTROL_RATE(actuator)   actuator one of NPB_ACTUATOR_ROD, _FLOW, _VALVE, _BORON.  y is a signed magnitude: y > 0 is the
+ *       reference's move with the actuator's increasing ControlAction code (1, 2, 4, 10) at magnitude y, y < 0 the decreasing code (0, 3,
+ *       5, 9) at -y, y == 0 nothing.  The usual clip is [-1, 1].
+ *   NPB_CONTROL_TARGET(actuator) y is a position in the member's own units; the move is the reference's move at magnitude max_magnitude,
+ *       stopped at the target: with pos the member now, y > pos gives new = min(up, y), up what the increasing code at max_magnitude
+ *       makes of pos; y < pos gives new = max(down, y); y == pos nothing.  The actuator's range limit comes with up and down.
+ *   NPB_CONTROL_COLUMN(input)    input NPB_CONTROL_INPUT_POWER_SETPOINT or NPB_CONTROL_INPUT_COOLING_WATER_TEMP: y goes into a column
+ *       [n_plants] of the handle's, which npb_step hands to the step kernel as that input (the step's own setpoint clip still applies).
+ *   NPB_CONTROL_VALUE            y moves nothing and fills nothing: it is held like every axis, for the task, the features, the
+ *       statistics and the windows to read (a policy output the plant does not take but the reward prices).  With four actuators and two
+ *       inputs, each named at most once, these are what brings an input tensor to more than six columns.
+ * Both actuator kinds call the step's own npd_apply_control_actions: the rate expressions and the range limits are stated once.  Each
+ * actuator and each input may be named by at most one axis.
+ * Moving the actuators in front of the step is the same physics as the step's own action: control_rod_position, coolant_flow_rate,
+ * steam_valve_position and boron_concentration are read only inside the primary update, behind its call of npd_apply_control_actions,
+ * and in the observation at the end of the step; "move here, then step with NO_ACTION" is bit for bit "step with that action" (fp64
+ * storage; under fp32 storage the moved member is rounded to float at the store here, as npb_set_field rounds it).  The maintenance
+ * screen's cooldown cache watches the feedwater pumps' parameters, none of these four, and stays valid.  The caller may still pass
+ * action and magnitude to npb_step: the step kernel applies them behind the controls, as it always did.
+ * A lane stores only the members an axis changed, where the new bits differ from the old: a plant whose actuators do not move keeps its
+ * exact bits under either storage type.
+ * The hold: interval = K, 1 .. NPB_CONTROLS_INTERVAL_MAX.  Per plant the handle keeps age, primed and seen (int32 [n_plants]) and works on
+ * `held` and `prev` (double [n_axes][n_plants], device memory of the caller's like `in`, so that a task, features, statistics or windows
+ * can name a row of them as a side source).  A plant is unprimed when the controls are set, after npb_controls_clear(mask) and when the
+ * handle carries an episode index that differs from `seen` (the task's rule; this kernel runs before the step, so it sees the index the
+ * previous step's episode kernel left: the first step of a new episode starts a new hold).  Each step and plant: unprimed gives age = 0;
+ * if age % K == 0 the row is read and transformed, prev = held (for an unprimed plant prev = the new y), held = y; otherwise the row is
+ * not read and held is applied again (a held TARGET keeps moving towards its target, a held RATE repeats its move); then age += 1,
+ * primed = 1, seen = index.
+ * npb_controls_clear: the plants of mask (device uint8 [n_plants], NULL = all) become unprimed.  npb_controls_get_state /
+ * npb_controls_set_state move held, prev ([n_axes][n_plants]), age, primed and seen to and from host arrays, synchronous on `stream`.
+ * These return NPB_EINVAL when no controls are set.
+ * npb_set_controls(h, desc): desc = NULL turns the controls off; the descriptor is copied, every plant unprimed.  NPB_EINVAL with the
+ * reason in npb_last_error, before any device work, for what npb_controls_check refuses -- that check alone, without a handle, NULL =
+ * accepted, else the reason: n_plants < 1; an axis count or interval out of range, or a count without its array; an unknown kind,
+ * actuator or input; two axes on one target; a NaN or infinite scale, offset, nan_to, deadband or max_magnitude; deadband < 0 or
+ * max_magnitude < 0; a NaN lo or hi, or lo > hi; an unknown input type; a NULL or misaligned in (4-byte for float, 8-byte for double),
+ * held or prev; a POWER_SETPOINT axis under NPB_HEAT_EXTERNAL, where the column carries the plugin's power -- and on the handle a
+ * POWER_SETPOINT axis while episode streams drive the profile (likewise npb_set_episode_streams with a profile while such an axis is set).
+ * npb_step refuses a non-NULL caller column for an input an axis fills, naming the axis.
+ * No step, restore, episode, task or features kernel changes.  Not here: a discrete action table, a rate limit on the COLUMN kind
+ * (npb_profile_ramp), half-precision input, the feedwater action codes (the reference accepts them and they do nothing), K steps in
+ * one call.
+ * NPB_VERSION stays 154: a binding detects the entry points by name.  A handle that never calls this behaves as before in every entry
+ * point. */
+#define NPB_CONTROLS_AXES_MAX 8
+#define NPB_CONTROLS_INTERVAL_MAX 64
+enum { NPB_CONTROL_KIND_RATE = 0, NPB_CONTROL_KIND_TARGET = 1, NPB_CONTROL_KIND_COLUMN = 2, NPB_CONTROL_KIND_VALUE = 3 };
+enum { NPB_ACTUATOR_ROD = 0, NPB_ACTUATOR_FLOW = 1, NPB_ACTUATOR_VALVE = 2, NPB_ACTUATOR_BORON = 3, NPB_ACTUATOR_COUNT = 4 };
+enum { NPB_CONTROL_INPUT_POWER_SETPOINT = 0, NPB_CONTROL_INPUT_COOLING_WATER_TEMP = 1, NPB_CONTROL_INPUT_COUNT = 2 };
+enum { NPB_CONTROLS_F32 = 0, NPB_CONTROLS_F64 = 1 };
+/* the members kind, target of an npb_control_axis_t initialiser */
+#define NPB_CONTROL_RATE(actuator) NPB_CONTROL_KIND_RATE, (actuator)
+#define NPB_CONTROL_TARGET(actuator) NPB_CONTROL_KIND_TARGET, (actuator)
+#define NPB_CONTROL_COLUMN(input) NPB_CONTROL_KIND_COLUMN, (input)
+#define NPB_CONTROL_VALUE NPB_CONTROL_KIND_VALUE, 0
+typedef struct npb_control_axis_t {
+  int kind, target;              /* NPB_CONTROL_RATE(actuator), NPB_CONTROL_TARGET(actuator), NPB_CONTROL_COLUMN(input) or NPB_CONTROL_VALUE */
+  double scale, offset;          /* y = x * scale + offset */
+  double lo, hi;                 /* the clip; -inf / +inf = none */
+  double nan_to;                 /* what a NaN x becomes; finite */
+  double deadband;               /* RATE: fabs(y) < deadband gives 0; >= 0 */
+  double max_magnitude;          /* TARGET: the magnitude of one step's move; >= 0 */
+} npb_control_axis_t;
+typedef struct npb_controls_desc_t {
+  int n_axes; const npb_control_axis_t *axes;      /* host */
+  int interval;                  /* K */
+  int in_type;                   /* NPB_CONTROLS_F32 | NPB_CONTROLS_F64 */
+  const void *in;                /* device [n_plants][n_axes] */
+  double *held, *prev;           /* device [n_axes][n_plants] each */
+} npb_controls_desc_t;
+NPB_API int npb_set_controls(NpbHandle *h, const npb_controls_desc_t *desc);
+NPB_API const char *npb_controls_check(const npb_controls_desc_t *desc, int n_plants, int heat_source);
+NPB_API int npb_controls_clear(NpbHandle *h, const uint8_t *mask, void *stream);
+NPB_API int npb_controls_get_state(NpbHandle *h, double *held, double *prev, int32_t *age, int32_t *primed, int32_t *seen, void *stream);
+NPB_API int npb_controls_set_state(NpbHandle *h, const double *held, const double *prev, const int32_t *age, const int32_t *primed,
+                                   const int32_t *seen, void *stream);
+
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the
  * rocprofv3 FETCH_SIZE / WRITE_SIZE counters (tools/profile_traffic.py). */

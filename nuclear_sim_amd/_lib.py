@@ -451,13 +451,14 @@ def _summary_side(word, k, summary_keys, what):
     return ("n_created" if word == "work_order" else "n_completed", int(k), 1, "i32")
 
 
-def column_word(col, info_columns=None, task: bool = False, integer_sides: bool = False, summary_keys: int = 0) -> dict:
+def column_word(col, info_columns=None, task: bool = False, integer_sides: bool = False, summary_keys: int = 0, controls: int = 0) -> dict:
     """THE resolver of a per-plant column word, for ``column_stats_request``, ``event_windows_request``, ``task_request`` and whoever reads
     a column next; a pure function, an unknown word is refused (ValueError).  Every vocabulary has the state members as ``set_fields`` keys
     them (``name``, ``(name, instance)`` or ``(name, instance, k)``), ``("info", column_name)``, ``("obs", i)`` and ``"reward"``.  ``task``:
     a task is set, so ``"task_reward"`` is a word too (statistics and windows; a task's own columns never admit it).  ``integer_sides``:
     the task's further words ``"flags"``, ``"done"``, ``"maintenance"`` and ``("work_order" | "completed", key_index)`` with ``summary_keys``
-    keys in the summary.  Returns {"member": (kind, slot) -- 0 f64 / 1 i32, as npb_gather_fields takes them -- or None, "side": (buffer,
+    keys in the summary.  ``controls``: the axis count while controls are set (``BatchedPlantEnv.set_controls``), so ``("control", a)`` and
+    ``("control_prev", a)`` -- axis a's row of the held and of the previous action, real-valued -- are words too.  Returns {"member": (kind, slot) -- 0 f64 / 1 i32, as npb_gather_fields takes them -- or None, "side": (buffer,
     element offset, plant stride, element type) over the buffers of ``BatchedPlantEnv._side_buffers`` or None, "integer": bool}."""
     if info_columns is None:
         from .env import INFO_COLUMNS as info_columns
@@ -469,6 +470,10 @@ def column_word(col, info_columns=None, task: bool = False, integer_sides: bool 
         side = _summary_side(key[0], key[1], summary_keys, "column")
     elif key == ("reward",):
         side = ("reward", 0, 1, "f64")
+    elif controls and len(key) == 2 and key[0] in ("control", "control_prev"):
+        if isinstance(key[1], bool) or not isinstance(key[1], (int, np.integer)) or not 0 <= key[1] < controls:
+            raise ValueError("the column %r: the controls' axes are 0 .. %d, not %r" % (key[0], controls - 1, key[1]))
+        side = (key[0], int(key[1]), 1, "f64")
     elif key == ("task_reward",):
         if not task:
             raise ValueError("the column 'task_reward' needs a task: set_task() first")
@@ -495,7 +500,8 @@ def column_word(col, info_columns=None, task: bool = False, integer_sides: bool 
     return {"member": member, "side": side, "integer": member[0] == 1 if member else side[3] in ("i32", "u8")}
 
 
-def column_stats_request(columns, limits=None, stats=("min", "max", "sum", "sumsq", "last"), info_columns=None, task: bool = False) -> dict:
+def column_stats_request(columns, limits=None, stats=("min", "max", "sum", "sumsq", "last"), info_columns=None, task: bool = False,
+                         controls: int = 0) -> dict:
     """What ``BatchedPlantEnv.enable_column_stats`` asks of npb_set_column_stats, from the caller's words; a pure function, host only, so an
     unknown name, index or statistic is refused (ValueError) before any device work.  ``columns``: a state member as ``set_fields`` keys it
     (``name``, ``(name, instance)`` or ``(name, instance, k)``), ``("info", column_name)``, ``("obs", i)`` or ``"reward"``.  ``limits``:
@@ -514,7 +520,7 @@ def column_stats_request(columns, limits=None, stats=("min", "max", "sum", "sums
             raise ValueError("unknown statistic %r: one of %r" % (name, COLUMN_STATS))
     members, sides, where = [], [], []
     for col in columns:
-        C = column_word(col, info_columns, task)
+        C = column_word(col, info_columns, task, controls=controls)
         if C["member"]:
             where.append(("member", len(members))); members.append(C["member"])
         else:
@@ -556,7 +562,7 @@ class NpbEventWindowsDesc(ctypes.Structure):
                [(name, ctypes.c_void_p) for name in EVENT_WINDOW_WORDS + ("fired", "time", "times", "values", "cursor")]
 
 
-def event_windows_request(columns, triggers, pre, post, info_columns=None, summary_keys: int = 0, task: bool = False) -> dict:
+def event_windows_request(columns, triggers, pre, post, info_columns=None, summary_keys: int = 0, task: bool = False, controls: int = 0) -> dict:
     """What ``BatchedPlantEnv.enable_event_windows`` asks of npb_set_event_windows, from the caller's words; a pure function, host only, so
     an unknown name or a trigger that cannot work is refused (ValueError) before any device work.  ``columns`` as ``column_stats_request``
     takes them, 1 to 16.  ``triggers``: 1 to 8, each ``("trip", mask)`` (rising bits of the step's trip flags), ``("done",)``,
@@ -571,7 +577,7 @@ def event_windows_request(columns, triggers, pre, post, info_columns=None, summa
     columns = list(columns)
     if not 1 <= len(columns) <= EVENT_WINDOW_COLS_MAX:
         raise ValueError("event windows take 1 to %d columns, not %d" % (EVENT_WINDOW_COLS_MAX, len(columns)))
-    req = column_stats_request(columns, None, ("last",), info_columns, task)
+    req = column_stats_request(columns, None, ("last",), info_columns, task, controls)
     triggers = list(triggers)
     if not 1 <= len(triggers) <= EVENT_WINDOW_TRIGGERS_MAX:
         raise ValueError("event windows take 1 to %d triggers, not %d" % (EVENT_WINDOW_TRIGGERS_MAX, len(triggers)))
@@ -605,7 +611,7 @@ def event_windows_request(columns, triggers, pre, post, info_columns=None, summa
         elif len(t) == 3 and t[1] in (">", "<"):
             if np.isnan(float(t[2])):
                 raise ValueError("the limit of trigger %r is NaN" % (t,))
-            C = column_word(t[0], info_columns, task)
+            C = column_word(t[0], info_columns, task, controls=controls)
             T.update(member=C["member"], side=C["side"], mode="beyond", direction=1 if t[1] == ">" else -1, limit=float(t[2]))
             as_numpy.append((t[1], float(t[2])))
         else:
@@ -646,7 +652,7 @@ class NpbTaskDesc(ctypes.Structure):
                 ("terms_out", ctypes.c_void_p)]
 
 
-def task_request(reward=(), terminate=(), bias: float = 0.0, info_columns=None, summary_keys: int = 0) -> dict:
+def task_request(reward=(), terminate=(), bias: float = 0.0, info_columns=None, summary_keys: int = 0, controls: int = 0) -> dict:
     """What ``BatchedPlantEnv.set_task`` asks of npb_set_task, from the caller's words; a pure function, host only, so a word that cannot
     work is refused (ValueError, naming it) before any device work.
     A column is keyed as ``column_stats_request`` keys it -- a state member, ``("info", name)``, ``("obs", i)``, ``"reward"`` (the step's
@@ -678,7 +684,7 @@ def task_request(reward=(), terminate=(), bias: float = 0.0, info_columns=None, 
         key = (col,) if isinstance(col, str) else tuple(col)
         if key in index:
             return index[key]
-        C = column_word(col, info_columns, integer_sides=True, summary_keys=summary_keys)      # (an unknown word is refused there)
+        C = column_word(col, info_columns, integer_sides=True, summary_keys=summary_keys, controls=controls)      # (an unknown word is refused there)
         index[key] = len(columns)
         columns.append(C)
         return index[key]
@@ -766,7 +772,8 @@ class NpbFeaturesDesc(ctypes.Structure):
                 ("out", ctypes.c_void_p), ("final", ctypes.c_void_p)]
 
 
-def features_request(columns, stack: int = 1, dtype="float32", info_columns=None, task: bool = False, summary_keys: int = 0) -> dict:
+def features_request(columns, stack: int = 1, dtype="float32", info_columns=None, task: bool = False, summary_keys: int = 0,
+                     controls: int = 0) -> dict:
     """What ``BatchedPlantEnv.set_features`` asks of npb_set_features, from the caller's words; a pure function, host only, so a word that
     cannot work is refused (ValueError, naming it) before any device work.
     ``columns``: 1 to 64, each a column word or ``(word, options)``.  A word is what ``column_word`` resolves: a state member,
@@ -796,7 +803,7 @@ def features_request(columns, stack: int = 1, dtype="float32", info_columns=None
     def row(col):
         key = (col,) if isinstance(col, str) else tuple(col)
         if key not in index:
-            C = column_word(col, info_columns, task, integer_sides=True, summary_keys=summary_keys)      # (an unknown word is refused there)
+            C = column_word(col, info_columns, task, integer_sides=True, summary_keys=summary_keys, controls=controls)      # (an unknown word is refused there)
             index[key] = len(rows)
             rows.append(C)
         return index[key]
@@ -850,6 +857,108 @@ def features_request(columns, stack: int = 1, dtype="float32", info_columns=None
         D["fresh"] = number(opts.get("fresh", 0.0), "fresh", where)
         spec.append(D)
     return {"columns": rows, "spec": {"stack": int(stack), "dtype": name, "columns": spec}}
+
+
+# include/npb.h npb_controls_desc_t: the caller's policy outputs, decoded on the device in front of every step (npb_set_controls)
+CONTROLS_AXES_MAX, CONTROLS_INTERVAL_MAX = 8, 64
+CONTROL_KINDS = {"rate": 0, "target": 1, "column": 2, "value": 3}                  # NPB_CONTROL_KIND_* (controls.KINDS)
+CONTROL_ACTUATORS = {"rod": 0, "flow": 1, "valve": 2, "boron": 3}      # NPB_ACTUATOR_* (controls.ACTUATORS)
+CONTROL_INPUTS = {"power_setpoint": 0, "cooling_water_temp": 1}        # NPB_CONTROL_INPUT_* (controls.INPUTS)
+CONTROL_DTYPES = {"float32": 0, "float64": 1}                          # NPB_CONTROLS_F32 / NPB_CONTROLS_F64 (controls.DTYPES)
+CONTROL_OPTIONS = ("scale", "offset", "clip", "nan_to", "deadband", "max_magnitude")
+
+
+class NpbControlAxis(ctypes.Structure):
+    """npb_control_axis_t: one axis, its transform and what it moves or fills"""
+    _fields_ = [("kind", ctypes.c_int), ("target", ctypes.c_int), ("scale", ctypes.c_double), ("offset", ctypes.c_double), ("lo", ctypes.c_double),
+                ("hi", ctypes.c_double), ("nan_to", ctypes.c_double), ("deadband", ctypes.c_double), ("max_magnitude", ctypes.c_double)]
+
+
+class NpbControlsDesc(ctypes.Structure):
+    """npb_controls_desc_t: the axes (a host array), the hold interval, the input type and the caller's device tensors (``input``: the
+    header's ``in``)"""
+    _fields_ = [("n_axes", ctypes.c_int), ("axes", ctypes.POINTER(NpbControlAxis)), ("interval", ctypes.c_int), ("in_type", ctypes.c_int),
+                ("input", ctypes.c_void_p), ("held", ctypes.c_void_p), ("prev", ctypes.c_void_p)]
+
+
+def controls_request(axes, interval: int = 1, dtype="float32", heat_source: int = 0) -> dict:
+    """What ``BatchedPlantEnv.set_controls`` asks of npb_set_controls, from the caller's words; a pure function, host only, so an axis that
+    cannot work is refused (ValueError, naming it) before any device work.
+    ``axes``: 1 to 8, each ``(target, kind)`` or ``(target, kind, options)``: ``("rod" | "flow" | "valve" | "boron", "rate" | "target")`` or
+    ``("power_setpoint" | "cooling_water_temp", "column")``, or ``(None, "value")`` for an output that moves nothing and is only held, for
+    the task and the features to read.  ``options``: a dict of ``"scale"`` and ``"offset"`` (y = x * scale + offset),
+    ``"clip": (lo, hi)`` (None = that side open; a rate's default is (-1, 1)), ``"nan_to"`` (what a NaN x becomes, default 0.0),
+    ``"deadband"`` (a rate: |y| below it gives 0) and ``"max_magnitude"`` (a target: the magnitude of one step's move, default 1.0).
+    ``interval``: K, 1 to 64, the steps a decoded row is held.  ``dtype``: float32 or float64, as a name, a numpy dtype or a torch dtype.
+    ``heat_source``: the handle's (a "power_setpoint" axis is refused under the external heat source, whose plugin owns that column).
+    Returns the spec ``controls.Decoder`` takes: {"interval", "dtype", "axes": [{"kind", "target", "scale", "offset", "lo", "hi", "nan_to",
+    "deadband", "max_magnitude"}]}."""
+    axes = list(axes)
+    if not 1 <= len(axes) <= CONTROLS_AXES_MAX:
+        raise ValueError("controls take 1 to %d axes, not %d" % (CONTROLS_AXES_MAX, len(axes)))
+    if isinstance(interval, bool) or not isinstance(interval, (int, np.integer)) or not 1 <= interval <= CONTROLS_INTERVAL_MAX:
+        raise ValueError("the interval must be 1 .. %d, not %r" % (CONTROLS_INTERVAL_MAX, interval))
+    try:
+        name = np.dtype(dtype).name
+    except TypeError:      # (a torch dtype: "torch.float32")
+        name = str(dtype).rsplit(".", 1)[-1]
+    if name not in CONTROL_DTYPES:
+        raise ValueError("the input type must be float32 or float64 (no half types), not %r" % (dtype,))
+
+    def number(x, what, where):
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise ValueError("%s: %s must be a number, not %r" % (where, what, x))
+        if not np.isfinite(float(x)):
+            raise ValueError("%s: %s must be finite, not %r" % (where, what, x))
+        return float(x)
+
+    spec, taken = [], {}
+    for a, ax in enumerate(axes):
+        where = "control axis %d %r" % (a, ax)
+        if not isinstance(ax, (tuple, list)) or len(ax) not in (2, 3) or (len(ax) == 3 and not isinstance(ax[2], dict)):
+            raise ValueError("%s: an axis is (target, kind) or (target, kind, options)" % where)
+        target, kind, opts = ax[0], ax[1], (ax[2] if len(ax) == 3 else {})
+        if kind not in CONTROL_KINDS:
+            raise ValueError("%s: unknown kind %r: one of %r" % (where, kind, tuple(CONTROL_KINDS)))
+        names = CONTROL_INPUTS if kind == "column" else CONTROL_ACTUATORS if kind != "value" else (None,)
+        if target not in names:
+            raise ValueError("%s: unknown %s %r: one of %r" % (where, "input" if kind == "column" else "actuator", target, tuple(names)))
+        if target is not None and target in taken:
+            raise ValueError("%s: %r is already taken by axis %d" % (where, target, taken[target]))
+        taken[target] = a
+        for key in opts:
+            if key not in CONTROL_OPTIONS:
+                raise ValueError("%s: unknown option %r: one of %r" % (where, key, CONTROL_OPTIONS))
+        if "deadband" in opts and kind != "rate":
+            raise ValueError("%s: 'deadband' is a rate's option" % where)
+        if "max_magnitude" in opts and kind != "target":
+            raise ValueError("%s: 'max_magnitude' is a target's option" % where)
+        D = {"kind": kind, "target": target, "scale": number(opts.get("scale", 1.0), "the scale", where),
+             "offset": number(opts.get("offset", 0.0), "the offset", where), "lo": -1.0 if kind == "rate" else -np.inf,
+             "hi": 1.0 if kind == "rate" else np.inf, "nan_to": number(opts.get("nan_to", 0.0), "nan_to", where),
+             "deadband": number(opts.get("deadband", 0.0), "the deadband", where),
+             "max_magnitude": number(opts.get("max_magnitude", 1.0), "max_magnitude", where)}
+        if D["deadband"] < 0:
+            raise ValueError("%s: a negative deadband" % where)
+        if D["max_magnitude"] < 0:
+            raise ValueError("%s: a negative max_magnitude" % where)
+        if "clip" in opts:
+            clip = opts["clip"]
+            if not isinstance(clip, (tuple, list)) or len(clip) != 2:
+                raise ValueError("%s: 'clip' is (lo, hi), either None for an open side" % where)
+            for side, x, open_side in (("lo", clip[0], -np.inf), ("hi", clip[1], np.inf)):
+                if x is None:
+                    D[side] = open_side
+                elif isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or np.isnan(float(x)):
+                    raise ValueError("%s: the clip limits must be numbers (or None), not %r" % (where, x))
+                else:
+                    D[side] = float(x)
+            if D["lo"] > D["hi"]:
+                raise ValueError("%s: a clip with lo > hi" % where)
+        if target == "power_setpoint" and heat_source == HEAT_EXTERNAL:
+            raise ValueError("%s: under the external heat source the power_setpoint column carries the plugin's power" % where)
+        spec.append(D)
+    return {"interval": int(interval), "dtype": name, "axes": spec}
 
 
 def episode_streams_desc(block, bank_noise_seeds=None, bank_profile_seeds=None, outputs=(None, None, None)):
@@ -1051,6 +1160,13 @@ def load():
         L.npb_features_clear.argtypes = [vp, vp, vp]
         L.npb_features_get_state.argtypes = [vp, vp, vp, vp]
         L.npb_features_set_state.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "npb_set_controls"):     # the caller's policy outputs: decoded in front of every step
+        L.npb_set_controls.argtypes = [vp, ctypes.POINTER(NpbControlsDesc)]
+        L.npb_controls_check.argtypes = [ctypes.POINTER(NpbControlsDesc), ci, ci]
+        L.npb_controls_check.restype = ctypes.c_char_p
+        L.npb_controls_clear.argtypes = [vp, vp, vp]
+        L.npb_controls_get_state.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.npb_controls_set_state.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "npb_set_event_windows"):     # state windows around events, captured behind every step
         L.npb_set_event_windows.argtypes = [vp, ctypes.POINTER(NpbEventWindowsDesc)]
         L.npb_event_windows_check.argtypes = [ctypes.POINTER(NpbEventWindowsDesc), ci, ci]

@@ -83,6 +83,9 @@ struct NpbHandle {
   npb_task_t task; bool ert_on; int32_t *ert_cause;
   /* npb_set_features: the columns and the bookkeeping on the device (feat.cols = the one allocation; NULL = off) and the caller's tensors */
   npb_features_t feat;
+  /* npb_set_controls: the axes, the caller's tensors and the handle's bookkeeping and input columns (ctl.age = the one allocation; NULL =
+   * off); ctl_axis[input]: the axis that fills that input column, -1 = none */
+  npb_controls_t ctl; int ctl_axis[NPB_CONTROL_INPUT_COUNT];
   double *ramp_prev;   /* npb_profile_ramp: the previous setpoint of every plant ([pitch], NaN = none yet), allocated on first use */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
   std::vector<int> plan_key;
@@ -515,6 +518,7 @@ int npb_destroy(NpbHandle *h) {
   if (h->ew.cols) (void)hipFree((void *)h->ew.cols);
   if (h->task.terms) (void)hipFree((void *)h->task.terms);
   if (h->feat.cols) (void)hipFree((void *)h->feat.cols);
+  if (h->ctl.age) (void)hipFree((void *)h->ctl.age);
   for (Sampler *sm : h->samplers) if (sm) { (void)hipFree(sm->dev); delete sm; }
   delete h;
   return NPB_OK;
@@ -1045,6 +1049,16 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
     return fail(h, NPB_EINVAL, "npb_step: episode records with final_obs are on (npb_set_episode_records) and copy the terminal row of the obs column: it must not be NULL");
   if (h->params.heat_source == NPB_HEAT_EXTERNAL && !noise_z)      /* a NULL column would read as 0 MW thermal, silently */
     return fail(h, NPB_EINVAL, "npb_step: params.heat_source is NPB_HEAT_EXTERNAL, whose thermal power arrives in the noise_z column (include/npb_params.h): it must not be NULL");
+  if (h->ctl.age) {      /* an input an axis fills has one writer */
+    const double *const given[NPB_CONTROL_INPUT_COUNT] = {power_setpoint, cooling_water_temp};
+    static const char *const name[NPB_CONTROL_INPUT_COUNT] = {"power_setpoint", "cooling_water_temp"};
+    for (int i = 0; i < NPB_CONTROL_INPUT_COUNT; i++)
+      if (h->ctl_axis[i] >= 0 && given[i]) {
+        char what[200];
+        snprintf(what, sizeof what, "npb_step: the %s column must be NULL: axis %d of the controls fills it (npb_set_controls)", name[i], h->ctl_axis[i]);
+        return fail(h, NPB_EINVAL, what);
+      }
+  }
   /* what the autoreset's restores take along beside the arena, from the bank while it has slots, else from the snapshot.  The step
    * reports a source without the diagnostics rows first, then the component maintenance's own needs, then a source without its state */
   const bool from_bank = h->bank && h->next_slot;
@@ -1074,6 +1088,11 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
     /* the rows taken go into the caller's columns in the restart kernel's launch behind the step (the mode needs the autoreset) */
     es_take = npb_episode_streams_take_t{noise_z, power_setpoint, target, take_noise ? h->es_noise_out : nullptr, take_prof ? h->es_setpoint_out : nullptr,
                                          take_prof ? h->es_target_out : nullptr};
+  }
+  if (h->ctl.age) {      /* the caller's policy outputs: the actuators moved, the input columns filled, in front of the step */
+    h->K->controls(h->f64, NPB_N(h), &h->ctl, &h->params, h->n_plants, h->ep_index, (hipStream_t)stream);
+    if (h->ctl_axis[NPB_CONTROL_INPUT_POWER_SETPOINT] >= 0) power_setpoint = h->ctl.column[NPB_CONTROL_INPUT_POWER_SETPOINT];
+    if (h->ctl_axis[NPB_CONTROL_INPUT_COOLING_WATER_TEMP] >= 0) cooling_water_temp = h->ctl.column[NPB_CONTROL_INPUT_COOLING_WATER_TEMP];
   }
   npb_maint_table_t table;
   const bool maint = h->params.maint_enabled != 0;
@@ -2034,6 +2053,124 @@ int npb_features_set_state(NpbHandle *h, const int32_t *primed, const int32_t *s
   return NPB_OK;
 }
 
+/* ---- controls (include/npb.h, npd_controls.h) */
+static bool is_finite(double x) { return x - x == 0.0; }
+const char *npb_controls_check(const npb_controls_desc_t *D, int n_plants, int heat_source) {
+  if (!D) return nullptr;
+  if (n_plants < 1) return "npb_set_controls: n_plants must be >= 1";
+  if (D->n_axes < 1 || D->n_axes > NPB_CONTROLS_AXES_MAX || !D->axes)
+    return "npb_set_controls: the axis count must be 1 .. NPB_CONTROLS_AXES_MAX (8), with their descriptors";
+  if (D->interval < 1 || D->interval > NPB_CONTROLS_INTERVAL_MAX) return "npb_set_controls: the interval must be 1 .. NPB_CONTROLS_INTERVAL_MAX (64)";
+  bool actuator[NPB_ACTUATOR_COUNT] = {}, input[NPB_CONTROL_INPUT_COUNT] = {};
+  for (int a = 0; a < D->n_axes; a++) {
+    const npb_control_axis_t &X = D->axes[a];
+    if (X.kind == NPB_CONTROL_KIND_RATE || X.kind == NPB_CONTROL_KIND_TARGET) {
+      if (X.target < 0 || X.target >= NPB_ACTUATOR_COUNT) return "npb_set_controls: an unknown actuator";
+      if (actuator[X.target]) return "npb_set_controls: two axes on one actuator";
+      actuator[X.target] = true;
+    } else if (X.kind == NPB_CONTROL_KIND_COLUMN) {
+      if (X.target < 0 || X.target >= NPB_CONTROL_INPUT_COUNT) return "npb_set_controls: an unknown input";
+      if (input[X.target]) return "npb_set_controls: two axes on one input";
+      input[X.target] = true;
+    } else if (X.kind != NPB_CONTROL_KIND_VALUE) {
+      return "npb_set_controls: an unknown control kind";
+    }
+    if (!is_finite(X.scale) || !is_finite(X.offset) || !is_finite(X.nan_to) || !is_finite(X.deadband) || !is_finite(X.max_magnitude))
+      return "npb_set_controls: a NaN or infinite scale, offset, nan_to, deadband or max_magnitude";
+    if (X.deadband < 0.0) return "npb_set_controls: a negative deadband";
+    if (X.max_magnitude < 0.0) return "npb_set_controls: a negative max_magnitude";
+    if (X.lo != X.lo || X.hi != X.hi) return "npb_set_controls: a NaN clip limit (lo, hi)";
+    if (X.lo > X.hi) return "npb_set_controls: a clip with lo > hi";
+  }
+  if (D->in_type != NPB_CONTROLS_F32 && D->in_type != NPB_CONTROLS_F64) return "npb_set_controls: an unknown input type";
+  if (!D->in) return "npb_set_controls: a NULL in tensor";
+  if ((uintptr_t)D->in & (D->in_type == NPB_CONTROLS_F64 ? 7u : 3u))
+    return "npb_set_controls: a misaligned in tensor: 4-byte aligned for float, 8-byte for double";
+  if (!D->held || !D->prev) return "npb_set_controls: NULL held or prev";
+  if (((uintptr_t)D->held | (uintptr_t)D->prev) & 7u) return "npb_set_controls: misaligned held or prev: 8-byte aligned";
+  if (input[NPB_CONTROL_INPUT_POWER_SETPOINT] && heat_source == NPB_HEAT_EXTERNAL)
+    return "npb_set_controls: a POWER_SETPOINT axis under NPB_HEAT_EXTERNAL, where the power_setpoint column carries the plugin's power";
+  return nullptr;
+}
+int npb_set_controls(NpbHandle *h, const npb_controls_desc_t *desc) {
+  if (!h) return NPB_EINVAL;
+  if (const char *why = npb_controls_check(desc, h->n_plants, h->params.heat_source)) return fail(h, NPB_EINVAL, why);
+  if (!desc) {
+    if (h->ctl.age) { NPB_USE_DEVICE(h); (void)hipFree((void *)h->ctl.age); }      /* (hipFree waits for the device: a launch still in flight finishes first) */
+    h->ctl = npb_controls_t{};
+    return NPB_OK;
+  }
+  npb_controls_t C = {};
+  int axis_of[NPB_CONTROL_INPUT_COUNT] = {-1, -1};
+  for (int a = 0; a < desc->n_axes; a++) {
+    C.axes[a] = desc->axes[a];
+    if (desc->axes[a].kind == NPB_CONTROL_KIND_COLUMN) axis_of[desc->axes[a].target] = a;
+  }
+  if (axis_of[NPB_CONTROL_INPUT_POWER_SETPOINT] >= 0 && h->es_on && h->es.prof.key)
+    return fail(h, NPB_EINVAL, "npb_set_controls: a POWER_SETPOINT axis while episode streams drive the profile (npb_set_episode_streams)");
+  NPB_USE_DEVICE(h);
+  /* the handle's one allocation: age [n] | primed [n] | seen [n] (padded to 8 bytes) | the two input columns [n] each; all zero: every
+   * plant unprimed */
+  const size_t n = (size_t)h->n_plants, words = (3 * n + 1) & ~(size_t)1, bytes = words * sizeof(int32_t) + NPB_CONTROL_INPUT_COUNT * n * sizeof(double);
+  char *dev = nullptr;
+  hipError_t e = hipMalloc((void **)&dev, bytes);
+  if (e != hipSuccess) {
+    char what[160];
+    snprintf(what, sizeof what, "npb_set_controls: hipMalloc of the bookkeeping and the input columns (%zu bytes) failed", bytes);
+    return fail(h, NPB_EHIP, what, e);
+  }
+  e = hipMemset(dev, 0, bytes);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess) { (void)hipFree(dev); return fail(h, NPB_EHIP, "npb_set_controls: setting up the bookkeeping failed", e); }
+  C.n_axes = desc->n_axes; C.interval = desc->interval; C.in_f64 = desc->in_type == NPB_CONTROLS_F64;
+  C.in = desc->in; C.held = desc->held; C.prev = desc->prev;
+  C.age = (int32_t *)dev; C.primed = C.age + n; C.seen = C.primed + n;
+  for (int i = 0; i < NPB_CONTROL_INPUT_COUNT; i++) C.column[i] = (double *)(dev + words * sizeof(int32_t)) + (size_t)i * n;
+  if (h->ctl.age) (void)hipFree((void *)h->ctl.age);
+  h->ctl = C;
+  for (int i = 0; i < NPB_CONTROL_INPUT_COUNT; i++) h->ctl_axis[i] = axis_of[i];
+  return NPB_OK;
+}
+int npb_controls_clear(NpbHandle *h, const uint8_t *mask, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->ctl.age) return fail(h, NPB_EINVAL, "npb_controls_clear: no controls set (npb_set_controls first)");
+  NPB_USE_DEVICE(h);
+  npb_launch_controls_clear(&h->ctl, mask, h->n_plants, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_controls_get_state(NpbHandle *h, double *held, double *prev, int32_t *age, int32_t *primed, int32_t *seen, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->ctl.age) return fail(h, NPB_EINVAL, "npb_controls_get_state: no controls set (npb_set_controls first)");
+  if (!held || !prev || !age || !primed || !seen) return fail(h, NPB_EINVAL, "npb_controls_get_state: NULL output");
+  NPB_USE_DEVICE(h);
+  const size_t n = (size_t)h->n_plants, values = (size_t)h->ctl.n_axes * n * sizeof(double);
+  hipStream_t st = (hipStream_t)stream;
+  NPB_HIP(h, hipMemcpyAsync(held, h->ctl.held, values, hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpyAsync(prev, h->ctl.prev, values, hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpyAsync(age, h->ctl.age, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpyAsync(primed, h->ctl.primed, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipMemcpyAsync(seen, h->ctl.seen, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NPB_HIP(h, hipStreamSynchronize(st));
+  return NPB_OK;
+}
+int npb_controls_set_state(NpbHandle *h, const double *held, const double *prev, const int32_t *age, const int32_t *primed, const int32_t *seen,
+                           void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->ctl.age) return fail(h, NPB_EINVAL, "npb_controls_set_state: no controls set (npb_set_controls first)");
+  if (!held || !prev || !age || !primed || !seen) return fail(h, NPB_EINVAL, "npb_controls_set_state: NULL input");
+  NPB_USE_DEVICE(h);
+  const size_t n = (size_t)h->n_plants, values = (size_t)h->ctl.n_axes * n * sizeof(double);
+  hipStream_t st = (hipStream_t)stream;
+  NPB_HIP(h, hipMemcpyAsync(h->ctl.held, held, values, hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(h->ctl.prev, prev, values, hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(h->ctl.age, age, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(h->ctl.primed, primed, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipMemcpyAsync(h->ctl.seen, seen, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  NPB_HIP(h, hipStreamSynchronize(st));      /* the host arrays may go */
+  return NPB_OK;
+}
+
 /* ---- episode streams (include/npb.h) */
 const char *npb_episode_streams_check(const npb_episode_streams_desc_t *desc, int has_generators, int bank_entries) {
   if (!desc) return nullptr;
@@ -2076,6 +2213,8 @@ int npb_set_episode_streams(NpbHandle *h, const npb_episode_streams_desc_t *desc
   if (const char *why = npb_episode_streams_check(desc, h->noise || h->prof, h->bank ? h->bank_M : 0)) return fail(h, NPB_EINVAL, why);
   if ((h->noise && h->noise_seeds.empty()) || (h->prof && h->prof_seeds.empty()))
     return fail(h, NPB_EINVAL, "npb_set_episode_streams: the noise generators were only ever loaded (npb_noise_set_state) and have no seed to restart from: npb_noise_seed first");
+  if (h->prof && h->ctl.age && h->ctl_axis[NPB_CONTROL_INPUT_POWER_SETPOINT] >= 0)
+    return fail(h, NPB_EINVAL, "npb_set_episode_streams: a POWER_SETPOINT axis of the controls fills the setpoint column the profile would drive (npb_set_controls)");
   if (!h->autoreset)
     return fail(h, NPB_EINVAL, "npb_set_episode_streams: needs the autoreset (npb_set_autoreset first): the restarts are read off the episode index it keeps");
   NPB_USE_DEVICE(h);

@@ -101,6 +101,14 @@ typedef struct {
   void *out, *final;
   int32_t *primed, *seen;
 } npb_features_t;
+/* npb_set_controls (npd_controls.h): the axes as the caller wrote them (uniform over the launch: kernel arguments), the caller's input
+ * tensor and held / prev [n_axes][n_plants], and of the handle's one allocation (age; NULL = off) the bookkeeping words and the two input
+ * columns [n_plants] (column[input]; NULL where no axis fills that input) */
+typedef struct {
+  npb_control_axis_t axes[NPB_CONTROLS_AXES_MAX]; int n_axes, interval, in_f64;
+  const void *in; double *held, *prev, *column[NPB_CONTROL_INPUT_COUNT];
+  int32_t *age, *primed, *seen;
+} npb_controls_t;
 typedef struct {
   int (*step)(const npb_params_t *P, int n_plants, size_t npad, void *arena, const int32_t *action,
               const double *magnitude, const double *setpoint, const double *noise_z, const double *cw_temp,
@@ -162,6 +170,9 @@ typedef struct {
    * kernel restarted (their stacks to `final`, then the fresh frame), 2 = the unprimed plants' fresh frame; index: the handle's carried
    * episode indices or NULL */
   void (*features)(const void *arena, size_t npad, const npb_features_t *F, int n_plants, int mode, const int32_t *index, hipStream_t stream);
+  /* npb_set_controls (npd_controls.h): every plant's row of the caller's input decoded in front of the step -- the actuators moved, the
+   * input columns filled, held / prev kept; index: the handle's carried episode indices or NULL */
+  void (*controls)(void *arena, size_t npad, const npb_controls_t *C, const npb_params_t *P, int n_plants, const int32_t *index, hipStream_t stream);
 } npb_launchers_t;
 extern npb_launchers_t npb_launch_table, npb32_launch_table;
 /* the same for either storage type */
@@ -194,6 +205,8 @@ void npb_launch_event_windows_clear(const npb_event_windows_t *W, const uint8_t 
 void npb_launch_task_clear(const npb_task_t *T, const uint8_t *mask, int n_plants, hipStream_t stream);
 /* npb_features_clear (npd_features.h): the plants of mask (NULL = all) unprimed */
 void npb_launch_features_clear(const npb_features_t *F, const uint8_t *mask, int n_plants, hipStream_t stream);
+/* npb_controls_clear (npd_controls.h): the plants of mask (NULL = all) unprimed */
+void npb_launch_controls_clear(const npb_controls_t *C, const uint8_t *mask, int n_plants, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -1609,13 +1609,14 @@ static void NPB_LAUNCHER(event_windows)(const void *arena, size_t npad, const np
                                         const int32_t *len, const uint8_t *done, int max_steps, hipStream_t stream);     /* the same */
 static void NPB_LAUNCHER(task)(const void *arena, size_t npad, const npb_task_t *T, int n_plants, const int32_t *index, hipStream_t stream);     /* the same */
 static void NPB_LAUNCHER(features)(const void *arena, size_t npad, const npb_features_t *F, int n_plants, int mode, const int32_t *index, hipStream_t stream);     /* the same */
+static void NPB_LAUNCHER(controls)(void *arena, size_t npad, const npb_controls_t *C, const npb_params_t *P, int n_plants, const int32_t *index, hipStream_t stream);     /* the same */
 /* not const: clang emits a namespace-scope const into the device code too, where these host functions do not exist */
 extern "C" npb_launchers_t NPB_LAUNCHER(table) = {
   NPB_LAUNCHER(step), NPB_LAUNCHER(maint), NPB_LAUNCHER(observe), NPB_LAUNCHER(init), NPB_LAUNCHER(reset),
   NPB_LAUNCHER(field_get), NPB_LAUNCHER(field_set), NPB_LAUNCHER(gather), NPB_LAUNCHER(restore), NPB_LAUNCHER(episode),
   NPB_LAUNCHER(operator_maint), NPB_LAUNCHER(operator_component_maint), NPB_LAUNCHER(operator_turbine_maint), NPB_LAUNCHER(maint_all),
   NPB_LAUNCHER(sample), NPB_LAUNCHER(episode_records), NPB_LAUNCHER(column_stats_fold), NPB_LAUNCHER(event_windows),
-  NPB_LAUNCHER(task), NPB_LAUNCHER(features),
+  NPB_LAUNCHER(task), NPB_LAUNCHER(features), NPB_LAUNCHER(controls),
 };
 #ifndef NPB_BUILD_F32
 /* npb_reset / npb_reset_reference / npb_restore: the episode counters (len, ret) and the carried start entries (start: -1, not from
@@ -1859,3 +1860,6 @@ static void NPB_LAUNCHER(episode_records)(int n_plants, size_t npad, const void 
 
 /* the caller's policy inputs (npb_set_features): the frame-stack kernel, the clear kernel and their launchers */
 #include "npd_features.h"
+
+/* the caller's policy outputs (npb_set_controls): the decode kernel in front of the step, the clear kernel and their launchers */
+#include "npd_controls.h"

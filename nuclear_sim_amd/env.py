@@ -1021,11 +1021,20 @@ class BatchedPlantEnv:
             buffers.update(n_created=ms["counts"][0], n_completed=ms["counts"][1])
         if tk is not None:
             buffers.update(task_reward=tk["reward"], task_cause=tk["cause"])
+        ct = getattr(self, "_ctl", None)
+        if ct is not None:
+            buffers.update(control=ct["held"], control_prev=ct["prev"])
         return buffers
 
+    def _n_controls(self) -> int:
+        """the axis count while controls are set, else 0: what ``_lib.column_word`` takes as ``controls``"""
+        ct = getattr(self, "_ctl", None)
+        return 0 if ct is None else ct["held"].shape[0]
+
     def _side_first(self, name, offset) -> int:
-        """the element of side buffer ``name`` that holds plant 0's value of the column at ``offset``: a summary table is [n_keys][n]"""
-        return offset * self.n if name in ("n_created", "n_completed") else offset
+        """the element of side buffer ``name`` that holds plant 0's value of the column at ``offset``: a summary table is [n_keys][n], the
+        controls' held and previous values [n_axes][n]"""
+        return offset * self.n if name in ("n_created", "n_completed", "control", "control_prev") else offset
 
     def _fill_source(self, S, buffers, name, offset, stride, kind="f64") -> None:
         """fill the NpbSampleSource ``S`` from a side column as ``_lib.column_word`` names it: one value per plant"""
@@ -1060,7 +1069,7 @@ class BatchedPlantEnv:
             self._cstats = None
             return
         tk = getattr(self, "_task", None)
-        req = _lib.column_stats_request(columns, limits, stats, INFO_COLUMNS, tk is not None)      # an unknown name, index or statistic is refused here
+        req = _lib.column_stats_request(columns, limits, stats, INFO_COLUMNS, tk is not None, self._n_controls())      # an unknown name, index or statistic is refused here
         if not hasattr(self.L, "npb_set_column_stats"):
             raise _lib.NpbError("libnpb.so has no npb_set_column_stats: rebuild")
         nm, ns = len(req["members"]), len(req["sides"])
@@ -1085,7 +1094,8 @@ class BatchedPlantEnv:
         d.n_samples = tables["n_samples"].data_ptr()
         _lib.check(self.L.npb_set_column_stats(self._h, ctypes.byref(d)), self._h)
         self._cstats = {"tables": tables, "stats": req["stats"], "order": req["order"], "columns": list(columns),
-                        "task": any(side[0] == "task_reward" for side in req["sides"])}
+                        "task": any(side[0] == "task_reward" for side in req["sides"]),
+                        "controls": any(side[0] in ("control", "control_prev") for side in req["sides"])}
 
     def column_stats(self) -> Dict[str, torch.Tensor]:
         """The statistics' tables, [n_cols, n] each in the order of ``columns``, and ``n_samples`` [n], on the device, never synchronised
@@ -1133,7 +1143,8 @@ class BatchedPlantEnv:
             return
         ms = getattr(self, "_msum", None)
         tk = getattr(self, "_task", None)
-        req = _lib.event_windows_request(columns, triggers or (), pre, post, INFO_COLUMNS, 0 if ms is None else len(ms["keys"]), tk is not None)
+        req = _lib.event_windows_request(columns, triggers or (), pre, post, INFO_COLUMNS, 0 if ms is None else len(ms["keys"]), tk is not None,
+                                         self._n_controls())
         if not hasattr(self.L, "npb_set_event_windows"):
             raise _lib.NpbError("libnpb.so has no npb_set_event_windows: rebuild")
         cap = max(self.n, 4096) if capacity is None else int(capacity)
@@ -1171,7 +1182,9 @@ class BatchedPlantEnv:
                       "bytes": int(self.L.npb_event_windows_bytes(ctypes.byref(d), self.n)),
                       "summary": ms["counts"] if any(T["side"] and T["side"][0] in ("n_created", "n_completed") for T in req["triggers"]) else None,
                       "task": any(side[0] == "task_reward" for side in req["sides"]) or
-                              any(T["side"] and T["side"][0] in ("task_reward", "task_cause") for T in req["triggers"])}
+                              any(T["side"] and T["side"][0] in ("task_reward", "task_cause") for T in req["triggers"]),
+                      "controls": any(side[0] in ("control", "control_prev") for side in req["sides"]) or
+                                  any(T["side"] and T["side"][0] in ("control", "control_prev") for T in req["triggers"])}
 
     def event_windows(self, clear: bool = True, allow_overflow: bool = False) -> Dict[str, np.ndarray]:
         """Drain the event windows on the env's stream, one read-back: numpy columns of m records sorted by (capture step, plant) --
@@ -1267,7 +1280,7 @@ class BatchedPlantEnv:
             self._task = None
             return
         ms = getattr(self, "_msum", None)
-        req = _lib.task_request(reward, terminate, bias, INFO_COLUMNS, 0 if ms is None else len(ms["keys"]))      # a bad word is refused here
+        req = _lib.task_request(reward, terminate, bias, INFO_COLUMNS, 0 if ms is None else len(ms["keys"]), self._n_controls())      # a bad word is refused here
         if not hasattr(self.L, "npb_set_task"):
             raise _lib.NpbError("libnpb.so has no npb_set_task: rebuild")
         for what, _user in self._task_readers():      # (they hold the old task's output columns)
@@ -1386,7 +1399,7 @@ class BatchedPlantEnv:
             self._feat = None
             return
         ms, tk = getattr(self, "_msum", None), getattr(self, "_task", None)
-        req = _lib.features_request(columns, stack, dtype, INFO_COLUMNS, tk is not None, 0 if ms is None else len(ms["keys"]))      # a bad word is refused here
+        req = _lib.features_request(columns, stack, dtype, INFO_COLUMNS, tk is not None, 0 if ms is None else len(ms["keys"]), self._n_controls())      # a bad word is refused here
         if not hasattr(self.L, "npb_set_features"):
             raise _lib.NpbError("libnpb.so has no npb_set_features: rebuild")
         spec, rows, buffers = req["spec"], req["columns"], self._side_buffers()
@@ -1488,6 +1501,114 @@ class BatchedPlantEnv:
                 name, offset, stride, _kind = C["side"]
                 rows.append(buffers[name].reshape(-1)[self._side_first(name, offset)::stride][:self.n].to(torch.float64))
         return torch.stack(rows)
+
+    def _control_readers(self):
+        """what reads the controls' held / previous columns: the names of the task, features, statistics and windows that do"""
+        def reads(rows):
+            return any(R.get("side") and R["side"][0] in ("control", "control_prev") for R in rows)
+        out = []
+        tk, ft, cs, ew = (getattr(self, name, None) for name in ("_task", "_feat", "_cstats", "_ewin"))
+        if tk is not None and reads(tk["request"]["columns"]):
+            out.append("the task")
+        if ft is not None and reads(ft["request"]["columns"]):
+            out.append("the features")
+        for what, user in (("the column statistics", cs), ("the event windows", ew)):
+            if user is not None and user.get("controls"):
+                out.append(what)
+        return out
+
+    def set_controls(self, axes, interval: int = 1, dtype=torch.float32) -> None:
+        """Define what the policy writes, on the device (npb_set_controls): in front of every step one more launch reads every plant's
+        row of a bound ``[n, len(axes)]`` tensor, transforms each element and moves the actuators or fills the input columns the axes
+        name.  Nothing is read back; nothing stands between the policy's output tensor and ``step()``.
+        ``axes``: 1 to 8, each ``(target, kind)`` or ``(target, kind, options)``:
+        ``("rod" | "flow" | "valve" | "boron", "rate")`` -- y is a signed magnitude, y > 0 the reference's move with the actuator's
+        increasing ControlAction at magnitude y, y < 0 the decreasing one at -y; ``(actuator, "target")`` -- y is a position the actuator
+        moves towards at ``max_magnitude`` per step and stops at; ``("power_setpoint" | "cooling_water_temp", "column")`` -- y is that
+        plant's value of the step's input; ``(None, "value")`` -- y moves nothing and is only held, for the task and the features to read.
+        ``options``: ``"scale"`` and ``"offset"`` (y = x * scale + offset), ``"clip": (lo, hi)`` (a
+        rate's default is (-1, 1)), ``"nan_to"`` (default 0.0), ``"deadband"`` (rate), ``"max_magnitude"`` (target, default 1.0).
+        ``interval``: K, a decoded row is held for K steps (a held target keeps moving, a held rate repeats its move); a plant's hold
+        restarts with its episode, and ``reset``, ``restore`` and ``restore_from_bank`` restart it for the plants they reset.
+        Several actuators may move in one step.  ``step(action, magnitude)`` still works: the step applies them behind the controls, as
+        it always did.  While controls are set ``("control", a)`` and ``("control_prev", a)`` -- axis a's held and previous value -- are
+        column words for ``set_task``, ``set_features``, ``enable_column_stats`` and ``enable_event_windows`` (effort: ``abs_err`` of
+        ``("control", a)`` against 0; jerk: ``sq_err`` against ``("control_prev", a)``), and ``step()`` adds ``info["controls"]``, the
+        held values ``[len(axes), n]``.  ``nuclear_sim_amd.controls`` is the same in numpy, bit for bit.  ``set_controls(None)`` turns
+        it off."""
+        old = getattr(self, "_ctl", None)
+        readers = self._control_readers() if old is not None else []
+        if readers:
+            raise _lib.NpbError("%s read(s) the controls' columns: turn that off first" % " and ".join(readers))
+        if axes is None:
+            if old is not None:
+                _lib.check(self.L.npb_set_controls(self._h, None), self._h)
+            self._ctl = None
+            return
+        spec = _lib.controls_request(axes, interval, dtype, self.params.heat_source)      # a bad axis is refused here
+        if self._profile is not None and any(D["target"] == "power_setpoint" for D in spec["axes"]):
+            raise ValueError("a 'power_setpoint' axis fills the column the power profile drives")
+        if not hasattr(self.L, "npb_set_controls"):
+            raise _lib.NpbError("libnpb.so has no npb_set_controls: rebuild")
+        A = len(spec["axes"])
+        cax = (_lib.NpbControlAxis * A)()
+        for k, D in enumerate(spec["axes"]):
+            X = cax[k]
+            X.kind = _lib.CONTROL_KINDS[D["kind"]]
+            X.target = 0 if D["target"] is None else (_lib.CONTROL_INPUTS if D["kind"] == "column" else _lib.CONTROL_ACTUATORS)[D["target"]]
+            X.scale, X.offset, X.lo, X.hi, X.nan_to, X.deadband, X.max_magnitude = (D[name] for name in ("scale", "offset", "lo", "hi", "nan_to",
+                                                                                                          "deadband", "max_magnitude"))
+        tdtype = torch.float64 if spec["dtype"] == "float64" else torch.float32
+        with torch.cuda.device(self.device):
+            tin = torch.zeros((self.n, A), dtype=tdtype, device=self.device)
+            held = torch.zeros((A, self.n), dtype=torch.float64, device=self.device)
+            prev = torch.zeros((A, self.n), dtype=torch.float64, device=self.device)
+        d = _lib.NpbControlsDesc()
+        d.n_axes, d.axes, d.interval, d.in_type = A, cax, spec["interval"], _lib.CONTROL_DTYPES[spec["dtype"]]
+        d.input, d.held, d.prev = tin.data_ptr(), held.data_ptr(), prev.data_ptr()
+        _lib.check(self.L.npb_set_controls(self._h, ctypes.byref(d)), self._h)      # (refused: what was set before stays)
+        self._ctl = {"in": tin, "held": held, "prev": prev, "spec": spec}
+
+    def _controls_on(self) -> dict:
+        if getattr(self, "_ctl", None) is None:
+            raise _lib.NpbError("no controls: set_controls() first")
+        return self._ctl
+
+    def controls_input(self) -> torch.Tensor:
+        """The bound ``[n, n_axes]`` tensor the next ``step`` decodes, the same storage on every call: have the policy write into it"""
+        return self._controls_on()["in"]
+
+    def clear_controls(self, mask=None) -> None:
+        """the masked plants (None = all) unprimed: their next step starts a new hold (npb_controls_clear)"""
+        self._controls_on()
+        m = None if mask is None else self._col(mask, torch.uint8)
+        _lib.check(self.L.npb_controls_clear(self._h, None if m is None else self._p(m), self._stream()), self._h)
+
+    def _restart_controls(self, mask) -> None:
+        """behind ``reset`` / ``restore`` / ``restore_from_bank``: the plants they reset start a new hold"""
+        if getattr(self, "_ctl", None) is not None:
+            self.clear_controls(mask)
+
+    def controls_state(self) -> Dict[str, np.ndarray]:
+        """The controls' own state for a checkpoint (npb_controls_get_state), beside ``state_arrays()``: ``held`` and ``prev`` float64
+        [n_axes, n], ``age``, ``primed`` and ``seen`` int32 [n]."""
+        A = self._controls_on()["held"].shape[0]
+        out = {"held": np.zeros((A, self.n)), "prev": np.zeros((A, self.n)), "age": np.zeros(self.n, dtype=np.int32),
+               "primed": np.zeros(self.n, dtype=np.int32), "seen": np.zeros(self.n, dtype=np.int32)}
+        _lib.check(self.L.npb_controls_get_state(self._h, *[out[name].ctypes.data for name in ("held", "prev", "age", "primed", "seen")],
+                                                 self._stream()), self._h)
+        return out
+
+    def load_controls_state(self, state) -> None:
+        """put back what ``controls_state()`` returned (npb_controls_set_state)"""
+        A = self._controls_on()["held"].shape[0]
+        keep = [np.ascontiguousarray(np.asarray(state[name], dtype=np.float64).reshape(A, self.n)) for name in ("held", "prev")]
+        keep += [np.ascontiguousarray(np.asarray(state[name], dtype=np.int32).reshape(self.n)) for name in ("age", "primed", "seen")]
+        _lib.check(self.L.npb_controls_set_state(self._h, *[x.ctypes.data for x in keep], self._stream()), self._h)
+
+    def controls_spec(self) -> dict:
+        """the request as data: what ``nuclear_sim_amd.controls.Decoder`` takes"""
+        return self._controls_on()["spec"]
 
     def _order_buffers(self):
         """the buffers the perform_*_maintenance methods keep for their order columns, with the ``success`` column they all return"""
@@ -1666,6 +1787,7 @@ class BatchedPlantEnv:
         self._reset_carried_diagnostics(m)
         _lib.check(self.L.npb_restore(self._h, self._p(m), self._stream()), self._h)
         self._refill_features(m)
+        self._restart_controls(m)
         return self.get_observation()
 
     def set_start_bank(self, bank_env: Optional["BatchedPlantEnv"], slots=None, advance: Optional[int] = None) -> None:
@@ -1703,6 +1825,7 @@ class BatchedPlantEnv:
         self._reset_carried_diagnostics(m)
         _lib.check(self.L.npb_restore_bank(self._h, self._p(m), self._stream()), self._h)
         self._refill_features(m)
+        self._restart_controls(m)
         return self.get_observation()
 
     def _enable_autoreset(self, max_episode_steps: Optional[int]) -> None:
@@ -1784,6 +1907,7 @@ class BatchedPlantEnv:
         self._ewin = None      # (the handle has freed the ring; the record columns go with it)
         self._task = None
         self._feat = None
+        self._ctl = None
 
     def __del__(self):
         try:
@@ -1910,6 +2034,7 @@ class BatchedPlantEnv:
             if mask is None and self._profile is not None and self._streams is None:      # and a freshly started runner a freshly drawn profile
                 self._profile = PowerProfile(self, **self._profile_args)
         self._refill_features(m)
+        self._restart_controls(m)
         return self.get_observation()
 
     def ramp_setpoints(self, targets: torch.Tensor) -> torch.Tensor:
@@ -1944,8 +2069,14 @@ class BatchedPlantEnv:
         return secondary_result(info, members)
 
     def step(self, action=None, magnitude=None, power_setpoint=None, cooling_water_temp=None, noise_z=None,
-             thermal_power_mw=None, power_percent=None):
+             thermal_power_mw=None, power_percent=None, controls=None):
         self._keep = []
+        ctl = getattr(self, "_ctl", None)
+        if controls is not None:      # the policy's output for this step (set_controls): into the bound tensor unless it is that tensor
+            if ctl is None:
+                raise _lib.NpbError("step(controls=...) without controls: set_controls() first")
+            if not (isinstance(controls, torch.Tensor) and controls.data_ptr() == ctl["in"].data_ptr() and controls.dtype == ctl["in"].dtype):
+                ctl["in"].copy_(torch.as_tensor(controls).to(device=self.device).reshape(ctl["in"].shape))
         if self.heat_source == "external":
             # the plugin's heat_result['thermal_power_mw'] / ['power_percent'] for this step travel in the noise_z / power_setpoint
             # columns of the C ABI (include/npb_params.h, NPB_HEAT_EXTERNAL); power_percent None = thermal power / rated x 100
@@ -1996,6 +2127,8 @@ class BatchedPlantEnv:
             info.update(self._episode)
             if self._bank is not None:    # the episode kernel's, restoring from the bank: the bank entry this transition's episode started from
                 info["episode_start"] = self._episode_start_out
+        if ctl is not None:      # the action every plant is under after this step's decode: [n_axes, n] (set_controls)
+            info["controls"] = ctl["held"]
         obs = self._obs
         feat = getattr(self, "_feat", None)
         if feat is not None:      # the caller's policy inputs, kept behind the step (set_features)

@@ -1,0 +1,207 @@
+"""CPU: controls -- the caller's policy outputs (npb_set_controls and its companions) -- are declared by include/npb.h, exported by
+libnpb.so and bound; the binding lays the descriptors out as a C compiler does (a small compiled probe prints sizeof and every offsetof);
+the library's own check, which needs no handle and reads no device memory, accepts a valid descriptor and names every refusal the header
+lists.  No compute calls.
+
+The header keeps NPB_VERSION where the suites of the entry-point groups before this one pin it: the new entry points are detected by name."""
+import ctypes
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
+ENTRY_POINTS = ("npb_set_controls", "npb_controls_check", "npb_controls_clear", "npb_controls_get_state", "npb_controls_set_state")
+STRUCTS = {"npb_control_axis_t": "NpbControlAxis", "npb_controls_desc_t": "NpbControlsDesc"}
+C_NAME = {"input": "in"}      # `in` is no Python attribute name
+A16 = 0x7000       # "device addresses" the check only looks at: never dereferenced
+NAN, INF = float("nan"), float("inf")
+CONSTANT, EXTERNAL = 0, 2      # NPB_HEAT_*
+
+
+@pytest.fixture(scope="module")
+def L():
+    if not os.path.exists(LIB):
+        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
+    from nuclear_sim_amd import _lib
+    return _lib.load()
+
+
+def _header():
+    return open(os.path.join(ROOT, "include", "npb.h")).read()
+
+
+def test_header_declares_the_entry_points_the_maxima_and_the_rules_of_the_road():
+    text = _header()
+    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
+    for s in ENTRY_POINTS:
+        assert s in declared, s
+    assert int(re.search(r"#define NPB_CONTROLS_AXES_MAX (\d+)", text).group(1)) == 8
+    assert int(re.search(r"#define NPB_CONTROLS_INTERVAL_MAX (\d+)", text).group(1)) == 64
+    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) == 154
+    for words in ("every step rounded on its own", "fabs(y) == deadband stays", "npd_apply_control_actions", "the step kernel applies them behind the controls",
+                  "cooldown cache watches the feedwater pumps' parameters", "where the new bits differ from the old", "the first step of a new episode starts a new hold",
+                  "No half types", "Not here: a discrete action table"):
+        assert words in text, words
+
+
+def test_library_exports_and_binding_declares_them(L):
+    raw = ctypes.CDLL(LIB)
+    for s in ENTRY_POINTS:
+        assert hasattr(raw, s), "libnpb.so does not export %s" % s
+        assert getattr(L, s).argtypes is not None, s
+    assert L.npb_set_controls(None, None) == -1 and L.npb_controls_clear(None, None, None) == -1
+    assert L.npb_controls_get_state(None, None, None, None, None, None, None) == -1
+    assert L.npb_controls_set_state(None, None, None, None, None, None, None) == -1
+
+
+def test_the_binding_lays_the_descriptors_out_as_the_compiler_does(tmp_path):
+    from nuclear_sim_amd import _lib, controls
+    lines = []
+    for c_name, py_name in STRUCTS.items():
+        lines.append('  printf("%%zu\\n", sizeof(%s));\n' % c_name)
+        lines += ['  printf("%%zu\\n", offsetof(%s, %s));\n' % (c_name, C_NAME.get(f[0], f[0])) for f in getattr(_lib, py_name)._fields_]
+    # the initialiser macros name the members kind, target
+    lines.append("  { npb_control_axis_t r = { NPB_CONTROL_RATE(NPB_ACTUATOR_BORON) }, t = { NPB_CONTROL_TARGET(NPB_ACTUATOR_VALVE) },\n"
+                 "      c = { NPB_CONTROL_COLUMN(NPB_CONTROL_INPUT_COOLING_WATER_TEMP) };\n"
+                 '    printf("%d\\n%d\\n%d\\n%d\\n%d\\n%d\\n", r.kind, r.target, t.kind, t.target, c.kind, c.target); }\n')
+    src = tmp_path / "probe.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "npb.h"\nint main(void) {\n' + "".join(lines) + "  return 0;\n}\n")
+    exe = tmp_path / "probe"
+    subprocess.check_call([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
+    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    want = []
+    for py_name in STRUCTS.values():
+        S = getattr(_lib, py_name)
+        want += [ctypes.sizeof(S)] + [getattr(S, f[0]).offset for f in S._fields_]
+    assert got == want + [_lib.CONTROL_KINDS["rate"], _lib.CONTROL_ACTUATORS["boron"], _lib.CONTROL_KINDS["target"], _lib.CONTROL_ACTUATORS["valve"],
+                          _lib.CONTROL_KINDS["column"], _lib.CONTROL_INPUTS["cooling_water_temp"]]
+    text = _header()
+    assert {name: int(re.search(r"NPB_CONTROL_KIND_%s = (\d+)" % name.upper(), text).group(1)) for name in _lib.CONTROL_KINDS} == _lib.CONTROL_KINDS
+    assert {name: int(re.search(r"NPB_ACTUATOR_%s = (\d+)" % name.upper(), text).group(1)) for name in _lib.CONTROL_ACTUATORS} == _lib.CONTROL_ACTUATORS
+    assert {name: int(re.search(r"NPB_CONTROL_INPUT_%s = (\d+)" % name.upper(), text).group(1)) for name in _lib.CONTROL_INPUTS} == _lib.CONTROL_INPUTS
+    assert {"float32": int(re.search(r"NPB_CONTROLS_F32 = (\d+)", text).group(1)),
+            "float64": int(re.search(r"NPB_CONTROLS_F64 = (\d+)", text).group(1))} == _lib.CONTROL_DTYPES
+    assert (_lib.CONTROLS_AXES_MAX, _lib.CONTROLS_INTERVAL_MAX) == (controls.AXES_MAX, controls.INTERVAL_MAX) == (8, 64)
+    assert _lib.HEAT_EXTERNAL == int(re.search(r"NPB_HEAT_EXTERNAL = (\d+)", open(os.path.join(ROOT, "include", "npb_params.h")).read()).group(1))
+
+
+class _Desc:
+    """a valid descriptor: rod RATE, valve TARGET, flow RATE with a deadband, boron TARGET, both columns; float input; and the ctypes array
+    it points into"""
+
+    def __init__(self):
+        from nuclear_sim_amd import _lib
+        K, A, I = _lib.CONTROL_KINDS, _lib.CONTROL_ACTUATORS, _lib.CONTROL_INPUTS
+        self.axes = (_lib.NpbControlAxis * 9)()
+        for X in self.axes:
+            X.kind, X.target, X.scale, X.lo, X.hi, X.max_magnitude = K["rate"], A["rod"], 1.0, -1.0, 1.0, 1.0
+        what = [(K["rate"], A["rod"]), (K["target"], A["valve"]), (K["rate"], A["flow"]), (K["target"], A["boron"]),
+                (K["column"], I["power_setpoint"]), (K["column"], I["cooling_water_temp"])]
+        for X, (kind, target) in zip(self.axes, what):
+            X.kind, X.target = kind, target
+        self.axes[1].lo, self.axes[1].hi = -INF, INF
+        self.axes[2].deadband = 0.05
+        self.d = _lib.NpbControlsDesc()
+        self.d.n_axes, self.d.axes, self.d.interval, self.d.in_type = 6, self.axes, 4, _lib.CONTROL_DTYPES["float32"]
+        self.d.input, self.d.held, self.d.prev = A16 + 4, A16 + 8, A16 + 16
+
+
+def _why(L, D, n=70, heat=CONSTANT):
+    r = L.npb_controls_check(ctypes.byref(D.d), n, heat)
+    return None if r is None else r.decode()
+
+
+def test_the_check_accepts_valid_controls_and_null(L):
+    assert _why(L, _Desc()) is None
+    assert L.npb_controls_check(None, 70, CONSTANT) is None
+    D = _Desc(); D.d.n_axes = 1; D.d.interval = 1
+    assert _why(L, D) is None
+    D = _Desc(); D.axes[6].kind = D.axes[7].kind = 3; D.axes[7].target = 99; D.d.n_axes = 8      # two VALUE axes: the target is not read
+    assert _why(L, D) is None
+    D = _Desc(); D.d.interval = 64
+    assert _why(L, D) is None
+    D = _Desc(); D.d.in_type, D.d.input = 1, A16 + 8                   # double
+    assert _why(L, D) is None
+    D = _Desc(); D.axes[0].lo = D.axes[0].hi = 0.5; D.axes[1].lo = -INF; D.axes[0].deadband = 0.0      # lo == hi, an open clip
+    assert _why(L, D) is None
+    D = _Desc(); D.d.n_axes = 4                                        # no POWER_SETPOINT axis: the external heat source is fine
+    assert _why(L, D, heat=EXTERNAL) is None
+    D = _Desc(); D.axes[4].target = 1; D.d.n_axes = 5                  # COOLING_WATER_TEMP alone under the external heat source
+    assert _why(L, D, heat=EXTERNAL) is None
+
+
+def _set(path, value):
+    def change(D):
+        obj = D
+        *head, last = path
+        for name in head:
+            obj = obj[name] if isinstance(name, int) else getattr(obj, name)
+        setattr(obj, last, value)
+    return change
+
+
+def _both(*changes):
+    def change(D):
+        for c in changes:
+            c(D)
+    return change
+
+
+REFUSALS = [
+    ("n_plants", None, "n_plants must be >= 1"),
+    ("no axes", _set(("d", "n_axes"), 0), "axis count must be 1 .. NPB_CONTROLS_AXES_MAX (8)"),
+    ("too many axes", _set(("d", "n_axes"), 9), "axis count must be 1 .. NPB_CONTROLS_AXES_MAX (8)"),
+    ("axes without their array", _set(("d", "axes"), None), "with their descriptors"),
+    ("no interval", _set(("d", "interval"), 0), "interval must be 1 .. NPB_CONTROLS_INTERVAL_MAX (64)"),
+    ("too long an interval", _set(("d", "interval"), 65), "interval must be 1 .. NPB_CONTROLS_INTERVAL_MAX (64)"),
+    ("unknown kind", _set(("axes", 0, "kind"), 4), "an unknown control kind"),
+    ("negative kind", _set(("axes", 0, "kind"), -1), "an unknown control kind"),
+    ("unknown actuator", _set(("axes", 0, "target"), 4), "an unknown actuator"),
+    ("negative actuator", _set(("axes", 1, "target"), -1), "an unknown actuator"),
+    ("unknown input", _set(("axes", 4, "target"), 2), "an unknown input"),
+    ("two axes on one actuator", _set(("axes", 1, "target"), 0), "two axes on one actuator"),
+    ("two axes on one input", _set(("axes", 5, "target"), 0), "two axes on one input"),
+    ("NaN scale", _set(("axes", 0, "scale"), NAN), "a NaN or infinite scale, offset, nan_to, deadband or max_magnitude"),
+    ("infinite scale", _set(("axes", 4, "scale"), INF), "a NaN or infinite scale"),
+    ("NaN offset", _set(("axes", 0, "offset"), NAN), "a NaN or infinite scale, offset"),
+    ("infinite offset", _set(("axes", 0, "offset"), -INF), "a NaN or infinite scale, offset"),
+    ("NaN nan_to", _set(("axes", 3, "nan_to"), NAN), "a NaN or infinite scale, offset, nan_to"),
+    ("infinite nan_to", _set(("axes", 3, "nan_to"), INF), "a NaN or infinite scale, offset, nan_to"),
+    ("NaN deadband", _set(("axes", 2, "deadband"), NAN), "deadband or max_magnitude"),
+    ("infinite deadband", _set(("axes", 2, "deadband"), INF), "deadband or max_magnitude"),
+    ("NaN max_magnitude", _set(("axes", 1, "max_magnitude"), NAN), "deadband or max_magnitude"),
+    ("infinite max_magnitude", _set(("axes", 1, "max_magnitude"), INF), "deadband or max_magnitude"),
+    ("negative deadband", _set(("axes", 2, "deadband"), -0.5), "a negative deadband"),
+    ("negative max_magnitude", _set(("axes", 1, "max_magnitude"), -1.0), "a negative max_magnitude"),
+    ("NaN lo", _set(("axes", 0, "lo"), NAN), "a NaN clip limit"),
+    ("NaN hi", _set(("axes", 5, "hi"), NAN), "a NaN clip limit"),
+    ("lo > hi", _both(_set(("axes", 0, "lo"), 2.0), _set(("axes", 0, "hi"), 1.0)), "a clip with lo > hi"),
+    ("unknown input type", _set(("d", "in_type"), 2), "an unknown input type"),
+    ("NULL in", _set(("d", "input"), None), "a NULL in tensor"),
+    ("misaligned in", _set(("d", "input"), A16 + 2), "a misaligned in tensor"),
+    ("double in on 4 bytes", _set(("d", "in_type"), 1), "a misaligned in tensor"),
+    ("NULL held", _set(("d", "held"), None), "NULL held or prev"),
+    ("NULL prev", _set(("d", "prev"), None), "NULL held or prev"),
+    ("misaligned held", _set(("d", "held"), A16 + 4), "misaligned held or prev"),
+    ("misaligned prev", _set(("d", "prev"), A16 + 12), "misaligned held or prev"),
+]
+
+
+@pytest.mark.parametrize("what, change, reason", REFUSALS, ids=[r[0] for r in REFUSALS])
+def test_the_check_names_every_refusal(L, what, change, reason):
+    D = _Desc()
+    if change is None:
+        why = _why(L, D, n=0)
+    else:
+        change(D)
+        why = _why(L, D)
+    assert why is not None and why.startswith("npb_set_controls: ") and reason in why, (what, why)
+
+
+def test_a_power_setpoint_axis_is_refused_under_the_external_heat_source(L):
+    why = _why(L, _Desc(), heat=EXTERNAL)
+    assert why is not None and "a POWER_SETPOINT axis under NPB_HEAT_EXTERNAL" in why
+    assert _why(L, _Desc(), heat=1) is None      # the reactor heat source takes the setpoint
