@@ -71,20 +71,22 @@ struct NpbHandle {
   bool es_on; npb_episode_streams_t es; void *es_mem; int es_noise_cur, es_prof_cur; double *es_noise_out, *es_setpoint_out, *es_target_out; bool es_tables;
   /* npb_set_episode_records: the caller's record columns and cursor, and the npb_step calls since they were switched on */
   bool er_on; npb_episode_records_desc_t er; int er_step;
-  /* npb_set_column_stats: the columns on the device (cs.cols, one allocation; NULL = off) and the caller's tables; npb_set_episode_record_stats:
-   * the record-side columns that take them */
+  /* the per-step attachments (attachment_alloc ... state_copy below): each struct is what its kernel reads, and the member named here is
+   * the base of its device allocation, NULL = off.
+   * npb_set_column_stats: the columns on the device (base cs.cols) and the caller's tables; npb_set_episode_record_stats: the record-side
+   * columns that take them */
   npb_column_stats_t cs; bool ers_on; npb_episode_record_stats_desc_t ers;
   npb_record_stats_t *ers_dev;      /* what the records kernel reads of both (device, allocated on first use, uploaded by npb_set_episode_record_stats) */
-  /* npb_set_event_windows: the columns, triggers, ring and bookkeeping on the device (ew.cols = the one allocation of ew_bytes; NULL =
-   * off), the caller's record columns, and the npb_step calls since they were set */
+  /* npb_set_event_windows: the columns, triggers, ring and bookkeeping on the device (base ew.cols, ew_bytes of them), the caller's record
+   * columns, and the npb_step calls since they were set */
   npb_event_windows_t ew; size_t ew_bytes; int ew_step;
-  /* npb_set_task: the terms, rules, previous samples and bookkeeping on the device (task.terms = the one allocation; NULL = off) and the
-   * caller's outputs; npb_set_episode_record_task: the record-side column that takes the cause word */
+  /* npb_set_task: the terms, rules, previous samples and bookkeeping on the device (base task.terms) and the caller's outputs;
+   * npb_set_episode_record_task: the record-side column that takes the cause word */
   npb_task_t task; bool ert_on; int32_t *ert_cause;
-  /* npb_set_features: the columns and the bookkeeping on the device (feat.cols = the one allocation; NULL = off) and the caller's tensors */
+  /* npb_set_features: the columns and the bookkeeping on the device (base feat.cols) and the caller's tensors */
   npb_features_t feat;
-  /* npb_set_controls: the axes, the caller's tensors and the handle's bookkeeping and input columns (ctl.age = the one allocation; NULL =
-   * off); ctl_axis[input]: the axis that fills that input column, -1 = none */
+  /* npb_set_controls: the axes, the caller's tensors and the handle's bookkeeping and input columns (base ctl.age); ctl_axis[input]: the
+   * axis that fills that input column, -1 = none */
   npb_controls_t ctl; int ctl_axis[NPB_CONTROL_INPUT_COUNT];
   double *ramp_prev;   /* npb_profile_ramp: the previous setpoint of every plant ([pitch], NaN = none yet), allocated on first use */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
@@ -115,6 +117,73 @@ struct DeviceGuard {
 };
 #define NPB_USE_DEVICE(h) DeviceGuard guard__((h)->device); if (guard__.err != hipSuccess) return fail(h, NPB_EHIP, "hipSetDevice", guard__.err)
 #define NPB_HIP(h, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(h, NPB_EHIP, #call, e__); } while (0)
+static int fail_who(NpbHandle *h, const char *who, const char *what) { return fail(h, NPB_EINVAL, (std::string(who) + what).c_str()); }
+
+/* ---- the lifecycle the per-step attachments share (column statistics, event windows, task, features, controls).  Each keeps its tables
+ * and per-plant bookkeeping in one device allocation, whose base is the struct's "is it on" pointer.  npb_set_* = attachment_alloc, fill
+ * the struct from the base, attachment_drop the old one, assign; off and npb_destroy = attachment_drop; npb_*_clear = attachment_clear;
+ * npb_*_get_state / npb_*_set_state = that attachment's StateParts through state_copy */
+
+/* `bytes` on the device, zeroed, the host table (table_bytes of them, may be 0) uploaded to their start; synchronous, so the host table may
+ * go.  Where HIP fails nothing is kept and the failure is reported as `who`'s, about `what`; `nomem`: the code of a refused hipMalloc */
+static int attachment_alloc(NpbHandle *h, const char *who, const char *what, const void *table, size_t table_bytes, size_t bytes, char **dev,
+                            int nomem = NPB_EHIP) {
+  char text[200];
+  hipError_t e = hipMalloc((void **)dev, bytes);
+  if (e != hipSuccess) {
+    snprintf(text, sizeof text, "%s: hipMalloc of %s (%zu bytes) failed", who, what, bytes);
+    return fail(h, nomem, text, e);
+  }
+  e = hipMemset(*dev, 0, bytes);
+  if (e == hipSuccess && table_bytes) e = hipMemcpy(*dev, table, table_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (e == hipSuccess) return NPB_OK;
+  (void)hipFree(*dev);
+  snprintf(text, sizeof text, "%s: setting up %s failed", who, what);
+  return fail(h, NPB_EHIP, text, e);
+}
+/* the attachment off: its allocation freed (hipFree waits for the device: a launch still in flight finishes first), its struct empty */
+template <class T> static void attachment_drop(T *attachment, const void *base) {
+  if (base) (void)hipFree((void *)base);
+  *attachment = T{};
+}
+static const char *const g_no_event_windows = ": no event windows set (npb_set_event_windows first)";
+static const char *const g_no_column_stats = ": no column statistics set (npb_set_column_stats first)";
+static const char *const g_no_task = ": no task set (npb_set_task first)";
+static const char *const g_no_features = ": no features set (npb_set_features first)";
+static const char *const g_no_controls = ": no controls set (npb_set_controls first)";
+/* the body of an npb_*_clear: refused with `off` unless the attachment is on, then its launch on the handle's device */
+template <class Launch> static int attachment_clear(NpbHandle *h, const char *who, const void *on, const char *off, Launch launch) {
+  if (!on) return fail_who(h, who, off);
+  NPB_USE_DEVICE(h);
+  launch();
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+/* an attachment's checkpointed state: whether it is on (else refused with `off`), and its parts on the device in the order its get_state /
+ * set_state take them, stated once for both directions; a part that may be absent is one the caller may pass NULL for (`null_note` says
+ * which) */
+struct StatePart { void *dev; size_t bytes; bool may_be_absent; };
+struct StateParts { const void *on; const char *off, *null_note; int count; StatePart part[5]; };
+static int state_copy(NpbHandle *h, const char *who, StateParts (*parts_of)(const NpbHandle *), std::initializer_list<const void *> host,
+                      bool to_device, void *stream) {
+  if (!h) return NPB_EINVAL;
+  const StateParts S = parts_of(h);
+  if (!S.on) return fail_who(h, who, S.off);
+  for (int k = 0; k < S.count; k++)
+    if (!host.begin()[k] && !S.part[k].may_be_absent)
+      return fail_who(h, who, (std::string(to_device ? ": NULL input" : ": NULL output") + S.null_note).c_str());
+  NPB_USE_DEVICE(h);
+  hipStream_t st = (hipStream_t)stream;
+  for (int k = 0; k < S.count; k++) {
+    const StatePart &P = S.part[k];
+    void *mine = (void *)host.begin()[k];
+    if (!P.bytes) continue;
+    NPB_HIP(h, to_device ? hipMemcpyAsync(P.dev, mine, P.bytes, hipMemcpyHostToDevice, st) : hipMemcpyAsync(mine, P.dev, P.bytes, hipMemcpyDeviceToHost, st));
+  }
+  NPB_HIP(h, hipStreamSynchronize(st));      /* the host arrays may go */
+  return NPB_OK;
+}
 
 /* where the members of the schema live in the arena (include/npb_fields.h: carried fp64 members one per column,
  * then the narrow members -- outputs as float, int32 -- two per 8-byte column or one per 4-byte column) */
@@ -513,12 +582,9 @@ int npb_destroy(NpbHandle *h) {
   if (h->prof_z) (void)hipFree(h->prof_z);
   if (h->ramp_prev) (void)hipFree(h->ramp_prev);
   if (h->es_mem) (void)hipFree(h->es_mem);
-  if (h->cs.cols) (void)hipFree((void *)h->cs.cols);
   if (h->ers_dev) (void)hipFree(h->ers_dev);
-  if (h->ew.cols) (void)hipFree((void *)h->ew.cols);
-  if (h->task.terms) (void)hipFree((void *)h->task.terms);
-  if (h->feat.cols) (void)hipFree((void *)h->feat.cols);
-  if (h->ctl.age) (void)hipFree((void *)h->ctl.age);
+  attachment_drop(&h->cs, h->cs.cols); attachment_drop(&h->ew, h->ew.cols); attachment_drop(&h->task, h->task.terms);
+  attachment_drop(&h->feat, h->feat.cols); attachment_drop(&h->ctl, h->ctl.age);
   for (Sampler *sm : h->samplers) if (sm) { (void)hipFree(sm->dev); delete sm; }
   delete h;
   return NPB_OK;
@@ -1303,7 +1369,6 @@ int npb_set_episode_start_buffer(NpbHandle *h, int32_t *out_start) {
 
 /* ---- the Mersenne-Twister generators (npb_noise_t: the heat-source noise's and the power profile's), between the device's [624][pitch]
  * key columns and numpy's get_state() layout, [n][624]; `who` = the ABI entry, for the messages */
-static int fail_who(NpbHandle *h, const char *who, const char *what) { return fail(h, NPB_EINVAL, (std::string(who) + what).c_str()); }
 static int seeds_narrow(NpbHandle *h, const char *who, const int64_t *seeds, uint32_t *s32) {
   for (int p = 0; p < h->n_plants; p++) {
     if (seeds[p] < 0 || seeds[p] > (int64_t)0xffffffffLL) return fail_who(h, who, ": a seed is outside [0, 2^32), which numpy.random.RandomState refuses");
@@ -1598,7 +1663,7 @@ const char *npb_event_windows_check(const npb_event_windows_desc_t *D, int n_pla
   }
   return nullptr;
 }
-/* the handle's one allocation: [the columns][the triggers] | ring | prev | a_time | the eight 4-byte words per plant; every part 8-byte aligned */
+/* the allocation: [the columns][the triggers] | ring | prev | a_time | the eight 4-byte words per plant; every part 8-byte aligned */
 static size_t ew_table_bytes() {
   return NPB_EVENT_WINDOW_COLS_MAX * sizeof(npb_colstat_col_t) + NPB_EVENT_WINDOW_TRIGGERS_MAX * sizeof(npb_event_trigger_col_t);
 }
@@ -1612,11 +1677,7 @@ int npb_set_event_windows(NpbHandle *h, const npb_event_windows_desc_t *desc) {
   if (!h) return NPB_EINVAL;
   if (const char *why = npb_event_windows_check(desc, h->n_plants, h->autoreset ? 1 : 0)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
-  if (!desc) {
-    if (h->ew.cols) (void)hipFree((void *)h->ew.cols);      /* (hipFree waits for the device: a launch still in flight finishes first) */
-    h->ew = npb_event_windows_t{}; h->ew_bytes = 0;
-    return NPB_OK;
-  }
+  if (!desc) { attachment_drop(&h->ew, h->ew.cols); h->ew_bytes = 0; return NPB_OK; }
   struct { npb_colstat_col_t cols[NPB_EVENT_WINDOW_COLS_MAX]; npb_event_trigger_col_t triggers[NPB_EVENT_WINDOW_TRIGGERS_MAX]; } table = {};
   static_assert(sizeof table == NPB_EVENT_WINDOW_COLS_MAX * sizeof(npb_colstat_col_t) + NPB_EVENT_WINDOW_TRIGGERS_MAX * sizeof(npb_event_trigger_col_t), "packed");
   const int n_cols = desc->n_fields + desc->n_sources;
@@ -1630,13 +1691,9 @@ int npb_set_event_windows(NpbHandle *h, const npb_event_windows_desc_t *desc) {
     if (T.mode == NPB_TRIGGER_MODE_BEYOND) { O.c.direction = T.direction; O.c.limit = T.limit; }
   }
   const size_t bytes = npb_event_windows_bytes(desc, h->n_plants), n = (size_t)h->n_plants, H = (size_t)desc->pre + 1 + (size_t)desc->post;
+  /* the tables up, everything else zero (the indices last seen too: a first sample that finds another index empties an empty ring) */
   char *dev = nullptr;
-  hipError_t e = hipMalloc((void **)&dev, bytes);
-  if (e != hipSuccess) {
-    char what[160];
-    snprintf(what, sizeof what, "npb_set_event_windows: hipMalloc of the ring and the bookkeeping (%zu bytes) failed", bytes);
-    return fail(h, NPB_EHIP, what, e);
-  }
+  if (int rc = attachment_alloc(h, "npb_set_event_windows", "the ring and the bookkeeping", &table, sizeof table, bytes, &dev)) return rc;
   npb_event_windows_t W = {};
   W.cols = (const npb_colstat_col_t *)dev; W.triggers = (const npb_event_trigger_col_t *)(dev + sizeof table.cols);
   W.n_cols = n_cols; W.n_triggers = desc->n_triggers; W.pre = desc->pre; W.post = desc->post;
@@ -1648,24 +1705,19 @@ int npb_set_event_windows(NpbHandle *h, const npb_event_windows_desc_t *desc) {
   W.a_retriggers = words + 6 * n; W.a_fired = (uint32_t *)(words + 7 * n);
   W.D = npb_event_window_records_t{desc->capacity, desc->plant, desc->episode, desc->trigger, desc->step, desc->n_pre, desc->n_post, desc->flags,
                                    desc->retriggers, desc->fired, desc->time, desc->times, desc->values, desc->cursor};
-  /* the tables up, everything else zero (the indices last seen too: a first sample that finds another index empties an empty ring), every
-   * plant unprimed and idle; synchronous, so the host copies may go */
-  e = hipMemset(dev, 0, bytes);
-  if (e == hipSuccess) e = hipMemcpy(dev, &table, sizeof table, hipMemcpyHostToDevice);
-  if (e == hipSuccess) { npb_launch_event_windows_clear(&W, nullptr, h->n_plants, nullptr); e = hipGetLastError(); }
+  /* every plant unprimed and idle (idle is not zero: due = -1) before the first step can read it */
+  npb_launch_event_windows_clear(&W, nullptr, h->n_plants, nullptr);
+  hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   if (e != hipSuccess) { (void)hipFree(dev); return fail(h, NPB_EHIP, "npb_set_event_windows: setting up the ring and the bookkeeping failed", e); }
-  if (h->ew.cols) (void)hipFree((void *)h->ew.cols);
+  attachment_drop(&h->ew, h->ew.cols);
   h->ew = W; h->ew_bytes = bytes; h->ew_step = 0;
   return NPB_OK;
 }
 int npb_event_windows_clear(NpbHandle *h, const uint8_t *mask, void *stream) {
   if (!h) return NPB_EINVAL;
-  if (!h->ew.cols) return fail(h, NPB_EINVAL, "npb_event_windows_clear: no event windows set (npb_set_event_windows first)");
-  NPB_USE_DEVICE(h);
-  npb_launch_event_windows_clear(&h->ew, mask, h->n_plants, (hipStream_t)stream);
-  NPB_HIP(h, hipGetLastError());
-  return NPB_OK;
+  return attachment_clear(h, "npb_event_windows_clear", h->ew.cols, g_no_event_windows,
+                          [&] { npb_launch_event_windows_clear(&h->ew, mask, h->n_plants, (hipStream_t)stream); });
 }
 
 /* ---- column statistics (include/npb.h, npd_column_stats.h) */
@@ -1698,11 +1750,7 @@ int npb_set_column_stats(NpbHandle *h, const npb_column_stats_desc_t *desc) {
     return fail(h, NPB_EINVAL, "npb_set_column_stats: episode records that copy or clear the column statistics are on (npb_set_episode_record_stats) and hold its tables and column count; switch them off first");
   if (const char *why = npb_column_stats_check(desc, h->n_plants)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
-  if (!desc) {
-    if (h->cs.cols) (void)hipFree((void *)h->cs.cols);      /* (hipFree waits for the device: a fold still in flight finishes first) */
-    h->cs = npb_column_stats_t{};
-    return NPB_OK;
-  }
+  if (!desc) { attachment_drop(&h->cs, h->cs.cols); return NPB_OK; }
   const int n_cols = desc->n_fields + desc->n_sources;
   npb_colstat_col_t cols[NPB_COLUMN_STATS_MAX] = {};
   for (int c = 0; c < n_cols; c++) {
@@ -1711,12 +1759,9 @@ int npb_set_column_stats(NpbHandle *h, const npb_column_stats_desc_t *desc) {
     C.direction = desc->direction ? desc->direction[c] : 0;
     C.limit = C.direction ? desc->limit[c] : 0.0;
   }
-  void *dev = nullptr;
-  hipError_t e = hipMalloc(&dev, sizeof cols);
-  if (e != hipSuccess) return fail(h, NPB_ENOMEM, "npb_set_column_stats: hipMalloc of the column table failed", e);
-  e = hipMemcpy(dev, cols, sizeof cols, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(dev); return fail(h, NPB_EHIP, "npb_set_column_stats: upload of the column table failed", e); }
-  if (h->cs.cols) (void)hipFree((void *)h->cs.cols);
+  char *dev = nullptr;
+  if (int rc = attachment_alloc(h, "npb_set_column_stats", "the column table", cols, sizeof cols, sizeof cols, &dev, NPB_ENOMEM)) return rc;
+  attachment_drop(&h->cs, h->cs.cols);
   h->cs = npb_column_stats_t{(const npb_colstat_col_t *)dev, n_cols, desc->min, desc->max, desc->sum, desc->sumsq, desc->last, desc->first_beyond,
                              desc->n_beyond, desc->n_samples};
   return NPB_OK;
@@ -1731,11 +1776,8 @@ int npb_column_stats_fold(NpbHandle *h, void *stream) {
 }
 int npb_column_stats_clear(NpbHandle *h, const uint8_t *mask, void *stream) {
   if (!h) return NPB_EINVAL;
-  if (!h->cs.cols) return fail(h, NPB_EINVAL, "npb_column_stats_clear: no column statistics set (npb_set_column_stats first)");
-  NPB_USE_DEVICE(h);
-  npb_launch_column_stats_clear(&h->cs, mask, h->n_plants, (hipStream_t)stream);
-  NPB_HIP(h, hipGetLastError());
-  return NPB_OK;
+  return attachment_clear(h, "npb_column_stats_clear", h->cs.cols, g_no_column_stats,
+                          [&] { npb_launch_column_stats_clear(&h->cs, mask, h->n_plants, (hipStream_t)stream); });
 }
 /* what the records kernel reads beside its own descriptor -- the column statistics with their record-side columns, the task's cause column
  * with its own -- into the handle's device copy (allocated on first use); synchronous: a records kernel in flight has finished */
@@ -1825,12 +1867,8 @@ int npb_set_task(NpbHandle *h, const npb_task_desc_t *desc) {
     return fail(h, NPB_EINVAL, "npb_set_task: episode records that copy the task's cause word are on (npb_set_episode_record_task) and hold its cause column; drop that first");
   if (const char *why = npb_task_check(desc, h->n_plants)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
-  if (!desc) {
-    if (h->task.terms) (void)hipFree((void *)h->task.terms);      /* (hipFree waits for the device: a launch still in flight finishes first) */
-    h->task = npb_task_t{};
-    return NPB_OK;
-  }
-  /* the handle's one allocation: [the terms][the rules] | prev [n_delta][n] | primed [n] | seen [n]; every part 8-byte aligned */
+  if (!desc) { attachment_drop(&h->task, h->task.terms); return NPB_OK; }
+  /* the allocation: [the terms][the rules] | prev [n_delta][n] | primed [n] | seen [n]; every part 8-byte aligned */
   struct { npb_task_term_col_t terms[NPB_TASK_TERMS_MAX]; npb_task_rule_col_t rules[NPB_TASK_RULES_MAX]; } table = {};
   static_assert(sizeof table == NPB_TASK_TERMS_MAX * sizeof(npb_task_term_col_t) + NPB_TASK_RULES_MAX * sizeof(npb_task_rule_col_t) && sizeof table % 8 == 0, "packed");
   int n_delta = 0;
@@ -1855,62 +1893,36 @@ int npb_set_task(NpbHandle *h, const npb_task_desc_t *desc) {
   }
   const size_t n = (size_t)h->n_plants, words = (2 * n * sizeof(int32_t) + 7) / 8 * 8;
   const size_t bytes = sizeof table + (size_t)n_delta * n * sizeof(double) + words;
+  /* the tables up, everything else zero: every plant unprimed (the indices last seen too: a first sample that finds another index
+   * unprimes an unprimed plant) */
   char *dev = nullptr;
-  hipError_t e = hipMalloc((void **)&dev, bytes);
-  if (e != hipSuccess) {
-    char what[160];
-    snprintf(what, sizeof what, "npb_set_task: hipMalloc of the tables and the previous samples (%zu bytes) failed", bytes);
-    return fail(h, NPB_EHIP, what, e);
-  }
+  if (int rc = attachment_alloc(h, "npb_set_task", "the tables and the previous samples", &table, sizeof table, bytes, &dev)) return rc;
   npb_task_t T = {};
   T.terms = (const npb_task_term_col_t *)dev; T.rules = (const npb_task_rule_col_t *)(dev + sizeof table.terms);
   T.n_terms = desc->n_terms; T.n_rules = desc->n_rules; T.n_delta = n_delta; T.bias = desc->bias;
   T.reward = desc->reward; T.done = desc->done; T.cause = desc->cause; T.terms_out = desc->terms_out;
   T.prev = (double *)(dev + sizeof table);
   T.primed = (int32_t *)(T.prev + (size_t)n_delta * n); T.seen = T.primed + n;
-  /* the tables up, everything else zero: every plant unprimed (the indices last seen too: a first sample that finds another index
-   * unprimes an unprimed plant); synchronous, so the host copies may go */
-  e = hipMemset(dev, 0, bytes);
-  if (e == hipSuccess) e = hipMemcpy(dev, &table, sizeof table, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  if (e != hipSuccess) { (void)hipFree(dev); return fail(h, NPB_EHIP, "npb_set_task: setting up the tables and the previous samples failed", e); }
-  if (h->task.terms) (void)hipFree((void *)h->task.terms);
+  attachment_drop(&h->task, h->task.terms);
   h->task = T;
   return NPB_OK;
 }
 int npb_task_clear(NpbHandle *h, const uint8_t *mask, void *stream) {
   if (!h) return NPB_EINVAL;
-  if (!h->task.terms) return fail(h, NPB_EINVAL, "npb_task_clear: no task set (npb_set_task first)");
-  NPB_USE_DEVICE(h);
-  npb_launch_task_clear(&h->task, mask, h->n_plants, (hipStream_t)stream);
-  NPB_HIP(h, hipGetLastError());
-  return NPB_OK;
+  return attachment_clear(h, "npb_task_clear", h->task.terms, g_no_task, [&] { npb_launch_unprime(h->task.primed, mask, h->n_plants, (hipStream_t)stream); });
+}
+/* prev, primed, seen; without DELTA terms there is no prev */
+static StateParts task_state_parts(const NpbHandle *h) {
+  const size_t n = (size_t)h->n_plants;
+  return {h->task.terms, g_no_task, " (prev may be NULL only for a task without DELTA terms)", 3,
+          {{h->task.prev, (size_t)h->task.n_delta * n * sizeof(double), h->task.n_delta == 0}, {h->task.primed, n * sizeof(int32_t), false},
+           {h->task.seen, n * sizeof(int32_t), false}}};
 }
 int npb_task_get_state(NpbHandle *h, double *prev, int32_t *primed, int32_t *seen, void *stream) {
-  if (!h) return NPB_EINVAL;
-  if (!h->task.terms) return fail(h, NPB_EINVAL, "npb_task_get_state: no task set (npb_set_task first)");
-  if (!primed || !seen || (h->task.n_delta > 0 && !prev)) return fail(h, NPB_EINVAL, "npb_task_get_state: NULL output (prev may be NULL only for a task without DELTA terms)");
-  NPB_USE_DEVICE(h);
-  const size_t n = (size_t)h->n_plants;
-  hipStream_t st = (hipStream_t)stream;
-  if (h->task.n_delta > 0) NPB_HIP(h, hipMemcpyAsync(prev, h->task.prev, (size_t)h->task.n_delta * n * sizeof(double), hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipMemcpyAsync(primed, h->task.primed, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipMemcpyAsync(seen, h->task.seen, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipStreamSynchronize(st));
-  return NPB_OK;
+  return state_copy(h, "npb_task_get_state", task_state_parts, {prev, primed, seen}, false, stream);
 }
 int npb_task_set_state(NpbHandle *h, const double *prev, const int32_t *primed, const int32_t *seen, void *stream) {
-  if (!h) return NPB_EINVAL;
-  if (!h->task.terms) return fail(h, NPB_EINVAL, "npb_task_set_state: no task set (npb_set_task first)");
-  if (!primed || !seen || (h->task.n_delta > 0 && !prev)) return fail(h, NPB_EINVAL, "npb_task_set_state: NULL input (prev may be NULL only for a task without DELTA terms)");
-  NPB_USE_DEVICE(h);
-  const size_t n = (size_t)h->n_plants;
-  hipStream_t st = (hipStream_t)stream;
-  if (h->task.n_delta > 0) NPB_HIP(h, hipMemcpyAsync(h->task.prev, prev, (size_t)h->task.n_delta * n * sizeof(double), hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipMemcpyAsync(h->task.primed, primed, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipMemcpyAsync(h->task.seen, seen, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipStreamSynchronize(st));      /* the host arrays may go */
-  return NPB_OK;
+  return state_copy(h, "npb_task_set_state", task_state_parts, {prev, primed, seen}, true, stream);
 }
 int npb_set_episode_record_task(NpbHandle *h, int32_t *cause) {
   if (!h) return NPB_EINVAL;
@@ -1969,12 +1981,8 @@ int npb_set_features(NpbHandle *h, const npb_features_desc_t *desc) {
   if (!h) return NPB_EINVAL;
   if (const char *why = npb_features_check(desc, h->n_plants)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
-  if (!desc) {
-    if (h->feat.cols) (void)hipFree((void *)h->feat.cols);      /* (hipFree waits for the device: a launch still in flight finishes first) */
-    h->feat = npb_features_t{};
-    return NPB_OK;
-  }
-  /* the handle's one allocation: [the columns] | primed [n] | seen [n] */
+  if (!desc) { attachment_drop(&h->feat, h->feat.cols); return NPB_OK; }
+  /* the allocation: [the columns] | primed [n] | seen [n] */
   std::vector<npb_feature_col_t> table(NPB_FEATURES_COLS_MAX);
   for (int c = 0; c < desc->n_columns; c++) {
     const npb_feature_column_t &F = desc->columns[c];
@@ -1992,23 +2000,14 @@ int npb_set_features(NpbHandle *h, const npb_features_desc_t *desc) {
   }
   const size_t n = (size_t)h->n_plants, table_bytes = table.size() * sizeof(npb_feature_col_t), bytes = table_bytes + 2 * n * sizeof(int32_t);
   static_assert(sizeof(npb_feature_col_t) % 8 == 0, "packed");
+  /* the columns up, everything else zero: every plant unprimed */
   char *dev = nullptr;
-  hipError_t e = hipMalloc((void **)&dev, bytes);
-  if (e != hipSuccess) {
-    char what[160];
-    snprintf(what, sizeof what, "npb_set_features: hipMalloc of the columns and the bookkeeping (%zu bytes) failed", bytes);
-    return fail(h, NPB_EHIP, what, e);
-  }
+  if (int rc = attachment_alloc(h, "npb_set_features", "the columns and the bookkeeping", table.data(), table_bytes, bytes, &dev)) return rc;
   npb_features_t F = {};
   F.cols = (const npb_feature_col_t *)dev; F.n_cols = desc->n_columns; F.stack = desc->stack; F.out_f64 = desc->out_type == NPB_FEATURES_F64;
   F.out = desc->out; F.final = desc->final;
   F.primed = (int32_t *)(dev + table_bytes); F.seen = F.primed + n;
-  /* the columns up, everything else zero: every plant unprimed; synchronous, so the host copy may go */
-  e = hipMemset(dev, 0, bytes);
-  if (e == hipSuccess) e = hipMemcpy(dev, table.data(), table_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  if (e != hipSuccess) { (void)hipFree(dev); return fail(h, NPB_EHIP, "npb_set_features: setting up the columns and the bookkeeping failed", e); }
-  if (h->feat.cols) (void)hipFree((void *)h->feat.cols);
+  attachment_drop(&h->feat, h->feat.cols);
   h->feat = F;
   return NPB_OK;
 }
@@ -2022,35 +2021,19 @@ int npb_features_prime(NpbHandle *h, void *stream) {
 }
 int npb_features_clear(NpbHandle *h, const uint8_t *mask, void *stream) {
   if (!h) return NPB_EINVAL;
-  if (!h->feat.cols) return fail(h, NPB_EINVAL, "npb_features_clear: no features set (npb_set_features first)");
-  NPB_USE_DEVICE(h);
-  npb_launch_features_clear(&h->feat, mask, h->n_plants, (hipStream_t)stream);
-  NPB_HIP(h, hipGetLastError());
-  return NPB_OK;
+  return attachment_clear(h, "npb_features_clear", h->feat.cols, g_no_features,
+                          [&] { npb_launch_unprime(h->feat.primed, mask, h->n_plants, (hipStream_t)stream); });
+}
+/* primed, seen (the stack is the caller's tensor) */
+static StateParts features_state_parts(const NpbHandle *h) {
+  const size_t words = (size_t)h->n_plants * sizeof(int32_t);
+  return {h->feat.cols, g_no_features, "", 2, {{h->feat.primed, words, false}, {h->feat.seen, words, false}}};
 }
 int npb_features_get_state(NpbHandle *h, int32_t *primed, int32_t *seen, void *stream) {
-  if (!h) return NPB_EINVAL;
-  if (!h->feat.cols) return fail(h, NPB_EINVAL, "npb_features_get_state: no features set (npb_set_features first)");
-  if (!primed || !seen) return fail(h, NPB_EINVAL, "npb_features_get_state: NULL output");
-  NPB_USE_DEVICE(h);
-  const size_t n = (size_t)h->n_plants;
-  hipStream_t st = (hipStream_t)stream;
-  NPB_HIP(h, hipMemcpyAsync(primed, h->feat.primed, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipMemcpyAsync(seen, h->feat.seen, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipStreamSynchronize(st));
-  return NPB_OK;
+  return state_copy(h, "npb_features_get_state", features_state_parts, {primed, seen}, false, stream);
 }
 int npb_features_set_state(NpbHandle *h, const int32_t *primed, const int32_t *seen, void *stream) {
-  if (!h) return NPB_EINVAL;
-  if (!h->feat.cols) return fail(h, NPB_EINVAL, "npb_features_set_state: no features set (npb_set_features first)");
-  if (!primed || !seen) return fail(h, NPB_EINVAL, "npb_features_set_state: NULL input");
-  NPB_USE_DEVICE(h);
-  const size_t n = (size_t)h->n_plants;
-  hipStream_t st = (hipStream_t)stream;
-  NPB_HIP(h, hipMemcpyAsync(h->feat.primed, primed, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipMemcpyAsync(h->feat.seen, seen, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipStreamSynchronize(st));      /* the host arrays may go */
-  return NPB_OK;
+  return state_copy(h, "npb_features_set_state", features_state_parts, {primed, seen}, true, stream);
 }
 
 /* ---- controls (include/npb.h, npd_controls.h) */
@@ -2095,11 +2078,8 @@ const char *npb_controls_check(const npb_controls_desc_t *D, int n_plants, int h
 int npb_set_controls(NpbHandle *h, const npb_controls_desc_t *desc) {
   if (!h) return NPB_EINVAL;
   if (const char *why = npb_controls_check(desc, h->n_plants, h->params.heat_source)) return fail(h, NPB_EINVAL, why);
-  if (!desc) {
-    if (h->ctl.age) { NPB_USE_DEVICE(h); (void)hipFree((void *)h->ctl.age); }      /* (hipFree waits for the device: a launch still in flight finishes first) */
-    h->ctl = npb_controls_t{};
-    return NPB_OK;
-  }
+  NPB_USE_DEVICE(h);
+  if (!desc) { attachment_drop(&h->ctl, h->ctl.age); return NPB_OK; }
   npb_controls_t C = {};
   int axis_of[NPB_CONTROL_INPUT_COUNT] = {-1, -1};
   for (int a = 0; a < desc->n_axes; a++) {
@@ -2108,67 +2088,37 @@ int npb_set_controls(NpbHandle *h, const npb_controls_desc_t *desc) {
   }
   if (axis_of[NPB_CONTROL_INPUT_POWER_SETPOINT] >= 0 && h->es_on && h->es.prof.key)
     return fail(h, NPB_EINVAL, "npb_set_controls: a POWER_SETPOINT axis while episode streams drive the profile (npb_set_episode_streams)");
-  NPB_USE_DEVICE(h);
-  /* the handle's one allocation: age [n] | primed [n] | seen [n] (padded to 8 bytes) | the two input columns [n] each; all zero: every
+  /* the allocation: age [n] | primed [n] | seen [n] (padded to 8 bytes) | the two input columns [n] each; no table, all zero: every
    * plant unprimed */
   const size_t n = (size_t)h->n_plants, words = (3 * n + 1) & ~(size_t)1, bytes = words * sizeof(int32_t) + NPB_CONTROL_INPUT_COUNT * n * sizeof(double);
   char *dev = nullptr;
-  hipError_t e = hipMalloc((void **)&dev, bytes);
-  if (e != hipSuccess) {
-    char what[160];
-    snprintf(what, sizeof what, "npb_set_controls: hipMalloc of the bookkeeping and the input columns (%zu bytes) failed", bytes);
-    return fail(h, NPB_EHIP, what, e);
-  }
-  e = hipMemset(dev, 0, bytes);
-  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  if (e != hipSuccess) { (void)hipFree(dev); return fail(h, NPB_EHIP, "npb_set_controls: setting up the bookkeeping failed", e); }
+  if (int rc = attachment_alloc(h, "npb_set_controls", "the bookkeeping and the input columns", nullptr, 0, bytes, &dev)) return rc;
   C.n_axes = desc->n_axes; C.interval = desc->interval; C.in_f64 = desc->in_type == NPB_CONTROLS_F64;
   C.in = desc->in; C.held = desc->held; C.prev = desc->prev;
   C.age = (int32_t *)dev; C.primed = C.age + n; C.seen = C.primed + n;
   for (int i = 0; i < NPB_CONTROL_INPUT_COUNT; i++) C.column[i] = (double *)(dev + words * sizeof(int32_t)) + (size_t)i * n;
-  if (h->ctl.age) (void)hipFree((void *)h->ctl.age);
+  attachment_drop(&h->ctl, h->ctl.age);
   h->ctl = C;
   for (int i = 0; i < NPB_CONTROL_INPUT_COUNT; i++) h->ctl_axis[i] = axis_of[i];
   return NPB_OK;
 }
 int npb_controls_clear(NpbHandle *h, const uint8_t *mask, void *stream) {
   if (!h) return NPB_EINVAL;
-  if (!h->ctl.age) return fail(h, NPB_EINVAL, "npb_controls_clear: no controls set (npb_set_controls first)");
-  NPB_USE_DEVICE(h);
-  npb_launch_controls_clear(&h->ctl, mask, h->n_plants, (hipStream_t)stream);
-  NPB_HIP(h, hipGetLastError());
-  return NPB_OK;
+  return attachment_clear(h, "npb_controls_clear", h->ctl.age, g_no_controls,
+                          [&] { npb_launch_unprime(h->ctl.primed, mask, h->n_plants, (hipStream_t)stream); });
+}
+/* held, prev (the caller's tensors, which the decode carries from step to step), age, primed, seen */
+static StateParts controls_state_parts(const NpbHandle *h) {
+  const size_t n = (size_t)h->n_plants, values = (size_t)h->ctl.n_axes * n * sizeof(double), words = n * sizeof(int32_t);
+  return {h->ctl.age, g_no_controls, "", 5,
+          {{h->ctl.held, values, false}, {h->ctl.prev, values, false}, {h->ctl.age, words, false}, {h->ctl.primed, words, false}, {h->ctl.seen, words, false}}};
 }
 int npb_controls_get_state(NpbHandle *h, double *held, double *prev, int32_t *age, int32_t *primed, int32_t *seen, void *stream) {
-  if (!h) return NPB_EINVAL;
-  if (!h->ctl.age) return fail(h, NPB_EINVAL, "npb_controls_get_state: no controls set (npb_set_controls first)");
-  if (!held || !prev || !age || !primed || !seen) return fail(h, NPB_EINVAL, "npb_controls_get_state: NULL output");
-  NPB_USE_DEVICE(h);
-  const size_t n = (size_t)h->n_plants, values = (size_t)h->ctl.n_axes * n * sizeof(double);
-  hipStream_t st = (hipStream_t)stream;
-  NPB_HIP(h, hipMemcpyAsync(held, h->ctl.held, values, hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipMemcpyAsync(prev, h->ctl.prev, values, hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipMemcpyAsync(age, h->ctl.age, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipMemcpyAsync(primed, h->ctl.primed, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipMemcpyAsync(seen, h->ctl.seen, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  NPB_HIP(h, hipStreamSynchronize(st));
-  return NPB_OK;
+  return state_copy(h, "npb_controls_get_state", controls_state_parts, {held, prev, age, primed, seen}, false, stream);
 }
 int npb_controls_set_state(NpbHandle *h, const double *held, const double *prev, const int32_t *age, const int32_t *primed, const int32_t *seen,
                            void *stream) {
-  if (!h) return NPB_EINVAL;
-  if (!h->ctl.age) return fail(h, NPB_EINVAL, "npb_controls_set_state: no controls set (npb_set_controls first)");
-  if (!held || !prev || !age || !primed || !seen) return fail(h, NPB_EINVAL, "npb_controls_set_state: NULL input");
-  NPB_USE_DEVICE(h);
-  const size_t n = (size_t)h->n_plants, values = (size_t)h->ctl.n_axes * n * sizeof(double);
-  hipStream_t st = (hipStream_t)stream;
-  NPB_HIP(h, hipMemcpyAsync(h->ctl.held, held, values, hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipMemcpyAsync(h->ctl.prev, prev, values, hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipMemcpyAsync(h->ctl.age, age, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipMemcpyAsync(h->ctl.primed, primed, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipMemcpyAsync(h->ctl.seen, seen, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  NPB_HIP(h, hipStreamSynchronize(st));      /* the host arrays may go */
-  return NPB_OK;
+  return state_copy(h, "npb_controls_set_state", controls_state_parts, {held, prev, age, primed, seen}, true, stream);
 }
 
 /* ---- episode streams (include/npb.h) */

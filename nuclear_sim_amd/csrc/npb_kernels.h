@@ -201,12 +201,8 @@ void npb_launch_maint_summary_clear(const npb_maint_summary_desc_t *D, const uin
 void npb_launch_column_stats_clear(const npb_column_stats_t *S, const uint8_t *mask, int n_plants, hipStream_t stream);
 /* npb_event_windows_clear (npd_event_windows.h): the plants of mask (NULL = all) unprimed, their rings empty, an armed capture dropped */
 void npb_launch_event_windows_clear(const npb_event_windows_t *W, const uint8_t *mask, int n_plants, hipStream_t stream);
-/* npb_task_clear (npd_task.h): the plants of mask (NULL = all) unprimed */
-void npb_launch_task_clear(const npb_task_t *T, const uint8_t *mask, int n_plants, hipStream_t stream);
-/* npb_features_clear (npd_features.h): the plants of mask (NULL = all) unprimed */
-void npb_launch_features_clear(const npb_features_t *F, const uint8_t *mask, int n_plants, hipStream_t stream);
-/* npb_controls_clear (npd_controls.h): the plants of mask (NULL = all) unprimed */
-void npb_launch_controls_clear(const npb_controls_t *C, const uint8_t *mask, int n_plants, hipStream_t stream);
+/* npb_task_clear, npb_features_clear, npb_controls_clear: the plants of mask (NULL = all) unprimed in that attachment's `primed` column */
+void npb_launch_unprime(int32_t *primed, const uint8_t *mask, int n_plants, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

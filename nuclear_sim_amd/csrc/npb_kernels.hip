@@ -1855,11 +1855,25 @@ static void NPB_LAUNCHER(episode_records)(int n_plants, size_t npad, const void 
 /* state windows around events (npb_set_event_windows): the per-step kernel, the clear kernel and their launchers */
 #include "npd_event_windows.h"
 
-/* the caller's reward terms and termination rules (npb_set_task): the per-step kernel, the clear kernel and their launchers */
+/* the caller's reward terms and termination rules (npb_set_task): the per-step kernel and its launcher */
 #include "npd_task.h"
 
-/* the caller's policy inputs (npb_set_features): the frame-stack kernel, the clear kernel and their launchers */
+/* the caller's policy inputs (npb_set_features): the frame-stack kernel and its launcher */
 #include "npd_features.h"
 
-/* the caller's policy outputs (npb_set_controls): the decode kernel in front of the step, the clear kernel and their launchers */
+/* the caller's policy outputs (npb_set_controls): the decode kernel in front of the step and its launcher */
 #include "npd_controls.h"
+
+#ifndef NPB_BUILD_F32
+/* npb_task_clear, npb_features_clear, npb_controls_clear: the plants of mask (NULL = all) unprimed in that attachment's `primed` column --
+ * the task's next DELTA samples are 0, the features' next frame fills every slot, the controls' next step starts a new hold; the same
+ * for either storage type (compiled once) */
+__global__ __launch_bounds__(256) void npb_unprime_kernel(int32_t *__restrict__ primed, const uint8_t *__restrict__ mask, int n_plants) {
+  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= (size_t)n_plants || (mask && !mask[p])) return;
+  primed[p] = 0;
+}
+extern "C" void npb_launch_unprime(int32_t *primed, const uint8_t *mask, int n_plants, hipStream_t stream) {
+  hipLaunchKernelGGL(npb_unprime_kernel, dim3((unsigned)((n_plants + 255) / 256)), dim3(256), 0, stream, primed, mask, n_plants);
+}
+#endif

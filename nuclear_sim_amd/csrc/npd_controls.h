@@ -127,17 +127,4 @@ static void NPB_LAUNCHER(controls)(void *arena, size_t npad, const npb_controls_
   if (C->in_f64) hipLaunchKernelGGL(npb_controls_kernel<double>, grid, block, 0, stream, (npd_real_t *)arena, npad, *C, *P, n_plants, index);
   else hipLaunchKernelGGL(npb_controls_kernel<float>, grid, block, 0, stream, (npd_real_t *)arena, npad, *C, *P, n_plants, index);
 }
-
-#ifndef NPB_BUILD_F32
-/* npb_controls_clear, and the start of npb_set_controls: the plants of mask (NULL = all) unprimed -- their next step starts a new hold;
- * the same for either storage type (compiled once) */
-__global__ __launch_bounds__(256) void npb_controls_clear_kernel(npb_controls_t C, const uint8_t *__restrict__ mask, int n_plants) {
-  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= (size_t)n_plants || (mask && !mask[p])) return;
-  C.primed[p] = 0;
-}
-extern "C" void npb_launch_controls_clear(const npb_controls_t *C, const uint8_t *mask, int n_plants, hipStream_t stream) {
-  hipLaunchKernelGGL(npb_controls_clear_kernel, dim3((unsigned)((n_plants + 255) / 256)), dim3(256), 0, stream, *C, mask, n_plants);
-}
-#endif
 #endif

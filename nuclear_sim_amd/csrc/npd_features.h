@@ -152,17 +152,4 @@ static void NPB_LAUNCHER(features)(const void *arena, size_t npad, const npb_fea
   else { if (wide) NPD_FEATURES_LAUNCH(float, 4); else NPD_FEATURES_LAUNCH(float, 1); }
 #undef NPD_FEATURES_LAUNCH
 }
-
-#ifndef NPB_BUILD_F32
-/* npb_features_clear, and the start of npb_set_features: the plants of mask (NULL = all) unprimed -- their next frame fills every slot;
- * the same for either storage type (compiled once) */
-__global__ __launch_bounds__(256) void npb_features_clear_kernel(npb_features_t F, const uint8_t *__restrict__ mask, int n_plants) {
-  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= (size_t)n_plants || (mask && !mask[p])) return;
-  F.primed[p] = 0;
-}
-extern "C" void npb_launch_features_clear(const npb_features_t *F, const uint8_t *mask, int n_plants, hipStream_t stream) {
-  hipLaunchKernelGGL(npb_features_clear_kernel, dim3((unsigned)((n_plants + 255) / 256)), dim3(256), 0, stream, *F, mask, n_plants);
-}
-#endif
 #endif

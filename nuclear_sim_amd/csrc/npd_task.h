@@ -85,17 +85,4 @@ static void NPB_LAUNCHER(task)(const void *arena, size_t npad, const npb_task_t 
   hipLaunchKernelGGL(npb_task_kernel, dim3((unsigned)((n_plants + NPB_WAVE - 1) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream,
                      (const npd_real_t *)arena, npad, *T, n_plants, index);
 }
-
-#ifndef NPB_BUILD_F32
-/* npb_task_clear, and the start of npb_set_task: the plants of mask (NULL = all) unprimed -- their next DELTA samples are 0; the same
- * for either storage type (compiled once) */
-__global__ __launch_bounds__(256) void npb_task_clear_kernel(npb_task_t T, const uint8_t *__restrict__ mask, int n_plants) {
-  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= (size_t)n_plants || (mask && !mask[p])) return;
-  T.primed[p] = 0;
-}
-extern "C" void npb_launch_task_clear(const npb_task_t *T, const uint8_t *mask, int n_plants, hipStream_t stream) {
-  hipLaunchKernelGGL(npb_task_clear_kernel, dim3((unsigned)((n_plants + 255) / 256)), dim3(256), 0, stream, *T, mask, n_plants);
-}
-#endif
 #endif

@@ -504,6 +504,7 @@ class BatchedPlantEnv:
         self._keep = []
         self._episode = None
         self._bank = None
+        self._mlog = self._msum = self._erec = self._cstats = self._ewin = self._task = self._feat = self._ctl = None      # (see ``_OFF``)
         self._diag_buf = None; self.diagnostics = None; self._diag_carried = False
         if diagnostics:      # before the first snapshot (autoreset=True takes it below), so that it records the carried rows
             self.enable_diagnostics(True, carried=True)
@@ -703,7 +704,7 @@ class BatchedPlantEnv:
         # the drain's landing place: pinned host memory, so that a drain is a DMA copy rather than a staged one
         self._mlog = {"records": records, "cursor": cursor, "capacity": cap, "host": torch.empty(records.numel(), dtype=torch.uint8, pin_memory=True),
                       "host_cursor": torch.empty(1, dtype=torch.int32, pin_memory=True)}
-        ms = getattr(self, "_msum", None)
+        ms = self._msum
         if ms is not None:      # a summary that consumed a staging log of its own now folds the caller's log, and leaves it to the caller
             ms["desc"].consume = 0
             ms["words"].zero_()
@@ -714,13 +715,11 @@ class BatchedPlantEnv:
         """Drain the log on the env's stream: the records (numpy, ``maintlog.EVENT_DTYPE``) in the device's order.  An overflowed
         log raises, naming how many events were dropped, and is left as it is, unless ``allow_overflow``."""
         from . import maintlog
-        ml = getattr(self, "_mlog", None)
-        ms = getattr(self, "_msum", None)
+        ms = self._msum
         if ms is not None and ms["consume"]:
             raise _lib.NpbError("the maintenance summary consumes the log (enable_maintenance_summary's staging ring): there is nothing to "
                                 "drain; enable_maintenance_summary(..., keep_log=True) keeps the records")
-        if ml is None:
-            raise _lib.NpbError("no maintenance log: enable_maintenance_log() first")
+        ml = self._on("_mlog")
         stream = torch.cuda.current_stream(self.device)
         ml["host_cursor"].copy_(ml["cursor"], non_blocking=True)
         stream.synchronize()
@@ -773,14 +772,14 @@ class BatchedPlantEnv:
         that did not fit the log are counted in ``maintenance_summary()["dropped"]``.  ``include_logged=True`` also folds, at once, the
         records the caller's log already holds: an existing log summarised under new keys.  Output only, like the log: ``snapshot``,
         ``restore``, the autoreset and the start bank leave it alone; ``clear_maintenance_summary(mask)`` starts the masked plants afresh."""
-        er = getattr(self, "_erec", None)
+        er = self._erec
         if er is not None and (er["n_keys"] or er["desc"].clear_summary):
             raise _lib.NpbError("episode records that copy or clear the maintenance summary are on: disable_episode_records() first")
-        ew = getattr(self, "_ewin", None)
-        if ew is not None and ew["summary"] is not None:
+        # (the task and the features may read the count tables too: they keep the tensors they read alive, and are not refused)
+        if self._readers_of(("n_created", "n_completed"), among=("_ewin",)):
             raise _lib.NpbError("event windows with a work_order / completed trigger read the maintenance summary's tables: enable_event_windows(None) first")
         if keys is None:
-            if getattr(self, "_msum", None) is not None:
+            if self._msum is not None:
                 _lib.check(self.L.npb_set_maintenance_summary(self._h, None), self._h)
                 if self._msum["own_log"]:
                     self._msum = None
@@ -792,8 +791,8 @@ class BatchedPlantEnv:
             raise ValueError("a maintenance summary has 1 to %d keys, not %d" % (_lib.SUMMARY_MAX_KEYS, len(K)))
         if not hasattr(self.L, "npb_set_maintenance_summary"):
             raise _lib.NpbError("libnpb.so has no npb_set_maintenance_summary (older than ABI 154): rebuild")
-        prev = getattr(self, "_msum", None)
-        own_log = getattr(self, "_mlog", None) is None or (prev is not None and prev["own_log"])
+        prev = self._msum
+        own_log = self._mlog is None or (prev is not None and prev["own_log"])
         if own_log:
             self._msum = None
             self.enable_maintenance_log(max(4 * self.n, 4096) if log_capacity is None else int(log_capacity))
@@ -821,24 +820,18 @@ class BatchedPlantEnv:
         never), ``n_created`` / ``n_completed`` (int32), and ``dropped`` (a 0-d int32 tensor: events the log had no room for, which the
         summary therefore never saw).  The env's own buffers, as ``info`` is: current after every ``step`` and ``perform_*_maintenance``,
         valid in stream order, never synchronised here."""
-        ms = getattr(self, "_msum", None)
-        if ms is None:
-            raise _lib.NpbError("no maintenance summary: enable_maintenance_summary() first")
+        ms = self._on("_msum")
         return {"first_created": ms["times"][0], "first_completed": ms["times"][1], "n_created": ms["counts"][0],
                 "n_completed": ms["counts"][1], "dropped": ms["words"][1]}
 
     def clear_maintenance_summary(self, mask=None) -> None:
         """the summary rows of the masked plants (None = all) back to "never" and 0 (npb_maint_summary_clear): what a caller does for the
         plants it restarted when it wants per-episode summaries"""
-        if getattr(self, "_msum", None) is None:
-            raise _lib.NpbError("no maintenance summary: enable_maintenance_summary() first")
-        m = None if mask is None else self._col(mask, torch.uint8)
-        _lib.check(self.L.npb_maint_summary_clear(self._h, None if m is None else self._p(m), self._stream()), self._h)
+        self._clear("_msum", self.L.npb_maint_summary_clear, mask)
 
     def fold_maintenance_summary(self) -> None:
         """fold the log into the summary now (npb_maint_summary_fold); ``step`` and the ``perform_*_maintenance`` calls do it themselves"""
-        if getattr(self, "_msum", None) is None:
-            raise _lib.NpbError("no maintenance summary: enable_maintenance_summary() first")
+        self._on("_msum")
         _lib.check(self.L.npb_maint_summary_fold(self._h, self._stream()), self._h)
 
     def enable_episode_records(self, capacity: Optional[int] = None, final_obs: bool = False, summary: Optional[bool] = None,
@@ -858,7 +851,7 @@ class BatchedPlantEnv:
         and releases the buffers.  An episode the caller abandons (``restore``, ``restore_from_bank``, ``reset``) starts the next index
         and leaves no record."""
         if off:
-            if getattr(self, "_erec", None) is not None:
+            if self._erec is not None:
                 _lib.check(self.L.npb_set_episode_records(self._h, None), self._h)
             self._erec = None
             return
@@ -866,12 +859,12 @@ class BatchedPlantEnv:
             raise _lib.NpbError("libnpb.so has no npb_set_episode_records: rebuild")
         if self._episode is None:
             raise ValueError("episode records need autoreset=True: they are the episodes the autoreset ends")
-        has_summary = getattr(self, "_msum", None) is not None
+        has_summary = self._msum is not None
         summary = has_summary if summary is None else bool(summary)
         clear_summary = has_summary if clear_summary is None else bool(clear_summary)
         if (summary or clear_summary) and not has_summary:
             raise ValueError("episode records with summary / clear_summary need enable_maintenance_summary() first")
-        cst = getattr(self, "_cstats", None)
+        cst = self._cstats
         stats = (cst is not None) if stats is None else bool(stats)
         clear_stats = (cst is not None) if clear_stats is None else bool(clear_stats)
         if (stats or clear_stats) and cst is None:
@@ -927,8 +920,8 @@ class BatchedPlantEnv:
     def _record_task_cause(self) -> None:
         """while records and a task are both on every record carries the task's cause word (npb_set_episode_record_task); the handle drops
         the column with every new set of record columns, so this follows ``enable_episode_records`` and ``set_task``"""
-        er = getattr(self, "_erec", None)
-        if er is None or getattr(self, "_task", None) is None:
+        er = self._erec
+        if er is None or self._task is None:
             return
         if "cause" not in er["dev"]:
             with torch.cuda.device(self.device):
@@ -938,7 +931,7 @@ class BatchedPlantEnv:
 
     def _drop_record_task_cause(self) -> None:
         """the records without the cause column (the handle refuses another task, or none, while they hold the old one's)"""
-        er = getattr(self, "_erec", None)
+        er = self._erec
         if er is not None and "cause" in er["dev"]:
             _lib.check(self.L.npb_set_episode_record_task(self._h, None), self._h)
             del er["dev"]["cause"], er["host"]["cause"]
@@ -956,9 +949,7 @@ class BatchedPlantEnv:
         ``stat_n_samples``; while a task is set (``set_task``) ``cause`` (uint32: the rules that ended the episode, 0 = none did).  An
         overflowed log raises, naming how many episodes were dropped, and is left as it is,
         unless ``allow_overflow`` (which of one step's episodes fitted is then not defined)."""
-        er = getattr(self, "_erec", None)
-        if er is None:
-            raise _lib.NpbError("no episode records: enable_episode_records() first")
+        er = self._on("_erec")
         stream = torch.cuda.current_stream(self.device)
         er["host_cursor"].copy_(er["cursor"], non_blocking=True)
         stream.synchronize()
@@ -1016,20 +1007,81 @@ class BatchedPlantEnv:
         the summary's two count tables while a summary is on, the task's reward and cause while a task is on.  Which of them a feature
         accepts is decided by its vocabulary in ``_lib``, not by what is listed here"""
         buffers = {"info": self._info_buf, "obs": self._obs, "reward": self._reward, "flags": self._flags, "done": self._done}
-        ms, tk = getattr(self, "_msum", None), getattr(self, "_task", None)
+        ms, tk, ct = self._msum, self._task, self._ctl
         if ms is not None:
             buffers.update(n_created=ms["counts"][0], n_completed=ms["counts"][1])
         if tk is not None:
             buffers.update(task_reward=tk["reward"], task_cause=tk["cause"])
-        ct = getattr(self, "_ctl", None)
         if ct is not None:
             buffers.update(control=ct["held"], control_prev=ct["prev"])
         return buffers
 
+    # ------------------------------------------------------------------ what the attachments share
+    # The per-step attachments -- maintenance log and summary, episode records, column statistics, event windows, task, features,
+    # controls: None = off, else what the enable_* / set_* method keeps of it.  __init__ sets them; the class has them too, so that a
+    # refusal "before any device work" can be checked on an object made without it.  ``_on`` reads them, with these refusals:
+    _mlog = _msum = _erec = _cstats = _ewin = _task = _feat = _ctl = None
+    _OFF = {"_mlog": "no maintenance log: enable_maintenance_log() first", "_msum": "no maintenance summary: enable_maintenance_summary() first",
+            "_erec": "no episode records: enable_episode_records() first", "_cstats": "no column statistics: enable_column_stats() first",
+            "_ewin": "no event windows: enable_event_windows() first", "_task": "no task: set_task() first",
+            "_feat": "no features: set_features() first", "_ctl": "no controls: set_controls() first"}
+    # who reads side buffers, as a refusal names them: each keeps ``"reads"``, the buffers its request resolved to (``_reading``)
+    _CONSUMERS = {"_task": "the task", "_feat": "the features", "_cstats": "the column statistics", "_ewin": "the event windows"}
+
+    def _on(self, attr) -> dict:
+        """THE "is it on" of an attachment: what it keeps, or its refusal"""
+        what = getattr(self, attr)
+        if what is None:
+            raise _lib.NpbError(self._OFF[attr])
+        return what
+
+    def _clear(self, attr, clear, mask) -> dict:
+        """the body of the ``clear_*`` methods: the attachment must be on, the mask (None = all) goes to the library's ``clear`` as a column"""
+        what = self._on(attr)
+        _lib.check(clear(self._h, self._p(self._col(mask, torch.uint8)), self._stream()), self._h)
+        return what
+
+    @staticmethod
+    def _reading(req, buffers) -> dict:
+        """What a consumer keeps of the side buffers its request resolved to -- columns, reference columns and triggers alike:
+        ``"reads"``, the frozenset of their names, by which ``_readers_of`` finds it, and ``"holds"``, the tensors themselves, so that
+        none is freed while a kernel reads it, whether or not its provider refuses to change meanwhile"""
+        rows = list(req.get("columns", ())) + list(req.get("triggers", ()))
+        reads = frozenset([side[0] for side in req.get("sides", ())] + [R["side"][0] for R in rows if R["side"]])
+        return {"reads": reads, "holds": [buffers[name] for name in sorted(reads)]}
+
+    def _readers_of(self, names, among=tuple(_CONSUMERS)):
+        """the consumers, of ``among`` and in its order, that read any of the side buffers ``names``, as a refusal names them"""
+        return [self._CONSUMERS[attr] for attr in among if getattr(self, attr) is not None and getattr(self, attr)["reads"] & set(names)]
+
     def _n_controls(self) -> int:
         """the axis count while controls are set, else 0: what ``_lib.column_word`` takes as ``controls``"""
-        ct = getattr(self, "_ctl", None)
-        return 0 if ct is None else ct["held"].shape[0]
+        return 0 if self._ctl is None else self._ctl["held"].shape[0]
+
+    def _get_state(self, attr, getter) -> Dict[str, np.ndarray]:
+        """an attachment's checkpointed state, the arrays of its ``"state"`` tuple of (name, dtype, shape) filled by the library's
+        ``getter``, which takes them in that order (an empty one as NULL)"""
+        out = {name: np.zeros(shape, dtype=dtype) for name, dtype, shape in self._on(attr)["state"]}
+        _lib.check(getter(self._h, *[a.ctypes.data if a.size else None for a in out.values()], self._stream()), self._h)
+        return out
+
+    def _load_state(self, attr, setter, state) -> list:
+        """the inverse: ``state``'s entries coerced to the dtypes and shapes of the ``"state"`` tuple and handed to the library's ``setter``"""
+        parts = [np.ascontiguousarray(np.asarray(state[name], dtype=dtype).reshape(shape)) for name, dtype, shape in self._on(attr)["state"]]
+        _lib.check(setter(self._h, *[a.ctypes.data if a.size else None for a in parts], self._stream()), self._h)
+        return parts
+
+    def _column_samples(self, columns) -> torch.Tensor:
+        """the rows ``columns`` (``_lib.column_word``'s answers) name as they are NOW, widened to float64, [len(columns), n] on the device"""
+        buffers = self._side_buffers()
+        rows = []
+        for C in columns:
+            if C["member"] is not None:
+                rows.append(self._get_slot("f64" if C["member"][0] == 0 else "i32", C["member"][1]).to(torch.float64))
+            else:
+                name, offset, stride, _kind = C["side"]
+                rows.append(buffers[name].reshape(-1)[self._side_first(name, offset)::stride][:self.n].to(torch.float64))
+        return torch.stack(rows)
 
     def _side_first(self, name, offset) -> int:
         """the element of side buffer ``name`` that holds plant 0's value of the column at ``offset``: a summary table is [n_keys][n], the
@@ -1049,6 +1101,18 @@ class BatchedPlantEnv:
             C.from_source = 1
             self._fill_source(C.source, buffers, *where["side"])
 
+    def _fill_columns(self, d, req, buffers):
+        """fill n_fields / kinds / slots / n_sources / sources of the descriptor ``d`` from a request's members and sides; returns the ctypes
+        arrays, which the caller keeps alive for as long as the descriptor is read"""
+        nm, ns = len(req["members"]), len(req["sides"])
+        kinds = (ctypes.c_int * max(nm, 1))(*[m[0] for m in req["members"]])
+        slots = (ctypes.c_int * max(nm, 1))(*[m[1] for m in req["members"]])
+        side = (_lib.NpbSampleSource * max(ns, 1))()
+        for k, where in enumerate(req["sides"]):
+            self._fill_source(side[k], buffers, *where)
+        d.n_fields, d.kinds, d.slots, d.n_sources, d.sources = nm, kinds, slots, ns, side
+        return kinds, slots, side
+
     def enable_column_stats(self, columns, limits=None, stats=("min", "max", "sum", "sumsq", "last")) -> None:
         """Have the device fold per-plant statistics of ``columns`` behind every step (npb_set_column_stats): one more launch, a thread per
         (column, plant), the sample being the end-of-step state of the episode the step belonged to, before any restore.  ``columns``: up
@@ -1060,29 +1124,21 @@ class BatchedPlantEnv:
         numpy, bit for bit.  ``None`` for ``columns`` turns it off.  Output only, like the maintenance summary: ``snapshot``, ``restore``,
         the resets, the autoreset and the start bank leave the tables alone; ``clear_column_stats(mask)`` starts the masked plants afresh,
         and episode records enabled afterwards do so for every episode that ends (``enable_episode_records(stats=..., clear_stats=...)``)."""
-        er = getattr(self, "_erec", None)
-        if er is not None and er.get("stats") is not None:
+        if self._erec is not None and self._erec.get("stats") is not None:
             raise _lib.NpbError("episode records that copy or clear the column statistics are on: disable_episode_records() first")
         if columns is None:
-            if getattr(self, "_cstats", None) is not None:
+            if self._cstats is not None:
                 _lib.check(self.L.npb_set_column_stats(self._h, None), self._h)
             self._cstats = None
             return
-        tk = getattr(self, "_task", None)
-        req = _lib.column_stats_request(columns, limits, stats, INFO_COLUMNS, tk is not None, self._n_controls())      # an unknown name, index or statistic is refused here
+        req = _lib.column_stats_request(columns, limits, stats, INFO_COLUMNS, self._task is not None, self._n_controls())      # an unknown name, index or statistic is refused here
         if not hasattr(self.L, "npb_set_column_stats"):
             raise _lib.NpbError("libnpb.so has no npb_set_column_stats: rebuild")
-        nm, ns = len(req["members"]), len(req["sides"])
-        n_cols = nm + ns
+        n_cols = len(req["members"]) + len(req["sides"])
         d = _lib.NpbColumnStatsDesc()
-        kinds = (ctypes.c_int * max(nm, 1))(*[m[0] for m in req["members"]])
-        slots = (ctypes.c_int * max(nm, 1))(*[m[1] for m in req["members"]])
-        side = (_lib.NpbSampleSource * max(ns, 1))()
         buffers = self._side_buffers()
-        for k, where in enumerate(req["sides"]):
-            self._fill_source(side[k], buffers, *where)
-        direction, limit = (ctypes.c_int * n_cols)(*req["direction"]), (ctypes.c_double * n_cols)(*req["limit"])
-        d.n_fields, d.kinds, d.slots, d.n_sources, d.sources, d.direction, d.limit = nm, kinds, slots, ns, side, direction, limit
+        keep = self._fill_columns(d, req, buffers)      # (the library copies the descriptor's arrays during the call)
+        d.direction, d.limit = (ctypes.c_int * n_cols)(*req["direction"]), (ctypes.c_double * n_cols)(*req["limit"])
         from . import colstats
         tables = {}
         with torch.cuda.device(self.device):
@@ -1093,32 +1149,24 @@ class BatchedPlantEnv:
             tables["n_samples"] = torch.zeros(self.n, dtype=torch.int32, device=self.device)
         d.n_samples = tables["n_samples"].data_ptr()
         _lib.check(self.L.npb_set_column_stats(self._h, ctypes.byref(d)), self._h)
-        self._cstats = {"tables": tables, "stats": req["stats"], "order": req["order"], "columns": list(columns),
-                        "task": any(side[0] == "task_reward" for side in req["sides"]),
-                        "controls": any(side[0] in ("control", "control_prev") for side in req["sides"])}
+        self._cstats = dict(self._reading(req, buffers), tables=tables, stats=req["stats"], order=req["order"], columns=list(columns))
 
     def column_stats(self) -> Dict[str, torch.Tensor]:
         """The statistics' tables, [n_cols, n] each in the order of ``columns``, and ``n_samples`` [n], on the device, never synchronised
         here.  Where ``columns`` lists every state member ahead of every info / obs / reward column -- the order the device keeps them in
         -- these are the env's own buffers, as ``maintenance_summary()``'s are: current after every later ``step`` too.  For a request in
         any other order the tables are an indexed COPY made now, in stream order: it does not follow later steps; call again."""
-        cs = getattr(self, "_cstats", None)
-        if cs is None:
-            raise _lib.NpbError("no column statistics: enable_column_stats() first")
+        cs = self._on("_cstats")
         identity = cs["order"] == list(range(len(cs["order"])))
         return {name: t if (identity or t.dim() == 1) else t[cs["order"]] for name, t in cs["tables"].items()}
 
     def clear_column_stats(self, mask=None) -> None:
         """the cells of the masked plants (None = all) back to the empty values in every table (npb_column_stats_clear)"""
-        if getattr(self, "_cstats", None) is None:
-            raise _lib.NpbError("no column statistics: enable_column_stats() first")
-        m = None if mask is None else self._col(mask, torch.uint8)
-        _lib.check(self.L.npb_column_stats_clear(self._h, None if m is None else self._p(m), self._stream()), self._h)
+        self._clear("_cstats", self.L.npb_column_stats_clear, mask)
 
     def fold_column_stats(self) -> None:
         """fold one sample of the current state now (npb_column_stats_fold); ``step`` does it itself"""
-        if getattr(self, "_cstats", None) is None:
-            raise _lib.NpbError("no column statistics: enable_column_stats() first")
+        self._on("_cstats")
         _lib.check(self.L.npb_column_stats_fold(self._h, self._stream()), self._h)
 
     def enable_event_windows(self, columns, triggers=None, pre: int = 8, post: int = 8, capacity: Optional[int] = None) -> None:
@@ -1137,33 +1185,28 @@ class BatchedPlantEnv:
         Output only: ``snapshot``, ``restore`` and the start bank leave it alone.  While it is on, the maintenance summary a
         ``work_order`` trigger reads must stay as it is."""
         if columns is None:
-            if getattr(self, "_ewin", None) is not None:
+            if self._ewin is not None:
                 _lib.check(self.L.npb_set_event_windows(self._h, None), self._h)
             self._ewin = None
             return
-        ms = getattr(self, "_msum", None)
-        tk = getattr(self, "_task", None)
-        req = _lib.event_windows_request(columns, triggers or (), pre, post, INFO_COLUMNS, 0 if ms is None else len(ms["keys"]), tk is not None,
+        ms = self._msum
+        req = _lib.event_windows_request(columns, triggers or (), pre, post, INFO_COLUMNS, 0 if ms is None else len(ms["keys"]), self._task is not None,
                                          self._n_controls())
         if not hasattr(self.L, "npb_set_event_windows"):
             raise _lib.NpbError("libnpb.so has no npb_set_event_windows: rebuild")
         cap = max(self.n, 4096) if capacity is None else int(capacity)
         if cap < 1:
             raise ValueError("capacity must be >= 1")
-        nm, ns, nt = len(req["members"]), len(req["sides"]), len(req["triggers"])
-        n_cols, H = nm + ns, req["pre"] + 1 + req["post"]
+        nt = len(req["triggers"])
+        n_cols, H = len(req["members"]) + len(req["sides"]), req["pre"] + 1 + req["post"]
         d = _lib.NpbEventWindowsDesc()
-        kinds = (ctypes.c_int * max(nm, 1))(*[m[0] for m in req["members"]])
-        slots = (ctypes.c_int * max(nm, 1))(*[m[1] for m in req["members"]])
-        side = (_lib.NpbSampleSource * max(ns, 1))()
         buffers = self._side_buffers()
-        for k, where in enumerate(req["sides"]):
-            self._fill_source(side[k], buffers, *where)
+        keep = self._fill_columns(d, req, buffers)
         trig = (_lib.NpbEventTrigger * nt)()
         for k, T in enumerate(req["triggers"]):
             self._fill_column(trig[k], buffers, T)
             trig[k].mode, trig[k].mask, trig[k].direction, trig[k].limit = _lib.TRIGGER_MODES[T["mode"]], T["mask"], T["direction"], T["limit"]
-        d.n_fields, d.kinds, d.slots, d.n_sources, d.sources, d.n_triggers, d.triggers = nm, kinds, slots, ns, side, nt, trig
+        d.n_triggers, d.triggers = nt, trig
         d.pre, d.post, d.capacity = req["pre"], req["post"], cap
         dev, host = {}, {}
         with torch.cuda.device(self.device):
@@ -1176,15 +1219,10 @@ class BatchedPlantEnv:
             cursor = torch.zeros(1, dtype=torch.int32, device=self.device)     # a uint32 on the device
         d.cursor = cursor.data_ptr()
         _lib.check(self.L.npb_set_event_windows(self._h, ctypes.byref(d)), self._h)
-        self._ewin = {"desc": d, "keep": (kinds, slots, side, trig), "dev": dev, "host": host, "cursor": cursor,
-                      "host_cursor": torch.empty(1, dtype=torch.int32, pin_memory=True), "capacity": cap, "order": req["order"],
-                      "columns": list(columns), "pre": req["pre"], "post": req["post"], "triggers": req["numpy"],
-                      "bytes": int(self.L.npb_event_windows_bytes(ctypes.byref(d), self.n)),
-                      "summary": ms["counts"] if any(T["side"] and T["side"][0] in ("n_created", "n_completed") for T in req["triggers"]) else None,
-                      "task": any(side[0] == "task_reward" for side in req["sides"]) or
-                              any(T["side"] and T["side"][0] in ("task_reward", "task_cause") for T in req["triggers"]),
-                      "controls": any(side[0] in ("control", "control_prev") for side in req["sides"]) or
-                                  any(T["side"] and T["side"][0] in ("control", "control_prev") for T in req["triggers"])}
+        self._ewin = dict(self._reading(req, buffers), desc=d, keep=keep + (trig,), dev=dev, host=host, cursor=cursor,
+                          host_cursor=torch.empty(1, dtype=torch.int32, pin_memory=True), capacity=cap, order=req["order"],
+                          columns=list(columns), pre=req["pre"], post=req["post"], triggers=req["numpy"],
+                          bytes=int(self.L.npb_event_windows_bytes(ctypes.byref(d), self.n)))
 
     def event_windows(self, clear: bool = True, allow_overflow: bool = False) -> Dict[str, np.ndarray]:
         """Drain the event windows on the env's stream, one read-back: numpy columns of m records sorted by (capture step, plant) --
@@ -1194,9 +1232,7 @@ class BatchedPlantEnv:
         ``pre`` is the trigger sample; rows outside ``[pre - n_pre, pre + n_post]`` are NaN) and ``early`` = ``flags & 1``.  An
         overflowed log raises, naming how many captures were dropped, and is left as it is, unless ``allow_overflow`` (which of one
         step's captures fitted is then not defined)."""
-        ew = getattr(self, "_ewin", None)
-        if ew is None:
-            raise _lib.NpbError("no event windows: enable_event_windows() first")
+        ew = self._on("_ewin")
         stream = torch.cuda.current_stream(self.device)
         ew["host_cursor"].copy_(ew["cursor"], non_blocking=True)
         stream.synchronize()
@@ -1237,16 +1273,11 @@ class BatchedPlantEnv:
     def clear_event_windows(self, mask=None) -> None:
         """the masked plants (None = all) unprimed, their rings empty, an armed capture dropped without a record
         (npb_event_windows_clear): what a caller without autoreset does for the plants it restarted"""
-        if getattr(self, "_ewin", None) is None:
-            raise _lib.NpbError("no event windows: enable_event_windows() first")
-        m = None if mask is None else self._col(mask, torch.uint8)
-        _lib.check(self.L.npb_event_windows_clear(self._h, None if m is None else self._p(m), self._stream()), self._h)
+        self._clear("_ewin", self.L.npb_event_windows_clear, mask)
 
     def _task_readers(self):
-        """what reads the task's output columns: (name, settings) of the column statistics, the event windows and the features that do"""
-        return [(what, user) for what, user in (("column statistics", getattr(self, "_cstats", None)), ("event windows", getattr(self, "_ewin", None)),
-                                                ("features", getattr(self, "_feat", None)))
-                if user is not None and user.get("task")]
+        """what reads the task's output columns, as a refusal names them"""
+        return self._readers_of(("task_reward", "task_cause"), among=("_cstats", "_ewin", "_feat"))
 
     def set_task(self, reward=(), terminate=(), bias: float = 0.0, keep_terms: bool = False) -> None:
         """Define the reward and the termination rule on the device (npb_set_task): behind every step one more launch forms a per-plant
@@ -1269,22 +1300,21 @@ class BatchedPlantEnv:
         ``info["scram_activated"]`` stays the step's column.  ``episode_records()`` gains ``cause``.  ``nuclear_sim_amd.task.evaluate``
         is the same in numpy, bit for bit.  ``set_task(None)`` turns it off; while column statistics or event windows read
         ``"task_reward"`` / ``("task", mask)`` that, and a new task, are refused: turn them off first."""
-        old = getattr(self, "_task", None)
         if reward is None and not terminate:
-            if old is None:
+            if self._task is None:
                 return
-            for what, _user in self._task_readers():
-                raise _lib.NpbError("set_task(None): the %s read 'task_reward' / ('task', mask): turn them off first" % what)
+            for what in self._task_readers():
+                raise _lib.NpbError("set_task(None): %s read 'task_reward' / ('task', mask): turn them off first" % what)
             self._drop_record_task_cause()
             _lib.check(self.L.npb_set_task(self._h, None), self._h)
             self._task = None
             return
-        ms = getattr(self, "_msum", None)
+        ms = self._msum
         req = _lib.task_request(reward, terminate, bias, INFO_COLUMNS, 0 if ms is None else len(ms["keys"]), self._n_controls())      # a bad word is refused here
         if not hasattr(self.L, "npb_set_task"):
             raise _lib.NpbError("libnpb.so has no npb_set_task: rebuild")
-        for what, _user in self._task_readers():      # (they hold the old task's output columns)
-            raise _lib.NpbError("set_task: the %s read 'task_reward' / ('task', mask) of the task that is set: turn them off first" % what)
+        for what in self._task_readers():      # (they hold the old task's output columns)
+            raise _lib.NpbError("set_task: %s read 'task_reward' / ('task', mask) of the task that is set: turn them off first" % what)
         buffers = self._side_buffers()
         nt, nr = len(req["terms"]), len(req["rules"])
         terms, rules = (_lib.NpbTaskTerm * max(nt, 1))(), (_lib.NpbTaskRule * max(nr, 1))()
@@ -1316,64 +1346,39 @@ class BatchedPlantEnv:
         except _lib.NpbError:
             self._record_task_cause()      # (what was set before stays, its cause column in the records too)
             raise
-        self._task = dict(out, request=req, n_delta=sum(T["kind"] == "delta" for T in req["terms"]),
-                          summary=ms["counts"] if any(C["side"] and C["side"][0] in ("n_created", "n_completed") for C in req["columns"]) else None)
+        nd = sum(T["kind"] == "delta" for T in req["terms"])
+        self._task = dict(out, **self._reading(req, buffers), request=req,
+                          state=(("prev", np.float64, (nd, self.n)), ("primed", np.int32, (self.n,)), ("seen", np.int32, (self.n,))))
         self._record_task_cause()
 
     def task_spec(self) -> dict:
         """the task as ``nuclear_sim_amd.task.evaluate`` takes it -- {"bias", "terms", "rules"} over the rows of ``task_samples()``"""
-        if getattr(self, "_task", None) is None:
-            raise _lib.NpbError("no task: set_task() first")
-        req = self._task["request"]
+        req = self._on("_task")["request"]
         return {"bias": req["bias"], "terms": req["terms"], "rules": req["rules"]}
 
     def task_samples(self) -> torch.Tensor:
         """The columns the task reads as they are NOW, widened to float64, [n_cols, n] on the device (gather launches and copies: for
         checks and debugging, not for the hot path).  Behind a ``step()`` without autoreset these are the samples the task was formed
         from; a plant the autoreset restarted shows its start state."""
-        if getattr(self, "_task", None) is None:
-            raise _lib.NpbError("no task: set_task() first")
-        buffers = self._side_buffers()
-        rows = []
-        for C in self._task["request"]["columns"]:
-            if C["member"] is not None:
-                rows.append(self._get_slot("f64" if C["member"][0] == 0 else "i32", C["member"][1]).to(torch.float64))
-            else:
-                name, offset, stride, _kind = C["side"]
-                rows.append(buffers[name].reshape(-1)[self._side_first(name, offset)::stride][:self.n].to(torch.float64))
-        return torch.stack(rows)
+        return self._column_samples(self._on("_task")["request"]["columns"])
 
     def clear_task(self, mask=None) -> None:
         """the masked plants (None = all) unprimed: their next ``"delta"`` samples are 0 (npb_task_clear) -- what a caller without
         autoreset does for the plants it restarted"""
-        if getattr(self, "_task", None) is None:
-            raise _lib.NpbError("no task: set_task() first")
-        m = None if mask is None else self._col(mask, torch.uint8)
-        _lib.check(self.L.npb_task_clear(self._h, None if m is None else self._p(m), self._stream()), self._h)
+        self._clear("_task", self.L.npb_task_clear, mask)
 
     def task_state(self) -> Dict[str, np.ndarray]:
         """The task's own state for a checkpoint (npb_task_get_state), beside ``state_arrays()``: ``prev`` float64 [n_delta, n] (the
         previous samples of the ``"delta"`` terms, in term order), ``primed`` and ``seen`` int32 [n] (the plant has a previous sample;
         the episode index last seen)."""
-        if getattr(self, "_task", None) is None:
-            raise _lib.NpbError("no task: set_task() first")
-        nd = self._task["n_delta"]
-        out = {"prev": np.zeros((nd, self.n)), "primed": np.zeros(self.n, dtype=np.int32), "seen": np.zeros(self.n, dtype=np.int32)}
-        _lib.check(self.L.npb_task_get_state(self._h, out["prev"].ctypes.data if nd else None, out["primed"].ctypes.data, out["seen"].ctypes.data,
-                                             self._stream()), self._h)
-        return out
+        return self._get_state("_task", self.L.npb_task_get_state)
 
     def load_task_state(self, state) -> None:
         """put back what ``task_state()`` returned (npb_task_set_state): the task must be the one it was taken under"""
-        if getattr(self, "_task", None) is None:
-            raise _lib.NpbError("no task: set_task() first")
-        nd = self._task["n_delta"]
-        prev = np.ascontiguousarray(state["prev"], dtype=np.float64)
-        if prev.shape != (nd, self.n):
-            raise ValueError("task state: prev must be [%d, %d] (the task's 'delta' terms x plants), not %r" % (nd, self.n, prev.shape))
-        primed = np.ascontiguousarray(np.asarray(state["primed"], dtype=np.int32).reshape(self.n))
-        seen = np.ascontiguousarray(np.asarray(state["seen"], dtype=np.int32).reshape(self.n))
-        _lib.check(self.L.npb_task_set_state(self._h, prev.ctypes.data if nd else None, primed.ctypes.data, seen.ctypes.data, self._stream()), self._h)
+        want, got = self._on("_task")["state"][0][2], np.shape(state["prev"])
+        if got != want:
+            raise ValueError("task state: prev must be [%d, %d] (the task's 'delta' terms x plants), not %r" % (want + (got,)))
+        self._load_state("_task", self.L.npb_task_set_state, state)
 
     def set_features(self, columns, stack: int = 1, dtype=torch.float32, final: Optional[bool] = None, as_observation: bool = False) -> None:
         """Define what the policy reads, on the device (npb_set_features): behind every step one more launch -- two with autoreset --
@@ -1394,12 +1399,12 @@ class BatchedPlantEnv:
         with autoreset, ``info["final_features"]``; with ``as_observation`` it returns the features in place of the observation (which
         stays in ``info["observation"]``).  ``set_features(None)`` turns it off."""
         if columns is None:
-            if getattr(self, "_feat", None) is not None:
+            if self._feat is not None:
                 _lib.check(self.L.npb_set_features(self._h, None), self._h)
             self._feat = None
             return
-        ms, tk = getattr(self, "_msum", None), getattr(self, "_task", None)
-        req = _lib.features_request(columns, stack, dtype, INFO_COLUMNS, tk is not None, 0 if ms is None else len(ms["keys"]), self._n_controls())      # a bad word is refused here
+        ms = self._msum
+        req = _lib.features_request(columns, stack, dtype, INFO_COLUMNS, self._task is not None, 0 if ms is None else len(ms["keys"]), self._n_controls())      # a bad word is refused here
         if not hasattr(self.L, "npb_set_features"):
             raise _lib.NpbError("libnpb.so has no npb_set_features: rebuild")
         spec, rows, buffers = req["spec"], req["columns"], self._side_buffers()
@@ -1424,20 +1429,14 @@ class BatchedPlantEnv:
         d.n_columns, d.columns, d.stack, d.out_type = C, cols, spec["stack"], _lib.FEATURE_DTYPES[spec["dtype"]]
         d.out, d.final = out.data_ptr(), None if fin is None else fin.data_ptr()
         _lib.check(self.L.npb_set_features(self._h, ctypes.byref(d)), self._h)      # (refused: what was set before stays)
-        self._feat = {"out": out, "final": fin, "request": req, "as_observation": bool(as_observation), "unprimed": True,
-                      "summary": ms["counts"] if any(R["side"] and R["side"][0] in ("n_created", "n_completed") for R in rows) else None,
-                      "task": tk if any(R["side"] and R["side"][0] == "task_reward" for R in rows) else None}
-
-    def _features_on(self) -> dict:
-        if getattr(self, "_feat", None) is None:
-            raise _lib.NpbError("no features: set_features() first")
-        return self._feat
+        self._feat = dict(self._reading(req, buffers), out=out, final=fin, request=req, as_observation=bool(as_observation), unprimed=True,
+                          state=(("primed", np.int32, (self.n,)), ("seen", np.int32, (self.n,))))
 
     def features(self) -> torch.Tensor:
         """The ``[n, stack, n_columns]`` tensor, the same storage on every call and current after every ``step``.  Plants without a frame
         yet -- before the first step, after ``clear_features`` -- first get the frame of their current state in every slot
         (npb_features_prime)."""
-        ft = self._features_on()
+        ft = self._on("_feat")
         if ft["unprimed"]:
             self.get_observation()      # (a fresh frame reads the observation live)
             _lib.check(self.L.npb_features_prime(self._h, self._stream()), self._h)
@@ -1447,38 +1446,33 @@ class BatchedPlantEnv:
     def final_features(self) -> torch.Tensor:
         """``[n, stack, n_columns]``: row p is the stack, terminal frame included, of the last episode of plant p that the autoreset ended;
         the rows of the other plants stay as they were (as ``info["final_observation"]``)"""
-        ft = self._features_on()
+        ft = self._on("_feat")
         if ft["final"] is None:
             raise _lib.NpbError("no final features: set_features(..., final=True), with autoreset")
         return ft["final"]
 
     def clear_features(self, mask=None) -> None:
         """the masked plants (None = all) unprimed: their next frame fills every slot of their stack (npb_features_clear)"""
-        ft = self._features_on()
-        m = None if mask is None else self._col(mask, torch.uint8)
-        _lib.check(self.L.npb_features_clear(self._h, None if m is None else self._p(m), self._stream()), self._h)
-        ft["unprimed"] = True
+        self._clear("_feat", self.L.npb_features_clear, mask)["unprimed"] = True
 
-    def _refill_features(self, mask) -> None:
-        """behind ``reset`` / ``restore`` / ``restore_from_bank``: the plants they reset show the frame of their new state"""
-        if getattr(self, "_feat", None) is not None:
+    def _after_restart(self, mask) -> None:
+        """behind ``reset`` / ``restore`` / ``restore_from_bank``, THE place where an attachment follows a restart the caller made: the
+        plants they reset show the features' frame of their new state, and start a new hold of the controls"""
+        if self._feat is not None:
             self.clear_features(mask)
             self.features()
+        if self._ctl is not None:
+            self.clear_controls(mask)
 
     def features_state(self) -> Dict[str, np.ndarray]:
         """The features' own state for a checkpoint (npb_features_get_state), beside ``state_arrays()`` and a copy of ``features()``:
         ``primed`` and ``seen`` int32 [n] (the plant has a frame; the episode index last seen)."""
-        self._features_on()
-        out = {"primed": np.zeros(self.n, dtype=np.int32), "seen": np.zeros(self.n, dtype=np.int32)}
-        _lib.check(self.L.npb_features_get_state(self._h, out["primed"].ctypes.data, out["seen"].ctypes.data, self._stream()), self._h)
-        return out
+        return self._get_state("_feat", self.L.npb_features_get_state)
 
     def load_features_state(self, state, stack=None) -> None:
         """put back what ``features_state()`` returned (npb_features_set_state) and, with ``stack``, a saved copy of ``features()``"""
-        ft = self._features_on()
-        primed = np.ascontiguousarray(np.asarray(state["primed"], dtype=np.int32).reshape(self.n))
-        seen = np.ascontiguousarray(np.asarray(state["seen"], dtype=np.int32).reshape(self.n))
-        _lib.check(self.L.npb_features_set_state(self._h, primed.ctypes.data, seen.ctypes.data, self._stream()), self._h)
+        ft = self._on("_feat")
+        primed = self._load_state("_feat", self.L.npb_features_set_state, state)[0]
         if stack is not None:
             ft["out"].copy_(torch.as_tensor(stack).to(device=self.device, dtype=ft["out"].dtype).reshape(ft["out"].shape))
         ft["unprimed"] = not bool(primed.all())
@@ -1486,36 +1480,16 @@ class BatchedPlantEnv:
     def features_spec(self) -> dict:
         """the request as data: {"columns": what each row read is (``_lib.column_word``), "spec": what ``nuclear_sim_amd.features`` takes
         over those rows}"""
-        return self._features_on()["request"]
+        return self._on("_feat")["request"]
 
     def features_samples(self) -> torch.Tensor:
         """The rows the features read as they are NOW, widened to float64, [n_rows, n] on the device (gather launches and copies: for checks
         and debugging, not for the hot path), as ``task_samples`` gives the task's."""
-        ft = self._features_on()
-        buffers = self._side_buffers()
-        rows = []
-        for C in ft["request"]["columns"]:
-            if C["member"] is not None:
-                rows.append(self._get_slot("f64" if C["member"][0] == 0 else "i32", C["member"][1]).to(torch.float64))
-            else:
-                name, offset, stride, _kind = C["side"]
-                rows.append(buffers[name].reshape(-1)[self._side_first(name, offset)::stride][:self.n].to(torch.float64))
-        return torch.stack(rows)
+        return self._column_samples(self._on("_feat")["request"]["columns"])
 
     def _control_readers(self):
-        """what reads the controls' held / previous columns: the names of the task, features, statistics and windows that do"""
-        def reads(rows):
-            return any(R.get("side") and R["side"][0] in ("control", "control_prev") for R in rows)
-        out = []
-        tk, ft, cs, ew = (getattr(self, name, None) for name in ("_task", "_feat", "_cstats", "_ewin"))
-        if tk is not None and reads(tk["request"]["columns"]):
-            out.append("the task")
-        if ft is not None and reads(ft["request"]["columns"]):
-            out.append("the features")
-        for what, user in (("the column statistics", cs), ("the event windows", ew)):
-            if user is not None and user.get("controls"):
-                out.append(what)
-        return out
+        """what reads the controls' held / previous columns, as a refusal names them"""
+        return self._readers_of(("control", "control_prev"))
 
     def set_controls(self, axes, interval: int = 1, dtype=torch.float32) -> None:
         """Define what the policy writes, on the device (npb_set_controls): in front of every step one more launch reads every plant's
@@ -1536,12 +1510,11 @@ class BatchedPlantEnv:
         ``("control", a)`` against 0; jerk: ``sq_err`` against ``("control_prev", a)``), and ``step()`` adds ``info["controls"]``, the
         held values ``[len(axes), n]``.  ``nuclear_sim_amd.controls`` is the same in numpy, bit for bit.  ``set_controls(None)`` turns
         it off."""
-        old = getattr(self, "_ctl", None)
-        readers = self._control_readers() if old is not None else []
+        readers = self._control_readers()      # (none without controls: their columns are no words then)
         if readers:
             raise _lib.NpbError("%s read(s) the controls' columns: turn that off first" % " and ".join(readers))
         if axes is None:
-            if old is not None:
+            if self._ctl is not None:
                 _lib.check(self.L.npb_set_controls(self._h, None), self._h)
             self._ctl = None
             return
@@ -1567,48 +1540,30 @@ class BatchedPlantEnv:
         d.n_axes, d.axes, d.interval, d.in_type = A, cax, spec["interval"], _lib.CONTROL_DTYPES[spec["dtype"]]
         d.input, d.held, d.prev = tin.data_ptr(), held.data_ptr(), prev.data_ptr()
         _lib.check(self.L.npb_set_controls(self._h, ctypes.byref(d)), self._h)      # (refused: what was set before stays)
-        self._ctl = {"in": tin, "held": held, "prev": prev, "spec": spec}
-
-    def _controls_on(self) -> dict:
-        if getattr(self, "_ctl", None) is None:
-            raise _lib.NpbError("no controls: set_controls() first")
-        return self._ctl
+        self._ctl = {"in": tin, "held": held, "prev": prev, "spec": spec,
+                     "state": (("held", np.float64, (A, self.n)), ("prev", np.float64, (A, self.n)), ("age", np.int32, (self.n,)),
+                               ("primed", np.int32, (self.n,)), ("seen", np.int32, (self.n,)))}
 
     def controls_input(self) -> torch.Tensor:
         """The bound ``[n, n_axes]`` tensor the next ``step`` decodes, the same storage on every call: have the policy write into it"""
-        return self._controls_on()["in"]
+        return self._on("_ctl")["in"]
 
     def clear_controls(self, mask=None) -> None:
         """the masked plants (None = all) unprimed: their next step starts a new hold (npb_controls_clear)"""
-        self._controls_on()
-        m = None if mask is None else self._col(mask, torch.uint8)
-        _lib.check(self.L.npb_controls_clear(self._h, None if m is None else self._p(m), self._stream()), self._h)
-
-    def _restart_controls(self, mask) -> None:
-        """behind ``reset`` / ``restore`` / ``restore_from_bank``: the plants they reset start a new hold"""
-        if getattr(self, "_ctl", None) is not None:
-            self.clear_controls(mask)
+        self._clear("_ctl", self.L.npb_controls_clear, mask)
 
     def controls_state(self) -> Dict[str, np.ndarray]:
         """The controls' own state for a checkpoint (npb_controls_get_state), beside ``state_arrays()``: ``held`` and ``prev`` float64
         [n_axes, n], ``age``, ``primed`` and ``seen`` int32 [n]."""
-        A = self._controls_on()["held"].shape[0]
-        out = {"held": np.zeros((A, self.n)), "prev": np.zeros((A, self.n)), "age": np.zeros(self.n, dtype=np.int32),
-               "primed": np.zeros(self.n, dtype=np.int32), "seen": np.zeros(self.n, dtype=np.int32)}
-        _lib.check(self.L.npb_controls_get_state(self._h, *[out[name].ctypes.data for name in ("held", "prev", "age", "primed", "seen")],
-                                                 self._stream()), self._h)
-        return out
+        return self._get_state("_ctl", self.L.npb_controls_get_state)
 
     def load_controls_state(self, state) -> None:
         """put back what ``controls_state()`` returned (npb_controls_set_state)"""
-        A = self._controls_on()["held"].shape[0]
-        keep = [np.ascontiguousarray(np.asarray(state[name], dtype=np.float64).reshape(A, self.n)) for name in ("held", "prev")]
-        keep += [np.ascontiguousarray(np.asarray(state[name], dtype=np.int32).reshape(self.n)) for name in ("age", "primed", "seen")]
-        _lib.check(self.L.npb_controls_set_state(self._h, *[x.ctypes.data for x in keep], self._stream()), self._h)
+        self._load_state("_ctl", self.L.npb_controls_set_state, state)
 
     def controls_spec(self) -> dict:
         """the request as data: what ``nuclear_sim_amd.controls.Decoder`` takes"""
-        return self._controls_on()["spec"]
+        return self._on("_ctl")["spec"]
 
     def _order_buffers(self):
         """the buffers the perform_*_maintenance methods keep for their order columns, with the ``success`` column they all return"""
@@ -1786,8 +1741,7 @@ class BatchedPlantEnv:
         m = self._col(mask, torch.uint8)
         self._reset_carried_diagnostics(m)
         _lib.check(self.L.npb_restore(self._h, self._p(m), self._stream()), self._h)
-        self._refill_features(m)
-        self._restart_controls(m)
+        self._after_restart(m)
         return self.get_observation()
 
     def set_start_bank(self, bank_env: Optional["BatchedPlantEnv"], slots=None, advance: Optional[int] = None) -> None:
@@ -1824,8 +1778,7 @@ class BatchedPlantEnv:
         m = self._col(mask, torch.uint8)
         self._reset_carried_diagnostics(m)
         _lib.check(self.L.npb_restore_bank(self._h, self._p(m), self._stream()), self._h)
-        self._refill_features(m)
-        self._restart_controls(m)
+        self._after_restart(m)
         return self.get_observation()
 
     def _enable_autoreset(self, max_episode_steps: Optional[int]) -> None:
@@ -2033,8 +1986,7 @@ class BatchedPlantEnv:
                 self._noise = self._make_noise(self._noise_seeds)
             if mask is None and self._profile is not None and self._streams is None:      # and a freshly started runner a freshly drawn profile
                 self._profile = PowerProfile(self, **self._profile_args)
-        self._refill_features(m)
-        self._restart_controls(m)
+        self._after_restart(m)
         return self.get_observation()
 
     def ramp_setpoints(self, targets: torch.Tensor) -> torch.Tensor:
@@ -2071,7 +2023,7 @@ class BatchedPlantEnv:
     def step(self, action=None, magnitude=None, power_setpoint=None, cooling_water_temp=None, noise_z=None,
              thermal_power_mw=None, power_percent=None, controls=None):
         self._keep = []
-        ctl = getattr(self, "_ctl", None)
+        ctl = self._ctl
         if controls is not None:      # the policy's output for this step (set_controls): into the bound tensor unless it is that tensor
             if ctl is None:
                 raise _lib.NpbError("step(controls=...) without controls: set_controls() first")
@@ -2112,7 +2064,7 @@ class BatchedPlantEnv:
             info["reactivity_components"] = {name: self._rho[:, j] for j, name in enumerate(_lib.REACTIVITY_COMPONENTS)}
         info["trip_flags"] = self._flags
         info["scram_activated"] = self._done
-        task = getattr(self, "_task", None)
+        task = self._task
         if task is not None:      # the caller's reward and termination rule, formed behind the step (set_task)
             info["reference_reward"] = self._reward
             info["task_cause"] = task["cause"]
@@ -2130,7 +2082,7 @@ class BatchedPlantEnv:
         if ctl is not None:      # the action every plant is under after this step's decode: [n_axes, n] (set_controls)
             info["controls"] = ctl["held"]
         obs = self._obs
-        feat = getattr(self, "_feat", None)
+        feat = self._feat
         if feat is not None:      # the caller's policy inputs, kept behind the step (set_features)
             feat["unprimed"] = False
             info["features"] = feat["out"]

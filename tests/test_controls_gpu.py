@@ -518,3 +518,57 @@ def test_off_is_off():
         assert "controls" not in ra[3]
         _compare_envs(env, ra, plain, rb, t)
     env.close(); plain.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 9
+def test_the_shared_unprime_and_state_copy_of_task_features_and_controls():
+    """The task, the features and the controls share one unprime kernel (blocks of 256) and one state copy over a parts list each.  On one
+    env of 300 plants -- a full clear block and a partial one, four full waves and 44 lanes -- with all three set, ``clear_*`` under the mask
+    ``plant % 3 == 0`` zeroes ``primed`` of exactly the masked plants in exactly that attachment and touches nothing else of its state, and
+    a saved state put back over a later one reads back bit for bit; the same for a task without ``"delta"`` terms, whose ``prev`` is
+    [0, n].  Integers and bits only: no tolerance."""
+    from nuclear_sim_amd.env import BatchedPlantEnv
+    n = 300
+    mask = np.arange(n) % 3 == 0
+    env = BatchedPlantEnv(n, dt=DT)
+    env.set_controls([(None, "value")])
+    env.set_features(["prim.fuel_temperature"], stack=2)
+    parts = {"task": ("prev", "primed", "seen"), "features": ("primed", "seen"), "controls": ("held", "prev", "age", "primed", "seen")}
+    states = {"task": env.task_state, "features": env.features_state, "controls": env.controls_state}
+    loads = {"task": env.load_task_state, "features": env.load_features_state, "controls": env.load_controls_state}
+    clears = {"task": env.clear_task, "features": env.clear_features, "controls": env.clear_controls}
+
+    def step(t):
+        env.step(power_setpoint=_setpoint(t, n), controls=torch.as_tensor(0.25 * t + 0.01 * np.arange(n)[:, None]))
+
+    def same(got, want, where):
+        assert sorted(got) == sorted(want), where
+        for name in want:
+            assert got[name].dtype == want[name].dtype and got[name].shape == want[name].shape, (where, name, got[name].dtype, got[name].shape)
+            assert got[name].tobytes() == want[name].tobytes(), (where, name)
+
+    t = 0
+    for reward, n_delta in (([("prim.fuel_temperature", 1.0, "delta")], 1), ([("prim.fuel_temperature", 1.0)], 0)):
+        env.set_task(reward=reward)
+        step(t); step(t + 1)
+        t += 2
+        whose = ("task", "features", "controls") if n_delta else ("task",)
+        last = {name: states[name]() for name in states}
+        assert last["task"]["prev"].shape == (n_delta, n) and last["controls"]["held"].shape == (1, n)
+        for who in whose:
+            assert sorted(last[who]) == sorted(parts[who]) and (last[who]["primed"] == 1).all(), who
+            clears[who](mask)
+            now = {name: states[name]() for name in states}
+            assert np.array_equal(now[who]["primed"], np.where(mask, 0, 1).astype(np.int32)), (who, n_delta)
+            for other in states:      # nothing else of its own state has moved, and nothing at all of the other two's
+                same({k: v for k, v in now[other].items() if (other, k) != (who, "primed")},
+                     {k: v for k, v in last[other].items() if (other, k) != (who, "primed")}, (who, "clear", other))
+            last = now
+        step(t)      # the state moves on: every plant primed again, the controls' held, prev and age other values
+        t += 1
+        for who in whose:
+            moved = states[who]()
+            assert (moved["primed"] == 1).all() and (who != "controls" or moved["held"].tobytes() != last[who]["held"].tobytes()), who
+            loads[who](last[who])
+            same(states[who](), last[who], (who, "round trip"))
+    env.close()
