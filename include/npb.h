@@ -1118,6 +1118,103 @@ NPB_API int npb_controls_get_state(NpbHandle *h, double *held, double *prev, int
 NPB_API int npb_controls_set_state(NpbHandle *h, const double *held, const double *prev, const int32_t *age, const int32_t *primed,
                                    const int32_t *seen, void *stream);
 
+/* The rollout: the learner's half of the loop, written down on the device -- what the policy saw (the features), what it did (the
+ * controls' input and up to NPB_ROLLOUT_EXTRAS_MAX floats of its own per plant: value, log-probability, ...), what came of it (reward, how
+ * the episode went on) for a horizon of T steps, and from that the GAE advantages and returns in one launch.  The rollout needs features
+ * to be set; controls are optional.  Opt-in: a handle that never sets a rollout behaves as before in every entry point.
+ * npb_set_rollout(h, desc) binds caller-owned device buffers, contiguous and time-major, slot t first, for 1 <= T <= NPB_ROLLOUT_HORIZON_MAX:
+ *   obs        [T][n][K][C]   the features' out type   the features tensor as the policy saw it in front of step t
+ *   act        [T][n][A]      the controls' in type    the bound controls input as the policy wrote it; NULL (and A = 0) without controls
+ *   extra      [T][n][E]      float                    a copy of extras_in, a bound [n][E] input the caller writes before each step, E = 0 ..
+ *                                                      NPB_ROLLOUT_EXTRAS_MAX (E = 0: both NULL)
+ *   reward     [T][n]         double                   the reward the episode kernel sums: the task's while a task is set, else the step's
+ *   ended      [T][n]         uint8                    bit 0 (NPB_ROLLOUT_TERMINATED), bit 1 (NPB_ROLLOUT_TRUNCATED), bit 2 (NPB_ROLLOUT_CUT)
+ *   episode    [T][n]         int32                    the carried index of the episode the transition belonged to; -1 without autoreset
+ *   final_row  [T][n]         int32                    a row of final_obs, or -1
+ *   final_obs  [n * R][K][C]  the features' out type   the terminal stack of each truncated transition; NULL with R = 0
+ * The handle keeps a host cursor t, the number of slots recorded (npb_rollout_steps), and a device int32 n_final[n], the rows of final_obs
+ * each plant has taken.  npb_rollout_begin(h, stream): t = 0, n_final zeroed, final_row filled with -1.  npb_set_rollout begins too.
+ * With a rollout set npb_step launches two kernels more (npd_rollout.h); neither touches the arena:
+ *   pre, in front of the controls kernel: three contiguous copies into slot t in one launch, the features' out -> obs[t], the controls' in
+ *     -> act[t], extras_in -> extra[t]; 16 bytes per lane where source and slot are 16-byte aligned.
+ *   post, behind features pass A and in front of the episode-records and episode kernels, one lane per plant: there the features' out[p]
+ *     IS the stack with the terminal frame appended, and the carried length is still the old one.  The outcome is decided as the episode
+ *     kernel decides it behind this kernel on the same columns: terminated = done[p] != 0; truncated = max_episode_steps > 0 && len[p] + 1
+ *     >= max_episode_steps && !terminated (termination wins); without autoreset only bit 0 can be set.  reward[t][p], ended[t][p] and
+ *     episode[t][p] are written.  A truncated plant takes row p * R + n_final[p] of final_obs, n_final[p] += 1, final_row[t][p] = that row,
+ *     and the wave copies the plant's K * C cells of out[p] to the row, all lanes on one row, 16 bytes per lane where K * C allows.
+ *     No atomics: the row assignment is deterministic.  The terminal stacks of TERMINATED transitions are not stored: their bootstrap is 0.
+ *   The host then bumps t.  npb_step at t == T is refused (NPB_EINVAL, before any launch; the rollout does not wrap silently:
+ *   npb_rollout_begin rewinds it), and so is a NULL reward or done column while a rollout is set.
+ * R is derived, not tuned: truncations of one plant are at least max_episode_steps steps apart and the first can fall on slot 0, so R >=
+ * ceil(T / max_episode_steps) suffices; npb_step refuses (NPB_EINVAL) a smaller R while the autoreset has max_episode_steps > 0; R = 0
+ * with final_obs NULL is valid when no truncation can happen.  (A plant that still runs out of rows -- the limit was lowered while the
+ * rollout was recording -- takes none: final_row stays -1 and its bootstrap is 0.  npb_rollout_begin after such a change.)
+ * npb_rollout_cut(h, mask, stream): a restart the caller makes between two recorded steps (npb_reset, npb_restore, npb_restore_bank).  With
+ * t > 0 the plants of mask (device uint8 [n_plants], NULL = all) get bit 2 set in ended[t - 1]; with t == 0 nothing happens.
+ * npb_rollout_advantages(h, desc, stream): one launch over the slots [0, t), one lane per plant, backwards over the slots, every access
+ * consecutive along n.  In double, every operation rounded on its own (the library is built with -ffp-contract=off):
+ *   gl    = gamma * lam                                   (once, on the host)
+ *   v     = value ? (double)value[t][p] : 0.0
+ *   nv    = (ended & 5) ? 0.0                             terminated or cut: no bootstrap
+ *         : (ended & 2) ? (final_row[t][p] >= 0 ? (double)final_value[final_row[t][p]] : 0.0)      truncated: the value of the TERMINAL state
+ *         : t == t_end - 1 ? (last_value ? (double)last_value[p] : 0.0)
+ *         : value ? (double)value[t + 1][p] : 0.0
+ *   delta = (reward[t][p] + gamma * nv) - v
+ *   carry = (ended & 7) ? 0.0 : A[t + 1][p]               (0.0 behind the last slot)
+ *   A     = delta + gl * carry
+ *   ret   = A + v
+ * carry is a select, not a product with 1 - done: a NaN in one episode never reaches the episode in front of it.  value is float, given as
+ * base + time stride + plant stride in elements, so a column of `extra` serves in place; last_value is float [n], final_value float [n * R]:
+ * the caller's value of final_obs.  adv and ret are [T][n], float (NPB_ROLLOUT_F32) or double (NPB_ROLLOUT_F64); either may be NULL; the
+ * narrowing rounds to nearest even, as the features' does.  With lam = 1 and no values ret is the discounted return-to-go.
+ * nuclear_sim_amd/rollout.py states all of it in numpy, and that statement is the contract: the recurrence is not restated as a scan.
+ * NPB_EINVAL: no rollout set; t == 0; final_value NULL while R > 0; gamma or lam a NaN or outside [0, 1]; adv and ret both NULL; an
+ * unknown out type.
+ * npb_set_rollout(h, NULL) turns the rollout off; npb_destroy drops it.  While a rollout is set npb_set_features and npb_set_controls are
+ * refused, set and NULL alike, naming the rollout: they would free or reshape what the pre kernel copies.  NPB_EINVAL with the reason in
+ * npb_last_error, before any device work: no features set, and what npb_rollout_check refuses -- that check alone, without a handle
+ * (features_cells = K * C, n_axes = the controls' axis count or 0), NULL = accepted, else the reason: n_plants < 1 or features_cells < 1;
+ * T or E out of range; an act buffer without axes, or axes without an act buffer; R < 0, or n_plants * R beyond int32; final_obs NULL with R > 0; a NULL obs, reward,
+ * ended, episode or final_row; E > 0 without extras_in or extra; a misaligned buffer (16 bytes for obs, act, extras_in, extra and
+ * final_obs, 8 for reward, 4 for episode and final_row).
+ * No step, restore, episode, task, features or controls kernel changes.  Not here: advantage normalisation (a reduction order would have
+ * to be pinned), minibatch shuffling, a checkpoint of a half-filled rollout, half types, V-trace or other off-policy corrections,
+ * rollouts without features.
+ * NPB_VERSION stays 154: a binding detects the entry points by name. */
+#define NPB_ROLLOUT_HORIZON_MAX 4096
+#define NPB_ROLLOUT_EXTRAS_MAX 8
+enum { NPB_ROLLOUT_TERMINATED = 1, NPB_ROLLOUT_TRUNCATED = 2, NPB_ROLLOUT_CUT = 4 };
+enum { NPB_ROLLOUT_F32 = 0, NPB_ROLLOUT_F64 = 1 };
+typedef struct npb_rollout_desc_t {
+  int horizon;                   /* T */
+  int n_extras;                  /* E */
+  int final_rows;                /* R */
+  const float *extras_in;        /* device [n_plants][E], or NULL with E = 0 */
+  void *obs;                     /* device [T][n_plants][K][C] */
+  void *act;                     /* device [T][n_plants][A], or NULL without controls */
+  float *extra;                  /* device [T][n_plants][E], or NULL with E = 0 */
+  double *reward;                /* device [T][n_plants] */
+  uint8_t *ended;                /* device [T][n_plants] */
+  int32_t *episode, *final_row;  /* device [T][n_plants] each */
+  void *final_obs;               /* device [n_plants * R][K][C], or NULL with R = 0 */
+} npb_rollout_desc_t;
+typedef struct npb_rollout_advantages_desc_t {
+  double gamma, lam;
+  const float *value;            /* device, or NULL: value[t][p] = value[t * value_time_stride + p * value_plant_stride] */
+  int64_t value_time_stride, value_plant_stride;      /* in elements */
+  const float *last_value;       /* device [n_plants], or NULL */
+  const float *final_value;      /* device [n_plants * R]; NULL only with R = 0 */
+  int out_type;                  /* NPB_ROLLOUT_F32 | NPB_ROLLOUT_F64 */
+  void *adv, *ret;               /* device [T][n_plants] each; one of them may be NULL */
+} npb_rollout_advantages_desc_t;
+NPB_API int npb_set_rollout(NpbHandle *h, const npb_rollout_desc_t *desc);
+NPB_API const char *npb_rollout_check(const npb_rollout_desc_t *desc, int n_plants, int features_cells, int n_axes);
+NPB_API int npb_rollout_begin(NpbHandle *h, void *stream);
+NPB_API int npb_rollout_steps(const NpbHandle *h);      /* t, or -1 without a rollout */
+NPB_API int npb_rollout_cut(NpbHandle *h, const uint8_t *mask, void *stream);
+NPB_API int npb_rollout_advantages(NpbHandle *h, const npb_rollout_advantages_desc_t *desc, void *stream);
+
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the
  * rocprofv3 FETCH_SIZE / WRITE_SIZE counters (tools/profile_traffic.py). */

@@ -881,6 +881,27 @@ class NpbControlsDesc(ctypes.Structure):
                 ("input", ctypes.c_void_p), ("held", ctypes.c_void_p), ("prev", ctypes.c_void_p)]
 
 
+# include/npb.h npb_rollout_desc_t: what the policy saw, did and got for a horizon of steps, recorded on the device (npb_set_rollout)
+ROLLOUT_HORIZON_MAX, ROLLOUT_EXTRAS_MAX = 4096, 8
+ROLLOUT_BITS = {"terminated": 1, "truncated": 2, "cut": 4}             # NPB_ROLLOUT_TERMINATED / _TRUNCATED / _CUT (rollout.TERMINATED ...)
+ROLLOUT_DTYPES = {"float32": 0, "float64": 1}                          # NPB_ROLLOUT_F32 / NPB_ROLLOUT_F64
+
+
+class NpbRolloutDesc(ctypes.Structure):
+    """npb_rollout_desc_t: the horizon, the extras count, the rows of final_obs per plant and the caller's device buffers"""
+    _fields_ = [("horizon", ctypes.c_int), ("n_extras", ctypes.c_int), ("final_rows", ctypes.c_int), ("extras_in", ctypes.c_void_p),
+                ("obs", ctypes.c_void_p), ("act", ctypes.c_void_p), ("extra", ctypes.c_void_p), ("reward", ctypes.c_void_p),
+                ("ended", ctypes.c_void_p), ("episode", ctypes.c_void_p), ("final_row", ctypes.c_void_p), ("final_obs", ctypes.c_void_p)]
+
+
+class NpbRolloutAdvantagesDesc(ctypes.Structure):
+    """npb_rollout_advantages_desc_t: gamma, lambda, the value column (base and strides in elements), the last and final values, the
+    output type and the two outputs"""
+    _fields_ = [("gamma", ctypes.c_double), ("lam", ctypes.c_double), ("value", ctypes.c_void_p), ("value_time_stride", ctypes.c_int64),
+                ("value_plant_stride", ctypes.c_int64), ("last_value", ctypes.c_void_p), ("final_value", ctypes.c_void_p),
+                ("out_type", ctypes.c_int), ("adv", ctypes.c_void_p), ("ret", ctypes.c_void_p)]
+
+
 def controls_request(axes, interval: int = 1, dtype="float32", heat_source: int = 0) -> dict:
     """What ``BatchedPlantEnv.set_controls`` asks of npb_set_controls, from the caller's words; a pure function, host only, so an axis that
     cannot work is refused (ValueError, naming it) before any device work.
@@ -1167,6 +1188,14 @@ def load():
         L.npb_controls_clear.argtypes = [vp, vp, vp]
         L.npb_controls_get_state.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.npb_controls_set_state.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "npb_set_rollout"):     # the rollout: trajectories recorded on the device, and their GAE advantages
+        L.npb_set_rollout.argtypes = [vp, ctypes.POINTER(NpbRolloutDesc)]
+        L.npb_rollout_check.argtypes = [ctypes.POINTER(NpbRolloutDesc), ci, ci, ci]
+        L.npb_rollout_check.restype = ctypes.c_char_p
+        L.npb_rollout_begin.argtypes = [vp, vp]
+        L.npb_rollout_steps.argtypes = [vp]
+        L.npb_rollout_cut.argtypes = [vp, vp, vp]
+        L.npb_rollout_advantages.argtypes = [vp, ctypes.POINTER(NpbRolloutAdvantagesDesc), vp]
     if hasattr(L, "npb_set_event_windows"):     # state windows around events, captured behind every step
         L.npb_set_event_windows.argtypes = [vp, ctypes.POINTER(NpbEventWindowsDesc)]
         L.npb_event_windows_check.argtypes = [ctypes.POINTER(NpbEventWindowsDesc), ci, ci]

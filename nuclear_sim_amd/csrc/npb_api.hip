@@ -88,6 +88,9 @@ struct NpbHandle {
   /* npb_set_controls: the axes, the caller's tensors and the handle's bookkeeping and input columns (base ctl.age); ctl_axis[input]: the
    * axis that fills that input column, -1 = none */
   npb_controls_t ctl; int ctl_axis[NPB_CONTROL_INPUT_COUNT];
+  /* npb_set_rollout: the caller's time-major buffers, the shapes they were bound with, the rows of final_obs every plant has taken (base
+   * ro.n_final) and the cursor */
+  npb_rollout_t ro;
   double *ramp_prev;   /* npb_profile_ramp: the previous setpoint of every plant ([pitch], NaN = none yet), allocated on first use */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
   std::vector<int> plan_key;
@@ -119,7 +122,7 @@ struct DeviceGuard {
 #define NPB_HIP(h, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(h, NPB_EHIP, #call, e__); } while (0)
 static int fail_who(NpbHandle *h, const char *who, const char *what) { return fail(h, NPB_EINVAL, (std::string(who) + what).c_str()); }
 
-/* ---- the lifecycle the per-step attachments share (column statistics, event windows, task, features, controls).  Each keeps its tables
+/* ---- the lifecycle the per-step attachments share (column statistics, event windows, task, features, controls, rollout).  Each keeps its tables
  * and per-plant bookkeeping in one device allocation, whose base is the struct's "is it on" pointer.  npb_set_* = attachment_alloc, fill
  * the struct from the base, attachment_drop the old one, assign; off and npb_destroy = attachment_drop; npb_*_clear = attachment_clear;
  * npb_*_get_state / npb_*_set_state = that attachment's StateParts through state_copy */
@@ -152,6 +155,9 @@ static const char *const g_no_column_stats = ": no column statistics set (npb_se
 static const char *const g_no_task = ": no task set (npb_set_task first)";
 static const char *const g_no_features = ": no features set (npb_set_features first)";
 static const char *const g_no_controls = ": no controls set (npb_set_controls first)";
+static const char *const g_no_rollout = ": no rollout set (npb_set_rollout first)";
+/* npb_set_features / npb_set_controls while a rollout is set, set and NULL alike: its pre kernel copies their tensors, in the shapes it was bound with */
+static const char *const g_rollout_holds = ": a rollout is set (npb_set_rollout) and records this tensor every step; npb_set_rollout(h, NULL) first";
 /* the body of an npb_*_clear: refused with `off` unless the attachment is on, then its launch on the handle's device */
 template <class Launch> static int attachment_clear(NpbHandle *h, const char *who, const void *on, const char *off, Launch launch) {
   if (!on) return fail_who(h, who, off);
@@ -584,7 +590,7 @@ int npb_destroy(NpbHandle *h) {
   if (h->es_mem) (void)hipFree(h->es_mem);
   if (h->ers_dev) (void)hipFree(h->ers_dev);
   attachment_drop(&h->cs, h->cs.cols); attachment_drop(&h->ew, h->ew.cols); attachment_drop(&h->task, h->task.terms);
-  attachment_drop(&h->feat, h->feat.cols); attachment_drop(&h->ctl, h->ctl.age);
+  attachment_drop(&h->feat, h->feat.cols); attachment_drop(&h->ctl, h->ctl.age); attachment_drop(&h->ro, h->ro.n_final);
   for (Sampler *sm : h->samplers) if (sm) { (void)hipFree(sm->dev); delete sm; }
   delete h;
   return NPB_OK;
@@ -1125,6 +1131,15 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
         return fail(h, NPB_EINVAL, what);
       }
   }
+  if (h->ro.n_final) {      /* the rollout: a slot to record into, the columns it records, and rows for every truncation the horizon can hold */
+    if (h->ro.t >= h->ro.D.horizon)
+      return fail(h, NPB_EINVAL, "npb_step: the rollout is full (npb_set_rollout: t == horizon): npb_rollout_begin rewinds it");
+    if (!h->task.terms && (!reward || !done))      /* (a task brings its own) */
+      return fail(h, NPB_EINVAL, "npb_step: a rollout is set (npb_set_rollout) and records the reward and done columns: they must not be NULL");
+    if (h->autoreset && h->max_episode_steps > 0 &&
+        h->ro.D.final_rows < (h->ro.D.horizon + h->max_episode_steps - 1) / h->max_episode_steps)
+      return fail(h, NPB_EINVAL, "npb_step: the rollout's final_rows is below ceil(horizon / max_episode_steps): a truncated plant would find no row for its terminal stack (npb_set_rollout)");
+  }
   /* what the autoreset's restores take along beside the arena, from the bank while it has slots, else from the snapshot.  The step
    * reports a source without the diagnostics rows first, then the component maintenance's own needs, then a source without its state */
   const bool from_bank = h->bank && h->next_slot;
@@ -1155,6 +1170,8 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
     es_take = npb_episode_streams_take_t{noise_z, power_setpoint, target, take_noise ? h->es_noise_out : nullptr, take_prof ? h->es_setpoint_out : nullptr,
                                          take_prof ? h->es_target_out : nullptr};
   }
+  if (h->ro.n_final)      /* the rollout's slot t: what the policy saw and what it wrote, before the controls kernel and the step change either */
+    npb_launch_rollout_pre(&h->ro, h->feat.out, h->ctl.age ? h->ctl.in : nullptr, h->n_plants, (hipStream_t)stream);
   if (h->ctl.age) {      /* the caller's policy outputs: the actuators moved, the input columns filled, in front of the step */
     h->K->controls(h->f64, NPB_N(h), &h->ctl, &h->params, h->n_plants, h->ep_index, (hipStream_t)stream);
     if (h->ctl_axis[NPB_CONTROL_INPUT_POWER_SETPOINT] >= 0) power_setpoint = h->ctl.column[NPB_CONTROL_INPUT_POWER_SETPOINT];
@@ -1205,6 +1222,11 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
                         h->max_episode_steps, (hipStream_t)stream);
   if (h->feat.cols)      /* pass A: this step's frame into every plant's stack, while everything still describes the episode it belongs to */
     h->K->features(h->f64, NPB_N(h), &h->feat, h->n_plants, 0, h->ep_index, (hipStream_t)stream);
+  if (h->ro.n_final) {      /* the rollout's slot t: reward, outcome and the truncated plants' stacks, terminal frame included, while the carried length is the old one */
+    npb_launch_rollout_post(&h->ro, h->feat.out, reward, done, h->autoreset ? h->ep_len : nullptr, h->autoreset ? h->ep_index : nullptr,
+                            h->max_episode_steps, h->n_plants, (hipStream_t)stream);
+    h->ro.t++;
+  }
   if (h->er_on && h->autoreset)      /* the episodes that end on this step, recorded while everything still describes them; then their summary rows cleared */
     h->K->episode_records(h->n_plants, NPB_N(h), h->f64, done, reward, obs, trip_flags, counters_of(h), h->ep_start,
                           h->max_episode_steps, h->er_step++, &h->er, er_uses_summary(h) ? &h->summary : nullptr,
@@ -1979,6 +2001,7 @@ const char *npb_features_check(const npb_features_desc_t *D, int n_plants) {
 }
 int npb_set_features(NpbHandle *h, const npb_features_desc_t *desc) {
   if (!h) return NPB_EINVAL;
+  if (h->ro.n_final) return fail_who(h, "npb_set_features", g_rollout_holds);
   if (const char *why = npb_features_check(desc, h->n_plants)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
   if (!desc) { attachment_drop(&h->feat, h->feat.cols); return NPB_OK; }
@@ -2077,6 +2100,7 @@ const char *npb_controls_check(const npb_controls_desc_t *D, int n_plants, int h
 }
 int npb_set_controls(NpbHandle *h, const npb_controls_desc_t *desc) {
   if (!h) return NPB_EINVAL;
+  if (h->ro.n_final) return fail_who(h, "npb_set_controls", g_rollout_holds);
   if (const char *why = npb_controls_check(desc, h->n_plants, h->params.heat_source)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
   if (!desc) { attachment_drop(&h->ctl, h->ctl.age); return NPB_OK; }
@@ -2119,6 +2143,83 @@ int npb_controls_get_state(NpbHandle *h, double *held, double *prev, int32_t *ag
 int npb_controls_set_state(NpbHandle *h, const double *held, const double *prev, const int32_t *age, const int32_t *primed, const int32_t *seen,
                            void *stream) {
   return state_copy(h, "npb_controls_set_state", controls_state_parts, {held, prev, age, primed, seen}, true, stream);
+}
+
+/* ---- the rollout (include/npb.h, npd_rollout.h) */
+const char *npb_rollout_check(const npb_rollout_desc_t *D, int n_plants, int features_cells, int n_axes) {
+  if (!D) return nullptr;
+  if (n_plants < 1) return "npb_set_rollout: n_plants must be >= 1";
+  if (features_cells < 1) return "npb_set_rollout: the features' stack must have cells (K * C >= 1): a rollout needs features";
+  if (D->horizon < 1 || D->horizon > NPB_ROLLOUT_HORIZON_MAX) return "npb_set_rollout: the horizon must be 1 .. NPB_ROLLOUT_HORIZON_MAX (4096)";
+  if (D->n_extras < 0 || D->n_extras > NPB_ROLLOUT_EXTRAS_MAX) return "npb_set_rollout: the extras count must be 0 .. NPB_ROLLOUT_EXTRAS_MAX (8)";
+  if (n_axes < 0) return "npb_set_rollout: a negative axis count";
+  if (D->act && n_axes == 0) return "npb_set_rollout: an act buffer without axes (no controls are set)";
+  if (!D->act && n_axes > 0) return "npb_set_rollout: controls are set and the act buffer is NULL";
+  if (D->final_rows < 0) return "npb_set_rollout: final_rows must be >= 0";
+  if ((int64_t)n_plants * D->final_rows > INT32_MAX) return "npb_set_rollout: n_plants * final_rows is beyond what final_row (int32) holds";
+  if (D->final_rows > 0 && !D->final_obs) return "npb_set_rollout: final_rows > 0 and final_obs is NULL";
+  if (!D->obs || !D->reward || !D->ended || !D->episode || !D->final_row) return "npb_set_rollout: NULL obs, reward, ended, episode or final_row";
+  if (D->n_extras > 0 && (!D->extras_in || !D->extra)) return "npb_set_rollout: extras without their input (extras_in) or their buffer (extra)";
+  if (((uintptr_t)D->obs | (uintptr_t)D->act | (uintptr_t)D->extras_in | (uintptr_t)D->extra | (uintptr_t)D->final_obs) & 15u)
+    return "npb_set_rollout: misaligned obs, act, extras_in, extra or final_obs: 16-byte aligned";
+  if ((uintptr_t)D->reward & 7u) return "npb_set_rollout: a misaligned reward buffer: 8-byte aligned";
+  if (((uintptr_t)D->episode | (uintptr_t)D->final_row) & 3u) return "npb_set_rollout: misaligned episode or final_row: 4-byte aligned";
+  return nullptr;
+}
+static int rollout_rewind(NpbHandle *h, npb_rollout_t *R, hipStream_t stream) {
+  const size_t n = (size_t)h->n_plants;
+  NPB_HIP(h, hipMemsetAsync(R->n_final, 0, n * sizeof(int32_t), stream));
+  NPB_HIP(h, hipMemsetAsync(R->D.final_row, 0xff, (size_t)R->D.horizon * n * sizeof(int32_t), stream));      /* -1 */
+  R->t = 0;
+  return NPB_OK;
+}
+int npb_set_rollout(NpbHandle *h, const npb_rollout_desc_t *desc) {
+  if (!h) return NPB_EINVAL;
+  if (desc && !h->feat.cols) return fail(h, NPB_EINVAL, "npb_set_rollout: no features set (npb_set_features first): the rollout records their tensor");
+  const int cells = h->feat.n_cols * h->feat.stack, n_axes = h->ctl.age ? h->ctl.n_axes : 0;
+  if (const char *why = npb_rollout_check(desc, h->n_plants, cells, n_axes)) return fail(h, NPB_EINVAL, why);
+  NPB_USE_DEVICE(h);
+  if (!desc) { attachment_drop(&h->ro, h->ro.n_final); return NPB_OK; }
+  char *dev = nullptr;
+  if (int rc = attachment_alloc(h, "npb_set_rollout", "the final-row counters", nullptr, 0, (size_t)h->n_plants * sizeof(int32_t), &dev)) return rc;
+  npb_rollout_t R = {};
+  R.n_final = (int32_t *)dev; R.D = *desc; R.cells = cells; R.n_axes = n_axes;
+  R.obs_bytes = h->feat.out_f64 ? 8 : 4; R.act_bytes = h->ctl.in_f64 ? 8 : 4;
+  if (!R.D.final_obs) R.D.final_rows = 0;
+  if (int rc = rollout_rewind(h, &R, nullptr)) { (void)hipFree(dev); return rc; }
+  NPB_HIP(h, hipStreamSynchronize(nullptr));
+  attachment_drop(&h->ro, h->ro.n_final);
+  h->ro = R;
+  return NPB_OK;
+}
+int npb_rollout_steps(const NpbHandle *h) { return h && h->ro.n_final ? h->ro.t : -1; }
+int npb_rollout_begin(NpbHandle *h, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->ro.n_final) return fail_who(h, "npb_rollout_begin", g_no_rollout);
+  NPB_USE_DEVICE(h);
+  return rollout_rewind(h, &h->ro, (hipStream_t)stream);
+}
+int npb_rollout_cut(NpbHandle *h, const uint8_t *mask, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (h->ro.n_final && h->ro.t == 0) return NPB_OK;      /* nothing recorded yet: nothing in front of slot 0 */
+  return attachment_clear(h, "npb_rollout_cut", h->ro.n_final, g_no_rollout,
+                          [&] { npb_launch_rollout_cut(&h->ro, mask, h->n_plants, (hipStream_t)stream); });
+}
+int npb_rollout_advantages(NpbHandle *h, const npb_rollout_advantages_desc_t *A, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->ro.n_final) return fail_who(h, "npb_rollout_advantages", g_no_rollout);
+  if (!A) return fail(h, NPB_EINVAL, "npb_rollout_advantages: a NULL descriptor");
+  if (h->ro.t == 0) return fail(h, NPB_EINVAL, "npb_rollout_advantages: nothing recorded yet (t == 0)");
+  if (!(A->gamma >= 0.0 && A->gamma <= 1.0) || !(A->lam >= 0.0 && A->lam <= 1.0))
+    return fail(h, NPB_EINVAL, "npb_rollout_advantages: gamma and lam must lie in [0, 1] (a NaN does not)");
+  if (!A->adv && !A->ret) return fail(h, NPB_EINVAL, "npb_rollout_advantages: adv and ret are both NULL");
+  if (A->out_type != NPB_ROLLOUT_F32 && A->out_type != NPB_ROLLOUT_F64) return fail(h, NPB_EINVAL, "npb_rollout_advantages: an unknown out type");
+  if (h->ro.D.final_rows > 0 && !A->final_value)
+    return fail(h, NPB_EINVAL, "npb_rollout_advantages: the rollout keeps terminal stacks (final_rows > 0) and final_value, the caller's value of them, is NULL");
+  NPB_USE_DEVICE(h);
+  npb_launch_rollout_advantages(&h->ro, A, A->gamma * A->lam, h->n_plants, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
 }
 
 /* ---- episode streams (include/npb.h) */

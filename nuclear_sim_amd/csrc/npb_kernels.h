@@ -109,6 +109,14 @@ typedef struct {
   const void *in; double *held, *prev, *column[NPB_CONTROL_INPUT_COUNT];
   int32_t *age, *primed, *seen;
 } npb_controls_t;
+/* npb_set_rollout (npd_rollout.h): the caller's buffers as the descriptor names them, the shapes they were bound with (cells = K * C of the
+ * features, n_axes of the controls or 0, the element sizes of obs and act), and of the handle: n_final int32 [n_plants] (its one
+ * allocation; NULL = off) and the host cursor t */
+typedef struct {
+  int32_t *n_final;
+  npb_rollout_desc_t D;
+  int cells, n_axes, obs_bytes, act_bytes, t;
+} npb_rollout_t;
 typedef struct {
   int (*step)(const npb_params_t *P, int n_plants, size_t npad, void *arena, const int32_t *action,
               const double *magnitude, const double *setpoint, const double *noise_z, const double *cw_temp,
@@ -203,6 +211,18 @@ void npb_launch_column_stats_clear(const npb_column_stats_t *S, const uint8_t *m
 void npb_launch_event_windows_clear(const npb_event_windows_t *W, const uint8_t *mask, int n_plants, hipStream_t stream);
 /* npb_task_clear, npb_features_clear, npb_controls_clear: the plants of mask (NULL = all) unprimed in that attachment's `primed` column */
 void npb_launch_unprime(int32_t *primed, const uint8_t *mask, int n_plants, hipStream_t stream);
+/* npb_set_rollout (npd_rollout.h), the same for either storage type: none of them touches the arena.
+ * pre: the three copies into slot R->t in front of the controls kernel, feat_out and ctl_in the tensors the features and the controls are
+ *   bound to (ctl_in NULL without controls).
+ * post: reward, ended, episode and the terminal stacks of slot R->t, behind features pass A; len / index: the carried lengths and episode
+ *   indices while the autoreset is on, else NULL.
+ * cut: bit 2 into ended[R->t - 1] for the plants of mask (NULL = all); R->t > 0.
+ * advantages: the recurrence over the slots [0, R->t), gl = gamma * lam */
+void npb_launch_rollout_pre(const npb_rollout_t *R, const void *feat_out, const void *ctl_in, int n_plants, hipStream_t stream);
+void npb_launch_rollout_post(const npb_rollout_t *R, const void *feat_out, const double *reward, const uint8_t *done, const int32_t *len,
+                             const int32_t *index, int max_steps, int n_plants, hipStream_t stream);
+void npb_launch_rollout_cut(const npb_rollout_t *R, const uint8_t *mask, int n_plants, hipStream_t stream);
+void npb_launch_rollout_advantages(const npb_rollout_t *R, const npb_rollout_advantages_desc_t *A, double gl, int n_plants, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -1876,4 +1876,8 @@ __global__ __launch_bounds__(256) void npb_unprime_kernel(int32_t *__restrict__ 
 extern "C" void npb_launch_unprime(int32_t *primed, const uint8_t *mask, int n_plants, hipStream_t stream) {
   hipLaunchKernelGGL(npb_unprime_kernel, dim3((unsigned)((n_plants + 255) / 256)), dim3(256), 0, stream, primed, mask, n_plants);
 }
+
+/* the rollout (npb_set_rollout): the two kernels around the step, the cut, the advantages and their launchers; none touches the arena,
+ * so they too are compiled once */
+#include "npd_rollout.h"
 #endif

@@ -19,7 +19,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, rollout
 from .schema import SCHEMA
 
 
@@ -504,7 +504,7 @@ class BatchedPlantEnv:
         self._keep = []
         self._episode = None
         self._bank = None
-        self._mlog = self._msum = self._erec = self._cstats = self._ewin = self._task = self._feat = self._ctl = None      # (see ``_OFF``)
+        self._mlog = self._msum = self._erec = self._cstats = self._ewin = self._task = self._feat = self._ctl = self._roll = None      # (see ``_OFF``)
         self._diag_buf = None; self.diagnostics = None; self._diag_carried = False
         if diagnostics:      # before the first snapshot (autoreset=True takes it below), so that it records the carried rows
             self.enable_diagnostics(True, carried=True)
@@ -1018,13 +1018,14 @@ class BatchedPlantEnv:
 
     # ------------------------------------------------------------------ what the attachments share
     # The per-step attachments -- maintenance log and summary, episode records, column statistics, event windows, task, features,
-    # controls: None = off, else what the enable_* / set_* method keeps of it.  __init__ sets them; the class has them too, so that a
+    # controls, rollout: None = off, else what the enable_* / set_* method keeps of it.  __init__ sets them; the class has them too, so that a
     # refusal "before any device work" can be checked on an object made without it.  ``_on`` reads them, with these refusals:
-    _mlog = _msum = _erec = _cstats = _ewin = _task = _feat = _ctl = None
+    _mlog = _msum = _erec = _cstats = _ewin = _task = _feat = _ctl = _roll = None
+    _max_episode_steps = 0      # the autoreset's limit, 0 = none (``_enable_autoreset``)
     _OFF = {"_mlog": "no maintenance log: enable_maintenance_log() first", "_msum": "no maintenance summary: enable_maintenance_summary() first",
             "_erec": "no episode records: enable_episode_records() first", "_cstats": "no column statistics: enable_column_stats() first",
             "_ewin": "no event windows: enable_event_windows() first", "_task": "no task: set_task() first",
-            "_feat": "no features: set_features() first", "_ctl": "no controls: set_controls() first"}
+            "_feat": "no features: set_features() first", "_ctl": "no controls: set_controls() first", "_roll": "no rollout: set_rollout() first"}
     # who reads side buffers, as a refusal names them: each keeps ``"reads"``, the buffers its request resolved to (``_reading``)
     _CONSUMERS = {"_task": "the task", "_feat": "the features", "_cstats": "the column statistics", "_ewin": "the event windows"}
 
@@ -1398,6 +1399,7 @@ class BatchedPlantEnv:
         ``restore`` and ``restore_from_bank`` refill the plants they reset.  With features on ``step()`` adds ``info["features"]`` and,
         with autoreset, ``info["final_features"]``; with ``as_observation`` it returns the features in place of the observation (which
         stays in ``info["observation"]``).  ``set_features(None)`` turns it off."""
+        self._refuse_under_rollout("the features")
         if columns is None:
             if self._feat is not None:
                 _lib.check(self.L.npb_set_features(self._h, None), self._h)
@@ -1457,12 +1459,15 @@ class BatchedPlantEnv:
 
     def _after_restart(self, mask) -> None:
         """behind ``reset`` / ``restore`` / ``restore_from_bank``, THE place where an attachment follows a restart the caller made: the
-        plants they reset show the features' frame of their new state, and start a new hold of the controls"""
+        plants they reset show the features' frame of their new state, start a new hold of the controls, and have their episode cut in the
+        rollout's last recorded slot"""
         if self._feat is not None:
             self.clear_features(mask)
             self.features()
         if self._ctl is not None:
             self.clear_controls(mask)
+        if self._roll is not None:
+            _lib.check(self.L.npb_rollout_cut(self._h, self._p(mask), self._stream()), self._h)
 
     def features_state(self) -> Dict[str, np.ndarray]:
         """The features' own state for a checkpoint (npb_features_get_state), beside ``state_arrays()`` and a copy of ``features()``:
@@ -1510,6 +1515,7 @@ class BatchedPlantEnv:
         ``("control", a)`` against 0; jerk: ``sq_err`` against ``("control_prev", a)``), and ``step()`` adds ``info["controls"]``, the
         held values ``[len(axes), n]``.  ``nuclear_sim_amd.controls`` is the same in numpy, bit for bit.  ``set_controls(None)`` turns
         it off."""
+        self._refuse_under_rollout("the controls")
         readers = self._control_readers()      # (none without controls: their columns are no words then)
         if readers:
             raise _lib.NpbError("%s read(s) the controls' columns: turn that off first" % " and ".join(readers))
@@ -1564,6 +1570,132 @@ class BatchedPlantEnv:
     def controls_spec(self) -> dict:
         """the request as data: what ``nuclear_sim_amd.controls.Decoder`` takes"""
         return self._on("_ctl")["spec"]
+
+    def _refuse_under_rollout(self, what: str) -> None:
+        """``set_features`` / ``set_controls`` while a rollout is set, set and None alike: its pre kernel copies their tensors every step,
+        in the shapes it was bound with"""
+        if self._roll is not None:
+            raise _lib.NpbError("the rollout records %s every step: set_rollout(None) first" % what)
+
+    def set_rollout(self, horizon, extras: int = 0, final_rows: Optional[int] = None) -> None:
+        """Record trajectories on the device (npb_set_rollout): for ``horizon`` steps (1 to 4096) every ``step()`` writes slot t of
+        time-major tensors the env keeps -- two launches more, nothing read back: ``obs`` [T, n, K, C], the features as the policy saw them
+        in front of the step (so features must be set; plants without a frame are primed first); ``act`` [T, n, A], the controls input as
+        it wrote it (with controls set); ``extra`` [T, n, extras] float32, a copy of ``rollout_extras_input()``, [n, extras], which the
+        caller writes before each step (value, log-probability, ...; up to 8); ``reward`` [T, n] float64 (the task's while a task is set);
+        ``ended`` [T, n] uint8 (bit 0 terminated, bit 1 truncated, bit 2 cut: ``reset`` / ``restore`` / ``restore_from_bank`` between two
+        steps cut the plants they reset); ``episode`` [T, n] int32 (-1 without autoreset); and for every truncated transition
+        ``final_obs[final_row[t, p]]``, its terminal stack, whose value a learner bootstraps from (``final_rows`` per plant: default the
+        derived bound ceil(horizon / max_episode_steps), or 0 where nothing truncates).  A step at t == horizon is refused:
+        ``rollout_begin()`` rewinds.  ``rollout_advantages`` forms GAE advantages and returns over the recorded slots in one launch.
+        While the rollout is set ``set_features`` and ``set_controls`` are refused.  ``nuclear_sim_amd.rollout`` is the same in numpy, bit
+        for bit.  ``set_rollout(None)`` turns it off."""
+        if horizon is None:
+            if self._roll is not None:
+                _lib.check(self.L.npb_set_rollout(self._h, None), self._h)
+            self._roll = None
+            return
+        ft, ct = self._feat, self._ctl
+        if ft is None:
+            raise _lib.NpbError("a rollout records the features: set_features() first")
+        if not hasattr(self.L, "npb_set_rollout"):
+            raise _lib.NpbError("libnpb.so has no npb_set_rollout: rebuild")
+        T, E = int(horizon), int(extras)
+        if not 1 <= T <= _lib.ROLLOUT_HORIZON_MAX:
+            raise ValueError("a rollout's horizon is 1 to %d steps, not %r" % (_lib.ROLLOUT_HORIZON_MAX, horizon))
+        if not 0 <= E <= _lib.ROLLOUT_EXTRAS_MAX:
+            raise ValueError("a rollout takes 0 to %d extras, not %r" % (_lib.ROLLOUT_EXTRAS_MAX, extras))
+        R = rollout.final_rows_bound(T, self._max_episode_steps) if final_rows is None else int(final_rows)
+        if R < 0:
+            raise ValueError("final_rows must be >= 0")
+        n, (_, K, C) = self.n, ft["out"].shape
+        A = 0 if ct is None else ct["in"].shape[1]
+        with torch.cuda.device(self.device):
+            def zeros(shape, dtype):
+                return torch.zeros(shape, dtype=dtype, device=self.device)
+            t = {"obs": zeros((T, n, K, C), ft["out"].dtype), "act": zeros((T, n, A), ct["in"].dtype) if A else None,
+                 "extra": zeros((T, n, E), torch.float32) if E else None, "reward": zeros((T, n), torch.float64),
+                 "ended": zeros((T, n), torch.uint8), "episode": zeros((T, n), torch.int32), "final_row": zeros((T, n), torch.int32),
+                 "final_obs": zeros((n * R, K, C), ft["out"].dtype) if R else None}
+            extras_in = zeros((n, E), torch.float32) if E else None
+        d = _lib.NpbRolloutDesc()
+        d.horizon, d.n_extras, d.final_rows, d.extras_in = T, E, R, None if extras_in is None else extras_in.data_ptr()
+        for name, x in t.items():
+            setattr(d, name, None if x is None else x.data_ptr())
+        _lib.check(self.L.npb_set_rollout(self._h, ctypes.byref(d)), self._h)      # (refused: what was set before stays)
+        self._roll = {"tensors": t, "extras_in": extras_in, "out": {},
+                      "spec": {"horizon": T, "extras": E, "final_rows": R, "stack": (K, C), "axes": A, "autoreset": self._episode is not None,
+                               "max_episode_steps": self._max_episode_steps, "obs_dtype": str(ft["out"].dtype).split(".")[1],
+                               "act_dtype": None if ct is None else str(ct["in"].dtype).split(".")[1]}}
+
+    def rollout_extras_input(self) -> torch.Tensor:
+        """The bound ``[n, extras]`` float32 tensor whose rows the next ``step`` copies into ``extra[t]``, the same storage on every call"""
+        x = self._on("_roll")["extras_in"]
+        if x is None:
+            raise _lib.NpbError("no extras: set_rollout(..., extras=E)")
+        return x
+
+    def rollout(self) -> dict:
+        """The recorded tensors, the same storage on every call (``act``, ``extra`` and ``final_obs`` None where there are none), and
+        ``"t"``, the number of slots recorded"""
+        return dict(self._on("_roll")["tensors"], t=int(self.L.npb_rollout_steps(self._h)))
+
+    def rollout_begin(self) -> None:
+        """rewind: t = 0, every row of ``final_obs`` free again, ``final_row`` -1 (npb_rollout_begin)"""
+        self._on("_roll")
+        _lib.check(self.L.npb_rollout_begin(self._h, self._stream()), self._h)
+
+    def rollout_advantages(self, gamma: float, lam: float, values=None, last_value=None, final_values=None, dtype=torch.float32):
+        """GAE advantages and returns over the recorded slots in one launch (npb_rollout_advantages): ``(adv, ret)``, each ``[t, n]`` of
+        ``dtype`` (float32 or float64), views of tensors the env keeps per dtype.  ``values``: None (0 everywhere: with ``lam`` 1 ``ret`` is the
+        discounted return-to-go), a float32 ``[>= t, n]`` tensor, or ``("extra", j)`` -- column j of the recorded extras, read in place.
+        ``last_value``: float32 [n], the value of the state behind the last slot; ``final_values``: float32 [n * final_rows], the caller's
+        value of every row of ``final_obs`` (needed when final_rows > 0): a truncated transition bootstraps from the value of its TERMINAL
+        state, a terminated or cut one from 0.  Double arithmetic, as ``nuclear_sim_amd.rollout.advantages`` states it, bit for bit."""
+        ro = self._on("_roll")
+        T, tensors = ro["spec"]["horizon"], ro["tensors"]
+        name = {torch.float32: "float32", torch.float64: "float64"}.get(dtype)
+        if name is None:
+            raise ValueError("advantages are float32 or float64, not %r" % (dtype,))
+
+        def column(x, what, shape=None):      # a float32 device tensor of the caller's, as it is when it can be
+            if x is None:
+                return None
+            x = torch.as_tensor(x).to(device=self.device, dtype=torch.float32).contiguous()
+            if shape is not None and tuple(x.shape) != shape:
+                raise ValueError("%s must be %r, not %r" % (what, shape, tuple(x.shape)))
+            return x
+        d = _lib.NpbRolloutAdvantagesDesc()
+        d.gamma, d.lam, d.out_type = float(gamma), float(lam), _lib.ROLLOUT_DTYPES[name]
+        if isinstance(values, tuple):
+            if len(values) != 2 or values[0] != "extra" or tensors["extra"] is None or not 0 <= int(values[1]) < ro["spec"]["extras"]:
+                raise ValueError("values in place: ('extra', j) with j one of the rollout's %d extras, not %r" % (ro["spec"]["extras"], values))
+            E = ro["spec"]["extras"]
+            d.value, d.value_time_stride, d.value_plant_stride = tensors["extra"].data_ptr() + 4 * int(values[1]), self.n * E, E
+            values = None
+        else:
+            values = column(values, "values")
+            if values is not None:
+                if values.dim() != 2 or values.shape[1] != self.n or values.shape[0] < int(self.L.npb_rollout_steps(self._h)):
+                    raise ValueError("values must be [>= t, n], not %r" % (tuple(values.shape),))
+                d.value, d.value_time_stride, d.value_plant_stride = values.data_ptr(), self.n, 1
+        last_value = column(last_value, "last_value", (self.n,))
+        final_values = column(final_values, "final_values", (self.n * ro["spec"]["final_rows"],))
+        d.last_value = None if last_value is None else last_value.data_ptr()
+        d.final_value = None if final_values is None else final_values.data_ptr()
+        if name not in ro["out"]:
+            with torch.cuda.device(self.device):
+                ro["out"][name] = (torch.zeros((T, self.n), dtype=dtype, device=self.device), torch.zeros((T, self.n), dtype=dtype, device=self.device))
+        adv, ret = ro["out"][name]
+        d.adv, d.ret = adv.data_ptr(), ret.data_ptr()
+        _lib.check(self.L.npb_rollout_advantages(self._h, ctypes.byref(d), self._stream()), self._h)
+        ro["held"] = (values, last_value, final_values)      # (alive while the launch reads them)
+        t = int(self.L.npb_rollout_steps(self._h))
+        return adv[:t], ret[:t]
+
+    def rollout_spec(self) -> dict:
+        """the request as data: what ``nuclear_sim_amd.rollout.Recorder`` takes"""
+        return self._on("_roll")["spec"]
 
     def _order_buffers(self):
         """the buffers the perform_*_maintenance methods keep for their order columns, with the ``success`` column they all return"""
@@ -1791,6 +1923,7 @@ class BatchedPlantEnv:
             if hasattr(self.L, "npb_set_episode_index_buffer"):
                 self._episode["episode_index"] = torch.zeros(self.n, dtype=torch.int32, device=self.device)
         _lib.check(self.L.npb_set_autoreset(self._h, 1, int(max_episode_steps or 0)), self._h)
+        self._max_episode_steps = int(max_episode_steps or 0)
         e = self._episode
         _lib.check(self.L.npb_set_episode_buffers(self._h, self._p(e["episode_length"]), self._p(e["episode_return"]), self._p(e["truncated"]),
                                                   self._p(e["final_observation"])), self._h)
@@ -1861,6 +1994,7 @@ class BatchedPlantEnv:
         self._task = None
         self._feat = None
         self._ctl = None
+        self._roll = None
 
     def __del__(self):
         try:
@@ -2024,6 +2158,8 @@ class BatchedPlantEnv:
              thermal_power_mw=None, power_percent=None, controls=None):
         self._keep = []
         ctl = self._ctl
+        if self._roll is not None:      # the rollout records the features in front of the step: every plant has a frame by then
+            self.features()
         if controls is not None:      # the policy's output for this step (set_controls): into the bound tensor unless it is that tensor
             if ctl is None:
                 raise _lib.NpbError("step(controls=...) without controls: set_controls() first")
