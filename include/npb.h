@@ -1178,9 +1178,9 @@ NPB_API int npb_controls_set_state(NpbHandle *h, const double *held, const doubl
  * T or E out of range; an act buffer without axes, or axes without an act buffer; R < 0, or n_plants * R beyond int32; final_obs NULL with R > 0; a NULL obs, reward,
  * ended, episode or final_row; E > 0 without extras_in or extra; a misaligned buffer (16 bytes for obs, act, extras_in, extra and
  * final_obs, 8 for reward, 4 for episode and final_row).
- * No step, restore, episode, task, features or controls kernel changes.  Not here: advantage normalisation (a reduction order would have
- * to be pinned), minibatch shuffling, a checkpoint of a half-filled rollout, half types, V-trace or other off-policy corrections,
- * rollouts without features.
+ * No step, restore, episode, task, features or controls kernel changes.  Not here: advantage normalisation and minibatch shuffling (they
+ * have the section below, where the reduction order is pinned: npb_rollout_moments, npb_rollout_minibatch),
+ * a checkpoint of a half-filled rollout, half types, V-trace or other off-policy corrections, rollouts without features.
  * NPB_VERSION stays 154: a binding detects the entry points by name. */
 #define NPB_ROLLOUT_HORIZON_MAX 4096
 #define NPB_ROLLOUT_EXTRAS_MAX 8
@@ -1214,6 +1214,84 @@ NPB_API int npb_rollout_begin(NpbHandle *h, void *stream);
 NPB_API int npb_rollout_steps(const NpbHandle *h);      /* t, or -1 without a rollout */
 NPB_API int npb_rollout_cut(NpbHandle *h, const uint8_t *mask, void *stream);
 NPB_API int npb_rollout_advantages(NpbHandle *h, const npb_rollout_advantages_desc_t *desc, void *stream);
+
+/* Between the advantages and the optimiser: what a PPO-style learner does with a finished rollout -- the advantages' mean and standard
+ * deviation, a shuffled order, and the gather of one minibatch after the other -- on the device, with nothing read back.
+ * nuclear_sim_amd/rollout.py (moments, permutation_keys, permutation, minibatch) states all of it in numpy, and that statement is the
+ * contract; the device produces its bits whatever the launch geometry.  No kernel here touches the arena, uses atomics or depends on the
+ * launch order; they are built without -freciprocal-math / -fapprox-func (npb_minibatch.hip): division and root are IEEE.
+ * npb_rollout_moments(h, desc, stream): out = {count, mean, var, std} of src, a contiguous device [rows][cols] float or double tensor --
+ *   any such tensor, no rollout need be set.  The order of every addition is pinned:
+ *     col[p]  = 0.0, then col[p] += (double)src[s][p] for s = 0 .. rows - 1 in that order
+ *     tree(c) : while c has more than one value: pad it with +0.0 to a multiple of 256, and in each group of 256 add the upper half onto
+ *               the lower for half = 128, 64, ... 1; the groups' first values are the next c.  Its one value is the result.
+ *     count   = rows * cols;  mean = tree(col) / count
+ *     col2[p] += d * d with d = (double)src[s][p] - mean, the product rounded before the sum;  var = tree(col2) / (count - ddof)
+ *     std     = sqrt(var)
+ *   the sum is not restated as a scan or a different tree.  A NaN or an infinity propagates.  Four launches: a column pass with one lane
+ *   per column whose workgroup of 256 evaluates one group of the tree in LDS and writes one partial, and one workgroup that finishes the
+ *   tree over the partials, divides and (second pass) takes the root -- twice.  The partials live in a workspace of the handle's, grown
+ *   on demand and dropped by npb_destroy.  NPB_EINVAL: a NULL descriptor, src or out; an unknown type; rows or cols < 1, cols beyond
+ *   2^31 - 1, rows * cols beyond 2^53; ddof < 0 or rows * cols <= ddof; src misaligned for its type or out not 8-byte aligned.
+ * npb_rollout_permutation(h, N, keys, first, count, out, stream): out[j] = entry first + j of a permutation of [0, N), 1 <= N <= 2^31 - 1,
+ *   each entry a function of its position and the NPB_MINIBATCH_ROUNDS round keys alone -- no table, no sort, no memory:
+ *     b = max(bit_length(N - 1), 2);  w = (b + 1) / 2;  x = position: L = x >> w, R = x & (2^w - 1)
+ *     for r = 0 .. 5: (L, R) = (R, L ^ (mix(R ^ keys[r]) & (2^w - 1)))      mix: murmur3's 32-bit finaliser, in uint32 arithmetic
+ *     x = L << w | R;  while x >= N the network is applied to x again (cycle walking)
+ *   The network is a bijection on [0, 2^(2w)), so the walk is one on [0, N), and it ends: the walk from a position below N stays on that
+ *   position's cycle.  2^(2w) < 4 N: under 4 applications in the mean.  One lane per entry.  The caller derives the keys from its seed
+ *   and epoch (rollout.permutation_keys: a splitmix64 chain).  NPB_EINVAL: N out of range, count < 1, first < 0 or first + count > N, NULL
+ *   keys or out, out not 4-byte aligned.
+ * npb_rollout_minibatch(h, desc, stream): entries [first, first + count) of the epoch `keys` belong to, gathered from the handle's rollout
+ *   -- sources and shapes (the recorded slots t, n, K * C, A, E, the types) are the rollout's -- in ONE launch:
+ *   unit NPB_MINIBATCH_TRANSITION: N = t * n; index[j] = permutation(N)[first + j], the flat cell s * n + p; obs [count][K][C], act
+ *     [count][A], extra [count][E], adv_out, ret_out [count] are that cell's rows of obs, act, extra, adv, ret.
+ *   unit NPB_MINIBATCH_PLANT (recurrent policies: sequences kept whole): N = n; index[j] is a plant; every output is time-major,
+ *     [t][count]... = src[s][index[j]] for every s < t.
+ *   adv, ret: device [>= t][n] of `type`, as npb_rollout_advantages wrote them.  With moments (device, what npb_rollout_moments wrote)
+ *     adv_out = narrow(((double)adv - moments[1]) / (moments[3] + eps)): one subtraction, one addition, one IEEE division in double, then
+ *     one narrowing to `type`, round-to-nearest-even.  Without, adv is copied.  Any output but index may be NULL.
+ *   A wave takes 32 output rows: one lane per row computes its source index and writes index, adv_out and ret_out, consecutive lanes on
+ *   consecutive outputs; then the wave walks its rows, L lanes on each -- L the smallest power of two with L * 16 bytes >= the row, at
+ *   most 64 --, 16 bytes per lane where the row is a whole number of 16-byte pieces, else one element per lane.  max_blocks: the most
+ *   workgroups the launch may have (0: the launcher's own bound); the result does not depend on it.
+ *   NPB_EINVAL with the reason in npb_last_error, before any device work: no rollout set, and what npb_minibatch_check refuses -- that
+ *   check alone, without a handle (t = the recorded slots, features_cells = K * C), NULL = accepted, else the reason: a NULL descriptor;
+ *   n_plants < 1 or features_cells < 1; t == 0 (nothing recorded); an unknown unit or type; N beyond 2^31 - 1; count < 1; first < 0 or
+ *   first + count > N; index NULL; an act / extra output without axes / extras; adv_out without adv, ret_out without ret; moments set
+ *   with adv_out NULL; eps negative or a NaN; max_blocks < 0; a misaligned buffer (16 bytes for the obs, act and extra outputs, 8 for
+ *   moments, the element size for adv, ret and their outputs, 4 for index).
+ * A handle that never calls these behaves as before in every entry point.  Not here: half or bfloat16 outputs, weighted or prioritised
+ * sampling, sampling with replacement, masks over transitions, a checkpoint of a half-drained epoch (the epoch IS (seed, epoch, first):
+ * three numbers the caller has), V-trace, running normalisation across rollouts, gathering final_obs (its use ended in
+ * npb_rollout_advantages).  NPB_VERSION stays 154: a binding detects the entry points by name. */
+#define NPB_MINIBATCH_ROUNDS 6
+enum { NPB_MINIBATCH_TRANSITION = 0, NPB_MINIBATCH_PLANT = 1 };
+typedef struct npb_moments_desc_t {
+  const void *src;               /* device [rows][cols], contiguous */
+  int type;                      /* NPB_ROLLOUT_F32 | NPB_ROLLOUT_F64 */
+  int ddof;
+  int64_t rows, cols;
+  double *out;                   /* device [4]: count, mean, var, std */
+} npb_moments_desc_t;
+typedef struct npb_minibatch_desc_t {
+  int unit;                      /* NPB_MINIBATCH_TRANSITION | NPB_MINIBATCH_PLANT */
+  uint32_t keys[NPB_MINIBATCH_ROUNDS];
+  int type;                      /* of adv, ret, adv_out and ret_out: NPB_ROLLOUT_F32 | NPB_ROLLOUT_F64 */
+  int64_t first, count;          /* entries [first, first + count) of the permutation */
+  const void *adv, *ret;         /* device [>= t][n_plants]; NULL only where its output is */
+  const double *moments;         /* device [4] as npb_rollout_moments writes it, or NULL: adv is copied */
+  double eps;
+  int32_t *index;                /* device [count] */
+  void *obs, *act;               /* device [count][K][C], [count][A] (PLANT: [t][count]...), or NULL */
+  float *extra;                  /* device [count][E] (PLANT: [t][count][E]), or NULL */
+  void *adv_out, *ret_out;       /* device [count] (PLANT: [t][count]), or NULL */
+  int max_blocks;                /* 0 = the launcher's bound */
+} npb_minibatch_desc_t;
+NPB_API int npb_rollout_moments(NpbHandle *h, const npb_moments_desc_t *desc, void *stream);
+NPB_API int npb_rollout_permutation(NpbHandle *h, int64_t N, const uint32_t *keys, int64_t first, int64_t count, int32_t *out, void *stream);
+NPB_API int npb_rollout_minibatch(NpbHandle *h, const npb_minibatch_desc_t *desc, void *stream);
+NPB_API const char *npb_minibatch_check(const npb_minibatch_desc_t *desc, int n_plants, int t, int features_cells, int n_axes, int n_extras);
 
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the

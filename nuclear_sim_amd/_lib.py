@@ -902,6 +902,27 @@ class NpbRolloutAdvantagesDesc(ctypes.Structure):
                 ("out_type", ctypes.c_int), ("adv", ctypes.c_void_p), ("ret", ctypes.c_void_p)]
 
 
+# include/npb.h npb_moments_desc_t / npb_minibatch_desc_t: the pinned moments and one shuffled minibatch of the rollout (npb_rollout_moments,
+# npb_rollout_minibatch)
+MINIBATCH_ROUNDS = 6
+MINIBATCH_UNITS = {"transition": 0, "plant": 1}                        # NPB_MINIBATCH_TRANSITION / NPB_MINIBATCH_PLANT (rollout.UNITS)
+
+
+class NpbMomentsDesc(ctypes.Structure):
+    """npb_moments_desc_t: a contiguous device [rows, cols] tensor, its type, ddof and the four doubles count, mean, var, std"""
+    _fields_ = [("src", ctypes.c_void_p), ("type", ctypes.c_int), ("ddof", ctypes.c_int), ("rows", ctypes.c_int64), ("cols", ctypes.c_int64),
+                ("out", ctypes.c_void_p)]
+
+
+class NpbMinibatchDesc(ctypes.Structure):
+    """npb_minibatch_desc_t: the unit, the epoch's round keys, the window of the permutation, the advantages and returns with their type,
+    the moments (or NULL), eps, the outputs and the most workgroups the launch may have (0: the launcher's bound)"""
+    _fields_ = [("unit", ctypes.c_int), ("keys", ctypes.c_uint32 * MINIBATCH_ROUNDS), ("type", ctypes.c_int), ("first", ctypes.c_int64),
+                ("count", ctypes.c_int64), ("adv", ctypes.c_void_p), ("ret", ctypes.c_void_p), ("moments", ctypes.c_void_p),
+                ("eps", ctypes.c_double), ("index", ctypes.c_void_p), ("obs", ctypes.c_void_p), ("act", ctypes.c_void_p),
+                ("extra", ctypes.c_void_p), ("adv_out", ctypes.c_void_p), ("ret_out", ctypes.c_void_p), ("max_blocks", ctypes.c_int)]
+
+
 def controls_request(axes, interval: int = 1, dtype="float32", heat_source: int = 0) -> dict:
     """What ``BatchedPlantEnv.set_controls`` asks of npb_set_controls, from the caller's words; a pure function, host only, so an axis that
     cannot work is refused (ValueError, naming it) before any device work.
@@ -1196,6 +1217,12 @@ def load():
         L.npb_rollout_steps.argtypes = [vp]
         L.npb_rollout_cut.argtypes = [vp, vp, vp]
         L.npb_rollout_advantages.argtypes = [vp, ctypes.POINTER(NpbRolloutAdvantagesDesc), vp]
+    if hasattr(L, "npb_rollout_minibatch"):     # pinned moments, the keyed permutation and the minibatch gather over a rollout
+        L.npb_rollout_moments.argtypes = [vp, ctypes.POINTER(NpbMomentsDesc), vp]
+        L.npb_rollout_permutation.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64, ctypes.c_int64, vp, vp]
+        L.npb_rollout_minibatch.argtypes = [vp, ctypes.POINTER(NpbMinibatchDesc), vp]
+        L.npb_minibatch_check.argtypes = [ctypes.POINTER(NpbMinibatchDesc), ci, ci, ci, ci, ci]
+        L.npb_minibatch_check.restype = ctypes.c_char_p
     if hasattr(L, "npb_set_event_windows"):     # state windows around events, captured behind every step
         L.npb_set_event_windows.argtypes = [vp, ctypes.POINTER(NpbEventWindowsDesc)]
         L.npb_event_windows_check.argtypes = [ctypes.POINTER(NpbEventWindowsDesc), ci, ci]

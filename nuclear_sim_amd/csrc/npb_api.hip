@@ -11,6 +11,7 @@
 #include "../../include/npb.h"
 #include "npb_kernels.h"
 #include "npb_noise.h"
+#include "npb_minibatch.h"
 
 /* a side block's rows as recorded with a snapshot or a bank: a packed [rows][pitch] copy beside that arena, or NULL; its allocation */
 struct SideCopy { double *rows; size_t pitch, doubles; };
@@ -91,6 +92,8 @@ struct NpbHandle {
   /* npb_set_rollout: the caller's time-major buffers, the shapes they were bound with, the rows of final_obs every plant has taken (base
    * ro.n_final) and the cursor */
   npb_rollout_t ro;
+  /* npb_rollout_moments: the partials' workspace (base mom.ws), grown on demand */
+  npb_moments_ws_t mom;
   double *ramp_prev;   /* npb_profile_ramp: the previous setpoint of every plant ([pitch], NaN = none yet), allocated on first use */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
   std::vector<int> plan_key;
@@ -591,6 +594,7 @@ int npb_destroy(NpbHandle *h) {
   if (h->ers_dev) (void)hipFree(h->ers_dev);
   attachment_drop(&h->cs, h->cs.cols); attachment_drop(&h->ew, h->ew.cols); attachment_drop(&h->task, h->task.terms);
   attachment_drop(&h->feat, h->feat.cols); attachment_drop(&h->ctl, h->ctl.age); attachment_drop(&h->ro, h->ro.n_final);
+  attachment_drop(&h->mom, h->mom.ws);
   for (Sampler *sm : h->samplers) if (sm) { (void)hipFree(sm->dev); delete sm; }
   delete h;
   return NPB_OK;
@@ -2218,6 +2222,86 @@ int npb_rollout_advantages(NpbHandle *h, const npb_rollout_advantages_desc_t *A,
     return fail(h, NPB_EINVAL, "npb_rollout_advantages: the rollout keeps terminal stacks (final_rows > 0) and final_value, the caller's value of them, is NULL");
   NPB_USE_DEVICE(h);
   npb_launch_rollout_advantages(&h->ro, A, A->gamma * A->lam, h->n_plants, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+
+/* ---- between the advantages and the optimiser (include/npb.h, npb_minibatch.hip): pinned moments, the permutation, the minibatch */
+static const char *moments_check(const npb_moments_desc_t *M) {
+  if (!M) return "npb_rollout_moments: a NULL descriptor";
+  if (!M->src || !M->out) return "npb_rollout_moments: NULL src or out";
+  if (M->type != NPB_ROLLOUT_F32 && M->type != NPB_ROLLOUT_F64) return "npb_rollout_moments: an unknown type";
+  if (M->rows < 1 || M->cols < 1) return "npb_rollout_moments: rows and cols must be >= 1";
+  if (M->cols > INT32_MAX) return "npb_rollout_moments: cols beyond 2^31 - 1";
+  if (M->rows > ((int64_t)1 << 53) / M->cols) return "npb_rollout_moments: rows * cols beyond 2^53, what a double counts exactly";
+  if (M->ddof < 0) return "npb_rollout_moments: ddof must be >= 0";
+  if (M->rows * M->cols <= (int64_t)M->ddof) return "npb_rollout_moments: rows * cols <= ddof: nothing to divide by";
+  if ((uintptr_t)M->src & (M->type == NPB_ROLLOUT_F64 ? 7u : 3u)) return "npb_rollout_moments: src is misaligned for its type";
+  if ((uintptr_t)M->out & 7u) return "npb_rollout_moments: a misaligned out: 8-byte aligned";
+  return nullptr;
+}
+int npb_rollout_moments(NpbHandle *h, const npb_moments_desc_t *M, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (const char *why = moments_check(M)) return fail(h, NPB_EINVAL, why);
+  NPB_USE_DEVICE(h);
+  const size_t need = npb_moments_workspace(M->cols);
+  if (need > h->mom.cap) {      /* (hipFree of the old one waits for a launch that still reads it) */
+    char *dev = nullptr;
+    if (int rc = attachment_alloc(h, "npb_rollout_moments", "the partials' workspace", nullptr, 0, need * sizeof(double), &dev)) return rc;
+    attachment_drop(&h->mom, h->mom.ws);
+    h->mom.ws = (double *)dev; h->mom.cap = need;
+  }
+  npb_launch_moments(M, h->mom.ws, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_rollout_permutation(NpbHandle *h, int64_t N, const uint32_t *keys, int64_t first, int64_t count, int32_t *out, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (N < 1 || N > INT32_MAX) return fail(h, NPB_EINVAL, "npb_rollout_permutation: N must be 1 .. 2^31 - 1");
+  if (count < 1) return fail(h, NPB_EINVAL, "npb_rollout_permutation: count must be >= 1");
+  if (first < 0 || first > N - count) return fail(h, NPB_EINVAL, "npb_rollout_permutation: entries [first, first + count) must lie inside [0, N)");
+  if (!keys || !out) return fail(h, NPB_EINVAL, "npb_rollout_permutation: NULL keys or out");
+  if ((uintptr_t)out & 3u) return fail(h, NPB_EINVAL, "npb_rollout_permutation: a misaligned out: 4-byte aligned");
+  NPB_USE_DEVICE(h);
+  npb_launch_permutation((uint32_t)N, keys, first, count, out, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+const char *npb_minibatch_check(const npb_minibatch_desc_t *D, int n_plants, int t, int features_cells, int n_axes, int n_extras) {
+  if (!D) return "npb_rollout_minibatch: a NULL descriptor";
+  if (n_plants < 1) return "npb_rollout_minibatch: n_plants must be >= 1";
+  if (features_cells < 1) return "npb_rollout_minibatch: the features' stack must have cells (K * C >= 1)";
+  if (n_axes < 0 || n_extras < 0) return "npb_rollout_minibatch: a negative axis or extras count";
+  if (t < 1) return "npb_rollout_minibatch: nothing recorded yet (t == 0)";
+  if (D->unit != NPB_MINIBATCH_TRANSITION && D->unit != NPB_MINIBATCH_PLANT) return "npb_rollout_minibatch: an unknown unit";
+  if (D->type != NPB_ROLLOUT_F32 && D->type != NPB_ROLLOUT_F64) return "npb_rollout_minibatch: an unknown type";
+  const int64_t N = D->unit == NPB_MINIBATCH_PLANT ? (int64_t)n_plants : (int64_t)t * n_plants;
+  if (N > INT32_MAX) return "npb_rollout_minibatch: t * n_plants is beyond 2^31 - 1, what an index (int32) holds";
+  if (D->count < 1) return "npb_rollout_minibatch: count must be >= 1";
+  if (D->first < 0 || D->first > N - D->count) return "npb_rollout_minibatch: entries [first, first + count) must lie inside [0, N)";
+  if (!D->index) return "npb_rollout_minibatch: index is NULL";
+  if (D->act && n_axes == 0) return "npb_rollout_minibatch: an act output without axes (the rollout recorded no controls)";
+  if (D->extra && n_extras == 0) return "npb_rollout_minibatch: an extra output without extras";
+  if (D->adv_out && !D->adv) return "npb_rollout_minibatch: adv_out without adv";
+  if (D->ret_out && !D->ret) return "npb_rollout_minibatch: ret_out without ret";
+  if (D->moments && !D->adv_out) return "npb_rollout_minibatch: moments are set and adv_out, what they normalise, is NULL";
+  if (!(D->eps >= 0.0)) return "npb_rollout_minibatch: eps must be >= 0 (a NaN is not)";
+  if (D->max_blocks < 0) return "npb_rollout_minibatch: max_blocks must be >= 0";
+  if (((uintptr_t)D->obs | (uintptr_t)D->act | (uintptr_t)D->extra) & 15u) return "npb_rollout_minibatch: a misaligned obs, act or extra output: 16-byte aligned";
+  if ((uintptr_t)D->moments & 7u) return "npb_rollout_minibatch: misaligned moments: 8-byte aligned";
+  if (((uintptr_t)D->adv | (uintptr_t)D->ret | (uintptr_t)D->adv_out | (uintptr_t)D->ret_out) & (D->type == NPB_ROLLOUT_F64 ? 7u : 3u))
+    return "npb_rollout_minibatch: misaligned adv, ret, adv_out or ret_out: aligned to their element";
+  if ((uintptr_t)D->index & 3u) return "npb_rollout_minibatch: a misaligned index: 4-byte aligned";
+  return nullptr;
+}
+int npb_rollout_minibatch(NpbHandle *h, const npb_minibatch_desc_t *D, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->ro.n_final) return fail_who(h, "npb_rollout_minibatch", g_no_rollout);
+  const npb_rollout_t &R = h->ro;
+  if (const char *why = npb_minibatch_check(D, h->n_plants, R.t, R.cells, R.n_axes, R.D.n_extras)) return fail(h, NPB_EINVAL, why);
+  NPB_USE_DEVICE(h);
+  const npb_minibatch_src_t S = {R.D.obs, R.D.act, R.D.extra, R.t, h->n_plants, R.cells, R.n_axes, R.D.n_extras, R.obs_bytes, R.act_bytes};
+  npb_launch_minibatch(&S, D, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }

@@ -1691,11 +1691,134 @@ class BatchedPlantEnv:
         _lib.check(self.L.npb_rollout_advantages(self._h, ctypes.byref(d), self._stream()), self._h)
         ro["held"] = (values, last_value, final_values)      # (alive while the launch reads them)
         t = int(self.L.npb_rollout_steps(self._h))
+        ro["last"] = (adv[:t], ret[:t])      # (what ``rollout_moments`` and ``rollout_minibatches`` take by default)
         return adv[:t], ret[:t]
 
     def rollout_spec(self) -> dict:
         """the request as data: what ``nuclear_sim_amd.rollout.Recorder`` takes"""
         return self._on("_roll")["spec"]
+
+    _MB_DTYPES = {torch.float32: "float32", torch.float64: "float64"}
+
+    def _last_advantages(self, ro, advantages=None):
+        """``(adv, ret)`` a minibatch or the moments are taken of: the caller's pair, else what the last ``rollout_advantages`` formed"""
+        if advantages is None:
+            advantages = ro.get("last")
+            if advantages is None:
+                raise _lib.NpbError("no advantages formed yet: rollout_advantages() first, or pass advantages=(adv, ret)")
+        adv, ret = advantages
+        t = int(self.L.npb_rollout_steps(self._h))
+        for name, x in (("adv", adv), ("ret", ret)):
+            if not isinstance(x, torch.Tensor) or x.device != self.device or x.dtype != adv.dtype or x.dtype not in self._MB_DTYPES:
+                raise ValueError("%s must be a float32 or float64 tensor on %s, of adv's type" % (name, self.device))
+            if x.dim() != 2 or x.shape[1] != self.n or x.shape[0] < t or not x.is_contiguous():
+                raise ValueError("%s must be a contiguous [>= t, n] = [>= %d, %d] tensor, not %r" % (name, t, self.n, tuple(x.shape)))
+        return adv, ret, t
+
+    def rollout_moments(self, x=None, ddof: int = 1) -> torch.Tensor:
+        """``(count, mean, var, std)`` of ``x``, a contiguous [rows, cols] float32 or float64 device tensor (default: the advantages the
+        last ``rollout_advantages`` formed), as a device float64 [4] tensor: nothing is read back (npb_rollout_moments).  The order of
+        every addition is pinned -- rows in order down each column, then a tree of groups of 256 over the columns -- so the bits are
+        ``nuclear_sim_amd.rollout.moments``'s, whatever the launch geometry.  Any tensor will do: no rollout need be set for one given."""
+        if not hasattr(self.L, "npb_rollout_moments"):
+            raise _lib.NpbError("libnpb.so has no npb_rollout_moments: rebuild")
+        if x is None:
+            adv, _, t = self._last_advantages(self._on("_roll"))
+            x = adv[:t]
+        if not isinstance(x, torch.Tensor) or x.device != self.device or x.dim() != 2 or x.dtype not in self._MB_DTYPES or not x.is_contiguous():
+            raise ValueError("moments are taken of a contiguous [rows, cols] float32 or float64 tensor on %s" % (self.device,))
+        rows, cols = x.shape
+        if int(ddof) < 0 or rows * cols <= int(ddof):
+            raise ValueError("rows * cols = %d must exceed ddof = %d" % (rows * cols, int(ddof)))
+        with torch.cuda.device(self.device):
+            out = torch.zeros(4, dtype=torch.float64, device=self.device)
+        d = _lib.NpbMomentsDesc()
+        d.src, d.type, d.ddof, d.rows, d.cols, d.out = x.data_ptr(), _lib.ROLLOUT_DTYPES[self._MB_DTYPES[x.dtype]], int(ddof), rows, cols, out.data_ptr()
+        _lib.check(self.L.npb_rollout_moments(self._h, ctypes.byref(d), self._stream()), self._h)
+        self._moments_held = x      # (alive while the launches read it)
+        return out
+
+    def rollout_permutation(self, N: int, keys, first: int = 0, count: Optional[int] = None) -> torch.Tensor:
+        """entries ``first .. first + count`` of the permutation of range(N) under ``keys`` (``rollout.permutation_keys(seed, epoch)``)
+        as a device int32 tensor (npb_rollout_permutation): ``nuclear_sim_amd.rollout.permutation``, entry by entry"""
+        count = int(N) - int(first) if count is None else int(count)
+        k = (ctypes.c_uint32 * _lib.MINIBATCH_ROUNDS)(*[int(v) for v in keys])
+        with torch.cuda.device(self.device):
+            out = torch.zeros(max(count, 1), dtype=torch.int32, device=self.device)
+        _lib.check(self.L.npb_rollout_permutation(self._h, int(N), k, int(first), count, out.data_ptr(), self._stream()), self._h)
+        return out[:count]
+
+    def rollout_minibatches(self, batch_size, epochs: int = 1, seed: int = 0, first_epoch: int = 0, normalize: bool = True, eps: float = 1e-8,
+                            ddof: int = 1, unit: str = "transition", drop_last: bool = False, advantages=None, max_blocks: int = 0):
+        """Shuffled minibatches of the recorded slots, gathered on the device (npb_rollout_minibatch): a generator of dicts ``{"index",
+        "obs", "act", "extra", "adv", "ret", "epoch"}``, one launch each on the env's stream and no host synchronisation.
+        ``unit="transition"``: every epoch is a permutation of the t * n recorded cells; ``index`` [count] is the flat cell s * n + p and
+        ``obs`` [count, K, C], ``act`` [count, A], ``extra`` [count, E], ``adv``, ``ret`` [count] its rows.  ``unit="plant"`` (recurrent
+        policies): a permutation of the plants, every tensor time-major with the sequences whole, [t, count, ...].  The order of epoch e is
+        a function of ``(seed, e)`` alone (``rollout.permutation_keys``; epochs ``first_epoch .. first_epoch + epochs``), so an epoch is
+        resumed from three numbers.  ``normalize``: the advantages' moments are formed once (``rollout_moments``, ``ddof``) and ``adv`` is
+        ``((double)adv - mean) / (std + eps)``, narrowed once.  ``advantages``: ``(adv, ret)`` [>= t, n] device tensors of one type,
+        default what the last ``rollout_advantages`` returned.  A short last batch is yielded unless ``drop_last``.
+        THE YIELDED TENSORS ARE VIEWS OF BUFFERS THE ENV KEEPS, the same storage on every yield: use or copy a minibatch before asking for
+        the next.  ``act`` / ``extra`` are None where the rollout has none.  ``set_rollout(None)`` drops the buffers.
+        ``nuclear_sim_amd.rollout.minibatch`` is the same in numpy, bit for bit."""
+        ro = self._on("_roll")
+        if not hasattr(self.L, "npb_rollout_minibatch"):
+            raise _lib.NpbError("libnpb.so has no npb_rollout_minibatch: rebuild")
+        if unit not in _lib.MINIBATCH_UNITS:
+            raise ValueError("a minibatch's unit is 'transition' or 'plant', not %r" % (unit,))
+        B, epochs, first_epoch = int(batch_size), int(epochs), int(first_epoch)
+        if B < 1 or epochs < 0:
+            raise ValueError("batch_size must be >= 1 and epochs >= 0")
+        if not float(eps) >= 0.0:
+            raise ValueError("eps must be >= 0")
+        adv, ret, t = self._last_advantages(ro, advantages)
+        if t < 1:
+            raise _lib.NpbError("nothing recorded yet (t == 0)")
+        plant = unit == "plant"
+        N = self.n if plant else t * self.n
+        if N > rollout.N_MAX:
+            raise ValueError("t * n = %d is beyond 2^31 - 1, what an index holds" % N)
+        B = min(B, N)
+        moments = self.rollout_moments(adv[:t], ddof) if normalize else None
+        spec, tensors = ro["spec"], ro["tensors"]
+        (K, C), A, E = spec["stack"], spec["axes"], spec["extras"]
+        rows = B * t if plant else B
+        key = (B, rows, adv.dtype)
+        if ro.get("mb_key") != key:      # the buffers: one set, flat, as many rows as the largest minibatch has
+            with torch.cuda.device(self.device):
+                def zeros(cells, dtype):
+                    return torch.zeros(rows * cells, dtype=dtype, device=self.device)
+                ro["mb"] = {"index": torch.zeros(B, dtype=torch.int32, device=self.device), "obs": zeros(K * C, tensors["obs"].dtype),
+                            "act": zeros(A, tensors["act"].dtype) if A else None, "extra": zeros(E, torch.float32) if E else None,
+                            "adv": zeros(1, adv.dtype), "ret": zeros(1, adv.dtype)}
+            ro["mb_key"] = key
+        buf = ro["mb"]
+        d = _lib.NpbMinibatchDesc()
+        d.unit, d.type, d.eps, d.max_blocks = _lib.MINIBATCH_UNITS[unit], _lib.ROLLOUT_DTYPES[self._MB_DTYPES[adv.dtype]], float(eps), int(max_blocks)
+        d.adv, d.ret, d.moments = adv.data_ptr(), ret.data_ptr(), None if moments is None else moments.data_ptr()
+        d.index, d.obs, d.adv_out, d.ret_out = buf["index"].data_ptr(), buf["obs"].data_ptr(), buf["adv"].data_ptr(), buf["ret"].data_ptr()
+        d.act = None if buf["act"] is None else buf["act"].data_ptr()
+        d.extra = None if buf["extra"] is None else buf["extra"].data_ptr()
+
+        def view(x, count, *cells):
+            shape = ((t, count) if plant else (count,)) + cells
+            return None if x is None else x[:int(np.prod(shape))].view(shape)
+
+        def batches():
+            held = (adv, ret, moments)      # (alive while the launches read them)
+            for e in range(first_epoch, first_epoch + epochs):
+                d.keys[:] = [int(k) for k in rollout.permutation_keys(seed, e)]
+                for first in range(0, N, B):
+                    count = min(B, N - first)
+                    if count < B and drop_last:
+                        break
+                    d.first, d.count = first, count
+                    _lib.check(self.L.npb_rollout_minibatch(self._h, ctypes.byref(d), self._stream()), self._h)
+                    yield {"index": buf["index"][:count], "obs": view(buf["obs"], count, K, C), "act": view(buf["act"], count, A),
+                           "extra": view(buf["extra"], count, E), "adv": view(buf["adv"], count), "ret": view(buf["ret"], count), "epoch": e}
+            del held
+        return batches()
 
     def _order_buffers(self):
         """the buffers the perform_*_maintenance methods keep for their order columns, with the ``success`` column they all return"""

@@ -6,7 +6,11 @@ a restart the caller makes between two recorded steps.  The outcome of a transit
 truncation, and a truncation is due when the carried length reaches ``max_episode_steps``.
 
 ``advantages`` is the recurrence in float64, step by step, every operation rounded on its own; the device produces its bits.  It is the
-contract: no scan, no vectorisation along t."""
+contract: no scan, no vectorisation along t.
+
+``moments``, ``permutation_keys``, ``permutation`` and ``minibatch`` state what happens between the advantages and the optimiser
+(npb_rollout_moments, npb_rollout_permutation, npb_rollout_minibatch): the order of every addition of the moments is pinned, the shuffled
+order is a function of (seed, epoch, position) alone, and the device produces their bits too."""
 import numpy as np
 
 HORIZON_MAX, EXTRAS_MAX = 4096, 8
@@ -135,3 +139,160 @@ def advantages(reward, ended, final_row, values=None, last_value=None, final_val
         a_next = a
     with np.errstate(over="ignore"):
         return adv.astype(dtype), ret.astype(dtype)
+
+
+# ------------------------------------------------------------------------------------------------ between advantages() and the optimiser
+# What a PPO-style learner does with a finished rollout (npb_rollout_moments, npb_rollout_permutation, npb_rollout_minibatch): the
+# advantages' mean and standard deviation with the order of every addition pinned, a shuffled order that is a function of (seed, epoch, i)
+# alone -- no table, no sort --, and the gather of one minibatch.  The device produces these bits.
+TREE_WIDTH = 256      # the pairwise tree's fan-in: one workgroup
+ROUNDS = 6            # the Feistel network's rounds, one uint32 key each
+N_MAX = 2 ** 31 - 1   # entries a permutation can have: an index is an int32
+UNITS = {"transition": 0, "plant": 1}      # NPB_MINIBATCH_TRANSITION / NPB_MINIBATCH_PLANT
+
+
+def _tree(c: np.ndarray) -> np.float64:
+    """the pinned sum of a float64 vector: groups of 256 padded with +0.0, in each the halves 128, 64, ... 1 added onto each other, the
+    groups' results the next level's vector, until one value is left; a vector of one value is that value"""
+    c = np.asarray(c, dtype=np.float64)
+    while c.size > 1:
+        g = -(-c.size // TREE_WIDTH)
+        padded = np.zeros(g * TREE_WIDTH, dtype=np.float64)
+        padded[:c.size] = c
+        c = padded.reshape(g, TREE_WIDTH)
+        half = TREE_WIDTH // 2
+        while half >= 1:
+            c = c[:, :half] + c[:, half:2 * half]
+            half //= 2
+        c = c[:, 0]
+    return np.float64(c[0])
+
+
+def moments(x, ddof=1):
+    """``(count, mean, var, std)`` of ``x`` [rows, cols] (float32 or float64) as float64, the order of every addition pinned: a column's
+    rows are added in order into a double that starts at 0.0, the columns' sums go through ``_tree``; mean = that / count; a second pass
+    adds the rounded squares of ``(double)x - mean`` the same way, var = that / (count - ddof), std = sqrt(var).  Division and root are
+    IEEE, a NaN or an infinity propagates.  This is the contract: it is not restated as np.sum, whose order is numpy's own."""
+    x = np.asarray(x)
+    if x.ndim != 2 or x.dtype not in (np.float32, np.float64):
+        raise ValueError("moments are taken of a [rows, cols] float32 or float64 array")
+    rows, cols = x.shape
+    count, ddof = rows * cols, int(ddof)
+    if ddof < 0 or count <= ddof:
+        raise ValueError("rows * cols = %d must exceed ddof = %d" % (count, ddof))
+    with np.errstate(invalid="ignore", over="ignore"):
+        col = np.zeros(cols, dtype=np.float64)
+        for s in range(rows):
+            col += x[s].astype(np.float64)
+        mean = _tree(col) / np.float64(count)
+        col2 = np.zeros(cols, dtype=np.float64)
+        for s in range(rows):
+            d = x[s].astype(np.float64) - mean
+            col2 += d * d
+        var = _tree(col2) / np.float64(count - ddof)
+        std = np.sqrt(var)
+    return np.float64(count), mean, var, std
+
+
+_M64 = (1 << 64) - 1
+
+
+def _splitmix64(state: int):
+    """one step of splitmix64: the next state and its output"""
+    state = (state + 0x9E3779B97F4A7C15) & _M64
+    z = state
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return state, z ^ (z >> 31)
+
+
+def permutation_keys(seed, epoch) -> np.ndarray:
+    """the ROUNDS uint32 round keys of epoch ``epoch`` under ``seed`` (both taken modulo 2^64): a splitmix64 chain -- the first output
+    from the seed, xor the epoch, is the state the next ROUNDS outputs are drawn from; a key is the high word of an output"""
+    _, z = _splitmix64(int(seed) & _M64)
+    state = z ^ (int(epoch) & _M64)
+    keys = np.zeros(ROUNDS, dtype=np.uint32)
+    for r in range(ROUNDS):
+        state, z = _splitmix64(state)
+        keys[r] = z >> 32
+    return keys
+
+
+def _mix(h: np.ndarray) -> np.ndarray:
+    """murmur3's 32-bit finaliser, in uint32 arithmetic"""
+    h = h ^ (h >> np.uint32(16))
+    h = h * np.uint32(0x85EBCA6B)
+    h = h ^ (h >> np.uint32(13))
+    h = h * np.uint32(0xC2B2AE35)
+    return h ^ (h >> np.uint32(16))
+
+
+def permutation(N, keys, first=0, count=None) -> np.ndarray:
+    """entries ``first .. first + count`` (default: to the end) of a permutation of range(N), 1 <= N <= 2^31 - 1, as int32; each entry is a
+    function of its position alone.  b = max(bit_length(N - 1), 2), w = (b + 1) // 2; position i is split into L = i >> w and R = i & (2^w
+    - 1), ROUNDS times ``L, R = R, L ^ (mix(R ^ key[r]) & (2^w - 1))``, and the result is L << w | R: a bijection on [0, 2^(2w)).  While
+    the result is >= N the network is applied to it again (cycle walking): the walk from i < N stays on i's cycle, so it ends, and it is
+    a bijection on [0, N)."""
+    N = int(N)
+    if not 1 <= N <= N_MAX:
+        raise ValueError("a permutation has 1 .. 2^31 - 1 entries, not %r" % (N,))
+    keys = np.asarray(keys, dtype=np.uint32)
+    if keys.shape != (ROUNDS,):
+        raise ValueError("%d round keys, not %r" % (ROUNDS, keys.shape))
+    first = int(first)
+    count = N - first if count is None else int(count)
+    if first < 0 or count < 0 or first + count > N:
+        raise ValueError("entries [%d, %d) are not inside [0, %d)" % (first, first + count, N))
+    w = np.uint32((max((N - 1).bit_length(), 2) + 1) // 2)
+    mask = np.uint32((1 << int(w)) - 1)
+
+    def network(x):
+        L, R = x >> w, x & mask
+        for r in range(ROUNDS):
+            L, R = R, L ^ (_mix(R ^ keys[r]) & mask)
+        return (L << w) | R
+    with np.errstate(over="ignore"):
+        x = network(np.arange(first, first + count, dtype=np.uint32))
+        while True:
+            out = np.flatnonzero(x >= np.uint32(N))
+            if not out.size:
+                break
+            x[out] = network(x[out])
+    return x.astype(np.int32)
+
+
+def minibatch(arrays, t, adv, ret, keys, first, count, unit="transition", moments=None, eps=1e-8) -> dict:
+    """What npb_rollout_minibatch returns for entries ``first .. first + count`` of the epoch ``keys`` belong to.  ``arrays``: what
+    ``Recorder.arrays()`` / ``env.rollout()`` give, of which the first ``t`` slots count; ``adv``, ``ret``: [>= t, n].
+    ``unit="transition"``: a permutation of the t * n cells; ``index[j]`` is the flat cell s * n + p, and ``obs`` [count, K, C], ``act``
+    [count, A], ``extra`` [count, E], ``adv``, ``ret`` [count] are its rows.  ``unit="plant"``: a permutation of the n plants, every output
+    time-major with the plants' sequences whole: ``src[:t, index]``, [t, count, ...].  ``moments`` (count, mean, var, std): adv becomes
+    ``((double)adv - mean) / (std + eps)``, one subtraction, one addition and one IEEE division in double, narrowed once to adv's type."""
+    if unit not in UNITS:
+        raise ValueError("a minibatch's unit is 'transition' or 'plant', not %r" % (unit,))
+    t = int(t)
+    if t < 1:
+        raise ValueError("nothing recorded (t == 0)")
+    if not float(eps) >= 0.0:
+        raise ValueError("eps must be >= 0")
+    obs = np.asarray(arrays["obs"])[:t]
+    n = obs.shape[1]
+    adv, ret = np.asarray(adv)[:t], np.asarray(ret)[:t]
+    N = t * n if unit == "transition" else n
+    if count < 1:
+        raise ValueError("a minibatch has at least one entry")
+    index = permutation(N, keys, first, count)
+    if unit == "transition":
+        def take(x):
+            return None if x is None or x.shape[2:] == (0,) else x[:t].reshape((t * n,) + x.shape[2:])[index]
+    else:
+        def take(x):
+            return None if x is None or x.shape[2:] == (0,) else x[:t][:, index]
+    a = take(adv)
+    if moments is not None:
+        mean, std = np.float64(moments[1]), np.float64(moments[3])
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            a = ((a.astype(np.float64) - mean) / (std + np.float64(eps))).astype(adv.dtype)
+    act, extra = arrays.get("act"), arrays.get("extra")
+    return {"index": index, "obs": take(obs), "act": take(None if act is None else np.asarray(act)),
+            "extra": take(None if extra is None else np.asarray(extra)), "adv": a, "ret": take(ret)}
