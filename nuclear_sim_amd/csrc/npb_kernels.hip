@@ -402,20 +402,22 @@ struct npd_maint_screen_t {
   uint32_t want_gt, want_lt, want_eq, want_near, want_far;    /* bit q: row q fires on value > / < / == threshold, |value - threshold| < / >= 0.001 */
 };
 struct npd_maint_rule_consts_t { npb_params_t P; npb_maint_table_t T; npd_maint_screen_t S; npd_maint_log_t L; };
-/* one event site of a wave: the lanes with `want` take consecutive slots of the log through one device-scope atomic of the
- * wave's first active lane (ballot, mbcnt, readfirstlane).  The cursor counts every event; a slot at or past the capacity is
- * not written. */
+#include "npd_record_log.h"
+/* one event site of a wave, possibly inside divergent code: the lanes with `want` take slots of the log (npd_record_log.h); the cursor
+ * counts every event, and a slot at or past the capacity is not written */
 __device__ __forceinline__ void npd_maint_log(const npd_maint_log_t &L, bool want, const npb_maint_event_t &e) {
-  const uint64_t lanes = __ballot(want);
-  if (lanes == 0) return;
-  const uint64_t active = __ballot(1);
-  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(lanes >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lanes, 0u));
-  const bool first = __builtin_amdgcn_mbcnt_hi((uint32_t)(active >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)active, 0u)) == 0;
-  uint32_t base = 0;
-  if (first) base = __hip_atomic_fetch_add(L.cursor, (uint32_t)__popcll(lanes), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-  const uint32_t slot = base + rank;
+  const npd_log_slots_t s = npd_log_reserve(L.cursor, want);
+  if (!s.rows) return;
+  const uint32_t slot = npd_log_slot(s);
   if (want && slot < (uint32_t)L.capacity) L.records[slot] = e;
+}
+/* the tail of the npb_operator_*_maint_kernel: one record per successful order, stamped with the plant's clock t, one atomic per wave.
+ * The caller guards it with `if (L.cursor)`: a run without a log (npb_set_maintenance_log) does not load the clock */
+__device__ __forceinline__ void npd_maint_log_operator(const npd_maint_log_t &L, bool ok, size_t p, double t, int unit, int action, int kind, int bearing = 0) {
+  npb_maint_event_t ev = {};
+  ev.time = t; ev.created = t; ev.planned_start = t; ev.plant = (int32_t)p;
+  ev.pump = (uint8_t)unit; ev.action = (uint8_t)action; ev.kind = (uint8_t)kind; ev.bearing = (uint8_t)bearing;
+  npd_maint_log(L, ok, ev);
 }
 /* does pump k of this lane's plant have a crossed threshold outside its cooldown?  (StateManager._check_maintenance_thresholds up
  * to the point where a violation is recorded, state_manager.py:1307-1369) */
@@ -1010,14 +1012,9 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_operator_maint_kernel(npd_operat
       NPD_STORE(PUMP, npb_pump_t, pm, k);
     }
   }
-  if (L.cursor) {      /* the event log (npb_set_maintenance_log): one record per successful order, one atomic per wave */
-    const double t = NPD_F64_COL(PRIM, npb_prim_t, sim_time, 0);
-    npb_maint_event_t ev = {};
-    ev.time = t; ev.created = t; ev.planned_start = t; ev.plant = (int32_t)p;
-    ev.pump = (uint8_t)pump; ev.action = (uint8_t)action; ev.kind = NPB_MAINT_EVENT_OPERATOR;
-    ev.bearing = action == NPB_MA_BEARING_REPLACEMENT ? (uint8_t)bearing : 0;
-    npd_maint_log(L, ok, ev);
-  }
+  if (L.cursor)
+    npd_maint_log_operator(L, ok, p, NPD_F64_COL(PRIM, npb_prim_t, sim_time, 0), pump, action, NPB_MAINT_EVENT_OPERATOR,
+                           action == NPB_MA_BEARING_REPLACEMENT ? bearing : 0);
 }
 
 /* operator-ordered maintenance of steam generators and condenser (npb_perform_component_maintenance): perform_maintenance(type, **kwargs)
@@ -1094,13 +1091,7 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_operator_component_maint_kernel(
       NPD_STORE(COND, npb_cond_t, cd, 0);
     }
   }
-  if (L.cursor) {      /* the event log (npb_set_maintenance_log): one record per successful order, one atomic per wave */
-    const double t = NPD_F64_COL(PRIM, npb_prim_t, sim_time, 0);
-    npb_maint_event_t ev = {};
-    ev.time = t; ev.created = t; ev.planned_start = t; ev.plant = (int32_t)p;
-    ev.pump = (uint8_t)unit; ev.action = (uint8_t)action; ev.kind = NPB_MAINT_EVENT_OPERATOR_COMPONENT;
-    npd_maint_log(L, ok, ev);
-  }
+  if (L.cursor) npd_maint_log_operator(L, ok, p, NPD_F64_COL(PRIM, npb_prim_t, sim_time, 0), unit, action, NPB_MAINT_EVENT_OPERATOR_COMPONENT);
 }
 
 /* operator-ordered maintenance of the turbine (npb_perform_turbine_maintenance): perform_maintenance(type) of the turbine, one of its
@@ -1160,13 +1151,7 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_operator_turbine_maint_kernel(np
       }
     }
   }
-  if (L.cursor) {      /* the event log (npb_set_maintenance_log): one record per successful order, one atomic per wave */
-    const double t = NPD_F64_COL(PRIM, npb_prim_t, sim_time, 0);
-    npb_maint_event_t ev = {};
-    ev.time = t; ev.created = t; ev.planned_start = t; ev.plant = (int32_t)p;
-    ev.pump = (uint8_t)unit; ev.action = (uint8_t)action; ev.kind = NPB_MAINT_EVENT_OPERATOR_TURBINE;
-    npd_maint_log(L, ok, ev);
-  }
+  if (L.cursor) npd_maint_log_operator(L, ok, p, NPD_F64_COL(PRIM, npb_prim_t, sim_time, 0), unit, action, NPB_MAINT_EVENT_OPERATOR_TURBINE);
 }
 
 #ifndef NPB_BUILD_F32
@@ -1765,14 +1750,10 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_episode_records_kernel(int n_pla
   }
   const bool ended = terminated || truncated;
   if (!__any(ended)) return;
-  /* slots: the ended lanes of the wave take consecutive ones in plant order, one atomic for the wave */
-  const uint64_t rows = __ballot(ended);
-  const int lane = threadIdx.x, leader = __ffsll((unsigned long long)rows) - 1;
-  uint32_t base = 0;
-  if (lane == leader) base = __hip_atomic_fetch_add(R.D.cursor, (uint32_t)__popcll(rows), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  base = (uint32_t)__shfl((int)base, leader);
+  const npd_log_slots_t s = npd_log_reserve(R.D.cursor, ended);      /* the ended lanes' slots (npd_record_log.h) */
+  const int lane = threadIdx.x;
   const uint32_t cap = (uint32_t)R.D.capacity;
-  const uint32_t slot = base + (uint32_t)__popcll(rows & ((1ull << lane) - 1ull));
+  const uint32_t slot = npd_log_slot(s);
   const bool store = ended && slot < cap;
   if (store) {
     R.D.plant[slot] = (int32_t)p;
@@ -1789,8 +1770,8 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_episode_records_kernel(int n_pla
 #pragma unroll
     for (int k = 0; k < NPB_OBS_DIM; k++) {
       const int idx = k * NPB_WAVE + lane, r = idx / NPB_OBS_DIM, c = idx % NPB_OBS_DIM;
-      const uint32_t slot_r = base + (uint32_t)__popcll(rows & ((1ull << r) - 1ull));
-      if (((rows >> r) & 1u) && slot_r < cap) R.D.final_obs[(size_t)slot_r * NPB_OBS_DIM + c] = obs[block_base * NPB_OBS_DIM + idx];
+      const uint32_t slot_r = npd_log_slot(s, r);
+      if (((s.rows >> r) & 1u) && slot_r < cap) R.D.final_obs[(size_t)slot_r * NPB_OBS_DIM + c] = obs[block_base * NPB_OBS_DIM + idx];
     }
   }
   if (!ended) return;

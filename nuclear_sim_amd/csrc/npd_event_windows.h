@@ -7,7 +7,7 @@
  * bookkeeping column and every trigger source is read and written with consecutive lanes on consecutive plants.  A wave first asks for
  * everything it reads and stores afterwards (the kernel is bound by latency, not by bytes).  The descriptors (columns,
  * triggers) are uniform over the launch: scalar loads.  A wave none of whose lanes captures ends there.  Otherwise its capturing lanes take
- * consecutive slots in plant order with one atomic add (as npb_episode_records_kernel hands them out), and for each of them in turn all 64
+ * consecutive slots in plant order with one atomic add (npd_record_log.h), and for each of them in turn all 64
  * lanes copy its window: the reads walk the ring with the plant stride (one line per element, whoever reads them), the stores into
  * `values` are contiguous.  No LDS.  Included behind every other kernel of npb_kernels.hip and compiled with it for either storage type: it
  * reads the arena. */
@@ -85,15 +85,10 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_event_windows_kernel(const npd_r
     }
     W.due[p] = due;
   }
-  const uint64_t rows = __ballot(capture);
-  if (!rows) return;
-  /* slots: the capturing lanes of the wave take consecutive ones in plant order, one atomic for the wave */
-  const int leader = __ffsll((unsigned long long)rows) - 1;
-  uint32_t base = 0;
-  if (lane == leader) base = __hip_atomic_fetch_add(W.D.cursor, (uint32_t)__popcll(rows), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  base = (uint32_t)__shfl((int)base, leader);
+  const npd_log_slots_t s = npd_log_reserve(W.D.cursor, capture);      /* the capturing lanes' slots (npd_record_log.h) */
+  if (!s.rows) return;
   const uint32_t cap = (uint32_t)W.D.capacity;
-  const uint32_t slot = base + (uint32_t)__popcll(rows & ((1ull << lane) - 1ull));
+  const uint32_t slot = npd_log_slot(s);
   if (capture && slot < cap) {
     W.D.plant[slot] = (int32_t)p;
     W.D.episode[slot] = episode;
@@ -108,9 +103,9 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_event_windows_kernel(const npd_r
   }
   /* the windows, one captured lane after the other, all 64 lanes copying: row k of a record is sample a_step + k - pre */
   const int cells = H * stride;
-  for (uint64_t left = rows; left; left &= left - 1) {
+  for (uint64_t left = s.rows; left; left &= left - 1) {
     const int r = __ffsll((unsigned long long)left) - 1;
-    const uint32_t slot_r = base + (uint32_t)__popcll(rows & ((1ull << r) - 1ull));
+    const uint32_t slot_r = npd_log_slot(s, r);
     if (slot_r >= cap) break;      /* (slots rise with the lane: the rest did not fit either) */
     const int first = __shfl(a_step, r) - W.pre, lo = W.pre - __shfl(a_n_pre, r), hi = W.pre + __shfl(a_n_post, r);
     const double *from = W.ring + (block_base + (size_t)r);

@@ -19,7 +19,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, rollout
+from . import _lib, recordlog, rollout
 from .schema import SCHEMA
 
 
@@ -697,13 +697,9 @@ class BatchedPlantEnv:
         from . import maintlog
         nbytes = int(self.L.npb_maint_event_bytes())
         assert nbytes == maintlog.EVENT_DTYPE.itemsize, (nbytes, maintlog.EVENT_DTYPE.itemsize)
-        with torch.cuda.device(self.device):
-            records = torch.zeros(max(cap, 1) * nbytes, dtype=torch.uint8, device=self.device)
-            cursor = torch.zeros(1, dtype=torch.int32, device=self.device)     # a uint32 on the device
-        _lib.check(self.L.npb_set_maintenance_log(self._h, self._p(records), cap, self._p(cursor)), self._h)
-        # the drain's landing place: pinned host memory, so that a drain is a DMA copy rather than a staged one
-        self._mlog = {"records": records, "cursor": cursor, "capacity": cap, "host": torch.empty(records.numel(), dtype=torch.uint8, pin_memory=True),
-                      "host_cursor": torch.empty(1, dtype=torch.int32, pin_memory=True)}
+        log = recordlog.allocate(self.device, cap, [("records", (max(cap, 1), nbytes), torch.uint8, 0)])      # (capacity 0 still has a buffer to point at)
+        _lib.check(self.L.npb_set_maintenance_log(self._h, self._p(log["dev"]["records"]), cap, self._p(log["cursor"])), self._h)
+        self._mlog = log
         ms = self._msum
         if ms is not None:      # a summary that consumed a staging log of its own now folds the caller's log, and leaves it to the caller
             ms["desc"].consume = 0
@@ -712,32 +708,17 @@ class BatchedPlantEnv:
             ms["consume"] = False
 
     def maintenance_log_records(self, clear: bool = True, allow_overflow: bool = False) -> np.ndarray:
-        """Drain the log on the env's stream: the records (numpy, ``maintlog.EVENT_DTYPE``) in the device's order.  An overflowed
-        log raises, naming how many events were dropped, and is left as it is, unless ``allow_overflow``."""
+        """Drain the log on the env's stream: the records (numpy, ``maintlog.EVENT_DTYPE``) in the device's order.  A log past its
+        capacity raises, naming how many events were dropped, and is left as it is, unless ``allow_overflow``."""
         from . import maintlog
         ms = self._msum
         if ms is not None and ms["consume"]:
             raise _lib.NpbError("the maintenance summary consumes the log (enable_maintenance_summary's staging ring): there is nothing to "
                                 "drain; enable_maintenance_summary(..., keep_log=True) keeps the records")
-        ml = self._on("_mlog")
-        stream = torch.cuda.current_stream(self.device)
-        ml["host_cursor"].copy_(ml["cursor"], non_blocking=True)
-        stream.synchronize()
-        count = int(ml["host_cursor"][0]) & 0xFFFFFFFF
-        cap = ml["capacity"]
-        if count > cap and not allow_overflow:
-            raise _lib.NpbError("maintenance log overflowed: %d events, capacity %d, %d dropped (enable_maintenance_log with a larger "
-                                "capacity, drain more often, or pass allow_overflow=True)" % (count, cap, count - cap))
-        nb = min(count, cap) * maintlog.EVENT_DTYPE.itemsize
-        if nb:
-            ml["host"][:nb].copy_(ml["records"][:nb], non_blocking=True)
-            stream.synchronize()
-        rec = ml["host"][:nb].numpy().view(maintlog.EVENT_DTYPE).copy()
-        if clear:
-            ml["cursor"].zero_()
-            if ms is not None:      # the summary has folded what was drained: its mark goes back with the cursor
-                ms["words"][0].zero_()
-        return rec
+        raw = recordlog.drain(self._on("_mlog"), self.device, "maintenance log", "events", "enable_maintenance_log", clear, allow_overflow)
+        if clear and ms is not None:      # the summary has folded what was drained: its mark goes back with the cursor
+            ms["words"][0].zero_()
+        return raw["records"].reshape(-1).view(maintlog.EVENT_DTYPE)
 
     def maintenance_log(self, clear: bool = True, allow_overflow: bool = False) -> Dict[str, np.ndarray]:
         """``maintenance_log_records`` as columns sorted by (plant, time, completion before creation, pump), named as the
@@ -875,33 +856,29 @@ class BatchedPlantEnv:
         n_keys = len(self._msum["keys"]) if summary else 0
         d = _lib.NpbEpisodeRecordsDesc()
         d.capacity, d.clear_summary = cap, int(clear_summary)
-        dev, host = {}, {}
+        log = recordlog.allocate(self.device, cap)
 
-        def column(name, shape, dtype, desc=d, member=None):
-            dev[name] = torch.zeros(shape, dtype=dtype, device=self.device)
-            host[name] = torch.empty(shape, dtype=dtype, pin_memory=True)      # the drain's landing place, as the maintenance log's
-            setattr(desc, member or name, dev[name].data_ptr())
-        with torch.cuda.device(self.device):
-            for name, np_type in _lib.EPISODE_RECORD_COLUMNS:      # (uint32 trip flags travel as int32 bits)
-                column(name, (cap,), torch.float64 if np_type is np.float64 else torch.int32)
-            if final_obs:
-                column("final_obs", (cap, 22), torch.float64)
-            if summary:
-                for name in ("first_created", "first_completed"):
-                    column(name, (n_keys, cap), torch.float64)
-                for name in ("n_created", "n_completed"):
-                    column(name, (n_keys, cap), torch.int32)
-            cursor = torch.zeros(1, dtype=torch.int32, device=self.device)     # a uint32 on the device
-            rs = None
-            if stats or clear_stats:      # the record-side columns of the statistics, as "stat_<name>"
-                rs = _lib.NpbEpisodeRecordStatsDesc()
-                rs.clear = int(clear_stats)
-                if stats:
-                    for name in cst["stats"] + ("n_samples",):
-                        int_table = name in ("n_beyond", "n_samples")
-                        column("stat_" + name, (cap,) if name == "n_samples" else (len(cst["order"]), cap), torch.int32 if int_table else torch.float64,
-                               desc=rs, member=name)
-        d.cursor = cursor.data_ptr()
+        def column(name, shape, dtype, slot_axis=0, desc=d, member=None):      # (a table's records lie along its last axis)
+            setattr(desc, member or name, recordlog.add_column(log, name, shape, dtype, slot_axis).data_ptr())
+        for name, np_type in _lib.EPISODE_RECORD_COLUMNS:      # (uint32 trip flags travel as int32 bits)
+            column(name, (cap,), torch.float64 if np_type is np.float64 else torch.int32)
+        if final_obs:
+            column("final_obs", (cap, 22), torch.float64)
+        if summary:
+            for name in ("first_created", "first_completed"):
+                column(name, (n_keys, cap), torch.float64, -1)
+            for name in ("n_created", "n_completed"):
+                column(name, (n_keys, cap), torch.int32, -1)
+        rs = None
+        if stats or clear_stats:      # the record-side columns of the statistics, as "stat_<name>"
+            rs = _lib.NpbEpisodeRecordStatsDesc()
+            rs.clear = int(clear_stats)
+            if stats:
+                for name in cst["stats"] + ("n_samples",):
+                    int_table, per_column = name in ("n_beyond", "n_samples"), name != "n_samples"
+                    column("stat_" + name, (len(cst["order"]), cap) if per_column else (cap,), torch.int32 if int_table else torch.float64,
+                           -1 if per_column else 0, desc=rs, member=name)
+        d.cursor = log["cursor"].data_ptr()
         _lib.check(self.L.npb_set_episode_records(self._h, ctypes.byref(d)), self._h)
         self._erec = None      # (new record columns: the handle has dropped the statistics columns of the old ones with them)
         if rs is None:
@@ -913,8 +890,7 @@ class BatchedPlantEnv:
             except _lib.NpbError:
                 self.L.npb_set_episode_records(self._h, None)
                 raise
-        self._erec = {"desc": d, "dev": dev, "host": host, "cursor": cursor, "host_cursor": torch.empty(1, dtype=torch.int32, pin_memory=True),
-                      "capacity": cap, "n_keys": n_keys, "stats": rs, "stat_order": list(cst["order"]) if stats else None}
+        self._erec = dict(log, desc=d, n_keys=n_keys, stats=rs, stat_order=list(cst["order"]) if stats else None)
         self._record_task_cause()
 
     def _record_task_cause(self) -> None:
@@ -924,9 +900,7 @@ class BatchedPlantEnv:
         if er is None or self._task is None:
             return
         if "cause" not in er["dev"]:
-            with torch.cuda.device(self.device):
-                er["dev"]["cause"] = torch.zeros(er["capacity"], dtype=torch.int32, device=self.device)      # (uint32 bits travel as int32)
-            er["host"]["cause"] = torch.empty(er["capacity"], dtype=torch.int32, pin_memory=True)
+            recordlog.add_column(er, "cause", (er["capacity"],), torch.int32)      # (uint32 bits travel as int32)
         _lib.check(self.L.npb_set_episode_record_task(self._h, self._p(er["dev"]["cause"])), self._h)
 
     def _drop_record_task_cause(self) -> None:
@@ -934,7 +908,7 @@ class BatchedPlantEnv:
         er = self._erec
         if er is not None and "cause" in er["dev"]:
             _lib.check(self.L.npb_set_episode_record_task(self._h, None), self._h)
-            del er["dev"]["cause"], er["host"]["cause"]
+            recordlog.drop_column(er, "cause")
 
     def disable_episode_records(self) -> None:
         """episode records off; the buffers are released"""
@@ -946,32 +920,11 @@ class BatchedPlantEnv:
         (steps since the records were enabled, 0 = the first), ``ret``, ``end_time`` (plant minutes); with ``final_obs``
         ``final_observation`` [m, 22]; with ``summary`` ``first_created`` / ``first_completed`` (float64, +inf = never) and ``n_created`` /
         ``n_completed`` (int32), [m, n_keys]; with ``stats`` ``stat_min`` ... (the tables ``enable_column_stats`` keeps) [m, n_cols] and
-        ``stat_n_samples``; while a task is set (``set_task``) ``cause`` (uint32: the rules that ended the episode, 0 = none did).  An
-        overflowed log raises, naming how many episodes were dropped, and is left as it is,
+        ``stat_n_samples``; while a task is set (``set_task``) ``cause`` (uint32: the rules that ended the episode, 0 = none did).  A
+        log past its capacity raises, naming how many episodes were dropped, and is left as it is,
         unless ``allow_overflow`` (which of one step's episodes fitted is then not defined)."""
         er = self._on("_erec")
-        stream = torch.cuda.current_stream(self.device)
-        er["host_cursor"].copy_(er["cursor"], non_blocking=True)
-        stream.synchronize()
-        count = int(er["host_cursor"][0]) & 0xFFFFFFFF
-        cap = er["capacity"]
-        if count > cap and not allow_overflow:
-            raise _lib.NpbError("episode records overflowed: %d episodes, capacity %d, %d dropped (enable_episode_records with a larger "
-                                "capacity, drain more often, or pass allow_overflow=True)" % (count, cap, count - cap))
-        m = min(count, cap)
-        raw = {}
-        if m:
-            for name, t in er["dev"].items():
-                if t.dim() == 2 and name != "final_obs":
-                    er["host"][name][:, :m].copy_(t[:, :m], non_blocking=True)
-                else:
-                    er["host"][name][:m].copy_(t[:m], non_blocking=True)
-            stream.synchronize()
-        for name, t in er["host"].items():
-            a = t.numpy()
-            raw[name] = (a[:, :m].T if (a.ndim == 2 and name != "final_obs") else a[:m]).copy()
-        if clear:
-            er["cursor"].zero_()
+        raw = recordlog.drain(er, self.device, "episode records", "episodes", "enable_episode_records", clear, allow_overflow)
         order = np.lexsort((raw["plant"], raw["step"]))
         out = {name: raw[name][order] for name, _ in _lib.EPISODE_RECORD_COLUMNS}
         out["trip_flags"] = out["trip_flags"].view(np.uint32)
@@ -1209,19 +1162,14 @@ class BatchedPlantEnv:
             trig[k].mode, trig[k].mask, trig[k].direction, trig[k].limit = _lib.TRIGGER_MODES[T["mode"]], T["mask"], T["direction"], T["limit"]
         d.n_triggers, d.triggers = nt, trig
         d.pre, d.post, d.capacity = req["pre"], req["post"], cap
-        dev, host = {}, {}
-        with torch.cuda.device(self.device):
-            shapes = [(name, (cap,), torch.int32) for name in _lib.EVENT_WINDOW_WORDS + ("fired",)]      # (the uint32 fired set travels as int32 bits)
-            shapes += [("time", (cap,), torch.float64), ("times", (cap, H), torch.float64), ("values", (cap, H, n_cols), torch.float64)]
-            for name, shape, dtype in shapes:
-                dev[name] = torch.zeros(shape, dtype=dtype, device=self.device)
-                host[name] = torch.empty(shape, dtype=dtype, pin_memory=True)      # the drain's landing place, as the episode records'
-                setattr(d, name, dev[name].data_ptr())
-            cursor = torch.zeros(1, dtype=torch.int32, device=self.device)     # a uint32 on the device
-        d.cursor = cursor.data_ptr()
+        shapes = [(name, (cap,), torch.int32, 0) for name in _lib.EVENT_WINDOW_WORDS + ("fired",)]      # (the uint32 fired set travels as int32 bits)
+        shapes += [("time", (cap,), torch.float64, 0), ("times", (cap, H), torch.float64, 0), ("values", (cap, H, n_cols), torch.float64, 0)]
+        log = recordlog.allocate(self.device, cap, shapes)
+        for name, t in log["dev"].items():
+            setattr(d, name, t.data_ptr())
+        d.cursor = log["cursor"].data_ptr()
         _lib.check(self.L.npb_set_event_windows(self._h, ctypes.byref(d)), self._h)
-        self._ewin = dict(self._reading(req, buffers), desc=d, keep=keep + (trig,), dev=dev, host=host, cursor=cursor,
-                          host_cursor=torch.empty(1, dtype=torch.int32, pin_memory=True), capacity=cap, order=req["order"],
+        self._ewin = dict(self._reading(req, buffers), **log, desc=d, keep=keep + (trig,), order=req["order"],
                           columns=list(columns), pre=req["pre"], post=req["post"], triggers=req["numpy"],
                           bytes=int(self.L.npb_event_windows_bytes(ctypes.byref(d), self.n)))
 
@@ -1230,26 +1178,11 @@ class BatchedPlantEnv:
         ``plant``, ``episode``, ``trigger`` (the lowest trigger that fired), ``step`` (the trigger's step since the windows were enabled,
         0 = the first), ``n_pre``, ``n_post``, ``flags``, ``retriggers`` (int32), ``fired`` (uint32: every trigger that fired on that
         step), ``time`` (the plant clock at the trigger), ``times`` [m, H], ``values`` [m, H, n_cols] in the order of ``columns`` (row
-        ``pre`` is the trigger sample; rows outside ``[pre - n_pre, pre + n_post]`` are NaN) and ``early`` = ``flags & 1``.  An
-        overflowed log raises, naming how many captures were dropped, and is left as it is, unless ``allow_overflow`` (which of one
+        ``pre`` is the trigger sample; rows outside ``[pre - n_pre, pre + n_post]`` are NaN) and ``early`` = ``flags & 1``.  A
+        log past its capacity raises, naming how many captures were dropped, and is left as it is, unless ``allow_overflow`` (which of one
         step's captures fitted is then not defined)."""
         ew = self._on("_ewin")
-        stream = torch.cuda.current_stream(self.device)
-        ew["host_cursor"].copy_(ew["cursor"], non_blocking=True)
-        stream.synchronize()
-        count = int(ew["host_cursor"][0]) & 0xFFFFFFFF
-        cap = ew["capacity"]
-        if count > cap and not allow_overflow:
-            raise _lib.NpbError("event windows overflowed: %d captures, capacity %d, %d dropped (enable_event_windows with a larger "
-                                "capacity, drain more often, or pass allow_overflow=True)" % (count, cap, count - cap))
-        m = min(count, cap)
-        if m:
-            for name, t in ew["dev"].items():
-                ew["host"][name][:m].copy_(t[:m], non_blocking=True)
-            stream.synchronize()
-        raw = {name: t.numpy()[:m].copy() for name, t in ew["host"].items()}
-        if clear:
-            ew["cursor"].zero_()
+        raw = recordlog.drain(ew, self.device, "event windows", "captures", "enable_event_windows", clear, allow_overflow)
         order = np.lexsort((raw["plant"], raw["step"] + raw["n_post"]))
         out = {name: np.ascontiguousarray(a[order]) for name, a in raw.items()}
         out["fired"] = out["fired"].view(np.uint32)
