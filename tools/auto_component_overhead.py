@@ -1,7 +1,6 @@
 """What the automatic maintenance of steam generators and condenser (npb_set_component_maintenance) costs per step on BASELINE config 4.
 
-action_test("oil_top_off", range(n), dt = 5) at 32 768 and 65 536 plants, ONE handle per size throughout (where an arena lands in
-physical memory moves the step time from one handle to the next: npb_api.hip, probe_placement); the feature is switched on and off on
+action_test("oil_top_off", range(n), dt = 5) at 32 768 and 65 536 plants, ONE handle per size throughout; the feature is switched on and off on
 that handle through the C ABI.  After the usual preconditioning (untimed steps until the clocks have settled) every timed block replays
 the SAME simulated interval: restore(), the same pre-drawn heat-source noise rows, `--warm` untimed steps, then `--block` steps, each
 bracketed by its own pair of events.  The cases, in an order that rotates from round to round:
@@ -16,12 +15,13 @@ pumps_in_step.  One JSON line, also written to --out.  The kernels' own times: r
 """
 import argparse
 import ctypes
-import json
 import os
 import sys
 
 import numpy as np
 import torch
+
+from overhead_harness import write_line
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -61,6 +61,7 @@ def measure(n, a):
             poke()
         for t in range(a.warm):
             env.step(power_setpoint=sp, noise_z=z[t])
+        # (not the harness's time_steps: every launch has its own pair of events, and the block one synchronise at its end)
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.block)]
         for k in range(a.block):
             ev[k][0].record()
@@ -107,11 +108,7 @@ def main():
     a = ap.parse_args()
     res = {"workload": "action_test('oil_top_off', range(n), dt=5), fp64 storage", "block": a.block, "warm": a.warm, "rounds": a.rounds,
            "device": torch.cuda.get_device_name(0), "sizes": {str(n): measure(n, a) for n in a.sizes}}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    write_line(res, a.out)
 
 
 if __name__ == "__main__":

@@ -13,13 +13,13 @@ Prints one JSON line (per-step time in us: median, quartiles, min, max over the 
 The episode kernel's own time: run this under `rocprofv3 --kernel-trace --stats -- python tools/autoreset_overhead.py --rounds 2`.
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import torch
+
+from overhead_harness import head, stats, time_steps, write_line
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -89,14 +89,7 @@ def main():
             set_autoreset(True, 1)
 
     def run_block(name, steps):
-        step = composed_step if name == "composed_1pct" else env.step
-        a_ev, b_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a_ev.record(stream)
-        for _ in range(steps):
-            step()
-        b_ev.record(stream)
-        b_ev.synchronize()
-        return a_ev.elapsed_time(b_ev) * 1e3 / steps     # us per step
+        return time_steps(stream, composed_step if name == "composed_1pct" else env.step, steps)
 
     setups = ["off", "on_idle", "on_1pct", "composed_1pct", "on_all"]
     # warm-up: >= 200 launches of every setup's kernels
@@ -110,38 +103,23 @@ def main():
         _, _, d, info = env.step()
         resets.append(int(((d != 0) | (info["truncated"] != 0)).sum().item()))
     times = {s: [] for s in setups}
-    for r in range(a.rounds):
+    for r in range(a.rounds):      # (not the harness's rotation: on_all, a full arena copy per step, runs every second round only)
         for name in setups:
             if name == "on_all" and r % 2:
                 continue
             prepare(name)
             times[name].append(run_block(name, a.block))
-    torch.cuda.synchronize(dev)
-
-    def stats(v):
-        v = np.asarray(v)
-        return {"median_us": float(np.median(v)), "p25_us": float(np.percentile(v, 25)), "p75_us": float(np.percentile(v, 75)),
-                "min_us": float(v.min()), "max_us": float(v.max()), "blocks": int(v.size)}
 
     S = {s: stats(v) for s, v in times.items()}
     off = S["off"]["median_us"]
-    try:
-        head = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        head = None
     res = {"what": "per-step time of npb_step with and without same-step autoreset, one handle", "n_plants": n,
            "device": torch.cuda.get_device_name(dev), "storage": env.storage, "step_kernel": env.last_step_kernel(),
            "block_steps": a.block, "rounds": a.rounds, "max_episode_steps_1pct": MAX,
            "resets_per_step_1pct": {"mean": float(np.mean(resets)), "min": int(min(resets)), "max": int(max(resets))},
            "setups": S,
            "overhead_vs_off_pct": {s: 100.0 * (S[s]["median_us"] / off - 1.0) for s in setups if s != "off"},
-           "head": head}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+           "head": head(ROOT)}
+    write_line(res, a.out)
     env.close()
 
 

@@ -13,13 +13,13 @@ Prints one JSON line (per-step time in us: median, quartiles, min, max over the 
 The episode kernels' own time: run this under `rocprofv3 --kernel-trace --stats -- python tools/bank_autoreset_overhead.py --rounds 2`.
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import torch
+
+from overhead_harness import head, stats, time_steps, write_line
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -78,13 +78,7 @@ def main():
             set_autoreset(True, 1)
 
     def run_block(steps):
-        a_ev, b_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a_ev.record(stream)
-        for _ in range(steps):
-            env.step()
-        b_ev.record(stream)
-        b_ev.synchronize()
-        return a_ev.elapsed_time(b_ev) * 1e3 / steps     # us per step
+        return time_steps(stream, env.step, steps)
 
     setups = ["snap_idle", "bank_idle", "snap_1pct", "bank_1pct", "bank_all"]
     for name in setups:      # warm-up: >= 200 launches of every setup's kernels
@@ -99,37 +93,22 @@ def main():
             r.append(int(((d != 0) | (info["truncated"] != 0)).sum().item()))
         resets[name] = {"mean": float(np.mean(r)), "min": int(min(r)), "max": int(max(r))}
     times = {s: [] for s in setups}
-    for r in range(a.rounds):
+    for r in range(a.rounds):      # (not the harness's rotation: bank_all, a full arena copy per step, runs every second round only)
         for name in setups:
             if name == "bank_all" and r % 2:
                 continue
             prepare(name)
             times[name].append(run_block(a.block))
-    torch.cuda.synchronize(dev)
-
-    def stats(v):
-        v = np.asarray(v)
-        return {"median_us": float(np.median(v)), "p25_us": float(np.percentile(v, 25)), "p75_us": float(np.percentile(v, 75)),
-                "min_us": float(v.min()), "max_us": float(v.max()), "blocks": int(v.size)}
 
     S = {s: stats(v) for s, v in times.items()}
-    try:
-        head = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        head = None
     res = {"what": "per-step time of npb_step with the autoreset restoring from a start bank vs from the snapshot, one handle",
            "n_plants": n, "bank_entries": M, "device": torch.cuda.get_device_name(dev), "storage": env.storage,
            "step_kernel": env.last_step_kernel(), "block_steps": a.block, "rounds": a.rounds, "max_episode_steps_1pct": MAX,
            "resets_per_step": resets, "setups": S,
            "bank_vs_snapshot_pct": {"idle": 100.0 * (S["bank_idle"]["median_us"] / S["snap_idle"]["median_us"] - 1.0),
                                     "1pct": 100.0 * (S["bank_1pct"]["median_us"] / S["snap_1pct"]["median_us"] - 1.0)},
-           "head": head}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+           "head": head(ROOT)}
+    write_line(res, a.out)
     bank.close()
     env.close()
 

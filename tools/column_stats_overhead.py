@@ -2,9 +2,8 @@
 
 action_test("oil_top_off", range(n), dt = 5) with autoreset from a bank of `--bank` scenarios, device noise and a constant setpoint: no
 per-step host input.  Eight columns -- three carried fp64 members, an output member, an int32 member, an info column, an obs column and
-the reward --, every statistic, two limits.  One handle per size throughout (where an arena lands in physical memory moves the step time
-from one handle to the next); statistics and records are switched on and off on it between blocks, in an order that rotates from round
-to round.  Setups, event-timed us per step:
+the reward --, every statistic, two limits.  One handle per size throughout; statistics and records are switched on and off on it
+between blocks, in an order that rotates from round to round.  Setups, event-timed us per step:
   off         statistics off, no episode ending
   on          statistics on, no episode ending: the fold's launch behind every step
   on_records  statistics on and episode records copying and clearing them; episodes of 100 steps, the plants' episode clocks staggered
@@ -15,17 +14,16 @@ The condition that follows from the bytes: the fold moves at most about 104 B pe
 MB, plus one light launch, so it should cost under a quarter of the step it follows (`fold_under_a_quarter_of_the_step`).
 
 --parent DIR: a checkout of the parent commit, built.  `off` is then also measured in fresh processes, alternately on this build and on
-the parent's (this script run with --package-root and --only-off), `--process-repeats` times each: off agrees with the parent if the two
-differ by no more than this build's own round-to-round spread.  bench.py is run alternately from the two trees and its ms per step
-printed beside it.  One JSON line per run, all sizes in one object, also written to --out.
+the parent's (this script run with --package-root and --only-off), `--process-repeats` times each, and held against each other by
+overhead_harness.compare_off.  bench.py is run alternately from the two trees and its ms per step printed beside it.  One JSON line per
+run, all sizes in one object, also written to --out.
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 
-import numpy as np
+from overhead_harness import (add_parent_arguments, bench_alternated, compare_off, head, off_across_builds, paired, rotated_blocks, stats,
+                              time_steps, write_line)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W = 8
@@ -48,15 +46,6 @@ def measure(n, block, rounds, bank, only_off):
     setups = ["off"] + (["on", "on_records", "records"] if has_stats else [])
     rates = {}
 
-    def timed(steps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        for _ in range(steps):
-            env.step(power_setpoint=sp)
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b) * 1e3 / steps
-
     def run_block(setup):
         busy = setup in ("on_records", "records")
         if hasattr(env, "disable_episode_records"):
@@ -73,54 +62,24 @@ def measure(n, block, rounds, bank, only_off):
         for _ in range(W):
             env.step(power_setpoint=sp)
         before = env.step(power_setpoint=sp)[3]["episode_index"].sum().item()
-        us = timed(block)
+        us = time_steps(stream, lambda: env.step(power_setpoint=sp), block)
         after = env.step(power_setpoint=sp)[3]["episode_index"].sum().item()
         rates[setup] = 100.0 * (after - before) / (block + 1) / n
         if busy:                                                   # the drain is the caller's, outside the timed steps; nothing may have been dropped
             env.episode_records()
         return us
 
-    for s in setups:      # warm-up
-        run_block(s)
-    blocks = {s: [] for s in setups}
-    for r in range(rounds):
-        k = r % len(setups)
-        for s in setups[k:] + setups[:k]:
-            blocks[s].append(run_block(s))
-    torch.cuda.synchronize(dev)
-
-    def stats(v):
-        v = np.asarray(v)
-        return {"median_us": float(np.median(v)), "p25_us": float(np.percentile(v, 25)), "p75_us": float(np.percentile(v, 75)),
-                "min_us": float(v.min()), "max_us": float(v.max()), "blocks": int(v.size)}
-
-    def paired(a, b):
-        d = np.asarray(blocks[a]) - np.asarray(blocks[b])      # the same round's blocks
-        return {"median": float(np.median(d)), "min": float(d.min()), "max": float(d.max())}
+    blocks = rotated_blocks(setups, rounds, run_block)
     out = {"n_plants": n, "device": torch.cuda.get_device_name(dev), "step_kernel": env.last_step_kernel(), "block_steps": block, "rounds": rounds,
            "bank_entries": bank, "columns": len(COLUMNS), "statistics": list(STATS), "limits": len(LIMITS),
            "setups": {s: stats(v) for s, v in blocks.items()}, "ended_percent_of_plants_per_step": dict(rates)}
     if has_stats:
-        out["fold_cost_us_per_step"] = paired("on", "off")
-        out["fold_and_record_copy_cost_us_per_step"] = paired("on_records", "records")
+        out["fold_cost_us_per_step"] = paired(blocks, "on", "off")
+        out["fold_and_record_copy_cost_us_per_step"] = paired(blocks, "on_records", "records")
         out["fold_percent_of_the_step"] = 100.0 * out["fold_cost_us_per_step"]["median"] / out["setups"]["off"]["median_us"]
         out["fold_under_a_quarter_of_the_step"] = bool(out["fold_cost_us_per_step"]["median"] < 0.25 * out["setups"]["off"]["median_us"])
     env.close()
     return out
-
-
-def bench_alternated(parent, repeats, steps, warmup):
-    """bench.py from this tree and from the parent's, alternately: ms per step of each run"""
-    runs = {"this": [], "parent": []}
-    for _ in range(repeats):
-        for which, root in (("this", ROOT), ("parent", parent)):
-            p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)],
-                               capture_output=True, text=True, timeout=900, cwd=root)
-            if p.returncode != 0:
-                raise SystemExit("bench.py of the %s tree failed:\n%s" % (which, p.stderr[-2000:]))
-            runs[which].append(json.loads(p.stdout.strip().splitlines()[-1])["ms_per_step"])
-    return {"steps": steps, "warmup": warmup, "this_ms_per_step": runs["this"], "parent_ms_per_step": runs["parent"],
-            "parent_minus_this_ms": float(np.median(runs["parent"]) - np.median(runs["this"]))}
 
 
 def main():
@@ -129,12 +88,8 @@ def main():
     ap.add_argument("--block", type=int, default=192)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--bank", type=int, default=64, help="entries of the start bank")
-    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit: `off` and bench.py across the two builds")
-    ap.add_argument("--process-repeats", type=int, default=2)
     ap.add_argument("--bench-steps", type=int, default=200)
-    ap.add_argument("--package-root", default=ROOT, help="where nuclear_sim_amd is imported from (used for the parent's build)")
-    ap.add_argument("--only-off", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "column_stats_overhead.json"))
+    add_parent_arguments(ap, "column_stats_overhead.json")
     a = ap.parse_args()
     sys.path.insert(0, a.package_root)
     sizes = {}
@@ -142,37 +97,16 @@ def main():
         res = measure(n, a.block, a.rounds, a.bank, a.only_off)
         print("%d plants: measured" % n, file=sys.stderr, flush=True)
         if a.parent and not a.only_off:
-            runs = {"this": [], "parent": []}
-            for _ in range(a.process_repeats):
-                for which, root in (("this", ROOT), ("parent", os.path.abspath(a.parent))):
-                    cmd = [sys.executable, os.path.abspath(__file__), "--n", str(n), "--block", str(a.block), "--rounds", str(a.rounds),
-                           "--bank", str(a.bank), "--package-root", root, "--only-off", "--out", ""]
-                    p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-                    if p.returncode != 0:
-                        raise SystemExit("the %s build's run failed:\n%s" % (which, p.stderr[-2000:]))
-                    runs[which].append(json.loads(p.stdout.strip().splitlines()[-1])["sizes"][str(n)]["setups"]["off"]["median_us"])
-                    print("%d plants: off of the %s build in a fresh process" % (n, which), file=sys.stderr, flush=True)
-            mine = runs["this"] + [res["setups"]["off"]["median_us"]]
-            spread = max(max(mine) - min(mine), res["setups"]["off"]["max_us"] - res["setups"]["off"]["min_us"])
-            diff = float(np.median(runs["parent"]) - np.median(mine))
-            res["parent_comparison"] = {"off": {"this_medians_us": mine, "parent_medians_us": runs["parent"], "parent_minus_this_us": diff,
-                                                "this_spread_us": float(spread), "off_agrees": bool(abs(diff) <= spread)}}
+            this, parent = off_across_builds(__file__, ["--n", n, "--block", a.block, "--rounds", a.rounds, "--bank", a.bank], a.parent, a.process_repeats,
+                                             lambda run: run["sizes"][str(n)]["setups"]["off"]["median_us"], 900)
+            res["parent_comparison"] = {"off": compare_off(this, parent, res["setups"]["off"])}
         sizes[str(n)] = res
-    try:
-        head = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        head = None
     out = {"what": "per-step time of config 4 with autoreset from a bank and device noise: column statistics (8 columns, every statistic, two limits) "
                    "off and on, and on with episode records copying and clearing them at about 1 % of the plants ending per step",
-           "sizes": sizes, "head": head}
+           "sizes": sizes, "head": head(ROOT)}
     if a.parent and not a.only_off:
-        out["bench"] = bench_alternated(os.path.abspath(a.parent), a.process_repeats, a.bench_steps, 20)
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+        out["bench"] = bench_alternated(a.parent, a.process_repeats, a.bench_steps, 20)
+    write_line(out, a.out)
 
 
 if __name__ == "__main__":

@@ -14,13 +14,14 @@ setpoints.  Prints one JSON line (per-step times in us) and writes it to --out. 
 """
 import argparse
 import ctypes
-import json
 import os
 import sys
 import time
 
 import numpy as np
 import torch
+
+from overhead_harness import time_steps, write_line
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -65,15 +66,9 @@ def main():
     blk = torch.empty((B, n), dtype=torch.float64, device=dev)
     predrawn = torch.empty((B, n), dtype=torch.float64, device=dev)
     _lib.check(L.npb_noise_fill(gen_env._h, B, ctypes.c_void_p(predrawn.data_ptr()), gen_env._stream()), gen_env._h)
-    fill_ms = []
-    for i in range(a.fills + 3):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
+    def one_fill():
         _lib.check(L.npb_noise_fill(gen_env._h, B, ctypes.c_void_p(blk.data_ptr()), gen_env._stream()), gen_env._h)
-        e1.record(stream)
-        e1.synchronize()
-        if i >= 3:
-            fill_ms.append(e0.elapsed_time(e1))
+    fill_us = [time_steps(stream, one_fill, 1) for _ in range(a.fills + 3)][3:]
     gen_env.close()
 
     t_dev = [0]
@@ -102,7 +97,7 @@ def main():
     kernel = env.last_step_kernel()
     env.close()
 
-    fill = stats([x * 1e3 for x in fill_ms])
+    fill = stats(fill_us)
     dev_s, pre_s = stats(per_step["device"]), stats(per_step["predrawn"])
     out = {"plants": n, "block": B, "seeds": "42 + i", "step_kernel": kernel,
            "fill_us_per_block": fill, "fill_us_per_step_amortised": fill["median"] / B,
@@ -123,11 +118,7 @@ def main():
                 hn.next()
         out["host_draw_ms_per_block"] = stats([x * 1e3 for x in draws])
         out["host_draw_us_per_step"] = out["host_draw_ms_per_block"]["median"] * 1e3 / B
-    line = json.dumps(out)
-    print(line)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
+    write_line(out, a.out)
 
 
 if __name__ == "__main__":

@@ -18,8 +18,9 @@ autoreset.  One JSON line, written to --out.
 import argparse
 import json
 import os
-import subprocess
 import sys
+
+from overhead_harness import fresh_process, head, stats, time_steps, write_line
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAX = 100
@@ -51,13 +52,7 @@ def worker(a):
             _lib.check(L.npb_set_autoreset(h, 1, 1), h)
 
     def run_block(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(steps):
-            env.step()
-        e1.record(stream)
-        e1.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / steps     # us per step
+        return time_steps(stream, env.step, steps)
 
     cases = (("off",) if a.diagnostics else ()) + CASES
     for name in cases:
@@ -68,30 +63,16 @@ def worker(a):
         for name in cases:
             prepare(name)
             times[name].append(run_block(a.block))
-    torch.cuda.synchronize(dev)
-    print("WORKER " + json.dumps({"times_us": times, "step_kernel": env.last_step_kernel(), "device": torch.cuda.get_device_name(dev)}))
+    info = {"times_us": times, "step_kernel": env.last_step_kernel(), "device": torch.cuda.get_device_name(dev)}
     env.close()
-
-
-def stats(v):
-    import numpy as np
-    v = np.asarray(v, dtype=float)
-    return {"median_us": float(np.median(v)), "p25_us": float(np.percentile(v, 25)), "p75_us": float(np.percentile(v, 75)),
-            "min_us": float(v.min()), "max_us": float(v.max()), "blocks": int(v.size)}
+    print(json.dumps(info))      # the worker's last line: what fresh_process reads
 
 
 def run_worker(a, tree, diagnostics):
     cmd = [sys.executable, os.path.abspath(__file__), "--worker", tree, "--n", str(a.n), "--blocks", str(a.blocks), "--block", str(a.block)]
     if diagnostics:
         cmd.append("--diagnostics")
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.worker_timeout)
-    if p.returncode != 0:      # nothing more is started on the device after a worker that failed
-        sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
-        raise SystemExit("worker on %s failed with status %d" % (tree, p.returncode))
-    for ln in p.stdout.splitlines():
-        if ln.startswith("WORKER "):
-            return json.loads(ln[7:])
-    raise SystemExit("worker on %s printed no result" % tree)
+    return fresh_process(cmd, a.worker_timeout)
 
 
 def main():
@@ -129,26 +110,17 @@ def main():
     off = {who: {c: stats(v) for c, v in t.items()} for who, t in times.items()}
     gate = {c: bool(off["parent"][c]["p25_us"] <= off["this"][c]["median_us"] <= off["parent"][c]["p75_us"]) for c in CASES}
     below = {c: bool(off["this"][c]["median_us"] < off["parent"][c]["p25_us"]) for c in CASES}
-    try:
-        head = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        head = None
     res = {"what": "per-step time of npb_step with autoreset: diagnostics off, this tree against the parent commit in alternating worker "
                    "processes of one session; and with the diagnostics rows carried (diagnostics=True), this tree",
            "n_plants": a.n, "block_steps": a.block, "blocks_per_worker": a.blocks, "rounds": a.rounds, "max_episode_steps_1pct": MAX,
            "diagnostics_off": dict(off, **meta),
            "this_median_within_parent_iqr": gate, "this_median_below_parent_p25": below,
            "diagnostics_carried": {"step_kernel": carry_kernel, "setups": {c: stats(v) for c, v in carry.items()} if a.carry_rounds else {}},
-           "head": head}
+           "head": head(ROOT)}
     if a.carry_rounds:
         o = res["diagnostics_carried"]["setups"]["off"]["median_us"]
         res["diagnostics_carried"]["overhead_vs_no_autoreset_pct"] = {c: 100.0 * (res["diagnostics_carried"]["setups"][c]["median_us"] / o - 1.0) for c in CASES}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    write_line(res, a.out)
     return 0
 
 

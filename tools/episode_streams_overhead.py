@@ -1,9 +1,8 @@
 """What episode streams (npb_set_episode_streams) cost on BASELINE config 4 at 65 536 and 32 768 plants.
 
 action_test("oil_top_off", range(n), dt = 5) with autoreset from a bank of `--bank` scenarios, the runner's power profile of `--profile`
-steps and device noise: no per-step host input.  One handle per size throughout (where an arena lands in physical memory moves the step
-time from one handle to the next); the mode is switched on and off on it between blocks.  Three states, each with the mode off and on,
-in an order that rotates from round to round:
+steps and device noise: no per-step host input.  One handle per size throughout; the mode is switched on and off on it between
+blocks.  Three states, each with the mode off and on, in an order that rotates from round to round:
   quiet   no episode limit and no scram: nothing restarts.  On minus off is what the mode costs a step on which nothing happens -- the
           restart kernel's one vote per wave, the rows taken into the output columns, and the handle's refills against PowerProfile's.
   busy    episodes of 100 steps, the plants' episode clocks staggered beforehand (100 untimed steps, one group of n / 100 plants restored
@@ -16,17 +15,16 @@ Reported per setup: the per-step time of each block (mean, median, quartiles, mi
 state and round.
 
 --parent DIR: a checkout of the parent commit, built.  The mode-off setups are then also measured in fresh processes, alternately on
-this build and on the parent's (this script run with --package-root), `--process-repeats` times each; `off_agrees` says whether the two
-builds' medians differ by no more than the spread of this build's own repeats (blocks and processes).  One JSON line per run, all sizes
-in one object, also written to --out.
+this build and on the parent's (this script run with --package-root), `--process-repeats` times each, and held against each other setup by
+setup by overhead_harness.compare_off.  One JSON line per run, all sizes in one object, also written to --out.
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
+
+from overhead_harness import add_parent_arguments, compare_off, head, off_across_builds, paired, rotated_blocks, stats, time_steps, write_line
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W = 8
@@ -49,15 +47,10 @@ def measure(n, block, rounds, profile, bank, worst_steps, stream_block, only_off
     rates, worst = {}, {s: [] for s in setups}
 
     def timed(steps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        for _ in range(steps):
-            env.step()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b) * 1e3 / steps
+        return time_steps(stream, env.step, steps)
 
-    def run_block(state, on):
+    def run_block(setup):
+        state, on = setup
         if has_mode:
             if env.stream_rows is not None:
                 env.disable_episode_streams()
@@ -82,32 +75,19 @@ def measure(n, block, rounds, profile, bank, worst_steps, stream_block, only_off
         rates[(state, on)] = 100.0 * (after - before) / (block + 1) / n
         return us
 
-    for s in setups:      # warm-up
-        run_block(*s)
-    blocks = {s: [] for s in setups}
-    for r in range(rounds):
-        k = r % len(setups)
-        for s in setups[k:] + setups[:k]:
-            blocks[s].append(run_block(*s))
-    torch.cuda.synchronize(dev)
-
-    def stats(v):
-        v = np.asarray(v)
-        return {"mean_us": float(v.mean()), "median_us": float(np.median(v)), "p25_us": float(np.percentile(v, 25)),
-                "p75_us": float(np.percentile(v, 75)), "min_us": float(v.min()), "max_us": float(v.max()), "blocks": int(v.size)}
+    blocks = rotated_blocks(setups, rounds, run_block)
 
     def name(s, on):
         return "%s_%s" % (s, "on" if on else "off")
     out = {"n_plants": n, "device": torch.cuda.get_device_name(dev), "step_kernel": env.last_step_kernel(), "block_steps": block, "rounds": rounds,
            "profile_steps": profile, "bank_entries": bank, "stream_block": stream_block, "worst_episode_steps": worst_steps,
-           "setups": {name(*s): stats(v) for s, v in blocks.items()},
+           "setups": {name(*s): dict(stats(v), mean_us=float(np.mean(v))) for s, v in blocks.items()},
            "restarted_percent_of_plants_per_step": {name(*s): v for s, v in rates.items()},
            "worst": {name(*s): {"truncating_step_us": float(np.median([w["truncating_step_us"] for w in v[1:]])),
                                 "other_steps_us": float(np.median([w["other_steps_us"] for w in v[1:]]))} for s, v in worst.items() if len(v) > 1}}
     for s in ("quiet", "busy", "worst"):
-        if (s, True) in blocks:
-            d = np.asarray(blocks[(s, True)]) - np.asarray(blocks[(s, False)])      # the same round's blocks, paired
-            out["mode_cost_us_per_step_" + s] = {"median": float(np.median(d)), "mean": float(d.mean()), "min": float(d.min()), "max": float(d.max())}
+        if (s, True) in blocks:      # this script reports the mean beside the harness's median, min and max
+            out["mode_cost_us_per_step_" + s] = dict(paired(blocks, (s, True), (s, False)), mean=float(np.mean(blocks[(s, True)]) - np.mean(blocks[(s, False)])))
     if "worst_on" in out["worst"]:
         out["mode_cost_us_truncating_step"] = out["worst"]["worst_on"]["truncating_step_us"] - out["worst"]["worst_off"]["truncating_step_us"]
     env.close()
@@ -123,50 +103,22 @@ def main():
     ap.add_argument("--bank", type=int, default=64, help="entries of the start bank")
     ap.add_argument("--worst-steps", type=int, default=16, help="episode length of the worst state")
     ap.add_argument("--stream-block", type=int, default=64, help="rows the handle draws at a time with the mode on")
-    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit: compare the mode-off setups across the two builds")
-    ap.add_argument("--process-repeats", type=int, default=2)
-    ap.add_argument("--package-root", default=ROOT, help="where nuclear_sim_amd is imported from (used for the parent's build)")
-    ap.add_argument("--only-off", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "episode_streams_overhead.json"))
+    add_parent_arguments(ap, "episode_streams_overhead.json")
     a = ap.parse_args()
     sys.path.insert(0, a.package_root)
     sizes = {}
     for n in a.n:
         res = measure(n, a.block, a.rounds, a.profile, a.bank, a.worst_steps, a.stream_block, a.only_off)
         if a.parent and not a.only_off:
-            runs = {"this": [], "parent": []}
-            for _ in range(a.process_repeats):
-                for which, root in (("this", ROOT), ("parent", os.path.abspath(a.parent))):
-                    cmd = [sys.executable, os.path.abspath(__file__), "--n", str(n), "--block", str(a.block), "--rounds", str(a.rounds),
-                           "--profile", str(a.profile), "--bank", str(a.bank), "--worst-steps", str(a.worst_steps),
-                           "--package-root", root, "--only-off", "--out", ""]
-                    p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-                    if p.returncode != 0:
-                        raise SystemExit("the %s build's run failed:\n%s" % (which, p.stderr[-2000:]))
-                    runs[which].append(json.loads(p.stdout.strip().splitlines()[-1])["sizes"][str(n)]["setups"])
-            cmp = {}
-            for s in ("quiet_off", "busy_off", "worst_off"):
-                mine = [r[s]["median_us"] for r in runs["this"]] + [res["setups"][s]["median_us"]]
-                theirs = [r[s]["median_us"] for r in runs["parent"]]
-                spread = max(max(mine) - min(mine), res["setups"][s]["max_us"] - res["setups"][s]["min_us"])
-                diff = float(np.median(theirs) - np.median(mine))
-                cmp[s] = {"this_medians_us": mine, "parent_medians_us": theirs, "parent_minus_this_us": diff,
-                          "this_spread_us": float(spread), "off_agrees": bool(abs(diff) <= spread)}
-            res["parent_comparison"] = cmp
+            argv = ["--n", n, "--block", a.block, "--rounds", a.rounds, "--profile", a.profile, "--bank", a.bank, "--worst-steps", a.worst_steps]
+            this, parent = off_across_builds(__file__, argv, a.parent, a.process_repeats, lambda run: run["sizes"][str(n)]["setups"], 900)
+            res["parent_comparison"] = {s: compare_off([r[s]["median_us"] for r in this], [r[s]["median_us"] for r in parent], res["setups"][s])
+                                        for s in ("quiet_off", "busy_off", "worst_off")}
         sizes[str(n)] = res
-    try:
-        head = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        head = None
     out = {"what": "per-step time of config 4 with autoreset from a bank, a power profile and device noise, episode streams off and on: nothing "
                    "restarting, about 1 % of the plants truncating per step, and the one step on which every plant truncates at once",
-           "sizes": sizes, "head": head}
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+           "sizes": sizes, "head": head(ROOT)}
+    write_line(out, a.out)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,7 @@
 action_test("oil_top_off", range(n), dt = 5) with autoreset from a bank of `--bank` scenarios, device noise and a constant setpoint: no
 per-step host input.  The features are 16 columns -- 8 state members, 4 info columns, 2 obs columns (one against a second column), the
 step's reward and the trip flags' pump bits -- each with a ref, a scale and a clip, K = 4 frames, float32: a [n, 4, 16] tensor.  One
-handle per size throughout (where an arena lands in physical memory moves the step time from one handle to the next); the features are
+handle per size throughout; the features are
 set and dropped on it between blocks, in an order that rotates from round to round.  Setups, event-timed us per step:
   off        no features, no episode ending                                                                                   (a)
   on         features on, nothing restarting: pass A behind every step, and pass B finding nothing                            (b)
@@ -19,19 +19,17 @@ What the bytes say: pass A reads 17 values and two bookkeeping words per plant, 
 16: some 600 B, 39 MB at 65 536 plants against the step's 451 MB.
 
 --parent DIR: a checkout of the parent commit, built.  `off` is then also measured in fresh processes, alternately on this build and on
-the parent's (this script run with --package-root and --only-off), `--process-repeats` times each: off agrees with the parent if the
-medians of the two differ by no more than the run-to-run spread (the largest of the parent's processes', this build's processes' and
-this handle's blocks').  bench.py is run alternately from the two trees and its ms per step printed beside it.  One JSON line per run,
-all sizes in one object, also written to --out.
+the parent's (this script run with --package-root and --only-off), `--process-repeats` times each, and held against each other by
+overhead_harness.compare_off.  bench.py is run alternately from the two trees and its ms per step printed beside it.  One JSON line per
+run, all sizes in one object, also written to --out.
 """
 import argparse
 import ctypes
-import json
 import os
-import subprocess
 import sys
 
-import numpy as np
+from overhead_harness import (add_parent_arguments, bench_alternated, compare_off, head, off_across_builds, paired, rotated_blocks, stats,
+                              time_steps, write_line)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W = 8
@@ -99,15 +97,6 @@ def measure(n, block, rounds, bank, only_off):
             by_hand.update(out[0], out[1], out[3])
         return out
 
-    def timed(setup, steps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        for _ in range(steps):
-            step(setup)
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b) * 1e3 / steps
-
     def run_block(setup):
         busy = setup in ("busy", "busy_off")
         env._enable_autoreset(EPISODE if busy else None)      # the episode limit of the setup; the counters begin at zero
@@ -122,7 +111,7 @@ def measure(n, block, rounds, bank, only_off):
             step(setup)
         first = step(setup)
         before = first[3]["episode_index"].sum().item()
-        us = timed(setup, block)
+        us = time_steps(stream, lambda: step(setup), block)
         last = step(setup)
         rates[setup] = 100.0 * (last[3]["episode_index"].sum().item() - before) / (block + 1) / n
         return us
@@ -134,50 +123,20 @@ def measure(n, block, rounds, bank, only_off):
             mine = by_hand.update(out[0], out[1], out[3])
         agree = {"max_abs_difference_of_the_stacks": float((mine - env.features()).abs().max().item())}
         env.set_features(None)
-    for s in setups:      # warm-up
-        run_block(s)
-    blocks = {s: [] for s in setups}
-    for r in range(rounds):
-        k = r % len(setups)
-        for s in setups[k:] + setups[:k]:
-            blocks[s].append(run_block(s))
-    torch.cuda.synchronize(dev)
-
-    def stats(v):
-        v = np.asarray(v)
-        return {"median_us": float(np.median(v)), "p25_us": float(np.percentile(v, 25)), "p75_us": float(np.percentile(v, 75)),
-                "min_us": float(v.min()), "max_us": float(v.max()), "blocks": int(v.size)}
-
-    def paired(a, b):
-        d = np.asarray(blocks[a]) - np.asarray(blocks[b])      # the same round's blocks
-        return {"median": float(np.median(d)), "min": float(d.min()), "max": float(d.max())}
+    blocks = rotated_blocks(setups, rounds, run_block)
     out = {"n_plants": n, "device": torch.cuda.get_device_name(dev), "step_kernel": env.last_step_kernel(), "block_steps": block, "rounds": rounds,
            "bank_entries": bank, "columns": 16, "stack": STACK, "dtype": "float32", "setups": {s: stats(v) for s, v in blocks.items()},
            "ended_percent_of_plants_per_step": dict(rates)}
     if has:
         out["by_hand_against_the_device"] = agree
-        out["on_cost_us_per_step"] = paired("on", "off")
-        out["by_hand_in_torch_cost_us_per_step"] = paired("torch", "off")
-        out["one_percent_restarting_cost_us_per_step"] = paired("busy", "busy_off")
+        out["on_cost_us_per_step"] = paired(blocks, "on", "off")
+        out["by_hand_in_torch_cost_us_per_step"] = paired(blocks, "torch", "off")
+        out["one_percent_restarting_cost_us_per_step"] = paired(blocks, "busy", "busy_off")
         out["on_percent_of_the_step"] = 100.0 * out["on_cost_us_per_step"]["median"] / out["setups"]["off"]["median_us"]
         out["on_is_below_by_hand"] = bool(out["on_cost_us_per_step"]["median"] < out["by_hand_in_torch_cost_us_per_step"]["median"])
         env.set_features(None)
     env.close()
     return out
-
-
-def bench_alternated(parent, repeats, steps, warmup):
-    """bench.py from this tree and from the parent's, alternately: ms per step of each run"""
-    runs = {"this": [], "parent": []}
-    for _ in range(repeats):
-        for which, root in (("this", ROOT), ("parent", parent)):
-            p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)],
-                               capture_output=True, text=True, timeout=900, cwd=root)
-            if p.returncode != 0:
-                raise SystemExit("bench.py of the %s tree failed:\n%s" % (which, p.stderr[-2000:]))
-            runs[which].append(json.loads(p.stdout.strip().splitlines()[-1])["ms_per_step"])
-    return {"steps": steps, "warmup": warmup, "this_ms_per_step": runs["this"], "parent_ms_per_step": runs["parent"],
-            "parent_minus_this_ms": float(np.median(runs["parent"]) - np.median(runs["this"]))}
 
 
 def main():
@@ -186,12 +145,8 @@ def main():
     ap.add_argument("--block", type=int, default=192)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--bank", type=int, default=64, help="entries of the start bank")
-    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit: `off` and bench.py across the two builds")
-    ap.add_argument("--process-repeats", type=int, default=2)
     ap.add_argument("--bench-steps", type=int, default=200)
-    ap.add_argument("--package-root", default=ROOT, help="where nuclear_sim_amd is imported from (used for the parent's build)")
-    ap.add_argument("--only-off", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "features_overhead.json"))
+    add_parent_arguments(ap, "features_overhead.json")
     a = ap.parse_args()
     sys.path.insert(0, a.package_root)
     sizes = {}
@@ -199,39 +154,17 @@ def main():
         res = measure(n, a.block, a.rounds, a.bank, a.only_off)
         print("%d plants: measured" % n, file=sys.stderr, flush=True)
         if a.parent and not a.only_off:
-            runs = {"this": [], "parent": []}
-            for _ in range(a.process_repeats):
-                for which, root in (("this", ROOT), ("parent", os.path.abspath(a.parent))):
-                    cmd = [sys.executable, os.path.abspath(__file__), "--n", str(n), "--block", str(a.block), "--rounds", str(a.rounds),
-                           "--bank", str(a.bank), "--package-root", root, "--only-off", "--out", ""]
-                    p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-                    if p.returncode != 0:
-                        raise SystemExit("the %s build's run failed:\n%s" % (which, p.stderr[-2000:]))
-                    runs[which].append(json.loads(p.stdout.strip().splitlines()[-1])["sizes"][str(n)]["setups"]["off"]["median_us"])
-                    print("%d plants: off of the %s build in a fresh process" % (n, which), file=sys.stderr, flush=True)
-            # this build's off, and the parent's, in fresh processes only: like against like
-            spread_parent = max(runs["parent"]) - min(runs["parent"])
-            spread = max(max(runs["this"]) - min(runs["this"]), spread_parent, res["setups"]["off"]["max_us"] - res["setups"]["off"]["min_us"])
-            diff = float(np.median(runs["parent"]) - np.median(runs["this"]))
-            res["parent_comparison"] = {"off": {"this_medians_us": runs["this"], "parent_medians_us": runs["parent"], "parent_minus_this_us": diff,
-                                                "parent_spread_us": float(spread_parent), "spread_us": float(spread), "off_agrees": bool(abs(diff) <= spread)}}
+            this, parent = off_across_builds(__file__, ["--n", n, "--block", a.block, "--rounds", a.rounds, "--bank", a.bank], a.parent, a.process_repeats,
+                                             lambda run: run["sizes"][str(n)]["setups"]["off"]["median_us"], 900)
+            res["parent_comparison"] = {"off": compare_off(this, parent, res["setups"]["off"])}
         sizes[str(n)] = res
-    try:
-        head = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        head = None
     out = {"what": "per-step time of config 4 with autoreset from a bank and device noise: features of 16 columns, 4 frames, float32 off, on with "
                    "nothing restarting, on with about 1 % of the plants truncated per step and their final stacks kept; the same frames formed "
                    "by hand in torch on the same build, without restart handling, beside it",
-           "sizes": sizes, "head": head}
+           "sizes": sizes, "head": head(ROOT)}
     if a.parent and not a.only_off:
-        out["bench"] = bench_alternated(os.path.abspath(a.parent), a.process_repeats, a.bench_steps, 20)
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+        out["bench"] = bench_alternated(a.parent, a.process_repeats, a.bench_steps, 20)
+    write_line(out, a.out)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,6 @@
 """What the maintenance event log (npb_set_maintenance_log) costs on BASELINE config 4 at 65 536 plants.
 
-action_test("oil_top_off", range(n), dt = 5), one handle throughout (where an arena lands in physical memory moves the step time
-from one handle to the next: npb_api.hip, probe_placement).  The batch is snapshotted once, and every timed block of every setup
+action_test("oil_top_off", range(n), dt = 5), one handle throughout.  The batch is snapshotted once, and every timed block of every setup
 replays the SAME simulated interval: restore(), the same pre-drawn heat-source noise rows, 8 untimed steps (switching the log
 re-uploads the rule's constants and has the rule look at every wave once), then `--block` steps, each bracketed by its own pair of
 events.  The setups, in an order that rotates from round to round:
@@ -15,14 +14,14 @@ the drains.  One JSON line, also written to --out.  The kernels' own times: run 
 `rocprofv3 --kernel-trace --stats -- python tools/maintenance_log_overhead.py --rounds 2`.
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 import time
 
 import numpy as np
 import torch
+
+from overhead_harness import head, stats, time_steps, write_line
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -79,19 +78,20 @@ def main():
             step(t)
         prev["c"] = env.get_field("maint.work_orders_created"); prev["p"] = env.get_field("maint.maintenance_actions_performed")
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(B)]
-        a_ev, b_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         f = steps[name]
-        a_ev.record(stream)
-        for k in range(B):
+        ks = iter(range(B))
+
+        def bracketed():      # the step between its own pair of events, inside the block's
+            k = next(ks)
             ev[k][0].record(stream)
             f(W + k, k)
             ev[k][1].record(stream)
-        b_ev.record(stream)
-        b_ev.synchronize()
+        us = time_steps(stream, bracketed, B)
         per_step = [x.elapsed_time(y) * 1e3 for x, y in ev]        # us: the step launch (and, composed, its gathers) per step
-        return a_ev.elapsed_time(b_ev) * 1e3 / B, per_step
+        return us, per_step
 
     setups = list(steps)
+    # (not the harness's rotated_blocks: the event counts and the drain times are zeroed between the warm-up and the rounds)
     for name in setups:              # warm-up
         run_block(name)
     events["on_drain48"] = events["composed"] = 0
@@ -103,14 +103,8 @@ def main():
         for name in order:
             bt, ps = run_block(name)
             blocks[name].append(bt); per_step[name].append(ps)
-    torch.cuda.synchronize(dev)
 
-    def stats(v):
-        v = np.asarray(v)
-        return {"mean_us": float(v.mean()), "median_us": float(np.median(v)), "p25_us": float(np.percentile(v, 25)),
-                "p75_us": float(np.percentile(v, 75)), "min_us": float(v.min()), "max_us": float(v.max()), "blocks": int(v.size)}
-
-    S = {s: stats(v) for s, v in blocks.items()}
+    S = {s: dict(stats(v), mean_us=float(np.mean(v))) for s, v in blocks.items()}
     for s in setups:
         ps = np.asarray(per_step[s])                 # [rounds, B]
         med = np.median(ps, axis=0)                  # per step index, over the rounds: the same simulated step every time
@@ -118,10 +112,6 @@ def main():
         S[s]["step_max_us"] = float(ps.max())
         S[s]["slow_steps"] = [[int(k), float(med[k])] for k in np.nonzero(med > 3 * np.median(med))[0]]
     off = S["off"]
-    try:
-        head = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        head = None
     res = {"what": "per-step time of config 4 with the maintenance event log off, on (drained every 48 steps) and composed from the "
                    "counters; every block replays the same simulated interval",
            "n_plants": n, "device": torch.cuda.get_device_name(dev), "storage": env.storage, "step_kernel": env.last_step_kernel(),
@@ -131,13 +121,8 @@ def main():
            "setups": S,
            "overhead_vs_off_pct": {s: {"mean": 100.0 * (S[s]["mean_us"] / off["mean_us"] - 1.0),
                                        "median": 100.0 * (S[s]["median_us"] / off["median_us"] - 1.0)} for s in setups if s != "off"},
-           "head": head}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+           "head": head(ROOT)}
+    write_line(res, a.out)
 
 
 if __name__ == "__main__":

@@ -20,17 +20,14 @@ and so is that of the moments themselves; the indices necessarily differ.
 
 `off`: the step with features, controls and the rollout on, nothing of this feature called -- what the parent commit's build runs too.
 --parent DIR: a checkout of the parent commit, built.  `off` is then measured in fresh processes, alternately on this build and on the
-parent's (this script run with --package-root and --only-off), `--process-repeats` times each: `off_within_the_parents_own_spread` holds
-the difference of the medians against the spread between the parent's runs alone, `off_agrees` against the largest of the spreads.
-One JSON line per run, all sizes in one object, also written to --out.
+parent's (this script run with --package-root and --only-off), `--process-repeats` times each, and held against each other by
+overhead_harness.compare_off.  One JSON line per run, all sizes in one object, also written to --out.
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 
-import numpy as np
+from overhead_harness import add_parent_arguments, compare_off, head, off_across_builds, stats, time_steps, write_line
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W = 8
@@ -95,23 +92,13 @@ def measure(n, rounds, only_off, calls):
     env.set_rollout(T, extras=E)
     env.rollout_extras_input().copy_(extras)
 
-    def timed(work):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        work()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b) * 1e3
+    def timed(work):      # one window: us
+        return time_steps(stream, work, 1)
 
     def horizon(steps=T):
         for _ in range(steps):
             x.neg_()      # the policy's new output
             env.step()
-
-    def stats(v):
-        v = np.asarray(v)
-        return {"median_us": float(np.median(v)), "p25_us": float(np.percentile(v, 25)), "p75_us": float(np.percentile(v, 75)),
-                "min_us": float(v.min()), "max_us": float(v.max()), "blocks": int(v.size)}
     # off: blocks of one horizon with the rollout recording, nothing of the feature called
     off = []
     for k in range(1 + rounds):
@@ -190,11 +177,7 @@ def main():
     ap.add_argument("--n", type=int, nargs="+", default=[65536, 32768])
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--calls", type=int, default=20, help="timed calls of rollout_moments")
-    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit: `off` across the two builds")
-    ap.add_argument("--process-repeats", type=int, default=2)
-    ap.add_argument("--package-root", default=ROOT, help="where nuclear_sim_amd is imported from (used for the parent's build)")
-    ap.add_argument("--only-off", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "minibatch_overhead.json"))
+    add_parent_arguments(ap, "minibatch_overhead.json")
     a = ap.parse_args()
     sys.path.insert(0, a.package_root)
     sizes = {}
@@ -202,37 +185,16 @@ def main():
         res = measure(n, a.rounds, a.only_off, a.calls)
         print("%d plants: measured" % n, file=sys.stderr, flush=True)
         if a.parent and not a.only_off:
-            runs = {"this": [], "parent": []}
-            for _ in range(a.process_repeats):
-                for which, root in (("this", ROOT), ("parent", os.path.abspath(a.parent))):
-                    cmd = [sys.executable, os.path.abspath(__file__), "--n", str(n), "--rounds", str(a.rounds), "--package-root", root, "--only-off", "--out", ""]
-                    p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-                    if p.returncode != 0:
-                        raise SystemExit("the %s build's run failed:\n%s" % (which, p.stderr[-2000:]))
-                    runs[which].append(json.loads(p.stdout.strip().splitlines()[-1])["sizes"][str(n)]["setups"]["off"]["median_us"])
-                    print("%d plants: off of the %s build in a fresh process" % (n, which), file=sys.stderr, flush=True)
-            spread_parent = max(runs["parent"]) - min(runs["parent"])
-            spread = max(max(runs["this"]) - min(runs["this"]), spread_parent, res["setups"]["off"]["max_us"] - res["setups"]["off"]["min_us"])
-            diff = float(np.median(runs["parent"]) - np.median(runs["this"]))
-            res["parent_comparison"] = {"off": {"this_medians_us": runs["this"], "parent_medians_us": runs["parent"], "parent_minus_this_us": diff,
-                                                "parent_spread_us": float(spread_parent), "spread_us": float(spread), "off_agrees": bool(abs(diff) <= spread),
-                                                "off_within_the_parents_own_spread": bool(abs(diff) <= spread_parent)}}
+            this, parent = off_across_builds(__file__, ["--n", n, "--rounds", a.rounds], a.parent, a.process_repeats,
+                                             lambda run: run["sizes"][str(n)]["setups"]["off"]["median_us"], 900)
+            res["parent_comparison"] = {"off": compare_off(this, parent, res["setups"]["off"])}
         sizes[str(n)] = res
-    try:
-        head = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        head = None
     out = {"what": "over a recorded rollout of config 4 (device noise, autoreset, features of 16 columns x 4 frames float32, controls of 4 axes, "
                    "E = 2, T = 128): one epoch of shuffled minibatches of 65 536 transitions through rollout_minibatches, by transition and by "
                    "plant, against randperm + five index_selects + mean / std by hand in torch; rollout_moments alone; and the step with the "
                    "feature unused",
-           "sizes": sizes, "head": head}
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+           "sizes": sizes, "head": head(ROOT)}
+    write_line(out, a.out)
 
 
 if __name__ == "__main__":

@@ -13,13 +13,14 @@ line (per-step times in us) and writes it to --out.
 """
 import argparse
 import ctypes
-import json
 import os
 import sys
 import time
 
 import numpy as np
 import torch
+
+from overhead_harness import time_steps, write_line
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -35,16 +36,7 @@ def stats(xs):
 
 
 def timed(stream, fills, call):
-    ms = []
-    for i in range(fills + 3):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        call()
-        e1.record(stream)
-        e1.synchronize()
-        if i >= 3:
-            ms.append(e0.elapsed_time(e1))
-    return stats([x * 1e3 for x in ms])
+    return stats([time_steps(stream, call, 1) for _ in range(fills + 3)][3:])
 
 
 def measure(n, a):
@@ -115,11 +107,7 @@ def main():
         raise SystemExit("power_profile_overhead.py measures the GPU: no HIP device")
     out = {"block": a.block, "horizon": a.horizon, "seeds": "42 + i", "steps_per_round": a.steps, "rounds": a.rounds,
            "sizes": [measure(n, a) for n in a.n]}
-    line = json.dumps(out)
-    print(line)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
+    write_line(out, a.out)
 
 
 if __name__ == "__main__":

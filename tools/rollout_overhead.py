@@ -18,18 +18,16 @@ Reported per setup: the per-step time of each block (median, quartiles, min..max
 and whether the device path is below the by-hand one -- as measured, whichever way it falls.
 
 --parent DIR: a checkout of the parent commit, built.  `off` is then also measured in fresh processes, alternately on this build and on
-the parent's (this script run with --package-root and --only-off), `--process-repeats` times each: off agrees with the parent if the
-medians of the two differ by no more than the run-to-run spread (the largest of the parent's processes', this build's processes' and
-this handle's blocks'); `off_within_the_parents_own_spread` holds the same difference against the spread between the parent's runs
-alone.  One JSON line per run, all sizes in one object, also written to --out.
+the parent's (this script run with --package-root and --only-off), `--process-repeats` times each, and held against each other by
+overhead_harness.compare_off.  One JSON line per run, all sizes in one object, also written to --out.
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
+
+from overhead_harness import add_parent_arguments, compare_off, head, off_across_builds, paired, rotated_blocks, stats, time_steps, write_line
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W = 8
@@ -119,15 +117,6 @@ def measure(n, rounds, only_off, calls):
             return by_hand.step(x)
         return env.step()
 
-    def timed(setup, steps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        for _ in range(steps):
-            step(setup)
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b) * 1e3 / steps
-
     def run_block(setup):
         if has:
             if setup == "on":
@@ -146,30 +135,14 @@ def measure(n, rounds, only_off, calls):
         else:
             for _ in range(W):
                 step(setup)
-        return timed(setup, T)
+        return time_steps(stream, lambda: step(setup), T)
 
-    for s in setups:      # warm-up
-        run_block(s)
-    blocks = {s: [] for s in setups}
-    for r in range(rounds):
-        k = r % len(setups)
-        for s in setups[k:] + setups[:k]:
-            blocks[s].append(run_block(s))
-    torch.cuda.synchronize(dev)
-
-    def stats(v):
-        v = np.asarray(v)
-        return {"median_us": float(np.median(v)), "p25_us": float(np.percentile(v, 25)), "p75_us": float(np.percentile(v, 75)),
-                "min_us": float(v.min()), "max_us": float(v.max()), "blocks": int(v.size)}
-
-    def paired(a, b):
-        d = np.asarray(blocks[a]) - np.asarray(blocks[b])      # the same round's blocks
-        return {"median": float(np.median(d)), "min": float(d.min()), "max": float(d.max())}
+    blocks = rotated_blocks(setups, rounds, run_block)
     out = {"n_plants": n, "device": torch.cuda.get_device_name(dev), "step_kernel": env.last_step_kernel(), "block_steps": T, "rounds": rounds,
            "features": [K, C], "axes": len(AXES), "extras": E, "max_episode_steps": L, "setups": {s: stats(v) for s, v in blocks.items()}}
     if has:
-        out["on_cost_us_per_step"] = paired("on", "off")
-        out["by_hand_in_torch_cost_us_per_step"] = paired("torch", "off")
+        out["on_cost_us_per_step"] = paired(blocks, "on", "off")
+        out["by_hand_in_torch_cost_us_per_step"] = paired(blocks, "torch", "off")
         out["on_percent_of_the_step"] = 100.0 * out["on_cost_us_per_step"]["median"] / out["setups"]["off"]["median_us"]
         out["on_is_below_by_hand"] = bool(out["on_cost_us_per_step"]["median"] < out["by_hand_in_torch_cost_us_per_step"]["median"])
         # (c): a full horizon recorded, then the advantages on the device and as a torch loop over the same tensors
@@ -187,17 +160,13 @@ def measure(n, rounds, only_off, calls):
             if which == "advantages":
                 return env.rollout_advantages(GAMMA, LAM, values=("extra", 0), last_value=last, final_values=final)
             return advantages_in_torch(torch, r["reward"], r["ended"], r["final_row"], value, last, final, GAMMA, LAM)
-        times = {"advantages": [], "advantages_torch": []}
+        times, res = {"advantages": [], "advantages_torch": []}, {}
+
+        def keep(which):
+            res[which] = call(which)
         for which in times:
-            for k in range(W // 2 + calls):
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record(stream)
-                res = call(which)
-                b.record(stream)
-                b.synchronize()
-                if k >= W // 2:
-                    times[which].append(a.elapsed_time(b) * 1e3)
-            times[which] = (times[which], [t.clone() for t in res])
+            us = [time_steps(stream, lambda: keep(which), 1) for _ in range(W // 2 + calls)]
+            times[which] = (us[W // 2:], [t.clone() for t in res[which]])
         same = all(torch.equal(p.view(torch.int32), q.view(torch.int32)) for p, q in zip(times["advantages"][1], times["advantages_torch"][1]))
         out["advantages"] = {"slots": T, "truncated_transitions": int((r["ended"] == 2).sum().item()), "device": stats(times["advantages"][0]),
                              "torch_loop": stats(times["advantages_torch"][0]), "the_two_agree_by_bits": bool(same),
@@ -212,11 +181,7 @@ def main():
     ap.add_argument("--n", type=int, nargs="+", default=[65536, 32768])
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--calls", type=int, default=20, help="timed calls of each advantages path")
-    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit: `off` across the two builds")
-    ap.add_argument("--process-repeats", type=int, default=2)
-    ap.add_argument("--package-root", default=ROOT, help="where nuclear_sim_amd is imported from (used for the parent's build)")
-    ap.add_argument("--only-off", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rollout_overhead.json"))
+    add_parent_arguments(ap, "rollout_overhead.json")
     a = ap.parse_args()
     sys.path.insert(0, a.package_root)
     sizes = {}
@@ -224,36 +189,15 @@ def main():
         res = measure(n, a.rounds, a.only_off, a.calls)
         print("%d plants: measured" % n, file=sys.stderr, flush=True)
         if a.parent and not a.only_off:
-            runs = {"this": [], "parent": []}
-            for _ in range(a.process_repeats):
-                for which, root in (("this", ROOT), ("parent", os.path.abspath(a.parent))):
-                    cmd = [sys.executable, os.path.abspath(__file__), "--n", str(n), "--rounds", str(a.rounds), "--package-root", root, "--only-off", "--out", ""]
-                    p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-                    if p.returncode != 0:
-                        raise SystemExit("the %s build's run failed:\n%s" % (which, p.stderr[-2000:]))
-                    runs[which].append(json.loads(p.stdout.strip().splitlines()[-1])["sizes"][str(n)]["setups"]["off"]["median_us"])
-                    print("%d plants: off of the %s build in a fresh process" % (n, which), file=sys.stderr, flush=True)
-            spread_parent = max(runs["parent"]) - min(runs["parent"])
-            spread = max(max(runs["this"]) - min(runs["this"]), spread_parent, res["setups"]["off"]["max_us"] - res["setups"]["off"]["min_us"])
-            diff = float(np.median(runs["parent"]) - np.median(runs["this"]))
-            res["parent_comparison"] = {"off": {"this_medians_us": runs["this"], "parent_medians_us": runs["parent"], "parent_minus_this_us": diff,
-                                                "parent_spread_us": float(spread_parent), "spread_us": float(spread), "off_agrees": bool(abs(diff) <= spread),
-                                                "off_within_the_parents_own_spread": bool(abs(diff) <= spread_parent)}}
+            this, parent = off_across_builds(__file__, ["--n", n, "--rounds", a.rounds], a.parent, a.process_repeats,
+                                             lambda run: run["sizes"][str(n)]["setups"]["off"]["median_us"], 900)
+            res["parent_comparison"] = {"off": compare_off(this, parent, res["setups"]["off"])}
         sizes[str(n)] = res
-    try:
-        head = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        head = None
     out = {"what": "per-step time of config 4 with device noise and autoreset (max_episode_steps 64), features of 16 columns x 4 frames float32, "
                    "controls of 4 axes: the rollout (T = 128, E = 2) off and on; the same recording done by hand in torch on the same build "
                    "beside it; and rollout_advantages against the same recurrence as a torch loop over T",
-           "sizes": sizes, "head": head}
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+           "sizes": sizes, "head": head(ROOT)}
+    write_line(out, a.out)
 
 
 if __name__ == "__main__":

@@ -3,9 +3,8 @@
 action_test("oil_top_off", range(n), dt = 5) with autoreset from a bank of `--bank` scenarios, device noise and a constant setpoint: no
 per-step host input.  The task has 8 terms -- the step's reward, an info column against a constant, an obs column against another, a
 limit and an excess on carried members, the trip flags' pump bits, and the deltas of the event count and of an oil level -- and 3 rules:
-the scram pulse, a limit on the plant clock, and NONFINITE on the reward.  One handle per size throughout (where an arena lands in
-physical memory moves the step time from one handle to the next); the task is set and dropped on it between blocks, in an order that
-rotates from round to round.  Setups, event-timed us per step:
+the scram pulse, a limit on the plant clock, and NONFINITE on the reward.  One handle per size throughout; the task is set and dropped on it
+between blocks, in an order that rotates from round to round.  Setups, event-timed us per step:
   off        no task, no episode ending
   quiet      task on, nothing firing (the clock limit is never reached): the one launch behind every step
   terms      the same with keep_terms: 8 more stores per plant
@@ -19,18 +18,16 @@ What the bytes say: the quiet launch reads about 11 values and the bookkeeping a
 previous samples per plant, some 150 B: 10 MB at 65 536 plants against the step's 451 MB.
 
 --parent DIR: a checkout of the parent commit, built.  `off` is then also measured in fresh processes, alternately on this build and on
-the parent's (this script run with --package-root and --only-off), `--process-repeats` times each: off agrees with the parent if the
-medians of the two differ by no more than the run-to-run spread (the largest of the parent's processes', this build's processes' and
-this handle's blocks').  bench.py is run alternately from the two trees and its ms per step printed beside it.  One JSON line per run,
-all sizes in one object, also written to --out.
+the parent's (this script run with --package-root and --only-off), `--process-repeats` times each, and held against each other by
+overhead_harness.compare_off.  bench.py is run alternately from the two trees and its ms per step printed beside it.  One JSON line per
+run, all sizes in one object, also written to --out.
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 
-import numpy as np
+from overhead_harness import (add_parent_arguments, bench_alternated, compare_off, head, off_across_builds, paired, rotated_blocks, stats,
+                              time_steps, write_line)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W = 8
@@ -63,15 +60,6 @@ def measure(n, block, rounds, bank, only_off):
     clock = {"quiet": 1e30, "terms": 1e30, "busy": DT * EPISODE - 0.5 * DT}
     rates, by_task = {}, {}
 
-    def timed(steps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        for _ in range(steps):
-            env.step(power_setpoint=sp)
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b) * 1e3 / steps
-
     def run_block(setup):
         busy = setup in ("busy", "busy_off")
         if has:
@@ -91,57 +79,27 @@ def measure(n, block, rounds, bank, only_off):
             env.step(power_setpoint=sp)
         first = env.step(power_setpoint=sp)
         before = first[3]["episode_index"].sum().item()
-        us = timed(block)
+        us = time_steps(stream, lambda: env.step(power_setpoint=sp), block)
         last = env.step(power_setpoint=sp)
         rates[setup] = 100.0 * (last[3]["episode_index"].sum().item() - before) / (block + 1) / n
         if setup in clock:      # of this last step: plants the task ended, in percent
             by_task[setup] = 100.0 * float((last[3]["task_cause"] != 0).sum().item()) / n
         return us
 
-    for s in setups:      # warm-up
-        run_block(s)
-    blocks = {s: [] for s in setups}
-    for r in range(rounds):
-        k = r % len(setups)
-        for s in setups[k:] + setups[:k]:
-            blocks[s].append(run_block(s))
-    torch.cuda.synchronize(dev)
-
-    def stats(v):
-        v = np.asarray(v)
-        return {"median_us": float(np.median(v)), "p25_us": float(np.percentile(v, 25)), "p75_us": float(np.percentile(v, 75)),
-                "min_us": float(v.min()), "max_us": float(v.max()), "blocks": int(v.size)}
-
-    def paired(a, b):
-        d = np.asarray(blocks[a]) - np.asarray(blocks[b])      # the same round's blocks
-        return {"median": float(np.median(d)), "min": float(d.min()), "max": float(d.max())}
+    blocks = rotated_blocks(setups, rounds, run_block)
     out = {"n_plants": n, "device": torch.cuda.get_device_name(dev), "step_kernel": env.last_step_kernel(), "block_steps": block, "rounds": rounds,
            "bank_entries": bank, "terms": 8, "rules": 3, "setups": {s: stats(v) for s, v in blocks.items()},
            "ended_percent_of_plants_per_step": dict(rates), "ended_by_the_task_percent_of_plants_on_the_last_step": dict(by_task)}
     if has:
-        out["quiet_cost_us_per_step"] = paired("quiet", "off")
-        out["keep_terms_cost_us_per_step"] = paired("terms", "off")
-        out["one_percent_ending_cost_us_per_step"] = paired("busy", "busy_off")
-        out["column_stats_cost_us_per_step"] = paired("stats", "off")
-        out["event_windows_quiet_cost_us_per_step"] = paired("windows", "off")
+        out["quiet_cost_us_per_step"] = paired(blocks, "quiet", "off")
+        out["keep_terms_cost_us_per_step"] = paired(blocks, "terms", "off")
+        out["one_percent_ending_cost_us_per_step"] = paired(blocks, "busy", "busy_off")
+        out["column_stats_cost_us_per_step"] = paired(blocks, "stats", "off")
+        out["event_windows_quiet_cost_us_per_step"] = paired(blocks, "windows", "off")
         out["quiet_percent_of_the_step"] = 100.0 * out["quiet_cost_us_per_step"]["median"] / out["setups"]["off"]["median_us"]
         env.set_task(None)
     env.close()
     return out
-
-
-def bench_alternated(parent, repeats, steps, warmup):
-    """bench.py from this tree and from the parent's, alternately: ms per step of each run"""
-    runs = {"this": [], "parent": []}
-    for _ in range(repeats):
-        for which, root in (("this", ROOT), ("parent", parent)):
-            p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)],
-                               capture_output=True, text=True, timeout=900, cwd=root)
-            if p.returncode != 0:
-                raise SystemExit("bench.py of the %s tree failed:\n%s" % (which, p.stderr[-2000:]))
-            runs[which].append(json.loads(p.stdout.strip().splitlines()[-1])["ms_per_step"])
-    return {"steps": steps, "warmup": warmup, "this_ms_per_step": runs["this"], "parent_ms_per_step": runs["parent"],
-            "parent_minus_this_ms": float(np.median(runs["parent"]) - np.median(runs["this"]))}
 
 
 def main():
@@ -150,12 +108,8 @@ def main():
     ap.add_argument("--block", type=int, default=192)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--bank", type=int, default=64, help="entries of the start bank")
-    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit: `off` and bench.py across the two builds")
-    ap.add_argument("--process-repeats", type=int, default=2)
     ap.add_argument("--bench-steps", type=int, default=200)
-    ap.add_argument("--package-root", default=ROOT, help="where nuclear_sim_amd is imported from (used for the parent's build)")
-    ap.add_argument("--only-off", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "task_overhead.json"))
+    add_parent_arguments(ap, "task_overhead.json")
     a = ap.parse_args()
     sys.path.insert(0, a.package_root)
     sizes = {}
@@ -163,39 +117,17 @@ def main():
         res = measure(n, a.block, a.rounds, a.bank, a.only_off)
         print("%d plants: measured" % n, file=sys.stderr, flush=True)
         if a.parent and not a.only_off:
-            runs = {"this": [], "parent": []}
-            for _ in range(a.process_repeats):
-                for which, root in (("this", ROOT), ("parent", os.path.abspath(a.parent))):
-                    cmd = [sys.executable, os.path.abspath(__file__), "--n", str(n), "--block", str(a.block), "--rounds", str(a.rounds),
-                           "--bank", str(a.bank), "--package-root", root, "--only-off", "--out", ""]
-                    p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-                    if p.returncode != 0:
-                        raise SystemExit("the %s build's run failed:\n%s" % (which, p.stderr[-2000:]))
-                    runs[which].append(json.loads(p.stdout.strip().splitlines()[-1])["sizes"][str(n)]["setups"]["off"]["median_us"])
-                    print("%d plants: off of the %s build in a fresh process" % (n, which), file=sys.stderr, flush=True)
-            # this build's off, and the parent's, in fresh processes only: like against like
-            spread_parent = max(runs["parent"]) - min(runs["parent"])
-            spread = max(max(runs["this"]) - min(runs["this"]), spread_parent, res["setups"]["off"]["max_us"] - res["setups"]["off"]["min_us"])
-            diff = float(np.median(runs["parent"]) - np.median(runs["this"]))
-            res["parent_comparison"] = {"off": {"this_medians_us": runs["this"], "parent_medians_us": runs["parent"], "parent_minus_this_us": diff,
-                                                "parent_spread_us": float(spread_parent), "spread_us": float(spread), "off_agrees": bool(abs(diff) <= spread)}}
+            this, parent = off_across_builds(__file__, ["--n", n, "--block", a.block, "--rounds", a.rounds, "--bank", a.bank], a.parent, a.process_repeats,
+                                             lambda run: run["sizes"][str(n)]["setups"]["off"]["median_us"], 900)
+            res["parent_comparison"] = {"off": compare_off(this, parent, res["setups"]["off"])}
         sizes[str(n)] = res
-    try:
-        head = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        head = None
     out = {"what": "per-step time of config 4 with autoreset from a bank and device noise: a task of 8 reward terms and 3 termination rules off, "
                    "on with nothing firing, on with keep_terms, on with about 1 % of the plants ended by it per step; column statistics and "
                    "event windows of 8 columns each beside it, from the same run",
-           "sizes": sizes, "head": head}
+           "sizes": sizes, "head": head(ROOT)}
     if a.parent and not a.only_off:
-        out["bench"] = bench_alternated(os.path.abspath(a.parent), a.process_repeats, a.bench_steps, 20)
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+        out["bench"] = bench_alternated(a.parent, a.process_repeats, a.bench_steps, 20)
+    write_line(out, a.out)
 
 
 if __name__ == "__main__":

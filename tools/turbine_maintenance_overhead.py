@@ -19,11 +19,12 @@ import csv
 import glob
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import torch
+
+from overhead_harness import head, rotated_blocks, time_steps, write_line
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -76,23 +77,14 @@ def measure(n, B, rounds, only):
         env.restore()
         for t in range(W):
             iteration(name, t)
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        for k in range(B):
-            iteration(name, W + k)
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b) / B        # ms per iteration
+        t = iter(range(W, W + B))
+        return time_steps(stream, lambda: iteration(name, next(t)), B) / 1e3        # ms per iteration
 
     setups = [s for s in SETUPS if only in (None, s)]
-    for q in range(3):                      # clocks: ~100 ms of the same launches before anything is timed
+    for q in range(2):                      # clocks: with the rotation's own warm-up block, ~100 ms of the same launches before anything is timed
         for name in setups:
             run_block(name)
-    blocks = {s: [] for s in setups}
-    for r in range(rounds):
-        k = r % len(setups)
-        for name in setups[k:] + setups[:k]:
-            blocks[name].append(run_block(name))
+    blocks = rotated_blocks(setups, rounds, run_block)
     ordered = {name: int((orders[name] >= 0).sum().item()) for name in orders if only in (None, name)}
     kernel = env.last_step_kernel()
     env.close()
@@ -136,10 +128,6 @@ def main():
         res["kernel_trace"] = {"kernel": KERNEL, "what": "rocprofv3 --kernel-trace --stats, one run per batch size and setup: average duration of the kernel",
                                "by_plants": collect_traces(a.collect_traces)}
     else:
-        try:
-            head = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-        except OSError:
-            head = None
         res = {"what": "ms per iteration of step() alone and of step(); perform_turbine_maintenance(...) with no plant, 1 % of the plants and every plant "
                        "ordered (one type: the lubrication system's turbine_oil_change; mixed: a quarter each turbine routine_maintenance, bearing "
                        "replacement, lubrication oil change, stage overhaul), and of step(); perform_component_maintenance(...) with no plant ordered; "
@@ -147,13 +135,8 @@ def main():
                "device": torch.cuda.get_device_name(0), "block_iterations": a.block, "rounds": a.rounds,
                # a sweep of what an order touches: turb (35 eight-byte columns) read and written, or a stage's three columns
                "expected_bytes_per_plant_turb_order": 35 * 8 * 2, "expected_bytes_per_plant_stage_order": 3 * 8 * 2,
-               "by_plants": {str(n): measure(n, a.block, a.rounds, a.only) for n in a.n}, "head": head}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+               "by_plants": {str(n): measure(n, a.block, a.rounds, a.only) for n in a.n}, "head": head(ROOT)}
+    write_line(res, a.out)
 
 
 if __name__ == "__main__":

@@ -27,8 +27,9 @@ Everything else is reported, not gated; c_n16_scattered, c_n4_scattered and c_al
 import argparse
 import json
 import os
-import subprocess
 import sys
+
+from overhead_harness import fresh_process, head, stats, time_steps, write_line
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RING = 2
@@ -72,13 +73,8 @@ def worker(a):
             log.record(k, k * env.dt)
 
     def per_launch(log, iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for k in range(iters):
-            iteration(log, k)
-        e1.record(stream)
-        e1.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / iters       # us
+        k = iter(range(iters))
+        return time_steps(stream, lambda: iteration(log, next(k)), iters)
 
     def following_step(log, iters):
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
@@ -105,21 +101,21 @@ def worker(a):
         for name in names[r % len(names):] + names[:r % len(names)]:
             launch[name].append(per_launch(logs[name], a.block))
             follow[name].append(following_step(logs[name], a.block))
-    torch.cuda.synchronize(dev)
-    print("WORKER " + json.dumps({"per_launch_us": launch, "following_step_us": follow, "rows_per_sample": rows,
-                                  "n_watched": {name: len(ids) for name, ids in lists.items()},
-                                  "step_kernel": env.last_step_kernel(), "device": torch.cuda.get_device_name(dev)}))
+    info = {"per_launch_us": launch, "following_step_us": follow, "rows_per_sample": rows,
+            "n_watched": {name: len(ids) for name, ids in lists.items()},
+            "step_kernel": env.last_step_kernel(), "device": torch.cuda.get_device_name(dev)}
     for log in logs.values():
         if log is not None:
             log.close()
     env.close()
+    print(json.dumps(info))      # the worker's last line: what fresh_process reads
 
 
-def stats(v):
-    import numpy as np
-    v = np.asarray(v, dtype=float)
-    return {"median_us": float(np.median(v)), "p25_us": float(np.percentile(v, 25)), "p75_us": float(np.percentile(v, 75)),
-            "min_us": float(v.min()), "max_us": float(v.max()), "rounds": int(v.size)}
+def over_rounds(v):
+    """the harness's stats, its count named for what a value is here: one per round"""
+    s = stats(v)
+    s["rounds"] = s.pop("blocks")
+    return s
 
 
 def main():
@@ -137,18 +133,11 @@ def main():
     meta = {}
     for n in a.sizes:
         cmd = [sys.executable, os.path.abspath(__file__), "--worker", str(n), "--rounds", str(a.rounds), "--block", str(a.block)]
-        p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.worker_timeout)
-        if p.returncode != 0:      # nothing more is started on the device after a worker that failed
-            sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
-            raise SystemExit("the worker for %d plants failed with status %d" % (n, p.returncode))
-        w = [json.loads(ln[7:]) for ln in p.stdout.splitlines() if ln.startswith("WORKER ")]
-        if not w:
-            raise SystemExit("the worker for %d plants printed no result" % n)
-        w = w[0]
+        w = fresh_process(cmd, a.worker_timeout)
         meta = {"step_kernel": w["step_kernel"], "device": w["device"]}
         cases = {}
         for name in w["per_launch_us"]:
-            cases[name] = {"per_launch": stats(w["per_launch_us"][name]), "following_step": stats(w["following_step_us"][name]),
+            cases[name] = {"per_launch": over_rounds(w["per_launch_us"][name]), "following_step": over_rounds(w["following_step_us"][name]),
                            "rows_per_sample": w["rows_per_sample"][name], "n_watched": w["n_watched"].get(name)}
         med = lambda name: cases[name]["per_launch"]["median_us"]
         full_cost = med("b") - med("a")
@@ -167,16 +156,8 @@ def main():
     if "65536" in sizes:
         c = sizes["65536"]
         res["gate_1024_scattered_under_half_of_full_at_65536"] = bool(c["c_1024_scattered"]["sample_cost_us"] < 0.5 * c["b"]["sample_cost_us"])
-    try:
-        res["head"] = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        res["head"] = None
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    res["head"] = head(ROOT)
+    write_line(res, a.out)
     return 0 if res.get("gate_1024_scattered_under_half_of_full_at_65536", True) else 1
 
 
