@@ -994,7 +994,8 @@ NPB_API int npb_set_episode_record_task(NpbHandle *h, int32_t *cause /* device [
  * BITS on a real-valued column, or with mask 0; a NaN scale, ref, lo, hi or fresh; lo > hi; an unknown out type; a NULL or misaligned
  * out, or a misaligned final (4-byte for float, 8-byte for double).
  * No step, restore or episode kernel changes.  Not here: the terminal stack in the episode records, half-precision output, a delta or rate
- * kind (the stack carries it), running statistics updated on the device.
+ * kind (the stack carries it).  Running statistics updated on the device have the normaliser's section below (npb_set_normalizer), which
+ * rewrites `ref` and `scale` of the columns it is given in front of pass A.
  * NPB_VERSION stays 154: a binding detects the entry points by name.  A handle that never calls this behaves as before in every entry
  * point. */
 #define NPB_FEATURES_COLS_MAX 64
@@ -1263,8 +1264,9 @@ NPB_API int npb_rollout_advantages(NpbHandle *h, const npb_rollout_advantages_de
  *   moments, the element size for adv, ret and their outputs, 4 for index).
  * A handle that never calls these behaves as before in every entry point.  Not here: half or bfloat16 outputs, weighted or prioritised
  * sampling, sampling with replacement, masks over transitions, a checkpoint of a half-drained epoch (the epoch IS (seed, epoch, first):
- * three numbers the caller has), V-trace, running normalisation across rollouts, gathering final_obs (its use ended in
- * npb_rollout_advantages).  NPB_VERSION stays 154: a binding detects the entry points by name. */
+ * three numbers the caller has), V-trace, gathering final_obs (its use ended in npb_rollout_advantages).  Running normalisation across
+ * rollouts has the normaliser's section below (npb_set_normalizer), which shares this section's tree.  NPB_VERSION stays 154: a binding
+ * detects the entry points by name. */
 #define NPB_MINIBATCH_ROUNDS 6
 enum { NPB_MINIBATCH_TRANSITION = 0, NPB_MINIBATCH_PLANT = 1 };
 typedef struct npb_moments_desc_t {
@@ -1292,6 +1294,81 @@ NPB_API int npb_rollout_moments(NpbHandle *h, const npb_moments_desc_t *desc, vo
 NPB_API int npb_rollout_permutation(NpbHandle *h, int64_t N, const uint32_t *keys, int64_t first, int64_t count, int32_t *out, void *stream);
 NPB_API int npb_rollout_minibatch(NpbHandle *h, const npb_minibatch_desc_t *desc, void *stream);
 NPB_API const char *npb_minibatch_check(const npb_minibatch_desc_t *desc, int n_plants, int t, int features_cells, int n_axes, int n_extras);
+
+/* The normaliser: running observation and reward normalisation on the device -- what VecNormalize gives a PPO user, with the order of every
+ * addition pinned.  An optional per-handle attachment.  While it is on and training, every npb_step folds this step's raw samples into
+ * running statistics (count, mean, M2 per stream) and writes ref = mean and scale = 1 / sqrt(var + eps) into the features' device column
+ * table BEFORE the features' pass A runs: the frame the policy sees is normalised with statistics that include it.  Optionally it keeps a
+ * per-plant discounted return, folds that as one more stream, and writes a normalised reward.  nuclear_sim_amd/normalizer.py states all
+ * of it in numpy, and that statement is the contract; the device produces its bits for every n_plants, storage type and launch geometry.
+ * Streams, S of them: the chosen columns of the features (indices into npb_features_desc_t.columns, at most NPB_FEATURES_COLS_MAX, each
+ * NPB_FEATURE_AFFINE with a constant ref), then, with reward != 0, the return stream.  Per stream three doubles, count, mean, M2, all 0 at
+ * the start.
+ * One fold over the n plants, stream c with raw sample x[p] (the column's value before any transform, widened to double as the features
+ * widen it; for the return stream ret[p], below):
+ *     shift = count[c] > 0 ? mean[c] : the column's own ref (the return stream: 0.0)
+ *     d = x[p] - shift;  q = d * d                          each rounded (-ffp-contract=off)
+ *     a sample counts iff q - q == 0.0                      not a NaN, an infinity or a square that overflows; one that does not count
+ *                                                           contributes +0.0, +0.0 and count 0: a bad value never poisons a statistic
+ *     s1 = tree(d), s2 = tree(q)                            the tree of npb_rollout_moments over the plants in order: groups of 256
+ *                                                           padded with +0.0, the halves 128 .. 1, then the further levels
+ *     cnt = the samples that count;  N = count + cnt
+ *     if cnt > 0: mean = shift + s1 / N;  M2 = (M2 + s2) - (s1 * s1) / N, 0.0 where that is negative      IEEE division
+ *     count = N
+ *   Chan's merge with the batch taken around the running mean (normalizer.py derives it); from count == 0 it is the plain shifted-data
+ *   formula around the column's ref.  The features' table then holds ref = mean, scale = 1.0 / sqrt(M2 / count + eps) (IEEE root and
+ *   division) where count > 0, else the column's own ref and scale; lo, hi, nan_to stay the column's: the clip of the normalised
+ *   observation is the column's clip.
+ * The return stream (gamma, clip): per plant ret (double) and primed / seen as the features use them, and ended, this step's done[p] != 0.
+ *     carry = primed && episode_index == seen && !ended (of the step before);  ret = (carry ? ret * gamma : 0.0) + r
+ *   with ret * gamma rounded before the sum; r and done are the task's while a task is set, else the step's.  Behind fold and merge
+ *     norm_reward[p] = r * rscale, then y = y < -clip ? -clip : y, y = y > clip ? clip : y (a NaN passes both)
+ *   rscale = 1.0 / sqrt(M2 / count + eps) of the return stream (1.0 while its count is 0); the mean is not subtracted.  A truncation, an
+ *   autoreset or a caller's reset / restore shows as a changed episode index.  A handle WITHOUT autoreset (npb_set_autoreset) carries no
+ *   episode index: the index then always counts as the one seen and the carry is kept, so a caller that restarts plants itself
+ *   (npb_reset, npb_restore) calls npb_normalizer_clear for them.
+ * Fresh frames (the features' pass B and the priming) are not folded: they are normalised with the table as it stands.
+ * npb_normalizer_training(h, 0) freezes: no fold and no table write, the two fold launches are skipped; norm_reward is still written, with
+ * the frozen scale, and ret is still carried.
+ * With the normaliser training npb_step launches two kernels more, three with the return stream, behind the task kernel and in front of
+ * the features' pass A: the partials kernel (npd_normalizer.h; a workgroup of 256 per 256 plants = one group of the tree, the differences
+ * and squares through LDS, eight streams a pass, counts by ballot; no division, no atomics, no scratch), the finish kernel
+ * (npb_minibatch.hip, built with IEEE division and root: one workgroup ends the tree over the partials, merges, writes the state and,
+ * one lane per stream, ref and scale into the features' table) and the reward kernel (one lane per plant).  With the return stream
+ * npb_launch_rollout_post records norm_reward in place of the reward; the episode kernel, episode_return, the episode records, the
+ * statistics and the windows keep the raw reward.  Nothing else in the sequence moves.
+ * npb_set_normalizer(h, desc): desc = NULL turns it off, and the features' table gets the columns' own ref and scale back.  The state
+ * starts at zero.  NPB_EINVAL with the reason in npb_last_error, before any device work, for what npb_normalizer_check refuses -- that
+ * check alone, without a handle (features_desc: the features it would sit on, or NULL), NULL = accepted, else the reason: n_plants < 1;
+ * columns chosen while no features are set; a column count out of range or without its array; a column index out of range or named
+ * twice; a NPB_FEATURE_BITS column or one whose ref is a second column; a NaN or negative eps; gamma a NaN or outside [0, 1]; clip a NaN
+ * or not positive; a NULL or misaligned norm_reward; neither columns nor reward.  On the handle: npb_set_normalizer while a rollout is set
+ * (set the normaliser first); npb_set_features, set and NULL alike, while a normaliser with columns is on; npb_set_task, set and NULL
+ * alike, while the return stream reads the task's reward; npb_step without a reward or done column while the return stream is on.
+ * npb_normalizer_get_state / npb_normalizer_set_state move count, mean, M2 (double [S] each) and, with the return stream, ret (double
+ * [n_plants]), primed, seen, ended (int32 [n_plants] each; NULL without it) to and from host arrays, synchronous on `stream`; set_state
+ * is followed by one finish launch without a batch, so that the table follows a loaded state (a dry run's statistics warm-start a run).
+ * npb_normalizer_clear(h, mask, stream): the plants of mask (device uint8 [n_plants], NULL = all) start a new return on their next step.
+ * These return NPB_EINVAL when no normaliser is set.  npb_destroy drops it.
+ * Not here: statistics over fresh frames; per-plant statistics (npb_set_column_stats has them); an exponential-moving-average variant;
+ * half types; synchronising shards on the device (normalizer.merge is the host answer); normalising BITS or setpoint-error columns.
+ * NPB_VERSION stays 154: a binding detects the entry points by name.  A handle that never calls this behaves as before in every entry
+ * point. */
+typedef struct npb_normalizer_desc_t {
+  int n_columns; const int *columns;      /* host: indices into the features' columns; 0 / NULL = the return stream alone */
+  double eps;
+  int reward;                    /* != 0: the return stream */
+  double gamma, clip;
+  double *norm_reward;           /* device [n_plants]; with reward */
+} npb_normalizer_desc_t;
+NPB_API int npb_set_normalizer(NpbHandle *h, const npb_normalizer_desc_t *desc);
+NPB_API const char *npb_normalizer_check(const npb_normalizer_desc_t *desc, int n_plants, const npb_features_desc_t *features_desc);
+NPB_API int npb_normalizer_training(NpbHandle *h, int on);
+NPB_API int npb_normalizer_get_state(NpbHandle *h, double *count, double *mean, double *M2, double *ret, int32_t *primed, int32_t *seen,
+                                     int32_t *ended, void *stream);
+NPB_API int npb_normalizer_set_state(NpbHandle *h, const double *count, const double *mean, const double *M2, const double *ret,
+                                     const int32_t *primed, const int32_t *seen, const int32_t *ended, void *stream);
+NPB_API int npb_normalizer_clear(NpbHandle *h, const uint8_t *mask, void *stream);
 
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the

@@ -923,6 +923,12 @@ class NpbMinibatchDesc(ctypes.Structure):
                 ("extra", ctypes.c_void_p), ("adv_out", ctypes.c_void_p), ("ret_out", ctypes.c_void_p), ("max_blocks", ctypes.c_int)]
 
 
+class NpbNormalizerDesc(ctypes.Structure):
+    """npb_normalizer_desc_t: the chosen feature columns (a host array of indices), eps, and the return stream's gamma, clip and output"""
+    _fields_ = [("n_columns", ctypes.c_int), ("columns", ctypes.POINTER(ctypes.c_int)), ("eps", ctypes.c_double), ("reward", ctypes.c_int),
+                ("gamma", ctypes.c_double), ("clip", ctypes.c_double), ("norm_reward", ctypes.c_void_p)]
+
+
 def controls_request(axes, interval: int = 1, dtype="float32", heat_source: int = 0) -> dict:
     """What ``BatchedPlantEnv.set_controls`` asks of npb_set_controls, from the caller's words; a pure function, host only, so an axis that
     cannot work is refused (ValueError, naming it) before any device work.
@@ -1217,6 +1223,14 @@ def load():
         L.npb_rollout_steps.argtypes = [vp]
         L.npb_rollout_cut.argtypes = [vp, vp, vp]
         L.npb_rollout_advantages.argtypes = [vp, ctypes.POINTER(NpbRolloutAdvantagesDesc), vp]
+    if hasattr(L, "npb_set_normalizer"):     # running observation and reward normalisation, folded behind every step
+        L.npb_set_normalizer.argtypes = [vp, ctypes.POINTER(NpbNormalizerDesc)]
+        L.npb_normalizer_check.argtypes = [ctypes.POINTER(NpbNormalizerDesc), ci, ctypes.POINTER(NpbFeaturesDesc)]
+        L.npb_normalizer_check.restype = ctypes.c_char_p
+        L.npb_normalizer_training.argtypes = [vp, ci]
+        L.npb_normalizer_clear.argtypes = [vp, vp, vp]
+        L.npb_normalizer_get_state.argtypes = [vp] * 9
+        L.npb_normalizer_set_state.argtypes = [vp] * 9
     if hasattr(L, "npb_rollout_minibatch"):     # pinned moments, the keyed permutation and the minibatch gather over a rollout
         L.npb_rollout_moments.argtypes = [vp, ctypes.POINTER(NpbMomentsDesc), vp]
         L.npb_rollout_permutation.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64, ctypes.c_int64, vp, vp]

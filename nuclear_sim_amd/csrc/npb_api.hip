@@ -86,6 +86,10 @@ struct NpbHandle {
   npb_task_t task; bool ert_on; int32_t *ert_cause;
   /* npb_set_features: the columns and the bookkeeping on the device (base feat.cols) and the caller's tensors */
   npb_features_t feat;
+  std::vector<npb_feature_col_t> feat_host;      /* the table as npb_set_features uploaded it: the columns' own ref and scale */
+  /* npb_set_normalizer: the streams, the running statistics, the return carry and the partials on the device (base norm.streams), the
+   * caller's norm_reward, and whether a step folds (npb_normalizer_training) */
+  npb_normalizer_t norm; bool norm_training;
   /* npb_set_controls: the axes, the caller's tensors and the handle's bookkeeping and input columns (base ctl.age); ctl_axis[input]: the
    * axis that fills that input column, -1 = none */
   npb_controls_t ctl; int ctl_axis[NPB_CONTROL_INPUT_COUNT];
@@ -125,7 +129,7 @@ struct DeviceGuard {
 #define NPB_HIP(h, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(h, NPB_EHIP, #call, e__); } while (0)
 static int fail_who(NpbHandle *h, const char *who, const char *what) { return fail(h, NPB_EINVAL, (std::string(who) + what).c_str()); }
 
-/* ---- the lifecycle the per-step attachments share (column statistics, event windows, task, features, controls, rollout).  Each keeps its tables
+/* ---- the lifecycle the per-step attachments share (column statistics, event windows, task, features, controls, rollout, normaliser).  Each keeps its tables
  * and per-plant bookkeeping in one device allocation, whose base is the struct's "is it on" pointer.  npb_set_* = attachment_alloc, fill
  * the struct from the base, attachment_drop the old one, assign; off and npb_destroy = attachment_drop; npb_*_clear = attachment_clear;
  * npb_*_get_state / npb_*_set_state = that attachment's StateParts through state_copy */
@@ -159,6 +163,7 @@ static const char *const g_no_task = ": no task set (npb_set_task first)";
 static const char *const g_no_features = ": no features set (npb_set_features first)";
 static const char *const g_no_controls = ": no controls set (npb_set_controls first)";
 static const char *const g_no_rollout = ": no rollout set (npb_set_rollout first)";
+static const char *const g_no_normalizer = ": no normaliser set (npb_set_normalizer first)";
 /* npb_set_features / npb_set_controls while a rollout is set, set and NULL alike: its pre kernel copies their tensors, in the shapes it was bound with */
 static const char *const g_rollout_holds = ": a rollout is set (npb_set_rollout) and records this tensor every step; npb_set_rollout(h, NULL) first";
 /* the body of an npb_*_clear: refused with `off` unless the attachment is on, then its launch on the handle's device */
@@ -173,7 +178,7 @@ template <class Launch> static int attachment_clear(NpbHandle *h, const char *wh
  * set_state take them, stated once for both directions; a part that may be absent is one the caller may pass NULL for (`null_note` says
  * which) */
 struct StatePart { void *dev; size_t bytes; bool may_be_absent; };
-struct StateParts { const void *on; const char *off, *null_note; int count; StatePart part[5]; };
+struct StateParts { const void *on; const char *off, *null_note; int count; StatePart part[7]; };
 static int state_copy(NpbHandle *h, const char *who, StateParts (*parts_of)(const NpbHandle *), std::initializer_list<const void *> host,
                       bool to_device, void *stream) {
   if (!h) return NPB_EINVAL;
@@ -594,7 +599,7 @@ int npb_destroy(NpbHandle *h) {
   if (h->ers_dev) (void)hipFree(h->ers_dev);
   attachment_drop(&h->cs, h->cs.cols); attachment_drop(&h->ew, h->ew.cols); attachment_drop(&h->task, h->task.terms);
   attachment_drop(&h->feat, h->feat.cols); attachment_drop(&h->ctl, h->ctl.age); attachment_drop(&h->ro, h->ro.n_final);
-  attachment_drop(&h->mom, h->mom.ws);
+  attachment_drop(&h->mom, h->mom.ws); attachment_drop(&h->norm, h->norm.streams);
   for (Sampler *sm : h->samplers) if (sm) { (void)hipFree(sm->dev); delete sm; }
   delete h;
   return NPB_OK;
@@ -1144,6 +1149,8 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
         h->ro.D.final_rows < (h->ro.D.horizon + h->max_episode_steps - 1) / h->max_episode_steps)
       return fail(h, NPB_EINVAL, "npb_step: the rollout's final_rows is below ceil(horizon / max_episode_steps): a truncated plant would find no row for its terminal stack (npb_set_rollout)");
   }
+  if (h->norm.streams && h->norm.reward_on && !h->task.terms && (!reward || !done))      /* (a task brings its own) */
+    return fail(h, NPB_EINVAL, "npb_step: a normaliser with the return stream is set (npb_set_normalizer) and reads the reward and done columns: they must not be NULL");
   /* what the autoreset's restores take along beside the arena, from the bank while it has slots, else from the snapshot.  The step
    * reports a source without the diagnostics rows first, then the component maintenance's own needs, then a source without its state */
   const bool from_bank = h->bank && h->next_slot;
@@ -1224,10 +1231,21 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
   if (h->ew.cols)      /* the same sample into every plant's ring, the triggers, the windows that are due -- or cut short by an episode that ends here */
     h->K->event_windows(h->f64, NPB_N(h), &h->ew, h->n_plants, h->ew_step++, h->ep_index, h->autoreset ? h->ep_len : nullptr, done,
                         h->max_episode_steps, (hipStream_t)stream);
+  const double *recorded_reward = reward;
+  if (h->norm.streams) {      /* the running statistics take this step's samples and rewrite ref and scale in the features' table, in front of pass A */
+    if (h->norm_training) {
+      h->K->normalizer(h->f64, NPB_N(h), &h->norm, h->n_plants, h->ep_index, reward, (hipStream_t)stream);
+      npb_launch_normalizer_finish(&h->norm, (h->n_plants + 255) / 256, (hipStream_t)stream);
+    }
+    if (h->norm.reward_on) {      /* the reward the learner sees; everything that deals with episodes keeps the raw one */
+      npb_launch_normalizer_reward(&h->norm, h->n_plants, h->ep_index, reward, done, !h->norm_training, (hipStream_t)stream);
+      recorded_reward = h->norm.norm_reward;
+    }
+  }
   if (h->feat.cols)      /* pass A: this step's frame into every plant's stack, while everything still describes the episode it belongs to */
     h->K->features(h->f64, NPB_N(h), &h->feat, h->n_plants, 0, h->ep_index, (hipStream_t)stream);
   if (h->ro.n_final) {      /* the rollout's slot t: reward, outcome and the truncated plants' stacks, terminal frame included, while the carried length is the old one */
-    npb_launch_rollout_post(&h->ro, h->feat.out, reward, done, h->autoreset ? h->ep_len : nullptr, h->autoreset ? h->ep_index : nullptr,
+    npb_launch_rollout_post(&h->ro, h->feat.out, recorded_reward, done, h->autoreset ? h->ep_len : nullptr, h->autoreset ? h->ep_index : nullptr,
                             h->max_episode_steps, h->n_plants, (hipStream_t)stream);
     h->ro.t++;
   }
@@ -1891,6 +1909,8 @@ int npb_set_task(NpbHandle *h, const npb_task_desc_t *desc) {
   if (!h) return NPB_EINVAL;
   if (h->ert_on)
     return fail(h, NPB_EINVAL, "npb_set_task: episode records that copy the task's cause word are on (npb_set_episode_record_task) and hold its cause column; drop that first");
+  if (h->task.terms && h->norm.streams && h->norm.reward_on)
+    return fail(h, NPB_EINVAL, "npb_set_task: a normaliser is set (npb_set_normalizer) whose return stream reads the task's reward; npb_set_normalizer(h, NULL) first");
   if (const char *why = npb_task_check(desc, h->n_plants)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
   if (!desc) { attachment_drop(&h->task, h->task.terms); return NPB_OK; }
@@ -2006,9 +2026,11 @@ const char *npb_features_check(const npb_features_desc_t *D, int n_plants) {
 int npb_set_features(NpbHandle *h, const npb_features_desc_t *desc) {
   if (!h) return NPB_EINVAL;
   if (h->ro.n_final) return fail_who(h, "npb_set_features", g_rollout_holds);
+  if (h->norm.streams && h->norm.n_cols)
+    return fail(h, NPB_EINVAL, "npb_set_features: a normaliser with columns is set (npb_set_normalizer) and rewrites this table every step; npb_set_normalizer(h, NULL) first");
   if (const char *why = npb_features_check(desc, h->n_plants)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
-  if (!desc) { attachment_drop(&h->feat, h->feat.cols); return NPB_OK; }
+  if (!desc) { attachment_drop(&h->feat, h->feat.cols); h->feat_host.clear(); return NPB_OK; }
   /* the allocation: [the columns] | primed [n] | seen [n] */
   std::vector<npb_feature_col_t> table(NPB_FEATURES_COLS_MAX);
   for (int c = 0; c < desc->n_columns; c++) {
@@ -2036,6 +2058,7 @@ int npb_set_features(NpbHandle *h, const npb_features_desc_t *desc) {
   F.primed = (int32_t *)(dev + table_bytes); F.seen = F.primed + n;
   attachment_drop(&h->feat, h->feat.cols);
   h->feat = F;
+  h->feat_host = table;
   return NPB_OK;
 }
 int npb_features_prime(NpbHandle *h, void *stream) {
@@ -2222,6 +2245,140 @@ int npb_rollout_advantages(NpbHandle *h, const npb_rollout_advantages_desc_t *A,
     return fail(h, NPB_EINVAL, "npb_rollout_advantages: the rollout keeps terminal stacks (final_rows > 0) and final_value, the caller's value of them, is NULL");
   NPB_USE_DEVICE(h);
   npb_launch_rollout_advantages(&h->ro, A, A->gamma * A->lam, h->n_plants, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+
+/* ---- the normaliser (include/npb.h, npd_normalizer.h, npb_minibatch.hip): running statistics of the features' raw columns and of the
+ * discounted return, folded behind every step.  What a column of the features is to it: its kind and whether its ref is a second column --
+ * read off the caller's descriptor by the check without a handle, off the handle's host table by npb_set_normalizer */
+struct NormFeatures { int n; int kind[NPB_FEATURES_COLS_MAX]; int ref_col[NPB_FEATURES_COLS_MAX]; };
+static const char *normalizer_refusal(const npb_normalizer_desc_t *D, int n_plants, const NormFeatures *F) {
+  if (!D) return nullptr;
+  if (n_plants < 1) return "npb_set_normalizer: n_plants must be >= 1";
+  if (D->n_columns < 0 || D->n_columns > NPB_FEATURES_COLS_MAX || (D->n_columns > 0 && !D->columns))
+    return "npb_set_normalizer: the column count must be 0 .. NPB_FEATURES_COLS_MAX (64), with their indices";
+  if (D->n_columns == 0 && !D->reward) return "npb_set_normalizer: neither columns nor reward: nothing to normalise";
+  if (D->n_columns > 0 && !F) return "npb_set_normalizer: columns chosen while no features are set (npb_set_features first)";
+  bool taken[NPB_FEATURES_COLS_MAX] = {};
+  for (int c = 0; c < D->n_columns; c++) {
+    const int j = D->columns[c];
+    if (j < 0 || j >= F->n) return "npb_set_normalizer: a column index out of range: it names a column of the features";
+    if (taken[j]) return "npb_set_normalizer: a column named twice";
+    taken[j] = true;
+    if (F->kind[j] != NPB_FEATURE_KIND_AFFINE) return "npb_set_normalizer: a NPB_FEATURE_BITS column cannot be normalised";
+    if (F->ref_col[j]) return "npb_set_normalizer: a column whose ref is a second column (a setpoint error) cannot be normalised";
+  }
+  if (!(D->eps >= 0.0)) return "npb_set_normalizer: eps must be >= 0 (a NaN is not)";
+  if (D->reward) {
+    if (!(D->gamma >= 0.0 && D->gamma <= 1.0)) return "npb_set_normalizer: gamma must lie in [0, 1] (a NaN does not)";
+    if (!(D->clip > 0.0)) return "npb_set_normalizer: clip must be positive (a NaN is not)";
+    if (!D->norm_reward) return "npb_set_normalizer: a NULL norm_reward: the return stream writes it";
+    if ((uintptr_t)D->norm_reward & 7u) return "npb_set_normalizer: a misaligned norm_reward: 8-byte aligned";
+  }
+  return nullptr;
+}
+const char *npb_normalizer_check(const npb_normalizer_desc_t *D, int n_plants, const npb_features_desc_t *features) {
+  NormFeatures F = {};
+  if (D && n_plants < 1) return normalizer_refusal(D, n_plants, nullptr);
+  if (features) {
+    if (const char *why = npb_features_check(features, n_plants)) return why;
+    F.n = features->n_columns;
+    for (int j = 0; j < F.n; j++) { F.kind[j] = features->columns[j].kind; F.ref_col[j] = features->columns[j].ref_from_column != 0; }
+  }
+  return normalizer_refusal(D, n_plants, features ? &F : nullptr);
+}
+/* the table back to the columns' own ref and scale */
+static int normalizer_restore_table(NpbHandle *h, const char *who) {
+  if (!h->feat.cols || h->feat_host.empty()) return NPB_OK;
+  hipError_t e = hipMemcpy((void *)h->feat.cols, h->feat_host.data(), h->feat_host.size() * sizeof(npb_feature_col_t), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return fail(h, NPB_EHIP, (std::string(who) + ": putting the features' own ref and scale back failed").c_str(), e);
+  return NPB_OK;
+}
+int npb_set_normalizer(NpbHandle *h, const npb_normalizer_desc_t *desc) {
+  if (!h) return NPB_EINVAL;
+  if (h->ro.n_final)
+    return fail(h, NPB_EINVAL, "npb_set_normalizer: a rollout is set (npb_set_rollout) and records the reward the normaliser would change; npb_set_rollout(h, NULL) first: set the normaliser, then the rollout");
+  NormFeatures F = {};
+  if (h->feat.cols) {
+    F.n = h->feat.n_cols;
+    for (int j = 0; j < F.n; j++) { F.kind[j] = h->feat_host[j].kind; F.ref_col[j] = h->feat_host[j].ref_col; }
+  }
+  if (const char *why = normalizer_refusal(desc, h->n_plants, h->feat.cols ? &F : nullptr)) return fail(h, NPB_EINVAL, why);
+  NPB_USE_DEVICE(h);
+  /* the old normaliser's columns get their own ref and scale back (a synchronous copy on the null stream: the caller has let the steps on
+   * a non-blocking stream of its own finish, as before every npb_set_*) -- but only once nothing can fail any more: off here, and below
+   * behind the new allocation, so that a refused replacement leaves the old normaliser AND its table as they were */
+  const bool had_columns = h->norm.streams && h->norm.n_cols;
+  if (!desc) {
+    if (had_columns) { if (int rc = normalizer_restore_table(h, "npb_set_normalizer")) return rc; }
+    attachment_drop(&h->norm, h->norm.streams);
+    return NPB_OK;
+  }
+  /* the allocation: [the streams] | count, mean, M2, scale [S] | the partials [3 S][every level] | ret [n] | primed, seen, ended [n] */
+  const int C = desc->n_columns, S = C + (desc->reward ? 1 : 0);
+  std::vector<npb_norm_stream_t> table(NPB_NORM_STREAMS_MAX);
+  for (int c = 0; c < C; c++) {
+    const npb_feature_col_t &O = h->feat_host[desc->columns[c]];
+    table[c] = npb_norm_stream_t{O.c, O.ref, O.scale, desc->columns[c], 0};
+  }
+  if (desc->reward) table[C] = npb_norm_stream_t{npb_colstat_col_t{}, 0.0, 1.0, -1, 0};
+  static_assert(sizeof(npb_norm_stream_t) % 8 == 0, "packed");
+  const size_t n = (size_t)h->n_plants, table_bytes = table.size() * sizeof(npb_norm_stream_t), ws = npb_moments_workspace(h->n_plants);
+  const size_t doubles = 4 * (size_t)S + 3 * (size_t)S * ws + (desc->reward ? n : 0);
+  const size_t bytes = table_bytes + doubles * sizeof(double) + (desc->reward ? 3 * n * sizeof(int32_t) : 0);
+  char *dev = nullptr;
+  if (int rc = attachment_alloc(h, "npb_set_normalizer", "the streams, the statistics and the partials", table.data(), table_bytes, bytes, &dev)) return rc;
+  if (had_columns) { if (int rc = normalizer_restore_table(h, "npb_set_normalizer")) { (void)hipFree(dev); return rc; } }
+  npb_normalizer_t Z = {};
+  Z.streams = (const npb_norm_stream_t *)dev; Z.n_streams = S; Z.n_cols = C; Z.reward_on = desc->reward != 0;
+  Z.eps = desc->eps; Z.gamma = desc->gamma; Z.clip = desc->clip;
+  Z.count = (double *)(dev + table_bytes); Z.mean = Z.count + S; Z.M2 = Z.mean + S; Z.scale = Z.M2 + S;
+  Z.partial = Z.scale + S; Z.ws_stride = ws;
+  if (desc->reward) {
+    Z.ret = Z.partial + 3 * (size_t)S * ws;
+    Z.primed = (int32_t *)(Z.ret + n); Z.seen = Z.primed + n; Z.ended = Z.seen + n;
+    Z.norm_reward = desc->norm_reward;
+  }
+  Z.feat_cols = (npb_feature_col_t *)h->feat.cols;
+  attachment_drop(&h->norm, h->norm.streams);
+  h->norm = Z;
+  h->norm_training = true;
+  npb_launch_normalizer_finish(&h->norm, 0, nullptr);      /* no batch: scale[] takes the streams' own, which the reward kernel reads */
+  NPB_HIP(h, hipGetLastError());
+  NPB_HIP(h, hipStreamSynchronize(nullptr));
+  return NPB_OK;
+}
+int npb_normalizer_training(NpbHandle *h, int on) {
+  if (!h) return NPB_EINVAL;
+  if (!h->norm.streams) return fail_who(h, "npb_normalizer_training", g_no_normalizer);
+  h->norm_training = on != 0;
+  return NPB_OK;
+}
+int npb_normalizer_clear(NpbHandle *h, const uint8_t *mask, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (h->norm.streams && !h->norm.reward_on) return NPB_OK;      /* no return stream: no carry to start again */
+  return attachment_clear(h, "npb_normalizer_clear", h->norm.streams, g_no_normalizer,
+                          [&] { npb_launch_unprime(h->norm.primed, mask, h->n_plants, (hipStream_t)stream); });
+}
+/* count, mean, M2; with the return stream ret, primed, seen, ended */
+static StateParts normalizer_state_parts(const NpbHandle *h) {
+  const npb_normalizer_t &Z = h->norm;
+  const size_t n = Z.reward_on ? (size_t)h->n_plants : 0, s = (size_t)Z.n_streams * sizeof(double), words = n * sizeof(int32_t);
+  const bool none = !Z.reward_on;
+  return {Z.streams, g_no_normalizer, " (ret, primed, seen and ended may be NULL only without the return stream)", 7,
+          {{Z.count, s, false}, {Z.mean, s, false}, {Z.M2, s, false}, {Z.ret, n * sizeof(double), none}, {Z.primed, words, none},
+           {Z.seen, words, none}, {Z.ended, words, none}}};
+}
+int npb_normalizer_get_state(NpbHandle *h, double *count, double *mean, double *M2, double *ret, int32_t *primed, int32_t *seen, int32_t *ended,
+                             void *stream) {
+  return state_copy(h, "npb_normalizer_get_state", normalizer_state_parts, {count, mean, M2, ret, primed, seen, ended}, false, stream);
+}
+int npb_normalizer_set_state(NpbHandle *h, const double *count, const double *mean, const double *M2, const double *ret, const int32_t *primed,
+                             const int32_t *seen, const int32_t *ended, void *stream) {
+  if (int rc = state_copy(h, "npb_normalizer_set_state", normalizer_state_parts, {count, mean, M2, ret, primed, seen, ended}, true, stream)) return rc;
+  NPB_USE_DEVICE(h);
+  npb_launch_normalizer_finish(&h->norm, 0, (hipStream_t)stream);      /* the table follows the loaded state */
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }

@@ -117,6 +117,26 @@ typedef struct {
   npb_rollout_desc_t D;
   int cells, n_axes, obs_bytes, act_bytes, t;
 } npb_rollout_t;
+/* npb_set_normalizer (npd_normalizer.h, npb_minibatch.hip): one stream as the partials kernel and the finish kernel read it.  c: the
+ * column whose raw samples are folded (unused by the return stream); ref0 / scale0: the column's own ref and scale (the return stream: 0.0
+ * and 1.0), the shift of the first fold and what the table holds while count == 0; feat_col: the features' column whose table entry the
+ * finish kernel rewrites, -1 for the return stream */
+typedef struct { npb_colstat_col_t c; double ref0, scale0; int feat_col, pad_; } npb_norm_stream_t;
+#define NPB_NORM_STREAMS_MAX (NPB_FEATURES_COLS_MAX + 1)
+/* the handle's normaliser: the streams (device, one allocation with everything below but norm_reward and feat_cols; streams NULL = off);
+ * the state count, mean, M2 [n_streams] and beside it scale [n_streams], what the table holds (the reward kernel reads the return
+ * stream's); with the return stream ret [n_plants], primed, seen, ended [n_plants]; the partials, vector v = 3 * stream + {0: s1, 1: s2,
+ * 2: the count as a double} at partial + v * ws_stride, every level of the tree one behind the other (npb_moments_workspace); the
+ * caller's norm_reward; the features' device table */
+typedef struct {
+  const npb_norm_stream_t *streams; int n_streams, n_cols, reward_on;
+  double eps, gamma, clip;
+  double *count, *mean, *M2, *scale;
+  double *ret; int32_t *primed, *seen, *ended;
+  double *partial; size_t ws_stride;
+  double *norm_reward;
+  npb_feature_col_t *feat_cols;
+} npb_normalizer_t;
 typedef struct {
   int (*step)(const npb_params_t *P, int n_plants, size_t npad, void *arena, const int32_t *action,
               const double *magnitude, const double *setpoint, const double *noise_z, const double *cw_temp,
@@ -181,6 +201,11 @@ typedef struct {
   /* npb_set_controls (npd_controls.h): every plant's row of the caller's input decoded in front of the step -- the actuators moved, the
    * input columns filled, held / prev kept; index: the handle's carried episode indices or NULL */
   void (*controls)(void *arena, size_t npad, const npb_controls_t *C, const npb_params_t *P, int n_plants, const int32_t *index, hipStream_t stream);
+  /* npb_set_normalizer (npd_normalizer.h): this step's raw samples of every stream as partial sums of the pinned tree, one workgroup per
+   * 256 plants, and with the return stream every plant's discounted return carried; reward / done: the columns the episode kernel reads;
+   * index: the handle's carried episode indices or NULL */
+  void (*normalizer)(const void *arena, size_t npad, const npb_normalizer_t *Z, int n_plants, const int32_t *index, const double *reward,
+                     hipStream_t stream);
 } npb_launchers_t;
 extern npb_launchers_t npb_launch_table, npb32_launch_table;
 /* the same for either storage type */
@@ -211,6 +236,14 @@ void npb_launch_column_stats_clear(const npb_column_stats_t *S, const uint8_t *m
 void npb_launch_event_windows_clear(const npb_event_windows_t *W, const uint8_t *mask, int n_plants, hipStream_t stream);
 /* npb_task_clear, npb_features_clear, npb_controls_clear: the plants of mask (NULL = all) unprimed in that attachment's `primed` column */
 void npb_launch_unprime(int32_t *primed, const uint8_t *mask, int n_plants, hipStream_t stream);
+/* npb_set_normalizer, the same for either storage type: neither touches the arena.
+ * finish (npb_minibatch.hip, IEEE division and root): one workgroup ends the tree over the `groups` partials of every vector (0 = no batch:
+ *   the state stays), merges, writes count, mean, M2 and scale, and ref and scale into the features' table entries.
+ * reward (npd_normalizer.h): norm_reward, ended, primed and seen of every plant; carry != 0: the return is carried here (frozen: the partials
+ *   kernel, which carries it otherwise, has not run) */
+void npb_launch_normalizer_finish(const npb_normalizer_t *Z, int groups, hipStream_t stream);
+void npb_launch_normalizer_reward(const npb_normalizer_t *Z, int n_plants, const int32_t *index, const double *reward, const uint8_t *done, int carry,
+                                  hipStream_t stream);
 /* npb_set_rollout (npd_rollout.h), the same for either storage type: none of them touches the arena.
  * pre: the three copies into slot R->t in front of the controls kernel, feat_out and ctl_in the tensors the features and the controls are
  *   bound to (ctl_in NULL without controls).

@@ -1595,13 +1595,15 @@ static void NPB_LAUNCHER(event_windows)(const void *arena, size_t npad, const np
 static void NPB_LAUNCHER(task)(const void *arena, size_t npad, const npb_task_t *T, int n_plants, const int32_t *index, hipStream_t stream);     /* the same */
 static void NPB_LAUNCHER(features)(const void *arena, size_t npad, const npb_features_t *F, int n_plants, int mode, const int32_t *index, hipStream_t stream);     /* the same */
 static void NPB_LAUNCHER(controls)(void *arena, size_t npad, const npb_controls_t *C, const npb_params_t *P, int n_plants, const int32_t *index, hipStream_t stream);     /* the same */
+static void NPB_LAUNCHER(normalizer)(const void *arena, size_t npad, const npb_normalizer_t *Z, int n_plants, const int32_t *index, const double *reward,
+                                     hipStream_t stream);     /* the same */
 /* not const: clang emits a namespace-scope const into the device code too, where these host functions do not exist */
 extern "C" npb_launchers_t NPB_LAUNCHER(table) = {
   NPB_LAUNCHER(step), NPB_LAUNCHER(maint), NPB_LAUNCHER(observe), NPB_LAUNCHER(init), NPB_LAUNCHER(reset),
   NPB_LAUNCHER(field_get), NPB_LAUNCHER(field_set), NPB_LAUNCHER(gather), NPB_LAUNCHER(restore), NPB_LAUNCHER(episode),
   NPB_LAUNCHER(operator_maint), NPB_LAUNCHER(operator_component_maint), NPB_LAUNCHER(operator_turbine_maint), NPB_LAUNCHER(maint_all),
   NPB_LAUNCHER(sample), NPB_LAUNCHER(episode_records), NPB_LAUNCHER(column_stats_fold), NPB_LAUNCHER(event_windows),
-  NPB_LAUNCHER(task), NPB_LAUNCHER(features), NPB_LAUNCHER(controls),
+  NPB_LAUNCHER(task), NPB_LAUNCHER(features), NPB_LAUNCHER(controls), NPB_LAUNCHER(normalizer),
 };
 #ifndef NPB_BUILD_F32
 /* npb_reset / npb_reset_reference / npb_restore: the episode counters (len, ret) and the carried start entries (start: -1, not from
@@ -1844,6 +1846,9 @@ static void NPB_LAUNCHER(episode_records)(int n_plants, size_t npad, const void 
 
 /* the caller's policy outputs (npb_set_controls): the decode kernel in front of the step and its launcher */
 #include "npd_controls.h"
+
+/* running observation and reward normalisation (npb_set_normalizer): the partials kernel of a fold, the reward kernel and their launchers */
+#include "npd_normalizer.h"
 
 #ifndef NPB_BUILD_F32
 /* npb_task_clear, npb_features_clear, npb_controls_clear: the plants of mask (NULL = all) unprimed in that attachment's `primed` column --

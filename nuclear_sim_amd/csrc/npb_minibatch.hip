@@ -19,9 +19,9 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "npb_minibatch.h"
+#include "npb_kernels.h"
 
 #define NPD_MOMENTS_AHEAD 8          /* rows whose loads are in flight before their additions run */
-#define NPD_TREE 256                 /* the tree's fan-in: one workgroup */
 /* output rows a wave takes, and passes over them whose loads are in flight before their stores.  Measured on an MI355X (kernel trace,
  * 65 536 transitions of 256-byte stacks, 16-byte actions and 8-byte extras out of 8.4 M): 64 rows 17.6 us, 32 rows 15.9, 16 rows 15.9;
  * 8 passes ahead in place of 4: 17.1, 16.7, 16.5 -- the gather runs at the rate random 256-byte rows come in, not at a wave's latency */
@@ -31,16 +31,7 @@
 #define NPD_WAVE 64
 
 /* ---------------------------------------------------------------------------------------------------------------- moments */
-/* one group of the tree: s[0 .. 256) -> s[0]; every lane of the workgroup calls it */
-__device__ __forceinline__ void npd_tree_group(double *s, int lane) {
-#pragma unroll
-  for (int half = NPD_TREE / 2; half >= 1; half >>= 1) {
-    __syncthreads();
-    if (lane < half) s[lane] = s[lane] + s[lane + half];
-  }
-  __syncthreads();
-}
-
+/* (the tree itself: npd_tree_group and npd_tree_levels, npb_minibatch.h) */
 /* SQUARES = false: col[p] = sum of (double)x[s][p]; true: of the rounded squares of (double)x[s][p] - stats[1].  partial[block] = that
  * workgroup's group of the tree; a tensor of one column has no tree: partial[0] = col[0] */
 template <typename T, bool SQUARES>
@@ -78,21 +69,7 @@ template <bool SQUARES>
 __global__ __launch_bounds__(NPD_TREE) void npb_moments_finish_kernel(double *ws, size_t g, double count, double divisor, double *__restrict__ out) {
   __shared__ double s[NPD_TREE];
   const int lane = threadIdx.x;
-  double *in = ws;
-  while (g > 1) {
-    double *next = in + g;
-    const size_t groups = (g + NPD_TREE - 1) / NPD_TREE;
-    for (size_t c = 0; c < groups; c++) {
-      const size_t i = c * NPD_TREE + lane;
-      __syncthreads();                     /* (s[0] of the group before has been read) */
-      s[lane] = i < g ? in[i] : 0.0;
-      npd_tree_group(s, lane);
-      if (lane == 0) next[c] = s[0];
-    }
-    __threadfence_block();
-    __syncthreads();                       /* the level is written before the next one reads it */
-    in = next; g = groups;
-  }
+  const double *in = npd_tree_levels(ws, g, s, lane);
   if (lane == 0) {
     const double total = in[0];
     if (SQUARES) { const double var = total / divisor; out[2] = var; out[3] = sqrt(var); }
@@ -119,6 +96,68 @@ template <typename T> static void npd_moments_launch(const npb_moments_desc_t *M
 extern "C" void npb_launch_moments(const npb_moments_desc_t *M, double *ws, hipStream_t stream) {
   if (M->type == NPB_ROLLOUT_F64) npd_moments_launch<double>(M, ws, stream);
   else npd_moments_launch<float>(M, ws, stream);
+}
+
+/* ---------------------------------------------------------------------------------------------------------------- normaliser */
+/* The finish of one fold of the normaliser (include/npb.h, npb_set_normalizer; nuclear_sim_amd/normalizer.py states it): one workgroup.
+ * The partials kernel (npd_normalizer.h) has left, per vector v = 3 * stream + {s1, s2, the count as a double: integers, exact in any
+ * order}, `groups` values at partial + v * ws_stride.  The tree's further levels run over them here as npb_moments_finish_kernel runs
+ * them, but NPD_NORM_ROWS (vector, group) pairs at a time, each a row of LDS, so that a level of all vectors costs the barriers of a few
+ * groups and not of 3 S of them; the row stride is npd_normalizer.h's, for its reason.  Then one lane per stream merges -- Chan's merge
+ * with the batch taken around the running mean -- writes count, mean, M2 and scale, and ref and scale into the features' table entry of
+ * its column, in plain C++: vector stores, which the features kernel's loads of the next launch see.  It lives in this file for its
+ * flags: the divisions and the root are IEEE.  groups == 0: no batch (behind npb_set_normalizer and npb_normalizer_set_state): the table
+ * follows the state */
+#define NPD_NORM_ROWS 16
+__global__ __launch_bounds__(NPD_TREE) void npb_normalizer_finish_kernel(npb_normalizer_t Z, int groups) {
+  __shared__ double s[NPD_NORM_ROWS * NPD_NORM_STRIDE];
+  const int lane = threadIdx.x, S = Z.n_streams;
+  size_t at = 0;      /* where the level being read stands in every vector's workspace */
+  for (size_t g = (size_t)groups; g > 1;) {
+    const size_t per = (g + NPD_TREE - 1) / NPD_TREE, rows = 3 * (size_t)S * per;
+    for (size_t r0 = 0; r0 < rows; r0 += NPD_NORM_ROWS) {
+      __syncthreads();                     /* (the rows of the pass before have been read) */
+#pragma unroll
+      for (int j = 0; j < NPD_NORM_ROWS; j++) {
+        const size_t r = r0 + j, v = r / per, c = r - v * per, i = c * NPD_TREE + lane;
+        s[j * NPD_NORM_STRIDE + lane] = r < rows && i < g ? Z.partial[v * Z.ws_stride + at + i] : 0.0;
+      }
+      npd_tree_groups<NPD_NORM_ROWS>(s, NPD_NORM_STRIDE, lane);
+      if (lane < NPD_NORM_ROWS && r0 + lane < rows) {
+        const size_t r = r0 + lane, v = r / per, c = r - v * per;
+        Z.partial[v * Z.ws_stride + at + g + c] = s[lane * NPD_NORM_STRIDE];
+      }
+    }
+    __threadfence_block();
+    __syncthreads();                       /* the level is written before the next one reads it */
+    at += g; g = per;
+  }
+  if (lane >= S) return;
+  const npb_norm_stream_t &D = Z.streams[lane];
+  double count = Z.count[lane], mean = Z.mean[lane], M2 = Z.M2[lane];
+  const double *mine = Z.partial + 3 * (size_t)lane * Z.ws_stride + at;
+  const double cnt = groups > 0 ? mine[2 * Z.ws_stride] : 0.0;
+  if (cnt > 0.0) {
+    const double shift = count > 0.0 ? mean : D.ref0, s1 = mine[0], s2 = mine[Z.ws_stride];
+    const double N = count + cnt;
+    const double step = s1 / N;
+    mean = shift + step;
+    const double sum = M2 + s2, square = s1 * s1, less = square / N;
+    M2 = sum - less;
+    if (M2 < 0.0) M2 = 0.0;
+    count = N;
+    Z.count[lane] = count; Z.mean[lane] = mean; Z.M2[lane] = M2;
+  }
+  double ref = D.ref0, scale = D.scale0;
+  if (count > 0.0) {
+    const double var = M2 / count, spread = sqrt(var + Z.eps);
+    ref = mean; scale = 1.0 / spread;
+  }
+  Z.scale[lane] = scale;
+  if (D.feat_col >= 0) { Z.feat_cols[D.feat_col].ref = ref; Z.feat_cols[D.feat_col].scale = scale; }
+}
+extern "C" void npb_launch_normalizer_finish(const npb_normalizer_t *Z, int groups, hipStream_t stream) {
+  hipLaunchKernelGGL(npb_normalizer_finish_kernel, dim3(1), dim3(NPD_TREE), 0, stream, *Z, groups);
 }
 
 /* ---------------------------------------------------------------------------------------------------------------- permutation */

@@ -29,7 +29,8 @@
  * No scratch, no atomics.  Included behind every other kernel of npb_kernels.hip and compiled with it for either storage type: it reads
  * the arena.
  * NOT here (include/npb.h says so too): the terminal stack in the episode records, half-precision output, a delta or rate kind (the
- * stack carries it), running statistics updated on the device. */
+ * stack carries it).  Running statistics updated on the device are the normaliser's (npd_normalizer.h): it rewrites `ref` and `scale`
+ * of the table this kernel reads, in front of pass A. */
 #ifndef NPD_FEATURES_H
 #define NPD_FEATURES_H
 

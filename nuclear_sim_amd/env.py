@@ -19,7 +19,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, recordlog, rollout
+from . import _lib, normalizer, recordlog, rollout
 from .schema import SCHEMA
 
 
@@ -504,7 +504,7 @@ class BatchedPlantEnv:
         self._keep = []
         self._episode = None
         self._bank = None
-        self._mlog = self._msum = self._erec = self._cstats = self._ewin = self._task = self._feat = self._ctl = self._roll = None      # (see ``_OFF``)
+        self._mlog = self._msum = self._erec = self._cstats = self._ewin = self._task = self._feat = self._ctl = self._roll = self._norm = None      # (see ``_OFF``)
         self._diag_buf = None; self.diagnostics = None; self._diag_carried = False
         if diagnostics:      # before the first snapshot (autoreset=True takes it below), so that it records the carried rows
             self.enable_diagnostics(True, carried=True)
@@ -973,14 +973,16 @@ class BatchedPlantEnv:
     # The per-step attachments -- maintenance log and summary, episode records, column statistics, event windows, task, features,
     # controls, rollout: None = off, else what the enable_* / set_* method keeps of it.  __init__ sets them; the class has them too, so that a
     # refusal "before any device work" can be checked on an object made without it.  ``_on`` reads them, with these refusals:
-    _mlog = _msum = _erec = _cstats = _ewin = _task = _feat = _ctl = _roll = None
+    _mlog = _msum = _erec = _cstats = _ewin = _task = _feat = _ctl = _roll = _norm = None
     _max_episode_steps = 0      # the autoreset's limit, 0 = none (``_enable_autoreset``)
     _OFF = {"_mlog": "no maintenance log: enable_maintenance_log() first", "_msum": "no maintenance summary: enable_maintenance_summary() first",
             "_erec": "no episode records: enable_episode_records() first", "_cstats": "no column statistics: enable_column_stats() first",
             "_ewin": "no event windows: enable_event_windows() first", "_task": "no task: set_task() first",
-            "_feat": "no features: set_features() first", "_ctl": "no controls: set_controls() first", "_roll": "no rollout: set_rollout() first"}
+            "_feat": "no features: set_features() first", "_ctl": "no controls: set_controls() first", "_roll": "no rollout: set_rollout() first",
+            "_norm": "no normaliser: set_normalizer() first"}
     # who reads side buffers, as a refusal names them: each keeps ``"reads"``, the buffers its request resolved to (``_reading``)
-    _CONSUMERS = {"_task": "the task", "_feat": "the features", "_cstats": "the column statistics", "_ewin": "the event windows"}
+    _CONSUMERS = {"_task": "the task", "_feat": "the features", "_cstats": "the column statistics", "_ewin": "the event windows",
+                  "_norm": "the normaliser"}
 
     def _on(self, attr) -> dict:
         """THE "is it on" of an attachment: what it keeps, or its refusal"""
@@ -1211,7 +1213,7 @@ class BatchedPlantEnv:
 
     def _task_readers(self):
         """what reads the task's output columns, as a refusal names them"""
-        return self._readers_of(("task_reward", "task_cause"), among=("_cstats", "_ewin", "_feat"))
+        return self._readers_of(("task_reward", "task_cause"), among=("_cstats", "_ewin", "_feat", "_norm"))
 
     def set_task(self, reward=(), terminate=(), bias: float = 0.0, keep_terms: bool = False) -> None:
         """Define the reward and the termination rule on the device (npb_set_task): behind every step one more launch forms a per-plant
@@ -1401,6 +1403,10 @@ class BatchedPlantEnv:
             self.clear_controls(mask)
         if self._roll is not None:
             _lib.check(self.L.npb_rollout_cut(self._h, self._p(mask), self._stream()), self._h)
+        # the normaliser needs nothing new here: a restart bumps the carried episode index, and a changed index restarts the return's
+        # carry.  Only a handle without autoreset carries no index: there the plants are unprimed, as the features' are above
+        if self._norm is not None and self._norm["reward"] is not None and self._episode is None:
+            self.clear_normalizer(mask)
 
     def features_state(self) -> Dict[str, np.ndarray]:
         """The features' own state for a checkpoint (npb_features_get_state), beside ``state_arrays()`` and a copy of ``features()``:
@@ -1424,6 +1430,83 @@ class BatchedPlantEnv:
         """The rows the features read as they are NOW, widened to float64, [n_rows, n] on the device (gather launches and copies: for checks
         and debugging, not for the hot path), as ``task_samples`` gives the task's."""
         return self._column_samples(self._on("_feat")["request"]["columns"])
+
+    def set_normalizer(self, columns="all", reward=None, eps: float = 1e-8) -> None:
+        """Running observation and reward normalisation on the device (npb_set_normalizer), what ``VecNormalize`` gives a PPO loop: while
+        it is on and training every ``step()`` folds this step's raw samples of the chosen feature columns into running statistics
+        (count, mean, M2) -- two launches more, nothing read back, the order of every addition pinned -- and rewrites ``ref = mean`` and
+        ``scale = 1 / sqrt(var + eps)`` of those columns in front of the features' frame of that step; the options a column was given in
+        ``set_features`` are where it starts from, and its ``"clip"`` is the clip of the normalised value.
+        ``columns``: ``"all"`` (every eligible column: affine with a constant ref), a list of indices into the features' columns, or None.
+        ``reward``: None, or ``{"gamma": g, "clip": c}``: a per-plant discounted return is kept (it restarts with the episode), its
+        running spread scales the reward -- no mean is subtracted -- and ``step()`` adds ``info["norm_reward"]``; a rollout
+        (``set_rollout``, set AFTER the normaliser) records that in place of the reward, while ``info["episode_return"]`` and the episode
+        records keep the raw one.  The reward is the task's while a task is set.  ``columns=None`` with ``reward=None`` turns it off, and
+        the features get their own ``ref`` / ``scale`` back.  ``nuclear_sim_amd.normalizer`` is the same in numpy, bit for bit."""
+        if self._roll is not None:
+            raise _lib.NpbError("the rollout records the reward the normaliser would change: set_rollout(None) first, then the normaliser, then the rollout")
+        if columns is None and reward is None:
+            if self._norm is not None:
+                _lib.check(self.L.npb_set_normalizer(self._h, None), self._h)
+            self._norm = None
+            return
+        ft = self._feat
+        spec = None if ft is None else ft["request"]["spec"]
+        if isinstance(columns, str):
+            if columns != "all":
+                raise ValueError("columns is 'all', a list of feature column indices or None, not %r" % (columns,))
+            columns = [] if spec is None else [j for j, D in enumerate(spec["columns"]) if D["kind"] == "affine" and not isinstance(D["ref"], tuple)]
+        columns = [] if columns is None else [int(j) for j in columns]
+        normalizer.check(spec, columns, reward, eps)      # a bad request is refused here
+        if not hasattr(self.L, "npb_set_normalizer"):
+            raise _lib.NpbError("libnpb.so has no npb_set_normalizer: rebuild")
+        d = _lib.NpbNormalizerDesc()
+        idx = (ctypes.c_int * max(len(columns), 1))(*columns)
+        d.n_columns, d.columns, d.eps = len(columns), idx, float(eps)
+        out = None
+        if reward is not None:
+            with torch.cuda.device(self.device):
+                out = torch.zeros(self.n, dtype=torch.float64, device=self.device)
+            d.reward, d.gamma, d.clip, d.norm_reward = 1, float(reward["gamma"]), float(reward["clip"]), out.data_ptr()
+        _lib.check(self.L.npb_set_normalizer(self._h, ctypes.byref(d)), self._h)      # (refused: what was set before stays)
+        S, n = len(columns) + (reward is not None), self.n if reward is not None else 0
+        reads = frozenset(["task_reward"] if reward is not None and self._task is not None else [])
+        self._norm = {"norm_reward": out, "columns": columns, "reward": None if reward is None else dict(reward), "eps": float(eps),
+                      "reads": reads, "holds": [self._task["reward"]] if reads else [],
+                      "state": (("count", np.float64, (S,)), ("mean", np.float64, (S,)), ("M2", np.float64, (S,)), ("ret", np.float64, (n,)),
+                                ("primed", np.int32, (n,)), ("seen", np.int32, (n,)), ("ended", np.int32, (n,)))}
+
+    def normalizer_training(self, on: bool = True) -> None:
+        """``False`` freezes the statistics for evaluation (npb_normalizer_training): no fold, the features keep the table as it stands;
+        the reward is still normalised, with the frozen scale, and the return is still carried"""
+        self._on("_norm")
+        _lib.check(self.L.npb_normalizer_training(self._h, int(bool(on))), self._h)
+
+    def normalizer_state(self) -> Dict[str, np.ndarray]:
+        """The normaliser's own state for a checkpoint (npb_normalizer_get_state): ``count``, ``mean``, ``M2`` float64 [S], and with the
+        return stream ``ret`` float64 [n], ``primed``, ``seen``, ``ended`` int32 [n] (else empty)."""
+        return self._get_state("_norm", self.L.npb_normalizer_get_state)
+
+    def load_normalizer_state(self, state) -> None:
+        """put back what ``normalizer_state()`` returned (npb_normalizer_set_state); the features' table follows.  A dry run's statistics
+        warm-start a run this way."""
+        self._load_state("_norm", self.L.npb_normalizer_set_state, state)
+
+    def normalizer_stats(self) -> Dict[str, np.ndarray]:
+        """``count``, ``mean``, ``var`` and ``scale`` (what the features' table holds; the return stream's last) as numpy, float64 [S]"""
+        z = self.normalizer_spec()
+        z.load_state({k: v for k, v in self.normalizer_state().items() if v.size})
+        return z.stats()
+
+    def normalizer_spec(self) -> "normalizer.Normalizer":
+        """a ``nuclear_sim_amd.normalizer.Normalizer`` as this one was set, its state at zero: the statement to compare with"""
+        nm = self._on("_norm")
+        return normalizer.Normalizer(None if self._feat is None else self._feat["request"]["spec"], nm["columns"], self.n, nm["reward"], nm["eps"])
+
+    def clear_normalizer(self, mask=None) -> None:
+        """the masked plants (None = all) start a new discounted return on their next step (npb_normalizer_clear).  ``reset`` / ``restore``
+        need not call it: the episode index they bump does the work"""
+        self._clear("_norm", self.L.npb_normalizer_clear, mask)
 
     def _control_readers(self):
         """what reads the controls' held / previous columns, as a refusal names them"""
@@ -2051,6 +2134,7 @@ class BatchedPlantEnv:
         self._feat = None
         self._ctl = None
         self._roll = None
+        self._norm = None
 
     def __del__(self):
         try:
@@ -2283,6 +2367,8 @@ class BatchedPlantEnv:
             if feat["as_observation"]:
                 info["observation"] = obs
                 obs = feat["out"]
+        if self._norm is not None and self._norm["norm_reward"] is not None:      # the reward the learner sees (set_normalizer); the one returned stays raw
+            info["norm_reward"] = self._norm["norm_reward"]
         if task is not None:
             return obs, task["reward"], task["done"], info
         return obs, self._reward, self._done, info
