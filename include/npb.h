@@ -1084,6 +1084,7 @@ NPB_API int npb_features_set_state(NpbHandle *h, const int32_t *primed, const in
  * No step, restore, episode, task or features kernel changes.  Not here: a discrete action table, a rate limit on the COLUMN kind
  * (npb_profile_ramp), half-precision input, the feedwater action codes (the reference accepts them and they do nothing), K steps in
  * one call.
+ * (The policy's section below, npb_set_policy, writes `in` on the device, and its npb_collect runs K steps in one call.)
  * NPB_VERSION stays 154: a binding detects the entry points by name.  A handle that never calls this behaves as before in every entry
  * point. */
 #define NPB_CONTROLS_AXES_MAX 8
@@ -1182,6 +1183,7 @@ NPB_API int npb_controls_set_state(NpbHandle *h, const double *held, const doubl
  * No step, restore, episode, task, features or controls kernel changes.  Not here: advantage normalisation and minibatch shuffling (they
  * have the section below, where the reduction order is pinned: npb_rollout_moments, npb_rollout_minibatch),
  * a checkpoint of a half-filled rollout, half types, V-trace or other off-policy corrections, rollouts without features.
+ * (The values the advantages wait for, and the extras a policy writes by itself, have the policy's section below: npb_set_policy.)
  * NPB_VERSION stays 154: a binding detects the entry points by name. */
 #define NPB_ROLLOUT_HORIZON_MAX 4096
 #define NPB_ROLLOUT_EXTRAS_MAX 8
@@ -1369,6 +1371,84 @@ NPB_API int npb_normalizer_get_state(NpbHandle *h, double *count, double *mean, 
 NPB_API int npb_normalizer_set_state(NpbHandle *h, const double *count, const double *mean, const double *M2, const double *ret,
                                      const int32_t *primed, const int32_t *seen, const int32_t *ended, void *stream);
 NPB_API int npb_normalizer_clear(NpbHandle *h, const uint8_t *mask, void *stream);
+
+/* The policy: the one link of the per-step chain that used to leave the library -- between the features and the controls' input an MLP
+ * actor-critic, the Gaussian draw, the log-probability and the value -- run on the device, in ONE launch in front of the rollout's pre
+ * kernel.  An optional per-handle attachment; it needs features and controls to be set.  nuclear_sim_amd/policy.py states all of it in
+ * numpy, and that statement is the contract; the device produces its bits for every n_plants and launch geometry, with one licensed
+ * difference: the float tanh.
+ * The nets: a diagonal-Gaussian actor and a critic, two separate MLPs of 1 .. NPB_POLICY_HIDDEN_MAX hidden layers each, widths 1 ..
+ * NPB_POLICY_WIDTH_MAX chosen per net, activation NPB_POLICY_RELU or NPB_POLICY_TANH.  Input: the features' out[p] flattened, K * C
+ * cells, a double tensor narrowed to float first (round to nearest even).  The actor's head has A outputs, A the controls' axis count;
+ * the critic's one.
+ * The parameters: one flat float vector theta -- the actor's layers, then the critic's, then log_std[A], then std[A]; a layer is
+ * W[out][in] row-major, then b[out].  std is the caller's exp(log_std): the device takes no exponential.
+ * One layer, for output j: acc = b[j], then for k ascending acc = fmaf(x[k], W[j][k], acc) in float, a single rounding per step; k is
+ * extended with +0.0 cells and +0.0 weights to a multiple of 4.  A subnormal result or accumulator is outside the contract.  relu: acc >
+ * 0 ? acc : +0.0; tanh: the device's float tanh (the statement: the double tanh narrowed).
+ * The noise: Philox4x32-10, key = the two halves of seed (low first), counter = (first_plant + p, t & 0xffffffff, t >> 32, j); t is the
+ * policy's draw counter, a uint64 on the handle, advanced by every step the policy samples in; call j serves axes 2j and 2j + 1: u1 =
+ * (w0 * 2^20 + (w1 >> 12) + 0.5) * 2^-52, u2 likewise from w2 and w3, r = sqrt(-2 * log(u1)), th = 6.283185307179586 * u2, z0 = r *
+ * cos(th), z1 = r * sin(th), in double.  deterministic != 0: nothing is drawn, z = 0 and t does not advance.
+ * The outputs, in double, every operation rounded on its own:
+ *   a[i] = (double)mean[i] + (double)std[i] * z[i], narrowed to the controls' input type and written to their bound `in` tensor
+ *   lp   = -(A * 0.9189385332046727), then for i ascending lp = (lp - 0.5 * (z[i] * z[i])) - (double)log_std[i]
+ *   value[p] = the critic's float; logp[p] = (float)lp: the density of the UNROUNDED action.  With extras_in (the rollout's bound [n][E]
+ *   input) value and logp also go to its columns value_slot and logp_slot (-1 = none), so the rollout's pre kernel records them.
+ * A plant with a NaN or infinite feature gets THE quiet NaN in every output and touches no other plant.
+ * npb_set_policy(h, desc): desc = NULL turns it off.  theta starts as zeros: npb_policy_load before the first step.  While a policy is
+ * set npb_set_features, npb_set_controls and npb_set_rollout are refused, set and NULL alike, naming the policy: it reads and writes their
+ * tensors in the shapes it was set with (so: features, controls, rollout, then the policy).  The policy is the one writer of the
+ * controls' input: what the caller wrote there is overwritten by every step.  NPB_EINVAL with the reason in npb_last_error, before any
+ * device work: no features or no controls set, and what npb_policy_check refuses -- that check alone, without a handle (features_cells
+ * = K * C, n_axes = the controls' axis count), NULL = accepted, else the reason: n_plants < 1; features_cells outside 1 ..
+ * NPB_FEATURES_CELLS_MAX; n_axes outside 1 .. NPB_CONTROLS_AXES_MAX; a layer count or a width out of range; an unknown activation;
+ * first_plant negative or first_plant + n_plants beyond 2^32; a NULL or misaligned value or logp (4-byte aligned); slots without
+ * extras_in, extras_in without a count in 1 .. NPB_ROLLOUT_EXTRAS_MAX, a slot outside -1 .. E - 1, both slots the same column, a
+ * misaligned extras_in.
+ * npb_policy_count(desc, features_cells, n_axes): the length of theta for these shapes (0 for a NULL descriptor).
+ * npb_policy_load(h, theta, theta_is_device, stream): new parameters into the existing allocation and one launch that lays the weights
+ *   out as the kernel reads them (transposed, padded with +0.0); no reallocation, and no synchronisation for a device source.
+ * npb_policy_values(h, rows, type, n_rows, out, stream): the critic alone over any contiguous device [n_rows][K * C] tensor of float
+ *   (NPB_FEATURES_F32) or double (NPB_FEATURES_F64); rows = NULL: the features' out.  out: device float [n_rows].  It gives the
+ *   last_value (from the current features) and the final_value (from the rollout's final_obs) of npb_rollout_advantages.
+ * npb_policy_noise(h, t, z, words, stream): the z of draw t, device double [n][A], and (words != NULL) the Philox words behind it,
+ *   device uint32 [n][(A + 1) / 2][4], by the device function the step's launch inlines.  Either may be NULL, not both.
+ * npb_policy_get_state / npb_policy_set_state carry t.  npb_destroy drops the policy.
+ * npb_collect(h, steps, obs, reward, done, trip_flags, info, stream): `steps` calls of npb_step with NULL input columns and these output
+ *   columns, without a return to the caller in between.  Refused before any device work unless a policy is set, a rollout is set with
+ *   room for `steps` more slots, and every input column can be NULL: not under NPB_HEAT_EXTERNAL, not with the heat-source noise enabled
+ *   unless episode streams drive it, not with a power profile seeded on the handle unless episode streams drive it.  Prime the features
+ *   first (npb_features_prime).
+ * The kernel (npb_policy.hip) runs on the f32 matrix cores (v_mfma_f32_32x32x2_f32: exact f32, the statement's fmaf chain two k a call; the
+ * relu tests hold it to the statement's bits): one workgroup per 32 plants, the activations through LDS, no atomics, no scratch.
+ * Not here: a shared trunk; discrete or squashed (tanh-Gaussian) actions; a state-dependent std; recurrent nets; half types; training
+ * on the device; noise that restarts with the episode; skipping the forward pass on held steps of interval > 1.
+ * NPB_VERSION stays 154: a binding detects the entry points by name.  A handle that never calls this behaves as before in every entry
+ * point. */
+#define NPB_POLICY_HIDDEN_MAX 3
+#define NPB_POLICY_WIDTH_MAX 128
+enum { NPB_POLICY_RELU = 0, NPB_POLICY_TANH = 1 };
+typedef struct npb_policy_desc_t {
+  int actor_layers, actor_width[NPB_POLICY_HIDDEN_MAX];        /* hidden layers and their widths */
+  int critic_layers, critic_width[NPB_POLICY_HIDDEN_MAX];
+  int activation;                /* NPB_POLICY_RELU | NPB_POLICY_TANH */
+  int deterministic;             /* != 0: z = 0, t stands */
+  uint64_t seed;
+  int64_t first_plant;           /* the counter's first word is first_plant + p */
+  float *value, *logp;           /* device [n_plants] each */
+  float *extras_in;              /* device [n_plants][n_extras]: the rollout's bound extras input, or NULL */
+  int n_extras, value_slot, logp_slot;      /* E; columns of extras_in, -1 = none */
+} npb_policy_desc_t;
+NPB_API int npb_set_policy(NpbHandle *h, const npb_policy_desc_t *desc);
+NPB_API const char *npb_policy_check(const npb_policy_desc_t *desc, int n_plants, int features_cells, int n_axes);
+NPB_API int64_t npb_policy_count(const npb_policy_desc_t *desc, int features_cells, int n_axes);
+NPB_API int npb_policy_load(NpbHandle *h, const float *theta, int theta_is_device, void *stream);
+NPB_API int npb_policy_values(NpbHandle *h, const void *rows, int type, int n_rows, float *out, void *stream);
+NPB_API int npb_policy_noise(NpbHandle *h, uint64_t t, double *z, uint32_t *words, void *stream);
+NPB_API int npb_policy_get_state(NpbHandle *h, uint64_t *t);
+NPB_API int npb_policy_set_state(NpbHandle *h, uint64_t t);
+NPB_API int npb_collect(NpbHandle *h, int steps, double *obs, double *reward, uint8_t *done, uint32_t *trip_flags, double *info, void *stream);
 
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the

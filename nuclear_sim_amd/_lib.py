@@ -929,6 +929,20 @@ class NpbNormalizerDesc(ctypes.Structure):
                 ("gamma", ctypes.c_double), ("clip", ctypes.c_double), ("norm_reward", ctypes.c_void_p)]
 
 
+# include/npb.h npb_policy_desc_t: an MLP actor-critic with Gaussian sampling between the features and the controls' input (npb_set_policy)
+POLICY_HIDDEN_MAX, POLICY_WIDTH_MAX = 3, 128
+POLICY_ACTIVATIONS = {"relu": 0, "tanh": 1}                            # NPB_POLICY_RELU / NPB_POLICY_TANH (policy.ACTIVATIONS)
+
+
+class NpbPolicyDesc(ctypes.Structure):
+    """npb_policy_desc_t: the hidden widths of both nets, the activation, the noise's seed and first plant, the caller's value and logp
+    buffers and the rollout's extras input with the two slots (-1 = none)"""
+    _fields_ = [("actor_layers", ctypes.c_int), ("actor_width", ctypes.c_int * POLICY_HIDDEN_MAX), ("critic_layers", ctypes.c_int),
+                ("critic_width", ctypes.c_int * POLICY_HIDDEN_MAX), ("activation", ctypes.c_int), ("deterministic", ctypes.c_int),
+                ("seed", ctypes.c_uint64), ("first_plant", ctypes.c_int64), ("value", ctypes.c_void_p), ("logp", ctypes.c_void_p),
+                ("extras_in", ctypes.c_void_p), ("n_extras", ctypes.c_int), ("value_slot", ctypes.c_int), ("logp_slot", ctypes.c_int)]
+
+
 def controls_request(axes, interval: int = 1, dtype="float32", heat_source: int = 0) -> dict:
     """What ``BatchedPlantEnv.set_controls`` asks of npb_set_controls, from the caller's words; a pure function, host only, so an axis that
     cannot work is refused (ValueError, naming it) before any device work.
@@ -1231,6 +1245,18 @@ def load():
         L.npb_normalizer_clear.argtypes = [vp, vp, vp]
         L.npb_normalizer_get_state.argtypes = [vp] * 9
         L.npb_normalizer_set_state.argtypes = [vp] * 9
+    if hasattr(L, "npb_set_policy"):     # the policy on the device: actor, critic, the Gaussian draw, K steps in one call
+        L.npb_set_policy.argtypes = [vp, ctypes.POINTER(NpbPolicyDesc)]
+        L.npb_policy_check.argtypes = [ctypes.POINTER(NpbPolicyDesc), ci, ci, ci]
+        L.npb_policy_check.restype = ctypes.c_char_p
+        L.npb_policy_count.argtypes = [ctypes.POINTER(NpbPolicyDesc), ci, ci]
+        L.npb_policy_count.restype = ctypes.c_int64
+        L.npb_policy_load.argtypes = [vp, vp, ci, vp]
+        L.npb_policy_values.argtypes = [vp, vp, ci, ci, vp, vp]
+        L.npb_policy_noise.argtypes = [vp, ctypes.c_uint64, vp, vp, vp]
+        L.npb_policy_get_state.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+        L.npb_policy_set_state.argtypes = [vp, ctypes.c_uint64]
+        L.npb_collect.argtypes = [vp, ci] + [vp] * 6
     if hasattr(L, "npb_rollout_minibatch"):     # pinned moments, the keyed permutation and the minibatch gather over a rollout
         L.npb_rollout_moments.argtypes = [vp, ctypes.POINTER(NpbMomentsDesc), vp]
         L.npb_rollout_permutation.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64, ctypes.c_int64, vp, vp]

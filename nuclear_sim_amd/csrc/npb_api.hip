@@ -12,6 +12,7 @@
 #include "npb_kernels.h"
 #include "npb_noise.h"
 #include "npb_minibatch.h"
+#include "npb_policy.h"
 
 /* a side block's rows as recorded with a snapshot or a bank: a packed [rows][pitch] copy beside that arena, or NULL; its allocation */
 struct SideCopy { double *rows; size_t pitch, doubles; };
@@ -98,6 +99,9 @@ struct NpbHandle {
   npb_rollout_t ro;
   /* npb_rollout_moments: the partials' workspace (base mom.ws), grown on demand */
   npb_moments_ws_t mom;
+  /* npb_set_policy: the shapes, the parameters on the device as the caller packed them and as the kernel reads them (base pol.theta), the
+   * caller's descriptor, and the draw counter t */
+  npb_policy_t pol; uint64_t pol_t;
   double *ramp_prev;   /* npb_profile_ramp: the previous setpoint of every plant ([pitch], NaN = none yet), allocated on first use */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
   std::vector<int> plan_key;
@@ -165,6 +169,9 @@ static const char *const g_no_controls = ": no controls set (npb_set_controls fi
 static const char *const g_no_rollout = ": no rollout set (npb_set_rollout first)";
 static const char *const g_no_normalizer = ": no normaliser set (npb_set_normalizer first)";
 /* npb_set_features / npb_set_controls while a rollout is set, set and NULL alike: its pre kernel copies their tensors, in the shapes it was bound with */
+static const char *const g_no_policy = ": no policy set (npb_set_policy first)";
+/* npb_set_features / npb_set_controls / npb_set_rollout while a policy is set, set and NULL alike: it reads and writes their tensors */
+static const char *const g_policy_holds = ": a policy is set (npb_set_policy) and reads or writes this attachment's tensors every step; npb_set_policy(h, NULL) first";
 static const char *const g_rollout_holds = ": a rollout is set (npb_set_rollout) and records this tensor every step; npb_set_rollout(h, NULL) first";
 /* the body of an npb_*_clear: refused with `off` unless the attachment is on, then its launch on the handle's device */
 template <class Launch> static int attachment_clear(NpbHandle *h, const char *who, const void *on, const char *off, Launch launch) {
@@ -600,6 +607,7 @@ int npb_destroy(NpbHandle *h) {
   attachment_drop(&h->cs, h->cs.cols); attachment_drop(&h->ew, h->ew.cols); attachment_drop(&h->task, h->task.terms);
   attachment_drop(&h->feat, h->feat.cols); attachment_drop(&h->ctl, h->ctl.age); attachment_drop(&h->ro, h->ro.n_final);
   attachment_drop(&h->mom, h->mom.ws); attachment_drop(&h->norm, h->norm.streams);
+  attachment_drop(&h->pol, h->pol.theta);
   for (Sampler *sm : h->samplers) if (sm) { (void)hipFree(sm->dev); delete sm; }
   delete h;
   return NPB_OK;
@@ -1120,6 +1128,16 @@ int npb_locate_field(const NpbHandle *h, int kind, int slot, int *column, int *s
   return NPB_OK;
 }
 
+/* the step's launch of the policy: every plant's features in, the controls' input, value, logp and the extras slots out, at draw t */
+static npd_policy_run_t policy_run(const NpbHandle *h) {
+  const npb_policy_desc_t &D = h->pol.D;
+  npd_policy_run_t R = {};
+  R.x = h->feat.out; R.x_f64 = h->feat.out_f64; R.rows = h->n_plants;
+  R.act = (void *)h->ctl.in; R.act_f64 = h->ctl.in_f64;
+  R.value = D.value; R.logp = D.logp; R.extras = D.extras_in; R.n_extras = D.n_extras; R.value_slot = D.value_slot; R.logp_slot = D.logp_slot;
+  R.seed = D.seed; R.t = h->pol_t; R.first = (uint32_t)D.first_plant; R.deterministic = D.deterministic;
+  return R;
+}
 int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const double *power_setpoint,
              const double *noise_z, const double *cooling_water_temp, double *obs, double *reward, uint8_t *done,
              uint32_t *trip_flags, double *info, void *stream) {
@@ -1180,6 +1198,11 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
     /* the rows taken go into the caller's columns in the restart kernel's launch behind the step (the mode needs the autoreset) */
     es_take = npb_episode_streams_take_t{noise_z, power_setpoint, target, take_noise ? h->es_noise_out : nullptr, take_prof ? h->es_setpoint_out : nullptr,
                                          take_prof ? h->es_target_out : nullptr};
+  }
+  if (h->pol.theta) {      /* the policy: the features read, the controls' input, value and log-probability written, in front of the rollout's record of them */
+    const npd_policy_run_t run = policy_run(h);
+    npb_launch_policy(&h->pol, &run, (hipStream_t)stream);
+    if (!h->pol.D.deterministic) h->pol_t++;
   }
   if (h->ro.n_final)      /* the rollout's slot t: what the policy saw and what it wrote, before the controls kernel and the step change either */
     npb_launch_rollout_pre(&h->ro, h->feat.out, h->ctl.age ? h->ctl.in : nullptr, h->n_plants, (hipStream_t)stream);
@@ -2025,6 +2048,7 @@ const char *npb_features_check(const npb_features_desc_t *D, int n_plants) {
 }
 int npb_set_features(NpbHandle *h, const npb_features_desc_t *desc) {
   if (!h) return NPB_EINVAL;
+  if (h->pol.theta) return fail_who(h, "npb_set_features", g_policy_holds);
   if (h->ro.n_final) return fail_who(h, "npb_set_features", g_rollout_holds);
   if (h->norm.streams && h->norm.n_cols)
     return fail(h, NPB_EINVAL, "npb_set_features: a normaliser with columns is set (npb_set_normalizer) and rewrites this table every step; npb_set_normalizer(h, NULL) first");
@@ -2127,6 +2151,7 @@ const char *npb_controls_check(const npb_controls_desc_t *D, int n_plants, int h
 }
 int npb_set_controls(NpbHandle *h, const npb_controls_desc_t *desc) {
   if (!h) return NPB_EINVAL;
+  if (h->pol.theta) return fail_who(h, "npb_set_controls", g_policy_holds);
   if (h->ro.n_final) return fail_who(h, "npb_set_controls", g_rollout_holds);
   if (const char *why = npb_controls_check(desc, h->n_plants, h->params.heat_source)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
@@ -2202,6 +2227,7 @@ static int rollout_rewind(NpbHandle *h, npb_rollout_t *R, hipStream_t stream) {
 }
 int npb_set_rollout(NpbHandle *h, const npb_rollout_desc_t *desc) {
   if (!h) return NPB_EINVAL;
+  if (h->pol.theta) return fail_who(h, "npb_set_rollout", g_policy_holds);
   if (desc && !h->feat.cols) return fail(h, NPB_EINVAL, "npb_set_rollout: no features set (npb_set_features first): the rollout records their tensor");
   const int cells = h->feat.n_cols * h->feat.stack, n_axes = h->ctl.age ? h->ctl.n_axes : 0;
   if (const char *why = npb_rollout_check(desc, h->n_plants, cells, n_axes)) return fail(h, NPB_EINVAL, why);
@@ -2246,6 +2272,126 @@ int npb_rollout_advantages(NpbHandle *h, const npb_rollout_advantages_desc_t *A,
   NPB_USE_DEVICE(h);
   npb_launch_rollout_advantages(&h->ro, A, A->gamma * A->lam, h->n_plants, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+
+/* ---- the policy (include/npb.h, npb_policy.hip) */
+const char *npb_policy_check(const npb_policy_desc_t *D, int n_plants, int features_cells, int n_axes) {
+  if (!D) return nullptr;
+  if (n_plants < 1) return "npb_set_policy: n_plants must be >= 1";
+  if (features_cells < 1 || features_cells > NPB_FEATURES_CELLS_MAX) return "npb_set_policy: the features' stack must have 1 .. NPB_FEATURES_CELLS_MAX (256) cells: a policy needs features";
+  if (n_axes < 1 || n_axes > NPB_CONTROLS_AXES_MAX) return "npb_set_policy: the axis count must be 1 .. NPB_CONTROLS_AXES_MAX (8): a policy needs controls";
+  if (D->actor_layers < 1 || D->actor_layers > NPB_POLICY_HIDDEN_MAX || D->critic_layers < 1 || D->critic_layers > NPB_POLICY_HIDDEN_MAX)
+    return "npb_set_policy: the actor and the critic have 1 .. NPB_POLICY_HIDDEN_MAX (3) hidden layers each";
+  for (int l = 0; l < D->actor_layers; l++)
+    if (D->actor_width[l] < 1 || D->actor_width[l] > NPB_POLICY_WIDTH_MAX) return "npb_set_policy: a hidden layer of the actor must be 1 .. NPB_POLICY_WIDTH_MAX (128) wide";
+  for (int l = 0; l < D->critic_layers; l++)
+    if (D->critic_width[l] < 1 || D->critic_width[l] > NPB_POLICY_WIDTH_MAX) return "npb_set_policy: a hidden layer of the critic must be 1 .. NPB_POLICY_WIDTH_MAX (128) wide";
+  if (D->activation != NPB_POLICY_RELU && D->activation != NPB_POLICY_TANH) return "npb_set_policy: an unknown activation";
+  if (D->first_plant < 0 || D->first_plant + (int64_t)n_plants > ((int64_t)1 << 32)) return "npb_set_policy: first_plant must be >= 0 and first_plant + n_plants <= 2^32, what the counter's first word holds";
+  if (!D->value || !D->logp) return "npb_set_policy: NULL value or logp";
+  if (((uintptr_t)D->value | (uintptr_t)D->logp) & 3u) return "npb_set_policy: misaligned value or logp: 4-byte aligned";
+  if (!D->extras_in) {
+    if (D->value_slot >= 0 || D->logp_slot >= 0) return "npb_set_policy: a value or logp slot without extras_in";
+  } else {
+    if (D->n_extras < 1 || D->n_extras > NPB_ROLLOUT_EXTRAS_MAX) return "npb_set_policy: extras_in with an extras count outside 1 .. NPB_ROLLOUT_EXTRAS_MAX (8)";
+    if (D->value_slot < -1 || D->value_slot >= D->n_extras || D->logp_slot < -1 || D->logp_slot >= D->n_extras)
+      return "npb_set_policy: a value or logp slot outside -1 .. E - 1";
+    if (D->value_slot >= 0 && D->value_slot == D->logp_slot) return "npb_set_policy: value and logp in the same slot";
+    if ((uintptr_t)D->extras_in & 3u) return "npb_set_policy: a misaligned extras_in: 4-byte aligned";
+  }
+  return nullptr;
+}
+int64_t npb_policy_count(const npb_policy_desc_t *D, int features_cells, int n_axes) {
+  if (!D || npb_policy_check(D, 1, features_cells, n_axes)) return 0;
+  npb_policy_t P = {};
+  npb_policy_layout(D, features_cells, n_axes, &P);
+  return (int64_t)P.theta_count;
+}
+int npb_set_policy(NpbHandle *h, const npb_policy_desc_t *desc) {
+  if (!h) return NPB_EINVAL;
+  if (desc && !h->feat.cols) return fail(h, NPB_EINVAL, "npb_set_policy: no features set (npb_set_features first): the policy reads their tensor");
+  if (desc && !h->ctl.age) return fail(h, NPB_EINVAL, "npb_set_policy: no controls set (npb_set_controls first): the policy writes their input");
+  if (const char *why = npb_policy_check(desc, h->n_plants, h->feat.n_cols * h->feat.stack, h->ctl.n_axes)) return fail(h, NPB_EINVAL, why);
+  if (desc && desc->extras_in && (!h->ro.n_final || desc->extras_in != h->ro.D.extras_in || desc->n_extras != h->ro.D.n_extras))
+    return fail(h, NPB_EINVAL, "npb_set_policy: extras_in and its count must be the set rollout's (npb_set_rollout first)");
+  NPB_USE_DEVICE(h);
+  if (!desc) { attachment_drop(&h->pol, h->pol.theta); h->pol_t = 0; return NPB_OK; }
+  npb_policy_t P = {};
+  npb_policy_layout(desc, h->feat.n_cols * h->feat.stack, h->ctl.n_axes, &P);
+  /* the allocation: theta [theta_count, padded to 4 floats] | the kernel's copy of the weights [padded_count]; all zero */
+  const size_t theta_floats = ((size_t)P.theta_count + 3) & ~(size_t)3, bytes = (theta_floats + P.padded_count) * sizeof(float);
+  char *dev = nullptr;
+  if (int rc = attachment_alloc(h, "npb_set_policy", "the parameters", nullptr, 0, bytes, &dev)) return rc;
+  P.theta = (float *)dev; P.padded = P.theta + theta_floats;
+  attachment_drop(&h->pol, h->pol.theta);
+  h->pol = P; h->pol_t = 0;
+  return NPB_OK;
+}
+int npb_policy_load(NpbHandle *h, const float *theta, int theta_is_device, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->pol.theta) return fail_who(h, "npb_policy_load", g_no_policy);
+  if (!theta) return fail(h, NPB_EINVAL, "npb_policy_load: NULL theta");
+  NPB_USE_DEVICE(h);
+  NPB_HIP(h, hipMemcpyAsync(h->pol.theta, theta, (size_t)h->pol.theta_count * sizeof(float), theta_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                            (hipStream_t)stream));
+  if (!theta_is_device) NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));      /* the host array may go */
+  npb_launch_policy_repack(&h->pol, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_policy_values(NpbHandle *h, const void *rows, int type, int n_rows, float *out, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->pol.theta) return fail_who(h, "npb_policy_values", g_no_policy);
+  if (!rows) { rows = h->feat.out; type = h->feat.out_f64 ? NPB_FEATURES_F64 : NPB_FEATURES_F32; n_rows = h->n_plants; }
+  if (type != NPB_FEATURES_F32 && type != NPB_FEATURES_F64) return fail(h, NPB_EINVAL, "npb_policy_values: an unknown type");
+  if (n_rows < 1) return fail(h, NPB_EINVAL, "npb_policy_values: n_rows must be >= 1");
+  if (!out || ((uintptr_t)out & 3u) || ((uintptr_t)rows & (type == NPB_FEATURES_F64 ? 7u : 3u)))
+    return fail(h, NPB_EINVAL, "npb_policy_values: a NULL or misaligned out (4-byte aligned), or rows misaligned for their type");
+  NPB_USE_DEVICE(h);
+  npd_policy_run_t R = {};
+  R.x = rows; R.x_f64 = type == NPB_FEATURES_F64; R.rows = n_rows; R.value = out;
+  npb_launch_policy(&h->pol, &R, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_policy_noise(NpbHandle *h, uint64_t t, double *z, uint32_t *words, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->pol.theta) return fail_who(h, "npb_policy_noise", g_no_policy);
+  if ((!z && !words) || ((uintptr_t)z & 7u) || ((uintptr_t)words & 3u)) return fail(h, NPB_EINVAL, "npb_policy_noise: z and words both NULL, or one of them misaligned");
+  NPB_USE_DEVICE(h);
+  npb_launch_policy_noise(&h->pol, t, h->n_plants, z, words, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_policy_get_state(NpbHandle *h, uint64_t *t) {
+  if (!h) return NPB_EINVAL;
+  if (!h->pol.theta) return fail_who(h, "npb_policy_get_state", g_no_policy);
+  if (!t) return fail(h, NPB_EINVAL, "npb_policy_get_state: NULL output");
+  *t = h->pol_t;
+  return NPB_OK;
+}
+int npb_policy_set_state(NpbHandle *h, uint64_t t) {
+  if (!h) return NPB_EINVAL;
+  if (!h->pol.theta) return fail_who(h, "npb_policy_set_state", g_no_policy);
+  h->pol_t = t;
+  return NPB_OK;
+}
+int npb_collect(NpbHandle *h, int steps, double *obs, double *reward, uint8_t *done, uint32_t *trip_flags, double *info, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->pol.theta) return fail_who(h, "npb_collect", g_no_policy);
+  if (!h->ro.n_final) return fail_who(h, "npb_collect", g_no_rollout);
+  if (steps < 1) return fail(h, NPB_EINVAL, "npb_collect: steps must be >= 1");
+  if (h->ro.t + steps > h->ro.D.horizon)
+    return fail(h, NPB_EINVAL, "npb_collect: the rollout has no room for that many steps (t + steps > horizon): npb_rollout_begin rewinds it");
+  if (h->params.heat_source == NPB_HEAT_EXTERNAL)
+    return fail(h, NPB_EINVAL, "npb_collect: params.heat_source is NPB_HEAT_EXTERNAL, whose thermal power the caller brings every step: npb_step");
+  if (h->params.hs_noise_enabled && !(h->es_on && h->es.noise.key))
+    return fail(h, NPB_EINVAL, "npb_collect: the heat-source noise is enabled and its draws come from the caller every step: npb_step, or episode streams (npb_set_episode_streams)");
+  if (h->prof && !(h->es_on && h->es.prof.key))
+    return fail(h, NPB_EINVAL, "npb_collect: a power profile is seeded (npb_profile_seed) and its rows come from the caller every step: npb_step, or episode streams (npb_set_episode_streams)");
+  for (int s = 0; s < steps; s++)
+    if (int rc = npb_step(h, nullptr, nullptr, nullptr, nullptr, nullptr, obs, reward, done, trip_flags, info, stream)) return rc;
   return NPB_OK;
 }
 

@@ -1,0 +1,266 @@
+/* npb_policy.hip -- the policy on the device (npb_set_policy, include/npb.h): a diagonal-Gaussian actor and a critic, two MLPs over every
+ * plant's features stack, the Gaussian draw, the log-probability and the value, in ONE launch in front of every step.
+ * nuclear_sim_amd/policy.py states it in numpy; this file produces its bits (its float tanh apart, which the statement licenses): a layer
+ * is bias, then fmaf(x[k], W[j][k], acc) for k ascending in float32, k extended with +0.0 cells and +0.0 weights to a multiple of 4; the
+ * epilogue runs in double with every operation rounded on its own.  Built with the noise generator's flags (Makefile): no contraction, IEEE
+ * division and square root, no -freciprocal-math / -fapprox-func.
+ *
+ * THE KERNEL THAT SHIPS RUNS ON THE MATRIX CORES: v_mfma_f32_32x32x2_f32 is exact f32, one rounding per product in k order, and the
+ * relu tests hold it to the statement's bits (DESIGN.md has the v_fma_f32 chain it replaced and both times).
+ * One workgroup of 256 lanes (four waves) per tile of 32 plants.
+ *   1. the tile's 32 rows of x are ONE contiguous run of 32 x K*C elements: loaded with consecutive lanes on consecutive elements,
+ *      narrowed to float and transposed into LDS, xs[k][r] with a row stride of 33 (consecutive lanes write consecutive k: 33 spreads them
+ *      over the banks; a layer reads xs[k][r] with consecutive lanes on consecutive r).  A row beyond `rows` is neither loaded nor stored.
+ *      A cell that is not finite marks its plant (a plain LDS store of 1: every writer writes the same).
+ *   2. a layer: a wave takes 32 outputs at a time (npd_policy_layer says how the operands lie): per call one LDS read of the A operand
+ *      straight from xs / h, and one coalesced load of the B operand from the copy npb_policy_load made, Wt[k][j] with k and j padded
+ *      with +0.0 (rows of 128 bytes a half-wave).  The bias is the initial accumulator.  The activation, then h[j][r] into LDS, the
+ *      same layout and stride (a lane holds 16 plants of ONE output: its stores go 33 floats apart from its neighbour's: no conflict);
+ *      outputs beyond the width, up to the next multiple of 4, are written +0.0: they are the next layer's k extension.  A barrier
+ *      between layers; two hidden buffers, ping-pong; the actor first, then the critic, xs kept.  A layer narrower than 128 leaves
+ *      waves without a chunk: they wait at the barrier.
+ *   3. the epilogue, a lane being (group g = 0 .. 7, plant r = 0 .. 31): group j < ceil(A / 2) draws pair j of its plant (Philox4x32-10,
+ *      Box-Muller in double; npd_policy_pair, the function npb_policy_noise runs) into LDS; then group a < A forms and stores action a,
+ *      and group 7 the log-probability (ascending over the axes), value and logp, and the two extras slots.  A marked plant stores THE
+ *      quiet NaN everywhere.
+ * LDS: the small build (K*C <= 64, widths <= 64) 3 x 8.25 KiB and the epilogue's 4.7 KiB; the large one (256, 128) 33 + 2 x 16.5 KiB
+ * and the same -- static, beyond 64 KiB, which gfx950's 160 KiB per CU allows.  No scratch, no atomics, plain vector stores. */
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include "npb_policy.h"
+
+#define NPD_POLICY_TILE 32
+#define NPD_POLICY_GROUPS 8
+#define NPD_POLICY_LANES (NPD_POLICY_TILE * NPD_POLICY_GROUPS)
+#define NPD_POLICY_WAVES 4
+#define NPD_POLICY_AHEAD 8        /* matrix-core calls whose operands are in flight together */
+#define NPD_POLICY_STRIDE (NPD_POLICY_TILE + 1)      /* the LDS row stride of every [k][plant] buffer (the header says why it is odd) */
+
+/* ---- the noise: Philox4x32-10 and the pair of normals of one call (policy.py: philox4x32, noise_from_words) */
+__device__ __forceinline__ void npd_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t w[4]) {
+#pragma unroll
+  for (int round = 0; round < 10; round++) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0, hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+/* call j of plant `id` at draw t: z of axes 2j and 2j + 1 */
+__device__ __forceinline__ void npd_policy_pair(uint64_t seed, uint32_t id, uint64_t t, uint32_t j, uint32_t w[4], double *z0, double *z1) {
+  npd_philox4x32_10(id, (uint32_t)t, (uint32_t)(t >> 32), j, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+  const double u1 = (((double)w[0] * 1048576.0 + (double)(w[1] >> 12)) + 0.5) * 0x1p-52;
+  const double u2 = (((double)w[2] * 1048576.0 + (double)(w[3] >> 12)) + 0.5) * 0x1p-52;
+  const double r = sqrt(-2.0 * log(u1)), th = 6.283185307179586 * u2;
+  *z0 = r * cos(th);
+  *z1 = r * sin(th);
+}
+__global__ __launch_bounds__(256) void npb_policy_noise_kernel(uint64_t seed, uint32_t first, uint64_t t, int n_plants, int n_axes, double *z, uint32_t *words) {
+  const int J = (n_axes + 1) / 2;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)n_plants * J) return;
+  const size_t p = i / J;
+  const int j = (int)(i - p * J);
+  uint32_t w[4];
+  double z0, z1;
+  npd_policy_pair(seed, first + (uint32_t)p, t, (uint32_t)j, w, &z0, &z1);
+  if (z) {
+    z[p * n_axes + 2 * j] = z0;
+    if (2 * j + 1 < n_axes) z[p * n_axes + 2 * j + 1] = z1;
+  }
+  if (words) {
+#pragma unroll
+    for (int q = 0; q < 4; q++) words[i * 4 + q] = w[q];
+  }
+}
+
+/* ---- the kernel's copy of the weights, in the order the matrix cores' B operand is read: Wt[k][j], in_pad rows of out_pad floats (out_pad:
+ * the width up to a multiple of 32), the cells beyond `in` and beyond `out` +0.0 */
+__global__ __launch_bounds__(256) void npb_policy_repack_kernel(npb_policy_t P) {
+  const size_t first = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (int which = 0; which < 2; which++) {
+    const npd_policy_net_t &N = which ? P.critic : P.actor;
+    for (int l = 0; l < N.n_layers; l++) {
+      const npd_policy_layer_t L = N.layer[l];
+      const size_t total = (size_t)L.in_pad * L.out_pad;
+      for (size_t i = first; i < total; i += stride) {
+        const size_t k = i / L.out_pad, j = i - k * L.out_pad;
+        P.padded[L.wp + i] = k < (size_t)L.in && j < (size_t)L.out ? P.theta[L.w + j * L.in + k] : 0.0f;
+      }
+    }
+  }
+}
+
+/* ---- the nets */
+/* one layer over the tile on the matrix cores: in[k][r] -> out[j][r] (row stride NPD_POLICY_STRIDE both), j up to the next multiple of 4
+ * of the width; activation: NPB_POLICY_RELU, NPB_POLICY_TANH, or -1 for a head.  Wave `wave` takes the chunks wave, wave + 4, .. of 32
+ * outputs.  v_mfma_f32_32x32x2_f32: D[i][j] = fma(A[i][k0 + 1], B[k0 + 1][j], fma(A[i][k0], B[k0][j], C[i][j])), one rounding per product:
+ * the statement's chain, two k a call.  i is the plant, j the output.  Lane l gives A[i = l & 31][k = l >> 5] = in[k0 + (l >> 5)][l & 31]
+ * and B[k = l >> 5][j = l & 31] = Wt[k0 + (l >> 5)][j0 + (l & 31)], and holds D[i = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5)][j = l & 31] in
+ * register reg of 16: its column's bias is the initial accumulator of all 16 */
+typedef float npd_f32x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ void npd_policy_layer(const npd_policy_layer_t &L, const float *__restrict__ theta, const float *__restrict__ padded,
+                                                 const float *in, float *out, int activation, int wave, int lane) {
+  const int col = lane & 31, half = lane >> 5, out_pad4 = (L.out + 3) & ~3, pairs = L.in_pad >> 1;
+  for (int j0 = 32 * wave; j0 < L.out_pad; j0 += 32 * NPD_POLICY_WAVES) {
+    const int j = j0 + col;
+    const float bias = j < L.out ? theta[L.b + j] : 0.0f;
+    npd_f32x16 acc;
+#pragma unroll
+    for (int reg = 0; reg < 16; reg++) acc[reg] = bias;
+    const float *a = in + half * NPD_POLICY_STRIDE + col;
+    const float *b = padded + L.wp + (size_t)half * L.out_pad + j;
+    /* the operands of NPD_POLICY_AHEAD calls are asked for before the first of them runs: a call waits for its own two loads only, and
+     * the chain of dependent calls is the same chain (no call is added for padding: fma(+0, +0, acc) would turn an accumulator of -0.0) */
+    int s = 0;
+    for (; s + NPD_POLICY_AHEAD <= pairs; s += NPD_POLICY_AHEAD) {
+      float av[NPD_POLICY_AHEAD], bv[NPD_POLICY_AHEAD];
+#pragma unroll
+      for (int u = 0; u < NPD_POLICY_AHEAD; u++) {
+        av[u] = a[2 * (s + u) * NPD_POLICY_STRIDE];
+        bv[u] = b[(size_t)(2 * (s + u)) * L.out_pad];
+      }
+#pragma unroll
+      for (int u = 0; u < NPD_POLICY_AHEAD; u++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc, 0, 0, 0);
+    }
+    for (; s < pairs; s++)
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2 * s * NPD_POLICY_STRIDE], b[(size_t)(2 * s) * L.out_pad], acc, 0, 0, 0);
+    if (j < out_pad4) {
+#pragma unroll
+      for (int reg = 0; reg < 16; reg++) {
+        const int plant = (reg & 3) + 8 * (reg >> 2) + 4 * half;
+        float y = acc[reg];
+        if (activation == NPB_POLICY_RELU) y = y > 0.0f ? y : 0.0f;
+        else if (activation == NPB_POLICY_TANH) y = tanhf(y);
+        out[j * NPD_POLICY_STRIDE + plant] = j < L.out ? y : 0.0f;
+      }
+    }
+  }
+}
+/* a whole net: xs -> the head's outputs in head[j][r]; a, b: the two hidden buffers */
+__device__ __forceinline__ void npd_policy_net(const npd_policy_net_t &N, const float *theta, const float *padded, const float *xs, float *a, float *b,
+                                               float *head, int activation, int wave, int lane) {
+  const float *in = xs;
+  for (int l = 0; l < N.n_layers; l++) {
+    const bool last = l == N.n_layers - 1;
+    float *out = last ? head : (l & 1) ? b : a;
+    npd_policy_layer(N.layer[l], theta, padded, in, out, last ? -1 : activation, wave, lane);
+    __syncthreads();
+    in = out;
+  }
+}
+
+template <typename IN, int KC_MAX, int H_MAX>
+__global__ __launch_bounds__(NPD_POLICY_LANES) void npb_policy_kernel(npb_policy_t P, npd_policy_run_t R) {
+  __shared__ float xs[KC_MAX * NPD_POLICY_STRIDE];
+  __shared__ float ha[H_MAX * NPD_POLICY_STRIDE], hb[H_MAX * NPD_POLICY_STRIDE];
+  __shared__ float mean[NPB_CONTROLS_AXES_MAX * NPD_POLICY_STRIDE], val[4 * NPD_POLICY_STRIDE];
+  __shared__ double zs[NPB_CONTROLS_AXES_MAX * NPD_POLICY_TILE];
+  __shared__ int bad[NPD_POLICY_TILE];
+  const int tid = threadIdx.x, g = tid >> 5, r = tid & (NPD_POLICY_TILE - 1);
+  const size_t base = (size_t)blockIdx.x * NPD_POLICY_TILE, rows = (size_t)R.rows;
+  const int in_tile = rows - base < (size_t)NPD_POLICY_TILE ? (int)(rows - base) : NPD_POLICY_TILE;
+  const int KC = P.cells, KC_pad = (KC + 3) & ~3;
+  /* 1. the tile's run of x into LDS, narrowed and transposed; the k extension +0.0 */
+  if (tid < NPD_POLICY_TILE) bad[tid] = 0;
+  for (int i = tid; i < (KC_pad - KC) * NPD_POLICY_TILE; i += NPD_POLICY_LANES)
+    xs[(KC + i / NPD_POLICY_TILE) * NPD_POLICY_STRIDE + (i & (NPD_POLICY_TILE - 1))] = 0.0f;
+  __syncthreads();
+  const IN *run = (const IN *)R.x + base * (size_t)KC;
+  const int total = in_tile * KC;
+  for (int e = tid; e < total; e += NPD_POLICY_LANES) {
+    const int row = e / KC, k = e - row * KC;
+    const float v = (float)run[e];
+    xs[k * NPD_POLICY_STRIDE + row] = v;
+    if (!(v - v == 0.0f)) bad[row] = 1;
+  }
+  __syncthreads();
+  /* 2. the nets */
+  const int wave = tid >> 6, lane = tid & 63;
+  if (R.act) npd_policy_net(P.actor, P.theta, P.padded, xs, ha, hb, mean, P.D.activation, wave, lane);
+  npd_policy_net(P.critic, P.theta, P.padded, xs, ha, hb, val, P.D.activation, wave, lane);
+  const bool live = r < in_tile;
+  const size_t p = base + r;
+  const float qnan = __builtin_nanf("");
+  if (!R.act) {      /* npb_policy_values */
+    if (g == 0 && live) R.value[p] = bad[r] ? qnan : val[r];
+    return;
+  }
+  /* 3. the draw, then the outputs */
+  const int A = P.n_axes;
+  if (2 * g < A) {
+    double z0 = 0.0, z1 = 0.0;
+    if (!R.deterministic && live) {
+      uint32_t w[4];
+      npd_policy_pair(R.seed, R.first + (uint32_t)p, R.t, (uint32_t)g, w, &z0, &z1);
+    }
+    zs[(2 * g) * NPD_POLICY_TILE + r] = z0;
+    if (2 * g + 1 < NPB_CONTROLS_AXES_MAX) zs[(2 * g + 1) * NPD_POLICY_TILE + r] = z1;
+  }
+  __syncthreads();
+  if (!live) return;
+  const bool poisoned = bad[r] != 0;
+  if (g < A) {
+    const double scaled = (double)P.theta[P.std + g] * zs[g * NPD_POLICY_TILE + r];
+    const double a = (double)mean[g * NPD_POLICY_STRIDE + r] + scaled;
+    if (R.act_f64) ((double *)R.act)[p * A + g] = poisoned ? (double)qnan : a;
+    else ((float *)R.act)[p * A + g] = poisoned ? qnan : (float)a;
+  }
+  if (g == NPD_POLICY_GROUPS - 1) {
+    double lp = -((double)A * 0.9189385332046727);
+    for (int a = 0; a < A; a++) {
+      const double z = zs[a * NPD_POLICY_TILE + r], sq = z * z, half = 0.5 * sq;
+      lp = (lp - half) - (double)P.theta[P.log_std + a];
+    }
+    const float value = poisoned ? qnan : val[r], logp = poisoned ? qnan : (float)lp;
+    R.value[p] = value;
+    R.logp[p] = logp;
+    if (R.extras && R.value_slot >= 0) R.extras[p * R.n_extras + R.value_slot] = value;
+    if (R.extras && R.logp_slot >= 0) R.extras[p * R.n_extras + R.logp_slot] = logp;
+  }
+}
+
+/* ---- the launchers */
+extern "C" void npb_policy_layout(const npb_policy_desc_t *D, int cells, int n_axes, npb_policy_t *P) {
+  uint32_t at = 0, wp = 0;
+  int widest = 0;
+  for (int which = 0; which < 2; which++) {
+    npd_policy_net_t &N = which ? P->critic : P->actor;
+    const int hidden = which ? D->critic_layers : D->actor_layers;
+    const int *width = which ? D->critic_width : D->actor_width;
+    N.n_layers = hidden + 1;
+    int in = cells;
+    for (int l = 0; l <= hidden; l++) {
+      npd_policy_layer_t &L = N.layer[l];
+      L.in = in; L.in_pad = (in + 3) & ~3; L.out = l < hidden ? width[l] : which ? 1 : n_axes;
+      L.w = at; at += (uint32_t)L.in * L.out;
+      L.b = at; at += (uint32_t)L.out;
+      L.out_pad = (L.out + 31) & ~31;
+      L.wp = wp; wp += (uint32_t)L.in_pad * L.out_pad;
+      if (l < hidden && L.out > widest) widest = L.out;
+      in = L.out;
+    }
+  }
+  P->log_std = at; P->std = at + (uint32_t)n_axes;
+  P->theta_count = at + 2u * (uint32_t)n_axes;
+  P->padded_count = wp;
+  P->cells = cells; P->n_axes = n_axes; P->width_max = widest;
+  P->D = *D;
+}
+extern "C" void npb_launch_policy_repack(const npb_policy_t *P, hipStream_t stream) {
+  const unsigned blocks = (P->padded_count + 255u) / 256u;
+  hipLaunchKernelGGL(npb_policy_repack_kernel, dim3(blocks < 64u ? blocks : 64u), dim3(256), 0, stream, *P);
+}
+extern "C" void npb_launch_policy(const npb_policy_t *P, const npd_policy_run_t *R, hipStream_t stream) {
+  const dim3 grid((unsigned)((R->rows + NPD_POLICY_TILE - 1) / NPD_POLICY_TILE)), block(NPD_POLICY_LANES);
+  const bool small = P->cells <= 64 && P->width_max <= 64;
+#define NPD_POLICY_LAUNCH(IN, KC_MAX, H_MAX) hipLaunchKernelGGL((npb_policy_kernel<IN, KC_MAX, H_MAX>), grid, block, 0, stream, *P, *R)
+  if (R->x_f64) { if (small) NPD_POLICY_LAUNCH(double, 64, 64); else NPD_POLICY_LAUNCH(double, NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX); }
+  else { if (small) NPD_POLICY_LAUNCH(float, 64, 64); else NPD_POLICY_LAUNCH(float, NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX); }
+#undef NPD_POLICY_LAUNCH
+}
+extern "C" void npb_launch_policy_noise(const npb_policy_t *P, uint64_t t, int n_plants, double *z, uint32_t *words, hipStream_t stream) {
+  const size_t calls = (size_t)n_plants * ((P->n_axes + 1) / 2);
+  hipLaunchKernelGGL(npb_policy_noise_kernel, dim3((unsigned)((calls + 255) / 256)), dim3(256), 0, stream, P->D.seed, (uint32_t)P->D.first_plant, t, n_plants,
+                     P->n_axes, z, words);
+}

@@ -19,7 +19,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, normalizer, recordlog, rollout
+from . import _lib, normalizer, policy, recordlog, rollout
 from .schema import SCHEMA
 
 
@@ -504,7 +504,7 @@ class BatchedPlantEnv:
         self._keep = []
         self._episode = None
         self._bank = None
-        self._mlog = self._msum = self._erec = self._cstats = self._ewin = self._task = self._feat = self._ctl = self._roll = self._norm = None      # (see ``_OFF``)
+        self._mlog = self._msum = self._erec = self._cstats = self._ewin = self._task = self._feat = self._ctl = self._roll = self._norm = self._pol = None      # (see ``_OFF``)
         self._diag_buf = None; self.diagnostics = None; self._diag_carried = False
         if diagnostics:      # before the first snapshot (autoreset=True takes it below), so that it records the carried rows
             self.enable_diagnostics(True, carried=True)
@@ -973,13 +973,13 @@ class BatchedPlantEnv:
     # The per-step attachments -- maintenance log and summary, episode records, column statistics, event windows, task, features,
     # controls, rollout: None = off, else what the enable_* / set_* method keeps of it.  __init__ sets them; the class has them too, so that a
     # refusal "before any device work" can be checked on an object made without it.  ``_on`` reads them, with these refusals:
-    _mlog = _msum = _erec = _cstats = _ewin = _task = _feat = _ctl = _roll = _norm = None
+    _mlog = _msum = _erec = _cstats = _ewin = _task = _feat = _ctl = _roll = _norm = _pol = None
     _max_episode_steps = 0      # the autoreset's limit, 0 = none (``_enable_autoreset``)
     _OFF = {"_mlog": "no maintenance log: enable_maintenance_log() first", "_msum": "no maintenance summary: enable_maintenance_summary() first",
             "_erec": "no episode records: enable_episode_records() first", "_cstats": "no column statistics: enable_column_stats() first",
             "_ewin": "no event windows: enable_event_windows() first", "_task": "no task: set_task() first",
             "_feat": "no features: set_features() first", "_ctl": "no controls: set_controls() first", "_roll": "no rollout: set_rollout() first",
-            "_norm": "no normaliser: set_normalizer() first"}
+            "_norm": "no normaliser: set_normalizer() first", "_pol": "no policy: set_policy() first"}
     # who reads side buffers, as a refusal names them: each keeps ``"reads"``, the buffers its request resolved to (``_reading``)
     _CONSUMERS = {"_task": "the task", "_feat": "the features", "_cstats": "the column statistics", "_ewin": "the event windows",
                   "_norm": "the normaliser"}
@@ -1590,6 +1590,8 @@ class BatchedPlantEnv:
     def _refuse_under_rollout(self, what: str) -> None:
         """``set_features`` / ``set_controls`` while a rollout is set, set and None alike: its pre kernel copies their tensors every step,
         in the shapes it was bound with"""
+        if self._pol is not None:
+            raise _lib.NpbError("the policy reads or writes %s every step: set_policy(None) first" % what)
         if self._roll is not None:
             raise _lib.NpbError("the rollout records %s every step: set_rollout(None) first" % what)
 
@@ -1606,6 +1608,8 @@ class BatchedPlantEnv:
         ``rollout_begin()`` rewinds.  ``rollout_advantages`` forms GAE advantages and returns over the recorded slots in one launch.
         While the rollout is set ``set_features`` and ``set_controls`` are refused.  ``nuclear_sim_amd.rollout`` is the same in numpy, bit
         for bit.  ``set_rollout(None)`` turns it off."""
+        if self._pol is not None:
+            raise _lib.NpbError("the policy writes the rollout's extras every step: set_policy(None) first")
         if horizon is None:
             if self._roll is not None:
                 _lib.check(self.L.npb_set_rollout(self._h, None), self._h)
@@ -1835,6 +1839,189 @@ class BatchedPlantEnv:
                            "extra": view(buf["extra"], count, E), "adv": view(buf["adv"], count), "ret": view(buf["ret"], count), "epoch": e}
             del held
         return batches()
+
+    # ------------------------------------------------------------------ the policy on the device
+    @staticmethod
+    def _policy_layers(net, who):
+        """a net as a list of ``(W, b)`` tensors: the ``nn.Linear`` layers of a module in their order, or the caller's pairs"""
+        if isinstance(net, torch.nn.Module):
+            pairs = [(m.weight, m.bias) for m in net.modules() if isinstance(m, torch.nn.Linear)]
+            if any(b is None for _, b in pairs):
+                raise ValueError("a Linear layer of the %s has no bias" % who)
+        else:
+            pairs = [(torch.as_tensor(W), torch.as_tensor(b)) for W, b in net]
+        if len(pairs) < 2:
+            raise ValueError("the %s needs at least one hidden layer and its head" % who)
+        for W, b in pairs:
+            if W.dim() != 2 or tuple(b.shape) != (W.shape[0],):
+                raise ValueError("a layer of the %s is W[out][in] with b[out]" % who)
+        return pairs
+
+    def _policy_theta(self, actor, critic, log_std):
+        """``(theta, actor widths, critic widths)``: theta a float32 device tensor in the statement's order, std = exp(log_std) formed here"""
+        a, c = self._policy_layers(actor, "actor"), self._policy_layers(critic, "critic")
+        with torch.no_grad():
+            ls = torch.as_tensor(log_std).detach().to(device=self.device, dtype=torch.float32).reshape(-1)
+            flat = [x.detach().to(device=self.device, dtype=torch.float32).reshape(-1) for W, b in a + c for x in (W, b)]
+            theta = torch.cat(flat + [ls, torch.exp(ls)]).contiguous()
+        shapes = tuple([tuple(W.shape) for W, _ in net] for net in (a, c))
+        return theta, shapes, int(ls.numel())
+
+    def set_policy(self, actor, critic=None, log_std=None, activation: str = "tanh", seed: int = 0, deterministic: bool = False, extras=None,
+                   first_plant: int = 0) -> None:
+        """Run the policy on the device (npb_set_policy): in front of every ``step()`` ONE launch reads every plant's features stack,
+        runs a diagonal-Gaussian actor and a critic -- two MLPs of 1 to 3 hidden layers, up to 128 wide, ``"relu"`` or ``"tanh"`` -- draws
+        the noise, and writes the action into ``controls_input()``, and value and log-probability into tensors the env keeps
+        (``policy_outputs()``, ``info["value"]``, ``info["logp"]``).  Features and controls must be set; the actor's head has one output
+        per axis.  ``actor`` / ``critic``: ``torch.nn`` modules (their ``Linear`` layers in order, head last) or lists of ``(W, b)``;
+        ``log_std``: [n_axes]; ``std = exp(log_std)`` is formed here, in torch.  ``extras``: with a rollout set, where value and logp go
+        in its extras -- a tuple of names in slot order, e.g. ``("value", "logp")`` (None entries are left to the caller), or a dict
+        name -> slot -- so the rollout records them by itself.  ``seed`` and ``first_plant`` key the noise (Philox4x32-10, counter
+        ``(first_plant + p, t, j)``): shards of one batch draw what the whole batch would.  ``deterministic``: the mean, no draw.
+        While a policy is set ``set_features``, ``set_controls`` and ``set_rollout`` are refused, and so is ``step(controls=...)``.
+        ``nuclear_sim_amd.policy`` is the same in numpy: bit for bit with relu, within the float tanh's error with tanh.
+        ``logp`` is the density of the unrounded action.  ``set_policy(None)`` turns it off."""
+        if actor is None:
+            if self._pol is not None:
+                _lib.check(self.L.npb_set_policy(self._h, None), self._h)
+            self._pol = None
+            return
+        ft, ct = self._on("_feat"), self._on("_ctl")
+        if not hasattr(self.L, "npb_set_policy"):
+            raise _lib.NpbError("libnpb.so has no npb_set_policy: rebuild")
+        if critic is None or log_std is None:
+            raise ValueError("set_policy takes an actor, a critic and log_std")
+        theta, (ashape, cshape), n_ls = self._policy_theta(actor, critic, log_std)
+        n, (_, K, C), A = self.n, ft["out"].shape, ct["in"].shape[1]
+        hidden = tuple(tuple(o for o, _ in shape[:-1]) for shape in (ashape, cshape))
+        policy.check(K * C, A, hidden[0], hidden[1], activation)
+        want = policy.sizes(K * C, A, hidden[0], hidden[1])
+        if [(i, o) for o, i in ashape] != want[0] or [(i, o) for o, i in cshape] != want[1] or n_ls != A:
+            raise ValueError("the nets do not fit: both read %d cells, the actor's head and log_std have %d entries, the critic's head one" % (K * C, A))
+        slots = {"value": -1, "logp": -1}
+        if extras is not None:
+            ro = self._on("_roll")
+            named = extras.items() if isinstance(extras, dict) else [(name, j) for j, name in enumerate(extras) if name is not None]
+            for name, j in named:
+                if name not in slots or slots[name] >= 0 or not 0 <= int(j) < ro["spec"]["extras"]:
+                    raise ValueError("extras names 'value' and 'logp' once each, in slots 0 .. %d, not %r" % (ro["spec"]["extras"] - 1, extras))
+                slots[name] = int(j)
+        with torch.cuda.device(self.device):
+            value = torch.zeros((n,), dtype=torch.float32, device=self.device)
+            logp = torch.zeros((n,), dtype=torch.float32, device=self.device)
+        d = _lib.NpbPolicyDesc()
+        for name, widths in (("actor", hidden[0]), ("critic", hidden[1])):
+            setattr(d, name + "_layers", len(widths))
+            for l, w in enumerate(widths):
+                getattr(d, name + "_width")[l] = w
+        d.activation, d.deterministic, d.seed, d.first_plant = _lib.POLICY_ACTIVATIONS[activation], int(bool(deterministic)), int(seed) & (2 ** 64 - 1), int(first_plant)
+        d.value, d.logp = value.data_ptr(), logp.data_ptr()
+        d.value_slot, d.logp_slot = slots["value"], slots["logp"]
+        if extras is not None and (slots["value"] >= 0 or slots["logp"] >= 0):
+            d.extras_in, d.n_extras = self._roll["extras_in"].data_ptr(), self._roll["spec"]["extras"]
+        _lib.check(self.L.npb_set_policy(self._h, ctypes.byref(d)), self._h)      # (refused: what was set before stays)
+        self._pol = {"value": value, "logp": logp, "theta": None,
+                     "spec": {"cells": K * C, "n_axes": A, "actor": hidden[0], "critic": hidden[1], "activation": activation,
+                              "seed": int(seed) & (2 ** 64 - 1), "deterministic": bool(deterministic), "first_plant": int(first_plant),
+                              "act_dtype": str(ct["in"].dtype).split(".")[1], "extras": dict(slots)}}
+        self._policy_upload(theta)
+
+    def _policy_upload(self, theta) -> None:
+        pol = self._on("_pol")
+        S = pol["spec"]
+        if theta.numel() != policy.theta_size(S["cells"], S["n_axes"], S["actor"], S["critic"]):
+            raise ValueError("theta has %d elements, the set policy takes %d" % (theta.numel(), policy.theta_size(S["cells"], S["n_axes"], S["actor"], S["critic"])))
+        _lib.check(self.L.npb_policy_load(self._h, ctypes.c_void_p(theta.data_ptr()), 1, self._stream()), self._h)
+        pol["theta"] = theta      # (alive while the launch reads it)
+
+    def policy_load(self, theta_or_modules) -> None:
+        """New parameters into the set policy (npb_policy_load), once per optimiser iteration: a flat float32 ``theta`` in the
+        statement's order (``policy.pack``), device or host, or ``(actor, critic, log_std)`` as ``set_policy`` takes them.  No
+        reallocation, nothing read back; the shapes stay."""
+        self._on("_pol")
+        if isinstance(theta_or_modules, (tuple, list)) and len(theta_or_modules) == 3 and not isinstance(theta_or_modules[0], (int, float)):
+            theta, _, _ = self._policy_theta(*theta_or_modules)
+        else:
+            theta = torch.as_tensor(theta_or_modules).detach().to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        self._policy_upload(theta)
+
+    def policy_outputs(self) -> Dict[str, torch.Tensor]:
+        """``value`` and ``logp``, float32 [n] each, the same storage on every call: what the policy made of the features in front of the
+        last step.  The action is ``controls_input()``."""
+        pol = self._on("_pol")
+        return {"value": pol["value"], "logp": pol["logp"]}
+
+    def policy_theta(self) -> torch.Tensor:
+        """the parameters last loaded, the flat float32 device tensor in the statement's order (what ``policy.Policy.load`` takes)"""
+        return self._on("_pol")["theta"]
+
+    def policy_values(self, x=None) -> torch.Tensor:
+        """The critic alone (npb_policy_values): float32 [rows] of ``x``, a float32 or float64 device tensor [rows, K, C] (or [rows, K * C]);
+        None: the current features -- the ``last_value`` of ``rollout_advantages``; the rollout's ``final_obs`` gives its ``final_values``."""
+        pol = self._on("_pol")
+        if x is None:
+            x = self.features()
+        x = torch.as_tensor(x)
+        if x.dtype not in (torch.float32, torch.float64):
+            raise ValueError("policy_values takes float32 or float64 rows, not %r" % (x.dtype,))
+        x = x.to(device=self.device).contiguous()
+        rows = x.shape[0]
+        if x.numel() != rows * pol["spec"]["cells"]:
+            raise ValueError("policy_values takes rows of %d cells, not %r" % (pol["spec"]["cells"], tuple(x.shape)))
+        with torch.cuda.device(self.device):
+            out = torch.zeros((rows,), dtype=torch.float32, device=self.device)
+        if rows:
+            _lib.check(self.L.npb_policy_values(self._h, ctypes.c_void_p(x.data_ptr()), _lib.FEATURE_DTYPES["float64" if x.dtype == torch.float64 else "float32"],
+                                                rows, ctypes.c_void_p(out.data_ptr()), self._stream()), self._h)
+        pol["held"] = x      # (alive while the launch reads it)
+        return out
+
+    def policy_noise(self, t: int, words: bool = False):
+        """The z of draw ``t`` (npb_policy_noise), float64 [n, n_axes], by the device function the step's launch inlines; ``words``: also
+        the Philox words behind it, int64-held uint32 [n, ceil(n_axes / 2), 4]"""
+        A = self._on("_pol")["spec"]["n_axes"]
+        with torch.cuda.device(self.device):
+            z = torch.zeros((self.n, A), dtype=torch.float64, device=self.device)
+            w = torch.zeros((self.n, (A + 1) // 2, 4), dtype=torch.int32, device=self.device) if words else None
+        _lib.check(self.L.npb_policy_noise(self._h, int(t) & (2 ** 64 - 1), ctypes.c_void_p(z.data_ptr()), self._p(w), self._stream()), self._h)
+        return (z, w.to(torch.int64) & 0xFFFFFFFF) if words else z
+
+    def policy_state(self) -> Dict[str, np.ndarray]:
+        """The policy's own state for a checkpoint (npb_policy_get_state): ``t``, its draw counter"""
+        self._on("_pol")
+        t = ctypes.c_uint64()
+        _lib.check(self.L.npb_policy_get_state(self._h, ctypes.byref(t)), self._h)
+        return {"t": np.uint64(t.value)}
+
+    def load_policy_state(self, state) -> None:
+        """put back what ``policy_state()`` returned (npb_policy_set_state): the noise resumes at that draw"""
+        self._on("_pol")
+        _lib.check(self.L.npb_policy_set_state(self._h, int(state["t"])), self._h)
+
+    def policy_spec(self) -> dict:
+        """the request as data: what ``nuclear_sim_amd.policy.Policy`` takes"""
+        return self._on("_pol")["spec"]
+
+    def collect(self, steps: int) -> dict:
+        """``steps`` steps in one call (npb_collect): with a policy and a rollout set nothing of a step comes from Python, so a whole
+        rollout runs without it -- every buffer as ``steps`` calls of ``step()`` leave it.  Refused by name where a step input comes from
+        the caller: an external heat source, host-side noise or a host-side power profile (episode streams drive both on the device), or a
+        rollout without room.  Returns ``rollout()``."""
+        self._on("_pol")
+        self._on("_roll")
+        if self.heat_source == "external":
+            raise _lib.NpbError("collect() under heat_source='external': the heat source's power comes from the caller every step")
+        if self._streams is None and (self._noise is not None or self.params.hs_noise_enabled):
+            raise _lib.NpbError("collect() with host-side noise: the heat-source noise comes from the caller every step (enable_episode_streams drives it on the device)")
+        if self._streams is None and self._profile is not None:
+            raise _lib.NpbError("collect() with a host-side power profile: its rows come from the caller every step (enable_episode_streams drives it on the device)")
+        self._keep = []
+        self.features()
+        _lib.check(self.L.npb_collect(self._h, int(steps), self._p(self._obs), self._p(self._reward), self._p(self._done), self._p(self._flags),
+                                      self._p(self._info_buf), self._stream()), self._h)
+        if self._feat is not None:
+            self._feat["unprimed"] = False
+        return self.rollout()
 
     def _order_buffers(self):
         """the buffers the perform_*_maintenance methods keep for their order columns, with the ``success`` column they all return"""
@@ -2135,6 +2322,7 @@ class BatchedPlantEnv:
         self._ctl = None
         self._roll = None
         self._norm = None
+        self._pol = None
 
     def __del__(self):
         try:
@@ -2298,6 +2486,10 @@ class BatchedPlantEnv:
              thermal_power_mw=None, power_percent=None, controls=None):
         self._keep = []
         ctl = self._ctl
+        if self._pol is not None:      # the policy reads the features in front of the step and is the one writer of the controls' input
+            if controls is not None:
+                raise _lib.NpbError("step(controls=...) while a policy is set: the policy writes the controls (set_policy(None) first)")
+            self.features()
         if self._roll is not None:      # the rollout records the features in front of the step: every plant has a frame by then
             self.features()
         if controls is not None:      # the policy's output for this step (set_controls): into the bound tensor unless it is that tensor
@@ -2369,6 +2561,8 @@ class BatchedPlantEnv:
                 obs = feat["out"]
         if self._norm is not None and self._norm["norm_reward"] is not None:      # the reward the learner sees (set_normalizer); the one returned stays raw
             info["norm_reward"] = self._norm["norm_reward"]
+        if self._pol is not None:      # what the policy made of the features in front of this step (set_policy)
+            info["value"], info["logp"] = self._pol["value"], self._pol["logp"]
         if task is not None:
             return obs, task["reward"], task["done"], info
         return obs, self._reward, self._done, info
