@@ -1422,8 +1422,7 @@ NPB_API int npb_normalizer_clear(NpbHandle *h, const uint8_t *mask, void *stream
  *   first (npb_features_prime).
  * The kernel (npb_policy.hip) runs on the f32 matrix cores (v_mfma_f32_32x32x2_f32: exact f32, the statement's fmaf chain two k a call; the
  * relu tests hold it to the statement's bits): one workgroup per 32 plants, the activations through LDS, no atomics, no scratch.
- * Not here: a shared trunk; discrete or squashed (tanh-Gaussian) actions; a state-dependent std; recurrent nets; half types; training
- * on the device; noise that restarts with the episode; skipping the forward pass on held steps of interval > 1.
+ * Not here: a shared trunk; discrete or squashed (tanh-Gaussian) actions; a state-dependent std; recurrent nets; half types; noise that restarts with the episode; skipping the forward pass on held steps of interval > 1.
  * NPB_VERSION stays 154: a binding detects the entry points by name.  A handle that never calls this behaves as before in every entry
  * point. */
 #define NPB_POLICY_HIDDEN_MAX 3
@@ -1449,6 +1448,66 @@ NPB_API int npb_policy_noise(NpbHandle *h, uint64_t t, double *z, uint32_t *word
 NPB_API int npb_policy_get_state(NpbHandle *h, uint64_t *t);
 NPB_API int npb_policy_set_state(NpbHandle *h, uint64_t t);
 NPB_API int npb_collect(NpbHandle *h, int steps, double *obs, double *reward, uint8_t *done, uint32_t *trip_flags, double *info, void *stream);
+
+/* Training the set policy on the device: the PPO loss of one minibatch, its gradient through both nets, the gradient's clipping and one
+ * Adam step, with no autograd graph and no optimiser outside the library.  nuclear_sim_amd/ppo.py states all of it in numpy, and that
+ * statement is the contract; the device produces its bits for every count, storage type and launch geometry, with the forward pass's
+ * licensed float tanh and two more licensed differences: the device's double exp for the ratio and for std.
+ * One minibatch (npb_ppo_desc_t) is `count` rows as npb_rollout_minibatch gathers them: obs [count][K * C] (float or double: NPB_FEATURES_F32
+ * / _F64), act [count][A] (NPB_CONTROLS_F32 / _F64), logp_old [count] float, adv and ret [count] of one type (NPB_ROLLOUT_F32 / _F64).
+ * Forward: the step's own layer routine, every hidden activation kept.  Per row, in double, every operation rounded on its own:
+ *   d[a] = ((double)act[a] - (double)mean[a]) / (double)std[a];  lp as the step forms logp, with d for z;  r = exp(lp - (double)logp_old)
+ *   clipped = (adv > 0 and r > 1 + clip) or (adv < 0 and r < 1 - clip), every comparison strict;  c = clipped ? 0.0 : -(adv * r)
+ *   the seeds, narrowed once: dmean[a] = (float)(((c * d[a]) / std[a]) / count), dv = (float)((vf_coef * ((double)v - ret)) / count)
+ *   dls[a] = (c * (d[a] * d[a] - 1.0)) / count;  policy loss -min(r * adv, clamp(r, 1 - clip, 1 + clip) * adv);  value loss 0.5 * (v - ret)^2;
+ *   kl = (r - 1.0) - (lp - logp_old)
+ * A row with a feature, an action, logp_old, adv or ret that is not finite is SKIPPED: its features read as +0.0, every seed and term
+ * of it is +0.0, it is counted, and its logp_new, value_new and ratio are THE quiet NaN; the divisor stays count.
+ * Backward, float, per net from the head down: back[i][k] = the chain over j ascending of fmaf(delta[i][j], W[j][k], acc) from +0.0; relu:
+ * delta' = h > 0 ? back : +0.0; tanh: delta' = back * (1.0f - h * h), three rounded operations.
+ * The sums over rows are pinned: the rows are cut into chains of rows_per_chain rows (a positive multiple of 32); within a chain dW[j][k]
+ * = fmaf(delta[i][j], h[i][k], acc) for i ascending from +0.0 (db: h = 1.0f); across chains the partials are widened, added in ascending
+ * chain order onto 0.0 and narrowed once; the per-row doubles likewise.  grad(log_std[a]) = (float)(sum dls[a] - ent_coef), grad(std[a])
+ * = 0.  Then norm = sqrt(the pinned tree of npb_rollout_moments over (double)g * (double)g) over every entry but std's, and with
+ * max_grad_norm > 0 (0 = off) g = (float)((double)g * min(1.0, max_grad_norm / (norm + 1e-6))).
+ * stats, NPB_PPO_STATS doubles: policy_loss, value_loss, entropy, approx_kl, clip_fraction (means over count), skipped, grad_norm, count.
+ * Adam: the state is m, v (float, theta's layout) and step.  npb_policy_adam advances step and forms step_size = lr / (1 - b1^step)
+ * and root = sqrt(1 - b2^step) on the host; per element in double, each result narrowed once: m' = b1 * m + (1 - b1) * g, v' = b2 * v +
+ * (1 - b2) * (g * g), theta' = theta - step_size * (m' / (sqrt(v') / root + eps)); std's slots are skipped and then std[a] =
+ * (float)exp((double)log_std'[a]); the launch that lays the weights out as the step reads them follows, so the next step runs the new policy.
+ * npb_ppo_check(desc, features_cells, n_axes): the host-only validator, NULL = accepted, else the reason: a NULL descriptor; a NULL obs,
+ * act, logp_old, adv or ret; an unknown type; count < 1; rows_per_chain not a positive multiple of 32; clip outside (0, 1); a vf_coef,
+ * ent_coef or max_grad_norm that is not finite, or max_grad_norm < 0; max_blocks < 0; a tensor misaligned for its element.
+ * npb_policy_grad(h, desc, stream): leaves grad [theta_count] and stats on the handle; the optional outputs logp_new, value_new (float)
+ * and ratio (double), [count] each, may be NULL.  npb_policy_adam(h, lr, b1, b2, eps, stream): one step from the gradient on the handle.
+ * npb_policy_update: both.  npb_policy_get_grad / _get_stats / _get_theta copy into DEVICE buffers (float [theta_count], double
+ * [NPB_PPO_STATS], float [theta_count]) on the stream, nothing read back.  npb_policy_optimizer_get_state / _set_state carry m, v (HOST
+ * float [theta_count]) and step.  The optimiser's buffers and the chains' workspace belong to the policy: allocated on first use, grown on
+ * demand, dropped with it.  NPB_EINVAL by name before any device work: no policy set, and what npb_ppo_check refuses.
+ * The gradient kernel (npb_ppo.hip) runs on the f32 matrix cores (v_mfma_f32_32x32x2_f32), a workgroup a chain, no atomics.
+ * Not here: value-loss clipping, a shared trunk, learning-rate schedules and target_kl early stopping (the caller reads stats), half
+ * types, gradient exchange between devices. */
+#define NPB_PPO_STATS 8
+typedef struct npb_ppo_desc_t {
+  const void *obs; int obs_type;             /* device [count][K * C]; NPB_FEATURES_F32 | NPB_FEATURES_F64 */
+  const void *act; int act_type;             /* device [count][A]; NPB_CONTROLS_F32 | NPB_CONTROLS_F64 */
+  const float *logp_old;                     /* device [count] */
+  const void *adv, *ret; int adv_type;       /* device [count] each; NPB_ROLLOUT_F32 | NPB_ROLLOUT_F64, both */
+  int count;
+  float *logp_new, *value_new; double *ratio;      /* device [count] each, or NULL */
+  double clip, vf_coef, ent_coef, max_grad_norm;   /* max_grad_norm 0 = off */
+  int rows_per_chain;                        /* a positive multiple of 32: the statement's chains */
+  int max_blocks;                            /* workgroups the gradient kernel launches at most, 0 = the library's choice; no bit depends on it */
+} npb_ppo_desc_t;
+NPB_API const char *npb_ppo_check(const npb_ppo_desc_t *desc, int features_cells, int n_axes);
+NPB_API int npb_policy_grad(NpbHandle *h, const npb_ppo_desc_t *desc, void *stream);
+NPB_API int npb_policy_adam(NpbHandle *h, double lr, double b1, double b2, double eps, void *stream);
+NPB_API int npb_policy_update(NpbHandle *h, const npb_ppo_desc_t *desc, double lr, double b1, double b2, double eps, void *stream);
+NPB_API int npb_policy_get_grad(NpbHandle *h, float *grad, void *stream);
+NPB_API int npb_policy_get_stats(NpbHandle *h, double *stats, void *stream);
+NPB_API int npb_policy_get_theta(NpbHandle *h, float *theta, void *stream);
+NPB_API int npb_policy_optimizer_get_state(NpbHandle *h, float *m, float *v, uint64_t *step, void *stream);
+NPB_API int npb_policy_optimizer_set_state(NpbHandle *h, const float *m, const float *v, uint64_t step, void *stream);
 
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the

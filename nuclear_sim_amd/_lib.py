@@ -943,6 +943,20 @@ class NpbPolicyDesc(ctypes.Structure):
                 ("extras_in", ctypes.c_void_p), ("n_extras", ctypes.c_int), ("value_slot", ctypes.c_int), ("logp_slot", ctypes.c_int)]
 
 
+# include/npb.h npb_ppo_desc_t: one minibatch and the hyper-parameters of the policy's training step (npb_policy_grad, npb_policy_update)
+PPO_STATS = 8                                                          # NPB_PPO_STATS (ppo.STATS)
+
+
+class NpbPpoDesc(ctypes.Structure):
+    """npb_ppo_desc_t: the five input tensors with their types, the row count, the three optional per-row outputs, the hyper-parameters,
+    the statement's rows_per_chain and the launch's max_blocks"""
+    _fields_ = [("obs", ctypes.c_void_p), ("obs_type", ctypes.c_int), ("act", ctypes.c_void_p), ("act_type", ctypes.c_int),
+                ("logp_old", ctypes.c_void_p), ("adv", ctypes.c_void_p), ("ret", ctypes.c_void_p), ("adv_type", ctypes.c_int),
+                ("count", ctypes.c_int), ("logp_new", ctypes.c_void_p), ("value_new", ctypes.c_void_p), ("ratio", ctypes.c_void_p),
+                ("clip", ctypes.c_double), ("vf_coef", ctypes.c_double), ("ent_coef", ctypes.c_double), ("max_grad_norm", ctypes.c_double),
+                ("rows_per_chain", ctypes.c_int), ("max_blocks", ctypes.c_int)]
+
+
 def controls_request(axes, interval: int = 1, dtype="float32", heat_source: int = 0) -> dict:
     """What ``BatchedPlantEnv.set_controls`` asks of npb_set_controls, from the caller's words; a pure function, host only, so an axis that
     cannot work is refused (ValueError, naming it) before any device work.
@@ -1257,6 +1271,18 @@ def load():
         L.npb_policy_get_state.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
         L.npb_policy_set_state.argtypes = [vp, ctypes.c_uint64]
         L.npb_collect.argtypes = [vp, ci] + [vp] * 6
+    if hasattr(L, "npb_policy_grad"):     # training the policy: the PPO loss, its gradient and the Adam step
+        cd = ctypes.c_double
+        L.npb_ppo_check.argtypes = [ctypes.POINTER(NpbPpoDesc), ci, ci]
+        L.npb_ppo_check.restype = ctypes.c_char_p
+        L.npb_policy_grad.argtypes = [vp, ctypes.POINTER(NpbPpoDesc), vp]
+        L.npb_policy_adam.argtypes = [vp, cd, cd, cd, cd, vp]
+        L.npb_policy_update.argtypes = [vp, ctypes.POINTER(NpbPpoDesc), cd, cd, cd, cd, vp]
+        L.npb_policy_get_grad.argtypes = [vp, vp, vp]
+        L.npb_policy_get_stats.argtypes = [vp, vp, vp]
+        L.npb_policy_get_theta.argtypes = [vp, vp, vp]
+        L.npb_policy_optimizer_get_state.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_uint64), vp]
+        L.npb_policy_optimizer_set_state.argtypes = [vp, vp, vp, ctypes.c_uint64, vp]
     if hasattr(L, "npb_rollout_minibatch"):     # pinned moments, the keyed permutation and the minibatch gather over a rollout
         L.npb_rollout_moments.argtypes = [vp, ctypes.POINTER(NpbMomentsDesc), vp]
         L.npb_rollout_permutation.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64, ctypes.c_int64, vp, vp]

@@ -13,6 +13,7 @@
 #include "npb_noise.h"
 #include "npb_minibatch.h"
 #include "npb_policy.h"
+#include "npb_ppo.h"
 
 /* a side block's rows as recorded with a snapshot or a bank: a packed [rows][pitch] copy beside that arena, or NULL; its allocation */
 struct SideCopy { double *rows; size_t pitch, doubles; };
@@ -102,6 +103,9 @@ struct NpbHandle {
   /* npb_set_policy: the shapes, the parameters on the device as the caller packed them and as the kernel reads them (base pol.theta), the
    * caller's descriptor, and the draw counter t */
   npb_policy_t pol; uint64_t pol_t;
+  /* npb_policy_grad / npb_policy_adam: the gradient, the statistics, the optimiser's m, v and step (base ppo.stats) and the chains'
+   * workspace (base ppo.chain_stats), allocated on first use, dropped with the policy */
+  npb_ppo_t ppo;
   double *ramp_prev;   /* npb_profile_ramp: the previous setpoint of every plant ([pitch], NaN = none yet), allocated on first use */
   int *plan_dev;       /* npb_gather_fields: {column, sub, kind} per requested field, and the request it was built for */
   std::vector<int> plan_key;
@@ -169,6 +173,11 @@ static const char *const g_no_controls = ": no controls set (npb_set_controls fi
 static const char *const g_no_rollout = ": no rollout set (npb_set_rollout first)";
 static const char *const g_no_normalizer = ": no normaliser set (npb_set_normalizer first)";
 /* npb_set_features / npb_set_controls while a rollout is set, set and NULL alike: its pre kernel copies their tensors, in the shapes it was bound with */
+/* the policy's training buffers go with the policy */
+static void ppo_drop(NpbHandle *h) {
+  if (h->ppo.chain_stats) (void)hipFree(h->ppo.chain_stats);
+  attachment_drop(&h->ppo, h->ppo.stats);
+}
 static const char *const g_no_policy = ": no policy set (npb_set_policy first)";
 /* npb_set_features / npb_set_controls / npb_set_rollout while a policy is set, set and NULL alike: it reads and writes their tensors */
 static const char *const g_policy_holds = ": a policy is set (npb_set_policy) and reads or writes this attachment's tensors every step; npb_set_policy(h, NULL) first";
@@ -607,6 +616,7 @@ int npb_destroy(NpbHandle *h) {
   attachment_drop(&h->cs, h->cs.cols); attachment_drop(&h->ew, h->ew.cols); attachment_drop(&h->task, h->task.terms);
   attachment_drop(&h->feat, h->feat.cols); attachment_drop(&h->ctl, h->ctl.age); attachment_drop(&h->ro, h->ro.n_final);
   attachment_drop(&h->mom, h->mom.ws); attachment_drop(&h->norm, h->norm.streams);
+  ppo_drop(h);
   attachment_drop(&h->pol, h->pol.theta);
   for (Sampler *sm : h->samplers) if (sm) { (void)hipFree(sm->dev); delete sm; }
   delete h;
@@ -2316,7 +2326,7 @@ int npb_set_policy(NpbHandle *h, const npb_policy_desc_t *desc) {
   if (desc && desc->extras_in && (!h->ro.n_final || desc->extras_in != h->ro.D.extras_in || desc->n_extras != h->ro.D.n_extras))
     return fail(h, NPB_EINVAL, "npb_set_policy: extras_in and its count must be the set rollout's (npb_set_rollout first)");
   NPB_USE_DEVICE(h);
-  if (!desc) { attachment_drop(&h->pol, h->pol.theta); h->pol_t = 0; return NPB_OK; }
+  if (!desc) { ppo_drop(h); attachment_drop(&h->pol, h->pol.theta); h->pol_t = 0; return NPB_OK; }
   npb_policy_t P = {};
   npb_policy_layout(desc, h->feat.n_cols * h->feat.stack, h->ctl.n_axes, &P);
   /* the allocation: theta [theta_count, padded to 4 floats] | the kernel's copy of the weights [padded_count]; all zero */
@@ -2324,6 +2334,7 @@ int npb_set_policy(NpbHandle *h, const npb_policy_desc_t *desc) {
   char *dev = nullptr;
   if (int rc = attachment_alloc(h, "npb_set_policy", "the parameters", nullptr, 0, bytes, &dev)) return rc;
   P.theta = (float *)dev; P.padded = P.theta + theta_floats;
+  ppo_drop(h);
   attachment_drop(&h->pol, h->pol.theta);
   h->pol = P; h->pol_t = 0;
   return NPB_OK;
@@ -2392,6 +2403,132 @@ int npb_collect(NpbHandle *h, int steps, double *obs, double *reward, uint8_t *d
     return fail(h, NPB_EINVAL, "npb_collect: a power profile is seeded (npb_profile_seed) and its rows come from the caller every step: npb_step, or episode streams (npb_set_episode_streams)");
   for (int s = 0; s < steps; s++)
     if (int rc = npb_step(h, nullptr, nullptr, nullptr, nullptr, nullptr, obs, reward, done, trip_flags, info, stream)) return rc;
+  return NPB_OK;
+}
+
+/* ---- training the policy (include/npb.h, npb_ppo.hip) */
+const char *npb_ppo_check(const npb_ppo_desc_t *D, int features_cells, int n_axes) {
+  if (!D) return "npb_policy_grad: a NULL descriptor";
+  if (features_cells < 1 || features_cells > NPB_FEATURES_CELLS_MAX) return "npb_policy_grad: the features' stack must have 1 .. NPB_FEATURES_CELLS_MAX (256) cells";
+  if (n_axes < 1 || n_axes > NPB_CONTROLS_AXES_MAX) return "npb_policy_grad: the axis count must be 1 .. NPB_CONTROLS_AXES_MAX (8)";
+  if (!D->obs) return "npb_policy_grad: obs is NULL";
+  if (!D->act) return "npb_policy_grad: act is NULL";
+  if (!D->logp_old) return "npb_policy_grad: logp_old is NULL";
+  if (!D->adv) return "npb_policy_grad: adv is NULL";
+  if (!D->ret) return "npb_policy_grad: ret is NULL";
+  if (D->obs_type != NPB_FEATURES_F32 && D->obs_type != NPB_FEATURES_F64) return "npb_policy_grad: an unknown obs type";
+  if (D->act_type != NPB_CONTROLS_F32 && D->act_type != NPB_CONTROLS_F64) return "npb_policy_grad: an unknown act type";
+  if (D->adv_type != NPB_ROLLOUT_F32 && D->adv_type != NPB_ROLLOUT_F64) return "npb_policy_grad: an unknown adv type";
+  if (D->count < 1) return "npb_policy_grad: count must be >= 1";
+  if (D->rows_per_chain < 32 || D->rows_per_chain % 32) return "npb_policy_grad: rows_per_chain must be a positive multiple of 32";
+  if (!(D->clip > 0.0 && D->clip < 1.0)) return "npb_policy_grad: clip must lie inside (0, 1)";
+  if (!(D->vf_coef - D->vf_coef == 0.0) || !(D->ent_coef - D->ent_coef == 0.0)) return "npb_policy_grad: vf_coef and ent_coef must be finite";
+  if (!(D->max_grad_norm >= 0.0) || !(D->max_grad_norm - D->max_grad_norm == 0.0)) return "npb_policy_grad: max_grad_norm must be finite and >= 0 (0 = off)";
+  if (D->max_blocks < 0) return "npb_policy_grad: max_blocks must be >= 0";
+  if (((uintptr_t)D->obs & (D->obs_type == NPB_FEATURES_F64 ? 7u : 3u)) || ((uintptr_t)D->act & (D->act_type == NPB_CONTROLS_F64 ? 7u : 3u)) ||
+      (((uintptr_t)D->adv | (uintptr_t)D->ret) & (D->adv_type == NPB_ROLLOUT_F64 ? 7u : 3u)) || ((uintptr_t)D->logp_old & 3u))
+    return "npb_policy_grad: a misaligned obs, act, logp_old, adv or ret: aligned to their element";
+  if ((((uintptr_t)D->logp_new | (uintptr_t)D->value_new) & 3u) || ((uintptr_t)D->ratio & 7u))
+    return "npb_policy_grad: a misaligned logp_new, value_new (4-byte aligned) or ratio (8-byte aligned)";
+  return nullptr;
+}
+/* the training buffers on first use, and the chains' workspace grown to `chains` */
+static int ppo_room(NpbHandle *h, const char *who, size_t chains) {
+  npb_ppo_t &O = h->ppo;
+  if (!O.stats) {
+    const size_t floats = ((size_t)h->pol.theta_count + 3) & ~(size_t)3, tree = npb_moments_workspace((int64_t)h->pol.std);
+    char *dev = nullptr;
+    if (int rc = attachment_alloc(h, who, "the gradient and the optimiser's state", nullptr, 0, (NPB_PPO_STATS + tree) * sizeof(double) + 3 * floats * sizeof(float), &dev)) return rc;
+    O.stats = (double *)dev; O.tree = O.stats + NPB_PPO_STATS; O.tree_count = tree;
+    O.grad = (float *)(O.tree + tree); O.m = O.grad + floats; O.v = O.m + floats; O.floats = floats; O.step = 0;
+  }
+  if (chains > O.chains) {      /* (hipFree of the old one waits for a launch that still reads it) */
+    char *dev = nullptr;
+    if (int rc = attachment_alloc(h, who, "the chains' workspace", nullptr, 0, chains * (NPD_PPO_ROWVALS * sizeof(double) + O.floats * sizeof(float)), &dev)) return rc;
+    if (O.chain_stats) (void)hipFree(O.chain_stats);
+    O.chain_stats = (double *)dev; O.partials = (float *)(O.chain_stats + chains * NPD_PPO_ROWVALS); O.chains = chains;
+  }
+  return NPB_OK;
+}
+static int ppo_grad(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, void *stream) {
+  if (!h->pol.theta) return fail_who(h, who, g_no_policy);
+  if (const char *why = npb_ppo_check(D, h->pol.cells, h->pol.n_axes)) return fail(h, NPB_EINVAL, why);
+  NPB_USE_DEVICE(h);
+  if (int rc = ppo_room(h, who, ((size_t)D->count + D->rows_per_chain - 1) / D->rows_per_chain)) return rc;
+  npb_launch_ppo_grad(&h->pol, &h->ppo, D, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+static int ppo_adam(NpbHandle *h, const char *who, double lr, double b1, double b2, double eps, void *stream) {
+  if (!h->pol.theta) return fail_who(h, who, g_no_policy);
+  if (!(lr - lr == 0.0) || !(b1 >= 0.0 && b1 < 1.0) || !(b2 >= 0.0 && b2 < 1.0) || !(eps >= 0.0) || !(eps - eps == 0.0))
+    return fail_who(h, who, ": lr must be finite, b1 and b2 lie in [0, 1), eps be finite and >= 0");
+  if (!h->ppo.stats) return fail_who(h, who, ": no gradient formed yet (npb_policy_grad first)");
+  NPB_USE_DEVICE(h);
+  h->ppo.step++;
+  npb_launch_ppo_adam(&h->pol, &h->ppo, lr, b1, b2, eps, (hipStream_t)stream);
+  npb_launch_policy_repack(&h->pol, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_policy_grad(NpbHandle *h, const npb_ppo_desc_t *D, void *stream) {
+  if (!h) return NPB_EINVAL;
+  return ppo_grad(h, "npb_policy_grad", D, stream);
+}
+int npb_policy_adam(NpbHandle *h, double lr, double b1, double b2, double eps, void *stream) {
+  if (!h) return NPB_EINVAL;
+  return ppo_adam(h, "npb_policy_adam", lr, b1, b2, eps, stream);
+}
+int npb_policy_update(NpbHandle *h, const npb_ppo_desc_t *D, double lr, double b1, double b2, double eps, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (int rc = ppo_grad(h, "npb_policy_update", D, stream)) return rc;
+  return ppo_adam(h, "npb_policy_update", lr, b1, b2, eps, stream);
+}
+/* a copy between device buffers on the stream */
+static int ppo_copy_out(NpbHandle *h, const char *who, const void *src, void *dst, size_t bytes, size_t align, bool needs_grad, void *stream) {
+  if (!h->pol.theta) return fail_who(h, who, g_no_policy);
+  if (!dst || ((uintptr_t)dst & (align - 1))) return fail_who(h, who, ": a NULL or misaligned output");
+  if (needs_grad && !h->ppo.stats) return fail_who(h, who, ": no gradient formed yet (npb_policy_grad first)");
+  NPB_USE_DEVICE(h);
+  NPB_HIP(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return NPB_OK;
+}
+int npb_policy_get_grad(NpbHandle *h, float *grad, void *stream) {
+  if (!h) return NPB_EINVAL;
+  return ppo_copy_out(h, "npb_policy_get_grad", h->ppo.grad, grad, (size_t)h->pol.theta_count * sizeof(float), 4, true, stream);
+}
+int npb_policy_get_stats(NpbHandle *h, double *stats, void *stream) {
+  if (!h) return NPB_EINVAL;
+  return ppo_copy_out(h, "npb_policy_get_stats", h->ppo.stats, stats, NPB_PPO_STATS * sizeof(double), 8, true, stream);
+}
+int npb_policy_get_theta(NpbHandle *h, float *theta, void *stream) {
+  if (!h) return NPB_EINVAL;
+  return ppo_copy_out(h, "npb_policy_get_theta", h->pol.theta, theta, (size_t)h->pol.theta_count * sizeof(float), 4, false, stream);
+}
+int npb_policy_optimizer_get_state(NpbHandle *h, float *m, float *v, uint64_t *step, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->pol.theta) return fail_who(h, "npb_policy_optimizer_get_state", g_no_policy);
+  if (!m || !v || !step) return fail(h, NPB_EINVAL, "npb_policy_optimizer_get_state: NULL output");
+  NPB_USE_DEVICE(h);
+  if (int rc = ppo_room(h, "npb_policy_optimizer_get_state", 0)) return rc;
+  const size_t bytes = (size_t)h->pol.theta_count * sizeof(float);
+  NPB_HIP(h, hipMemcpyAsync(m, h->ppo.m, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  NPB_HIP(h, hipMemcpyAsync(v, h->ppo.v, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
+  *step = h->ppo.step;
+  return NPB_OK;
+}
+int npb_policy_optimizer_set_state(NpbHandle *h, const float *m, const float *v, uint64_t step, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->pol.theta) return fail_who(h, "npb_policy_optimizer_set_state", g_no_policy);
+  if (!m || !v) return fail(h, NPB_EINVAL, "npb_policy_optimizer_set_state: NULL input");
+  NPB_USE_DEVICE(h);
+  if (int rc = ppo_room(h, "npb_policy_optimizer_set_state", 0)) return rc;
+  const size_t bytes = (size_t)h->pol.theta_count * sizeof(float);
+  NPB_HIP(h, hipMemcpyAsync(h->ppo.m, m, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+  NPB_HIP(h, hipMemcpyAsync(h->ppo.v, v, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+  NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));      /* the host arrays may go */
+  h->ppo.step = step;
   return NPB_OK;
 }
 

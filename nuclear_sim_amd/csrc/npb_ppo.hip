@@ -1,0 +1,321 @@
+/* npb_ppo.hip -- training the policy on the device (npb_policy_grad, npb_policy_adam, include/npb.h): the clipped surrogate loss of one
+ * minibatch, its gradient through both MLPs, the gradient's clipping and one Adam step.  nuclear_sim_amd/ppo.py states it in numpy; this
+ * file produces its bits for a relu net fed the device's own ratio (the float tanh, and the double exp of the ratio and of std, are the
+ * statement's licensed differences).  Built with the noise generator's flags (Makefile): no contraction, IEEE division and square root.
+ *
+ * THE GRADIENT KERNEL: one workgroup of 256 lanes (four waves) runs one CHAIN of rows_per_chain rows, tile of 32 rows after tile, and a
+ * launch's workgroups stride over the chains; a chain's sums are the same whichever workgroup runs it and whenever.  Per tile:
+ *   1. the tile's rows of obs into LDS as the step's launch lays them, xs[k][row] with a row stride of 33; a row beyond count, and a
+ *      skipped row (a feature, an action, logp_old, adv or ret that is not finite), reads as +0.0 everywhere.
+ *   2. the actor forward by the step's own layer routine (npd_policy_layer, npb_policy.h), every hidden activation kept in LDS, h[l][k][row].
+ *   3. the per-row epilogue in double, a lane a row: the head's seeds dmean[a][row] as floats into LDS, the per-row doubles (dls, the
+ *      losses' terms) into LDS, logp_new and ratio out.
+ *   4. the actor backward, from the head down.  dW (npd_ppo_dw): v_mfma_f32_32x32x2_f32 with the output index j as the row of D, the input
+ *      index k as its column and the tile's ROWS as the k dimension, two rows a call in ascending order: the statement's chain.  A wave
+ *      takes blocks of 32 x 32 of a layer's W; the accumulator of a block is the chain's own row of the partials workspace, in theta's
+ *      layout: loaded as the C operand (+0.0 in the chain's first tile), sixteen calls, stored with plain vector stores -- a lane holds one
+ *      k of 16 j, so a half-wave stores 128 contiguous bytes.  db: a lane an output, the 32 rows added in order.  back (npd_ppo_back): the
+ *      row as the row of D, k as its column, j as the k dimension; theta's own row-major W[j][k] IS the B operand, consecutive lanes on
+ *      consecutive k; then the activation's derivative from h, and delta'[k][row] into the other of two LDS buffers.
+ *   5. the critic the same way, its hidden activations over the actor's: forward, the value's seed and loss, backward.
+ *   6. the per-row doubles of the tile added in row order onto the chain's running sums, a lane a quantity.
+ * No atomics, nothing depends on the launch order, no scratch.  LDS: the small build (K*C <= 64, widths <= 64) 6 x 8.25 KiB and 6 KiB; the
+ * large one 33 + 5 x 16.5 KiB and the same, 122 KiB of gfx950's 160.
+ * THE REDUCE KERNEL: a lane a parameter: its partials widened and added in ascending chain order, narrowed once; log_std's from the dls
+ * sums; then the first level of the pinned tree over the squares.  THE FINISH KERNEL, one workgroup: the tree's further levels, the norm,
+ * the scale, the statistics.  THE ADAM KERNEL: a lane a parameter, and log_std's lane refreshes std. */
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include "npb_ppo.h"
+#include "npb_minibatch.h"
+
+typedef struct {
+  npb_ppo_desc_t D;
+  int n_chains;
+  float *partials; size_t floats;      /* [n_chains][floats] */
+  double *chain_stats;                 /* [n_chains][NPD_PPO_ROWVALS] */
+} npd_ppo_run_t;
+
+__device__ __forceinline__ double npd_ppo_load(const void *x, int f64, size_t i) { return f64 ? ((const double *)x)[i] : (double)((const float *)x)[i]; }
+
+/* a layer's dW and db of this tile onto the chain's partials: delta[j][row], hin[k][row] (row stride NPD_POLICY_STRIDE both).  Lane l gives
+ * A[j = l & 31][row = l >> 5] and B[row = l >> 5][k = l & 31] and holds D[j = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5)][k = l & 31].  A block's
+ * cells beyond the layer's out or in read whatever LDS holds there and are neither loaded nor stored: D[j][k] depends on row j of A and
+ * column k of B alone */
+__device__ __forceinline__ void npd_ppo_dw(const npd_policy_layer_t &L, float *__restrict__ prow, bool first, const float *delta, const float *hin, int tid) {
+  const int wave = tid >> 6, lane = tid & 63, col = lane & 31, half = lane >> 5;
+  const int kb = (L.in + 31) >> 5, blocks = (L.out_pad >> 5) * kb;
+  for (int b = wave; b < blocks; b += NPD_POLICY_WAVES) {
+    const int j0 = 32 * (b / kb), k0 = 32 * (b % kb), k = k0 + col;
+    npd_f32x16 acc;
+#pragma unroll
+    for (int reg = 0; reg < 16; reg++) {
+      const int j = j0 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+      acc[reg] = !first && j < L.out && k < L.in ? prow[L.w + (size_t)j * L.in + k] : 0.0f;
+    }
+    const float *a = delta + (j0 + col) * NPD_POLICY_STRIDE + half;
+    const float *h = hin + k * NPD_POLICY_STRIDE + half;
+#pragma unroll
+    for (int s = 0; s < NPD_POLICY_TILE / 2; s++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2 * s], h[2 * s], acc, 0, 0, 0);
+#pragma unroll
+    for (int reg = 0; reg < 16; reg++) {
+      const int j = j0 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+      if (j < L.out && k < L.in) prow[L.w + (size_t)j * L.in + k] = acc[reg];
+    }
+  }
+  if (tid < L.out) {
+    float acc = first ? 0.0f : prow[L.b + tid];
+    const float *d = delta + tid * NPD_POLICY_STRIDE;
+#pragma unroll
+    for (int r = 0; r < NPD_POLICY_TILE; r++) acc = acc + d[r];      /* fmaf(delta, 1.0f, acc) */
+    prow[L.b + tid] = acc;
+  }
+}
+
+/* delta'[k][row] of the layer below: back[row][k] = the chain over j of fmaf(delta[row][j], W[j][k], acc) from +0.0, two j a call, j up
+ * to the next multiple of 4 of the width (the producer of delta wrote +0.0 there; W reads as +0.0 there), then the derivative of the
+ * activation that made h[k][row].  Lane l gives A[row = l & 31][j = l >> 5] and B[j = l >> 5][k = l & 31] = theta's W[j][k] and holds
+ * D[row = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5)][k = l & 31].  k up to the next multiple of 4 of the layer's in is written +0.0: the k
+ * extension of the back below */
+__device__ __forceinline__ void npd_ppo_back(const npd_policy_layer_t &L, const float *__restrict__ theta, const float *delta, float *out, const float *h,
+                                             int activation, int tid) {
+  const int wave = tid >> 6, lane = tid & 63, col = lane & 31, half = lane >> 5, pairs = ((L.out + 3) & ~3) >> 1;
+  for (int k0 = 32 * wave; k0 < L.in; k0 += 32 * NPD_POLICY_WAVES) {
+    const int k = k0 + col;
+    npd_f32x16 acc;
+#pragma unroll
+    for (int reg = 0; reg < 16; reg++) acc[reg] = 0.0f;
+    const float *a = delta + half * NPD_POLICY_STRIDE + col;
+    for (int s = 0; s < pairs; s++) {
+      const int j = 2 * s + half;
+      const float w = j < L.out && k < L.in ? theta[L.w + (size_t)j * L.in + k] : 0.0f;
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2 * s * NPD_POLICY_STRIDE], w, acc, 0, 0, 0);
+    }
+    if (k < L.in_pad) {
+#pragma unroll
+      for (int reg = 0; reg < 16; reg++) {
+        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * half;
+        const float hv = h[k * NPD_POLICY_STRIDE + row];
+        float y = acc[reg];
+        if (activation == NPB_POLICY_RELU) y = hv > 0.0f ? y : 0.0f;
+        else { const float sq = hv * hv; const float slope = 1.0f - sq; y = y * slope; }
+        out[k * NPD_POLICY_STRIDE + row] = k < L.in ? y : 0.0f;
+      }
+    }
+  }
+}
+
+/* one net of the tile: forward with every hidden activation kept (hid[l]), then `seeds` (a lane a row; it writes the head's delta into d0
+ * and ends with the barrier that publishes it), then backward onto the chain's partials */
+template <int H_MAX, class Seeds>
+__device__ __forceinline__ void npd_ppo_net(const npd_policy_net_t &N, const npb_policy_t &P, const float *xs, float (*hid)[H_MAX * NPD_POLICY_STRIDE], float *head,
+                                            float *d0, float *d1, float *prow, bool first, int tid, Seeds seeds) {
+  const int wave = tid >> 6, lane = tid & 63, last = N.n_layers - 1;
+  for (int l = 0; l <= last; l++) {
+    npd_policy_layer(N.layer[l], P.theta, P.padded, l ? hid[l - 1] : xs, l == last ? head : hid[l], l == last ? -1 : P.D.activation, wave, lane);
+    __syncthreads();
+  }
+  seeds();
+  __syncthreads();
+  for (int l = last; l >= 0; l--) {
+    const npd_policy_layer_t &L = N.layer[l];
+    npd_ppo_dw(L, prow, first, d0, l ? hid[l - 1] : xs, tid);
+    if (l) npd_ppo_back(L, P.theta, d0, d1, hid[l - 1], P.D.activation, tid);
+    __syncthreads();
+    float *t = d0; d0 = d1; d1 = t;
+  }
+}
+
+template <int KC_MAX, int H_MAX>
+__global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_grad_kernel(npb_policy_t P, npd_ppo_run_t R) {
+  __shared__ float xs[KC_MAX * NPD_POLICY_STRIDE];
+  __shared__ float hid[NPB_POLICY_HIDDEN_MAX][H_MAX * NPD_POLICY_STRIDE];
+  __shared__ float da[H_MAX * NPD_POLICY_STRIDE], db[H_MAX * NPD_POLICY_STRIDE];
+  __shared__ float head[NPB_CONTROLS_AXES_MAX * NPD_POLICY_STRIDE];
+  __shared__ double rowv[NPD_PPO_ROWVALS * NPD_POLICY_TILE];
+  __shared__ int bad[NPD_POLICY_TILE];
+  const npb_ppo_desc_t &D = R.D;
+  const int tid = threadIdx.x, A = P.n_axes, KC = P.cells, KC_pad = (KC + 3) & ~3;
+  const size_t count = (size_t)D.count, rpc = (size_t)D.rows_per_chain;
+  const double n = (double)D.count, qnan = (double)__builtin_nanf("");
+  for (size_t chain = blockIdx.x; chain < (size_t)R.n_chains; chain += gridDim.x) {
+    float *prow = R.partials + chain * R.floats;
+    double running = 0.0;      /* lane q < NPD_PPO_ROWVALS: the chain's sum of per-row double q */
+    for (size_t base = chain * rpc; base < (chain + 1) * rpc && base < count; base += NPD_POLICY_TILE) {
+      const bool first = base == chain * rpc;
+      const int in_tile = count - base < (size_t)NPD_POLICY_TILE ? (int)(count - base) : NPD_POLICY_TILE;
+      /* 1. the rows: +0.0 everywhere, then the tile's run of obs, then the skipped rows back to +0.0 */
+      __syncthreads();      /* (the tile before is done with every buffer) */
+      for (int i = tid; i < KC_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES) xs[(i >> 5) * NPD_POLICY_STRIDE + (i & 31)] = 0.0f;
+      for (int i = tid; i < NPD_PPO_ROWVALS * NPD_POLICY_TILE; i += NPD_POLICY_LANES) rowv[i] = 0.0;
+      if (tid < NPD_POLICY_TILE) {
+        int b = 0;
+        if (tid < in_tile) {
+          const size_t p = base + tid;
+          const double old = (double)D.logp_old[p], adv = npd_ppo_load(D.adv, D.adv_type, p), ret = npd_ppo_load(D.ret, D.adv_type, p);
+          b = !(old - old == 0.0) || !(adv - adv == 0.0) || !(ret - ret == 0.0);
+          for (int a = 0; a < A; a++) { const double x = npd_ppo_load(D.act, D.act_type, p * A + a); b |= !(x - x == 0.0); }
+        }
+        bad[tid] = b;
+      }
+      __syncthreads();
+      const int total = in_tile * KC;
+      for (int e = tid; e < total; e += NPD_POLICY_LANES) {
+        const int row = e / KC, k = e - row * KC;
+        const float v = D.obs_type ? (float)((const double *)D.obs)[base * KC + e] : ((const float *)D.obs)[base * KC + e];
+        xs[k * NPD_POLICY_STRIDE + row] = v;
+        if (!(v - v == 0.0f)) bad[row] = 1;
+      }
+      __syncthreads();
+      for (int i = tid; i < KC * NPD_POLICY_TILE; i += NPD_POLICY_LANES)
+        if (bad[i & 31]) xs[(i >> 5) * NPD_POLICY_STRIDE + (i & 31)] = 0.0f;
+      __syncthreads();
+      const bool live = tid < in_tile, skipped = tid < NPD_POLICY_TILE && bad[tid & 31] != 0;
+      const size_t p = base + tid;
+      /* 2 .. 4. the actor */
+      npd_ppo_net<H_MAX>(P.actor, P, xs, hid, head, da, db, prow, first, tid, [&]() {
+        const int A4 = (A + 3) & ~3;
+        if (tid >= NPD_POLICY_TILE) return;
+        for (int a = 0; a < A4; a++) da[a * NPD_POLICY_STRIDE + tid] = 0.0f;
+        if (!live) return;
+        if (skipped) {
+          rowv[NPD_PPO_SKIPPED * NPD_POLICY_TILE + tid] = 1.0;
+          if (D.logp_new) D.logp_new[p] = (float)qnan;
+          if (D.ratio) D.ratio[p] = qnan;
+          return;
+        }
+        double d[NPB_CONTROLS_AXES_MAX];
+        double lp = -((double)A * 0.9189385332046727);
+        for (int a = 0; a < A; a++) {
+          const double diff = npd_ppo_load(D.act, D.act_type, p * A + a) - (double)head[a * NPD_POLICY_STRIDE + tid];
+          d[a] = diff / (double)P.theta[P.std + a];
+          const double sq = d[a] * d[a], hf = 0.5 * sq;
+          lp = (lp - hf) - (double)P.theta[P.log_std + a];
+        }
+        const double lr = lp - (double)D.logp_old[p], r = exp(lr), adv = npd_ppo_load(D.adv, D.adv_type, p);
+        const double lo = 1.0 - D.clip, hi = 1.0 + D.clip;
+        const bool clipped = (adv > 0.0 && r > hi) || (adv < 0.0 && r < lo);
+        const double ar = adv * r, c = clipped ? 0.0 : -ar;
+        for (int a = 0; a < A; a++) {
+          const double cd = c * d[a], q = cd / (double)P.theta[P.std + a], seed = q / n;
+          da[a * NPD_POLICY_STRIDE + tid] = (float)seed;
+          const double sq = d[a] * d[a], less = sq - 1.0, t = c * less;
+          rowv[a * NPD_POLICY_TILE + tid] = t / n;
+        }
+        const double rc = r < lo ? lo : (r > hi ? hi : r), second = rc * adv;
+        rowv[NPD_PPO_POLICY_LOSS * NPD_POLICY_TILE + tid] = -(second < ar ? second : ar);
+        const double rm = r - 1.0;
+        rowv[NPD_PPO_KL * NPD_POLICY_TILE + tid] = rm - lr;
+        rowv[NPD_PPO_CLIPPED * NPD_POLICY_TILE + tid] = clipped ? 1.0 : 0.0;
+        if (D.logp_new) D.logp_new[p] = (float)lp;
+        if (D.ratio) D.ratio[p] = r;
+      });
+      /* 5. the critic */
+      npd_ppo_net<H_MAX>(P.critic, P, xs, hid, head, da, db, prow, first, tid, [&]() {
+        if (tid >= NPD_POLICY_TILE) return;
+        for (int a = 0; a < 4; a++) da[a * NPD_POLICY_STRIDE + tid] = 0.0f;
+        if (!live) return;
+        const float v = head[tid];
+        if (D.value_new) D.value_new[p] = skipped ? (float)qnan : v;
+        if (skipped) return;
+        const double diff = (double)v - npd_ppo_load(D.ret, D.adv_type, p), scaled = D.vf_coef * diff, sq = diff * diff;
+        da[tid] = (float)(scaled / n);
+        rowv[NPD_PPO_VALUE_LOSS * NPD_POLICY_TILE + tid] = 0.5 * sq;
+      });
+      /* 6. the tile's per-row doubles onto the chain's sums, rows ascending */
+      if (tid < NPD_PPO_ROWVALS)
+        for (int r = 0; r < NPD_POLICY_TILE; r++) running = running + rowv[tid * NPD_POLICY_TILE + r];
+    }
+    if (tid < NPD_PPO_ROWVALS) R.chain_stats[chain * NPD_PPO_ROWVALS + tid] = running;
+  }
+}
+
+/* a lane a parameter: the ascending sum over the chains, narrowed once; log_std's gradient from the dls sums; std's 0; and the first level
+ * of the pinned tree over the squares of every entry but std's (a workgroup IS a group of 256) */
+__global__ __launch_bounds__(NPD_TREE) void npb_ppo_reduce_kernel(npb_policy_t P, npd_ppo_run_t R, npb_ppo_t O) {
+  __shared__ double s[NPD_TREE];
+  const int lane = threadIdx.x;
+  const size_t e = (size_t)blockIdx.x * NPD_TREE + lane;
+  float g = 0.0f;
+  if (e < P.log_std) {
+    double sum = 0.0;
+    for (int c = 0; c < R.n_chains; c++) sum = sum + (double)R.partials[(size_t)c * R.floats + e];
+    g = (float)sum;
+  } else if (e < P.std) {
+    double sum = 0.0;
+    for (int c = 0; c < R.n_chains; c++) sum = sum + R.chain_stats[(size_t)c * NPD_PPO_ROWVALS + (e - P.log_std)];
+    g = (float)(sum - R.D.ent_coef);
+  }
+  if (e < P.theta_count) O.grad[e] = g;
+  s[lane] = e < P.std ? (double)g * (double)g : 0.0;
+  npd_tree_group(s, lane);
+  if (lane == 0 && (size_t)blockIdx.x * NPD_TREE < P.std) O.tree[blockIdx.x] = s[0];
+}
+
+/* one workgroup: the tree's further levels, the norm, the scale over every entry but std's, the statistics */
+__global__ __launch_bounds__(NPD_TREE) void npb_ppo_finish_kernel(npb_policy_t P, npd_ppo_run_t R, npb_ppo_t O) {
+  __shared__ double s[NPD_TREE];
+  const int lane = threadIdx.x;
+  const double *in = npd_tree_levels(O.tree, ((size_t)P.std + NPD_TREE - 1) / NPD_TREE, s, lane);
+  const double norm = sqrt(in[0]);
+  if (R.D.max_grad_norm > 0.0) {
+    const double bound = norm + 1e-6, ratio = R.D.max_grad_norm / bound, scale = ratio < 1.0 ? ratio : 1.0;
+    for (size_t e = lane; e < P.std; e += NPD_TREE) O.grad[e] = (float)((double)O.grad[e] * scale);
+  }
+  if (lane < 5) {
+    const int slot[5] = {NPD_PPO_POLICY_LOSS, NPD_PPO_VALUE_LOSS, -1, NPD_PPO_KL, NPD_PPO_CLIPPED};
+    const double n = (double)R.D.count;
+    double sum = 0.0;
+    if (lane == 2) {
+      for (int a = 0; a < P.n_axes; a++) { const double t = (double)P.theta[P.log_std + a] + 0.5; sum = sum + (t + 0.9189385332046727); }
+      O.stats[2] = sum;
+    } else {
+      for (int c = 0; c < R.n_chains; c++) sum = sum + R.chain_stats[(size_t)c * NPD_PPO_ROWVALS + slot[lane]];
+      O.stats[lane] = sum / n;
+    }
+  } else if (lane == 5) {
+    double sum = 0.0;
+    for (int c = 0; c < R.n_chains; c++) sum = sum + R.chain_stats[(size_t)c * NPD_PPO_ROWVALS + NPD_PPO_SKIPPED];
+    O.stats[5] = sum;
+  } else if (lane == 6) O.stats[6] = norm;
+  else if (lane == 7) O.stats[7] = (double)R.D.count;
+}
+
+/* Adam, a lane a parameter, std's slots apart: in double, every operation rounded on its own, each result narrowed once; log_std's lane
+ * then refreshes std = (float)exp((double)log_std') */
+__global__ __launch_bounds__(256) void npb_ppo_adam_kernel(npb_policy_t P, npb_ppo_t O, double step_size, double root, double b1, double c1, double b2, double c2,
+                                                           double eps) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= P.std) return;
+  const double g = (double)O.grad[e];
+  const double m_keep = b1 * (double)O.m[e], m_new = c1 * g;
+  const float m = (float)(m_keep + m_new);
+  const double gg = g * g, v_keep = b2 * (double)O.v[e], v_new = c2 * gg;
+  const float v = (float)(v_keep + v_new);
+  const double rt = sqrt((double)v), scaled = rt / root, denom = scaled + eps, dir = (double)m / denom, move = step_size * dir;
+  const float t = (float)((double)P.theta[e] - move);
+  O.m[e] = m; O.v[e] = v; P.theta[e] = t;
+  if (e >= P.log_std) P.theta[e + P.n_axes] = (float)exp((double)t);
+}
+
+static npd_ppo_run_t npd_ppo_run(const npb_ppo_t *O, const npb_ppo_desc_t *D) {
+  npd_ppo_run_t R = {};
+  R.D = *D;
+  R.n_chains = (int)(((int64_t)D->count + D->rows_per_chain - 1) / D->rows_per_chain);
+  R.partials = O->partials; R.floats = O->floats; R.chain_stats = O->chain_stats;
+  return R;
+}
+extern "C" void npb_launch_ppo_grad(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_desc_t *D, hipStream_t stream) {
+  const npd_ppo_run_t R = npd_ppo_run(O, D);
+  const int cap = D->max_blocks > 0 ? D->max_blocks : 2048;
+  const dim3 grid((unsigned)(R.n_chains < cap ? R.n_chains : cap)), block(NPD_POLICY_LANES);
+  if (P->cells <= 64 && P->width_max <= 64) hipLaunchKernelGGL((npb_ppo_grad_kernel<64, 64>), grid, block, 0, stream, *P, R);
+  else hipLaunchKernelGGL((npb_ppo_grad_kernel<NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX>), grid, block, 0, stream, *P, R);
+  hipLaunchKernelGGL(npb_ppo_reduce_kernel, dim3((P->theta_count + NPD_TREE - 1) / NPD_TREE), dim3(NPD_TREE), 0, stream, *P, R, *O);
+  hipLaunchKernelGGL(npb_ppo_finish_kernel, dim3(1), dim3(NPD_TREE), 0, stream, *P, R, *O);
+}
+extern "C" void npb_launch_ppo_adam(const npb_policy_t *P, const npb_ppo_t *O, double lr, double b1, double b2, double eps, hipStream_t stream) {
+  /* (formed here and not by the caller: this file's flags keep the host's division IEEE too) */
+  const double step = (double)O->step, step_size = lr / (1.0 - pow(b1, step)), root = sqrt(1.0 - pow(b2, step));
+  hipLaunchKernelGGL(npb_ppo_adam_kernel, dim3((P->std + 255u) / 256u), dim3(256), 0, stream, *P, *O, step_size, root, b1, 1.0 - b1, b2, 1.0 - b2, eps);
+}

@@ -1932,7 +1932,7 @@ class BatchedPlantEnv:
         if theta.numel() != policy.theta_size(S["cells"], S["n_axes"], S["actor"], S["critic"]):
             raise ValueError("theta has %d elements, the set policy takes %d" % (theta.numel(), policy.theta_size(S["cells"], S["n_axes"], S["actor"], S["critic"])))
         _lib.check(self.L.npb_policy_load(self._h, ctypes.c_void_p(theta.data_ptr()), 1, self._stream()), self._h)
-        pol["theta"] = theta      # (alive while the launch reads it)
+        pol["theta"], pol["moved"] = theta, False      # (alive while the launch reads it)
 
     def policy_load(self, theta_or_modules) -> None:
         """New parameters into the set policy (npb_policy_load), once per optimiser iteration: a flat float32 ``theta`` in the
@@ -1952,8 +1952,123 @@ class BatchedPlantEnv:
         return {"value": pol["value"], "logp": pol["logp"]}
 
     def policy_theta(self) -> torch.Tensor:
-        """the parameters last loaded, the flat float32 device tensor in the statement's order (what ``policy.Policy.load`` takes)"""
-        return self._on("_pol")["theta"]
+        """the handle's current parameters, a flat float32 device tensor in the statement's order (what ``policy.Policy.load`` takes): the
+        tensor last loaded until ``policy_adam`` / ``policy_train`` has moved them, then a copy of the handle's (npb_policy_get_theta)"""
+        pol = self._on("_pol")
+        if pol.get("moved"):
+            with torch.cuda.device(self.device):
+                theta = torch.zeros_like(pol["theta"])
+            _lib.check(self.L.npb_policy_get_theta(self._h, ctypes.c_void_p(theta.data_ptr()), self._stream()), self._h)
+            pol["theta"], pol["moved"] = theta, False
+        return pol["theta"]
+
+    # ------------------------------------------------------------------ training the policy on the device
+    def _ppo_desc(self, batch, clip, vf_coef, ent_coef, max_grad_norm, rows_per_chain, max_blocks=0):
+        """``(descriptor, tensors kept alive)`` of one minibatch: a dict as ``rollout_minibatches`` yields (``logp_old`` from the extras
+        slot the policy was set with) or one of explicit tensors ``obs``, ``act``, ``logp_old``, ``adv``, ``ret``"""
+        pol = self._on("_pol")
+        if not hasattr(self.L, "npb_policy_grad"):
+            raise _lib.NpbError("libnpb.so has no npb_policy_grad: rebuild")
+        S = pol["spec"]
+        for name in ("obs", "act", "adv", "ret"):
+            if batch.get(name) is None:
+                raise ValueError("a minibatch needs %r" % name)
+        old = batch.get("logp_old")
+        if old is None:
+            slot = S["extras"]["logp"]
+            if batch.get("extra") is None or slot < 0:
+                raise ValueError("no logp_old: pass it, or set the policy with extras naming 'logp' so the rollout records it")
+            old = batch["extra"][..., slot]
+        floats = (torch.float32, torch.float64)
+
+        def dev(x, dtypes, what):
+            x = torch.as_tensor(x)
+            if x.dtype not in dtypes:
+                raise ValueError("%s must be %s, not %r" % (what, " or ".join(str(t) for t in dtypes), x.dtype))
+            return x.to(device=self.device).contiguous()
+        obs, act = dev(batch["obs"], floats, "obs"), dev(batch["act"], floats, "act")
+        old, adv = dev(old, (torch.float32,), "logp_old").reshape(-1), dev(batch["adv"], floats, "adv").reshape(-1)
+        ret = dev(batch["ret"], (adv.dtype,), "ret").reshape(-1)
+        count = adv.numel()
+        if count < 1 or obs.numel() != count * S["cells"] or act.numel() != count * S["n_axes"] or old.numel() != count or ret.numel() != count:
+            raise ValueError("a minibatch of %d rows takes obs of %d cells and act of %d axes a row, and logp_old and ret of its length"
+                             % (count, S["cells"], S["n_axes"]))
+        if str(act.dtype).split(".")[1] != S["act_dtype"]:
+            raise ValueError("act must be of the controls' input type, %s" % S["act_dtype"])
+        d = _lib.NpbPpoDesc()
+        d.obs, d.obs_type = obs.data_ptr(), _lib.FEATURE_DTYPES[self._MB_DTYPES[obs.dtype]]
+        d.act, d.act_type = act.data_ptr(), _lib.CONTROL_DTYPES[self._MB_DTYPES[act.dtype]]
+        d.logp_old, d.adv, d.ret, d.adv_type, d.count = old.data_ptr(), adv.data_ptr(), ret.data_ptr(), _lib.ROLLOUT_DTYPES[self._MB_DTYPES[adv.dtype]], count
+        d.clip, d.vf_coef, d.ent_coef, d.max_grad_norm = float(clip), float(vf_coef), float(ent_coef), float(max_grad_norm)
+        d.rows_per_chain, d.max_blocks = int(rows_per_chain), int(max_blocks)
+        return d, [obs, act, old, adv, ret]
+
+    def policy_grad(self, batch, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0, max_grad_norm: float = 0.5,
+                    rows_per_chain: int = 256, diagnostics: bool = False, max_blocks: int = 0) -> dict:
+        """The PPO loss of one minibatch and its gradient through both nets, on the device (npb_policy_grad): ``{"grad", "stats"}`` --
+        ``grad`` float32 in theta's layout, clipped to ``max_grad_norm`` (0 = off), ``stats`` float64 [8] in ``ppo.STATS``'s order, both
+        device tensors, nothing read back -- and with ``diagnostics`` also ``logp_new``, ``value_new`` (float32) and ``ratio`` (float64),
+        [count] each.  ``batch``: a dict as ``rollout_minibatches`` yields (``logp_old`` is the extras slot the policy was set with) or one
+        with ``obs``, ``act``, ``logp_old``, ``adv``, ``ret``.  ``rows_per_chain`` pins the order of the sums over rows; no bit depends on
+        ``max_blocks``.  ``nuclear_sim_amd.ppo.gradient`` is the same in numpy: bit for bit with relu when fed the device's ``ratio``."""
+        d, held = self._ppo_desc(batch, clip, vf_coef, ent_coef, max_grad_norm, rows_per_chain, max_blocks)
+        pol = self._pol
+        out = {}
+        with torch.cuda.device(self.device):
+            if diagnostics:
+                out = {"logp_new": torch.zeros(d.count, dtype=torch.float32, device=self.device),
+                       "value_new": torch.zeros(d.count, dtype=torch.float32, device=self.device),
+                       "ratio": torch.zeros(d.count, dtype=torch.float64, device=self.device)}
+                d.logp_new, d.value_new, d.ratio = out["logp_new"].data_ptr(), out["value_new"].data_ptr(), out["ratio"].data_ptr()
+            out["grad"] = torch.zeros(pol["theta"].numel(), dtype=torch.float32, device=self.device)
+            out["stats"] = torch.zeros(_lib.PPO_STATS, dtype=torch.float64, device=self.device)
+        _lib.check(self.L.npb_policy_grad(self._h, ctypes.byref(d), self._stream()), self._h)
+        _lib.check(self.L.npb_policy_get_grad(self._h, ctypes.c_void_p(out["grad"].data_ptr()), self._stream()), self._h)
+        _lib.check(self.L.npb_policy_get_stats(self._h, ctypes.c_void_p(out["stats"].data_ptr()), self._stream()), self._h)
+        pol["ppo_held"] = held      # (alive while the launches read them)
+        return out
+
+    def policy_adam(self, lr: float = 3e-4, betas=(0.9, 0.999), eps: float = 1e-5) -> None:
+        """One Adam step from the gradient the last ``policy_grad`` left on the handle (npb_policy_adam): the parameters, ``std`` and the
+        weights as the step reads them are refreshed on the device; ``nuclear_sim_amd.ppo.adam`` is the same in numpy"""
+        pol = self._on("_pol")
+        _lib.check(self.L.npb_policy_adam(self._h, float(lr), float(betas[0]), float(betas[1]), float(eps), self._stream()), self._h)
+        pol["moved"] = True
+
+    def policy_train(self, batch_size, epochs: int = 1, seed: int = 0, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0,
+                     max_grad_norm: float = 0.5, rows_per_chain: int = 256, lr: float = 3e-4, betas=(0.9, 0.999), eps: float = 1e-5,
+                     **minibatches) -> torch.Tensor:
+        """The optimiser's half of a PPO iteration: ``rollout_minibatches(batch_size, epochs, seed, **minibatches)`` and one
+        npb_policy_update -- gradient and Adam step -- per minibatch.  Returns every update's stats as ONE device tensor [updates, 8]
+        (``ppo.STATS``'s order); no host synchronisation.  ``collect``, ``rollout_advantages``, ``policy_train`` is a whole iteration."""
+        pol = self._on("_pol")
+        rows = []
+        for batch in self.rollout_minibatches(batch_size, epochs, seed, **minibatches):
+            d, held = self._ppo_desc(batch, clip, vf_coef, ent_coef, max_grad_norm, rows_per_chain)
+            with torch.cuda.device(self.device):
+                row = torch.zeros(_lib.PPO_STATS, dtype=torch.float64, device=self.device)
+            _lib.check(self.L.npb_policy_update(self._h, ctypes.byref(d), float(lr), float(betas[0]), float(betas[1]), float(eps), self._stream()), self._h)
+            _lib.check(self.L.npb_policy_get_stats(self._h, ctypes.c_void_p(row.data_ptr()), self._stream()), self._h)
+            pol["moved"], pol["ppo_held"] = True, held
+            rows.append(row)
+        with torch.cuda.device(self.device):
+            return torch.stack(rows) if rows else torch.zeros((0, _lib.PPO_STATS), dtype=torch.float64, device=self.device)
+
+    def policy_optimizer_state(self) -> Dict[str, np.ndarray]:
+        """Adam's state for a checkpoint (npb_policy_optimizer_get_state): ``m``, ``v`` float32 in theta's layout, and ``step``"""
+        pol = self._on("_pol")
+        m, v = (np.zeros(pol["theta"].numel(), dtype=np.float32) for _ in range(2))
+        step = ctypes.c_uint64()
+        _lib.check(self.L.npb_policy_optimizer_get_state(self._h, m.ctypes.data, v.ctypes.data, ctypes.byref(step), self._stream()), self._h)
+        return {"m": m, "v": v, "step": np.uint64(step.value)}
+
+    def load_policy_optimizer_state(self, state) -> None:
+        """put back what ``policy_optimizer_state()`` returned (npb_policy_optimizer_set_state)"""
+        pol = self._on("_pol")
+        m, v = (np.ascontiguousarray(state[k], dtype=np.float32).reshape(-1) for k in ("m", "v"))
+        if m.size != pol["theta"].numel() or v.size != m.size:
+            raise ValueError("m and v have theta's %d elements" % pol["theta"].numel())
+        _lib.check(self.L.npb_policy_optimizer_set_state(self._h, m.ctypes.data, v.ctypes.data, int(state["step"]), self._stream()), self._h)
 
     def policy_values(self, x=None) -> torch.Tensor:
         """The critic alone (npb_policy_values): float32 [rows] of ``x``, a float32 or float64 device tensor [rows, K, C] (or [rows, K * C]);
