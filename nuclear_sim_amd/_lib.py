@@ -1052,11 +1052,202 @@ def episode_streams_desc(block, bank_noise_seeds=None, bank_profile_seeds=None, 
     return d, tables
 
 
+_vp, _ci, _cd, _sz, _cs, _i64, _u64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_int64,
+                                       ctypes.c_uint64)
+_P = ctypes.POINTER
+# THE statement of the C ABI's Python signatures (include/npb.h; tests/test_binding_cpu.py holds every row against its prototype):
+# (the symbol whose presence detects the group -- None: the core, always there --, {name: (restype, argtypes)}).  A restype of None
+# leaves ctypes' int (the header's int and void), argtypes of None leave the function as ctypes hands it out (no parameters).  A group
+# absent from an older or ablated build is skipped; NPB_VERSION does not move with a new group.
+ENTRY_POINTS = (
+    (None, {
+        "npb_version": (_ci, None), "npb_num_f64": (_ci, None), "npb_num_i32": (_ci, None),
+        "npb_state_bytes": (_sz, None), "npb_step_bytes_per_plant": (_sz, None),
+        "npb_default_params": (None, [_P(NpbParams)]),
+        "npb_create": (None, [_P(NpbParams), _ci, _ci, _P(_vp)]),
+        "npb_create_storage": (None, [_P(NpbParams), _ci, _ci, _ci, _P(_vp)]),
+        "npb_storage": (None, [_vp]),
+        "npb_handle_step_bytes_per_plant": (_sz, [_vp]),
+        "npb_destroy": (None, [_vp]),
+        "npb_last_error": (_cs, [_vp]),
+        "npb_num_plants": (None, [_vp]),
+        "npb_set_params": (None, [_vp, _P(NpbParams)]),
+        "npb_reset": (None, [_vp, _vp, _vp]),
+        "npb_set_step_kernel": (None, [_vp, _ci]),
+        "npb_set_maintenance_table": (None, [_vp, _P(NpbMaintTable)]),
+        "npb_default_maintenance_table": (None, [_P(NpbMaintTable)]),
+        "npb_reset_reference": (None, [_vp, _vp, _ci, _vp]),
+        "npb_get_field": (None, [_vp, _ci, _ci, _vp, _ci, _vp]),
+        "npb_set_field": (None, [_vp, _ci, _ci, _vp, _ci, _vp]),
+        "npb_state_arena": (None, [_vp, _P(_vp), _P(_sz), _P(_ci)]),
+        "npb_gather_fields": (None, [_vp, _ci, _vp, _vp, _vp, _vp]),
+        "npb_locate_field": (None, [_vp, _ci, _ci, _P(_ci), _P(_ci), _P(_ci)]),
+        "npb_step": (None, [_vp] * 12),
+        "npb_observe": (None, [_vp, _vp, _vp]),
+        "npb_debug_touch": (None, [_vp, _vp])}),
+    ("npb_debug_last_step_kernel", {     # ABI 140
+        "npb_debug_last_step_kernel": (None, [_vp]),
+        "npb_step_kernel_name": (_cs, [_ci]),
+        "npb_maint_param_name": (_cs, [_ci]), "npb_maint_action_name": (_cs, [_ci]),
+        "npb_maint_num_params": (None, None), "npb_maint_num_actions": (None, None),
+        "npb_obs_dim": (None, None), "npb_info_dim": (None, None), "npb_info_nrho": (None, None), "npb_diag_dim": (None, None)}),
+    ("npb_set_diagnostics", {     # (absent from builds older than ABI 133: tools/ab_kernel.py loads those)
+        "npb_set_diagnostics": (None, [_vp, _vp, _sz])}),
+    ("npb_set_maintenance_count_buffer", {
+        "npb_set_maintenance_count_buffer": (None, [_vp, _vp])}),
+    ("npb_state_arena_layout", {     # ABI 142
+        "npb_state_arena_layout": (None, [_vp, _P(_vp), _P(_sz), _P(_sz), _P(_ci), _P(_ci)])}),
+    ("npb_state_arena_segment", {    # ABI 141
+        "npb_state_arena_segment": (_sz, [_vp])}),
+    ("npb_snapshot", {     # ABI 143: episodes
+        "npb_snapshot": (None, [_vp, _vp]),
+        "npb_restore": (None, [_vp, _vp, _vp]),
+        "npb_set_autoreset": (None, [_vp, _ci, _ci]),
+        "npb_set_episode_buffers": (None, [_vp, _vp, _vp, _vp, _vp])}),
+    ("npb_set_start_bank", {     # ABI 144: restarts from a bank of start states
+        "npb_set_start_bank": (None, [_vp, _vp, _vp]),
+        "npb_set_start_slots": (None, [_vp, _vp, _vp, _ci]),
+        "npb_restore_bank": (None, [_vp, _vp, _vp]),
+        "npb_set_episode_start_buffer": (None, [_vp, _vp])}),
+    ("npb_set_maintenance_log", {     # ABI 146: the maintenance event log
+        "npb_set_maintenance_log": (None, [_vp, _vp, _ci, _vp]),
+        "npb_maint_event_bytes": (_sz, None),
+        "npb_maint_action_has_handler": (None, [_ci])}),
+    ("npb_perform_maintenance", {     # ABI 147: maintenance the caller orders
+        "npb_perform_maintenance": (None, [_vp] * 7)}),
+    ("npb_perform_component_maintenance", {     # ABI 148: maintenance of steam generators, condenser and ejectors the caller orders
+        "npb_perform_component_maintenance": (None, [_vp] * 7),
+        "npb_component_num_actions": (None, None),
+        "npb_component_action_name": (_cs, [_ci]),
+        "npb_component_kind_name": (_cs, [_ci]),
+        "npb_component_action_kind": (None, [_ci])}),
+    ("npb_perform_turbine_maintenance", {     # ABI 149: maintenance of the turbine the caller orders
+        "npb_perform_turbine_maintenance": (None, [_vp] * 5),
+        "npb_turbine_num_actions": (None, None),
+        "npb_turbine_action_name": (_cs, [_ci]),
+        "npb_turbine_kind_name": (_cs, [_ci]),
+        "npb_turbine_action_kind": (None, [_ci])}),
+    ("npb_set_component_maintenance", {     # ABI 150: automatic maintenance of steam generators and condenser
+        "npb_set_component_maintenance": (None, [_vp, _P(NpbComponentMaintTable)]),
+        "npb_default_component_maintenance_table": (None, [_P(NpbComponentMaintTable)]),
+        "npb_component_maint_num_params": (None, None),
+        "npb_component_maint_param_name": (_cs, [_ci]),
+        "npb_component_maint_param_kind": (None, [_ci]),
+        "npb_component_maintenance_state_bytes": (_sz, [_vp]),
+        "npb_get_component_maintenance_state": (None, [_vp, _vp, _vp]),
+        "npb_set_component_maintenance_state": (None, [_vp, _vp, _vp])}),
+    ("npb_carry_diagnostics", {     # ABI 151: the carried diagnostics rows travel with restores, resets and checkpoints
+        "npb_carry_diagnostics": (None, [_vp, _ci]),
+        "npb_diag_num_carried": (None, None),
+        "npb_diag_carried_row": (None, [_ci]),
+        "npb_diag_carried_fresh": (_cd, [_ci]),
+        "npb_get_diagnostics_state": (None, [_vp, _vp, _vp]),
+        "npb_set_diagnostics_state": (None, [_vp, _vp, _vp]),
+        "npb_set_episode_index_buffer": (None, [_vp, _vp])}),
+    ("npb_noise_seed", {     # ABI 145: heat-source noise streams on the device
+        "npb_noise_seed": (None, [_vp, _vp, _vp]),
+        "npb_noise_fill": (None, [_vp, _ci, _vp, _vp]),
+        "npb_noise_get_state": (None, [_vp] * 6),
+        "npb_noise_set_state": (None, [_vp] * 6)}),
+    ("npb_profile_seed", {     # ABI 152: the data-gen runner's power profile on the device
+        "npb_profile_seed": (None, [_vp, _vp, _ci, _vp, _ci, _vp, _ci, _vp]),
+        "npb_profile_fill": (None, [_vp, _ci, _vp, _vp, _vp, _vp]),
+        "npb_profile_ramp": (None, [_vp, _ci, _vp, _vp, _vp]),
+        "npb_profile_get_state": (None, [_vp] * 8),
+        "npb_profile_set_state": (None, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp])}),
+    ("npb_sampler_create", {     # ABI 153: a state log samples a watch list of plants
+        "npb_sampler_create": (None, [_vp, _P(NpbSamplerDesc), _P(_ci)]),
+        "npb_sampler_sample": (None, [_vp, _ci, _vp, _vp]),
+        "npb_sampler_destroy": (None, [_vp, _ci])}),
+    ("npb_set_maintenance_summary", {     # ABI 154: the event log folded into a per-plant work-order summary
+        "npb_set_maintenance_summary": (None, [_vp, _P(NpbMaintSummaryDesc)]),
+        "npb_maint_summary_check": (_cs, [_P(NpbMaintSummaryDesc), _ci, _ci]),
+        "npb_maint_summary_fold": (None, [_vp, _vp]),
+        "npb_maint_summary_clear": (None, [_vp, _vp, _vp])}),
+    ("npb_set_episode_streams", {     # (ABI 154 still) each plant's noise and power profile restart with its episode
+        "npb_set_episode_streams": (None, [_vp, _P(NpbEpisodeStreamsDesc), _vp]),
+        "npb_episode_streams_check": (_cs, [_P(NpbEpisodeStreamsDesc), _ci, _ci]),
+        "npb_profile_get_positions": (None, [_vp, _vp, _vp, _vp])}),
+    ("npb_set_episode_records", {     # a device-side log of finished episodes, with their work-order summary
+        "npb_set_episode_records": (None, [_vp, _P(NpbEpisodeRecordsDesc)]),
+        "npb_episode_records_check": (_cs, [_P(NpbEpisodeRecordsDesc), _ci, _ci])}),
+    ("npb_set_column_stats", {     # per-plant column statistics folded behind every step, and their copy into the episode records
+        "npb_set_column_stats": (None, [_vp, _P(NpbColumnStatsDesc)]),
+        "npb_column_stats_check": (_cs, [_P(NpbColumnStatsDesc), _ci]),
+        "npb_column_stats_fold": (None, [_vp, _vp]),
+        "npb_column_stats_clear": (None, [_vp, _vp, _vp]),
+        "npb_set_episode_record_stats": (None, [_vp, _P(NpbEpisodeRecordStatsDesc)])}),
+    ("npb_set_task", {     # the caller's reward terms and termination rules, formed behind every step
+        "npb_set_task": (None, [_vp, _P(NpbTaskDesc)]),
+        "npb_task_check": (_cs, [_P(NpbTaskDesc), _ci]),
+        "npb_task_clear": (None, [_vp, _vp, _vp]),
+        "npb_task_get_state": (None, [_vp] * 5),
+        "npb_task_set_state": (None, [_vp] * 5),
+        "npb_set_episode_record_task": (None, [_vp, _vp])}),
+    ("npb_set_features", {     # the caller's policy inputs: a stack of transformed frames kept behind every step
+        "npb_set_features": (None, [_vp, _P(NpbFeaturesDesc)]),
+        "npb_features_check": (_cs, [_P(NpbFeaturesDesc), _ci]),
+        "npb_features_prime": (None, [_vp, _vp]),
+        "npb_features_clear": (None, [_vp, _vp, _vp]),
+        "npb_features_get_state": (None, [_vp] * 4),
+        "npb_features_set_state": (None, [_vp] * 4)}),
+    ("npb_set_controls", {     # the caller's policy outputs: decoded in front of every step
+        "npb_set_controls": (None, [_vp, _P(NpbControlsDesc)]),
+        "npb_controls_check": (_cs, [_P(NpbControlsDesc), _ci, _ci]),
+        "npb_controls_clear": (None, [_vp, _vp, _vp]),
+        "npb_controls_get_state": (None, [_vp] * 7),
+        "npb_controls_set_state": (None, [_vp] * 7)}),
+    ("npb_set_rollout", {     # the rollout: trajectories recorded on the device, and their GAE advantages
+        "npb_set_rollout": (None, [_vp, _P(NpbRolloutDesc)]),
+        "npb_rollout_check": (_cs, [_P(NpbRolloutDesc), _ci, _ci, _ci]),
+        "npb_rollout_begin": (None, [_vp, _vp]),
+        "npb_rollout_steps": (None, [_vp]),
+        "npb_rollout_cut": (None, [_vp, _vp, _vp]),
+        "npb_rollout_advantages": (None, [_vp, _P(NpbRolloutAdvantagesDesc), _vp])}),
+    ("npb_set_normalizer", {     # running observation and reward normalisation, folded behind every step
+        "npb_set_normalizer": (None, [_vp, _P(NpbNormalizerDesc)]),
+        "npb_normalizer_check": (_cs, [_P(NpbNormalizerDesc), _ci, _P(NpbFeaturesDesc)]),
+        "npb_normalizer_training": (None, [_vp, _ci]),
+        "npb_normalizer_clear": (None, [_vp, _vp, _vp]),
+        "npb_normalizer_get_state": (None, [_vp] * 9),
+        "npb_normalizer_set_state": (None, [_vp] * 9)}),
+    ("npb_set_policy", {     # the policy on the device: actor, critic, the Gaussian draw, K steps in one call
+        "npb_set_policy": (None, [_vp, _P(NpbPolicyDesc)]),
+        "npb_policy_check": (_cs, [_P(NpbPolicyDesc), _ci, _ci, _ci]),
+        "npb_policy_count": (_i64, [_P(NpbPolicyDesc), _ci, _ci]),
+        "npb_policy_load": (None, [_vp, _vp, _ci, _vp]),
+        "npb_policy_values": (None, [_vp, _vp, _ci, _ci, _vp, _vp]),
+        "npb_policy_noise": (None, [_vp, _u64, _vp, _vp, _vp]),
+        "npb_policy_get_state": (None, [_vp, _P(_u64)]),
+        "npb_policy_set_state": (None, [_vp, _u64]),
+        "npb_collect": (None, [_vp, _ci] + [_vp] * 6)}),
+    ("npb_policy_grad", {     # training the policy: the PPO loss, its gradient and the Adam step
+        "npb_ppo_check": (_cs, [_P(NpbPpoDesc), _ci, _ci]),
+        "npb_policy_grad": (None, [_vp, _P(NpbPpoDesc), _vp]),
+        "npb_policy_adam": (None, [_vp, _cd, _cd, _cd, _cd, _vp]),
+        "npb_policy_update": (None, [_vp, _P(NpbPpoDesc), _cd, _cd, _cd, _cd, _vp]),
+        "npb_policy_get_grad": (None, [_vp, _vp, _vp]),
+        "npb_policy_get_stats": (None, [_vp, _vp, _vp]),
+        "npb_policy_get_theta": (None, [_vp, _vp, _vp]),
+        "npb_policy_optimizer_get_state": (None, [_vp, _vp, _vp, _P(_u64), _vp]),
+        "npb_policy_optimizer_set_state": (None, [_vp, _vp, _vp, _u64, _vp])}),
+    ("npb_rollout_minibatch", {     # pinned moments, the keyed permutation and the minibatch gather over a rollout
+        "npb_rollout_moments": (None, [_vp, _P(NpbMomentsDesc), _vp]),
+        "npb_rollout_permutation": (None, [_vp, _i64, _P(ctypes.c_uint32), _i64, _i64, _vp, _vp]),
+        "npb_rollout_minibatch": (None, [_vp, _P(NpbMinibatchDesc), _vp]),
+        "npb_minibatch_check": (_cs, [_P(NpbMinibatchDesc), _ci, _ci, _ci, _ci, _ci])}),
+    ("npb_set_event_windows", {     # state windows around events, captured behind every step
+        "npb_set_event_windows": (None, [_vp, _P(NpbEventWindowsDesc)]),
+        "npb_event_windows_check": (_cs, [_P(NpbEventWindowsDesc), _ci, _ci]),
+        "npb_event_windows_clear": (None, [_vp, _vp, _vp]),
+        "npb_event_windows_bytes": (_sz, [_P(NpbEventWindowsDesc), _ci])}),
+)
+
 _lib = None
 
 
 def load():
-    """Load libnpb.so and declare its entry points; raises NpbError when it is absent."""
+    """Load libnpb.so and declare its entry points from ENTRY_POINTS; raises NpbError when it is absent."""
     global _lib
     if _lib is not None:
         return _lib
@@ -1067,235 +1258,41 @@ def load():
     # runtime already in the process (two HIP runtimes in one process do not see the device).
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    vp, ci = ctypes.c_void_p, ctypes.c_int
-    L.npb_version.restype = ci
-    L.npb_num_f64.restype = ci
-    L.npb_num_i32.restype = ci
-    L.npb_state_bytes.restype = ctypes.c_size_t
-    L.npb_step_bytes_per_plant.restype = ctypes.c_size_t
-    L.npb_default_params.argtypes = [ctypes.POINTER(NpbParams)]
-    L.npb_create.argtypes = [ctypes.POINTER(NpbParams), ci, ci, ctypes.POINTER(vp)]
-    L.npb_create_storage.argtypes = [ctypes.POINTER(NpbParams), ci, ci, ci, ctypes.POINTER(vp)]
-    L.npb_storage.argtypes = [vp]
-    L.npb_handle_step_bytes_per_plant.argtypes = [vp]
-    L.npb_handle_step_bytes_per_plant.restype = ctypes.c_size_t
-    L.npb_destroy.argtypes = [vp]
-    L.npb_last_error.argtypes = [vp]
-    L.npb_last_error.restype = ctypes.c_char_p
-    L.npb_num_plants.argtypes = [vp]
-    L.npb_set_params.argtypes = [vp, ctypes.POINTER(NpbParams)]
-    L.npb_reset.argtypes = [vp, vp, vp]
-    L.npb_set_step_kernel.argtypes = [vp, ci]
-    if hasattr(L, "npb_debug_last_step_kernel"):    # ABI 140
-        L.npb_debug_last_step_kernel.argtypes = [vp]
-        L.npb_step_kernel_name.argtypes = [ci]
-        L.npb_step_kernel_name.restype = ctypes.c_char_p
-        for f in ("npb_maint_param_name", "npb_maint_action_name"):
-            getattr(L, f).argtypes = [ci]
-            getattr(L, f).restype = ctypes.c_char_p
+    for detect, functions in ENTRY_POINTS:
+        if detect is not None and not hasattr(L, detect):
+            continue
+        for name, (restype, argtypes) in functions.items():
+            if restype is not None:
+                getattr(L, name).restype = restype
+            if argtypes is not None:
+                getattr(L, name).argtypes = argtypes
+    if hasattr(L, "npb_debug_last_step_kernel"):
         # the widths this binding allocates its output blocks with must be the library's: a library that writes more info
         # columns than the caller allocated overruns the buffer (what crashed a round-2 test run on the host side)
         got = (L.npb_obs_dim(), L.npb_info_dim(), L.npb_info_nrho(), L.npb_diag_dim())
         if got != (OBS_DIM, INFO_DIM, INFO_NRHO, DIAG_DIM):
             raise NpbError("libnpb.so writes obs / info / reactivity / diagnostics blocks of width %r, this binding allocates %r: "
                            "rebuild the library or update nuclear_sim_amd/_lib.py" % (got, (OBS_DIM, INFO_DIM, INFO_NRHO, DIAG_DIM)))
-    if hasattr(L, "npb_set_diagnostics"):     # (absent from builds older than ABI 133: tools/ab_kernel.py loads those)
-        L.npb_set_diagnostics.argtypes = [vp, vp, ctypes.c_size_t]
-    L.npb_set_maintenance_table.argtypes = [vp, ctypes.POINTER(NpbMaintTable)]
-    if hasattr(L, "npb_set_maintenance_count_buffer"):
-        L.npb_set_maintenance_count_buffer.argtypes = [vp, vp]
-    L.npb_default_maintenance_table.argtypes = [ctypes.POINTER(NpbMaintTable)]
-    L.npb_reset_reference.argtypes = [vp, vp, ci, vp]
-    L.npb_get_field.argtypes = [vp, ci, ci, vp, ci, vp]
-    L.npb_set_field.argtypes = [vp, ci, ci, vp, ci, vp]
-    L.npb_state_arena.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ci)]
-    if hasattr(L, "npb_state_arena_layout"):     # ABI 142
-        L.npb_state_arena_layout.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ci), ctypes.POINTER(ci)]
-    if hasattr(L, "npb_state_arena_segment"):    # ABI 141
-        L.npb_state_arena_segment.argtypes = [vp]
-        L.npb_state_arena_segment.restype = ctypes.c_size_t
-    L.npb_gather_fields.argtypes = [vp, ci, vp, vp, vp, vp]
-    L.npb_locate_field.argtypes = [vp, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
-    L.npb_step.argtypes = [vp] + [vp] * 11
-    L.npb_observe.argtypes = [vp, vp, vp]
-    L.npb_debug_touch.argtypes = [vp, vp]
-    if hasattr(L, "npb_snapshot"):     # ABI 143: episodes
-        L.npb_snapshot.argtypes = [vp, vp]
-        L.npb_restore.argtypes = [vp, vp, vp]
-        L.npb_set_autoreset.argtypes = [vp, ci, ci]
-        L.npb_set_episode_buffers.argtypes = [vp, vp, vp, vp, vp]
-    if hasattr(L, "npb_set_start_bank"):     # ABI 144: restarts from a bank of start states
-        L.npb_set_start_bank.argtypes = [vp, vp, vp]
-        L.npb_set_start_slots.argtypes = [vp, vp, vp, ci]
-        L.npb_restore_bank.argtypes = [vp, vp, vp]
-        L.npb_set_episode_start_buffer.argtypes = [vp, vp]
-    if hasattr(L, "npb_set_maintenance_log"):     # ABI 146: the maintenance event log
-        L.npb_set_maintenance_log.argtypes = [vp, vp, ci, vp]
-        L.npb_maint_event_bytes.restype = ctypes.c_size_t
-        L.npb_maint_action_has_handler.argtypes = [ci]
-    if hasattr(L, "npb_perform_maintenance"):     # ABI 147: maintenance the caller orders
-        L.npb_perform_maintenance.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    if hasattr(L, "npb_perform_component_maintenance"):     # ABI 148: maintenance of steam generators, condenser and ejectors the caller orders
-        L.npb_perform_component_maintenance.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-        L.npb_component_action_name.restype = ctypes.c_char_p
-        L.npb_component_action_name.argtypes = [ci]
-        L.npb_component_kind_name.restype = ctypes.c_char_p
-        L.npb_component_kind_name.argtypes = [ci]
-        L.npb_component_action_kind.argtypes = [ci]
+    if hasattr(L, "npb_perform_component_maintenance"):
         catalog = tuple((L.npb_component_kind_name(L.npb_component_action_kind(a)).decode(), L.npb_component_action_name(a).decode())
                         for a in range(L.npb_component_num_actions()))
         if catalog != COMPONENT_ACTIONS:
             raise NpbError("libnpb.so's component catalog is not this binding's COMPONENT_ACTIONS: rebuild")
-    if hasattr(L, "npb_perform_turbine_maintenance"):     # ABI 149: maintenance of the turbine the caller orders
-        L.npb_perform_turbine_maintenance.argtypes = [vp, vp, vp, vp, vp]
-        L.npb_turbine_action_name.restype = ctypes.c_char_p
-        L.npb_turbine_action_name.argtypes = [ci]
-        L.npb_turbine_kind_name.restype = ctypes.c_char_p
-        L.npb_turbine_kind_name.argtypes = [ci]
-        L.npb_turbine_action_kind.argtypes = [ci]
+    if hasattr(L, "npb_perform_turbine_maintenance"):
         catalog = tuple((L.npb_turbine_kind_name(L.npb_turbine_action_kind(a)).decode(), L.npb_turbine_action_name(a).decode())
                         for a in range(L.npb_turbine_num_actions()))
         if catalog != TURBINE_ACTIONS:
             raise NpbError("libnpb.so's turbine catalog is not this binding's TURBINE_ACTIONS: rebuild")
-    if hasattr(L, "npb_set_component_maintenance"):     # ABI 150: automatic maintenance of steam generators and condenser
-        L.npb_set_component_maintenance.argtypes = [vp, ctypes.POINTER(NpbComponentMaintTable)]
-        L.npb_default_component_maintenance_table.argtypes = [ctypes.POINTER(NpbComponentMaintTable)]
-        L.npb_component_maint_param_name.restype = ctypes.c_char_p
-        L.npb_component_maint_param_name.argtypes = [ci]
-        L.npb_component_maint_param_kind.argtypes = [ci]
-        L.npb_component_maintenance_state_bytes.argtypes = [vp]
-        L.npb_component_maintenance_state_bytes.restype = ctypes.c_size_t
-        L.npb_get_component_maintenance_state.argtypes = [vp, vp, vp]
-        L.npb_set_component_maintenance_state.argtypes = [vp, vp, vp]
+    if hasattr(L, "npb_set_component_maintenance"):
         catalog = tuple((L.npb_component_kind_name(L.npb_component_maint_param_kind(k)).decode(), L.npb_component_maint_param_name(k).decode())
                         for k in range(L.npb_component_maint_num_params()))
         if catalog != CMAINT_PARAMS:
             raise NpbError("libnpb.so's component parameter catalog is not this binding's CMAINT_PARAMS: rebuild")
-    if hasattr(L, "npb_carry_diagnostics"):     # ABI 151: the carried diagnostics rows travel with restores, resets and checkpoints
-        L.npb_carry_diagnostics.argtypes = [vp, ci]
-        L.npb_diag_carried_row.argtypes = [ci]
-        L.npb_diag_carried_fresh.argtypes = [ci]
-        L.npb_diag_carried_fresh.restype = ctypes.c_double
-        L.npb_get_diagnostics_state.argtypes = [vp, vp, vp]
-        L.npb_set_diagnostics_state.argtypes = [vp, vp, vp]
-        L.npb_set_episode_index_buffer.argtypes = [vp, vp]
+    if hasattr(L, "npb_carry_diagnostics"):
         table = {L.npb_diag_carried_row(k): L.npb_diag_carried_fresh(k) for k in range(L.npb_diag_num_carried())}
         if table != DIAG_CARRIED_ROWS or list(table) != list(DIAG_CARRIED_ROWS):
             raise NpbError("libnpb.so carries the diagnostics rows %r (include/npb.h NPB_DIAG_CARRIED), this binding's DIAG_CARRIED_ROWS is %r: "
                            "rebuild the library or update nuclear_sim_amd/_lib.py" % (table, DIAG_CARRIED_ROWS))
-    if hasattr(L, "npb_noise_seed"):     # ABI 145: heat-source noise streams on the device
-        L.npb_noise_seed.argtypes = [vp, vp, vp]
-        L.npb_noise_fill.argtypes = [vp, ci, vp, vp]
-        L.npb_noise_get_state.argtypes = [vp, vp, vp, vp, vp, vp]
-        L.npb_noise_set_state.argtypes = [vp, vp, vp, vp, vp, vp]
-    if hasattr(L, "npb_profile_seed"):     # ABI 152: the data-gen runner's power profile on the device
-        L.npb_profile_seed.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp]
-        L.npb_profile_fill.argtypes = [vp, ci, vp, vp, vp, vp]
-        L.npb_profile_ramp.argtypes = [vp, ci, vp, vp, vp]
-        L.npb_profile_get_state.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-        L.npb_profile_set_state.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp]
-    if hasattr(L, "npb_sampler_create"):     # ABI 153: a state log samples a watch list of plants
-        L.npb_sampler_create.argtypes = [vp, ctypes.POINTER(NpbSamplerDesc), ctypes.POINTER(ci)]
-        L.npb_sampler_sample.argtypes = [vp, ci, vp, vp]
-        L.npb_sampler_destroy.argtypes = [vp, ci]
-    if hasattr(L, "npb_set_maintenance_summary"):     # ABI 154: the event log folded into a per-plant work-order summary
-        L.npb_set_maintenance_summary.argtypes = [vp, ctypes.POINTER(NpbMaintSummaryDesc)]
-        L.npb_maint_summary_check.argtypes = [ctypes.POINTER(NpbMaintSummaryDesc), ci, ci]
-        L.npb_maint_summary_check.restype = ctypes.c_char_p
-        L.npb_maint_summary_fold.argtypes = [vp, vp]
-        L.npb_maint_summary_clear.argtypes = [vp, vp, vp]
-    if hasattr(L, "npb_set_episode_streams"):     # (ABI 154 still) each plant's noise and power profile restart with its episode
-        L.npb_set_episode_streams.argtypes = [vp, ctypes.POINTER(NpbEpisodeStreamsDesc), vp]
-        L.npb_episode_streams_check.argtypes = [ctypes.POINTER(NpbEpisodeStreamsDesc), ci, ci]
-        L.npb_episode_streams_check.restype = ctypes.c_char_p
-        L.npb_profile_get_positions.argtypes = [vp, vp, vp, vp]
-    if hasattr(L, "npb_set_episode_records"):     # a device-side log of finished episodes, with their work-order summary
-        L.npb_set_episode_records.argtypes = [vp, ctypes.POINTER(NpbEpisodeRecordsDesc)]
-        L.npb_episode_records_check.argtypes = [ctypes.POINTER(NpbEpisodeRecordsDesc), ci, ci]
-        L.npb_episode_records_check.restype = ctypes.c_char_p
-    if hasattr(L, "npb_set_column_stats"):     # per-plant column statistics folded behind every step, and their copy into the episode records
-        L.npb_set_column_stats.argtypes = [vp, ctypes.POINTER(NpbColumnStatsDesc)]
-        L.npb_column_stats_check.argtypes = [ctypes.POINTER(NpbColumnStatsDesc), ci]
-        L.npb_column_stats_check.restype = ctypes.c_char_p
-        L.npb_column_stats_fold.argtypes = [vp, vp]
-        L.npb_column_stats_clear.argtypes = [vp, vp, vp]
-        L.npb_set_episode_record_stats.argtypes = [vp, ctypes.POINTER(NpbEpisodeRecordStatsDesc)]
-    if hasattr(L, "npb_set_task"):     # the caller's reward terms and termination rules, formed behind every step
-        L.npb_set_task.argtypes = [vp, ctypes.POINTER(NpbTaskDesc)]
-        L.npb_task_check.argtypes = [ctypes.POINTER(NpbTaskDesc), ci]
-        L.npb_task_check.restype = ctypes.c_char_p
-        L.npb_task_clear.argtypes = [vp, vp, vp]
-        L.npb_task_get_state.argtypes = [vp, vp, vp, vp, vp]
-        L.npb_task_set_state.argtypes = [vp, vp, vp, vp, vp]
-        L.npb_set_episode_record_task.argtypes = [vp, vp]
-    if hasattr(L, "npb_set_features"):     # the caller's policy inputs: a stack of transformed frames kept behind every step
-        L.npb_set_features.argtypes = [vp, ctypes.POINTER(NpbFeaturesDesc)]
-        L.npb_features_check.argtypes = [ctypes.POINTER(NpbFeaturesDesc), ci]
-        L.npb_features_check.restype = ctypes.c_char_p
-        L.npb_features_prime.argtypes = [vp, vp]
-        L.npb_features_clear.argtypes = [vp, vp, vp]
-        L.npb_features_get_state.argtypes = [vp, vp, vp, vp]
-        L.npb_features_set_state.argtypes = [vp, vp, vp, vp]
-    if hasattr(L, "npb_set_controls"):     # the caller's policy outputs: decoded in front of every step
-        L.npb_set_controls.argtypes = [vp, ctypes.POINTER(NpbControlsDesc)]
-        L.npb_controls_check.argtypes = [ctypes.POINTER(NpbControlsDesc), ci, ci]
-        L.npb_controls_check.restype = ctypes.c_char_p
-        L.npb_controls_clear.argtypes = [vp, vp, vp]
-        L.npb_controls_get_state.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-        L.npb_controls_set_state.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    if hasattr(L, "npb_set_rollout"):     # the rollout: trajectories recorded on the device, and their GAE advantages
-        L.npb_set_rollout.argtypes = [vp, ctypes.POINTER(NpbRolloutDesc)]
-        L.npb_rollout_check.argtypes = [ctypes.POINTER(NpbRolloutDesc), ci, ci, ci]
-        L.npb_rollout_check.restype = ctypes.c_char_p
-        L.npb_rollout_begin.argtypes = [vp, vp]
-        L.npb_rollout_steps.argtypes = [vp]
-        L.npb_rollout_cut.argtypes = [vp, vp, vp]
-        L.npb_rollout_advantages.argtypes = [vp, ctypes.POINTER(NpbRolloutAdvantagesDesc), vp]
-    if hasattr(L, "npb_set_normalizer"):     # running observation and reward normalisation, folded behind every step
-        L.npb_set_normalizer.argtypes = [vp, ctypes.POINTER(NpbNormalizerDesc)]
-        L.npb_normalizer_check.argtypes = [ctypes.POINTER(NpbNormalizerDesc), ci, ctypes.POINTER(NpbFeaturesDesc)]
-        L.npb_normalizer_check.restype = ctypes.c_char_p
-        L.npb_normalizer_training.argtypes = [vp, ci]
-        L.npb_normalizer_clear.argtypes = [vp, vp, vp]
-        L.npb_normalizer_get_state.argtypes = [vp] * 9
-        L.npb_normalizer_set_state.argtypes = [vp] * 9
-    if hasattr(L, "npb_set_policy"):     # the policy on the device: actor, critic, the Gaussian draw, K steps in one call
-        L.npb_set_policy.argtypes = [vp, ctypes.POINTER(NpbPolicyDesc)]
-        L.npb_policy_check.argtypes = [ctypes.POINTER(NpbPolicyDesc), ci, ci, ci]
-        L.npb_policy_check.restype = ctypes.c_char_p
-        L.npb_policy_count.argtypes = [ctypes.POINTER(NpbPolicyDesc), ci, ci]
-        L.npb_policy_count.restype = ctypes.c_int64
-        L.npb_policy_load.argtypes = [vp, vp, ci, vp]
-        L.npb_policy_values.argtypes = [vp, vp, ci, ci, vp, vp]
-        L.npb_policy_noise.argtypes = [vp, ctypes.c_uint64, vp, vp, vp]
-        L.npb_policy_get_state.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-        L.npb_policy_set_state.argtypes = [vp, ctypes.c_uint64]
-        L.npb_collect.argtypes = [vp, ci] + [vp] * 6
-    if hasattr(L, "npb_policy_grad"):     # training the policy: the PPO loss, its gradient and the Adam step
-        cd = ctypes.c_double
-        L.npb_ppo_check.argtypes = [ctypes.POINTER(NpbPpoDesc), ci, ci]
-        L.npb_ppo_check.restype = ctypes.c_char_p
-        L.npb_policy_grad.argtypes = [vp, ctypes.POINTER(NpbPpoDesc), vp]
-        L.npb_policy_adam.argtypes = [vp, cd, cd, cd, cd, vp]
-        L.npb_policy_update.argtypes = [vp, ctypes.POINTER(NpbPpoDesc), cd, cd, cd, cd, vp]
-        L.npb_policy_get_grad.argtypes = [vp, vp, vp]
-        L.npb_policy_get_stats.argtypes = [vp, vp, vp]
-        L.npb_policy_get_theta.argtypes = [vp, vp, vp]
-        L.npb_policy_optimizer_get_state.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_uint64), vp]
-        L.npb_policy_optimizer_set_state.argtypes = [vp, vp, vp, ctypes.c_uint64, vp]
-    if hasattr(L, "npb_rollout_minibatch"):     # pinned moments, the keyed permutation and the minibatch gather over a rollout
-        L.npb_rollout_moments.argtypes = [vp, ctypes.POINTER(NpbMomentsDesc), vp]
-        L.npb_rollout_permutation.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64, ctypes.c_int64, vp, vp]
-        L.npb_rollout_minibatch.argtypes = [vp, ctypes.POINTER(NpbMinibatchDesc), vp]
-        L.npb_minibatch_check.argtypes = [ctypes.POINTER(NpbMinibatchDesc), ci, ci, ci, ci, ci]
-        L.npb_minibatch_check.restype = ctypes.c_char_p
-    if hasattr(L, "npb_set_event_windows"):     # state windows around events, captured behind every step
-        L.npb_set_event_windows.argtypes = [vp, ctypes.POINTER(NpbEventWindowsDesc)]
-        L.npb_event_windows_check.argtypes = [ctypes.POINTER(NpbEventWindowsDesc), ci, ci]
-        L.npb_event_windows_check.restype = ctypes.c_char_p
-        L.npb_event_windows_clear.argtypes = [vp, vp, vp]
-        L.npb_event_windows_bytes.argtypes = [ctypes.POINTER(NpbEventWindowsDesc), ci]
-        L.npb_event_windows_bytes.restype = ctypes.c_size_t
     if L.npb_num_f64() != SCHEMA.total_f64 or L.npb_num_i32() != SCHEMA.total_i32:
         raise NpbError("libnpb.so was built against a different include/npb_fields.h (%d/%d vs %d/%d): rebuild"
                        % (L.npb_num_f64(), L.npb_num_i32(), SCHEMA.total_f64, SCHEMA.total_i32))

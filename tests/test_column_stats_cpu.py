@@ -5,15 +5,13 @@ refusal; the request builder of the binding refuses unknown names, indices and s
 numpy statement of what the device folds, on hand-made series: the NaN rule, a limit crossed twice, the empty values, the moments.
 No compute calls."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
+import abi_support as abi
+from nuclear_sim_amd import _lib
+
 ENTRY_POINTS = ("npb_set_column_stats", "npb_column_stats_check", "npb_column_stats_fold", "npb_column_stats_clear", "npb_set_episode_record_stats")
 TABLES = ("min", "max", "sum", "sumsq", "last", "first_beyond", "n_beyond", "n_samples")
 STATS_FIELDS = ("n_fields", "kinds", "slots", "n_sources", "sources", "direction", "limit") + TABLES
@@ -22,52 +20,29 @@ RECORD_FIELDS = TABLES + ("clear",)
 
 @pytest.fixture(scope="module")
 def L():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
-    from nuclear_sim_amd import _lib
-    return _lib.load()
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "npb.h")).read()
+    return abi.library()
 
 
 # ---------------------------------------------------------------------------------------------------------------- the ABI
 def test_header_declares_the_five_entry_points_and_keeps_the_version():
-    text = _header()
-    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
-    for s in ENTRY_POINTS:
-        assert s in declared, s
-    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) == 154
-    assert int(re.search(r"#define NPB_COLUMN_STATS_MAX (\d+)", text).group(1)) == 32
+    assert set(ENTRY_POINTS) <= set(abi.declared())
+    assert abi.define("NPB_VERSION") == 154
+    assert abi.define("NPB_COLUMN_STATS_MAX") == 32
 
 
 def test_library_exports_and_binding_declares_them(L):
-    from nuclear_sim_amd import _lib, colstats
-    raw = ctypes.CDLL(LIB)
-    for s in ENTRY_POINTS:
-        assert hasattr(raw, s), "libnpb.so does not export %s" % s
-        assert getattr(L, s).argtypes is not None, s
+    from nuclear_sim_amd import colstats
+    abi.check_entry_points(ENTRY_POINTS, [("npb_set_column_stats", None, None), ("npb_column_stats_fold", None, None),
+                                          ("npb_column_stats_clear", None, None, None), ("npb_set_episode_record_stats", None, None)])
     assert L.npb_version() == 154
-    assert L.npb_set_column_stats(None, None) == -1 and L.npb_column_stats_fold(None, None) == -1
-    assert L.npb_column_stats_clear(None, None, None) == -1 and L.npb_set_episode_record_stats(None, None) == -1
     assert _lib.COLUMN_STATS == colstats.STATS and _lib.COLUMN_STATS_MAX == colstats.MAX_COLUMNS == 32
 
 
-def test_the_binding_lays_both_descriptors_out_as_the_compiler_does(tmp_path):
-    from nuclear_sim_amd import _lib
-    assert tuple(f[0] for f in _lib.NpbColumnStatsDesc._fields_) == STATS_FIELDS
-    assert tuple(f[0] for f in _lib.NpbEpisodeRecordStatsDesc._fields_) == RECORD_FIELDS
-    lines = ['  printf("%zu\\n", sizeof(npb_column_stats_desc_t));\n']
-    lines += ['  printf("%%zu\\n", offsetof(npb_column_stats_desc_t, %s));\n' % f for f in STATS_FIELDS]
-    lines += ['  printf("%zu\\n", sizeof(npb_episode_record_stats_desc_t));\n']
-    lines += ['  printf("%%zu\\n", offsetof(npb_episode_record_stats_desc_t, %s));\n' % f for f in RECORD_FIELDS]
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "npb.h"\nint main(void) {\n' + "".join(lines) + "  return 0;\n}\n")
-    exe = tmp_path / "probe"
-    subprocess.check_call([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+def test_the_binding_lays_both_descriptors_out_as_the_compiler_does():
     A, B = _lib.NpbColumnStatsDesc, _lib.NpbEpisodeRecordStatsDesc
+    assert tuple(f[0] for f in A._fields_) == STATS_FIELDS
+    assert tuple(f[0] for f in B._fields_) == RECORD_FIELDS
+    got = abi.probe({"npb_column_stats_desc_t": A, "npb_episode_record_stats_desc_t": B})[0]
     k = 1 + len(STATS_FIELDS)
     assert got[0] == ctypes.sizeof(A) and got[1:k] == [getattr(A, f).offset for f in STATS_FIELDS]
     assert got[k] == ctypes.sizeof(B) and got[k + 1:] == [getattr(B, f).offset for f in RECORD_FIELDS]
@@ -75,7 +50,6 @@ def test_the_binding_lays_both_descriptors_out_as_the_compiler_does(tmp_path):
 
 def _good(n_fields=2, n_sources=2, limits=((0, -1, 50.0), (3, 1, 1000.0))):
     """a descriptor the check accepts (it reads no device memory: the addresses only have to be aligned), and what keeps it alive"""
-    from nuclear_sim_amd import _lib
     from nuclear_sim_amd.schema import SCHEMA
     d = _lib.NpbColumnStatsDesc()
     members = [SCHEMA.slot("pump.oil_level", 0), SCHEMA.slot("maint.maintenance_actions_performed")][:n_fields]
@@ -151,7 +125,6 @@ def test_check_names_every_refusal(L):
 
 # ---------------------------------------------------------------------------------------------------------------- the request builder
 def test_request_builder_orders_members_first_and_maps_the_limits():
-    from nuclear_sim_amd import _lib
     from nuclear_sim_amd.env import INFO_COLUMNS
     from nuclear_sim_amd.schema import SCHEMA
     req = _lib.column_stats_request(["reward", ("pump.oil_level", 1), ("info", "electrical_power"), "maint.maintenance_actions_performed", ("obs", 3)],
@@ -179,7 +152,6 @@ def test_request_builder_orders_members_first_and_maps_the_limits():
     (["reward"] * 33, None, ("min",), "1 to 32 columns"),
 ])
 def test_request_builder_refuses(columns, limits, stats, word):
-    from nuclear_sim_amd import _lib
     with pytest.raises(ValueError) as e:
         _lib.column_stats_request(columns, limits, stats)
     assert word in str(e.value), str(e.value)

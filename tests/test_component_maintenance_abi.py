@@ -2,30 +2,21 @@
 exported by libnpb.so and bound; a NULL handle is refused; the header's component catalog is the binding's and the library's; an unknown
 name and a handler that is not offered are refused on the host, each with its own message, before a device is looked for;
 nuclear_sim_amd.maintlog renders the fourth record kind and the other three as before.  No compute calls."""
-import ctypes
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_support as abi
+from nuclear_sim_amd import _lib
+
 from component_maintenance_golden import ACTIONS, KINDS, UNITS
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
-    return LIB
 
 
 def _header_catalog():
     """(kind, type string) per X(KIND, ID, "name") line of NPB_COMPONENT_ACTIONS in include/npb_maint.h"""
-    text = open(os.path.join(ROOT, "include", "npb_maint.h")).read()
+    text = abi.header_text("npb_maint.h")
     body = text[text.index("#define NPB_COMPONENT_ACTIONS(X)"):]
     body = body[:body.index("enum {")]
     kinds = {"SG": "steam_generator", "SGSYS": "steam_generator_system", "COND": "condenser", "EJECTOR": "ejector"}
@@ -33,27 +24,25 @@ def _header_catalog():
 
 
 def test_header_declares_the_entry_point_and_the_catalog():
-    text = open(os.path.join(ROOT, "include", "npb.h")).read()
-    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
+    text, declared = abi.header_text(), set(abi.declared())
     assert {"npb_perform_component_maintenance", "npb_component_num_actions", "npb_component_action_name", "npb_component_action_kind",
             "npb_perform_maintenance"} <= declared
-    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) >= 148
+    assert abi.define("NPB_VERSION") >= 148
     m = re.search(r"npb_perform_component_maintenance\(([^)]*)\)", text[text.index("NPB_API int npb_perform_component_maintenance"):])
     args = [a.strip() for a in m.group(1).split(",")]
     assert args == ["NpbHandle *h", "const int32_t *action", "const int32_t *unit", "const int32_t *option", "const double *amount",
                     "uint8_t *success", "void *stream"], args
     maint, catalog = _header_catalog()
     assert re.search(r"NPB_MAINT_EVENT_OPERATOR_COMPONENT\s*=\s*3\b", maint) and re.search(r"NPB_MAINT_EVENT_OPERATOR\s*=\s*2\b", maint)
-    assert int(re.search(r"#define NPB_COMPONENT_NACT (\d+)", maint).group(1)) == len(catalog) == len(ACTIONS)
+    assert abi.define("NPB_COMPONENT_NACT", "npb_maint.h") == len(catalog) == len(ACTIONS)
     assert catalog == list(ACTIONS)
 
 
-def test_host_catalog_is_the_headers_and_the_librarys(built_lib):
-    from nuclear_sim_amd import _lib
+def test_host_catalog_is_the_headers_and_the_librarys():
     _maint, catalog = _header_catalog()
     assert list(_lib.COMPONENT_ACTIONS) == catalog
     assert _lib.COMPONENT_KINDS == KINDS and _lib.COMPONENT_UNITS == UNITS
-    L = _lib.load()          # load() itself refuses a library whose catalog differs
+    L = abi.library()          # load() itself refuses a library whose catalog differs
     n = L.npb_component_num_actions()
     assert n == len(catalog)
     assert [(L.npb_component_kind_name(L.npb_component_action_kind(a)).decode(), L.npb_component_action_name(a).decode()) for a in range(n)] == catalog
@@ -63,26 +52,20 @@ def test_host_catalog_is_the_headers_and_the_librarys(built_lib):
     assert [k for k, _ in catalog] == sorted((k for k, _ in catalog), key=KINDS.index) and len(set(catalog)) == len(catalog)
 
 
-def test_library_exports_and_binding_declares_it(built_lib):
-    lib = ctypes.CDLL(built_lib)
-    assert hasattr(lib, "npb_perform_component_maintenance"), "libnpb.so does not export npb_perform_component_maintenance"
-    assert hasattr(lib, "npb_perform_maintenance")
-    assert lib.npb_version() >= 148
-    from nuclear_sim_amd import _lib
-    L = _lib.load()
+def test_library_exports_and_binding_declares_it():
+    abi.check_exported(["npb_perform_component_maintenance", "npb_perform_maintenance"])
+    L = abi.library()
+    assert L.npb_version() >= 148
     assert L.npb_perform_component_maintenance.argtypes is not None and len(L.npb_perform_component_maintenance.argtypes) == 7
     assert len(L.npb_perform_maintenance.argtypes) == 7
 
 
-def test_null_handle_is_refused(built_lib):
-    from nuclear_sim_amd import _lib
-    L = _lib.load()
-    assert L.npb_perform_component_maintenance(None, None, None, None, None, None, None) == -1
+def test_null_handle_is_refused():
+    abi.check_null_refused([("npb_perform_component_maintenance", None, None, None, None, None, None, None)])
 
 
 def test_unknown_and_refused_names_are_told_apart_before_any_device_work():
     """on an object that has no handle, no library and no device behind it"""
-    from nuclear_sim_amd import _lib
     from nuclear_sim_amd.env import BatchedPlantEnv
     env = object.__new__(BatchedPlantEnv)
     call = BatchedPlantEnv.perform_component_maintenance
@@ -108,9 +91,9 @@ def test_unknown_and_refused_names_are_told_apart_before_any_device_work():
     assert [_lib.cleaning_type_index(c) for c in (None, "chemical", "mechanical", "hydroblast", "replacement", "brush", 2)] == [0, 1, 2, 3, 4, 5, 2]
 
 
-def test_maintlog_renders_component_records_and_leaves_the_others(built_lib):
-    from nuclear_sim_amd import _lib, maintlog
-    L = _lib.load()
+def test_maintlog_renders_component_records_and_leaves_the_others():
+    from nuclear_sim_amd import maintlog
+    L = abi.library()
     A, P = _lib.MAINT_ACTIONS, _lib.MAINT_PARAMS
     handlers = [int(L.npb_maint_action_has_handler(a)) for a in range(len(A))]
     assert maintlog.OPERATOR_COMPONENT == 3 and maintlog.EVENT_TYPES[3] == "operator_component_maintenance"

@@ -5,87 +5,56 @@ lists.  No compute calls.
 
 The header keeps NPB_VERSION where the suites of the entry-point groups before this one pin it: the new entry points are detected by name."""
 import ctypes
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
+import abi_support as abi
+from nuclear_sim_amd import _lib
+
 ENTRY_POINTS = ("npb_set_controls", "npb_controls_check", "npb_controls_clear", "npb_controls_get_state", "npb_controls_set_state")
-STRUCTS = {"npb_control_axis_t": "NpbControlAxis", "npb_controls_desc_t": "NpbControlsDesc"}
+STRUCTS = {"npb_control_axis_t": _lib.NpbControlAxis, "npb_controls_desc_t": _lib.NpbControlsDesc}
 C_NAME = {"input": "in"}      # `in` is no Python attribute name
 A16 = 0x7000       # "device addresses" the check only looks at: never dereferenced
 NAN, INF = float("nan"), float("inf")
 CONSTANT, EXTERNAL = 0, 2      # NPB_HEAT_*
 
 
-@pytest.fixture(scope="module")
-def L():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
-    from nuclear_sim_amd import _lib
-    return _lib.load()
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "npb.h")).read()
-
-
 def test_header_declares_the_entry_points_the_maxima_and_the_rules_of_the_road():
-    text = _header()
-    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
-    for s in ENTRY_POINTS:
-        assert s in declared, s
-    assert int(re.search(r"#define NPB_CONTROLS_AXES_MAX (\d+)", text).group(1)) == 8
-    assert int(re.search(r"#define NPB_CONTROLS_INTERVAL_MAX (\d+)", text).group(1)) == 64
-    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) == 154
+    text = abi.header_text()
+    assert set(ENTRY_POINTS) <= set(abi.declared())
+    assert abi.define("NPB_CONTROLS_AXES_MAX") == 8
+    assert abi.define("NPB_CONTROLS_INTERVAL_MAX") == 64
+    assert abi.define("NPB_VERSION") == 154
     for words in ("every step rounded on its own", "fabs(y) == deadband stays", "npd_apply_control_actions", "the step kernel applies them behind the controls",
                   "cooldown cache watches the feedwater pumps' parameters", "where the new bits differ from the old", "the first step of a new episode starts a new hold",
                   "No half types", "Not here: a discrete action table"):
         assert words in text, words
 
 
-def test_library_exports_and_binding_declares_them(L):
-    raw = ctypes.CDLL(LIB)
-    for s in ENTRY_POINTS:
-        assert hasattr(raw, s), "libnpb.so does not export %s" % s
-        assert getattr(L, s).argtypes is not None, s
-    assert L.npb_set_controls(None, None) == -1 and L.npb_controls_clear(None, None, None) == -1
-    assert L.npb_controls_get_state(None, None, None, None, None, None, None) == -1
-    assert L.npb_controls_set_state(None, None, None, None, None, None, None) == -1
+def test_library_exports_and_binding_declares_them():
+    seven = [None] * 7
+    abi.check_entry_points(ENTRY_POINTS, [("npb_set_controls", None, None), ("npb_controls_clear", None, None, None),
+                                          ("npb_controls_get_state", *seven), ("npb_controls_set_state", *seven)])
 
 
-def test_the_binding_lays_the_descriptors_out_as_the_compiler_does(tmp_path):
-    from nuclear_sim_amd import _lib, controls
-    lines = []
-    for c_name, py_name in STRUCTS.items():
-        lines.append('  printf("%%zu\\n", sizeof(%s));\n' % c_name)
-        lines += ['  printf("%%zu\\n", offsetof(%s, %s));\n' % (c_name, C_NAME.get(f[0], f[0])) for f in getattr(_lib, py_name)._fields_]
+def test_the_binding_lays_the_descriptors_out_as_the_compiler_does():
+    from nuclear_sim_amd import controls
     # the initialiser macros name the members kind, target
-    lines.append("  { npb_control_axis_t r = { NPB_CONTROL_RATE(NPB_ACTUATOR_BORON) }, t = { NPB_CONTROL_TARGET(NPB_ACTUATOR_VALVE) },\n"
-                 "      c = { NPB_CONTROL_COLUMN(NPB_CONTROL_INPUT_COOLING_WATER_TEMP) };\n"
-                 '    printf("%d\\n%d\\n%d\\n%d\\n%d\\n%d\\n", r.kind, r.target, t.kind, t.target, c.kind, c.target); }\n')
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "npb.h"\nint main(void) {\n' + "".join(lines) + "  return 0;\n}\n")
-    exe = tmp_path / "probe"
-    subprocess.check_call([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    want = []
-    for py_name in STRUCTS.values():
-        S = getattr(_lib, py_name)
-        want += [ctypes.sizeof(S)] + [getattr(S, f[0]).offset for f in S._fields_]
-    assert got == want + [_lib.CONTROL_KINDS["rate"], _lib.CONTROL_ACTUATORS["boron"], _lib.CONTROL_KINDS["target"], _lib.CONTROL_ACTUATORS["valve"],
-                          _lib.CONTROL_KINDS["column"], _lib.CONTROL_INPUTS["cooling_water_temp"]]
-    text = _header()
+    axes = ["((npb_control_axis_t){ %s })" % m for m in ("NPB_CONTROL_RATE(NPB_ACTUATOR_BORON)", "NPB_CONTROL_TARGET(NPB_ACTUATOR_VALVE)",
+                                                         "NPB_CONTROL_COLUMN(NPB_CONTROL_INPUT_COOLING_WATER_TEMP)")]
+    got, values = abi.probe(STRUCTS, [a + member for a in axes for member in (".kind", ".target")], rename=C_NAME)
+    assert got == abi.layout(STRUCTS)
+    assert values == [_lib.CONTROL_KINDS["rate"], _lib.CONTROL_ACTUATORS["boron"], _lib.CONTROL_KINDS["target"], _lib.CONTROL_ACTUATORS["valve"],
+                      _lib.CONTROL_KINDS["column"], _lib.CONTROL_INPUTS["cooling_water_temp"]]
+    text = abi.header_text()
     assert {name: int(re.search(r"NPB_CONTROL_KIND_%s = (\d+)" % name.upper(), text).group(1)) for name in _lib.CONTROL_KINDS} == _lib.CONTROL_KINDS
     assert {name: int(re.search(r"NPB_ACTUATOR_%s = (\d+)" % name.upper(), text).group(1)) for name in _lib.CONTROL_ACTUATORS} == _lib.CONTROL_ACTUATORS
     assert {name: int(re.search(r"NPB_CONTROL_INPUT_%s = (\d+)" % name.upper(), text).group(1)) for name in _lib.CONTROL_INPUTS} == _lib.CONTROL_INPUTS
     assert {"float32": int(re.search(r"NPB_CONTROLS_F32 = (\d+)", text).group(1)),
             "float64": int(re.search(r"NPB_CONTROLS_F64 = (\d+)", text).group(1))} == _lib.CONTROL_DTYPES
     assert (_lib.CONTROLS_AXES_MAX, _lib.CONTROLS_INTERVAL_MAX) == (controls.AXES_MAX, controls.INTERVAL_MAX) == (8, 64)
-    assert _lib.HEAT_EXTERNAL == int(re.search(r"NPB_HEAT_EXTERNAL = (\d+)", open(os.path.join(ROOT, "include", "npb_params.h")).read()).group(1))
+    assert _lib.HEAT_EXTERNAL == int(re.search(r"NPB_HEAT_EXTERNAL = (\d+)", abi.header_text("npb_params.h")).group(1))
 
 
 class _Desc:
@@ -109,45 +78,30 @@ class _Desc:
         self.d.input, self.d.held, self.d.prev = A16 + 4, A16 + 8, A16 + 16
 
 
-def _why(L, D, n=70, heat=CONSTANT):
-    r = L.npb_controls_check(ctypes.byref(D.d), n, heat)
-    return None if r is None else r.decode()
+def _why(D, n=70, heat=CONSTANT):
+    return abi.why(abi.library().npb_controls_check, ctypes.byref(D.d), n, heat)
 
 
-def test_the_check_accepts_valid_controls_and_null(L):
-    assert _why(L, _Desc()) is None
-    assert L.npb_controls_check(None, 70, CONSTANT) is None
+def test_the_check_accepts_valid_controls_and_null():
+    assert _why(_Desc()) is None
+    assert abi.library().npb_controls_check(None, 70, CONSTANT) is None
     D = _Desc(); D.d.n_axes = 1; D.d.interval = 1
-    assert _why(L, D) is None
+    assert _why(D) is None
     D = _Desc(); D.axes[6].kind = D.axes[7].kind = 3; D.axes[7].target = 99; D.d.n_axes = 8      # two VALUE axes: the target is not read
-    assert _why(L, D) is None
+    assert _why(D) is None
     D = _Desc(); D.d.interval = 64
-    assert _why(L, D) is None
+    assert _why(D) is None
     D = _Desc(); D.d.in_type, D.d.input = 1, A16 + 8                   # double
-    assert _why(L, D) is None
+    assert _why(D) is None
     D = _Desc(); D.axes[0].lo = D.axes[0].hi = 0.5; D.axes[1].lo = -INF; D.axes[0].deadband = 0.0      # lo == hi, an open clip
-    assert _why(L, D) is None
+    assert _why(D) is None
     D = _Desc(); D.d.n_axes = 4                                        # no POWER_SETPOINT axis: the external heat source is fine
-    assert _why(L, D, heat=EXTERNAL) is None
+    assert _why(D, heat=EXTERNAL) is None
     D = _Desc(); D.axes[4].target = 1; D.d.n_axes = 5                  # COOLING_WATER_TEMP alone under the external heat source
-    assert _why(L, D, heat=EXTERNAL) is None
+    assert _why(D, heat=EXTERNAL) is None
 
 
-def _set(path, value):
-    def change(D):
-        obj = D
-        *head, last = path
-        for name in head:
-            obj = obj[name] if isinstance(name, int) else getattr(obj, name)
-        setattr(obj, last, value)
-    return change
-
-
-def _both(*changes):
-    def change(D):
-        for c in changes:
-            c(D)
-    return change
+_set, _both = abi.set_path, abi.both
 
 
 REFUSALS = [
@@ -191,17 +145,11 @@ REFUSALS = [
 
 
 @pytest.mark.parametrize("what, change, reason", REFUSALS, ids=[r[0] for r in REFUSALS])
-def test_the_check_names_every_refusal(L, what, change, reason):
-    D = _Desc()
-    if change is None:
-        why = _why(L, D, n=0)
-    else:
-        change(D)
-        why = _why(L, D)
-    assert why is not None and why.startswith("npb_set_controls: ") and reason in why, (what, why)
+def test_the_check_names_every_refusal(what, change, reason):
+    abi.check_refusal(_Desc, _why, "npb_set_controls: ", what, change, reason)
 
 
-def test_a_power_setpoint_axis_is_refused_under_the_external_heat_source(L):
-    why = _why(L, _Desc(), heat=EXTERNAL)
+def test_a_power_setpoint_axis_is_refused_under_the_external_heat_source():
+    why = _why(_Desc(), heat=EXTERNAL)
     assert why is not None and "a POWER_SETPOINT axis under NPB_HEAT_EXTERNAL" in why
-    assert _why(L, _Desc(), heat=1) is None      # the reactor heat source takes the setpoint
+    assert _why(_Desc(), heat=1) is None      # the reactor heat source takes the setpoint

@@ -1,57 +1,35 @@
 """CPU: the device noise entry points (npb_noise_seed, npb_noise_fill, npb_noise_get_state, npb_noise_set_state) are declared by
 include/npb.h, exported by libnpb.so and declared by the binding, and refuse a NULL handle; the binding's noise_generator keyword
 refuses an unknown generator.  No compute calls."""
-import ctypes
-import os
-import re
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
+import abi_support as abi
+
 NOISE_ENTRY_POINTS = ("npb_noise_seed", "npb_noise_fill", "npb_noise_get_state", "npb_noise_set_state")
 
 
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
-    return LIB
-
-
 def test_header_declares_the_noise_entry_points():
-    text = open(os.path.join(ROOT, "include", "npb.h")).read()
-    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
-    for s in NOISE_ENTRY_POINTS:
-        assert s in declared, s
-    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) >= 145
+    assert set(NOISE_ENTRY_POINTS) <= set(abi.declared())
+    assert abi.define("NPB_VERSION") >= 145
 
 
-def test_library_exports_the_noise_entry_points(built_lib):
-    lib = ctypes.CDLL(built_lib)
-    for s in NOISE_ENTRY_POINTS:
-        assert hasattr(lib, s), "libnpb.so does not export %s" % s
-    assert lib.npb_version() >= 145
+def test_library_exports_the_noise_entry_points():
+    abi.check_exported(NOISE_ENTRY_POINTS)
+    assert abi.library().npb_version() >= 145
 
 
-def test_binding_declares_the_noise_entry_points(built_lib):
-    from nuclear_sim_amd import _lib
-    L = _lib.load()
-    for s in NOISE_ENTRY_POINTS:
-        assert getattr(L, s).argtypes is not None, s
+def test_binding_declares_the_noise_entry_points():
+    abi.check_bound(NOISE_ENTRY_POINTS)
 
 
-def test_null_handle_is_refused(built_lib):
-    from nuclear_sim_amd import _lib
-    L = _lib.load()
-    assert L.npb_noise_seed(None, None, None) == -1
-    assert L.npb_noise_fill(None, 1, None, None) == -1
-    assert L.npb_noise_get_state(None, None, None, None, None, None) == -1
-    assert L.npb_noise_set_state(None, None, None, None, None, None) == -1
+def test_null_handle_is_refused():
+    abi.check_null_refused([("npb_noise_seed", None, None, None), ("npb_noise_fill", None, 1, None, None),
+                            ("npb_noise_get_state", None, None, None, None, None, None),
+                            ("npb_noise_set_state", None, None, None, None, None, None)])
 
 
-def test_unknown_noise_generator_is_refused(built_lib):
+def test_unknown_noise_generator_is_refused():
     from nuclear_sim_amd.env import BatchedPlantEnv
+    abi.library()
     with pytest.raises(ValueError):
         BatchedPlantEnv(4, noise_enabled=True, noise_generator="gpu")

@@ -6,65 +6,38 @@ checks come before any device work.  No compute calls.
 The header keeps NPB_VERSION where the suites of the two entry-point groups before this one pin it (== 154): the new entry points are
 detected by name, as npb_set_episode_streams is."""
 import ctypes
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
+import abi_support as abi
+from nuclear_sim_amd import _lib
+
 ENTRY_POINTS = ("npb_set_episode_records", "npb_episode_records_check")
 FIELDS = ("capacity", "clear_summary", "plant", "episode", "start", "length", "flags", "trip_flags", "step", "ret", "end_time", "final_obs",
           "first_created", "first_completed", "n_created", "n_completed", "cursor")
 
 
-@pytest.fixture(scope="module")
-def L():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
-    from nuclear_sim_amd import _lib
-    return _lib.load()
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "npb.h")).read()
-
-
 def test_header_declares_the_entry_points_the_descriptor_and_the_abandoned_rule():
-    text = _header()
-    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
-    for s in ENTRY_POINTS:
-        assert s in declared, s
+    text = abi.header_text()
+    assert set(ENTRY_POINTS) <= set(abi.declared())
     body = re.search(r"typedef struct npb_episode_records_desc_t \{(.*?)\} npb_episode_records_desc_t;", text, flags=re.S).group(1)
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     names = [n for decl in body.split(";") for n in re.findall(r"\*?\s*(\w+)\s*(?:,|$)", decl.strip().split(" ", 1)[-1])]
     assert tuple(names) == FIELDS
     assert "ABANDONS" in text and "writes NO record" in text
-    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) >= 154
+    assert abi.define("NPB_VERSION") >= 154
 
 
-def test_library_exports_and_binding_declares_them(L):
-    raw = ctypes.CDLL(LIB)
-    for s in ENTRY_POINTS:
-        assert hasattr(raw, s), "libnpb.so does not export %s" % s
-        assert getattr(L, s).argtypes is not None, s
-    assert L.npb_version() == int(re.search(r"#define NPB_VERSION (\d+)", _header()).group(1))
-    assert L.npb_set_episode_records(None, None) == -1
+def test_library_exports_and_binding_declares_them():
+    abi.check_entry_points(ENTRY_POINTS, [("npb_set_episode_records", None, None)])
+    assert abi.library().npb_version() == abi.define("NPB_VERSION")
 
 
-def test_the_binding_lays_the_descriptor_out_as_the_compiler_does(tmp_path):
-    from nuclear_sim_amd import _lib
-    assert tuple(f[0] for f in _lib.NpbEpisodeRecordsDesc._fields_) == FIELDS
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "npb.h"\nint main(void) {\n'
-                   '  printf("%zu\\n", sizeof(npb_episode_records_desc_t));\n'
-                   + "".join('  printf("%%zu\\n", offsetof(npb_episode_records_desc_t, %s));\n' % f for f in FIELDS)
-                   + "  return 0;\n}\n")
-    exe = tmp_path / "probe"
-    subprocess.check_call([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+def test_the_binding_lays_the_descriptor_out_as_the_compiler_does():
     D = _lib.NpbEpisodeRecordsDesc
+    assert tuple(f[0] for f in D._fields_) == FIELDS
+    got = abi.probe({"npb_episode_records_desc_t": D})[0]
     assert got[0] == ctypes.sizeof(D) == 8 + 15 * 8
     assert got[1:] == [getattr(D, f).offset for f in FIELDS]
     assert [np_type().itemsize for _, np_type in _lib.EPISODE_RECORD_COLUMNS] == [4, 4, 4, 4, 4, 4, 4, 8, 8]
@@ -73,7 +46,6 @@ def test_the_binding_lays_the_descriptor_out_as_the_compiler_does(tmp_path):
 
 def _desc(summary=False, **over):
     """a descriptor whose columns are made-up, aligned addresses: the check reads no memory"""
-    from nuclear_sim_amd import _lib
     d = _lib.NpbEpisodeRecordsDesc()
     d.capacity, d.clear_summary = 64, 0
     for k, name in enumerate(FIELDS[2:11]):
@@ -86,11 +58,12 @@ def _desc(summary=False, **over):
     return d
 
 
-def test_the_check_accepts_a_valid_descriptor_and_names_every_refusal(L):
+def test_the_check_accepts_a_valid_descriptor_and_names_every_refusal():
+    L = abi.library()
+
     def why(d, autoreset=1, keys=0):
-        m = L.npb_episode_records_check(ctypes.byref(d), autoreset, keys)
-        return None if m is None else m.decode()
-    assert L.npb_episode_records_check(None, 0, 0) is None      # NULL turns the records off
+        return abi.why(L.npb_episode_records_check, ctypes.byref(d), autoreset, keys)
+    assert L.npb_episode_records_check(None, 0, 0) is None     # NULL turns the records off
     assert why(_desc()) is None and why(_desc(final_obs=0x50000)) is None and why(_desc(capacity=1)) is None
     assert why(_desc(summary=True), keys=3) is None and why(_desc(summary=True, clear_summary=1), keys=1) is None
     assert why(_desc(clear_summary=1), keys=2) is None          # clearing without copying

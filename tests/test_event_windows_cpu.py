@@ -4,15 +4,13 @@ library's own check, which needs no handle and reads no device memory, accepts a
 builder of the binding refuses unknown triggers and a work_order trigger without a summary before any device work; and eventwin.record,
 the numpy statement of what the device captures, on hand-made series.  No compute calls."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
+import abi_support as abi
+from nuclear_sim_amd import _lib
+
 ENTRY_POINTS = ("npb_set_event_windows", "npb_event_windows_check", "npb_event_windows_clear", "npb_event_windows_bytes")
 WORDS = ("plant", "episode", "trigger", "step", "n_pre", "n_post", "flags", "retriggers", "fired")
 RECORD = WORDS + ("time", "times", "values", "cursor")
@@ -23,64 +21,43 @@ BITS, INCREASE, BEYOND = 0, 1, 2
 
 @pytest.fixture(scope="module")
 def L():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
-    from nuclear_sim_amd import _lib
-    return _lib.load()
+    return abi.library()
 
 
 # ---------------------------------------------------------------------------------------------------------------- the ABI
 def test_header_declares_the_four_entry_points_and_keeps_the_version():
-    text = open(os.path.join(ROOT, "include", "npb.h")).read()
-    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
-    for s in ENTRY_POINTS:
-        assert s in declared, s
-    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) == 154
-    assert int(re.search(r"#define NPB_EVENT_WINDOW_COLS_MAX (\d+)", text).group(1)) == 16
-    assert int(re.search(r"#define NPB_EVENT_WINDOW_TRIGGERS_MAX (\d+)", text).group(1)) == 8
+    assert set(ENTRY_POINTS) <= set(abi.declared())
+    assert abi.define("NPB_VERSION") == 154
+    assert abi.define("NPB_EVENT_WINDOW_COLS_MAX") == 16
+    assert abi.define("NPB_EVENT_WINDOW_TRIGGERS_MAX") == 8
 
 
 def test_library_exports_and_binding_declares_them(L):
-    from nuclear_sim_amd import _lib, eventwin
-    raw = ctypes.CDLL(LIB)
-    for s in ENTRY_POINTS:
-        assert hasattr(raw, s), "libnpb.so does not export %s" % s
-        assert getattr(L, s).argtypes is not None, s
+    from nuclear_sim_amd import eventwin
+    abi.check_entry_points(ENTRY_POINTS, [("npb_set_event_windows", None, None), ("npb_event_windows_clear", None, None, None)])
     assert L.npb_version() == 154
-    assert L.npb_set_event_windows(None, None) == -1 and L.npb_event_windows_clear(None, None, None) == -1
     assert L.npb_event_windows_bytes(None, 70) == 0
     assert (_lib.EVENT_WINDOW_COLS_MAX, _lib.EVENT_WINDOW_TRIGGERS_MAX, _lib.EVENT_WINDOW_ROWS_MAX) == \
         (eventwin.MAX_COLUMNS, eventwin.MAX_TRIGGERS, eventwin.MAX_ROWS) == (16, 8, 1024)
     assert _lib.EVENT_WINDOW_WORDS == eventwin.WORD_COLUMNS and _lib.TRIGGER_MODES == {"bits_rise": BITS, "increase": INCREASE, "beyond": BEYOND}
 
 
-def test_the_binding_lays_the_descriptor_and_the_trigger_out_as_the_compiler_does(tmp_path):
-    from nuclear_sim_amd import _lib
-    assert tuple(f[0] for f in _lib.NpbEventWindowsDesc._fields_) == DESC_FIELDS
-    assert tuple(f[0] for f in _lib.NpbEventTrigger._fields_) == TRIGGER_FIELDS
-    lines = ['  printf("%zu\\n", sizeof(npb_event_windows_desc_t));\n']
-    lines += ['  printf("%%zu\\n", offsetof(npb_event_windows_desc_t, %s));\n' % f for f in DESC_FIELDS]
-    lines += ['  printf("%zu\\n", sizeof(npb_event_trigger_t));\n']
-    lines += ['  printf("%%zu\\n", offsetof(npb_event_trigger_t, %s));\n' % f for f in TRIGGER_FIELDS]
-    lines += ['  npb_event_trigger_t t[3] = {{0, 1, 2, {0}, NPB_TRIGGER_BITS_RISE(5)}, {0, 1, 2, {0}, NPB_TRIGGER_INCREASE}, {0, 1, 2, {0}, NPB_TRIGGER_BEYOND(-1, 2.5)}};\n']
-    lines += ['  for (int i = 0; i < 3; i++) printf("%d %u %d %d\\n", t[i].mode, t[i].mask, t[i].direction, (int)(t[i].limit * 2));\n']
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "npb.h"\nint main(void) {\n' + "".join(lines) + "  return 0;\n}\n")
-    exe = tmp_path / "probe"
-    subprocess.check_call([os.environ.get("CC", "gcc"), "-std=c99", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+def test_the_binding_lays_the_descriptor_and_the_trigger_out_as_the_compiler_does():
     A, B = _lib.NpbEventWindowsDesc, _lib.NpbEventTrigger
+    assert tuple(f[0] for f in A._fields_) == DESC_FIELDS
+    assert tuple(f[0] for f in B._fields_) == TRIGGER_FIELDS
+    triggers = ["((npb_event_trigger_t){0, 1, 2, {0}, %s})" % m for m in ("NPB_TRIGGER_BITS_RISE(5)", "NPB_TRIGGER_INCREASE", "NPB_TRIGGER_BEYOND(-1, 2.5)")]
+    got, values = abi.probe({"npb_event_windows_desc_t": A, "npb_event_trigger_t": B},
+                            [m % t for t in triggers for m in ("%s.mode", "%s.mask", "%s.direction", "(int)(%s.limit * 2)")], std="c99")
     k = 1 + len(DESC_FIELDS)
     assert got[0] == ctypes.sizeof(A) and got[1:k] == [getattr(A, f).offset for f in DESC_FIELDS]
-    j = k + 1 + len(TRIGGER_FIELDS)
-    assert got[k] == ctypes.sizeof(B) and got[k + 1:j] == [getattr(B, f).offset for f in TRIGGER_FIELDS]
-    assert got[j:] == [BITS, 5, 0, 0, INCREASE, 0, 0, 0, BEYOND, 0, -1, 5]      # the three initialiser macros
+    assert got[k] == ctypes.sizeof(B) and got[k + 1:] == [getattr(B, f).offset for f in TRIGGER_FIELDS]
+    assert values == [BITS, 5, 0, 0, INCREASE, 0, 0, 0, BEYOND, 0, -1, 5]      # the three initialiser macros
 
 
 def _good(n_fields=2, n_sources=2, pre=3, post=2, capacity=64):
     """a descriptor the check accepts (it reads no device memory: the addresses only have to be aligned), and what keeps it alive.
     Triggers: rising bits of an I32 source, an increase of an int32 member, a limit on a carried member, a limit on an F64 source"""
-    from nuclear_sim_amd import _lib
     from nuclear_sim_amd.schema import SCHEMA
     d = _lib.NpbEventWindowsDesc()
     members = [SCHEMA.slot("pump.oil_level", 0), SCHEMA.slot("maint.maintenance_actions_performed")][:n_fields]
@@ -181,7 +158,6 @@ def test_check_names_every_refusal(L):
 
 # ---------------------------------------------------------------------------------------------------------------- the request builder
 def test_request_builder_maps_the_triggers():
-    from nuclear_sim_amd import _lib
     from nuclear_sim_amd.env import INFO_COLUMNS
     from nuclear_sim_amd.schema import SCHEMA
     req = _lib.event_windows_request(["reward", ("pump.oil_level", 1), ("obs", 3)],
@@ -222,7 +198,6 @@ def test_request_builder_maps_the_triggers():
     (["reward"], [("done",)], 1000, 24, 0, "<= 1024"),
 ])
 def test_request_builder_refuses(columns, triggers, pre, post, keys, word):
-    from nuclear_sim_amd import _lib
     with pytest.raises(ValueError) as e:
         _lib.event_windows_request(columns, triggers, pre, post, summary_keys=keys)
     assert word in str(e.value), str(e.value)

@@ -5,77 +5,47 @@ lists.  No compute calls.
 
 The header keeps NPB_VERSION where the suites of the entry-point groups before this one pin it: the new entry points are detected by name."""
 import ctypes
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
+import abi_support as abi
+from nuclear_sim_amd import _lib
+
 ENTRY_POINTS = ("npb_set_features", "npb_features_check", "npb_features_prime", "npb_features_clear", "npb_features_get_state",
                 "npb_features_set_state")
-STRUCTS = {"npb_feature_column_t": "NpbFeatureColumn", "npb_features_desc_t": "NpbFeaturesDesc"}
+STRUCTS = {"npb_feature_column_t": _lib.NpbFeatureColumn, "npb_features_desc_t": _lib.NpbFeaturesDesc}
 A16 = 0x7000       # "device addresses" the check only looks at: never dereferenced
 F64, I32 = 0, 1    # NPB_KIND_*
 NAN, INF = float("nan"), float("inf")
 
 
-@pytest.fixture(scope="module")
-def L():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
-    from nuclear_sim_amd import _lib
-    return _lib.load()
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "npb.h")).read()
-
-
 def test_header_declares_the_entry_points_the_maxima_and_the_rules_of_the_road():
-    text = _header()
-    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
-    for s in ENTRY_POINTS:
-        assert s in declared, s
-    assert int(re.search(r"#define NPB_FEATURES_COLS_MAX (\d+)", text).group(1)) == 64
-    assert int(re.search(r"#define NPB_FEATURES_STACK_MAX (\d+)", text).group(1)) == 16
-    assert int(re.search(r"#define NPB_FEATURES_CELLS_MAX (\d+)", text).group(1)) == 256
-    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) == 154
+    text = abi.header_text()
+    assert set(ENTRY_POINTS) <= set(abi.declared())
+    assert abi.define("NPB_FEATURES_COLS_MAX") == 64
+    assert abi.define("NPB_FEATURES_STACK_MAX") == 16
+    assert abi.define("NPB_FEATURES_CELLS_MAX") == 256
+    assert abi.define("NPB_VERSION") == 154
     for words in ("rounded before the product", "a NaN passes both comparisons", "overflows to an infinity", "THE quiet NaN", "the terminal frame pass A just",
                   "No half types", "Not here: the terminal stack in the episode records"):
         assert words in text, words
 
 
-def test_library_exports_and_binding_declares_them(L):
-    raw = ctypes.CDLL(LIB)
-    for s in ENTRY_POINTS:
-        assert hasattr(raw, s), "libnpb.so does not export %s" % s
-        assert getattr(L, s).argtypes is not None, s
-    assert L.npb_set_features(None, None) == -1 and L.npb_features_prime(None, None) == -1 and L.npb_features_clear(None, None, None) == -1
-    assert L.npb_features_get_state(None, None, None, None) == -1 and L.npb_features_set_state(None, None, None, None) == -1
+def test_library_exports_and_binding_declares_them():
+    abi.check_entry_points(ENTRY_POINTS, [("npb_set_features", None, None), ("npb_features_prime", None, None),
+                                          ("npb_features_clear", None, None, None), ("npb_features_get_state", None, None, None, None),
+                                          ("npb_features_set_state", None, None, None, None)])
 
 
-def test_the_binding_lays_the_descriptors_out_as_the_compiler_does(tmp_path):
-    from nuclear_sim_amd import _lib, features
-    lines = []
-    for c_name, py_name in STRUCTS.items():
-        lines.append('  printf("%%zu\\n", sizeof(%s));\n' % c_name)
-        lines += ['  printf("%%zu\\n", offsetof(%s, %s));\n' % (c_name, f[0]) for f in getattr(_lib, py_name)._fields_]
+def test_the_binding_lays_the_descriptors_out_as_the_compiler_does():
+    from nuclear_sim_amd import features
     # the initialiser macros name the members kind, mask
-    lines.append("  { npb_feature_column_t c = { {0}, NPB_FEATURE_BITS(0xF00) }, a = { {0}, NPB_FEATURE_AFFINE };\n"
-                 '    printf("%d\\n%u\\n%d\\n%u\\n", c.kind, c.mask, a.kind, a.mask); }\n')
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "npb.h"\nint main(void) {\n' + "".join(lines) + "  return 0;\n}\n")
-    exe = tmp_path / "probe"
-    subprocess.check_call([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    want = []
-    for py_name in STRUCTS.values():
-        S = getattr(_lib, py_name)
-        want += [ctypes.sizeof(S)] + [getattr(S, f[0]).offset for f in S._fields_]
-    assert got == want + [_lib.FEATURE_KINDS["bits"], 0xF00, _lib.FEATURE_KINDS["affine"], 0]
-    text = _header()
+    c, a = "((npb_feature_column_t){ {0}, NPB_FEATURE_BITS(0xF00) })", "((npb_feature_column_t){ {0}, NPB_FEATURE_AFFINE })"
+    got, values = abi.probe(STRUCTS, [c + ".kind", c + ".mask", a + ".kind", a + ".mask"])
+    assert got == abi.layout(STRUCTS)
+    assert values == [_lib.FEATURE_KINDS["bits"], 0xF00, _lib.FEATURE_KINDS["affine"], 0]
+    text = abi.header_text()
     assert {name: int(re.search(r"NPB_FEATURE_KIND_%s = (\d+)" % name.upper(), text).group(1)) for name in _lib.FEATURE_KINDS} == _lib.FEATURE_KINDS
     assert {"float32": int(re.search(r"NPB_FEATURES_F32 = (\d+)", text).group(1)),
             "float64": int(re.search(r"NPB_FEATURES_F64 = (\d+)", text).group(1))} == _lib.FEATURE_DTYPES
@@ -88,7 +58,6 @@ class _Desc:
     u8 source, float output with a final tensor; and the ctypes array it points into"""
 
     def __init__(self):
-        from nuclear_sim_amd import _lib
         from nuclear_sim_amd.schema import SCHEMA
         self.lib = _lib
         level = SCHEMA.slot("pump.oil_level", 1)[1]
@@ -112,41 +81,26 @@ class _Desc:
         C.source.base, C.source.type, C.source.rows, C.source.row_stride, C.source.plant_stride = A16, self.lib.SAMPLE_TYPES[kind], 1, 0, 1
 
 
-def _why(L, D, n=70):
-    r = L.npb_features_check(ctypes.byref(D.d), n)
-    return None if r is None else r.decode()
+def _why(D, n=70):
+    return abi.why(abi.library().npb_features_check, ctypes.byref(D.d), n)
 
 
-def test_the_check_accepts_valid_features_and_null(L):
-    assert _why(L, _Desc()) is None
-    assert L.npb_features_check(None, 70) is None
+def test_the_check_accepts_valid_features_and_null():
+    assert _why(_Desc()) is None
+    assert abi.library().npb_features_check(None, 70) is None
     D = _Desc(); D.d.final = None                                  # optional
-    assert _why(L, D) is None
+    assert _why(D) is None
     D = _Desc(); D.d.n_columns, D.d.stack = 64, 4                  # the largest shape: 256 cells
-    assert _why(L, D) is None
+    assert _why(D) is None
     D = _Desc(); D.d.n_columns, D.d.stack = 16, 16
-    assert _why(L, D) is None
+    assert _why(D) is None
     D = _Desc(); D.d.out_type, D.d.out, D.d.final = 1, A16 + 8, A16 + 16      # double
-    assert _why(L, D) is None
+    assert _why(D) is None
     D = _Desc(); D.cols[0].scale = INF; D.cols[0].nan_to = 0.0; D.cols[0].lo = D.cols[0].hi = 2.0      # the caller's business
-    assert _why(L, D) is None
+    assert _why(D) is None
 
 
-def _set(path, value):
-    def change(D):
-        obj = D
-        *head, last = path
-        for name in head:
-            obj = obj[name] if isinstance(name, int) else getattr(obj, name)
-        setattr(obj, last, value)
-    return change
-
-
-def _both(*changes):
-    def change(D):
-        for c in changes:
-            c(D)
-    return change
+_set, _both = abi.set_path, abi.both
 
 
 REFUSALS = [
@@ -183,18 +137,12 @@ REFUSALS = [
 
 
 @pytest.mark.parametrize("what, change, reason", REFUSALS, ids=[r[0] for r in REFUSALS])
-def test_the_check_names_every_refusal(L, what, change, reason):
-    D = _Desc()
-    if change is None:
-        why = _why(L, D, n=0)
-    else:
-        change(D)
-        why = _why(L, D)
-    assert why is not None and why.startswith("npb_set_features: ") and reason in why, (what, why)
+def test_the_check_names_every_refusal(what, change, reason):
+    abi.check_refusal(_Desc, _why, "npb_set_features: ", what, change, reason)
 
 
-def test_scale_and_ref_are_read_only_where_the_kind_has_them(L):
+def test_scale_and_ref_are_read_only_where_the_kind_has_them():
     """scale and ref belong to AFFINE: a BITS column's are not looked at"""
     D = _Desc()
     D.cols[2].scale = NAN; D.cols[2].ref = NAN
-    assert _why(L, D) is None
+    assert _why(D) is None

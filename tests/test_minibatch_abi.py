@@ -5,39 +5,23 @@ handle and reads no device memory, accepts a valid descriptor and names every re
 
 NPB_VERSION stays where the suites of the entry-point groups before this one pin it: the new entry points are detected by name."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
+import abi_support as abi
+from nuclear_sim_amd import _lib
+
 ENTRY_POINTS = ("npb_rollout_moments", "npb_rollout_permutation", "npb_rollout_minibatch", "npb_minibatch_check")
-STRUCTS = {"npb_moments_desc_t": "NpbMomentsDesc", "npb_minibatch_desc_t": "NpbMinibatchDesc"}
+STRUCTS = {"npb_moments_desc_t": _lib.NpbMomentsDesc, "npb_minibatch_desc_t": _lib.NpbMinibatchDesc}
 A16 = 0x7000       # "device addresses" the check only looks at: never dereferenced
 N, T, CELLS, AXES, EXTRAS = 70, 5, 8, 3, 2
 
 
-@pytest.fixture(scope="module")
-def L():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
-    from nuclear_sim_amd import _lib
-    return _lib.load()
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "npb.h")).read()
-
-
 def test_header_declares_the_entry_points_and_the_rules_of_the_road():
-    text = _header()
-    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
-    for s in ENTRY_POINTS:
-        assert s in declared, s
-    assert int(re.search(r"#define NPB_MINIBATCH_ROUNDS (\d+)", text).group(1)) == 6
-    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) == 154
+    text = abi.header_text()
+    assert set(ENTRY_POINTS) <= set(abi.declared())
+    assert abi.define("NPB_MINIBATCH_ROUNDS") == 6
+    assert abi.define("NPB_VERSION") == 154
     for words in ("The order of every addition is pinned", "pad it with +0.0 to a multiple of 256", "the product rounded before the sum",
                   "the sum is not restated as a scan or a different tree", "A NaN or an infinity propagates", "no table, no sort, no memory",
                   "cycle walking", "murmur3's 32-bit finaliser", "one IEEE division in double", "round-to-nearest-even",
@@ -46,33 +30,16 @@ def test_header_declares_the_entry_points_and_the_rules_of_the_road():
         assert words in text, words
 
 
-def test_library_exports_and_binding_declares_them(L):
-    raw = ctypes.CDLL(LIB)
-    for s in ENTRY_POINTS:
-        assert hasattr(raw, s), "libnpb.so does not export %s" % s
-        assert getattr(L, s).argtypes is not None, s
-    assert L.npb_rollout_moments(None, None, None) == -1 and L.npb_rollout_minibatch(None, None, None) == -1
-    assert L.npb_rollout_permutation(None, 10, None, 0, 10, None, None) == -1
+def test_library_exports_and_binding_declares_them():
+    abi.check_entry_points(ENTRY_POINTS, [("npb_rollout_moments", None, None, None), ("npb_rollout_minibatch", None, None, None),
+                                          ("npb_rollout_permutation", None, 10, None, 0, 10, None, None)])
 
 
-def test_the_binding_lays_the_descriptors_out_as_the_compiler_does(tmp_path):
-    from nuclear_sim_amd import _lib, rollout
-    lines = []
-    for c_name, py_name in STRUCTS.items():
-        lines.append('  printf("%%zu\\n", sizeof(%s));\n' % c_name)
-        lines += ['  printf("%%zu\\n", offsetof(%s, %s));\n' % (c_name, f[0]) for f in getattr(_lib, py_name)._fields_]
-    lines.append('  printf("%d\\n%d\\n%d\\n", NPB_MINIBATCH_TRANSITION, NPB_MINIBATCH_PLANT, NPB_MINIBATCH_ROUNDS);\n')
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "npb.h"\nint main(void) {\n' + "".join(lines) + "  return 0;\n}\n")
-    exe = tmp_path / "probe"
-    subprocess.check_call([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    want = []
-    for py_name in STRUCTS.values():
-        S = getattr(_lib, py_name)
-        want += [ctypes.sizeof(S)] + [getattr(S, f[0]).offset for f in S._fields_]
+def test_the_binding_lays_the_descriptors_out_as_the_compiler_does():
+    from nuclear_sim_amd import rollout
+    got, values = abi.probe(STRUCTS, ["NPB_MINIBATCH_TRANSITION", "NPB_MINIBATCH_PLANT", "NPB_MINIBATCH_ROUNDS"])
     U = _lib.MINIBATCH_UNITS
-    assert got == want + [U["transition"], U["plant"], _lib.MINIBATCH_ROUNDS]
+    assert got == abi.layout(STRUCTS) and values == [U["transition"], U["plant"], _lib.MINIBATCH_ROUNDS]
     assert U == rollout.UNITS and _lib.MINIBATCH_ROUNDS == rollout.ROUNDS == 6
 
 
@@ -80,7 +47,6 @@ class _Desc:
     """a valid descriptor: transitions 10 .. 74 of 5 x 70, float32 advantages normalised by moments, every output given"""
 
     def __init__(self):
-        from nuclear_sim_amd import _lib
         self.d = d = _lib.NpbMinibatchDesc()
         d.unit, d.type, d.first, d.count, d.eps, d.max_blocks = 0, 0, 10, 64, 1e-8, 0
         d.keys[:] = [1, 2, 3, 4, 5, 6]
@@ -88,27 +54,22 @@ class _Desc:
         d.index, d.obs, d.act, d.extra, d.adv_out, d.ret_out = A16 + 4, A16 + 16, A16 + 32, A16 + 48, A16 + 12, A16 + 20
 
 
-def _why(L, D, n=N, t=T, cells=CELLS, axes=AXES, extras=EXTRAS):
-    r = L.npb_minibatch_check(None if D is None else ctypes.byref(D.d), n, t, cells, axes, extras)
-    return None if r is None else r.decode()
+def _why(D, n=N, t=T, cells=CELLS, axes=AXES, extras=EXTRAS):
+    return abi.why(abi.library().npb_minibatch_check, None if D is None else ctypes.byref(D.d), n, t, cells, axes, extras)
 
 
-def _set(**members):
-    def change(D):
-        for name, value in members.items():
-            setattr(D.d, name, value)
-    return change
+_set = abi.set_members
 
 
-def test_the_check_accepts_valid_minibatches(L):
-    assert _why(L, _Desc()) is None
+def test_the_check_accepts_valid_minibatches():
+    assert _why(_Desc()) is None
     for change, kw in ((_set(unit=1, first=6, count=64), {}), (_set(first=0, count=N * T), {}), (_set(first=N * T - 1, count=1), {}),
                        (_set(type=1, adv=A16 + 8, adv_out=A16 + 16, ret_out=A16 + 24), {}), (_set(moments=None), {}), (_set(eps=0.0), {}),
                        (_set(obs=None, act=None, extra=None, adv_out=None, ret_out=None, moments=None, adv=None, ret=None), {}),
                        (_set(act=None), {"axes": 0}), (_set(extra=None), {"extras": 0}), (_set(max_blocks=3), {}),
                        (_set(first=2 ** 31 - 2, count=1), {"n": 2 ** 31 - 1, "t": 1})):
         D = _Desc(); change(D)
-        assert _why(L, D, **kw) is None, kw
+        assert _why(D, **kw) is None, kw
 
 
 REFUSALS = [
@@ -144,12 +105,9 @@ REFUSALS = [
 
 
 @pytest.mark.parametrize("what, change, kw, reason", REFUSALS, ids=[r[0] for r in REFUSALS])
-def test_the_check_names_every_refusal(L, what, change, kw, reason):
-    D = _Desc()
-    change(D)
-    why = _why(L, D, **kw)
-    assert why is not None and why.startswith("npb_rollout_minibatch: ") and reason in why, (what, why)
+def test_the_check_names_every_refusal(what, change, kw, reason):
+    abi.check_refusal(_Desc, _why, "npb_rollout_minibatch: ", what, change, reason, kw)
 
 
-def test_a_null_descriptor_is_refused(L):
-    assert "a NULL descriptor" in _why(L, None)
+def test_a_null_descriptor_is_refused():
+    assert "a NULL descriptor" in _why(None)

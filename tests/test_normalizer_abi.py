@@ -4,14 +4,12 @@ which needs no handle and reads no device memory, accepts a valid descriptor and
 
 The header keeps NPB_VERSION where the suites of the entry-point groups before this one pin it: the new entry points are detected by name."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
+import abi_support as abi
+from nuclear_sim_amd import _lib
+
 ENTRY_POINTS = ("npb_set_normalizer", "npb_normalizer_check", "npb_normalizer_training", "npb_normalizer_get_state", "npb_normalizer_set_state",
                 "npb_normalizer_clear")
 A16 = 0x7000       # "device addresses" the check only looks at: never dereferenced
@@ -19,24 +17,10 @@ F64, I32 = 0, 1    # NPB_KIND_*
 NAN, INF = float("nan"), float("inf")
 
 
-@pytest.fixture(scope="module")
-def L():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
-    from nuclear_sim_amd import _lib
-    return _lib.load()
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "npb.h")).read()
-
-
 def test_header_declares_the_entry_points_and_the_rules_of_the_road():
-    text = _header()
-    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
-    for s in ENTRY_POINTS:
-        assert s in declared, s
-    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) == 154
+    text = abi.header_text()
+    assert set(ENTRY_POINTS) <= set(abi.declared())
+    assert abi.define("NPB_VERSION") == 154
     for words in ("a sample counts iff q - q == 0.0", "mean = shift + s1 / N", "M2 = (M2 + s2) - (s1 * s1) / N", "a bad value never poisons a statistic",
                   "ret * gamma rounded before the sum", "the mean is not subtracted", "Fresh frames", "set the normaliser first",
                   "Not here: statistics over fresh frames", "an exponential-moving-average variant", "normalizer.merge is the host answer",
@@ -46,27 +30,15 @@ def test_header_declares_the_entry_points_and_the_rules_of_the_road():
         assert words in text, words
 
 
-def test_library_exports_and_binding_declares_them(L):
-    raw = ctypes.CDLL(LIB)
-    for s in ENTRY_POINTS:
-        assert hasattr(raw, s), "libnpb.so does not export %s" % s
-        assert getattr(L, s).argtypes is not None, s
+def test_library_exports_and_binding_declares_them():
     nine = [None] * 9
-    assert L.npb_set_normalizer(None, None) == -1 and L.npb_normalizer_training(None, 1) == -1 and L.npb_normalizer_clear(None, None, None) == -1
-    assert L.npb_normalizer_get_state(*nine) == -1 and L.npb_normalizer_set_state(*nine) == -1
+    abi.check_entry_points(ENTRY_POINTS, [("npb_set_normalizer", None, None), ("npb_normalizer_training", None, 1), ("npb_normalizer_clear", None, None, None),
+                                          ("npb_normalizer_get_state", *nine), ("npb_normalizer_set_state", *nine)])
 
 
-def test_the_binding_lays_the_descriptor_out_as_the_compiler_does(tmp_path):
-    from nuclear_sim_amd import _lib
-    S = _lib.NpbNormalizerDesc
-    lines = ['  printf("%zu\\n", sizeof(npb_normalizer_desc_t));\n']
-    lines += ['  printf("%%zu\\n", offsetof(npb_normalizer_desc_t, %s));\n' % f[0] for f in S._fields_]
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "npb.h"\nint main(void) {\n' + "".join(lines) + "  return 0;\n}\n")
-    exe = tmp_path / "probe"
-    subprocess.check_call([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == [ctypes.sizeof(S)] + [getattr(S, f[0]).offset for f in S._fields_]
+def test_the_binding_lays_the_descriptor_out_as_the_compiler_does():
+    structs = {"npb_normalizer_desc_t": _lib.NpbNormalizerDesc}
+    assert abi.probe(structs)[0] == abi.layout(structs)
 
 
 class _Desc:
@@ -74,7 +46,6 @@ class _Desc:
     and a valid normaliser on columns 0 and 1 with the return stream"""
 
     def __init__(self):
-        from nuclear_sim_amd import _lib
         from nuclear_sim_amd.schema import SCHEMA
         self.lib = _lib
         level = SCHEMA.slot("pump.oil_level", 1)[1]
@@ -101,42 +72,24 @@ class _Desc:
         C.source.base, C.source.type, C.source.rows, C.source.row_stride, C.source.plant_stride = A16, self.lib.SAMPLE_TYPES["f64"], 1, 0, 1
 
 
-def _why(L, D, n=70):
-    r = L.npb_normalizer_check(ctypes.byref(D.d), n, ctypes.byref(D.f) if D.features else None)
-    return None if r is None else r.decode()
+def _why(D, n=70):
+    return abi.why(abi.library().npb_normalizer_check, ctypes.byref(D.d), n, ctypes.byref(D.f) if D.features else None)
 
 
-def test_the_check_accepts_valid_normalisers_and_null(L):
-    assert _why(L, _Desc()) is None
-    assert L.npb_normalizer_check(None, 70, None) is None
+def test_the_check_accepts_valid_normalisers_and_null():
+    assert _why(_Desc()) is None
+    assert abi.library().npb_normalizer_check(None, 70, None) is None
     D = _Desc(); D.d.reward, D.d.norm_reward, D.d.gamma, D.d.clip = 0, None, NAN, NAN      # columns alone: the return's members are not looked at
-    assert _why(L, D) is None
+    assert _why(D) is None
     D = _Desc(); D.d.n_columns, D.d.columns, D.features = 0, None, False      # the return stream alone needs no features
-    assert _why(L, D) is None
+    assert _why(D) is None
     D = _Desc(); D.d.eps, D.d.gamma = 0.0, 0.0
-    assert _why(L, D) is None
+    assert _why(D) is None
     D = _Desc(); D.d.gamma = 1.0; D.d.clip = INF
-    assert _why(L, D) is None
+    assert _why(D) is None
 
 
-def _set(path, value):
-    def change(D):
-        obj = D
-        *head, last = path
-        for name in head:
-            obj = obj[name] if isinstance(name, int) else getattr(obj, name)
-        if isinstance(last, int):
-            obj[last] = value
-        else:
-            setattr(obj, last, value)
-    return change
-
-
-def _both(*changes):
-    def change(D):
-        for c in changes:
-            c(D)
-    return change
+_set, _both = abi.set_path, abi.both
 
 
 REFUSALS = [
@@ -165,17 +118,11 @@ REFUSALS = [
 
 
 @pytest.mark.parametrize("what, change, reason", REFUSALS, ids=[r[0] for r in REFUSALS])
-def test_the_check_names_every_refusal(L, what, change, reason):
-    D = _Desc()
-    if change is None:
-        why = _why(L, D, n=0)
-    else:
-        change(D)
-        why = _why(L, D)
-    assert why is not None and why.startswith("npb_set_normalizer: ") and reason in why, (what, why)
+def test_the_check_names_every_refusal(what, change, reason):
+    abi.check_refusal(_Desc, _why, "npb_set_normalizer: ", what, change, reason)
 
 
-def test_features_the_library_would_refuse_are_refused_as_theirs(L):
+def test_features_the_library_would_refuse_are_refused_as_theirs():
     D = _Desc()
     D.f.stack = 0
-    assert _why(L, D).startswith("npb_set_features: ")
+    assert _why(D).startswith("npb_set_features: ")

@@ -3,62 +3,47 @@ handle is refused; an unknown action name is refused on the host before a device
 third record kind and the automatic ones as before; and the reference fixtures under tests/golden/operator/
 (tools/make_operator_maintenance_golden.py) are not vacuous: every call that acts by construction changes the reference's pump state,
 every other call changes none.  No compute calls."""
-import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_support as abi
+from nuclear_sim_amd import _lib
+
 from operator_maintenance_golden import HANDLERS, OperatorGolden, operator_fixture_names
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
-    return LIB
 
 
 def test_header_declares_the_entry_point():
-    text = open(os.path.join(ROOT, "include", "npb.h")).read()
-    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
+    text, declared = abi.header_text(), set(abi.declared())
     assert "npb_perform_maintenance" in declared
-    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) >= 147
-    maint = open(os.path.join(ROOT, "include", "npb_maint.h")).read()
+    assert abi.define("NPB_VERSION") >= 147
+    maint = abi.header_text("npb_maint.h")
     assert re.search(r"NPB_MAINT_EVENT_OPERATOR\s*=\s*2\b", maint)
 
 
-def test_library_exports_and_binding_declares_it(built_lib):
-    lib = ctypes.CDLL(built_lib)
-    assert hasattr(lib, "npb_perform_maintenance"), "libnpb.so does not export npb_perform_maintenance"
-    assert lib.npb_version() >= 147
-    from nuclear_sim_amd import _lib
-    L = _lib.load()
+def test_library_exports_and_binding_declares_it():
+    abi.check_exported(["npb_perform_maintenance"])
+    L = abi.library()
+    assert L.npb_version() >= 147
     assert L.npb_perform_maintenance.argtypes is not None and len(L.npb_perform_maintenance.argtypes) == 7
 
 
-def test_null_handle_is_refused(built_lib):
-    from nuclear_sim_amd import _lib
-    L = _lib.load()
-    assert L.npb_perform_maintenance(None, None, None, None, None, None, None) == -1
+def test_null_handle_is_refused():
+    abi.check_null_refused([("npb_perform_maintenance", None, None, None, None, None, None, None)])
 
 
-def test_host_catalog_is_the_librarys(built_lib):
+def test_host_catalog_is_the_librarys():
     """the names the host checks an order against without the library are the library's own catalog, handlers included"""
-    from nuclear_sim_amd import _lib
-    L = _lib.load()
+    L = abi.library()
     assert list(_lib.MAINT_ACTION_NAMES) == list(_lib.MAINT_ACTIONS)
     assert {a for k, a in enumerate(_lib.MAINT_ACTION_NAMES) if L.npb_maint_action_has_handler(k)} == set(HANDLERS)
 
 
 def test_unknown_action_name_is_refused_before_any_device_work():
     """a name outside the catalog raises ValueError at once: on an object that has no handle, no library and no device behind it"""
-    from nuclear_sim_amd import _lib
     from nuclear_sim_amd.env import BatchedPlantEnv
     env = object.__new__(BatchedPlantEnv)
     with pytest.raises(ValueError, match="polish_the_nameplate"):
@@ -72,9 +57,9 @@ def test_unknown_action_name_is_refused_before_any_device_work():
     assert _lib.maint_action_index("oil_top_off") == 1 and _lib.maint_action_index(7) == 7
 
 
-def test_maintlog_renders_operator_records_and_leaves_the_automatic_ones(built_lib):
-    from nuclear_sim_amd import _lib, maintlog
-    L = _lib.load()
+def test_maintlog_renders_operator_records_and_leaves_the_automatic_ones():
+    from nuclear_sim_amd import maintlog
+    L = abi.library()
     A, P = _lib.MAINT_ACTIONS, _lib.MAINT_PARAMS
     handlers = [int(L.npb_maint_action_has_handler(a)) for a in range(len(A))]
     assert maintlog.OPERATOR == 2 and maintlog.EVENT_TYPES[2] == "operator_maintenance" and maintlog.EVENT_TYPES[:2] == ("work_order_created", "work_order_completed")
@@ -120,7 +105,7 @@ def test_fixtures_live_in_their_own_directory():
     assert {"om1_every_handler", "om2_with_automatic_maintenance"} <= set(names)
     assert not [n for n in fixture_names() if n.startswith("om")]
     for n in names:
-        assert os.path.getsize(os.path.join(ROOT, "tests", "golden", "operator", n + ".npz")) <= 360 * 1024, n
+        assert os.path.getsize(os.path.join(abi.ROOT, "tests", "golden", "operator", n + ".npz")) <= 360 * 1024, n
 
 
 @pytest.mark.parametrize("name", operator_fixture_names())
@@ -177,7 +162,6 @@ def test_om2_operator_calls_do_not_move_the_automatic_counters():
     """the operator's top-off keeps FWP-1 from ever reaching its threshold; FWP-4's open order executes although its oil was changed;
     the counters only ever move with the automatic system's own events"""
     from work_order_events import events_from_golden
-    from nuclear_sim_amd import _lib
     g = OperatorGolden("om2_with_automatic_maintenance")
     labels = [c[2] for c in g.cols]
     top_off = g.actions.index("oil_top_off")

@@ -6,40 +6,24 @@ statement's.  No compute calls.
 
 The header keeps NPB_VERSION where the suites of the entry-point groups before this one pin it: the new entry points are detected by name."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
+import abi_support as abi
+from nuclear_sim_amd import _lib
+
 ENTRY_POINTS = ("npb_set_policy", "npb_policy_check", "npb_policy_count", "npb_policy_load", "npb_policy_values", "npb_policy_noise",
                 "npb_policy_get_state", "npb_policy_set_state", "npb_collect")
 A4 = 0x7000       # "device addresses" the check only looks at: never dereferenced
 CELLS, AXES = 15, 3
 
 
-@pytest.fixture(scope="module")
-def L():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
-    from nuclear_sim_amd import _lib
-    return _lib.load()
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "npb.h")).read()
-
-
 def test_header_declares_the_entry_points_the_maxima_and_the_rules_of_the_road():
-    text = _header()
-    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
-    for s in ENTRY_POINTS:
-        assert s in declared, s
-    assert int(re.search(r"#define NPB_POLICY_HIDDEN_MAX (\d+)", text).group(1)) == 3
-    assert int(re.search(r"#define NPB_POLICY_WIDTH_MAX (\d+)", text).group(1)) == 128
-    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) == 154
+    text = abi.header_text()
+    assert set(ENTRY_POINTS) <= set(abi.declared())
+    assert abi.define("NPB_POLICY_HIDDEN_MAX") == 3
+    assert abi.define("NPB_POLICY_WIDTH_MAX") == 128
+    assert abi.define("NPB_VERSION") == 154
     for words in ("acc = fmaf(x[k], W[j][k], acc)", "extended with +0.0 cells and +0.0 weights to a multiple of 4", "A subnormal result or accumulator is outside the contract",
                   "the device takes no exponential", "Philox4x32-10", "(first_plant + p, t & 0xffffffff, t >> 32, j)", "(w0 * 2^20 + (w1 >> 12) + 0.5) * 2^-52",
                   "6.283185307179586", "0.9189385332046727", "the density of the UNROUNDED action", "THE quiet NaN in every output", "v_mfma_f32_32x32x2_f32",
@@ -49,30 +33,19 @@ def test_header_declares_the_entry_points_the_maxima_and_the_rules_of_the_road()
         assert words in text, words
 
 
-def test_library_exports_and_binding_declares_them(L):
-    raw = ctypes.CDLL(LIB)
-    for s in ENTRY_POINTS:
-        assert hasattr(raw, s), "libnpb.so does not export %s" % s
-        assert getattr(L, s).argtypes is not None, s
-    assert L.npb_set_policy(None, None) == -1 and L.npb_policy_load(None, None, 0, None) == -1
-    assert L.npb_policy_values(None, None, 0, 0, None, None) == -1 and L.npb_policy_noise(None, 0, None, None, None) == -1
-    assert L.npb_policy_get_state(None, None) == -1 and L.npb_policy_set_state(None, 0) == -1
-    assert L.npb_collect(None, 1, None, None, None, None, None, None) == -1
+def test_library_exports_and_binding_declares_them():
+    abi.check_entry_points(ENTRY_POINTS, [("npb_set_policy", None, None), ("npb_policy_load", None, None, 0, None),
+                                          ("npb_policy_values", None, None, 0, 0, None, None), ("npb_policy_noise", None, 0, None, None, None),
+                                          ("npb_policy_get_state", None, None), ("npb_policy_set_state", None, 0),
+                                          ("npb_collect", None, 1, None, None, None, None, None, None)])
 
 
-def test_the_binding_lays_the_descriptor_out_as_the_compiler_does(tmp_path):
-    from nuclear_sim_amd import _lib, policy
-    S = _lib.NpbPolicyDesc
-    lines = ['  printf("%zu\\n", sizeof(npb_policy_desc_t));\n']
-    lines += ['  printf("%%zu\\n", offsetof(npb_policy_desc_t, %s));\n' % f[0] for f in S._fields_]
-    lines.append('  printf("%d\\n%d\\n%d\\n%d\\n", NPB_POLICY_RELU, NPB_POLICY_TANH, NPB_POLICY_HIDDEN_MAX, NPB_POLICY_WIDTH_MAX);\n')
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "npb.h"\nint main(void) {\n' + "".join(lines) + "  return 0;\n}\n")
-    exe = tmp_path / "probe"
-    subprocess.check_call([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    want = [ctypes.sizeof(S)] + [getattr(S, f[0]).offset for f in S._fields_]
-    assert got == want + [_lib.POLICY_ACTIVATIONS["relu"], _lib.POLICY_ACTIVATIONS["tanh"], _lib.POLICY_HIDDEN_MAX, _lib.POLICY_WIDTH_MAX]
+def test_the_binding_lays_the_descriptor_out_as_the_compiler_does():
+    from nuclear_sim_amd import policy
+    structs = {"npb_policy_desc_t": _lib.NpbPolicyDesc}
+    got, values = abi.probe(structs, ["NPB_POLICY_RELU", "NPB_POLICY_TANH", "NPB_POLICY_HIDDEN_MAX", "NPB_POLICY_WIDTH_MAX"])
+    assert got == abi.layout(structs)
+    assert values == [_lib.POLICY_ACTIVATIONS["relu"], _lib.POLICY_ACTIVATIONS["tanh"], _lib.POLICY_HIDDEN_MAX, _lib.POLICY_WIDTH_MAX]
     assert _lib.POLICY_ACTIVATIONS == policy.ACTIVATIONS and (_lib.POLICY_HIDDEN_MAX, _lib.POLICY_WIDTH_MAX) == (policy.HIDDEN_MAX, policy.WIDTH_MAX) == (3, 128)
 
 
@@ -80,7 +53,6 @@ class _Desc:
     """a valid descriptor: actor (33, 17), critic (7,), tanh, both outputs and both slots of three extras"""
 
     def __init__(self):
-        from nuclear_sim_amd import _lib
         self.d = d = _lib.NpbPolicyDesc()
         d.actor_layers, d.critic_layers, d.activation = 2, 1, 1
         d.actor_width[0], d.actor_width[1], d.critic_width[0] = 33, 17, 7
@@ -88,9 +60,8 @@ class _Desc:
         d.value, d.logp, d.extras_in, d.n_extras, d.value_slot, d.logp_slot = A4, A4 + 4, A4 + 16, 3, 0, 2
 
 
-def _why(L, D, n=70, cells=CELLS, axes=AXES):
-    r = L.npb_policy_check(ctypes.byref(D.d), n, cells, axes)
-    return None if r is None else r.decode()
+def _why(D, n=70, cells=CELLS, axes=AXES):
+    return abi.why(abi.library().npb_policy_check, ctypes.byref(D.d), n, cells, axes)
 
 
 def _set(**members):
@@ -103,19 +74,19 @@ def _set(**members):
     return change
 
 
-def test_the_check_accepts_valid_policies_and_null_and_counts_the_parameters(L):
+def test_the_check_accepts_valid_policies_and_null_and_counts_the_parameters():
     from nuclear_sim_amd import policy
-    assert _why(L, _Desc()) is None
-    assert L.npb_policy_check(None, 70, CELLS, AXES) is None
+    assert _why(_Desc()) is None
+    assert abi.library().npb_policy_check(None, 70, CELLS, AXES) is None
     for change, kw in ((_set(actor_layers=3, actor_width2=(128,)), {}), (_set(actor_layers=1, actor_width0=(1,)), {}), (_set(activation=0), {}),
                        (_set(extras_in=None, value_slot=-1, logp_slot=-1, n_extras=0), {}), (_set(value_slot=-1), {}), (_set(deterministic=1), {}),
                        (_set(first_plant=2 ** 32 - 70), {}), (_set(), {"n": 1, "cells": 256, "axes": 8}), (_set(), {"cells": 1, "axes": 1})):
         D = _Desc(); change(D)
-        assert _why(L, D, **kw) is None, kw
-    assert L.npb_policy_count(ctypes.byref(_Desc().d), CELLS, AXES) == policy.theta_size(CELLS, AXES, (33, 17), (7,))
+        assert _why(D, **kw) is None, kw
+    assert abi.library().npb_policy_count(ctypes.byref(_Desc().d), CELLS, AXES) == policy.theta_size(CELLS, AXES, (33, 17), (7,))
     D = _Desc(); _set(actor_layers=3, actor_width2=(128,), critic_layers=3, critic_width1=(64,), critic_width2=(5,))(D)
-    assert L.npb_policy_count(ctypes.byref(D.d), 256, 8) == policy.theta_size(256, 8, (33, 17, 128), (7, 64, 5))
-    assert L.npb_policy_count(None, CELLS, AXES) == 0
+    assert abi.library().npb_policy_count(ctypes.byref(D.d), 256, 8) == policy.theta_size(256, 8, (33, 17, 128), (7, 64, 5))
+    assert abi.library().npb_policy_count(None, CELLS, AXES) == 0
 
 
 REFUSALS = [
@@ -146,8 +117,5 @@ REFUSALS = [
 
 
 @pytest.mark.parametrize("what, change, kw, reason", REFUSALS, ids=[r[0] for r in REFUSALS])
-def test_the_check_names_every_refusal(L, what, change, kw, reason):
-    D = _Desc()
-    change(D)
-    why = _why(L, D, **kw)
-    assert why is not None and why.startswith("npb_set_policy: ") and reason in why, (what, why)
+def test_the_check_names_every_refusal(what, change, kw, reason):
+    abi.check_refusal(_Desc, _why, "npb_set_policy: ", what, change, reason, kw)

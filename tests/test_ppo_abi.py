@@ -3,35 +3,23 @@ bound; the binding lays the descriptor out as a C compiler does (a small compile
 own check, which needs no handle and reads no device memory, accepts a valid descriptor and names every refusal the header lists.  No
 compute calls."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
+import abi_support as abi
+from nuclear_sim_amd import _lib
+
 ENTRY_POINTS = ("npb_ppo_check", "npb_policy_grad", "npb_policy_adam", "npb_policy_update", "npb_policy_get_grad", "npb_policy_get_stats",
                 "npb_policy_get_theta", "npb_policy_optimizer_get_state", "npb_policy_optimizer_set_state")
 A8 = 0x7000       # "device addresses" the check only looks at: never dereferenced
 CELLS, AXES = 15, 3
 
 
-@pytest.fixture(scope="module")
-def L():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
-    from nuclear_sim_amd import _lib
-    return _lib.load()
-
-
 def test_header_declares_the_entry_points_and_states_the_contract():
-    text = open(os.path.join(ROOT, "include", "npb.h")).read()
-    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
-    for s in ENTRY_POINTS:
-        assert s in declared, s
-    assert int(re.search(r"#define NPB_PPO_STATS (\d+)", text).group(1)) == 8
-    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) == 154
+    text = abi.header_text()
+    assert set(ENTRY_POINTS) <= set(abi.declared())
+    assert abi.define("NPB_PPO_STATS") == 8
+    assert abi.define("NPB_VERSION") == 154
     for words in ("c = clipped ? 0.0 : -(adv * r)", "every comparison strict", "dmean[a] = (float)(((c * d[a]) / std[a]) / count)",
                   "added in ascending\n * chain order onto 0.0 and narrowed once", "grad(log_std[a]) = (float)(sum dls[a] - ent_coef)",
                   "max_grad_norm / (norm + 1e-6)", "theta' = theta - step_size * (m' / (sqrt(v') / root + eps))", "is SKIPPED",
@@ -39,36 +27,24 @@ def test_header_declares_the_entry_points_and_states_the_contract():
         assert words in text, words
 
 
-def test_library_exports_and_binding_declares_them(L):
-    from nuclear_sim_amd import _lib, ppo
-    raw = ctypes.CDLL(LIB)
-    for s in ENTRY_POINTS:
-        assert hasattr(raw, s), "libnpb.so does not export %s" % s
-        assert getattr(L, s).argtypes is not None, s
-    assert L.npb_policy_grad(None, None, None) == -1 and L.npb_policy_adam(None, 1e-3, 0.9, 0.999, 1e-5, None) == -1
-    assert L.npb_policy_update(None, None, 1e-3, 0.9, 0.999, 1e-5, None) == -1
-    assert L.npb_policy_get_grad(None, None, None) == -1 and L.npb_policy_get_stats(None, None, None) == -1 and L.npb_policy_get_theta(None, None, None) == -1
-    assert L.npb_policy_optimizer_get_state(None, None, None, None, None) == -1 and L.npb_policy_optimizer_set_state(None, None, None, 0, None) == -1
+def test_library_exports_and_binding_declares_them():
+    from nuclear_sim_amd import ppo
+    abi.check_entry_points(ENTRY_POINTS, [("npb_policy_grad", None, None, None), ("npb_policy_adam", None, 1e-3, 0.9, 0.999, 1e-5, None),
+                                          ("npb_policy_update", None, None, 1e-3, 0.9, 0.999, 1e-5, None), ("npb_policy_get_grad", None, None, None),
+                                          ("npb_policy_get_stats", None, None, None), ("npb_policy_get_theta", None, None, None),
+                                          ("npb_policy_optimizer_get_state", None, None, None, None, None),
+                                          ("npb_policy_optimizer_set_state", None, None, None, 0, None)])
     assert _lib.PPO_STATS == len(ppo.STATS) == 8
 
 
-def test_the_binding_lays_the_descriptor_out_as_the_compiler_does(tmp_path):
-    from nuclear_sim_amd import _lib
-    S = _lib.NpbPpoDesc
-    lines = ['  printf("%zu\\n", sizeof(npb_ppo_desc_t));\n']
-    lines += ['  printf("%%zu\\n", offsetof(npb_ppo_desc_t, %s));\n' % f[0] for f in S._fields_]
-    lines.append('  printf("%d\\n", NPB_PPO_STATS);\n')
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "npb.h"\nint main(void) {\n' + "".join(lines) + "  return 0;\n}\n")
-    exe = tmp_path / "probe"
-    subprocess.check_call([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == [ctypes.sizeof(S)] + [getattr(S, f[0]).offset for f in S._fields_] + [_lib.PPO_STATS]
+def test_the_binding_lays_the_descriptor_out_as_the_compiler_does():
+    structs = {"npb_ppo_desc_t": _lib.NpbPpoDesc}
+    got, values = abi.probe(structs, ["NPB_PPO_STATS"])
+    assert got == abi.layout(structs) and values == [_lib.PPO_STATS]
 
 
 def _desc(**members):
     """a valid descriptor: 300 rows of double obs, float act and float adv, every output, chains of 64"""
-    from nuclear_sim_amd import _lib
     d = _lib.NpbPpoDesc()
     d.obs, d.obs_type, d.act, d.act_type, d.logp_old, d.adv, d.ret, d.adv_type, d.count = A8, 1, A8 + 8, 0, A8 + 16, A8 + 24, A8 + 32, 0, 300
     d.logp_new, d.value_new, d.ratio = A8 + 40, A8 + 44, A8 + 48
@@ -78,17 +54,16 @@ def _desc(**members):
     return d
 
 
-def _why(L, d, cells=CELLS, axes=AXES):
-    r = L.npb_ppo_check(ctypes.byref(d), cells, axes)
-    return None if r is None else r.decode()
+def _why(d, cells=CELLS, axes=AXES):
+    return abi.why(abi.library().npb_ppo_check, ctypes.byref(d), cells, axes)
 
 
-def test_the_check_accepts_valid_descriptors(L):
-    assert _why(L, _desc()) is None
+def test_the_check_accepts_valid_descriptors():
+    assert _why(_desc()) is None
     for members in (dict(logp_new=None, value_new=None, ratio=None), dict(count=1), dict(rows_per_chain=32), dict(rows_per_chain=4096), dict(max_grad_norm=0.0),
                     dict(ent_coef=-0.5, vf_coef=0.0), dict(max_blocks=7), dict(obs_type=0, act_type=1, adv_type=1), dict(clip=0.999), dict(clip=1e-9)):
-        assert _why(L, _desc(**members)) is None, members
-    assert _why(L, _desc(), cells=256, axes=8) is None and _why(L, _desc(), cells=1, axes=1) is None
+        assert _why(_desc(**members)) is None, members
+    assert _why(_desc(), cells=256, axes=8) is None and _why(_desc(), cells=1, axes=1) is None
 
 
 REFUSALS = [
@@ -124,10 +99,10 @@ REFUSALS = [
 
 
 @pytest.mark.parametrize("what, members, kw, reason", REFUSALS, ids=[r[0] for r in REFUSALS])
-def test_the_check_names_every_refusal(L, what, members, kw, reason):
-    why = _why(L, _desc(**members), **kw)
+def test_the_check_names_every_refusal(what, members, kw, reason):
+    why = _why(_desc(**members), **kw)
     assert why is not None and why.startswith("npb_policy_grad: ") and reason in why, (what, why)
 
 
-def test_a_null_descriptor_is_refused_by_name(L):
-    assert L.npb_ppo_check(None, CELLS, AXES).decode() == "npb_policy_grad: a NULL descriptor"
+def test_a_null_descriptor_is_refused_by_name():
+    assert abi.library().npb_ppo_check(None, CELLS, AXES).decode() == "npb_policy_grad: a NULL descriptor"

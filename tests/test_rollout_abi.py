@@ -5,40 +5,24 @@ every refusal the header lists.  No compute calls.
 
 The header keeps NPB_VERSION where the suites of the entry-point groups before this one pin it: the new entry points are detected by name."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
+import abi_support as abi
+from nuclear_sim_amd import _lib
+
 ENTRY_POINTS = ("npb_set_rollout", "npb_rollout_check", "npb_rollout_begin", "npb_rollout_steps", "npb_rollout_cut", "npb_rollout_advantages")
-STRUCTS = {"npb_rollout_desc_t": "NpbRolloutDesc", "npb_rollout_advantages_desc_t": "NpbRolloutAdvantagesDesc"}
+STRUCTS = {"npb_rollout_desc_t": _lib.NpbRolloutDesc, "npb_rollout_advantages_desc_t": _lib.NpbRolloutAdvantagesDesc}
 A16 = 0x7000       # "device addresses" the check only looks at: never dereferenced
 CELLS, AXES = 12, 3
 
 
-@pytest.fixture(scope="module")
-def L():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
-    from nuclear_sim_amd import _lib
-    return _lib.load()
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "npb.h")).read()
-
-
 def test_header_declares_the_entry_points_the_maxima_and_the_rules_of_the_road():
-    text = _header()
-    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
-    for s in ENTRY_POINTS:
-        assert s in declared, s
-    assert int(re.search(r"#define NPB_ROLLOUT_HORIZON_MAX (\d+)", text).group(1)) == 4096
-    assert int(re.search(r"#define NPB_ROLLOUT_EXTRAS_MAX (\d+)", text).group(1)) == 8
-    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) == 154
+    text = abi.header_text()
+    assert set(ENTRY_POINTS) <= set(abi.declared())
+    assert abi.define("NPB_ROLLOUT_HORIZON_MAX") == 4096
+    assert abi.define("NPB_ROLLOUT_EXTRAS_MAX") == 8
+    assert abi.define("NPB_VERSION") == 154
     for words in ("termination wins", "the rollout does not wrap silently", "R is derived, not tuned", "ceil(T / max_episode_steps)",
                   "carry is a select, not a product with 1 - done", "the value of the TERMINAL state", "every operation rounded on its own",
                   "the recurrence is not restated as a scan", "No atomics", "are not stored: their bootstrap is 0",
@@ -47,33 +31,16 @@ def test_header_declares_the_entry_points_the_maxima_and_the_rules_of_the_road()
         assert words in text, words
 
 
-def test_library_exports_and_binding_declares_them(L):
-    raw = ctypes.CDLL(LIB)
-    for s in ENTRY_POINTS:
-        assert hasattr(raw, s), "libnpb.so does not export %s" % s
-        assert getattr(L, s).argtypes is not None, s
-    assert L.npb_set_rollout(None, None) == -1 and L.npb_rollout_begin(None, None) == -1 and L.npb_rollout_steps(None) == -1
-    assert L.npb_rollout_cut(None, None, None) == -1 and L.npb_rollout_advantages(None, None, None) == -1
+def test_library_exports_and_binding_declares_them():
+    abi.check_entry_points(ENTRY_POINTS, [("npb_set_rollout", None, None), ("npb_rollout_begin", None, None), ("npb_rollout_steps", None),
+                                          ("npb_rollout_cut", None, None, None), ("npb_rollout_advantages", None, None, None)])
 
 
-def test_the_binding_lays_the_descriptors_out_as_the_compiler_does(tmp_path):
-    from nuclear_sim_amd import _lib, rollout
-    lines = []
-    for c_name, py_name in STRUCTS.items():
-        lines.append('  printf("%%zu\\n", sizeof(%s));\n' % c_name)
-        lines += ['  printf("%%zu\\n", offsetof(%s, %s));\n' % (c_name, f[0]) for f in getattr(_lib, py_name)._fields_]
-    lines.append('  printf("%d\\n%d\\n%d\\n%d\\n%d\\n", NPB_ROLLOUT_TERMINATED, NPB_ROLLOUT_TRUNCATED, NPB_ROLLOUT_CUT, NPB_ROLLOUT_F32, NPB_ROLLOUT_F64);\n')
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "npb.h"\nint main(void) {\n' + "".join(lines) + "  return 0;\n}\n")
-    exe = tmp_path / "probe"
-    subprocess.check_call([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    want = []
-    for py_name in STRUCTS.values():
-        S = getattr(_lib, py_name)
-        want += [ctypes.sizeof(S)] + [getattr(S, f[0]).offset for f in S._fields_]
+def test_the_binding_lays_the_descriptors_out_as_the_compiler_does():
+    from nuclear_sim_amd import rollout
+    got, values = abi.probe(STRUCTS, ["NPB_ROLLOUT_TERMINATED", "NPB_ROLLOUT_TRUNCATED", "NPB_ROLLOUT_CUT", "NPB_ROLLOUT_F32", "NPB_ROLLOUT_F64"])
     B, D = _lib.ROLLOUT_BITS, _lib.ROLLOUT_DTYPES
-    assert got == want + [B["terminated"], B["truncated"], B["cut"], D["float32"], D["float64"]]
+    assert got == abi.layout(STRUCTS) and values == [B["terminated"], B["truncated"], B["cut"], D["float32"], D["float64"]]
     assert (B["terminated"], B["truncated"], B["cut"]) == (rollout.TERMINATED, rollout.TRUNCATED, rollout.CUT) == (1, 2, 4)
     assert (_lib.ROLLOUT_HORIZON_MAX, _lib.ROLLOUT_EXTRAS_MAX) == (rollout.HORIZON_MAX, rollout.EXTRAS_MAX) == (4096, 8)
 
@@ -82,33 +49,27 @@ class _Desc:
     """a valid descriptor: 16 slots, 2 extras, 4 rows per plant, every buffer given"""
 
     def __init__(self):
-        from nuclear_sim_amd import _lib
         self.d = d = _lib.NpbRolloutDesc()
         d.horizon, d.n_extras, d.final_rows = 16, 2, 4
         d.extras_in, d.obs, d.act, d.extra, d.final_obs = A16, A16 + 16, A16 + 32, A16 + 48, A16 + 64
         d.reward, d.ended, d.episode, d.final_row = A16 + 8, A16 + 1, A16 + 4, A16 + 12
 
 
-def _why(L, D, n=70, cells=CELLS, axes=AXES):
-    r = L.npb_rollout_check(ctypes.byref(D.d), n, cells, axes)
-    return None if r is None else r.decode()
+def _why(D, n=70, cells=CELLS, axes=AXES):
+    return abi.why(abi.library().npb_rollout_check, ctypes.byref(D.d), n, cells, axes)
 
 
-def _set(**members):
-    def change(D):
-        for name, value in members.items():
-            setattr(D.d, name, value)
-    return change
+_set = abi.set_members
 
 
-def test_the_check_accepts_valid_rollouts_and_null(L):
-    assert _why(L, _Desc()) is None
-    assert L.npb_rollout_check(None, 70, CELLS, AXES) is None
+def test_the_check_accepts_valid_rollouts_and_null():
+    assert _why(_Desc()) is None
+    assert abi.library().npb_rollout_check(None, 70, CELLS, AXES) is None
     for change, kw in ((_set(horizon=1), {}), (_set(horizon=4096), {}), (_set(n_extras=8), {}), (_set(act=None), {"axes": 0}),
                        (_set(n_extras=0, extras_in=None, extra=None), {}), (_set(final_rows=0, final_obs=None), {}),
                        (_set(final_rows=0), {}), (_set(), {"n": 1, "cells": 1, "axes": 8})):
         D = _Desc(); change(D)
-        assert _why(L, D, **kw) is None, kw
+        assert _why(D, **kw) is None, kw
 
 
 REFUSALS = [
@@ -142,8 +103,5 @@ REFUSALS = [
 
 
 @pytest.mark.parametrize("what, change, kw, reason", REFUSALS, ids=[r[0] for r in REFUSALS])
-def test_the_check_names_every_refusal(L, what, change, kw, reason):
-    D = _Desc()
-    change(D)
-    why = _why(L, D, **kw)
-    assert why is not None and why.startswith("npb_set_rollout: ") and reason in why, (what, why)
+def test_the_check_names_every_refusal(what, change, kw, reason):
+    abi.check_refusal(_Desc, _why, "npb_set_rollout: ", what, change, reason, kw)

@@ -5,69 +5,37 @@ refusal the header lists.  No compute calls.
 
 The header keeps NPB_VERSION where the suites of the entry-point groups before this one pin it: the new entry points are detected by name."""
 import ctypes
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
+import abi_support as abi
+from nuclear_sim_amd import _lib
+
 ENTRY_POINTS = ("npb_set_task", "npb_task_check", "npb_task_clear", "npb_task_get_state", "npb_task_set_state", "npb_set_episode_record_task")
-STRUCTS = {"npb_task_column_t": "NpbTaskColumn", "npb_task_term_t": "NpbTaskTerm", "npb_task_rule_t": "NpbTaskRule", "npb_task_desc_t": "NpbTaskDesc"}
+STRUCTS = {"npb_task_column_t": _lib.NpbTaskColumn, "npb_task_term_t": _lib.NpbTaskTerm, "npb_task_rule_t": _lib.NpbTaskRule, "npb_task_desc_t": _lib.NpbTaskDesc}
 A8 = 0x7000        # "device addresses" the check only looks at: never dereferenced
 F64, I32 = 0, 1    # NPB_KIND_*
 
 
-@pytest.fixture(scope="module")
-def L():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
-    from nuclear_sim_amd import _lib
-    return _lib.load()
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "npb.h")).read()
-
-
 def test_header_declares_the_entry_points_the_maxima_and_the_rules_of_the_road():
-    text = _header()
-    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
-    for s in ENTRY_POINTS:
-        assert s in declared, s
-    assert int(re.search(r"#define NPB_TASK_TERMS_MAX (\d+)", text).group(1)) == 16
-    assert int(re.search(r"#define NPB_TASK_RULES_MAX (\d+)", text).group(1)) == 8
-    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) == 154
+    text = abi.header_text()
+    assert set(ENTRY_POINTS) <= set(abi.declared())
+    assert abi.define("NPB_TASK_TERMS_MAX") == 16
+    assert abi.define("NPB_TASK_RULES_MAX") == 8
+    assert abi.define("NPB_VERSION") == 154
     for words in ("A NaN sample gives a NaN reward", "LEVELS, not edges", "keeps reporting done", "each product rounded before its add"):
         assert words in text, words
 
 
-def test_library_exports_and_binding_declares_them(L):
-    raw = ctypes.CDLL(LIB)
-    for s in ENTRY_POINTS:
-        assert hasattr(raw, s), "libnpb.so does not export %s" % s
-        assert getattr(L, s).argtypes is not None, s
-    assert L.npb_set_task(None, None) == -1 and L.npb_task_clear(None, None, None) == -1 and L.npb_set_episode_record_task(None, None) == -1
+def test_library_exports_and_binding_declares_them():
+    abi.check_entry_points(ENTRY_POINTS, [("npb_set_task", None, None), ("npb_task_clear", None, None, None),
+                                          ("npb_set_episode_record_task", None, None)])
 
 
-def test_the_binding_lays_the_descriptors_out_as_the_compiler_does(tmp_path):
-    from nuclear_sim_amd import _lib
-    lines = []
-    for c_name, py_name in STRUCTS.items():
-        lines.append('  printf("%%zu\\n", sizeof(%s));\n' % c_name)
-        lines += ['  printf("%%zu\\n", offsetof(%s, %s));\n' % (c_name, f[0]) for f in getattr(_lib, py_name)._fields_]
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "npb.h"\nint main(void) {\n' + "".join(lines) + "  return 0;\n}\n")
-    exe = tmp_path / "probe"
-    subprocess.check_call([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    want = []
-    for py_name in STRUCTS.values():
-        S = getattr(_lib, py_name)
-        want += [ctypes.sizeof(S)] + [getattr(S, f[0]).offset for f in S._fields_]
-    assert got == want
-    text = _header()
+def test_the_binding_lays_the_descriptors_out_as_the_compiler_does():
+    assert abi.probe(STRUCTS)[0] == abi.layout(STRUCTS)
+    text = abi.header_text()
     assert {name: int(re.search(r"NPB_TASK_%s = (\d+)" % name.upper(), text).group(1)) for name in _lib.TASK_KINDS} == _lib.TASK_KINDS
     assert {name: int(re.search(r"NPB_TASK_RULE_MODE_%s = (\d+)" % name.upper(), text).group(1)) for name in _lib.TASK_MODES} == _lib.TASK_MODES
 
@@ -76,7 +44,6 @@ class _Desc:
     """a valid descriptor with one term of every kind and one rule of every mode, and the ctypes arrays it points into"""
 
     def __init__(self):
-        from nuclear_sim_amd import _lib
         from nuclear_sim_amd.schema import SCHEMA
         self.lib = _lib
         level = SCHEMA.slot("pump.oil_level", 1)[1]
@@ -108,35 +75,27 @@ class _Desc:
         C.source.base, C.source.type, C.source.rows, C.source.row_stride, C.source.plant_stride = A8, self.lib.SAMPLE_TYPES[kind], 1, 0, 1
 
 
-def _why(L, D, n=70):
-    r = L.npb_task_check(ctypes.byref(D.d), n)
-    return None if r is None else r.decode()
+def _why(D, n=70):
+    return abi.why(abi.library().npb_task_check, ctypes.byref(D.d), n)
 
 
-def test_the_check_accepts_a_valid_task_and_null(L):
-    assert _why(L, _Desc()) is None
-    assert L.npb_task_check(None, 70) is None
+def test_the_check_accepts_a_valid_task_and_null():
+    assert _why(_Desc()) is None
+    assert abi.library().npb_task_check(None, 70) is None
     D = _Desc(); D.d.cause = None; D.d.terms_out = None       # both optional
-    assert _why(L, D) is None
+    assert _why(D) is None
     D = _Desc(); D.d.n_terms = 0                               # rules alone
-    assert _why(L, D) is None
+    assert _why(D) is None
     D = _Desc(); D.d.n_rules = 0                               # terms alone
-    assert _why(L, D) is None
+    assert _why(D) is None
     D = _Desc(); D.terms[0].weight = float("inf")              # an infinite weight is the caller's business
-    assert _why(L, D) is None
+    assert _why(D) is None
 
 
 NAN = float("nan")
 
 
-def _set(path, value):
-    def change(D):
-        obj = D
-        *head, last = path
-        for name in head:
-            obj = obj[name] if isinstance(name, int) else getattr(obj, name)
-        setattr(obj, last, value)
-    return change
+_set = abi.set_path
 
 
 REFUSALS = [
@@ -176,25 +135,19 @@ REFUSALS = [
 
 
 @pytest.mark.parametrize("what, change, reason", REFUSALS, ids=[r[0] for r in REFUSALS])
-def test_the_check_names_every_refusal(L, what, change, reason):
-    D = _Desc()
-    if change is None:
-        why = _why(L, D, n=0)
-    else:
-        change(D)
-        why = _why(L, D)
-    assert why is not None and why.startswith("npb_set_task: ") and reason in why, (what, why)
+def test_the_check_names_every_refusal(what, change, reason):
+    abi.check_refusal(_Desc, _why, "npb_set_task: ", what, change, reason)
 
 
-def test_the_check_refuses_a_task_with_neither_terms_nor_rules(L):
+def test_the_check_refuses_a_task_with_neither_terms_nor_rules():
     D = _Desc()
     D.d.n_terms = D.d.n_rules = 0
-    assert "neither reward terms nor termination rules" in _why(L, D)
+    assert "neither reward terms nor termination rules" in _why(D)
 
 
-def test_a_nan_ref_is_read_only_where_the_term_has_one(L):
+def test_a_nan_ref_is_read_only_where_the_term_has_one():
     """ref belongs to ABS_ERR / SQ_ERR with a constant; limit and direction to BEYOND / EXCESS: elsewhere they are not looked at"""
     D = _Desc()
     D.terms[0].ref = NAN; D.terms[0].limit = NAN; D.terms[0].direction = 5      # a VALUE term
     D.terms[2].ref = NAN                                                        # SQ_ERR against a column
-    assert _why(L, D) is None
+    assert _why(D) is None

@@ -2,49 +2,33 @@
 include/npb.h, exported by libnpb.so and bound; the watch list's validator and the builder of the sample request are pure host
 functions and are checked here without a device.  No compute calls."""
 import ctypes
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "nuclear_sim_amd", "libnpb.so")
+import abi_support as abi
+from nuclear_sim_amd import _lib
+
 ENTRY_POINTS = ("npb_sampler_create", "npb_sampler_sample", "npb_sampler_destroy")
 
 
-@pytest.fixture(scope="module")
-def built_lib():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "nuclear_sim_amd", "csrc"), "-s"])
-    return LIB
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "npb.h")).read()
-
-
 def test_header_declares_the_entry_points():
-    text = _header()
-    declared = set(re.findall(r"NPB_API[^;]*?\b(npb_\w+)\s*\(", text))
+    text, declared = abi.header_text(), set(abi.declared())
     for s in ENTRY_POINTS:
         assert s in declared, s
-    assert int(re.search(r"#define NPB_VERSION (\d+)", text).group(1)) >= 153
+    assert abi.define("NPB_VERSION") >= 153
 
 
-def test_library_exports_the_entry_points(built_lib):
-    lib = ctypes.CDLL(built_lib)
-    for s in ENTRY_POINTS:
-        assert hasattr(lib, s), "libnpb.so does not export %s" % s
-    assert lib.npb_version() >= 153
+def test_library_exports_the_entry_points():
+    abi.check_exported(ENTRY_POINTS)
+    assert abi.library().npb_version() >= 153
 
 
-def test_binding_declares_the_entry_points_and_the_request_as_the_header_lays_it_out(built_lib):
-    from nuclear_sim_amd import _lib
-    L = _lib.load()
+def test_binding_declares_the_entry_points_and_the_request_as_the_header_lays_it_out():
+    L = abi.library()
     for s in ENTRY_POINTS:
         assert getattr(L, s).argtypes is not None, s
-    text = _header()
+    text = abi.header_text()
     types = dict((name, int(v)) for name, v in re.findall(r"\b(NPB_SAMPLE_\w+) = (\d+)", text))
     assert {k: types["NPB_SAMPLE_" + k.upper()] for k in _lib.SAMPLE_TYPES} == _lib.SAMPLE_TYPES
     # the two structs: field names in the header's order
@@ -55,9 +39,8 @@ def test_binding_declares_the_entry_points_and_the_request_as_the_header_lays_it
     assert ctypes.sizeof(_lib.NpbSampleSource) == 32
 
 
-def test_null_handle_is_refused(built_lib):
-    from nuclear_sim_amd import _lib
-    L = _lib.load()
+def test_null_handle_is_refused():
+    L = abi.library()
     sampler = ctypes.c_int(7)
     desc = _lib.NpbSamplerDesc()
     assert L.npb_sampler_create(None, ctypes.byref(desc), ctypes.byref(sampler)) == -1
@@ -120,7 +103,6 @@ def test_the_request_of_the_reference_layout_lists_every_member_exactly_once():
 
 
 def test_the_side_sources_come_in_the_documented_order_with_the_documented_strides():
-    from nuclear_sim_amd import _lib
     cols, req = _reference_request(result=True, diagnostics=True, outputs=True, episodic=True, diag_pitch=256)
     sides = req["sides"]
     assert [(s["name"], s["type"], s["rows"], s["row_stride"], s["plant_stride"]) for s in sides] == [
