@@ -128,11 +128,9 @@ def test_pack_and_unpack_round_trip():
         policy.check(cells, A, actor, critic, "gelu")
 
 
-@pytest.mark.parametrize("cells, actor, critic", [(15, (7,), (33, 17)), (64, (64, 64), (64, 64))])
-def test_the_relu_statement_is_a_network(cells, actor, critic):
+def _a_network(cells, actor, critic, A=3, n=40):
     """against a float64 matmul to 1e-5: the fmaf chain, the padding and the layout compute an MLP"""
     rng = np.random.default_rng(11)
-    A, n = 3, 40
     a, c, log_std = _nets(rng, cells, A, actor, critic, scale=0.15)
     P = policy.Policy(cells, A, actor, critic, "relu", deterministic=True)
     P.load(policy.pack(a, c, log_std))
@@ -147,6 +145,34 @@ def test_the_relu_statement_is_a_network(cells, actor, critic):
     assert np.abs(act - ref(a)).max() < 1e-5 and np.abs(value - ref(c)[:, 0]).max() < 1e-5
     assert np.allclose(logp, -(A * policy.HALF_LOG_2PI) - log_std.astype(np.float64).sum(), rtol=0, atol=1e-6) and P.t == 0
     assert np.array_equal(P.values(x), value)
+    assert np.ptp(act, axis=0).min() > 0 and np.ptp(value) > 0
+
+
+@pytest.mark.parametrize("cells, actor, critic", [(15, (7,), (33, 17)), (64, (64, 64), (64, 64))])
+def test_the_relu_statement_is_a_network(cells, actor, critic):
+    _a_network(cells, actor, critic)
+
+
+@pytest.mark.parametrize("row", ["a", "d", "e", "f"])
+def test_the_relu_statement_is_a_network_at_the_shape_tables_rows(row):
+    """the rows of tests/test_policy_shapes_gpu.py's table with 65, 100, 255 and 66 cells, widths from 1 to 128 that differ between the
+    nets, 2, 5, 7 and 6 axes: the same float64 matmul, the same 1e-5"""
+    import test_policy_shapes_gpu as T
+    S = T.table_spec(row)
+    _a_network(S["cells"], S["actor"], S["critic"], S["n_axes"])
+
+
+@pytest.mark.parametrize("row", ["a", "b", "c", "d", "e", "f"])
+def test_the_explicit_rows_of_the_shape_table_reach_the_critic(row):
+    """a condition on the GPU test's inputs: the 70 rows policy_values is given have values that are finite and differ, float32 and
+    float64 rows alike (the critic of row e has ONE hidden unit, row f's chain ends in one)"""
+    import test_policy_shapes_gpu as T
+    S = T.table_spec(row)
+    P = policy.Policy(S["cells"], S["n_axes"], S["actor"], S["critic"], "relu", deterministic=True)
+    P.load(T.table_theta(row))
+    for dtype in (np.float32, np.float64):
+        v = P.values(T.table_rows(row, dtype))
+        assert np.isfinite(v).all() and np.ptp(v) > 0 and len(np.unique(v)) > 10
 
 
 def test_sampling_outputs_and_the_nan_rule():

@@ -7,7 +7,14 @@ one thing that may differ) and its Philox words exactly.
 The run is the features suite's: BatchedPlantEnv.action_test("oil_top_off", seeds=range(n), dt=5.0), every plant with a setpoint of its
 own, a handful of steps.  Weights come from a seeded generator, every row's L1 norm between 1 and 4.  The shapes are chosen for where
 tiles go wrong: one plant, one more than a tile of 32, two tiles, 257; 15, 64 and 256 cells (no multiple of 4, the small build's
-limit, the maximum); widths 7, (33, 17), (64, 64) and (128, 128, 128); 1, 3 and 8 axes; float and double features and controls."""
+limit, the maximum); widths 7, (33, 17), (64, 64) and (128, 128, 128); 1, 3 and 8 axes; float and double features and controls.
+
+Every case here lies wholly at or under the small build's limits (64 cells, widths of 64) or at the maximum.  The shapes BETWEEN them are
+test_policy_shapes_gpu.py's table, run through this file's helpers by the same contracts, each row the smallest case of something the
+launcher or the layer routine decides: a 65 cells with widths of 64 (cells alone one past the small build; in_pad 68); b 64 cells, actor
+(65,), critic (7,) (the actor alone one past; out_pad 96); c the same with the nets swapped (the widest layer is taken over BOTH nets);
+d 100 cells, (100, 96) / (127,), 5 axes (a last k-block with 4 live columns, 127 -> 128, a half-used Box-Muller pair); e 255 cells,
+(128,) / (1,), 7 axes (255 -> 256, a hidden width of 1); f 66 cells, (31, 32, 33) / (3, 2, 1), 6 axes (three layers around 32)."""
 import numpy as np
 import pytest
 import torch
@@ -126,13 +133,10 @@ def test_relu_deterministic_bit_for_bit(n, C, K, fdtype, actor, critic, A, cdtyp
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2
-@pytest.mark.parametrize("n, A, cdtype, seed", [(33, 3, F32, 7), (257, 8, F64, 2 ** 64 - 3), (64, 1, F32, 0)])
-def test_relu_sampling_the_words_the_noise_and_the_outputs(n, A, cdtype, seed):
-    """The Philox words exactly, z within 1e-12 of the statement's, and action and logp the statement's bits when it is fed the device's own
-    z -- which also pins that the step's launch and npb_policy_noise draw the same numbers"""
-    env = _env(n, 5, 3, F32, A, cdtype)
-    a, c, log_std = _weights(n, 15, A, (33, 17), (7,))
-    env.set_policy(a, c, log_std, activation="relu", seed=seed)
+def _hold_sampling(env, seed):
+    """three sampling steps of an env whose policy was set with ``seed``: the Philox words exactly, z within 1e-12 of the statement's, and
+    action, value and logp the statement's bits when it is fed the device's own z"""
+    n, A = env.n, env.policy_spec()["n_axes"]
     P = _statement(env)
     for t in range(3):
         z, words = env.policy_noise(t, words=True)
@@ -147,6 +151,17 @@ def test_relu_sampling_the_words_the_noise_and_the_outputs(n, A, cdtype, seed):
         _same(env.controls_input(), act, (t, "act")); _same(info["value"], value, (t, "value")); _same(info["logp"], logp, (t, "logp"))
     assert env.policy_state()["t"] == 3 and P.t == 3
     assert not np.array_equal(_np(env.policy_noise(0)), _np(env.policy_noise(1)))
+
+
+@pytest.mark.parametrize("n, A, cdtype, seed", [(33, 3, F32, 7), (257, 8, F64, 2 ** 64 - 3), (64, 1, F32, 0)])
+def test_relu_sampling_the_words_the_noise_and_the_outputs(n, A, cdtype, seed):
+    """The Philox words exactly, z within 1e-12 of the statement's, and action and logp the statement's bits when it is fed the device's own
+    z -- which also pins that the step's launch and npb_policy_noise draw the same numbers.  The axes counts 1, 3 and 8 are here; 2, 5
+    and 7 (with 5 and 7 the last pair is half used) run on the shape table's rows in test_policy_shapes_gpu.py, through the same body"""
+    env = _env(n, 5, 3, F32, A, cdtype)
+    a, c, log_std = _weights(n, 15, A, (33, 17), (7,))
+    env.set_policy(a, c, log_std, activation="relu", seed=seed)
+    _hold_sampling(env, seed)
     env.close()
 
 

@@ -199,3 +199,125 @@ def test_the_clipping_scales_by_the_pinned_norm_and_refusals_are_named():
         args.update(kw)
         with pytest.raises(ValueError, match=words.replace("(", r"\(").replace(")", r"\)")):
             ppo.check(**args)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the shape table
+# tests/test_policy_shapes_gpu.py holds the device to this statement at ragged shapes and other settings.  The statement has to be right
+# there first, and the inputs of those tests have to be what the tests take them for: both are checked here, without a GPU.
+def _table():
+    import test_policy_shapes_gpu as T      # (not at the top: that module imports this one)
+    return T
+
+
+@pytest.mark.parametrize("activation", ["relu", "tanh"])
+@pytest.mark.parametrize("row", ["a", "d", "e", "f"])
+def test_the_gradient_at_the_shape_tables_rows_against_float64_autograd(row, activation):
+    """70 rows in chains of 32, the actor and the critic of different shapes, 2 / 5 / 7 / 6 axes: the same yardstick and the same factor
+    of 4 as the first test of this file"""
+    T = _table()
+    S = T.table_spec(row)
+    shape = (S["cells"], S["n_axes"], S["actor"], S["critic"])
+    rng = np.random.default_rng({"a": 2, "d": 1, "e": 1, "f": 1}[row])
+    theta = make_theta(rng, *shape)
+    batch = make_batch(rng, theta, 70, *shape, activation)
+    g64, r = autograd(theta, *shape, activation, batch, torch.float64)
+    near = min(np.abs(r - (1 + CLIP)).min(), np.abs(r - (1 - CLIP)).min())
+    assert near > 1e-4, near
+    assert all(np.abs(g).max() > 0 for g in g64)      # (every tensor has a scale to be measured against)
+    g32, _ = autograd(theta, *shape, activation, batch, torch.float32)
+    out = ppo.gradient(theta, *shape, activation, clip=CLIP, vf_coef=VF, ent_coef=ENT, max_grad_norm=0.0, rows_per_chain=32, **batch)
+    assert 0.05 <= out["stats"]["clip_fraction"] <= 0.95 and out["stats"]["skipped"] == 0 and out["stats"]["count"] == 70
+    mine, yard = pooled(split(out["grad"], *shape), g64), pooled(g32, g64)
+    print("row %s %s: the statement %.3e, float32 autograd %.3e, ratio %.2f" % (row, activation, mine, yard, mine / yard))
+    assert mine <= 4 * yard
+    assert abs(out["stats"]["grad_norm"] - np.sqrt(sum((g ** 2).sum() for g in g64))) < 1e-5 * out["stats"]["grad_norm"]
+
+
+@pytest.mark.parametrize("row", ["a", "b", "c", "d", "e", "f"])
+def test_the_shape_tables_batches_take_both_branches_of_the_loss_clip(row):
+    """a condition on the inputs of the GPU tests, not a measurement: every batch they run has a clip fraction strictly inside (0.02,
+    0.98), skips nothing and has a gradient that is finite and not zero"""
+    T = _table()
+    theta = T.table_theta(row)
+    A = T.table_spec(row)["n_axes"]
+    for count, chain in T.GRADIENT_RUNS:
+        out = T.table_gradient(row, theta, T.table_batch(row, count, theta), chain)
+        assert 0.02 < out["stats"]["clip_fraction"] < 0.98, (count, out["stats"]["clip_fraction"])
+        assert out["stats"]["skipped"] == 0 and np.isfinite(out["grad"]).all() and out["grad"][:-A].any()
+
+
+def test_the_tanh_batch_of_row_d_has_no_ratio_on_a_clip_boundary():
+    T = _table()
+    S = T.table_spec("d")
+    theta = T.table_theta("d")
+    batch = T.table_batch("d", 97, theta, "tanh")
+    _, r = autograd(theta, S["cells"], S["n_axes"], S["actor"], S["critic"], "tanh", batch, torch.float64)
+    assert min(np.abs(r - (1 + CLIP)).min(), np.abs(r - (1 - CLIP)).min()) > 1e-3      # (ten times what the GPU test needs: its std is the device's)
+    out = T.table_gradient("d", theta, batch, 64, "tanh", max_grad_norm=0.0)
+    assert 0.02 < out["stats"]["clip_fraction"] < 0.98
+
+
+def test_every_setting_of_the_settings_tests_moves_the_statements_gradient():
+    """the batch of 97 rows on row b: each loss coefficient changes the gradient (and keeps both clip branches taken), ent_coef changes
+    log_std's entries alone, vf_coef = 0 makes the critic's entries +0.0, and the unclipped norm lies strictly between the two bounds of
+    the norm-clip test, of which the first then scales and the second does not"""
+    T = _table()
+    row, count, chain = T.SETTINGS_ROW, T.SETTINGS_COUNT, T.SETTINGS_CHAIN
+    A = T.table_spec(row)["n_axes"]
+    theta = T.table_theta(row)
+    batch = T.table_batch(row, count, theta)
+    default = T.table_gradient(row, theta, batch, chain)
+    for setting in T.SETTINGS:
+        out = T.table_gradient(row, theta, batch, chain, **setting)
+        assert not np.array_equal(out["grad"], default["grad"]), setting
+        assert 0.02 < out["stats"]["clip_fraction"] < 0.98, (setting, out["stats"]["clip_fraction"])
+        if setting.get("vf_coef") == 0.0:
+            assert not out["grad"][T.critic_slice(row)].view(np.int32).any()
+        if "ent_coef" in setting:
+            one, two = (T.table_gradient(row, theta, batch, chain, max_grad_norm=0.0, **kw)["grad"] for kw in ({}, setting))
+            assert np.array_equal(np.delete(one, np.s_[-2 * A:-A]).view(np.int32), np.delete(two, np.s_[-2 * A:-A]).view(np.int32))
+            assert (one[-2 * A:-A] != two[-2 * A:-A]).all()
+    norm = default["stats"]["grad_norm"]
+    assert T.NORM_LOW < norm < T.NORM_HIGH
+    low, high, off = (T.table_gradient(row, theta, batch, chain, max_grad_norm=x) for x in (T.NORM_LOW, T.NORM_HIGH, 0.0))
+    assert np.array_equal(high["grad"].view(np.int32), off["grad"].view(np.int32)) and not np.array_equal(low["grad"], off["grad"])
+    # a bad row at each tile seam is skipped in the statement too, and the rest of the batch goes on
+    dirty = {k: v.copy() for k, v in batch.items()}
+    dirty["obs"][31, 63], dirty["act"][32, 3], dirty["logp_old"][63], dirty["adv"][96], dirty["ret"][96] = np.nan, np.inf, np.nan, -np.inf, np.nan
+    out = T.table_gradient(row, theta, dirty, chain)
+    assert out["stats"]["skipped"] == 4 and np.flatnonzero(np.isnan(out["ratio"])).tolist() == [31, 32, 63, 96] and np.isfinite(out["grad"]).all()
+
+
+def test_the_dead_units_give_exact_zeros_and_adam_leaves_them():
+    T = _table()
+    row = T.SETTINGS_ROW
+    A = T.table_spec(row)["n_axes"]
+    theta = T.table_theta(row, dead=True)
+    mask = T.dead_mask(row)
+    out = T.table_gradient(row, theta, T.table_batch(row, T.SETTINGS_COUNT, theta), T.SETTINGS_CHAIN)
+    assert mask.sum() == (64 + 1 + 4) + (64 + 1 + 1) and not out["grad"].view(np.int32)[mask].any()
+    assert (out["grad"][:-A][~mask[:-A]] != 0).mean() > 0.9      # (and the rest of the gradient is there)
+    new, m, v, step = ppo.adam(theta, np.zeros_like(theta), np.zeros_like(theta), 0, out["grad"], A)
+    assert step == 1 and not m.view(np.int32)[mask].any() and not v.view(np.int32)[mask].any()
+    assert np.array_equal(new.view(np.int32)[mask], theta.view(np.int32)[mask])
+    assert (new[:-2 * A][~mask[:-2 * A]] != theta[:-2 * A][~mask[:-2 * A]]).mean() > 0.9
+
+
+def test_adam_at_large_loaded_steps_and_other_settings():
+    """the host's step_size and root at the loaded steps of the GPU test: finite, root exactly 1 once b2^step has underflowed; and the
+    loaded state (zeros, float denormals, entries near 1e30) goes through one update finite, under every setting the GPU test runs"""
+    T = _table()
+    rng = np.random.default_rng(2)
+    A, size = 4, 400
+    theta = rng.standard_normal(size).astype(np.float32)
+    g = (rng.standard_normal(size) * 10.0 ** rng.uniform(-4, 0, size)).astype(np.float32)
+    m, v = T.adam_state(size, A)
+    assert 0.999 ** 10_000_001 == 0.0 and np.sqrt(1.0 - 0.999 ** 10_000_001) == 1.0 and 0.0 < 0.999 ** 10_001 < 1e-4
+    default = ppo.adam(theta, m, v, 9, g, A)[0]
+    for step in T.ADAM_STEPS:
+        new, m1, v1, now = ppo.adam(theta, m, v, step, g, A)
+        assert now == step + 1 and np.isfinite(new).all() and np.isfinite(m1).all() and np.isfinite(v1).all() and (v1 >= 0).all()
+        assert not m1[-A:].any() and not v1[-A:].any()
+    for kw in T.ADAM_SETTINGS:
+        new = ppo.adam(theta, m, v, 9, g, A, **kw)[0]
+        assert np.isfinite(new).all() and not np.array_equal(new, default), kw
