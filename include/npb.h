@@ -1485,9 +1485,42 @@ NPB_API int npb_collect(NpbHandle *h, int steps, double *obs, double *reward, ui
  * float [theta_count]) and step.  The optimiser's buffers and the chains' workspace belong to the policy: allocated on first use, grown on
  * demand, dropped with it.  NPB_EINVAL by name before any device work: no policy set, and what npb_ppo_check refuses.
  * The gradient kernel (npb_ppo.hip) runs on the f32 matrix cores (v_mfma_f32_32x32x2_f32), a workgroup a chain, no atomics.
- * Not here: value-loss clipping, a shared trunk, learning-rate schedules and target_kl early stopping (the caller reads stats), half
- * types, gradient exchange between devices. */
+ * Not here: a shared trunk, learning-rate schedules (host arithmetic: lr is an argument of every update), half types, gradient
+ * exchange between devices.
+ *
+ * THE OPTIONS (npb_ppo_more_t; the entry points below that take one; a binding detects them by name, NPB_VERSION stays 154).  With
+ * more == NULL, and with clip_vf == 0 and kl_limit == 0, every launch computes the bits of the calls above.
+ * Value-loss clipping (clip_vf > 0; value_old device [count] float, what the rollout recorded in the policy's value slot), the max form
+ * of baselines' PPO2.  Per row, in double, every operation rounded on its own, behind diff = (double)v - ret:
+ *   dvo = (double)v - (double)value_old;  dc = dvo < -clip_vf ? -clip_vf : (dvo > clip_vf ? clip_vf : dvo)
+ *   vc = (double)value_old + dc;  diffc = vc - ret;  sq = diff * diff;  sqc = diffc * diffc
+ *   use = sqc > sq (strict);  out = dvo < -clip_vf or dvo > clip_vf (strict)
+ *   value loss = 0.5 * (use ? sqc : sq);  dv = (float)((vf_coef * (use ? (out ? 0.0 : diffc) : diff)) / count);  vf_clipped = out ? 1.0 : 0.0
+ * With clip_vf > 0 a value_old that is not finite makes the row a skipped row; with clip_vf == 0 value_old is not read and may be NULL.
+ * More statistics, always formed: four more per-row doubles, +0.0 on a skipped row -- ret, ret * ret, diff, diff * diff (always the
+ * unclipped diff) -- summed as the other per-row doubles are.  From the sums S_r, S_rr, S_d, S_dd and m = count - skipped:
+ *   vr = S_rr / m - (S_r / m) * (S_r / m);  vd = S_dd / m - (S_d / m) * (S_d / m);  explained_variance = 1.0 - vd / vr
+ * THE quiet NaN when m < 1 or not vr > 0.  more, NPB_PPO_STATS_MORE doubles: vf_clip_fraction (the pinned sum of vf_clipped over count),
+ * explained_variance, applied, stopped (1.0 / 0.0: what the gate made of the last update; 1.0, 0.0 with no gate).
+ * The gate (kl_limit > 0; target_kl early stopping as SB3 takes it, kl_limit = 1.5 * target_kl formed by the caller in double), on the
+ * device between the finish kernel and the Adam kernel, so nothing is read back per update:
+ *   stopped' = stopped or (approx_kl > kl_limit)  (strict; a NaN approx_kl does not stop);  applied = not stopped'
+ * An update that is not applied leaves theta, std, m and v exactly as they were; its gradient and all its statistics are still formed.
+ * Once stopped, every later update up to npb_policy_train_end is not applied.  step counts applied updates only: they are a prefix, so
+ * update i (0-based) since npb_policy_train_begin, if applied, is step step0 + i + 1.
+ * npb_ppo_more_check(more, count): the host-only validator, NULL = accepted (a NULL more is), else the reason: a clip_vf or kl_limit that
+ * is negative or not finite; clip_vf > 0 with value_old NULL; a misaligned value_old (4-byte aligned).
+ * npb_policy_grad_more(h, desc, more, stream): npb_policy_grad with the options; kl_limit > 0 is refused by name (the gate is an
+ * update's).  npb_policy_update_more(h, desc, more, lr, b1, b2, eps, stream): npb_policy_update with the options.
+ * npb_policy_train_begin(h, stream) clears stopped and applied on the device and remembers step0 = step.  npb_policy_train_end(h,
+ * applied, stream) is THE ONE READ-BACK: it waits for the stream, reads the count of applied updates (into *applied unless NULL), sets
+ * step = step0 + applied and disarms the gate.  Between the two, refused by name: npb_policy_optimizer_get_state,
+ * npb_policy_optimizer_set_state, npb_policy_adam, a second npb_policy_train_begin, and an update with kl_limit == 0 (every update of
+ * the pair is gated: that keeps the applied ones a prefix).  Outside a pair an update with kl_limit > 0 and npb_policy_train_end are
+ * refused by name.  A policy set again or dropped takes an open pair with it.
+ * npb_policy_get_stats_more(h, more, stream) copies into a DEVICE buffer, double [NPB_PPO_STATS_MORE], nothing read back. */
 #define NPB_PPO_STATS 8
+#define NPB_PPO_STATS_MORE 4
 typedef struct npb_ppo_desc_t {
   const void *obs; int obs_type;             /* device [count][K * C]; NPB_FEATURES_F32 | NPB_FEATURES_F64 */
   const void *act; int act_type;             /* device [count][A]; NPB_CONTROLS_F32 | NPB_CONTROLS_F64 */
@@ -1508,6 +1541,18 @@ NPB_API int npb_policy_get_stats(NpbHandle *h, double *stats, void *stream);
 NPB_API int npb_policy_get_theta(NpbHandle *h, float *theta, void *stream);
 NPB_API int npb_policy_optimizer_get_state(NpbHandle *h, float *m, float *v, uint64_t *step, void *stream);
 NPB_API int npb_policy_optimizer_set_state(NpbHandle *h, const float *m, const float *v, uint64_t step, void *stream);
+typedef struct npb_ppo_more_t {
+  const float *value_old;                    /* device [count], or NULL with clip_vf == 0 */
+  double clip_vf;                            /* 0 = off */
+  double kl_limit;                           /* 0 = this update neither raises nor obeys the gate */
+} npb_ppo_more_t;
+NPB_API const char *npb_ppo_more_check(const npb_ppo_more_t *more, int count);
+NPB_API int npb_policy_grad_more(NpbHandle *h, const npb_ppo_desc_t *desc, const npb_ppo_more_t *more, void *stream);
+NPB_API int npb_policy_update_more(NpbHandle *h, const npb_ppo_desc_t *desc, const npb_ppo_more_t *more, double lr, double b1, double b2, double eps,
+                                   void *stream);
+NPB_API int npb_policy_train_begin(NpbHandle *h, void *stream);
+NPB_API int npb_policy_train_end(NpbHandle *h, uint32_t *applied, void *stream);
+NPB_API int npb_policy_get_stats_more(NpbHandle *h, double *more, void *stream);
 
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the

@@ -11,6 +11,7 @@ import os
 
 import numpy as np
 
+from .ppo_abi import PPO_STATS_MORE, NpbPpoMore
 from .schema import PARAMS, SCHEMA
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -957,6 +958,9 @@ class NpbPpoDesc(ctypes.Structure):
                 ("rows_per_chain", ctypes.c_int), ("max_blocks", ctypes.c_int)]
 
 
+# npb_ppo_more_t, the options of one update, and NPB_PPO_STATS_MORE: nuclear_sim_amd/ppo_abi.py (tests/test_ppo_options_abi.py holds its layout)
+
+
 def controls_request(axes, interval: int = 1, dtype="float32", heat_source: int = 0) -> dict:
     """What ``BatchedPlantEnv.set_controls`` asks of npb_set_controls, from the caller's words; a pure function, host only, so an axis that
     cannot work is refused (ValueError, naming it) before any device work.
@@ -1231,6 +1235,13 @@ ENTRY_POINTS = (
         "npb_policy_get_theta": (None, [_vp, _vp, _vp]),
         "npb_policy_optimizer_get_state": (None, [_vp, _vp, _vp, _P(_u64), _vp]),
         "npb_policy_optimizer_set_state": (None, [_vp, _vp, _vp, _u64, _vp])}),
+    ("npb_policy_grad_more", {     # training's options: value-loss clipping, the target_kl gate, more statistics
+        "npb_ppo_more_check": (_cs, [_P(NpbPpoMore), _ci]),
+        "npb_policy_grad_more": (None, [_vp, _P(NpbPpoDesc), _P(NpbPpoMore), _vp]),
+        "npb_policy_update_more": (None, [_vp, _P(NpbPpoDesc), _P(NpbPpoMore), _cd, _cd, _cd, _cd, _vp]),
+        "npb_policy_train_begin": (None, [_vp, _vp]),
+        "npb_policy_train_end": (None, [_vp, _P(ctypes.c_uint32), _vp]),
+        "npb_policy_get_stats_more": (None, [_vp, _vp, _vp])}),
     ("npb_rollout_minibatch", {     # pinned moments, the keyed permutation and the minibatch gather over a rollout
         "npb_rollout_moments": (None, [_vp, _P(NpbMomentsDesc), _vp]),
         "npb_rollout_permutation": (None, [_vp, _i64, _P(ctypes.c_uint32), _i64, _i64, _vp, _vp]),

@@ -2438,8 +2438,10 @@ static int ppo_room(NpbHandle *h, const char *who, size_t chains) {
   if (!O.stats) {
     const size_t floats = ((size_t)h->pol.theta_count + 3) & ~(size_t)3, tree = npb_moments_workspace((int64_t)h->pol.std);
     char *dev = nullptr;
-    if (int rc = attachment_alloc(h, who, "the gradient and the optimiser's state", nullptr, 0, (NPB_PPO_STATS + tree) * sizeof(double) + 3 * floats * sizeof(float), &dev)) return rc;
-    O.stats = (double *)dev; O.tree = O.stats + NPB_PPO_STATS; O.tree_count = tree;
+    if (int rc = attachment_alloc(h, who, "the gradient and the optimiser's state", nullptr, 0,
+                                  (NPB_PPO_STATS + NPB_PPO_STATS_MORE + 1 + tree) * sizeof(double) + 3 * floats * sizeof(float), &dev)) return rc;
+    O.stats = (double *)dev; O.more = O.stats + NPB_PPO_STATS; O.gate = (uint32_t *)(O.more + NPB_PPO_STATS_MORE);      /* (two words in one double's room) */
+    O.tree = O.more + NPB_PPO_STATS_MORE + 1; O.tree_count = tree;
     O.grad = (float *)(O.tree + tree); O.m = O.grad + floats; O.v = O.m + floats; O.floats = floats; O.step = 0;
   }
   if (chains > O.chains) {      /* (hipFree of the old one waits for a launch that still reads it) */
@@ -2450,39 +2452,95 @@ static int ppo_room(NpbHandle *h, const char *who, size_t chains) {
   }
   return NPB_OK;
 }
-static int ppo_grad(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, void *stream) {
+const char *npb_ppo_more_check(const npb_ppo_more_t *M, int count) {
+  if (!M) return nullptr;
+  (void)count;      /* (value_old's length: nothing on the host can see it) */
+  if (!(M->clip_vf >= 0.0) || !(M->clip_vf - M->clip_vf == 0.0)) return "npb_policy_grad_more: clip_vf must be finite and >= 0 (0 = off)";
+  if (!(M->kl_limit >= 0.0) || !(M->kl_limit - M->kl_limit == 0.0)) return "npb_policy_grad_more: kl_limit must be finite and >= 0 (0 = no gate)";
+  if (M->clip_vf > 0.0 && !M->value_old) return "npb_policy_grad_more: clip_vf > 0 and value_old is NULL";
+  if ((uintptr_t)M->value_old & 3u) return "npb_policy_grad_more: a misaligned value_old (4-byte aligned)";
+  return nullptr;
+}
+static const char *const g_train_open = ": between npb_policy_train_begin and npb_policy_train_end (npb_policy_train_end first)";
+static const char *adam_refusal(double lr, double b1, double b2, double eps) {
+  if (!(lr - lr == 0.0) || !(b1 >= 0.0 && b1 < 1.0) || !(b2 >= 0.0 && b2 < 1.0) || !(eps >= 0.0) || !(eps - eps == 0.0))
+    return ": lr must be finite, b1 and b2 lie in [0, 1), eps be finite and >= 0";
+  return nullptr;
+}
+static int ppo_grad(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, void *stream) {
   if (!h->pol.theta) return fail_who(h, who, g_no_policy);
   if (const char *why = npb_ppo_check(D, h->pol.cells, h->pol.n_axes)) return fail(h, NPB_EINVAL, why);
+  if (const char *why = npb_ppo_more_check(M, D->count)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
   if (int rc = ppo_room(h, who, ((size_t)D->count + D->rows_per_chain - 1) / D->rows_per_chain)) return rc;
-  npb_launch_ppo_grad(&h->pol, &h->ppo, D, (hipStream_t)stream);
+  npb_launch_ppo_grad(&h->pol, &h->ppo, D, M, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
-static int ppo_adam(NpbHandle *h, const char *who, double lr, double b1, double b2, double eps, void *stream) {
+static int ppo_adam(NpbHandle *h, const char *who, double lr, double b1, double b2, double eps, int gated, void *stream) {
   if (!h->pol.theta) return fail_who(h, who, g_no_policy);
-  if (!(lr - lr == 0.0) || !(b1 >= 0.0 && b1 < 1.0) || !(b2 >= 0.0 && b2 < 1.0) || !(eps >= 0.0) || !(eps - eps == 0.0))
-    return fail_who(h, who, ": lr must be finite, b1 and b2 lie in [0, 1), eps be finite and >= 0");
+  if (const char *why = adam_refusal(lr, b1, b2, eps)) return fail_who(h, who, why);
   if (!h->ppo.stats) return fail_who(h, who, ": no gradient formed yet (npb_policy_grad first)");
   NPB_USE_DEVICE(h);
   h->ppo.step++;
-  npb_launch_ppo_adam(&h->pol, &h->ppo, lr, b1, b2, eps, (hipStream_t)stream);
+  npb_launch_ppo_adam(&h->pol, &h->ppo, lr, b1, b2, eps, gated, (hipStream_t)stream);
   npb_launch_policy_repack(&h->pol, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
 int npb_policy_grad(NpbHandle *h, const npb_ppo_desc_t *D, void *stream) {
   if (!h) return NPB_EINVAL;
-  return ppo_grad(h, "npb_policy_grad", D, stream);
+  return ppo_grad(h, "npb_policy_grad", D, nullptr, stream);
+}
+int npb_policy_grad_more(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (M && M->kl_limit > 0.0) return fail(h, NPB_EINVAL, "npb_policy_grad_more: kl_limit > 0: the gate is an update's (npb_policy_update_more)");
+  return ppo_grad(h, "npb_policy_grad_more", D, M, stream);
 }
 int npb_policy_adam(NpbHandle *h, double lr, double b1, double b2, double eps, void *stream) {
   if (!h) return NPB_EINVAL;
-  return ppo_adam(h, "npb_policy_adam", lr, b1, b2, eps, stream);
+  if (h->ppo.armed) return fail_who(h, "npb_policy_adam", g_train_open);
+  return ppo_adam(h, "npb_policy_adam", lr, b1, b2, eps, 0, stream);
+}
+static int ppo_update(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, double lr, double b1, double b2, double eps, void *stream) {
+  const int gated = M && M->kl_limit > 0.0;
+  if (gated && !h->ppo.armed) return fail_who(h, who, ": kl_limit > 0 outside npb_policy_train_begin / npb_policy_train_end (npb_policy_train_begin first)");
+  if (!gated && h->ppo.armed) return fail_who(h, who, ": kl_limit == 0 between npb_policy_train_begin and npb_policy_train_end: every update of the pair is gated");
+  if (gated && h->pol.theta)      /* (a gated gradient counts itself applied: its Adam step must not be refused behind it) */
+    if (const char *why = adam_refusal(lr, b1, b2, eps)) return fail_who(h, who, why);
+  if (int rc = ppo_grad(h, who, D, M, stream)) return rc;
+  return ppo_adam(h, who, lr, b1, b2, eps, gated, stream);
 }
 int npb_policy_update(NpbHandle *h, const npb_ppo_desc_t *D, double lr, double b1, double b2, double eps, void *stream) {
   if (!h) return NPB_EINVAL;
-  if (int rc = ppo_grad(h, "npb_policy_update", D, stream)) return rc;
-  return ppo_adam(h, "npb_policy_update", lr, b1, b2, eps, stream);
+  return ppo_update(h, "npb_policy_update", D, nullptr, lr, b1, b2, eps, stream);
+}
+int npb_policy_update_more(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, double lr, double b1, double b2, double eps, void *stream) {
+  if (!h) return NPB_EINVAL;
+  return ppo_update(h, "npb_policy_update_more", D, M, lr, b1, b2, eps, stream);
+}
+int npb_policy_train_begin(NpbHandle *h, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->pol.theta) return fail_who(h, "npb_policy_train_begin", g_no_policy);
+  if (h->ppo.armed) return fail_who(h, "npb_policy_train_begin", g_train_open);
+  NPB_USE_DEVICE(h);
+  if (int rc = ppo_room(h, "npb_policy_train_begin", 0)) return rc;
+  NPB_HIP(h, hipMemsetAsync(h->ppo.gate, 0, 2 * sizeof(uint32_t), (hipStream_t)stream));
+  h->ppo.armed = 1; h->ppo.step0 = h->ppo.step;
+  return NPB_OK;
+}
+int npb_policy_train_end(NpbHandle *h, uint32_t *applied, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->pol.theta) return fail_who(h, "npb_policy_train_end", g_no_policy);
+  if (!h->ppo.armed) return fail_who(h, "npb_policy_train_end", ": no npb_policy_train_begin before it");
+  NPB_USE_DEVICE(h);
+  h->ppo.armed = 0; h->ppo.step = h->ppo.step0;      /* (whatever HIP says below, nothing stays armed) */
+  uint32_t n = 0;
+  NPB_HIP(h, hipMemcpyAsync(&n, h->ppo.gate + NPD_PPO_GATE_APPLIED, sizeof n, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));
+  h->ppo.step = h->ppo.step0 + n;
+  if (applied) *applied = n;
+  return NPB_OK;
 }
 /* a copy between device buffers on the stream */
 static int ppo_copy_out(NpbHandle *h, const char *who, const void *src, void *dst, size_t bytes, size_t align, bool needs_grad, void *stream) {
@@ -2501,6 +2559,10 @@ int npb_policy_get_stats(NpbHandle *h, double *stats, void *stream) {
   if (!h) return NPB_EINVAL;
   return ppo_copy_out(h, "npb_policy_get_stats", h->ppo.stats, stats, NPB_PPO_STATS * sizeof(double), 8, true, stream);
 }
+int npb_policy_get_stats_more(NpbHandle *h, double *more, void *stream) {
+  if (!h) return NPB_EINVAL;
+  return ppo_copy_out(h, "npb_policy_get_stats_more", h->ppo.more, more, NPB_PPO_STATS_MORE * sizeof(double), 8, true, stream);
+}
 int npb_policy_get_theta(NpbHandle *h, float *theta, void *stream) {
   if (!h) return NPB_EINVAL;
   return ppo_copy_out(h, "npb_policy_get_theta", h->pol.theta, theta, (size_t)h->pol.theta_count * sizeof(float), 4, false, stream);
@@ -2509,6 +2571,7 @@ int npb_policy_optimizer_get_state(NpbHandle *h, float *m, float *v, uint64_t *s
   if (!h) return NPB_EINVAL;
   if (!h->pol.theta) return fail_who(h, "npb_policy_optimizer_get_state", g_no_policy);
   if (!m || !v || !step) return fail(h, NPB_EINVAL, "npb_policy_optimizer_get_state: NULL output");
+  if (h->ppo.armed) return fail_who(h, "npb_policy_optimizer_get_state", g_train_open);
   NPB_USE_DEVICE(h);
   if (int rc = ppo_room(h, "npb_policy_optimizer_get_state", 0)) return rc;
   const size_t bytes = (size_t)h->pol.theta_count * sizeof(float);
@@ -2522,6 +2585,7 @@ int npb_policy_optimizer_set_state(NpbHandle *h, const float *m, const float *v,
   if (!h) return NPB_EINVAL;
   if (!h->pol.theta) return fail_who(h, "npb_policy_optimizer_set_state", g_no_policy);
   if (!m || !v) return fail(h, NPB_EINVAL, "npb_policy_optimizer_set_state: NULL input");
+  if (h->ppo.armed) return fail_who(h, "npb_policy_optimizer_set_state", g_train_open);
   NPB_USE_DEVICE(h);
   if (int rc = ppo_room(h, "npb_policy_optimizer_set_state", 0)) return rc;
   const size_t bytes = (size_t)h->pol.theta_count * sizeof(float);

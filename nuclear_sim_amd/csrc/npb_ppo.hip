@@ -17,13 +17,16 @@
  *      k of 16 j, so a half-wave stores 128 contiguous bytes.  db: a lane an output, the 32 rows added in order.  back (npd_ppo_back): the
  *      row as the row of D, k as its column, j as the k dimension; theta's own row-major W[j][k] IS the B operand, consecutive lanes on
  *      consecutive k; then the activation's derivative from h, and delta'[k][row] into the other of two LDS buffers.
- *   5. the critic the same way, its hidden activations over the actor's: forward, the value's seed and loss, backward.
+ *   5. the critic the same way, its hidden activations over the actor's: forward, the value's seed and loss (with clip_vf > 0 the
+ *      clipped branch: the larger of the two squares and its own derivative), the four terms of explained_variance, backward.
  *   6. the per-row doubles of the tile added in row order onto the chain's running sums, a lane a quantity.
  * No atomics, nothing depends on the launch order, no scratch.  LDS: the small build (K*C <= 64, widths <= 64) 6 x 8.25 KiB and 6 KiB; the
  * large one 33 + 5 x 16.5 KiB and the same, 122 KiB of gfx950's 160.
  * THE REDUCE KERNEL: a lane a parameter: its partials widened and added in ascending chain order, narrowed once; log_std's from the dls
  * sums; then the first level of the pinned tree over the squares.  THE FINISH KERNEL, one workgroup: the tree's further levels, the norm,
- * the scale, the statistics.  THE ADAM KERNEL: a lane a parameter, and log_std's lane refreshes std. */
+ * the scale, the statistics, and with a gate armed (kl_limit > 0) the gate: one lane ORs approx_kl > kl_limit into the training block's
+ * stopped word and counts an applied update, with ordinary stores.  THE ADAM KERNEL: a lane a parameter, and log_std's lane refreshes
+ * std; its gated twin reads the stopped word first and stores nothing when it is set. */
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "npb_ppo.h"
@@ -31,6 +34,7 @@
 
 typedef struct {
   npb_ppo_desc_t D;
+  npb_ppo_more_t M;                    /* every option off: {NULL, 0.0, 0.0} */
   int n_chains;
   float *partials; size_t floats;      /* [n_chains][floats] */
   double *chain_stats;                 /* [n_chains][NPD_PPO_ROWVALS] */
@@ -154,6 +158,7 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_grad_kernel(npb_poli
           const size_t p = base + tid;
           const double old = (double)D.logp_old[p], adv = npd_ppo_load(D.adv, D.adv_type, p), ret = npd_ppo_load(D.ret, D.adv_type, p);
           b = !(old - old == 0.0) || !(adv - adv == 0.0) || !(ret - ret == 0.0);
+          if (R.M.clip_vf > 0.0) { const float vo = R.M.value_old[p]; b |= !(vo - vo == 0.0f); }
           for (int a = 0; a < A; a++) { const double x = npd_ppo_load(D.act, D.act_type, p * A + a); b |= !(x - x == 0.0); }
         }
         bad[tid] = b;
@@ -218,9 +223,23 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_grad_kernel(npb_poli
         const float v = head[tid];
         if (D.value_new) D.value_new[p] = skipped ? (float)qnan : v;
         if (skipped) return;
-        const double diff = (double)v - npd_ppo_load(D.ret, D.adv_type, p), scaled = D.vf_coef * diff, sq = diff * diff;
+        const double ret = npd_ppo_load(D.ret, D.adv_type, p), diff = (double)v - ret, sq = diff * diff;
+        double seed = diff, lsq = sq;
+        if (R.M.clip_vf > 0.0) {      /* the max form: the larger of the two squares, and its own derivative */
+          const double c = R.M.clip_vf, vo = (double)R.M.value_old[p], dvo = (double)v - vo;
+          const double dc = dvo < -c ? -c : (dvo > c ? c : dvo), vc = vo + dc, diffc = vc - ret, sqc = diffc * diffc;
+          const bool use = sqc > sq, out = dvo < -c || dvo > c;
+          seed = use ? (out ? 0.0 : diffc) : diff;
+          lsq = use ? sqc : sq;
+          rowv[NPD_PPO_VF_CLIPPED * NPD_POLICY_TILE + tid] = out ? 1.0 : 0.0;
+        }
+        const double scaled = D.vf_coef * seed;
         da[tid] = (float)(scaled / n);
-        rowv[NPD_PPO_VALUE_LOSS * NPD_POLICY_TILE + tid] = 0.5 * sq;
+        rowv[NPD_PPO_VALUE_LOSS * NPD_POLICY_TILE + tid] = 0.5 * lsq;
+        rowv[NPD_PPO_RET * NPD_POLICY_TILE + tid] = ret;
+        rowv[NPD_PPO_RET2 * NPD_POLICY_TILE + tid] = ret * ret;
+        rowv[NPD_PPO_DIFF * NPD_POLICY_TILE + tid] = diff;
+        rowv[NPD_PPO_DIFF2 * NPD_POLICY_TILE + tid] = sq;
       });
       /* 6. the tile's per-row doubles onto the chain's sums, rows ascending */
       if (tid < NPD_PPO_ROWVALS)
@@ -252,39 +271,64 @@ __global__ __launch_bounds__(NPD_TREE) void npb_ppo_reduce_kernel(npb_policy_t P
   if (lane == 0 && (size_t)blockIdx.x * NPD_TREE < P.std) O.tree[blockIdx.x] = s[0];
 }
 
-/* one workgroup: the tree's further levels, the norm, the scale over every entry but std's, the statistics */
+/* one workgroup: the tree's further levels, the norm, the scale over every entry but std's, the statistics (the chains' sums first, a
+ * lane a quantity, so that no two of them wait for each other inside one wave), the gate */
 __global__ __launch_bounds__(NPD_TREE) void npb_ppo_finish_kernel(npb_policy_t P, npd_ppo_run_t R, npb_ppo_t O) {
-  __shared__ double s[NPD_TREE];
+  __shared__ double s[NPD_TREE], sums[NPD_PPO_ROWVALS];
   const int lane = threadIdx.x;
   const double *in = npd_tree_levels(O.tree, ((size_t)P.std + NPD_TREE - 1) / NPD_TREE, s, lane);
   const double norm = sqrt(in[0]);
+  /* every per-row quantity's sum over the chains, ascending, a lane a quantity: one pass of coalesced loads, the waves beyond the first
+   * already scaling */
+  if (lane < NPD_PPO_ROWVALS) {
+    double sum = 0.0;
+    for (int c = 0; c < R.n_chains; c++) sum = sum + R.chain_stats[(size_t)c * NPD_PPO_ROWVALS + lane];
+    sums[lane] = sum;
+  }
   if (R.D.max_grad_norm > 0.0) {
     const double bound = norm + 1e-6, ratio = R.D.max_grad_norm / bound, scale = ratio < 1.0 ? ratio : 1.0;
     for (size_t e = lane; e < P.std; e += NPD_TREE) O.grad[e] = (float)((double)O.grad[e] * scale);
   }
-  if (lane < 5) {
-    const int slot[5] = {NPD_PPO_POLICY_LOSS, NPD_PPO_VALUE_LOSS, -1, NPD_PPO_KL, NPD_PPO_CLIPPED};
-    const double n = (double)R.D.count;
+  __syncthreads();
+  const double n = (double)R.D.count;
+  if (lane == 0) O.stats[0] = sums[NPD_PPO_POLICY_LOSS] / n;
+  else if (lane == 1) O.stats[1] = sums[NPD_PPO_VALUE_LOSS] / n;
+  else if (lane == 2) {
     double sum = 0.0;
-    if (lane == 2) {
-      for (int a = 0; a < P.n_axes; a++) { const double t = (double)P.theta[P.log_std + a] + 0.5; sum = sum + (t + 0.9189385332046727); }
-      O.stats[2] = sum;
-    } else {
-      for (int c = 0; c < R.n_chains; c++) sum = sum + R.chain_stats[(size_t)c * NPD_PPO_ROWVALS + slot[lane]];
-      O.stats[lane] = sum / n;
+    for (int a = 0; a < P.n_axes; a++) { const double t = (double)P.theta[P.log_std + a] + 0.5; sum = sum + (t + 0.9189385332046727); }
+    O.stats[2] = sum;
+  } else if (lane == 3) O.stats[3] = sums[NPD_PPO_KL] / n;
+  else if (lane == 4) O.stats[4] = sums[NPD_PPO_CLIPPED] / n;
+  else if (lane == 5) O.stats[5] = sums[NPD_PPO_SKIPPED];
+  else if (lane == 6) O.stats[6] = norm;
+  else if (lane == 7) O.stats[7] = n;
+  else if (lane == 8) O.more[0] = sums[NPD_PPO_VF_CLIPPED] / n;
+  else if (lane == 9) {      /* explained_variance from the four pinned sums over the rows that were not skipped */
+    const double m = n - sums[NPD_PPO_SKIPPED];
+    double ev = (double)__builtin_nanf("");
+    if (m >= 1.0) {
+      const double mr = sums[NPD_PPO_RET] / m, md = sums[NPD_PPO_DIFF] / m, er = sums[NPD_PPO_RET2] / m, ed = sums[NPD_PPO_DIFF2] / m;
+      const double mr2 = mr * mr, md2 = md * md, vr = er - mr2, vd = ed - md2;
+      if (vr > 0.0) { const double q = vd / vr; ev = 1.0 - q; }
     }
-  } else if (lane == 5) {
-    double sum = 0.0;
-    for (int c = 0; c < R.n_chains; c++) sum = sum + R.chain_stats[(size_t)c * NPD_PPO_ROWVALS + NPD_PPO_SKIPPED];
-    O.stats[5] = sum;
-  } else if (lane == 6) O.stats[6] = norm;
-  else if (lane == 7) O.stats[7] = (double)R.D.count;
+    O.more[1] = ev;
+  } else if (lane == 10) {      /* the gate: one lane, ordinary stores */
+    double applied = 1.0, stopped = 0.0;
+    if (R.M.kl_limit > 0.0) {
+      const double kl = sums[NPD_PPO_KL] / n;
+      const bool stop = O.gate[NPD_PPO_GATE_STOPPED] != 0u || kl > R.M.kl_limit;
+      O.gate[NPD_PPO_GATE_STOPPED] = stop ? 1u : 0u;
+      if (!stop) O.gate[NPD_PPO_GATE_APPLIED] = O.gate[NPD_PPO_GATE_APPLIED] + 1u;
+      applied = stop ? 0.0 : 1.0; stopped = stop ? 1.0 : 0.0;
+    }
+    O.more[2] = applied; O.more[3] = stopped;
+  }
 }
 
 /* Adam, a lane a parameter, std's slots apart: in double, every operation rounded on its own, each result narrowed once; log_std's lane
  * then refreshes std = (float)exp((double)log_std') */
-__global__ __launch_bounds__(256) void npb_ppo_adam_kernel(npb_policy_t P, npb_ppo_t O, double step_size, double root, double b1, double c1, double b2, double c2,
-                                                           double eps) {
+__device__ __forceinline__ void npd_ppo_adam(const npb_policy_t &P, const npb_ppo_t &O, double step_size, double root, double b1, double c1, double b2, double c2,
+                                             double eps) {
   const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= P.std) return;
   const double g = (double)O.grad[e];
@@ -297,16 +341,27 @@ __global__ __launch_bounds__(256) void npb_ppo_adam_kernel(npb_policy_t P, npb_p
   O.m[e] = m; O.v[e] = v; P.theta[e] = t;
   if (e >= P.log_std) P.theta[e + P.n_axes] = (float)exp((double)t);
 }
+__global__ __launch_bounds__(256) void npb_ppo_adam_kernel(npb_policy_t P, npb_ppo_t O, double step_size, double root, double b1, double c1, double b2, double c2,
+                                                           double eps) {
+  npd_ppo_adam(P, O, step_size, root, b1, c1, b2, c2, eps);
+}
+/* the same behind the gate: an update that is not applied stores nothing */
+__global__ __launch_bounds__(256) void npb_ppo_adam_gated_kernel(npb_policy_t P, npb_ppo_t O, double step_size, double root, double b1, double c1, double b2,
+                                                                 double c2, double eps) {
+  if (O.gate[NPD_PPO_GATE_STOPPED] != 0u) return;
+  npd_ppo_adam(P, O, step_size, root, b1, c1, b2, c2, eps);
+}
 
-static npd_ppo_run_t npd_ppo_run(const npb_ppo_t *O, const npb_ppo_desc_t *D) {
+static npd_ppo_run_t npd_ppo_run(const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M) {
   npd_ppo_run_t R = {};
   R.D = *D;
+  if (M) R.M = *M;
   R.n_chains = (int)(((int64_t)D->count + D->rows_per_chain - 1) / D->rows_per_chain);
   R.partials = O->partials; R.floats = O->floats; R.chain_stats = O->chain_stats;
   return R;
 }
-extern "C" void npb_launch_ppo_grad(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_desc_t *D, hipStream_t stream) {
-  const npd_ppo_run_t R = npd_ppo_run(O, D);
+extern "C" void npb_launch_ppo_grad(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, hipStream_t stream) {
+  const npd_ppo_run_t R = npd_ppo_run(O, D, M);
   const int cap = D->max_blocks > 0 ? D->max_blocks : 2048;
   const dim3 grid((unsigned)(R.n_chains < cap ? R.n_chains : cap)), block(NPD_POLICY_LANES);
   if (P->cells <= 64 && P->width_max <= 64) hipLaunchKernelGGL((npb_ppo_grad_kernel<64, 64>), grid, block, 0, stream, *P, R);
@@ -314,8 +369,10 @@ extern "C" void npb_launch_ppo_grad(const npb_policy_t *P, const npb_ppo_t *O, c
   hipLaunchKernelGGL(npb_ppo_reduce_kernel, dim3((P->theta_count + NPD_TREE - 1) / NPD_TREE), dim3(NPD_TREE), 0, stream, *P, R, *O);
   hipLaunchKernelGGL(npb_ppo_finish_kernel, dim3(1), dim3(NPD_TREE), 0, stream, *P, R, *O);
 }
-extern "C" void npb_launch_ppo_adam(const npb_policy_t *P, const npb_ppo_t *O, double lr, double b1, double b2, double eps, hipStream_t stream) {
+extern "C" void npb_launch_ppo_adam(const npb_policy_t *P, const npb_ppo_t *O, double lr, double b1, double b2, double eps, int gated, hipStream_t stream) {
   /* (formed here and not by the caller: this file's flags keep the host's division IEEE too) */
   const double step = (double)O->step, step_size = lr / (1.0 - pow(b1, step)), root = sqrt(1.0 - pow(b2, step));
-  hipLaunchKernelGGL(npb_ppo_adam_kernel, dim3((P->std + 255u) / 256u), dim3(256), 0, stream, *P, *O, step_size, root, b1, 1.0 - b1, b2, 1.0 - b2, eps);
+  const dim3 grid((P->std + 255u) / 256u), block(256);
+  if (gated) hipLaunchKernelGGL(npb_ppo_adam_gated_kernel, grid, block, 0, stream, *P, *O, step_size, root, b1, 1.0 - b1, b2, 1.0 - b2, eps);
+  else hipLaunchKernelGGL(npb_ppo_adam_kernel, grid, block, 0, stream, *P, *O, step_size, root, b1, 1.0 - b1, b2, 1.0 - b2, eps);
 }

@@ -2003,15 +2003,48 @@ class BatchedPlantEnv:
         d.rows_per_chain, d.max_blocks = int(rows_per_chain), int(max_blocks)
         return d, [obs, act, old, adv, ret]
 
+    def _ppo_more(self, batch, count, clip_vf, value_old, kl_limit=0.0):
+        """``(npb_ppo_more_t or None, tensors kept alive)``: the options of one update.  None with every option off: the caller then
+        makes the plain call.  ``value_old`` defaults to the batch's extras slot the policy was set with for ``"value"``"""
+        clip_vf, kl_limit = float(clip_vf), float(kl_limit)
+        if not 0.0 <= clip_vf < float("inf"):
+            raise ValueError("clip_vf must be finite and >= 0 (0 = off), not %r" % (clip_vf,))
+        if clip_vf == 0.0 and kl_limit == 0.0:
+            return None, []
+        if not hasattr(self.L, "npb_policy_grad_more"):
+            raise _lib.NpbError("libnpb.so has no npb_policy_grad_more: rebuild")
+        m, held = _lib.NpbPpoMore(), []
+        m.clip_vf, m.kl_limit = clip_vf, kl_limit
+        if clip_vf > 0.0:
+            if value_old is None:
+                value_old = batch.get("value_old")
+            if value_old is None:
+                slot = self._pol["spec"]["extras"]["value"]
+                if batch.get("extra") is None or slot < 0:
+                    raise ValueError("clip_vf > 0 and no value_old: pass it, or set the policy with extras naming 'value' so the rollout records it")
+                value_old = batch["extra"][..., slot]
+            value_old = torch.as_tensor(value_old)
+            if value_old.dtype != torch.float32 or value_old.numel() != count:
+                raise ValueError("value_old must be float32 with one value a row (%d)" % count)
+            value_old = value_old.to(device=self.device).contiguous().reshape(-1)
+            m.value_old = value_old.data_ptr()
+            held.append(value_old)
+        return m, held
+
     def policy_grad(self, batch, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0, max_grad_norm: float = 0.5,
-                    rows_per_chain: int = 256, diagnostics: bool = False, max_blocks: int = 0) -> dict:
-        """The PPO loss of one minibatch and its gradient through both nets, on the device (npb_policy_grad): ``{"grad", "stats"}`` --
-        ``grad`` float32 in theta's layout, clipped to ``max_grad_norm`` (0 = off), ``stats`` float64 [8] in ``ppo.STATS``'s order, both
-        device tensors, nothing read back -- and with ``diagnostics`` also ``logp_new``, ``value_new`` (float32) and ``ratio`` (float64),
+                    rows_per_chain: int = 256, diagnostics: bool = False, max_blocks: int = 0, clip_vf: float = 0.0, value_old=None) -> dict:
+        """The PPO loss of one minibatch and its gradient through both nets, on the device (npb_policy_grad): ``{"grad", "stats",
+        "more"}`` -- ``grad`` float32 in theta's layout, clipped to ``max_grad_norm`` (0 = off), ``stats`` float64 [8] in ``ppo.STATS``'s
+        order, ``more`` float64 [4] in ``ppo.STATS_MORE``'s, all device tensors, nothing read back -- and with ``diagnostics`` also
+        ``logp_new``, ``value_new`` (float32) and ``ratio`` (float64),
         [count] each.  ``batch``: a dict as ``rollout_minibatches`` yields (``logp_old`` is the extras slot the policy was set with) or one
         with ``obs``, ``act``, ``logp_old``, ``adv``, ``ret``.  ``rows_per_chain`` pins the order of the sums over rows; no bit depends on
-        ``max_blocks``.  ``nuclear_sim_amd.ppo.gradient`` is the same in numpy: bit for bit with relu when fed the device's ``ratio``."""
+        ``max_blocks``.  ``clip_vf`` > 0 clips the value loss around ``value_old`` (float32 [count]; by default the batch's extras slot
+        the policy was set with for ``"value"``).  ``nuclear_sim_amd.ppo.gradient`` is the same in numpy: bit for bit with relu when fed
+        the device's ``ratio``."""
         d, held = self._ppo_desc(batch, clip, vf_coef, ent_coef, max_grad_norm, rows_per_chain, max_blocks)
+        more, held_more = self._ppo_more(batch, d.count, clip_vf, value_old)
+        held = held + held_more
         pol = self._pol
         out = {}
         with torch.cuda.device(self.device):
@@ -2022,9 +2055,16 @@ class BatchedPlantEnv:
                 d.logp_new, d.value_new, d.ratio = out["logp_new"].data_ptr(), out["value_new"].data_ptr(), out["ratio"].data_ptr()
             out["grad"] = torch.zeros(pol["theta"].numel(), dtype=torch.float32, device=self.device)
             out["stats"] = torch.zeros(_lib.PPO_STATS, dtype=torch.float64, device=self.device)
-        _lib.check(self.L.npb_policy_grad(self._h, ctypes.byref(d), self._stream()), self._h)
+            if hasattr(self.L, "npb_policy_get_stats_more"):
+                out["more"] = torch.zeros(_lib.PPO_STATS_MORE, dtype=torch.float64, device=self.device)
+        if more is None:
+            _lib.check(self.L.npb_policy_grad(self._h, ctypes.byref(d), self._stream()), self._h)
+        else:
+            _lib.check(self.L.npb_policy_grad_more(self._h, ctypes.byref(d), ctypes.byref(more), self._stream()), self._h)
         _lib.check(self.L.npb_policy_get_grad(self._h, ctypes.c_void_p(out["grad"].data_ptr()), self._stream()), self._h)
         _lib.check(self.L.npb_policy_get_stats(self._h, ctypes.c_void_p(out["stats"].data_ptr()), self._stream()), self._h)
+        if "more" in out:
+            _lib.check(self.L.npb_policy_get_stats_more(self._h, ctypes.c_void_p(out["more"].data_ptr()), self._stream()), self._h)
         pol["ppo_held"] = held      # (alive while the launches read them)
         return out
 
@@ -2036,23 +2076,69 @@ class BatchedPlantEnv:
         pol["moved"] = True
 
     def policy_train(self, batch_size, epochs: int = 1, seed: int = 0, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0,
-                     max_grad_norm: float = 0.5, rows_per_chain: int = 256, lr: float = 3e-4, betas=(0.9, 0.999), eps: float = 1e-5,
-                     **minibatches) -> torch.Tensor:
+                     max_grad_norm: float = 0.5, rows_per_chain: int = 256, lr=3e-4, betas=(0.9, 0.999), eps: float = 1e-5,
+                     clip_vf: float = 0.0, target_kl=None, more: bool = False, **minibatches):
         """The optimiser's half of a PPO iteration: ``rollout_minibatches(batch_size, epochs, seed, **minibatches)`` and one
         npb_policy_update -- gradient and Adam step -- per minibatch.  Returns every update's stats as ONE device tensor [updates, 8]
-        (``ppo.STATS``'s order); no host synchronisation.  ``collect``, ``rollout_advantages``, ``policy_train`` is a whole iteration."""
+        (``ppo.STATS``'s order), and with ``more=True`` ``(stats, more [updates, 4])`` (``ppo.STATS_MORE``'s order).  ``collect``,
+        ``rollout_advantages``, ``policy_train`` is a whole iteration.
+        ``lr``: a float, a sequence with one value per update, or a callable ``lr(i, updates)``: a schedule is host arithmetic.
+        ``clip_vf`` > 0 clips the value loss around the values the rollout recorded (the policy's ``"value"`` extras slot).
+        ``target_kl``: SB3's early stop, taken on the device: the first update whose ``approx_kl`` exceeds ``1.5 * target_kl``, and every
+        later one of this call, is formed and reported but not applied; Adam's step counts the applied ones.
+        With ``target_kl=None`` there is no host synchronisation.  With it set the call ends with exactly ONE stream-synchronising
+        read-back, of the count of applied updates (npb_policy_train_end) -- one per iteration, none per update -- so a checkpoint taken
+        after this call returns sees the right step."""
         pol = self._on("_pol")
-        rows = []
-        for batch in self.rollout_minibatches(batch_size, epochs, seed, **minibatches):
-            d, held = self._ppo_desc(batch, clip, vf_coef, ent_coef, max_grad_norm, rows_per_chain)
-            with torch.cuda.device(self.device):
-                row = torch.zeros(_lib.PPO_STATS, dtype=torch.float64, device=self.device)
-            _lib.check(self.L.npb_policy_update(self._h, ctypes.byref(d), float(lr), float(betas[0]), float(betas[1]), float(eps), self._stream()), self._h)
-            _lib.check(self.L.npb_policy_get_stats(self._h, ctypes.c_void_p(row.data_ptr()), self._stream()), self._h)
-            pol["moved"], pol["ppo_held"] = True, held
-            rows.append(row)
+        kl_limit = 0.0
+        if target_kl is not None:
+            if not float(target_kl) > 0.0 or float(target_kl) == float("inf"):
+                raise ValueError("target_kl must be finite and > 0 (None = off), not %r" % (target_kl,))
+            kl_limit = 1.5 * float(target_kl)
+        batches = self.rollout_minibatches(batch_size, epochs, seed, **minibatches)
+        rates = None
+        if callable(lr) or isinstance(lr, (list, tuple, np.ndarray)):
+            # the number of updates, as rollout_minibatches cuts them (its batches are views of one buffer: they cannot be listed first)
+            t = self._last_advantages(self._on("_roll"), minibatches.get("advantages"))[2]
+            N = self.n if minibatches.get("unit", "transition") == "plant" else t * self.n
+            B = min(int(batch_size), N)
+            updates = int(epochs) * (N // B if minibatches.get("drop_last") else -(-N // B))
+            rates = [float(lr(i, updates)) for i in range(updates)] if callable(lr) else [float(x) for x in lr]
+            if len(rates) != updates:
+                raise ValueError("lr has %d values and the call makes %d updates" % (len(rates), updates))
+        rows, mores = [], []
+        b1, b2, eps = float(betas[0]), float(betas[1]), float(eps)
+        if kl_limit:
+            if not hasattr(self.L, "npb_policy_train_begin"):
+                raise _lib.NpbError("libnpb.so has no npb_policy_train_begin: rebuild")
+            _lib.check(self.L.npb_policy_train_begin(self._h, self._stream()), self._h)
+        try:
+            for i, batch in enumerate(batches):
+                rate = float(lr) if rates is None else rates[i]
+                d, held = self._ppo_desc(batch, clip, vf_coef, ent_coef, max_grad_norm, rows_per_chain)
+                m, held_more = self._ppo_more(batch, d.count, clip_vf, None, kl_limit)
+                with torch.cuda.device(self.device):
+                    row = torch.zeros(_lib.PPO_STATS, dtype=torch.float64, device=self.device)
+                    if more:
+                        mores.append(torch.zeros(_lib.PPO_STATS_MORE, dtype=torch.float64, device=self.device))
+                if m is None:
+                    _lib.check(self.L.npb_policy_update(self._h, ctypes.byref(d), rate, b1, b2, eps, self._stream()), self._h)
+                else:
+                    _lib.check(self.L.npb_policy_update_more(self._h, ctypes.byref(d), ctypes.byref(m), rate, b1, b2, eps, self._stream()), self._h)
+                _lib.check(self.L.npb_policy_get_stats(self._h, ctypes.c_void_p(row.data_ptr()), self._stream()), self._h)
+                if more:
+                    _lib.check(self.L.npb_policy_get_stats_more(self._h, ctypes.c_void_p(mores[-1].data_ptr()), self._stream()), self._h)
+                pol["moved"], pol["ppo_held"] = True, held + held_more
+                rows.append(row)
+        finally:
+            if kl_limit:      # (the one read-back; and whatever was refused above, nothing stays armed)
+                applied = ctypes.c_uint32()
+                _lib.check(self.L.npb_policy_train_end(self._h, ctypes.byref(applied), self._stream()), self._h)
         with torch.cuda.device(self.device):
-            return torch.stack(rows) if rows else torch.zeros((0, _lib.PPO_STATS), dtype=torch.float64, device=self.device)
+            stats = torch.stack(rows) if rows else torch.zeros((0, _lib.PPO_STATS), dtype=torch.float64, device=self.device)
+            if not more:
+                return stats
+            return stats, (torch.stack(mores) if mores else torch.zeros((0, _lib.PPO_STATS_MORE), dtype=torch.float64, device=self.device))
 
     def policy_optimizer_state(self) -> Dict[str, np.ndarray]:
         """Adam's state for a checkpoint (npb_policy_optimizer_get_state): ``m``, ``v`` float32 in theta's layout, and ``step``"""

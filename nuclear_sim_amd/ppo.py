@@ -54,13 +54,50 @@ operation rounded on its own, each result narrowed once:
 std's slots are skipped in all three; then ``std[a] = (float)exp((double)log_std'[a])``.
 
 ``stats`` is float64: ``{policy_loss, value_loss, entropy, approx_kl, clip_fraction, skipped, grad_norm, count}`` (``STATS`` has the
-order); the first five are means over ``count`` (the entropy is the same for every row)."""
+order); the first five are means over ``count`` (the entropy is the same for every row).
+
+THE OPTIONS.  Left at their defaults, every function here returns the bits it returned before they existed.
+
+VALUE-LOSS CLIPPING (``value_old`` [count] float32, ``clip_vf`` a double, 0.0 = off), the max form of baselines' PPO2.  Per row, in
+double, every operation rounded on its own, behind ``diff = (double)v - ret``:
+
+    dvo  = (double)v - (double)value_old
+    dc   = dvo < -clip_vf ? -clip_vf : (dvo > clip_vf ? clip_vf : dvo)
+    vc   = (double)value_old + dc;   diffc = vc - ret
+    sq   = diff * diff;   sqc = diffc * diffc
+    use  = sqc > sq                                 (strict)
+    out  = dvo < -clip_vf or dvo > clip_vf          (strict)
+    value loss = 0.5 * (use ? sqc : sq)
+    dv   = (float)((vf_coef * (use ? (out ? 0.0 : diffc) : diff)) / count)
+    vf_clipped = out ? 1.0 : 0.0
+
+With ``clip_vf > 0`` a ``value_old`` that is not finite makes the row a skipped row; with ``clip_vf == 0`` it is not read and may be absent.
+
+MORE STATISTICS, always formed.  Four more per-row doubles, +0.0 on a skipped row: ``ret``, ``ret * ret``, ``diff`` and ``diff * diff``
+(always the unclipped ``diff``), summed as the other per-row doubles are.  From the sums ``S_r, S_rr, S_d, S_dd`` and ``m = count -
+skipped`` (``explained_variance``):
+
+    vr = S_rr / m - (S_r / m) * (S_r / m);   vd = S_dd / m - (S_d / m) * (S_d / m);   explained_variance = 1.0 - vd / vr
+
+THE quiet NaN when ``m < 1`` or not ``vr > 0``.  ``more`` is float64: ``{vf_clip_fraction, explained_variance, applied, stopped}``
+(``STATS_MORE`` has the order); ``vf_clip_fraction`` is the pinned sum of ``vf_clipped`` over ``count``.
+
+THE GATE (``gate``), target_kl early stopping as SB3 takes it: the check comes before the optimiser step of the offending minibatch.
+``kl_limit = 1.5 * target_kl``, formed by the caller in double.
+
+    stopped' = stopped or (approx_kl > kl_limit)      (strict; a NaN approx_kl does not stop)
+    applied  = not stopped'
+
+An update that is not applied leaves theta, ``std``, ``m`` and ``v`` exactly as they were; its gradient and all its statistics are still
+formed.  Once stopped, every later update of the same training call is not applied.  Adam's ``step`` counts applied updates only: within
+one call they are a prefix, so update ``i`` (0-based), if applied, is step ``step0 + i + 1``."""
 import numpy as np
 
 from .policy import HALF_LOG_2PI, activate, fmaf, layer, unpack
 from .rollout import _tree
 
 STATS = ("policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "skipped", "grad_norm", "count")
+STATS_MORE = ("vf_clip_fraction", "explained_variance", "applied", "stopped")
 ROWS_PER_CHAIN = 256
 TILE = 32
 
@@ -75,6 +112,16 @@ def check(count, rows_per_chain, clip):
         raise ValueError("clip must lie inside (0, 1), not %r" % (clip,))
 
 
+def check_clip_vf(clip_vf, value_old):
+    """``clip_vf`` as a float: refused, by name, when negative or not finite, or positive with no ``value_old``"""
+    clip_vf = float(clip_vf)
+    if not 0.0 <= clip_vf < float("inf"):
+        raise ValueError("clip_vf must be finite and >= 0 (0 = off), not %r" % (clip_vf,))
+    if clip_vf > 0.0 and value_old is None:
+        raise ValueError("clip_vf > 0 needs value_old")
+    return clip_vf
+
+
 def forward_keep(net, x, activation):
     """``(inputs, head)``: the float32 input of every layer of the net (the rows first, then each hidden activation) and the head's
     outputs, exactly ``policy.forward``"""
@@ -84,10 +131,12 @@ def forward_keep(net, x, activation):
     return hs, layer(hs[-1], *net[-1])
 
 
-def rows(mean, v, log_std, std, act, logp_old, adv, ret, bad, clip, vf_coef, ratio=None):
+def rows(mean, v, log_std, std, act, logp_old, adv, ret, bad, clip, vf_coef, ratio=None, value_old=None, clip_vf=0.0):
     """the per-row epilogue: a dict of ``dmean`` float32 [n, A], ``dv`` float32 [n], ``dls`` float64 [n, A], ``policy_loss``,
-    ``value_loss``, ``kl``, ``clipped``, ``skipped`` float64 [n], and ``logp_new``, ``value_new`` float32 [n], ``ratio`` float64 [n].
-    ``bad``: the rows with a feature that is not finite.  ``ratio``: the device's own r in place of numpy's exp"""
+    ``value_loss``, ``kl``, ``clipped``, ``skipped`` float64 [n], and ``logp_new``, ``value_new`` float32 [n], ``ratio`` float64 [n];
+    and ``vf_clipped``, ``ret``, ``ret2``, ``diff``, ``diff2`` float64 [n], the options' per-row doubles, with ``vf_use`` (not summed).
+    ``bad``: the rows with a feature that is not finite.  ``ratio``: the device's own r in place of numpy's exp.  ``value_old`` float32
+    [n] and ``clip_vf`` > 0: the value loss clipped"""
     mean = np.asarray(mean, dtype=np.float32).astype(np.float64)
     n, A = mean.shape
     count = np.float64(n)
@@ -98,6 +147,10 @@ def rows(mean, v, log_std, std, act, logp_old, adv, ret, bad, clip, vf_coef, rat
     adv, ret = (np.asarray(x).astype(np.float64).reshape(n) for x in (adv, ret))
     vd = np.asarray(v, dtype=np.float32).astype(np.float64).reshape(n)
     skipped = np.asarray(bad, dtype=bool) | ~np.isfinite(act).all(axis=1) | ~np.isfinite(old) | ~np.isfinite(adv) | ~np.isfinite(ret)
+    clip_vf = np.float64(check_clip_vf(clip_vf, value_old))
+    if clip_vf > 0.0:
+        vo = np.asarray(value_old, dtype=np.float32).astype(np.float64).reshape(n)
+        skipped = skipped | ~np.isfinite(vo)
     with np.errstate(all="ignore"):
         d = (act - mean) / std[None, :]
         lp = np.full(n, -(A * HALF_LOG_2PI))
@@ -110,16 +163,26 @@ def rows(mean, v, log_std, std, act, logp_old, adv, ret, bad, clip, vf_coef, rat
         c = np.where(clipped, 0.0, -(adv * r))
         dmean = (((c[:, None] * d) / std[None, :]) / count).astype(np.float32)
         diff = vd - ret
-        dv = ((vf_coef * diff) / count).astype(np.float32)
+        sq = diff * diff
+        seed, lsq, out_vf, use = diff, sq, np.zeros(n, dtype=bool), np.zeros(n, dtype=bool)
+        if clip_vf > 0.0:
+            dvo = vd - vo
+            dc = np.where(dvo < -clip_vf, -clip_vf, np.where(dvo > clip_vf, clip_vf, dvo))
+            diffc = (vo + dc) - ret
+            sqc = diffc * diffc
+            use, out_vf = sqc > sq, (dvo < -clip_vf) | (dvo > clip_vf)
+            seed, lsq = np.where(use, np.where(out_vf, 0.0, diffc), diff), np.where(use, sqc, sq)
+        dv = ((vf_coef * seed) / count).astype(np.float32)
         dls = (c[:, None] * (d * d - 1.0)) / count
         rc = np.where(r < lo, lo, np.where(r > hi, hi, r))
         first, second = r * adv, rc * adv
         ploss = -np.where(second < first, second, first)
-        vloss = 0.5 * (diff * diff)
+        vloss = 0.5 * lsq
         kl = (r - 1.0) - lr
     out = {"dmean": dmean, "dv": dv, "dls": dls, "policy_loss": ploss, "value_loss": vloss, "kl": kl, "clipped": clipped.astype(np.float64),
-           "logp_new": lp.astype(np.float32), "value_new": np.asarray(v, dtype=np.float32).reshape(n).copy(), "ratio": np.array(r, dtype=np.float64)}
-    for name in ("dmean", "dv", "dls", "policy_loss", "value_loss", "kl", "clipped"):
+           "logp_new": lp.astype(np.float32), "value_new": np.asarray(v, dtype=np.float32).reshape(n).copy(), "ratio": np.array(r, dtype=np.float64),
+           "vf_clipped": out_vf.astype(np.float64), "ret": ret.copy(), "ret2": ret * ret, "diff": diff.copy(), "diff2": sq.copy(), "vf_use": use.astype(np.float64)}
+    for name in ("dmean", "dv", "dls", "policy_loss", "value_loss", "kl", "clipped", "vf_clipped", "ret", "ret2", "diff", "diff2", "vf_use"):
         out[name][skipped] = 0.0
     for name in ("logp_new", "value_new", "ratio"):
         out[name][skipped] = np.nan
@@ -223,10 +286,32 @@ def clip_grad(grad, n_axes, max_grad_norm):
     return g, np.float64(norm)
 
 
+def explained_variance(s_r, s_rr, s_d, s_dd, m):
+    """``1 - var(ret - v) / var(ret)`` from the four pinned sums over the ``m`` rows that were not skipped; THE quiet NaN when ``m < 1``
+    or not ``vr > 0``"""
+    m = np.float64(m)
+    if not m >= 1.0:
+        return np.float64(np.nan)
+    with np.errstate(all="ignore"):
+        mr, md = np.float64(s_r) / m, np.float64(s_d) / m
+        vr = np.float64(s_rr) / m - mr * mr
+        vd = np.float64(s_dd) / m - md * md
+        if not vr > 0.0:
+            return np.float64(np.nan)
+        return np.float64(1.0) - vd / vr
+
+
+def gate(stopped, approx_kl, kl_limit):
+    """``(stopped', applied)`` of one update: strict, sticky, and a NaN ``approx_kl`` does not stop"""
+    stopped = bool(stopped) or bool(np.float64(approx_kl) > np.float64(kl_limit))
+    return stopped, not stopped
+
+
 def gradient(theta, cells, n_axes, actor, critic, activation, obs, act, logp_old, adv, ret, clip=0.2, vf_coef=0.5, ent_coef=0.0,
-             max_grad_norm=0.5, rows_per_chain=ROWS_PER_CHAIN, ratio=None):
-    """``{"grad", "stats", "logp_new", "value_new", "ratio"}`` of one minibatch: grad float32 in theta's layout (clipped), stats a dict
-    of float64 (``STATS``)"""
+             max_grad_norm=0.5, rows_per_chain=ROWS_PER_CHAIN, ratio=None, value_old=None, clip_vf=0.0, stopped=False, kl_limit=0.0):
+    """``{"grad", "stats", "more", "rows", "logp_new", "value_new", "ratio"}`` of one minibatch: grad float32 in theta's layout
+    (clipped), stats a dict of float64 (``STATS``), more a dict of float64 (``STATS_MORE``), rows what ``rows`` returned.  ``stopped`` and ``kl_limit`` (0 = no gate) are the
+    gate's: ``more``'s ``applied`` and ``stopped`` are what it says of this update"""
     obs = np.asarray(obs)
     n = len(obs)
     check(n, rows_per_chain, clip)
@@ -238,11 +323,13 @@ def gradient(theta, cells, n_axes, actor, critic, activation, obs, act, logp_old
     per_row_bad = bad | ~np.isfinite(np.asarray(act).astype(np.float64).reshape(n, A)).all(axis=1) | \
         ~np.isfinite(np.asarray(logp_old, dtype=np.float64).reshape(n)) | ~np.isfinite(np.asarray(adv, dtype=np.float64).reshape(n)) | \
         ~np.isfinite(np.asarray(ret, dtype=np.float64).reshape(n))
+    if check_clip_vf(clip_vf, value_old) > 0.0:
+        per_row_bad = per_row_bad | ~np.isfinite(np.asarray(value_old, dtype=np.float32).reshape(n))
     x = x.copy()
     x[per_row_bad] = 0.0
     a_in, mean = forward_keep(nets[0], x, activation)
     c_in, value = forward_keep(nets[1], x, activation)
-    R = rows(mean, value[:, 0], nets[2], nets[3], act, logp_old, adv, ret, bad, clip, vf_coef, ratio)
+    R = rows(mean, value[:, 0], nets[2], nets[3], act, logp_old, adv, ret, bad, clip, vf_coef, ratio, value_old, clip_vf)
     parts = []
     for net, inputs, seed in ((nets[0], a_in, R["dmean"]), (nets[1], c_in, R["dv"][:, None])):
         for dW, db in backward(net, inputs, seed, activation, rows_per_chain):
@@ -253,7 +340,12 @@ def gradient(theta, cells, n_axes, actor, critic, activation, obs, act, logp_old
     sums = {name: row_sums(R[name], rows_per_chain) for name in ("policy_loss", "value_loss", "kl", "clipped", "skipped")}
     stats = {"policy_loss": sums["policy_loss"] / count, "value_loss": sums["value_loss"] / count, "entropy": entropy(nets[2]),
              "approx_kl": sums["kl"] / count, "clip_fraction": sums["clipped"] / count, "skipped": sums["skipped"], "grad_norm": norm, "count": count}
-    return {"grad": g, "stats": stats, "logp_new": R["logp_new"], "value_new": R["value_new"], "ratio": R["ratio"]}
+    extra = {name: row_sums(R[name], rows_per_chain) for name in ("vf_clipped", "ret", "ret2", "diff", "diff2")}
+    now, applied = gate(stopped, stats["approx_kl"], kl_limit) if float(kl_limit) > 0.0 else (False, True)
+    more = {"vf_clip_fraction": extra["vf_clipped"] / count,
+            "explained_variance": explained_variance(extra["ret"], extra["ret2"], extra["diff"], extra["diff2"], count - sums["skipped"]),
+            "applied": np.float64(applied), "stopped": np.float64(now)}
+    return {"grad": g, "stats": stats, "more": more, "rows": R, "logp_new": R["logp_new"], "value_new": R["value_new"], "ratio": R["ratio"]}
 
 
 def adam(theta, m, v, step, grad, n_axes, lr=3e-4, betas=(0.9, 0.999), eps=1e-5, std=None):

@@ -16,6 +16,17 @@ checkout of the parent commit) it is measured in fresh processes alternately on 
 other by overhead_harness.compare_off.  --resources FILE: the remarks of a -Rpass-analysis=kernel-resource-usage build of npb_ppo.hip.
 One JSON line, also written to --out (profiles/ppo_cost.json).
 
+--options: what the training step's options cost instead (profiles/ppo_options_cost.json).  The same minibatch and nets, relu; setups,
+event-timed us per update in blocks of `--updates`, the order rotating:
+  off            npb_policy_update, as above
+  clip_vf        npb_policy_update_more with clip_vf 0.2 around old values that stand 0.3 * N(0, 1) from the returns
+  gate_open      npb_policy_update_more with a kl_limit no approx_kl reaches, between npb_policy_train_begin and npb_policy_train_end
+                 (both outside the timed region: the pair's one read-back is per iteration, and reported as train_end_us)
+  gate_stopped   the same with a kl_limit the first update exceeds: every update forms its gradient and statistics and applies nothing
+With --parent DIR the `off` update is also timed in fresh processes alternately on this build and on the parent's (--only-off: that
+setup alone, which the parent's library has too) and held against each other by overhead_harness.compare_off: the always-on row sums of
+explained_variance are what could make `off` dearer.
+
 Built on tools/overhead_harness.py like the *_overhead.py scripts; it is not named as they are because tests/test_overhead_harness_cpu.py
 pins their list.
 """
@@ -133,8 +144,104 @@ def measure(n, rows, updates, rounds, only_off):
     return out
 
 
+def measure_options(n, rows, updates, rounds, only_off):
+    import time
+
+    import torch
+    from nuclear_sim_amd import _lib
+    from nuclear_sim_amd.env import BatchedPlantEnv
+    env = BatchedPlantEnv.action_test("oil_top_off", range(n), dt=DT)
+    env.set_features(columns(), stack=K, final=True)
+    env.set_controls(AXES)
+    dev = env.device
+    stream = torch.cuda.current_stream(dev)
+    env.features()
+    actor, critic, log_std = nets(torch, dev, "relu")
+    env.set_policy(actor, critic, log_std, activation="relu", seed=1)
+    g = torch.Generator(device="cpu").manual_seed(0)
+    A = len(AXES)
+    obs = torch.randn((rows, K * C), generator=g).to(dev)
+    z = torch.randn((rows, A), generator=g).to(dev)
+    scatter = 0.15 * torch.randn((rows, A), generator=g).to(dev)
+    with torch.no_grad():
+        act = (actor(obs) + torch.exp(log_std) * (z + scatter)).contiguous()
+        old = (-(A * HALF_LOG_2PI) - (0.5 * z * z + log_std).sum(dim=1)).contiguous()
+    batch = {"obs": obs, "act": act, "logp_old": old, "adv": torch.randn(rows, generator=g).to(dev), "ret": torch.randn(rows, generator=g).to(dev)}
+    value_old = (batch["ret"] + 0.3 * torch.randn(rows, generator=g).to(dev)).contiguous()
+    d, held = env._ppo_desc(batch, rows_per_chain=256, **HYPER)
+    L, h = env.L, env._h
+
+    def plain():
+        _lib.check(L.npb_policy_update(h, ctypes.byref(d), LR, BETAS[0], BETAS[1], EPS, env._stream()), h)
+    out = {"n_plants": n, "device": torch.cuda.get_device_name(dev), "rounds": rounds, "features": [K, C], "axes": A, "hidden": list(HIDDEN), "rows": rows,
+           "updates_per_block": updates, "rows_per_chain": 256, "hyper": HYPER, "lr": LR, "activation": "relu"}
+    if only_off or not hasattr(L, "npb_policy_update_more"):
+        for _ in range(3):
+            plain()
+        out["update_off"] = stats([time_steps(stream, plain, updates) for _ in range(1 + rounds)][1:])
+        env.close()
+        return out
+    more = {}
+    for name, clip_vf, kl_limit in (("clip_vf", 0.2, 0.0), ("gate_open", 0.0, 1e300), ("gate_stopped", 0.0, 1e-300)):
+        m = _lib.NpbPpoMore()
+        m.value_old, m.clip_vf, m.kl_limit = value_old.data_ptr(), clip_vf, kl_limit
+        more[name] = m
+    ends, last = [], {}
+
+    def run_block(setup):
+        if setup == "off":
+            step = plain
+        else:
+            m = more[setup]
+
+            def step():
+                _lib.check(L.npb_policy_update_more(h, ctypes.byref(d), ctypes.byref(m), LR, BETAS[0], BETAS[1], EPS, env._stream()), h)
+        gated = setup.startswith("gate")
+        if gated:
+            _lib.check(L.npb_policy_train_begin(h, env._stream()), h)
+        for _ in range(3):
+            step()
+        us = time_steps(stream, step, updates)
+        if gated:
+            applied = ctypes.c_uint32()
+            t0 = time.perf_counter()
+            _lib.check(L.npb_policy_train_end(h, ctypes.byref(applied), env._stream()), h)
+            ends.append(1e6 * (time.perf_counter() - t0))
+            last[setup + "_applied"] = applied.value
+        row = torch.zeros(_lib.PPO_STATS_MORE, dtype=torch.float64, device=dev)
+        _lib.check(L.npb_policy_get_stats_more(h, ctypes.c_void_p(row.data_ptr()), env._stream()), h)
+        last[setup] = row.cpu().tolist()
+        return us
+    setups = ["off", "clip_vf", "gate_open", "gate_stopped"]
+    blocks = rotated_blocks(setups, rounds, run_block)
+    out.update({"setups": {s: stats(v) for s, v in blocks.items()}, "update_off": stats(blocks["off"]), "last_more": last,
+                "train_end_us": stats(ends), "updates_between_begin_and_end": updates + 3})
+    for s in setups[1:]:
+        out[s + "_minus_off_us"] = paired(blocks, s, "off")
+    out["off_spread_us"] = out["setups"]["off"]["max_us"] - out["setups"]["off"]["min_us"]
+    del held
+    env.close()
+    return out
+
+
+def main_options(a):
+    res = measure_options(a.n, a.rows, a.updates, a.rounds, a.only_off)
+    if a.parent and not a.only_off:
+        argv = ["--options", "--n", a.n, "--rows", a.rows, "--updates", a.updates, "--rounds", a.rounds]
+        this, parent = off_across_builds(__file__, argv, a.parent, a.process_repeats, lambda run: run["result"]["update_off"]["median_us"], 900)
+        res["parent_comparison"] = {"update_off": compare_off(this, parent, res["update_off"])}
+    out = {"what": "one update of the policy on a minibatch of 65 536 rows (64 cells, 4 axes, hidden (64, 64) actor and critic, relu) with the training "
+                   "step's options off (npb_policy_update), with clip_vf, and with the target_kl gate armed, not stopping and stopped, event-timed us "
+                   "per update; and the options-off update of this build against the parent's in fresh processes",
+           "result": res, "head": head(ROOT)}
+    if a.resources:
+        out["kernel_resources"] = resources(a.resources)
+    write_line(out, a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--options", action="store_true", help="the cost of value-loss clipping and of the target_kl gate (profiles/ppo_options_cost.json)")
     ap.add_argument("--n", type=int, default=65536, help="plants of the env whose step is `off`")
     ap.add_argument("--rows", type=int, default=65536)
     ap.add_argument("--updates", type=int, default=20)
@@ -143,6 +250,10 @@ def main():
     add_parent_arguments(ap, "ppo_cost.json")
     a = ap.parse_args()
     sys.path.insert(0, a.package_root)
+    if a.options:
+        if a.out == os.path.join(ROOT, "profiles", "ppo_cost.json"):
+            a.out = os.path.join(ROOT, "profiles", "ppo_options_cost.json")
+        return main_options(a)
     res = measure(a.n, a.rows, a.updates, a.rounds, a.only_off)
     if a.parent and not a.only_off:
         this, parent = off_across_builds(__file__, ["--n", a.n, "--rounds", a.rounds], a.parent, a.process_repeats, lambda run: run["result"]["off"]["median_us"], 900)
