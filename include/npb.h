@@ -1485,8 +1485,7 @@ NPB_API int npb_collect(NpbHandle *h, int steps, double *obs, double *reward, ui
  * float [theta_count]) and step.  The optimiser's buffers and the chains' workspace belong to the policy: allocated on first use, grown on
  * demand, dropped with it.  NPB_EINVAL by name before any device work: no policy set, and what npb_ppo_check refuses.
  * The gradient kernel (npb_ppo.hip) runs on the f32 matrix cores (v_mfma_f32_32x32x2_f32), a workgroup a chain, no atomics.
- * Not here: a shared trunk, learning-rate schedules (host arithmetic: lr is an argument of every update), half types, gradient
- * exchange between devices.
+ * Not here: a shared trunk, learning-rate schedules (host arithmetic: lr is an argument of every update), half types.
  *
  * THE OPTIONS (npb_ppo_more_t; the entry points below that take one; a binding detects them by name, NPB_VERSION stays 154).  With
  * more == NULL, and with clip_vf == 0 and kl_limit == 0, every launch computes the bits of the calls above.
@@ -1553,6 +1552,59 @@ NPB_API int npb_policy_update_more(NpbHandle *h, const npb_ppo_desc_t *desc, con
 NPB_API int npb_policy_train_begin(NpbHandle *h, void *stream);
 NPB_API int npb_policy_train_end(NpbHandle *h, uint32_t *applied, void *stream);
 NPB_API int npb_policy_get_stats_more(NpbHandle *h, double *more, void *stream);
+
+/* TRAINING ONE POLICY ACROSS SHARDS (npb_ppo_shards_t; the entry points below; a binding detects them by name, NPB_VERSION stays 154).
+ * An update is cut where the pinned double sums end: a handle exports the sums of its own rows (npb_policy_shard_sums), a second call
+ * adds W such vectors in ascending shard order and finishes the update (npb_policy_apply_shards).  Every replica that applies the same
+ * W vectors computes the same bits, so replicas stay identical with no broadcast of parameters; two handles on one device train one
+ * policy the same way, and one handle accumulates several minibatches into one Adam step by writing their sums into the rows of one
+ * buffer.  nuclear_sim_amd/ppo.py (shard_sums, combine) states both calls in numpy.  A handle that never calls these computes the bits
+ * it computed before, in every entry point.
+ * The vector: L = npb_ppo_shard_count(theta_count, n_axes) = theta_count - 2 * n_axes + NPB_PPO_SHARD_ROWS doubles -- every weight and
+ * bias slot in theta's layout, up to where log_std starts, then the NPB_PPO_SHARD_ROWS (18) per-row sums: dls[a] at a (< 8, +0.0 beyond
+ * A), policy_loss 8, kl 9, clipped 10, skipped 11, value_loss 12, vf_clipped 13, ret 14, ret2 15, diff 16, diff2 17.
+ * npb_policy_shard_sums(h, desc, more, count_total, out, stream): the gradient kernel of npb_policy_grad_more over desc's count rows,
+ * with ONE change in the per-row arithmetic: every seed is divided by the count of the whole update,
+ *   dmean[a] = (float)(((c * d[a]) / std[a]) / (double)count_total);  dv = (float)((vf_coef * seed) / (double)count_total)
+ *   dls[a] = (c * (d[a] * d[a] - 1.0)) / (double)count_total
+ * then a lane an entry: sums[e] = the chains' partials (per-row sums) widened, added in ascending chain order onto 0.0, stored as a
+ * double and NOT narrowed; ent_coef is not yet subtracted.  out: a DEVICE double [L], 8-byte aligned; it may be a row of a larger [W][L]
+ * buffer.  ent_coef and max_grad_norm of desc are not read; more may be NULL, and its kl_limit must be 0 (the gate belongs to the
+ * combine).  The handle's grad, stats, more and the gate's words are left as they were.  Refused by name: count_total < desc->count, a
+ * NULL or misaligned out, kl_limit > 0, and what npb_ppo_check and npb_ppo_more_check refuse.
+ * npb_policy_apply_shards(h, shards, lr, b1, b2, eps, stream): a lane a parameter,
+ *   total[e] = 0.0;  for w ascending  total[e] = total[e] + sums[w][e]      (in double)
+ *   grad[e] = (float)total[e];  grad(log_std[a]) = (float)(total_dls[a] - ent_coef);  grad(std[a]) = 0
+ * then what npb_policy_grad does behind its own sums: the norm over the pinned tree, the scale by max_grad_norm (0 = off), stats and more
+ * with count = count_total and the 18 totals for the sums, the gate on the GLOBAL approx_kl (kl_limit > 0), the Adam step (gated when
+ * kl_limit > 0) and the launch that lays the weights out as the step reads them.  With n_shards == 1 and count_total == count the two
+ * calls are npb_policy_update_more, bit for bit.  Between npb_policy_train_begin and npb_policy_train_end only an apply with kl_limit >
+ * 0 is accepted; outside the pair one with kl_limit > 0 is refused by name.
+ * npb_policy_combine_shards(h, shards, stream): the same without Adam and without the gate (kl_limit > 0 is refused by name, as
+ * npb_policy_grad_more refuses it); grad, stats and more stay on the handle for npb_policy_get_grad / _get_stats / _get_stats_more.
+ * npb_ppo_shards_check(shards, count, n_axes): the host-only validator (count: theta's element count), NULL = accepted, else the
+ * reason: a NULL descriptor or NULL sums; sums misaligned for a double; n_shards outside 1 .. NPB_PPO_SHARDS_MAX (64); count_total < 1
+ * or beyond 2^53; an ent_coef or max_grad_norm that is not finite, or max_grad_norm < 0; a kl_limit that is negative or not finite; an
+ * axis count outside 1 .. 8 or a count that leaves no weights.  NPB_EINVAL by name before any device work: no policy set, and those.
+ * One exchange moves 8 * L bytes a shard.  The kernels use plain vector stores, no atomics and no scratch.
+ * Not here: synchronising the running normaliser between shards (normalizer.merge stays the host answer); advantage moments over all
+ * shards (every shard normalises its own); shards with different numbers of updates; overlapping the exchange with the next minibatch's
+ * gather; the exchange itself (the caller's all-gather: nuclear_sim_amd/sharding.py has one over torch.distributed); any measurement
+ * across more than one device. */
+#define NPB_PPO_SHARD_ROWS 18
+#define NPB_PPO_SHARDS_MAX 64
+typedef struct npb_ppo_shards_t {
+  const double *sums;                        /* device [n_shards][L], shard order */
+  int n_shards;                              /* 1 .. NPB_PPO_SHARDS_MAX */
+  int64_t count_total;                       /* the rows of the whole update: what every shard divided its seeds by */
+  double ent_coef, max_grad_norm, kl_limit;  /* max_grad_norm 0 = off; kl_limit 0 = no gate */
+} npb_ppo_shards_t;
+NPB_API int64_t npb_ppo_shard_count(int64_t theta_count, int n_axes);
+NPB_API const char *npb_ppo_shards_check(const npb_ppo_shards_t *shards, int64_t count, int n_axes);
+NPB_API int npb_policy_shard_sums(NpbHandle *h, const npb_ppo_desc_t *desc, const npb_ppo_more_t *more, int64_t count_total, double *out,
+                                  void *stream);
+NPB_API int npb_policy_apply_shards(NpbHandle *h, const npb_ppo_shards_t *shards, double lr, double b1, double b2, double eps, void *stream);
+NPB_API int npb_policy_combine_shards(NpbHandle *h, const npb_ppo_shards_t *shards, void *stream);
 
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the

@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .ppo_abi import PPO_STATS_MORE, NpbPpoMore
+from .ppo_abi import PPO_SHARD_ROWS, PPO_SHARDS_MAX, PPO_STATS_MORE, NpbPpoMore, NpbPpoShards
 from .schema import PARAMS, SCHEMA
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -1242,6 +1242,12 @@ ENTRY_POINTS = (
         "npb_policy_train_begin": (None, [_vp, _vp]),
         "npb_policy_train_end": (None, [_vp, _P(ctypes.c_uint32), _vp]),
         "npb_policy_get_stats_more": (None, [_vp, _vp, _vp])}),
+    ("npb_policy_shard_sums", {     # one policy across shards: a handle's pinned double sums and the combine of W of them
+        "npb_ppo_shard_count": (_i64, [_i64, _ci]),
+        "npb_ppo_shards_check": (_cs, [_P(NpbPpoShards), _i64, _ci]),
+        "npb_policy_shard_sums": (None, [_vp, _P(NpbPpoDesc), _P(NpbPpoMore), _i64, _vp, _vp]),
+        "npb_policy_apply_shards": (None, [_vp, _P(NpbPpoShards), _cd, _cd, _cd, _cd, _vp]),
+        "npb_policy_combine_shards": (None, [_vp, _P(NpbPpoShards), _vp])}),
     ("npb_rollout_minibatch", {     # pinned moments, the keyed permutation and the minibatch gather over a rollout
         "npb_rollout_moments": (None, [_vp, _P(NpbMomentsDesc), _vp]),
         "npb_rollout_permutation": (None, [_vp, _i64, _P(ctypes.c_uint32), _i64, _i64, _vp, _vp]),

@@ -2542,6 +2542,63 @@ int npb_policy_train_end(NpbHandle *h, uint32_t *applied, void *stream) {
   if (applied) *applied = n;
   return NPB_OK;
 }
+/* ---- one policy across shards: a handle's pinned double sums, and the combine of W of them (include/npb.h, npb_ppo.hip) */
+int64_t npb_ppo_shard_count(int64_t theta_count, int n_axes) { return theta_count - 2 * (int64_t)n_axes + NPB_PPO_SHARD_ROWS; }
+const char *npb_ppo_shards_check(const npb_ppo_shards_t *S, int64_t count, int n_axes) {
+  if (!S) return "npb_policy_apply_shards: a NULL descriptor";
+  if (n_axes < 1 || n_axes > NPB_CONTROLS_AXES_MAX) return "npb_policy_apply_shards: the axis count must be 1 .. NPB_CONTROLS_AXES_MAX (8)";
+  if (count <= 2 * (int64_t)n_axes) return "npb_policy_apply_shards: theta's count leaves no weights before log_std and std";
+  if (!S->sums) return "npb_policy_apply_shards: sums is NULL";
+  if ((uintptr_t)S->sums & 7u) return "npb_policy_apply_shards: a misaligned sums (8-byte aligned)";
+  if (S->n_shards < 1 || S->n_shards > NPB_PPO_SHARDS_MAX) return "npb_policy_apply_shards: n_shards must be 1 .. NPB_PPO_SHARDS_MAX (64)";
+  if (S->count_total < 1 || S->count_total > ((int64_t)1 << 53)) return "npb_policy_apply_shards: count_total must be 1 .. 2^53";
+  if (!(S->ent_coef - S->ent_coef == 0.0)) return "npb_policy_apply_shards: ent_coef must be finite";
+  if (!(S->max_grad_norm >= 0.0) || !(S->max_grad_norm - S->max_grad_norm == 0.0)) return "npb_policy_apply_shards: max_grad_norm must be finite and >= 0 (0 = off)";
+  if (!(S->kl_limit >= 0.0) || !(S->kl_limit - S->kl_limit == 0.0)) return "npb_policy_apply_shards: kl_limit must be finite and >= 0 (0 = no gate)";
+  return nullptr;
+}
+int npb_policy_shard_sums(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, int64_t count_total, double *out, void *stream) {
+  if (!h) return NPB_EINVAL;
+  const char *who = "npb_policy_shard_sums";
+  if (!h->pol.theta) return fail_who(h, who, g_no_policy);
+  if (const char *why = npb_ppo_check(D, h->pol.cells, h->pol.n_axes)) return fail(h, NPB_EINVAL, why);
+  if (const char *why = npb_ppo_more_check(M, D->count)) return fail(h, NPB_EINVAL, why);
+  if (M && M->kl_limit > 0.0) return fail_who(h, who, ": kl_limit > 0: the gate belongs to the combine (npb_policy_apply_shards)");
+  if (count_total < (int64_t)D->count) return fail_who(h, who, ": count_total < desc->count: it is the rows of the whole update");
+  if (count_total > ((int64_t)1 << 53)) return fail_who(h, who, ": count_total is beyond 2^53");
+  if (!out || ((uintptr_t)out & 7u)) return fail_who(h, who, ": a NULL or misaligned out (8-byte aligned)");
+  NPB_USE_DEVICE(h);
+  if (int rc = ppo_room(h, who, ((size_t)D->count + D->rows_per_chain - 1) / D->rows_per_chain)) return rc;
+  npb_launch_ppo_shard_sums(&h->pol, &h->ppo, D, M, count_total, out, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+static int ppo_combine(NpbHandle *h, const char *who, const npb_ppo_shards_t *S, void *stream) {
+  if (!h->pol.theta) return fail_who(h, who, g_no_policy);
+  if (const char *why = npb_ppo_shards_check(S, (int64_t)h->pol.theta_count, h->pol.n_axes)) return fail(h, NPB_EINVAL, why);
+  NPB_USE_DEVICE(h);
+  if (int rc = ppo_room(h, who, 0)) return rc;
+  npb_launch_ppo_combine(&h->pol, &h->ppo, S, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_policy_combine_shards(NpbHandle *h, const npb_ppo_shards_t *S, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (S && S->kl_limit > 0.0) return fail(h, NPB_EINVAL, "npb_policy_combine_shards: kl_limit > 0: the gate is an update's (npb_policy_apply_shards)");
+  return ppo_combine(h, "npb_policy_combine_shards", S, stream);
+}
+int npb_policy_apply_shards(NpbHandle *h, const npb_ppo_shards_t *S, double lr, double b1, double b2, double eps, void *stream) {
+  if (!h) return NPB_EINVAL;
+  const char *who = "npb_policy_apply_shards";
+  const int gated = S && S->kl_limit > 0.0;
+  if (gated && !h->ppo.armed) return fail_who(h, who, ": kl_limit > 0 outside npb_policy_train_begin / npb_policy_train_end (npb_policy_train_begin first)");
+  if (!gated && h->ppo.armed) return fail_who(h, who, ": kl_limit == 0 between npb_policy_train_begin and npb_policy_train_end: every update of the pair is gated");
+  if (h->pol.theta)      /* (a gated combine counts itself applied: its Adam step must not be refused behind it) */
+    if (const char *why = adam_refusal(lr, b1, b2, eps)) return fail_who(h, who, why);
+  if (int rc = ppo_combine(h, who, S, stream)) return rc;
+  return ppo_adam(h, who, lr, b1, b2, eps, gated, stream);
+}
+
 /* a copy between device buffers on the stream */
 static int ppo_copy_out(NpbHandle *h, const char *who, const void *src, void *dst, size_t bytes, size_t align, bool needs_grad, void *stream) {
   if (!h->pol.theta) return fail_who(h, who, g_no_policy);

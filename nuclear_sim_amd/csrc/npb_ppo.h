@@ -29,6 +29,13 @@ void npb_launch_ppo_grad(const npb_policy_t *P, const npb_ppo_t *O, const npb_pp
 /* one Adam step on P->theta from O->grad, O->step the step it is (already advanced): step_size = lr / (1 - b1^step) and root = sqrt(1 -
  * b2^step) are formed on the host, in double.  gated: the launch reads O->gate's stopped word and stores nothing when it is set */
 void npb_launch_ppo_adam(const npb_policy_t *P, const npb_ppo_t *O, double lr, double b1, double b2, double eps, int gated, hipStream_t stream);
+/* one shard's sums (npb_policy_shard_sums): the gradient kernel with the seeds' divisor (double)count_total, then a lane an entry of out
+ * [P->log_std + NPD_PPO_ROWVALS] doubles: the ascending sum over the chains, not narrowed.  O's grad, stats, more and gate are not touched */
+void npb_launch_ppo_shard_sums(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, int64_t count_total, double *out,
+                               hipStream_t stream);
+/* the combine (npb_policy_apply_shards, npb_policy_combine_shards): a lane a parameter adds S->sums' rows in ascending order onto 0.0,
+ * narrows once and takes the tree's first level; then the finish over the 18 totals with n = count_total, S->kl_limit > 0 ORing the gate */
+void npb_launch_ppo_combine(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_shards_t *S, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

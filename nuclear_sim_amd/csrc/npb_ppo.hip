@@ -26,7 +26,12 @@
  * sums; then the first level of the pinned tree over the squares.  THE FINISH KERNEL, one workgroup: the tree's further levels, the norm,
  * the scale, the statistics, and with a gate armed (kl_limit > 0) the gate: one lane ORs approx_kl > kl_limit into the training block's
  * stopped word and counts an applied update, with ordinary stores.  THE ADAM KERNEL: a lane a parameter, and log_std's lane refreshes
- * std; its gated twin reads the stopped word first and stores nothing when it is set. */
+ * std; its gated twin reads the stopped word first and stores nothing when it is set.
+ * ACROSS SHARDS (npb_policy_shard_sums, npb_policy_apply_shards): the update cut where the double sums end.  The gradient kernel divides
+ * its seeds by R.n, (double)count of a plain call and (double)count_total of a shard's.  THE SHARD REDUCE KERNEL: a lane an entry of the
+ * shard's vector: the reduce kernel's ascending sum over the chains, stored as the double it is.  THE COMBINE KERNEL: a lane a parameter:
+ * the shards' entries added in ascending shard order onto 0.0, narrowed once, then as the reduce kernel.  The finish kernel's second
+ * instance reads the 18 totals' rows out of the shards' vectors and divides by count_total; the plain instance is the code it was. */
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "npb_ppo.h"
@@ -38,6 +43,9 @@ typedef struct {
   int n_chains;
   float *partials; size_t floats;      /* [n_chains][floats] */
   double *chain_stats;                 /* [n_chains][NPD_PPO_ROWVALS] */
+  double n;                            /* the seeds' divisor: (double)D.count, or a shard's (double)count_total */
+  const double *shards; size_t shard_len; int n_shards;      /* the combine's: [n_shards][shard_len], shard_len = P.log_std + NPD_PPO_ROWVALS */
+  double ent_coef;                     /* the combine's (a plain call's is D.ent_coef) */
 } npd_ppo_run_t;
 
 __device__ __forceinline__ double npd_ppo_load(const void *x, int f64, size_t i) { return f64 ? ((const double *)x)[i] : (double)((const float *)x)[i]; }
@@ -141,7 +149,7 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_grad_kernel(npb_poli
   const npb_ppo_desc_t &D = R.D;
   const int tid = threadIdx.x, A = P.n_axes, KC = P.cells, KC_pad = (KC + 3) & ~3;
   const size_t count = (size_t)D.count, rpc = (size_t)D.rows_per_chain;
-  const double n = (double)D.count, qnan = (double)__builtin_nanf("");
+  const double n = R.n, qnan = (double)__builtin_nanf("");
   for (size_t chain = blockIdx.x; chain < (size_t)R.n_chains; chain += gridDim.x) {
     float *prow = R.partials + chain * R.floats;
     double running = 0.0;      /* lane q < NPD_PPO_ROWVALS: the chain's sum of per-row double q */
@@ -271,8 +279,39 @@ __global__ __launch_bounds__(NPD_TREE) void npb_ppo_reduce_kernel(npb_policy_t P
   if (lane == 0 && (size_t)blockIdx.x * NPD_TREE < P.std) O.tree[blockIdx.x] = s[0];
 }
 
+/* a shard's vector (npb_policy_shard_sums): a lane an entry, the reduce kernel's ascending sums over the chains stored as doubles: the
+ * weights' and biases' from the partials, then the NPD_PPO_ROWVALS per-row sums.  Plain vector stores */
+__global__ __launch_bounds__(NPD_TREE) void npb_ppo_shard_reduce_kernel(npb_policy_t P, npd_ppo_run_t R, double *__restrict__ out) {
+  const size_t e = (size_t)blockIdx.x * NPD_TREE + threadIdx.x;
+  if (e >= (size_t)P.log_std + NPD_PPO_ROWVALS) return;
+  double sum = 0.0;
+  if (e < P.log_std) for (int c = 0; c < R.n_chains; c++) sum = sum + (double)R.partials[(size_t)c * R.floats + e];
+  else for (int c = 0; c < R.n_chains; c++) sum = sum + R.chain_stats[(size_t)c * NPD_PPO_ROWVALS + (e - P.log_std)];
+  out[e] = sum;
+}
+
+/* the combine (npb_policy_apply_shards): a lane a parameter: its entry of every shard's vector added in ascending shard order onto 0.0,
+ * narrowed once (dls[a] sits at log_std[a]'s own index of the vector; its lane subtracts ent_coef first); std's 0; and the first level
+ * of the pinned tree, as the reduce kernel */
+__global__ __launch_bounds__(NPD_TREE) void npb_ppo_combine_kernel(npb_policy_t P, npd_ppo_run_t R, npb_ppo_t O) {
+  __shared__ double s[NPD_TREE];
+  const int lane = threadIdx.x;
+  const size_t e = (size_t)blockIdx.x * NPD_TREE + lane;
+  float g = 0.0f;
+  if (e < P.std) {
+    double sum = 0.0;
+    for (int w = 0; w < R.n_shards; w++) sum = sum + R.shards[(size_t)w * R.shard_len + e];
+    g = e < P.log_std ? (float)sum : (float)(sum - R.ent_coef);
+  }
+  if (e < P.theta_count) O.grad[e] = g;
+  s[lane] = e < P.std ? (double)g * (double)g : 0.0;
+  npd_tree_group(s, lane);
+  if (lane == 0 && (size_t)blockIdx.x * NPD_TREE < P.std) O.tree[blockIdx.x] = s[0];
+}
+
 /* one workgroup: the tree's further levels, the norm, the scale over every entry but std's, the statistics (the chains' sums first, a
  * lane a quantity, so that no two of them wait for each other inside one wave), the gate */
+template <bool SHARDS>
 __global__ __launch_bounds__(NPD_TREE) void npb_ppo_finish_kernel(npb_policy_t P, npd_ppo_run_t R, npb_ppo_t O) {
   __shared__ double s[NPD_TREE], sums[NPD_PPO_ROWVALS];
   const int lane = threadIdx.x;
@@ -282,7 +321,8 @@ __global__ __launch_bounds__(NPD_TREE) void npb_ppo_finish_kernel(npb_policy_t P
    * already scaling */
   if (lane < NPD_PPO_ROWVALS) {
     double sum = 0.0;
-    for (int c = 0; c < R.n_chains; c++) sum = sum + R.chain_stats[(size_t)c * NPD_PPO_ROWVALS + lane];
+    if (SHARDS) for (int w = 0; w < R.n_shards; w++) sum = sum + R.shards[(size_t)w * R.shard_len + P.log_std + lane];
+    else for (int c = 0; c < R.n_chains; c++) sum = sum + R.chain_stats[(size_t)c * NPD_PPO_ROWVALS + lane];
     sums[lane] = sum;
   }
   if (R.D.max_grad_norm > 0.0) {
@@ -290,7 +330,7 @@ __global__ __launch_bounds__(NPD_TREE) void npb_ppo_finish_kernel(npb_policy_t P
     for (size_t e = lane; e < P.std; e += NPD_TREE) O.grad[e] = (float)((double)O.grad[e] * scale);
   }
   __syncthreads();
-  const double n = (double)R.D.count;
+  const double n = SHARDS ? R.n : (double)R.D.count;
   if (lane == 0) O.stats[0] = sums[NPD_PPO_POLICY_LOSS] / n;
   else if (lane == 1) O.stats[1] = sums[NPD_PPO_VALUE_LOSS] / n;
   else if (lane == 2) {
@@ -358,16 +398,36 @@ static npd_ppo_run_t npd_ppo_run(const npb_ppo_t *O, const npb_ppo_desc_t *D, co
   if (M) R.M = *M;
   R.n_chains = (int)(((int64_t)D->count + D->rows_per_chain - 1) / D->rows_per_chain);
   R.partials = O->partials; R.floats = O->floats; R.chain_stats = O->chain_stats;
+  R.n = (double)D->count;
   return R;
 }
-extern "C" void npb_launch_ppo_grad(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, hipStream_t stream) {
-  const npd_ppo_run_t R = npd_ppo_run(O, D, M);
+static void npd_ppo_launch_grad(const npb_policy_t *P, const npb_ppo_desc_t *D, const npd_ppo_run_t &R, hipStream_t stream) {
   const int cap = D->max_blocks > 0 ? D->max_blocks : 2048;
   const dim3 grid((unsigned)(R.n_chains < cap ? R.n_chains : cap)), block(NPD_POLICY_LANES);
   if (P->cells <= 64 && P->width_max <= 64) hipLaunchKernelGGL((npb_ppo_grad_kernel<64, 64>), grid, block, 0, stream, *P, R);
   else hipLaunchKernelGGL((npb_ppo_grad_kernel<NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX>), grid, block, 0, stream, *P, R);
+}
+extern "C" void npb_launch_ppo_grad(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, hipStream_t stream) {
+  const npd_ppo_run_t R = npd_ppo_run(O, D, M);
+  npd_ppo_launch_grad(P, D, R, stream);
   hipLaunchKernelGGL(npb_ppo_reduce_kernel, dim3((P->theta_count + NPD_TREE - 1) / NPD_TREE), dim3(NPD_TREE), 0, stream, *P, R, *O);
-  hipLaunchKernelGGL(npb_ppo_finish_kernel, dim3(1), dim3(NPD_TREE), 0, stream, *P, R, *O);
+  hipLaunchKernelGGL(npb_ppo_finish_kernel<false>, dim3(1), dim3(NPD_TREE), 0, stream, *P, R, *O);
+}
+extern "C" void npb_launch_ppo_shard_sums(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, int64_t count_total,
+                                          double *out, hipStream_t stream) {
+  npd_ppo_run_t R = npd_ppo_run(O, D, M);
+  R.n = (double)count_total;
+  npd_ppo_launch_grad(P, D, R, stream);
+  const size_t L = (size_t)P->log_std + NPD_PPO_ROWVALS;
+  hipLaunchKernelGGL(npb_ppo_shard_reduce_kernel, dim3((unsigned)((L + NPD_TREE - 1) / NPD_TREE)), dim3(NPD_TREE), 0, stream, *P, R, out);
+}
+extern "C" void npb_launch_ppo_combine(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_shards_t *S, hipStream_t stream) {
+  npd_ppo_run_t R = {};
+  R.D.max_grad_norm = S->max_grad_norm; R.M.kl_limit = S->kl_limit;
+  R.n = (double)S->count_total; R.ent_coef = S->ent_coef;
+  R.shards = S->sums; R.shard_len = (size_t)P->log_std + NPD_PPO_ROWVALS; R.n_shards = S->n_shards;
+  hipLaunchKernelGGL(npb_ppo_combine_kernel, dim3((P->theta_count + NPD_TREE - 1) / NPD_TREE), dim3(NPD_TREE), 0, stream, *P, R, *O);
+  hipLaunchKernelGGL(npb_ppo_finish_kernel<true>, dim3(1), dim3(NPD_TREE), 0, stream, *P, R, *O);
 }
 extern "C" void npb_launch_ppo_adam(const npb_policy_t *P, const npb_ppo_t *O, double lr, double b1, double b2, double eps, int gated, hipStream_t stream) {
   /* (formed here and not by the caller: this file's flags keep the host's division IEEE too) */

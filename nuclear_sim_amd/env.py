@@ -2075,9 +2075,84 @@ class BatchedPlantEnv:
         _lib.check(self.L.npb_policy_adam(self._h, float(lr), float(betas[0]), float(betas[1]), float(eps), self._stream()), self._h)
         pol["moved"] = True
 
+    # ------------------------------------------------------------------ one policy across shards
+    def policy_shard_size(self) -> int:
+        """L, the length of a shard's vector for the set policy (npb_ppo_shard_count; ``ppo.shard_size``)"""
+        pol = self._on("_pol")
+        if not hasattr(self.L, "npb_policy_shard_sums"):
+            raise _lib.NpbError("libnpb.so has no npb_policy_shard_sums: rebuild")
+        return int(self.L.npb_ppo_shard_count(pol["theta"].numel(), pol["spec"]["n_axes"]))
+
+    def policy_shard_sums(self, batch, count_total: int, clip: float = 0.2, vf_coef: float = 0.5, rows_per_chain: int = 256,
+                          clip_vf: float = 0.0, value_old=None, out=None, max_blocks: int = 0) -> torch.Tensor:
+        """This shard's pinned double sums of one update over ``count_total`` rows in all (npb_policy_shard_sums): a device float64 [L]
+        -- the chains' sums of every weight and bias, not narrowed, and the 18 per-row sums, every seed divided by ``count_total`` --
+        nothing read back.  ``out``: a caller's contiguous float64 [L] row to write into (a row of a [W, L] buffer: that is how one
+        handle accumulates several minibatches into one Adam step).  The handle's gradient and statistics are left as they were.
+        ``nuclear_sim_amd.ppo.shard_sums`` is the same in numpy: bit for bit with relu when fed the device's ``ratio``."""
+        L = self.policy_shard_size()
+        d, held = self._ppo_desc(batch, clip, vf_coef, 0.0, 0.0, rows_per_chain, max_blocks)
+        more, held_more = self._ppo_more(batch, d.count, clip_vf, value_old)
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = torch.zeros(L, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or out.numel() != L or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous float64 tensor of %d elements on %s" % (L, self.device))
+        _lib.check(self.L.npb_policy_shard_sums(self._h, ctypes.byref(d), None if more is None else ctypes.byref(more), int(count_total),
+                                                ctypes.c_void_p(out.data_ptr()), self._stream()), self._h)
+        self._pol["ppo_held"] = held + held_more      # (alive while the launches read them)
+        return out
+
+    def _ppo_shards(self, shards, count_total, ent_coef, max_grad_norm, kl_limit=0.0):
+        """the npb_ppo_shards_t of a contiguous device float64 [W, L] tensor"""
+        L = self.policy_shard_size()
+        if not isinstance(shards, torch.Tensor) or shards.dtype != torch.float64 or shards.dim() != 2 or shards.shape[1] != L or \
+                not shards.is_contiguous() or shards.device != self.device:
+            raise ValueError("shards must be a contiguous float64 [W, %d] tensor on %s" % (L, self.device))
+        s = _lib.NpbPpoShards()
+        s.sums, s.n_shards, s.count_total = shards.data_ptr(), shards.shape[0], int(count_total)
+        s.ent_coef, s.max_grad_norm, s.kl_limit = float(ent_coef), float(max_grad_norm), float(kl_limit)
+        return s
+
+    def policy_apply_shards(self, shards, count_total: int, ent_coef: float = 0.0, max_grad_norm: float = 0.5, lr: float = 3e-4,
+                            betas=(0.9, 0.999), eps: float = 1e-5, kl_limit: float = 0.0) -> None:
+        """One update from W shards' vectors (npb_policy_apply_shards): ``shards`` a contiguous device float64 [W, L] in shard order, added
+        in ascending order in double, narrowed once, clipped, then the Adam step; statistics with ``count = count_total`` stay on the
+        handle.  Every replica that applies the same vectors computes the same bits.  ``kl_limit`` > 0: the gate on the global
+        ``approx_kl``, only between npb_policy_train_begin and npb_policy_train_end.  ``ppo.combine`` and ``ppo.adam`` are the same in numpy."""
+        pol = self._on("_pol")
+        s = self._ppo_shards(shards, count_total, ent_coef, max_grad_norm, kl_limit)
+        _lib.check(self.L.npb_policy_apply_shards(self._h, ctypes.byref(s), float(lr), float(betas[0]), float(betas[1]), float(eps), self._stream()), self._h)
+        pol["moved"], pol["shards_held"] = True, shards
+
+    def policy_combine_shards(self, shards, count_total: int, ent_coef: float = 0.0, max_grad_norm: float = 0.5) -> dict:
+        """``policy_apply_shards`` without the Adam step and without a gate (npb_policy_combine_shards): ``{"grad", "stats", "more"}`` as
+        ``policy_grad`` returns them, device tensors, nothing read back"""
+        pol = self._on("_pol")
+        s = self._ppo_shards(shards, count_total, ent_coef, max_grad_norm)
+        with torch.cuda.device(self.device):
+            out = {"grad": torch.zeros(pol["theta"].numel(), dtype=torch.float32, device=self.device),
+                   "stats": torch.zeros(_lib.PPO_STATS, dtype=torch.float64, device=self.device),
+                   "more": torch.zeros(_lib.PPO_STATS_MORE, dtype=torch.float64, device=self.device)}
+        _lib.check(self.L.npb_policy_combine_shards(self._h, ctypes.byref(s), self._stream()), self._h)
+        _lib.check(self.L.npb_policy_get_grad(self._h, ctypes.c_void_p(out["grad"].data_ptr()), self._stream()), self._h)
+        _lib.check(self.L.npb_policy_get_stats(self._h, ctypes.c_void_p(out["stats"].data_ptr()), self._stream()), self._h)
+        _lib.check(self.L.npb_policy_get_stats_more(self._h, ctypes.c_void_p(out["more"].data_ptr()), self._stream()), self._h)
+        pol["shards_held"] = shards
+        return out
+
+    @staticmethod
+    def _update_counts(cells, batch_size, epochs, drop_last):
+        """the rows of every update of one shard of ``cells`` cells, as ``rollout_minibatches`` cuts them"""
+        B = min(int(batch_size), int(cells))
+        one = [min(B, cells - first) for first in range(0, cells, B)]
+        if drop_last:
+            one = [c for c in one if c == B]
+        return one * int(epochs)
+
     def policy_train(self, batch_size, epochs: int = 1, seed: int = 0, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0,
                      max_grad_norm: float = 0.5, rows_per_chain: int = 256, lr=3e-4, betas=(0.9, 0.999), eps: float = 1e-5,
-                     clip_vf: float = 0.0, target_kl=None, more: bool = False, **minibatches):
+                     clip_vf: float = 0.0, target_kl=None, more: bool = False, exchange=None, shard_cells=None, **minibatches):
         """The optimiser's half of a PPO iteration: ``rollout_minibatches(batch_size, epochs, seed, **minibatches)`` and one
         npb_policy_update -- gradient and Adam step -- per minibatch.  Returns every update's stats as ONE device tensor [updates, 8]
         (``ppo.STATS``'s order), and with ``more=True`` ``(stats, more [updates, 4])`` (``ppo.STATS_MORE``'s order).  ``collect``,
@@ -2088,13 +2163,38 @@ class BatchedPlantEnv:
         later one of this call, is formed and reported but not applied; Adam's step counts the applied ones.
         With ``target_kl=None`` there is no host synchronisation.  With it set the call ends with exactly ONE stream-synchronising
         read-back, of the count of applied updates (npb_policy_train_end) -- one per iteration, none per update -- so a checkpoint taken
-        after this call returns sees the right step."""
+        after this call returns sees the right step.
+        ONE POLICY ACROSS SHARDS (``exchange`` and ``shard_cells``, both or neither; with neither the call is what it was).
+        ``shard_cells``: the number of recorded cells (t * n; plants for ``unit="plant"``) of every shard, in shard order, this env's
+        among them (``sharding.gather_cells``).  ``exchange(vec)``: takes this shard's device float64 [L] and returns the [W, L] of all
+        of them, on the device, in shard order (``sharding.ppo_exchange``).  ``batch_size`` is per shard and the advantages are
+        normalised per shard.  Every shard's update count under ``batch_size`` and ``drop_last`` is formed on the host before any
+        device work, and a mismatch is refused by name; update i's ``count_total`` is the sum of the shards' rows of update i, and the
+        update is ``policy_shard_sums``, ``exchange``, ``policy_apply_shards``: every shard ends with the same parameters, bit for bit,
+        with no broadcast.  The gate is taken on the global ``approx_kl``; the stats are the whole update's."""
         pol = self._on("_pol")
         kl_limit = 0.0
         if target_kl is not None:
             if not float(target_kl) > 0.0 or float(target_kl) == float("inf"):
                 raise ValueError("target_kl must be finite and > 0 (None = off), not %r" % (target_kl,))
             kl_limit = 1.5 * float(target_kl)
+        totals = None
+        if (exchange is None) != (shard_cells is None):
+            raise ValueError("exchange and shard_cells come together: both, or neither")
+        if exchange is not None:
+            cells = [int(c) for c in shard_cells]
+            if not 1 <= len(cells) <= _lib.PPO_SHARDS_MAX or min(cells) < 1:
+                raise ValueError("shard_cells: 1 .. %d shards of >= 1 cells each, not %r" % (_lib.PPO_SHARDS_MAX, cells))
+            counts = [self._update_counts(c, batch_size, epochs, bool(minibatches.get("drop_last"))) for c in cells]
+            if len({len(c) for c in counts}) != 1:
+                raise ValueError("shard_cells: the shards make different numbers of updates (%r) under batch_size %d: shards with different "
+                                 "numbers of updates are not supported" % ([len(c) for c in counts], int(batch_size)))
+            t = self._last_advantages(self._on("_roll"), minibatches.get("advantages"))[2]
+            own = self.n if minibatches.get("unit", "transition") == "plant" else t * self.n
+            if own not in cells:
+                raise ValueError("shard_cells %r does not hold this shard's own %d cells" % (cells, own))
+            per = t if minibatches.get("unit", "transition") == "plant" else 1      # (a plant is t rows: the shards record in lockstep)
+            totals = [per * sum(c[i] for c in counts) for i in range(len(counts[0]))]
         batches = self.rollout_minibatches(batch_size, epochs, seed, **minibatches)
         rates = None
         if callable(lr) or isinstance(lr, (list, tuple, np.ndarray)):
@@ -2115,13 +2215,22 @@ class BatchedPlantEnv:
         try:
             for i, batch in enumerate(batches):
                 rate = float(lr) if rates is None else rates[i]
-                d, held = self._ppo_desc(batch, clip, vf_coef, ent_coef, max_grad_norm, rows_per_chain)
-                m, held_more = self._ppo_more(batch, d.count, clip_vf, None, kl_limit)
+                held = held_more = []
+                if totals is None:
+                    d, held = self._ppo_desc(batch, clip, vf_coef, ent_coef, max_grad_norm, rows_per_chain)
+                    m, held_more = self._ppo_more(batch, d.count, clip_vf, None, kl_limit)
                 with torch.cuda.device(self.device):
                     row = torch.zeros(_lib.PPO_STATS, dtype=torch.float64, device=self.device)
                     if more:
                         mores.append(torch.zeros(_lib.PPO_STATS_MORE, dtype=torch.float64, device=self.device))
-                if m is None:
+                if totals is not None:
+                    vec = self.policy_shard_sums(batch, totals[i], clip, vf_coef, rows_per_chain, clip_vf)
+                    held = pol["ppo_held"] + [vec]
+                    every = exchange(vec)
+                    if not isinstance(every, torch.Tensor) or every.shape != (len(cells), vec.numel()):
+                        raise ValueError("exchange must return the [%d, %d] tensor of every shard's sums" % (len(cells), vec.numel()))
+                    self.policy_apply_shards(every.contiguous(), totals[i], ent_coef, max_grad_norm, rate, (b1, b2), eps, kl_limit)
+                elif m is None:
                     _lib.check(self.L.npb_policy_update(self._h, ctypes.byref(d), rate, b1, b2, eps, self._stream()), self._h)
                 else:
                     _lib.check(self.L.npb_policy_update_more(self._h, ctypes.byref(d), ctypes.byref(m), rate, b1, b2, eps, self._stream()), self._h)

@@ -90,7 +90,24 @@ THE GATE (``gate``), target_kl early stopping as SB3 takes it: the check comes b
 
 An update that is not applied leaves theta, ``std``, ``m`` and ``v`` exactly as they were; its gradient and all its statistics are still
 formed.  Once stopped, every later update of the same training call is not applied.  Adam's ``step`` counts applied updates only: within
-one call they are a prefix, so update ``i`` (0-based), if applied, is step ``step0 + i + 1``."""
+one call they are a prefix, so update ``i`` (0-based), if applied, is step ``step0 + i + 1``.
+
+ONE POLICY ACROSS SHARDS (``shard_sums``, ``combine``; npb_policy_shard_sums, npb_policy_apply_shards).  An update over ``count_total``
+rows held by W shards (the devices of a node, two handles on one device, or successive minibatches of one handle) is cut where the pinned
+double sums end.  A shard's VECTOR is float64 [L], ``L = shard_size(theta_size, A) = theta_size - 2 * A + 18``: every weight and bias
+slot in theta's layout, up to where ``log_std`` starts, each ``across(chain partials)`` as the double it is; then the 18 per-row sums
+``row_sums(...)`` in ``SHARD_ROWS``'s order: ``dls[a]`` at a < 8 (+0.0 beyond A), ``policy_loss`` 8, ``kl`` 9, ``clipped`` 10,
+``skipped`` 11, ``value_loss`` 12, ``vf_clipped`` 13, ``ret`` 14, ``ret2`` 15, ``diff`` 16, ``diff2`` 17.  ``ent_coef`` is not yet
+subtracted.  ONE change in the per-row arithmetic: wherever ``gradient`` divides a seed by ``count`` (``dmean``, ``dv``, ``dls``), a shard
+divides by ``(double)count_total``; skipped rows behave as they do there.  THE COMBINE:
+
+    total = 0.0;  for w ascending  total = total + shards[w]                    (in double, entry by entry)
+    grad[e] = (float)total[e];  grad(log_std[a]) = (float)(total_dls[a] - ent_coef);  grad(std[a]) = 0
+
+then ``clip_grad``, the ``STATS`` and ``STATS_MORE`` of ``gradient`` with ``count = count_total`` and the totals for the sums, and
+``gate`` on the GLOBAL ``approx_kl``.  Every replica that combines the same W vectors computes the same bits, so replicas that apply
+``adam`` to them stay identical with no broadcast of parameters.  THE INVARIANT: ``combine(shard_sums(..., count_total=count)[None],
+...)`` has the bits of ``gradient(...)``: no sum over the chains is ever -0.0, so ``0.0 + x`` is ``x``."""
 import numpy as np
 
 from .policy import HALF_LOG_2PI, activate, fmaf, layer, unpack
@@ -98,6 +115,9 @@ from .rollout import _tree
 
 STATS = ("policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "skipped", "grad_norm", "count")
 STATS_MORE = ("vf_clip_fraction", "explained_variance", "applied", "stopped")
+SHARD_ROWS = ("dls0", "dls1", "dls2", "dls3", "dls4", "dls5", "dls6", "dls7", "policy_loss", "kl", "clipped", "skipped", "value_loss",
+              "vf_clipped", "ret", "ret2", "diff", "diff2")      # NPD_PPO_* of csrc/npb_ppo.h: the per-row sums in the device's order
+SHARDS_MAX = 64      # NPB_PPO_SHARDS_MAX
 ROWS_PER_CHAIN = 256
 TILE = 32
 
@@ -131,15 +151,16 @@ def forward_keep(net, x, activation):
     return hs, layer(hs[-1], *net[-1])
 
 
-def rows(mean, v, log_std, std, act, logp_old, adv, ret, bad, clip, vf_coef, ratio=None, value_old=None, clip_vf=0.0):
+def rows(mean, v, log_std, std, act, logp_old, adv, ret, bad, clip, vf_coef, ratio=None, value_old=None, clip_vf=0.0, count_total=None):
     """the per-row epilogue: a dict of ``dmean`` float32 [n, A], ``dv`` float32 [n], ``dls`` float64 [n, A], ``policy_loss``,
     ``value_loss``, ``kl``, ``clipped``, ``skipped`` float64 [n], and ``logp_new``, ``value_new`` float32 [n], ``ratio`` float64 [n];
     and ``vf_clipped``, ``ret``, ``ret2``, ``diff``, ``diff2`` float64 [n], the options' per-row doubles, with ``vf_use`` (not summed).
     ``bad``: the rows with a feature that is not finite.  ``ratio``: the device's own r in place of numpy's exp.  ``value_old`` float32
-    [n] and ``clip_vf`` > 0: the value loss clipped"""
+    [n] and ``clip_vf`` > 0: the value loss clipped.  ``count_total``: the seeds' divisor (``dmean``, ``dv``, ``dls``) in place of n, for
+    a shard's rows of a larger update (``shard_sums``)"""
     mean = np.asarray(mean, dtype=np.float32).astype(np.float64)
     n, A = mean.shape
-    count = np.float64(n)
+    count = np.float64(n if count_total is None else int(count_total))
     clip, vf_coef = np.float64(clip), np.float64(vf_coef)
     log_std, std = (np.asarray(x, dtype=np.float32).astype(np.float64) for x in (log_std, std))
     act = np.asarray(act).astype(np.float64).reshape(n, A)
@@ -253,13 +274,14 @@ def row_sums(x, rows_per_chain):
     return total
 
 
-def backward(net, inputs, seed, activation, rows_per_chain):
-    """the gradient of one net, ``[(dW float32 [out, in], db float32 [out])]`` in the net's order, of the head's seed [n, out]"""
+def backward(net, inputs, seed, activation, rows_per_chain, wide=False):
+    """the gradient of one net, ``[(dW float32 [out, in], db float32 [out])]`` in the net's order, of the head's seed [n, out]; ``wide``:
+    the float64 sums over the chains as they are, not narrowed"""
     delta = np.asarray(seed, dtype=np.float32)
     grads = [None] * len(net)
     for l in range(len(net) - 1, -1, -1):
         dW, db = chain_sums(delta, inputs[l], rows_per_chain)
-        grads[l] = (across(dW).astype(np.float32), across(db).astype(np.float32))
+        grads[l] = (across(dW), across(db)) if wide else (across(dW).astype(np.float32), across(db).astype(np.float32))
         if l:
             delta = through(back(delta, net[l][0]), inputs[l], activation)
     return grads
@@ -346,6 +368,78 @@ def gradient(theta, cells, n_axes, actor, critic, activation, obs, act, logp_old
             "explained_variance": explained_variance(extra["ret"], extra["ret2"], extra["diff"], extra["diff2"], count - sums["skipped"]),
             "applied": np.float64(applied), "stopped": np.float64(now)}
     return {"grad": g, "stats": stats, "more": more, "rows": R, "logp_new": R["logp_new"], "value_new": R["value_new"], "ratio": R["ratio"]}
+
+
+def shard_size(theta_size, n_axes):
+    """L, the length of a shard's vector: theta's slots up to ``log_std``, then the ``SHARD_ROWS`` sums"""
+    return int(theta_size) - 2 * int(n_axes) + len(SHARD_ROWS)
+
+
+def shard_sums(theta, cells, n_axes, actor, critic, activation, obs, act, logp_old, adv, ret, count_total, clip=0.2, vf_coef=0.5,
+               rows_per_chain=ROWS_PER_CHAIN, ratio=None, value_old=None, clip_vf=0.0):
+    """a shard's vector, float64 [L]: what ``gradient`` computes of these rows up to, but not including, the narrowing, with every seed
+    divided by ``(double)count_total``, the rows of the whole update.  ``combine(shard_sums(..., count_total=count)[None], ...)`` has the
+    bits of ``gradient(...)``"""
+    obs = np.asarray(obs)
+    n = len(obs)
+    check(n, rows_per_chain, clip)
+    if int(count_total) < n:
+        raise ValueError("count_total must be >= the shard's %d rows, not %r" % (n, count_total))
+    A = int(n_axes)
+    nets = unpack(theta, cells, A, actor, critic)
+    with np.errstate(over="ignore", invalid="ignore"):
+        x = obs.reshape(n, -1).astype(np.float32)
+    bad = ~np.isfinite(x).all(axis=1)
+    per_row_bad = bad | ~np.isfinite(np.asarray(act).astype(np.float64).reshape(n, A)).all(axis=1) | \
+        ~np.isfinite(np.asarray(logp_old, dtype=np.float64).reshape(n)) | ~np.isfinite(np.asarray(adv, dtype=np.float64).reshape(n)) | \
+        ~np.isfinite(np.asarray(ret, dtype=np.float64).reshape(n))
+    if check_clip_vf(clip_vf, value_old) > 0.0:
+        per_row_bad = per_row_bad | ~np.isfinite(np.asarray(value_old, dtype=np.float32).reshape(n))
+    x = x.copy()
+    x[per_row_bad] = 0.0
+    a_in, mean = forward_keep(nets[0], x, activation)
+    c_in, value = forward_keep(nets[1], x, activation)
+    R = rows(mean, value[:, 0], nets[2], nets[3], act, logp_old, adv, ret, bad, clip, vf_coef, ratio, value_old, clip_vf, count_total)
+    parts = []
+    for net, inputs, seed in ((nets[0], a_in, R["dmean"]), (nets[1], c_in, R["dv"][:, None])):
+        for dW, db in backward(net, inputs, seed, activation, rows_per_chain, wide=True):
+            parts += [dW.reshape(-1), db]
+    dls = np.zeros(8, dtype=np.float64)
+    dls[:A] = row_sums(R["dls"], rows_per_chain)
+    tail = np.array([row_sums(R[name], rows_per_chain) for name in SHARD_ROWS[8:]], dtype=np.float64)
+    out = np.concatenate(parts + [dls, tail])
+    assert out.size == shard_size(np.asarray(theta).size, A)
+    return out
+
+
+def combine(shards, theta, n_axes, count_total, ent_coef=0.0, max_grad_norm=0.5, stopped=False, kl_limit=0.0):
+    """``(grad, stats, more)`` of W shards' vectors [W, L]: added in ascending shard order onto 0.0 in double, narrowed once, then the
+    clipping, the statistics (``count = count_total``) and the gate of ``gradient``.  ``theta``: the parameters, for the entropy.
+    ``combine(shard_sums(..., count_total=count)[None], ...)`` has the bits of ``gradient(...)``"""
+    shards = np.asarray(shards, dtype=np.float64)
+    theta = np.asarray(theta, dtype=np.float32).reshape(-1)
+    A = int(n_axes)
+    L = shard_size(theta.size, A)
+    if shards.ndim != 2 or shards.shape[1] != L or not 1 <= len(shards) <= SHARDS_MAX:
+        raise ValueError("shards must be [W, %d] with W in 1 .. %d, not %r" % (L, SHARDS_MAX, shards.shape))
+    if int(count_total) < 1:
+        raise ValueError("count_total must be >= 1")
+    P = L - len(SHARD_ROWS)
+    total = np.zeros(L, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        for w in range(len(shards)):
+            total = total + shards[w]
+        dls = (total[P:P + A] - np.float64(ent_coef)).astype(np.float32)
+        g, norm = clip_grad(np.concatenate([total[:P].astype(np.float32), dls, np.zeros(A, np.float32)]), A, max_grad_norm)
+        count = np.float64(int(count_total))
+        sums = dict(zip(SHARD_ROWS, total[P:]))
+        stats = {"policy_loss": sums["policy_loss"] / count, "value_loss": sums["value_loss"] / count, "entropy": entropy(theta[P:P + A]),
+                 "approx_kl": sums["kl"] / count, "clip_fraction": sums["clipped"] / count, "skipped": sums["skipped"], "grad_norm": norm, "count": count}
+        now, applied = gate(stopped, stats["approx_kl"], kl_limit) if float(kl_limit) > 0.0 else (False, True)
+        more = {"vf_clip_fraction": sums["vf_clipped"] / count,
+                "explained_variance": explained_variance(sums["ret"], sums["ret2"], sums["diff"], sums["diff2"], count - sums["skipped"]),
+                "applied": np.float64(applied), "stopped": np.float64(now)}
+    return g, stats, more
 
 
 def adam(theta, m, v, step, grad, n_axes, lr=3e-4, betas=(0.9, 0.999), eps=1e-5, std=None):

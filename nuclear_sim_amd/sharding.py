@@ -38,6 +38,30 @@ def reduce_counters(counters: torch.Tensor, group=None) -> torch.Tensor:
     return c
 
 
+def gather_shard_sums(vec: torch.Tensor, group=None) -> torch.Tensor:
+    """One all-gather of a shard's L pinned double sums (``env.policy_shard_sums``) into [W, L] on every rank, in rank order: what
+    ``policy_apply_shards`` and ``ppo.combine`` add in ascending order.  A gather and not an all-reduce: the order of a reduce is not ours
+    to pin, while the gather plus the pinned combine gives every rank the same bits.  8 * L bytes a shard."""
+    world = dist.get_world_size(group)
+    vec = vec.contiguous()
+    out = torch.empty((world, vec.numel()), dtype=vec.dtype, device=vec.device)
+    dist.all_gather(list(out.unbind(0)), vec.reshape(-1), group=group)
+    return out
+
+
+def ppo_exchange(group=None):
+    """the ``exchange`` callable of ``env.policy_train``: ``gather_shard_sums`` over ``group``"""
+    return lambda vec: gather_shard_sums(vec, group)
+
+
+def gather_cells(n_cells: int, group=None) -> list:
+    """The one host all-gather of the shards' sizes: every rank's number of recorded cells, in rank order (``shard_cells`` of
+    ``env.policy_train``)"""
+    out = [None] * dist.get_world_size(group)
+    dist.all_gather_object(out, int(n_cells), group=group)
+    return [int(c) for c in out]
+
+
 def event_histogram(events: torch.Tensor, bins: int = 16, group=None) -> torch.Tensor:
     """Histogram of a per-plant event count over the WHOLE job (BASELINE config 4's report: how many plants topped off 0, 1, 2 ...
     times): the local bincount, counts beyond the last bin clamped into it, summed over the ranks when there are several."""

@@ -27,6 +27,15 @@ With --parent DIR the `off` update is also timed in fresh processes alternately 
 setup alone, which the parent's library has too) and held against each other by overhead_harness.compare_off: the always-on row sums of
 explained_variance are what could make `off` dearer.
 
+--shards: what the update cut across shards costs (profiles/ppo_shards_cost.json).  The same minibatch and nets, relu; setups, event-timed
+us per call in blocks of `--updates`, the order rotating:
+  off            npb_policy_update, as above
+  shards_w1      npb_policy_shard_sums then npb_policy_apply_shards over that one vector: the same update in two calls
+  sums_alone     npb_policy_shard_sums
+  apply_w2 / 8 / 64   npb_policy_apply_shards alone over W synthetic vectors (the handle's own sums in every row)
+exchange_bytes_per_shard = 8 * L is stated, not measured, and no all-gather across devices is timed.  With --parent DIR the `off` update
+is held against the parent's in fresh processes as under --options: the finish kernel's second instance must leave the plain one alone.
+
 Built on tools/overhead_harness.py like the *_overhead.py scripts; it is not named as they are because tests/test_overhead_harness_cpu.py
 pins their list.
 """
@@ -239,9 +248,96 @@ def main_options(a):
     write_line(out, a.out)
 
 
+def measure_shards(n, rows, updates, rounds, only_off):
+    import torch
+    from nuclear_sim_amd import _lib
+    from nuclear_sim_amd.env import BatchedPlantEnv
+    env = BatchedPlantEnv.action_test("oil_top_off", range(n), dt=DT)
+    env.set_features(columns(), stack=K, final=True)
+    env.set_controls(AXES)
+    dev = env.device
+    stream = torch.cuda.current_stream(dev)
+    env.features()
+    actor, critic, log_std = nets(torch, dev, "relu")
+    env.set_policy(actor, critic, log_std, activation="relu", seed=1)
+    g = torch.Generator(device="cpu").manual_seed(0)
+    A = len(AXES)
+    obs = torch.randn((rows, K * C), generator=g).to(dev)
+    z = torch.randn((rows, A), generator=g).to(dev)
+    scatter = 0.15 * torch.randn((rows, A), generator=g).to(dev)
+    with torch.no_grad():
+        act = (actor(obs) + torch.exp(log_std) * (z + scatter)).contiguous()
+        old = (-(A * HALF_LOG_2PI) - (0.5 * z * z + log_std).sum(dim=1)).contiguous()
+    batch = {"obs": obs, "act": act, "logp_old": old, "adv": torch.randn(rows, generator=g).to(dev), "ret": torch.randn(rows, generator=g).to(dev)}
+    d, held = env._ppo_desc(batch, rows_per_chain=256, **HYPER)
+    L, h = env.L, env._h
+
+    def plain():
+        _lib.check(L.npb_policy_update(h, ctypes.byref(d), LR, BETAS[0], BETAS[1], EPS, env._stream()), h)
+    out = {"n_plants": n, "device": torch.cuda.get_device_name(dev), "rounds": rounds, "features": [K, C], "axes": A, "hidden": list(HIDDEN), "rows": rows,
+           "updates_per_block": updates, "rows_per_chain": 256, "hyper": HYPER, "lr": LR, "activation": "relu"}
+    if only_off or not hasattr(L, "npb_policy_shard_sums"):
+        for _ in range(3):
+            plain()
+        out["update_off"] = stats([time_steps(stream, plain, updates) for _ in range(1 + rounds)][1:])
+        env.close()
+        return out
+    length = env.policy_shard_size()
+    widths = (1, 2, 8, 64)
+    own = torch.zeros((1, length), dtype=torch.float64, device=dev)
+    own_desc = env._ppo_shards(own, rows, HYPER["ent_coef"], HYPER["max_grad_norm"])
+    # synthetic vectors: the handle's own sums of this minibatch, divided for W * rows rows, in every row
+    synthetic, descs = {}, {}
+    for W in widths[1:]:
+        row = env.policy_shard_sums(batch, W * rows, HYPER["clip"], HYPER["vf_coef"], 256)
+        synthetic[W] = row[None].repeat(W, 1).contiguous()
+        descs[W] = env._ppo_shards(synthetic[W], W * rows, HYPER["ent_coef"], HYPER["max_grad_norm"])
+
+    def sums():
+        _lib.check(L.npb_policy_shard_sums(h, ctypes.byref(d), None, rows, ctypes.c_void_p(own.data_ptr()), env._stream()), h)
+
+    def apply(s):
+        _lib.check(L.npb_policy_apply_shards(h, ctypes.byref(s), LR, BETAS[0], BETAS[1], EPS, env._stream()), h)
+
+    def two_calls():
+        sums()
+        apply(own_desc)
+    steps = {"off": plain, "shards_w1": two_calls, "sums_alone": sums}
+    for W in widths[1:]:
+        steps["apply_w%d" % W] = lambda s=descs[W]: apply(s)
+
+    def run_block(setup):
+        for _ in range(3):
+            steps[setup]()
+        return time_steps(stream, steps[setup], updates)
+    blocks = rotated_blocks(list(steps), rounds, run_block)
+    out.update({"setups": {s: stats(v) for s, v in blocks.items()}, "update_off": stats(blocks["off"]), "shard_doubles": length, "exchange_bytes_per_shard": 8 * length,
+                "shards_w1_minus_off_us": paired(blocks, "shards_w1", "off"), "off_spread_us": max(blocks["off"]) - min(blocks["off"])})
+    del held
+    env.close()
+    return out
+
+
+def main_shards(a):
+    res = measure_shards(a.n, a.rows, a.updates, a.rounds, a.only_off)
+    if a.parent and not a.only_off:
+        argv = ["--shards", "--n", a.n, "--rows", a.rows, "--updates", a.updates, "--rounds", a.rounds]
+        this, parent = off_across_builds(__file__, argv, a.parent, a.process_repeats, lambda run: run["result"]["update_off"]["median_us"], 900)
+        res["parent_comparison"] = {"update_off": compare_off(this, parent, res["update_off"])}
+    out = {"what": "one policy across shards, on a minibatch of 65 536 rows (64 cells, 4 axes, hidden (64, 64) actor and critic, relu), event-timed us per "
+                   "call: the plain npb_policy_update (off); npb_policy_shard_sums + npb_policy_apply_shards at W = 1 (shards_w1); the sums alone; "
+                   "npb_policy_apply_shards alone at W = 2, 8 and 64 over synthetic vectors; and the plain update of this build against the parent's in "
+                   "fresh processes.  exchange_bytes_per_shard = 8 * L is stated, not measured; no all-gather across devices is timed",
+           "result": res, "head": head(ROOT)}
+    if a.resources:
+        out["kernel_resources"] = resources(a.resources)
+    write_line(out, a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--options", action="store_true", help="the cost of value-loss clipping and of the target_kl gate (profiles/ppo_options_cost.json)")
+    ap.add_argument("--shards", action="store_true", help="the cost of the update cut across shards (profiles/ppo_shards_cost.json)")
     ap.add_argument("--n", type=int, default=65536, help="plants of the env whose step is `off`")
     ap.add_argument("--rows", type=int, default=65536)
     ap.add_argument("--updates", type=int, default=20)
@@ -250,6 +346,10 @@ def main():
     add_parent_arguments(ap, "ppo_cost.json")
     a = ap.parse_args()
     sys.path.insert(0, a.package_root)
+    if a.shards:
+        if a.out == os.path.join(ROOT, "profiles", "ppo_cost.json"):
+            a.out = os.path.join(ROOT, "profiles", "ppo_shards_cost.json")
+        return main_shards(a)
     if a.options:
         if a.out == os.path.join(ROOT, "profiles", "ppo_cost.json"):
             a.out = os.path.join(ROOT, "profiles", "ppo_options_cost.json")
