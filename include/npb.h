@@ -1355,7 +1355,7 @@ NPB_API const char *npb_minibatch_check(const npb_minibatch_desc_t *desc, int n_
  * Not here: statistics over fresh frames; per-plant statistics (npb_set_column_stats has them); an exponential-moving-average variant;
  * half types; synchronising shards on the device (normalizer.merge is the host answer); normalising BITS or setpoint-error columns.
  * NPB_VERSION stays 154: a binding detects the entry points by name.  A handle that never calls this behaves as before in every entry
- * point. */
+ * point.  Synchronising shards on the device has the section ONE NORMALISER AND ONE SET OF ADVANTAGE MOMENTS ACROSS SHARDS below. */
 typedef struct npb_normalizer_desc_t {
   int n_columns; const int *columns;      /* host: indices into the features' columns; 0 / NULL = the return stream alone */
   double eps;
@@ -1590,7 +1590,7 @@ NPB_API int npb_policy_get_stats_more(NpbHandle *h, double *more, void *stream);
  * Not here: synchronising the running normaliser between shards (normalizer.merge stays the host answer); advantage moments over all
  * shards (every shard normalises its own); shards with different numbers of updates; overlapping the exchange with the next minibatch's
  * gather; the exchange itself (the caller's all-gather: nuclear_sim_amd/sharding.py has one over torch.distributed); any measurement
- * across more than one device. */
+ * across more than one device.  The first two have the section below. */
 #define NPB_PPO_SHARD_ROWS 18
 #define NPB_PPO_SHARDS_MAX 64
 typedef struct npb_ppo_shards_t {
@@ -1605,6 +1605,69 @@ NPB_API int npb_policy_shard_sums(NpbHandle *h, const npb_ppo_desc_t *desc, cons
                                   void *stream);
 NPB_API int npb_policy_apply_shards(NpbHandle *h, const npb_ppo_shards_t *shards, double lr, double b1, double b2, double eps, void *stream);
 NPB_API int npb_policy_combine_shards(NpbHandle *h, const npb_ppo_shards_t *shards, void *stream);
+
+/* ONE NORMALISER AND ONE SET OF ADVANTAGE MOMENTS ACROSS SHARDS (the entry points below; a binding detects them by name, NPB_VERSION
+ * stays 154; no new struct).  What still made a sharded run W different runs: every shard folded only its own plants into its running
+ * normaliser, and every shard normalised its advantages with its own moments.  Both are cut where the pinned sums end, as the gradient
+ * is: a shard exports a short double vector, the caller all-gathers it, and every shard combines the W rows in ascending shard order.
+ * Replicas that combine the same rows hold the same bits, so nothing is broadcast.  nuclear_sim_amd/normalizer.py (shard_delta, combine)
+ * and nuclear_sim_amd/rollout.py (moments_part, moments_combine, moments_shards) state the calls in numpy, every operation in double and
+ * rounded on its own; the device produces their bits.  A handle that never calls these computes the bits it computed before, in every
+ * entry point; no step, fold, moments, permutation or minibatch kernel changes.
+ * THE NORMALISER.  Beside its state a handle keeps the BASE, double [3][S] (count, then mean, then M2): what the shards agreed on at the
+ * last synchronisation, zeros from npb_set_normalizer on.  npb_normalizer_shard_count(h) = 3 * S (0, with the reason in npb_last_error,
+ * when no normaliser is set).
+ * npb_normalizer_shard_delta(h, out, stream): out, a DEVICE double [3][S], 8-byte aligned, takes per stream the population folded since
+ * the base -- Chan's merge run backwards, a lane per stream:
+ *     na, ma, Ma = base;  N, m, M = the state;  nb = N - na
+ *     nb > 0:   mb = m + (m - ma) * (na / nb);   d = mb - ma
+ *               Mb = (M - Ma) - (d * d) * ((na * nb) / N),   0.0 where that is negative
+ *               delta = (nb, mb, Mb)
+ *     else:     delta = (0.0, 0.0, 0.0)        (a frozen shard, or one that did not step)
+ *   With a zero base the delta is the state exactly.  Neither the state nor the base is written.
+ * npb_normalizer_apply_shards(h, deltas, n_shards, stream): deltas a DEVICE double [W][3][S] in shard order, W = 1 ..
+ * NPB_PPO_SHARDS_MAX.  A lane per stream starts from the base and goes through w ascending; only a shard with nb > 0 is merged:
+ *     N = n + nb;  d = mb - mean;  mean = mean + d * (nb / N)
+ *     M2 = (M2 + Mb) + (d * d) * ((n * nb) / N);  n = N
+ *   The result is written as the state AND as the base; one finish launch without a batch follows, so scale (the return stream's rscale)
+ *   and the features' table follow it exactly as they follow npb_normalizer_set_state.  The per-plant return carry (ret, primed, seen,
+ *   ended) stays with its shard.  It is allowed while frozen: npb_normalizer_training(h, 0) stops folds, not synchronisation.  W = 1 is
+ *   the identity only from a zero base: un-merging and re-merging rounds.
+ * npb_normalizer_get_base / npb_normalizer_set_base move the base to and from a HOST double [3][S], synchronous on `stream`, for
+ * checkpoints.  npb_set_normalizer zeroes the base; npb_normalizer_set_state leaves it alone.
+ * npb_normalizer_shards_check(deltas, n_shards): the host-only validator, NULL = accepted, else the reason: deltas NULL; deltas
+ * misaligned for a double; n_shards outside 1 .. NPB_PPO_SHARDS_MAX (64).  NPB_EINVAL by name before any device work: no normaliser set,
+ * a NULL or misaligned out or base, and those.
+ * THE MOMENTS.  npb_rollout_moments is cut in four: every shard's part, the combine, every shard's part around the GLOBAL mean, the
+ * combine.  Both calls take the existing npb_moments_desc_t.
+ * npb_rollout_moments_part(h, desc, squares, part, stream): part, a DEVICE double [2] = {count, total}.  count = rows * cols; total is
+ * the undivided value npb_rollout_moments has before its division: a column's rows added in order onto 0.0, then the tree over the
+ * columns.  With squares != 0 the summands are the rounded squares of (double)x - desc->out[1]: the mean is read where
+ * npb_rollout_moments reads it.  desc->out is never written.  desc->ddof is not used -- the combine divides -- but the descriptor is
+ * checked as npb_rollout_moments checks it: pass 0.
+ * npb_rollout_moments_combine(h, parts, n_shards, squares, ddof, out, stream): parts a DEVICE double [W][2] in shard order; one lane,
+ *     C = 0.0;  T = 0.0;  for w ascending  C = C + count_w;  T = T + total_w
+ *   squares == 0: out[0] = C, out[1] = T / C.  squares != 0: out[2] = T / (C - ddof), out[3] = sqrt(out[2]).  IEEE division and root.
+ *   With W = 1 the four calls are npb_rollout_moments, bit for bit: no total is ever -0.0, so 0.0 + T is T.
+ * npb_moments_shards_check(desc, part, parts, n_shards, ddof, out): the host-only validator of both.  desc != NULL: the part is checked
+ * -- whatever npb_rollout_moments refuses a descriptor for (a count <= desc->ddof among it), part NULL, part misaligned for a double.
+ * desc == NULL: the combine is checked -- parts NULL or misaligned; n_shards outside 1 .. NPB_PPO_SHARDS_MAX (64); ddof < 0; out NULL or
+ * misaligned.  The shards' counts are device values: a total count <= ddof cannot be seen on the host and gives an infinity or a NaN, as
+ * the division says; a part's count is >= 1 because its descriptor's is.
+ * One exchange moves 24 * S bytes a shard for the normaliser and 16 bytes, twice, for the moments.  The kernels (npb_minibatch.hip, for
+ * its IEEE division and root) use plain vector stores, no atomics and no scratch.
+ * Still not here: the exchange itself (the caller's all-gather; sharding.gather_shard_sums serves every vector); any measurement across
+ * more than one device; a synchronisation of the per-plant return carry (it belongs to its plants). */
+NPB_API int npb_normalizer_shard_count(NpbHandle *h);
+NPB_API const char *npb_normalizer_shards_check(const double *deltas, int n_shards);
+NPB_API int npb_normalizer_shard_delta(NpbHandle *h, double *out, void *stream);
+NPB_API int npb_normalizer_apply_shards(NpbHandle *h, const double *deltas, int n_shards, void *stream);
+NPB_API int npb_normalizer_get_base(NpbHandle *h, double *base, void *stream);
+NPB_API int npb_normalizer_set_base(NpbHandle *h, const double *base, void *stream);
+NPB_API const char *npb_moments_shards_check(const npb_moments_desc_t *desc, const double *part, const double *parts, int n_shards, int ddof,
+                                             const double *out);
+NPB_API int npb_rollout_moments_part(NpbHandle *h, const npb_moments_desc_t *desc, int squares, double *part, void *stream);
+NPB_API int npb_rollout_moments_combine(NpbHandle *h, const double *parts, int n_shards, int squares, int ddof, double *out, void *stream);
 
 /* Measurement aid (no reference counterpart): streams every state column through the GPU unchanged,
  * 2 * npb_state_bytes() * pitch bytes with the step kernel's access shape; used to calibrate the

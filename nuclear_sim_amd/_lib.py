@@ -1248,6 +1248,16 @@ ENTRY_POINTS = (
         "npb_policy_shard_sums": (None, [_vp, _P(NpbPpoDesc), _P(NpbPpoMore), _i64, _vp, _vp]),
         "npb_policy_apply_shards": (None, [_vp, _P(NpbPpoShards), _cd, _cd, _cd, _cd, _vp]),
         "npb_policy_combine_shards": (None, [_vp, _P(NpbPpoShards), _vp])}),
+    ("npb_normalizer_apply_shards", {     # one normaliser and one set of advantage moments across shards
+        "npb_normalizer_shard_count": (None, [_vp]),
+        "npb_normalizer_shards_check": (_cs, [_vp, _ci]),
+        "npb_normalizer_shard_delta": (None, [_vp, _vp, _vp]),
+        "npb_normalizer_apply_shards": (None, [_vp, _vp, _ci, _vp]),
+        "npb_normalizer_get_base": (None, [_vp, _vp, _vp]),
+        "npb_normalizer_set_base": (None, [_vp, _vp, _vp]),
+        "npb_moments_shards_check": (_cs, [_P(NpbMomentsDesc), _vp, _vp, _ci, _ci, _vp]),
+        "npb_rollout_moments_part": (None, [_vp, _P(NpbMomentsDesc), _ci, _vp, _vp]),
+        "npb_rollout_moments_combine": (None, [_vp, _vp, _ci, _ci, _ci, _vp, _vp])}),
     ("npb_rollout_minibatch", {     # pinned moments, the keyed permutation and the minibatch gather over a rollout
         "npb_rollout_moments": (None, [_vp, _P(NpbMomentsDesc), _vp]),
         "npb_rollout_permutation": (None, [_vp, _i64, _P(ctypes.c_uint32), _i64, _i64, _vp, _vp]),

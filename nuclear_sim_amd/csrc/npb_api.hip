@@ -2719,7 +2719,8 @@ int npb_set_normalizer(NpbHandle *h, const npb_normalizer_desc_t *desc) {
     attachment_drop(&h->norm, h->norm.streams);
     return NPB_OK;
   }
-  /* the allocation: [the streams] | count, mean, M2, scale [S] | the partials [3 S][every level] | ret [n] | primed, seen, ended [n] */
+  /* the allocation: [the streams] | count, mean, M2, scale [S] | the shards' base [3][S] (normalizer_base) | the partials [3 S][every level]
+   * | ret [n] | primed, seen, ended [n] */
   const int C = desc->n_columns, S = C + (desc->reward ? 1 : 0);
   std::vector<npb_norm_stream_t> table(NPB_NORM_STREAMS_MAX);
   for (int c = 0; c < C; c++) {
@@ -2729,7 +2730,7 @@ int npb_set_normalizer(NpbHandle *h, const npb_normalizer_desc_t *desc) {
   if (desc->reward) table[C] = npb_norm_stream_t{npb_colstat_col_t{}, 0.0, 1.0, -1, 0};
   static_assert(sizeof(npb_norm_stream_t) % 8 == 0, "packed");
   const size_t n = (size_t)h->n_plants, table_bytes = table.size() * sizeof(npb_norm_stream_t), ws = npb_moments_workspace(h->n_plants);
-  const size_t doubles = 4 * (size_t)S + 3 * (size_t)S * ws + (desc->reward ? n : 0);
+  const size_t doubles = 7 * (size_t)S + 3 * (size_t)S * ws + (desc->reward ? n : 0);
   const size_t bytes = table_bytes + doubles * sizeof(double) + (desc->reward ? 3 * n * sizeof(int32_t) : 0);
   char *dev = nullptr;
   if (int rc = attachment_alloc(h, "npb_set_normalizer", "the streams, the statistics and the partials", table.data(), table_bytes, bytes, &dev)) return rc;
@@ -2738,7 +2739,7 @@ int npb_set_normalizer(NpbHandle *h, const npb_normalizer_desc_t *desc) {
   Z.streams = (const npb_norm_stream_t *)dev; Z.n_streams = S; Z.n_cols = C; Z.reward_on = desc->reward != 0;
   Z.eps = desc->eps; Z.gamma = desc->gamma; Z.clip = desc->clip;
   Z.count = (double *)(dev + table_bytes); Z.mean = Z.count + S; Z.M2 = Z.mean + S; Z.scale = Z.M2 + S;
-  Z.partial = Z.scale + S; Z.ws_stride = ws;
+  Z.partial = Z.scale + 4 * (size_t)S; Z.ws_stride = ws;
   if (desc->reward) {
     Z.ret = Z.partial + 3 * (size_t)S * ws;
     Z.primed = (int32_t *)(Z.ret + n); Z.seen = Z.primed + n; Z.ended = Z.seen + n;
@@ -2753,6 +2754,8 @@ int npb_set_normalizer(NpbHandle *h, const npb_normalizer_desc_t *desc) {
   NPB_HIP(h, hipStreamSynchronize(nullptr));
   return NPB_OK;
 }
+/* what the shards agreed on at the last synchronisation, device [3][S]: count, mean, M2; zeros from npb_set_normalizer on */
+static double *normalizer_base(const NpbHandle *h) { return h->norm.scale + h->norm.n_streams; }
 int npb_normalizer_training(NpbHandle *h, int on) {
   if (!h) return NPB_EINVAL;
   if (!h->norm.streams) return fail_who(h, "npb_normalizer_training", g_no_normalizer);
@@ -2786,6 +2789,53 @@ int npb_normalizer_set_state(NpbHandle *h, const double *count, const double *me
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
+/* ---- one normaliser across shards (include/npb.h, npb_minibatch.hip): a handle's delta since the base, and the combine of W of them */
+int npb_normalizer_shard_count(NpbHandle *h) {
+  if (!h) return 0;
+  if (!h->norm.streams) { (void)fail_who(h, "npb_normalizer_shard_count", g_no_normalizer); return 0; }
+  return 3 * h->norm.n_streams;
+}
+const char *npb_normalizer_shards_check(const double *deltas, int n_shards) {
+  if (!deltas) return "npb_normalizer_apply_shards: deltas is NULL";
+  if ((uintptr_t)deltas & 7u) return "npb_normalizer_apply_shards: a misaligned deltas (8-byte aligned)";
+  if (n_shards < 1 || n_shards > NPB_PPO_SHARDS_MAX) return "npb_normalizer_apply_shards: n_shards must be 1 .. NPB_PPO_SHARDS_MAX (64)";
+  return nullptr;
+}
+int npb_normalizer_shard_delta(NpbHandle *h, double *out, void *stream) {
+  if (!h) return NPB_EINVAL;
+  const char *who = "npb_normalizer_shard_delta";
+  if (!h->norm.streams) return fail_who(h, who, g_no_normalizer);
+  if (!out || ((uintptr_t)out & 7u)) return fail_who(h, who, ": a NULL or misaligned out (8-byte aligned)");
+  NPB_USE_DEVICE(h);
+  npb_launch_normalizer_delta(&h->norm, normalizer_base(h), out, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_normalizer_apply_shards(NpbHandle *h, const double *deltas, int n_shards, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->norm.streams) return fail_who(h, "npb_normalizer_apply_shards", g_no_normalizer);
+  if (const char *why = npb_normalizer_shards_check(deltas, n_shards)) return fail(h, NPB_EINVAL, why);
+  NPB_USE_DEVICE(h);
+  npb_launch_normalizer_combine(&h->norm, normalizer_base(h), deltas, n_shards, (hipStream_t)stream);
+  npb_launch_normalizer_finish(&h->norm, 0, (hipStream_t)stream);      /* no batch: the table follows the state */
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+static int normalizer_base_copy(NpbHandle *h, const char *who, double *host, bool to_device, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->norm.streams) return fail_who(h, who, g_no_normalizer);
+  if (!host) return fail_who(h, who, to_device ? ": NULL input" : ": NULL output");
+  NPB_USE_DEVICE(h);
+  const size_t bytes = 3 * (size_t)h->norm.n_streams * sizeof(double);
+  NPB_HIP(h, to_device ? hipMemcpyAsync(normalizer_base(h), host, bytes, hipMemcpyHostToDevice, (hipStream_t)stream)
+                       : hipMemcpyAsync(host, normalizer_base(h), bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));      /* the host array may go */
+  return NPB_OK;
+}
+int npb_normalizer_get_base(NpbHandle *h, double *base, void *stream) { return normalizer_base_copy(h, "npb_normalizer_get_base", base, false, stream); }
+int npb_normalizer_set_base(NpbHandle *h, const double *base, void *stream) {
+  return normalizer_base_copy(h, "npb_normalizer_set_base", (double *)base, true, stream);
+}
 
 /* ---- between the advantages and the optimiser (include/npb.h, npb_minibatch.hip): pinned moments, the permutation, the minibatch */
 static const char *moments_check(const npb_moments_desc_t *M) {
@@ -2801,18 +2851,57 @@ static const char *moments_check(const npb_moments_desc_t *M) {
   if ((uintptr_t)M->out & 7u) return "npb_rollout_moments: a misaligned out: 8-byte aligned";
   return nullptr;
 }
+/* the partials' workspace holds a tensor of `cols` columns */
+static int moments_room(NpbHandle *h, const char *who, int64_t cols) {
+  const size_t need = npb_moments_workspace(cols);
+  if (need > h->mom.cap) {      /* (hipFree of the old one waits for a launch that still reads it) */
+    char *dev = nullptr;
+    if (int rc = attachment_alloc(h, who, "the partials' workspace", nullptr, 0, need * sizeof(double), &dev)) return rc;
+    attachment_drop(&h->mom, h->mom.ws);
+    h->mom.ws = (double *)dev; h->mom.cap = need;
+  }
+  return NPB_OK;
+}
 int npb_rollout_moments(NpbHandle *h, const npb_moments_desc_t *M, void *stream) {
   if (!h) return NPB_EINVAL;
   if (const char *why = moments_check(M)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
-  const size_t need = npb_moments_workspace(M->cols);
-  if (need > h->mom.cap) {      /* (hipFree of the old one waits for a launch that still reads it) */
-    char *dev = nullptr;
-    if (int rc = attachment_alloc(h, "npb_rollout_moments", "the partials' workspace", nullptr, 0, need * sizeof(double), &dev)) return rc;
-    attachment_drop(&h->mom, h->mom.ws);
-    h->mom.ws = (double *)dev; h->mom.cap = need;
-  }
+  if (int rc = moments_room(h, "npb_rollout_moments", M->cols)) return rc;
   npb_launch_moments(M, h->mom.ws, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+/* ---- the moments across shards: a shard's part, and the combine of W parts (include/npb.h, npb_minibatch.hip) */
+const char *npb_moments_shards_check(const npb_moments_desc_t *M, const double *part, const double *parts, int n_shards, int ddof, const double *out) {
+  if (M) {      /* the part */
+    if (const char *why = moments_check(M)) return why;
+    if (!part) return "npb_rollout_moments_part: part is NULL";
+    if ((uintptr_t)part & 7u) return "npb_rollout_moments_part: a misaligned part (8-byte aligned)";
+    return nullptr;
+  }
+  if (!parts) return "npb_rollout_moments_combine: parts is NULL";
+  if ((uintptr_t)parts & 7u) return "npb_rollout_moments_combine: a misaligned parts (8-byte aligned)";
+  if (n_shards < 1 || n_shards > NPB_PPO_SHARDS_MAX) return "npb_rollout_moments_combine: n_shards must be 1 .. NPB_PPO_SHARDS_MAX (64)";
+  if (ddof < 0) return "npb_rollout_moments_combine: ddof must be >= 0";
+  if (!out) return "npb_rollout_moments_combine: out is NULL";
+  if ((uintptr_t)out & 7u) return "npb_rollout_moments_combine: a misaligned out (8-byte aligned)";
+  return nullptr;
+}
+int npb_rollout_moments_part(NpbHandle *h, const npb_moments_desc_t *M, int squares, double *part, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!M) return fail(h, NPB_EINVAL, "npb_rollout_moments_part: a NULL descriptor");
+  if (const char *why = npb_moments_shards_check(M, part, nullptr, 0, 0, nullptr)) return fail(h, NPB_EINVAL, why);
+  NPB_USE_DEVICE(h);
+  if (int rc = moments_room(h, "npb_rollout_moments_part", M->cols)) return rc;
+  npb_launch_moments_part(M, squares != 0, h->mom.ws, part, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_rollout_moments_combine(NpbHandle *h, const double *parts, int n_shards, int squares, int ddof, double *out, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (const char *why = npb_moments_shards_check(nullptr, nullptr, parts, n_shards, ddof, out)) return fail(h, NPB_EINVAL, why);
+  NPB_USE_DEVICE(h);
+  npb_launch_moments_combine(parts, n_shards, squares != 0, ddof, out, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }

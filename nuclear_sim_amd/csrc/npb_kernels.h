@@ -242,6 +242,11 @@ void npb_launch_unprime(int32_t *primed, const uint8_t *mask, int n_plants, hipS
  * reward (npd_normalizer.h): norm_reward, ended, primed and seen of every plant; carry != 0: the return is carried here (frozen: the partials
  *   kernel, which carries it otherwise, has not run) */
 void npb_launch_normalizer_finish(const npb_normalizer_t *Z, int groups, hipStream_t stream);
+/* one normaliser across shards (npb_minibatch.hip): base, device [3][n_streams], what the shards agreed on last.
+ * delta: out [3][n_streams] = the population folded since the base.  combine: the base merged with deltas [n_shards][3][n_streams] in
+ *   ascending order into the state AND the base; the caller follows it with npb_launch_normalizer_finish(Z, 0) for scale and the table */
+void npb_launch_normalizer_delta(const npb_normalizer_t *Z, const double *base, double *out, hipStream_t stream);
+void npb_launch_normalizer_combine(const npb_normalizer_t *Z, double *base, const double *deltas, int n_shards, hipStream_t stream);
 void npb_launch_normalizer_reward(const npb_normalizer_t *Z, int n_plants, const int32_t *index, const double *reward, const uint8_t *done, int carry,
                                   hipStream_t stream);
 /* npb_set_rollout (npd_rollout.h), the same for either storage type: none of them touches the arena.

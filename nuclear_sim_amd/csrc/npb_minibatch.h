@@ -66,6 +66,10 @@ typedef struct { double *ws; size_t cap; } npb_moments_ws_t;
 size_t npb_moments_workspace(int64_t cols);
 /* the four launches; ws holds at least npb_moments_workspace(M->cols) doubles */
 void npb_launch_moments(const npb_moments_desc_t *M, double *ws, hipStream_t stream);
+/* the moments across shards: a shard's part (one columns pass, squares != 0: around M->out[1]; part [2] = count, the undivided total;
+ * M->out is not written), and the combine of n_shards parts [n_shards][2] into out[0], out[1] (squares == 0) or out[2], out[3] */
+void npb_launch_moments_part(const npb_moments_desc_t *M, int squares, double *ws, double *part, hipStream_t stream);
+void npb_launch_moments_combine(const double *parts, int n_shards, int squares, int ddof, double *out, hipStream_t stream);
 void npb_launch_permutation(uint32_t N, const uint32_t *keys, int64_t first, int64_t count, int32_t *out, hipStream_t stream);
 /* what the gather reads of the handle's rollout: its buffers, the slots recorded, the shapes and element sizes they were bound with */
 typedef struct {

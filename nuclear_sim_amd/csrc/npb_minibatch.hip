@@ -160,6 +160,91 @@ extern "C" void npb_launch_normalizer_finish(const npb_normalizer_t *Z, int grou
   hipLaunchKernelGGL(npb_normalizer_finish_kernel, dim3(1), dim3(NPD_TREE), 0, stream, *Z, groups);
 }
 
+/* ---------------------------------------------------------------------------------------------------------------- across shards */
+/* One normaliser and one set of moments across W shards (include/npb.h, "ONE NORMALISER AND ONE SET OF ADVANTAGE MOMENTS ACROSS SHARDS";
+ * normalizer.shard_delta / combine and rollout.moments_part / moments_combine state them).  They live in this file for its flags: every
+ * division and the root are IEEE and no product is fused into a sum.  No atomics, no scratch, plain vector stores.
+ * The delta: a lane per stream un-merges the base from the state -- Chan's merge run backwards -- into out [3][S]: count, mean, M2 */
+#define NPD_SHARD_LANES 128          /* one workgroup: a lane per stream, NPB_NORM_STREAMS_MAX (65) at most */
+__global__ __launch_bounds__(NPD_SHARD_LANES) void npb_normalizer_delta_kernel(const double *__restrict__ count, const double *__restrict__ mean,
+                                                                              const double *__restrict__ M2, const double *__restrict__ base, int S,
+                                                                              double *__restrict__ out) {
+  const int c = threadIdx.x;
+  if (c >= S) return;
+  const double na = base[c], ma = base[S + c], Ma = base[2 * S + c], N = count[c], m = mean[c], M = M2[c];
+  const double nb = N - na;
+  double mb = 0.0, Mb = 0.0, n = 0.0;
+  if (nb > 0.0) {
+    const double ratio = na / nb, drift = m - ma, back = drift * ratio;
+    mb = m + back;
+    const double d = mb - ma, square = d * d, pairs = na * nb, weight = pairs / N, between = square * weight, within = M - Ma;
+    Mb = within - between;
+    if (Mb < 0.0) Mb = 0.0;
+    n = nb;
+  }
+  out[c] = n; out[S + c] = mb; out[2 * S + c] = Mb;
+}
+/* The combine: a lane per stream starts from the base and merges the W deltas [W][3][S] in ascending shard order, a shard with nothing
+ * new skipped; the result is the state AND the base.  scale and the features' table follow in npb_normalizer_finish_kernel (groups == 0) */
+__global__ __launch_bounds__(NPD_SHARD_LANES) void npb_normalizer_combine_kernel(double *__restrict__ count, double *__restrict__ mean, double *__restrict__ M2,
+                                                                                double *__restrict__ base, int S, const double *__restrict__ deltas, int W) {
+  const int c = threadIdx.x;
+  if (c >= S) return;
+  double n = base[c], mu = base[S + c], M = base[2 * S + c];
+  for (int w = 0; w < W; w++) {
+    const double *D = deltas + (size_t)w * 3 * S;
+    const double nb = D[c], mb = D[S + c], Mb = D[2 * S + c];
+    if (!(nb > 0.0)) continue;
+    const double N = n + nb, d = mb - mu, share = nb / N, step = d * share;
+    mu = mu + step;
+    const double sum = M + Mb, square = d * d, pairs = n * nb, weight = pairs / N, between = square * weight;
+    M = sum + between;
+    n = N;
+  }
+  count[c] = n; mean[c] = mu; M2[c] = M;
+  base[c] = n; base[S + c] = mu; base[2 * S + c] = M;
+}
+extern "C" void npb_launch_normalizer_delta(const npb_normalizer_t *Z, const double *base, double *out, hipStream_t stream) {
+  hipLaunchKernelGGL(npb_normalizer_delta_kernel, dim3(1), dim3(NPD_SHARD_LANES), 0, stream, (const double *)Z->count, (const double *)Z->mean,
+                     (const double *)Z->M2, base, Z->n_streams, out);
+}
+extern "C" void npb_launch_normalizer_combine(const npb_normalizer_t *Z, double *base, const double *deltas, int n_shards, hipStream_t stream) {
+  hipLaunchKernelGGL(npb_normalizer_combine_kernel, dim3(1), dim3(NPD_SHARD_LANES), 0, stream, Z->count, Z->mean, Z->M2, base, Z->n_streams, deltas,
+                     n_shards);
+}
+
+/* a shard's part of the moments: one workgroup ends the tree over the partials as npb_moments_finish_kernel does and stores the count and
+ * the UNDIVIDED total: part[0] = count, part[1] = total */
+__global__ __launch_bounds__(NPD_TREE) void npb_moments_part_finish_kernel(double *ws, size_t g, double count, double *__restrict__ part) {
+  __shared__ double s[NPD_TREE];
+  const int lane = threadIdx.x;
+  const double *in = npd_tree_levels(ws, g, s, lane);
+  if (lane == 0) { part[0] = count; part[1] = in[0]; }
+}
+/* one lane: the W parts [W][2] added in ascending shard order onto 0.0, then the division npb_moments_finish_kernel makes */
+__global__ __launch_bounds__(64) void npb_moments_combine_kernel(const double *__restrict__ parts, int W, int squares, double ddof, double *__restrict__ out) {
+  if (threadIdx.x != 0) return;
+  double C = 0.0, T = 0.0;
+  for (int w = 0; w < W; w++) { C = C + parts[2 * w]; T = T + parts[2 * w + 1]; }
+  if (squares) { const double less = C - ddof, var = T / less; out[2] = var; out[3] = sqrt(var); }
+  else { out[0] = C; out[1] = T / C; }
+}
+template <typename T> static void npd_moments_part_launch(const npb_moments_desc_t *M, int squares, double *ws, double *part, hipStream_t stream) {
+  const size_t rows = (size_t)M->rows, cols = (size_t)M->cols, g = (cols + NPD_TREE - 1) / NPD_TREE;
+  const dim3 grid((unsigned)g), block(NPD_TREE), one(1);
+  const T *x = (const T *)M->src;
+  if (squares) hipLaunchKernelGGL((npb_moments_columns_kernel<T, true>), grid, block, 0, stream, x, rows, cols, (const double *)M->out, ws);
+  else hipLaunchKernelGGL((npb_moments_columns_kernel<T, false>), grid, block, 0, stream, x, rows, cols, (const double *)M->out, ws);
+  hipLaunchKernelGGL(npb_moments_part_finish_kernel, one, block, 0, stream, ws, g, (double)(M->rows * M->cols), part);
+}
+extern "C" void npb_launch_moments_part(const npb_moments_desc_t *M, int squares, double *ws, double *part, hipStream_t stream) {
+  if (M->type == NPB_ROLLOUT_F64) npd_moments_part_launch<double>(M, squares, ws, part, stream);
+  else npd_moments_part_launch<float>(M, squares, ws, part, stream);
+}
+extern "C" void npb_launch_moments_combine(const double *parts, int n_shards, int squares, int ddof, double *out, hipStream_t stream) {
+  hipLaunchKernelGGL(npb_moments_combine_kernel, dim3(1), dim3(64), 0, stream, parts, n_shards, squares, (double)ddof, out);
+}
+
 /* ---------------------------------------------------------------------------------------------------------------- permutation */
 struct npd_perm_t { uint32_t N, w, mask, key[NPB_MINIBATCH_ROUNDS]; };
 

@@ -1492,6 +1492,66 @@ class BatchedPlantEnv:
         warm-start a run this way."""
         self._load_state("_norm", self.L.npb_normalizer_set_state, state)
 
+    # ---- one normaliser across shards (npb_normalizer_shard_delta, npb_normalizer_apply_shards; normalizer.shard_delta / combine)
+    def _norm_streams(self) -> int:
+        """S of the set normaliser, for the calls that synchronise shards"""
+        nm = self._on("_norm")
+        if not hasattr(self.L, "npb_normalizer_apply_shards"):
+            raise _lib.NpbError("libnpb.so has no npb_normalizer_apply_shards: rebuild")
+        return len(nm["columns"]) + (nm["reward"] is not None)
+
+    def normalizer_shard_delta(self) -> torch.Tensor:
+        """What this shard folded since the last synchronisation, a device float64 [3, S] -- count, mean, M2 -- with nothing read back
+        (npb_normalizer_shard_delta): zeros for a shard that is frozen or did not step.  ``normalizer.shard_delta`` is the same in numpy,
+        bit for bit."""
+        S = self._norm_streams()
+        with torch.cuda.device(self.device):
+            out = torch.zeros((3, S), dtype=torch.float64, device=self.device)
+        _lib.check(self.L.npb_normalizer_shard_delta(self._h, ctypes.c_void_p(out.data_ptr()), self._stream()), self._h)
+        return out
+
+    def normalizer_apply_shards(self, deltas) -> None:
+        """The base merged with W shards' deltas, a contiguous device float64 [W, 3, S] in shard order (npb_normalizer_apply_shards): the
+        result is this handle's state and its new base, and the features' table and the reward's scale follow it.  Every shard that
+        applies the same deltas holds the same bits.  Allowed while frozen.  ``normalizer.combine`` is the same in numpy."""
+        S = self._norm_streams()
+        if not isinstance(deltas, torch.Tensor) or deltas.dtype != torch.float64 or deltas.dim() != 3 or tuple(deltas.shape[1:]) != (3, S) or \
+                not 1 <= deltas.shape[0] <= _lib.PPO_SHARDS_MAX or not deltas.is_contiguous() or deltas.device != self.device:
+            raise ValueError("deltas must be a contiguous float64 [W, 3, %d] tensor on %s, W 1 .. %d" % (S, self.device, _lib.PPO_SHARDS_MAX))
+        _lib.check(self.L.npb_normalizer_apply_shards(self._h, ctypes.c_void_p(deltas.data_ptr()), deltas.shape[0], self._stream()), self._h)
+        self._norm["shards_held"] = deltas      # (alive while the launch reads it)
+
+    def normalizer_sync(self, exchange) -> None:
+        """One synchronisation of the running normaliser between shards, nothing read back: ``normalizer_shard_delta()``,
+        ``exchange(vec)`` -- this shard's device float64 [3 S] in, the [W, 3 S] of all shards out, in shard order
+        (``sharding.normalizer_exchange``) -- then ``normalizer_apply_shards``.  Afterwards every shard holds the statistics of all
+        samples of all shards, bit for bit the same, and samples from before the last synchronisation are not counted again."""
+        vec = self.normalizer_shard_delta()
+        every = exchange(vec.reshape(-1))
+        if not isinstance(every, torch.Tensor) or every.dim() != 2 or every.shape[1] != vec.numel() or not 1 <= every.shape[0] <= _lib.PPO_SHARDS_MAX:
+            raise ValueError("exchange must return the [W, %d] tensor of every shard's delta, W 1 .. %d, not %r"
+                             % (vec.numel(), _lib.PPO_SHARDS_MAX, tuple(every.shape) if isinstance(every, torch.Tensor) else every))
+        self.normalizer_apply_shards(every.contiguous().view(every.shape[0], 3, vec.shape[1]))
+
+    def normalizer_shard_state(self) -> Dict[str, np.ndarray]:
+        """``normalizer_state()`` and ``base``, float64 [3, S]: what the shards agreed on at the last synchronisation
+        (npb_normalizer_get_base).  A checkpoint of a sharded run keeps this one."""
+        S = self._norm_streams()
+        state = self.normalizer_state()
+        base = np.zeros((3, S), dtype=np.float64)
+        _lib.check(self.L.npb_normalizer_get_base(self._h, base.ctypes.data_as(ctypes.c_void_p), self._stream()), self._h)
+        state["base"] = base
+        return state
+
+    def load_normalizer_shard_state(self, state) -> None:
+        """put back what ``normalizer_shard_state()`` returned: the state as ``load_normalizer_state`` does, and the base"""
+        S = self._norm_streams()
+        base = np.ascontiguousarray(state["base"], dtype=np.float64)
+        if base.shape != (3, S):
+            raise ValueError("base must be [3, %d], not %r" % (S, base.shape))
+        self.load_normalizer_state({k: v for k, v in state.items() if k != "base"})
+        _lib.check(self.L.npb_normalizer_set_base(self._h, base.ctypes.data_as(ctypes.c_void_p), self._stream()), self._h)
+
     def normalizer_stats(self) -> Dict[str, np.ndarray]:
         """``count``, ``mean``, ``var`` and ``scale`` (what the features' table holds; the return stream's last) as numpy, float64 [S]"""
         z = self.normalizer_spec()
@@ -1758,6 +1818,45 @@ class BatchedPlantEnv:
         self._moments_held = x      # (alive while the launches read it)
         return out
 
+    def rollout_moments_shards(self, exchange, x=None, ddof: int = 1) -> torch.Tensor:
+        """``(count, mean, var, std)`` over ALL shards' ``x`` (default: the advantages the last ``rollout_advantages`` formed) as a device
+        float64 [4] tensor, the same bits on every shard, nothing read back: this shard's part (npb_rollout_moments_part), the combine
+        (npb_rollout_moments_combine), the part around the global mean, the combine.  ``exchange(vec)`` takes this shard's device
+        float64 [2] and returns the [W, 2] of all shards in shard order (``sharding.ppo_exchange`` serves); it is called twice.  With one
+        shard the result is ``rollout_moments``'s, bit for bit.  ``nuclear_sim_amd.rollout.moments_shards`` is the same in numpy.  A
+        total count that does not exceed ``ddof`` cannot be seen without a read-back: the variance is then an infinity or a NaN."""
+        if not hasattr(self.L, "npb_rollout_moments_part"):
+            raise _lib.NpbError("libnpb.so has no npb_rollout_moments_part: rebuild")
+        if x is None:
+            adv, _, t = self._last_advantages(self._on("_roll"))
+            x = adv[:t]
+        if not isinstance(x, torch.Tensor) or x.device != self.device or x.dim() != 2 or x.dtype not in self._MB_DTYPES or not x.is_contiguous():
+            raise ValueError("moments are taken of a contiguous [rows, cols] float32 or float64 tensor on %s" % (self.device,))
+        rows, cols = x.shape
+        if rows * cols < 1:
+            raise ValueError("rows * cols must be >= 1")
+        if int(ddof) < 0:
+            raise ValueError("ddof must be >= 0")
+        with torch.cuda.device(self.device):
+            out = torch.zeros(4, dtype=torch.float64, device=self.device)
+            parts = [torch.zeros(2, dtype=torch.float64, device=self.device) for _ in range(2)]
+        d = _lib.NpbMomentsDesc()
+        d.src, d.type, d.ddof, d.rows, d.cols, d.out = x.data_ptr(), _lib.ROLLOUT_DTYPES[self._MB_DTYPES[x.dtype]], 0, rows, cols, out.data_ptr()
+        held = [x, out] + parts
+        for squares, part in enumerate(parts):
+            _lib.check(self.L.npb_rollout_moments_part(self._h, ctypes.byref(d), squares, ctypes.c_void_p(part.data_ptr()), self._stream()), self._h)
+            every = exchange(part)
+            if not isinstance(every, torch.Tensor) or every.dim() != 2 or every.shape[1] != 2 or not 1 <= every.shape[0] <= _lib.PPO_SHARDS_MAX or \
+                    every.dtype != torch.float64 or every.device != self.device:
+                raise ValueError("exchange must return the float64 [W, 2] tensor of every shard's part on %s, W 1 .. %d"
+                                 % (self.device, _lib.PPO_SHARDS_MAX))
+            every = every.contiguous()
+            held.append(every)
+            _lib.check(self.L.npb_rollout_moments_combine(self._h, ctypes.c_void_p(every.data_ptr()), every.shape[0], squares, int(ddof),
+                                                          ctypes.c_void_p(out.data_ptr()), self._stream()), self._h)
+        self._moments_held = held      # (alive while the launches read them)
+        return out
+
     def rollout_permutation(self, N: int, keys, first: int = 0, count: Optional[int] = None) -> torch.Tensor:
         """entries ``first .. first + count`` of the permutation of range(N) under ``keys`` (``rollout.permutation_keys(seed, epoch)``)
         as a device int32 tensor (npb_rollout_permutation): ``nuclear_sim_amd.rollout.permutation``, entry by entry"""
@@ -1769,7 +1868,7 @@ class BatchedPlantEnv:
         return out[:count]
 
     def rollout_minibatches(self, batch_size, epochs: int = 1, seed: int = 0, first_epoch: int = 0, normalize: bool = True, eps: float = 1e-8,
-                            ddof: int = 1, unit: str = "transition", drop_last: bool = False, advantages=None, max_blocks: int = 0):
+                            ddof: int = 1, unit: str = "transition", drop_last: bool = False, advantages=None, max_blocks: int = 0, moments=None):
         """Shuffled minibatches of the recorded slots, gathered on the device (npb_rollout_minibatch): a generator of dicts ``{"index",
         "obs", "act", "extra", "adv", "ret", "epoch"}``, one launch each on the env's stream and no host synchronisation.
         ``unit="transition"``: every epoch is a permutation of the t * n recorded cells; ``index`` [count] is the flat cell s * n + p and
@@ -1778,7 +1877,9 @@ class BatchedPlantEnv:
         a function of ``(seed, e)`` alone (``rollout.permutation_keys``; epochs ``first_epoch .. first_epoch + epochs``), so an epoch is
         resumed from three numbers.  ``normalize``: the advantages' moments are formed once (``rollout_moments``, ``ddof``) and ``adv`` is
         ``((double)adv - mean) / (std + eps)``, narrowed once.  ``advantages``: ``(adv, ret)`` [>= t, n] device tensors of one type,
-        default what the last ``rollout_advantages`` returned.  A short last batch is yielded unless ``drop_last``.
+        default what the last ``rollout_advantages`` returned.  A short last batch is yielded unless ``drop_last``.  ``moments``: a
+        device float64 [4] (``rollout_moments_shards``: the moments over all shards) used in place of the handle's own; together with
+        ``normalize=False`` it is refused by name.
         THE YIELDED TENSORS ARE VIEWS OF BUFFERS THE ENV KEEPS, the same storage on every yield: use or copy a minibatch before asking for
         the next.  ``act`` / ``extra`` are None where the rollout has none.  ``set_rollout(None)`` drops the buffers.
         ``nuclear_sim_amd.rollout.minibatch`` is the same in numpy, bit for bit."""
@@ -1792,6 +1893,12 @@ class BatchedPlantEnv:
             raise ValueError("batch_size must be >= 1 and epochs >= 0")
         if not float(eps) >= 0.0:
             raise ValueError("eps must be >= 0")
+        if moments is not None:
+            if not normalize:
+                raise ValueError("moments= are given and normalize=False: the moments are what normalises the advantages")
+            if not isinstance(moments, torch.Tensor) or moments.dtype != torch.float64 or tuple(moments.shape) != (4,) or \
+                    not moments.is_contiguous() or moments.device != self.device:
+                raise ValueError("moments must be a contiguous float64 [4] tensor on %s" % (self.device,))
         adv, ret, t = self._last_advantages(ro, advantages)
         if t < 1:
             raise _lib.NpbError("nothing recorded yet (t == 0)")
@@ -1800,7 +1907,8 @@ class BatchedPlantEnv:
         if N > rollout.N_MAX:
             raise ValueError("t * n = %d is beyond 2^31 - 1, what an index holds" % N)
         B = min(B, N)
-        moments = self.rollout_moments(adv[:t], ddof) if normalize else None
+        if moments is None:
+            moments = self.rollout_moments(adv[:t], ddof) if normalize else None
         spec, tensors = ro["spec"], ro["tensors"]
         (K, C), A, E = spec["stack"], spec["axes"], spec["extras"]
         rows = B * t if plant else B
@@ -2152,7 +2260,8 @@ class BatchedPlantEnv:
 
     def policy_train(self, batch_size, epochs: int = 1, seed: int = 0, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0,
                      max_grad_norm: float = 0.5, rows_per_chain: int = 256, lr=3e-4, betas=(0.9, 0.999), eps: float = 1e-5,
-                     clip_vf: float = 0.0, target_kl=None, more: bool = False, exchange=None, shard_cells=None, **minibatches):
+                     clip_vf: float = 0.0, target_kl=None, more: bool = False, exchange=None, shard_cells=None, global_moments: bool = False,
+                     **minibatches):
         """The optimiser's half of a PPO iteration: ``rollout_minibatches(batch_size, epochs, seed, **minibatches)`` and one
         npb_policy_update -- gradient and Adam step -- per minibatch.  Returns every update's stats as ONE device tensor [updates, 8]
         (``ppo.STATS``'s order), and with ``more=True`` ``(stats, more [updates, 4])`` (``ppo.STATS_MORE``'s order).  ``collect``,
@@ -2168,7 +2277,9 @@ class BatchedPlantEnv:
         ``shard_cells``: the number of recorded cells (t * n; plants for ``unit="plant"``) of every shard, in shard order, this env's
         among them (``sharding.gather_cells``).  ``exchange(vec)``: takes this shard's device float64 [L] and returns the [W, L] of all
         of them, on the device, in shard order (``sharding.ppo_exchange``).  ``batch_size`` is per shard and the advantages are
-        normalised per shard.  Every shard's update count under ``batch_size`` and ``drop_last`` is formed on the host before any
+        normalised per shard -- unless ``global_moments=True``, which needs ``exchange``: ``rollout_moments_shards(exchange)`` is formed
+        once, over all shards, and every minibatch of every shard is normalised with it (two exchanges of a [2] vector more, nothing
+        read back).  Every shard's update count under ``batch_size`` and ``drop_last`` is formed on the host before any
         device work, and a mismatch is refused by name; update i's ``count_total`` is the sum of the shards' rows of update i, and the
         update is ``policy_shard_sums``, ``exchange``, ``policy_apply_shards``: every shard ends with the same parameters, bit for bit,
         with no broadcast.  The gate is taken on the global ``approx_kl``; the stats are the whole update's."""
@@ -2195,6 +2306,13 @@ class BatchedPlantEnv:
                 raise ValueError("shard_cells %r does not hold this shard's own %d cells" % (cells, own))
             per = t if minibatches.get("unit", "transition") == "plant" else 1      # (a plant is t rows: the shards record in lockstep)
             totals = [per * sum(c[i] for c in counts) for i in range(len(counts[0]))]
+        if global_moments:
+            if exchange is None:
+                raise ValueError("global_moments=True needs exchange= and shard_cells=: the moments are formed over all shards")
+            if minibatches.get("moments") is not None or minibatches.get("normalize", True) is False:
+                raise ValueError("global_moments=True forms the moments itself: leave moments= and normalize= alone")
+            adv, _, t = self._last_advantages(self._on("_roll"), minibatches.get("advantages"))
+            minibatches = dict(minibatches, moments=self.rollout_moments_shards(exchange, adv[:t], minibatches.get("ddof", 1)))
         batches = self.rollout_minibatches(batch_size, epochs, seed, **minibatches)
         rates = None
         if callable(lr) or isinstance(lr, (list, tuple, np.ndarray)):

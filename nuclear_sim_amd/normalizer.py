@@ -59,8 +59,35 @@ still carried.
 
 ``merge`` is Chan's merge of several states -- shards' --, host only and not bit-pinned.
 
+ONE NORMALISER ACROSS SHARDS (``shard_delta``, ``combine``; npb_normalizer_shard_delta, npb_normalizer_apply_shards and
+``env.normalizer_sync`` give these bits).  Every shard keeps, beside its state, the BASE: what all shards agreed on at the last
+synchronisation, zeros before the first.  A synchronisation has two halves.  ``shard_delta(cur, base)`` is, per stream, the population
+the shard folded since the base -- Chan's merge run backwards, every operation in float64 and rounded on its own:
+
+    na, ma, Ma = base;  N, m, M = cur;  nb = N - na
+    nb > 0:   mb = m + (m - ma) * (na / nb);   d = mb - ma
+              Mb = (M - Ma) - (d * d) * ((na * nb) / N),   0.0 where that is negative
+              delta = (nb, mb, Mb)
+    else:     delta = (0.0, 0.0, 0.0)        (a frozen shard, or one that did not step)
+
+The forward merge has m = ma + (mb - ma) * nb / N, so m - ma = (mb - ma) * nb / N and mb - m = (mb - ma) * na / N = (m - ma) * na / nb:
+the first line; and M = Ma + Mb + d^2 * na * nb / N solved for Mb is the second.  With ``base == 0`` the delta is ``cur`` exactly: na = 0
+makes the correction of the mean m * 0 and that of M2 d^2 * 0.  ``combine(base, deltas)`` starts from the base and goes through the
+shards in ascending order; only a shard with nb > 0 is merged:
+
+    N = n + nb;  d = mb - mean;  mean = mean + d * (nb / N)
+    M2 = (M2 + Mb) + (d * d) * ((n * nb) / N);  n = N
+
+The result is every shard's new state AND its new base; the features' table and the return stream's rscale follow it as they follow a
+loaded state.  The per-plant return carry (``ret``, ``primed``, ``seen``, ``ended``) stays with its shard.  Shards that combine the same
+deltas in the same order hold the same bits, so nothing is broadcast, and samples folded before the base are never counted twice.
+ONE CONSEQUENCE: W = 1 is the identity only from a zero base.  From any other base the shard's own samples are un-merged and merged
+again, and both round: the state after a synchronisation of one shard may differ from the state before it in the last bits.  That is
+intended -- the price of every shard computing the same thing.
+
 NOT here: statistics over fresh frames; per-plant statistics (``env.enable_column_stats`` has them); an exponential moving average; half
-types; synchronising shards on the device; normalising ``bits`` or setpoint-error columns."""
+types; synchronising shards on the device; normalising ``bits`` or setpoint-error columns.  (Synchronising shards on the device has
+since come: ``shard_delta`` and ``combine`` above state it.)"""
 import copy
 from typing import Dict, Optional, Sequence
 
@@ -208,3 +235,61 @@ def merge(states: Sequence[Dict]) -> Dict[str, np.ndarray]:
         M2 = M2 + Mb + delta * delta * (count * nb / safe)
         count = N
     return {"count": count, "mean": mean, "M2": M2}
+
+
+SHARDS_MAX = 64       # NPB_PPO_SHARDS_MAX: the shards one combine takes
+
+
+def _triple(state, who):
+    """``{count, mean, M2}`` or an array [3, S] as three float64 [S] vectors"""
+    if isinstance(state, dict):
+        rows = [np.asarray(state[k], dtype=np.float64) for k in ("count", "mean", "M2")]
+    else:
+        a = np.asarray(state, dtype=np.float64)
+        if a.ndim != 2 or a.shape[0] != 3:
+            raise ValueError("%s: a state is {count, mean, M2} or an array [3, S], not an array %r" % (who, a.shape))
+        rows = list(a)
+    if any(r.ndim != 1 or r.shape != rows[0].shape for r in rows):
+        raise ValueError("%s: count, mean and M2 must be vectors of one length" % who)
+    return rows
+
+
+def shard_delta(cur: Dict, base: Dict) -> Dict[str, np.ndarray]:
+    """The population a shard folded since ``base`` (module docstring): ``{count, mean, M2}`` float64 [S]; zeros for a stream with nothing
+    new.  ``shard_delta(cur, zeros)`` is ``cur`` by bits."""
+    N, m, M = _triple(cur, "shard_delta")
+    na, ma, Ma = _triple(base, "shard_delta")
+    if N.shape != na.shape:
+        raise ValueError("shard_delta: cur has %d streams and base %d" % (N.size, na.size))
+    with np.errstate(all="ignore"):
+        nb = N - na
+        on = nb > 0
+        safe = np.where(on, nb, 1.0)
+        mb = m + (m - ma) * (na / safe)
+        d = mb - ma
+        Mb = (M - Ma) - (d * d) * ((na * nb) / np.where(on, N, 1.0))
+        Mb = np.where(Mb < 0.0, 0.0, Mb)
+    zero = np.zeros_like(nb)
+    return {"count": np.where(on, nb, zero), "mean": np.where(on, mb, zero), "M2": np.where(on, Mb, zero)}
+
+
+def combine(base: Dict, deltas: Sequence) -> Dict[str, np.ndarray]:
+    """``base`` merged with the shards' deltas in ascending order (module docstring): every shard's new state and new base, ``{count,
+    mean, M2}`` float64 [S].  ``deltas``: 1 .. 64 of what ``shard_delta`` returns, or an array [W, 3, S]."""
+    n, mean, M2 = (r.copy() for r in _triple(base, "combine"))
+    deltas = list(deltas)
+    if not 1 <= len(deltas) <= SHARDS_MAX:
+        raise ValueError("combine: 1 .. %d shards, not %d" % (SHARDS_MAX, len(deltas)))
+    with np.errstate(all="ignore"):
+        for D in deltas:
+            nb, mb, Mb = _triple(D, "combine")
+            if nb.shape != n.shape:
+                raise ValueError("combine: a delta has %d streams and the base %d" % (nb.size, n.size))
+            on = nb > 0
+            N = n + nb
+            safe = np.where(on, N, 1.0)
+            d = mb - mean
+            mean = np.where(on, mean + d * (nb / safe), mean)
+            M2 = np.where(on, (M2 + Mb) + (d * d) * ((n * nb) / safe), M2)
+            n = np.where(on, N, n)
+    return {"count": n, "mean": mean, "M2": M2}

@@ -10,7 +10,9 @@ contract: no scan, no vectorisation along t.
 
 ``moments``, ``permutation_keys``, ``permutation`` and ``minibatch`` state what happens between the advantages and the optimiser
 (npb_rollout_moments, npb_rollout_permutation, npb_rollout_minibatch): the order of every addition of the moments is pinned, the shuffled
-order is a function of (seed, epoch, position) alone, and the device produces their bits too."""
+order is a function of (seed, epoch, position) alone, and the device produces their bits too.  ``moments_part``, ``moments_combine`` and
+``moments_shards`` cut the moments where the pinned sums end, so that W shards form ONE mean and ONE spread (npb_rollout_moments_part,
+npb_rollout_moments_combine)."""
 import numpy as np
 
 HORIZON_MAX, EXTRAS_MAX = 4096, 8
@@ -192,6 +194,67 @@ def moments(x, ddof=1):
         var = _tree(col2) / np.float64(count - ddof)
         std = np.sqrt(var)
     return np.float64(count), mean, var, std
+
+
+SHARDS_MAX = 64       # NPB_PPO_SHARDS_MAX: the shards one combine takes
+
+
+def moments_part(x, mean=None):
+    """``(count, total)`` of one shard's ``x`` [rows, cols] (float32 or float64), both float64 (npb_rollout_moments_part): ``total`` is the
+    undivided value ``moments`` has before its division -- a column's rows added in order onto 0.0, then ``_tree`` over the columns.  With
+    ``mean`` given the summands are the rounded squares of ``(double)x - mean``."""
+    x = np.asarray(x)
+    if x.ndim != 2 or x.dtype not in (np.float32, np.float64):
+        raise ValueError("moments are taken of a [rows, cols] float32 or float64 array")
+    rows, cols = x.shape
+    if rows < 1 or cols < 1:
+        raise ValueError("rows and cols must be >= 1")
+    with np.errstate(invalid="ignore", over="ignore"):
+        col = np.zeros(cols, dtype=np.float64)
+        for s in range(rows):
+            w = x[s].astype(np.float64)
+            if mean is not None:
+                d = w - np.float64(mean)
+                w = d * d
+            col += w
+        return np.float64(rows * cols), _tree(col)
+
+
+def moments_combine(parts, ddof=1, squares=False):
+    """W shards' parts [W, 2] added in ascending shard order (npb_rollout_moments_combine): ``C = 0.0; T = 0.0; for w ascending: C = C +
+    count_w; T = T + total_w``.  ``squares`` false: ``(C, T / C)``, the count and the mean; true: ``(var, std)`` with ``var = T / (C -
+    ddof)``, ``std = sqrt(var)``.  IEEE division and root; a NaN propagates."""
+    parts = np.asarray(parts, dtype=np.float64)
+    if parts.ndim != 2 or parts.shape[1] != 2 or not 1 <= parts.shape[0] <= SHARDS_MAX:
+        raise ValueError("parts are [W, 2] with W 1 .. %d, not %r" % (SHARDS_MAX, parts.shape))
+    ddof = int(ddof)
+    if ddof < 0:
+        raise ValueError("ddof must be >= 0")
+    C, T = np.float64(0.0), np.float64(0.0)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for count, total in parts:
+            C = C + count
+            T = T + total
+        if not C >= 1.0:
+            raise ValueError("the shards' total count %r is below 1" % (float(C),))
+        if not squares:
+            return C, T / C
+        if C <= ddof:
+            raise ValueError("the shards' total count %d must exceed ddof = %d" % (int(C), ddof))
+        var = T / (C - np.float64(ddof))
+        return var, np.sqrt(var)
+
+
+def moments_shards(xs, ddof=1):
+    """``(count, mean, var, std)`` over W shards' arrays (``env.rollout_moments_shards``), the four steps in order: every shard's part,
+    the combine, every shard's part around the GLOBAL mean, the combine.  ``moments_shards([x], ddof)`` has the bits of ``moments(x,
+    ddof)``: no total is ever -0.0, so ``0.0 + T`` is ``T``."""
+    xs = list(xs)
+    count, mean = moments_combine([moments_part(x) for x in xs], ddof, False)
+    if count <= int(ddof):
+        raise ValueError("the shards' total count %d must exceed ddof = %d" % (int(count), int(ddof)))
+    var, std = moments_combine([moments_part(x, mean) for x in xs], ddof, True)
+    return count, mean, var, std
 
 
 _M64 = (1 << 64) - 1

@@ -41,7 +41,8 @@ def reduce_counters(counters: torch.Tensor, group=None) -> torch.Tensor:
 def gather_shard_sums(vec: torch.Tensor, group=None) -> torch.Tensor:
     """One all-gather of a shard's L pinned double sums (``env.policy_shard_sums``) into [W, L] on every rank, in rank order: what
     ``policy_apply_shards`` and ``ppo.combine`` add in ascending order.  A gather and not an all-reduce: the order of a reduce is not ours
-    to pin, while the gather plus the pinned combine gives every rank the same bits.  8 * L bytes a shard."""
+    to pin, while the gather plus the pinned combine gives every rank the same bits.  8 * L bytes a shard.  It serves every pinned vector:
+    the normaliser's delta (``env.normalizer_sync``, L = 3 S) and the moments' parts (``env.rollout_moments_shards``, L = 2) too."""
     world = dist.get_world_size(group)
     vec = vec.contiguous()
     out = torch.empty((world, vec.numel()), dtype=vec.dtype, device=vec.device)
@@ -52,6 +53,11 @@ def gather_shard_sums(vec: torch.Tensor, group=None) -> torch.Tensor:
 def ppo_exchange(group=None):
     """the ``exchange`` callable of ``env.policy_train``: ``gather_shard_sums`` over ``group``"""
     return lambda vec: gather_shard_sums(vec, group)
+
+
+def normalizer_exchange(group=None):
+    """the ``exchange`` callable of ``env.normalizer_sync`` and ``env.rollout_moments_shards``: ``gather_shard_sums`` over ``group``"""
+    return ppo_exchange(group)
 
 
 def gather_cells(n_cells: int, group=None) -> list:
