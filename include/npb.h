@@ -1422,7 +1422,37 @@ NPB_API int npb_normalizer_clear(NpbHandle *h, const uint8_t *mask, void *stream
  *   first (npb_features_prime).
  * The kernel (npb_policy.hip) runs on the f32 matrix cores (v_mfma_f32_32x32x2_f32: exact f32, the statement's fmaf chain two k a call; the
  * relu tests hold it to the statement's bits): one workgroup per 32 plants, the activations through LDS, no atomics, no scratch.
- * Not here: a shared trunk; discrete or squashed (tanh-Gaussian) actions; a state-dependent std; recurrent nets; half types; noise that restarts with the episode; skipping the forward pass on held steps of interval > 1.
+ * THE RECURRENT CORE (npb_set_policy_core; npb_policy_core.hip; nuclear_sim_amd/recurrent.py states it in numpy, and that statement is the
+ * contract): one GRU cell of width H = 1 .. NPB_POLICY_WIDTH_MAX shared by actor and critic, in the same ONE launch.  Its input is the K * C
+ * feature cells; both nets read the new hidden state h' in place of the features (their first layers have in = H).  Parameters in
+ * torch.nn.GRUCell's layout and gate order (r, z, n), at the front of theta: W_ih[3H][K * C] | b_ih[3H] | W_hh[3H][H] | b_hh[3H] | the
+ * actor | the critic | log_std | std.  One step of one plant, all float, every operation rounded on its own:
+ *   gi = layer(x, W_ih, b_ih); gh = layer(h, W_hh, b_hh)      (the fmaf chain above)
+ *   r[j] = S(gi[j] + gh[j]); z[j] = S(gi[H + j] + gh[H + j]); n[j] = T(gi[2H + j] + r[j] * gh[2H + j]); h'[j] = n[j] + z[j] * (h[j] - n[j])
+ * NPB_POLICY_GATES_HARD (bit-exact): y = 0.25f * a + 0.5f, S = y < 0 ? +0.0 : (y > 1 ? 1 : y); T = a < -1 ? -1 : (a > 1 ? 1 : a).
+ * NPB_POLICY_GATES_SOFT: T = the float tanh, S(a) = 0.5f * tanh(0.5f * a) + 0.5f: the float tanh stays the one licensed difference.
+ * Restart: in front of a step a plant's h is +0.0 where the plant is unprimed (fresh, or restarted by npb_reset, npb_reset_reference,
+ * npb_restore, npb_restore_bank, which unprime exactly the plants of their mask) or where its carried episode index is not the one the
+ * policy saw last (the autoreset's restarts); a step then primes the plant and remembers the index.  A plant with a non-finite feature
+ * gets THE quiet NaN in every output and h' = +0.0.
+ * npb_policy_core_t: width, gates, and device tensors of the caller's: hidden [n][H], the live state, updated in place by every step;
+ *   first [n][H] or NULL: on the step recorded into slot 0 of a set rollout, the h that step read, the restart rule applied; final
+ *   [n * final_rows][H] or NULL with final_rows = 0 (else the set rollout's final_rows): behind the rollout's post kernel, hidden[p] -- the
+ *   h' of this step -- into row final_row[t][p] for every plant that took a row of final_obs.  The value of a truncated transition's
+ *   terminal state is critic(GRU(final_obs[row], final[row])).
+ * npb_set_policy_core(h, desc, core): npb_set_policy with a core (core = NULL: without one).  npb_policy_core_check(core, n_plants,
+ *   features_cells): that check alone, without a handle; NULL = accepted, else the reason: n_plants < 1; features_cells out of range; a width
+ *   outside 1 .. NPB_POLICY_WIDTH_MAX; unknown gates; a NULL hidden; final_rows < 0; final without final_rows or final_rows without final;
+ *   n_plants * final_rows beyond int32; a misaligned tensor.  npb_policy_core_count(desc, core, features_cells, n_axes): theta's length.
+ * npb_policy_values_hidden(h, rows, type, n_rows, hidden_rows, out, stream): the critic over GRU(rows, hidden_rows), hidden_rows device float
+ *   [n_rows][H] the states in front of the rows; rows = NULL and hidden_rows = NULL: the current features and the live hidden state under the
+ *   restart rule (the last_value: a plant that restarted on the last step bootstraps from +0.0).  Nothing is written to hidden, seen or
+ *   primed.  npb_policy_values is refused by name while a core is set.
+ * npb_policy_core_get_state / _set_state carry hidden (HOST float [n][H]), seen and primed (HOST int32 [n]).
+ * Training through time is not built: npb_policy_grad, _update, _shard_sums, _apply_shards, _combine_shards (and their _more forms) and
+ *   npb_policy_train_begin refuse a policy with a core by name.  Collect on the device, train on whole-sequence minibatches outside
+ *   (recurrent.replay gives the states from `first`), put the parameters back with npb_policy_load.
+ * Not here: a shared trunk; discrete or squashed (tanh-Gaussian) actions; a state-dependent std; LSTM cells, stacked or per-net cores, training the core on the device; half types; noise that restarts with the episode; skipping the forward pass on held steps of interval > 1.
  * NPB_VERSION stays 154: a binding detects the entry points by name.  A handle that never calls this behaves as before in every entry
  * point. */
 #define NPB_POLICY_HIDDEN_MAX 3
@@ -1447,6 +1477,21 @@ NPB_API int npb_policy_values(NpbHandle *h, const void *rows, int type, int n_ro
 NPB_API int npb_policy_noise(NpbHandle *h, uint64_t t, double *z, uint32_t *words, void *stream);
 NPB_API int npb_policy_get_state(NpbHandle *h, uint64_t *t);
 NPB_API int npb_policy_set_state(NpbHandle *h, uint64_t t);
+enum { NPB_POLICY_GATES_SOFT = 0, NPB_POLICY_GATES_HARD = 1 };
+typedef struct npb_policy_core_t {
+  int width;                     /* H */
+  int gates;                     /* NPB_POLICY_GATES_SOFT | NPB_POLICY_GATES_HARD */
+  float *hidden;                 /* device [n_plants][H] */
+  float *first;                  /* device [n_plants][H], or NULL */
+  float *final;                  /* device [n_plants * final_rows][H], or NULL */
+  int final_rows;                /* R of the set rollout, 0 without final */
+} npb_policy_core_t;
+NPB_API int npb_set_policy_core(NpbHandle *h, const npb_policy_desc_t *desc, const npb_policy_core_t *core);
+NPB_API const char *npb_policy_core_check(const npb_policy_core_t *core, int n_plants, int features_cells);
+NPB_API int64_t npb_policy_core_count(const npb_policy_desc_t *desc, const npb_policy_core_t *core, int features_cells, int n_axes);
+NPB_API int npb_policy_values_hidden(NpbHandle *h, const void *rows, int type, int n_rows, const float *hidden_rows, float *out, void *stream);
+NPB_API int npb_policy_core_get_state(NpbHandle *h, float *hidden, int32_t *seen, int32_t *primed, void *stream);
+NPB_API int npb_policy_core_set_state(NpbHandle *h, const float *hidden, const int32_t *seen, const int32_t *primed, void *stream);
 NPB_API int npb_collect(NpbHandle *h, int steps, double *obs, double *reward, uint8_t *done, uint32_t *trip_flags, double *info, void *stream);
 
 /* Training the set policy on the device: the PPO loss of one minibatch, its gradient through both nets, the gradient's clipping and one

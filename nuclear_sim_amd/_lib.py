@@ -12,6 +12,7 @@ import os
 import numpy as np
 
 from .ppo_abi import PPO_SHARD_ROWS, PPO_SHARDS_MAX, PPO_STATS_MORE, NpbPpoMore, NpbPpoShards
+from .recurrent_abi import POLICY_GATES, NpbPolicyCore
 from .schema import PARAMS, SCHEMA
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -1225,6 +1226,13 @@ ENTRY_POINTS = (
         "npb_policy_get_state": (None, [_vp, _P(_u64)]),
         "npb_policy_set_state": (None, [_vp, _u64]),
         "npb_collect": (None, [_vp, _ci] + [_vp] * 6)}),
+    ("npb_set_policy_core", {     # the recurrent policy: a GRU cell in front of actor and critic, its hidden state carried per plant
+        "npb_set_policy_core": (None, [_vp, _P(NpbPolicyDesc), _P(NpbPolicyCore)]),
+        "npb_policy_core_check": (_cs, [_P(NpbPolicyCore), _ci, _ci]),
+        "npb_policy_core_count": (_i64, [_P(NpbPolicyDesc), _P(NpbPolicyCore), _ci, _ci]),
+        "npb_policy_values_hidden": (None, [_vp, _vp, _ci, _ci, _vp, _vp, _vp]),
+        "npb_policy_core_get_state": (None, [_vp] * 5),
+        "npb_policy_core_set_state": (None, [_vp] * 5)}),
     ("npb_policy_grad", {     # training the policy: the PPO loss, its gradient and the Adam step
         "npb_ppo_check": (_cs, [_P(NpbPpoDesc), _ci, _ci]),
         "npb_policy_grad": (None, [_vp, _P(NpbPpoDesc), _vp]),

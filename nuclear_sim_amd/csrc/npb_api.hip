@@ -103,6 +103,9 @@ struct NpbHandle {
   /* npb_set_policy: the shapes, the parameters on the device as the caller packed them and as the kernel reads them (base pol.theta), the
    * caller's descriptor, and the draw counter t */
   npb_policy_t pol; uint64_t pol_t;
+  /* npb_set_policy_core: the GRU cell in front of both nets -- its six gate layers, the caller's hidden, first and final, and the restart
+   * words primed and seen on the device (base core.primed; NULL = the policy has no core); dropped with the policy */
+  npd_policy_core_t core;
   /* npb_policy_grad / npb_policy_adam: the gradient, the statistics, the optimiser's m, v and step (base ppo.stats) and the chains'
    * workspace (base ppo.chain_stats), allocated on first use, dropped with the policy */
   npb_ppo_t ppo;
@@ -336,6 +339,11 @@ static const char *side_refusal(int b, bool bank) { return bank ? g_side[b].no_b
 static void clear_episodes(NpbHandle *h, const uint8_t *mask, bool counters, hipStream_t stream) {
   int32_t *len = counters ? h->ep_len : nullptr;
   if (len || h->ep_start) npb_launch_episode_clear(mask, len, counters ? h->ep_ret : nullptr, h->ep_index, h->ep_start, h->n_plants, h->pitch, stream);
+}
+/* npb_reset, npb_reset_reference, npb_restore, npb_restore_bank: a recurrent policy's hidden state restarts with the plants of mask -- they
+ * are unprimed, and the policy's next launch reads +0.0 for them (npb_policy_core.hip) */
+static void core_restart(NpbHandle *h, const uint8_t *mask, hipStream_t stream) {
+  if (h->core.primed) npb_launch_unprime(h->core.primed, mask, h->n_plants, stream);
 }
 static npb_episode_counters_t counters_of(const NpbHandle *h) { return npb_episode_counters_t{h->ep_len, h->ep_ret, h->ep_index, h->ep_out_index}; }
 /* episode streams: the plants whose episode index the call before has bumped begin their streams anew, behind that call's kernels.
@@ -617,6 +625,7 @@ int npb_destroy(NpbHandle *h) {
   attachment_drop(&h->feat, h->feat.cols); attachment_drop(&h->ctl, h->ctl.age); attachment_drop(&h->ro, h->ro.n_final);
   attachment_drop(&h->mom, h->mom.ws); attachment_drop(&h->norm, h->norm.streams);
   ppo_drop(h);
+  attachment_drop(&h->core, h->core.primed);
   attachment_drop(&h->pol, h->pol.theta);
   for (Sampler *sm : h->samplers) if (sm) { (void)hipFree(sm->dev); delete sm; }
   delete h;
@@ -932,6 +941,7 @@ int npb_reset(NpbHandle *h, const uint8_t *mask, void *stream) {
   }
   clear_episodes(h, mask, true, (hipStream_t)stream);
   restart_streams(h, false, (hipStream_t)stream);
+  core_restart(h, mask, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -944,6 +954,7 @@ int npb_reset_reference(NpbHandle *h, const uint8_t *mask, int start_at_steady_s
   if (h->diag_carry) npb_launch_diag_carried_put(h->diag, h->diag_pitch, mask, h->n_plants, h->pitch, diag_reference_reset_values(), (hipStream_t)stream);
   clear_episodes(h, mask, true, (hipStream_t)stream);
   restart_streams(h, false, (hipStream_t)stream);
+  core_restart(h, mask, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -1211,7 +1222,14 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
   }
   if (h->pol.theta) {      /* the policy: the features read, the controls' input, value and log-probability written, in front of the rollout's record of them */
     const npd_policy_run_t run = policy_run(h);
-    npb_launch_policy(&h->pol, &run, (hipStream_t)stream);
+    if (h->core.primed) {      /* with a core: the cell first, its hidden state restarted with the episode; slot 0 of a rollout keeps the state it read */
+      npd_policy_core_run_t cell = {};
+      cell.h = cell.h_out = h->core.hidden; cell.first_out = h->ro.n_final && h->ro.t == 0 ? h->core.first : nullptr;
+      cell.primed = h->core.primed; cell.seen = h->core.seen; cell.index = h->ep_index; cell.remember = 1;
+      npb_launch_policy_core(&h->pol, &h->core, &run, &cell, (hipStream_t)stream);
+    } else {
+      npb_launch_policy(&h->pol, &run, (hipStream_t)stream);
+    }
     if (!h->pol.D.deterministic) h->pol_t++;
   }
   if (h->ro.n_final)      /* the rollout's slot t: what the policy saw and what it wrote, before the controls kernel and the step change either */
@@ -1280,6 +1298,8 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
   if (h->ro.n_final) {      /* the rollout's slot t: reward, outcome and the truncated plants' stacks, terminal frame included, while the carried length is the old one */
     npb_launch_rollout_post(&h->ro, h->feat.out, recorded_reward, done, h->autoreset ? h->ep_len : nullptr, h->autoreset ? h->ep_index : nullptr,
                             h->max_episode_steps, h->n_plants, (hipStream_t)stream);
+    if (h->core.primed && h->core.final)      /* the truncated plants' hidden state beside their terminal stacks: the h' of this step, in the rows the post kernel handed out */
+      npb_launch_policy_core_final(&h->core, h->ro.D.final_row + (size_t)h->ro.t * (size_t)h->n_plants, h->n_plants, (hipStream_t)stream);
     h->ro.t++;
   }
   if (h->er_on && h->autoreset)      /* the episodes that end on this step, recorded while everything still describes them; then their summary rows cleared */
@@ -1322,6 +1342,7 @@ static int restore_from(NpbHandle *h, bool bank, const uint8_t *mask, hipStream_
                 maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, side, stream);
   if (!bank) clear_episodes(h, mask, false, stream);     /* the restored episodes are not from the bank */
   restart_streams(h, bank, stream);
+  core_restart(h, mask, stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -2318,25 +2339,68 @@ int64_t npb_policy_count(const npb_policy_desc_t *D, int features_cells, int n_a
   npb_policy_layout(D, features_cells, n_axes, &P);
   return (int64_t)P.theta_count;
 }
-int npb_set_policy(NpbHandle *h, const npb_policy_desc_t *desc) {
+static void policy_drop(NpbHandle *h) {
+  ppo_drop(h);
+  attachment_drop(&h->core, h->core.primed);
+  attachment_drop(&h->pol, h->pol.theta);
+  h->pol_t = 0;
+}
+static int set_policy(NpbHandle *h, const npb_policy_desc_t *desc, const npb_policy_core_t *core);
+int npb_set_policy(NpbHandle *h, const npb_policy_desc_t *desc) { return set_policy(h, desc, nullptr); }
+int npb_set_policy_core(NpbHandle *h, const npb_policy_desc_t *desc, const npb_policy_core_t *core) { return set_policy(h, desc, desc ? core : nullptr); }
+const char *npb_policy_core_check(const npb_policy_core_t *C, int n_plants, int features_cells) {
+  if (!C) return nullptr;
+  if (n_plants < 1) return "npb_set_policy_core: n_plants must be >= 1";
+  if (features_cells < 1 || features_cells > NPB_FEATURES_CELLS_MAX) return "npb_set_policy_core: the features' stack must have 1 .. NPB_FEATURES_CELLS_MAX (256) cells";
+  if (C->width < 1 || C->width > NPB_POLICY_WIDTH_MAX) return "npb_set_policy_core: the core must be 1 .. NPB_POLICY_WIDTH_MAX (128) wide";
+  if (C->gates != NPB_POLICY_GATES_SOFT && C->gates != NPB_POLICY_GATES_HARD) return "npb_set_policy_core: unknown gates";
+  if (!C->hidden) return "npb_set_policy_core: NULL hidden";
+  if (C->final_rows < 0) return "npb_set_policy_core: final_rows must be >= 0";
+  if ((C->final_rows > 0) != (C->final != nullptr)) return "npb_set_policy_core: final goes with final_rows > 0, and NULL with 0";
+  if ((int64_t)n_plants * C->final_rows > INT32_MAX) return "npb_set_policy_core: n_plants * final_rows is beyond what the rollout's final_row (int32) holds";
+  if (((uintptr_t)C->hidden | (uintptr_t)C->first | (uintptr_t)C->final) & 3u) return "npb_set_policy_core: misaligned hidden, first or final: 4-byte aligned";
+  return nullptr;
+}
+int64_t npb_policy_core_count(const npb_policy_desc_t *D, const npb_policy_core_t *C, int features_cells, int n_axes) {
+  if (!C) return npb_policy_count(D, features_cells, n_axes);
+  if (!D || npb_policy_check(D, 1, features_cells, n_axes) || C->width < 1 || C->width > NPB_POLICY_WIDTH_MAX) return 0;
+  npd_policy_core_t G = {};
+  npb_policy_core_layout(C->width, C->gates, features_cells, &G);
+  npb_policy_t P = {};
+  npb_policy_layout_at(D, features_cells, C->width, n_axes, G.theta_count, G.padded_count, &P);
+  return (int64_t)P.theta_count;
+}
+static int set_policy(NpbHandle *h, const npb_policy_desc_t *desc, const npb_policy_core_t *core) {
   if (!h) return NPB_EINVAL;
   if (desc && !h->feat.cols) return fail(h, NPB_EINVAL, "npb_set_policy: no features set (npb_set_features first): the policy reads their tensor");
   if (desc && !h->ctl.age) return fail(h, NPB_EINVAL, "npb_set_policy: no controls set (npb_set_controls first): the policy writes their input");
   if (const char *why = npb_policy_check(desc, h->n_plants, h->feat.n_cols * h->feat.stack, h->ctl.n_axes)) return fail(h, NPB_EINVAL, why);
   if (desc && desc->extras_in && (!h->ro.n_final || desc->extras_in != h->ro.D.extras_in || desc->n_extras != h->ro.D.n_extras))
     return fail(h, NPB_EINVAL, "npb_set_policy: extras_in and its count must be the set rollout's (npb_set_rollout first)");
+  if (const char *why = npb_policy_core_check(core, h->n_plants, h->feat.n_cols * h->feat.stack)) return fail(h, NPB_EINVAL, why);
+  if (core && core->final && (!h->ro.n_final || core->final_rows != h->ro.D.final_rows))
+    return fail(h, NPB_EINVAL, "npb_set_policy_core: final and final_rows go with the set rollout's final_obs and final_rows (npb_set_rollout first)");
   NPB_USE_DEVICE(h);
-  if (!desc) { ppo_drop(h); attachment_drop(&h->pol, h->pol.theta); h->pol_t = 0; return NPB_OK; }
+  if (!desc) { policy_drop(h); return NPB_OK; }
   npb_policy_t P = {};
-  npb_policy_layout(desc, h->feat.n_cols * h->feat.stack, h->ctl.n_axes, &P);
+  npd_policy_core_t G = {};
+  if (core) {
+    npb_policy_core_layout(core->width, core->gates, h->feat.n_cols * h->feat.stack, &G);
+    G.hidden = core->hidden; G.first = core->first; G.final = core->final; G.final_rows = core->final_rows;
+  }
+  npb_policy_layout_at(desc, h->feat.n_cols * h->feat.stack, core ? core->width : h->feat.n_cols * h->feat.stack, h->ctl.n_axes, G.theta_count, G.padded_count, &P);
   /* the allocation: theta [theta_count, padded to 4 floats] | the kernel's copy of the weights [padded_count]; all zero */
   const size_t theta_floats = ((size_t)P.theta_count + 3) & ~(size_t)3, bytes = (theta_floats + P.padded_count) * sizeof(float);
   char *dev = nullptr;
   if (int rc = attachment_alloc(h, "npb_set_policy", "the parameters", nullptr, 0, bytes, &dev)) return rc;
   P.theta = (float *)dev; P.padded = P.theta + theta_floats;
-  ppo_drop(h);
-  attachment_drop(&h->pol, h->pol.theta);
-  h->pol = P; h->pol_t = 0;
+  if (core) {      /* the restart words: primed [n] | seen [n], all zero: every plant unprimed */
+    char *words = nullptr;
+    if (int rc = attachment_alloc(h, "npb_set_policy_core", "the restart words", nullptr, 0, 2 * (size_t)h->n_plants * sizeof(int32_t), &words)) { (void)hipFree(dev); return rc; }
+    G.primed = (int32_t *)words; G.seen = G.primed + h->n_plants;
+  }
+  policy_drop(h);
+  h->pol = P; h->core = G;
   return NPB_OK;
 }
 int npb_policy_load(NpbHandle *h, const float *theta, int theta_is_device, void *stream) {
@@ -2348,12 +2412,14 @@ int npb_policy_load(NpbHandle *h, const float *theta, int theta_is_device, void 
                             (hipStream_t)stream));
   if (!theta_is_device) NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));      /* the host array may go */
   npb_launch_policy_repack(&h->pol, (hipStream_t)stream);
+  if (h->core.primed) npb_launch_policy_core_repack(&h->pol, &h->core, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
 int npb_policy_values(NpbHandle *h, const void *rows, int type, int n_rows, float *out, void *stream) {
   if (!h) return NPB_EINVAL;
   if (!h->pol.theta) return fail_who(h, "npb_policy_values", g_no_policy);
+  if (h->core.primed) return fail_who(h, "npb_policy_values", ": the policy has a core, and its critic reads a hidden state beside the rows: npb_policy_values_hidden");
   if (!rows) { rows = h->feat.out; type = h->feat.out_f64 ? NPB_FEATURES_F64 : NPB_FEATURES_F32; n_rows = h->n_plants; }
   if (type != NPB_FEATURES_F32 && type != NPB_FEATURES_F64) return fail(h, NPB_EINVAL, "npb_policy_values: an unknown type");
   if (n_rows < 1) return fail(h, NPB_EINVAL, "npb_policy_values: n_rows must be >= 1");
@@ -2365,6 +2431,42 @@ int npb_policy_values(NpbHandle *h, const void *rows, int type, int n_rows, floa
   npb_launch_policy(&h->pol, &R, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
+}
+static const char *const g_no_core = ": the policy has no core (npb_set_policy_core)";
+int npb_policy_values_hidden(NpbHandle *h, const void *rows, int type, int n_rows, const float *hidden_rows, float *out, void *stream) {
+  if (!h) return NPB_EINVAL;
+  const char *who = "npb_policy_values_hidden";
+  if (!h->pol.theta) return fail_who(h, who, g_no_policy);
+  if (!h->core.primed) return fail_who(h, who, g_no_core);
+  const bool own = !rows;      /* the current features and the current hidden state, the restart rule applied */
+  if (own && hidden_rows) return fail_who(h, who, ": hidden_rows without rows: the current features go with the handle's own hidden state");
+  if (!own && !hidden_rows) return fail_who(h, who, ": rows of the caller's need hidden_rows, the state in front of each");
+  if (own) { rows = h->feat.out; type = h->feat.out_f64 ? NPB_FEATURES_F64 : NPB_FEATURES_F32; n_rows = h->n_plants; }
+  if (type != NPB_FEATURES_F32 && type != NPB_FEATURES_F64) return fail_who(h, who, ": an unknown type");
+  if (n_rows < 1) return fail_who(h, who, ": n_rows must be >= 1");
+  if (!out || ((uintptr_t)out & 3u) || ((uintptr_t)hidden_rows & 3u) || ((uintptr_t)rows & (type == NPB_FEATURES_F64 ? 7u : 3u)))
+    return fail_who(h, who, ": a NULL or misaligned out, misaligned hidden_rows (4-byte aligned), or rows misaligned for their type");
+  NPB_USE_DEVICE(h);
+  npd_policy_run_t R = {};
+  R.x = rows; R.x_f64 = type == NPB_FEATURES_F64; R.rows = n_rows; R.value = out;
+  npd_policy_core_run_t cell = {};
+  cell.h = own ? h->core.hidden : hidden_rows;
+  if (own) { cell.primed = h->core.primed; cell.seen = h->core.seen; cell.index = h->ep_index; }
+  npb_launch_policy_core(&h->pol, &h->core, &R, &cell, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+/* hidden (the caller's tensor, which the cell carries from step to step), seen, primed */
+static StateParts policy_core_state_parts(const NpbHandle *h) {
+  const size_t n = (size_t)h->n_plants, words = n * sizeof(int32_t);
+  if (!h->pol.theta) return {nullptr, g_no_policy, "", 0, {}};
+  return {h->core.primed, g_no_core, "", 3, {{h->core.hidden, n * (size_t)h->core.H * sizeof(float), false}, {h->core.seen, words, false}, {h->core.primed, words, false}}};
+}
+int npb_policy_core_get_state(NpbHandle *h, float *hidden, int32_t *seen, int32_t *primed, void *stream) {
+  return state_copy(h, "npb_policy_core_get_state", policy_core_state_parts, {hidden, seen, primed}, false, stream);
+}
+int npb_policy_core_set_state(NpbHandle *h, const float *hidden, const int32_t *seen, const int32_t *primed, void *stream) {
+  return state_copy(h, "npb_policy_core_set_state", policy_core_state_parts, {hidden, seen, primed}, true, stream);
 }
 int npb_policy_noise(NpbHandle *h, uint64_t t, double *z, uint32_t *words, void *stream) {
   if (!h) return NPB_EINVAL;
@@ -2467,8 +2569,10 @@ static const char *adam_refusal(double lr, double b1, double b2, double eps) {
     return ": lr must be finite, b1 and b2 lie in [0, 1), eps be finite and >= 0";
   return nullptr;
 }
+static const char *const g_core_untrained = ": the policy has a core (npb_set_policy_core), and training through time is not built: train on whole-sequence minibatches outside, then npb_policy_load";
 static int ppo_grad(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, void *stream) {
   if (!h->pol.theta) return fail_who(h, who, g_no_policy);
+  if (h->core.primed) return fail_who(h, who, g_core_untrained);
   if (const char *why = npb_ppo_check(D, h->pol.cells, h->pol.n_axes)) return fail(h, NPB_EINVAL, why);
   if (const char *why = npb_ppo_more_check(M, D->count)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
@@ -2504,6 +2608,7 @@ int npb_policy_adam(NpbHandle *h, double lr, double b1, double b2, double eps, v
 }
 static int ppo_update(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, double lr, double b1, double b2, double eps, void *stream) {
   const int gated = M && M->kl_limit > 0.0;
+  if (h->core.primed) return fail_who(h, who, g_core_untrained);
   if (gated && !h->ppo.armed) return fail_who(h, who, ": kl_limit > 0 outside npb_policy_train_begin / npb_policy_train_end (npb_policy_train_begin first)");
   if (!gated && h->ppo.armed) return fail_who(h, who, ": kl_limit == 0 between npb_policy_train_begin and npb_policy_train_end: every update of the pair is gated");
   if (gated && h->pol.theta)      /* (a gated gradient counts itself applied: its Adam step must not be refused behind it) */
@@ -2522,6 +2627,7 @@ int npb_policy_update_more(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_
 int npb_policy_train_begin(NpbHandle *h, void *stream) {
   if (!h) return NPB_EINVAL;
   if (!h->pol.theta) return fail_who(h, "npb_policy_train_begin", g_no_policy);
+  if (h->core.primed) return fail_who(h, "npb_policy_train_begin", g_core_untrained);
   if (h->ppo.armed) return fail_who(h, "npb_policy_train_begin", g_train_open);
   NPB_USE_DEVICE(h);
   if (int rc = ppo_room(h, "npb_policy_train_begin", 0)) return rc;
@@ -2561,6 +2667,7 @@ int npb_policy_shard_sums(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_m
   if (!h) return NPB_EINVAL;
   const char *who = "npb_policy_shard_sums";
   if (!h->pol.theta) return fail_who(h, who, g_no_policy);
+  if (h->core.primed) return fail_who(h, who, g_core_untrained);
   if (const char *why = npb_ppo_check(D, h->pol.cells, h->pol.n_axes)) return fail(h, NPB_EINVAL, why);
   if (const char *why = npb_ppo_more_check(M, D->count)) return fail(h, NPB_EINVAL, why);
   if (M && M->kl_limit > 0.0) return fail_who(h, who, ": kl_limit > 0: the gate belongs to the combine (npb_policy_apply_shards)");
@@ -2575,6 +2682,7 @@ int npb_policy_shard_sums(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_m
 }
 static int ppo_combine(NpbHandle *h, const char *who, const npb_ppo_shards_t *S, void *stream) {
   if (!h->pol.theta) return fail_who(h, who, g_no_policy);
+  if (h->core.primed) return fail_who(h, who, g_core_untrained);
   if (const char *why = npb_ppo_shards_check(S, (int64_t)h->pol.theta_count, h->pol.n_axes)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
   if (int rc = ppo_room(h, who, 0)) return rc;
@@ -2591,6 +2699,7 @@ int npb_policy_apply_shards(NpbHandle *h, const npb_ppo_shards_t *S, double lr, 
   if (!h) return NPB_EINVAL;
   const char *who = "npb_policy_apply_shards";
   const int gated = S && S->kl_limit > 0.0;
+  if (h->core.primed) return fail_who(h, who, g_core_untrained);
   if (gated && !h->ppo.armed) return fail_who(h, who, ": kl_limit > 0 outside npb_policy_train_begin / npb_policy_train_end (npb_policy_train_begin first)");
   if (!gated && h->ppo.armed) return fail_who(h, who, ": kl_limit == 0 between npb_policy_train_begin and npb_policy_train_end: every update of the pair is gated");
   if (h->pol.theta)      /* (a gated combine counts itself applied: its Adam step must not be refused behind it) */

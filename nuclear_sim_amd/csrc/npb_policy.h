@@ -34,10 +34,34 @@ typedef struct {
 } npd_policy_run_t;
 /* the shapes of a descriptor laid out: every offset and count of *P but its pointers */
 void npb_policy_layout(const npb_policy_desc_t *D, int cells, int n_axes, npb_policy_t *P);
+void npb_policy_layout_at(const npb_policy_desc_t *D, int cells, int in0, int n_axes, uint32_t at, uint32_t wp, npb_policy_t *P);
 void npb_launch_policy_repack(const npb_policy_t *P, hipStream_t stream);
 void npb_launch_policy(const npb_policy_t *P, const npd_policy_run_t *R, hipStream_t stream);
 /* the z of draw t ([n][A] double) and, where words != NULL, the Philox words behind it ([n][(A + 1) / 2][4] uint32) */
 void npb_launch_policy_noise(const npb_policy_t *P, uint64_t t, int n_plants, double *z, uint32_t *words, hipStream_t stream);
+/* ---- the recurrent core (npb_set_policy_core; npb_policy_core.hip; nuclear_sim_amd/recurrent.py states it): a GRU cell of width H in front of
+ * both nets.  gate[0 .. 2]: the row blocks r, z, n of W_ih with their slices of b_ih (in = K * C, out = H); gate[3 .. 5]: those of W_hh and b_hh
+ * (in = H) -- six layers of npd_policy_layer, at the front of theta and of the kernel's copy.  hidden, first, final: the caller's tensors;
+ * primed, seen: the handle's bookkeeping, [n] each (base primed; NULL = no core) */
+typedef struct {
+  int H, gates, final_rows;
+  npd_policy_layer_t gate[6];
+  uint32_t theta_count, padded_count;      /* the core's own floats of theta and of the kernel's copy */
+  float *hidden, *first, *final;
+  int32_t *primed, *seen;
+} npd_policy_core_t;
+/* one launch of the recurrent kernel beside its npd_policy_run_t: h [rows][H] read; h_out: where h' goes (NULL: nowhere); first_out: where the
+ * h read goes, the restart rule applied (NULL: nowhere); primed, seen, index: the restart rule's words (primed NULL: no rule, h as it is; index
+ * NULL: nothing carried, a plant's index is the one seen); remember: prime the plants and remember their index */
+typedef struct {
+  const float *h; float *h_out, *first_out;
+  int32_t *primed, *seen; const int32_t *index; int remember;
+} npd_policy_core_run_t;
+void npb_policy_core_layout(int H, int gates, int cells, npd_policy_core_t *C);
+void npb_launch_policy_core_repack(const npb_policy_t *P, const npd_policy_core_t *C, hipStream_t stream);
+void npb_launch_policy_core(const npb_policy_t *P, const npd_policy_core_t *C, const npd_policy_run_t *R, const npd_policy_core_run_t *G, hipStream_t stream);
+/* behind the rollout's post kernel: hidden[p] into final[final_row[p]] for every plant that took a row of final_obs in this slot */
+void npb_launch_policy_core_final(const npd_policy_core_t *C, const int32_t *final_row, int n_plants, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif
@@ -92,6 +116,81 @@ __device__ __forceinline__ void npd_policy_layer(const npd_policy_layer_t &L, co
         out[j * NPD_POLICY_STRIDE + plant] = j < L.out ? y : 0.0f;
       }
     }
+  }
+}
+/* a whole net: xs -> the head's outputs in head[j][r]; a, b: the two hidden buffers */
+__device__ __forceinline__ void npd_policy_net(const npd_policy_net_t &N, const float *theta, const float *padded, const float *xs, float *a, float *b,
+                                               float *head, int activation, int wave, int lane) {
+  const float *in = xs;
+  for (int l = 0; l < N.n_layers; l++) {
+    const bool last = l == N.n_layers - 1;
+    float *out = last ? head : (l & 1) ? b : a;
+    npd_policy_layer(N.layer[l], theta, padded, in, out, last ? -1 : activation, wave, lane);
+    __syncthreads();
+    in = out;
+  }
+}
+/* ---- the noise: Philox4x32-10 and the pair of normals of one call (policy.py: philox4x32, noise_from_words) */
+__device__ __forceinline__ void npd_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t w[4]) {
+#pragma unroll
+  for (int round = 0; round < 10; round++) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0, hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+/* call j of plant `id` at draw t: z of axes 2j and 2j + 1 */
+__device__ __forceinline__ void npd_policy_pair(uint64_t seed, uint32_t id, uint64_t t, uint32_t j, uint32_t w[4], double *z0, double *z1) {
+  npd_philox4x32_10(id, (uint32_t)t, (uint32_t)(t >> 32), j, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+  const double u1 = (((double)w[0] * 1048576.0 + (double)(w[1] >> 12)) + 0.5) * 0x1p-52;
+  const double u2 = (((double)w[2] * 1048576.0 + (double)(w[3] >> 12)) + 0.5) * 0x1p-52;
+  const double r = sqrt(-2.0 * log(u1)), th = 6.283185307179586 * u2;
+  *z0 = r * cos(th);
+  *z1 = r * sin(th);
+}
+/* ---- the epilogue of a step's launch, what the MLP kernel (npb_policy.hip) and the recurrent one (npb_policy_core.hip) share: the draw,
+ * then every output.  A lane is (group g = 0 .. 7, plant r = 0 .. 31) of the tile at `base`; mean[a][r] and val[r] are the heads' floats in LDS
+ * (row stride NPD_POLICY_STRIDE), zs the draw's LDS, bad[r] != 0 a poisoned plant.  Every lane of the workgroup calls it (it holds a barrier). */
+__device__ __forceinline__ void npd_policy_epilogue(const npb_policy_t &P, const npd_policy_run_t &R, const float *mean, const float *val, double *zs,
+                                                    const int *bad, int g, int r, int in_tile, size_t base) {
+  const bool live = r < in_tile;
+  const size_t p = base + r;
+  const float qnan = __builtin_nanf("");
+  if (!R.act) {      /* npb_policy_values */
+    if (g == 0 && live) R.value[p] = bad[r] ? qnan : val[r];
+    return;
+  }
+  const int A = P.n_axes;
+  if (2 * g < A) {
+    double z0 = 0.0, z1 = 0.0;
+    if (!R.deterministic && live) {
+      uint32_t w[4];
+      npd_policy_pair(R.seed, R.first + (uint32_t)p, R.t, (uint32_t)g, w, &z0, &z1);
+    }
+    zs[(2 * g) * NPD_POLICY_TILE + r] = z0;
+    if (2 * g + 1 < NPB_CONTROLS_AXES_MAX) zs[(2 * g + 1) * NPD_POLICY_TILE + r] = z1;
+  }
+  __syncthreads();
+  if (!live) return;
+  const bool poisoned = bad[r] != 0;
+  if (g < A) {
+    const double scaled = (double)P.theta[P.std + g] * zs[g * NPD_POLICY_TILE + r];
+    const double a = (double)mean[g * NPD_POLICY_STRIDE + r] + scaled;
+    if (R.act_f64) ((double *)R.act)[p * A + g] = poisoned ? (double)qnan : a;
+    else ((float *)R.act)[p * A + g] = poisoned ? qnan : (float)a;
+  }
+  if (g == NPD_POLICY_GROUPS - 1) {
+    double lp = -((double)A * 0.9189385332046727);
+    for (int a = 0; a < A; a++) {
+      const double z = zs[a * NPD_POLICY_TILE + r], sq = z * z, half = 0.5 * sq;
+      lp = (lp - half) - (double)P.theta[P.log_std + a];
+    }
+    const float value = poisoned ? qnan : val[r], logp = poisoned ? qnan : (float)lp;
+    R.value[p] = value;
+    R.logp[p] = logp;
+    if (R.extras && R.value_slot >= 0) R.extras[p * R.n_extras + R.value_slot] = value;
+    if (R.extras && R.logp_slot >= 0) R.extras[p * R.n_extras + R.logp_slot] = logp;
   }
 }
 #endif

@@ -19,7 +19,8 @@
  *      outputs beyond the width, up to the next multiple of 4, are written +0.0: they are the next layer's k extension.  A barrier
  *      between layers; two hidden buffers, ping-pong; the actor first, then the critic, xs kept.  A layer narrower than 128 leaves
  *      waves without a chunk: they wait at the barrier.
- *   3. the epilogue, a lane being (group g = 0 .. 7, plant r = 0 .. 31): group j < ceil(A / 2) draws pair j of its plant (Philox4x32-10,
+ *   3. the epilogue (npd_policy_epilogue, npb_policy.h: the recurrent kernel of npb_policy_core.hip ends in the same one), a lane being
+ *      (group g = 0 .. 7, plant r = 0 .. 31): group j < ceil(A / 2) draws pair j of its plant (Philox4x32-10,
  *      Box-Muller in double; npd_policy_pair, the function npb_policy_noise runs) into LDS; then group a < A forms and stores action a,
  *      and group 7 the log-probability (ascending over the axes), value and logp, and the two extras slots.  A marked plant stores THE
  *      quiet NaN everywhere.
@@ -29,25 +30,7 @@
 #include <math.h>
 #include "npb_policy.h"
 
-/* ---- the noise: Philox4x32-10 and the pair of normals of one call (policy.py: philox4x32, noise_from_words) */
-__device__ __forceinline__ void npd_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t w[4]) {
-#pragma unroll
-  for (int round = 0; round < 10; round++) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0, hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
-/* call j of plant `id` at draw t: z of axes 2j and 2j + 1 */
-__device__ __forceinline__ void npd_policy_pair(uint64_t seed, uint32_t id, uint64_t t, uint32_t j, uint32_t w[4], double *z0, double *z1) {
-  npd_philox4x32_10(id, (uint32_t)t, (uint32_t)(t >> 32), j, (uint32_t)seed, (uint32_t)(seed >> 32), w);
-  const double u1 = (((double)w[0] * 1048576.0 + (double)(w[1] >> 12)) + 0.5) * 0x1p-52;
-  const double u2 = (((double)w[2] * 1048576.0 + (double)(w[3] >> 12)) + 0.5) * 0x1p-52;
-  const double r = sqrt(-2.0 * log(u1)), th = 6.283185307179586 * u2;
-  *z0 = r * cos(th);
-  *z1 = r * sin(th);
-}
+/* ---- the noise: Philox4x32-10 and the pair of normals of one call are npb_policy.h's (npd_policy_pair): the recurrent kernel draws with them too */
 __global__ __launch_bounds__(256) void npb_policy_noise_kernel(uint64_t seed, uint32_t first, uint64_t t, int n_plants, int n_axes, double *z, uint32_t *words) {
   const int J = (n_axes + 1) / 2;
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -86,19 +69,7 @@ __global__ __launch_bounds__(256) void npb_policy_repack_kernel(npb_policy_t P) 
 
 /* ---- the nets */
 /* (one layer on the matrix cores: npd_policy_layer, npb_policy.h -- the gradient kernel, npb_ppo.hip, runs the same routine) */
-/* a whole net: xs -> the head's outputs in head[j][r]; a, b: the two hidden buffers */
-__device__ __forceinline__ void npd_policy_net(const npd_policy_net_t &N, const float *theta, const float *padded, const float *xs, float *a, float *b,
-                                               float *head, int activation, int wave, int lane) {
-  const float *in = xs;
-  for (int l = 0; l < N.n_layers; l++) {
-    const bool last = l == N.n_layers - 1;
-    float *out = last ? head : (l & 1) ? b : a;
-    npd_policy_layer(N.layer[l], theta, padded, in, out, last ? -1 : activation, wave, lane);
-    __syncthreads();
-    in = out;
-  }
-}
-
+/* (a whole net, layer after layer: npd_policy_net, npb_policy.h) */
 template <typename IN, int KC_MAX, int H_MAX>
 __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_policy_kernel(npb_policy_t P, npd_policy_run_t R) {
   __shared__ float xs[KC_MAX * NPD_POLICY_STRIDE];
@@ -128,57 +99,21 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_policy_kernel(npb_policy
   const int wave = tid >> 6, lane = tid & 63;
   if (R.act) npd_policy_net(P.actor, P.theta, P.padded, xs, ha, hb, mean, P.D.activation, wave, lane);
   npd_policy_net(P.critic, P.theta, P.padded, xs, ha, hb, val, P.D.activation, wave, lane);
-  const bool live = r < in_tile;
-  const size_t p = base + r;
-  const float qnan = __builtin_nanf("");
-  if (!R.act) {      /* npb_policy_values */
-    if (g == 0 && live) R.value[p] = bad[r] ? qnan : val[r];
-    return;
-  }
   /* 3. the draw, then the outputs */
-  const int A = P.n_axes;
-  if (2 * g < A) {
-    double z0 = 0.0, z1 = 0.0;
-    if (!R.deterministic && live) {
-      uint32_t w[4];
-      npd_policy_pair(R.seed, R.first + (uint32_t)p, R.t, (uint32_t)g, w, &z0, &z1);
-    }
-    zs[(2 * g) * NPD_POLICY_TILE + r] = z0;
-    if (2 * g + 1 < NPB_CONTROLS_AXES_MAX) zs[(2 * g + 1) * NPD_POLICY_TILE + r] = z1;
-  }
-  __syncthreads();
-  if (!live) return;
-  const bool poisoned = bad[r] != 0;
-  if (g < A) {
-    const double scaled = (double)P.theta[P.std + g] * zs[g * NPD_POLICY_TILE + r];
-    const double a = (double)mean[g * NPD_POLICY_STRIDE + r] + scaled;
-    if (R.act_f64) ((double *)R.act)[p * A + g] = poisoned ? (double)qnan : a;
-    else ((float *)R.act)[p * A + g] = poisoned ? qnan : (float)a;
-  }
-  if (g == NPD_POLICY_GROUPS - 1) {
-    double lp = -((double)A * 0.9189385332046727);
-    for (int a = 0; a < A; a++) {
-      const double z = zs[a * NPD_POLICY_TILE + r], sq = z * z, half = 0.5 * sq;
-      lp = (lp - half) - (double)P.theta[P.log_std + a];
-    }
-    const float value = poisoned ? qnan : val[r], logp = poisoned ? qnan : (float)lp;
-    R.value[p] = value;
-    R.logp[p] = logp;
-    if (R.extras && R.value_slot >= 0) R.extras[p * R.n_extras + R.value_slot] = value;
-    if (R.extras && R.logp_slot >= 0) R.extras[p * R.n_extras + R.logp_slot] = logp;
-  }
+  npd_policy_epilogue(P, R, mean, val, zs, bad, g, r, in_tile, base);
 }
 
 /* ---- the launchers */
-extern "C" void npb_policy_layout(const npb_policy_desc_t *D, int cells, int n_axes, npb_policy_t *P) {
-  uint32_t at = 0, wp = 0;
+extern "C" void npb_policy_layout(const npb_policy_desc_t *D, int cells, int n_axes, npb_policy_t *P) { npb_policy_layout_at(D, cells, cells, n_axes, 0, 0, P); }
+/* the same with the nets reading `in0` cells (a core's width) and their parameters behind `at` floats of theta and `wp` of the kernel's copy (the core's) */
+extern "C" void npb_policy_layout_at(const npb_policy_desc_t *D, int cells, int in0, int n_axes, uint32_t at, uint32_t wp, npb_policy_t *P) {
   int widest = 0;
   for (int which = 0; which < 2; which++) {
     npd_policy_net_t &N = which ? P->critic : P->actor;
     const int hidden = which ? D->critic_layers : D->actor_layers;
     const int *width = which ? D->critic_width : D->actor_width;
     N.n_layers = hidden + 1;
-    int in = cells;
+    int in = in0;
     for (int l = 0; l <= hidden; l++) {
       npd_policy_layer_t &L = N.layer[l];
       L.in = in; L.in_pad = (in + 3) & ~3; L.out = l < hidden ? width[l] : which ? 1 : n_axes;

@@ -1,0 +1,197 @@
+/* npb_policy_core.hip -- the recurrent policy on the device (npb_set_policy_core, include/npb.h): a GRU cell of width H in front of the actor
+ * and the critic, its hidden state carried per plant, in the ONE launch in front of every step that npb_policy.hip's kernel is without a core.
+ * nuclear_sim_amd/recurrent.py states it in numpy; this file produces its bits (the float tanh of the soft gates apart, which the statement
+ * licenses): the six gate pre-activations are layers of npd_policy_layer -- bias, then fmaf(x[k], W[j][k], acc) for k ascending, on the f32
+ * matrix cores -- and the combines are plain float operations, each rounded on its own.  Built with the policy's flags (Makefile): no
+ * contraction, IEEE division and square root.
+ *
+ * One workgroup of 256 lanes (four waves) per tile of 32 plants, npb_policy.hip's geometry and LDS layout: every buffer [k][plant], row
+ * stride 33.
+ *   1. lanes 0 .. 31 read their plant's restart words: h starts at +0.0 where the plant is unprimed or its carried episode index is not the
+ *      one seen (npd_controls.h's rule); a step that acts primes the plant and remembers the index, the same lane storing what it read.
+ *      The tile's rows of x and of h are ONE contiguous run each (32 x K*C and 32 x H): consecutive lanes on consecutive elements, narrowed
+ *      and transposed into LDS (xs, hs); a restarted plant's column of hs is +0.0; on the rollout's slot 0 the run goes out again, as read,
+ *      into `first`.  The k extensions of xs and hs are +0.0.
+ *   2. gate by gate, so that only H-wide buffers live in LDS: gi = W_i* x into ha and gh = W_h* h into hb (two layers, one barrier: they
+ *      read xs and hs and write apart; gh's chunks of 32 outputs start two waves on, so a cell of up to 64 cells keeps all four waves
+ *      busy where a layer alone would leave two without a chunk), then 256 lanes over the H x 32 cells: r = S(gi + gh) into rs; z
+ *      likewise into zg; for the candidate n = T(gi + r * gh) and h' = n + z * (h - n) over hs in place (a cell is read and written by
+ *      one lane).  Cells from H up to the next multiple of 4 are +0.0: the next layer's k extension.  A poisoned plant's h' is +0.0.
+ *   3. h' goes back to the per-plant buffer as it came: the tile's run, consecutive lanes on consecutive elements, read out of hs
+ *      transposed (consecutive k are 33 floats apart: no bank conflict).
+ *   4. the actor and the critic over hs with ha and hb as their ping-pong buffers, and the epilogue: npb_policy.h's, the MLP kernel's own.
+ * npb_policy_values_hidden is the same kernel with act == NULL: the critic over GRU(x, h), nothing written back to h, primed or seen.
+ * LDS, from the declarations below: (KC_MAX + 5 H_MAX) x 33 x 4 B for xs, hs, ha, hb, rs, zg, and the epilogue's 1056 + 528 + 2048 + 128 B
+ * with 256 B of poison and restart words: the small build (64, 64) 54 576 B, the large one (256, 128) 122 160 B, as the compiler reports
+ * them -- static, beyond 64 KiB, inside gfx950's 160 KiB per CU (one workgroup a CU in the large build, three in the small one).  A 3H-wide
+ * gi and gh together would not fit.  64 VGPRs and 16 AGPRs, no scratch, no spills, no atomics. */
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include "npb_policy.h"
+
+#define NPD_CORE_SOFT 0
+#define NPD_CORE_HARD 1
+
+__device__ __forceinline__ float npd_core_sigma(float a, int gates) {
+  if (gates == NPD_CORE_HARD) {
+    const float q = 0.25f * a;
+    const float y = q + 0.5f;
+    return y < 0.0f ? 0.0f : (y > 1.0f ? 1.0f : y);
+  }
+  const float half = 0.5f * a;
+  const float t = tanhf(half);
+  const float s = 0.5f * t;
+  return s + 0.5f;
+}
+__device__ __forceinline__ float npd_core_tau(float a, int gates) {
+  if (gates == NPD_CORE_HARD) return a < -1.0f ? -1.0f : (a > 1.0f ? 1.0f : a);
+  return tanhf(a);
+}
+
+/* the kernel's copy of the six gate layers, as npb_policy_repack_kernel lays out a net's */
+__global__ __launch_bounds__(256) void npb_policy_core_repack_kernel(npd_policy_core_t C, const float *__restrict__ theta, float *__restrict__ padded) {
+  const size_t first = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (int l = 0; l < 6; l++) {
+    const npd_policy_layer_t L = C.gate[l];
+    const size_t total = (size_t)L.in_pad * L.out_pad;
+    for (size_t i = first; i < total; i += stride) {
+      const size_t k = i / L.out_pad, j = i - k * L.out_pad;
+      padded[L.wp + i] = k < (size_t)L.in && j < (size_t)L.out ? theta[L.w + j * L.in + k] : 0.0f;
+    }
+  }
+}
+
+template <typename IN, int KC_MAX, int H_MAX>
+__global__ __launch_bounds__(NPD_POLICY_LANES) void npb_policy_core_kernel(npb_policy_t P, npd_policy_core_t C, npd_policy_run_t R, npd_policy_core_run_t G) {
+  __shared__ float xs[KC_MAX * NPD_POLICY_STRIDE];
+  __shared__ float hs[H_MAX * NPD_POLICY_STRIDE], ha[H_MAX * NPD_POLICY_STRIDE], hb[H_MAX * NPD_POLICY_STRIDE];
+  __shared__ float rs[H_MAX * NPD_POLICY_STRIDE], zg[H_MAX * NPD_POLICY_STRIDE];
+  __shared__ float mean[NPB_CONTROLS_AXES_MAX * NPD_POLICY_STRIDE], val[4 * NPD_POLICY_STRIDE];
+  __shared__ double zs[NPB_CONTROLS_AXES_MAX * NPD_POLICY_TILE];
+  __shared__ int bad[NPD_POLICY_TILE], fresh[NPD_POLICY_TILE];
+  const int tid = threadIdx.x, g = tid >> 5, r = tid & (NPD_POLICY_TILE - 1);
+  const size_t base = (size_t)blockIdx.x * NPD_POLICY_TILE, rows = (size_t)R.rows;
+  const int in_tile = rows - base < (size_t)NPD_POLICY_TILE ? (int)(rows - base) : NPD_POLICY_TILE;
+  const int KC = P.cells, KC_pad = (KC + 3) & ~3, H = C.H, H_pad = (H + 3) & ~3;
+  /* 1. the restart words; the tile's runs of x and h into LDS, narrowed and transposed; the k extensions +0.0 */
+  if (tid < NPD_POLICY_TILE) {
+    int restart = 0;
+    if (G.primed && tid < in_tile) {
+      const size_t p = base + tid;
+      const int32_t seen = G.seen[p], episode = G.index ? G.index[p] : seen;
+      restart = !(G.primed[p] != 0 && episode == seen);
+      if (G.remember) { G.primed[p] = 1; G.seen[p] = episode; }
+    }
+    bad[tid] = 0;
+    fresh[tid] = restart;
+  }
+  for (int i = tid; i < (KC_pad - KC) * NPD_POLICY_TILE; i += NPD_POLICY_LANES)
+    xs[(KC + i / NPD_POLICY_TILE) * NPD_POLICY_STRIDE + (i & (NPD_POLICY_TILE - 1))] = 0.0f;
+  for (int i = tid; i < (H_pad - H) * NPD_POLICY_TILE; i += NPD_POLICY_LANES)
+    hs[(H + i / NPD_POLICY_TILE) * NPD_POLICY_STRIDE + (i & (NPD_POLICY_TILE - 1))] = 0.0f;
+  __syncthreads();
+  const IN *run = (const IN *)R.x + base * (size_t)KC;
+  const int total = in_tile * KC;
+  for (int e = tid; e < total; e += NPD_POLICY_LANES) {
+    const int row = e / KC, k = e - row * KC;
+    const float v = (float)run[e];
+    xs[k * NPD_POLICY_STRIDE + row] = v;
+    if (!(v - v == 0.0f)) bad[row] = 1;
+  }
+  const int h_total = in_tile * H;
+  const float *h_run = G.h + base * (size_t)H;
+  for (int e = tid; e < h_total; e += NPD_POLICY_LANES) {
+    const int row = e / H, k = e - row * H;
+    const float v = fresh[row] ? 0.0f : h_run[e];
+    hs[k * NPD_POLICY_STRIDE + row] = v;
+    if (G.first_out) G.first_out[base * (size_t)H + e] = v;
+  }
+  __syncthreads();
+  /* 2. the cell, gate by gate */
+  const int wave = tid >> 6, lane = tid & 63;
+  for (int gate = 0; gate < 3; gate++) {
+    npd_policy_layer(C.gate[gate], P.theta, P.padded, xs, ha, -1, wave, lane);
+    npd_policy_layer(C.gate[3 + gate], P.theta, P.padded, hs, hb, -1, (wave + 2) & (NPD_POLICY_WAVES - 1), lane);
+    __syncthreads();
+    for (int i = tid; i < H_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES) {
+      const int j = i / NPD_POLICY_TILE, plant = i & (NPD_POLICY_TILE - 1), o = j * NPD_POLICY_STRIDE + plant;
+      if (gate < 2) {
+        const float a = ha[o] + hb[o];
+        (gate ? zg : rs)[o] = npd_core_sigma(a, C.gates);
+      } else {
+        const float gated = rs[o] * hb[o];
+        const float a = ha[o] + gated;
+        const float n = npd_core_tau(a, C.gates);
+        const float h = hs[o];
+        const float away = h - n;
+        const float kept = zg[o] * away;
+        const float next = n + kept;
+        hs[o] = j < H && !bad[plant] ? next : 0.0f;
+      }
+    }
+    __syncthreads();
+  }
+  /* 3. h' back to the per-plant buffer */
+  if (G.h_out)
+    for (int e = tid; e < h_total; e += NPD_POLICY_LANES) {
+      const int row = e / H, k = e - row * H;
+      G.h_out[base * (size_t)H + e] = hs[k * NPD_POLICY_STRIDE + row];
+    }
+  /* 4. the nets over h', the draw and the outputs */
+  if (R.act) npd_policy_net(P.actor, P.theta, P.padded, hs, ha, hb, mean, P.D.activation, wave, lane);
+  npd_policy_net(P.critic, P.theta, P.padded, hs, ha, hb, val, P.D.activation, wave, lane);
+  npd_policy_epilogue(P, R, mean, val, zs, bad, g, r, in_tile, base);
+}
+
+/* behind the rollout's post kernel: one wave per 64 plants, one lane per plant reads the row its plant took in this slot (-1: none); then the
+ * wave copies those plants' H cells, one plant after the other, consecutive lanes on consecutive cells */
+__global__ __launch_bounds__(64) void npb_policy_core_final_kernel(const float *__restrict__ hidden, float *__restrict__ final, const int32_t *__restrict__ final_row,
+                                                                   int n_plants, int H, int64_t n_rows) {
+  const size_t block_base = (size_t)blockIdx.x * 64;
+  const int lane = threadIdx.x;
+  const size_t p = block_base + lane;
+  int32_t row = -1;
+  if (p < (size_t)n_plants) row = final_row[p];
+  if (row >= n_rows) row = -1;
+  for (uint64_t left = __ballot(row >= 0); left; left &= left - 1) {
+    const int r = __ffsll((unsigned long long)left) - 1;
+    const float *src = hidden + (block_base + (size_t)r) * (size_t)H;
+    float *dst = final + (size_t)__shfl(row, r) * (size_t)H;
+    for (int i = lane; i < H; i += 64) dst[i] = src[i];
+  }
+}
+
+/* ---- the launchers */
+extern "C" void npb_policy_core_layout(int H, int gates, int cells, npd_policy_core_t *C) {
+  uint32_t at = 0, wp = 0;
+  C->H = H; C->gates = gates;
+  for (int block = 0; block < 2; block++) {      /* W_ih | b_ih, then W_hh | b_hh: three row blocks of H each, r, z, n */
+    const int in = block ? H : cells;
+    const uint32_t w = at, b = at + 3u * (uint32_t)H * (uint32_t)in;
+    at = b + 3u * (uint32_t)H;
+    for (int gate = 0; gate < 3; gate++) {
+      npd_policy_layer_t &L = C->gate[3 * block + gate];
+      L.in = in; L.in_pad = (in + 3) & ~3; L.out = H; L.out_pad = (H + 31) & ~31;
+      L.w = w + (uint32_t)gate * (uint32_t)H * (uint32_t)in;
+      L.b = b + (uint32_t)gate * (uint32_t)H;
+      L.wp = wp; wp += (uint32_t)L.in_pad * L.out_pad;
+    }
+  }
+  C->theta_count = at; C->padded_count = wp;
+}
+extern "C" void npb_launch_policy_core_repack(const npb_policy_t *P, const npd_policy_core_t *C, hipStream_t stream) {
+  const unsigned blocks = (C->padded_count + 255u) / 256u;
+  hipLaunchKernelGGL(npb_policy_core_repack_kernel, dim3(blocks < 64u ? blocks : 64u), dim3(256), 0, stream, *C, P->theta, P->padded);
+}
+extern "C" void npb_launch_policy_core(const npb_policy_t *P, const npd_policy_core_t *C, const npd_policy_run_t *R, const npd_policy_core_run_t *G, hipStream_t stream) {
+  const dim3 grid((unsigned)((R->rows + NPD_POLICY_TILE - 1) / NPD_POLICY_TILE)), block(NPD_POLICY_LANES);
+  const bool small = P->cells <= 64 && P->width_max <= 64 && C->H <= 64;
+#define NPD_CORE_LAUNCH(IN, KC_MAX, H_MAX) hipLaunchKernelGGL((npb_policy_core_kernel<IN, KC_MAX, H_MAX>), grid, block, 0, stream, *P, *C, *R, *G)
+  if (R->x_f64) { if (small) NPD_CORE_LAUNCH(double, 64, 64); else NPD_CORE_LAUNCH(double, NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX); }
+  else { if (small) NPD_CORE_LAUNCH(float, 64, 64); else NPD_CORE_LAUNCH(float, NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX); }
+#undef NPD_CORE_LAUNCH
+}
+extern "C" void npb_launch_policy_core_final(const npd_policy_core_t *C, const int32_t *final_row, int n_plants, hipStream_t stream) {
+  hipLaunchKernelGGL(npb_policy_core_final_kernel, dim3((unsigned)((n_plants + 63) / 64)), dim3(64), 0, stream, C->hidden, C->final, final_row, n_plants, C->H,
+                     (int64_t)n_plants * C->final_rows);
+}

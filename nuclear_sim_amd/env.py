@@ -19,7 +19,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, normalizer, policy, recordlog, rollout
+from . import _lib, normalizer, policy, recordlog, recurrent, rollout
 from .schema import SCHEMA
 
 
@@ -1965,18 +1965,36 @@ class BatchedPlantEnv:
                 raise ValueError("a layer of the %s is W[out][in] with b[out]" % who)
         return pairs
 
-    def _policy_theta(self, actor, critic, log_std):
-        """``(theta, actor widths, critic widths)``: theta a float32 device tensor in the statement's order, std = exp(log_std) formed here"""
+    @staticmethod
+    def _policy_core(core):
+        """a core as ``(W_ih, b_ih, W_hh, b_hh)`` tensors, theta's order: a ``torch.nn.GRUCell``'s parameters, or the caller's
+        ``(W_ih, W_hh, b_ih, b_hh)`` (GRUCell's own order)"""
+        if isinstance(core, torch.nn.GRUCell):
+            if not core.bias:
+                raise ValueError("the core's GRUCell has no bias")
+            core = (core.weight_ih, core.weight_hh, core.bias_ih, core.bias_hh)
+        if not isinstance(core, (tuple, list)) or len(core) != 4:
+            raise ValueError("core is a torch.nn.GRUCell or (W_ih, W_hh, b_ih, b_hh)")
+        W_ih, W_hh, b_ih, b_hh = (torch.as_tensor(v) for v in core)
+        H = W_hh.shape[-1]
+        if W_ih.dim() != 2 or W_ih.shape[0] != 3 * H or tuple(W_hh.shape) != (3 * H, H) or tuple(b_ih.shape) != (3 * H,) or tuple(b_hh.shape) != (3 * H,):
+            raise ValueError("a core is W_ih[3H][cells], W_hh[3H][H], b_ih[3H], b_hh[3H]")
+        return W_ih, b_ih, W_hh, b_hh
+
+    def _policy_theta(self, actor, critic, log_std, core=None):
+        """``(theta, actor widths, critic widths)``: theta a float32 device tensor in the statement's order, std = exp(log_std) formed here;
+        ``core``: its four tensors come first (``recurrent.pack``)"""
         a, c = self._policy_layers(actor, "actor"), self._policy_layers(critic, "critic")
+        g = [] if core is None else list(self._policy_core(core))
         with torch.no_grad():
             ls = torch.as_tensor(log_std).detach().to(device=self.device, dtype=torch.float32).reshape(-1)
-            flat = [x.detach().to(device=self.device, dtype=torch.float32).reshape(-1) for W, b in a + c for x in (W, b)]
+            flat = [x.detach().to(device=self.device, dtype=torch.float32).reshape(-1) for x in g + [x for W, b in a + c for x in (W, b)]]
             theta = torch.cat(flat + [ls, torch.exp(ls)]).contiguous()
         shapes = tuple([tuple(W.shape) for W, _ in net] for net in (a, c))
         return theta, shapes, int(ls.numel())
 
     def set_policy(self, actor, critic=None, log_std=None, activation: str = "tanh", seed: int = 0, deterministic: bool = False, extras=None,
-                   first_plant: int = 0) -> None:
+                   first_plant: int = 0, core=None, gates: str = "soft") -> None:
         """Run the policy on the device (npb_set_policy): in front of every ``step()`` ONE launch reads every plant's features stack,
         runs a diagonal-Gaussian actor and a critic -- two MLPs of 1 to 3 hidden layers, up to 128 wide, ``"relu"`` or ``"tanh"`` -- draws
         the noise, and writes the action into ``controls_input()``, and value and log-probability into tensors the env keeps
@@ -1988,7 +2006,14 @@ class BatchedPlantEnv:
         ``(first_plant + p, t, j)``): shards of one batch draw what the whole batch would.  ``deterministic``: the mean, no draw.
         While a policy is set ``set_features``, ``set_controls`` and ``set_rollout`` are refused, and so is ``step(controls=...)``.
         ``nuclear_sim_amd.policy`` is the same in numpy: bit for bit with relu, within the float tanh's error with tanh.
-        ``logp`` is the density of the unrounded action.  ``set_policy(None)`` turns it off."""
+        ``logp`` is the density of the unrounded action.  ``set_policy(None)`` turns it off.
+        ``core``: a ``torch.nn.GRUCell`` or ``(W_ih, W_hh, b_ih, b_hh)`` -- a recurrent policy (npb_set_policy_core): the cell reads the
+        features, both nets read its new hidden state (their first layers take the cell's width), and the state is carried per plant in
+        ``policy_hidden()`` and restarts with the plant's episode -- the autoreset's restarts, ``reset``, ``restore`` and
+        ``restore_from_bank``.  ``gates``: ``"soft"`` (GRUCell's sigmoid and tanh) or ``"hard"`` (piecewise linear, bit-exact).  With a
+        rollout set, ``policy_rollout_hidden()`` has the state in front of slot 0 and the states beside ``final_obs``.
+        ``nuclear_sim_amd.recurrent`` is the same in numpy.  Training a recurrent policy on the device is not built: train on
+        ``rollout_minibatches(unit="plant")`` in torch and put the parameters back with ``policy_load``."""
         if actor is None:
             if self._pol is not None:
                 _lib.check(self.L.npb_set_policy(self._h, None), self._h)
@@ -1999,13 +2024,22 @@ class BatchedPlantEnv:
             raise _lib.NpbError("libnpb.so has no npb_set_policy: rebuild")
         if critic is None or log_std is None:
             raise ValueError("set_policy takes an actor, a critic and log_std")
-        theta, (ashape, cshape), n_ls = self._policy_theta(actor, critic, log_std)
+        theta, (ashape, cshape), n_ls = self._policy_theta(actor, critic, log_std, core)
         n, (_, K, C), A = self.n, ft["out"].shape, ct["in"].shape[1]
         hidden = tuple(tuple(o for o, _ in shape[:-1]) for shape in (ashape, cshape))
-        policy.check(K * C, A, hidden[0], hidden[1], activation)
-        want = policy.sizes(K * C, A, hidden[0], hidden[1])
+        H = None if core is None else int(self._policy_core(core)[2].shape[-1])
+        if core is None:
+            policy.check(K * C, A, hidden[0], hidden[1], activation)
+        else:
+            if not hasattr(self.L, "npb_set_policy_core"):
+                raise _lib.NpbError("libnpb.so has no npb_set_policy_core: rebuild")
+            recurrent.check(K * C, A, hidden[0], hidden[1], activation, H, gates)
+            if self._policy_core(core)[0].shape[1] != K * C:
+                raise ValueError("the core does not fit: W_ih reads %d cells, not %d" % (K * C, self._policy_core(core)[0].shape[1]))
+        reads = K * C if core is None else H
+        want = policy.sizes(reads, A, hidden[0], hidden[1])
         if [(i, o) for o, i in ashape] != want[0] or [(i, o) for o, i in cshape] != want[1] or n_ls != A:
-            raise ValueError("the nets do not fit: both read %d cells, the actor's head and log_std have %d entries, the critic's head one" % (K * C, A))
+            raise ValueError("the nets do not fit: both read %d cells, the actor's head and log_std have %d entries, the critic's head one" % (reads, A))
         slots = {"value": -1, "logp": -1}
         if extras is not None:
             ro = self._on("_roll")
@@ -2027,28 +2061,46 @@ class BatchedPlantEnv:
         d.value_slot, d.logp_slot = slots["value"], slots["logp"]
         if extras is not None and (slots["value"] >= 0 or slots["logp"] >= 0):
             d.extras_in, d.n_extras = self._roll["extras_in"].data_ptr(), self._roll["spec"]["extras"]
-        _lib.check(self.L.npb_set_policy(self._h, ctypes.byref(d)), self._h)      # (refused: what was set before stays)
+        cell = {}
+        if core is None:
+            _lib.check(self.L.npb_set_policy(self._h, ctypes.byref(d)), self._h)      # (refused: what was set before stays)
+        else:
+            R = 0 if self._roll is None else self._roll["spec"]["final_rows"]
+            with torch.cuda.device(self.device):
+                cell = {"hidden": torch.zeros((n, H), dtype=torch.float32, device=self.device),
+                        "first": None if self._roll is None else torch.zeros((n, H), dtype=torch.float32, device=self.device),
+                        "final": torch.zeros((n * R, H), dtype=torch.float32, device=self.device) if R else None,
+                        "state": (("hidden", np.float32, (n, H)), ("seen", np.int32, (n,)), ("primed", np.int32, (n,)))}
+            g = _lib.NpbPolicyCore()
+            g.width, g.gates, g.hidden, g.final_rows = H, _lib.POLICY_GATES[gates], cell["hidden"].data_ptr(), R
+            g.first = None if cell["first"] is None else cell["first"].data_ptr()
+            g.final = None if cell["final"] is None else cell["final"].data_ptr()
+            _lib.check(self.L.npb_set_policy_core(self._h, ctypes.byref(d), ctypes.byref(g)), self._h)
         self._pol = {"value": value, "logp": logp, "theta": None,
                      "spec": {"cells": K * C, "n_axes": A, "actor": hidden[0], "critic": hidden[1], "activation": activation,
                               "seed": int(seed) & (2 ** 64 - 1), "deterministic": bool(deterministic), "first_plant": int(first_plant),
-                              "act_dtype": str(ct["in"].dtype).split(".")[1], "extras": dict(slots)}}
+                              "act_dtype": str(ct["in"].dtype).split(".")[1], "extras": dict(slots), "core": H, "gates": gates if core is not None else None}}
+        self._pol.update(cell)
         self._policy_upload(theta)
 
     def _policy_upload(self, theta) -> None:
         pol = self._on("_pol")
         S = pol["spec"]
-        if theta.numel() != policy.theta_size(S["cells"], S["n_axes"], S["actor"], S["critic"]):
-            raise ValueError("theta has %d elements, the set policy takes %d" % (theta.numel(), policy.theta_size(S["cells"], S["n_axes"], S["actor"], S["critic"])))
+        takes = recurrent.theta_size(S["cells"], S["n_axes"], S["actor"], S["critic"], S["core"])
+        if theta.numel() != takes:
+            raise ValueError("theta has %d elements, the set policy takes %d" % (theta.numel(), takes))
         _lib.check(self.L.npb_policy_load(self._h, ctypes.c_void_p(theta.data_ptr()), 1, self._stream()), self._h)
         pol["theta"], pol["moved"] = theta, False      # (alive while the launch reads it)
 
     def policy_load(self, theta_or_modules) -> None:
         """New parameters into the set policy (npb_policy_load), once per optimiser iteration: a flat float32 ``theta`` in the
-        statement's order (``policy.pack``), device or host, or ``(actor, critic, log_std)`` as ``set_policy`` takes them.  No
-        reallocation, nothing read back; the shapes stay."""
-        self._on("_pol")
-        if isinstance(theta_or_modules, (tuple, list)) and len(theta_or_modules) == 3 and not isinstance(theta_or_modules[0], (int, float)):
-            theta, _, _ = self._policy_theta(*theta_or_modules)
+        statement's order (``policy.pack``), device or host, or ``(actor, critic, log_std)`` as ``set_policy`` takes them -- with a
+        core the longer ``theta`` of ``recurrent.pack``, or ``(core, actor, critic, log_std)``.  No reallocation, nothing read back; the
+        shapes stay."""
+        has_core = self._on("_pol")["spec"]["core"] is not None
+        if isinstance(theta_or_modules, (tuple, list)) and len(theta_or_modules) == 3 + has_core and not isinstance(theta_or_modules[0], (int, float)):
+            parts = tuple(theta_or_modules)
+            theta, _, _ = self._policy_theta(*parts[has_core:], core=parts[0] if has_core else None)
         else:
             theta = torch.as_tensor(theta_or_modules).detach().to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
         self._policy_upload(theta)
@@ -2383,10 +2435,44 @@ class BatchedPlantEnv:
             raise ValueError("m and v have theta's %d elements" % pol["theta"].numel())
         _lib.check(self.L.npb_policy_optimizer_set_state(self._h, m.ctypes.data, v.ctypes.data, int(state["step"]), self._stream()), self._h)
 
-    def policy_values(self, x=None) -> torch.Tensor:
-        """The critic alone (npb_policy_values): float32 [rows] of ``x``, a float32 or float64 device tensor [rows, K, C] (or [rows, K * C]);
-        None: the current features -- the ``last_value`` of ``rollout_advantages``; the rollout's ``final_obs`` gives its ``final_values``."""
+    def _policy_cell(self, what) -> dict:
         pol = self._on("_pol")
+        if pol["spec"]["core"] is None:
+            raise _lib.NpbError("%s: the policy has no core (set_policy(core=...))" % what)
+        return pol
+
+    def policy_hidden(self) -> torch.Tensor:
+        """The recurrent policy's live hidden state, float32 [n, H], the same storage on every call: what the cell made of the features in
+        front of the last step.  A restarted plant's row is read as zeros by the next step; the row itself stays until then."""
+        return self._policy_cell("policy_hidden()")["hidden"]
+
+    def policy_rollout_hidden(self) -> Dict[str, torch.Tensor]:
+        """What a recurrent policy records beside a rollout: ``first`` float32 [n, H], the state the policy read in front of slot 0 (the
+        restart rule applied), from which ``recurrent.replay`` forms the state in front of every slot; ``final`` float32
+        [n * final_rows, H], the states beside ``final_obs``: ``policy_values(final_obs, hidden=final)`` are the ``final_values``."""
+        pol = self._policy_cell("policy_rollout_hidden()")
+        self._on("_roll")
+        if pol["first"] is None:
+            raise _lib.NpbError("policy_rollout_hidden(): the policy was set without a rollout (set_rollout, then set_policy)")
+        H = pol["spec"]["core"]
+        with torch.cuda.device(self.device):
+            final = pol["final"] if pol["final"] is not None else torch.zeros((0, H), dtype=torch.float32, device=self.device)
+        return {"first": pol["first"], "final": final}
+
+    def policy_values(self, x=None, hidden=None) -> torch.Tensor:
+        """The critic alone (npb_policy_values): float32 [rows] of ``x``, a float32 or float64 device tensor [rows, K, C] (or [rows, K * C]);
+        None: the current features -- the ``last_value`` of ``rollout_advantages``; the rollout's ``final_obs`` gives its ``final_values``.
+        With a core (npb_policy_values_hidden) the critic reads GRU(x, hidden): ``hidden`` float32 [rows, H], the states in front of the
+        rows, is required with rows of the caller's; with ``x=None`` the live hidden state is used under the restart rule."""
+        pol = self._on("_pol")
+        H = pol["spec"]["core"]
+        if hidden is not None:
+            self._policy_cell("policy_values(hidden=...)")
+            if x is None:
+                raise ValueError("policy_values(hidden=...) goes with rows x; x=None reads the live hidden state")
+        elif H is not None and x is not None:
+            raise ValueError("policy_values(x) of a recurrent policy needs hidden=, the states in front of the rows")
+        own = x is None
         if x is None:
             x = self.features()
         x = torch.as_tensor(x)
@@ -2398,9 +2484,20 @@ class BatchedPlantEnv:
             raise ValueError("policy_values takes rows of %d cells, not %r" % (pol["spec"]["cells"], tuple(x.shape)))
         with torch.cuda.device(self.device):
             out = torch.zeros((rows,), dtype=torch.float32, device=self.device)
+        ftype = _lib.FEATURE_DTYPES["float64" if x.dtype == torch.float64 else "float32"]
+        if H is not None:
+            if not own:
+                hidden = torch.as_tensor(hidden).to(device=self.device, dtype=torch.float32).contiguous()
+                if tuple(hidden.shape) != (rows, H):
+                    raise ValueError("hidden is [%d, %d], one state in front of every row, not %r" % (rows, H, tuple(hidden.shape)))
+            if rows:
+                _lib.check(self.L.npb_policy_values_hidden(self._h, None if own else ctypes.c_void_p(x.data_ptr()), ftype, rows,
+                                                           None if own else ctypes.c_void_p(hidden.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                                           self._stream()), self._h)
+            pol["held"] = (x, hidden)
+            return out
         if rows:
-            _lib.check(self.L.npb_policy_values(self._h, ctypes.c_void_p(x.data_ptr()), _lib.FEATURE_DTYPES["float64" if x.dtype == torch.float64 else "float32"],
-                                                rows, ctypes.c_void_p(out.data_ptr()), self._stream()), self._h)
+            _lib.check(self.L.npb_policy_values(self._h, ctypes.c_void_p(x.data_ptr()), ftype, rows, ctypes.c_void_p(out.data_ptr()), self._stream()), self._h)
         pol["held"] = x      # (alive while the launch reads it)
         return out
 
@@ -2415,19 +2512,26 @@ class BatchedPlantEnv:
         return (z, w.to(torch.int64) & 0xFFFFFFFF) if words else z
 
     def policy_state(self) -> Dict[str, np.ndarray]:
-        """The policy's own state for a checkpoint (npb_policy_get_state): ``t``, its draw counter"""
-        self._on("_pol")
+        """The policy's own state for a checkpoint (npb_policy_get_state): ``t``, its draw counter; with a core, and only then, also
+        ``hidden`` float32 [n, H], ``seen`` and ``primed`` int32 [n] (npb_policy_core_get_state)"""
+        pol = self._on("_pol")
         t = ctypes.c_uint64()
         _lib.check(self.L.npb_policy_get_state(self._h, ctypes.byref(t)), self._h)
-        return {"t": np.uint64(t.value)}
+        out = {"t": np.uint64(t.value)}
+        if pol["spec"]["core"] is not None:
+            out.update(self._get_state("_pol", self.L.npb_policy_core_get_state))
+        return out
 
     def load_policy_state(self, state) -> None:
         """put back what ``policy_state()`` returned (npb_policy_set_state): the noise resumes at that draw"""
-        self._on("_pol")
+        pol = self._on("_pol")
         _lib.check(self.L.npb_policy_set_state(self._h, int(state["t"])), self._h)
+        if pol["spec"]["core"] is not None:
+            self._load_state("_pol", self.L.npb_policy_core_set_state, state)
 
     def policy_spec(self) -> dict:
-        """the request as data: what ``nuclear_sim_amd.policy.Policy`` takes"""
+        """the request as data: what ``nuclear_sim_amd.policy.Policy`` takes (``core``, the cell's width, and ``gates`` are None without
+        a core; with one, ``nuclear_sim_amd.recurrent.Policy`` takes them)"""
         return self._on("_pol")["spec"]
 
     def collect(self, steps: int) -> dict:
