@@ -1159,6 +1159,11 @@ static npd_policy_run_t policy_run(const NpbHandle *h) {
   R.seed = D.seed; R.t = h->pol_t; R.first = (uint32_t)D.first_plant; R.deterministic = D.deterministic;
   return R;
 }
+/* every launch of the handle's policy: the recurrent kernel with a core (`cell`: what of the hidden state it reads and writes), else the MLP's (cell NULL) */
+static void policy_launch(const NpbHandle *h, const npd_policy_run_t *R, const npd_policy_core_run_t *cell, void *stream) {
+  if (cell) npb_launch_policy_core(&h->pol, &h->core, R, cell, (hipStream_t)stream);
+  else npb_launch_policy(&h->pol, R, (hipStream_t)stream);
+}
 int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const double *power_setpoint,
              const double *noise_z, const double *cooling_water_temp, double *obs, double *reward, uint8_t *done,
              uint32_t *trip_flags, double *info, void *stream) {
@@ -1222,14 +1227,12 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
   }
   if (h->pol.theta) {      /* the policy: the features read, the controls' input, value and log-probability written, in front of the rollout's record of them */
     const npd_policy_run_t run = policy_run(h);
+    npd_policy_core_run_t cell = {};
     if (h->core.primed) {      /* with a core: the cell first, its hidden state restarted with the episode; slot 0 of a rollout keeps the state it read */
-      npd_policy_core_run_t cell = {};
       cell.h = cell.h_out = h->core.hidden; cell.first_out = h->ro.n_final && h->ro.t == 0 ? h->core.first : nullptr;
       cell.primed = h->core.primed; cell.seen = h->core.seen; cell.index = h->ep_index; cell.remember = 1;
-      npb_launch_policy_core(&h->pol, &h->core, &run, &cell, (hipStream_t)stream);
-    } else {
-      npb_launch_policy(&h->pol, &run, (hipStream_t)stream);
     }
+    policy_launch(h, &run, h->core.primed ? &cell : nullptr, stream);
     if (!h->pol.D.deterministic) h->pol_t++;
   }
   if (h->ro.n_final)      /* the rollout's slot t: what the policy saw and what it wrote, before the controls kernel and the step change either */
@@ -2411,26 +2414,34 @@ int npb_policy_load(NpbHandle *h, const float *theta, int theta_is_device, void 
   NPB_HIP(h, hipMemcpyAsync(h->pol.theta, theta, (size_t)h->pol.theta_count * sizeof(float), theta_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                             (hipStream_t)stream));
   if (!theta_is_device) NPB_HIP(h, hipStreamSynchronize((hipStream_t)stream));      /* the host array may go */
-  npb_launch_policy_repack(&h->pol, (hipStream_t)stream);
-  if (h->core.primed) npb_launch_policy_core_repack(&h->pol, &h->core, (hipStream_t)stream);
+  npb_launch_policy_repack(&h->pol, h->core.primed ? &h->core : nullptr, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+/* what npb_policy_values and npb_policy_values_hidden share, their own refusals behind them: rows NULL = the current features (with a core: and the current
+ * hidden state, the restart rule applied); the checks of type, count and alignment (`misaligned`: the entry point's words for the last); the critic's launch */
+static int policy_values(NpbHandle *h, const char *who, const char *misaligned, const void *rows, int type, int n_rows, const float *hidden_rows, float *out, void *stream) {
+  const bool own = !rows;
+  if (own) { rows = h->feat.out; type = h->feat.out_f64 ? NPB_FEATURES_F64 : NPB_FEATURES_F32; n_rows = h->n_plants; }
+  if (type != NPB_FEATURES_F32 && type != NPB_FEATURES_F64) return fail_who(h, who, ": an unknown type");
+  if (n_rows < 1) return fail_who(h, who, ": n_rows must be >= 1");
+  if (!out || ((uintptr_t)out & 3u) || ((uintptr_t)hidden_rows & 3u) || ((uintptr_t)rows & (type == NPB_FEATURES_F64 ? 7u : 3u))) return fail_who(h, who, misaligned);
+  NPB_USE_DEVICE(h);
+  npd_policy_run_t R = {};
+  R.x = rows; R.x_f64 = type == NPB_FEATURES_F64; R.rows = n_rows; R.value = out;
+  npd_policy_core_run_t cell = {};
+  cell.h = own ? h->core.hidden : hidden_rows;
+  if (own) { cell.primed = h->core.primed; cell.seen = h->core.seen; cell.index = h->ep_index; }
+  policy_launch(h, &R, h->core.primed ? &cell : nullptr, stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
 int npb_policy_values(NpbHandle *h, const void *rows, int type, int n_rows, float *out, void *stream) {
   if (!h) return NPB_EINVAL;
-  if (!h->pol.theta) return fail_who(h, "npb_policy_values", g_no_policy);
-  if (h->core.primed) return fail_who(h, "npb_policy_values", ": the policy has a core, and its critic reads a hidden state beside the rows: npb_policy_values_hidden");
-  if (!rows) { rows = h->feat.out; type = h->feat.out_f64 ? NPB_FEATURES_F64 : NPB_FEATURES_F32; n_rows = h->n_plants; }
-  if (type != NPB_FEATURES_F32 && type != NPB_FEATURES_F64) return fail(h, NPB_EINVAL, "npb_policy_values: an unknown type");
-  if (n_rows < 1) return fail(h, NPB_EINVAL, "npb_policy_values: n_rows must be >= 1");
-  if (!out || ((uintptr_t)out & 3u) || ((uintptr_t)rows & (type == NPB_FEATURES_F64 ? 7u : 3u)))
-    return fail(h, NPB_EINVAL, "npb_policy_values: a NULL or misaligned out (4-byte aligned), or rows misaligned for their type");
-  NPB_USE_DEVICE(h);
-  npd_policy_run_t R = {};
-  R.x = rows; R.x_f64 = type == NPB_FEATURES_F64; R.rows = n_rows; R.value = out;
-  npb_launch_policy(&h->pol, &R, (hipStream_t)stream);
-  NPB_HIP(h, hipGetLastError());
-  return NPB_OK;
+  const char *who = "npb_policy_values";
+  if (!h->pol.theta) return fail_who(h, who, g_no_policy);
+  if (h->core.primed) return fail_who(h, who, ": the policy has a core, and its critic reads a hidden state beside the rows: npb_policy_values_hidden");
+  return policy_values(h, who, ": a NULL or misaligned out (4-byte aligned), or rows misaligned for their type", rows, type, n_rows, nullptr, out, stream);
 }
 static const char *const g_no_core = ": the policy has no core (npb_set_policy_core)";
 int npb_policy_values_hidden(NpbHandle *h, const void *rows, int type, int n_rows, const float *hidden_rows, float *out, void *stream) {
@@ -2438,23 +2449,10 @@ int npb_policy_values_hidden(NpbHandle *h, const void *rows, int type, int n_row
   const char *who = "npb_policy_values_hidden";
   if (!h->pol.theta) return fail_who(h, who, g_no_policy);
   if (!h->core.primed) return fail_who(h, who, g_no_core);
-  const bool own = !rows;      /* the current features and the current hidden state, the restart rule applied */
-  if (own && hidden_rows) return fail_who(h, who, ": hidden_rows without rows: the current features go with the handle's own hidden state");
-  if (!own && !hidden_rows) return fail_who(h, who, ": rows of the caller's need hidden_rows, the state in front of each");
-  if (own) { rows = h->feat.out; type = h->feat.out_f64 ? NPB_FEATURES_F64 : NPB_FEATURES_F32; n_rows = h->n_plants; }
-  if (type != NPB_FEATURES_F32 && type != NPB_FEATURES_F64) return fail_who(h, who, ": an unknown type");
-  if (n_rows < 1) return fail_who(h, who, ": n_rows must be >= 1");
-  if (!out || ((uintptr_t)out & 3u) || ((uintptr_t)hidden_rows & 3u) || ((uintptr_t)rows & (type == NPB_FEATURES_F64 ? 7u : 3u)))
-    return fail_who(h, who, ": a NULL or misaligned out, misaligned hidden_rows (4-byte aligned), or rows misaligned for their type");
-  NPB_USE_DEVICE(h);
-  npd_policy_run_t R = {};
-  R.x = rows; R.x_f64 = type == NPB_FEATURES_F64; R.rows = n_rows; R.value = out;
-  npd_policy_core_run_t cell = {};
-  cell.h = own ? h->core.hidden : hidden_rows;
-  if (own) { cell.primed = h->core.primed; cell.seen = h->core.seen; cell.index = h->ep_index; }
-  npb_launch_policy_core(&h->pol, &h->core, &R, &cell, (hipStream_t)stream);
-  NPB_HIP(h, hipGetLastError());
-  return NPB_OK;
+  if (!rows && hidden_rows) return fail_who(h, who, ": hidden_rows without rows: the current features go with the handle's own hidden state");
+  if (rows && !hidden_rows) return fail_who(h, who, ": rows of the caller's need hidden_rows, the state in front of each");
+  return policy_values(h, who, ": a NULL or misaligned out, misaligned hidden_rows (4-byte aligned), or rows misaligned for their type", rows, type, n_rows, hidden_rows,
+                       out, stream);
 }
 /* hidden (the caller's tensor, which the cell carries from step to step), seen, primed */
 static StateParts policy_core_state_parts(const NpbHandle *h) {
@@ -2588,7 +2586,7 @@ static int ppo_adam(NpbHandle *h, const char *who, double lr, double b1, double 
   NPB_USE_DEVICE(h);
   h->ppo.step++;
   npb_launch_ppo_adam(&h->pol, &h->ppo, lr, b1, b2, eps, gated, (hipStream_t)stream);
-  npb_launch_policy_repack(&h->pol, (hipStream_t)stream);
+  npb_launch_policy_repack(&h->pol, h->core.primed ? &h->core : nullptr, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }

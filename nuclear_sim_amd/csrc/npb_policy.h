@@ -24,6 +24,13 @@ typedef struct {
   int cells, n_axes, width_max;      /* K * C; A; the widest hidden layer of either net */
   npb_policy_desc_t D;
 } npb_policy_t;
+/* the two builds of the forward kernels and of the gradient kernel: the small one where the features stack, every hidden layer and a
+ * core's width fit these; else the large one, NPB_FEATURES_CELLS_MAX and NPB_POLICY_WIDTH_MAX */
+#define NPD_POLICY_SMALL_CELLS 64
+#define NPD_POLICY_SMALL_WIDTH 64
+static inline bool npd_policy_small(const npb_policy_t *P, int core_width /* 0: none */) {
+  return P->cells <= NPD_POLICY_SMALL_CELLS && P->width_max <= NPD_POLICY_SMALL_WIDTH && core_width <= NPD_POLICY_SMALL_WIDTH;
+}
 /* one launch of the nets over `rows` rows of x ([rows][cells], float or double).  act != NULL: the step's launch -- actor, noise, critic,
  * every output; act == NULL: the critic alone into value (npb_policy_values) */
 typedef struct {
@@ -35,7 +42,6 @@ typedef struct {
 /* the shapes of a descriptor laid out: every offset and count of *P but its pointers */
 void npb_policy_layout(const npb_policy_desc_t *D, int cells, int n_axes, npb_policy_t *P);
 void npb_policy_layout_at(const npb_policy_desc_t *D, int cells, int in0, int n_axes, uint32_t at, uint32_t wp, npb_policy_t *P);
-void npb_launch_policy_repack(const npb_policy_t *P, hipStream_t stream);
 void npb_launch_policy(const npb_policy_t *P, const npd_policy_run_t *R, hipStream_t stream);
 /* the z of draw t ([n][A] double) and, where words != NULL, the Philox words behind it ([n][(A + 1) / 2][4] uint32) */
 void npb_launch_policy_noise(const npb_policy_t *P, uint64_t t, int n_plants, double *z, uint32_t *words, hipStream_t stream);
@@ -58,7 +64,7 @@ typedef struct {
   int32_t *primed, *seen; const int32_t *index; int remember;
 } npd_policy_core_run_t;
 void npb_policy_core_layout(int H, int gates, int cells, npd_policy_core_t *C);
-void npb_launch_policy_core_repack(const npb_policy_t *P, const npd_policy_core_t *C, hipStream_t stream);
+void npb_launch_policy_repack(const npb_policy_t *P, const npd_policy_core_t *C /* NULL: no core */, hipStream_t stream);      /* (npb_policy.hip: every layer, one launch) */
 void npb_launch_policy_core(const npb_policy_t *P, const npd_policy_core_t *C, const npd_policy_run_t *R, const npd_policy_core_run_t *G, hipStream_t stream);
 /* behind the rollout's post kernel: hidden[p] into final[final_row[p]] for every plant that took a row of final_obs in this slot */
 void npb_launch_policy_core_final(const npd_policy_core_t *C, const int32_t *final_row, int n_plants, hipStream_t stream);
@@ -66,13 +72,34 @@ void npb_launch_policy_core_final(const npd_policy_core_t *C, const int32_t *fin
 }
 #endif
 #ifdef __HIPCC__
-/* ---- what the step's launch (npb_policy.hip) and the gradient kernel (npb_ppo.hip) share: the tile's geometry and one layer of a net */
+/* ---- what the step's launches (npb_policy.hip, npb_policy_core.hip) and the gradient kernel (npb_ppo.hip) share: the tile's geometry, its
+ * rows into LDS and one layer of a net */
 #define NPD_POLICY_TILE 32
 #define NPD_POLICY_GROUPS 8
 #define NPD_POLICY_LANES (NPD_POLICY_TILE * NPD_POLICY_GROUPS)
 #define NPD_POLICY_WAVES 4
 #define NPD_POLICY_AHEAD 8        /* matrix-core calls whose operands are in flight together */
 #define NPD_POLICY_STRIDE (NPD_POLICY_TILE + 1)      /* the LDS row stride of every [k][plant] buffer (the header says why it is odd) */
+/* the live rows of the tile at `base`, 1 .. 32: the last tile may be ragged.  None of the three tile pieces holds a barrier: the callers
+ * place theirs */
+__device__ __forceinline__ int npd_policy_in_tile(size_t rows, size_t base) { return rows - base < (size_t)NPD_POLICY_TILE ? (int)(rows - base) : NPD_POLICY_TILE; }
+/* +0.0 into rows k_from .. k_to - 1 of a [k][plant] buffer, all 32 plants, 256 lanes: a k extension, or the gradient kernel's whole xs */
+__device__ __forceinline__ void npd_policy_tile_zero(float *buf, int k_from, int k_to, int tid) {
+  for (int i = tid; i < (k_to - k_from) * NPD_POLICY_TILE; i += NPD_POLICY_LANES)
+    buf[(k_from + i / NPD_POLICY_TILE) * NPD_POLICY_STRIDE + (i & (NPD_POLICY_TILE - 1))] = 0.0f;
+}
+/* the tile's in_tile rows of K elements, ONE contiguous run: consecutive lanes on consecutive elements, narrowed to float and transposed
+ * into xs[k][row]; a cell that is not finite marks its row in bad (set, never cleared: every writer writes the same 1) */
+template <typename IN>
+__device__ __forceinline__ void npd_policy_tile_load(const IN *run, int in_tile, int K, float *xs, int *bad, int tid) {
+  const int total = in_tile * K;
+  for (int e = tid; e < total; e += NPD_POLICY_LANES) {
+    const int row = e / K, k = e - row * K;
+    const float v = (float)run[e];
+    xs[k * NPD_POLICY_STRIDE + row] = v;
+    if (!(v - v == 0.0f)) bad[row] = 1;
+  }
+}
 /* one layer over the tile on the matrix cores: in[k][r] -> out[j][r] (row stride NPD_POLICY_STRIDE both), j up to the next multiple of 4
  * of the width; activation: NPB_POLICY_RELU, NPB_POLICY_TANH, or -1 for a head.  Wave `wave` takes the chunks wave, wave + 4, .. of 32
  * outputs.  v_mfma_f32_32x32x2_f32: D[i][j] = fma(A[i][k0 + 1], B[k0 + 1][j], fma(A[i][k0], B[k0][j], C[i][j])), one rounding per product:

@@ -11,7 +11,8 @@
  *   1. the tile's 32 rows of x are ONE contiguous run of 32 x K*C elements: loaded with consecutive lanes on consecutive elements,
  *      narrowed to float and transposed into LDS, xs[k][r] with a row stride of 33 (consecutive lanes write consecutive k: 33 spreads them
  *      over the banks; a layer reads xs[k][r] with consecutive lanes on consecutive r).  A row beyond `rows` is neither loaded nor stored.
- *      A cell that is not finite marks its plant (a plain LDS store of 1: every writer writes the same).
+ *      A cell that is not finite marks its plant (a plain LDS store of 1: every writer writes the same).  The pieces are npb_policy.h's,
+ *      which the recurrent kernel and the gradient kernel call too: npd_policy_in_tile, npd_policy_tile_zero, npd_policy_tile_load.
  *   2. a layer: a wave takes 32 outputs at a time (npd_policy_layer says how the operands lie): per call one LDS read of the A operand
  *      straight from xs / h, and one coalesced load of the B operand from the copy npb_policy_load made, Wt[k][j] with k and j padded
  *      with +0.0 (rows of 128 bytes a half-wave).  The bias is the initial accumulator.  The activation, then h[j][r] into LDS, the
@@ -24,8 +25,10 @@
  *      Box-Muller in double; npd_policy_pair, the function npb_policy_noise runs) into LDS; then group a < A forms and stores action a,
  *      and group 7 the log-probability (ascending over the axes), value and logp, and the two extras slots.  A marked plant stores THE
  *      quiet NaN everywhere.
- * LDS: the small build (K*C <= 64, widths <= 64) 3 x 8.25 KiB and the epilogue's 4.7 KiB; the large one (256, 128) 33 + 2 x 16.5 KiB
- * and the same -- static, beyond 64 KiB, which gfx950's 160 KiB per CU allows.  No scratch, no atomics, plain vector stores. */
+ * LDS: the small build (npd_policy_small, npb_policy.h: K*C <= NPD_POLICY_SMALL_CELLS, widths <= NPD_POLICY_SMALL_WIDTH) 3 x 8.25 KiB and
+ * the epilogue's 4.7 KiB; the large one (NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX) 33 + 2 x 16.5 KiB and the same -- static, beyond
+ * 64 KiB, which gfx950's 160 KiB per CU allows.  No scratch, no atomics, plain vector stores.
+ * npb_launch_policy_repack, the one repack there is, lays out every layer in one launch: a core's gates, the actor, the critic. */
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "npb_policy.h"
@@ -51,18 +54,17 @@ __global__ __launch_bounds__(256) void npb_policy_noise_kernel(uint64_t seed, ui
 }
 
 /* ---- the kernel's copy of the weights, in the order the matrix cores' B operand is read: Wt[k][j], in_pad rows of out_pad floats (out_pad:
- * the width up to a multiple of 32), the cells beyond `in` and beyond `out` +0.0 */
-__global__ __launch_bounds__(256) void npb_policy_repack_kernel(npb_policy_t P) {
+ * the width up to a multiple of 32), the cells beyond `in` and beyond `out` +0.0.  ONE launch over every layer there is: a core's six gate
+ * layers, the actor's, the critic's */
+typedef struct { const float *theta; float *padded; int n_layers; npd_policy_layer_t layer[6 + 2 * NPD_POLICY_LAYERS_MAX]; } npd_policy_repack_t;
+__global__ __launch_bounds__(256) void npb_policy_repack_kernel(npd_policy_repack_t K) {
   const size_t first = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (int which = 0; which < 2; which++) {
-    const npd_policy_net_t &N = which ? P.critic : P.actor;
-    for (int l = 0; l < N.n_layers; l++) {
-      const npd_policy_layer_t L = N.layer[l];
-      const size_t total = (size_t)L.in_pad * L.out_pad;
-      for (size_t i = first; i < total; i += stride) {
-        const size_t k = i / L.out_pad, j = i - k * L.out_pad;
-        P.padded[L.wp + i] = k < (size_t)L.in && j < (size_t)L.out ? P.theta[L.w + j * L.in + k] : 0.0f;
-      }
+  for (int l = 0; l < K.n_layers; l++) {
+    const npd_policy_layer_t L = K.layer[l];
+    const size_t total = (size_t)L.in_pad * L.out_pad;
+    for (size_t i = first; i < total; i += stride) {
+      const size_t k = i / L.out_pad, j = i - k * L.out_pad;
+      K.padded[L.wp + i] = k < (size_t)L.in && j < (size_t)L.out ? K.theta[L.w + j * L.in + k] : 0.0f;
     }
   }
 }
@@ -79,21 +81,13 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_policy_kernel(npb_policy
   __shared__ int bad[NPD_POLICY_TILE];
   const int tid = threadIdx.x, g = tid >> 5, r = tid & (NPD_POLICY_TILE - 1);
   const size_t base = (size_t)blockIdx.x * NPD_POLICY_TILE, rows = (size_t)R.rows;
-  const int in_tile = rows - base < (size_t)NPD_POLICY_TILE ? (int)(rows - base) : NPD_POLICY_TILE;
+  const int in_tile = npd_policy_in_tile(rows, base);
   const int KC = P.cells, KC_pad = (KC + 3) & ~3;
   /* 1. the tile's run of x into LDS, narrowed and transposed; the k extension +0.0 */
   if (tid < NPD_POLICY_TILE) bad[tid] = 0;
-  for (int i = tid; i < (KC_pad - KC) * NPD_POLICY_TILE; i += NPD_POLICY_LANES)
-    xs[(KC + i / NPD_POLICY_TILE) * NPD_POLICY_STRIDE + (i & (NPD_POLICY_TILE - 1))] = 0.0f;
+  npd_policy_tile_zero(xs, KC, KC_pad, tid);
   __syncthreads();
-  const IN *run = (const IN *)R.x + base * (size_t)KC;
-  const int total = in_tile * KC;
-  for (int e = tid; e < total; e += NPD_POLICY_LANES) {
-    const int row = e / KC, k = e - row * KC;
-    const float v = (float)run[e];
-    xs[k * NPD_POLICY_STRIDE + row] = v;
-    if (!(v - v == 0.0f)) bad[row] = 1;
-  }
+  npd_policy_tile_load((const IN *)R.x + base * (size_t)KC, in_tile, KC, xs, bad, tid);
   __syncthreads();
   /* 2. the nets */
   const int wave = tid >> 6, lane = tid & 63;
@@ -131,16 +125,20 @@ extern "C" void npb_policy_layout_at(const npb_policy_desc_t *D, int cells, int 
   P->cells = cells; P->n_axes = n_axes; P->width_max = widest;
   P->D = *D;
 }
-extern "C" void npb_launch_policy_repack(const npb_policy_t *P, hipStream_t stream) {
-  const unsigned blocks = (P->padded_count + 255u) / 256u;
-  hipLaunchKernelGGL(npb_policy_repack_kernel, dim3(blocks < 64u ? blocks : 64u), dim3(256), 0, stream, *P);
+extern "C" void npb_launch_policy_repack(const npb_policy_t *P, const npd_policy_core_t *C, hipStream_t stream) {
+  npd_policy_repack_t K = {P->theta, P->padded, 0, {}};
+  for (int l = 0; C && l < 6; l++) K.layer[K.n_layers++] = C->gate[l];
+  for (int l = 0; l < P->actor.n_layers; l++) K.layer[K.n_layers++] = P->actor.layer[l];
+  for (int l = 0; l < P->critic.n_layers; l++) K.layer[K.n_layers++] = P->critic.layer[l];
+  const unsigned blocks = (P->padded_count + 255u) / 256u;      /* (with a core the count includes the gates' cells: the nets' lie behind them) */
+  hipLaunchKernelGGL(npb_policy_repack_kernel, dim3(blocks < 64u ? blocks : 64u), dim3(256), 0, stream, K);
 }
 extern "C" void npb_launch_policy(const npb_policy_t *P, const npd_policy_run_t *R, hipStream_t stream) {
   const dim3 grid((unsigned)((R->rows + NPD_POLICY_TILE - 1) / NPD_POLICY_TILE)), block(NPD_POLICY_LANES);
-  const bool small = P->cells <= 64 && P->width_max <= 64;
+  const bool small = npd_policy_small(P, 0);
 #define NPD_POLICY_LAUNCH(IN, KC_MAX, H_MAX) hipLaunchKernelGGL((npb_policy_kernel<IN, KC_MAX, H_MAX>), grid, block, 0, stream, *P, *R)
-  if (R->x_f64) { if (small) NPD_POLICY_LAUNCH(double, 64, 64); else NPD_POLICY_LAUNCH(double, NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX); }
-  else { if (small) NPD_POLICY_LAUNCH(float, 64, 64); else NPD_POLICY_LAUNCH(float, NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX); }
+  if (R->x_f64) { if (small) NPD_POLICY_LAUNCH(double, NPD_POLICY_SMALL_CELLS, NPD_POLICY_SMALL_WIDTH); else NPD_POLICY_LAUNCH(double, NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX); }
+  else { if (small) NPD_POLICY_LAUNCH(float, NPD_POLICY_SMALL_CELLS, NPD_POLICY_SMALL_WIDTH); else NPD_POLICY_LAUNCH(float, NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX); }
 #undef NPD_POLICY_LAUNCH
 }
 extern "C" void npb_launch_policy_noise(const npb_policy_t *P, uint64_t t, int n_plants, double *z, uint32_t *words, hipStream_t stream) {

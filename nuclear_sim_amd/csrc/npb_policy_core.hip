@@ -11,7 +11,9 @@
  *      one seen (npd_controls.h's rule); a step that acts primes the plant and remembers the index, the same lane storing what it read.
  *      The tile's rows of x and of h are ONE contiguous run each (32 x K*C and 32 x H): consecutive lanes on consecutive elements, narrowed
  *      and transposed into LDS (xs, hs); a restarted plant's column of hs is +0.0; on the rollout's slot 0 the run goes out again, as read,
- *      into `first`.  The k extensions of xs and hs are +0.0.
+ *      into `first`.  The k extensions of xs and hs are +0.0.  The load of x, the zeroing and the ragged tile's row count are the MLP
+ *      kernel's own (npb_policy.h: npd_policy_tile_load, npd_policy_tile_zero, npd_policy_in_tile); the load of h, with its restart
+ *      mask and its store into `first`, is this file's.
  *   2. gate by gate, so that only H-wide buffers live in LDS: gi = W_i* x into ha and gh = W_h* h into hb (two layers, one barrier: they
  *      read xs and hs and write apart; gh's chunks of 32 outputs start two waves on, so a cell of up to 64 cells keeps all four waves
  *      busy where a layer alone would leave two without a chunk), then 256 lanes over the H x 32 cells: r = S(gi + gh) into rs; z
@@ -22,9 +24,11 @@
  *   4. the actor and the critic over hs with ha and hb as their ping-pong buffers, and the epilogue: npb_policy.h's, the MLP kernel's own.
  * npb_policy_values_hidden is the same kernel with act == NULL: the critic over GRU(x, h), nothing written back to h, primed or seen.
  * LDS, from the declarations below: (KC_MAX + 5 H_MAX) x 33 x 4 B for xs, hs, ha, hb, rs, zg, and the epilogue's 1056 + 528 + 2048 + 128 B
- * with 256 B of poison and restart words: the small build (64, 64) 54 576 B, the large one (256, 128) 122 160 B, as the compiler reports
- * them -- static, beyond 64 KiB, inside gfx950's 160 KiB per CU (one workgroup a CU in the large build, three in the small one).  A 3H-wide
- * gi and gh together would not fit.  64 VGPRs and 16 AGPRs, no scratch, no spills, no atomics. */
+ * with 256 B of poison and restart words: the small build (NPD_POLICY_SMALL_CELLS, NPD_POLICY_SMALL_WIDTH; npd_policy_small with the core's
+ * width, npb_policy.h) 54 576 B, the large one (NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX) 122 160 B, as the compiler reports them --
+ * static, beyond 64 KiB, inside gfx950's 160 KiB per CU (one workgroup a CU in the large build, three in the small one).  A 3H-wide gi and
+ * gh together would not fit.  64 VGPRs and 16 AGPRs, no scratch, no spills, no atomics.  The gate layers' copy for the matrix cores is laid out by the policy's
+ * one repack launch (npb_launch_policy_repack, npb_policy.hip), together with the nets'. */
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "npb_policy.h"
@@ -48,19 +52,6 @@ __device__ __forceinline__ float npd_core_tau(float a, int gates) {
   return tanhf(a);
 }
 
-/* the kernel's copy of the six gate layers, as npb_policy_repack_kernel lays out a net's */
-__global__ __launch_bounds__(256) void npb_policy_core_repack_kernel(npd_policy_core_t C, const float *__restrict__ theta, float *__restrict__ padded) {
-  const size_t first = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (int l = 0; l < 6; l++) {
-    const npd_policy_layer_t L = C.gate[l];
-    const size_t total = (size_t)L.in_pad * L.out_pad;
-    for (size_t i = first; i < total; i += stride) {
-      const size_t k = i / L.out_pad, j = i - k * L.out_pad;
-      padded[L.wp + i] = k < (size_t)L.in && j < (size_t)L.out ? theta[L.w + j * L.in + k] : 0.0f;
-    }
-  }
-}
-
 template <typename IN, int KC_MAX, int H_MAX>
 __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_policy_core_kernel(npb_policy_t P, npd_policy_core_t C, npd_policy_run_t R, npd_policy_core_run_t G) {
   __shared__ float xs[KC_MAX * NPD_POLICY_STRIDE];
@@ -71,7 +62,7 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_policy_core_kernel(npb_p
   __shared__ int bad[NPD_POLICY_TILE], fresh[NPD_POLICY_TILE];
   const int tid = threadIdx.x, g = tid >> 5, r = tid & (NPD_POLICY_TILE - 1);
   const size_t base = (size_t)blockIdx.x * NPD_POLICY_TILE, rows = (size_t)R.rows;
-  const int in_tile = rows - base < (size_t)NPD_POLICY_TILE ? (int)(rows - base) : NPD_POLICY_TILE;
+  const int in_tile = npd_policy_in_tile(rows, base);
   const int KC = P.cells, KC_pad = (KC + 3) & ~3, H = C.H, H_pad = (H + 3) & ~3;
   /* 1. the restart words; the tile's runs of x and h into LDS, narrowed and transposed; the k extensions +0.0 */
   if (tid < NPD_POLICY_TILE) {
@@ -85,19 +76,10 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_policy_core_kernel(npb_p
     bad[tid] = 0;
     fresh[tid] = restart;
   }
-  for (int i = tid; i < (KC_pad - KC) * NPD_POLICY_TILE; i += NPD_POLICY_LANES)
-    xs[(KC + i / NPD_POLICY_TILE) * NPD_POLICY_STRIDE + (i & (NPD_POLICY_TILE - 1))] = 0.0f;
-  for (int i = tid; i < (H_pad - H) * NPD_POLICY_TILE; i += NPD_POLICY_LANES)
-    hs[(H + i / NPD_POLICY_TILE) * NPD_POLICY_STRIDE + (i & (NPD_POLICY_TILE - 1))] = 0.0f;
+  npd_policy_tile_zero(xs, KC, KC_pad, tid);
+  npd_policy_tile_zero(hs, H, H_pad, tid);
   __syncthreads();
-  const IN *run = (const IN *)R.x + base * (size_t)KC;
-  const int total = in_tile * KC;
-  for (int e = tid; e < total; e += NPD_POLICY_LANES) {
-    const int row = e / KC, k = e - row * KC;
-    const float v = (float)run[e];
-    xs[k * NPD_POLICY_STRIDE + row] = v;
-    if (!(v - v == 0.0f)) bad[row] = 1;
-  }
+  npd_policy_tile_load((const IN *)R.x + base * (size_t)KC, in_tile, KC, xs, bad, tid);
   const int h_total = in_tile * H;
   const float *h_run = G.h + base * (size_t)H;
   for (int e = tid; e < h_total; e += NPD_POLICY_LANES) {
@@ -179,16 +161,12 @@ extern "C" void npb_policy_core_layout(int H, int gates, int cells, npd_policy_c
   }
   C->theta_count = at; C->padded_count = wp;
 }
-extern "C" void npb_launch_policy_core_repack(const npb_policy_t *P, const npd_policy_core_t *C, hipStream_t stream) {
-  const unsigned blocks = (C->padded_count + 255u) / 256u;
-  hipLaunchKernelGGL(npb_policy_core_repack_kernel, dim3(blocks < 64u ? blocks : 64u), dim3(256), 0, stream, *C, P->theta, P->padded);
-}
 extern "C" void npb_launch_policy_core(const npb_policy_t *P, const npd_policy_core_t *C, const npd_policy_run_t *R, const npd_policy_core_run_t *G, hipStream_t stream) {
   const dim3 grid((unsigned)((R->rows + NPD_POLICY_TILE - 1) / NPD_POLICY_TILE)), block(NPD_POLICY_LANES);
-  const bool small = P->cells <= 64 && P->width_max <= 64 && C->H <= 64;
+  const bool small = npd_policy_small(P, C->H);
 #define NPD_CORE_LAUNCH(IN, KC_MAX, H_MAX) hipLaunchKernelGGL((npb_policy_core_kernel<IN, KC_MAX, H_MAX>), grid, block, 0, stream, *P, *C, *R, *G)
-  if (R->x_f64) { if (small) NPD_CORE_LAUNCH(double, 64, 64); else NPD_CORE_LAUNCH(double, NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX); }
-  else { if (small) NPD_CORE_LAUNCH(float, 64, 64); else NPD_CORE_LAUNCH(float, NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX); }
+  if (R->x_f64) { if (small) NPD_CORE_LAUNCH(double, NPD_POLICY_SMALL_CELLS, NPD_POLICY_SMALL_WIDTH); else NPD_CORE_LAUNCH(double, NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX); }
+  else { if (small) NPD_CORE_LAUNCH(float, NPD_POLICY_SMALL_CELLS, NPD_POLICY_SMALL_WIDTH); else NPD_CORE_LAUNCH(float, NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX); }
 #undef NPD_CORE_LAUNCH
 }
 extern "C" void npb_launch_policy_core_final(const npd_policy_core_t *C, const int32_t *final_row, int n_plants, hipStream_t stream) {

@@ -6,7 +6,8 @@
  * THE GRADIENT KERNEL: one workgroup of 256 lanes (four waves) runs one CHAIN of rows_per_chain rows, tile of 32 rows after tile, and a
  * launch's workgroups stride over the chains; a chain's sums are the same whichever workgroup runs it and whenever.  Per tile:
  *   1. the tile's rows of obs into LDS as the step's launch lays them, xs[k][row] with a row stride of 33; a row beyond count, and a
- *      skipped row (a feature, an action, logp_old, adv or ret that is not finite), reads as +0.0 everywhere.
+ *      skipped row (a feature, an action, logp_old, adv or ret that is not finite), reads as +0.0 everywhere.  The zeroing and the load
+ *      are the step's (npb_policy.h: npd_policy_tile_zero, npd_policy_tile_load, its float or double instance picked once a tile).
  *   2. the actor forward by the step's own layer routine (npd_policy_layer, npb_policy.h), every hidden activation kept in LDS, h[l][k][row].
  *   3. the per-row epilogue in double, a lane a row: the head's seeds dmean[a][row] as floats into LDS, the per-row doubles (dls, the
  *      losses' terms) into LDS, logp_new and ratio out.
@@ -20,8 +21,9 @@
  *   5. the critic the same way, its hidden activations over the actor's: forward, the value's seed and loss (with clip_vf > 0 the
  *      clipped branch: the larger of the two squares and its own derivative), the four terms of explained_variance, backward.
  *   6. the per-row doubles of the tile added in row order onto the chain's running sums, a lane a quantity.
- * No atomics, nothing depends on the launch order, no scratch.  LDS: the small build (K*C <= 64, widths <= 64) 6 x 8.25 KiB and 6 KiB; the
- * large one 33 + 5 x 16.5 KiB and the same, 122 KiB of gfx950's 160.
+ * No atomics, nothing depends on the launch order, no scratch.  LDS: the small build (npd_policy_small, npb_policy.h: K*C <=
+ * NPD_POLICY_SMALL_CELLS, widths <= NPD_POLICY_SMALL_WIDTH) 6 x 8.25 KiB and 6 KiB; the large one 33 + 5 x 16.5 KiB and the same, 122 KiB
+ * of gfx950's 160.
  * THE REDUCE KERNEL: a lane a parameter: its partials widened and added in ascending chain order, narrowed once; log_std's from the dls
  * sums; then the first level of the pinned tree over the squares.  THE FINISH KERNEL, one workgroup: the tree's further levels, the norm,
  * the scale, the statistics, and with a gate armed (kl_limit > 0) the gate: one lane ORs approx_kl > kl_limit into the training block's
@@ -155,10 +157,10 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_grad_kernel(npb_poli
     double running = 0.0;      /* lane q < NPD_PPO_ROWVALS: the chain's sum of per-row double q */
     for (size_t base = chain * rpc; base < (chain + 1) * rpc && base < count; base += NPD_POLICY_TILE) {
       const bool first = base == chain * rpc;
-      const int in_tile = count - base < (size_t)NPD_POLICY_TILE ? (int)(count - base) : NPD_POLICY_TILE;
+      const int in_tile = npd_policy_in_tile(count, base);
       /* 1. the rows: +0.0 everywhere, then the tile's run of obs, then the skipped rows back to +0.0 */
       __syncthreads();      /* (the tile before is done with every buffer) */
-      for (int i = tid; i < KC_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES) xs[(i >> 5) * NPD_POLICY_STRIDE + (i & 31)] = 0.0f;
+      npd_policy_tile_zero(xs, 0, KC_pad, tid);
       for (int i = tid; i < NPD_PPO_ROWVALS * NPD_POLICY_TILE; i += NPD_POLICY_LANES) rowv[i] = 0.0;
       if (tid < NPD_POLICY_TILE) {
         int b = 0;
@@ -172,13 +174,8 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_grad_kernel(npb_poli
         bad[tid] = b;
       }
       __syncthreads();
-      const int total = in_tile * KC;
-      for (int e = tid; e < total; e += NPD_POLICY_LANES) {
-        const int row = e / KC, k = e - row * KC;
-        const float v = D.obs_type ? (float)((const double *)D.obs)[base * KC + e] : ((const float *)D.obs)[base * KC + e];
-        xs[k * NPD_POLICY_STRIDE + row] = v;
-        if (!(v - v == 0.0f)) bad[row] = 1;
-      }
+      if (D.obs_type) npd_policy_tile_load((const double *)D.obs + base * KC, in_tile, KC, xs, bad, tid);
+      else npd_policy_tile_load((const float *)D.obs + base * KC, in_tile, KC, xs, bad, tid);
       __syncthreads();
       for (int i = tid; i < KC * NPD_POLICY_TILE; i += NPD_POLICY_LANES)
         if (bad[i & 31]) xs[(i >> 5) * NPD_POLICY_STRIDE + (i & 31)] = 0.0f;
@@ -404,7 +401,7 @@ static npd_ppo_run_t npd_ppo_run(const npb_ppo_t *O, const npb_ppo_desc_t *D, co
 static void npd_ppo_launch_grad(const npb_policy_t *P, const npb_ppo_desc_t *D, const npd_ppo_run_t &R, hipStream_t stream) {
   const int cap = D->max_blocks > 0 ? D->max_blocks : 2048;
   const dim3 grid((unsigned)(R.n_chains < cap ? R.n_chains : cap)), block(NPD_POLICY_LANES);
-  if (P->cells <= 64 && P->width_max <= 64) hipLaunchKernelGGL((npb_ppo_grad_kernel<64, 64>), grid, block, 0, stream, *P, R);
+  if (npd_policy_small(P, 0)) hipLaunchKernelGGL((npb_ppo_grad_kernel<NPD_POLICY_SMALL_CELLS, NPD_POLICY_SMALL_WIDTH>), grid, block, 0, stream, *P, R);
   else hipLaunchKernelGGL((npb_ppo_grad_kernel<NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX>), grid, block, 0, stream, *P, R);
 }
 extern "C" void npb_launch_ppo_grad(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, hipStream_t stream) {

@@ -8,6 +8,8 @@ autoreset with max_episode_steps = 3 from a start bank and the training-loop sui
 while the step limit truncates others.  Shapes: n in {33, 70} (a ragged last tile; more than two tiles), K * C in {5, 65} (no multiple of
 4; one past the small LDS build), H in {6, 33, 65} (a k extension; one past a chunk of 32 outputs; one past the small build), and one case
 at n = 64, K * C = 256, H = 128 for the large build's LDS plan; float32 and float64 features."""
+import copy
+
 import numpy as np
 import pytest
 import torch
@@ -382,3 +384,35 @@ def test_off_is_off_and_training_is_refused_by_name():
     with pytest.raises(ValueError):
         on.policy_load(theta[:-1])
     off.close(); on.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 8
+def test_a_second_policy_load_lays_out_every_layer_behind_a_core():
+    """33 plants (two tiles, the second ragged), 5 cells (a live k extension), H = 6, hard gates, relu nets, deterministic.  theta_a, one
+    step; policy_load of a theta_b whose six gate layers, every net layer and log_std all differ; one more step.  After each step hidden,
+    action, value and logp are the statement's bits under the parameters then loaded: one layer left at theta_a in the kernel's own copy
+    of the weights would show.  Teeth: the second step under theta_a, from the same state, gives another hidden state and another action"""
+    n, C, K, H, A, actor, critic = 33, 5, 1, 6, 3, (33, 17), (7,)
+    env = _env(n, C, K, F32, H, actor=actor, critic=critic, deterministic=True)
+    theta_a = _np(env.policy_theta())
+    theta_b = recurrent.pack(*_weights(501, H, A, actor, critic), core=_core(502, K * C, H))
+    core_a, actor_a, critic_a, log_std_a, _ = recurrent.unpack(theta_a, K * C, A, actor, critic, H)
+    core_b, actor_b, critic_b, log_std_b, _ = recurrent.unpack(theta_b, K * C, A, actor, critic, H)
+    for gate in range(3):      # W_ih's and W_hh's row blocks r, z, n with their biases: the six gate layers
+        rows = slice(gate * H, (gate + 1) * H)
+        assert all((x[rows] != y[rows]).all() for x, y in zip(core_a, core_b))
+    assert all((Wa != Wb).all() and (ba != bb).all() for (Wa, ba), (Wb, bb) in zip(actor_a + critic_a, actor_b + critic_b)) and (log_std_a != log_std_b).all()
+    env.policy_load(theta_a)
+    P = _statement(env)
+    info, out, _ = _one(env, P, 0)
+    _hold(env, P, info, out, "theta_a")
+    env.policy_load(theta_b)
+    stale = copy.deepcopy(P)      # the statement that goes on under theta_a
+    P.load(_np(env.policy_theta()))
+    _same(P.theta[:-A], theta_b[:-A], "theta_b on the device")
+    before = _np(env.features())
+    info, out, _ = _one(env, P, 1)
+    _hold(env, P, info, out, "theta_b")
+    old_act, _, _ = stale.step(before, episode=_np(info["episode_index"]))
+    assert not np.array_equal(_bits(stale.h), _bits(env.policy_hidden())) and not np.array_equal(_bits(old_act), _bits(env.controls_input()))
+    env.close()
