@@ -26,9 +26,10 @@ struct NpbHandle {
   int n_plants;
   int device;
   size_t pitch;        /* n_plants rounded up to a multiple of the wave size */
-  size_t seg;          /* plants per arena segment (npb_kernels.hip, "segmented arena"), 0 = the arena is one [column][pitch] block */
+  size_t seg;          /* plants per arena segment (npd_arena.h, "segmented arena"), 0 = the arena is one [column][pitch] block */
   int storage;         /* NPB_STORAGE_F64 | NPB_STORAGE_F32: element type of the real-valued columns */
   const npb_launchers_t *K;   /* the launchers of that storage type's build of npb_kernels.hip */
+  const npb_attach_launchers_t *A;   /* and of npb_attachments.hip */
   size_t real_bytes;   /* 8 | 4 */
   void *f64;           /* the arena: [NPB_TOTAL_COL64][pitch] 8-byte columns, or [NPB_TOTAL_COL32][pitch] 4-byte ones */
   double *convert;     /* one staging column (pitch doubles) used by get/set_field with host buffers */
@@ -570,8 +571,9 @@ int npb_create_storage(const npb_params_t *params, int n_plants, int device, int
   h->pitch = ((size_t)n_plants + 63) / 64 * 64;
   h->storage = storage; h->real_bytes = real_bytes;
   h->K = storage == NPB_STORAGE_F32 ? &npb32_launch_table : &npb_launch_table;
+  h->A = storage == NPB_STORAGE_F32 ? &npb32_launch_attach_table : &npb_launch_attach_table;
   h->f64 = nullptr; h->convert = nullptr; h->plan_dev = nullptr;
-  /* batches past the two-wave kernel's range keep their arena in segments of 16 384 plants (npb_kernels.hip, "segmented arena") */
+  /* batches past the two-wave kernel's range keep their arena in segments of 16 384 plants (npd_arena.h, "segmented arena") */
   {   /* NPB_ARENA_SEGMENT=0 turns it off, =<plants> (a multiple of 64) forces that segment size at any batch size: A/B aids */
     const char *e2 = getenv("NPB_ARENA_SEGMENT");
     h->seg = h->pitch > 45056 ? 16384 : 0;     /* from NPB_SEGMENTED_FROM of npb_kernels.hip on: the four-wave kernel's second range and everything above it */
@@ -1098,7 +1100,7 @@ int npb_sampler_sample(NpbHandle *h, int sampler, double *out, void *stream) {
   if (!out) return fail(h, NPB_EINVAL, "npb_sampler_sample: NULL output buffer");
   NPB_USE_DEVICE(h);
   const Sampler *sm = h->samplers[(size_t)sampler];
-  h->K->sample(h->f64, NPB_N(h), sm->plan, sm->n_fields, sm->side, sm->n_rows, sm->ids, sm->n_watched, out, (hipStream_t)stream);
+  h->A->sample(h->f64, NPB_N(h), sm->plan, sm->n_fields, sm->side, sm->n_rows, sm->ids, sm->n_watched, out, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -1238,7 +1240,7 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
   if (h->ro.n_final)      /* the rollout's slot t: what the policy saw and what it wrote, before the controls kernel and the step change either */
     npb_launch_rollout_pre(&h->ro, h->feat.out, h->ctl.age ? h->ctl.in : nullptr, h->n_plants, (hipStream_t)stream);
   if (h->ctl.age) {      /* the caller's policy outputs: the actuators moved, the input columns filled, in front of the step */
-    h->K->controls(h->f64, NPB_N(h), &h->ctl, &h->params, h->n_plants, h->ep_index, (hipStream_t)stream);
+    h->A->controls(h->f64, NPB_N(h), &h->ctl, &h->params, h->n_plants, h->ep_index, (hipStream_t)stream);
     if (h->ctl_axis[NPB_CONTROL_INPUT_POWER_SETPOINT] >= 0) power_setpoint = h->ctl.column[NPB_CONTROL_INPUT_POWER_SETPOINT];
     if (h->ctl_axis[NPB_CONTROL_INPUT_COOLING_WATER_TEMP] >= 0) cooling_water_temp = h->ctl.column[NPB_CONTROL_INPUT_COOLING_WATER_TEMP];
   }
@@ -1277,18 +1279,18 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
     h->K->maint(NPB_N(h), h->f64, h->maint_side, h->maint_counts, h->n_plants, (hipStream_t)stream);
   if (maint) summary_fold(h, (hipStream_t)stream);      /* the rule has appended this step's records: the summary is current when the call returns */
   if (h->task.terms) {      /* the caller's reward and termination rule: everything below that deals with episodes reads the task's columns in place of the step's */
-    h->K->task(h->f64, NPB_N(h), &h->task, h->n_plants, h->ep_index, (hipStream_t)stream);
+    h->A->task(h->f64, NPB_N(h), &h->task, h->n_plants, h->ep_index, (hipStream_t)stream);
     done = h->task.done; reward = h->task.reward;
   }
   if (h->cs.cols)      /* the end-of-step state of the episode this step belonged to, before any restore */
-    h->K->column_stats_fold(h->f64, NPB_N(h), &h->cs, h->n_plants, (hipStream_t)stream);
+    h->A->column_stats_fold(h->f64, NPB_N(h), &h->cs, h->n_plants, (hipStream_t)stream);
   if (h->ew.cols)      /* the same sample into every plant's ring, the triggers, the windows that are due -- or cut short by an episode that ends here */
-    h->K->event_windows(h->f64, NPB_N(h), &h->ew, h->n_plants, h->ew_step++, h->ep_index, h->autoreset ? h->ep_len : nullptr, done,
+    h->A->event_windows(h->f64, NPB_N(h), &h->ew, h->n_plants, h->ew_step++, h->ep_index, h->autoreset ? h->ep_len : nullptr, done,
                         h->max_episode_steps, (hipStream_t)stream);
   const double *recorded_reward = reward;
   if (h->norm.streams) {      /* the running statistics take this step's samples and rewrite ref and scale in the features' table, in front of pass A */
     if (h->norm_training) {
-      h->K->normalizer(h->f64, NPB_N(h), &h->norm, h->n_plants, h->ep_index, reward, (hipStream_t)stream);
+      h->A->normalizer(h->f64, NPB_N(h), &h->norm, h->n_plants, h->ep_index, reward, (hipStream_t)stream);
       npb_launch_normalizer_finish(&h->norm, (h->n_plants + 255) / 256, (hipStream_t)stream);
     }
     if (h->norm.reward_on) {      /* the reward the learner sees; everything that deals with episodes keeps the raw one */
@@ -1297,7 +1299,7 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
     }
   }
   if (h->feat.cols)      /* pass A: this step's frame into every plant's stack, while everything still describes the episode it belongs to */
-    h->K->features(h->f64, NPB_N(h), &h->feat, h->n_plants, 0, h->ep_index, (hipStream_t)stream);
+    h->A->features(h->f64, NPB_N(h), &h->feat, h->n_plants, 0, h->ep_index, (hipStream_t)stream);
   if (h->ro.n_final) {      /* the rollout's slot t: reward, outcome and the truncated plants' stacks, terminal frame included, while the carried length is the old one */
     npb_launch_rollout_post(&h->ro, h->feat.out, recorded_reward, done, h->autoreset ? h->ep_len : nullptr, h->autoreset ? h->ep_index : nullptr,
                             h->max_episode_steps, h->n_plants, (hipStream_t)stream);
@@ -1306,7 +1308,7 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
     h->ro.t++;
   }
   if (h->er_on && h->autoreset)      /* the episodes that end on this step, recorded while everything still describes them; then their summary rows cleared */
-    h->K->episode_records(h->n_plants, NPB_N(h), h->f64, done, reward, obs, trip_flags, counters_of(h), h->ep_start,
+    h->A->episode_records(h->n_plants, NPB_N(h), h->f64, done, reward, obs, trip_flags, counters_of(h), h->ep_start,
                           h->max_episode_steps, h->er_step++, &h->er, er_uses_summary(h) ? &h->summary : nullptr,
                           (h->ers_on || h->ert_on) ? h->ers_dev : nullptr, (hipStream_t)stream);
   if (h->autoreset)   /* same stream, nothing read back, the maintenance cache kept per plant by the kernel itself */
@@ -1315,7 +1317,7 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
                   maint ? h->maint_side : nullptr, maint ? h->maint_counts : nullptr, side, (hipStream_t)stream);
   if (h->autoreset) restart_streams(h, from_bank, (hipStream_t)stream, &es_take);      /* the plants the episode kernel has just restarted */
   if (h->feat.cols && h->autoreset)      /* pass B: their stacks into `final`, then the fresh frame of the restored state */
-    h->K->features(h->f64, NPB_N(h), &h->feat, h->n_plants, 1, h->ep_index, (hipStream_t)stream);
+    h->A->features(h->f64, NPB_N(h), &h->feat, h->n_plants, 1, h->ep_index, (hipStream_t)stream);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, NPB_EHIP, "npb_step: kernel launch failed", e);
   return NPB_OK;
@@ -1871,7 +1873,7 @@ int npb_column_stats_fold(NpbHandle *h, void *stream) {
   if (!h) return NPB_EINVAL;
   if (!h->cs.cols) return fail(h, NPB_EINVAL, "npb_column_stats_fold: no column statistics set (npb_set_column_stats first)");
   NPB_USE_DEVICE(h);
-  h->K->column_stats_fold(h->f64, NPB_N(h), &h->cs, h->n_plants, (hipStream_t)stream);
+  h->A->column_stats_fold(h->f64, NPB_N(h), &h->cs, h->n_plants, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -2123,7 +2125,7 @@ int npb_features_prime(NpbHandle *h, void *stream) {
   if (!h) return NPB_EINVAL;
   if (!h->feat.cols) return fail(h, NPB_EINVAL, "npb_features_prime: no features set (npb_set_features first)");
   NPB_USE_DEVICE(h);
-  h->K->features(h->f64, NPB_N(h), &h->feat, h->n_plants, 2, h->ep_index, (hipStream_t)stream);
+  h->A->features(h->f64, NPB_N(h), &h->feat, h->n_plants, 2, h->ep_index, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }

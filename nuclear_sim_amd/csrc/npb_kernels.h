@@ -1,7 +1,9 @@
 /* npb_kernels.h -- host-callable launchers of the device kernels (internal to libnpb.so).
- * npb_kernels.hip is compiled twice: 8-byte arena columns (npb_launch_table) and 4-byte columns for fp32 storage
- * (npb32_launch_table, -DNPB_BUILD_F32); the arena pointer is void* here and typed inside each translation unit.  A handle
- * picks its table once, by its storage type. */
+ * npb_kernels.hip (the plant kernels: npb_launchers_t) and npb_attachments.hip (the per-step attachments that read the arena:
+ * npb_attach_launchers_t) are compiled twice each: 8-byte arena columns (npb_launch_table, npb_launch_attach_table) and 4-byte columns for
+ * fp32 storage (npb32_launch_table, npb32_launch_attach_table, -DNPB_BUILD_F32); the arena pointer is void* here and typed inside each
+ * translation unit.  A handle picks its two tables once, by its storage type.  What never sees an arena element is compiled once
+ * (npb_storage_free.hip) and declared behind the tables. */
 #ifndef NPB_KERNELS_H
 #define NPB_KERNELS_H
 #include <hip/hip_runtime.h>
@@ -172,6 +174,10 @@ typedef struct {
    * behind the plain step kernel; maint_side = the rule's constants, cm_side = the component table and side state */
   void (*maint_all)(size_t npad, void *arena, void *maint_side, void *cm_side, int32_t *counts, int n_plants, double *diag, size_t diag_pitch,
                     hipStream_t stream);
+} npb_launchers_t;
+extern npb_launchers_t npb_launch_table, npb32_launch_table;
+/* the per-step attachments that read the arena (npb_attachments.hip) */
+typedef struct {
   /* npb_sampler_sample: rows = n_fields arena members (plan_dev as for gather) then the side rows, of the plants ids_dev[0 .. n_watched):
    * out[r * n_watched + j], one launch */
   void (*sample)(const void *arena, size_t npad, const int *plan_dev, int n_fields, const npb_sample_row_t *side_dev, int n_rows,
@@ -206,9 +212,9 @@ typedef struct {
    * index: the handle's carried episode indices or NULL */
   void (*normalizer)(const void *arena, size_t npad, const npb_normalizer_t *Z, int n_plants, const int32_t *index, const double *reward,
                      hipStream_t stream);
-} npb_launchers_t;
-extern npb_launchers_t npb_launch_table, npb32_launch_table;
-/* the same for either storage type */
+} npb_attach_launchers_t;
+extern npb_attach_launchers_t npb_launch_attach_table, npb32_launch_attach_table;
+/* the same for either storage type (npb_storage_free.hip) */
 void npb_launch_maint_consts(const npb_params_t *P, const npb_maint_table_t *T, npd_maint_log_t log, void *host_out);
 size_t npb_launch_maint_consts_bytes(void);
 size_t npb_launch_maint_side_bytes(size_t npad);

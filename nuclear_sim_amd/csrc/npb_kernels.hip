@@ -1,5 +1,8 @@
 /*
- * npb_kernels.hip -- the fused plant-step kernel for gfx950 (MI355X) and its small companions.
+ * npb_kernels.hip -- the plant kernels for gfx950 (MI355X): the fused step kernels bench.py times and the maintenance rule they call,
+ * and the kernels that move whole plants -- observe, init, reset, restore, episode, the operator's maintenance orders, field get / set /
+ * gather.  Compiled once per storage type; its launchers make up npb_launch_table / npb32_launch_table.  What else libnpb.so holds,
+ * and why in units of its own: DESIGN.md, "The translation units of libnpb.so".
  *
  * One wavefront lane = one plant.  State lives in HBM as a struct-of-arrays: column `slot` of the
  * fp64 table is f64[slot * Npad + plant], so every load/store instruction of a wave touches 64
@@ -42,6 +45,8 @@ extern "C" __attribute__((visibility("default"))) int npb_debug_set_stamp_buffer
 #define NPD_WAIT_ACC_STORE()
 #endif
 #include "npd_stage.h"
+#include "npd_arena.h"
+#include "npd_record_log.h"
 #include "npd_primary.h"
 #include "npd_sg.h"
 #include "npd_feedwater.h"
@@ -62,71 +67,6 @@ extern "C" __attribute__((visibility("default"))) int npb_debug_set_stamp_buffer
 #endif
 #define NPB_OBS_PAD 23 /* LDS row stride in doubles: 22 + 1 keeps the transpose at <= 2-way bank conflicts */
 
-/* ---- segmented arena.  A handle of more than 45 056 plants keeps its arena in SEGMENTS of 16 384 plants: segment s
- * is the whole [column][plant] block of plants s * seg .. (s + 1) * seg - 1, so a launch over one segment sweeps one dense range of
- * memory (two handles of 32 768 plants step 4-6 % faster than one of 65 536 laid out column by column over all plants,
- * profiles/r3_shared_launches.txt; what makes the difference is not the launch per handle but the layout: one launch of the four-wave kernel
- * over a segmented arena is as fast, profiles/r3_segment_size.txt).  Every kernel takes
- * the arena pointer and "N", the column pitch in plants, whose upper 32 bits carry the segment size (0 = one segment); with
- *   address(column, plant p) = arena + s * seg * columns + column * seg + (p - s * seg) = [arena + s * seg * (columns - 1)] + column * seg + p
- * a kernel only has to move its base pointer once, by its plant's segment, and use the segment size as its pitch. */
-#ifdef NPB_BUILD_F32
-#define NPD_ARENA_COLS NPB_TOTAL_COL32
-#else
-#define NPD_ARENA_COLS NPB_TOTAL_COL64
-#endif
-#define NPD_SEGMENT(arena, N, p) do { const size_t seg__ = (size_t)(N) >> 32; (N) = (size_t)(N) & 0xffffffffu; \
-    if (seg__) { (arena) += ((size_t)(p) / seg__) * seg__ * (size_t)(NPD_ARENA_COLS - 1); (N) = seg__; } } while (0)
-/* launcher side: the pitch and the segment size out of a packed N */
-#define NPD_NPAD(npad) ((size_t)(npad) & 0xffffffffu)
-#define NPD_SEG_OF(npad) ((size_t)(npad) >> 32)
-
-/* ---- section <-> arena movers outside the step kernel (init, observe, maintenance): plain global accesses.
- * A section struct is NF doubles (the last NO of them outputs) followed by NI int32s (include/npb_fields.h); in the
- * arena the NF - NO carried doubles take one column each and the narrow members share columns (npd_stage.h). */
-__device__ __forceinline__ char *npd_gaddr(npd_real_t *arena, size_t N, size_t p, int col) {
-  return (char *)(arena + (size_t)col * N + p);
-}
-template <int NF, int NO, int NI, typename S>
-__device__ __forceinline__ void npd_load(S &s, const npd_real_t *__restrict__ arena, size_t N, size_t p, int col0) {
-  double *d = reinterpret_cast<double *>(&s);
-  constexpr int NC = NF - NO;
-  npd_real_t *a = const_cast<npd_real_t *>(arena);
-#pragma unroll
-  for (int k = 0; k < NC; k++) d[k] = (double)*(const npd_real_t *)npd_gaddr(a, N, p, col0 + k);
-#pragma unroll
-  for (int j = 0; j < NO; j++) d[NC + j] = (double)*(const float *)(npd_gaddr(a, N, p, col0 + NC + j / NPD_NPC) + (j % NPD_NPC) * 4);
-  int32_t *q = reinterpret_cast<int32_t *>(d + NF);
-#pragma unroll
-  for (int k = 0; k < NI; k++) q[k] = *(const int32_t *)(npd_gaddr(a, N, p, col0 + NC + (NO + k) / NPD_NPC) + ((NO + k) % NPD_NPC) * 4);
-}
-template <int NF, int NO, int NI, typename S>
-__device__ __forceinline__ void npd_store(const S &s, npd_real_t *__restrict__ arena, size_t N, size_t p, int col0) {
-  const double *d = reinterpret_cast<const double *>(&s);
-  constexpr int NC = NF - NO;
-#pragma unroll
-  for (int k = 0; k < NC; k++) *(npd_real_t *)npd_gaddr(arena, N, p, col0 + k) = (npd_real_t)d[k];
-#pragma unroll
-  for (int j = 0; j < NO; j++) *(float *)(npd_gaddr(arena, N, p, col0 + NC + j / NPD_NPC) + (j % NPD_NPC) * 4) = (float)d[NC + j];
-  const int32_t *q = reinterpret_cast<const int32_t *>(d + NF);
-#pragma unroll
-  for (int k = 0; k < NI; k++) *(int32_t *)(npd_gaddr(arena, N, p, col0 + NC + (NO + k) / NPD_NPC) + ((NO + k) % NPD_NPC) * 4) = q[k];
-  if ((NO + NI) % NPD_NPC) *(int32_t *)(npd_gaddr(arena, N, p, col0 + NC + (NO + NI) / NPD_NPC) + 4) = 0; /* unused half of the last column */
-}
-#define NPD_LOAD(T, stype, s, inst) npd_load<NPB_##T##_NF64, NPB_##T##_NOUT, NPB_##T##_NI32, stype>(s, f64, N, p, NPD_SEC_COL(T, inst))
-#define NPD_STORE(T, stype, s, inst) npd_store<NPB_##T##_NF64, NPB_##T##_NOUT, NPB_##T##_NI32, stype>(s, f64, N, p, NPD_SEC_COL(T, inst))
-/* single member reads: fp64 member (carried or output) / int32 member */
-template <int NC> __device__ __forceinline__ double npd_gread_real(const npd_real_t *arena, size_t N, size_t p, int col0, int idx) {
-  npd_real_t *a = const_cast<npd_real_t *>(arena);
-  if (idx < NC) return (double)*(const npd_real_t *)npd_gaddr(a, N, p, col0 + idx);
-  const int j = idx - NC;
-  return (double)*(const float *)(npd_gaddr(a, N, p, col0 + NC + j / NPD_NPC) + (j % NPD_NPC) * 4);
-}
-#define NPD_F64_COL(T, stype, member, inst) npd_gread_real<NPB_##T##_NCARRY>(f64, N, p, NPD_SEC_COL(T, inst), NPB_F64_SLOT(stype, member))
-#define NPD_F64_COLK(T, stype, member, inst, k) npd_gread_real<NPB_##T##_NCARRY>(f64, N, p, NPD_SEC_COL(T, inst), NPB_F64_SLOT(stype, member) + (k))
-#define NPD_I32_COL(T, stype, member, inst) \
-  (*(const int32_t *)(npd_gaddr(const_cast<npd_real_t *>(f64), N, p, NPD_SEC_COL(T, inst) + NPB_##T##_NCARRY + (NPB_##T##_NOUT + NPB_I32_SLOT(stype, T, member)) / NPD_NPC) + \
-                      ((NPB_##T##_NOUT + NPB_I32_SLOT(stype, T, member)) % NPD_NPC) * 4))
 
 /* ---- step kernel: section stores through the pinned 32-bit-offset addressing of npd_stage.h.
  * bits of narrow member j of a section struct: outputs as float, then the int32 members */
@@ -196,14 +136,6 @@ __device__ __forceinline__ void npd_st_store_narrow_cols(const S &s, const npd_s
  * members named in the masks below are stored only if some lane's bits changed.  Which members are listed is a
  * performance choice only: the compare is on the bit patterns, so the arena always ends up with exactly the
  * bits a plain store would have written.  "old" is the copy of the section as it was staged in. */
-/* bit pattern of a value as it is stored (fp32 storage: after rounding to fp32) */
-__device__ __forceinline__ long long npd_real_bits(double v) {
-#ifdef NPB_BUILD_F32
-  return (long long)__float_as_int((float)v);
-#else
-  return __double_as_longlong(v);
-#endif
-}
 /* SKIP0 .. SKIP1: carried members that were not loaded this step and must not be stored (wave-uniform `skip`) */
 template <int NF, int NO, int NI, int SKIP0 = 0, int SKIP1 = 0, typename S, int SM = 0>
 __device__ __forceinline__ void npd_st_store_elide(const S &s, const S &old, const npd_stage_t &st, int col0, uint64_t fmask, bool skip = false) {
@@ -395,14 +327,6 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_step_primary_kernel(
     mp.member[q__] = (double)*(const npd_real_t *)npd_gaddr(f64, N, p, NPD_MP_COL(inst, member, q__)); } while (0)
 #define NPD_MP_STORE(inst, member, count) do { _Pragma("unroll") for (int q__ = 0; q__ < (count); q__++) \
     *(npd_real_t *)npd_gaddr(f64, N, p, NPD_MP_COL(inst, member, q__)) = (npd_real_t)mp.member[q__]; } while (0)
-/* the proper look's view of the table: scan membership folded into the comparison masks on the host side */
-struct npd_maint_screen_t {
-  double threshold[NPB_MAINT_NPARAM];
-  double cooldown_minutes[NPB_MAINT_NPARAM];
-  uint32_t want_gt, want_lt, want_eq, want_near, want_far;    /* bit q: row q fires on value > / < / == threshold, |value - threshold| < / >= 0.001 */
-};
-struct npd_maint_rule_consts_t { npb_params_t P; npb_maint_table_t T; npd_maint_screen_t S; npd_maint_log_t L; };
-#include "npd_record_log.h"
 /* one event site of a wave, possibly inside divergent code: the lanes with `want` take slots of the log (npd_record_log.h); the cursor
  * counts every event, and a slot at or past the capacity is not written */
 __device__ __forceinline__ void npd_maint_log(const npd_maint_log_t &L, bool want, const npb_maint_event_t &e) {
@@ -1154,24 +1078,6 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_operator_turbine_maint_kernel(np
   if (L.cursor) npd_maint_log_operator(L, ok, p, NPD_F64_COL(PRIM, npb_prim_t, sim_time, 0), unit, action, NPB_MAINT_EVENT_OPERATOR_TURBINE);
 }
 
-#ifndef NPB_BUILD_F32
-/* calibration aid for the HBM traffic counters: reads every arena column and writes it back unchanged,
- * with exactly the access shape of the step kernel (8 B per lane, one 512-B line per wave and column),
- * so that FETCH_SIZE / WRITE_SIZE can be scaled against a known byte count (2 * state_bytes * pitch) */
-__global__ __launch_bounds__(NPB_WAVE) void npb_touch_kernel(size_t N, double *__restrict__ f64) {
-  const size_t p = (size_t)blockIdx.x * NPB_WAVE + threadIdx.x;
-  { const size_t seg = N >> 32; N &= 0xffffffffu; if (seg) { f64 += (p / seg) * seg * (size_t)(NPB_TOTAL_COL64 - 1); N = seg; } }
-#pragma unroll 8
-  for (int k = 0; k < NPB_TOTAL_COL64; k++) { double v = f64[(size_t)k * N + p]; f64[(size_t)k * N + p] = v + 0.0; }
-}
-extern "C" void npb_launch_touch(size_t npad_seg, double *f64, hipStream_t stream) {
-  const size_t npad = NPD_NPAD(npad_seg);
-  dim3 grid((unsigned)(npad / NPB_WAVE)), block(NPB_WAVE);
-  hipLaunchKernelGGL(npb_touch_kernel, grid, block, 0, stream, npad_seg, f64);
-}
-#endif
-
-/* ---- host-side launchers: one table per storage type (npb_launchers_t), which npb_api.hip calls through */
 /* ---- automatic maintenance of the feedwater pumps, the steam generators and the condenser in ONE queue (npb_set_component_maintenance;
  * npd_component_auto.h): a launch of its own behind the PLAIN step kernel, which is the step kernel of a handle without any automatic
  * maintenance -- the step kernels do not know this rule.  One wave = 64 plants.  The wave first screens: is a check due on open orders,
@@ -1179,8 +1085,6 @@ extern "C" void npb_launch_touch(size_t npad_seg, double *f64, hipStream_t strea
  * last_check_time where a check fell due and leaves.  Otherwise the reference's order: AutoMaintenanceSystem.update carries out one due
  * order, the earliest created of any component; then the scan in the order of StateManager.maintenance_thresholds, FWP-1..4, SG-0..2,
  * the condenser, every created order numbered from the one counter maint.work_orders_created. */
-/* (Behind every other kernel of the file on purpose: kernels are laid out in the code object in source order, and the step kernels, which
- * bench.py times, keep the offsets they had before this one existed.) */
 __device__ __forceinline__ void npd_cmaint_values(const npd_real_t *f64c, size_t N, size_t p, int c, double dt, double *v) {
   npd_real_t *f64 = const_cast<npd_real_t *>(f64c);
   if (c == NPB_CMAINT_COND) {
@@ -1344,12 +1248,8 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_maint_all_kernel(const npd_maint
   if (!__any(work) && !scan_bits) return;
   npd_maint_all_rule(RC, side, MC, f64, N, p, t, work, scan_bits);
 }
-#ifdef NPB_BUILD_F32
-#define NPB_LAUNCHER(name) npb32_launch_##name
-#else
-#define NPB_LAUNCHER(name) npb_launch_##name
-#endif
 
+/* ---- host-side launchers: one table per storage type (npb_launchers_t), which npb_api.hip calls through */
 /* field access of the C ABI: one member of every plant <-> a contiguous buffer of double (real members) or
  * int32 (int members).  where = arena column, sub = narrow position inside the column, kind: 0 carried real,
  * 1 output real (stored as float), 2 int32 */
@@ -1397,7 +1297,7 @@ static void NPB_LAUNCHER(field_set)(void *arena, size_t npad, int col, int sub, 
 /* fp64-storage plants above which the sweep of a step (4 221 B per plant) is so far past the 256 MB Infinity Cache that streaming
  * state stores win (measured: even at 81 920, -5 % at 98 304, -10 % at 131 072); fp32 storage moves half the bytes */
 #define NPB_NT_STORE_ABOVE ((size_t)90112)
-/* plants (of either storage type) from which on npb_create segments the arena ("segmented arena" above), and between which npb_step gives
+/* plants (of either storage type) from which on npb_create segments the arena ("segmented arena", npd_arena.h), and between which npb_step gives
  * the batch to the four-wave kernel although its groups no longer fit at once.  Measured
  * (profiles/r3_segment_sweep.txt, r3_segment_size.txt): 65 536 plants 0.0906 ms against the one-wave kernel's 0.0956 on a one-block arena
  * (the four-wave kernel there: 0.0975); 49 152 0.0784 against the two-wave kernel's 0.0792, 40 960 level; 81 920 0.122 against 0.166;
@@ -1420,8 +1320,6 @@ static void npd_maint_fold_table(const npb_params_t *P, const npb_maint_table_t 
   H->tab[2 * NPB_MAINT_NPARAM] = always ? 1.0 : 0.0;
   H->tab[2 * NPB_MAINT_NPARAM + 1] = P->maint_check_interval_hours * 60;
 }
-/* the handle's maintenance side buffer: [rule constants, 256-byte slot][cache entries: npad x 4 pumps x {u32, float}] */
-#define NPD_MAINT_CONSTS_BYTES ((sizeof(npd_maint_rule_consts_t) + 255) / 256 * 256)
 static npd_maint_cache_t npd_maint_cache_of(void *maint_side, int32_t *counts, int n_plants, double *diag = nullptr, size_t diag_pitch = 0) {
   npd_maint_cache_t C;
   C.counts = counts; C.n_plants = n_plants; C.diag = diag; C.diag_pitch = diag_pitch;
@@ -1501,32 +1399,6 @@ static void NPB_LAUNCHER(maint_all)(size_t npad, void *arena, void *maint_side, 
   hipLaunchKernelGGL(npb_maint_all_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, (const npd_maint_rule_consts_t *)maint_side, side,
                      npd_maint_cache_of(maint_side, counts, n_plants, diag, diag_pitch), npad, (npd_real_t *)arena);
 }
-#ifndef NPB_BUILD_F32
-/* the maintenance side buffer does not depend on the storage type (npd_maint_rule_consts_t holds no npd_real_t): one copy of
- * these.  The rule's constants as the device reads them: host_out = npb_launch_maint_consts_bytes() bytes */
-extern "C" void npb_launch_maint_consts(const npb_params_t *P, const npb_maint_table_t *T, npd_maint_log_t log, void *host_out) {
-  npd_maint_rule_consts_t *RC = (npd_maint_rule_consts_t *)host_out;
-  memset(RC, 0, sizeof(*RC));
-  RC->P = *P; RC->T = *T; RC->L = log;
-  npd_maint_screen_t &S = RC->S;
-  for (int q = 0; q < NPB_MAINT_NPARAM; q++) {
-    S.threshold[q] = T->threshold[q];
-    S.cooldown_minutes[q] = T->cooldown_hours[q] * 60;
-    if (T->rank[q] < 0) continue;             /* not in the scan: no mask bit, never fires */
-    const int c = T->comparison[q];
-    const uint32_t bit = 1u << q;
-    if (c == NPB_CMP_GREATER_THAN || c == NPB_CMP_GREATER_EQUAL) S.want_gt |= bit;
-    if (c == NPB_CMP_LESS_THAN || c == NPB_CMP_LESS_EQUAL) S.want_lt |= bit;
-    if (c == NPB_CMP_GREATER_EQUAL || c == NPB_CMP_LESS_EQUAL) S.want_eq |= bit;
-    if (c == NPB_CMP_EQUALS) S.want_near |= bit;
-    if (c != NPB_CMP_GREATER_THAN && c != NPB_CMP_GREATER_EQUAL && c != NPB_CMP_LESS_THAN && c != NPB_CMP_LESS_EQUAL && c != NPB_CMP_EQUALS) S.want_far |= bit;
-  }
-}
-extern "C" size_t npb_launch_maint_consts_bytes(void) { return sizeof(npd_maint_rule_consts_t); }
-/* rule constants + cooldown cache (npd_maint_cache_of); a zeroed cache = "nothing known: look" */
-extern "C" size_t npb_launch_maint_side_bytes(size_t npad) { return NPD_MAINT_CONSTS_BYTES + (size_t)NPB_NUM_PUMPS * NPD_NPAD(npad) * (sizeof(float) + sizeof(uint32_t)); }
-extern "C" size_t npb_launch_maint_cache_offset(void) { return NPD_MAINT_CONSTS_BYTES; }
-#endif
 static void NPB_LAUNCHER(observe)(int mode, int n_plants, size_t npad, const void *arena, double *obs, hipStream_t stream) {
   dim3 grid((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), block(NPB_WAVE);
   hipLaunchKernelGGL(npb_observe_kernel, grid, block, 0, stream, mode, n_plants, npad, (const npd_real_t *)arena, obs);
@@ -1583,287 +1455,9 @@ static void NPB_LAUNCHER(operator_turbine_maint)(int n_plants, size_t npad, void
   O.action = action; O.unit = unit; O.success = success; O.n_plants = n_plants; O.turbine = turbine;
   hipLaunchKernelGGL(npb_operator_turbine_maint_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, O, L, npad, (npd_real_t *)arena);
 }
-static void NPB_LAUNCHER(sample)(const void *arena, size_t npad, const int *plan_dev, int n_fields, const npb_sample_row_t *side_dev, int n_rows,
-                                 const int32_t *ids_dev, int n_watched, double *out, hipStream_t stream);     /* behind every other kernel, at the end of the file */
-static void NPB_LAUNCHER(episode_records)(int n_plants, size_t npad, const void *arena, const uint8_t *done, const double *reward, const double *obs,
-                                          const uint32_t *trip_flags, npb_episode_counters_t C, const int32_t *start, int max_steps, int step,
-                                          const npb_episode_records_desc_t *D, const npb_maint_summary_desc_t *summary, const npb_record_stats_t *record_stats,
-                                          hipStream_t stream);     /* the same */
-static void NPB_LAUNCHER(column_stats_fold)(const void *arena, size_t npad, const npb_column_stats_t *S, int n_plants, hipStream_t stream);     /* the same */
-static void NPB_LAUNCHER(event_windows)(const void *arena, size_t npad, const npb_event_windows_t *W, int n_plants, int step, const int32_t *index,
-                                        const int32_t *len, const uint8_t *done, int max_steps, hipStream_t stream);     /* the same */
-static void NPB_LAUNCHER(task)(const void *arena, size_t npad, const npb_task_t *T, int n_plants, const int32_t *index, hipStream_t stream);     /* the same */
-static void NPB_LAUNCHER(features)(const void *arena, size_t npad, const npb_features_t *F, int n_plants, int mode, const int32_t *index, hipStream_t stream);     /* the same */
-static void NPB_LAUNCHER(controls)(void *arena, size_t npad, const npb_controls_t *C, const npb_params_t *P, int n_plants, const int32_t *index, hipStream_t stream);     /* the same */
-static void NPB_LAUNCHER(normalizer)(const void *arena, size_t npad, const npb_normalizer_t *Z, int n_plants, const int32_t *index, const double *reward,
-                                     hipStream_t stream);     /* the same */
 /* not const: clang emits a namespace-scope const into the device code too, where these host functions do not exist */
 extern "C" npb_launchers_t NPB_LAUNCHER(table) = {
   NPB_LAUNCHER(step), NPB_LAUNCHER(maint), NPB_LAUNCHER(observe), NPB_LAUNCHER(init), NPB_LAUNCHER(reset),
   NPB_LAUNCHER(field_get), NPB_LAUNCHER(field_set), NPB_LAUNCHER(gather), NPB_LAUNCHER(restore), NPB_LAUNCHER(episode),
   NPB_LAUNCHER(operator_maint), NPB_LAUNCHER(operator_component_maint), NPB_LAUNCHER(operator_turbine_maint), NPB_LAUNCHER(maint_all),
-  NPB_LAUNCHER(sample), NPB_LAUNCHER(episode_records), NPB_LAUNCHER(column_stats_fold), NPB_LAUNCHER(event_windows),
-  NPB_LAUNCHER(task), NPB_LAUNCHER(features), NPB_LAUNCHER(controls), NPB_LAUNCHER(normalizer),
 };
-#ifndef NPB_BUILD_F32
-/* npb_reset / npb_reset_reference / npb_restore: the episode counters (len, ret) and the carried start entries (start: -1, not from
- * the bank) of the plants of mask (NULL = every lane of the pitch); each column may be NULL */
-__global__ void npb_episode_clear_kernel(const uint8_t *__restrict__ mask, int32_t *__restrict__ len, double *__restrict__ ret, int32_t *__restrict__ index,
-                                         int32_t *__restrict__ start, int n_plants, int npad) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= npad || (mask && (p >= n_plants || !mask[p]))) return;
-  if (len) { len[p] = 0; index[p] += 1; }      /* (the index is allocated with the length) */
-  if (ret) ret[p] = 0.0;
-  if (start) start[p] = -1;
-}
-/* the component maintenance's side state (npd_component_auto.h) of the plants of mask (NULL = every lane of the pitch) as a freshly
- * constructed plant has it (npb_set_component_maintenance, npb_reset) */
-__global__ void npb_cmaint_init_kernel(double *state, size_t pitch, const uint8_t *__restrict__ mask, int n_plants) {
-  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= pitch || (mask && (p >= (size_t)n_plants || !mask[p]))) return;
-  npd_cmaint_init(state, pitch, p);
-}
-/* the side buffer of one handle: [the table as the device reads it, a 256-byte slot][NPB_CMAINT_SIDE_DOUBLES][pitch] doubles */
-#define NPD_CMAINT_CONSTS_BYTES ((sizeof(npd_cmaint_consts_t) + 255) / 256 * 256)
-extern "C" size_t npb_launch_cmaint_side_bytes(size_t pitch) { return NPD_CMAINT_CONSTS_BYTES + (size_t)NPB_CMAINT_SIDE_DOUBLES * pitch * sizeof(double); }
-extern "C" size_t npb_launch_cmaint_state_offset(void) { return NPD_CMAINT_CONSTS_BYTES; }
-extern "C" void npb_launch_cmaint_init(void *cm_side, size_t pitch, const uint8_t *mask, int n_plants, hipStream_t stream) {
-  hipLaunchKernelGGL(npb_cmaint_init_kernel, dim3((unsigned)((pitch + 255) / 256)), dim3(256), 0, stream,
-                     (double *)((char *)cm_side + NPD_CMAINT_CONSTS_BYTES), pitch, mask, n_plants);
-}
-extern "C" void npb_launch_episode_clear(const uint8_t *mask, int32_t *len, double *ret, int32_t *index, int32_t *start, int n_plants, size_t npad,
-                                         hipStream_t stream) {
-  const int n = (int)NPD_NPAD(npad);
-  hipLaunchKernelGGL(npb_episode_clear_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, mask, len, ret, index, start, n_plants, n);
-}
-/* the carried diagnostics rows (include/npb.h NPB_DIAG_CARRIED) of a diagnostics buffer into a packed [NPB_DIAG_NUM_CARRIED][pitch] copy in
- * table order: npb_snapshot, npb_set_start_bank */
-__global__ void npb_diag_carried_pack_kernel(const double *__restrict__ live, size_t live_pitch, double *__restrict__ packed, size_t packed_pitch,
-                                             size_t lanes) {
-  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= lanes) return;
-  int k = 0;
-#define NPB__X(row, fresh) packed[(size_t)(k++) * packed_pitch + p] = live[(size_t)(row) * live_pitch + p];
-  NPB_DIAG_CARRIED(NPB__X)
-#undef NPB__X
-}
-/* npb_reset / npb_reset_reference: the carried rows of the plants of mask (NULL = every lane below `lanes`) to values.v[k]; NaN = kept */
-__global__ void npb_diag_carried_put_kernel(double *__restrict__ live, size_t live_pitch, const uint8_t *__restrict__ mask, int n_plants, size_t lanes,
-                                            npb_diag_carried_values_t values) {
-  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= lanes || (mask && (p >= (size_t)n_plants || !mask[p]))) return;
-  int k = 0;
-#define NPB__X(row, fresh) { const double v = values.v[k++]; if (v == v) live[(size_t)(row) * live_pitch + p] = v; }
-  NPB_DIAG_CARRIED(NPB__X)
-#undef NPB__X
-}
-extern "C" void npb_launch_diag_carried_pack(const double *live, size_t live_pitch, double *packed, size_t packed_pitch, size_t lanes, hipStream_t stream) {
-  hipLaunchKernelGGL(npb_diag_carried_pack_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, live, live_pitch, packed, packed_pitch, lanes);
-}
-extern "C" void npb_launch_diag_carried_put(double *live, size_t live_pitch, const uint8_t *mask, int n_plants, size_t lanes,
-                                            npb_diag_carried_values_t values, hipStream_t stream) {
-  hipLaunchKernelGGL(npb_diag_carried_put_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, live, live_pitch, mask, n_plants, lanes,
-                     values);
-}
-/* the per-plant work-order summary folded from the event log (npb_set_maintenance_summary): its kernels and launchers */
-#include "npd_maint_summary.h"
-#endif
-/* the state log's sampling step for a watch list (npb_sampler_sample): one grid row per output row, lanes over the watched plants.
- * Row r < n_fields is an arena member, addressed as npb_gather_kernel addresses it with the plant ids[j] in place of the lane; the rows
- * behind are side rows (npb_sample_row_t): caller-owned buffers beside the arena.  Every value is widened to double: out[r * n_watched + j].
- * The row's descriptor is uniform over the block (scalar loads); consecutive ids read consecutive elements */
-__global__ void npb_sample_kernel(const npd_real_t *__restrict__ arena, size_t N, const int *__restrict__ plan, int n_fields,
-                                  const npb_sample_row_t *__restrict__ side, const int32_t *__restrict__ ids, double *__restrict__ out, int n_watched) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
-  if (j >= n_watched) return;
-  const size_t p = (size_t)ids[j];
-  double v;
-  if (r < n_fields) {
-    const int col = plan[3 * r], sub = plan[3 * r + 1], kind = plan[3 * r + 2];
-    NPD_SEGMENT(arena, N, p);
-    const char *e = (const char *)(arena + (size_t)col * N + p);
-    if (kind == 0) v = (double)*(const npd_real_t *)e;
-    else if (kind == 1) v = (double)*(const float *)(e + sub * 4);
-    else v = (double)*(const int32_t *)(e + sub * 4);
-  } else {
-    const npb_sample_row_t S = side[r - n_fields];
-    const int64_t e = (int64_t)p * S.plant_stride;
-    if (S.type == NPB_SAMPLE_F64) v = ((const double *)S.row)[e];
-    else if (S.type == NPB_SAMPLE_F32) v = (double)((const float *)S.row)[e];
-    else if (S.type == NPB_SAMPLE_I32) v = (double)((const int32_t *)S.row)[e];
-    else v = (double)((const uint8_t *)S.row)[e];
-  }
-  out[(size_t)r * n_watched + j] = v;
-}
-static void NPB_LAUNCHER(sample)(const void *arena, size_t npad, const int *plan_dev, int n_fields, const npb_sample_row_t *side_dev, int n_rows,
-                                 const int32_t *ids_dev, int n_watched, double *out, hipStream_t stream) {
-  const int block = n_watched <= 64 ? 64 : 256;      /* a short watch list: one wave per row, no idle waves */
-  hipLaunchKernelGGL(npb_sample_kernel, dim3((n_watched + block - 1) / block, n_rows), dim3(block), 0, stream, (const npd_real_t *)arena, npad, plan_dev,
-                     n_fields, side_dev, ids_dev, out, n_watched);
-}
-/* THE reader of a per-plant column (npb_colstat_col_t, npb_kernels.h): one value of plant p, widened to double as npb_sample_kernel widens
- * it.  f64 / N: the arena and its pitch AFTER NPD_SEGMENT (the fold applies it per thread, the windows and the task per wave: that stays
- * with the kernels).  The call site names how the descriptor arrives, because this compiler's code depends on it: a copy of the fold's
- * (D = npb_colstat_col_t) keeps its side-row loads global_load_*, where a reference makes them flat_load_* with lgkmcnt waits; a reference
- * into the kernel's argument (D = const npb_colstat_col_t &) keeps the windows' and the task's loads where they are, where a copy
- * reorders them (tools/compare_step_kernels.py shows either) */
-template <class D> __device__ __forceinline__ double npd_column_read(const npd_real_t *f64, size_t N, size_t p, D C) {
-  if (C.kind < 3) {
-    const char *e = (const char *)(f64 + (size_t)C.col * N + p);
-    if (C.kind == 0) return (double)*(const npd_real_t *)e;
-    if (C.kind == 1) return (double)*(const float *)(e + C.sub * 4);
-    return (double)*(const int32_t *)(e + C.sub * 4);
-  }
-  const int64_t e = (int64_t)p * C.plant_stride;
-  const int type = C.kind - 3;
-  if (type == NPB_SAMPLE_F64) return ((const double *)C.row)[e];
-  if (type == NPB_SAMPLE_F32) return (double)((const float *)C.row)[e];
-  if (type == NPB_SAMPLE_I32) return (double)((const int32_t *)C.row)[e];
-  return (double)((const uint8_t *)C.row)[e];
-}
-
-/* npb_set_episode_records: the record of every episode that ends on this step, behind the step kernel, the rule and the summary fold and
- * BEFORE the episode kernel, which then does the bookkeeping and the restore as it always does: here the arena, the step's output columns
- * and the carried counters still describe the episode that ended.  Nothing of them is written */
-struct npd_episode_records_t {
-  npb_episode_records_desc_t D;                               /* the caller's columns and cursor */
-  const int32_t *len; const double *ret; const int32_t *index; const int32_t *start;      /* carried [pitch]; start NULL = no bank */
-  double *s_first_created, *s_first_completed; int32_t *s_n_created, *s_n_completed;      /* the handle's summary tables [n_keys][n_plants], or NULL */
-  int n_keys;
-  int max_steps;                                              /* 0 = no limit */
-  int step;                                                   /* npb_step calls since the records were switched on */
-  const npb_record_stats_t *stats;                            /* device: the handle's column statistics and the record-side columns that take them
-                                                               * (npb_set_episode_record_stats), read by ended lanes only; NULL = not taken */
-};
-__global__ __launch_bounds__(NPB_WAVE) void npb_episode_records_kernel(int n_plants, size_t N, const npd_real_t *__restrict__ f64, const uint8_t *__restrict__ done,
-                                                                       const double *__restrict__ reward, const double *__restrict__ obs,
-                                                                       const uint32_t *__restrict__ trip_flags, npd_episode_records_t R) {
-  const size_t block_base = (size_t)blockIdx.x * NPB_WAVE;
-  NPD_SEGMENT(f64, N, block_base);
-  const size_t p = block_base + threadIdx.x;
-  bool terminated = false, truncated = false;
-  int32_t len = 0;
-  double ret = 0.0;
-  if (p < (size_t)n_plants) {           /* the outcome as npb_episode_kernel decides it, behind this kernel on the same columns */
-    terminated = done[p] != 0;
-    len = R.len[p] + 1;
-    ret = reward ? R.ret[p] + reward[p] : R.ret[p];
-    truncated = R.max_steps > 0 && len >= R.max_steps && !terminated;     /* termination wins */
-  }
-  const bool ended = terminated || truncated;
-  if (!__any(ended)) return;
-  const npd_log_slots_t s = npd_log_reserve(R.D.cursor, ended);      /* the ended lanes' slots (npd_record_log.h) */
-  const int lane = threadIdx.x;
-  const uint32_t cap = (uint32_t)R.D.capacity;
-  const uint32_t slot = npd_log_slot(s);
-  const bool store = ended && slot < cap;
-  if (store) {
-    R.D.plant[slot] = (int32_t)p;
-    R.D.episode[slot] = R.index[p];
-    R.D.start[slot] = R.start ? R.start[p] : -1;
-    R.D.length[slot] = len;
-    R.D.flags[slot] = (terminated ? 1 : 0) | (truncated ? 2 : 0);
-    R.D.trip_flags[slot] = trip_flags ? trip_flags[p] : 0u;
-    R.D.step[slot] = R.step;
-    R.D.ret[slot] = ret;
-    R.D.end_time[slot] = NPD_F64_COL(PRIM, npb_prim_t, sim_time, 0);
-  }
-  if (R.D.final_obs && obs) {           /* the terminal observation: the wave's rows are consecutive in obs, and so are its slots */
-#pragma unroll
-    for (int k = 0; k < NPB_OBS_DIM; k++) {
-      const int idx = k * NPB_WAVE + lane, r = idx / NPB_OBS_DIM, c = idx % NPB_OBS_DIM;
-      const uint32_t slot_r = npd_log_slot(s, r);
-      if (((s.rows >> r) & 1u) && slot_r < cap) R.D.final_obs[(size_t)slot_r * NPB_OBS_DIM + c] = obs[block_base * NPB_OBS_DIM + idx];
-    }
-  }
-  if (!ended) return;
-  const bool copy = store && R.D.first_created;
-  for (int j = 0; R.s_first_created && j < R.n_keys; j++) {  /* the plant's summary cells as of this step (the fold ran before this launch), then "never" and 0 again */
-    const size_t cell = (size_t)j * (size_t)n_plants + p;
-    if (copy) {
-      const size_t out = (size_t)j * (size_t)cap + slot;
-      R.D.first_created[out] = R.s_first_created[cell];
-      R.D.first_completed[out] = R.s_first_completed[cell];
-      R.D.n_created[out] = R.s_n_created[cell];
-      R.D.n_completed[out] = R.s_n_completed[cell];
-    }
-    if (R.D.clear_summary) {
-      ((uint64_t *)R.s_first_created)[cell] = 0x7ff0000000000000ull;
-      ((uint64_t *)R.s_first_completed)[cell] = 0x7ff0000000000000ull;
-      R.s_n_created[cell] = 0;
-      R.s_n_completed[cell] = 0;
-    }
-  }
-  if (!R.stats) return;
-  if (store && R.stats->cause) R.stats->cause[slot] = (int32_t)R.stats->task_cause[p];      /* why it ended: the task's cause word (npb_set_episode_record_task) */
-  /* the plant's column statistics as of this step (their fold ran before this launch), then the empty values again (npd_column_stats.h) */
-  const npb_column_stats_t st = R.stats->st;
-  const npb_episode_record_stats_desc_t rs = R.stats->rs;
-  if (store && rs.n_samples) rs.n_samples[slot] = st.n_samples[p];
-  if (rs.clear) st.n_samples[p] = 0;
-#define NPD_RECORD_STAT(name, empty) \
-    if (store && rs.name) rs.name[(size_t)c * (size_t)cap + slot] = st.name[cell]; \
-    if (rs.clear && st.name) st.name[cell] = (empty);
-  for (int c = 0; c < st.n_cols; c++) {
-    const size_t cell = (size_t)c * (size_t)n_plants + p;
-    NPD_RECORD_STAT(min, __longlong_as_double(0x7ff0000000000000ll))
-    NPD_RECORD_STAT(max, __longlong_as_double((long long)0xfff0000000000000ull))
-    NPD_RECORD_STAT(sum, 0.0)
-    NPD_RECORD_STAT(sumsq, 0.0)
-    NPD_RECORD_STAT(last, __longlong_as_double(0x7ff8000000000000ll))
-    NPD_RECORD_STAT(first_beyond, __longlong_as_double(0x7ff0000000000000ll))
-    NPD_RECORD_STAT(n_beyond, 0)
-  }
-#undef NPD_RECORD_STAT
-}
-/* C: the handle's carried counters; start: its carried bank entries or NULL; summary: the handle's summary while the records copy or clear it, else NULL;
- * record_stats: the handle's device copy of its column statistics and the record-side columns that take them, or NULL */
-static void NPB_LAUNCHER(episode_records)(int n_plants, size_t npad, const void *arena, const uint8_t *done, const double *reward, const double *obs,
-                                          const uint32_t *trip_flags, npb_episode_counters_t C, const int32_t *start, int max_steps, int step,
-                                          const npb_episode_records_desc_t *D, const npb_maint_summary_desc_t *summary, const npb_record_stats_t *record_stats,
-                                          hipStream_t stream) {
-  npd_episode_records_t R;
-  R.stats = record_stats;
-  R.D = *D; R.len = C.len; R.ret = C.ret; R.index = C.index; R.start = start; R.max_steps = max_steps; R.step = step;
-  R.s_first_created = summary ? summary->first_created : nullptr; R.s_first_completed = summary ? summary->first_completed : nullptr;
-  R.s_n_created = summary ? summary->n_created : nullptr; R.s_n_completed = summary ? summary->n_completed : nullptr;
-  R.n_keys = summary ? summary->n_keys : 0;
-  hipLaunchKernelGGL(npb_episode_records_kernel, dim3((unsigned)(NPD_NPAD(npad) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream, n_plants, npad,
-                     (const npd_real_t *)arena, done, reward, obs, trip_flags, R);
-}
-
-/* the per-plant column statistics (npb_set_column_stats): the fold kernel, the clear kernel and their launchers */
-#include "npd_column_stats.h"
-
-/* state windows around events (npb_set_event_windows): the per-step kernel, the clear kernel and their launchers */
-#include "npd_event_windows.h"
-
-/* the caller's reward terms and termination rules (npb_set_task): the per-step kernel and its launcher */
-#include "npd_task.h"
-
-/* the caller's policy inputs (npb_set_features): the frame-stack kernel and its launcher */
-#include "npd_features.h"
-
-/* the caller's policy outputs (npb_set_controls): the decode kernel in front of the step and its launcher */
-#include "npd_controls.h"
-
-/* running observation and reward normalisation (npb_set_normalizer): the partials kernel of a fold, the reward kernel and their launchers */
-#include "npd_normalizer.h"
-
-#ifndef NPB_BUILD_F32
-/* npb_task_clear, npb_features_clear, npb_controls_clear: the plants of mask (NULL = all) unprimed in that attachment's `primed` column --
- * the task's next DELTA samples are 0, the features' next frame fills every slot, the controls' next step starts a new hold; the same
- * for either storage type (compiled once) */
-__global__ __launch_bounds__(256) void npb_unprime_kernel(int32_t *__restrict__ primed, const uint8_t *__restrict__ mask, int n_plants) {
-  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= (size_t)n_plants || (mask && !mask[p])) return;
-  primed[p] = 0;
-}
-extern "C" void npb_launch_unprime(int32_t *primed, const uint8_t *mask, int n_plants, hipStream_t stream) {
-  hipLaunchKernelGGL(npb_unprime_kernel, dim3((unsigned)((n_plants + 255) / 256)), dim3(256), 0, stream, primed, mask, n_plants);
-}
-
-/* the rollout (npb_set_rollout): the two kernels around the step, the cut, the advantages and their launchers; none touches the arena,
- * so they too are compiled once */
-#include "npd_rollout.h"
-#endif

@@ -7,15 +7,10 @@
  * column's descriptor is uniform over the block (scalar loads), consecutive lanes are consecutive plants, so the value and every table row
  * coalesce (a side row with a plant stride, such as an info column, costs what that stride costs).  A cell belongs to one thread and folds
  * are ordered by the stream: no atomics, no LDS.  min / max / first_beyond are stored only when they change; the plant clock is read only
- * on the step a cell first goes beyond its limit.  Included behind every other kernel of npb_kernels.hip and compiled with it for either
- * storage type: it reads the arena. */
+ * on the step a cell first goes beyond its limit.  Part of npb_attachments.hip, compiled for either
+ * storage type: it reads the arena.  The clear kernel does not: npb_storage_free.hip. */
 #ifndef NPD_COLUMN_STATS_H
 #define NPD_COLUMN_STATS_H
-
-#define NPD_COLSTAT_BLOCK 256
-#define NPD_COLSTAT_POS_INF __longlong_as_double(0x7ff0000000000000ll)
-#define NPD_COLSTAT_NEG_INF __longlong_as_double((long long)0xfff0000000000000ull)
-#define NPD_COLSTAT_NAN __longlong_as_double(0x7ff8000000000000ll)
 
 __global__ __launch_bounds__(NPD_COLSTAT_BLOCK) void npb_column_stats_fold_kernel(const npd_real_t *__restrict__ f64, size_t N, npb_column_stats_t S,
                                                                                   int n_plants) {
@@ -42,27 +37,4 @@ static void NPB_LAUNCHER(column_stats_fold)(const void *arena, size_t npad, cons
   hipLaunchKernelGGL(npb_column_stats_fold_kernel, dim3((unsigned)((n_plants + NPD_COLSTAT_BLOCK - 1) / NPD_COLSTAT_BLOCK), (unsigned)S->n_cols),
                      dim3(NPD_COLSTAT_BLOCK), 0, stream, (const npd_real_t *)arena, npad, *S, n_plants);
 }
-
-#ifndef NPB_BUILD_F32
-/* npb_column_stats_clear: the cells of the plants of mask (NULL = all) back to the empty values, over the fold's grid; the same for either
- * storage type (compiled once) */
-__global__ __launch_bounds__(NPD_COLSTAT_BLOCK) void npb_column_stats_clear_kernel(npb_column_stats_t S, const uint8_t *__restrict__ mask, int n_plants) {
-  const int c = blockIdx.y;
-  const size_t p = (size_t)blockIdx.x * NPD_COLSTAT_BLOCK + threadIdx.x;
-  if (p >= (size_t)n_plants || (mask && !mask[p])) return;
-  const size_t cell = (size_t)c * (size_t)n_plants + p;
-  if (S.min) S.min[cell] = NPD_COLSTAT_POS_INF;
-  if (S.max) S.max[cell] = NPD_COLSTAT_NEG_INF;
-  if (S.sum) S.sum[cell] = 0.0;
-  if (S.sumsq) S.sumsq[cell] = 0.0;
-  if (S.last) S.last[cell] = NPD_COLSTAT_NAN;
-  if (S.first_beyond) S.first_beyond[cell] = NPD_COLSTAT_POS_INF;
-  if (S.n_beyond) S.n_beyond[cell] = 0;
-  if (c == 0) S.n_samples[p] = 0;
-}
-extern "C" void npb_launch_column_stats_clear(const npb_column_stats_t *S, const uint8_t *mask, int n_plants, hipStream_t stream) {
-  hipLaunchKernelGGL(npb_column_stats_clear_kernel, dim3((unsigned)((n_plants + NPD_COLSTAT_BLOCK - 1) / NPD_COLSTAT_BLOCK), (unsigned)S->n_cols),
-                     dim3(NPD_COLSTAT_BLOCK), 0, stream, *S, mask, n_plants);
-}
-#endif
 #endif

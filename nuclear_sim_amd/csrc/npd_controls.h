@@ -20,7 +20,7 @@
  * The state goes through NPD_SEGMENT and the per-member addresses the operator-maintenance kernels use, for either storage type and the
  * segmented arena.  A lane stores a member only where the bits it would store differ from the bits it loaded: a plant whose actuators
  * do not move has nothing stored to it; under float storage a moved member is rounded to float at this store (as npb_set_field rounds).
- * No scratch, no atomics.  Included behind every other kernel of npb_kernels.hip and compiled with it for either storage type. */
+ * No scratch, no atomics.  Part of npb_attachments.hip, compiled for either storage type. */
 #ifndef NPD_CONTROLS_H
 #define NPD_CONTROLS_H
 

@@ -9,8 +9,8 @@
  * triggers) are uniform over the launch: scalar loads.  A wave none of whose lanes captures ends there.  Otherwise its capturing lanes take
  * consecutive slots in plant order with one atomic add (npd_record_log.h), and for each of them in turn all 64
  * lanes copy its window: the reads walk the ring with the plant stride (one line per element, whoever reads them), the stores into
- * `values` are contiguous.  No LDS.  Included behind every other kernel of npb_kernels.hip and compiled with it for either storage type: it
- * reads the arena. */
+ * `values` are contiguous.  No LDS.  Part of npb_attachments.hip, compiled for either storage type: it
+ * reads the arena.  The clear kernel does not: npb_storage_free.hip. */
 #ifndef NPD_EVENT_WINDOWS_H
 #define NPD_EVENT_WINDOWS_H
 
@@ -123,18 +123,4 @@ static void NPB_LAUNCHER(event_windows)(const void *arena, size_t npad, const np
   hipLaunchKernelGGL(npb_event_windows_kernel, dim3((unsigned)((n_plants + NPB_WAVE - 1) / NPB_WAVE)), dim3(NPB_WAVE), 0, stream,
                      (const npd_real_t *)arena, npad, *W, n_plants, step, index, len, done, max_steps);
 }
-
-#ifndef NPB_BUILD_F32
-/* npb_event_windows_clear, and the start of npb_set_event_windows: the plants of mask (NULL = all) unprimed, their rings empty, an armed
- * capture dropped; the same for either storage type (compiled once) */
-__global__ __launch_bounds__(256) void npb_event_windows_clear_kernel(npb_event_windows_t W, const uint8_t *__restrict__ mask, int n_plants) {
-  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= (size_t)n_plants || (mask && !mask[p])) return;
-  W.valid[p] = 0;
-  W.due[p] = -1;
-}
-extern "C" void npb_launch_event_windows_clear(const npb_event_windows_t *W, const uint8_t *mask, int n_plants, hipStream_t stream) {
-  hipLaunchKernelGGL(npb_event_windows_clear_kernel, dim3((unsigned)((n_plants + 255) / 256)), dim3(256), 0, stream, *W, mask, n_plants);
-}
-#endif
 #endif

@@ -26,7 +26,7 @@
  * chunk's load, so it issues only when that load has returned, and loads return in order: every load of the same or an earlier chunk
  * has returned by then.  The loads still in flight, of later chunks, touch only elements above the chunk being stored.  The copy to `final` and the refill of pass B and of the priming go per concerned plant, all 64 lanes on its K x C contiguous
  * elements, as the event windows copy a captured lane's window.
- * No scratch, no atomics.  Included behind every other kernel of npb_kernels.hip and compiled with it for either storage type: it reads
+ * No scratch, no atomics.  Part of npb_attachments.hip, compiled for either storage type: it reads
  * the arena.
  * NOT here (include/npb.h says so too): the terminal stack in the episode records, half-precision output, a delta or rate kind (the
  * stack carries it).  Running statistics updated on the device are the normaliser's (npd_normalizer.h): it rewrites `ref` and `scale`
@@ -38,8 +38,6 @@ enum { NPD_FEATURES_STEP = 0, NPD_FEATURES_RESTART = 1, NPD_FEATURES_PRIME = 2 }
 #define NPD_FEATURES_CHUNK 16      /* columns asked for together: 2 x 16 doubles in registers */
 #define NPD_FEATURES_GROUP 8       /* chunks of the walk whose loads are in flight together */
 #define NPD_FEATURES_ROW (NPB_FEATURES_COLS_MAX + 1)
-
-template <typename OUT, int W> struct alignas(sizeof(OUT) * W) npd_features_vec { OUT x[W]; };
 
 /* one column's value from its raw sample(s): the statement's transform, in its order */
 __device__ __forceinline__ double npd_feature_transform(const npb_feature_col_t &D, double v, double ref) {

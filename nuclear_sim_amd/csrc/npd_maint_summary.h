@@ -1,7 +1,7 @@
 /* npd_maint_summary.h -- the per-plant work-order summary (npb_set_maintenance_summary, include/npb_maint.h): the maintenance event log
  * folded into first-created / first-completed times and created / completed counts per (key, plant).  What the data-gen runner returns of a
  * finished scenario (maintenance_scenario_runner.py:431-468) and what the timing optimiser reads of a probe run (timing_optimizer.py:273-320),
- * kept on the device.  The same for either storage type: a record's time is fp64 under both (compiled once, npb_kernels.hip).
+ * kept on the device.  The same for either storage type: a record's time is fp64 under both (compiled once, npb_storage_free.hip).
  *
  * One launch of a fixed grid: the host does not know the cursor, so every thread reads the two device words that bound the fold and strides
  * over the records between them.  Counts move by integer atomic adds, times by an unsigned 64-bit atomic minimum on the double's bit pattern

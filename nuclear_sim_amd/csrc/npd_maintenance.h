@@ -24,6 +24,7 @@
 #include "npd_common.h"
 #include "npd_feedwater.h"
 #include "../../include/npb_maint.h"
+#include "npb_kernels.h"      /* npd_maint_log_t */
 
 /* action types the lubrication system's dispatcher has a handler for (include/npb_maint.h, third column) */
 static constexpr uint32_t NPD_MA_HANDLER_MASK = 0u
@@ -338,6 +339,17 @@ struct npd_maint_cache_t { npd_u32x4 *entry;      /* [pitch][2]: pumps 0,1 | pum
                            int32_t *counts;       /* the caller's maintenance_actions_performed column (npb_set_maintenance_count_buffer), or NULL */
                            int n_plants;
                            double *diag; size_t diag_pitch;   /* npb_set_diagnostics buffer (the maintenance flags of NPB_DIAG_PUMP_*), or NULL */ };
+/* ---- the rule's constants in device memory (npb_launch_maint_consts writes them, npb_step uploads them when they change): the
+ * parameters, the table, the proper look's view of it and the event log's descriptor */
+/* the proper look's view of the table: scan membership folded into the comparison masks on the host side */
+struct npd_maint_screen_t {
+  double threshold[NPB_MAINT_NPARAM];
+  double cooldown_minutes[NPB_MAINT_NPARAM];
+  uint32_t want_gt, want_lt, want_eq, want_near, want_far;    /* bit q: row q fires on value > / < / == threshold, |value - threshold| < / >= 0.001 */
+};
+struct npd_maint_rule_consts_t { npb_params_t P; npb_maint_table_t T; npd_maint_screen_t S; npd_maint_log_t L; };
+/* the handle's maintenance side buffer: [rule constants, 256-byte slot][cache entries: npad x 4 pumps x {u32, float}] */
+#define NPD_MAINT_CONSTS_BYTES ((sizeof(npd_maint_rule_consts_t) + 255) / 256 * 256)
 __device__ __forceinline__ npd_u32x4 npd_maint_cache_fetch(const npd_maint_cache_t &C, size_t p, int half) {
   npd_u32x4 v;
   asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(C.entry + p * 2 + half) : "memory");

@@ -19,7 +19,7 @@
  * With the return stream (the last stream) the same kernel forms ret[p] = (carry ? ret * gamma : 0.0) + r, stores it, and folds it.
  *
  * Reward kernel, behind the finish, one lane per plant: norm_reward = clip(r * rscale), ended, primed, seen; frozen, when the partials
- * kernel has not run, it carries ret itself.  It reads nothing of the arena and is compiled once.
+ * kernel has not run, it carries ret itself.  It reads nothing of the arena and is compiled once (npb_storage_free.hip).
  * No atomics, no scratch.
  * NOT here (include/npb.h says so too): statistics over fresh frames, per-plant statistics, an exponential moving average, half types,
  * synchronising shards on the device, BITS or setpoint-error columns. */
@@ -29,14 +29,6 @@
 
 #define NPD_NORM_CHUNK 16      /* streams whose samples a lane asks for together */
 #define NPD_NORM_PASS 8        /* streams whose d and q stand in LDS together */
-
-/* the discounted return of plant p behind this step's reward r: the statement's carry, ret * gamma rounded before the sum */
-__device__ __forceinline__ double npd_normalizer_return(const npb_normalizer_t &Z, size_t p, const int32_t *__restrict__ index, double r) {
-  const int32_t seen = Z.seen[p];
-  const bool carry = Z.primed[p] && (index ? index[p] : seen) == seen && !Z.ended[p];
-  const double kept = Z.ret[p] * Z.gamma;
-  return (carry ? kept : 0.0) + r;
-}
 
 __global__ __launch_bounds__(NPD_TREE) void npb_normalizer_partials_kernel(const npd_real_t *__restrict__ f64, size_t N, npb_normalizer_t Z, int n_plants,
                                                                            const int32_t *__restrict__ index, const double *__restrict__ reward) {
@@ -103,27 +95,4 @@ static void NPB_LAUNCHER(normalizer)(const void *arena, size_t npad, const npb_n
   const dim3 grid((unsigned)((n_plants + NPD_TREE - 1) / NPD_TREE)), block(NPD_TREE);
   hipLaunchKernelGGL(npb_normalizer_partials_kernel, grid, block, 0, stream, (const npd_real_t *)arena, npad, *Z, n_plants, index, reward);
 }
-
-#ifndef NPB_BUILD_F32
-/* the same for either storage type (compiled once): nothing of the arena */
-__global__ __launch_bounds__(256) void npb_normalizer_reward_kernel(npb_normalizer_t Z, int n_plants, const int32_t *__restrict__ index,
-                                                                    const double *__restrict__ reward, const uint8_t *__restrict__ done, int carry) {
-  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= (size_t)n_plants) return;
-  const double r = reward[p];
-  if (carry) Z.ret[p] = npd_normalizer_return(Z, p, index, r);
-  double y = r * Z.scale[Z.n_streams - 1];
-  const double lo = -Z.clip;
-  y = y < lo ? lo : y;
-  y = y > Z.clip ? Z.clip : y;
-  Z.norm_reward[p] = y;
-  Z.ended[p] = done[p] != 0;
-  Z.primed[p] = 1;
-  if (index) Z.seen[p] = index[p];
-}
-extern "C" void npb_launch_normalizer_reward(const npb_normalizer_t *Z, int n_plants, const int32_t *index, const double *reward, const uint8_t *done,
-                                             int carry, hipStream_t stream) {
-  hipLaunchKernelGGL(npb_normalizer_reward_kernel, dim3((unsigned)((n_plants + 255) / 256)), dim3(256), 0, stream, *Z, n_plants, index, reward, done, carry);
-}
-#endif
 #endif

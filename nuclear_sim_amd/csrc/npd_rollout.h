@@ -3,7 +3,7 @@
  * nuclear_sim_amd/rollout.py states it in numpy; this file produces its bits: the recurrence runs in double with the product rounded
  * before the sum (-ffp-contract=off), the bootstrap and the carry are selects, the narrowing is the hardware's round-to-nearest-even.
  *
- * FOUR kernels, none of which touches the arena: compiled once, the same for either storage type (as npb_unprime_kernel).
+ * FOUR kernels, none of which touches the arena: compiled once, the same for either storage type (npb_storage_free.hip).
  * pre (in front of the controls kernel): three contiguous regions -- the features' out, the controls' in, the extras input -- into slot t
  *   in ONE launch: a flat grid-stride copy, consecutive lanes on consecutive 16-byte pieces where a region's two addresses allow (the
  *   launcher looks at them: a slot of an odd plant count x an odd cell count starts on 8 or 4 bytes), the words past the last whole piece

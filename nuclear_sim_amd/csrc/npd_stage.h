@@ -34,7 +34,7 @@
 
 /* Storage type of the fp64 state columns in HBM.  The arithmetic is fp64 either way; a build with
  * -DNPB_BUILD_F32 keeps the arena in fp32 (BASELINE config 5, "fp32 mixed precision"): half the bytes, state
- * rounded to fp32 at every store.  npb_kernels.hip is compiled once per storage type (Makefile). */
+ * rounded to fp32 at every store.  npb_kernels.hip and npb_attachments.hip are compiled once per storage type (Makefile). */
 #ifdef NPB_BUILD_F32
 typedef float npd_real_t;
 #else

@@ -8,8 +8,8 @@
  * consecutive plants in every column read and written.  The descriptors (terms, rules) are uniform over the launch: scalar loads.  A
  * thread first asks for everything it reads -- every term's column, its second column, its previous sample, every rule's column, the
  * bookkeeping words -- and stores afterwards: at one wave per SIMD nothing else hides a load's latency (npd_event_windows.h).  The loops
- * are unrolled over the maxima with wave-uniform guards, so the arrays stay in registers.  No LDS, no atomics.  Included behind every
- * other kernel of npb_kernels.hip and compiled with it for either storage type: it reads the arena. */
+ * are unrolled over the maxima with wave-uniform guards, so the arrays stay in registers.  No LDS, no atomics.  Part of
+ * npb_attachments.hip, compiled for either storage type: it reads the arena. */
 #ifndef NPD_TASK_H
 #define NPD_TASK_H
 

@@ -10,6 +10,9 @@
 #define NPD_TURBINE_H
 #include "npd_common.h"
 #include "npd_lube.h"
+#ifndef NPD_STAMP
+#define NPD_STAMP(k)      /* the phase stamps are the stamped build of npb_kernels.hip's, which defines this in front of its includes */
+#endif
 
 /* Antoine-form saturation temperature used by the turbine and condenser-side helpers
  * stage_system.py:458-466, enhanced_physics.py:1295-1303 */

@@ -1,13 +1,15 @@
-"""Are the step kernels of this tree, instruction for instruction, those of another checkout?
+"""Are the step kernels of this tree, instruction for instruction, those of another checkout?  And every other kernel built with their flags?
 
     python tools/compare_step_kernels.py OTHER_TREE [--keep DIR]
 
-Compiles nuclear_sim_amd/csrc/npb_kernels.hip of both trees for the device only (each tree's own HIPFLAGS, read from its
-csrc/Makefile, -S, both storage builds) with -Rpass-analysis=kernel-resource-usage, and compares every function whose name contains "npb_step" or "npd_maint_rule_for_wave" -- the
-step kernels bench.py times and the rule they call -- by its assembly text (comments and debug directives dropped; local labels
+Compiles, of both trees, every unit that the tree's csrc/Makefile builds with HIPFLAGS through its two pattern rules (the <unit>_f64.o and
+<unit>_f32.o of `make print-objects`; a tree without that target builds npb_kernels.hip alone that way) for the device only (each tree's own
+HIPFLAGS, read from its csrc/Makefile, -S) with -Rpass-analysis=kernel-resource-usage, and pools the functions per storage build: which
+unit a function lives in is not compared.  Every function whose name contains "npb_step" or "npd_maint_rule_for_wave" -- the
+step kernels bench.py times and the rule they call -- is compared by its assembly text (comments and debug directives dropped; local labels
 .LBB<f>_<n> / .Ltmp<n> stripped of the function's ordinal in the file, which moves when a kernel is added elsewhere) and by its
-resource table (registers, spills, scratch, occupancy, LDS).  Lists the other functions that changed or are new.  Exit status 1 if a
-step kernel differs.  Needs hipcc, no GPU.
+resource table (registers, spills, scratch, occupancy, LDS).  So is every other pooled function: the changed, the new and the lost ones are
+listed.  Exit status 1 if a step kernel differs.  Needs hipcc and make, no GPU.
 """
 import os
 import re
@@ -26,12 +28,39 @@ def makefile_flags(tree):
     return flags + ["--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage"]
 
 
-def compile_tree(tree, out, storage):
+def makefile_objects(tree):
+    """the tree's object list as its csrc/Makefile prints it (`make print-objects`), or None for a tree whose Makefile has no such target"""
+    make = subprocess.run(["make", "-s", "-C", os.path.join(tree, "nuclear_sim_amd", "csrc"), "print-objects"], capture_output=True, text=True)
+    return make.stdout.split() if make.returncode == 0 else None
+
+
+def units(tree, storage):
+    """the sources the tree's Makefile compiles with HIPFLAGS for this storage build"""
+    objects = makefile_objects(tree)
+    if objects is None:
+        return ["npb_kernels.hip"]
+    return [o[:-len("_%s.o" % storage)] + ".hip" for o in objects if o.endswith("_%s.o" % storage)]
+
+
+def compile_unit(tree, out, storage, unit):
     src = os.path.join(tree, "nuclear_sim_amd", "csrc")
-    asm, rem = os.path.join(out, storage + ".s"), os.path.join(out, storage + ".remarks")
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + makefile_flags(tree) + (["-DNPB_BUILD_F32"] if storage == "f32" else []) + ["-o", asm, "npb_kernels.hip"]
+    stem = os.path.join(out, "%s_%s" % (unit[:-len(".hip")], storage))
+    asm, rem = stem + ".s", stem + ".remarks"
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + makefile_flags(tree) + (["-DNPB_BUILD_F32"] if storage == "f32" else []) + ["-o", asm, unit]
     with open(rem, "w") as f:
         return subprocess.Popen(cmd, cwd=src, stderr=f), asm, rem
+
+
+def pooled(jobs):
+    """the functions and resource tables of one tree's units of one storage build, as one pool each"""
+    fn, res = {}, {}
+    for _p, asm, rem in jobs:
+        for k, v in functions(asm).items():
+            if k in fn:
+                raise SystemExit("%s is defined by two units of one build: %s" % (k, asm))
+            fn[k] = v
+        res.update(resources(rem))
+    return fn, res
 
 
 def functions(path):
@@ -64,21 +93,25 @@ def main(argv):
     for tag, tree in (("other", other), ("this", ROOT)):
         for st in ("f64", "f32"):
             d = os.path.join(keep, tag); os.makedirs(d, exist_ok=True)
-            jobs[(tag, st)] = compile_tree(tree, d, st)
-    for (tag, st), (p, _a, _r) in jobs.items():
-        if p.wait() != 0:
-            raise SystemExit("compiling the %s tree (%s) failed: see %s" % (tag, st, jobs[(tag, st)][2]))
+            jobs[(tag, st)] = [compile_unit(tree, d, st, unit) for unit in units(tree, st)]
+    for (tag, st), started in jobs.items():
+        for p, _a, rem in started:
+            if p.wait() != 0:
+                raise SystemExit("compiling the %s tree (%s) failed: see %s" % (tag, st, rem))
     bad = 0
     for st in ("f64", "f32"):
-        a, b = functions(jobs[("other", st)][1]), functions(jobs[("this", st)][1])
-        ra, rb = resources(jobs[("other", st)][2]), resources(jobs[("this", st)][2])
+        (a, ra), (b, rb) = pooled(jobs[("other", st)]), pooled(jobs[("this", st)])
         step = sorted(k for k in a if "npb_step" in k or "npd_maint_rule_for_wave" in k)
         differ = [k for k in step if k not in b or a[k] != b[k] or ra.get(k) != rb.get(k)]
         bad += len(differ)
         print("%s storage: %d step kernels and rule instantiations, %d instructions and directives: %s" % (
             st, len(step), sum(len(a[k].splitlines()) for k in step), "identical, resource tables too" if not differ else "DIFFERENT: %s" % differ))
-        print("  other functions changed:", sorted(k for k in a if k not in step and (k not in b or a[k] != b[k] or ra.get(k) != rb.get(k))))
+        same = [k for k in a if k in b and a[k] == b[k] and ra.get(k) == rb.get(k)]
+        print("  all functions of %s: %d in the other tree, %d in this one, %d identical in text and resource table" % (
+            ", ".join(units(ROOT, st)), len(a), len(b), len(same)))
+        print("  other functions changed:", sorted(k for k in a if k not in step and k in b and (a[k] != b[k] or ra.get(k) != rb.get(k))))
         print("  new functions:", sorted(k for k in b if k not in a))
+        print("  lost functions:", sorted(k for k in a if k not in b))
     return 1 if bad else 0
 
 

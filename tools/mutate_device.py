@@ -27,12 +27,19 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import mutate_oracle as M   # noqa: E402
+from compare_step_kernels import makefile_objects   # noqa: E402
 
 CSRC = os.path.join(ROOT, "nuclear_sim_amd", "csrc")
 BUILD = os.path.join(ROOT, "nuclear_sim_amd", "build")
 OUT = os.path.join(ROOT, "tools", "device_mutants")
 STEMS = ("primary", "ph", "chem", "reset", "condenser", "sg", "init")
 HIPFLAGS = "-O3 --offload-arch=gfx950 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -freciprocal-math -fapprox-func -fvisibility=hidden -w".split()
+MUTATED = "npb_kernels_f64.o"      # the one object a mutant compiles for itself
+
+
+def link_objects():
+    """every other object of libnpb.so, by the Makefile's own list (make print-objects), as paths into the product build"""
+    return [os.path.join(BUILD, o) for o in makefile_objects(ROOT) if o != MUTATED]
 
 
 def device_sites(stem):
@@ -92,8 +99,7 @@ def build_one(job):
             rec["build"] = "stillborn"
             return rec
         so = os.path.join(OUT, "libnpb_%d.so" % k)
-        ld = subprocess.run(["/opt/rocm/bin/hipcc"] + HIPFLAGS + ["-shared", "-pthread", "-o", so, obj, os.path.join(BUILD, "npb_kernels_f32.o"),
-                                                                 os.path.join(BUILD, "npb_api_f64.o"), os.path.join(BUILD, "npb_seeds.o")], capture_output=True, text=True)
+        ld = subprocess.run(["/opt/rocm/bin/hipcc"] + HIPFLAGS + ["-shared", "-pthread", "-o", so, obj] + link_objects(), capture_output=True, text=True)
         rec["build"] = "ok" if ld.returncode == 0 else "link failed"
         return rec
     finally:
@@ -101,8 +107,8 @@ def build_one(job):
 
 
 def cmd_build(args):
-    for f in ("npb_kernels_f32.o", "npb_api_f64.o", "npb_seeds.o"):
-        if not os.path.exists(os.path.join(BUILD, f)):
+    for f in link_objects():
+        if not os.path.exists(f):
             sys.exit("build the product library first (make -C nuclear_sim_amd/csrc): %s is missing" % f)
     shutil.rmtree(OUT, ignore_errors=True); os.makedirs(OUT)
     rng = random.Random(args.seed)

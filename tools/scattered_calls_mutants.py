@@ -23,6 +23,8 @@ import tempfile
 import threading
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from mutate_device import link_objects   # noqa: E402
 CSRC = os.path.join(ROOT, "nuclear_sim_amd", "csrc")
 BUILD = os.path.join(ROOT, "nuclear_sim_amd", "build")
 OUT = os.path.join(ROOT, "tools", "device_mutants")
@@ -81,8 +83,7 @@ def build_one(k):
             rec["build"] = "stillborn"
             return rec
         so = os.path.join(OUT, "libnpb_sc%d.so" % k)
-        ld = subprocess.run(["/opt/rocm/bin/hipcc"] + HIPFLAGS + ["-shared", "-pthread", "-o", so, obj] +
-                            [os.path.join(BUILD, f) for f in ("npb_kernels_f32.o", "npb_api_f64.o", "npb_seeds.o", "npb_noise.o")], capture_output=True, text=True)
+        ld = subprocess.run(["/opt/rocm/bin/hipcc"] + HIPFLAGS + ["-shared", "-pthread", "-o", so, obj] + link_objects(), capture_output=True, text=True)
         rec["build"] = "ok" if ld.returncode == 0 else "link failed"
         return rec
     finally:
@@ -90,8 +91,8 @@ def build_one(k):
 
 
 def cmd_build(args):
-    for f in ("npb_kernels_f32.o", "npb_api_f64.o", "npb_seeds.o", "npb_noise.o"):
-        if not os.path.exists(os.path.join(BUILD, f)):
+    for f in link_objects():
+        if not os.path.exists(f):
             sys.exit("build the product library first (make -C nuclear_sim_amd/csrc): %s is missing" % f)
     os.makedirs(OUT, exist_ok=True)
     out = []
