@@ -1449,10 +1449,10 @@ NPB_API int npb_normalizer_clear(NpbHandle *h, const uint8_t *mask, void *stream
  *   restart rule (the last_value: a plant that restarted on the last step bootstraps from +0.0).  Nothing is written to hidden, seen or
  *   primed.  npb_policy_values is refused by name while a core is set.
  * npb_policy_core_get_state / _set_state carry hidden (HOST float [n][H]), seen and primed (HOST int32 [n]).
- * Training through time is not built: npb_policy_grad, _update, _shard_sums, _apply_shards, _combine_shards (and their _more forms) and
- *   npb_policy_train_begin refuse a policy with a core by name.  Collect on the device, train on whole-sequence minibatches outside
- *   (recurrent.replay gives the states from `first`), put the parameters back with npb_policy_load.
- * Not here: a shared trunk; discrete or squashed (tanh-Gaussian) actions; a state-dependent std; LSTM cells, stacked or per-net cores, training the core on the device; half types; noise that restarts with the episode; skipping the forward pass on held steps of interval > 1.
+ * Training through time is not built into the row-wise entry points: npb_policy_grad, _update and _shard_sums (and their _more forms) refuse a
+ *   policy with a core by name, because rows carry no order.  npb_policy_grad_seq, npb_policy_update_seq and npb_policy_shard_sums_seq (below:
+ *   TRAINING THROUGH TIME) take whole sequences; npb_policy_train_begin, _apply_shards and _combine_shards read no rows and serve both.
+ * Not here: a shared trunk; discrete or squashed (tanh-Gaussian) actions; a state-dependent std; LSTM cells, stacked or per-net cores; half types; noise that restarts with the episode; skipping the forward pass on held steps of interval > 1.
  * NPB_VERSION stays 154: a binding detects the entry points by name.  A handle that never calls this behaves as before in every entry
  * point. */
 #define NPB_POLICY_HIDDEN_MAX 3
@@ -1650,6 +1650,66 @@ NPB_API int npb_policy_shard_sums(NpbHandle *h, const npb_ppo_desc_t *desc, cons
                                   void *stream);
 NPB_API int npb_policy_apply_shards(NpbHandle *h, const npb_ppo_shards_t *shards, double lr, double b1, double b2, double eps, void *stream);
 NPB_API int npb_policy_combine_shards(NpbHandle *h, const npb_ppo_shards_t *shards, void *stream);
+
+/* TRAINING THROUGH TIME (npb_ppo_seq_t; the entry points below; a binding detects them by name, NPB_VERSION stays 154): PPO over whole
+ * sequences for a policy with a core (npb_set_policy_core) -- the loss above and its gradient through both nets, through the GRU cell and
+ * through time, on the device.  nuclear_sim_amd/recurrent.py (gradient, shard_sums) states it in numpy, out of ppo.py's own functions, and
+ * that statement is the contract: the device gives its bits with hard gates and relu nets when fed the device's ratio.  A handle that
+ * never calls these computes the bits it computed before, in every entry point.
+ * One sequence minibatch is npb_ppo_desc_t's tensors TIME-MAJOR, as npb_rollout_minibatch gathers them with NPB_MINIBATCH_PLANT: obs [t]
+ * [plants][K * C], act [t][plants][A], logp_old, adv, ret (and value_old) [t][plants]; count = t * plants; rows_per_chain is read as the
+ * PLANTS of a chain (a positive multiple of 32).  npb_ppo_seq_t says where the sequences came from: t, plants, index [plants] (the
+ * minibatch's own index output: the rollout's plant of every sequence; NULL = identity), and the rollout's tensors episode [T][n_plants],
+ * ended [T][n_plants] and the core's first [n_plants][H]; hidden, optional, receives every cell's h'.  The kernel reads a plant's restart words and its state in front of slot 0
+ * through index; an index outside 0 .. n_plants - 1 makes every cell of that plant a skipped, poisoned cell and nothing is read through it.
+ * first is the state the COLLECTING parameters produced: after the first update of an iteration it is stale; that is inherent, and what
+ * every recurrent PPO does.  Truncated segments are not here: a sequence is differentiated whole.
+ * Forward: the step's recurrence under the current theta.  Slot s reads h_s, +0.0 where the plant restarted in front of s (episode[s] !=
+ * episode[s - 1], or ended[s - 1] & NPB_ROLLOUT_CUT; a restart in front of slot 0 is in first); the cell gives h'_s, +0.0 on a poisoned
+ * cell (a feature that is not finite); both nets read h'_s.  Per cell the row-wise epilogue, unchanged; a cell whose features are finite
+ * and whose act, logp_old, adv, ret (or value_old) is not is a skipped row: its seeds are +0.0, the cell still runs, the carry still flows.
+ * Backward, s descending, all float, every operation rounded on its own:
+ *   dh' = (carry + back(delta_actor_layer0, W_actor0)) + back(delta_critic_layer0, W_critic0)      no derivative: h' is an input; carry = +0.0 behind the last slot
+ * On a poisoned cell dh', every gate delta and the outgoing carry are +0.0.  Otherwise, with u = h - n:
+ *   dn = dh' * (1.0f - z);  dz = dh' * u;  direct = dh' * z
+ *   dan = dn * T'      soft: T' = 1.0f - n * n;  hard: +0.0 where the forward took a clamped branch (a < -1 or a > 1), else dn
+ *   dghn = dan * r;  dr = dan * gh_n
+ *   daz = dz * S'(z)   soft: S' = s * (1.0f - s);  hard: +0.0 where y < 0 or y > 1 (the forward's own strict tests), else d * 0.25f
+ *   dar = dr * S'(r)   likewise
+ *   delta_i = [dar | daz | dan];  delta_h = [dar | daz | dghn]      (3H wide, GRUCell's row order)
+ *   carry_out = direct + back(delta_h, W_hh)      ONE fmaf chain over the 3H rows of W_hh ascending, from +0.0
+ * and carry_out is +0.0 where the plant restarted in front of slot s.
+ * The sums are pinned: a chain is rows_per_chain plants with all their slots; within a chain the rows enter in the order tiles of 32
+ * plants ascending, within a tile s DESCENDING, within a slot the plants ascending.  dW_ih, db_ih come from (delta_i, x) and dW_hh, db_hh
+ * from (delta_h, h); x of a poisoned cell reads +0.0; the nets' as above, their first layers reading h'.  Across chains as above.  The
+ * gradient is in theta's layout, the core in front; clipping, stats, more, the options and Adam are unchanged.
+ * npb_ppo_seq_check(desc, seq, features_cells, n_axes): the host-only validator, NULL = accepted, else the reason: a NULL seq; what
+ * npb_ppo_check refuses of desc; t < 1; plants < 1; count != t * plants; n_plants < 1; t * n_plants beyond 2^31 - 1; a NULL episode, ended
+ * or first; a misaligned index, episode, first or hidden (4-byte aligned).
+ * npb_policy_grad_seq(h, desc, more, seq, stream): npb_policy_grad_more over sequences (more may be NULL; kl_limit > 0 is refused by name).
+ * npb_policy_update_seq(h, desc, more, seq, lr, b1, b2, eps, stream): the gradient and the Adam step, gated as npb_policy_update_more is.
+ * npb_policy_shard_sums_seq(h, desc, more, seq, count_total, out, stream): npb_policy_shard_sums over sequences; count_total counts cells
+ * (t * plants of every shard).  npb_policy_apply_shards / _combine_shards take its vectors.  All three refuse a policy without a core by name.
+ * The kernel (npb_ppo_seq.hip): one workgroup a chain, per tile of 32 plants a forward sweep that stores only h' ([t][plants][H] floats,
+ * a workspace the handle grows on demand) and a backward sweep that recomputes the gates; f32 matrix cores, no atomics, no scratch.
+ * Measured on an MI355X (tools/recurrent_train_cost.py): one update of t = 128 through a cell of 64 and (64, 64) nets takes 21.0 ms at
+ * 4 096 plants and 30.1 ms at 8 192 (the same BPTT in eager torch: 26.3 / 39.8 ms); serial in t, plants / 32 workgroups.
+ * Not here: truncated segments; sequences longer than one rollout; the exchange between shards (the caller's all-gather). */
+typedef struct npb_ppo_seq_t {
+  int t, plants;                             /* slots and sequences of the minibatch: desc->count == t * plants */
+  const int32_t *index;                      /* device [plants]: the rollout's plant of every sequence, or NULL = identity */
+  int n_plants;                              /* the rollout's plants: the row length of episode and ended, the rows of first */
+  const int32_t *episode;                    /* device [>= t][n_plants]: the rollout's episode */
+  const uint8_t *ended;                      /* device [>= t][n_plants]: the rollout's ended */
+  const float *first;                        /* device [n_plants][H]: the core's first */
+  float *hidden;                             /* device [t][plants][H], or NULL: where the states h' under the current theta go (NULL: the handle's workspace) */
+} npb_ppo_seq_t;
+NPB_API const char *npb_ppo_seq_check(const npb_ppo_desc_t *desc, const npb_ppo_seq_t *seq, int features_cells, int n_axes);
+NPB_API int npb_policy_grad_seq(NpbHandle *h, const npb_ppo_desc_t *desc, const npb_ppo_more_t *more, const npb_ppo_seq_t *seq, void *stream);
+NPB_API int npb_policy_update_seq(NpbHandle *h, const npb_ppo_desc_t *desc, const npb_ppo_more_t *more, const npb_ppo_seq_t *seq, double lr, double b1,
+                                  double b2, double eps, void *stream);
+NPB_API int npb_policy_shard_sums_seq(NpbHandle *h, const npb_ppo_desc_t *desc, const npb_ppo_more_t *more, const npb_ppo_seq_t *seq, int64_t count_total,
+                                      double *out, void *stream);
 
 /* ONE NORMALISER AND ONE SET OF ADVANTAGE MOMENTS ACROSS SHARDS (the entry points below; a binding detects them by name, NPB_VERSION
  * stays 154; no new struct).  What still made a sharded run W different runs: every shard folded only its own plants into its running

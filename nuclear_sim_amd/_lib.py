@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from .ppo_abi import PPO_SHARD_ROWS, PPO_SHARDS_MAX, PPO_STATS_MORE, NpbPpoMore, NpbPpoShards
-from .recurrent_abi import POLICY_GATES, NpbPolicyCore
+from .recurrent_abi import POLICY_GATES, NpbPolicyCore, NpbPpoSeq
 from .schema import PARAMS, SCHEMA
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -1256,6 +1256,11 @@ ENTRY_POINTS = (
         "npb_policy_shard_sums": (None, [_vp, _P(NpbPpoDesc), _P(NpbPpoMore), _i64, _vp, _vp]),
         "npb_policy_apply_shards": (None, [_vp, _P(NpbPpoShards), _cd, _cd, _cd, _cd, _vp]),
         "npb_policy_combine_shards": (None, [_vp, _P(NpbPpoShards), _vp])}),
+    ("npb_policy_grad_seq", {     # training through time: whole sequences through the recurrent core
+        "npb_ppo_seq_check": (_cs, [_P(NpbPpoDesc), _P(NpbPpoSeq), _ci, _ci]),
+        "npb_policy_grad_seq": (None, [_vp, _P(NpbPpoDesc), _P(NpbPpoMore), _P(NpbPpoSeq), _vp]),
+        "npb_policy_update_seq": (None, [_vp, _P(NpbPpoDesc), _P(NpbPpoMore), _P(NpbPpoSeq), _cd, _cd, _cd, _cd, _vp]),
+        "npb_policy_shard_sums_seq": (None, [_vp, _P(NpbPpoDesc), _P(NpbPpoMore), _P(NpbPpoSeq), _i64, _vp, _vp])}),
     ("npb_normalizer_apply_shards", {     # one normaliser and one set of advantage moments across shards
         "npb_normalizer_shard_count": (None, [_vp]),
         "npb_normalizer_shards_check": (_cs, [_vp, _ci]),

@@ -180,6 +180,7 @@ static const char *const g_no_normalizer = ": no normaliser set (npb_set_normali
 /* the policy's training buffers go with the policy */
 static void ppo_drop(NpbHandle *h) {
   if (h->ppo.chain_stats) (void)hipFree(h->ppo.chain_stats);
+  if (h->ppo.hseq) (void)hipFree(h->ppo.hseq);
   attachment_drop(&h->ppo, h->ppo.stats);
 }
 static const char *const g_no_policy = ": no policy set (npb_set_policy first)";
@@ -2569,7 +2570,7 @@ static const char *adam_refusal(double lr, double b1, double b2, double eps) {
     return ": lr must be finite, b1 and b2 lie in [0, 1), eps be finite and >= 0";
   return nullptr;
 }
-static const char *const g_core_untrained = ": the policy has a core (npb_set_policy_core), and training through time is not built: train on whole-sequence minibatches outside, then npb_policy_load";
+static const char *const g_core_untrained = ": the policy has a core (npb_set_policy_core), and training through time is not built into the row-wise entry points: rows carry no order; npb_policy_grad_seq, npb_policy_update_seq and npb_policy_shard_sums_seq take whole sequences";
 static int ppo_grad(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, void *stream) {
   if (!h->pol.theta) return fail_who(h, who, g_no_policy);
   if (h->core.primed) return fail_who(h, who, g_core_untrained);
@@ -2627,7 +2628,6 @@ int npb_policy_update_more(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_
 int npb_policy_train_begin(NpbHandle *h, void *stream) {
   if (!h) return NPB_EINVAL;
   if (!h->pol.theta) return fail_who(h, "npb_policy_train_begin", g_no_policy);
-  if (h->core.primed) return fail_who(h, "npb_policy_train_begin", g_core_untrained);
   if (h->ppo.armed) return fail_who(h, "npb_policy_train_begin", g_train_open);
   NPB_USE_DEVICE(h);
   if (int rc = ppo_room(h, "npb_policy_train_begin", 0)) return rc;
@@ -2682,7 +2682,6 @@ int npb_policy_shard_sums(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_m
 }
 static int ppo_combine(NpbHandle *h, const char *who, const npb_ppo_shards_t *S, void *stream) {
   if (!h->pol.theta) return fail_who(h, who, g_no_policy);
-  if (h->core.primed) return fail_who(h, who, g_core_untrained);
   if (const char *why = npb_ppo_shards_check(S, (int64_t)h->pol.theta_count, h->pol.n_axes)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
   if (int rc = ppo_room(h, who, 0)) return rc;
@@ -2699,13 +2698,83 @@ int npb_policy_apply_shards(NpbHandle *h, const npb_ppo_shards_t *S, double lr, 
   if (!h) return NPB_EINVAL;
   const char *who = "npb_policy_apply_shards";
   const int gated = S && S->kl_limit > 0.0;
-  if (h->core.primed) return fail_who(h, who, g_core_untrained);
   if (gated && !h->ppo.armed) return fail_who(h, who, ": kl_limit > 0 outside npb_policy_train_begin / npb_policy_train_end (npb_policy_train_begin first)");
   if (!gated && h->ppo.armed) return fail_who(h, who, ": kl_limit == 0 between npb_policy_train_begin and npb_policy_train_end: every update of the pair is gated");
   if (h->pol.theta)      /* (a gated combine counts itself applied: its Adam step must not be refused behind it) */
     if (const char *why = adam_refusal(lr, b1, b2, eps)) return fail_who(h, who, why);
   if (int rc = ppo_combine(h, who, S, stream)) return rc;
   return ppo_adam(h, who, lr, b1, b2, eps, gated, stream);
+}
+
+/* ---- training through time: whole sequences through the recurrent core (include/npb.h, npb_ppo_seq.hip) */
+const char *npb_ppo_seq_check(const npb_ppo_desc_t *D, const npb_ppo_seq_t *S, int features_cells, int n_axes) {
+  if (!S) return "npb_policy_grad_seq: a NULL sequence descriptor";
+  if (const char *why = npb_ppo_check(D, features_cells, n_axes)) return why;
+  if (S->t < 1) return "npb_policy_grad_seq: t must be >= 1";
+  if (S->plants < 1) return "npb_policy_grad_seq: plants must be >= 1";
+  if ((int64_t)S->t * S->plants != (int64_t)D->count) return "npb_policy_grad_seq: desc->count must be t * plants";
+  if (S->n_plants < 1) return "npb_policy_grad_seq: n_plants must be >= 1";
+  if ((int64_t)S->t * S->n_plants > INT32_MAX) return "npb_policy_grad_seq: t * n_plants is beyond 2^31 - 1";
+  if (!S->episode) return "npb_policy_grad_seq: episode is NULL";
+  if (!S->ended) return "npb_policy_grad_seq: ended is NULL";
+  if (!S->first) return "npb_policy_grad_seq: first is NULL";
+  if (((uintptr_t)S->index | (uintptr_t)S->episode | (uintptr_t)S->first | (uintptr_t)S->hidden) & 3u)
+    return "npb_policy_grad_seq: a misaligned index, episode, first or hidden: 4-byte aligned";
+  return nullptr;
+}
+static const char *const g_seq_no_core = ": the policy has no core (npb_set_policy_core): sequences are a recurrent policy's; rows go to npb_policy_grad";
+/* the checks of a sequence call and its workspaces: the chains' (a chain is rows_per_chain plants) and h' [t][plants][H] */
+static int ppo_seq_room(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S) {
+  if (!h->pol.theta) return fail_who(h, who, g_no_policy);
+  if (!h->core.primed) return fail_who(h, who, g_seq_no_core);
+  if (const char *why = npb_ppo_seq_check(D, S, h->pol.cells, h->pol.n_axes)) return fail(h, NPB_EINVAL, why);
+  if (const char *why = npb_ppo_more_check(M, D->count)) return fail(h, NPB_EINVAL, why);
+  NPB_USE_DEVICE(h);
+  if (int rc = ppo_room(h, who, ((size_t)S->plants + D->rows_per_chain - 1) / D->rows_per_chain)) return rc;
+  const size_t floats = (size_t)D->count * (size_t)h->core.H;
+  if (!S->hidden && floats > h->ppo.hseq_floats) {      /* (hipFree of the old one waits for a launch that still reads it) */
+    char *dev = nullptr;
+    if (int rc = attachment_alloc(h, who, "the sequences' hidden states", nullptr, 0, floats * sizeof(float), &dev)) return rc;
+    if (h->ppo.hseq) (void)hipFree(h->ppo.hseq);
+    h->ppo.hseq = (float *)dev; h->ppo.hseq_floats = floats;
+  }
+  return NPB_OK;
+}
+static int ppo_grad_seq(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, void *stream) {
+  if (int rc = ppo_seq_room(h, who, D, M, S)) return rc;
+  npb_launch_ppo_grad_seq(&h->pol, &h->core, &h->ppo, D, M, S, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_policy_grad_seq(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (M && M->kl_limit > 0.0) return fail(h, NPB_EINVAL, "npb_policy_grad_seq: kl_limit > 0: the gate is an update's (npb_policy_update_seq)");
+  return ppo_grad_seq(h, "npb_policy_grad_seq", D, M, S, stream);
+}
+int npb_policy_update_seq(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, double lr, double b1, double b2, double eps,
+                          void *stream) {
+  if (!h) return NPB_EINVAL;
+  const char *who = "npb_policy_update_seq";
+  const int gated = M && M->kl_limit > 0.0;
+  if (gated && !h->ppo.armed) return fail_who(h, who, ": kl_limit > 0 outside npb_policy_train_begin / npb_policy_train_end (npb_policy_train_begin first)");
+  if (!gated && h->ppo.armed) return fail_who(h, who, ": kl_limit == 0 between npb_policy_train_begin and npb_policy_train_end: every update of the pair is gated");
+  if (gated && h->pol.theta)      /* (a gated gradient counts itself applied: its Adam step must not be refused behind it) */
+    if (const char *why = adam_refusal(lr, b1, b2, eps)) return fail_who(h, who, why);
+  if (int rc = ppo_grad_seq(h, who, D, M, S, stream)) return rc;
+  return ppo_adam(h, who, lr, b1, b2, eps, gated, stream);
+}
+int npb_policy_shard_sums_seq(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, int64_t count_total, double *out,
+                              void *stream) {
+  if (!h) return NPB_EINVAL;
+  const char *who = "npb_policy_shard_sums_seq";
+  if (M && M->kl_limit > 0.0) return fail_who(h, who, ": kl_limit > 0: the gate belongs to the combine (npb_policy_apply_shards)");
+  if (D && count_total < (int64_t)D->count) return fail_who(h, who, ": count_total < desc->count: it is the cells of the whole update");
+  if (count_total > ((int64_t)1 << 53)) return fail_who(h, who, ": count_total is beyond 2^53");
+  if (!out || ((uintptr_t)out & 7u)) return fail_who(h, who, ": a NULL or misaligned out (8-byte aligned)");
+  if (int rc = ppo_seq_room(h, who, D, M, S)) return rc;
+  npb_launch_ppo_shard_sums_seq(&h->pol, &h->core, &h->ppo, D, M, S, count_total, out, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
 }
 
 /* a copy between device buffers on the stream */

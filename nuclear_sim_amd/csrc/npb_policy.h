@@ -157,6 +157,26 @@ __device__ __forceinline__ void npd_policy_net(const npd_policy_net_t &N, const 
     in = out;
   }
 }
+/* ---- the cell's gates, S and T of the statement (recurrent.py: sigma, tau), what the recurrent step (npb_policy_core.hip) and the sequence
+ * gradient kernel (npb_ppo_seq.hip) share */
+#define NPD_CORE_SOFT 0
+#define NPD_CORE_HARD 1
+
+__device__ __forceinline__ float npd_core_sigma(float a, int gates) {
+  if (gates == NPD_CORE_HARD) {
+    const float q = 0.25f * a;
+    const float y = q + 0.5f;
+    return y < 0.0f ? 0.0f : (y > 1.0f ? 1.0f : y);
+  }
+  const float half = 0.5f * a;
+  const float t = tanhf(half);
+  const float s = 0.5f * t;
+  return s + 0.5f;
+}
+__device__ __forceinline__ float npd_core_tau(float a, int gates) {
+  if (gates == NPD_CORE_HARD) return a < -1.0f ? -1.0f : (a > 1.0f ? 1.0f : a);
+  return tanhf(a);
+}
 /* ---- the noise: Philox4x32-10 and the pair of normals of one call (policy.py: philox4x32, noise_from_words) */
 __device__ __forceinline__ void npd_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t w[4]) {
 #pragma unroll

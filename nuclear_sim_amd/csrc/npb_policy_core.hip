@@ -33,25 +33,6 @@
 #include <math.h>
 #include "npb_policy.h"
 
-#define NPD_CORE_SOFT 0
-#define NPD_CORE_HARD 1
-
-__device__ __forceinline__ float npd_core_sigma(float a, int gates) {
-  if (gates == NPD_CORE_HARD) {
-    const float q = 0.25f * a;
-    const float y = q + 0.5f;
-    return y < 0.0f ? 0.0f : (y > 1.0f ? 1.0f : y);
-  }
-  const float half = 0.5f * a;
-  const float t = tanhf(half);
-  const float s = 0.5f * t;
-  return s + 0.5f;
-}
-__device__ __forceinline__ float npd_core_tau(float a, int gates) {
-  if (gates == NPD_CORE_HARD) return a < -1.0f ? -1.0f : (a > 1.0f ? 1.0f : a);
-  return tanhf(a);
-}
-
 template <typename IN, int KC_MAX, int H_MAX>
 __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_policy_core_kernel(npb_policy_t P, npd_policy_core_t C, npd_policy_run_t R, npd_policy_core_run_t G) {
   __shared__ float xs[KC_MAX * NPD_POLICY_STRIDE];

@@ -39,107 +39,6 @@
 #include "npb_ppo.h"
 #include "npb_minibatch.h"
 
-typedef struct {
-  npb_ppo_desc_t D;
-  npb_ppo_more_t M;                    /* every option off: {NULL, 0.0, 0.0} */
-  int n_chains;
-  float *partials; size_t floats;      /* [n_chains][floats] */
-  double *chain_stats;                 /* [n_chains][NPD_PPO_ROWVALS] */
-  double n;                            /* the seeds' divisor: (double)D.count, or a shard's (double)count_total */
-  const double *shards; size_t shard_len; int n_shards;      /* the combine's: [n_shards][shard_len], shard_len = P.log_std + NPD_PPO_ROWVALS */
-  double ent_coef;                     /* the combine's (a plain call's is D.ent_coef) */
-} npd_ppo_run_t;
-
-__device__ __forceinline__ double npd_ppo_load(const void *x, int f64, size_t i) { return f64 ? ((const double *)x)[i] : (double)((const float *)x)[i]; }
-
-/* a layer's dW and db of this tile onto the chain's partials: delta[j][row], hin[k][row] (row stride NPD_POLICY_STRIDE both).  Lane l gives
- * A[j = l & 31][row = l >> 5] and B[row = l >> 5][k = l & 31] and holds D[j = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5)][k = l & 31].  A block's
- * cells beyond the layer's out or in read whatever LDS holds there and are neither loaded nor stored: D[j][k] depends on row j of A and
- * column k of B alone */
-__device__ __forceinline__ void npd_ppo_dw(const npd_policy_layer_t &L, float *__restrict__ prow, bool first, const float *delta, const float *hin, int tid) {
-  const int wave = tid >> 6, lane = tid & 63, col = lane & 31, half = lane >> 5;
-  const int kb = (L.in + 31) >> 5, blocks = (L.out_pad >> 5) * kb;
-  for (int b = wave; b < blocks; b += NPD_POLICY_WAVES) {
-    const int j0 = 32 * (b / kb), k0 = 32 * (b % kb), k = k0 + col;
-    npd_f32x16 acc;
-#pragma unroll
-    for (int reg = 0; reg < 16; reg++) {
-      const int j = j0 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
-      acc[reg] = !first && j < L.out && k < L.in ? prow[L.w + (size_t)j * L.in + k] : 0.0f;
-    }
-    const float *a = delta + (j0 + col) * NPD_POLICY_STRIDE + half;
-    const float *h = hin + k * NPD_POLICY_STRIDE + half;
-#pragma unroll
-    for (int s = 0; s < NPD_POLICY_TILE / 2; s++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2 * s], h[2 * s], acc, 0, 0, 0);
-#pragma unroll
-    for (int reg = 0; reg < 16; reg++) {
-      const int j = j0 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
-      if (j < L.out && k < L.in) prow[L.w + (size_t)j * L.in + k] = acc[reg];
-    }
-  }
-  if (tid < L.out) {
-    float acc = first ? 0.0f : prow[L.b + tid];
-    const float *d = delta + tid * NPD_POLICY_STRIDE;
-#pragma unroll
-    for (int r = 0; r < NPD_POLICY_TILE; r++) acc = acc + d[r];      /* fmaf(delta, 1.0f, acc) */
-    prow[L.b + tid] = acc;
-  }
-}
-
-/* delta'[k][row] of the layer below: back[row][k] = the chain over j of fmaf(delta[row][j], W[j][k], acc) from +0.0, two j a call, j up
- * to the next multiple of 4 of the width (the producer of delta wrote +0.0 there; W reads as +0.0 there), then the derivative of the
- * activation that made h[k][row].  Lane l gives A[row = l & 31][j = l >> 5] and B[j = l >> 5][k = l & 31] = theta's W[j][k] and holds
- * D[row = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5)][k = l & 31].  k up to the next multiple of 4 of the layer's in is written +0.0: the k
- * extension of the back below */
-__device__ __forceinline__ void npd_ppo_back(const npd_policy_layer_t &L, const float *__restrict__ theta, const float *delta, float *out, const float *h,
-                                             int activation, int tid) {
-  const int wave = tid >> 6, lane = tid & 63, col = lane & 31, half = lane >> 5, pairs = ((L.out + 3) & ~3) >> 1;
-  for (int k0 = 32 * wave; k0 < L.in; k0 += 32 * NPD_POLICY_WAVES) {
-    const int k = k0 + col;
-    npd_f32x16 acc;
-#pragma unroll
-    for (int reg = 0; reg < 16; reg++) acc[reg] = 0.0f;
-    const float *a = delta + half * NPD_POLICY_STRIDE + col;
-    for (int s = 0; s < pairs; s++) {
-      const int j = 2 * s + half;
-      const float w = j < L.out && k < L.in ? theta[L.w + (size_t)j * L.in + k] : 0.0f;
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2 * s * NPD_POLICY_STRIDE], w, acc, 0, 0, 0);
-    }
-    if (k < L.in_pad) {
-#pragma unroll
-      for (int reg = 0; reg < 16; reg++) {
-        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * half;
-        const float hv = h[k * NPD_POLICY_STRIDE + row];
-        float y = acc[reg];
-        if (activation == NPB_POLICY_RELU) y = hv > 0.0f ? y : 0.0f;
-        else { const float sq = hv * hv; const float slope = 1.0f - sq; y = y * slope; }
-        out[k * NPD_POLICY_STRIDE + row] = k < L.in ? y : 0.0f;
-      }
-    }
-  }
-}
-
-/* one net of the tile: forward with every hidden activation kept (hid[l]), then `seeds` (a lane a row; it writes the head's delta into d0
- * and ends with the barrier that publishes it), then backward onto the chain's partials */
-template <int H_MAX, class Seeds>
-__device__ __forceinline__ void npd_ppo_net(const npd_policy_net_t &N, const npb_policy_t &P, const float *xs, float (*hid)[H_MAX * NPD_POLICY_STRIDE], float *head,
-                                            float *d0, float *d1, float *prow, bool first, int tid, Seeds seeds) {
-  const int wave = tid >> 6, lane = tid & 63, last = N.n_layers - 1;
-  for (int l = 0; l <= last; l++) {
-    npd_policy_layer(N.layer[l], P.theta, P.padded, l ? hid[l - 1] : xs, l == last ? head : hid[l], l == last ? -1 : P.D.activation, wave, lane);
-    __syncthreads();
-  }
-  seeds();
-  __syncthreads();
-  for (int l = last; l >= 0; l--) {
-    const npd_policy_layer_t &L = N.layer[l];
-    npd_ppo_dw(L, prow, first, d0, l ? hid[l - 1] : xs, tid);
-    if (l) npd_ppo_back(L, P.theta, d0, d1, hid[l - 1], P.D.activation, tid);
-    __syncthreads();
-    float *t = d0; d0 = d1; d1 = t;
-  }
-}
-
 template <int KC_MAX, int H_MAX>
 __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_grad_kernel(npb_policy_t P, npd_ppo_run_t R) {
   __shared__ float xs[KC_MAX * NPD_POLICY_STRIDE];
@@ -151,7 +50,7 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_grad_kernel(npb_poli
   const npb_ppo_desc_t &D = R.D;
   const int tid = threadIdx.x, A = P.n_axes, KC = P.cells, KC_pad = (KC + 3) & ~3;
   const size_t count = (size_t)D.count, rpc = (size_t)D.rows_per_chain;
-  const double n = R.n, qnan = (double)__builtin_nanf("");
+  const double n = R.n;
   for (size_t chain = blockIdx.x; chain < (size_t)R.n_chains; chain += gridDim.x) {
     float *prow = R.partials + chain * R.floats;
     double running = 0.0;      /* lane q < NPD_PPO_ROWVALS: the chain's sum of per-row double q */
@@ -183,69 +82,9 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_grad_kernel(npb_poli
       const bool live = tid < in_tile, skipped = tid < NPD_POLICY_TILE && bad[tid & 31] != 0;
       const size_t p = base + tid;
       /* 2 .. 4. the actor */
-      npd_ppo_net<H_MAX>(P.actor, P, xs, hid, head, da, db, prow, first, tid, [&]() {
-        const int A4 = (A + 3) & ~3;
-        if (tid >= NPD_POLICY_TILE) return;
-        for (int a = 0; a < A4; a++) da[a * NPD_POLICY_STRIDE + tid] = 0.0f;
-        if (!live) return;
-        if (skipped) {
-          rowv[NPD_PPO_SKIPPED * NPD_POLICY_TILE + tid] = 1.0;
-          if (D.logp_new) D.logp_new[p] = (float)qnan;
-          if (D.ratio) D.ratio[p] = qnan;
-          return;
-        }
-        double d[NPB_CONTROLS_AXES_MAX];
-        double lp = -((double)A * 0.9189385332046727);
-        for (int a = 0; a < A; a++) {
-          const double diff = npd_ppo_load(D.act, D.act_type, p * A + a) - (double)head[a * NPD_POLICY_STRIDE + tid];
-          d[a] = diff / (double)P.theta[P.std + a];
-          const double sq = d[a] * d[a], hf = 0.5 * sq;
-          lp = (lp - hf) - (double)P.theta[P.log_std + a];
-        }
-        const double lr = lp - (double)D.logp_old[p], r = exp(lr), adv = npd_ppo_load(D.adv, D.adv_type, p);
-        const double lo = 1.0 - D.clip, hi = 1.0 + D.clip;
-        const bool clipped = (adv > 0.0 && r > hi) || (adv < 0.0 && r < lo);
-        const double ar = adv * r, c = clipped ? 0.0 : -ar;
-        for (int a = 0; a < A; a++) {
-          const double cd = c * d[a], q = cd / (double)P.theta[P.std + a], seed = q / n;
-          da[a * NPD_POLICY_STRIDE + tid] = (float)seed;
-          const double sq = d[a] * d[a], less = sq - 1.0, t = c * less;
-          rowv[a * NPD_POLICY_TILE + tid] = t / n;
-        }
-        const double rc = r < lo ? lo : (r > hi ? hi : r), second = rc * adv;
-        rowv[NPD_PPO_POLICY_LOSS * NPD_POLICY_TILE + tid] = -(second < ar ? second : ar);
-        const double rm = r - 1.0;
-        rowv[NPD_PPO_KL * NPD_POLICY_TILE + tid] = rm - lr;
-        rowv[NPD_PPO_CLIPPED * NPD_POLICY_TILE + tid] = clipped ? 1.0 : 0.0;
-        if (D.logp_new) D.logp_new[p] = (float)lp;
-        if (D.ratio) D.ratio[p] = r;
-      });
+      npd_ppo_net<H_MAX>(P.actor, P, xs, hid, head, da, db, prow, first, tid, nullptr, [&]() { npd_ppo_seeds_actor(P, D, n, head, da, rowv, tid, live, skipped, p); });
       /* 5. the critic */
-      npd_ppo_net<H_MAX>(P.critic, P, xs, hid, head, da, db, prow, first, tid, [&]() {
-        if (tid >= NPD_POLICY_TILE) return;
-        for (int a = 0; a < 4; a++) da[a * NPD_POLICY_STRIDE + tid] = 0.0f;
-        if (!live) return;
-        const float v = head[tid];
-        if (D.value_new) D.value_new[p] = skipped ? (float)qnan : v;
-        if (skipped) return;
-        const double ret = npd_ppo_load(D.ret, D.adv_type, p), diff = (double)v - ret, sq = diff * diff;
-        double seed = diff, lsq = sq;
-        if (R.M.clip_vf > 0.0) {      /* the max form: the larger of the two squares, and its own derivative */
-          const double c = R.M.clip_vf, vo = (double)R.M.value_old[p], dvo = (double)v - vo;
-          const double dc = dvo < -c ? -c : (dvo > c ? c : dvo), vc = vo + dc, diffc = vc - ret, sqc = diffc * diffc;
-          const bool use = sqc > sq, out = dvo < -c || dvo > c;
-          seed = use ? (out ? 0.0 : diffc) : diff;
-          lsq = use ? sqc : sq;
-          rowv[NPD_PPO_VF_CLIPPED * NPD_POLICY_TILE + tid] = out ? 1.0 : 0.0;
-        }
-        const double scaled = D.vf_coef * seed;
-        da[tid] = (float)(scaled / n);
-        rowv[NPD_PPO_VALUE_LOSS * NPD_POLICY_TILE + tid] = 0.5 * lsq;
-        rowv[NPD_PPO_RET * NPD_POLICY_TILE + tid] = ret;
-        rowv[NPD_PPO_RET2 * NPD_POLICY_TILE + tid] = ret * ret;
-        rowv[NPD_PPO_DIFF * NPD_POLICY_TILE + tid] = diff;
-        rowv[NPD_PPO_DIFF2 * NPD_POLICY_TILE + tid] = sq;
-      });
+      npd_ppo_net<H_MAX>(P.critic, P, xs, hid, head, da, db, prow, first, tid, nullptr, [&]() { npd_ppo_seeds_critic(P, D, R.M, n, head, da, rowv, tid, live, skipped, p); });
       /* 6. the tile's per-row doubles onto the chain's sums, rows ascending */
       if (tid < NPD_PPO_ROWVALS)
         for (int r = 0; r < NPD_POLICY_TILE; r++) running = running + rowv[tid * NPD_POLICY_TILE + r];
@@ -389,15 +228,7 @@ __global__ __launch_bounds__(256) void npb_ppo_adam_gated_kernel(npb_policy_t P,
   npd_ppo_adam(P, O, step_size, root, b1, c1, b2, c2, eps);
 }
 
-static npd_ppo_run_t npd_ppo_run(const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M) {
-  npd_ppo_run_t R = {};
-  R.D = *D;
-  if (M) R.M = *M;
-  R.n_chains = (int)(((int64_t)D->count + D->rows_per_chain - 1) / D->rows_per_chain);
-  R.partials = O->partials; R.floats = O->floats; R.chain_stats = O->chain_stats;
-  R.n = (double)D->count;
-  return R;
-}
+static int npd_ppo_chains(const npb_ppo_desc_t *D) { return (int)(((int64_t)D->count + D->rows_per_chain - 1) / D->rows_per_chain); }
 static void npd_ppo_launch_grad(const npb_policy_t *P, const npb_ppo_desc_t *D, const npd_ppo_run_t &R, hipStream_t stream) {
   const int cap = D->max_blocks > 0 ? D->max_blocks : 2048;
   const dim3 grid((unsigned)(R.n_chains < cap ? R.n_chains : cap)), block(NPD_POLICY_LANES);
@@ -405,18 +236,24 @@ static void npd_ppo_launch_grad(const npb_policy_t *P, const npb_ppo_desc_t *D, 
   else hipLaunchKernelGGL((npb_ppo_grad_kernel<NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX>), grid, block, 0, stream, *P, R);
 }
 extern "C" void npb_launch_ppo_grad(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, hipStream_t stream) {
-  const npd_ppo_run_t R = npd_ppo_run(O, D, M);
+  const npd_ppo_run_t R = npd_ppo_run(O, D, M, npd_ppo_chains(D));
   npd_ppo_launch_grad(P, D, R, stream);
-  hipLaunchKernelGGL(npb_ppo_reduce_kernel, dim3((P->theta_count + NPD_TREE - 1) / NPD_TREE), dim3(NPD_TREE), 0, stream, *P, R, *O);
-  hipLaunchKernelGGL(npb_ppo_finish_kernel<false>, dim3(1), dim3(NPD_TREE), 0, stream, *P, R, *O);
+  npb_launch_ppo_reduce(P, O, &R, stream);
+}
+void npb_launch_ppo_reduce(const npb_policy_t *P, const npb_ppo_t *O, const npd_ppo_run_t *R, hipStream_t stream) {
+  hipLaunchKernelGGL(npb_ppo_reduce_kernel, dim3((P->theta_count + NPD_TREE - 1) / NPD_TREE), dim3(NPD_TREE), 0, stream, *P, *R, *O);
+  hipLaunchKernelGGL(npb_ppo_finish_kernel<false>, dim3(1), dim3(NPD_TREE), 0, stream, *P, *R, *O);
+}
+void npb_launch_ppo_shard_reduce(const npb_policy_t *P, const npd_ppo_run_t *R, double *out, hipStream_t stream) {
+  const size_t L = (size_t)P->log_std + NPD_PPO_ROWVALS;
+  hipLaunchKernelGGL(npb_ppo_shard_reduce_kernel, dim3((unsigned)((L + NPD_TREE - 1) / NPD_TREE)), dim3(NPD_TREE), 0, stream, *P, *R, out);
 }
 extern "C" void npb_launch_ppo_shard_sums(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, int64_t count_total,
                                           double *out, hipStream_t stream) {
-  npd_ppo_run_t R = npd_ppo_run(O, D, M);
+  npd_ppo_run_t R = npd_ppo_run(O, D, M, npd_ppo_chains(D));
   R.n = (double)count_total;
   npd_ppo_launch_grad(P, D, R, stream);
-  const size_t L = (size_t)P->log_std + NPD_PPO_ROWVALS;
-  hipLaunchKernelGGL(npb_ppo_shard_reduce_kernel, dim3((unsigned)((L + NPD_TREE - 1) / NPD_TREE)), dim3(NPD_TREE), 0, stream, *P, R, out);
+  npb_launch_ppo_shard_reduce(P, &R, out, stream);
 }
 extern "C" void npb_launch_ppo_combine(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_shards_t *S, hipStream_t stream) {
   npd_ppo_run_t R = {};

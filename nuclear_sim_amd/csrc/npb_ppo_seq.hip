@@ -1,0 +1,293 @@
+/* npb_ppo_seq.hip -- training the recurrent policy through time on the device (npb_policy_grad_seq, npb_policy_shard_sums_seq, include/npb.h):
+ * PPO's loss over a minibatch of whole sequences and its gradient through both MLPs, through the GRU cell and through time.
+ * nuclear_sim_amd/recurrent.py (gradient, shard_sums) states it in numpy; this file produces its bits for hard gates and relu nets fed the
+ * device's own ratio (the float tanh and the double exp are the statement's licensed differences).  Built with npb_ppo.hip's flags (Makefile):
+ * no contraction, IEEE division and square root.  The reduce, finish, Adam, shard and combine kernels are npb_ppo.hip's: they work on theta's
+ * flat layout, and the core's parameters are its front.
+ *
+ * THE GRADIENT KERNEL: one workgroup of 256 lanes (four waves) runs one CHAIN of rows_per_chain PLANTS with all their t slots, tile of 32
+ * plants after tile; a launch's workgroups stride over the chains.  The geometry and the LDS layout are the policy's: every buffer
+ * [k][plant], row stride 33.  The minibatch is time-major, [t][plants][...]; a plant's restart words and its state in front of slot 0 are
+ * read from the rollout's own tensors through the minibatch's index: episode and ended [T][n_plants], first [n_plants][H].  An index outside
+ * 0 .. n_plants - 1 makes every cell of that plant a skipped, poisoned cell, and nothing is read through it.  Per tile, two sweeps:
+ *   FORWARD, s ascending: the step kernel's cell, gate by gate (npb_policy_core.hip's step 2: npd_policy_layer, npd_core_sigma, npd_core_tau),
+ *   h carried in LDS, +0.0 where the plant restarted in front of s (an episode change, or the cut bit of ended[s - 1]) and behind a poisoned
+ *   cell; h'_s goes to the handle's workspace [t][plants][H] (or the caller's hidden).  Only h' is stored: the backward sweep recomputes the
+ *   gates, which gives the same bits and keeps the workspace at t * plants * H floats.
+ *   BACKWARD, s descending, the carry dh in LDS (+0.0 behind the last slot):
+ *     the nets, one after the other (npb_ppo.h's npd_ppo_net, the row-wise kernel's own): h'_s from the workspace, forward with the
+ *     activations kept, the per-row epilogue (npd_ppo_seeds_actor, npd_ppo_seeds_critic), dW / db onto the chain's partials, back; the first
+ *     layer's back has no derivative behind it and is added onto dh: dh' = (carry + back_actor) + back_critic.
+ *     the cell: h_s (first, or h'_(s-1) from the workspace, the restart applied) and x_s (a poisoned cell's +0.0) into LDS; the gates again,
+ *     r into b2, z into b3, n into b4, gh_n into b5, and for hard gates the three clamped-branch flags of a cell as a small number in b6;
+ *     then a lane a cell, in place: dar over r, daz over z, dan over n, dghn over gh_n, direct = dh' * z over dh (all +0.0 on a poisoned
+ *     cell); dW / db of the six gate layers onto the partials (delta_i = [dar | daz | dan] with x, delta_h = [dar | daz | dghn] with h); and
+ *     the carry: dh = direct + back(delta_h, W_hh), ONE chain over W_hh's 3H rows, the accumulator carried through the three blocks as the
+ *     matrix core's C operand (npd_ppo_back_onto<3>), +0.0 where the plant restarted in front of s.
+ *   The per-row doubles of a slot are added in plant order onto the chain's running sums, a lane a quantity.
+ * A chain's rows therefore enter every sum in the statement's order: tiles ascending, within a tile s descending, within a slot the plants
+ * ascending.  No atomics, nothing depends on the launch order, no scratch.
+ * LDS, from the declarations below: xs (K*C x 33 floats), seven H-wide buffers (H_MAX x 33 floats each; H_MAX covers the core and both nets'
+ * widths), the head's 1056 B, the per-row doubles' 4608 B, four words a plant: the small build (npd_policy_small with the core's width)
+ * 8448 + 7 x 8448 + 6176 = 73 760 B, the large one 33 792 + 7 x 16 896 + 6176 = 158 240 B of gfx950's 160 KiB (one workgroup a CU), as the
+ * compiler reports them.  Its other figures (-Rpass-analysis=kernel-resource-usage), both builds: 255 VGPRs, 22 / 40 AGPRs, no scratch, no
+ * VGPR spills, and 469 / 488 of the descriptors' scalars spilled from SGPRs into VGPR lanes (the row-wise kernel: 133 / 129) -- no memory
+ * traffic, but a workgroup is alone on its CU in the small build too.  No shape is refused: both builds fit.  Measured on an MI355X
+ * (tools/recurrent_train_cost.py): one update of t = 128 through a cell of 64 and (64, 64) nets, 21.0 ms at 4 096 plants, 30.1 ms at 8 192.  The
+ * nets' phase and the cell's phase alias the seven buffers: b0 the carry; b1 h' then h; b2 .. b4 the nets' hidden activations then r, z, n;
+ * b5, b6 the nets' two delta buffers then gh_n and the flags. */
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include "npb_ppo.h"
+
+#define NPD_SEQ_CUT 4      /* NPB_ROLLOUT_CUT */
+
+/* what the sequence kernel takes beside npd_ppo_run_t: the caller's descriptor and the workspace of h' */
+typedef struct {
+  npb_ppo_seq_t S;
+  float *hseq;      /* [t][plants][H] */
+} npd_ppo_seq_run_t;
+
+/* a tile's H-wide buffer filled whole, [k][plant] with k up to H_pad: plant `row` reads H contiguous floats at run + offset(row), or +0.0
+ * where it has none (beyond the tile, a plant without a source, a restarted plant).  Consecutive lanes on consecutive k of one plant */
+template <class Source>
+__device__ __forceinline__ void npd_seq_fill(float *dst, int H, int H_pad, int tid, Source source) {
+  for (int e = tid; e < H_pad * NPD_POLICY_TILE; e += NPD_POLICY_LANES) {
+    const int row = e / H_pad, k = e - row * H_pad;
+    const float *from = source(row);
+    dst[k * NPD_POLICY_STRIDE + row] = from && k < H ? from[k] : 0.0f;
+  }
+}
+
+template <int KC_MAX, int H_MAX>
+__global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_seq_kernel(npb_policy_t P, npd_policy_core_t C, npd_ppo_run_t R, npd_ppo_seq_run_t Q) {
+  __shared__ float xs[KC_MAX * NPD_POLICY_STRIDE];
+  __shared__ float buf[7][H_MAX * NPD_POLICY_STRIDE];
+  __shared__ float head[NPB_CONTROLS_AXES_MAX * NPD_POLICY_STRIDE];
+  __shared__ double rowv[NPD_PPO_ROWVALS * NPD_POLICY_TILE];
+  __shared__ int bad[NPD_POLICY_TILE], fresh[NPD_POLICY_TILE], skip[NPD_POLICY_TILE], src[NPD_POLICY_TILE];
+  float *const b0 = buf[0], *const b1 = buf[1], *const b2 = buf[2], *const b3 = buf[3], *const b4 = buf[4], *const b5 = buf[5], *const b6 = buf[6];
+  const npb_ppo_desc_t &D = R.D;
+  const npb_ppo_seq_t &S = Q.S;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, A = P.n_axes, KC = P.cells, KC_pad = (KC + 3) & ~3, H = C.H, H_pad = (H + 3) & ~3;
+  const int T = S.t;
+  const size_t plants = (size_t)S.plants, ppc = (size_t)D.rows_per_chain, n_plants = (size_t)S.n_plants;
+  const double n = R.n;
+  for (size_t chain = blockIdx.x; chain < (size_t)R.n_chains; chain += gridDim.x) {
+    float *prow = R.partials + chain * R.floats;
+    double running = 0.0;      /* lane q < NPD_PPO_ROWVALS: the chain's sum of per-row double q */
+    for (size_t base = chain * ppc; base < (chain + 1) * ppc && base < plants; base += NPD_POLICY_TILE) {
+      const int in_tile = npd_policy_in_tile(plants, base);
+      __syncthreads();      /* (the tile before is done with every buffer) */
+      /* the tile's plants of the rollout: -1 beyond the tile and for an index outside the rollout's plants */
+      if (tid < NPD_POLICY_TILE) {
+        int64_t from = -1;
+        if (tid < in_tile) {
+          from = S.index ? (int64_t)S.index[base + tid] : (int64_t)(base + tid);
+          if (from < 0 || from >= (int64_t)n_plants) from = -1;
+        }
+        src[tid] = (int)from;
+      }
+      npd_policy_tile_zero(xs, 0, KC_pad, tid);      /* (once a tile: every slot's load overwrites the same cells) */
+      __syncthreads();
+      /* the restart in front of slot s and the poison a plant starts a slot with, lanes 0 .. 31 */
+      auto words = [&](int s) {
+        const int from = src[tid];
+        int restart = 0;
+        if (from >= 0 && s > 0) {
+          const size_t now = (size_t)s * n_plants + from, before = now - n_plants;
+          restart = S.episode[now] != S.episode[before] || (S.ended[before] & NPD_SEQ_CUT) != 0;
+        }
+        fresh[tid] = restart;
+        bad[tid] = from < 0;
+      };
+      auto first_of = [&](int row) -> const float * { return src[row] >= 0 ? S.first + (size_t)src[row] * H : nullptr; };
+      /* ---- the forward sweep: h in b1, the step kernel's cell gate by gate (gi into b2, gh into b3, r into b4, z into b5) */
+      for (int s = 0; s < T; s++) {
+        if (tid < NPD_POLICY_TILE) words(s);
+        __syncthreads();
+        const size_t cell0 = (size_t)s * plants + base;
+        if (D.obs_type) npd_policy_tile_load((const double *)D.obs + cell0 * KC, in_tile, KC, xs, bad, tid);
+        else npd_policy_tile_load((const float *)D.obs + cell0 * KC, in_tile, KC, xs, bad, tid);
+        if (s == 0) npd_seq_fill(b1, H, H_pad, tid, first_of);
+        else
+          for (int i = tid; i < H_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES)
+            if (fresh[i & (NPD_POLICY_TILE - 1)]) b1[(i / NPD_POLICY_TILE) * NPD_POLICY_STRIDE + (i & (NPD_POLICY_TILE - 1))] = 0.0f;
+        __syncthreads();
+        for (int gate = 0; gate < 3; gate++) {
+          npd_policy_layer(C.gate[gate], P.theta, P.padded, xs, b2, -1, wave, lane);
+          npd_policy_layer(C.gate[3 + gate], P.theta, P.padded, b1, b3, -1, (wave + 2) & (NPD_POLICY_WAVES - 1), lane);
+          __syncthreads();
+          for (int i = tid; i < H_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES) {
+            const int j = i / NPD_POLICY_TILE, plant = i & (NPD_POLICY_TILE - 1), o = j * NPD_POLICY_STRIDE + plant;
+            if (gate < 2) {
+              const float a = b2[o] + b3[o];
+              (gate ? b5 : b4)[o] = npd_core_sigma(a, C.gates);
+            } else {
+              const float gated = b4[o] * b3[o];
+              const float a = b2[o] + gated;
+              const float nn = npd_core_tau(a, C.gates);
+              const float h = b1[o];
+              const float away = h - nn;
+              const float kept = b5[o] * away;
+              const float next = nn + kept;
+              b1[o] = j < H && !bad[plant] ? next : 0.0f;
+            }
+          }
+          __syncthreads();
+        }
+        float *out = Q.hseq + cell0 * H;
+        for (int e = tid; e < in_tile * H; e += NPD_POLICY_LANES) {
+          const int row = e / H, k = e - row * H;
+          out[e] = b1[k * NPD_POLICY_STRIDE + row];
+        }
+      }
+      /* ---- the backward sweep */
+      __syncthreads();
+      npd_policy_tile_zero(b0, 0, H_pad, tid);
+      for (int s = T - 1; s >= 0; s--) {
+        const bool first = base == chain * ppc && s == T - 1;
+        const size_t cell0 = (size_t)s * plants + base, p = cell0 + tid;
+        __syncthreads();      /* (the slot behind is done with every buffer, and the forward sweep's h' are this workgroup's to read) */
+        for (int i = tid; i < NPD_PPO_ROWVALS * NPD_POLICY_TILE; i += NPD_POLICY_LANES) rowv[i] = 0.0;
+        if (tid < NPD_POLICY_TILE) {
+          words(s);
+          int b = 0;
+          if (tid < in_tile) {
+            const double old = (double)D.logp_old[p], adv = npd_ppo_load(D.adv, D.adv_type, p), ret = npd_ppo_load(D.ret, D.adv_type, p);
+            b = !(old - old == 0.0) || !(adv - adv == 0.0) || !(ret - ret == 0.0);
+            if (R.M.clip_vf > 0.0) { const float vo = R.M.value_old[p]; b |= !(vo - vo == 0.0f); }
+            for (int a = 0; a < A; a++) { const double x = npd_ppo_load(D.act, D.act_type, p * A + a); b |= !(x - x == 0.0); }
+          }
+          skip[tid] = b;
+        }
+        __syncthreads();
+        if (D.obs_type) npd_policy_tile_load((const double *)D.obs + cell0 * KC, in_tile, KC, xs, bad, tid);
+        else npd_policy_tile_load((const float *)D.obs + cell0 * KC, in_tile, KC, xs, bad, tid);
+        const float *hp = Q.hseq + cell0 * H;
+        npd_seq_fill(b1, H, H_pad, tid, [&](int row) -> const float * { return row < in_tile ? hp + (size_t)row * H : nullptr; });
+        __syncthreads();
+        for (int i = tid; i < KC * NPD_POLICY_TILE; i += NPD_POLICY_LANES)
+          if (bad[i & 31]) xs[(i >> 5) * NPD_POLICY_STRIDE + (i & 31)] = 0.0f;      /* (read by the cell's phase, behind the nets' barriers) */
+        const bool live = tid < in_tile, skipped = tid < NPD_POLICY_TILE && (bad[tid & 31] != 0 || skip[tid & 31] != 0);
+        /* the nets over h'_s: hidden activations b2 .. b4, deltas b5 and b6, the first layers' backs onto the carry */
+        npd_ppo_net<H_MAX>(P.actor, P, b1, buf + 2, head, b5, b6, prow, first, tid, b0, [&]() { npd_ppo_seeds_actor(P, D, n, head, b5, rowv, tid, live, skipped, p); });
+        npd_ppo_net<H_MAX>(P.critic, P, b1, buf + 2, head, b5, b6, prow, first, tid, b0, [&]() { npd_ppo_seeds_critic(P, D, R.M, n, head, b5, rowv, tid, live, skipped, p); });
+        if (tid < NPD_PPO_ROWVALS)
+          for (int r = 0; r < NPD_POLICY_TILE; r++) running = running + rowv[tid * NPD_POLICY_TILE + r];
+        /* the cell: h_s into b1, the gates again */
+        if (s == 0) npd_seq_fill(b1, H, H_pad, tid, first_of);
+        else {
+          const float *hb = Q.hseq + (cell0 - plants) * H;
+          npd_seq_fill(b1, H, H_pad, tid, [&](int row) -> const float * { return row < in_tile && !fresh[row] ? hb + (size_t)row * H : nullptr; });
+        }
+        __syncthreads();
+        const bool hard = C.gates == NPD_CORE_HARD;
+        npd_policy_layer(C.gate[0], P.theta, P.padded, xs, b2, -1, wave, lane);
+        npd_policy_layer(C.gate[3], P.theta, P.padded, b1, b6, -1, (wave + 2) & (NPD_POLICY_WAVES - 1), lane);
+        __syncthreads();
+        for (int i = tid; i < H_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES) {
+          const int o = (i / NPD_POLICY_TILE) * NPD_POLICY_STRIDE + (i & (NPD_POLICY_TILE - 1));
+          const float a = b2[o] + b6[o];
+          const float q = 0.25f * a;
+          const float y = q + 0.5f;
+          b2[o] = npd_core_sigma(a, C.gates);
+          b6[o] = hard && (y < 0.0f || y > 1.0f) ? 1.0f : 0.0f;
+        }
+        __syncthreads();
+        npd_policy_layer(C.gate[1], P.theta, P.padded, xs, b3, -1, wave, lane);
+        npd_policy_layer(C.gate[4], P.theta, P.padded, b1, b4, -1, (wave + 2) & (NPD_POLICY_WAVES - 1), lane);
+        __syncthreads();
+        for (int i = tid; i < H_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES) {
+          const int o = (i / NPD_POLICY_TILE) * NPD_POLICY_STRIDE + (i & (NPD_POLICY_TILE - 1));
+          const float a = b3[o] + b4[o];
+          const float q = 0.25f * a;
+          const float y = q + 0.5f;
+          b3[o] = npd_core_sigma(a, C.gates);
+          if (hard && (y < 0.0f || y > 1.0f)) b6[o] = b6[o] + 2.0f;
+        }
+        __syncthreads();
+        npd_policy_layer(C.gate[2], P.theta, P.padded, xs, b4, -1, wave, lane);
+        npd_policy_layer(C.gate[5], P.theta, P.padded, b1, b5, -1, (wave + 2) & (NPD_POLICY_WAVES - 1), lane);
+        __syncthreads();
+        /* a lane a cell: the candidate, then the cell backwards, in place */
+        for (int i = tid; i < H_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES) {
+          const int j = i / NPD_POLICY_TILE, plant = i & (NPD_POLICY_TILE - 1), o = j * NPD_POLICY_STRIDE + plant;
+          const float r = b2[o], z = b3[o], ghn = b5[o], h = b1[o], dh = b0[o];
+          const int flags = (int)b6[o];
+          const float gated = r * ghn;
+          const float an = b4[o] + gated;
+          const float nn = npd_core_tau(an, C.gates);
+          const float u = h - nn;
+          const float omz = 1.0f - z;
+          const float dn = dh * omz;
+          const float dz = dh * u;
+          const float direct = dh * z;
+          float dan, daz, dr, dar;
+          if (hard) {
+            dan = an < -1.0f || an > 1.0f ? 0.0f : dn;
+            dr = dan * ghn;
+            const float qz = dz * 0.25f, qr = dr * 0.25f;
+            daz = flags & 2 ? 0.0f : qz;
+            dar = flags & 1 ? 0.0f : qr;
+          } else {
+            const float sq = nn * nn;
+            const float slope = 1.0f - sq;
+            dan = dn * slope;
+            dr = dan * ghn;
+            const float sz = z * omz;
+            daz = dz * sz;
+            const float omr = 1.0f - r;
+            const float sr = r * omr;
+            dar = dr * sr;
+          }
+          const float dghn = dan * r;
+          const bool dead = j >= H || bad[plant] != 0;
+          b2[o] = dead ? 0.0f : dar;
+          b3[o] = dead ? 0.0f : daz;
+          b4[o] = dead ? 0.0f : dan;
+          b5[o] = dead ? 0.0f : dghn;
+          b0[o] = dead ? 0.0f : direct;
+        }
+        __syncthreads();
+        npd_ppo_dw(C.gate[0], prow, first, b2, xs, tid);
+        npd_ppo_dw(C.gate[1], prow, first, b3, xs, tid);
+        npd_ppo_dw(C.gate[2], prow, first, b4, xs, tid);
+        npd_ppo_dw(C.gate[3], prow, first, b2, b1, tid);
+        npd_ppo_dw(C.gate[4], prow, first, b3, b1, tid);
+        npd_ppo_dw(C.gate[5], prow, first, b5, b1, tid);
+        const npd_policy_layer_t *const layers[3] = {&C.gate[3], &C.gate[4], &C.gate[5]};
+        const float *const deltas[3] = {b2, b3, b5};
+        npd_ppo_back_onto<3>(layers, deltas, P.theta, b0, fresh, tid);
+      }
+    }
+    if (tid < NPD_PPO_ROWVALS) R.chain_stats[chain * NPD_PPO_ROWVALS + tid] = running;
+  }
+}
+
+/* ---- the launchers */
+static npd_ppo_run_t npd_ppo_seq_run(const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S) {
+  return npd_ppo_run(O, D, M, (int)(((int64_t)S->plants + D->rows_per_chain - 1) / D->rows_per_chain));
+}
+static void npd_ppo_seq_launch(const npb_policy_t *P, const npd_policy_core_t *C, const npb_ppo_desc_t *D, const npd_ppo_run_t &R, const npb_ppo_seq_t *S, float *hseq,
+                               hipStream_t stream) {
+  npd_ppo_seq_run_t Q = {};
+  Q.S = *S; Q.hseq = hseq;
+  const int cap = D->max_blocks > 0 ? D->max_blocks : 2048;
+  const dim3 grid((unsigned)(R.n_chains < cap ? R.n_chains : cap)), block(NPD_POLICY_LANES);
+  if (npd_policy_small(P, C->H)) hipLaunchKernelGGL((npb_ppo_seq_kernel<NPD_POLICY_SMALL_CELLS, NPD_POLICY_SMALL_WIDTH>), grid, block, 0, stream, *P, *C, R, Q);
+  else hipLaunchKernelGGL((npb_ppo_seq_kernel<NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX>), grid, block, 0, stream, *P, *C, R, Q);
+}
+extern "C" void npb_launch_ppo_grad_seq(const npb_policy_t *P, const npd_policy_core_t *C, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M,
+                                        const npb_ppo_seq_t *S, hipStream_t stream) {
+  const npd_ppo_run_t R = npd_ppo_seq_run(O, D, M, S);
+  npd_ppo_seq_launch(P, C, D, R, S, S->hidden ? S->hidden : O->hseq, stream);
+  npb_launch_ppo_reduce(P, O, &R, stream);
+}
+extern "C" void npb_launch_ppo_shard_sums_seq(const npb_policy_t *P, const npd_policy_core_t *C, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M,
+                                              const npb_ppo_seq_t *S, int64_t count_total, double *out, hipStream_t stream) {
+  npd_ppo_run_t R = npd_ppo_seq_run(O, D, M, S);
+  R.n = (double)count_total;
+  npd_ppo_seq_launch(P, C, D, R, S, S->hidden ? S->hidden : O->hseq, stream);
+  npb_launch_ppo_shard_reduce(P, &R, out, stream);
+}

@@ -2012,8 +2012,9 @@ class BatchedPlantEnv:
         ``policy_hidden()`` and restarts with the plant's episode -- the autoreset's restarts, ``reset``, ``restore`` and
         ``restore_from_bank``.  ``gates``: ``"soft"`` (GRUCell's sigmoid and tanh) or ``"hard"`` (piecewise linear, bit-exact).  With a
         rollout set, ``policy_rollout_hidden()`` has the state in front of slot 0 and the states beside ``final_obs``.
-        ``nuclear_sim_amd.recurrent`` is the same in numpy.  Training a recurrent policy on the device is not built: train on
-        ``rollout_minibatches(unit="plant")`` in torch and put the parameters back with ``policy_load``."""
+        ``nuclear_sim_amd.recurrent`` is the same in numpy.  A recurrent policy trains through time on the device, on whole sequences:
+        ``policy_train(..., unit="plant")``, or ``policy_grad_sequences`` on ``rollout_minibatches(unit="plant")`` and ``policy_adam``.
+        The row-wise calls (``policy_grad``, ``policy_train`` with the default unit) refuse it by name: rows carry no order."""
         if actor is None:
             if self._pol is not None:
                 _lib.check(self.L.npb_set_policy(self._h, None), self._h)
@@ -2301,6 +2302,103 @@ class BatchedPlantEnv:
         pol["shards_held"] = shards
         return out
 
+    # ------------------------------------------------------------------ training through time
+    def _ppo_seq(self, batch, d):
+        """``(npb_ppo_seq_t, tensors kept alive)`` of a ``unit="plant"`` minibatch whose descriptor ``d`` is made (its ``rows_per_chain``
+        counting the plants of a chain): its [t, count] shape, its
+        ``index``, and the rollout's ``episode`` and ``ended`` and the core's ``first`` from the handle -- or the batch's own ``episode``
+        [T, n], ``ended`` [T, n] and ``first`` [n, H], which ``index`` (None = identity) then points into"""
+        pol = self._policy_cell("training through time")
+        if not hasattr(self.L, "npb_policy_grad_seq"):
+            raise _lib.NpbError("libnpb.so has no npb_policy_grad_seq: rebuild")
+        H = pol["spec"]["core"]
+        shape = tuple(torch.as_tensor(batch["adv"]).shape)
+        if len(shape) != 2:
+            raise ValueError("a sequence minibatch is time-major, adv [t, count] (rollout_minibatches(unit='plant')), not %r" % (shape,))
+        t, count = shape
+        own = [batch.get(name) for name in ("episode", "ended", "first")]
+        if any(x is None for x in own):
+            if any(x is not None for x in own):
+                raise ValueError("episode, ended and first come together: all three, or none (the rollout's)")
+            ro = self._on("_roll")
+            if pol["first"] is None:
+                raise _lib.NpbError("the policy was set without a rollout (set_rollout, then set_policy): no state in front of slot 0")
+            own = [ro["tensors"]["episode"], ro["tensors"]["ended"], pol["first"]]
+        episode, ended, first = (torch.as_tensor(x).to(device=self.device).contiguous() for x in own)
+        if episode.dtype != torch.int32 or ended.dtype != torch.uint8 or first.dtype != torch.float32:
+            raise ValueError("episode is int32, ended uint8 and first float32")
+        n = first.shape[0]
+        if first.dim() != 2 or first.shape[1] != H or episode.dim() != 2 or episode.shape[1] != n or episode.shape[0] < t or ended.shape != episode.shape:
+            raise ValueError("episode and ended are [>= %d, n] and first [n, %d]" % (t, H))
+        index = batch.get("index")
+        if index is None and count != n:
+            raise ValueError("a minibatch of %d of the rollout's %d plants needs its index" % (count, n))
+        held = [episode, ended, first]
+        s = _lib.NpbPpoSeq()
+        s.t, s.plants, s.n_plants = t, count, n
+        s.episode, s.ended, s.first = episode.data_ptr(), ended.data_ptr(), first.data_ptr()
+        if index is not None:
+            index = torch.as_tensor(index).to(device=self.device).contiguous()
+            if index.dtype != torch.int32 or index.numel() != count:
+                raise ValueError("index must be int32 with one entry a sequence (%d)" % count)
+            s.index = index.data_ptr()
+            held.append(index)
+        return s, held
+
+    def policy_grad_sequences(self, batch, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0, max_grad_norm: float = 0.5,
+                              plants_per_chain: int = 32, diagnostics: bool = False, max_blocks: int = 0, clip_vf: float = 0.0, value_old=None) -> dict:
+        """``policy_grad`` for a policy with a core (npb_policy_grad_seq): the PPO loss of one minibatch of WHOLE SEQUENCES and its
+        gradient through both nets, through the cell and through time, on the device.  ``batch``: as ``rollout_minibatches(unit="plant")``
+        yields it, every tensor time-major [t, count, ...]; the restart words and the state in front of slot 0 are the handle's own
+        (the rollout's ``episode`` and ``ended``, ``policy_rollout_hidden()["first"]``), read through the batch's ``index`` -- or the
+        batch's own ``episode``, ``ended`` and ``first``.  Returns ``{"grad", "stats", "more"}`` as ``policy_grad`` does, and with
+        ``diagnostics`` ``logp_new``, ``value_new``, ``ratio`` [t, count] and ``hidden`` [t, count, H], the states under the current
+        parameters.  ``plants_per_chain`` (a positive multiple of 32) pins the order of the sums; no bit depends on ``max_blocks``.
+        ``first`` is the state the collecting parameters produced: after the first update of an iteration it is stale, as in every
+        recurrent PPO.  ``nuclear_sim_amd.recurrent.gradient`` is the same in numpy: bit for bit with hard gates and relu when fed the
+        device's ``ratio``."""
+        d, held = self._ppo_desc(batch, clip, vf_coef, ent_coef, max_grad_norm, plants_per_chain, max_blocks)
+        more, held_more = self._ppo_more(batch, d.count, clip_vf, value_old)
+        pol = self._policy_cell("policy_grad_sequences()")
+        s, held_seq = self._ppo_seq(batch, d)
+        t, count = s.t, s.plants
+        out = {}
+        with torch.cuda.device(self.device):
+            if diagnostics:
+                out = {"logp_new": torch.zeros((t, count), dtype=torch.float32, device=self.device),
+                       "value_new": torch.zeros((t, count), dtype=torch.float32, device=self.device),
+                       "ratio": torch.zeros((t, count), dtype=torch.float64, device=self.device),
+                       "hidden": torch.zeros((t, count, pol["spec"]["core"]), dtype=torch.float32, device=self.device)}
+                d.logp_new, d.value_new, d.ratio, s.hidden = out["logp_new"].data_ptr(), out["value_new"].data_ptr(), out["ratio"].data_ptr(), out["hidden"].data_ptr()
+            out["grad"] = torch.zeros(pol["theta"].numel(), dtype=torch.float32, device=self.device)
+            out["stats"] = torch.zeros(_lib.PPO_STATS, dtype=torch.float64, device=self.device)
+            out["more"] = torch.zeros(_lib.PPO_STATS_MORE, dtype=torch.float64, device=self.device)
+        _lib.check(self.L.npb_policy_grad_seq(self._h, ctypes.byref(d), None if more is None else ctypes.byref(more), ctypes.byref(s), self._stream()), self._h)
+        _lib.check(self.L.npb_policy_get_grad(self._h, ctypes.c_void_p(out["grad"].data_ptr()), self._stream()), self._h)
+        _lib.check(self.L.npb_policy_get_stats(self._h, ctypes.c_void_p(out["stats"].data_ptr()), self._stream()), self._h)
+        _lib.check(self.L.npb_policy_get_stats_more(self._h, ctypes.c_void_p(out["more"].data_ptr()), self._stream()), self._h)
+        pol["ppo_held"] = held + held_more + held_seq      # (alive while the launches read them)
+        return out
+
+    def policy_shard_sums_sequences(self, batch, count_total: int, clip: float = 0.2, vf_coef: float = 0.5, plants_per_chain: int = 32,
+                                    clip_vf: float = 0.0, value_old=None, out=None, max_blocks: int = 0) -> torch.Tensor:
+        """``policy_shard_sums`` for a policy with a core (npb_policy_shard_sums_seq): this shard's pinned double sums of one update
+        over ``count_total`` CELLS (t * plants of every shard) from a ``unit="plant"`` minibatch; ``policy_apply_shards`` and
+        ``policy_combine_shards`` take the vectors.  ``nuclear_sim_amd.recurrent.shard_sums`` is the same in numpy."""
+        L = self.policy_shard_size()
+        d, held = self._ppo_desc(batch, clip, vf_coef, 0.0, 0.0, plants_per_chain, max_blocks)
+        more, held_more = self._ppo_more(batch, d.count, clip_vf, value_old)
+        s, held_seq = self._ppo_seq(batch, d)
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = torch.zeros(L, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or out.numel() != L or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous float64 tensor of %d elements on %s" % (L, self.device))
+        _lib.check(self.L.npb_policy_shard_sums_seq(self._h, ctypes.byref(d), None if more is None else ctypes.byref(more), ctypes.byref(s), int(count_total),
+                                                    ctypes.c_void_p(out.data_ptr()), self._stream()), self._h)
+        self._pol["ppo_held"] = held + held_more + held_seq      # (alive while the launches read them)
+        return out
+
     @staticmethod
     def _update_counts(cells, batch_size, epochs, drop_last):
         """the rows of every update of one shard of ``cells`` cells, as ``rollout_minibatches`` cuts them"""
@@ -2311,7 +2409,7 @@ class BatchedPlantEnv:
         return one * int(epochs)
 
     def policy_train(self, batch_size, epochs: int = 1, seed: int = 0, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0,
-                     max_grad_norm: float = 0.5, rows_per_chain: int = 256, lr=3e-4, betas=(0.9, 0.999), eps: float = 1e-5,
+                     max_grad_norm: float = 0.5, rows_per_chain: Optional[int] = None, lr=3e-4, betas=(0.9, 0.999), eps: float = 1e-5,
                      clip_vf: float = 0.0, target_kl=None, more: bool = False, exchange=None, shard_cells=None, global_moments: bool = False,
                      **minibatches):
         """The optimiser's half of a PPO iteration: ``rollout_minibatches(batch_size, epochs, seed, **minibatches)`` and one
@@ -2334,8 +2432,15 @@ class BatchedPlantEnv:
         read back).  Every shard's update count under ``batch_size`` and ``drop_last`` is formed on the host before any
         device work, and a mismatch is refused by name; update i's ``count_total`` is the sum of the shards' rows of update i, and the
         update is ``policy_shard_sums``, ``exchange``, ``policy_apply_shards``: every shard ends with the same parameters, bit for bit,
-        with no broadcast.  The gate is taken on the global ``approx_kl``; the stats are the whole update's."""
+        with no broadcast.  The gate is taken on the global ``approx_kl``; the stats are the whole update's.
+        A POLICY WITH A CORE trains through time with ``unit="plant"``: every minibatch is whole sequences and an update is
+        npb_policy_update_seq (``policy_grad_sequences`` and the Adam step); ``rows_per_chain`` then counts the PLANTS of a chain (default
+        32; row-wise a chain is 256 rows by default), and every option above works as it does row-wise.  With the default unit a policy with a core is refused
+        by name: rows carry no order."""
         pol = self._on("_pol")
+        sequences = pol["spec"]["core"] is not None and minibatches.get("unit", "transition") == "plant"
+        if rows_per_chain is None:      # (a chain of sequences counts plants: one tile of them; a chain of rows is 256 rows, as it was)
+            rows_per_chain = 32 if sequences else 256
         kl_limit = 0.0
         if target_kl is not None:
             if not float(target_kl) > 0.0 or float(target_kl) == float("inf"):
@@ -2389,17 +2494,24 @@ class BatchedPlantEnv:
                 if totals is None:
                     d, held = self._ppo_desc(batch, clip, vf_coef, ent_coef, max_grad_norm, rows_per_chain)
                     m, held_more = self._ppo_more(batch, d.count, clip_vf, None, kl_limit)
+                    if sequences:
+                        s, held_seq = self._ppo_seq(batch, d)
+                        held = held + held_seq
                 with torch.cuda.device(self.device):
                     row = torch.zeros(_lib.PPO_STATS, dtype=torch.float64, device=self.device)
                     if more:
                         mores.append(torch.zeros(_lib.PPO_STATS_MORE, dtype=torch.float64, device=self.device))
                 if totals is not None:
-                    vec = self.policy_shard_sums(batch, totals[i], clip, vf_coef, rows_per_chain, clip_vf)
+                    vec = self.policy_shard_sums_sequences(batch, totals[i], clip, vf_coef, rows_per_chain, clip_vf) if sequences else \
+                        self.policy_shard_sums(batch, totals[i], clip, vf_coef, rows_per_chain, clip_vf)
                     held = pol["ppo_held"] + [vec]
                     every = exchange(vec)
                     if not isinstance(every, torch.Tensor) or every.shape != (len(cells), vec.numel()):
                         raise ValueError("exchange must return the [%d, %d] tensor of every shard's sums" % (len(cells), vec.numel()))
                     self.policy_apply_shards(every.contiguous(), totals[i], ent_coef, max_grad_norm, rate, (b1, b2), eps, kl_limit)
+                elif sequences:
+                    _lib.check(self.L.npb_policy_update_seq(self._h, ctypes.byref(d), None if m is None else ctypes.byref(m), ctypes.byref(s), rate, b1, b2, eps,
+                                                            self._stream()), self._h)
                 elif m is None:
                     _lib.check(self.L.npb_policy_update(self._h, ctypes.byref(d), rate, b1, b2, eps, self._stream()), self._h)
                 else:

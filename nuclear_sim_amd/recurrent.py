@@ -38,10 +38,55 @@ in front of slot 0, the restart rule applied.  The states in front of every late
 ``episode[t] != episode[t - 1]`` (the autoreset's restarts, and the caller's under autoreset: both bump the index) or
 ``ended[t - 1] & NPB_ROLLOUT_CUT`` (the caller's reset / restore between two recorded steps, which the env marks in the slot before).
 ``npb_reset``, ``npb_restore``, ``npb_restore_bank`` and the episode kernel restart nothing these two columns do not show: a restart in
-front of slot 0 is in ``first`` already."""
+front of slot 0 is in ``first`` already.
+
+TRAINING THROUGH TIME (``gradient``, ``shard_sums``; npb_policy_grad_seq, npb_policy_shard_sums_seq, nuclear_sim_amd/csrc/npb_ppo_seq.hip):
+PPO's loss over whole sequences and its gradient through both nets, through the cell and through time.  Everything it does not restate is
+``ppo``'s, whose functions it calls and whose bits it leaves alone.
+
+THE INPUTS.  One sequence minibatch of ``t`` slots by ``count`` plants, time-major as ``rollout_minibatches(unit="plant")`` yields it:
+``obs`` [t, count, K * C], ``act`` [t, count, A], ``logp_old``, ``adv``, ``ret`` and optionally ``value_old`` [t, count]; the restart words
+``episode`` and ``ended`` [t, count] of the same plants; ``first`` [count, H], the state in front of slot 0.  The seeds' divisor is
+``t * count``, or ``count_total`` for a shard.  ``first`` is the state the COLLECTING parameters produced: after the first update of an
+iteration it is stale.  That is inherent, and what every recurrent PPO does.  Truncated segments are not here: a sequence is differentiated
+whole.
+
+FORWARD.  ``replay``'s recurrence under the CURRENT theta: slot s reads ``h_s``, +0.0 where the plant restarted in front of s (``replay``'s
+rule: an episode change, or ``ended[s - 1] & ROLLOUT_CUT``); ``advance`` gives ``h'_s`` and the poison flag; both nets run
+``ppo.forward_keep`` over ``h'_s``.  ``cell_keep`` is ``cell`` with everything the backward pass reads.
+
+PER CELL ``ppo.rows``, unchanged, ``bad`` the poison flag.  A cell whose features are finite and whose ``act``, ``logp_old``, ``adv``,
+``ret`` or ``value_old`` is not is a skipped row as there: its seeds are +0.0, but the cell still runs and the carry still flows through
+it.  A plant marked not ``valid`` (the device: an index outside the rollout's plants) is poisoned and skipped in every slot.
+
+BACKWARD, s descending, all float32, every operation rounded on its own.  The nets as in ``ppo.backward``, and one ``back`` more, through
+their first layers and without a derivative (``h'`` is an input, not an activation):
+
+    dh' = (carry + back(delta_actor_layer0, W_actor0)) + back(delta_critic_layer0, W_critic0)            carry = +0.0 behind the last slot
+
+On a poisoned cell ``dh'``, every gate delta and the outgoing carry are +0.0 (its ``h'`` was the constant +0.0).  Otherwise, ``u = h - n``:
+
+    dn = dh' * (1.0f - z)        dz = dh' * u        direct = dh' * z
+    dan  = dn * T'               soft: T' = 1.0f - n * n         hard: +0.0 where the forward took a clamped branch (a < -1 or a > 1), else dn
+    dghn = dan * r               dr = dan * gh_n
+    daz  = dz * S'(z)            soft: S' = s * (1.0f - s)       hard: +0.0 where y < 0 or y > 1 (the forward's own strict tests), else d * 0.25f
+    dar  = dr * S'(r)            likewise
+    delta_i = [dar | daz | dan]          delta_h = [dar | daz | dghn]          (3H wide, GRUCell's row order)
+    carry_out = direct + back(delta_h, W_hh)
+
+``back(delta_h, W_hh)`` is ONE fmaf chain over the 3H rows of ``W_hh`` ascending, from +0.0 (``ppo.back``).  ``carry_out`` is then +0.0
+where the plant restarted in front of slot s.
+
+THE SUMS.  A chain is ``plants_per_chain`` plants (a positive multiple of 32, default 32) with all their slots.  The row order within a
+chain: tiles of 32 plants ascending, within a tile s DESCENDING, within a slot the plants ascending; ``ppo.chain_sums`` and
+``ppo.row_sums`` are fed the rows in that order (``order``), the last chain extended with +0.0 rows, which change no bit.  ``dW_ih, db_ih``
+come from ``(delta_i, x)`` and ``dW_hh, db_hh`` from ``(delta_h, h)``; the nets' as in ``ppo.backward``, their first layers reading
+``h'``.  ``x`` of a poisoned cell reads +0.0.  Across chains ``ppo.across``.  The gradient comes out in theta's layout; clipping, the
+statistics, the options and Adam are ``ppo``'s, unchanged.  THE INVARIANT: ``ppo.combine(shard_sums(..., count_total=t * count)[None],
+...)`` has the bits of ``gradient(...)``."""
 import numpy as np
 
-from . import policy
+from . import policy, ppo
 from .policy import fmaf, layer, activate, forward, noise, outputs      # noqa: F401  (the statement's pieces, for its readers)
 
 CORE_MAX = 128
@@ -220,3 +265,206 @@ class Policy(policy.Policy):
                 z = noise(self.seed, self.t, len(h2), self.n_axes, self.first_plant)
             self.t += 1
         return outputs(forward(actor, h2, self.activation), forward(critic, h2, self.activation)[:, 0], log_std, std, z, _rows(x), self.act_dtype)
+
+
+# ---------------------------------------------------------------------------------------------------------------- training through time
+
+PLANTS_PER_CHAIN = 32
+
+
+def cell_keep(core, x, h, gates="soft"):
+    """``cell`` with what it computed on the way: a dict of ``h2`` (``cell``'s own bits), ``gi``, ``gh`` [n, 3H], ``r``, ``z``, ``n`` and
+    the three pre-activations ``ar``, ``az``, ``an`` [n, H]"""
+    W_ih, W_hh, b_ih, b_hh = core
+    x, h = np.asarray(x, dtype=np.float32), np.asarray(h, dtype=np.float32)
+    H = h.shape[1]
+    with np.errstate(invalid="ignore", over="ignore"):
+        gi, gh = layer(x, W_ih, b_ih), layer(h, W_hh, b_hh)
+        ar = (gi[:, :H] + gh[:, :H]).astype(np.float32)
+        az = (gi[:, H:2 * H] + gh[:, H:2 * H]).astype(np.float32)
+        r, z = sigma(ar, gates), sigma(az, gates)
+        an = (gi[:, 2 * H:] + (r * gh[:, 2 * H:]).astype(np.float32)).astype(np.float32)
+        n = tau(an, gates)
+        h2 = (n + (z * (h - n).astype(np.float32)).astype(np.float32)).astype(np.float32)
+    return {"h2": h2, "gi": gi, "gh": gh, "r": r, "z": z, "n": n, "ar": ar, "az": az, "an": an}
+
+
+def sigma_slope(d, a, s, gates):
+    """``d * S'``: float32 elementwise, of the pre-activation a and S(a) = s"""
+    one = np.float32(1.0)
+    if gates == "hard":
+        y = (np.float32(0.25) * a).astype(np.float32) + np.float32(0.5)
+        return np.where((y < 0) | (y > 1), np.float32(0.0), (d * np.float32(0.25)).astype(np.float32)).astype(np.float32)
+    return (d * (s * (one - s).astype(np.float32)).astype(np.float32)).astype(np.float32)
+
+
+def tau_slope(d, a, n, gates):
+    """``d * T'``"""
+    if gates == "hard":
+        return np.where((a < -1) | (a > 1), np.float32(0.0), d).astype(np.float32)
+    return (d * (np.float32(1.0) - (n * n).astype(np.float32)).astype(np.float32)).astype(np.float32)
+
+
+def cell_back(core, K, dh2, h, bad, gates="soft"):
+    """one cell backwards: ``(delta_i, delta_h, carry_out)`` of ``dh2`` = dh', what ``cell_keep`` kept (K) and the states h it read; the
+    restart in front of the slot is the caller's"""
+    W_hh = core[1]
+    one = np.float32(1.0)
+    bad = np.asarray(bad, dtype=bool)
+    with np.errstate(invalid="ignore", over="ignore"):
+        dh2 = np.where(bad[:, None], np.float32(0.0), dh2).astype(np.float32)
+        r, z, n, H = K["r"], K["z"], K["n"], h.shape[1]
+        ghn = K["gh"][:, 2 * H:]
+        u = (h - n).astype(np.float32)
+        dn, dz, direct = (dh2 * (one - z).astype(np.float32)).astype(np.float32), (dh2 * u).astype(np.float32), (dh2 * z).astype(np.float32)
+        dan = tau_slope(dn, K["an"], n, gates)
+        dghn, dr = (dan * r).astype(np.float32), (dan * ghn).astype(np.float32)
+        daz, dar = sigma_slope(dz, K["az"], z, gates), sigma_slope(dr, K["ar"], r, gates)
+        parts = [np.where(bad[:, None], np.float32(0.0), v).astype(np.float32) for v in (dar, daz, dan, dghn, direct)]
+        dar, daz, dan, dghn, direct = parts
+        delta_i, delta_h = np.concatenate([dar, daz, dan], axis=1), np.concatenate([dar, daz, dghn], axis=1)
+        carry = (direct + ppo.back(delta_h, W_hh)).astype(np.float32)
+    return delta_i, delta_h, carry
+
+
+def restarts(episode, ended):
+    """bool [t, count]: the plant restarted in front of slot s (``replay``'s rule; False at s = 0: that restart is in ``first``)"""
+    episode, ended = np.asarray(episode), np.asarray(ended)
+    out = np.zeros(episode.shape, dtype=bool)
+    out[1:] = (episode[1:] != episode[:-1]) | ((ended[:-1] & ROLLOUT_CUT) != 0)
+    return out
+
+
+def order(t, count, plants_per_chain=PLANTS_PER_CHAIN):
+    """``(rows, rows_per_chain)``: the flat cells ``s * count + p`` in the sums' order -- per chain of ``plants_per_chain`` plants the tiles
+    of 32 plants ascending, within a tile s descending, within a slot the plants ascending -- every chain extended with -1 (a +0.0 row) to
+    ``rows_per_chain = t * plants_per_chain`` rows"""
+    t, count, ppc = int(t), int(count), int(plants_per_chain)
+    if ppc < ppo.TILE or ppc % ppo.TILE:
+        raise ValueError("plants_per_chain must be a positive multiple of 32, not %r" % (plants_per_chain,))
+    rows = []
+    for c0 in range(0, count, ppc):
+        chain = [s * count + p for p0 in range(c0, min(c0 + ppc, count), ppo.TILE) for s in range(t - 1, -1, -1) for p in range(p0, min(p0 + ppo.TILE, c0 + ppc, count))]
+        rows += chain + [-1] * (t * ppc - len(chain))
+    return np.asarray(rows, dtype=np.int64), t * ppc
+
+
+def _ordered(x, rows):
+    """x [cells, ...] in the sums' order, a row of +0.0 where rows is -1"""
+    x = np.asarray(x)
+    return np.concatenate([x, np.zeros((1,) + x.shape[1:], x.dtype)])[rows]
+
+
+def _sweep(theta, cells, n_axes, actor, critic, activation, core, gates, obs, act, logp_old, adv, ret, episode, ended, first, clip, vf_coef,
+           plants_per_chain, ratio, value_old, clip_vf, count_total, valid, wide):
+    """what ``gradient`` and ``shard_sums`` share: ``(parts, R, rows, rpc, nets, hidden, gate deltas)`` -- the weights' and biases' sums in
+    theta's order (float32, or the float64 sums as they are with ``wide``), ``ppo.rows``'s dict over the t * count cells (time-major), the
+    sums' order, the states h' [t, count, H], and ``(delta_i, delta_h)`` [t, count, 3H]"""
+    obs = np.asarray(obs)
+    t, count = obs.shape[:2]
+    N, A, H = t * count, int(n_axes), int(core)
+    ppo.check(N, ppo.TILE, clip)
+    rows, rpc = order(t, count, plants_per_chain)
+    gru, a_net, c_net, log_std, std = unpack(theta, cells, A, actor, critic, H)
+    with np.errstate(over="ignore", invalid="ignore"):
+        x = obs.reshape(t, count, -1).astype(np.float32)
+    valid = np.ones(count, dtype=bool) if valid is None else np.asarray(valid, dtype=bool)
+    fresh = restarts(np.asarray(episode).reshape(t, count), np.asarray(ended).reshape(t, count))
+    # forward, s ascending
+    h = np.where(valid[:, None], np.asarray(first, dtype=np.float32).reshape(count, H), np.float32(0.0)).astype(np.float32)
+    hs, h2s, bads, keeps = [], [], [], []
+    for s in range(t):
+        h = h.copy()
+        h[fresh[s]] = np.float32(0.0)
+        bad = ~np.isfinite(x[s]).all(axis=1) | ~valid
+        xs = x[s].copy()
+        xs[bad] = np.float32(0.0)
+        K = cell_keep(gru, xs, h, gates)
+        h2 = K["h2"].copy()
+        h2[bad] = np.float32(0.0)
+        hs.append(h); h2s.append(h2); bads.append(bad); keeps.append((xs, K))
+        h = h2
+    hidden, bad_all = np.stack(h2s), np.stack(bads).reshape(N)
+    flat = hidden.reshape(N, H)
+    a_in, mean = ppo.forward_keep(a_net, flat, activation)
+    c_in, value = ppo.forward_keep(c_net, flat, activation)
+    R = ppo.rows(mean, value[:, 0], log_std, std, np.asarray(act).reshape(N, A), np.asarray(logp_old).reshape(N), np.asarray(adv).reshape(N),
+                 np.asarray(ret).reshape(N), bad_all, clip, vf_coef, None if ratio is None else np.asarray(ratio).reshape(N),
+                 None if value_old is None else np.asarray(value_old).reshape(N), clip_vf, N if count_total is None else count_total)
+    # the nets backward over every cell at once (a row's deltas depend on that row alone), keeping every layer's delta
+    deltas = []
+    for net, inputs, seed in ((a_net, a_in, R["dmean"]), (c_net, c_in, R["dv"][:, None])):
+        delta, per = np.asarray(seed, dtype=np.float32), [None] * len(net)
+        for l in range(len(net) - 1, -1, -1):
+            per[l] = delta
+            delta = ppo.back(delta, net[l][0])
+            if l:
+                delta = ppo.through(delta, inputs[l], activation)
+        deltas.append((per, delta.reshape(t, count, H)))      # (the last one: back through layer 0, no derivative)
+    # the cell backward through time, s descending
+    carry = np.zeros((count, H), dtype=np.float32)
+    d_i, d_h = np.zeros((t, count, 3 * H), np.float32), np.zeros((t, count, 3 * H), np.float32)
+    for s in range(t - 1, -1, -1):
+        dh2 = ((carry + deltas[0][1][s]).astype(np.float32) + deltas[1][1][s]).astype(np.float32)
+        d_i[s], d_h[s], carry = cell_back(gru, keeps[s][1], dh2, hs[s], bads[s], gates)
+        carry[fresh[s]] = np.float32(0.0)
+    # the sums, in the chains' order
+    def sums(delta, inputs):
+        dW, db = ppo.chain_sums(_ordered(delta, rows), _ordered(inputs, rows), rpc)
+        dW, db = ppo.across(dW), ppo.across(db)
+        return [dW.reshape(-1), db] if wide else [dW.astype(np.float32).reshape(-1), db.astype(np.float32)]
+    xs_all, h_all = np.stack([k[0] for k in keeps]).reshape(N, -1), np.stack(hs).reshape(N, H)
+    (dW_ih, db_ih), (dW_hh, db_hh) = sums(d_i.reshape(N, -1), xs_all), sums(d_h.reshape(N, -1), h_all)
+    parts = [dW_ih, db_ih, dW_hh, db_hh]
+    for (per, _), inputs in zip(deltas, (a_in, c_in)):
+        for l in range(len(per)):
+            parts += sums(per[l], inputs[l])
+    return parts, R, rows, rpc, (log_std, std), hidden, (d_i, d_h)
+
+
+def gradient(theta, cells, n_axes, actor, critic, activation, core, gates, obs, act, logp_old, adv, ret, episode, ended, first, clip=0.2,
+             vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, plants_per_chain=PLANTS_PER_CHAIN, ratio=None, value_old=None, clip_vf=0.0,
+             stopped=False, kl_limit=0.0, valid=None, keep=False):
+    """``{"grad", "stats", "more", "rows", "logp_new", "value_new", "ratio", "hidden"}`` of one sequence minibatch: what ``ppo.gradient``
+    returns, grad in theta's layout with the core in front; ``logp_new``, ``value_new``, ``ratio`` [t, count]; ``hidden`` [t, count, H]
+    the states h' under the current theta.  ``ratio``: the device's own values back, as ``ppo.gradient`` takes them.  ``keep``: also ``delta_i`` and ``delta_h``
+    [t, count, 3H], every cell's gate deltas"""
+    parts, R, rows, rpc, (log_std, _), hidden, gates_d = _sweep(theta, cells, n_axes, actor, critic, activation, core, gates, obs, act, logp_old, adv, ret,
+                                                       episode, ended, first, clip, vf_coef, plants_per_chain, ratio, value_old, clip_vf, None, valid, False)
+    t, count = hidden.shape[:2]
+    A = int(n_axes)
+
+    def total(name):
+        return ppo.row_sums(_ordered(R[name], rows), rpc)
+    dls = (total("dls") - np.float64(ent_coef)).astype(np.float32)
+    g, norm = ppo.clip_grad(np.concatenate(parts + [dls, np.zeros(A, np.float32)]), A, max_grad_norm)
+    n = np.float64(t * count)
+    sums = {name: total(name) for name in ("policy_loss", "value_loss", "kl", "clipped", "skipped", "vf_clipped", "ret", "ret2", "diff", "diff2")}
+    stats = {"policy_loss": sums["policy_loss"] / n, "value_loss": sums["value_loss"] / n, "entropy": ppo.entropy(log_std),
+             "approx_kl": sums["kl"] / n, "clip_fraction": sums["clipped"] / n, "skipped": sums["skipped"], "grad_norm": norm, "count": n}
+    now, applied = ppo.gate(stopped, stats["approx_kl"], kl_limit) if float(kl_limit) > 0.0 else (False, True)
+    more = {"vf_clip_fraction": sums["vf_clipped"] / n,
+            "explained_variance": ppo.explained_variance(sums["ret"], sums["ret2"], sums["diff"], sums["diff2"], n - sums["skipped"]),
+            "applied": np.float64(applied), "stopped": np.float64(now)}
+    out = {"grad": g, "stats": stats, "more": more, "rows": R, "logp_new": R["logp_new"].reshape(t, count), "value_new": R["value_new"].reshape(t, count),
+           "ratio": R["ratio"].reshape(t, count), "hidden": hidden}
+    if keep:
+        out["delta_i"], out["delta_h"] = gates_d
+    return out
+
+
+def shard_sums(theta, cells, n_axes, actor, critic, activation, core, gates, obs, act, logp_old, adv, ret, episode, ended, first, count_total,
+               clip=0.2, vf_coef=0.5, plants_per_chain=PLANTS_PER_CHAIN, ratio=None, value_old=None, clip_vf=0.0, valid=None):
+    """a shard's vector, float64 [``ppo.shard_size``]: ``gradient``'s sums up to, but not including, the narrowing, every seed divided by
+    ``(double)count_total``, the cells of the whole update (``ppo.shard_sums`` says what for)"""
+    obs = np.asarray(obs)
+    if int(count_total) < obs.shape[0] * obs.shape[1]:
+        raise ValueError("count_total must be >= the shard's %d cells, not %r" % (obs.shape[0] * obs.shape[1], count_total))
+    parts, R, rows, rpc, _, _, _ = _sweep(theta, cells, n_axes, actor, critic, activation, core, gates, obs, act, logp_old, adv, ret, episode, ended, first,
+                                       clip, vf_coef, plants_per_chain, ratio, value_old, clip_vf, count_total, valid, True)
+    dls = np.zeros(8, dtype=np.float64)
+    dls[:int(n_axes)] = ppo.row_sums(_ordered(R["dls"], rows), rpc)
+    tail = np.array([ppo.row_sums(_ordered(R[name], rows), rpc) for name in ppo.SHARD_ROWS[8:]], dtype=np.float64)
+    out = np.concatenate(parts + [dls, tail])
+    assert out.size == ppo.shard_size(np.asarray(theta).size, n_axes)
+    return out
