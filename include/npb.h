@@ -1270,7 +1270,7 @@ NPB_API int npb_rollout_advantages(NpbHandle *h, const npb_rollout_advantages_de
  * rollouts has the normaliser's section below (npb_set_normalizer), which shares this section's tree.  NPB_VERSION stays 154: a binding
  * detects the entry points by name. */
 #define NPB_MINIBATCH_ROUNDS 6
-enum { NPB_MINIBATCH_TRANSITION = 0, NPB_MINIBATCH_PLANT = 1 };
+enum { NPB_MINIBATCH_TRANSITION = 0, NPB_MINIBATCH_PLANT = 1, NPB_MINIBATCH_SEGMENT = 2 /* npb_rollout_minibatch_segments alone */ };
 typedef struct npb_moments_desc_t {
   const void *src;               /* device [rows][cols], contiguous */
   int type;                      /* NPB_ROLLOUT_F32 | NPB_ROLLOUT_F64 */
@@ -1663,7 +1663,7 @@ NPB_API int npb_policy_combine_shards(NpbHandle *h, const npb_ppo_shards_t *shar
  * ended [T][n_plants] and the core's first [n_plants][H]; hidden, optional, receives every cell's h'.  The kernel reads a plant's restart words and its state in front of slot 0
  * through index; an index outside 0 .. n_plants - 1 makes every cell of that plant a skipped, poisoned cell and nothing is read through it.
  * first is the state the COLLECTING parameters produced: after the first update of an iteration it is stale; that is inherent, and what
- * every recurrent PPO does.  Truncated segments are not here: a sequence is differentiated whole.
+ * every recurrent PPO does.  Here a sequence is differentiated whole; truncated segments have the section below (TRUNCATED SEGMENTS).
  * Forward: the step's recurrence under the current theta.  Slot s reads h_s, +0.0 where the plant restarted in front of s (episode[s] !=
  * episode[s - 1], or ended[s - 1] & NPB_ROLLOUT_CUT; a restart in front of slot 0 is in first); the cell gives h'_s, +0.0 on a poisoned
  * cell (a feature that is not finite); both nets read h'_s.  Per cell the row-wise epilogue, unchanged; a cell whose features are finite
@@ -1694,7 +1694,7 @@ NPB_API int npb_policy_combine_shards(NpbHandle *h, const npb_ppo_shards_t *shar
  * a workspace the handle grows on demand) and a backward sweep that recomputes the gates; f32 matrix cores, no atomics, no scratch.
  * Measured on an MI355X (tools/recurrent_train_cost.py): one update of t = 128 through a cell of 64 and (64, 64) nets takes 21.0 ms at
  * 4 096 plants and 30.1 ms at 8 192 (the same BPTT in eager torch: 26.3 / 39.8 ms); serial in t, plants / 32 workgroups.
- * Not here: truncated segments; sequences longer than one rollout; the exchange between shards (the caller's all-gather). */
+ * Not here: sequences longer than one rollout; the exchange between shards (the caller's all-gather).  Truncated segments: the section below. */
 typedef struct npb_ppo_seq_t {
   int t, plants;                             /* slots and sequences of the minibatch: desc->count == t * plants */
   const int32_t *index;                      /* device [plants]: the rollout's plant of every sequence, or NULL = identity */
@@ -1710,6 +1710,68 @@ NPB_API int npb_policy_update_seq(NpbHandle *h, const npb_ppo_desc_t *desc, cons
                                   double b2, double eps, void *stream);
 NPB_API int npb_policy_shard_sums_seq(NpbHandle *h, const npb_ppo_desc_t *desc, const npb_ppo_more_t *more, const npb_ppo_seq_t *seq, int64_t count_total,
                                       double *out, void *stream);
+
+/* TRUNCATED SEGMENTS (the entry points below; a binding detects them by name, NPB_VERSION stays 154; no existing struct changes): truncated
+ * back-propagation through time for a policy with a core.  The rollout's t recorded slots are cut into chunks = t / every segments of
+ * `every` slots; each starts from the state RECORDED in front of its first slot and is differentiated within itself only.  A segment id is
+ * g = c * n_plants + p: chunk c, plant p, slots c * every .. c * every + every - 1 of plant p.  A segment of L slots with a stored start state
+ * IS what the section above calls a sequence -- t = L, a `first` row, restart words found through an index -- so nothing of the loss, the
+ * backward pass, the sums or the optimiser is restated.  nuclear_sim_amd/recurrent.py (starts, segment_words, gradient_segments,
+ * shard_sums_segments) and rollout.py (minibatch with unit "segment") state it in numpy, out of the functions they already have.  Opt-in: a
+ * handle that never calls these computes, in every entry point, the bits it computed before.
+ * npb_policy_core_segments(h, every, starts, rows): starts a device float tensor [rows][n_plants][H] of the caller's, rows >= ceil(T / every), T
+ *   the set rollout's horizon.  On the step recorded into slot s of the set rollout with s % every == 0 the run of h that the cell kernel read,
+ *   the restart rule applied (+0.0 for a restarted plant), goes into row s / every -- what `first` receives at slot 0: starts[0] equals first
+ *   bit for bit, and first is written as before.  Steps at other slots write nothing; npb_rollout_begin starts over at row 0.  every = 0 clears
+ *   it (starts and rows are not read).  It follows `first`: set after npb_set_rollout and npb_set_policy_core, dropped with the policy.
+ *   npb_policy_core_segments_check(every, starts, rows, horizon, core_width): that check alone, NULL = accepted, else the reason: no core
+ *   (core_width < 1); no rollout (horizon < 1); every < 0 or every > horizon; rows < ceil(horizon / every); a NULL or misaligned starts (4-byte
+ *   aligned).  every == 0 is accepted with anything.
+ * npb_rollout_minibatch_segments(h, desc, every, stream): npb_rollout_minibatch with desc->unit == NPB_MINIBATCH_SEGMENT: N = chunks *
+ *   n_plants; index[j] = permutation(N)[first + j] is a segment id g; every output is time-major [every][count]..., out[s][j] = src[c * every +
+ *   s][p].  The normalisation, the permutation and the types are unchanged; the kernel is the same, its `slots` every and its source c * every
+ *   slots down.  npb_minibatch_segments_check(desc, every, n_plants, t, features_cells, n_axes, n_extras): what npb_minibatch_check refuses,
+ *   and a unit that is not NPB_MINIBATCH_SEGMENT, every < 1, every > t, t % every != 0 (ragged last segments are not here).
+ *   npb_rollout_minibatch refuses NPB_MINIBATCH_SEGMENT as an unknown unit: its descriptor has no room for every.
+ * npb_policy_grad_segments / _update_segments / _shard_sums_segments(h, desc, more, seq, seg, ...): their _seq forms with npb_ppo_segments_t
+ *   {every, chunks} beside npb_ppo_seq_t, whose fields then mean: seq->t == every; seq->plants the SEGMENTS of the minibatch; seq->n_plants the
+ *   rollout's plants; seq->index[j] = g; seq->first = starts read as [chunks * n_plants][H], row g; episode and ended [>= chunks * every]
+ *   [n_plants].  The kernel's only differences: an index decodes to (c, p) = (g / n_plants, g % n_plants); a g outside 0 .. chunks * n_plants - 1
+ *   poisons the sequence and nothing is read through it; the restart words of local slot s > 0 are read at rollout rows c * every + s and
+ *   c * every + s - 1, column p; the restart in front of local slot 0 is in starts already and no word at row c * every - 1 is read; the state
+ *   in front of local slot 0 is starts row g; the carry out of local slot 0 is dropped -- that is the truncation.  The order of the sums is
+ *   unchanged (chains of rows_per_chain SEGMENTS: tiles ascending, slots descending, segments ascending), and so are the epilogue, clip_vf,
+ *   the gate, more, Adam, and the shard sums with count_total counting cells.  The h' workspace stays count * H floats.
+ *   npb_ppo_segments_check(desc, seq, seg, features_cells, n_axes): what npb_ppo_seq_check refuses, a NULL seg, every < 1, chunks < 1,
+ *   seq->t != every, chunks * every * n_plants beyond 2^31 - 1.
+ * npb_policy_segment_starts(h, every, stream): the refresh.  After the first update of an iteration the stored states are stale.  One
+ *   forward-only launch recomputes rows 1 .. chunks - 1 of the set starts under the CURRENT theta from the rollout's own tensors: for every
+ *   plant the recurrence from `first` over the recorded obs slots, the kernel's restart and poison rules; row c receives the state read in
+ *   front of slot c * every; row 0 is left alone.  One workgroup per tile of 32 plants, serial in t: the gradient kernel's forward sweep, the
+ *   same code.  Under the collecting parameters it reproduces the recorded rows bit for bit, soft gates included.  Refused by name: no core,
+ *   no rollout, no starts set, every not the set one, nothing recorded, t % every != 0.
+ * Measured on an MI355X (tools/recurrent_train_cost.py --segments, profiles/segment_train_cost.json): one update of t = 128 through a cell of
+ *   64 and (64, 64) nets over all segments of 16 takes 7.8 / 15.6 / 31.4 ms at 2 048 / 4 096 / 8 192 plants against 19.8 / 20.6 / 30.0 ms over
+ *   whole sequences in the same run: faster below 8 192 plants, 5 % slower at 8 192, where the chip is already full.  Recording adds nothing
+ *   measurable to a step; the refresh launch takes 1.7 ms over 128 slots.
+ * Not here: ragged last segments (t % every != 0 is refused by name); burn-in slots and overlapping segments; segments longer than one
+ * rollout; per-slot storage of every state; LSTM cells; any change to the row-wise entry points or to the plant kernels. */
+typedef struct npb_ppo_segments_t {
+  int every;                                 /* L: the slots of a segment; seq->t */
+  int chunks;                                /* t / L: the rows of starts; a segment id is c * n_plants + p with c < chunks */
+} npb_ppo_segments_t;
+NPB_API int npb_policy_core_segments(NpbHandle *h, int every, float *starts, int rows);
+NPB_API const char *npb_policy_core_segments_check(int every, const float *starts, int rows, int horizon, int core_width);
+NPB_API int npb_rollout_minibatch_segments(NpbHandle *h, const npb_minibatch_desc_t *desc, int every, void *stream);
+NPB_API const char *npb_minibatch_segments_check(const npb_minibatch_desc_t *desc, int every, int n_plants, int t, int features_cells, int n_axes, int n_extras);
+NPB_API const char *npb_ppo_segments_check(const npb_ppo_desc_t *desc, const npb_ppo_seq_t *seq, const npb_ppo_segments_t *seg, int features_cells, int n_axes);
+NPB_API int npb_policy_grad_segments(NpbHandle *h, const npb_ppo_desc_t *desc, const npb_ppo_more_t *more, const npb_ppo_seq_t *seq, const npb_ppo_segments_t *seg,
+                                     void *stream);
+NPB_API int npb_policy_update_segments(NpbHandle *h, const npb_ppo_desc_t *desc, const npb_ppo_more_t *more, const npb_ppo_seq_t *seq, const npb_ppo_segments_t *seg,
+                                       double lr, double b1, double b2, double eps, void *stream);
+NPB_API int npb_policy_shard_sums_segments(NpbHandle *h, const npb_ppo_desc_t *desc, const npb_ppo_more_t *more, const npb_ppo_seq_t *seq,
+                                           const npb_ppo_segments_t *seg, int64_t count_total, double *out, void *stream);
+NPB_API int npb_policy_segment_starts(NpbHandle *h, int every, void *stream);
 
 /* ONE NORMALISER AND ONE SET OF ADVANTAGE MOMENTS ACROSS SHARDS (the entry points below; a binding detects them by name, NPB_VERSION
  * stays 154; no new struct).  What still made a sharded run W different runs: every shard folded only its own plants into its running

@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from .ppo_abi import PPO_SHARD_ROWS, PPO_SHARDS_MAX, PPO_STATS_MORE, NpbPpoMore, NpbPpoShards
-from .recurrent_abi import POLICY_GATES, NpbPolicyCore, NpbPpoSeq
+from .recurrent_abi import POLICY_GATES, NpbPolicyCore, NpbPpoSeq, NpbPpoSegments
 from .schema import PARAMS, SCHEMA
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -907,7 +907,7 @@ class NpbRolloutAdvantagesDesc(ctypes.Structure):
 # include/npb.h npb_moments_desc_t / npb_minibatch_desc_t: the pinned moments and one shuffled minibatch of the rollout (npb_rollout_moments,
 # npb_rollout_minibatch)
 MINIBATCH_ROUNDS = 6
-MINIBATCH_UNITS = {"transition": 0, "plant": 1}                        # NPB_MINIBATCH_TRANSITION / NPB_MINIBATCH_PLANT (rollout.UNITS)
+MINIBATCH_UNITS = {"transition": 0, "plant": 1, "segment": 2}          # NPB_MINIBATCH_TRANSITION / _PLANT / _SEGMENT (rollout.UNITS)
 
 
 class NpbMomentsDesc(ctypes.Structure):
@@ -1261,6 +1261,16 @@ ENTRY_POINTS = (
         "npb_policy_grad_seq": (None, [_vp, _P(NpbPpoDesc), _P(NpbPpoMore), _P(NpbPpoSeq), _vp]),
         "npb_policy_update_seq": (None, [_vp, _P(NpbPpoDesc), _P(NpbPpoMore), _P(NpbPpoSeq), _cd, _cd, _cd, _cd, _vp]),
         "npb_policy_shard_sums_seq": (None, [_vp, _P(NpbPpoDesc), _P(NpbPpoMore), _P(NpbPpoSeq), _i64, _vp, _vp])}),
+    ("npb_policy_core_segments", {     # truncated segments: stored start states, segment minibatches, their gradient, the refresh
+        "npb_policy_core_segments": (None, [_vp, _ci, _vp, _ci]),
+        "npb_policy_core_segments_check": (_cs, [_ci, _vp, _ci, _ci, _ci]),
+        "npb_rollout_minibatch_segments": (None, [_vp, _P(NpbMinibatchDesc), _ci, _vp]),
+        "npb_minibatch_segments_check": (_cs, [_P(NpbMinibatchDesc), _ci, _ci, _ci, _ci, _ci, _ci]),
+        "npb_ppo_segments_check": (_cs, [_P(NpbPpoDesc), _P(NpbPpoSeq), _P(NpbPpoSegments), _ci, _ci]),
+        "npb_policy_grad_segments": (None, [_vp, _P(NpbPpoDesc), _P(NpbPpoMore), _P(NpbPpoSeq), _P(NpbPpoSegments), _vp]),
+        "npb_policy_update_segments": (None, [_vp, _P(NpbPpoDesc), _P(NpbPpoMore), _P(NpbPpoSeq), _P(NpbPpoSegments), _cd, _cd, _cd, _cd, _vp]),
+        "npb_policy_shard_sums_segments": (None, [_vp, _P(NpbPpoDesc), _P(NpbPpoMore), _P(NpbPpoSeq), _P(NpbPpoSegments), _i64, _vp, _vp]),
+        "npb_policy_segment_starts": (None, [_vp, _ci, _vp])}),
     ("npb_normalizer_apply_shards", {     # one normaliser and one set of advantage moments across shards
         "npb_normalizer_shard_count": (None, [_vp]),
         "npb_normalizer_shards_check": (_cs, [_vp, _ci]),

@@ -107,6 +107,9 @@ struct NpbHandle {
   /* npb_set_policy_core: the GRU cell in front of both nets -- its six gate layers, the caller's hidden, first and final, and the restart
    * words primed and seen on the device (base core.primed; NULL = the policy has no core); dropped with the policy */
   npd_policy_core_t core;
+  /* npb_policy_core_segments: the caller's stored segment states [seg_rows][n][H], a row every seg_every slots of the rollout (0 = off);
+   * dropped with the policy */
+  float *seg_starts; int seg_every, seg_rows;
   /* npb_policy_grad / npb_policy_adam: the gradient, the statistics, the optimiser's m, v and step (base ppo.stats) and the chains'
    * workspace (base ppo.chain_stats), allocated on first use, dropped with the policy */
   npb_ppo_t ppo;
@@ -1234,6 +1237,8 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
     if (h->core.primed) {      /* with a core: the cell first, its hidden state restarted with the episode; slot 0 of a rollout keeps the state it read */
       cell.h = cell.h_out = h->core.hidden; cell.first_out = h->ro.n_final && h->ro.t == 0 ? h->core.first : nullptr;
       cell.primed = h->core.primed; cell.seen = h->core.seen; cell.index = h->ep_index; cell.remember = 1;
+      if (h->seg_every && h->ro.n_final && h->ro.t % h->seg_every == 0 && h->ro.t / h->seg_every < h->seg_rows)      /* a slot that begins a segment keeps it too */
+        cell.start_out = h->seg_starts + (size_t)(h->ro.t / h->seg_every) * (size_t)h->n_plants * (size_t)h->core.H;
     }
     policy_launch(h, &run, h->core.primed ? &cell : nullptr, stream);
     if (!h->pol.D.deterministic) h->pol_t++;
@@ -2350,6 +2355,7 @@ static void policy_drop(NpbHandle *h) {
   attachment_drop(&h->core, h->core.primed);
   attachment_drop(&h->pol, h->pol.theta);
   h->pol_t = 0;
+  h->seg_starts = nullptr; h->seg_every = h->seg_rows = 0;
 }
 static int set_policy(NpbHandle *h, const npb_policy_desc_t *desc, const npb_policy_core_t *core);
 int npb_set_policy(NpbHandle *h, const npb_policy_desc_t *desc) { return set_policy(h, desc, nullptr); }
@@ -2457,6 +2463,24 @@ int npb_policy_values_hidden(NpbHandle *h, const void *rows, int type, int n_row
   return policy_values(h, who, ": a NULL or misaligned out, misaligned hidden_rows (4-byte aligned), or rows misaligned for their type", rows, type, n_rows, hidden_rows,
                        out, stream);
 }
+/* ---- truncated segments (include/npb.h): the stored start states beside a rollout */
+const char *npb_policy_core_segments_check(int every, const float *starts, int rows, int horizon, int core_width) {
+  if (every == 0) return nullptr;
+  if (core_width < 1) return "npb_policy_core_segments: the policy has no core (npb_set_policy_core first)";
+  if (horizon < 1) return "npb_policy_core_segments: no rollout set (npb_set_rollout first): its horizon bounds every and the rows";
+  if (every < 0 || every > horizon) return "npb_policy_core_segments: every must be 0 (off) or 1 .. the rollout's horizon";
+  if (rows < (horizon + every - 1) / every) return "npb_policy_core_segments: too few rows: starts has ceil(horizon / every) of them";
+  if (!starts || ((uintptr_t)starts & 3u)) return "npb_policy_core_segments: a NULL or misaligned starts: 4-byte aligned";
+  return nullptr;
+}
+int npb_policy_core_segments(NpbHandle *h, int every, float *starts, int rows) {
+  if (!h) return NPB_EINVAL;
+  if (const char *why = npb_policy_core_segments_check(every, starts, rows, h->ro.n_final ? h->ro.D.horizon : 0, h->core.primed ? h->core.H : 0))
+    return fail(h, NPB_EINVAL, why);
+  h->seg_every = every; h->seg_starts = every ? starts : nullptr; h->seg_rows = every ? rows : 0;
+  return NPB_OK;
+}
+
 /* hidden (the caller's tensor, which the cell carries from step to step), seen, primed */
 static StateParts policy_core_state_parts(const NpbHandle *h) {
   const size_t n = (size_t)h->n_plants, words = n * sizeof(int32_t);
@@ -2723,11 +2747,24 @@ const char *npb_ppo_seq_check(const npb_ppo_desc_t *D, const npb_ppo_seq_t *S, i
   return nullptr;
 }
 static const char *const g_seq_no_core = ": the policy has no core (npb_set_policy_core): sequences are a recurrent policy's; rows go to npb_policy_grad";
+/* the same for truncated segments (include/npb.h): what npb_ppo_seq_check refuses, and the segments' own */
+const char *npb_ppo_segments_check(const npb_ppo_desc_t *D, const npb_ppo_seq_t *S, const npb_ppo_segments_t *G, int features_cells, int n_axes) {
+  if (const char *why = npb_ppo_seq_check(D, S, features_cells, n_axes)) return why;
+  if (!G) return "npb_policy_grad_segments: a NULL segments descriptor";
+  if (G->every < 1) return "npb_policy_grad_segments: every must be >= 1";
+  if (G->chunks < 1) return "npb_policy_grad_segments: chunks must be >= 1";
+  if (S->t != G->every) return "npb_policy_grad_segments: seq->t must be every: a sequence of the minibatch is one segment";
+  if ((int64_t)G->chunks * G->every * S->n_plants > INT32_MAX) return "npb_policy_grad_segments: chunks * every * n_plants is beyond 2^31 - 1";
+  return nullptr;
+}
 /* the checks of a sequence call and its workspaces: the chains' (a chain is rows_per_chain plants) and h' [t][plants][H] */
-static int ppo_seq_room(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S) {
+/* (segments: G is not NULL behind the entry points below that take one; `segments` says which check names the refusal) */
+static int ppo_seq_room(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, bool segments = false,
+                        const npb_ppo_segments_t *G = nullptr) {
   if (!h->pol.theta) return fail_who(h, who, g_no_policy);
   if (!h->core.primed) return fail_who(h, who, g_seq_no_core);
-  if (const char *why = npb_ppo_seq_check(D, S, h->pol.cells, h->pol.n_axes)) return fail(h, NPB_EINVAL, why);
+  if (const char *why = segments ? npb_ppo_segments_check(D, S, G, h->pol.cells, h->pol.n_axes) : npb_ppo_seq_check(D, S, h->pol.cells, h->pol.n_axes))
+    return fail(h, NPB_EINVAL, why);
   if (const char *why = npb_ppo_more_check(M, D->count)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
   if (int rc = ppo_room(h, who, ((size_t)S->plants + D->rows_per_chain - 1) / D->rows_per_chain)) return rc;
@@ -2740,9 +2777,10 @@ static int ppo_seq_room(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, 
   }
   return NPB_OK;
 }
-static int ppo_grad_seq(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, void *stream) {
-  if (int rc = ppo_seq_room(h, who, D, M, S)) return rc;
-  npb_launch_ppo_grad_seq(&h->pol, &h->core, &h->ppo, D, M, S, (hipStream_t)stream);
+static int ppo_grad_seq(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, void *stream, bool segments = false,
+                        const npb_ppo_segments_t *G = nullptr) {
+  if (int rc = ppo_seq_room(h, who, D, M, S, segments, G)) return rc;
+  npb_launch_ppo_grad_seq(&h->pol, &h->core, &h->ppo, D, M, S, G, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -2751,29 +2789,68 @@ int npb_policy_grad_seq(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_mor
   if (M && M->kl_limit > 0.0) return fail(h, NPB_EINVAL, "npb_policy_grad_seq: kl_limit > 0: the gate is an update's (npb_policy_update_seq)");
   return ppo_grad_seq(h, "npb_policy_grad_seq", D, M, S, stream);
 }
-int npb_policy_update_seq(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, double lr, double b1, double b2, double eps,
-                          void *stream) {
+int npb_policy_grad_segments(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, const npb_ppo_segments_t *G, void *stream) {
   if (!h) return NPB_EINVAL;
-  const char *who = "npb_policy_update_seq";
+  if (M && M->kl_limit > 0.0) return fail(h, NPB_EINVAL, "npb_policy_grad_segments: kl_limit > 0: the gate is an update's (npb_policy_update_segments)");
+  return ppo_grad_seq(h, "npb_policy_grad_segments", D, M, S, stream, true, G);
+}
+static int ppo_update_seq(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, bool segments,
+                          const npb_ppo_segments_t *G, double lr, double b1, double b2, double eps, void *stream) {
+  if (!h) return NPB_EINVAL;
   const int gated = M && M->kl_limit > 0.0;
   if (gated && !h->ppo.armed) return fail_who(h, who, ": kl_limit > 0 outside npb_policy_train_begin / npb_policy_train_end (npb_policy_train_begin first)");
   if (!gated && h->ppo.armed) return fail_who(h, who, ": kl_limit == 0 between npb_policy_train_begin and npb_policy_train_end: every update of the pair is gated");
   if (gated && h->pol.theta)      /* (a gated gradient counts itself applied: its Adam step must not be refused behind it) */
     if (const char *why = adam_refusal(lr, b1, b2, eps)) return fail_who(h, who, why);
-  if (int rc = ppo_grad_seq(h, who, D, M, S, stream)) return rc;
+  if (int rc = ppo_grad_seq(h, who, D, M, S, stream, segments, G)) return rc;
   return ppo_adam(h, who, lr, b1, b2, eps, gated, stream);
 }
-int npb_policy_shard_sums_seq(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, int64_t count_total, double *out,
-                              void *stream) {
+int npb_policy_update_seq(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, double lr, double b1, double b2, double eps,
+                          void *stream) {
+  return ppo_update_seq(h, "npb_policy_update_seq", D, M, S, false, nullptr, lr, b1, b2, eps, stream);
+}
+int npb_policy_update_segments(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, const npb_ppo_segments_t *G, double lr,
+                               double b1, double b2, double eps, void *stream) {
+  return ppo_update_seq(h, "npb_policy_update_segments", D, M, S, true, G, lr, b1, b2, eps, stream);
+}
+static int ppo_shard_sums_seq(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, bool segments,
+                              const npb_ppo_segments_t *G, int64_t count_total, double *out, void *stream) {
   if (!h) return NPB_EINVAL;
-  const char *who = "npb_policy_shard_sums_seq";
   if (M && M->kl_limit > 0.0) return fail_who(h, who, ": kl_limit > 0: the gate belongs to the combine (npb_policy_apply_shards)");
   if (D && count_total < (int64_t)D->count) return fail_who(h, who, ": count_total < desc->count: it is the cells of the whole update");
   if (count_total > ((int64_t)1 << 53)) return fail_who(h, who, ": count_total is beyond 2^53");
   if (!out || ((uintptr_t)out & 7u)) return fail_who(h, who, ": a NULL or misaligned out (8-byte aligned)");
-  if (int rc = ppo_seq_room(h, who, D, M, S)) return rc;
-  npb_launch_ppo_shard_sums_seq(&h->pol, &h->core, &h->ppo, D, M, S, count_total, out, (hipStream_t)stream);
+  if (int rc = ppo_seq_room(h, who, D, M, S, segments, G)) return rc;
+  npb_launch_ppo_shard_sums_seq(&h->pol, &h->core, &h->ppo, D, M, S, G, count_total, out, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_policy_shard_sums_seq(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, int64_t count_total, double *out,
+                              void *stream) {
+  return ppo_shard_sums_seq(h, "npb_policy_shard_sums_seq", D, M, S, false, nullptr, count_total, out, stream);
+}
+int npb_policy_shard_sums_segments(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, const npb_ppo_segments_t *G,
+                                   int64_t count_total, double *out, void *stream) {
+  return ppo_shard_sums_seq(h, "npb_policy_shard_sums_segments", D, M, S, true, G, count_total, out, stream);
+}
+/* the refresh of the stored states under the current theta (npb_ppo_seq.hip's forward sweep over the rollout's own tensors) */
+int npb_policy_segment_starts(NpbHandle *h, int every, void *stream) {
+  if (!h) return NPB_EINVAL;
+  const char *who = "npb_policy_segment_starts";
+  if (!h->pol.theta) return fail_who(h, who, g_no_policy);
+  if (!h->core.primed) return fail_who(h, who, g_seq_no_core);
+  if (!h->ro.n_final) return fail_who(h, who, g_no_rollout);
+  if (!h->seg_every) return fail_who(h, who, ": no stored states set (npb_policy_core_segments first)");
+  if (every != h->seg_every) return fail_who(h, who, ": every is not the one the stored states were set with (npb_policy_core_segments)");
+  if (!h->core.first) return fail_who(h, who, ": the core has no first: the state in front of slot 0 is where the recurrence starts");
+  if (h->ro.t < 1) return fail_who(h, who, ": nothing recorded yet (t == 0)");
+  if (h->ro.t % every) return fail_who(h, who, ": the recorded slots are not a multiple of every: ragged last segments are not supported");
+  NPB_USE_DEVICE(h);
+  if (h->ro.t / every > 1) {
+    npb_launch_segment_starts(&h->pol, &h->core, h->ro.D.obs, h->ro.obs_bytes == 8, h->ro.t, h->n_plants, every, h->ro.D.episode, h->ro.D.ended, h->seg_starts,
+                              (hipStream_t)stream);
+    NPB_HIP(h, hipGetLastError());
+  }
   return NPB_OK;
 }
 
@@ -3095,16 +3172,18 @@ int npb_rollout_permutation(NpbHandle *h, int64_t N, const uint32_t *keys, int64
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
-const char *npb_minibatch_check(const npb_minibatch_desc_t *D, int n_plants, int t, int features_cells, int n_axes, int n_extras) {
+/* every: 0 for npb_rollout_minibatch's units, else the slots of a segment (npb_rollout_minibatch_segments) */
+static const char *minibatch_check(const npb_minibatch_desc_t *D, int every, int n_plants, int t, int features_cells, int n_axes, int n_extras) {
   if (!D) return "npb_rollout_minibatch: a NULL descriptor";
   if (n_plants < 1) return "npb_rollout_minibatch: n_plants must be >= 1";
   if (features_cells < 1) return "npb_rollout_minibatch: the features' stack must have cells (K * C >= 1)";
   if (n_axes < 0 || n_extras < 0) return "npb_rollout_minibatch: a negative axis or extras count";
   if (t < 1) return "npb_rollout_minibatch: nothing recorded yet (t == 0)";
-  if (D->unit != NPB_MINIBATCH_TRANSITION && D->unit != NPB_MINIBATCH_PLANT) return "npb_rollout_minibatch: an unknown unit";
+  if (D->unit != NPB_MINIBATCH_TRANSITION && D->unit != NPB_MINIBATCH_PLANT && !(every && D->unit == NPB_MINIBATCH_SEGMENT))
+    return "npb_rollout_minibatch: an unknown unit";
   if (D->type != NPB_ROLLOUT_F32 && D->type != NPB_ROLLOUT_F64) return "npb_rollout_minibatch: an unknown type";
-  const int64_t N = D->unit == NPB_MINIBATCH_PLANT ? (int64_t)n_plants : (int64_t)t * n_plants;
-  if (N > INT32_MAX) return "npb_rollout_minibatch: t * n_plants is beyond 2^31 - 1, what an index (int32) holds";
+  const int64_t N = D->unit == NPB_MINIBATCH_PLANT ? (int64_t)n_plants : (int64_t)(every ? t / every : t) * n_plants;
+  if (D->unit != NPB_MINIBATCH_PLANT && (int64_t)t * n_plants > INT32_MAX) return "npb_rollout_minibatch: t * n_plants is beyond 2^31 - 1, what an index (int32) holds";
   if (D->count < 1) return "npb_rollout_minibatch: count must be >= 1";
   if (D->first < 0 || D->first > N - D->count) return "npb_rollout_minibatch: entries [first, first + count) must lie inside [0, N)";
   if (!D->index) return "npb_rollout_minibatch: index is NULL";
@@ -3122,6 +3201,18 @@ const char *npb_minibatch_check(const npb_minibatch_desc_t *D, int n_plants, int
   if ((uintptr_t)D->index & 3u) return "npb_rollout_minibatch: a misaligned index: 4-byte aligned";
   return nullptr;
 }
+const char *npb_minibatch_check(const npb_minibatch_desc_t *D, int n_plants, int t, int features_cells, int n_axes, int n_extras) {
+  return minibatch_check(D, 0, n_plants, t, features_cells, n_axes, n_extras);
+}
+const char *npb_minibatch_segments_check(const npb_minibatch_desc_t *D, int every, int n_plants, int t, int features_cells, int n_axes, int n_extras) {
+  if (D && D->unit != NPB_MINIBATCH_SEGMENT) return "npb_rollout_minibatch_segments: the unit must be NPB_MINIBATCH_SEGMENT";
+  if (D && t >= 1) {
+    if (every < 1) return "npb_rollout_minibatch_segments: every must be >= 1";
+    if (every > t) return "npb_rollout_minibatch_segments: every is beyond the recorded slots t";
+    if (t % every) return "npb_rollout_minibatch_segments: t is not a multiple of every: ragged last segments are not supported";
+  }
+  return minibatch_check(D, every > 0 ? every : 1, n_plants, t, features_cells, n_axes, n_extras);
+}
 int npb_rollout_minibatch(NpbHandle *h, const npb_minibatch_desc_t *D, void *stream) {
   if (!h) return NPB_EINVAL;
   if (!h->ro.n_final) return fail_who(h, "npb_rollout_minibatch", g_no_rollout);
@@ -3129,7 +3220,18 @@ int npb_rollout_minibatch(NpbHandle *h, const npb_minibatch_desc_t *D, void *str
   if (const char *why = npb_minibatch_check(D, h->n_plants, R.t, R.cells, R.n_axes, R.D.n_extras)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
   const npb_minibatch_src_t S = {R.D.obs, R.D.act, R.D.extra, R.t, h->n_plants, R.cells, R.n_axes, R.D.n_extras, R.obs_bytes, R.act_bytes};
-  npb_launch_minibatch(&S, D, (hipStream_t)stream);
+  npb_launch_minibatch(&S, D, 0, (hipStream_t)stream);
+  NPB_HIP(h, hipGetLastError());
+  return NPB_OK;
+}
+int npb_rollout_minibatch_segments(NpbHandle *h, const npb_minibatch_desc_t *D, int every, void *stream) {
+  if (!h) return NPB_EINVAL;
+  if (!h->ro.n_final) return fail_who(h, "npb_rollout_minibatch_segments", g_no_rollout);
+  const npb_rollout_t &R = h->ro;
+  if (const char *why = npb_minibatch_segments_check(D, every, h->n_plants, R.t, R.cells, R.n_axes, R.D.n_extras)) return fail(h, NPB_EINVAL, why);
+  NPB_USE_DEVICE(h);
+  const npb_minibatch_src_t S = {R.D.obs, R.D.act, R.D.extra, R.t, h->n_plants, R.cells, R.n_axes, R.D.n_extras, R.obs_bytes, R.act_bytes};
+  npb_launch_minibatch(&S, D, every, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }

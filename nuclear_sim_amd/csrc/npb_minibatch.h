@@ -76,7 +76,8 @@ typedef struct {
   const void *obs, *act, *extra;
   int t, n_plants, cells, n_axes, n_extras, obs_bytes, act_bytes;
 } npb_minibatch_src_t;
-void npb_launch_minibatch(const npb_minibatch_src_t *S, const npb_minibatch_desc_t *D, hipStream_t stream);
+/* every: the slots of a segment with D->unit == NPB_MINIBATCH_SEGMENT (S->t a multiple of it), else not read */
+void npb_launch_minibatch(const npb_minibatch_src_t *S, const npb_minibatch_desc_t *D, int every, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,8 @@
  *   index by the walk, then index, adv and ret with consecutive lanes on consecutive outputs.  Phase 2: the wave walks its rows, L lanes on each, the source
  *   index of a row taken by __shfl from the lane that computed it; the loads of NPD_MINIBATCH_AHEAD passes are issued before their stores.
  *   A tensor's width (16 bytes, else one element) and L are the launcher's, as npb_launch_rollout_post picks W; they are uniform in the
- *   launch, so one kernel serves every shape.
+ *   launch, so one kernel serves every shape.  Segments of `every` slots (npb_rollout_minibatch_segments) are sequences of `every` slots whose
+ *   source starts `c * every` slots down: an entry c * n_plants + p is turned into that cell once, behind the store of index.
  * No atomics, no scratch, nothing of the arena. */
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -289,7 +290,8 @@ extern "C" void npb_launch_permutation(uint32_t N, const uint32_t *keys, int64_t
 struct npd_gather_t { const char *src; char *dst; uint32_t row_bytes; int width, lanes_log2; };
 struct npd_minibatch_t {
   npd_perm_t perm;
-  uint32_t first, count, n_plants, slots;      /* slots: 1 for transitions, t for whole sequences */
+  uint32_t first, count, n_plants, slots;      /* slots: 1 for transitions, t for whole sequences, every for segments */
+  uint32_t every;                              /* 0, or the slots of a segment: an entry is a segment id c * n_plants + p, its source slots c * every .. */
   const void *adv, *ret; void *adv_out, *ret_out; int32_t *index;
   const double *moments; double eps; int f64;
   npd_gather_t g[3];
@@ -349,6 +351,10 @@ __global__ __launch_bounds__(256) void npb_minibatch_kernel(npd_minibatch_t M) {
     if (lane < rows) {
       idx = (int)npd_permute(M.perm, M.first + (uint32_t)j);
       if (slot == 0) M.index[j] = idx;
+      if (M.every) {      /* a segment id: from here on the source cell of the segment's slot 0, (c * every) * n_plants + p */
+        const uint32_t c = (uint32_t)idx / M.n_plants;
+        idx = (int)(c * M.every * M.n_plants + ((uint32_t)idx - c * M.n_plants));
+      }
       if (M.f64) npd_minibatch_scalars<double>(M, src_base + (size_t)idx, dst_base + lane);
       else npd_minibatch_scalars<float>(M, src_base + (size_t)idx, dst_base + lane);
     }
@@ -373,11 +379,12 @@ static npd_gather_t npd_gather(const void *src, void *dst, size_t row_bytes, int
   while (G.lanes_log2 < 6 && ((size_t)G.width << G.lanes_log2) < row_bytes) G.lanes_log2++;
   return G;
 }
-extern "C" void npb_launch_minibatch(const npb_minibatch_src_t *S, const npb_minibatch_desc_t *D, hipStream_t stream) {
-  const bool plant = D->unit == NPB_MINIBATCH_PLANT;
+extern "C" void npb_launch_minibatch(const npb_minibatch_src_t *S, const npb_minibatch_desc_t *D, int every, hipStream_t stream) {
+  const bool plant = D->unit == NPB_MINIBATCH_PLANT, segment = D->unit == NPB_MINIBATCH_SEGMENT;
   npd_minibatch_t M;
-  M.perm = npd_perm(plant ? (uint32_t)S->n_plants : (uint32_t)((int64_t)S->t * S->n_plants), D->keys);
-  M.first = (uint32_t)D->first; M.count = (uint32_t)D->count; M.n_plants = (uint32_t)S->n_plants; M.slots = plant ? (uint32_t)S->t : 1u;
+  M.perm = npd_perm(plant ? (uint32_t)S->n_plants : (uint32_t)((int64_t)(segment ? S->t / every : S->t) * S->n_plants), D->keys);
+  M.first = (uint32_t)D->first; M.count = (uint32_t)D->count; M.n_plants = (uint32_t)S->n_plants; M.slots = plant ? (uint32_t)S->t : (segment ? (uint32_t)every : 1u);
+  M.every = segment ? (uint32_t)every : 0u;
   M.adv = D->adv; M.ret = D->ret; M.adv_out = D->adv_out; M.ret_out = D->ret_out; M.index = D->index;
   M.moments = D->moments; M.eps = D->eps; M.f64 = D->type == NPB_ROLLOUT_F64;
   M.g[0] = npd_gather(S->obs, D->obs, (size_t)S->cells * S->obs_bytes, S->obs_bytes);

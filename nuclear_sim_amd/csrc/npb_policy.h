@@ -58,10 +58,12 @@ typedef struct {
 } npd_policy_core_t;
 /* one launch of the recurrent kernel beside its npd_policy_run_t: h [rows][H] read; h_out: where h' goes (NULL: nowhere); first_out: where the
  * h read goes, the restart rule applied (NULL: nowhere); primed, seen, index: the restart rule's words (primed NULL: no rule, h as it is; index
- * NULL: nothing carried, a plant's index is the one seen); remember: prime the plants and remember their index */
+ * NULL: nothing carried, a plant's index is the one seen); remember: prime the plants and remember their index; start_out: a second copy of
+ * what first_out receives, the row of the stored segment states that this step begins (NULL: none; npb_policy_core_segments) */
 typedef struct {
   const float *h; float *h_out, *first_out;
   int32_t *primed, *seen; const int32_t *index; int remember;
+  float *start_out;
 } npd_policy_core_run_t;
 void npb_policy_core_layout(int H, int gates, int cells, npd_policy_core_t *C);
 void npb_launch_policy_repack(const npb_policy_t *P, const npd_policy_core_t *C /* NULL: no core */, hipStream_t stream);      /* (npb_policy.hip: every layer, one launch) */

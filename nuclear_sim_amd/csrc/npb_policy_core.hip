@@ -11,7 +11,8 @@
  *      one seen (npd_controls.h's rule); a step that acts primes the plant and remembers the index, the same lane storing what it read.
  *      The tile's rows of x and of h are ONE contiguous run each (32 x K*C and 32 x H): consecutive lanes on consecutive elements, narrowed
  *      and transposed into LDS (xs, hs); a restarted plant's column of hs is +0.0; on the rollout's slot 0 the run goes out again, as read,
- *      into `first`.  The k extensions of xs and hs are +0.0.  The load of x, the zeroing and the ragged tile's row count are the MLP
+ *      into `first` (and on a slot that begins a segment, npb_policy_core_segments, into that segment's row of the stored states).  The k
+ *      extensions of xs and hs are +0.0.  The load of x, the zeroing and the ragged tile's row count are the MLP
  *      kernel's own (npb_policy.h: npd_policy_tile_load, npd_policy_tile_zero, npd_policy_in_tile); the load of h, with its restart
  *      mask and its store into `first`, is this file's.
  *   2. gate by gate, so that only H-wide buffers live in LDS: gi = W_i* x into ha and gh = W_h* h into hb (two layers, one barrier: they
@@ -68,6 +69,7 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_policy_core_kernel(npb_p
     const float v = fresh[row] ? 0.0f : h_run[e];
     hs[k * NPD_POLICY_STRIDE + row] = v;
     if (G.first_out) G.first_out[base * (size_t)H + e] = v;
+    if (G.start_out) G.start_out[base * (size_t)H + e] = v;
   }
   __syncthreads();
   /* 2. the cell, gate by gate */

@@ -39,11 +39,16 @@ void npb_launch_ppo_shard_sums(const npb_policy_t *P, const npb_ppo_t *O, const 
 void npb_launch_ppo_combine(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_shards_t *S, hipStream_t stream);
 /* the same two over whole sequences through the recurrent core (npb_ppo_seq.hip; npb_policy_grad_seq, npb_policy_shard_sums_seq): D's tensors
  * time-major [S->t][S->plants][...], D->rows_per_chain the PLANTS of a chain; O holds room for ceil(plants / rows_per_chain) chains and
- * O->hseq for t * plants * H floats */
+ * O->hseq for t * plants * H floats.  G (NULL: whole sequences): the sequences are segments of S->t slots, S->index their ids c * n_plants + p,
+ * S->first the stored states [G->chunks * n_plants][H] (npb_policy_grad_segments) */
 void npb_launch_ppo_grad_seq(const npb_policy_t *P, const npd_policy_core_t *C, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M,
-                             const npb_ppo_seq_t *S, hipStream_t stream);
+                             const npb_ppo_seq_t *S, const npb_ppo_segments_t *G, hipStream_t stream);
 void npb_launch_ppo_shard_sums_seq(const npb_policy_t *P, const npd_policy_core_t *C, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M,
-                                   const npb_ppo_seq_t *S, int64_t count_total, double *out, hipStream_t stream);
+                                   const npb_ppo_seq_t *S, const npb_ppo_segments_t *G, int64_t count_total, double *out, hipStream_t stream);
+/* the refresh of the stored states (npb_policy_segment_starts): the forward sweep over the rollout's t recorded slots from C->first under the
+ * current theta; rows 1 .. t / every - 1 of starts [t / every][n_plants][H] receive the state read in front of slot c * every */
+void npb_launch_segment_starts(const npb_policy_t *P, const npd_policy_core_t *C, const void *obs, int obs_f64, int t, int n_plants, int every,
+                               const int32_t *episode, const uint8_t *ended, float *starts, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -29,13 +29,26 @@
  * ascending.  No atomics, nothing depends on the launch order, no scratch.
  * LDS, from the declarations below: xs (K*C x 33 floats), seven H-wide buffers (H_MAX x 33 floats each; H_MAX covers the core and both nets'
  * widths), the head's 1056 B, the per-row doubles' 4608 B, four words a plant: the small build (npd_policy_small with the core's width)
- * 8448 + 7 x 8448 + 6176 = 73 760 B, the large one 33 792 + 7 x 16 896 + 6176 = 158 240 B of gfx950's 160 KiB (one workgroup a CU), as the
- * compiler reports them.  Its other figures (-Rpass-analysis=kernel-resource-usage), both builds: 255 VGPRs, 22 / 40 AGPRs, no scratch, no
- * VGPR spills, and 469 / 488 of the descriptors' scalars spilled from SGPRs into VGPR lanes (the row-wise kernel: 133 / 129) -- no memory
- * traffic, but a workgroup is alone on its CU in the small build too.  No shape is refused: both builds fit.  Measured on an MI355X
+ * 8448 + 7 x 8448 + 6176 = 73 760 B, the large one 33 792 + 7 x 16 896 + 6176 = 158 240 B of gfx950's 160 KiB (one workgroup a CU), and 128 B
+ * more for word0 (below): 73 888 / 158 368 B as the compiler reports them.  Its other figures (-Rpass-analysis=kernel-resource-usage added to the Makefile's
+ * own line for this file: -O3 -ffp-contract=off -fno-fast-math; the scalar spills move with the flags: plain -O3 gives 464 / 466 of
+ * them, every other figure the same), small / large build: 255 / 256 VGPRs, 40 / 40 AGPRs, no scratch, no VGPR spills, and 481 / 476 of the descriptors' scalars spilled from SGPRs into
+ * VGPR lanes (the row-wise kernel: 133 / 129) -- no memory traffic, but a workgroup is alone on its CU in the small build too.  No atomics.
+ * No shape is refused: both builds fit.  Measured on an MI355X
  * (tools/recurrent_train_cost.py): one update of t = 128 through a cell of 64 and (64, 64) nets, 21.0 ms at 4 096 plants, 30.1 ms at 8 192.  The
  * nets' phase and the cell's phase alias the seven buffers: b0 the carry; b1 h' then h; b2 .. b4 the nets' hidden activations then r, z, n;
- * b5, b6 the nets' two delta buffers then gh_n and the flags. */
+ * b5, b6 the nets' two delta buffers then gh_n and the flags.
+ *
+ * TRUNCATED SEGMENTS (npb_policy_grad_segments and its companions; Q.chunks > 0) run the same kernel: a sequence is a segment of S.t = every
+ * slots, its index a segment id g = c * n_plants + p.  The only differences are in the tile's decode (lanes 0 .. 31, once a tile): g outside
+ * 0 .. chunks * n_plants - 1 poisons the sequence and nothing is read through it; src[] keeps g, the row of S.first (the stored states
+ * [chunks * n_plants][H]); word0[] keeps (c * every) * n_plants + p, the cell of local slot 0 in episode and ended, so that local slot s > 0
+ * reads its restart words at rollout rows c * every + s and c * every + s - 1.  No word in front of local slot 0 is read (that restart is in
+ * the stored state), and the carry out of local slot 0 goes nowhere: that is the truncation.  Whole sequences have word0 = src = the plant.
+ * THE REFRESH (npb_policy_segment_starts; npb_segment_starts_kernel) is the forward sweep alone -- npd_seq_forward, the one piece of code
+ * both kernels call -- over the rollout's own tensors, one workgroup per tile of 32 plants, serial in t; the state in front of slot c * every
+ * goes into row c of the stored states for c >= 1.  Five H-wide buffers and xs: 50 944 / 118 528 B of LDS, 105 / 78 VGPRs, 16 AGPRs, no
+ * scratch, no VGPR spills (34 / 36 scalars into VGPR lanes), no atomics. */
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "npb_ppo.h"
@@ -46,7 +59,16 @@
 typedef struct {
   npb_ppo_seq_t S;
   float *hseq;      /* [t][plants][H] */
+  int chunks;       /* 0: whole sequences, index a plant; > 0: segments of S.t slots, index a segment id c * n_plants + p with c < chunks */
 } npd_ppo_seq_run_t;
+/* what the refresh of the stored states takes (npb_policy_segment_starts): the rollout's own tensors, no minibatch */
+typedef struct {
+  const void *obs; int obs_f64;      /* [t][n_plants][K * C] */
+  int t, n_plants, every;
+  const int32_t *episode; const uint8_t *ended;      /* [t][n_plants] */
+  const float *first;      /* [n_plants][H] */
+  float *starts;           /* [t / every][n_plants][H]: rows 1 .. are written */
+} npd_seq_starts_t;
 
 /* a tile's H-wide buffer filled whole, [k][plant] with k up to H_pad: plant `row` reads H contiguous floats at run + offset(row), or +0.0
  * where it has none (beyond the tile, a plant without a source, a restarted plant).  Consecutive lanes on consecutive k of one plant */
@@ -59,13 +81,60 @@ __device__ __forceinline__ void npd_seq_fill(float *dst, int H, int H_pad, int t
   }
 }
 
+/* THE FORWARD SWEEP of one tile, s ascending, what the gradient kernel and the refresh of the stored states share: h in b1, the step kernel's
+ * cell gate by gate (gi into b2, gh into b3, r into b4, z into b5).  obs: slot s of the tile is in_tile rows of KC cells at cell (s * rows +
+ * base); words(s), lanes 0 .. 31: fresh and bad of the slot; first_of(row): the state in front of slot 0; front(s): h_s stands in b1, the
+ * restart applied, and is only read until the cell has run; behind(s): h'_s stands in b1.  xs is zero beyond KC on entry */
+template <class Words, class First, class Front, class Behind>
+__device__ __forceinline__ void npd_seq_forward(const npb_policy_t &P, const npd_policy_core_t &C, const void *obs, int obs_f64, size_t rows, size_t base, int in_tile,
+                                                int T, float *xs, float *b1, float *b2, float *b3, float *b4, float *b5, int *bad, const int *fresh, int tid,
+                                                Words words, First first_of, Front front, Behind behind) {
+  const int wave = tid >> 6, lane = tid & 63, KC = P.cells, H = C.H, H_pad = (H + 3) & ~3;
+  for (int s = 0; s < T; s++) {
+    if (tid < NPD_POLICY_TILE) words(s);
+    __syncthreads();
+    const size_t cell0 = (size_t)s * rows + base;
+    if (obs_f64) npd_policy_tile_load((const double *)obs + cell0 * KC, in_tile, KC, xs, bad, tid);
+    else npd_policy_tile_load((const float *)obs + cell0 * KC, in_tile, KC, xs, bad, tid);
+    if (s == 0) npd_seq_fill(b1, H, H_pad, tid, first_of);
+    else
+      for (int i = tid; i < H_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES)
+        if (fresh[i & (NPD_POLICY_TILE - 1)]) b1[(i / NPD_POLICY_TILE) * NPD_POLICY_STRIDE + (i & (NPD_POLICY_TILE - 1))] = 0.0f;
+    __syncthreads();
+    front(s);
+    for (int gate = 0; gate < 3; gate++) {
+      npd_policy_layer(C.gate[gate], P.theta, P.padded, xs, b2, -1, wave, lane);
+      npd_policy_layer(C.gate[3 + gate], P.theta, P.padded, b1, b3, -1, (wave + 2) & (NPD_POLICY_WAVES - 1), lane);
+      __syncthreads();
+      for (int i = tid; i < H_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES) {
+        const int j = i / NPD_POLICY_TILE, plant = i & (NPD_POLICY_TILE - 1), o = j * NPD_POLICY_STRIDE + plant;
+        if (gate < 2) {
+          const float a = b2[o] + b3[o];
+          (gate ? b5 : b4)[o] = npd_core_sigma(a, C.gates);
+        } else {
+          const float gated = b4[o] * b3[o];
+          const float a = b2[o] + gated;
+          const float nn = npd_core_tau(a, C.gates);
+          const float h = b1[o];
+          const float away = h - nn;
+          const float kept = b5[o] * away;
+          const float next = nn + kept;
+          b1[o] = j < H && !bad[plant] ? next : 0.0f;
+        }
+      }
+      __syncthreads();
+    }
+    behind(s);
+  }
+}
+
 template <int KC_MAX, int H_MAX>
 __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_seq_kernel(npb_policy_t P, npd_policy_core_t C, npd_ppo_run_t R, npd_ppo_seq_run_t Q) {
   __shared__ float xs[KC_MAX * NPD_POLICY_STRIDE];
   __shared__ float buf[7][H_MAX * NPD_POLICY_STRIDE];
   __shared__ float head[NPB_CONTROLS_AXES_MAX * NPD_POLICY_STRIDE];
   __shared__ double rowv[NPD_PPO_ROWVALS * NPD_POLICY_TILE];
-  __shared__ int bad[NPD_POLICY_TILE], fresh[NPD_POLICY_TILE], skip[NPD_POLICY_TILE], src[NPD_POLICY_TILE];
+  __shared__ int bad[NPD_POLICY_TILE], fresh[NPD_POLICY_TILE], skip[NPD_POLICY_TILE], src[NPD_POLICY_TILE], word0[NPD_POLICY_TILE];
   float *const b0 = buf[0], *const b1 = buf[1], *const b2 = buf[2], *const b3 = buf[3], *const b4 = buf[4], *const b5 = buf[5], *const b6 = buf[6];
   const npb_ppo_desc_t &D = R.D;
   const npb_ppo_seq_t &S = Q.S;
@@ -79,14 +148,17 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_seq_kernel(npb_polic
     for (size_t base = chain * ppc; base < (chain + 1) * ppc && base < plants; base += NPD_POLICY_TILE) {
       const int in_tile = npd_policy_in_tile(plants, base);
       __syncthreads();      /* (the tile before is done with every buffer) */
-      /* the tile's plants of the rollout: -1 beyond the tile and for an index outside the rollout's plants */
+      /* the tile's sequences of the rollout: src the row of `first` (a plant, or a segment id c * n_plants + p), -1 beyond the tile and for
+       * an index outside the rollout's; word0 the restart word of local slot 0 in episode and ended: column p of row 0, or of row c * t */
       if (tid < NPD_POLICY_TILE) {
-        int64_t from = -1;
+        int64_t from = -1, at = 0;
         if (tid < in_tile) {
           from = S.index ? (int64_t)S.index[base + tid] : (int64_t)(base + tid);
-          if (from < 0 || from >= (int64_t)n_plants) from = -1;
+          if (from < 0 || from >= (int64_t)(Q.chunks ? Q.chunks : 1) * (int64_t)n_plants) from = -1;
+          else if (Q.chunks) { const int64_t c = from / (int64_t)n_plants; at = c * T * (int64_t)n_plants + (from - c * (int64_t)n_plants); }
+          else at = from;
         }
-        src[tid] = (int)from;
+        src[tid] = (int)from; word0[tid] = (int)at;
       }
       npd_policy_tile_zero(xs, 0, KC_pad, tid);      /* (once a tile: every slot's load overwrites the same cells) */
       __syncthreads();
@@ -95,53 +167,21 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_seq_kernel(npb_polic
         const int from = src[tid];
         int restart = 0;
         if (from >= 0 && s > 0) {
-          const size_t now = (size_t)s * n_plants + from, before = now - n_plants;
+          const size_t now = (size_t)s * n_plants + (size_t)word0[tid], before = now - n_plants;
           restart = S.episode[now] != S.episode[before] || (S.ended[before] & NPD_SEQ_CUT) != 0;
         }
         fresh[tid] = restart;
         bad[tid] = from < 0;
       };
       auto first_of = [&](int row) -> const float * { return src[row] >= 0 ? S.first + (size_t)src[row] * H : nullptr; };
-      /* ---- the forward sweep: h in b1, the step kernel's cell gate by gate (gi into b2, gh into b3, r into b4, z into b5) */
-      for (int s = 0; s < T; s++) {
-        if (tid < NPD_POLICY_TILE) words(s);
-        __syncthreads();
-        const size_t cell0 = (size_t)s * plants + base;
-        if (D.obs_type) npd_policy_tile_load((const double *)D.obs + cell0 * KC, in_tile, KC, xs, bad, tid);
-        else npd_policy_tile_load((const float *)D.obs + cell0 * KC, in_tile, KC, xs, bad, tid);
-        if (s == 0) npd_seq_fill(b1, H, H_pad, tid, first_of);
-        else
-          for (int i = tid; i < H_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES)
-            if (fresh[i & (NPD_POLICY_TILE - 1)]) b1[(i / NPD_POLICY_TILE) * NPD_POLICY_STRIDE + (i & (NPD_POLICY_TILE - 1))] = 0.0f;
-        __syncthreads();
-        for (int gate = 0; gate < 3; gate++) {
-          npd_policy_layer(C.gate[gate], P.theta, P.padded, xs, b2, -1, wave, lane);
-          npd_policy_layer(C.gate[3 + gate], P.theta, P.padded, b1, b3, -1, (wave + 2) & (NPD_POLICY_WAVES - 1), lane);
-          __syncthreads();
-          for (int i = tid; i < H_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES) {
-            const int j = i / NPD_POLICY_TILE, plant = i & (NPD_POLICY_TILE - 1), o = j * NPD_POLICY_STRIDE + plant;
-            if (gate < 2) {
-              const float a = b2[o] + b3[o];
-              (gate ? b5 : b4)[o] = npd_core_sigma(a, C.gates);
-            } else {
-              const float gated = b4[o] * b3[o];
-              const float a = b2[o] + gated;
-              const float nn = npd_core_tau(a, C.gates);
-              const float h = b1[o];
-              const float away = h - nn;
-              const float kept = b5[o] * away;
-              const float next = nn + kept;
-              b1[o] = j < H && !bad[plant] ? next : 0.0f;
-            }
-          }
-          __syncthreads();
-        }
-        float *out = Q.hseq + cell0 * H;
+      /* ---- the forward sweep (npd_seq_forward): h'_s into the workspace */
+      npd_seq_forward(P, C, D.obs, D.obs_type, plants, base, in_tile, T, xs, b1, b2, b3, b4, b5, bad, fresh, tid, words, first_of, [](int) {}, [&](int s) {
+        float *out = Q.hseq + ((size_t)s * plants + base) * H;
         for (int e = tid; e < in_tile * H; e += NPD_POLICY_LANES) {
           const int row = e / H, k = e - row * H;
           out[e] = b1[k * NPD_POLICY_STRIDE + row];
         }
-      }
+      });
       /* ---- the backward sweep */
       __syncthreads();
       npd_policy_tile_zero(b0, 0, H_pad, tid);
@@ -265,29 +305,68 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_seq_kernel(npb_polic
   }
 }
 
+/* THE REFRESH OF THE STORED STATES (npb_policy_segment_starts): the forward sweep alone over the rollout's own tensors, one workgroup per tile
+ * of 32 plants, serial in t; the state read in front of slot c * every, the restart applied, goes into row c of starts for c >= 1 */
+template <int KC_MAX, int H_MAX>
+__global__ __launch_bounds__(NPD_POLICY_LANES) void npb_segment_starts_kernel(npb_policy_t P, npd_policy_core_t C, npd_seq_starts_t G) {
+  __shared__ float xs[KC_MAX * NPD_POLICY_STRIDE];
+  __shared__ float buf[5][H_MAX * NPD_POLICY_STRIDE];
+  __shared__ int bad[NPD_POLICY_TILE], fresh[NPD_POLICY_TILE];
+  const int tid = threadIdx.x, KC_pad = (P.cells + 3) & ~3, H = C.H;
+  const size_t n_plants = (size_t)G.n_plants, base = (size_t)blockIdx.x * NPD_POLICY_TILE;
+  const int in_tile = npd_policy_in_tile(n_plants, base);
+  npd_policy_tile_zero(xs, 0, KC_pad, tid);
+  __syncthreads();
+  auto words = [&](int s) {
+    int restart = 0;
+    if (tid < in_tile && s > 0) {
+      const size_t now = (size_t)s * n_plants + base + tid, before = now - n_plants;
+      restart = G.episode[now] != G.episode[before] || (G.ended[before] & NPD_SEQ_CUT) != 0;
+    }
+    fresh[tid] = restart;
+    bad[tid] = tid >= in_tile;
+  };
+  auto first_of = [&](int row) -> const float * { return row < in_tile ? G.first + (base + row) * H : nullptr; };
+  npd_seq_forward(P, C, G.obs, G.obs_f64, n_plants, base, in_tile, G.t, xs, buf[0], buf[1], buf[2], buf[3], buf[4], bad, fresh, tid, words, first_of, [&](int s) {
+    if (s == 0 || s % G.every) return;
+    float *out = G.starts + ((size_t)(s / G.every) * n_plants + base) * H;
+    for (int e = tid; e < in_tile * H; e += NPD_POLICY_LANES) {
+      const int row = e / H, k = e - row * H;
+      out[e] = buf[0][k * NPD_POLICY_STRIDE + row];
+    }
+  }, [](int) {});
+}
+
 /* ---- the launchers */
 static npd_ppo_run_t npd_ppo_seq_run(const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S) {
   return npd_ppo_run(O, D, M, (int)(((int64_t)S->plants + D->rows_per_chain - 1) / D->rows_per_chain));
 }
-static void npd_ppo_seq_launch(const npb_policy_t *P, const npd_policy_core_t *C, const npb_ppo_desc_t *D, const npd_ppo_run_t &R, const npb_ppo_seq_t *S, float *hseq,
-                               hipStream_t stream) {
+static void npd_ppo_seq_launch(const npb_policy_t *P, const npd_policy_core_t *C, const npb_ppo_desc_t *D, const npd_ppo_run_t &R, const npb_ppo_seq_t *S,
+                               const npb_ppo_segments_t *G, float *hseq, hipStream_t stream) {
   npd_ppo_seq_run_t Q = {};
-  Q.S = *S; Q.hseq = hseq;
+  Q.S = *S; Q.hseq = hseq; Q.chunks = G ? G->chunks : 0;
   const int cap = D->max_blocks > 0 ? D->max_blocks : 2048;
   const dim3 grid((unsigned)(R.n_chains < cap ? R.n_chains : cap)), block(NPD_POLICY_LANES);
   if (npd_policy_small(P, C->H)) hipLaunchKernelGGL((npb_ppo_seq_kernel<NPD_POLICY_SMALL_CELLS, NPD_POLICY_SMALL_WIDTH>), grid, block, 0, stream, *P, *C, R, Q);
   else hipLaunchKernelGGL((npb_ppo_seq_kernel<NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX>), grid, block, 0, stream, *P, *C, R, Q);
 }
 extern "C" void npb_launch_ppo_grad_seq(const npb_policy_t *P, const npd_policy_core_t *C, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M,
-                                        const npb_ppo_seq_t *S, hipStream_t stream) {
+                                        const npb_ppo_seq_t *S, const npb_ppo_segments_t *G, hipStream_t stream) {
   const npd_ppo_run_t R = npd_ppo_seq_run(O, D, M, S);
-  npd_ppo_seq_launch(P, C, D, R, S, S->hidden ? S->hidden : O->hseq, stream);
+  npd_ppo_seq_launch(P, C, D, R, S, G, S->hidden ? S->hidden : O->hseq, stream);
   npb_launch_ppo_reduce(P, O, &R, stream);
 }
 extern "C" void npb_launch_ppo_shard_sums_seq(const npb_policy_t *P, const npd_policy_core_t *C, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M,
-                                              const npb_ppo_seq_t *S, int64_t count_total, double *out, hipStream_t stream) {
+                                              const npb_ppo_seq_t *S, const npb_ppo_segments_t *G, int64_t count_total, double *out, hipStream_t stream) {
   npd_ppo_run_t R = npd_ppo_seq_run(O, D, M, S);
   R.n = (double)count_total;
-  npd_ppo_seq_launch(P, C, D, R, S, S->hidden ? S->hidden : O->hseq, stream);
+  npd_ppo_seq_launch(P, C, D, R, S, G, S->hidden ? S->hidden : O->hseq, stream);
   npb_launch_ppo_shard_reduce(P, &R, out, stream);
+}
+extern "C" void npb_launch_segment_starts(const npb_policy_t *P, const npd_policy_core_t *C, const void *obs, int obs_f64, int t, int n_plants, int every,
+                                          const int32_t *episode, const uint8_t *ended, float *starts, hipStream_t stream) {
+  const npd_seq_starts_t G = {obs, obs_f64, t, n_plants, every, episode, ended, C->first, starts};
+  const dim3 grid((unsigned)((n_plants + NPD_POLICY_TILE - 1) / NPD_POLICY_TILE)), block(NPD_POLICY_LANES);
+  if (npd_policy_small(P, C->H)) hipLaunchKernelGGL((npb_segment_starts_kernel<NPD_POLICY_SMALL_CELLS, NPD_POLICY_SMALL_WIDTH>), grid, block, 0, stream, *P, *C, G);
+  else hipLaunchKernelGGL((npb_segment_starts_kernel<NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX>), grid, block, 0, stream, *P, *C, G);
 }

@@ -1880,6 +1880,9 @@ class BatchedPlantEnv:
         default what the last ``rollout_advantages`` returned.  A short last batch is yielded unless ``drop_last``.  ``moments``: a
         device float64 [4] (``rollout_moments_shards``: the moments over all shards) used in place of the handle's own; together with
         ``normalize=False`` it is refused by name.
+        ``unit="segment"`` (truncated segments of a recurrent policy; npb_rollout_minibatch_segments; after ``policy_segments(every)``): a
+        permutation of the ``(t / every) * n`` segments; ``index`` [count] is the segment id ``c * n + p``, every tensor is time-major
+        [every, count, ...] with ``out[s][j] = src[c * every + s][p]``, and the dict carries ``"every"``.  ``t % every != 0`` is refused.
         THE YIELDED TENSORS ARE VIEWS OF BUFFERS THE ENV KEEPS, the same storage on every yield: use or copy a minibatch before asking for
         the next.  ``act`` / ``extra`` are None where the rollout has none.  ``set_rollout(None)`` drops the buffers.
         ``nuclear_sim_amd.rollout.minibatch`` is the same in numpy, bit for bit."""
@@ -1887,7 +1890,8 @@ class BatchedPlantEnv:
         if not hasattr(self.L, "npb_rollout_minibatch"):
             raise _lib.NpbError("libnpb.so has no npb_rollout_minibatch: rebuild")
         if unit not in _lib.MINIBATCH_UNITS:
-            raise ValueError("a minibatch's unit is 'transition' or 'plant', not %r" % (unit,))
+            raise ValueError("a minibatch's unit is 'transition' or 'plant', not %r (or 'segment', after policy_segments())" % (unit,))
+        every = self._segments("rollout_minibatches(unit='segment')")["every"] if unit == "segment" else None
         B, epochs, first_epoch = int(batch_size), int(epochs), int(first_epoch)
         if B < 1 or epochs < 0:
             raise ValueError("batch_size must be >= 1 and epochs >= 0")
@@ -1902,16 +1906,21 @@ class BatchedPlantEnv:
         adv, ret, t = self._last_advantages(ro, advantages)
         if t < 1:
             raise _lib.NpbError("nothing recorded yet (t == 0)")
-        plant = unit == "plant"
-        N = self.n if plant else t * self.n
-        if N > rollout.N_MAX:
+        plant = unit != "transition"      # (time-major outputs: whole sequences, or segments)
+        slots = t if unit == "plant" else every
+        if every is not None:
+            if not hasattr(self.L, "npb_rollout_minibatch_segments"):
+                raise _lib.NpbError("libnpb.so has no npb_rollout_minibatch_segments: rebuild")
+            recurrent.chunks_of(t, every)
+        N = self.n if unit == "plant" else (t * self.n if every is None else (t // every) * self.n)
+        if N > rollout.N_MAX or t * self.n > rollout.N_MAX and unit != "plant":
             raise ValueError("t * n = %d is beyond 2^31 - 1, what an index holds" % N)
         B = min(B, N)
         if moments is None:
             moments = self.rollout_moments(adv[:t], ddof) if normalize else None
         spec, tensors = ro["spec"], ro["tensors"]
         (K, C), A, E = spec["stack"], spec["axes"], spec["extras"]
-        rows = B * t if plant else B
+        rows = B * slots if plant else B
         key = (B, rows, adv.dtype)
         if ro.get("mb_key") != key:      # the buffers: one set, flat, as many rows as the largest minibatch has
             with torch.cuda.device(self.device):
@@ -1930,7 +1939,7 @@ class BatchedPlantEnv:
         d.extra = None if buf["extra"] is None else buf["extra"].data_ptr()
 
         def view(x, count, *cells):
-            shape = ((t, count) if plant else (count,)) + cells
+            shape = ((slots, count) if plant else (count,)) + cells
             return None if x is None else x[:int(np.prod(shape))].view(shape)
 
         def batches():
@@ -1942,9 +1951,15 @@ class BatchedPlantEnv:
                     if count < B and drop_last:
                         break
                     d.first, d.count = first, count
-                    _lib.check(self.L.npb_rollout_minibatch(self._h, ctypes.byref(d), self._stream()), self._h)
-                    yield {"index": buf["index"][:count], "obs": view(buf["obs"], count, K, C), "act": view(buf["act"], count, A),
-                           "extra": view(buf["extra"], count, E), "adv": view(buf["adv"], count), "ret": view(buf["ret"], count), "epoch": e}
+                    if every is None:
+                        _lib.check(self.L.npb_rollout_minibatch(self._h, ctypes.byref(d), self._stream()), self._h)
+                    else:
+                        _lib.check(self.L.npb_rollout_minibatch_segments(self._h, ctypes.byref(d), every, self._stream()), self._h)
+                    batch = {"index": buf["index"][:count], "obs": view(buf["obs"], count, K, C), "act": view(buf["act"], count, A),
+                             "extra": view(buf["extra"], count, E), "adv": view(buf["adv"], count), "ret": view(buf["ret"], count), "epoch": e}
+                    if every is not None:
+                        batch["every"] = every
+                    yield batch
             del held
         return batches()
 
@@ -2304,10 +2319,14 @@ class BatchedPlantEnv:
 
     # ------------------------------------------------------------------ training through time
     def _ppo_seq(self, batch, d):
-        """``(npb_ppo_seq_t, tensors kept alive)`` of a ``unit="plant"`` minibatch whose descriptor ``d`` is made (its ``rows_per_chain``
+        """``(npb_ppo_seq_t, npb_ppo_segments_t or None, tensors kept alive)`` of a ``unit="plant"`` minibatch whose descriptor ``d`` is made (its ``rows_per_chain``
         counting the plants of a chain): its [t, count] shape, its
         ``index``, and the rollout's ``episode`` and ``ended`` and the core's ``first`` from the handle -- or the batch's own ``episode``
-        [T, n], ``ended`` [T, n] and ``first`` [n, H], which ``index`` (None = identity) then points into"""
+        [T, n], ``ended`` [T, n] and ``first`` [n, H], which ``index`` (None = identity) then points into.
+        A SEGMENT minibatch (the batch carries ``"every"``: ``rollout_minibatches(unit="segment")``) is the same with ``t = every``, its
+        sequences segments and ``index`` their ids ``c * n + p``; ``first`` is then the stored states [chunks, n, H] (the handle's: what
+        ``policy_segments`` bound, its first ``recorded slots / every`` rows), and the second member is the
+        npb_ppo_segments_t that selects the segment entry points (None for whole sequences)"""
         pol = self._policy_cell("training through time")
         if not hasattr(self.L, "npb_policy_grad_seq"):
             raise _lib.NpbError("libnpb.so has no npb_policy_grad_seq: rebuild")
@@ -2316,6 +2335,12 @@ class BatchedPlantEnv:
         if len(shape) != 2:
             raise ValueError("a sequence minibatch is time-major, adv [t, count] (rollout_minibatches(unit='plant')), not %r" % (shape,))
         t, count = shape
+        every = batch.get("every")
+        if every is not None:
+            if not hasattr(self.L, "npb_policy_grad_segments"):
+                raise _lib.NpbError("libnpb.so has no npb_policy_grad_segments: rebuild")
+            if int(every) != t:
+                raise ValueError("a segment minibatch is [every, count]: every = %r, and adv has %d slots" % (every, t))
         own = [batch.get(name) for name in ("episode", "ended", "first")]
         if any(x is None for x in own):
             if any(x is not None for x in own):
@@ -2324,17 +2349,34 @@ class BatchedPlantEnv:
             if pol["first"] is None:
                 raise _lib.NpbError("the policy was set without a rollout (set_rollout, then set_policy): no state in front of slot 0")
             own = [ro["tensors"]["episode"], ro["tensors"]["ended"], pol["first"]]
+            if every is not None:
+                seg = self._segments("a segment minibatch without its own episode, ended and first")
+                if seg["every"] != t:
+                    raise ValueError("the batch's every = %d is not policy_segments' %d" % (t, seg["every"]))
+                recorded = int(self.L.npb_rollout_steps(self._h))
+                own[2] = seg["starts"][:recurrent.chunks_of(recorded, t)]
         episode, ended, first = (torch.as_tensor(x).to(device=self.device).contiguous() for x in own)
         if episode.dtype != torch.int32 or ended.dtype != torch.uint8 or first.dtype != torch.float32:
             raise ValueError("episode is int32, ended uint8 and first float32")
-        n = first.shape[0]
-        if first.dim() != 2 or first.shape[1] != H or episode.dim() != 2 or episode.shape[1] != n or episode.shape[0] < t or ended.shape != episode.shape:
-            raise ValueError("episode and ended are [>= %d, n] and first [n, %d]" % (t, H))
+        chunks = None
+        if every is not None:
+            if first.dim() != 3 or first.shape[2] != H or episode.dim() != 2 or episode.shape[1] != first.shape[1] or \
+                    episode.shape[0] < first.shape[0] * t or ended.shape != episode.shape:
+                raise ValueError("a segment minibatch's first is the stored states [chunks, n, %d], episode and ended [>= chunks * %d, n]" % (H, t))
+            chunks, n = first.shape[0], first.shape[1]
+        else:
+            n = first.shape[0]
+            if first.dim() != 2 or first.shape[1] != H or episode.dim() != 2 or episode.shape[1] != n or episode.shape[0] < t or ended.shape != episode.shape:
+                raise ValueError("episode and ended are [>= %d, n] and first [n, %d]" % (t, H))
         index = batch.get("index")
-        if index is None and count != n:
-            raise ValueError("a minibatch of %d of the rollout's %d plants needs its index" % (count, n))
+        if index is None and count != n * (chunks or 1):
+            raise ValueError("a minibatch of %d of the rollout's %d %s needs its index" % (count, n * (chunks or 1), "plants" if chunks is None else "segments"))
         held = [episode, ended, first]
         s = _lib.NpbPpoSeq()
+        seg = None
+        if chunks is not None:
+            seg = _lib.NpbPpoSegments()
+            seg.every, seg.chunks = t, chunks
         s.t, s.plants, s.n_plants = t, count, n
         s.episode, s.ended, s.first = episode.data_ptr(), ended.data_ptr(), first.data_ptr()
         if index is not None:
@@ -2343,7 +2385,7 @@ class BatchedPlantEnv:
                 raise ValueError("index must be int32 with one entry a sequence (%d)" % count)
             s.index = index.data_ptr()
             held.append(index)
-        return s, held
+        return s, seg, held
 
     def policy_grad_sequences(self, batch, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0, max_grad_norm: float = 0.5,
                               plants_per_chain: int = 32, diagnostics: bool = False, max_blocks: int = 0, clip_vf: float = 0.0, value_old=None) -> dict:
@@ -2356,11 +2398,15 @@ class BatchedPlantEnv:
         parameters.  ``plants_per_chain`` (a positive multiple of 32) pins the order of the sums; no bit depends on ``max_blocks``.
         ``first`` is the state the collecting parameters produced: after the first update of an iteration it is stale, as in every
         recurrent PPO.  ``nuclear_sim_amd.recurrent.gradient`` is the same in numpy: bit for bit with hard gates and relu when fed the
-        device's ``ratio``."""
+        device's ``ratio``.
+        A SEGMENT minibatch (``rollout_minibatches(unit="segment")``; its ``"every"`` selects npb_policy_grad_segments) is truncated
+        back-propagation through time: every sequence is one segment, started from the stored state of ``policy_segments`` (or the
+        batch's own ``first`` = starts [chunks, n, H]) and differentiated within itself only; ``plants_per_chain`` counts segments.
+        ``nuclear_sim_amd.recurrent.gradient_segments`` is the same in numpy."""
         d, held = self._ppo_desc(batch, clip, vf_coef, ent_coef, max_grad_norm, plants_per_chain, max_blocks)
         more, held_more = self._ppo_more(batch, d.count, clip_vf, value_old)
         pol = self._policy_cell("policy_grad_sequences()")
-        s, held_seq = self._ppo_seq(batch, d)
+        s, seg, held_seq = self._ppo_seq(batch, d)
         t, count = s.t, s.plants
         out = {}
         with torch.cuda.device(self.device):
@@ -2373,7 +2419,11 @@ class BatchedPlantEnv:
             out["grad"] = torch.zeros(pol["theta"].numel(), dtype=torch.float32, device=self.device)
             out["stats"] = torch.zeros(_lib.PPO_STATS, dtype=torch.float64, device=self.device)
             out["more"] = torch.zeros(_lib.PPO_STATS_MORE, dtype=torch.float64, device=self.device)
-        _lib.check(self.L.npb_policy_grad_seq(self._h, ctypes.byref(d), None if more is None else ctypes.byref(more), ctypes.byref(s), self._stream()), self._h)
+        if seg is None:
+            _lib.check(self.L.npb_policy_grad_seq(self._h, ctypes.byref(d), None if more is None else ctypes.byref(more), ctypes.byref(s), self._stream()), self._h)
+        else:
+            _lib.check(self.L.npb_policy_grad_segments(self._h, ctypes.byref(d), None if more is None else ctypes.byref(more), ctypes.byref(s),
+                                                       ctypes.byref(seg), self._stream()), self._h)
         _lib.check(self.L.npb_policy_get_grad(self._h, ctypes.c_void_p(out["grad"].data_ptr()), self._stream()), self._h)
         _lib.check(self.L.npb_policy_get_stats(self._h, ctypes.c_void_p(out["stats"].data_ptr()), self._stream()), self._h)
         _lib.check(self.L.npb_policy_get_stats_more(self._h, ctypes.c_void_p(out["more"].data_ptr()), self._stream()), self._h)
@@ -2388,14 +2438,18 @@ class BatchedPlantEnv:
         L = self.policy_shard_size()
         d, held = self._ppo_desc(batch, clip, vf_coef, 0.0, 0.0, plants_per_chain, max_blocks)
         more, held_more = self._ppo_more(batch, d.count, clip_vf, value_old)
-        s, held_seq = self._ppo_seq(batch, d)
+        s, seg, held_seq = self._ppo_seq(batch, d)
         if out is None:
             with torch.cuda.device(self.device):
                 out = torch.zeros(L, dtype=torch.float64, device=self.device)
         elif out.dtype != torch.float64 or out.numel() != L or not out.is_contiguous() or out.device != self.device:
             raise ValueError("out must be a contiguous float64 tensor of %d elements on %s" % (L, self.device))
-        _lib.check(self.L.npb_policy_shard_sums_seq(self._h, ctypes.byref(d), None if more is None else ctypes.byref(more), ctypes.byref(s), int(count_total),
-                                                    ctypes.c_void_p(out.data_ptr()), self._stream()), self._h)
+        if seg is None:
+            _lib.check(self.L.npb_policy_shard_sums_seq(self._h, ctypes.byref(d), None if more is None else ctypes.byref(more), ctypes.byref(s), int(count_total),
+                                                        ctypes.c_void_p(out.data_ptr()), self._stream()), self._h)
+        else:      # (a segment minibatch: its "every" selects the segment entry point)
+            _lib.check(self.L.npb_policy_shard_sums_segments(self._h, ctypes.byref(d), None if more is None else ctypes.byref(more), ctypes.byref(s),
+                                                             ctypes.byref(seg), int(count_total), ctypes.c_void_p(out.data_ptr()), self._stream()), self._h)
         self._pol["ppo_held"] = held + held_more + held_seq      # (alive while the launches read them)
         return out
 
@@ -2411,7 +2465,7 @@ class BatchedPlantEnv:
     def policy_train(self, batch_size, epochs: int = 1, seed: int = 0, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0,
                      max_grad_norm: float = 0.5, rows_per_chain: Optional[int] = None, lr=3e-4, betas=(0.9, 0.999), eps: float = 1e-5,
                      clip_vf: float = 0.0, target_kl=None, more: bool = False, exchange=None, shard_cells=None, global_moments: bool = False,
-                     **minibatches):
+                     refresh=None, **minibatches):
         """The optimiser's half of a PPO iteration: ``rollout_minibatches(batch_size, epochs, seed, **minibatches)`` and one
         npb_policy_update -- gradient and Adam step -- per minibatch.  Returns every update's stats as ONE device tensor [updates, 8]
         (``ppo.STATS``'s order), and with ``more=True`` ``(stats, more [updates, 4])`` (``ppo.STATS_MORE``'s order).  ``collect``,
@@ -2436,9 +2490,20 @@ class BatchedPlantEnv:
         A POLICY WITH A CORE trains through time with ``unit="plant"``: every minibatch is whole sequences and an update is
         npb_policy_update_seq (``policy_grad_sequences`` and the Adam step); ``rows_per_chain`` then counts the PLANTS of a chain (default
         32; row-wise a chain is 256 rows by default), and every option above works as it does row-wise.  With the default unit a policy with a core is refused
-        by name: rows carry no order."""
+        by name: rows carry no order.
+        ``unit="segment"`` (after ``policy_segments(every)``) trains over truncated segments: every minibatch is segments of ``every``
+        slots and an update is npb_policy_update_segments; ``rows_per_chain`` counts SEGMENTS (default 32), ``shard_cells`` counts segments
+        (``(t / every) * n``) and ``count_total`` counts cells.  ``refresh="epoch"``: ``policy_refresh_segments()`` runs before every
+        epoch after the first, so the segments of later epochs start from states of the current parameters (None: they stay as
+        collected)."""
         pol = self._on("_pol")
-        sequences = pol["spec"]["core"] is not None and minibatches.get("unit", "transition") == "plant"
+        unit = minibatches.get("unit", "transition")
+        if refresh not in (None, "epoch"):
+            raise ValueError("refresh is None or 'epoch', not %r" % (refresh,))
+        if refresh is not None and unit != "segment":
+            raise ValueError("refresh='epoch' recomputes the stored segment states: it goes with unit='segment'")
+        sequences = pol["spec"]["core"] is not None and unit in ("plant", "segment")
+        seg_every = self._segments("policy_train(unit='segment')")["every"] if unit == "segment" else None
         if rows_per_chain is None:      # (a chain of sequences counts plants: one tile of them; a chain of rows is 256 rows, as it was)
             rows_per_chain = 32 if sequences else 256
         kl_limit = 0.0
@@ -2458,10 +2523,10 @@ class BatchedPlantEnv:
                 raise ValueError("shard_cells: the shards make different numbers of updates (%r) under batch_size %d: shards with different "
                                  "numbers of updates are not supported" % ([len(c) for c in counts], int(batch_size)))
             t = self._last_advantages(self._on("_roll"), minibatches.get("advantages"))[2]
-            own = self.n if minibatches.get("unit", "transition") == "plant" else t * self.n
+            own = self.n if unit == "plant" else (t * self.n if seg_every is None else recurrent.chunks_of(t, seg_every) * self.n)
             if own not in cells:
                 raise ValueError("shard_cells %r does not hold this shard's own %d cells" % (cells, own))
-            per = t if minibatches.get("unit", "transition") == "plant" else 1      # (a plant is t rows: the shards record in lockstep)
+            per = t if unit == "plant" else (1 if seg_every is None else seg_every)      # (a plant is t rows, a segment every: the shards record in lockstep)
             totals = [per * sum(c[i] for c in counts) for i in range(len(counts[0]))]
         if global_moments:
             if exchange is None:
@@ -2475,7 +2540,7 @@ class BatchedPlantEnv:
         if callable(lr) or isinstance(lr, (list, tuple, np.ndarray)):
             # the number of updates, as rollout_minibatches cuts them (its batches are views of one buffer: they cannot be listed first)
             t = self._last_advantages(self._on("_roll"), minibatches.get("advantages"))[2]
-            N = self.n if minibatches.get("unit", "transition") == "plant" else t * self.n
+            N = self.n if unit == "plant" else (t * self.n if seg_every is None else recurrent.chunks_of(t, seg_every) * self.n)
             B = min(int(batch_size), N)
             updates = int(epochs) * (N // B if minibatches.get("drop_last") else -(-N // B))
             rates = [float(lr(i, updates)) for i in range(updates)] if callable(lr) else [float(x) for x in lr]
@@ -2488,14 +2553,20 @@ class BatchedPlantEnv:
                 raise _lib.NpbError("libnpb.so has no npb_policy_train_begin: rebuild")
             _lib.check(self.L.npb_policy_train_begin(self._h, self._stream()), self._h)
         try:
+            epoch0 = None
             for i, batch in enumerate(batches):
+                if refresh is not None:      # (the batch is gathered already: the gather reads no stored state)
+                    epoch0 = batch["epoch"] if epoch0 is None else epoch0
+                    if batch["epoch"] != epoch0:
+                        epoch0 = batch["epoch"]
+                        self.policy_refresh_segments()
                 rate = float(lr) if rates is None else rates[i]
                 held = held_more = []
                 if totals is None:
                     d, held = self._ppo_desc(batch, clip, vf_coef, ent_coef, max_grad_norm, rows_per_chain)
                     m, held_more = self._ppo_more(batch, d.count, clip_vf, None, kl_limit)
                     if sequences:
-                        s, held_seq = self._ppo_seq(batch, d)
+                        s, seg, held_seq = self._ppo_seq(batch, d)
                         held = held + held_seq
                 with torch.cuda.device(self.device):
                     row = torch.zeros(_lib.PPO_STATS, dtype=torch.float64, device=self.device)
@@ -2509,6 +2580,9 @@ class BatchedPlantEnv:
                     if not isinstance(every, torch.Tensor) or every.shape != (len(cells), vec.numel()):
                         raise ValueError("exchange must return the [%d, %d] tensor of every shard's sums" % (len(cells), vec.numel()))
                     self.policy_apply_shards(every.contiguous(), totals[i], ent_coef, max_grad_norm, rate, (b1, b2), eps, kl_limit)
+                elif sequences and seg is not None:
+                    _lib.check(self.L.npb_policy_update_segments(self._h, ctypes.byref(d), None if m is None else ctypes.byref(m), ctypes.byref(s),
+                                                                 ctypes.byref(seg), rate, b1, b2, eps, self._stream()), self._h)
                 elif sequences:
                     _lib.check(self.L.npb_policy_update_seq(self._h, ctypes.byref(d), None if m is None else ctypes.byref(m), ctypes.byref(s), rate, b1, b2, eps,
                                                             self._stream()), self._h)
@@ -2569,7 +2643,54 @@ class BatchedPlantEnv:
         H = pol["spec"]["core"]
         with torch.cuda.device(self.device):
             final = pol["final"] if pol["final"] is not None else torch.zeros((0, H), dtype=torch.float32, device=self.device)
-        return {"first": pol["first"], "final": final}
+        out = {"first": pol["first"], "final": final}
+        if pol.get("segments") is not None:
+            out["starts"], out["every"] = pol["segments"]["starts"], pol["segments"]["every"]
+        return out
+
+    # ------------------------------------------------------------------ truncated segments
+    def _segments(self, what) -> dict:
+        pol = self._policy_cell(what)
+        if pol.get("segments") is None:
+            raise _lib.NpbError("%s: no stored segment states (policy_segments(every) first)" % what)
+        return pol["segments"]
+
+    def policy_segments(self, every) -> None:
+        """Truncated back-propagation through time for a policy with a core (npb_policy_core_segments): while collecting, the state the
+        policy read in front of every slot ``c * every`` of the rollout, the restart rule applied, is kept in ``starts`` float32
+        [ceil(T / every), n, H] (``policy_rollout_hidden()["starts"]``; row 0 has ``first``'s bits; rows of slots not reached keep what
+        they held).  Call it after ``set_rollout`` and ``set_policy(core=...)``; ``None`` clears it; ``set_policy`` drops it.
+        ``rollout_minibatches(unit="segment")`` then cuts the recorded slots into segments of ``every`` slots, ``policy_grad_sequences``
+        differentiates each within itself from its stored state, ``policy_train(unit="segment")`` is the loop, and
+        ``policy_refresh_segments()`` recomputes the stored states under the current parameters.  ``recurrent.starts`` is the numpy
+        statement.  A handle that never calls this behaves as before."""
+        if not hasattr(self.L, "npb_policy_core_segments"):
+            raise _lib.NpbError("libnpb.so has no npb_policy_core_segments: rebuild")
+        if every is None:
+            pol = self._on("_pol")
+            _lib.check(self.L.npb_policy_core_segments(self._h, 0, None, 0), self._h)
+            pol.pop("segments", None)
+            return
+        pol = self._policy_cell("policy_segments()")
+        ro = self._on("_roll")
+        if pol["first"] is None:
+            raise _lib.NpbError("policy_segments(): the policy was set without a rollout (set_rollout, then set_policy)")
+        L, T, H = int(every), int(ro["spec"]["horizon"]), pol["spec"]["core"]
+        if L < 1 or L > T:
+            raise ValueError("every must be 1 .. the rollout's horizon %d, not %r" % (T, every))
+        rows = -(-T // L)
+        with torch.cuda.device(self.device):
+            starts = torch.zeros((rows, self.n, H), dtype=torch.float32, device=self.device)
+        _lib.check(self.L.npb_policy_core_segments(self._h, L, ctypes.c_void_p(starts.data_ptr()), rows), self._h)
+        pol["segments"] = {"every": L, "starts": starts}
+
+    def policy_refresh_segments(self) -> None:
+        """Recompute the stored segment states under the CURRENT parameters (npb_policy_segment_starts): one forward-only launch over the
+        rollout's recorded slots from ``first``; rows ``1 .. t / every - 1`` of ``starts`` are rewritten, row 0 is left alone.  Before
+        any update it reproduces the recorded rows bit for bit.  ``recurrent.starts`` under the new theta is the same in numpy."""
+        seg = self._segments("policy_refresh_segments()")
+        self._on("_roll")
+        _lib.check(self.L.npb_policy_segment_starts(self._h, seg["every"], self._stream()), self._h)
 
     def policy_values(self, x=None, hidden=None) -> torch.Tensor:
         """The critic alone (npb_policy_values): float32 [rows] of ``x``, a float32 or float64 device tensor [rows, K, C] (or [rows, K * C]);

@@ -48,8 +48,8 @@ THE INPUTS.  One sequence minibatch of ``t`` slots by ``count`` plants, time-maj
 ``obs`` [t, count, K * C], ``act`` [t, count, A], ``logp_old``, ``adv``, ``ret`` and optionally ``value_old`` [t, count]; the restart words
 ``episode`` and ``ended`` [t, count] of the same plants; ``first`` [count, H], the state in front of slot 0.  The seeds' divisor is
 ``t * count``, or ``count_total`` for a shard.  ``first`` is the state the COLLECTING parameters produced: after the first update of an
-iteration it is stale.  That is inherent, and what every recurrent PPO does.  Truncated segments are not here: a sequence is differentiated
-whole.
+iteration it is stale.  That is inherent, and what every recurrent PPO does.  Here a sequence is differentiated whole; TRUNCATED SEGMENTS,
+below, cut it.
 
 FORWARD.  ``replay``'s recurrence under the CURRENT theta: slot s reads ``h_s``, +0.0 where the plant restarted in front of s (``replay``'s
 rule: an episode change, or ``ended[s - 1] & ROLLOUT_CUT``); ``advance`` gives ``h'_s`` and the poison flag; both nets run
@@ -83,7 +83,19 @@ chain: tiles of 32 plants ascending, within a tile s DESCENDING, within a slot t
 come from ``(delta_i, x)`` and ``dW_hh, db_hh`` from ``(delta_h, h)``; the nets' as in ``ppo.backward``, their first layers reading
 ``h'``.  ``x`` of a poisoned cell reads +0.0.  Across chains ``ppo.across``.  The gradient comes out in theta's layout; clipping, the
 statistics, the options and Adam are ``ppo``'s, unchanged.  THE INVARIANT: ``ppo.combine(shard_sums(..., count_total=t * count)[None],
-...)`` has the bits of ``gradient(...)``."""
+...)`` has the bits of ``gradient(...)``.
+
+TRUNCATED SEGMENTS (``starts``, ``segment_words``, ``gradient_segments``, ``shard_sums_segments``; npb_policy_core_segments,
+npb_policy_grad_segments, npb_policy_segment_starts).  The t recorded slots are cut into ``chunks = t / every`` segments of ``every`` slots;
+segment ``g = c * n + p`` is slots ``c * every .. c * every + every - 1`` of plant p.  While collecting, the policy records beside
+``first`` the state it read in front of every slot ``c * every`` (``starts`` [chunks, n, H]; ``starts[0]`` is ``first``); that is
+``replay(...)[::every]``.  A segment minibatch IS a sequence minibatch of length ``every`` whose plants are segments: its restart words are
+the rollout's at the segment's own slots, the word in front of its first slot dropped (that restart is in ``starts`` already), and its
+``first`` is ``starts.reshape(-1, H)[index]``.  The gradient stops at the segment's first slot: the carry out of it is dropped.
+``gradient_segments`` and ``shard_sums_segments`` call ``gradient`` and ``shard_sums`` on exactly that and add no arithmetic of their
+own.  A segment id outside ``0 .. chunks * n - 1`` is not ``valid``: poisoned and skipped in every slot.  After an update the stored
+states are stale, as ``first`` is; the refresh recomputes ``starts(first, obs, ...)`` under the current parameters, row 0 left alone.
+Ragged last segments (``t % every != 0``) are refused."""
 import numpy as np
 
 from . import policy, ppo
@@ -468,3 +480,68 @@ def shard_sums(theta, cells, n_axes, actor, critic, activation, core, gates, obs
     out = np.concatenate(parts + [dls, tail])
     assert out.size == ppo.shard_size(np.asarray(theta).size, n_axes)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- truncated segments
+
+def chunks_of(t, every):
+    """``t / every``, the segments a plant's t recorded slots are cut into; a ragged last segment is refused"""
+    t, L = int(t), int(every)
+    if L < 1 or L > t:
+        raise ValueError("every must be 1 .. the recorded slots %d, not %r" % (t, every))
+    if t % L:
+        raise ValueError("the recorded slots %d are not a multiple of every = %d: ragged last segments are not supported" % (t, L))
+    return t // L
+
+
+def starts(first, obs, episode, ended, core, gates, every):
+    """The stored states, float32 [chunks, n, H]: the state in front of every slot ``c * every``, the restart rule applied --
+    ``replay(...)[::every]``.  Row 0 is ``first``.  What the device records while collecting (npb_policy_core_segments) and what the
+    refresh recomputes under the current parameters (npb_policy_segment_starts)"""
+    chunks_of(len(np.asarray(obs)), every)
+    return replay(first, obs, episode, ended, core, gates)[::int(every)]
+
+
+def segment_words(episode, ended, index, n, every):
+    """``(episode [L, count], ended [L, count], valid [count])`` of the segments ``index`` (ids ``c * n + p``; None: every segment in
+    order) of a rollout's ``episode`` and ``ended`` [t, n]: segment g's words are rows ``c * L .. c * L + L - 1`` of column p.  An id
+    outside ``0 .. (t / L) * n - 1`` is not valid, and nothing is read through it (its words are zeros)"""
+    episode, ended = np.asarray(episode), np.asarray(ended)
+    n, L = int(n), int(every)
+    chunks = chunks_of(len(episode), L)
+    g = np.arange(chunks * n, dtype=np.int64) if index is None else np.asarray(index, dtype=np.int64).reshape(-1)
+    valid = (g >= 0) & (g < chunks * n)
+    safe = np.where(valid, g, 0)
+    slots = (safe // n)[None, :] * L + np.arange(L)[:, None]
+    cols = (safe % n)[None, :]
+    return (np.where(valid[None, :], episode[slots, cols], 0).astype(episode.dtype), np.where(valid[None, :], ended[slots, cols], 0).astype(ended.dtype), valid)
+
+
+def _segments(episode, ended, starts, index, n, every, valid):
+    starts = np.asarray(starts, dtype=np.float32)
+    H = starts.shape[-1]
+    ep, en, ok = segment_words(episode, ended, index, n, every)
+    rows = starts.reshape(-1, H)
+    if len(rows) < chunks_of(len(np.asarray(episode)), every) * int(n):
+        raise ValueError("starts has %d rows, the rollout's segments are %d" % (len(rows), chunks_of(len(np.asarray(episode)), every) * int(n)))
+    g = np.arange(len(ok), dtype=np.int64) if index is None else np.asarray(index, dtype=np.int64).reshape(-1)
+    first = rows[np.where(ok, g, 0)]
+    return ep, en, first, ok if valid is None else ok & np.asarray(valid, dtype=bool)
+
+
+def gradient_segments(theta, cells, n_axes, actor, critic, activation, core, gates, obs, act, logp_old, adv, ret, episode, ended, starts, index, n,
+                      every, valid=None, **options):
+    """``gradient`` over a segment minibatch: ``obs`` [every, count, K * C] and the other tensors as
+    ``rollout.minibatch(unit="segment", every=every)`` gathers them, ``index`` [count] its segment ids (None: every segment in order),
+    ``episode`` and ``ended`` the ROLLOUT's [t, n], ``starts`` [chunks, n, H].  ``plants_per_chain`` counts segments.  No arithmetic of
+    its own: ``gradient(..., *segment_words(...), starts.reshape(-1, H)[index], valid=...)``"""
+    ep, en, first, ok = _segments(episode, ended, starts, index, n, every, valid)
+    return gradient(theta, cells, n_axes, actor, critic, activation, core, gates, obs, act, logp_old, adv, ret, ep, en, first, valid=ok, **options)
+
+
+def shard_sums_segments(theta, cells, n_axes, actor, critic, activation, core, gates, obs, act, logp_old, adv, ret, episode, ended, starts, index, n,
+                        every, count_total, valid=None, **options):
+    """``shard_sums`` over a segment minibatch, as ``gradient_segments`` is ``gradient``; ``count_total`` counts cells"""
+    ep, en, first, ok = _segments(episode, ended, starts, index, n, every, valid)
+    return shard_sums(theta, cells, n_axes, actor, critic, activation, core, gates, obs, act, logp_old, adv, ret, ep, en, first, count_total, valid=ok,
+                      **options)

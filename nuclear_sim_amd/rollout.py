@@ -150,7 +150,7 @@ def advantages(reward, ended, final_row, values=None, last_value=None, final_val
 TREE_WIDTH = 256      # the pairwise tree's fan-in: one workgroup
 ROUNDS = 6            # the Feistel network's rounds, one uint32 key each
 N_MAX = 2 ** 31 - 1   # entries a permutation can have: an index is an int32
-UNITS = {"transition": 0, "plant": 1}      # NPB_MINIBATCH_TRANSITION / NPB_MINIBATCH_PLANT
+UNITS = {"transition": 0, "plant": 1, "segment": 2}      # NPB_MINIBATCH_TRANSITION / NPB_MINIBATCH_PLANT / NPB_MINIBATCH_SEGMENT
 
 
 def _tree(c: np.ndarray) -> np.float64:
@@ -324,15 +324,20 @@ def permutation(N, keys, first=0, count=None) -> np.ndarray:
     return x.astype(np.int32)
 
 
-def minibatch(arrays, t, adv, ret, keys, first, count, unit="transition", moments=None, eps=1e-8) -> dict:
+def minibatch(arrays, t, adv, ret, keys, first, count, unit="transition", moments=None, eps=1e-8, every=None) -> dict:
     """What npb_rollout_minibatch returns for entries ``first .. first + count`` of the epoch ``keys`` belong to.  ``arrays``: what
     ``Recorder.arrays()`` / ``env.rollout()`` give, of which the first ``t`` slots count; ``adv``, ``ret``: [>= t, n].
     ``unit="transition"``: a permutation of the t * n cells; ``index[j]`` is the flat cell s * n + p, and ``obs`` [count, K, C], ``act``
     [count, A], ``extra`` [count, E], ``adv``, ``ret`` [count] are its rows.  ``unit="plant"``: a permutation of the n plants, every output
     time-major with the plants' sequences whole: ``src[:t, index]``, [t, count, ...].  ``moments`` (count, mean, var, std): adv becomes
-    ``((double)adv - mean) / (std + eps)``, one subtraction, one addition and one IEEE division in double, narrowed once to adv's type."""
+    ``((double)adv - mean) / (std + eps)``, one subtraction, one addition and one IEEE division in double, narrowed once to adv's type.
+    ``unit="segment"`` with ``every=L`` (npb_rollout_minibatch_segments; truncated segments of a recurrent policy): a permutation of the
+    ``(t / L) * n`` segments; ``index[j]`` is the segment id ``g = c * n + p`` -- chunk c, plant p -- and every output is time-major
+    [L, count, ...] with ``out[s][j] = src[c * L + s][p]``.  ``t % L != 0`` is refused: ragged last segments are not supported."""
     if unit not in UNITS:
-        raise ValueError("a minibatch's unit is 'transition' or 'plant', not %r" % (unit,))
+        raise ValueError("a minibatch's unit is 'transition' or 'plant', not %r (or 'segment', with every=)" % (unit,))
+    if (unit == "segment") != (every is not None):
+        raise ValueError("every= is the slots of a segment: it goes with unit='segment', and only with it")
     t = int(t)
     if t < 1:
         raise ValueError("nothing recorded (t == 0)")
@@ -341,16 +346,27 @@ def minibatch(arrays, t, adv, ret, keys, first, count, unit="transition", moment
     obs = np.asarray(arrays["obs"])[:t]
     n = obs.shape[1]
     adv, ret = np.asarray(adv)[:t], np.asarray(ret)[:t]
-    N = t * n if unit == "transition" else n
+    if unit == "segment":
+        L = int(every)
+        if L < 1 or L > t:
+            raise ValueError("every must be 1 .. the recorded slots %d, not %r" % (t, every))
+        if t % L:
+            raise ValueError("the recorded slots %d are not a multiple of every = %d: ragged last segments are not supported" % (t, L))
+    N = t * n if unit == "transition" else (n if unit == "plant" else (t // L) * n)
     if count < 1:
         raise ValueError("a minibatch has at least one entry")
     index = permutation(N, keys, first, count)
     if unit == "transition":
         def take(x):
             return None if x is None or x.shape[2:] == (0,) else x[:t].reshape((t * n,) + x.shape[2:])[index]
-    else:
+    elif unit == "plant":
         def take(x):
             return None if x is None or x.shape[2:] == (0,) else x[:t][:, index]
+    else:
+        slots = (index // n)[None, :] * L + np.arange(L)[:, None]      # [L, count]: the rollout's slot of every output cell
+
+        def take(x):
+            return None if x is None or x.shape[2:] == (0,) else x[:t][slots, (index % n)[None, :]]
     a = take(adv)
     if moments is not None:
         mean, std = np.float64(moments[1]), np.float64(moments[3])

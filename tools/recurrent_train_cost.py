@@ -19,6 +19,18 @@ overhead_harness.compare_off; off_within_the_parents_own_spread judges by the pa
 -Rpass-analysis=kernel-resource-usage build of npb_ppo_seq.hip.  One JSON line, also written to --out
 (profiles/recurrent_train_cost.json).
 
+--segments: TRUNCATED SEGMENTS (npb_policy_update_segments, npb_policy_segment_starts, npb_policy_core_segments) beside whole sequences, in
+the same run, into profiles/segment_train_cost.json.  Setups, event-timed us:
+  seq_<plants>              the whole-sequence update above
+  seg_<plants>_<every>      policy_grad_sequences on a segment minibatch of ALL (t / every) * plants segments and policy_adam: the cells of the
+                            whole-sequence update, in (t / every) times as many workgroups, each (t / every) times less deep
+and on a handle of <plants> plants with config 4's autoreset, the features, the controls and a rollout of T = 128 slots:
+  step_core / step_core_rec a step with the recurrent policy, without and with policy_segments(16): the difference of the same round's
+                            blocks is what recording the stored states costs a step
+  refresh_<every>           policy_refresh_segments() alone, over the 128 recorded slots
+With --parent the whole-sequence update and step_core (no policy_segments: what the parent runs too) are measured in fresh processes,
+alternately on this build and on the parent's, and judged by overhead_harness.compare_off.
+
 Built on tools/overhead_harness.py like the *_overhead.py scripts; it is not named as they are because tests/test_overhead_harness_cpu.py
 pins their list.
 """
@@ -26,8 +38,8 @@ import argparse
 import os
 import sys
 
-from overhead_harness import add_parent_arguments, compare_off, head, off_across_builds, rotated_blocks, stats, time_steps, write_line
-from policy_cost import AXES, DT, HIDDEN, C, K, columns, nets, resources
+from overhead_harness import add_parent_arguments, compare_off, head, off_across_builds, paired, rotated_blocks, stats, time_steps, write_line
+from policy_cost import AXES, DT, HIDDEN, C, E, K, L, W, columns, nets, resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H, T, ROWS = 64, 128, 65536
@@ -134,15 +146,128 @@ def measure(plants, updates, rounds, only_off):
     return out
 
 
+def measure_segments(plants, everys, updates, rounds, only_off):
+    """--segments: the updates on a small handle with explicit tensors, then per size a handle that steps and refreshes.  only_off: what
+    the parent's build runs too -- the whole-sequence updates and the step without stored states"""
+    import torch
+    from nuclear_sim_amd.env import BatchedPlantEnv
+    env = BatchedPlantEnv.action_test("oil_top_off", range(64), dt=DT)
+    env.set_features(columns(), stack=K)
+    env.set_controls(AXES)
+    dev = env.device
+    stream = torch.cuda.current_stream(dev)
+    actor, critic, _ = nets(torch, dev, "tanh")
+    log_std = torch.full((len(AXES),), -0.5, device=dev)
+    torch.manual_seed(1)
+    gru = torch.nn.GRUCell(K * C, H).to(dev)
+    env.set_policy(actor, critic, log_std, activation="tanh", seed=1, core=gru, gates="soft")
+    batches, setups = {}, []
+    for n in plants:
+        b = batch_of(torch, dev, (T, n), 2 + n)
+        words = dict(episode=torch.zeros((T, n), dtype=torch.int32, device=dev), ended=torch.zeros((T, n), dtype=torch.uint8, device=dev))
+        batches["seq_%d" % n] = dict(b, first=torch.zeros((n, H), dtype=torch.float32, device=dev), **words)
+        setups.append("seq_%d" % n)
+        for every in ([] if only_off else everys):
+            chunks = T // every
+            # segment g = c * n + p of the identity index: [every][chunks * n] is the [T][n] tensor's rows c * every + s, chunk by chunk
+            cut = {k: v.reshape((chunks, every, n) + tuple(v.shape[2:])).transpose(0, 1).reshape((every, chunks * n) + tuple(v.shape[2:])).contiguous() for k, v in b.items()}
+            batches["seg_%d_%d" % (n, every)] = dict(cut, first=torch.zeros((chunks, n, H), dtype=torch.float32, device=dev), every=every, **words)
+            setups.append("seg_%d_%d" % (n, every))
+
+    def run_block(setup):
+        def update():
+            env.policy_grad_sequences(batches[setup], plants_per_chain=32, **HYPER)
+            env.policy_adam(lr=LR, betas=BETAS, eps=EPS)
+        return time_steps(stream, update, updates)
+    blocks = rotated_blocks(setups, rounds, run_block)
+    out = {"device": torch.cuda.get_device_name(dev), "compute_units": torch.cuda.get_device_properties(dev).multi_processor_count, "updates_per_block": updates,
+           "rounds": rounds, "features": [K, C], "axes": len(AXES), "hidden": list(HIDDEN), "core": H, "gates": "soft", "activation": "tanh", "t": T,
+           "setups": {s: stats(v) for s, v in blocks.items()}}
+    env.close()
+    for n in plants:
+        whole = out["setups"]["seq_%d" % n]["median_us"]
+        row = {"cells": T * n, "seq_workgroups": -(-n // 32), "seq_us_per_update": whole}
+        for every in ([] if only_off else everys):
+            seg = out["setups"]["seg_%d_%d" % (n, every)]["median_us"]
+            row["every_%d" % every] = {"workgroups": -(-(T // every) * n // 32), "seg_us_per_update": seg, "seg_over_seq": seg / whole, "seg_is_below_seq": bool(seg < whole)}
+        # the handle that steps: config 4's autoreset, the rollout of T slots, the recurrent policy
+        big = BatchedPlantEnv.action_test("oil_top_off", range(n), dt=DT, noise_generator="device", autoreset=True, max_episode_steps=L, episode_streams=True,
+                                          power_profile_steps=L)
+        big.set_features(columns(), stack=K, final=True)
+        big.set_controls(AXES)
+        big.set_rollout(T, extras=E)
+        stream_n = torch.cuda.current_stream(big.device)
+        big.features()
+        big.set_policy(actor, critic, log_std, activation="tanh", seed=1, extras=("value", "logp"), core=gru, gates="soft")
+
+        def step_block(setup):
+            if not only_off:
+                big.policy_segments(16 if setup == "step_core_rec" else None)
+            big.rollout_begin()
+            for _ in range(W):
+                big.step()
+            big.rollout_begin()
+            us = time_steps(stream_n, big.step, T)
+            big.rollout_begin()
+            return us
+        steps = rotated_blocks(["step_core"] if only_off else ["step_core", "step_core_rec"], rounds, step_block)
+        row["steps"] = {s: stats(v) for s, v in steps.items()}
+        if not only_off:
+            row["recording_added_us_per_step"] = paired(steps, "step_core_rec", "step_core")
+            for every in everys:
+                big.policy_segments(every)
+                big.rollout_begin()
+                for _ in range(T):
+                    big.step()
+                time_steps(stream_n, big.policy_refresh_segments, 2)
+                row["refresh_%d_us" % every] = stats([time_steps(stream_n, big.policy_refresh_segments, 5) for _ in range(rounds)])
+        big.close()
+        out["plants_%d" % n] = row
+        print("%d plants: measured" % n, file=sys.stderr, flush=True)
+    return out
+
+
+def main_segments(a):
+    out = measure_segments(a.plants, a.every, a.updates, a.rounds, a.only_off)
+    if a.parent and not a.only_off:
+        argv = ["--segments", "--updates", a.updates, "--rounds", a.rounds, "--plants"] + list(a.plants)
+        picked = []
+        this, parent = off_across_builds(__file__, argv, a.parent, a.process_repeats, lambda run: picked.append(run) or 0.0, 1500)
+        runs = {"this": picked[0::2], "parent": picked[1::2]}
+        out["parent_comparison"] = {}
+        for n in a.plants:
+            for name, pick, mine in (("seq_%d" % n, lambda r: r["setups"]["seq_%d" % n]["median_us"], out["setups"]["seq_%d" % n]),
+                                     ("step_core_%d" % n, lambda r: r["plants_%d" % n]["steps"]["step_core"]["median_us"], out["plants_%d" % n]["steps"]["step_core"])):
+                out["parent_comparison"][name] = compare_off([pick(r) for r in runs["this"]], [pick(r) for r in runs["parent"]], mine)
+    out["what"] = ("us per update of t = 128 slots x plants cells through a GRU cell 64 wide (soft gates) and nets (64, 64), tanh: policy_grad_sequences + "
+                   "policy_adam over whole sequences (seq) and over all the truncated segments of `every` slots (seg); us per step of the recurrent policy "
+                   "without and with the stored segment states recorded every 16 slots; us per policy_refresh_segments() over the 128 recorded slots; and, "
+                   "with --parent, the whole-sequence update and the step without stored states of this build against the parent's in fresh processes")
+    out["kernel"] = "v_mfma_f32_32x32x2_f32 (npb_ppo_seq.hip)"
+    out["head"] = head(ROOT)
+    if a.resources:
+        out["kernel_resources"] = resources(a.resources)
+    write_line(out, a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--plants", type=int, nargs="+", default=[4096, 8192])
+    ap.add_argument("--segments", action="store_true", help="truncated segments beside whole sequences (profiles/segment_train_cost.json)")
+    ap.add_argument("--every", type=int, nargs="+", default=[16, 32, 128])
+    ap.add_argument("--plants", type=int, nargs="+", default=None)
     ap.add_argument("--updates", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--resources", default=None, help="the output of a -Rpass-analysis=kernel-resource-usage build of npb_ppo_seq.hip")
     add_parent_arguments(ap, "recurrent_train_cost.json")
+    ap.set_defaults(out=None)      # (each mode has its own file)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "segment_train_cost.json" if a.segments else "recurrent_train_cost.json")
     sys.path.insert(0, a.package_root)
+    if a.plants is None:
+        a.plants = [2048, 4096, 8192] if a.segments else [4096, 8192]
+    if a.segments:
+        return main_segments(a)
     out = measure(a.plants, a.updates, a.rounds, a.only_off)
     if a.parent and not a.only_off:
         this, parent = off_across_builds(__file__, ["--updates", a.updates, "--rounds", a.rounds], a.parent, a.process_repeats,
