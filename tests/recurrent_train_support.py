@@ -66,6 +66,39 @@ def problem(seed, t, count, cells, H, A, actor, critic, gates, activation, speci
     return P
 
 
+EDGE_PLANTS = {"episode": 6, "cut": 7, "restarted": 8, "skipped": 9, "wide": 10}
+
+
+def edges(P):
+    """Plants the cells at time's edges and on the tile seam into a problem made with ``special=False`` (t >= 3, count >= 33), in place,
+    and returns the ``skipped`` count they make.  EDGE_PLANTS names the plants:
+      "episode" restarts by an episode change in front of the LAST slot, "cut" by a cut in front of slot 1;
+      plant 31, the last of tile 0, is poisoned at slot 0 (a NaN); plant 32, the first of tile 1, at the last slot (an infinity);
+      the last plant is poisoned at slots 1 and 2, two in a row (a NaN, then -infinity);
+      "restarted" restarts in front of slot 2 and is poisoned there; "skipped" is poisoned at slot 1 and has a NaN adv there;
+      float64 ``obs`` only: "wide" holds 1e300 at slot 1, finite as a double and an infinity once narrowed, so that cell is poisoned too."""
+    t, count, cells = P["t"], P["count"], P["cells"]
+    assert t >= 3 and count >= 33 and P["obs"].shape == (t, count, cells)
+    E = EDGE_PLANTS
+    P["episode"][t - 1:, E["episode"]] += 1
+    P["ended"][0, E["cut"]] |= CUT
+    P["episode"][2:, E["restarted"]] += 1
+    poisoned = {(0, 31): (0, np.nan), (t - 1, 32): (cells - 1, np.inf), (1, count - 1): (cells // 2, np.nan), (2, count - 1): (0, -np.inf),
+                (2, E["restarted"]): (1 % cells, np.nan), (1, E["skipped"]): (cells - 1, np.nan)}
+    if P["obs"].dtype == np.float64:
+        poisoned[(1, E["wide"])] = (0, 1e300)
+    for (s, p), (k, value) in poisoned.items():
+        P["obs"][s, p, k] = value
+    P["adv"][1, E["skipped"]] = np.nan
+    return len(poisoned)      # (distinct cells: with count = 33 and t = 3 the last plant's slot 2 IS plant 32's last slot)
+
+
+def poisoned_cells(P):
+    """bool [t, count]: the cells with a feature that is not finite once narrowed to float32"""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return ~np.isfinite(P["obs"].astype(np.float32)).all(axis=2)
+
+
 def statement(P, fn=recurrent.gradient, **kw):
     args = dict(clip=0.2, vf_coef=0.5)
     args.update(kw)
@@ -75,7 +108,8 @@ def statement(P, fn=recurrent.gradient, **kw):
 
 def autograd(P, clip=0.2, vf_coef=0.5, ent_coef=0.0):
     """the gradient of the same loss by torch float64 autograd, in theta's layout (std's slots 0): the cell written out from clamps for hard
-    gates.  A poisoned cell gives h' = 0 and no loss term; a skipped cell gives no loss term and carries"""
+    gates.  A poisoned cell gives h' = 0 and no loss term; a skipped cell gives no loss term and carries.  The features are the float32
+    roundings the policy reads, widened again: the loss is a function of those"""
     f64 = torch.float64
     theta = torch.tensor(P["theta"].astype(np.float64), requires_grad=True)
     cells, A, H, t, count = P["cells"], P["n_axes"], P["core"], P["t"], P["count"]
@@ -101,8 +135,10 @@ def autograd(P, clip=0.2, vf_coef=0.5, ent_coef=0.0):
             x = act_fn(x @ W.T + b)
         return x @ net[-1][0].T + net[-1][1]
     fresh = recurrent.restarts(P["episode"], P["ended"])
-    obs = np.nan_to_num(P["obs"].astype(np.float64), nan=0.0)
-    bad = ~np.isfinite(P["obs"]).all(axis=2)
+    # the features as the policy reads them: narrowed to float32 (a double beyond float's range is an infinity); a poisoned cell's are +0.0
+    bad = poisoned_cells(P)
+    with np.errstate(over="ignore", invalid="ignore"):
+        obs = np.where(bad[..., None], 0.0, P["obs"].astype(np.float32).astype(np.float64))
     skipped = bad | ~np.isfinite(P["adv"])
     h = torch.tensor(P["first"].astype(np.float64))
     loss = torch.zeros((), dtype=f64)

@@ -25,24 +25,27 @@ HYPER = dict(clip=0.2, vf_coef=0.5, ent_coef=0.01, max_grad_norm=0.5)
 T = 5
 
 
-def _setup(seed, count, C, K, H, actor, critic, gates="hard", activation="relu", n=4):
-    """an env whose policy has the problem's shapes and parameters, and the problem with the device's own theta (torch formed its std)"""
+def _setup(seed, count, C, K, H, actor, critic, gates="hard", activation="relu", n=4, A=3, t=T, cdtype=F32, P=None):
+    """an env whose policy has the problem's shapes and parameters, and the problem with the device's own theta (torch formed its std).
+    ``A`` axes, ``t`` slots, controls of ``cdtype`` (the type ``act`` must have); ``P``: a problem made elsewhere, in place of the seed's"""
     from nuclear_sim_amd.env import BatchedPlantEnv
-    P = problem(seed, T, count, C * K, H, 3, actor, critic, gates, activation)
-    core, a, c, log_std, _ = recurrent.unpack(P["theta"], C * K, 3, actor, critic, H)
+    if P is None:
+        P = problem(seed, t, count, C * K, H, A, actor, critic, gates, activation)
+    A = P["n_axes"]
+    core, a, c, log_std, _ = recurrent.unpack(P["theta"], C * K, A, actor, critic, H)
     env = BatchedPlantEnv.action_test("oil_top_off", range(n), dt=DT)
     env.set_features(_columns(C), stack=K, dtype=F32)
-    env.set_controls(AXES[:3])
+    env.set_controls(AXES[:A], dtype=cdtype)
     env.set_policy(a, c, log_std, activation=activation, deterministic=True, core=core, gates=gates)
     P["theta"] = _np(env.policy_theta())
-    assert np.array_equal(P["theta"][:-3].view(np.int32), recurrent.pack(a, c, log_std, core=core)[:-3].view(np.int32))
+    assert np.array_equal(P["theta"][:-A].view(np.int32), recurrent.pack(a, c, log_std, core=core)[:-A].view(np.int32))
     return env, P
 
 
 def _batch(env, P, shuffle=None, extra_plants=0):
     """the problem as the device takes it: the minibatch's tensors, and the 'rollout' the sequences came from -- its plants in another
     order, and more of them, when ``shuffle`` (a seed) is given: ``index`` then says where each sequence's restart words and first lie"""
-    count, n = P["count"], P["count"] + extra_plants
+    count, n, T = P["count"], P["count"] + extra_plants, P["t"]
     where = np.arange(count) if shuffle is None else np.random.default_rng(shuffle).permutation(n)[:count]
     episode, ended, first = np.full((T, n), 7, np.int32), np.full((T, n), 4, np.uint8), np.full((n, P["core"]), 0.5, np.float32)
     episode[:, where], ended[:, where], first[where] = P["episode"], P["ended"], P["first"]
@@ -57,8 +60,8 @@ def _array(d, names):
     return np.array([d[k] for k in names])
 
 
-def _hold(env, P, chain, batch=None, valid=None, **hyper):
-    """the bit contract on one minibatch; returns the device's outputs and the statement's"""
+def _hold(env, P, chain, batch=None, valid=None, keep=False, **hyper):
+    """the bit contract on one minibatch; returns the device's outputs and the statement's (``keep``: with its gate deltas)"""
     kw = dict(HYPER, **hyper)
     got = env.policy_grad_sequences(_batch(env, P) if batch is None else batch, plants_per_chain=chain, diagnostics=True, **kw)
     extra = dict(value_old=P["value_old"]) if kw.get("clip_vf") else {}
@@ -70,10 +73,10 @@ def _hold(env, P, chain, batch=None, valid=None, **hyper):
     ulps = np.abs(ratio[live] - own["ratio"][live]) / np.spacing(own["ratio"][live])
     print("the ratio: at most %.1f ulp from numpy's" % ulps.max())
     assert ulps.max() <= 4
-    want = statement(P, plants_per_chain=chain, ratio=ratio, valid=valid, **kw, **extra)
+    want = statement(P, plants_per_chain=chain, ratio=ratio, valid=valid, keep=keep, **kw, **extra)
     _same(got["grad"], want["grad"], "grad"); _same(got["stats"], _array(want["stats"], ppo.STATS), "stats"); _same(got["more"], _array(want["more"], ppo.STATS_MORE), "more")
     n_core = recurrent.core_size(P["cells"], P["core"])
-    assert np.isfinite(want["grad"]).all() and want["grad"][:n_core].any() and want["grad"][n_core:-3].any()
+    assert np.isfinite(want["grad"]).all() and want["grad"][:n_core].any() and want["grad"][n_core:-P["n_axes"]].any()
     return got, want
 
 

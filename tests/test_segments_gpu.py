@@ -29,14 +29,17 @@ T = 6
 KEYS = ("grad", "stats", "more", "logp_new", "value_new", "ratio", "hidden")
 
 
-def _setup(seed, n, every, C, K, H, actor, critic, gates="hard", activation="relu"):
-    """an env whose policy has the rollout problem's shapes and parameters, and the problem with the device's own theta"""
+def _setup(seed, n, every, C, K, H, actor, critic, gates="hard", activation="relu", A=3, cdtype=F32, R=None):
+    """an env whose policy has the rollout problem's shapes and parameters, and the problem with the device's own theta.  ``A`` axes,
+    controls of ``cdtype`` (the type ``act`` must have); ``R``: a rollout problem made elsewhere, in place of the seed's"""
     from nuclear_sim_amd.env import BatchedPlantEnv
-    R = rollout_problem(seed, T, n, C * K, H, 3, actor, critic, gates, activation, every)
-    core, a, c, log_std, _ = recurrent.unpack(R["theta"], C * K, 3, actor, critic, H)
+    if R is None:
+        R = rollout_problem(seed, T, n, C * K, H, A, actor, critic, gates, activation, every)
+    A = R["n_axes"]
+    core, a, c, log_std, _ = recurrent.unpack(R["theta"], C * K, A, actor, critic, H)
     env = BatchedPlantEnv.action_test("oil_top_off", range(4), dt=DT)
     env.set_features(_columns(C), stack=K, dtype=F32)
-    env.set_controls(AXES[:3])
+    env.set_controls(AXES[:A], dtype=cdtype)
     env.set_policy(a, c, log_std, activation=activation, deterministic=True, core=core, gates=gates)
     R["theta"] = _np(env.policy_theta())
     return env, R
@@ -81,7 +84,7 @@ def _hold(env, R, Q, chain, **hyper):
     want = statement_segments(R, Q, plants_per_chain=chain, ratio=ratio, **kw, **extra)
     _same(got["grad"], want["grad"], "grad"); _same(got["stats"], _array(want["stats"], ppo.STATS), "stats"); _same(got["more"], _array(want["more"], ppo.STATS_MORE), "more")
     n_core = recurrent.core_size(R["cells"], R["core"])
-    assert np.isfinite(want["grad"]).all() and want["grad"][:n_core].any() and want["grad"][n_core:-3].any()
+    assert np.isfinite(want["grad"]).all() and want["grad"][:n_core].any() and want["grad"][n_core:-R["n_axes"]].any()
     return got, want
 
 
@@ -184,10 +187,10 @@ def test_soft_gates_and_tanh_nets_within_8_times_the_statements_distance_from_fl
 SENTINEL = 7.25
 
 
-def _collecting(n, steps, gates="hard", activation="relu", every=3, H=6, first=0, fdtype=F32):
+def _collecting(n, steps, gates="hard", activation="relu", every=3, H=6, first=0, fdtype=F32, C=5, K=3, **nets):
     """a recurrent policy with stored segment states, some plants reset just before the rollout begins, so that the step limit restarts
-    some in front of a boundary slot and others inside a segment; the stored states filled with a sentinel"""
-    env = _env(n, 5, 3, fdtype, H, gates=gates, activation=activation, steps=steps, rollout=T, first=first)
+    some in front of a boundary slot and others inside a segment; the stored states filled with a sentinel.  ``nets``: actor=, critic="""
+    env = _env(n, C, K, fdtype, H, gates=gates, activation=activation, steps=steps, rollout=T, first=first, **nets)
     env.policy_segments(every)
     env.step()
     env.reset(torch.as_tensor(np.arange(first, first + n) % 3 == 1))
