@@ -1084,6 +1084,7 @@ NPB_API int npb_features_set_state(NpbHandle *h, const int32_t *primed, const in
  * No step, restore, episode, task or features kernel changes.  Not here: a discrete action table, a rate limit on the COLUMN kind
  * (npb_profile_ramp), half-precision input, the feedwater action codes (the reference accepts them and they do nothing), K steps in
  * one call.
+ * (A maintenance order needs no action table: it is a thresholded VALUE axis, npb_set_control_orders below.)
  * (The policy's section below, npb_set_policy, writes `in` on the device, and its npb_collect runs K steps in one call.)
  * NPB_VERSION stays 154: a binding detects the entry points by name.  A handle that never calls this behaves as before in every entry
  * point. */
@@ -1119,6 +1120,66 @@ NPB_API int npb_controls_clear(NpbHandle *h, const uint8_t *mask, void *stream);
 NPB_API int npb_controls_get_state(NpbHandle *h, double *held, double *prev, int32_t *age, int32_t *primed, int32_t *seen, void *stream);
 NPB_API int npb_controls_set_state(NpbHandle *h, const double *held, const double *prev, const int32_t *age, const int32_t *primed,
                                    const int32_t *seen, void *stream);
+
+/* Order rules on the controls' axes: how a policy orders maintenance.  A policy output on an NPB_CONTROL_VALUE axis is decoded and held
+ * and moves nothing; an order rule says what service happens when that held value is positive enough.  npb_set_control_orders(h, desc)
+ * attaches 1 .. NPB_CONTROL_ORDERS_MAX rules to a handle whose controls are set.  Rule r:
+ *   axis          an axis of kind NPB_CONTROL_VALUE; several rules may share one
+ *   family        NPB_ORDER_PUMP (npb_perform_maintenance), NPB_ORDER_COMPONENT (npb_perform_component_maintenance) or NPB_ORDER_TURBINE
+ *                 (npb_perform_turbine_maintenance)
+ *   action        the catalog index of that family (NPB_MA_*, NPB_CA_*, NPB_TA_*; include/npb_maint.h)
+ *   unit          pump 0..3; generator 0..2 or ejector 0..1; bearing 0..3 or stage 0..13; ignored where the family's call ignores it
+ *   option        NPB_BEARING_* for a pump's bearing replacement, NPB_CLEANING_* for the component family, else 0
+ *   amount        the pump family's target_level (95.0 is the call's default) or the component family's tubes_to_plug
+ *   threshold     a finite double
+ *   min_interval  >= 1: the steps from one firing of the rule on a plant to the next at the earliest
+ * With rules set npb_step (and so npb_collect) launches one kernel more (npd_control_orders.h; one wave per 64 plants, no LDS, no atomics
+ * beyond the maintenance log's slot hand-out), behind the controls kernel and in front of the step kernel.  For plant p let latch be
+ * "the controls read p's row on this step" and restart "the controls found p unprimed on this step" (above: a new episode index,
+ * npb_controls_clear, a fresh npb_set_controls; the Python layer's reset / restore / restore_from_bank clear the controls of the plants
+ * they restart): the orders follow exactly the plants the hold follows, and keep no restart words of their own.  With NEVER = INT32_MAX,
+ * for r ascending:
+ *   c = restart ? NEVER : since[r][p];   y = held[axis_r][p];
+ *   fire = latch && y > threshold_r && (c == NEVER || c >= min_interval_r);
+ *   since[r][p] = fire ? 1 : (c == NEVER ? NEVER : c + 1), saturating below NEVER;   fired[r][p] = fire ? 1.0 : 0.0
+ * A held row orders once, on the step it was read, not K times; a NaN output never fires, because nan_to is finite.  Where fire holds
+ * the plant gets what the family's npb_perform_* call does for (action, unit, option, amount), rule r + 1 seeing what rule r left: by
+ * bits the kernel is "for r: npb_perform_<family>(action_r, unit_r, ..., masked by fire[r])", under either storage type; with a
+ * maintenance log set it appends the NPB_MAINT_EVENT_OPERATOR* records those calls append, and the summary is folded behind it.  A plant
+ * on which nothing fires has nothing stored to it.  The work-order queue, the maint.* / mpump.* sections, the counters and the cooldown
+ * cache are untouched, for the reason npb_perform_maintenance gives.
+ * fired: the caller's device double [n_orders][n_plants], like held: a side buffer a task, features, statistics or windows can name a
+ * row of -- how an order gets a price, becomes a policy input and triggers a window.
+ * A rule that cannot succeed on this handle is refused at set time, so at run time fire means success.  npb_control_orders_check(desc,
+ * controls_desc, n_plants, mode) -- without a handle, NULL = accepted, else the reason: n_plants < 1; no controls descriptor; a rule
+ * count out of range or without its array; an axis that is none or not VALUE; an unknown family; an action outside the catalog; a pump
+ * action without a handler; a unit that does not exist; a thrust adjustment on a journal bearing; a bearing (option of a pump's bearing
+ * replacement) outside NPB_BEARING_ALL .. _THRUST; a component or a turbine the mode does not step; a NaN or infinite threshold or
+ * amount; min_interval < 1; a NULL or misaligned fired.
+ * npb_set_control_orders: desc = NULL drops the rules; NPB_EINVAL without controls and for what the check refuses, and while a policy is
+ * set (the message of npb_set_controls).  npb_set_controls, with NULL or a new descriptor, drops the rules.  Every since starts at NEVER.
+ * npb_control_orders_get_state / _set_state move since (int32 [n_orders][n_plants]) to and from a host array, synchronous on `stream`;
+ * NPB_EINVAL when no rules are set.
+ * Not here: a categorical or Bernoulli head, queued (delayed, counted) work orders, per-plant rule parameters, rules on RATE, TARGET or
+ * COLUMN axes, durations or outages of a service, the turbine's automatic maintenance.
+ * NPB_VERSION stays 154: a binding detects the entry points by name.  A handle that never calls this behaves as before in every entry
+ * point. */
+#define NPB_CONTROL_ORDERS_MAX 8
+#define NPB_CONTROL_ORDER_NEVER 0x7fffffff
+enum { NPB_ORDER_PUMP = 0, NPB_ORDER_COMPONENT = 1, NPB_ORDER_TURBINE = 2, NPB_ORDER_NFAMILY = 3 };
+typedef struct npb_control_order_t {
+  int axis, family, action, unit, option;
+  int min_interval;
+  double amount, threshold;
+} npb_control_order_t;
+typedef struct npb_control_orders_desc_t {
+  int n_orders; const npb_control_order_t *orders;      /* host */
+  double *fired;                 /* device [n_orders][n_plants] */
+} npb_control_orders_desc_t;
+NPB_API int npb_set_control_orders(NpbHandle *h, const npb_control_orders_desc_t *desc);
+NPB_API const char *npb_control_orders_check(const npb_control_orders_desc_t *desc, const npb_controls_desc_t *controls, int n_plants, int mode);
+NPB_API int npb_control_orders_get_state(NpbHandle *h, int32_t *since, void *stream);
+NPB_API int npb_control_orders_set_state(NpbHandle *h, const int32_t *since, void *stream);
 
 /* The rollout: the learner's half of the loop, written down on the device -- what the policy saw (the features), what it did (the
  * controls' input and up to NPB_ROLLOUT_EXTRAS_MAX floats of its own per plant: value, log-probability, ...), what came of it (reward, how

@@ -11,6 +11,7 @@ import os
 
 import numpy as np
 
+from .orders_abi import CONTROL_ORDER_NEVER, CONTROL_ORDERS_MAX, ORDER_FAMILIES, NpbControlOrder, NpbControlOrdersDesc
 from .ppo_abi import PPO_SHARD_ROWS, PPO_SHARDS_MAX, PPO_STATS_MORE, NpbPpoMore, NpbPpoShards
 from .recurrent_abi import POLICY_GATES, NpbPolicyCore, NpbPpoSeq, NpbPpoSegments
 from .schema import PARAMS, SCHEMA
@@ -453,14 +454,17 @@ def _summary_side(word, k, summary_keys, what):
     return ("n_created" if word == "work_order" else "n_completed", int(k), 1, "i32")
 
 
-def column_word(col, info_columns=None, task: bool = False, integer_sides: bool = False, summary_keys: int = 0, controls: int = 0) -> dict:
+def column_word(col, info_columns=None, task: bool = False, integer_sides: bool = False, summary_keys: int = 0, controls: int = 0,
+                orders: int = 0) -> dict:
     """THE resolver of a per-plant column word, for ``column_stats_request``, ``event_windows_request``, ``task_request`` and whoever reads
     a column next; a pure function, an unknown word is refused (ValueError).  Every vocabulary has the state members as ``set_fields`` keys
     them (``name``, ``(name, instance)`` or ``(name, instance, k)``), ``("info", column_name)``, ``("obs", i)`` and ``"reward"``.  ``task``:
     a task is set, so ``"task_reward"`` is a word too (statistics and windows; a task's own columns never admit it).  ``integer_sides``:
     the task's further words ``"flags"``, ``"done"``, ``"maintenance"`` and ``("work_order" | "completed", key_index)`` with ``summary_keys``
     keys in the summary.  ``controls``: the axis count while controls are set (``BatchedPlantEnv.set_controls``), so ``("control", a)`` and
-    ``("control_prev", a)`` -- axis a's row of the held and of the previous action, real-valued -- are words too.  Returns {"member": (kind, slot) -- 0 f64 / 1 i32, as npb_gather_fields takes them -- or None, "side": (buffer,
+    ``("control_prev", a)`` -- axis a's row of the held and of the previous action, real-valued -- are words too.  ``orders``: the rule
+    count while order rules are set (``BatchedPlantEnv.set_control_orders``), so ``("order", r)`` -- 1.0 where rule r fired on this step,
+    else 0.0 -- is a word too.  Returns {"member": (kind, slot) -- 0 f64 / 1 i32, as npb_gather_fields takes them -- or None, "side": (buffer,
     element offset, plant stride, element type) over the buffers of ``BatchedPlantEnv._side_buffers`` or None, "integer": bool}."""
     if info_columns is None:
         from .env import INFO_COLUMNS as info_columns
@@ -476,6 +480,10 @@ def column_word(col, info_columns=None, task: bool = False, integer_sides: bool 
         if isinstance(key[1], bool) or not isinstance(key[1], (int, np.integer)) or not 0 <= key[1] < controls:
             raise ValueError("the column %r: the controls' axes are 0 .. %d, not %r" % (key[0], controls - 1, key[1]))
         side = (key[0], int(key[1]), 1, "f64")
+    elif orders and len(key) == 2 and key[0] == "order":
+        if isinstance(key[1], bool) or not isinstance(key[1], (int, np.integer)) or not 0 <= key[1] < orders:
+            raise ValueError("the column 'order': the order rules are 0 .. %d, not %r" % (orders - 1, key[1]))
+        side = ("order", int(key[1]), 1, "f64")
     elif key == ("task_reward",):
         if not task:
             raise ValueError("the column 'task_reward' needs a task: set_task() first")
@@ -503,7 +511,7 @@ def column_word(col, info_columns=None, task: bool = False, integer_sides: bool 
 
 
 def column_stats_request(columns, limits=None, stats=("min", "max", "sum", "sumsq", "last"), info_columns=None, task: bool = False,
-                         controls: int = 0) -> dict:
+                         controls: int = 0, orders: int = 0) -> dict:
     """What ``BatchedPlantEnv.enable_column_stats`` asks of npb_set_column_stats, from the caller's words; a pure function, host only, so an
     unknown name, index or statistic is refused (ValueError) before any device work.  ``columns``: a state member as ``set_fields`` keys it
     (``name``, ``(name, instance)`` or ``(name, instance, k)``), ``("info", column_name)``, ``("obs", i)`` or ``"reward"``.  ``limits``:
@@ -522,7 +530,7 @@ def column_stats_request(columns, limits=None, stats=("min", "max", "sum", "sums
             raise ValueError("unknown statistic %r: one of %r" % (name, COLUMN_STATS))
     members, sides, where = [], [], []
     for col in columns:
-        C = column_word(col, info_columns, task, controls=controls)
+        C = column_word(col, info_columns, task, controls=controls, orders=orders)
         if C["member"]:
             where.append(("member", len(members))); members.append(C["member"])
         else:
@@ -564,7 +572,8 @@ class NpbEventWindowsDesc(ctypes.Structure):
                [(name, ctypes.c_void_p) for name in EVENT_WINDOW_WORDS + ("fired", "time", "times", "values", "cursor")]
 
 
-def event_windows_request(columns, triggers, pre, post, info_columns=None, summary_keys: int = 0, task: bool = False, controls: int = 0) -> dict:
+def event_windows_request(columns, triggers, pre, post, info_columns=None, summary_keys: int = 0, task: bool = False, controls: int = 0,
+                          orders: int = 0) -> dict:
     """What ``BatchedPlantEnv.enable_event_windows`` asks of npb_set_event_windows, from the caller's words; a pure function, host only, so
     an unknown name or a trigger that cannot work is refused (ValueError) before any device work.  ``columns`` as ``column_stats_request``
     takes them, 1 to 16.  ``triggers``: 1 to 8, each ``("trip", mask)`` (rising bits of the step's trip flags), ``("done",)``,
@@ -579,7 +588,7 @@ def event_windows_request(columns, triggers, pre, post, info_columns=None, summa
     columns = list(columns)
     if not 1 <= len(columns) <= EVENT_WINDOW_COLS_MAX:
         raise ValueError("event windows take 1 to %d columns, not %d" % (EVENT_WINDOW_COLS_MAX, len(columns)))
-    req = column_stats_request(columns, None, ("last",), info_columns, task, controls)
+    req = column_stats_request(columns, None, ("last",), info_columns, task, controls, orders)
     triggers = list(triggers)
     if not 1 <= len(triggers) <= EVENT_WINDOW_TRIGGERS_MAX:
         raise ValueError("event windows take 1 to %d triggers, not %d" % (EVENT_WINDOW_TRIGGERS_MAX, len(triggers)))
@@ -613,7 +622,7 @@ def event_windows_request(columns, triggers, pre, post, info_columns=None, summa
         elif len(t) == 3 and t[1] in (">", "<"):
             if np.isnan(float(t[2])):
                 raise ValueError("the limit of trigger %r is NaN" % (t,))
-            C = column_word(t[0], info_columns, task, controls=controls)
+            C = column_word(t[0], info_columns, task, controls=controls, orders=orders)
             T.update(member=C["member"], side=C["side"], mode="beyond", direction=1 if t[1] == ">" else -1, limit=float(t[2]))
             as_numpy.append((t[1], float(t[2])))
         else:
@@ -654,7 +663,8 @@ class NpbTaskDesc(ctypes.Structure):
                 ("terms_out", ctypes.c_void_p)]
 
 
-def task_request(reward=(), terminate=(), bias: float = 0.0, info_columns=None, summary_keys: int = 0, controls: int = 0) -> dict:
+def task_request(reward=(), terminate=(), bias: float = 0.0, info_columns=None, summary_keys: int = 0, controls: int = 0,
+                 orders: int = 0) -> dict:
     """What ``BatchedPlantEnv.set_task`` asks of npb_set_task, from the caller's words; a pure function, host only, so a word that cannot
     work is refused (ValueError, naming it) before any device work.
     A column is keyed as ``column_stats_request`` keys it -- a state member, ``("info", name)``, ``("obs", i)``, ``"reward"`` (the step's
@@ -686,7 +696,7 @@ def task_request(reward=(), terminate=(), bias: float = 0.0, info_columns=None, 
         key = (col,) if isinstance(col, str) else tuple(col)
         if key in index:
             return index[key]
-        C = column_word(col, info_columns, integer_sides=True, summary_keys=summary_keys, controls=controls)      # (an unknown word is refused there)
+        C = column_word(col, info_columns, integer_sides=True, summary_keys=summary_keys, controls=controls, orders=orders)      # (an unknown word is refused there)
         index[key] = len(columns)
         columns.append(C)
         return index[key]
@@ -775,7 +785,7 @@ class NpbFeaturesDesc(ctypes.Structure):
 
 
 def features_request(columns, stack: int = 1, dtype="float32", info_columns=None, task: bool = False, summary_keys: int = 0,
-                     controls: int = 0) -> dict:
+                     controls: int = 0, orders: int = 0) -> dict:
     """What ``BatchedPlantEnv.set_features`` asks of npb_set_features, from the caller's words; a pure function, host only, so a word that
     cannot work is refused (ValueError, naming it) before any device work.
     ``columns``: 1 to 64, each a column word or ``(word, options)``.  A word is what ``column_word`` resolves: a state member,
@@ -805,7 +815,7 @@ def features_request(columns, stack: int = 1, dtype="float32", info_columns=None
     def row(col):
         key = (col,) if isinstance(col, str) else tuple(col)
         if key not in index:
-            C = column_word(col, info_columns, task, integer_sides=True, summary_keys=summary_keys, controls=controls)      # (an unknown word is refused there)
+            C = column_word(col, info_columns, task, integer_sides=True, summary_keys=summary_keys, controls=controls, orders=orders)      # (an unknown word is refused there)
             index[key] = len(rows)
             rows.append(C)
         return index[key]
@@ -881,6 +891,66 @@ class NpbControlsDesc(ctypes.Structure):
     header's ``in``)"""
     _fields_ = [("n_axes", ctypes.c_int), ("axes", ctypes.POINTER(NpbControlAxis)), ("interval", ctypes.c_int), ("in_type", ctypes.c_int),
                 ("input", ctypes.c_void_p), ("held", ctypes.c_void_p), ("prev", ctypes.c_void_p)]
+
+
+
+# include/npb.h npb_control_orders_desc_t: order rules on the controls' VALUE axes (npb_set_control_orders)
+# (CONTROL_ORDERS_MAX, CONTROL_ORDER_NEVER, ORDER_FAMILIES and the two structures: orders_abi.py)
+ORDER_OPTIONS = ("unit", "threshold", "min_interval", "bearing", "target_level", "cleaning_type", "tubes_to_plug")
+# include/npb_maint.h NPB_MAINT_ACTIONS' handler column: the pump actions the dispatcher has a handler for (load() holds it against the library's)
+MAINT_ACTION_HANDLERS = (1, 1, 1, 1, 1, 0, 0, 1, 1, 1, 0, 1, 1, 0, 1, 1, 1, 0)
+MAINT_BEARING_REPLACEMENT = MAINT_ACTION_NAMES.index("bearing_replacement")
+TURBINE_THRUST_ADJUSTMENT = TURBINE_ACTIONS.index(("bearing", "thrust_bearing_adjustment"))
+
+
+def control_orders_request(orders) -> list:
+    """What ``BatchedPlantEnv.set_control_orders`` asks of npb_set_control_orders, from the caller's words; a pure function, host only.
+    ``orders``: 1 to 8, each ``(axis, component, action)`` or ``(axis, component, action, options)``.  ``component``: ``"pump"``, a kind of
+    ``COMPONENT_KINDS`` or a kind of ``TURBINE_KINDS``; ``action``: a name of that component's catalog or its index, resolved by
+    ``maint_action_index`` / ``component_action_index`` / ``turbine_action_index`` (whose refusals, "not offered" among them, keep their
+    messages).  ``options``: ``"unit"`` (default 0), ``"threshold"`` (0.0), ``"min_interval"`` (1), ``"bearing"`` (a pump's bearing
+    replacement; a name of ``MAINT_BEARINGS`` or NPB_BEARING_*), ``"target_level"`` (a pump's oil top-off, default 95.0),
+    ``"cleaning_type"`` (the component family; a name or NPB_CLEANING_*), ``"tubes_to_plug"``.  Returns the rules ``controls.Orders``
+    takes: [{"axis", "family", "action", "unit", "option", "amount", "threshold", "min_interval"}]; what only the controls' axes, the
+    plant count and the mode can refuse is ``controls.orders_check``'s."""
+    orders = list(orders)
+    if not 1 <= len(orders) <= CONTROL_ORDERS_MAX:
+        raise ValueError("order rules: 1 to %d, not %d" % (CONTROL_ORDERS_MAX, len(orders)))
+    rules = []
+    for r, o in enumerate(orders):
+        where = "order rule %d %r" % (r, o)
+        if not isinstance(o, (tuple, list)) or len(o) not in (3, 4):
+            raise ValueError("%s: (axis, component, action) or (axis, component, action, options)" % where)
+        axis, component, action = o[0], o[1], o[2]
+        opt = dict(o[3]) if len(o) == 4 else {}
+        unknown = sorted(set(opt) - set(ORDER_OPTIONS))
+        if unknown:
+            raise ValueError("%s: unknown option(s) %r: of %r" % (where, unknown, ORDER_OPTIONS))
+        if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)):
+            raise ValueError("%s: the axis is an index into the controls' axes" % where)
+        option, amount = 0, 0.0
+        if component == "pump":
+            family, a = "pump", maint_action_index(action)
+            bearing = opt.get("bearing")
+            if isinstance(bearing, str) and bearing not in MAINT_BEARINGS:
+                raise ValueError("%s: unknown bearing %r: one of %r" % (where, bearing, [k for k in MAINT_BEARINGS if k]))
+            option = MAINT_BEARINGS[bearing] if bearing is None or isinstance(bearing, str) else int(bearing)
+            amount = float(opt.get("target_level", 95.0))
+        elif component in COMPONENT_KINDS:
+            family, a = "component", component_action_index(component, action)
+            option = cleaning_type_index(opt.get("cleaning_type"))
+            amount = float(opt.get("tubes_to_plug", 0.0))
+        elif component in TURBINE_KINDS:
+            family, a = "turbine", turbine_action_index(component, action)
+        else:
+            raise ValueError("%s: unknown component %r: 'pump', one of %r or one of %r" % (where, component, COMPONENT_KINDS, TURBINE_KINDS))
+        if not isinstance(action, str):      # an index must name an action of the component given
+            catalog = COMPONENT_ACTIONS if family == "component" else TURBINE_ACTIONS if family == "turbine" else None
+            if catalog is not None and 0 <= a < len(catalog) and catalog[a][0] != component:
+                raise ValueError("%s: index %d of the %s catalog is a %s action, not a %s one" % (where, a, family, catalog[a][0], component))
+        rules.append({"axis": int(axis), "family": family, "action": int(a), "unit": int(opt.get("unit", 0)), "option": int(option),
+                      "amount": amount, "threshold": float(opt.get("threshold", 0.0)), "min_interval": opt.get("min_interval", 1)})
+    return rules
 
 
 # include/npb.h npb_rollout_desc_t: what the policy saw, did and got for a horizon of steps, recorded on the device (npb_set_rollout)
@@ -1202,6 +1272,11 @@ ENTRY_POINTS = (
         "npb_controls_clear": (None, [_vp, _vp, _vp]),
         "npb_controls_get_state": (None, [_vp] * 7),
         "npb_controls_set_state": (None, [_vp] * 7)}),
+    ("npb_set_control_orders", {     # order rules on the controls' VALUE axes: a policy orders maintenance
+        "npb_set_control_orders": (None, [_vp, _P(NpbControlOrdersDesc)]),
+        "npb_control_orders_check": (_cs, [_P(NpbControlOrdersDesc), _P(NpbControlsDesc), _ci, _ci]),
+        "npb_control_orders_get_state": (None, [_vp] * 3),
+        "npb_control_orders_set_state": (None, [_vp] * 3)}),
     ("npb_set_rollout", {     # the rollout: trajectories recorded on the device, and their GAE advantages
         "npb_set_rollout": (None, [_vp, _P(NpbRolloutDesc)]),
         "npb_rollout_check": (_cs, [_P(NpbRolloutDesc), _ci, _ci, _ci]),
@@ -1323,6 +1398,9 @@ def load():
         if got != (OBS_DIM, INFO_DIM, INFO_NRHO, DIAG_DIM):
             raise NpbError("libnpb.so writes obs / info / reactivity / diagnostics blocks of width %r, this binding allocates %r: "
                            "rebuild the library or update nuclear_sim_amd/_lib.py" % (got, (OBS_DIM, INFO_DIM, INFO_NRHO, DIAG_DIM)))
+    if hasattr(L, "npb_set_control_orders") and \
+            tuple(int(L.npb_maint_action_has_handler(a) != 0) for a in range(L.npb_maint_num_actions())) != MAINT_ACTION_HANDLERS:
+        raise NpbError("libnpb.so's pump action handlers are not this binding's MAINT_ACTION_HANDLERS: rebuild")
     if hasattr(L, "npb_perform_component_maintenance"):
         catalog = tuple((L.npb_component_kind_name(L.npb_component_action_kind(a)).decode(), L.npb_component_action_name(a).decode())
                         for a in range(L.npb_component_num_actions()))

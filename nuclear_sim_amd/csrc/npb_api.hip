@@ -96,6 +96,9 @@ struct NpbHandle {
   /* npb_set_controls: the axes, the caller's tensors and the handle's bookkeeping and input columns (base ctl.age); ctl_axis[input]: the
    * axis that fills that input column, -1 = none */
   npb_controls_t ctl; int ctl_axis[NPB_CONTROL_INPUT_COUNT];
+  /* npb_set_control_orders: the rules, the controls' columns they read, the caller's fired and the handle's since (base ord.since);
+   * dropped with the controls */
+  npb_control_orders_t ord;
   /* npb_set_rollout: the caller's time-major buffers, the shapes they were bound with, the rows of final_obs every plant has taken (base
    * ro.n_final) and the cursor */
   npb_rollout_t ro;
@@ -628,7 +631,7 @@ int npb_destroy(NpbHandle *h) {
   if (h->es_mem) (void)hipFree(h->es_mem);
   if (h->ers_dev) (void)hipFree(h->ers_dev);
   attachment_drop(&h->cs, h->cs.cols); attachment_drop(&h->ew, h->ew.cols); attachment_drop(&h->task, h->task.terms);
-  attachment_drop(&h->feat, h->feat.cols); attachment_drop(&h->ctl, h->ctl.age); attachment_drop(&h->ro, h->ro.n_final);
+  attachment_drop(&h->feat, h->feat.cols); attachment_drop(&h->ord, h->ord.since); attachment_drop(&h->ctl, h->ctl.age); attachment_drop(&h->ro, h->ro.n_final);
   attachment_drop(&h->mom, h->mom.ws); attachment_drop(&h->norm, h->norm.streams);
   ppo_drop(h);
   attachment_drop(&h->core, h->core.primed);
@@ -1249,6 +1252,10 @@ int npb_step(NpbHandle *h, const int32_t *action, const double *magnitude, const
     h->A->controls(h->f64, NPB_N(h), &h->ctl, &h->params, h->n_plants, h->ep_index, (hipStream_t)stream);
     if (h->ctl_axis[NPB_CONTROL_INPUT_POWER_SETPOINT] >= 0) power_setpoint = h->ctl.column[NPB_CONTROL_INPUT_POWER_SETPOINT];
     if (h->ctl_axis[NPB_CONTROL_INPUT_COOLING_WATER_TEMP] >= 0) cooling_water_temp = h->ctl.column[NPB_CONTROL_INPUT_COOLING_WATER_TEMP];
+    if (h->ord.since) {      /* the order rules on the held values: the firing plants serviced as npb_perform_* services them, their records folded */
+      h->A->control_orders(h->f64, NPB_N(h), &h->ord, h->maint_log, h->n_plants, (hipStream_t)stream);
+      summary_fold(h, (hipStream_t)stream);
+    }
   }
   npb_maint_table_t table;
   const bool maint = h->params.maint_enabled != 0;
@@ -2197,7 +2204,7 @@ int npb_set_controls(NpbHandle *h, const npb_controls_desc_t *desc) {
   if (h->ro.n_final) return fail_who(h, "npb_set_controls", g_rollout_holds);
   if (const char *why = npb_controls_check(desc, h->n_plants, h->params.heat_source)) return fail(h, NPB_EINVAL, why);
   NPB_USE_DEVICE(h);
-  if (!desc) { attachment_drop(&h->ctl, h->ctl.age); return NPB_OK; }
+  if (!desc) { attachment_drop(&h->ord, h->ord.since); attachment_drop(&h->ctl, h->ctl.age); return NPB_OK; }
   npb_controls_t C = {};
   int axis_of[NPB_CONTROL_INPUT_COUNT] = {-1, -1};
   for (int a = 0; a < desc->n_axes; a++) {
@@ -2215,6 +2222,7 @@ int npb_set_controls(NpbHandle *h, const npb_controls_desc_t *desc) {
   C.in = desc->in; C.held = desc->held; C.prev = desc->prev;
   C.age = (int32_t *)dev; C.primed = C.age + n; C.seen = C.primed + n;
   for (int i = 0; i < NPB_CONTROL_INPUT_COUNT; i++) C.column[i] = (double *)(dev + words * sizeof(int32_t)) + (size_t)i * n;
+  attachment_drop(&h->ord, h->ord.since);      /* the rules read the old axes' columns */
   attachment_drop(&h->ctl, h->ctl.age);
   h->ctl = C;
   for (int i = 0; i < NPB_CONTROL_INPUT_COUNT; i++) h->ctl_axis[i] = axis_of[i];
@@ -2237,6 +2245,93 @@ int npb_controls_get_state(NpbHandle *h, double *held, double *prev, int32_t *ag
 int npb_controls_set_state(NpbHandle *h, const double *held, const double *prev, const int32_t *age, const int32_t *primed, const int32_t *seen,
                            void *stream) {
   return state_copy(h, "npb_controls_set_state", controls_state_parts, {held, prev, age, primed, seen}, true, stream);
+}
+
+/* ---- order rules on the controls' axes (include/npb.h, npd_control_orders.h) */
+const char *npb_control_orders_check(const npb_control_orders_desc_t *D, const npb_controls_desc_t *C, int n_plants, int mode) {
+  if (!D) return nullptr;
+  if (n_plants < 1) return "npb_set_control_orders: n_plants must be >= 1";
+  if (!C || C->n_axes < 1 || C->n_axes > NPB_CONTROLS_AXES_MAX || !C->axes) return "npb_set_control_orders: no controls set (npb_set_controls first)";
+  if (D->n_orders < 1 || D->n_orders > NPB_CONTROL_ORDERS_MAX || !D->orders)
+    return "npb_set_control_orders: the rule count must be 1 .. NPB_CONTROL_ORDERS_MAX (8), with their descriptors";
+  for (int r = 0; r < D->n_orders; r++) {
+    const npb_control_order_t &R = D->orders[r];
+    if (R.axis < 0 || R.axis >= C->n_axes) return "npb_set_control_orders: a rule on an axis the controls do not have";
+    if (C->axes[R.axis].kind != NPB_CONTROL_KIND_VALUE) return "npb_set_control_orders: a rule on an axis that is not NPB_CONTROL_VALUE";
+    if (R.family == NPB_ORDER_PUMP) {
+      if (R.action < 0 || R.action >= NPB_MAINT_NACT) return "npb_set_control_orders: a pump action outside the catalog (NPB_MA_*)";
+      if (!g_maint_actions[R.action].handler) return "npb_set_control_orders: a pump action without a handler";
+      if (R.unit < 0 || R.unit >= NPB_NUM_PUMPS) return "npb_set_control_orders: a feedwater pump that does not exist (0 .. 3)";
+      if (R.action == NPB_MA_BEARING_REPLACEMENT && (R.option < NPB_BEARING_ALL || R.option > NPB_BEARING_THRUST))
+        return "npb_set_control_orders: a bearing outside NPB_BEARING_ALL .. NPB_BEARING_THRUST";
+    } else if (R.family == NPB_ORDER_COMPONENT) {
+      if (R.action < 0 || R.action >= NPB_COMPONENT_NACT) return "npb_set_control_orders: a component action outside the catalog (NPB_CA_*)";
+      const int kind = g_component_actions[R.action].kind;
+      const bool ignored = kind == NPB_COMPONENT_SGSYS || kind == NPB_COMPONENT_COND;
+      if (!ignored && (R.unit < 0 || R.unit >= NPB_COMPONENT_UNITS(kind))) return "npb_set_control_orders: a generator or ejector that does not exist";
+      const bool sg_side = kind == NPB_COMPONENT_SG || kind == NPB_COMPONENT_SGSYS;
+      if (!(mode == NPB_MODE_FULL || (mode == NPB_MODE_PRIMARY_SG && sg_side))) return "npb_set_control_orders: a component the mode does not step";
+    } else if (R.family == NPB_ORDER_TURBINE) {
+      if (R.action < 0 || R.action >= NPB_TURBINE_NACT) return "npb_set_control_orders: a turbine action outside the catalog (NPB_TA_*)";
+      const int kind = g_turbine_actions[R.action].kind;
+      const bool ignored = kind == NPB_TURBINE_SYSTEM || kind == NPB_TURBINE_LUBE;
+      if (!ignored && (R.unit < 0 || R.unit >= NPB_TURBINE_UNITS(kind))) return "npb_set_control_orders: a turbine bearing or stage that does not exist";
+      if (R.action == NPB_TA_BEARING_THRUST_BEARING_ADJUSTMENT && R.unit != NPB_TURBINE_THRUST_BEARING)
+        return "npb_set_control_orders: a thrust adjustment on a journal bearing";
+      if (mode != NPB_MODE_FULL) return "npb_set_control_orders: a turbine rule in a mode that steps no turbine";
+    } else {
+      return "npb_set_control_orders: an unknown family (NPB_ORDER_PUMP, _COMPONENT, _TURBINE)";
+    }
+    if (!is_finite(R.threshold) || !is_finite(R.amount)) return "npb_set_control_orders: a NaN or infinite threshold or amount";
+    if (R.min_interval < 1) return "npb_set_control_orders: min_interval must be >= 1";
+  }
+  if (!D->fired) return "npb_set_control_orders: a NULL fired";
+  if ((uintptr_t)D->fired & 7u) return "npb_set_control_orders: a misaligned fired: 8-byte aligned";
+  return nullptr;
+}
+static const char *const g_no_control_orders = ": no order rules set (npb_set_control_orders first)";
+int npb_set_control_orders(NpbHandle *h, const npb_control_orders_desc_t *desc) {
+  if (!h) return NPB_EINVAL;
+  if (h->pol.theta) return fail_who(h, "npb_set_control_orders", g_policy_holds);
+  NPB_USE_DEVICE(h);
+  if (!desc) { attachment_drop(&h->ord, h->ord.since); return NPB_OK; }
+  if (!h->ctl.age) return fail_who(h, "npb_set_control_orders", g_no_controls);
+  npb_controls_desc_t C = {};
+  C.n_axes = h->ctl.n_axes; C.axes = h->ctl.axes;
+  if (const char *why = npb_control_orders_check(desc, &C, h->n_plants, h->params.mode)) return fail(h, NPB_EINVAL, why);
+  npb_control_orders_t O = {};
+  for (int r = 0; r < desc->n_orders; r++) {
+    npb_control_order_t R = desc->orders[r];      /* what the family's call ignores is 0 here, as its kernel makes it before it logs */
+    if (R.family == NPB_ORDER_PUMP) { if (R.action != NPB_MA_BEARING_REPLACEMENT) R.option = 0; }
+    else if (R.family == NPB_ORDER_COMPONENT) {
+      const int kind = g_component_actions[R.action].kind;
+      if (kind == NPB_COMPONENT_SGSYS || kind == NPB_COMPONENT_COND) R.unit = 0;
+    } else {
+      const int kind = g_turbine_actions[R.action].kind;
+      if (kind == NPB_TURBINE_SYSTEM || kind == NPB_TURBINE_LUBE) R.unit = 0;
+      R.option = 0;
+    }
+    O.rule[r] = R;
+  }
+  /* the allocation: since [n_orders][n], every cell NEVER */
+  const size_t cells = (size_t)desc->n_orders * (size_t)h->n_plants;
+  std::vector<int32_t> never(cells, NPB_CONTROL_ORDER_NEVER);
+  char *dev = nullptr;
+  if (int rc = attachment_alloc(h, "npb_set_control_orders", "the rules' since words", never.data(), cells * sizeof(int32_t), cells * sizeof(int32_t), &dev)) return rc;
+  O.n_orders = desc->n_orders; O.interval = h->ctl.interval; O.held = h->ctl.held; O.age = h->ctl.age;
+  O.fired = desc->fired; O.since = (int32_t *)dev;
+  attachment_drop(&h->ord, h->ord.since);
+  h->ord = O;
+  return NPB_OK;
+}
+static StateParts control_orders_state_parts(const NpbHandle *h) {
+  return {h->ord.since, g_no_control_orders, "", 1, {{h->ord.since, (size_t)h->ord.n_orders * (size_t)h->n_plants * sizeof(int32_t), false}}};
+}
+int npb_control_orders_get_state(NpbHandle *h, int32_t *since, void *stream) {
+  return state_copy(h, "npb_control_orders_get_state", control_orders_state_parts, {since}, false, stream);
+}
+int npb_control_orders_set_state(NpbHandle *h, const int32_t *since, void *stream) {
+  return state_copy(h, "npb_control_orders_set_state", control_orders_state_parts, {since}, true, stream);
 }
 
 /* ---- the rollout (include/npb.h, npd_rollout.h) */

@@ -1,7 +1,7 @@
 /*
  * npb_attachments.hip -- the per-step attachments that read the arena ("The translation units of libnpb.so"): the state
  * log's sampler, the episode records, the reader of a per-plant column and what is built on it -- column statistics, event windows,
- * the task, the features, the controls and the normaliser's partials.  Each is a launch of its own beside the step kernels of
+ * the task, the features, the controls, the order rules on their axes and the normaliser's partials.  Each is a launch of its own beside the step kernels of
  * npb_kernels.hip and shares no device code with them beyond the headers below.  Compiled once per storage type, with the step
  * kernels' flags; its launchers make up npb_launch_attach_table / npb32_launch_attach_table (npb_attach_launchers_t, npb_kernels.h).  The halves of
  * these attachments that never see an arena element -- their clear kernels, the normaliser's reward kernel -- are in
@@ -15,6 +15,9 @@
 #include "npd_record_log.h"
 #include "npb_kernels.h"
 #include "npd_attach.h"
+#include "npd_maintenance.h"             /* the handlers the order rules call, as the operator kernels of npb_kernels.hip call them */
+#include "npd_component_maintenance.h"
+#include "npd_turbine_maintenance.h"
 
 /* the state log's sampling step for a watch list (npb_sampler_sample): one grid row per output row, lanes over the watched plants.
  * Row r < n_fields is an arena member, addressed as npb_gather_kernel addresses it with the plant ids[j] in place of the lane; the rows
@@ -195,6 +198,9 @@ static void NPB_LAUNCHER(episode_records)(int n_plants, size_t npad, const void 
 /* the caller's policy outputs (npb_set_controls): the decode kernel in front of the step and its launcher */
 #include "npd_controls.h"
 
+/* order rules on the controls' axes (npb_set_control_orders): the kernel behind the decode and its launcher */
+#include "npd_control_orders.h"
+
 /* running observation and reward normalisation (npb_set_normalizer): the partials kernel of a fold and its launcher */
 #include "npd_normalizer.h"
 
@@ -202,4 +208,5 @@ static void NPB_LAUNCHER(episode_records)(int n_plants, size_t npad, const void 
 extern "C" npb_attach_launchers_t NPB_LAUNCHER(attach_table) = {
   NPB_LAUNCHER(sample), NPB_LAUNCHER(episode_records), NPB_LAUNCHER(column_stats_fold), NPB_LAUNCHER(event_windows),
   NPB_LAUNCHER(task), NPB_LAUNCHER(features), NPB_LAUNCHER(controls), NPB_LAUNCHER(normalizer),
+  NPB_LAUNCHER(control_orders),
 };

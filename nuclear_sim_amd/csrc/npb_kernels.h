@@ -111,6 +111,14 @@ typedef struct {
   const void *in; double *held, *prev, *column[NPB_CONTROL_INPUT_COUNT];
   int32_t *age, *primed, *seen;
 } npb_controls_t;
+/* npb_set_control_orders (npd_control_orders.h): the rules as the check left them (uniform over the launch: kernel arguments; a unit or
+ * option the family's call ignores is 0), the controls' held and age they read, the caller's fired [n_orders][n_plants], the handle's
+ * since [n_orders][n_plants] (its one allocation; NULL = off) */
+typedef struct {
+  npb_control_order_t rule[NPB_CONTROL_ORDERS_MAX]; int n_orders, interval;
+  const double *held; const int32_t *age;
+  double *fired; int32_t *since;
+} npb_control_orders_t;
 /* npb_set_rollout (npd_rollout.h): the caller's buffers as the descriptor names them, the shapes they were bound with (cells = K * C of the
  * features, n_axes of the controls or 0, the element sizes of obs and act), and of the handle: n_final int32 [n_plants] (its one
  * allocation; NULL = off) and the host cursor t */
@@ -212,6 +220,9 @@ typedef struct {
    * index: the handle's carried episode indices or NULL */
   void (*normalizer)(const void *arena, size_t npad, const npb_normalizer_t *Z, int n_plants, const int32_t *index, const double *reward,
                      hipStream_t stream);
+  /* npb_set_control_orders (npd_control_orders.h): behind the controls kernel -- which rule fires on which plant, since / fired kept,
+   * and the service of the firing plants, with its records in the maintenance event log */
+  void (*control_orders)(void *arena, size_t npad, const npb_control_orders_t *O, npd_maint_log_t log, int n_plants, hipStream_t stream);
 } npb_attach_launchers_t;
 extern npb_attach_launchers_t npb_launch_attach_table, npb32_launch_attach_table;
 /* the same for either storage type (npb_storage_free.hip) */

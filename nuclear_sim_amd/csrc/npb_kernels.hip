@@ -327,22 +327,7 @@ __global__ __launch_bounds__(NPB_WAVE) void npb_step_primary_kernel(
     mp.member[q__] = (double)*(const npd_real_t *)npd_gaddr(f64, N, p, NPD_MP_COL(inst, member, q__)); } while (0)
 #define NPD_MP_STORE(inst, member, count) do { _Pragma("unroll") for (int q__ = 0; q__ < (count); q__++) \
     *(npd_real_t *)npd_gaddr(f64, N, p, NPD_MP_COL(inst, member, q__)) = (npd_real_t)mp.member[q__]; } while (0)
-/* one event site of a wave, possibly inside divergent code: the lanes with `want` take slots of the log (npd_record_log.h); the cursor
- * counts every event, and a slot at or past the capacity is not written */
-__device__ __forceinline__ void npd_maint_log(const npd_maint_log_t &L, bool want, const npb_maint_event_t &e) {
-  const npd_log_slots_t s = npd_log_reserve(L.cursor, want);
-  if (!s.rows) return;
-  const uint32_t slot = npd_log_slot(s);
-  if (want && slot < (uint32_t)L.capacity) L.records[slot] = e;
-}
-/* the tail of the npb_operator_*_maint_kernel: one record per successful order, stamped with the plant's clock t, one atomic per wave.
- * The caller guards it with `if (L.cursor)`: a run without a log (npb_set_maintenance_log) does not load the clock */
-__device__ __forceinline__ void npd_maint_log_operator(const npd_maint_log_t &L, bool ok, size_t p, double t, int unit, int action, int kind, int bearing = 0) {
-  npb_maint_event_t ev = {};
-  ev.time = t; ev.created = t; ev.planned_start = t; ev.plant = (int32_t)p;
-  ev.pump = (uint8_t)unit; ev.action = (uint8_t)action; ev.kind = (uint8_t)kind; ev.bearing = (uint8_t)bearing;
-  npd_maint_log(L, ok, ev);
-}
+/* npd_maint_log, npd_maint_log_operator: the log's event sites (npd_record_log.h) */
 /* does pump k of this lane's plant have a crossed threshold outside its cooldown?  (StateManager._check_maintenance_thresholds up
  * to the point where a violation is recorded, state_manager.py:1307-1369) */
 __device__ __forceinline__ bool npd_maint_second_look(const npd_maint_screen_t &S, const npd_real_t *f64c, size_t N, size_t p, int k, double t) {

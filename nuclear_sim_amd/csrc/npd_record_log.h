@@ -3,9 +3,10 @@
  * columns of the caller's.  The wanting lanes of a wave take consecutive slots in plant order through one device-scope atomic; the
  * cursor counts every wanting lane, and a slot at or past the capacity is the caller's to leave unwritten (the host's drain tells an
  * overflow by the count).  Across waves the order is whatever the atomics make it: the drains sort.  Only the reservation is here; the
- * record stores stay in their kernels. */
+ * record stores stay in their kernels, but for the maintenance event log's, which several units append to: npd_maint_log below. */
 #ifndef NPD_RECORD_LOG_H
 #define NPD_RECORD_LOG_H
+#include "npb_kernels.h"      /* npd_maint_log_t */
 
 struct npd_log_slots_t { uint32_t base; uint64_t rows; };      /* wave-uniform: the wave's first slot, its wanting lanes */
 
@@ -26,5 +27,22 @@ __device__ __forceinline__ uint32_t npd_log_slot(npd_log_slots_t s, int lane) { 
 /* the calling lane's own (mbcnt: no lane index needed, whatever the block's shape) */
 __device__ __forceinline__ uint32_t npd_log_slot(npd_log_slots_t s) {
   return s.base + __builtin_amdgcn_mbcnt_hi((uint32_t)(s.rows >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)s.rows, 0u));
+}
+
+/* one event site of a wave, possibly inside divergent code: the lanes with `want` take slots of the log; the cursor
+ * counts every event, and a slot at or past the capacity is not written */
+__device__ __forceinline__ void npd_maint_log(const npd_maint_log_t &L, bool want, const npb_maint_event_t &e) {
+  const npd_log_slots_t s = npd_log_reserve(L.cursor, want);
+  if (!s.rows) return;
+  const uint32_t slot = npd_log_slot(s);
+  if (want && slot < (uint32_t)L.capacity) L.records[slot] = e;
+}
+/* the tail of the npb_operator_*_maint_kernel and of a rule of npb_control_orders_kernel: one record per successful order, stamped with the plant's clock t, one atomic per wave.
+ * The caller guards it with `if (L.cursor)`: a run without a log (npb_set_maintenance_log) does not load the clock */
+__device__ __forceinline__ void npd_maint_log_operator(const npd_maint_log_t &L, bool ok, size_t p, double t, int unit, int action, int kind, int bearing = 0) {
+  npb_maint_event_t ev = {};
+  ev.time = t; ev.created = t; ev.planned_start = t; ev.plant = (int32_t)p;
+  ev.pump = (uint8_t)unit; ev.action = (uint8_t)action; ev.kind = (uint8_t)kind; ev.bearing = (uint8_t)bearing;
+  npd_maint_log(L, ok, ev);
 }
 #endif

@@ -19,7 +19,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, normalizer, policy, recordlog, recurrent, rollout
+from . import _lib, controls, normalizer, policy, recordlog, recurrent, rollout
 from .schema import SCHEMA
 
 
@@ -504,7 +504,7 @@ class BatchedPlantEnv:
         self._keep = []
         self._episode = None
         self._bank = None
-        self._mlog = self._msum = self._erec = self._cstats = self._ewin = self._task = self._feat = self._ctl = self._roll = self._norm = self._pol = None      # (see ``_OFF``)
+        self._mlog = self._msum = self._erec = self._cstats = self._ewin = self._task = self._feat = self._ctl = self._ord = self._roll = self._norm = self._pol = None      # (see ``_OFF``)
         self._diag_buf = None; self.diagnostics = None; self._diag_carried = False
         if diagnostics:      # before the first snapshot (autoreset=True takes it below), so that it records the carried rows
             self.enable_diagnostics(True, carried=True)
@@ -967,18 +967,21 @@ class BatchedPlantEnv:
             buffers.update(task_reward=tk["reward"], task_cause=tk["cause"])
         if ct is not None:
             buffers.update(control=ct["held"], control_prev=ct["prev"])
+        if self._ord is not None:
+            buffers.update(order=self._ord["fired"])
         return buffers
 
     # ------------------------------------------------------------------ what the attachments share
     # The per-step attachments -- maintenance log and summary, episode records, column statistics, event windows, task, features,
     # controls, rollout: None = off, else what the enable_* / set_* method keeps of it.  __init__ sets them; the class has them too, so that a
     # refusal "before any device work" can be checked on an object made without it.  ``_on`` reads them, with these refusals:
-    _mlog = _msum = _erec = _cstats = _ewin = _task = _feat = _ctl = _roll = _norm = _pol = None
+    _mlog = _msum = _erec = _cstats = _ewin = _task = _feat = _ctl = _ord = _roll = _norm = _pol = None
     _max_episode_steps = 0      # the autoreset's limit, 0 = none (``_enable_autoreset``)
     _OFF = {"_mlog": "no maintenance log: enable_maintenance_log() first", "_msum": "no maintenance summary: enable_maintenance_summary() first",
             "_erec": "no episode records: enable_episode_records() first", "_cstats": "no column statistics: enable_column_stats() first",
             "_ewin": "no event windows: enable_event_windows() first", "_task": "no task: set_task() first",
-            "_feat": "no features: set_features() first", "_ctl": "no controls: set_controls() first", "_roll": "no rollout: set_rollout() first",
+            "_feat": "no features: set_features() first", "_ctl": "no controls: set_controls() first",
+            "_ord": "no order rules: set_control_orders() first", "_roll": "no rollout: set_rollout() first",
             "_norm": "no normaliser: set_normalizer() first", "_pol": "no policy: set_policy() first"}
     # who reads side buffers, as a refusal names them: each keeps ``"reads"``, the buffers its request resolved to (``_reading``)
     _CONSUMERS = {"_task": "the task", "_feat": "the features", "_cstats": "the column statistics", "_ewin": "the event windows",
@@ -1014,6 +1017,10 @@ class BatchedPlantEnv:
         """the axis count while controls are set, else 0: what ``_lib.column_word`` takes as ``controls``"""
         return 0 if self._ctl is None else self._ctl["held"].shape[0]
 
+    def _n_orders(self) -> int:
+        """the rule count while order rules are set, else 0: what ``_lib.column_word`` takes as ``orders``"""
+        return 0 if self._ord is None else self._ord["fired"].shape[0]
+
     def _get_state(self, attr, getter) -> Dict[str, np.ndarray]:
         """an attachment's checkpointed state, the arrays of its ``"state"`` tuple of (name, dtype, shape) filled by the library's
         ``getter``, which takes them in that order (an empty one as NULL)"""
@@ -1041,8 +1048,8 @@ class BatchedPlantEnv:
 
     def _side_first(self, name, offset) -> int:
         """the element of side buffer ``name`` that holds plant 0's value of the column at ``offset``: a summary table is [n_keys][n], the
-        controls' held and previous values [n_axes][n]"""
-        return offset * self.n if name in ("n_created", "n_completed", "control", "control_prev") else offset
+        controls' held and previous values [n_axes][n], the order rules' fired [n_orders][n]"""
+        return offset * self.n if name in ("n_created", "n_completed", "control", "control_prev", "order") else offset
 
     def _fill_source(self, S, buffers, name, offset, stride, kind="f64") -> None:
         """fill the NpbSampleSource ``S`` from a side column as ``_lib.column_word`` names it: one value per plant"""
@@ -1087,7 +1094,7 @@ class BatchedPlantEnv:
                 _lib.check(self.L.npb_set_column_stats(self._h, None), self._h)
             self._cstats = None
             return
-        req = _lib.column_stats_request(columns, limits, stats, INFO_COLUMNS, self._task is not None, self._n_controls())      # an unknown name, index or statistic is refused here
+        req = _lib.column_stats_request(columns, limits, stats, INFO_COLUMNS, self._task is not None, self._n_controls(), self._n_orders())      # an unknown name, index or statistic is refused here
         if not hasattr(self.L, "npb_set_column_stats"):
             raise _lib.NpbError("libnpb.so has no npb_set_column_stats: rebuild")
         n_cols = len(req["members"]) + len(req["sides"])
@@ -1147,7 +1154,7 @@ class BatchedPlantEnv:
             return
         ms = self._msum
         req = _lib.event_windows_request(columns, triggers or (), pre, post, INFO_COLUMNS, 0 if ms is None else len(ms["keys"]), self._task is not None,
-                                         self._n_controls())
+                                         self._n_controls(), self._n_orders())
         if not hasattr(self.L, "npb_set_event_windows"):
             raise _lib.NpbError("libnpb.so has no npb_set_event_windows: rebuild")
         cap = max(self.n, 4096) if capacity is None else int(capacity)
@@ -1246,7 +1253,7 @@ class BatchedPlantEnv:
             self._task = None
             return
         ms = self._msum
-        req = _lib.task_request(reward, terminate, bias, INFO_COLUMNS, 0 if ms is None else len(ms["keys"]), self._n_controls())      # a bad word is refused here
+        req = _lib.task_request(reward, terminate, bias, INFO_COLUMNS, 0 if ms is None else len(ms["keys"]), self._n_controls(), self._n_orders())      # a bad word is refused here
         if not hasattr(self.L, "npb_set_task"):
             raise _lib.NpbError("libnpb.so has no npb_set_task: rebuild")
         for what in self._task_readers():      # (they hold the old task's output columns)
@@ -1341,7 +1348,7 @@ class BatchedPlantEnv:
             self._feat = None
             return
         ms = self._msum
-        req = _lib.features_request(columns, stack, dtype, INFO_COLUMNS, self._task is not None, 0 if ms is None else len(ms["keys"]), self._n_controls())      # a bad word is refused here
+        req = _lib.features_request(columns, stack, dtype, INFO_COLUMNS, self._task is not None, 0 if ms is None else len(ms["keys"]), self._n_controls(), self._n_orders())      # a bad word is refused here
         if not hasattr(self.L, "npb_set_features"):
             raise _lib.NpbError("libnpb.so has no npb_set_features: rebuild")
         spec, rows, buffers = req["spec"], req["columns"], self._side_buffers()
@@ -1394,8 +1401,9 @@ class BatchedPlantEnv:
 
     def _after_restart(self, mask) -> None:
         """behind ``reset`` / ``restore`` / ``restore_from_bank``, THE place where an attachment follows a restart the caller made: the
-        plants they reset show the features' frame of their new state, start a new hold of the controls, and have their episode cut in the
-        rollout's last recorded slot"""
+        plants they reset show the features' frame of their new state, start a new hold of the controls -- and with it their order rules
+        anew, which follow the hold's restart words and keep none of their own -- and have their episode cut in the rollout's last
+        recorded slot"""
         if self._feat is not None:
             self.clear_features(mask)
             self.features()
@@ -1595,10 +1603,13 @@ class BatchedPlantEnv:
         readers = self._control_readers()      # (none without controls: their columns are no words then)
         if readers:
             raise _lib.NpbError("%s read(s) the controls' columns: turn that off first" % " and ".join(readers))
+        readers = self._readers_of(("order",))      # (the controls go, set or None alike, and their order rules with them)
+        if readers:
+            raise _lib.NpbError("%s read(s) the order rules' columns: turn that off first" % " and ".join(readers))
         if axes is None:
             if self._ctl is not None:
                 _lib.check(self.L.npb_set_controls(self._h, None), self._h)
-            self._ctl = None
+            self._ctl = self._ord = None
             return
         spec = _lib.controls_request(axes, interval, dtype, self.params.heat_source)      # a bad axis is refused here
         if self._profile is not None and any(D["target"] == "power_setpoint" for D in spec["axes"]):
@@ -1625,6 +1636,7 @@ class BatchedPlantEnv:
         self._ctl = {"in": tin, "held": held, "prev": prev, "spec": spec,
                      "state": (("held", np.float64, (A, self.n)), ("prev", np.float64, (A, self.n)), ("age", np.int32, (self.n,)),
                                ("primed", np.int32, (self.n,)), ("seen", np.int32, (self.n,)))}
+        self._ord = None      # (npb_set_controls dropped the rules: they read the old axes)
 
     def controls_input(self) -> torch.Tensor:
         """The bound ``[n, n_axes]`` tensor the next ``step`` decodes, the same storage on every call: have the policy write into it"""
@@ -1646,6 +1658,75 @@ class BatchedPlantEnv:
     def controls_spec(self) -> dict:
         """the request as data: what ``nuclear_sim_amd.controls.Decoder`` takes"""
         return self._on("_ctl")["spec"]
+
+    def set_control_orders(self, orders) -> None:
+        """Let the policy order maintenance (npb_set_control_orders): rules on the controls' ``"value"`` axes.  Behind the decode of every
+        step, and in front of the step, one more launch looks at the held value y of each rule's axis: where the plant's row was read on
+        this step, ``y > threshold`` and the rule has not fired on the plant for ``min_interval`` steps (or not since its restart), the
+        plant gets the rule's service -- by bits what ``perform_maintenance`` / ``perform_component_maintenance`` /
+        ``perform_turbine_maintenance`` would do to it, with the same record in the maintenance log.  Nothing is read back.
+        ``orders``: 1 to 8, each ``(axis, component, action)`` or ``(axis, component, action, options)``.  ``axis``: the index of a
+        ``(None, "value")`` axis of ``set_controls``; several rules may share one and are applied in their order.  ``component``:
+        ``"pump"``, ``"steam_generator"``, ``"steam_generator_system"``, ``"condenser"``, ``"ejector"``, ``"turbine"``, ``"bearing"``,
+        ``"lubrication"`` or ``"stage"``.  ``action``: a name of ``_lib.MAINT_ACTIONS``, ``_lib.COMPONENT_ACTIONS`` or
+        ``_lib.TURBINE_ACTIONS`` for that component, or its catalog index; a handler that is not offered is refused as the ``perform_*``
+        methods refuse it.  ``options``: ``"unit"`` (the pump 0..3, generator, ejector, bearing or stage; default 0), ``"threshold"``
+        (default 0.0), ``"min_interval"`` (default 1), ``"bearing"`` (a pump's bearing replacement), ``"target_level"`` (a pump's oil
+        top-off, default 95.0), ``"cleaning_type"`` (steam generators, condenser, ejectors).  A rule that cannot succeed on this env --
+        a unit that does not exist, an action without a handler, a component the mode does not step, an axis that is no ``"value"``
+        axis -- is refused here, so a firing is a success.
+        A held row (``interval`` > 1) orders once, on the step it was read.  A plant's rules restart with its hold: a new episode,
+        ``reset``, ``restore``, ``restore_from_bank`` and ``clear_controls`` let every rule fire again at once.
+        While rules are set ``("order", r)`` -- 1.0 where rule r fired on this step, else 0.0 -- is a column word for ``set_task`` (the
+        price of an order), ``set_features`` (an input of the policy), ``enable_column_stats`` and ``enable_event_windows`` (a window
+        around an order), and ``step()`` adds ``info["orders"]``, ``[len(orders), n]``.  ``nuclear_sim_amd.controls.Orders`` is the same
+        in numpy, bit for bit.  ``set_control_orders(None)`` turns it off; ``set_controls`` drops the rules."""
+        if self._pol is not None:
+            raise _lib.NpbError("the policy reads or writes the controls every step: set_policy(None) first")
+        readers = self._readers_of(("order",))      # (none without rules: their column is no word then)
+        if readers:
+            raise _lib.NpbError("%s read(s) the order rules' columns: turn that off first" % " and ".join(readers))
+        if orders is None:
+            if self._ord is not None:
+                _lib.check(self.L.npb_set_control_orders(self._h, None), self._h)
+            self._ord = None
+            return
+        rules = _lib.control_orders_request(orders)      # a bad word is refused here
+        ctl = self._on("_ctl")
+        mode = controls.MODES[self.params.mode]
+        controls.orders_check(rules, ctl["spec"], self.n, mode)      # and what this env cannot carry out here
+        if not hasattr(self.L, "npb_set_control_orders"):
+            raise _lib.NpbError("libnpb.so has no npb_set_control_orders: rebuild")
+        R = len(rules)
+        table = (_lib.NpbControlOrder * R)()
+        for k, D in enumerate(rules):
+            X = table[k]
+            X.axis, X.family, X.action, X.unit, X.option = D["axis"], _lib.ORDER_FAMILIES[D["family"]], D["action"], D["unit"], D["option"]
+            X.min_interval, X.amount, X.threshold = int(D["min_interval"]), D["amount"], D["threshold"]
+        with torch.cuda.device(self.device):
+            fired = torch.zeros((R, self.n), dtype=torch.float64, device=self.device)
+        d = _lib.NpbControlOrdersDesc()
+        d.n_orders, d.orders, d.fired = R, table, fired.data_ptr()
+        _lib.check(self.L.npb_set_control_orders(self._h, ctypes.byref(d)), self._h)      # (refused: what was set before stays)
+        self._ord = {"fired": fired, "rules": rules, "mode": mode, "state": (("since", np.int32, (R, self.n)),)}
+
+    def control_orders(self) -> Dict[str, object]:
+        """``{"fired": the device float64 [R, n] of the last step (1.0 where rule r fired), "since": int32 [R, n] as numpy -- the steps
+        since rule r last fired on the plant, 1 on the step it fired, ``controls.NEVER`` where it has not since the plant's restart}``"""
+        return {"fired": self._on("_ord")["fired"], "since": self.control_orders_state()["since"]}
+
+    def control_orders_state(self) -> Dict[str, np.ndarray]:
+        """The order rules' own state for a checkpoint (npb_control_orders_get_state), beside ``controls_state()``: ``since`` int32 [R, n]"""
+        return self._get_state("_ord", self.L.npb_control_orders_get_state)
+
+    def load_control_orders_state(self, state) -> None:
+        """put back what ``control_orders_state()`` returned (npb_control_orders_set_state)"""
+        self._load_state("_ord", self.L.npb_control_orders_set_state, state)
+
+    def control_orders_spec(self) -> "controls.Orders":
+        """a ``nuclear_sim_amd.controls.Orders`` as these rules were set, every ``since`` at NEVER: the statement to compare with"""
+        od = self._on("_ord")
+        return controls.Orders(od["rules"], self._on("_ctl")["spec"], self.n, od["mode"])
 
     def _refuse_under_rollout(self, what: str) -> None:
         """``set_features`` / ``set_controls`` while a rollout is set, set and None alike: its pre kernel copies their tensors every step,
@@ -3085,6 +3166,7 @@ class BatchedPlantEnv:
         self._task = None
         self._feat = None
         self._ctl = None
+        self._ord = None
         self._roll = None
         self._norm = None
         self._pol = None
@@ -3314,6 +3396,8 @@ class BatchedPlantEnv:
                 info["episode_start"] = self._episode_start_out
         if ctl is not None:      # the action every plant is under after this step's decode: [n_axes, n] (set_controls)
             info["controls"] = ctl["held"]
+        if self._ord is not None:      # which rule fired on which plant on this step: [n_orders, n] (set_control_orders)
+            info["orders"] = self._ord["fired"]
         obs = self._obs
         feat = self._feat
         if feat is not None:      # the caller's policy inputs, kept behind the step (set_features)
