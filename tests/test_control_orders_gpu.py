@@ -11,107 +11,10 @@ import numpy as np
 import pytest
 import torch
 
+from control_orders_support import (AXES, DT, NEVER, QUIET, RULES, STEPS, _compare_envs, _decoder, _follow, _inputs, _make, _np, _poke,  # noqa: F401
+                                    _loop_env, _positions, _quiet, _records, _same_np, _tbits)
+
 pytestmark = pytest.mark.gpu
-
-DT, STEPS = 5.0, 12
-NEVER = 2 ** 31 - 1
-QUIET = -2.0       # below every threshold of RULES
-
-
-def _np(t):
-    return t.detach().cpu().numpy().copy()
-
-
-def _tbits(t):
-    t = t.contiguous()
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int64) if t.is_floating_point() else t
-
-
-def _same_np(got, want, where):
-    g = np.ascontiguousarray(_np(got) if isinstance(got, torch.Tensor) else got, dtype=np.float64).view(np.int64)
-    w = np.ascontiguousarray(want, dtype=np.float64).view(np.int64)
-    assert g.shape == w.shape, (where, g.shape, w.shape)
-    assert np.array_equal(g, w), (where, np.argwhere(g != w)[:4].tolist())
-
-
-def _make(n, **kw):
-    from nuclear_sim_amd.env import BatchedPlantEnv
-    return BatchedPlantEnv.action_test("oil_top_off", range(n), dt=DT, **kw)
-
-
-# rod RATE, valve TARGET, two VALUE axes: the rules read axes 2 and 3
-AXES = [("rod", "rate", {"scale": 0.5}), ("valve", "target", {"clip": (20.0, 90.0), "max_magnitude": 0.25, "nan_to": 50.0}), (None, "value"), (None, "value")]
-# all three families; two rules on pump 1 (the second sees what the first left); several on each axis; thresholds that are float32 values
-RULES = [(2, "pump", "oil_top_off", {"unit": 1, "threshold": 0.25, "target_level": 92.5}),
-         (2, "pump", "bearing_replacement", {"unit": 1, "bearing": "pump_bearings", "threshold": 0.5, "min_interval": 2}),
-         (3, "steam_generator", "tsp_chemical_cleaning", {"unit": 2, "threshold": 0.0}),
-         (3, "steam_generator_system", "routine_maintenance", {"threshold": 0.5, "min_interval": 3}),
-         (2, "condenser", "condenser_tube_cleaning", {"cleaning_type": "mechanical", "threshold": -0.25}),
-         (3, "ejector", "vacuum_ejector_cleaning", {"unit": 1, "threshold": 0.5}),
-         (2, "bearing", "turbine_bearing_replacement", {"unit": 3, "threshold": 0.25, "min_interval": 5}),
-         (3, "stage", "overhaul", {"unit": 7, "threshold": 0.75})]
-
-
-def _poke(env):
-    """start states in which the handlers move something: low oil, worn bearings, TSP fouling, condenser fouling, stage deposits"""
-    p = np.arange(env.n)
-    env.set_field("pump.oil_level", 55.0 + (p % 9), 1)
-    env.set_field("pump.wear_pump_bearings", 1.5 + 0.125 * (p % 4), 1)
-    env.set_field("sg.tsp_fouling_fraction", 0.125 + 0.015625 * (p % 6), 2)
-    env.set_field("cond.biofouling_thickness", 0.375 + 0.0625 * (p % 3))
-    env.set_field("cond.scale_thickness", 0.25 + 0 * p)
-    env.set_field("cond.ej_nozzle_fouling", 0.25 + 0.03125 * (p % 5), 0, 1)
-    env.set_field("tstg.stage_deposit_thickness", 0.25 + 0.0625 * (p % 4), 0, 7)
-    env.set_field("tstg.stage_efficiency_degradation", 0.03125 + 0 * p, 0, 7)
-    env.set_field("turb.bearing_wear_factor", 1.25 + 0.125 * (p % 3), 0, 3)
-
-
-def _quiet(n):
-    """the plants that never order: every fifth, and the whole second wave where there is one (a wave in which nothing fires)"""
-    p = np.arange(n)
-    return (p % 5 == 0) | ((p >= 64) & (p < 128))
-
-
-def _inputs(t, n, rng, dtype):
-    """[n, 4]: the value axes around the thresholds -- a third of the plants on multiples of 0.25, exactly AT a threshold among them --
-    with a NaN on a fixed plant and the quiet plants below every threshold"""
-    x = rng.uniform(-1.0, 1.0, (n, 4))
-    x[:, 1] = 50.0 + 30.0 * x[:, 1]
-    grid = np.arange(n) % 3 == 1
-    x[grid, 2:] = np.round(x[grid, 2:] * 4.0) / 4.0
-    x[7 % n, 2] = np.nan
-    x[_quiet(n), 2:] = QUIET
-    return x.astype(dtype)
-
-
-def _decoder(env, storage):
-    from nuclear_sim_amd import controls
-    P = env.params
-    return controls.Decoder(env.controls_spec(), env.n, dt=float(P.dt), storage={"f64": "float64", "f32": "float32"}[storage],
-                            speeds={"rod": P.max_control_rod_speed, "flow": P.max_flow_change_rate, "valve": P.max_valve_speed})
-
-
-def _positions(env):
-    from nuclear_sim_amd import controls
-    return {D["target"]: _np(env.get_field(controls.MEMBERS[D["target"]])) for D in env.controls_spec()["axes"] if D["kind"] in ("rate", "target")}
-
-
-def _compare_envs(a, ra, b, rb, where):
-    from nuclear_sim_amd.env import INFO_COLUMNS
-    for k, (x, y) in enumerate(zip(ra[:3], rb[:3])):
-        assert torch.equal(_tbits(x), _tbits(y)), (where, ("obs", "reward", "done")[k])
-    for name in tuple(INFO_COLUMNS) + ("trip_flags",):
-        assert torch.equal(_tbits(ra[3][name]), _tbits(rb[3][name])), (where, name)
-    (fa, ia), (fb, ib) = a.state_arrays(), b.state_arrays()
-    assert torch.equal(_tbits(fa), _tbits(fb)) and torch.equal(ia, ib), (where, "state")
-    return fa, ia
-
-
-def _records(env):
-    """the drained maintenance log, sorted, and how many records of each kind are in it"""
-    rec = env.maintenance_log_records()
-    kinds, n = np.unique(rec["kind"], return_counts=True)
-    return sorted(map(tuple, rec.tolist())), dict(zip(kinds.tolist(), n.tolist()))
 
 
 # ---------------------------------------------------------------------------------------------------------------- the twin, by bits
@@ -171,31 +74,6 @@ def test_bit_for_bit_with_the_perform_calls_of_the_numpy_statement(n, K, R, dtyp
 
 
 # ---------------------------------------------------------------------------------------------------------------- lifecycle
-def _follow(env, dec, orders, steps, rng, dtype=np.float32, between=None, autoreset=False):
-    """steps of env against Decoder + Orders: fired and since by bits; the episode indices counted as the episode kernel counts them"""
-    n = env.n
-    index = np.zeros(n, dtype=np.int32)
-    restarts = 0
-    for t in range(steps):
-        if between is not None:
-            between(t)
-        x = _inputs(t, n, rng, dtype)
-        x[~_quiet(n), 2:] = np.abs(x[~_quiet(n), 2:]) + 0.8      # well above every threshold: a rule fires whenever its interval allows
-        out = dec.step(x, _positions(env), index if autoreset else None)
-        fire = orders.step(out["held"], out["latch"], out["restart"])
-        if t > 0:
-            restarts += int(out["restart"].sum())
-        obs, rew, done, info = env.step(controls=torch.as_tensor(x))
-        got = env.control_orders()
-        _same_np(got["fired"], fire.astype(np.float64), ("fired", t))
-        assert np.array_equal(got["since"], orders.since), ("since", t, np.argwhere(got["since"] != orders.since)[:4].tolist())
-        if autoreset:
-            ended = (_np(done) != 0) | (_np(info["truncated"]) != 0)
-            assert np.array_equal(_np(info["episode_index"]), index), t
-            index[ended] += 1
-    return restarts
-
-
 LIFE_RULES = [RULES[0], RULES[6], (3, "lubrication", "turbine_oil_change", {"min_interval": 4})]      # min_interval 1, 5 and 4
 
 
@@ -324,40 +202,6 @@ def test_a_task_prices_an_order_the_features_carry_it_and_a_window_is_triggered_
 
 
 # ---------------------------------------------------------------------------------------------------------------- the loop
-def _weights(seed, cells, n_axes, actor, critic):
-    from nuclear_sim_amd import policy
-    rng = np.random.default_rng(seed)
-
-    def net(dims):
-        out = []
-        for i, o in dims:
-            W = rng.standard_normal((o, i))
-            W *= rng.uniform(1.0, 3.9, (o, 1)) / np.abs(W).sum(axis=1, keepdims=True)
-            out.append((W.astype(np.float32), (0.1 * rng.standard_normal(o)).astype(np.float32)))
-        return out
-    a, c = policy.sizes(cells, n_axes, actor, critic)
-    return net(a), net(c), (0.3 * rng.standard_normal(n_axes) + 0.3).astype(np.float32)
-
-
-LOOP_AXES = [("rod", "rate", {"scale": 0.5}), ("valve", "target", {"scale": 10.0, "offset": 50.0, "clip": (20.0, 90.0), "max_magnitude": 0.25}), (None, "value")]
-LOOP_RULES = [(2, "pump", "oil_top_off", {"unit": 1, "threshold": 0.0, "min_interval": 2}), (2, "stage", "overhaul", {"unit": 7, "threshold": 0.5})]
-
-
-def _loop_env(n, T):
-    from nuclear_sim_amd.env import BatchedPlantEnv
-    env = BatchedPlantEnv(n, dt=DT, autoreset=True, max_episode_steps=3)
-    _poke(env)
-    env.snapshot()
-    env.set_start_bank(env)
-    env.set_controls(LOOP_AXES)
-    env.set_control_orders(LOOP_RULES)
-    env.set_features([(("obs", 0), {"scale": 1e-3}), (("pump.oil_level", 1), {"ref": 50.0, "scale": 0.02}), ("order", 0), ("order", 1)], stack=2, dtype=torch.float32)
-    env.set_rollout(T)
-    a, c, log_std = _weights(8, 8, 3, (16,), (7,))
-    env.set_policy(a, c, log_std, activation="tanh", seed=21)
-    return env
-
-
 def test_collect_is_t_steps_and_the_firing_history_is_what_the_rollouts_own_actions_make():
     n, T = 70, 8
     env, twin = _loop_env(n, T), _loop_env(n, T)
