@@ -2690,14 +2690,58 @@ static const char *adam_refusal(double lr, double b1, double b2, double eps) {
   return nullptr;
 }
 static const char *const g_core_untrained = ": the policy has a core (npb_set_policy_core), and training through time is not built into the row-wise entry points: rows carry no order; npb_policy_grad_seq, npb_policy_update_seq and npb_policy_shard_sums_seq take whole sequences";
-static int ppo_grad(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, void *stream) {
+static const char *const g_seq_no_core = ": the policy has no core (npb_set_policy_core): sequences are a recurrent policy's; rows go to npb_policy_grad";
+/* THE REQUEST: what a training call was asked to do.  Every entry point that forms a gradient -- npb_policy_grad, _grad_more, _update, _update_more,
+ * _shard_sums and their _seq and _segments companions -- is a wrapper that names itself, fills one of these and hands it to ppo_request.
+ * kind: what the entry point takes -- rows, whole sequences through the core (S) or segments (S and G).  It is the entry point's, not read off
+ * the pointers: a NULL S or G of the caller's is then refused by the kind's own check, in its words and at its place in the order, and never
+ * mistaken for another kind.  shard: the sums of one shard into out with the divisor count_total, the handle's gradient left alone (it stands
+ * beside out because a shard call's NULL out is a refusal, not a gradient call) */
+enum PpoKind { PPO_ROWS, PPO_SEQ, PPO_SEGMENTS };
+struct PpoRequest {
+  PpoKind kind;
+  const npb_ppo_desc_t *D; const npb_ppo_more_t *M; const npb_ppo_seq_t *S; const npb_ppo_segments_t *G;
+  bool shard; int64_t count_total; double *out;
+};
+/* THE ONE ORDER OF REFUSALS of a request ("The training calls: one request path"): no policy; a core under rows, or no core under
+ * sequences; the request's exported check (npb_ppo_check, npb_ppo_seq_check or npb_ppo_segments_check); npb_ppo_more_check; then a shard
+ * call's own -- a gate, count_total below the minibatch's or beyond 2^53, a NULL or misaligned out.  Then the rooms -- the chains' workspace (a
+ * chain is rows_per_chain rows, or plants) and, for sequences without a hidden of the caller's, h' [t][plants][H] -- and the launch.  In
+ * front of it an entry point's own refusals: a NULL handle, "the gate is an update's" of a gradient call, and an update's gate rule
+ * (ppo_gate).  Behind the check S is not NULL for sequences and segments, and G is not NULL for segments */
+static int ppo_request(NpbHandle *h, const char *who, const PpoRequest &Q, void *stream) {
+  const npb_ppo_desc_t *D = Q.D;
+  const bool rows = Q.kind == PPO_ROWS;
+  const npb_ppo_seq_t *S = rows ? nullptr : Q.S;
+  const npb_ppo_segments_t *G = Q.kind == PPO_SEGMENTS ? Q.G : nullptr;
   if (!h->pol.theta) return fail_who(h, who, g_no_policy);
-  if (h->core.primed) return fail_who(h, who, g_core_untrained);
-  if (const char *why = npb_ppo_check(D, h->pol.cells, h->pol.n_axes)) return fail(h, NPB_EINVAL, why);
-  if (const char *why = npb_ppo_more_check(M, D->count)) return fail(h, NPB_EINVAL, why);
+  if (rows && h->core.primed) return fail_who(h, who, g_core_untrained);
+  if (!rows && !h->core.primed) return fail_who(h, who, g_seq_no_core);
+  if (const char *why = rows                   ? npb_ppo_check(D, h->pol.cells, h->pol.n_axes)
+                        : Q.kind == PPO_SEQ    ? npb_ppo_seq_check(D, S, h->pol.cells, h->pol.n_axes)
+                                               : npb_ppo_segments_check(D, S, G, h->pol.cells, h->pol.n_axes))
+    return fail(h, NPB_EINVAL, why);
+  if (const char *why = npb_ppo_more_check(Q.M, D->count)) return fail(h, NPB_EINVAL, why);
+  if (Q.shard) {
+    if (Q.M && Q.M->kl_limit > 0.0) return fail_who(h, who, ": kl_limit > 0: the gate belongs to the combine (npb_policy_apply_shards)");
+    if (Q.count_total < (int64_t)D->count)
+      return fail_who(h, who, S ? ": count_total < desc->count: it is the cells of the whole update" : ": count_total < desc->count: it is the rows of the whole update");
+    if (Q.count_total > ((int64_t)1 << 53)) return fail_who(h, who, ": count_total is beyond 2^53");
+    if (!Q.out || ((uintptr_t)Q.out & 7u)) return fail_who(h, who, ": a NULL or misaligned out (8-byte aligned)");
+  }
   NPB_USE_DEVICE(h);
-  if (int rc = ppo_room(h, who, ((size_t)D->count + D->rows_per_chain - 1) / D->rows_per_chain)) return rc;
-  npb_launch_ppo_grad(&h->pol, &h->ppo, D, M, (hipStream_t)stream);
+  if (int rc = ppo_room(h, who, ((size_t)(S ? S->plants : D->count) + D->rows_per_chain - 1) / D->rows_per_chain)) return rc;
+  const size_t floats = S ? (size_t)D->count * (size_t)h->core.H : 0;
+  if (S && !S->hidden && floats > h->ppo.hseq_floats) {      /* (hipFree of the old one waits for a launch that still reads it) */
+    char *dev = nullptr;
+    if (int rc = attachment_alloc(h, who, "the sequences' hidden states", nullptr, 0, floats * sizeof(float), &dev)) return rc;
+    if (h->ppo.hseq) (void)hipFree(h->ppo.hseq);
+    h->ppo.hseq = (float *)dev; h->ppo.hseq_floats = floats;
+  }
+  const double n = Q.shard ? (double)Q.count_total : (double)D->count;
+  double *out = Q.shard ? Q.out : nullptr;
+  if (S) npb_launch_ppo_grad_seq(&h->pol, &h->core, &h->ppo, D, Q.M, S, G, n, out, (hipStream_t)stream);
+  else npb_launch_ppo_grad(&h->pol, &h->ppo, D, Q.M, n, out, (hipStream_t)stream);
   NPB_HIP(h, hipGetLastError());
   return NPB_OK;
 }
@@ -2714,35 +2758,41 @@ static int ppo_adam(NpbHandle *h, const char *who, double lr, double b1, double 
 }
 int npb_policy_grad(NpbHandle *h, const npb_ppo_desc_t *D, void *stream) {
   if (!h) return NPB_EINVAL;
-  return ppo_grad(h, "npb_policy_grad", D, nullptr, stream);
+  return ppo_request(h, "npb_policy_grad", {PPO_ROWS, D}, stream);
 }
 int npb_policy_grad_more(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, void *stream) {
   if (!h) return NPB_EINVAL;
   if (M && M->kl_limit > 0.0) return fail(h, NPB_EINVAL, "npb_policy_grad_more: kl_limit > 0: the gate is an update's (npb_policy_update_more)");
-  return ppo_grad(h, "npb_policy_grad_more", D, M, stream);
+  return ppo_request(h, "npb_policy_grad_more", {PPO_ROWS, D, M}, stream);
 }
 int npb_policy_adam(NpbHandle *h, double lr, double b1, double b2, double eps, void *stream) {
   if (!h) return NPB_EINVAL;
   if (h->ppo.armed) return fail_who(h, "npb_policy_adam", g_train_open);
   return ppo_adam(h, "npb_policy_adam", lr, b1, b2, eps, 0, stream);
 }
-static int ppo_update(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, double lr, double b1, double b2, double eps, void *stream) {
-  const int gated = M && M->kl_limit > 0.0;
-  if (h->core.primed) return fail_who(h, who, g_core_untrained);
+/* THE GATE RULE of an update (npb_policy_update and its companions, npb_policy_apply_shards), in front of everything else the update refuses:
+ * kl_limit > 0 only between npb_policy_train_begin and npb_policy_train_end, kl_limit == 0 never inside, and Adam's arguments refused in front
+ * of the gradient (a gated gradient counts itself applied: its Adam step must not be refused behind it) */
+static int ppo_gate(NpbHandle *h, const char *who, int gated, double lr, double b1, double b2, double eps) {
   if (gated && !h->ppo.armed) return fail_who(h, who, ": kl_limit > 0 outside npb_policy_train_begin / npb_policy_train_end (npb_policy_train_begin first)");
   if (!gated && h->ppo.armed) return fail_who(h, who, ": kl_limit == 0 between npb_policy_train_begin and npb_policy_train_end: every update of the pair is gated");
-  if (gated && h->pol.theta)      /* (a gated gradient counts itself applied: its Adam step must not be refused behind it) */
+  if (h->pol.theta)
     if (const char *why = adam_refusal(lr, b1, b2, eps)) return fail_who(h, who, why);
-  if (int rc = ppo_grad(h, who, D, M, stream)) return rc;
+  return NPB_OK;
+}
+static int ppo_update(NpbHandle *h, const char *who, const PpoRequest &Q, double lr, double b1, double b2, double eps, void *stream) {
+  const int gated = Q.M && Q.M->kl_limit > 0.0;
+  if (int rc = ppo_gate(h, who, gated, lr, b1, b2, eps)) return rc;
+  if (int rc = ppo_request(h, who, Q, stream)) return rc;
   return ppo_adam(h, who, lr, b1, b2, eps, gated, stream);
 }
 int npb_policy_update(NpbHandle *h, const npb_ppo_desc_t *D, double lr, double b1, double b2, double eps, void *stream) {
   if (!h) return NPB_EINVAL;
-  return ppo_update(h, "npb_policy_update", D, nullptr, lr, b1, b2, eps, stream);
+  return ppo_update(h, "npb_policy_update", {PPO_ROWS, D}, lr, b1, b2, eps, stream);
 }
 int npb_policy_update_more(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, double lr, double b1, double b2, double eps, void *stream) {
   if (!h) return NPB_EINVAL;
-  return ppo_update(h, "npb_policy_update_more", D, M, lr, b1, b2, eps, stream);
+  return ppo_update(h, "npb_policy_update_more", {PPO_ROWS, D, M}, lr, b1, b2, eps, stream);
 }
 int npb_policy_train_begin(NpbHandle *h, void *stream) {
   if (!h) return NPB_EINVAL;
@@ -2784,20 +2834,7 @@ const char *npb_ppo_shards_check(const npb_ppo_shards_t *S, int64_t count, int n
 }
 int npb_policy_shard_sums(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, int64_t count_total, double *out, void *stream) {
   if (!h) return NPB_EINVAL;
-  const char *who = "npb_policy_shard_sums";
-  if (!h->pol.theta) return fail_who(h, who, g_no_policy);
-  if (h->core.primed) return fail_who(h, who, g_core_untrained);
-  if (const char *why = npb_ppo_check(D, h->pol.cells, h->pol.n_axes)) return fail(h, NPB_EINVAL, why);
-  if (const char *why = npb_ppo_more_check(M, D->count)) return fail(h, NPB_EINVAL, why);
-  if (M && M->kl_limit > 0.0) return fail_who(h, who, ": kl_limit > 0: the gate belongs to the combine (npb_policy_apply_shards)");
-  if (count_total < (int64_t)D->count) return fail_who(h, who, ": count_total < desc->count: it is the rows of the whole update");
-  if (count_total > ((int64_t)1 << 53)) return fail_who(h, who, ": count_total is beyond 2^53");
-  if (!out || ((uintptr_t)out & 7u)) return fail_who(h, who, ": a NULL or misaligned out (8-byte aligned)");
-  NPB_USE_DEVICE(h);
-  if (int rc = ppo_room(h, who, ((size_t)D->count + D->rows_per_chain - 1) / D->rows_per_chain)) return rc;
-  npb_launch_ppo_shard_sums(&h->pol, &h->ppo, D, M, count_total, out, (hipStream_t)stream);
-  NPB_HIP(h, hipGetLastError());
-  return NPB_OK;
+  return ppo_request(h, "npb_policy_shard_sums", {PPO_ROWS, D, M, nullptr, nullptr, true, count_total, out}, stream);
 }
 static int ppo_combine(NpbHandle *h, const char *who, const npb_ppo_shards_t *S, void *stream) {
   if (!h->pol.theta) return fail_who(h, who, g_no_policy);
@@ -2817,10 +2854,7 @@ int npb_policy_apply_shards(NpbHandle *h, const npb_ppo_shards_t *S, double lr, 
   if (!h) return NPB_EINVAL;
   const char *who = "npb_policy_apply_shards";
   const int gated = S && S->kl_limit > 0.0;
-  if (gated && !h->ppo.armed) return fail_who(h, who, ": kl_limit > 0 outside npb_policy_train_begin / npb_policy_train_end (npb_policy_train_begin first)");
-  if (!gated && h->ppo.armed) return fail_who(h, who, ": kl_limit == 0 between npb_policy_train_begin and npb_policy_train_end: every update of the pair is gated");
-  if (h->pol.theta)      /* (a gated combine counts itself applied: its Adam step must not be refused behind it) */
-    if (const char *why = adam_refusal(lr, b1, b2, eps)) return fail_who(h, who, why);
+  if (int rc = ppo_gate(h, who, gated, lr, b1, b2, eps)) return rc;
   if (int rc = ppo_combine(h, who, S, stream)) return rc;
   return ppo_adam(h, who, lr, b1, b2, eps, gated, stream);
 }
@@ -2841,7 +2875,6 @@ const char *npb_ppo_seq_check(const npb_ppo_desc_t *D, const npb_ppo_seq_t *S, i
     return "npb_policy_grad_seq: a misaligned index, episode, first or hidden: 4-byte aligned";
   return nullptr;
 }
-static const char *const g_seq_no_core = ": the policy has no core (npb_set_policy_core): sequences are a recurrent policy's; rows go to npb_policy_grad";
 /* the same for truncated segments (include/npb.h): what npb_ppo_seq_check refuses, and the segments' own */
 const char *npb_ppo_segments_check(const npb_ppo_desc_t *D, const npb_ppo_seq_t *S, const npb_ppo_segments_t *G, int features_cells, int n_axes) {
   if (const char *why = npb_ppo_seq_check(D, S, features_cells, n_axes)) return why;
@@ -2852,81 +2885,35 @@ const char *npb_ppo_segments_check(const npb_ppo_desc_t *D, const npb_ppo_seq_t 
   if ((int64_t)G->chunks * G->every * S->n_plants > INT32_MAX) return "npb_policy_grad_segments: chunks * every * n_plants is beyond 2^31 - 1";
   return nullptr;
 }
-/* the checks of a sequence call and its workspaces: the chains' (a chain is rows_per_chain plants) and h' [t][plants][H] */
-/* (segments: G is not NULL behind the entry points below that take one; `segments` says which check names the refusal) */
-static int ppo_seq_room(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, bool segments = false,
-                        const npb_ppo_segments_t *G = nullptr) {
-  if (!h->pol.theta) return fail_who(h, who, g_no_policy);
-  if (!h->core.primed) return fail_who(h, who, g_seq_no_core);
-  if (const char *why = segments ? npb_ppo_segments_check(D, S, G, h->pol.cells, h->pol.n_axes) : npb_ppo_seq_check(D, S, h->pol.cells, h->pol.n_axes))
-    return fail(h, NPB_EINVAL, why);
-  if (const char *why = npb_ppo_more_check(M, D->count)) return fail(h, NPB_EINVAL, why);
-  NPB_USE_DEVICE(h);
-  if (int rc = ppo_room(h, who, ((size_t)S->plants + D->rows_per_chain - 1) / D->rows_per_chain)) return rc;
-  const size_t floats = (size_t)D->count * (size_t)h->core.H;
-  if (!S->hidden && floats > h->ppo.hseq_floats) {      /* (hipFree of the old one waits for a launch that still reads it) */
-    char *dev = nullptr;
-    if (int rc = attachment_alloc(h, who, "the sequences' hidden states", nullptr, 0, floats * sizeof(float), &dev)) return rc;
-    if (h->ppo.hseq) (void)hipFree(h->ppo.hseq);
-    h->ppo.hseq = (float *)dev; h->ppo.hseq_floats = floats;
-  }
-  return NPB_OK;
-}
-static int ppo_grad_seq(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, void *stream, bool segments = false,
-                        const npb_ppo_segments_t *G = nullptr) {
-  if (int rc = ppo_seq_room(h, who, D, M, S, segments, G)) return rc;
-  npb_launch_ppo_grad_seq(&h->pol, &h->core, &h->ppo, D, M, S, G, (hipStream_t)stream);
-  NPB_HIP(h, hipGetLastError());
-  return NPB_OK;
-}
 int npb_policy_grad_seq(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, void *stream) {
   if (!h) return NPB_EINVAL;
   if (M && M->kl_limit > 0.0) return fail(h, NPB_EINVAL, "npb_policy_grad_seq: kl_limit > 0: the gate is an update's (npb_policy_update_seq)");
-  return ppo_grad_seq(h, "npb_policy_grad_seq", D, M, S, stream);
+  return ppo_request(h, "npb_policy_grad_seq", {PPO_SEQ, D, M, S}, stream);
 }
 int npb_policy_grad_segments(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, const npb_ppo_segments_t *G, void *stream) {
   if (!h) return NPB_EINVAL;
   if (M && M->kl_limit > 0.0) return fail(h, NPB_EINVAL, "npb_policy_grad_segments: kl_limit > 0: the gate is an update's (npb_policy_update_segments)");
-  return ppo_grad_seq(h, "npb_policy_grad_segments", D, M, S, stream, true, G);
-}
-static int ppo_update_seq(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, bool segments,
-                          const npb_ppo_segments_t *G, double lr, double b1, double b2, double eps, void *stream) {
-  if (!h) return NPB_EINVAL;
-  const int gated = M && M->kl_limit > 0.0;
-  if (gated && !h->ppo.armed) return fail_who(h, who, ": kl_limit > 0 outside npb_policy_train_begin / npb_policy_train_end (npb_policy_train_begin first)");
-  if (!gated && h->ppo.armed) return fail_who(h, who, ": kl_limit == 0 between npb_policy_train_begin and npb_policy_train_end: every update of the pair is gated");
-  if (gated && h->pol.theta)      /* (a gated gradient counts itself applied: its Adam step must not be refused behind it) */
-    if (const char *why = adam_refusal(lr, b1, b2, eps)) return fail_who(h, who, why);
-  if (int rc = ppo_grad_seq(h, who, D, M, S, stream, segments, G)) return rc;
-  return ppo_adam(h, who, lr, b1, b2, eps, gated, stream);
+  return ppo_request(h, "npb_policy_grad_segments", {PPO_SEGMENTS, D, M, S, G}, stream);
 }
 int npb_policy_update_seq(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, double lr, double b1, double b2, double eps,
                           void *stream) {
-  return ppo_update_seq(h, "npb_policy_update_seq", D, M, S, false, nullptr, lr, b1, b2, eps, stream);
+  if (!h) return NPB_EINVAL;
+  return ppo_update(h, "npb_policy_update_seq", {PPO_SEQ, D, M, S}, lr, b1, b2, eps, stream);
 }
 int npb_policy_update_segments(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, const npb_ppo_segments_t *G, double lr,
                                double b1, double b2, double eps, void *stream) {
-  return ppo_update_seq(h, "npb_policy_update_segments", D, M, S, true, G, lr, b1, b2, eps, stream);
-}
-static int ppo_shard_sums_seq(NpbHandle *h, const char *who, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, bool segments,
-                              const npb_ppo_segments_t *G, int64_t count_total, double *out, void *stream) {
   if (!h) return NPB_EINVAL;
-  if (M && M->kl_limit > 0.0) return fail_who(h, who, ": kl_limit > 0: the gate belongs to the combine (npb_policy_apply_shards)");
-  if (D && count_total < (int64_t)D->count) return fail_who(h, who, ": count_total < desc->count: it is the cells of the whole update");
-  if (count_total > ((int64_t)1 << 53)) return fail_who(h, who, ": count_total is beyond 2^53");
-  if (!out || ((uintptr_t)out & 7u)) return fail_who(h, who, ": a NULL or misaligned out (8-byte aligned)");
-  if (int rc = ppo_seq_room(h, who, D, M, S, segments, G)) return rc;
-  npb_launch_ppo_shard_sums_seq(&h->pol, &h->core, &h->ppo, D, M, S, G, count_total, out, (hipStream_t)stream);
-  NPB_HIP(h, hipGetLastError());
-  return NPB_OK;
+  return ppo_update(h, "npb_policy_update_segments", {PPO_SEGMENTS, D, M, S, G}, lr, b1, b2, eps, stream);
 }
 int npb_policy_shard_sums_seq(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, int64_t count_total, double *out,
                               void *stream) {
-  return ppo_shard_sums_seq(h, "npb_policy_shard_sums_seq", D, M, S, false, nullptr, count_total, out, stream);
+  if (!h) return NPB_EINVAL;
+  return ppo_request(h, "npb_policy_shard_sums_seq", {PPO_SEQ, D, M, S, nullptr, true, count_total, out}, stream);
 }
 int npb_policy_shard_sums_segments(NpbHandle *h, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S, const npb_ppo_segments_t *G,
                                    int64_t count_total, double *out, void *stream) {
-  return ppo_shard_sums_seq(h, "npb_policy_shard_sums_segments", D, M, S, true, G, count_total, out, stream);
+  if (!h) return NPB_EINVAL;
+  return ppo_request(h, "npb_policy_shard_sums_segments", {PPO_SEGMENTS, D, M, S, G, true, count_total, out}, stream);
 }
 /* the refresh of the stored states under the current theta (npb_ppo_seq.hip's forward sweep over the rollout's own tensors) */
 int npb_policy_segment_starts(NpbHandle *h, int every, void *stream) {

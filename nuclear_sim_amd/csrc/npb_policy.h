@@ -159,15 +159,20 @@ __device__ __forceinline__ void npd_policy_net(const npd_policy_net_t &N, const 
     in = out;
   }
 }
-/* ---- the cell's gates, S and T of the statement (recurrent.py: sigma, tau), what the recurrent step (npb_policy_core.hip) and the sequence
- * gradient kernel (npb_ppo_seq.hip) share */
+/* ---- THE CELL, stated once under the statement's names (recurrent.py: sigma, tau, cell, sigma_slope, tau_slope): what the recurrent step
+ * (npb_policy_core.hip) and the sequence kernels (npb_ppo_seq.hip: the forward sweep, the backward sweep's recompute, the refresh) share.
+ * Every float operation below is rounded on its own, in the statement's order */
 #define NPD_CORE_SOFT 0
 #define NPD_CORE_HARD 1
 
+/* the hard S in front of its clamp; the clamp and "does it clamp at a" are the two bodies below and nowhere else */
+__device__ __forceinline__ float npd_core_hard_line(float a) {
+  const float q = 0.25f * a;
+  return q + 0.5f;
+}
 __device__ __forceinline__ float npd_core_sigma(float a, int gates) {
   if (gates == NPD_CORE_HARD) {
-    const float q = 0.25f * a;
-    const float y = q + 0.5f;
+    const float y = npd_core_hard_line(a);
     return y < 0.0f ? 0.0f : (y > 1.0f ? 1.0f : y);
   }
   const float half = 0.5f * a;
@@ -175,9 +180,79 @@ __device__ __forceinline__ float npd_core_sigma(float a, int gates) {
   const float s = 0.5f * t;
   return s + 0.5f;
 }
+__device__ __forceinline__ bool npd_core_sigma_clamps(float a, int gates) {
+  const float y = npd_core_hard_line(a);
+  return gates == NPD_CORE_HARD && (y < 0.0f || y > 1.0f);
+}
 __device__ __forceinline__ float npd_core_tau(float a, int gates) {
   if (gates == NPD_CORE_HARD) return a < -1.0f ? -1.0f : (a > 1.0f ? 1.0f : a);
   return tanhf(a);
+}
+/* d * S', given npd_core_sigma_clamps(a) and s = S(a) */
+__device__ __forceinline__ float npd_core_sigma_slope(float d, bool clamps, float s, int gates) {
+  if (gates == NPD_CORE_HARD) {
+    const float q = d * 0.25f;
+    return clamps ? 0.0f : q;
+  }
+  const float oms = 1.0f - s;
+  const float slope = s * oms;
+  return d * slope;
+}
+/* d * T', given a and n = T(a) */
+__device__ __forceinline__ float npd_core_tau_slope(float d, float a, float n, int gates) {
+  if (gates == NPD_CORE_HARD) return a < -1.0f || a > 1.0f ? 0.0f : d;
+  const float sq = n * n;
+  const float slope = 1.0f - sq;
+  return d * slope;
+}
+/* the forward of the cell over a tile, gate by gate, so that only H-wide buffers live in LDS: gi = W_i* xs and gh = W_h* h (two layers, one
+ * barrier: they read xs and h and write apart; gh's chunks of 32 outputs start two waves on, so a cell of up to 64 cells keeps all four waves
+ * busy), then 256 lanes over the H x 32 cells: r = S(gi + gh), z likewise, and for the candidate n = T(gi + r * gh), h' = n + z * (h - n) over h
+ * in place (a cell is read and written by one lane).  A poisoned plant (bad) and the k extension, H up to the next multiple of 4, get +0.0.
+ * Every lane of the workgroup calls it (it holds barriers, the last one behind h'); xs and h stand before the call */
+__device__ __forceinline__ void npd_core_cell(const npb_policy_t &P, const npd_policy_core_t &C, const float *xs, float *h, float *gi, float *gh, float *r, float *z,
+                                              const int *bad, int tid) {
+  const int wave = tid >> 6, lane = tid & 63, H = C.H, H_pad = (H + 3) & ~3;
+  for (int gate = 0; gate < 3; gate++) {
+    npd_policy_layer(C.gate[gate], P.theta, P.padded, xs, gi, -1, wave, lane);
+    npd_policy_layer(C.gate[3 + gate], P.theta, P.padded, h, gh, -1, (wave + 2) & (NPD_POLICY_WAVES - 1), lane);
+    __syncthreads();
+    for (int i = tid; i < H_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES) {
+      const int j = i / NPD_POLICY_TILE, plant = i & (NPD_POLICY_TILE - 1), o = j * NPD_POLICY_STRIDE + plant;
+      if (gate < 2) {
+        const float a = gi[o] + gh[o];
+        (gate ? z : r)[o] = npd_core_sigma(a, C.gates);
+      } else {
+        const float gated = r[o] * gh[o];
+        const float a = gi[o] + gated;
+        const float n = npd_core_tau(a, C.gates);
+        const float hv = h[o];
+        const float away = hv - n;
+        const float kept = z[o] * away;
+        const float next = n + kept;
+        h[o] = j < H && !bad[plant] ? next : 0.0f;
+      }
+    }
+    __syncthreads();
+  }
+}
+/* a tile's run of H-wide rows and a [k][plant] buffer, the reading and the writing twin.  npd_seq_fill: the buffer filled whole, k up to H_pad:
+ * plant `row` reads H contiguous floats at source(row), or +0.0 where it has none (beyond the tile, a plant without a source, a restarted
+ * plant).  npd_core_store: the tile's in_tile rows of H floats, ONE contiguous run, out of the buffer transposed (consecutive k are 33 floats
+ * apart: no bank conflict).  Consecutive lanes on consecutive elements of the run in both; no barrier in either */
+template <class Source>
+__device__ __forceinline__ void npd_seq_fill(float *dst, int H, int H_pad, int tid, Source source) {
+  for (int e = tid; e < H_pad * NPD_POLICY_TILE; e += NPD_POLICY_LANES) {
+    const int row = e / H_pad, k = e - row * H_pad;
+    const float *from = source(row);
+    dst[k * NPD_POLICY_STRIDE + row] = from && k < H ? from[k] : 0.0f;
+  }
+}
+__device__ __forceinline__ void npd_core_store(float *run, const float *src, int in_tile, int H, int tid) {
+  for (int e = tid; e < in_tile * H; e += NPD_POLICY_LANES) {
+    const int row = e / H, k = e - row * H;
+    run[e] = src[k * NPD_POLICY_STRIDE + row];
+  }
 }
 /* ---- the noise: Philox4x32-10 and the pair of normals of one call (policy.py: philox4x32, noise_from_words) */
 __device__ __forceinline__ void npd_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t w[4]) {

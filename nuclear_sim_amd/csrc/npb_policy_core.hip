@@ -15,20 +15,17 @@
  *      extensions of xs and hs are +0.0.  The load of x, the zeroing and the ragged tile's row count are the MLP
  *      kernel's own (npb_policy.h: npd_policy_tile_load, npd_policy_tile_zero, npd_policy_in_tile); the load of h, with its restart
  *      mask and its store into `first`, is this file's.
- *   2. gate by gate, so that only H-wide buffers live in LDS: gi = W_i* x into ha and gh = W_h* h into hb (two layers, one barrier: they
- *      read xs and hs and write apart; gh's chunks of 32 outputs start two waves on, so a cell of up to 64 cells keeps all four waves
- *      busy where a layer alone would leave two without a chunk), then 256 lanes over the H x 32 cells: r = S(gi + gh) into rs; z
- *      likewise into zg; for the candidate n = T(gi + r * gh) and h' = n + z * (h - n) over hs in place (a cell is read and written by
- *      one lane).  Cells from H up to the next multiple of 4 are +0.0: the next layer's k extension.  A poisoned plant's h' is +0.0.
- *   3. h' goes back to the per-plant buffer as it came: the tile's run, consecutive lanes on consecutive elements, read out of hs
- *      transposed (consecutive k are 33 floats apart: no bank conflict).
+ *   2. the cell, gate by gate, so that only H-wide buffers live in LDS: npb_policy.h's npd_core_cell, the one statement of it that the
+ *      training kernels (npb_ppo_seq.hip) run too -- gi into ha, gh into hb, r into rs, z into zg, h' over hs in place.  Cells from H up to
+ *      the next multiple of 4 are +0.0: the next layer's k extension.  A poisoned plant's h' is +0.0.
+ *   3. h' goes back to the per-plant buffer as it came: the tile's run, read out of hs transposed (npb_policy.h's npd_core_store).
  *   4. the actor and the critic over hs with ha and hb as their ping-pong buffers, and the epilogue: npb_policy.h's, the MLP kernel's own.
  * npb_policy_values_hidden is the same kernel with act == NULL: the critic over GRU(x, h), nothing written back to h, primed or seen.
  * LDS, from the declarations below: (KC_MAX + 5 H_MAX) x 33 x 4 B for xs, hs, ha, hb, rs, zg, and the epilogue's 1056 + 528 + 2048 + 128 B
  * with 256 B of poison and restart words: the small build (NPD_POLICY_SMALL_CELLS, NPD_POLICY_SMALL_WIDTH; npd_policy_small with the core's
  * width, npb_policy.h) 54 576 B, the large one (NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX) 122 160 B, as the compiler reports them --
  * static, beyond 64 KiB, inside gfx950's 160 KiB per CU (one workgroup a CU in the large build, three in the small one).  A 3H-wide gi and
- * gh together would not fit.  64 VGPRs and 16 AGPRs, no scratch, no spills, no atomics.  The gate layers' copy for the matrix cores is laid out by the policy's
+ * gh together would not fit.  57 VGPRs and 16 AGPRs, no scratch, no spills, no atomics.  The gate layers' copy for the matrix cores is laid out by the policy's
  * one repack launch (npb_launch_policy_repack, npb_policy.hip), together with the nets'. */
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -72,36 +69,11 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_policy_core_kernel(npb_p
     if (G.start_out) G.start_out[base * (size_t)H + e] = v;
   }
   __syncthreads();
-  /* 2. the cell, gate by gate */
+  /* 2. the cell, gate by gate (npb_policy.h) */
   const int wave = tid >> 6, lane = tid & 63;
-  for (int gate = 0; gate < 3; gate++) {
-    npd_policy_layer(C.gate[gate], P.theta, P.padded, xs, ha, -1, wave, lane);
-    npd_policy_layer(C.gate[3 + gate], P.theta, P.padded, hs, hb, -1, (wave + 2) & (NPD_POLICY_WAVES - 1), lane);
-    __syncthreads();
-    for (int i = tid; i < H_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES) {
-      const int j = i / NPD_POLICY_TILE, plant = i & (NPD_POLICY_TILE - 1), o = j * NPD_POLICY_STRIDE + plant;
-      if (gate < 2) {
-        const float a = ha[o] + hb[o];
-        (gate ? zg : rs)[o] = npd_core_sigma(a, C.gates);
-      } else {
-        const float gated = rs[o] * hb[o];
-        const float a = ha[o] + gated;
-        const float n = npd_core_tau(a, C.gates);
-        const float h = hs[o];
-        const float away = h - n;
-        const float kept = zg[o] * away;
-        const float next = n + kept;
-        hs[o] = j < H && !bad[plant] ? next : 0.0f;
-      }
-    }
-    __syncthreads();
-  }
+  npd_core_cell(P, C, xs, hs, ha, hb, rs, zg, bad, tid);
   /* 3. h' back to the per-plant buffer */
-  if (G.h_out)
-    for (int e = tid; e < h_total; e += NPD_POLICY_LANES) {
-      const int row = e / H, k = e - row * H;
-      G.h_out[base * (size_t)H + e] = hs[k * NPD_POLICY_STRIDE + row];
-    }
+  if (G.h_out) npd_core_store(G.h_out + base * (size_t)H, hs, in_tile, H, tid);
   /* 4. the nets over h', the draw and the outputs */
   if (R.act) npd_policy_net(P.actor, P.theta, P.padded, hs, ha, hb, mean, P.D.activation, wave, lane);
   npd_policy_net(P.critic, P.theta, P.padded, hs, ha, hb, val, P.D.activation, wave, lane);

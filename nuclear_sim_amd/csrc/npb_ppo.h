@@ -25,26 +25,22 @@ typedef struct {
 } npb_ppo_t;
 /* the gradient of one minibatch: the gradient kernel (a workgroup a chain), the ascending sum over the chains, the finish.  O holds
  * room for ceil(count / rows_per_chain) chains.  M (NULL = every option off): value-loss clipping, and with kl_limit > 0 the finish ORs
- * the gate on O->gate */
-void npb_launch_ppo_grad(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, hipStream_t stream);
+ * the gate on O->gate.  n: the seeds' divisor, (double)D->count or a shard's (double)count_total.  out == NULL: the reduce into the handle's
+ * grad, stats and more.  out != NULL (npb_policy_shard_sums): one shard's sums instead, a lane an entry of out [P->log_std + NPD_PPO_ROWVALS]
+ * doubles: the ascending sum over the chains, not narrowed; O's grad, stats, more and gate are not touched */
+void npb_launch_ppo_grad(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, double n, double *out, hipStream_t stream);
 /* one Adam step on P->theta from O->grad, O->step the step it is (already advanced): step_size = lr / (1 - b1^step) and root = sqrt(1 -
  * b2^step) are formed on the host, in double.  gated: the launch reads O->gate's stopped word and stores nothing when it is set */
 void npb_launch_ppo_adam(const npb_policy_t *P, const npb_ppo_t *O, double lr, double b1, double b2, double eps, int gated, hipStream_t stream);
-/* one shard's sums (npb_policy_shard_sums): the gradient kernel with the seeds' divisor (double)count_total, then a lane an entry of out
- * [P->log_std + NPD_PPO_ROWVALS] doubles: the ascending sum over the chains, not narrowed.  O's grad, stats, more and gate are not touched */
-void npb_launch_ppo_shard_sums(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, int64_t count_total, double *out,
-                               hipStream_t stream);
 /* the combine (npb_policy_apply_shards, npb_policy_combine_shards): a lane a parameter adds S->sums' rows in ascending order onto 0.0,
  * narrows once and takes the tree's first level; then the finish over the 18 totals with n = count_total, S->kl_limit > 0 ORing the gate */
 void npb_launch_ppo_combine(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_shards_t *S, hipStream_t stream);
-/* the same two over whole sequences through the recurrent core (npb_ppo_seq.hip; npb_policy_grad_seq, npb_policy_shard_sums_seq): D's tensors
+/* the gradient over whole sequences through the recurrent core (npb_ppo_seq.hip; npb_policy_grad_seq, npb_policy_shard_sums_seq; n and out as above): D's tensors
  * time-major [S->t][S->plants][...], D->rows_per_chain the PLANTS of a chain; O holds room for ceil(plants / rows_per_chain) chains and
  * O->hseq for t * plants * H floats.  G (NULL: whole sequences): the sequences are segments of S->t slots, S->index their ids c * n_plants + p,
  * S->first the stored states [G->chunks * n_plants][H] (npb_policy_grad_segments) */
 void npb_launch_ppo_grad_seq(const npb_policy_t *P, const npd_policy_core_t *C, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M,
-                             const npb_ppo_seq_t *S, const npb_ppo_segments_t *G, hipStream_t stream);
-void npb_launch_ppo_shard_sums_seq(const npb_policy_t *P, const npd_policy_core_t *C, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M,
-                                   const npb_ppo_seq_t *S, const npb_ppo_segments_t *G, int64_t count_total, double *out, hipStream_t stream);
+                             const npb_ppo_seq_t *S, const npb_ppo_segments_t *G, double n, double *out, hipStream_t stream);
 /* the refresh of the stored states (npb_policy_segment_starts): the forward sweep over the rollout's t recorded slots from C->first under the
  * current theta; rows 1 .. t / every - 1 of starts [t / every][n_plants][H] receive the state read in front of slot c * every */
 void npb_launch_segment_starts(const npb_policy_t *P, const npd_policy_core_t *C, const void *obs, int obs_f64, int t, int n_plants, int every,
@@ -264,19 +260,18 @@ __device__ __forceinline__ void npd_ppo_net(const npd_policy_net_t &N, const npb
     float *t = d0; d0 = d1; d1 = t;
   }
 }
-/* the run of a plain call: the chains' workspace of O, n = (double)count; n_chains: ceil(count / rows_per_chain), or a sequence call's chains */
-static inline npd_ppo_run_t npd_ppo_run(const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, int n_chains) {
+/* the run of a gradient call: the chains' workspace of O, the seeds' divisor n; n_chains: ceil(count / rows_per_chain), or a sequence call's chains */
+static inline npd_ppo_run_t npd_ppo_run(const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, int n_chains, double n) {
   npd_ppo_run_t R = {};
   R.D = *D;
   if (M) R.M = *M;
   R.n_chains = n_chains;
   R.partials = O->partials; R.floats = O->floats; R.chain_stats = O->chain_stats;
-  R.n = (double)D->count;
+  R.n = n;
   return R;
 }
-/* behind a gradient kernel that filled R's chains (npb_ppo.hip): the ascending sums over the chains, the norm, the scale, the statistics, the
- * gate; and a shard's vector of them */
-void npb_launch_ppo_reduce(const npb_policy_t *P, const npb_ppo_t *O, const npd_ppo_run_t *R, hipStream_t stream);
-void npb_launch_ppo_shard_reduce(const npb_policy_t *P, const npd_ppo_run_t *R, double *out, hipStream_t stream);
+/* behind a gradient kernel that filled R's chains (npb_ppo.hip).  out == NULL: the ascending sums over the chains, the norm, the scale, the
+ * statistics, the gate, into O; out != NULL: a shard's vector of the sums, and O is left alone */
+void npb_launch_ppo_reduce(const npb_policy_t *P, const npb_ppo_t *O, const npd_ppo_run_t *R, double *out, hipStream_t stream);
 #endif
 #endif

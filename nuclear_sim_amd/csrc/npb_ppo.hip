@@ -228,32 +228,23 @@ __global__ __launch_bounds__(256) void npb_ppo_adam_gated_kernel(npb_policy_t P,
   npd_ppo_adam(P, O, step_size, root, b1, c1, b2, c2, eps);
 }
 
-static int npd_ppo_chains(const npb_ppo_desc_t *D) { return (int)(((int64_t)D->count + D->rows_per_chain - 1) / D->rows_per_chain); }
-static void npd_ppo_launch_grad(const npb_policy_t *P, const npb_ppo_desc_t *D, const npd_ppo_run_t &R, hipStream_t stream) {
+extern "C" void npb_launch_ppo_grad(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, double n, double *out,
+                                    hipStream_t stream) {
+  const npd_ppo_run_t R = npd_ppo_run(O, D, M, (int)(((int64_t)D->count + D->rows_per_chain - 1) / D->rows_per_chain), n);
   const int cap = D->max_blocks > 0 ? D->max_blocks : 2048;
   const dim3 grid((unsigned)(R.n_chains < cap ? R.n_chains : cap)), block(NPD_POLICY_LANES);
   if (npd_policy_small(P, 0)) hipLaunchKernelGGL((npb_ppo_grad_kernel<NPD_POLICY_SMALL_CELLS, NPD_POLICY_SMALL_WIDTH>), grid, block, 0, stream, *P, R);
   else hipLaunchKernelGGL((npb_ppo_grad_kernel<NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX>), grid, block, 0, stream, *P, R);
+  npb_launch_ppo_reduce(P, O, &R, out, stream);
 }
-extern "C" void npb_launch_ppo_grad(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, hipStream_t stream) {
-  const npd_ppo_run_t R = npd_ppo_run(O, D, M, npd_ppo_chains(D));
-  npd_ppo_launch_grad(P, D, R, stream);
-  npb_launch_ppo_reduce(P, O, &R, stream);
-}
-void npb_launch_ppo_reduce(const npb_policy_t *P, const npb_ppo_t *O, const npd_ppo_run_t *R, hipStream_t stream) {
+void npb_launch_ppo_reduce(const npb_policy_t *P, const npb_ppo_t *O, const npd_ppo_run_t *R, double *out, hipStream_t stream) {
+  if (out) {
+    const size_t L = (size_t)P->log_std + NPD_PPO_ROWVALS;
+    hipLaunchKernelGGL(npb_ppo_shard_reduce_kernel, dim3((unsigned)((L + NPD_TREE - 1) / NPD_TREE)), dim3(NPD_TREE), 0, stream, *P, *R, out);
+    return;
+  }
   hipLaunchKernelGGL(npb_ppo_reduce_kernel, dim3((P->theta_count + NPD_TREE - 1) / NPD_TREE), dim3(NPD_TREE), 0, stream, *P, *R, *O);
   hipLaunchKernelGGL(npb_ppo_finish_kernel<false>, dim3(1), dim3(NPD_TREE), 0, stream, *P, *R, *O);
-}
-void npb_launch_ppo_shard_reduce(const npb_policy_t *P, const npd_ppo_run_t *R, double *out, hipStream_t stream) {
-  const size_t L = (size_t)P->log_std + NPD_PPO_ROWVALS;
-  hipLaunchKernelGGL(npb_ppo_shard_reduce_kernel, dim3((unsigned)((L + NPD_TREE - 1) / NPD_TREE)), dim3(NPD_TREE), 0, stream, *P, *R, out);
-}
-extern "C" void npb_launch_ppo_shard_sums(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, int64_t count_total,
-                                          double *out, hipStream_t stream) {
-  npd_ppo_run_t R = npd_ppo_run(O, D, M, npd_ppo_chains(D));
-  R.n = (double)count_total;
-  npd_ppo_launch_grad(P, D, R, stream);
-  npb_launch_ppo_shard_reduce(P, &R, out, stream);
 }
 extern "C" void npb_launch_ppo_combine(const npb_policy_t *P, const npb_ppo_t *O, const npb_ppo_shards_t *S, hipStream_t stream) {
   npd_ppo_run_t R = {};

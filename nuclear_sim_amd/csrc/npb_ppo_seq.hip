@@ -10,10 +10,12 @@
  * [k][plant], row stride 33.  The minibatch is time-major, [t][plants][...]; a plant's restart words and its state in front of slot 0 are
  * read from the rollout's own tensors through the minibatch's index: episode and ended [T][n_plants], first [n_plants][H].  An index outside
  * 0 .. n_plants - 1 makes every cell of that plant a skipped, poisoned cell, and nothing is read through it.  Per tile, two sweeps:
- *   FORWARD, s ascending: the step kernel's cell, gate by gate (npb_policy_core.hip's step 2: npd_policy_layer, npd_core_sigma, npd_core_tau),
+ *   FORWARD, s ascending: the step kernel's cell, the ONE statement of it both call (npb_policy.h's npd_core_cell: gate by gate),
  *   h carried in LDS, +0.0 where the plant restarted in front of s (an episode change, or the cut bit of ended[s - 1]) and behind a poisoned
  *   cell; h'_s goes to the handle's workspace [t][plants][H] (or the caller's hidden).  Only h' is stored: the backward sweep recomputes the
- *   gates, which gives the same bits and keeps the workspace at t * plants * H floats.
+ *   gates, which gives the same bits and keeps the workspace at t * plants * H floats.  It keeps a buffer assignment of its own (it needs gi_n
+ *   and gh_n apart, and the flags), but S, T, the clamp test and the slopes d * S' and d * T' are npb_policy.h's (npd_core_sigma, npd_core_tau,
+ *   npd_core_sigma_clamps, npd_core_sigma_slope, npd_core_tau_slope: recurrent.py's names), so a gate is changed in one place.
  *   BACKWARD, s descending, the carry dh in LDS (+0.0 behind the last slot):
  *     the nets, one after the other (npb_ppo.h's npd_ppo_net, the row-wise kernel's own): h'_s from the workspace, forward with the
  *     activations kept, the per-row epilogue (npd_ppo_seeds_actor, npd_ppo_seeds_critic), dW / db onto the chain's partials, back; the first
@@ -31,11 +33,11 @@
  * widths), the head's 1056 B, the per-row doubles' 4608 B, four words a plant: the small build (npd_policy_small with the core's width)
  * 8448 + 7 x 8448 + 6176 = 73 760 B, the large one 33 792 + 7 x 16 896 + 6176 = 158 240 B of gfx950's 160 KiB (one workgroup a CU), and 128 B
  * more for word0 (below): 73 888 / 158 368 B as the compiler reports them.  Its other figures (-Rpass-analysis=kernel-resource-usage added to the Makefile's
- * own line for this file: -O3 -ffp-contract=off -fno-fast-math; the scalar spills move with the flags: plain -O3 gives 464 / 466 of
- * them, every other figure the same), small / large build: 255 / 256 VGPRs, 40 / 40 AGPRs, no scratch, no VGPR spills, and 481 / 476 of the descriptors' scalars spilled from SGPRs into
+ * own line for this file: -O3 -ffp-contract=off -fno-fast-math; the scalar spills move with the flags and with every
+ * textual move of the code, every other figure stays), small / large build: 256 / 256 VGPRs, 40 / 40 AGPRs, no scratch, no VGPR spills, and 466 / 464 of the descriptors' scalars spilled from SGPRs into
  * VGPR lanes (the row-wise kernel: 133 / 129) -- no memory traffic, but a workgroup is alone on its CU in the small build too.  No atomics.
  * No shape is refused: both builds fit.  Measured on an MI355X
- * (tools/recurrent_train_cost.py): one update of t = 128 through a cell of 64 and (64, 64) nets, 21.0 ms at 4 096 plants, 30.1 ms at 8 192.  The
+ * (tools/recurrent_train_cost.py): one update of t = 128 through a cell of 64 and (64, 64) nets, 19.5 ms at 2 048 plants, 20.4 ms at 4 096, 29.8 ms at 8 192.  The
  * nets' phase and the cell's phase alias the seven buffers: b0 the carry; b1 h' then h; b2 .. b4 the nets' hidden activations then r, z, n;
  * b5, b6 the nets' two delta buffers then gh_n and the flags.
  *
@@ -48,7 +50,7 @@
  * THE REFRESH (npb_policy_segment_starts; npb_segment_starts_kernel) is the forward sweep alone -- npd_seq_forward, the one piece of code
  * both kernels call -- over the rollout's own tensors, one workgroup per tile of 32 plants, serial in t; the state in front of slot c * every
  * goes into row c of the stored states for c >= 1.  Five H-wide buffers and xs: 50 944 / 118 528 B of LDS, 105 / 78 VGPRs, 16 AGPRs, no
- * scratch, no VGPR spills (34 / 36 scalars into VGPR lanes), no atomics. */
+ * scratch, no VGPR spills (38 / 38 scalars into VGPR lanes), no atomics. */
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "npb_ppo.h"
@@ -70,26 +72,15 @@ typedef struct {
   float *starts;           /* [t / every][n_plants][H]: rows 1 .. are written */
 } npd_seq_starts_t;
 
-/* a tile's H-wide buffer filled whole, [k][plant] with k up to H_pad: plant `row` reads H contiguous floats at run + offset(row), or +0.0
- * where it has none (beyond the tile, a plant without a source, a restarted plant).  Consecutive lanes on consecutive k of one plant */
-template <class Source>
-__device__ __forceinline__ void npd_seq_fill(float *dst, int H, int H_pad, int tid, Source source) {
-  for (int e = tid; e < H_pad * NPD_POLICY_TILE; e += NPD_POLICY_LANES) {
-    const int row = e / H_pad, k = e - row * H_pad;
-    const float *from = source(row);
-    dst[k * NPD_POLICY_STRIDE + row] = from && k < H ? from[k] : 0.0f;
-  }
-}
-
 /* THE FORWARD SWEEP of one tile, s ascending, what the gradient kernel and the refresh of the stored states share: h in b1, the step kernel's
- * cell gate by gate (gi into b2, gh into b3, r into b4, z into b5).  obs: slot s of the tile is in_tile rows of KC cells at cell (s * rows +
+ * cell (npb_policy.h's npd_core_cell: gi into b2, gh into b3, r into b4, z into b5).  obs: slot s of the tile is in_tile rows of KC cells at cell (s * rows +
  * base); words(s), lanes 0 .. 31: fresh and bad of the slot; first_of(row): the state in front of slot 0; front(s): h_s stands in b1, the
  * restart applied, and is only read until the cell has run; behind(s): h'_s stands in b1.  xs is zero beyond KC on entry */
 template <class Words, class First, class Front, class Behind>
 __device__ __forceinline__ void npd_seq_forward(const npb_policy_t &P, const npd_policy_core_t &C, const void *obs, int obs_f64, size_t rows, size_t base, int in_tile,
                                                 int T, float *xs, float *b1, float *b2, float *b3, float *b4, float *b5, int *bad, const int *fresh, int tid,
                                                 Words words, First first_of, Front front, Behind behind) {
-  const int wave = tid >> 6, lane = tid & 63, KC = P.cells, H = C.H, H_pad = (H + 3) & ~3;
+  const int KC = P.cells, H = C.H, H_pad = (H + 3) & ~3;
   for (int s = 0; s < T; s++) {
     if (tid < NPD_POLICY_TILE) words(s);
     __syncthreads();
@@ -102,28 +93,7 @@ __device__ __forceinline__ void npd_seq_forward(const npb_policy_t &P, const npd
         if (fresh[i & (NPD_POLICY_TILE - 1)]) b1[(i / NPD_POLICY_TILE) * NPD_POLICY_STRIDE + (i & (NPD_POLICY_TILE - 1))] = 0.0f;
     __syncthreads();
     front(s);
-    for (int gate = 0; gate < 3; gate++) {
-      npd_policy_layer(C.gate[gate], P.theta, P.padded, xs, b2, -1, wave, lane);
-      npd_policy_layer(C.gate[3 + gate], P.theta, P.padded, b1, b3, -1, (wave + 2) & (NPD_POLICY_WAVES - 1), lane);
-      __syncthreads();
-      for (int i = tid; i < H_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES) {
-        const int j = i / NPD_POLICY_TILE, plant = i & (NPD_POLICY_TILE - 1), o = j * NPD_POLICY_STRIDE + plant;
-        if (gate < 2) {
-          const float a = b2[o] + b3[o];
-          (gate ? b5 : b4)[o] = npd_core_sigma(a, C.gates);
-        } else {
-          const float gated = b4[o] * b3[o];
-          const float a = b2[o] + gated;
-          const float nn = npd_core_tau(a, C.gates);
-          const float h = b1[o];
-          const float away = h - nn;
-          const float kept = b5[o] * away;
-          const float next = nn + kept;
-          b1[o] = j < H && !bad[plant] ? next : 0.0f;
-        }
-      }
-      __syncthreads();
-    }
+    npd_core_cell(P, C, xs, b1, b2, b3, b4, b5, bad, tid);
     behind(s);
   }
 }
@@ -175,13 +145,8 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_seq_kernel(npb_polic
       };
       auto first_of = [&](int row) -> const float * { return src[row] >= 0 ? S.first + (size_t)src[row] * H : nullptr; };
       /* ---- the forward sweep (npd_seq_forward): h'_s into the workspace */
-      npd_seq_forward(P, C, D.obs, D.obs_type, plants, base, in_tile, T, xs, b1, b2, b3, b4, b5, bad, fresh, tid, words, first_of, [](int) {}, [&](int s) {
-        float *out = Q.hseq + ((size_t)s * plants + base) * H;
-        for (int e = tid; e < in_tile * H; e += NPD_POLICY_LANES) {
-          const int row = e / H, k = e - row * H;
-          out[e] = b1[k * NPD_POLICY_STRIDE + row];
-        }
-      });
+      npd_seq_forward(P, C, D.obs, D.obs_type, plants, base, in_tile, T, xs, b1, b2, b3, b4, b5, bad, fresh, tid, words, first_of, [](int) {},
+                      [&](int s) { npd_core_store(Q.hseq + ((size_t)s * plants + base) * H, b1, in_tile, H, tid); });
       /* ---- the backward sweep */
       __syncthreads();
       npd_policy_tile_zero(b0, 0, H_pad, tid);
@@ -222,17 +187,14 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_seq_kernel(npb_polic
           npd_seq_fill(b1, H, H_pad, tid, [&](int row) -> const float * { return row < in_tile && !fresh[row] ? hb + (size_t)row * H : nullptr; });
         }
         __syncthreads();
-        const bool hard = C.gates == NPD_CORE_HARD;
         npd_policy_layer(C.gate[0], P.theta, P.padded, xs, b2, -1, wave, lane);
         npd_policy_layer(C.gate[3], P.theta, P.padded, b1, b6, -1, (wave + 2) & (NPD_POLICY_WAVES - 1), lane);
         __syncthreads();
         for (int i = tid; i < H_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES) {
           const int o = (i / NPD_POLICY_TILE) * NPD_POLICY_STRIDE + (i & (NPD_POLICY_TILE - 1));
           const float a = b2[o] + b6[o];
-          const float q = 0.25f * a;
-          const float y = q + 0.5f;
           b2[o] = npd_core_sigma(a, C.gates);
-          b6[o] = hard && (y < 0.0f || y > 1.0f) ? 1.0f : 0.0f;
+          b6[o] = npd_core_sigma_clamps(a, C.gates) ? 1.0f : 0.0f;
         }
         __syncthreads();
         npd_policy_layer(C.gate[1], P.theta, P.padded, xs, b3, -1, wave, lane);
@@ -241,10 +203,8 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_seq_kernel(npb_polic
         for (int i = tid; i < H_pad * NPD_POLICY_TILE; i += NPD_POLICY_LANES) {
           const int o = (i / NPD_POLICY_TILE) * NPD_POLICY_STRIDE + (i & (NPD_POLICY_TILE - 1));
           const float a = b3[o] + b4[o];
-          const float q = 0.25f * a;
-          const float y = q + 0.5f;
           b3[o] = npd_core_sigma(a, C.gates);
-          if (hard && (y < 0.0f || y > 1.0f)) b6[o] = b6[o] + 2.0f;
+          if (npd_core_sigma_clamps(a, C.gates)) b6[o] = b6[o] + 2.0f;
         }
         __syncthreads();
         npd_policy_layer(C.gate[2], P.theta, P.padded, xs, b4, -1, wave, lane);
@@ -263,24 +223,10 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_ppo_seq_kernel(npb_polic
           const float dn = dh * omz;
           const float dz = dh * u;
           const float direct = dh * z;
-          float dan, daz, dr, dar;
-          if (hard) {
-            dan = an < -1.0f || an > 1.0f ? 0.0f : dn;
-            dr = dan * ghn;
-            const float qz = dz * 0.25f, qr = dr * 0.25f;
-            daz = flags & 2 ? 0.0f : qz;
-            dar = flags & 1 ? 0.0f : qr;
-          } else {
-            const float sq = nn * nn;
-            const float slope = 1.0f - sq;
-            dan = dn * slope;
-            dr = dan * ghn;
-            const float sz = z * omz;
-            daz = dz * sz;
-            const float omr = 1.0f - r;
-            const float sr = r * omr;
-            dar = dr * sr;
-          }
+          const float dan = npd_core_tau_slope(dn, an, nn, C.gates);
+          const float dr = dan * ghn;
+          const float daz = npd_core_sigma_slope(dz, (flags & 2) != 0, z, C.gates);
+          const float dar = npd_core_sigma_slope(dr, (flags & 1) != 0, r, C.gates);
           const float dghn = dan * r;
           const bool dead = j >= H || bad[plant] != 0;
           b2[o] = dead ? 0.0f : dar;
@@ -329,39 +275,21 @@ __global__ __launch_bounds__(NPD_POLICY_LANES) void npb_segment_starts_kernel(np
   auto first_of = [&](int row) -> const float * { return row < in_tile ? G.first + (base + row) * H : nullptr; };
   npd_seq_forward(P, C, G.obs, G.obs_f64, n_plants, base, in_tile, G.t, xs, buf[0], buf[1], buf[2], buf[3], buf[4], bad, fresh, tid, words, first_of, [&](int s) {
     if (s == 0 || s % G.every) return;
-    float *out = G.starts + ((size_t)(s / G.every) * n_plants + base) * H;
-    for (int e = tid; e < in_tile * H; e += NPD_POLICY_LANES) {
-      const int row = e / H, k = e - row * H;
-      out[e] = buf[0][k * NPD_POLICY_STRIDE + row];
-    }
+    npd_core_store(G.starts + ((size_t)(s / G.every) * n_plants + base) * H, buf[0], in_tile, H, tid);
   }, [](int) {});
 }
 
 /* ---- the launchers */
-static npd_ppo_run_t npd_ppo_seq_run(const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M, const npb_ppo_seq_t *S) {
-  return npd_ppo_run(O, D, M, (int)(((int64_t)S->plants + D->rows_per_chain - 1) / D->rows_per_chain));
-}
-static void npd_ppo_seq_launch(const npb_policy_t *P, const npd_policy_core_t *C, const npb_ppo_desc_t *D, const npd_ppo_run_t &R, const npb_ppo_seq_t *S,
-                               const npb_ppo_segments_t *G, float *hseq, hipStream_t stream) {
+extern "C" void npb_launch_ppo_grad_seq(const npb_policy_t *P, const npd_policy_core_t *C, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M,
+                                        const npb_ppo_seq_t *S, const npb_ppo_segments_t *G, double n, double *out, hipStream_t stream) {
+  const npd_ppo_run_t R = npd_ppo_run(O, D, M, (int)(((int64_t)S->plants + D->rows_per_chain - 1) / D->rows_per_chain), n);
   npd_ppo_seq_run_t Q = {};
-  Q.S = *S; Q.hseq = hseq; Q.chunks = G ? G->chunks : 0;
+  Q.S = *S; Q.hseq = S->hidden ? S->hidden : O->hseq; Q.chunks = G ? G->chunks : 0;
   const int cap = D->max_blocks > 0 ? D->max_blocks : 2048;
   const dim3 grid((unsigned)(R.n_chains < cap ? R.n_chains : cap)), block(NPD_POLICY_LANES);
   if (npd_policy_small(P, C->H)) hipLaunchKernelGGL((npb_ppo_seq_kernel<NPD_POLICY_SMALL_CELLS, NPD_POLICY_SMALL_WIDTH>), grid, block, 0, stream, *P, *C, R, Q);
   else hipLaunchKernelGGL((npb_ppo_seq_kernel<NPB_FEATURES_CELLS_MAX, NPB_POLICY_WIDTH_MAX>), grid, block, 0, stream, *P, *C, R, Q);
-}
-extern "C" void npb_launch_ppo_grad_seq(const npb_policy_t *P, const npd_policy_core_t *C, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M,
-                                        const npb_ppo_seq_t *S, const npb_ppo_segments_t *G, hipStream_t stream) {
-  const npd_ppo_run_t R = npd_ppo_seq_run(O, D, M, S);
-  npd_ppo_seq_launch(P, C, D, R, S, G, S->hidden ? S->hidden : O->hseq, stream);
-  npb_launch_ppo_reduce(P, O, &R, stream);
-}
-extern "C" void npb_launch_ppo_shard_sums_seq(const npb_policy_t *P, const npd_policy_core_t *C, const npb_ppo_t *O, const npb_ppo_desc_t *D, const npb_ppo_more_t *M,
-                                              const npb_ppo_seq_t *S, const npb_ppo_segments_t *G, int64_t count_total, double *out, hipStream_t stream) {
-  npd_ppo_run_t R = npd_ppo_seq_run(O, D, M, S);
-  R.n = (double)count_total;
-  npd_ppo_seq_launch(P, C, D, R, S, G, S->hidden ? S->hidden : O->hseq, stream);
-  npb_launch_ppo_shard_reduce(P, &R, out, stream);
+  npb_launch_ppo_reduce(P, O, &R, out, stream);
 }
 extern "C" void npb_launch_segment_starts(const npb_policy_t *P, const npd_policy_core_t *C, const void *obs, int obs_f64, int t, int n_plants, int every,
                                           const int32_t *episode, const uint8_t *ended, float *starts, hipStream_t stream) {

@@ -2299,30 +2299,79 @@ class BatchedPlantEnv:
         ``max_blocks``.  ``clip_vf`` > 0 clips the value loss around ``value_old`` (float32 [count]; by default the batch's extras slot
         the policy was set with for ``"value"``).  ``nuclear_sim_amd.ppo.gradient`` is the same in numpy: bit for bit with relu when fed
         the device's ``ratio``."""
-        d, held = self._ppo_desc(batch, clip, vf_coef, ent_coef, max_grad_norm, rows_per_chain, max_blocks)
-        more, held_more = self._ppo_more(batch, d.count, clip_vf, value_old)
-        held = held + held_more
-        pol = self._pol
-        out = {}
-        with torch.cuda.device(self.device):
-            if diagnostics:
-                out = {"logp_new": torch.zeros(d.count, dtype=torch.float32, device=self.device),
-                       "value_new": torch.zeros(d.count, dtype=torch.float32, device=self.device),
-                       "ratio": torch.zeros(d.count, dtype=torch.float64, device=self.device)}
-                d.logp_new, d.value_new, d.ratio = out["logp_new"].data_ptr(), out["value_new"].data_ptr(), out["ratio"].data_ptr()
-            out["grad"] = torch.zeros(pol["theta"].numel(), dtype=torch.float32, device=self.device)
-            out["stats"] = torch.zeros(_lib.PPO_STATS, dtype=torch.float64, device=self.device)
-            if hasattr(self.L, "npb_policy_get_stats_more"):
-                out["more"] = torch.zeros(_lib.PPO_STATS_MORE, dtype=torch.float64, device=self.device)
-        if more is None:
-            _lib.check(self.L.npb_policy_grad(self._h, ctypes.byref(d), self._stream()), self._h)
+        return self._ppo_grad(self._ppo_request(batch, clip, vf_coef, ent_coef, max_grad_norm, rows_per_chain, max_blocks, clip_vf, value_old), diagnostics)
+
+    def _ppo_request(self, batch, clip, vf_coef, ent_coef, max_grad_norm, per_chain, max_blocks=0, clip_vf=0.0, value_old=None, kl_limit=0.0, sequences=False,
+                     what="training through time"):
+        """THE REQUEST of one minibatch, what every training call below hands to ``_ppo_call``: ``d`` (``_ppo_desc``), ``more``
+        (``_ppo_more``; None with every option off), ``seq`` and ``seg`` (``_ppo_seq``; None for rows, ``seg`` None for whole
+        sequences) and ``held``, the ONE list of every tensor a descriptor points into: whoever launches keeps that list.
+        ``sequences``: a minibatch of sequences or segments, not of rows; ``what``: the caller's name in the refusal of a policy without a core"""
+        d, held = self._ppo_desc(batch, clip, vf_coef, ent_coef, max_grad_norm, per_chain, max_blocks)
+        more, held_more = self._ppo_more(batch, d.count, clip_vf, value_old, kl_limit)
+        seq = seg = None
+        if sequences:
+            self._policy_cell(what)
+            seq, seg, held_seq = self._ppo_seq(batch, d)
+            held_more = held_more + held_seq
+        return {"d": d, "more": more, "seq": seq, "seg": seg, "held": held + held_more}
+
+    def _ppo_call(self, op, req, *tail) -> None:
+        """THE ONE MAP from (operation, kind) to the entry point: ``op`` is ``"grad"``, ``"update"`` or ``"shard_sums"``; the kind is the
+        request's -- rows (the plain / ``_more`` split of ``grad`` and ``update`` lives here), whole sequences (``_seq``) or segments
+        (``_segments``).  ``tail``: the operation's own arguments behind the descriptors.  The request's tensors stay alive on the env
+        while the launches read them"""
+        d, more, seq, seg = (None if req[k] is None else ctypes.byref(req[k]) for k in ("d", "more", "seq", "seg"))
+        if seq is not None:
+            name, args = "npb_policy_%s_%s" % (op, "seq" if seg is None else "segments"), [more, seq] + ([] if seg is None else [seg])
+        elif op == "shard_sums" or more is not None:
+            name, args = "npb_policy_" + op + ("" if op == "shard_sums" else "_more"), [more]
         else:
-            _lib.check(self.L.npb_policy_grad_more(self._h, ctypes.byref(d), ctypes.byref(more), self._stream()), self._h)
-        _lib.check(self.L.npb_policy_get_grad(self._h, ctypes.c_void_p(out["grad"].data_ptr()), self._stream()), self._h)
-        _lib.check(self.L.npb_policy_get_stats(self._h, ctypes.c_void_p(out["stats"].data_ptr()), self._stream()), self._h)
-        if "more" in out:
-            _lib.check(self.L.npb_policy_get_stats_more(self._h, ctypes.c_void_p(out["more"].data_ptr()), self._stream()), self._h)
-        pol["ppo_held"] = held      # (alive while the launches read them)
+            name, args = "npb_policy_" + op, []
+        _lib.check(getattr(self.L, name)(self._h, d, *args, *tail, self._stream()), self._h)
+        self._pol["ppo_held"] = req["held"]
+
+    def _ppo_outputs(self, names=("grad", "stats", "more")) -> dict:
+        """what the last gradient, update or combine left on the handle, copied on the stream into fresh device tensors (npb_policy_get_grad,
+        _get_stats, _get_stats_more): nothing read back"""
+        sizes = {"grad": (self._pol["theta"].numel(), torch.float32, "npb_policy_get_grad"), "stats": (_lib.PPO_STATS, torch.float64, "npb_policy_get_stats"),
+                 "more": (_lib.PPO_STATS_MORE, torch.float64, "npb_policy_get_stats_more")}
+        out = {}
+        for name in names:
+            count, dtype, getter = sizes[name]
+            if hasattr(self.L, getter):
+                with torch.cuda.device(self.device):
+                    out[name] = torch.zeros(count, dtype=dtype, device=self.device)
+                _lib.check(getattr(self.L, getter)(self._h, ctypes.c_void_p(out[name].data_ptr()), self._stream()), self._h)
+        return out
+
+    def _ppo_grad(self, req, diagnostics) -> dict:
+        """the gradient of a request, rows or sequences: the diagnostics' tensors in the minibatch's own shape, the call, the outputs"""
+        d, seq = req["d"], req["seq"]
+        shape = (d.count,) if seq is None else (seq.t, seq.plants)
+        out = {}
+        if diagnostics:
+            with torch.cuda.device(self.device):
+                out = {"logp_new": torch.zeros(shape, dtype=torch.float32, device=self.device), "value_new": torch.zeros(shape, dtype=torch.float32, device=self.device),
+                       "ratio": torch.zeros(shape, dtype=torch.float64, device=self.device)}
+                if seq is not None:
+                    out["hidden"] = torch.zeros(shape + (self._pol["spec"]["core"],), dtype=torch.float32, device=self.device)
+                    seq.hidden = out["hidden"].data_ptr()
+            d.logp_new, d.value_new, d.ratio = out["logp_new"].data_ptr(), out["value_new"].data_ptr(), out["ratio"].data_ptr()
+        self._ppo_call("grad", req)
+        out.update(self._ppo_outputs())
+        return out
+
+    def _ppo_shard_sums(self, batch, count_total, clip, vf_coef, per_chain, clip_vf, value_old, out, max_blocks, sequences) -> torch.Tensor:
+        """a shard's sums of a minibatch of rows or of sequences into ``out``, a fresh row where the caller brings none"""
+        L = self.policy_shard_size()
+        req = self._ppo_request(batch, clip, vf_coef, 0.0, 0.0, per_chain, max_blocks, clip_vf, value_old, sequences=sequences)
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = torch.zeros(L, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or out.numel() != L or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous float64 tensor of %d elements on %s" % (L, self.device))
+        self._ppo_call("shard_sums", req, int(count_total), ctypes.c_void_p(out.data_ptr()))
         return out
 
     def policy_adam(self, lr: float = 3e-4, betas=(0.9, 0.999), eps: float = 1e-5) -> None:
@@ -2347,18 +2396,7 @@ class BatchedPlantEnv:
         nothing read back.  ``out``: a caller's contiguous float64 [L] row to write into (a row of a [W, L] buffer: that is how one
         handle accumulates several minibatches into one Adam step).  The handle's gradient and statistics are left as they were.
         ``nuclear_sim_amd.ppo.shard_sums`` is the same in numpy: bit for bit with relu when fed the device's ``ratio``."""
-        L = self.policy_shard_size()
-        d, held = self._ppo_desc(batch, clip, vf_coef, 0.0, 0.0, rows_per_chain, max_blocks)
-        more, held_more = self._ppo_more(batch, d.count, clip_vf, value_old)
-        if out is None:
-            with torch.cuda.device(self.device):
-                out = torch.zeros(L, dtype=torch.float64, device=self.device)
-        elif out.dtype != torch.float64 or out.numel() != L or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("out must be a contiguous float64 tensor of %d elements on %s" % (L, self.device))
-        _lib.check(self.L.npb_policy_shard_sums(self._h, ctypes.byref(d), None if more is None else ctypes.byref(more), int(count_total),
-                                                ctypes.c_void_p(out.data_ptr()), self._stream()), self._h)
-        self._pol["ppo_held"] = held + held_more      # (alive while the launches read them)
-        return out
+        return self._ppo_shard_sums(batch, count_total, clip, vf_coef, rows_per_chain, clip_vf, value_old, out, max_blocks, False)
 
     def _ppo_shards(self, shards, count_total, ent_coef, max_grad_norm, kl_limit=0.0):
         """the npb_ppo_shards_t of a contiguous device float64 [W, L] tensor"""
@@ -2387,16 +2425,9 @@ class BatchedPlantEnv:
         ``policy_grad`` returns them, device tensors, nothing read back"""
         pol = self._on("_pol")
         s = self._ppo_shards(shards, count_total, ent_coef, max_grad_norm)
-        with torch.cuda.device(self.device):
-            out = {"grad": torch.zeros(pol["theta"].numel(), dtype=torch.float32, device=self.device),
-                   "stats": torch.zeros(_lib.PPO_STATS, dtype=torch.float64, device=self.device),
-                   "more": torch.zeros(_lib.PPO_STATS_MORE, dtype=torch.float64, device=self.device)}
         _lib.check(self.L.npb_policy_combine_shards(self._h, ctypes.byref(s), self._stream()), self._h)
-        _lib.check(self.L.npb_policy_get_grad(self._h, ctypes.c_void_p(out["grad"].data_ptr()), self._stream()), self._h)
-        _lib.check(self.L.npb_policy_get_stats(self._h, ctypes.c_void_p(out["stats"].data_ptr()), self._stream()), self._h)
-        _lib.check(self.L.npb_policy_get_stats_more(self._h, ctypes.c_void_p(out["more"].data_ptr()), self._stream()), self._h)
         pol["shards_held"] = shards
-        return out
+        return self._ppo_outputs()
 
     # ------------------------------------------------------------------ training through time
     def _ppo_seq(self, batch, d):
@@ -2484,55 +2515,23 @@ class BatchedPlantEnv:
         back-propagation through time: every sequence is one segment, started from the stored state of ``policy_segments`` (or the
         batch's own ``first`` = starts [chunks, n, H]) and differentiated within itself only; ``plants_per_chain`` counts segments.
         ``nuclear_sim_amd.recurrent.gradient_segments`` is the same in numpy."""
-        d, held = self._ppo_desc(batch, clip, vf_coef, ent_coef, max_grad_norm, plants_per_chain, max_blocks)
-        more, held_more = self._ppo_more(batch, d.count, clip_vf, value_old)
-        pol = self._policy_cell("policy_grad_sequences()")
-        s, seg, held_seq = self._ppo_seq(batch, d)
-        t, count = s.t, s.plants
-        out = {}
-        with torch.cuda.device(self.device):
-            if diagnostics:
-                out = {"logp_new": torch.zeros((t, count), dtype=torch.float32, device=self.device),
-                       "value_new": torch.zeros((t, count), dtype=torch.float32, device=self.device),
-                       "ratio": torch.zeros((t, count), dtype=torch.float64, device=self.device),
-                       "hidden": torch.zeros((t, count, pol["spec"]["core"]), dtype=torch.float32, device=self.device)}
-                d.logp_new, d.value_new, d.ratio, s.hidden = out["logp_new"].data_ptr(), out["value_new"].data_ptr(), out["ratio"].data_ptr(), out["hidden"].data_ptr()
-            out["grad"] = torch.zeros(pol["theta"].numel(), dtype=torch.float32, device=self.device)
-            out["stats"] = torch.zeros(_lib.PPO_STATS, dtype=torch.float64, device=self.device)
-            out["more"] = torch.zeros(_lib.PPO_STATS_MORE, dtype=torch.float64, device=self.device)
-        if seg is None:
-            _lib.check(self.L.npb_policy_grad_seq(self._h, ctypes.byref(d), None if more is None else ctypes.byref(more), ctypes.byref(s), self._stream()), self._h)
-        else:
-            _lib.check(self.L.npb_policy_grad_segments(self._h, ctypes.byref(d), None if more is None else ctypes.byref(more), ctypes.byref(s),
-                                                       ctypes.byref(seg), self._stream()), self._h)
-        _lib.check(self.L.npb_policy_get_grad(self._h, ctypes.c_void_p(out["grad"].data_ptr()), self._stream()), self._h)
-        _lib.check(self.L.npb_policy_get_stats(self._h, ctypes.c_void_p(out["stats"].data_ptr()), self._stream()), self._h)
-        _lib.check(self.L.npb_policy_get_stats_more(self._h, ctypes.c_void_p(out["more"].data_ptr()), self._stream()), self._h)
-        pol["ppo_held"] = held + held_more + held_seq      # (alive while the launches read them)
-        return out
+        return self._ppo_grad(self._ppo_request(batch, clip, vf_coef, ent_coef, max_grad_norm, plants_per_chain, max_blocks, clip_vf, value_old,
+                                                sequences=True, what="policy_grad_sequences()"), diagnostics)
 
     def policy_shard_sums_sequences(self, batch, count_total: int, clip: float = 0.2, vf_coef: float = 0.5, plants_per_chain: int = 32,
                                     clip_vf: float = 0.0, value_old=None, out=None, max_blocks: int = 0) -> torch.Tensor:
         """``policy_shard_sums`` for a policy with a core (npb_policy_shard_sums_seq): this shard's pinned double sums of one update
         over ``count_total`` CELLS (t * plants of every shard) from a ``unit="plant"`` minibatch; ``policy_apply_shards`` and
         ``policy_combine_shards`` take the vectors.  ``nuclear_sim_amd.recurrent.shard_sums`` is the same in numpy."""
-        L = self.policy_shard_size()
-        d, held = self._ppo_desc(batch, clip, vf_coef, 0.0, 0.0, plants_per_chain, max_blocks)
-        more, held_more = self._ppo_more(batch, d.count, clip_vf, value_old)
-        s, seg, held_seq = self._ppo_seq(batch, d)
-        if out is None:
-            with torch.cuda.device(self.device):
-                out = torch.zeros(L, dtype=torch.float64, device=self.device)
-        elif out.dtype != torch.float64 or out.numel() != L or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("out must be a contiguous float64 tensor of %d elements on %s" % (L, self.device))
-        if seg is None:
-            _lib.check(self.L.npb_policy_shard_sums_seq(self._h, ctypes.byref(d), None if more is None else ctypes.byref(more), ctypes.byref(s), int(count_total),
-                                                        ctypes.c_void_p(out.data_ptr()), self._stream()), self._h)
-        else:      # (a segment minibatch: its "every" selects the segment entry point)
-            _lib.check(self.L.npb_policy_shard_sums_segments(self._h, ctypes.byref(d), None if more is None else ctypes.byref(more), ctypes.byref(s),
-                                                             ctypes.byref(seg), int(count_total), ctypes.c_void_p(out.data_ptr()), self._stream()), self._h)
-        self._pol["ppo_held"] = held + held_more + held_seq      # (alive while the launches read them)
-        return out
+        return self._ppo_shard_sums(batch, count_total, clip, vf_coef, plants_per_chain, clip_vf, value_old, out, max_blocks, True)
+
+    def _shard_units(self, unit, seg_every, advantages):
+        """``(units, cells a unit)``: the units of this shard that ``rollout_minibatches`` cuts into minibatches -- plants of t cells each,
+        recorded cells, or segments of ``seg_every`` cells each"""
+        t = self._last_advantages(self._on("_roll"), advantages)[2]
+        if unit == "plant":
+            return self.n, t
+        return (t * self.n, 1) if seg_every is None else (recurrent.chunks_of(t, seg_every) * self.n, seg_every)
 
     @staticmethod
     def _update_counts(cells, batch_size, epochs, drop_last):
@@ -2603,11 +2602,9 @@ class BatchedPlantEnv:
             if len({len(c) for c in counts}) != 1:
                 raise ValueError("shard_cells: the shards make different numbers of updates (%r) under batch_size %d: shards with different "
                                  "numbers of updates are not supported" % ([len(c) for c in counts], int(batch_size)))
-            t = self._last_advantages(self._on("_roll"), minibatches.get("advantages"))[2]
-            own = self.n if unit == "plant" else (t * self.n if seg_every is None else recurrent.chunks_of(t, seg_every) * self.n)
+            own, per = self._shard_units(unit, seg_every, minibatches.get("advantages"))      # (the shards record in lockstep: one `per` for all)
             if own not in cells:
                 raise ValueError("shard_cells %r does not hold this shard's own %d cells" % (cells, own))
-            per = t if unit == "plant" else (1 if seg_every is None else seg_every)      # (a plant is t rows, a segment every: the shards record in lockstep)
             totals = [per * sum(c[i] for c in counts) for i in range(len(counts[0]))]
         if global_moments:
             if exchange is None:
@@ -2620,10 +2617,8 @@ class BatchedPlantEnv:
         rates = None
         if callable(lr) or isinstance(lr, (list, tuple, np.ndarray)):
             # the number of updates, as rollout_minibatches cuts them (its batches are views of one buffer: they cannot be listed first)
-            t = self._last_advantages(self._on("_roll"), minibatches.get("advantages"))[2]
-            N = self.n if unit == "plant" else (t * self.n if seg_every is None else recurrent.chunks_of(t, seg_every) * self.n)
-            B = min(int(batch_size), N)
-            updates = int(epochs) * (N // B if minibatches.get("drop_last") else -(-N // B))
+            N = self._shard_units(unit, seg_every, minibatches.get("advantages"))[0]
+            updates = len(self._update_counts(N, batch_size, epochs, bool(minibatches.get("drop_last"))))
             rates = [float(lr(i, updates)) for i in range(updates)] if callable(lr) else [float(x) for x in lr]
             if len(rates) != updates:
                 raise ValueError("lr has %d values and the call makes %d updates" % (len(rates), updates))
@@ -2642,40 +2637,21 @@ class BatchedPlantEnv:
                         epoch0 = batch["epoch"]
                         self.policy_refresh_segments()
                 rate = float(lr) if rates is None else rates[i]
-                held = held_more = []
                 if totals is None:
-                    d, held = self._ppo_desc(batch, clip, vf_coef, ent_coef, max_grad_norm, rows_per_chain)
-                    m, held_more = self._ppo_more(batch, d.count, clip_vf, None, kl_limit)
-                    if sequences:
-                        s, seg, held_seq = self._ppo_seq(batch, d)
-                        held = held + held_seq
-                with torch.cuda.device(self.device):
-                    row = torch.zeros(_lib.PPO_STATS, dtype=torch.float64, device=self.device)
-                    if more:
-                        mores.append(torch.zeros(_lib.PPO_STATS_MORE, dtype=torch.float64, device=self.device))
-                if totals is not None:
-                    vec = self.policy_shard_sums_sequences(batch, totals[i], clip, vf_coef, rows_per_chain, clip_vf) if sequences else \
-                        self.policy_shard_sums(batch, totals[i], clip, vf_coef, rows_per_chain, clip_vf)
-                    held = pol["ppo_held"] + [vec]
+                    self._ppo_call("update", self._ppo_request(batch, clip, vf_coef, ent_coef, max_grad_norm, rows_per_chain, 0, clip_vf, None, kl_limit, sequences),
+                                   rate, b1, b2, eps)
+                else:
+                    vec = self._ppo_shard_sums(batch, totals[i], clip, vf_coef, rows_per_chain, clip_vf, None, None, 0, sequences)
+                    pol["ppo_held"] = pol["ppo_held"] + [vec]
                     every = exchange(vec)
                     if not isinstance(every, torch.Tensor) or every.shape != (len(cells), vec.numel()):
                         raise ValueError("exchange must return the [%d, %d] tensor of every shard's sums" % (len(cells), vec.numel()))
                     self.policy_apply_shards(every.contiguous(), totals[i], ent_coef, max_grad_norm, rate, (b1, b2), eps, kl_limit)
-                elif sequences and seg is not None:
-                    _lib.check(self.L.npb_policy_update_segments(self._h, ctypes.byref(d), None if m is None else ctypes.byref(m), ctypes.byref(s),
-                                                                 ctypes.byref(seg), rate, b1, b2, eps, self._stream()), self._h)
-                elif sequences:
-                    _lib.check(self.L.npb_policy_update_seq(self._h, ctypes.byref(d), None if m is None else ctypes.byref(m), ctypes.byref(s), rate, b1, b2, eps,
-                                                            self._stream()), self._h)
-                elif m is None:
-                    _lib.check(self.L.npb_policy_update(self._h, ctypes.byref(d), rate, b1, b2, eps, self._stream()), self._h)
-                else:
-                    _lib.check(self.L.npb_policy_update_more(self._h, ctypes.byref(d), ctypes.byref(m), rate, b1, b2, eps, self._stream()), self._h)
-                _lib.check(self.L.npb_policy_get_stats(self._h, ctypes.c_void_p(row.data_ptr()), self._stream()), self._h)
+                got = self._ppo_outputs(("stats", "more") if more else ("stats",))
+                pol["moved"] = True
+                rows.append(got["stats"])
                 if more:
-                    _lib.check(self.L.npb_policy_get_stats_more(self._h, ctypes.c_void_p(mores[-1].data_ptr()), self._stream()), self._h)
-                pol["moved"], pol["ppo_held"] = True, held + held_more
-                rows.append(row)
+                    mores.append(got["more"])
         finally:
             if kl_limit:      # (the one read-back; and whatever was refused above, nothing stays armed)
                 applied = ctypes.c_uint32()

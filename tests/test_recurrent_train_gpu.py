@@ -284,3 +284,125 @@ def test_refusals_by_name():
     assert off.L.npb_policy_update_seq(off._h, ctypes.byref(d), None, ctypes.byref(s), 1e-3, 0.9, 0.999, 1e-5, None) != 0
     assert b"npb_policy_update_seq: the policy has no core" in off.L.npb_last_error(off._h)
     off.close()
+
+
+@pytest.mark.parametrize("gates, activation", [("hard", "relu"), ("soft", "tanh")], ids=["hard-relu", "soft-tanh"])
+def test_the_three_statements_of_the_cell_agree_device_against_device(gates, activation):
+    """The step's launch, the training kernel's forward sweep and the refresh kernel run one cell: after a collect under unchanged parameters
+    the hidden states they produce are the same bits, soft gates included (no tolerance: the device against itself).  33 plants (two tiles,
+    the second one row wide), 5 feature cells (the k extension to 8), H = 5 (padded to 8), 4 slots, a stored state in front of every slot,
+    no autoreset: no restart, so the state in front of slot s + 1 is h' of slot s"""
+    from nuclear_sim_amd.env import BatchedPlantEnv
+    n, t, H = 33, 4, 5
+    env = BatchedPlantEnv(n, dt=DT)
+    env.set_features(_columns(5), stack=1, dtype=F32)
+    env.set_controls(AXES[:3])
+    env.set_rollout(t, extras=2)
+    a, c, log_std = _weights(12, H, 3, (7,), (9, 6))
+    env.set_policy(a, c, log_std, activation=activation, seed=21, extras=("value", "logp"), core=_core(13, 5, H), gates=gates)
+    env.policy_segments(1)
+    env.rollout_begin()
+    env.collect(t)
+    r = env.rollout()
+    assert r["t"] == t and np.isfinite(_np(r["obs"])[:t]).all() and not recurrent.restarts(_np(r["episode"])[:t], _np(r["ended"])[:t])[1:].any()
+    zeros = torch.zeros((t, n), dtype=torch.float32, device=env.device)
+    batch = {"obs": r["obs"][:t], "act": r["act"][:t], "logp_old": r["extra"][:t, :, 1].contiguous(), "adv": zeros, "ret": zeros}
+    hidden = _np(env.policy_grad_sequences(batch, diagnostics=True)["hidden"])
+    starts = _np(env.policy_rollout_hidden()["starts"])
+    assert hidden.shape == (t, n, H) and starts.shape == (t, n, H) and hidden.any(axis=2).all()
+    for s in range(t - 1):
+        _same(hidden[s], starts[s + 1], "the forward sweep's h' of slot %d against the state the step read in front of slot %d" % (s, s + 1))
+    _same(hidden[t - 1], env.policy_hidden(), "the forward sweep's last h' against the live state")
+    env.policy_rollout_hidden()["starts"][1:].fill_(7.25)
+    env.policy_refresh_segments()
+    _same(env.policy_rollout_hidden()["starts"], starts, "the refresh kernel's rows against the recorded ones")
+    env.close()
+
+
+def test_one_table_over_the_update_and_shard_entry_points():
+    """Refusals only, no kernel runs: the gate rule of the five update calls, the three shard-sum calls' own refusals, and rows against
+    sequences on a handle with a core and on one without.  Every row names its entry point"""
+    from nuclear_sim_amd.env import BatchedPlantEnv
+    env, P = _setup(2, 33, 5, 1, 5, (7,), (9, 6))
+    batch = _batch(env, P)
+    off = BatchedPlantEnv.action_test("oil_top_off", range(4), dt=DT)
+    off.set_features(_columns(5), stack=1, dtype=F32)
+    off.set_controls(AXES[:3])
+    a, c, log_std = _weights(1, 5, 3, (7,), (7,))
+    off.set_policy(a, c, log_std, activation="relu", deterministic=True)
+    flat = {k: batch[k].reshape((-1,) + tuple(batch[k].shape[2:])) for k in ("obs", "act", "logp_old", "adv", "ret")}
+    ref, adam = ctypes.byref, (1e-3, 0.9, 0.999, 1e-5)
+    rows_d, held_rows = off._ppo_desc(flat, 0.2, 0.5, 0.0, 0.5, 32)
+    seq_d, held_d = env._ppo_desc(batch, 0.2, 0.5, 0.0, 0.5, 32)
+    s, none, held_s = env._ppo_seq(batch, seq_d)
+    g = _lib.NpbPpoSegments()
+    g.every, g.chunks = s.t, 1
+    assert none is None and rows_d.count == seq_d.count == T * 33
+    gated, plain, shards = _lib.NpbPpoMore(), _lib.NpbPpoMore(), {k: _lib.NpbPpoShards() for k in (0.0, 0.03)}
+    gated.kl_limit = 0.03
+    for k, v in shards.items():
+        v.kl_limit = k
+    outs = {h: torch.zeros(h.policy_shard_size(), dtype=torch.float64, device=h.device) for h in (env, off)}
+
+    def refused(h, name, words, *args, by=None):
+        """the call is refused in these words, under its own name (by: the exported check's name, where a shared check speaks)"""
+        assert getattr(h.L, name)(h._h, *args, None) != 0, name
+        why = h.L.npb_last_error(h._h)
+        assert why.startswith((by or name).encode() + b": ") and words in why, (name, words, why)
+
+    def update(name, m, seq=ref(s)):
+        """the arguments of an update call that takes options m; seq: the sequence calls' descriptor (None: a NULL one)"""
+        return {"npb_policy_update_more": (ref(rows_d), m), "npb_policy_update_seq": (ref(seq_d), m, seq),
+                "npb_policy_update_segments": (ref(seq_d), m, seq, ref(g))}[name] + adam
+
+    def shard(name, m, total, out, seq=ref(s)):
+        d = rows_d if name == "npb_policy_shard_sums" else seq_d
+        tail = (total, None if out is None else ctypes.c_void_p(out.data_ptr()))
+        return {"npb_policy_shard_sums": (ref(d), m), "npb_policy_shard_sums_seq": (ref(d), m, seq), "npb_policy_shard_sums_segments": (ref(d), m, seq, ref(g))}[name] + tail
+    total = T * 33
+    # ---- rows against sequences: the row-wise calls on the handle with a core, the sequence calls on the one without
+    order, no_core = b"rows carry no order", b"the policy has no core"
+    refused(env, "npb_policy_grad", order, ref(seq_d))
+    refused(env, "npb_policy_grad_more", order, ref(seq_d), ref(plain))
+    refused(env, "npb_policy_update", order, ref(seq_d), *adam)
+    refused(env, "npb_policy_update_more", order, ref(seq_d), ref(plain), *adam)
+    refused(env, "npb_policy_shard_sums", order, ref(seq_d), None, total, ctypes.c_void_p(outs[env].data_ptr()))
+    refused(off, "npb_policy_grad_seq", no_core, ref(seq_d), None, ref(s))
+    refused(off, "npb_policy_grad_segments", no_core, ref(seq_d), None, ref(s), ref(g))
+    for name in ("npb_policy_update_seq", "npb_policy_update_segments"):
+        refused(off, name, no_core, *update(name, None))
+    for name in ("npb_policy_shard_sums_seq", "npb_policy_shard_sums_segments"):
+        refused(off, name, no_core, *shard(name, None, total, outs[off]))
+    # ---- a NULL sequence descriptor is never read as rows: without a core "no core" under the call's own name, with one the check's words
+    null_seq = b"a NULL sequence descriptor"
+    for h, words, by in ((off, no_core, None), (env, null_seq, "npb_policy_grad_seq")):
+        refused(h, "npb_policy_grad_seq", words, ref(seq_d), None, None, by=by)
+        refused(h, "npb_policy_grad_segments", words, ref(seq_d), None, None, ref(g), by=by)
+        for name in ("npb_policy_update_seq", "npb_policy_update_segments"):
+            refused(h, name, words, *update(name, None, seq=None), by=by)
+        for name in ("npb_policy_shard_sums_seq", "npb_policy_shard_sums_segments"):
+            refused(h, name, words, *shard(name, None, total, outs[h], seq=None), by=by)
+    # ---- the shard-sum calls' own refusals, each on the handle of its kind
+    for h, name in ((off, "npb_policy_shard_sums"), (env, "npb_policy_shard_sums_seq"), (env, "npb_policy_shard_sums_segments")):
+        refused(h, name, b"the gate belongs to the combine", *shard(name, ref(gated), total, outs[h]))
+        refused(h, name, b"count_total < desc->count", *shard(name, None, total - 1, outs[h]))
+        refused(h, name, b"a NULL or misaligned out", *shard(name, None, total, None))
+    # ---- the gate rule: kl_limit > 0 outside the pair, kl_limit == 0 inside it
+    outside, inside = b"kl_limit > 0 outside npb_policy_train_begin", b"kl_limit == 0 between"
+    refused(off, "npb_policy_update_more", outside, *update("npb_policy_update_more", ref(gated)))
+    for name in ("npb_policy_update_seq", "npb_policy_update_segments"):
+        refused(env, name, outside, *update(name, ref(gated)))
+    for h in (env, off):
+        refused(h, "npb_policy_apply_shards", outside, ref(shards[0.03]), *adam)
+        assert h.L.npb_policy_train_begin(h._h, None) == 0
+    refused(off, "npb_policy_update", inside, ref(rows_d), *adam)
+    refused(off, "npb_policy_update_more", inside, *update("npb_policy_update_more", ref(plain)))
+    for name in ("npb_policy_update_seq", "npb_policy_update_segments"):
+        refused(env, name, inside, *update(name, None))
+    for h in (env, off):
+        refused(h, "npb_policy_apply_shards", inside, ref(shards[0.0]), *adam)
+        applied = ctypes.c_uint32(7)
+        assert h.L.npb_policy_train_end(h._h, ref(applied), None) == 0 and applied.value == 0
+        refused(h, "npb_policy_train_end", b"no npb_policy_train_begin before it", None)      # nothing stays armed
+        refused(h, "npb_policy_apply_shards", outside, ref(shards[0.03]), *adam)
+        h.close()
